@@ -12,7 +12,11 @@ Workload: --gpus 1 -> cfg3 = BASELINE.json configs[2] (wfi_warehouse, 192 agents
 north star's target is quoted on --, 64 parallel instances: the largest single-GPU configuration);
 --gpus N > 1 -> cfg4 = configs[3]'s per-GPU shard (random+maze mix, 128 agents, 6M, 512 instances per GPU; weak
 scaling: instances shard across ranks with no per-step collective; one metrics all_gather after the timed region).
-A short cfg2 (configs[1], 2M) run rides along at N = 1 as the secondary key "secondary".
+A plain run sets up, warms up, times exactly --steps steps and prints the headline.  --full adds everything else the
+benchmark measures: per-kernel HIP-event timings and the roofline, shader clock / socket power during the timed region, the
+episode-reset cost and, at N = 1, the tokenizer roofline launches, the secondary workloads (cfg2, cfg1, env6M, the cfg4 and cfg5
+shards) and the CPU baseline (the --no-* options trim that set).  --dump-outputs DIR writes what the last timed step returned
+(tokens, actions, positions, episode state, metrics) as float32 DIR/<name>.npy.
 Synthetic data: seeded starts/goals (instance i = seed i) and seeded random-init weights of the named architecture
 (released checkpoints need network).  Inputs are resident in HBM before the timed region; nothing crosses PCIe inside it.
 Rank 0 prints ONE JSON line.
@@ -620,6 +624,35 @@ def traffic_for(kernel_key, rows_per_launch=None):
             "source": f"profiles/{TRAFFIC_FILE} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes of this command, FETCH_SIZE x2 gfx950 correction)"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: at most 64 MiB of .npy payload per run
+
+
+def dump_outputs(w, metrics, out_dir, seed=0):
+    """What the last timed step returned to its caller (BatchedRunner.step + the env state it leaves), as float32 .npy files in
+    out_dir: tokens [rows, 256] (the observations the step generated), actions [rows] (what the policy chose), positions
+    [rows, 2] (after the env step), done [instances], metrics [instances, 6] (all instances of the job).  Rows are this rank's
+    shard; if the tokens would push the payload over DUMP_BUDGET_BYTES, a fixed seeded sample of rows is written for every
+    per-row array and token_rows holds their indices."""
+    run = w["run"]
+    pos, _, done = run.env.sync_state()
+    arrays = {"tokens": run.tokens, "actions": run.actions.reshape(-1), "positions": pos.reshape(-1, 2), "done": done,
+              "metrics": metrics}
+    arrays = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    rows = arrays["tokens"].shape[0]
+    per_row = sum(a[0].nbytes for k, a in arrays.items() if k in ("tokens", "actions", "positions"))
+    rest = sum(a.nbytes for k, a in arrays.items() if k not in ("tokens", "actions", "positions"))
+    keep = max(1, (DUMP_BUDGET_BYTES - rest) // (per_row + 8))
+    if keep < rows:
+        idx = np.sort(np.random.default_rng(seed).choice(rows, int(keep), replace=False))
+        for k in ("tokens", "actions", "positions"):
+            arrays[k] = arrays[k][idx]
+        arrays["token_rows"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -630,6 +663,11 @@ def main():
     ap.add_argument("--precision", default=os.environ.get("MGPT_BENCH_PRECISION", "f16x3"), choices=["f32", "f16x3", "bf16"])
     ap.add_argument("--instances", type=int, default=0, help="instances per GPU (default: the workload's)")
     ap.add_argument("--chunk-rows", type=int, default=0, help="rows per forward launch (default 16384; 4096 for the 85M shape)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel timings and roofline, clock / power, reset cost, "
+                         "tokenizer legs, secondary workloads, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-tokenizer-leg", action="store_true", help="skip the >=1e5-row tokenizer roofline launch")
     ap.add_argument("--no-secondary", action="store_true", help="skip the short cfg2 run reported under 'secondary'")
@@ -681,15 +719,18 @@ def main():
 
     name = a.workload or ("cfg3" if world == 1 else "cfg4")
     w = build_workload(name, a.precision, rank, world, local_rank, a.instances, chunk_rows=a.chunk_rows)
-    use_prof = not a.no_prof
-    dt, prof_raw = timed_steps(w, a.steps, a.warmup, world, use_prof, coll_dev, sample_clock=local_rank, collective=collective)
+    use_prof = a.full and not a.no_prof
+    dt, prof_raw = timed_steps(w, a.steps, a.warmup, world, use_prof, coll_dev, sample_clock=(local_rank if a.full else None),
+                               collective=collective)
     per_rank = per_rank_records(w, a.steps, rank, world, local_rank, coll_dev, collective)
     prof, prof_full, prof_last = fold_last(prof_raw)
     local_metrics = w["run"].metrics().to(coll_dev)
     metrics = gather_metrics(local_metrics, w["n_total"], rank, world, force=collective)       # the job's one collective
     gathered_on = str(metrics.device) if collective else None
     torch.cuda.synchronize()
-    reset_ms = reset_cost(w) if rank == 0 else None          # (after the timed region and the metrics: the reset starts a new episode)
+    if a.dump_outputs and rank == 0:                         # (before reset_cost below, which starts a new episode)
+        dump_outputs(w, metrics, a.dump_outputs)
+    reset_ms = reset_cost(w) if (rank == 0 and a.full) else None   # (after the timed region and the metrics: the reset starts a new episode)
     eff_prec = None
     if rank == 0 and a.precision == "f16x3":
         try:
@@ -714,11 +755,7 @@ def main():
                           "gflop_per_agent_step": f_total / 1e9,
                           "mean_ISR_after_run": float(metrics[:, 1].mean().item()),
                           "max_episode_steps": w["max_steps"],
-                          "timed_region_crosses_episode_boundary": bool(a.warmup + a.steps > w["max_steps"]),
-                          "reset_ms_per_episode": reset_ms,
-                          "amortised_reset_ms_per_step": (reset_ms / w["max_steps"] if reset_ms is not None else None),
-                          "reset_note": "env reset + tokenizer create_agents (one BFS field per agent, observation_generator.cpp:391-410) of this rank's "
-                                        "shard, HIP-event timed once outside the headline; a default run's timed region ends before max_episode_steps"},
+                          "timed_region_crosses_episode_boundary": bool(a.warmup + a.steps > w["max_steps"])},
                "per_rank": per_rank,
                "effective_precision": ((eff_prec or {}).get("effective_precision") if a.precision == "f16x3" else a.precision),
                "precision_envelope": eff_prec,
@@ -726,6 +763,12 @@ def main():
                        "unreachable offline, so the 1e-5 logit parity of the f16x3 mode is established on synthetic weights "
                        "(tests/test_gpu_gpt.py) and not on the released ones; the f16x3 figures hold while the loaded checkpoint's precision "
                        "envelope stays 'inside' (effective_precision / precision_envelope: a checkpoint outside it is served by the fp32 kernels)"}
+        if a.full:
+            out["config"].update({
+                "reset_ms_per_episode": reset_ms,
+                "amortised_reset_ms_per_step": (reset_ms / w["max_steps"] if reset_ms is not None else None),
+                "reset_note": "env reset + tokenizer create_agents (one BFS field per agent, observation_generator.cpp:391-410) of this rank's "
+                              "shard, HIP-event timed once outside the headline; a default run's timed region ends before max_episode_steps"})
         if prof:
             cls = class_flops(prof, f_class, margs["n_layer"], rows, prof_full)
             if cls:
@@ -757,13 +800,13 @@ def main():
             out["kernel_ms_per_step_last_layer_launches"] = {k: v[0] / a.steps for k, v in prof_last.items()}
         if w.get("clock_power"):
             out["clock_power"] = dict(w["clock_power"], note="sampled on this GPU between the two barriers of the timed region by a host thread reading hwmon every 20 ms -- the sampler runs DURING the timing (DESIGN section 10: the forward runs at the package power limit)")
-        if world == 1 and not a.no_tokenizer_leg:
+        if a.full and world == 1 and not a.no_tokenizer_leg:
             # SURVEY 8d asks for the tokenizer's HBM roofline on >= 1e5-row launches: cfg4's own per-GPU launch (65 536 rows on
             # per-instance maps, 128 agents: the KP = 2 path) is the headline tokenizer figure; the 524 288-row leg is secondary
             out["roofline_tokenizer_cfg4_shard"] = tokenizer_cfg4_launch(local_rank)
             if name != "cfg4":
                 out["roofline_tokenizer_large"] = tokenizer_large_launch(w["grid"], w["s_ok"], w["g_ok"], n_agents, local_rank)
-        if world == 1 and not a.no_secondary and name != "cfg2":
+        if a.full and world == 1 and not a.no_secondary and name != "cfg2":
             del w
             torch.cuda.empty_cache()
             w2 = build_workload("cfg2", a.precision, 0, 1, local_rank)
@@ -807,7 +850,7 @@ def main():
                                           "note": "the N = 1 point of the multi-GPU (cfg4) curve; `bench.py --gpus 1 --workload cfg4` reproduces it as the headline"}
             if name != "cfg5":
                 out["secondary"]["cfg5_shard"] = secondary_shard("cfg5", "bf16", 3, 1, local_rank, coll_dev)
-        if world == 1 and not a.no_cpu_baseline and name != "cfg4":
+        if a.full and world == 1 and not a.no_cpu_baseline and name != "cfg4":
             out["cpu_baseline"] = cpu_baseline(map_name, n_agents, model)
         print(json.dumps(out), flush=True)
     if collective:

@@ -11,7 +11,7 @@ while [ $# -ge 3 ]; do
   W=$1; P=$2; S=$3; shift 3
   for v in $A $B $A $B; do
     cp gpurun_tmp/lib_$v.so mapf_gpt_amd/csrc/libmapf_gpt_amd.so
-    timeout 600 python bench.py --workload $W --precision $P --steps $S --warmup 2 --no-cpu-baseline --no-secondary --no-tokenizer-leg > $OUT/$v.json 2> $OUT/$v.err
+    timeout 600 python bench.py --workload $W --precision $P --steps $S --warmup 2 --full --no-cpu-baseline --no-secondary --no-tokenizer-leg > $OUT/$v.json 2> $OUT/$v.err
     python - <<PY
 import json
 d = json.loads(open("$OUT/$v.json").read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 OUT=gpurun_out/quick; mkdir -p $OUT
 timeout 1500 python -m pytest ${@:-tests} -q -m gpu -p no:cacheprovider --timeout 900 > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -6 $OUT/pytest_gpu.log
-timeout 600 python bench.py --no-cpu-baseline --no-secondary --no-tokenizer-leg --steps 20 --warmup 4 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 600 python bench.py --full --no-cpu-baseline --no-secondary --no-tokenizer-leg --steps 20 --warmup 4 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/quick/bench.json").read().strip().splitlines()[-1])

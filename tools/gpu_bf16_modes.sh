@@ -5,7 +5,7 @@ export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 OUT=gpurun_out/modes; mkdir -p $OUT
 for spec in "cfg3 bf16 20" "cfg2 bf16 20" "cfg4 bf16 4" "cfg4 f16x3 4"; do
   set -- $spec
-  timeout 600 python bench.py --workload $1 --precision $2 --steps $3 --warmup 2 --no-cpu-baseline --no-secondary --no-tokenizer-leg > $OUT/$1_$2.json 2> $OUT/$1_$2.err
+  timeout 600 python bench.py --workload $1 --precision $2 --steps $3 --warmup 2 --full --no-cpu-baseline --no-secondary --no-tokenizer-leg > $OUT/$1_$2.json 2> $OUT/$1_$2.err
   python - <<PY
 import json
 d = json.loads(open("$OUT/$1_$2.json").read().strip().splitlines()[-1])

@@ -10,10 +10,10 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0          # dmabuf IPC: RCCL across processes
 run() {
     local n=$1 steps=${2:-20} warm=${3:-3}
     if [ "$n" = 1 ]; then
-        python bench.py --gpus 1 --workload cfg4 --steps "$steps" --warmup "$warm" --no-secondary --no-cpu-baseline
+        python bench.py --gpus 1 --workload cfg4 --steps "$steps" --warmup "$warm" --full --no-secondary --no-cpu-baseline
     else
         python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $((29500 + n)) \
-            bench.py --gpus "$n" --steps "$steps" --warmup "$warm"
+            bench.py --gpus "$n" --steps "$steps" --warmup "$warm" --full
     fi
 }
 if [ "$1" = curve ]; then
