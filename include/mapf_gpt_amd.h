@@ -264,7 +264,7 @@ int mgpt_gpt_envelope_probe(mgpt_gpt *gpt, float *out4);
 /* test/debug: event counters of the policy kernels since the last reset (synchronises the device).
  * which 0 = waves of the C = 256 / C = 160 attention kernels that threw a head of the pipelined key-tile loop (one softmax reference
  * per query and head) away and redid it with the exact running-maximum loop, because a half-row sum of exp2(s - ref) left the
- * fp16 range of the P planes (mapf_gpt_amd/csrc/gpt_kernels_c256a.h).  reset != 0 zeroes the counter after reading it. */
+ * fp16 range of the P planes (mapf_gpt_amd/csrc/gpt_kernels_attn_tiles.h).  reset != 0 zeroes the counter after reading it. */
 int mgpt_gpt_debug_counter(int which, uint64_t *value, int reset);
 
 /* mgpt_gpt_act with the RNG step read from device memory when the kernel runs (*d_step): for callers that replay the call

@@ -11,11 +11,9 @@
 #include "common.h"
 #include "gpt_ctx.h"
 #include "gpt_kernels_fast.h"
-#include "gpt_kernels_c256.h"
 #include "gpt_kernels_c256q.h"      // (includes gpt_kernels_c256p.h)
 #include "gpt_kernels_fused16.h"
-#include "gpt_kernels_c256a.h"
-#include "gpt_kernels_c256b.h"      // attn256q_kernel
+#include "gpt_kernels_c256b.h"      // attn256q_kernel (includes gpt_kernels_c256.h)
 #include "gpt_kernels_c160p.h"
 #include "gpt_kernels_c160a.h"
 #include "gpt_kernels_last.h"
@@ -26,54 +24,6 @@ namespace {
 
 constexpr int kT = 256;
 constexpr int kV = MGPT_VOCAB;
-// A/B builds (tools/ab_lib.sh): -DMGPT_AB_ATTN_UNFUSED keeps round 3's attn256_kernel + packed-GEMM out-projection
-#ifdef MGPT_AB_ATTN_UNFUSED
-constexpr bool kAttn256Fused = false;
-#else
-constexpr bool kAttn256Fused = true;
-#endif
-// -DMGPT_AB_NO_LAST1 keeps the last layer on the full attention kernels (attn256_kernel<LAST> / attn_block_kernel<LAST>)
-// -DMGPT_AB_NO_ATTN160O keeps the 2M shape's middle layers on attn_block_kernel
-#ifdef MGPT_AB_NO_ATTN160O
-constexpr bool kAttn160o = false;
-#else
-constexpr bool kAttn160o = true;
-#endif
-// -DMGPT_AB_NO_LN_FOLD keeps ln_pack_kernel in the one-plane packed-GEMM chain
-#ifdef MGPT_AB_NO_LN_FOLD
-constexpr bool kLnFold = false;
-#else
-constexpr bool kLnFold = true;
-#endif
-// -DMGPT_AB_NO_MLP160_HALF keeps 128-token blocks in mlp160p_kernel for every small launch
-// (-DMGPT_AB_NO_MLP160_QUARTER: no 32-token blocks)
-#ifdef MGPT_AB_NO_MLP160_QUARTER
-constexpr bool kMlp160Quarter = false;
-#else
-constexpr bool kMlp160Quarter = true;
-#endif
-#ifdef MGPT_AB_NO_MLP160_HALF
-constexpr bool kMlp160Half = false;
-#else
-constexpr bool kMlp160Half = true;
-#endif
-// -DMGPT_AB_NO_SMALL256 keeps small launches of the 6M shape on the row-per-workgroup kernels
-#ifdef MGPT_AB_NO_SMALL256
-constexpr bool kSmall256 = false;
-#else
-constexpr bool kSmall256 = true;
-#endif
-#ifdef MGPT_AB_NO_LAST1_TAIL
-constexpr bool kLast1Tail = false;
-#else
-constexpr bool kLast1Tail = true;
-#endif
-#ifdef MGPT_AB_NO_LAST1
-constexpr bool kLast1 = false;
-#else
-constexpr bool kLast1 = true;
-#endif
-
 // kSmallRows (gpt_ctx.h): rows up to which the C = 64 / 160 attention block runs head-parallel: beyond ~164 rows of 5 heads the (row, head)
 // workgroups need more rounds on 256 CUs than one workgroup per row takes (25 us against 80 us per workgroup, profiles/r02_cfg1_step_trace.txt)
 
@@ -93,9 +43,10 @@ struct ModeState {          // one precision mode
     uint16_t *vt[2] = {nullptr, nullptr};      // [M][C]
     uint16_t *y[2] = {nullptr, nullptr};       // [M][C]
     uint16_t *hbuf[2] = {nullptr, nullptr};    // [M][4C]
-    // fused MLP (C = 64 / 160): per layer one packed stream [hidden tile][fragment][plane][lane][8]
+    // fused MLP (C = 64 / 160): per layer one packed stream [hidden tile][fragment][plane][lane][8] in the fragment layout of
+    // mlp_fused16_kernel (16 x 16 x 32 MFMA: large calls), and (C = 64) in that of mlp_fused_kernel (32 x 32 x 16 MFMA: small calls)
+    std::vector<uint16_t *> mlp16_pk;
     std::vector<uint16_t *> mlp_pk;
-    std::vector<uint16_t *> mlp16_pk;           // the same packets in the fragment layout of mlp_fused16_kernel (16 x 16 x 32 MFMA: large calls)
     bool mlp_fused = false;
     // C = 256 (6M): mlp256p_kernel's cyclic weight stream in consumption order (LayerNorm gain folded into c_fc), per layer
     // [period step][pair][plane][lane][8], and the scale c_fc * gain was packed with
@@ -105,17 +56,16 @@ struct ModeState {          // one precision mode
     std::vector<float> attn256_inv;            // 1 / scale of the attn256 weight stream (c_attn.weight * ln_1.weight)
     float2 *gelu_lut = nullptr;                // the Phi table of the fused MLP kernels (kGeluLutN pairs)
     std::vector<float2 *> mlp256_lut;          // per layer: the same table times 1 / scale of the layer's c_fc stream (mlp256p_kernel)
-    // C = 256, head size 32 (6M): attn256_kernel's c_attn stream in consumption order, per layer
+    // C = 256, head size 32 (6M): attn256_kernel's c_attn stream in consumption order, per layer (small calls)
     std::vector<uint16_t *> attn256_pk;
     bool attn256 = false;
-    // attn256o_kernel (whole attention block, persistent): c_attn + c_proj stream per layer, and the per-workgroup spill slab
-    std::vector<uint16_t *> attn256o_pk;
-    std::vector<uint16_t *> attn256q_pk;   // the same stream in attn256q_kernel's fragment order (gpt_kernels_c256b.h)
-    unsigned char *attn256o_spill = nullptr;
+    // attn256q_kernel (whole attention block, persistent: gpt_kernels_c256b.h): c_attn + c_proj stream per layer, and the per-workgroup spill slab
+    std::vector<uint16_t *> attn256q_pk;
+    unsigned char *attn256q_spill = nullptr;
     // register-resident LN+QKV (C = 64 / 160): per layer [tile][k-step][plane][lane][8] of c_attn.weight
     std::vector<uint16_t *> qkv_pk;
     bool qkv_fused = false;
-    // out-projection slices per head for attn_block_kernel<PROJ>: [head][out tile][kk][plane][lane][8]
+    // out-projection slices per head for attn_block_kernel: [head][out tile][kk][plane][lane][8]
     std::vector<uint16_t *> proj_pk;
     // last-layer shortcut: new residual rows of token 255 only, [round_up(max_rows, 256)][C] fp32
     float *x_last = nullptr;
@@ -275,16 +225,10 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
             }
             {   // the whole attention block in one persistent kernel: 48 steps of c_attn * ln_1 followed by 16 steps of c_proj
                 const size_t n16o = (size_t)fastk::kA256oPeriod * 8 * NP * 512;
-                m->attn256o_pk.assign(g->L, nullptr);
                 m->attn256q_pk.assign(g->L, nullptr);
                 for (int l = 0; l < g->L; l++) {
-                    MGPT_HIP(hipMalloc(&m->attn256o_pk[l], n16o * sizeof(uint16_t)));
                     const LayerOff &lo = g->layers[l];
                     ProfScope ps(P_PACK, nullptr);
-                    hipLaunchKernelGGL((fastk::pack_attn256o_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kA256oPeriod * 8 * 64, 256)), dim3(256), 0,
-                                       nullptr, g->params + lo.attn_w, g->params + lo.ln1, g->params + lo.proj_w, m->attn256o_pk[l],
-                                       1.0f / m->attn256_inv[l], 1.0f / m->proj[l].inv_scale);
-                    MGPT_LAUNCH_CHECK();
                     MGPT_HIP(hipMalloc(&m->attn256q_pk[l], n16o * sizeof(uint16_t)));
                     hipLaunchKernelGGL((fastk::pack_attn256q_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kA256oPeriod * 8 * 64, 256)), dim3(256), 0,
                                        nullptr, g->params + lo.attn_w, g->params + lo.ln1, g->params + lo.proj_w, m->attn256q_pk[l],
@@ -299,41 +243,42 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
                                        g->params + g->off_wte, g->params + g->off_wpe, g->embed_table, C, kV);
                     MGPT_LAUNCH_CHECK();
                 }
-                MGPT_HIP(hipMalloc(&m->attn256o_spill, (size_t)m->n_cu * 8 * 14 * NP * 1024));
-                MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256o_kernel<T, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, kA256Lds<NP>));
+                MGPT_HIP(hipMalloc(&m->attn256q_spill, (size_t)m->n_cu * 8 * 14 * NP * 1024));
             }
-            MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256_kernel<T, NP, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kA256Lds<NP>));
-            MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256_kernel<T, NP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kA256Lds<NP>));
-            MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256_kernel<T, NP, false, 0, fastk::kA256Stagger, true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, kA256Lds<NP>));
+            MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256_kernel<T, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, kA256Lds<NP>));
         }
     } else if (m->mlp_fused) {
         const size_t frags = C / 16 + 2 * (C / 32), nt = 4 * C / 32;
         const size_t n16 = nt * frags * NP * 512;
-        m->mlp_pk.assign(g->L, nullptr);
+        // (the small calls of C = 160 take mlp160p_kernel, below: mlp_fused_kernel's packets only for C = 64)
+        if (C == 64) m->mlp_pk.assign(g->L, nullptr);
         m->mlp16_pk.assign(g->L, nullptr);
         for (int l = 0; l < g->L; l++) {
-            MGPT_HIP(hipMalloc(&m->mlp_pk[l], n16 * sizeof(uint16_t)));
-            MGPT_HIP(hipMalloc(&m->mlp16_pk[l], n16 * sizeof(uint16_t)));
             const LayerOff &lo = g->layers[l];
             ProfScope ps(P_PACK, nullptr);
-            hipLaunchKernelGGL((fastk::pack_mlp_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(nt * frags * 64), 256)), dim3(256), 0,
-                               nullptr, g->params + lo.fc_w, g->params + lo.proj2_w, m->mlp_pk[l], (int)C,
-                               1.0f / m->fc[l].inv_scale, 1.0f / m->proj2[l].inv_scale);
-            MGPT_LAUNCH_CHECK();
+            if (C == 64) {
+                MGPT_HIP(hipMalloc(&m->mlp_pk[l], n16 * sizeof(uint16_t)));
+                hipLaunchKernelGGL((fastk::pack_mlp_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(nt * frags * 64), 256)), dim3(256), 0,
+                                   nullptr, g->params + lo.fc_w, g->params + lo.proj2_w, m->mlp_pk[l], (int)C,
+                                   1.0f / m->fc[l].inv_scale, 1.0f / m->proj2[l].inv_scale);
+                MGPT_LAUNCH_CHECK();
+            }
+            MGPT_HIP(hipMalloc(&m->mlp16_pk[l], n16 * sizeof(uint16_t)));
             hipLaunchKernelGGL((fastk::pack_mlp16_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(nt * frags * 64), 256)), dim3(256), 0,
                                nullptr, g->params + lo.fc_w, g->params + lo.proj2_w, m->mlp16_pk[l], (int)C,
                                1.0f / m->fc[l].inv_scale, 1.0f / m->proj2[l].inv_scale);
             MGPT_LAUNCH_CHECK();
         }
         const int pkt = (int)(frags * NP * 1024 * 3) + fastk::kGeluLutN * 8;
-#define MGPT_MLP_ATTR(CT_, NW_) \
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp_fused_kernel<T, NP, CT_, NW_, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, pkt)); \
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp_fused_kernel<T, NP, CT_, NW_, CT_>), hipFuncAttributeMaxDynamicSharedMemorySize, pkt)); \
+#define MGPT_MLP16_ATTR(CT_, NW_) \
     MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp_fused16_kernel<T, NP, CT_, NW_, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, pkt))
-        if (C == 160) { MGPT_MLP_ATTR(5, 8); MGPT_MLP_ATTR(5, 4); MGPT_MLP_ATTR(5, 2); }
+#define MGPT_MLP_ATTR(CT_, NW_) \
+    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp_fused_kernel<T, NP, CT_, NW_>), hipFuncAttributeMaxDynamicSharedMemorySize, pkt)); \
+    MGPT_MLP16_ATTR(CT_, NW_)
+        if (C == 160) { MGPT_MLP16_ATTR(5, 8); MGPT_MLP16_ATTR(5, 4); MGPT_MLP16_ATTR(5, 2); }
         else { MGPT_MLP_ATTR(2, 8); MGPT_MLP_ATTR(2, 4); MGPT_MLP_ATTR(2, 2); }
 #undef MGPT_MLP_ATTR
+#undef MGPT_MLP16_ATTR
     }
     m->qkv_fused = (C == 160 || C == 64);
     if (m->qkv_fused) {
@@ -358,13 +303,11 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
             }
             // attn_block_kernel's dynamic LDS limit is a per-device function attribute: set it for this model's device
             const int lds = (int)((size_t)NP * (kT * 80 + 32 * 528) + (size_t)(C / 16) * NP * 1024 * 4);
-#define MGPT_ATTN_LDS(CT_, LAST_, EMB_, HP_)                                                                                      \
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn_block_kernel<T, NP, CT_, true, LAST_, EMB_, HP_>), \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-            if (C == 160) { MGPT_ATTN_LDS(5, false, false, false); MGPT_ATTN_LDS(5, true, false, false); MGPT_ATTN_LDS(5, false, true, false);
-                            MGPT_ATTN_LDS(5, false, false, true); MGPT_ATTN_LDS(5, true, false, true); }
-            else { MGPT_ATTN_LDS(2, false, false, false); MGPT_ATTN_LDS(2, true, false, false); MGPT_ATTN_LDS(2, false, true, false);
-                   MGPT_ATTN_LDS(2, false, false, true); MGPT_ATTN_LDS(2, true, false, true); }
+#define MGPT_ATTN_LDS(CT_, EMB_, HP_)                                                                                            \
+    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn_block_kernel<T, NP, CT_, EMB_, HP_>), hipFuncAttributeMaxDynamicSharedMemorySize, lds))
+            // (C = 160 runs it in small calls only: the persistent attn160o_kernel below serves the large ones)
+            if (C == 160) MGPT_ATTN_LDS(5, false, true);
+            else { MGPT_ATTN_LDS(2, false, false); MGPT_ATTN_LDS(2, true, false); MGPT_ATTN_LDS(2, false, true); }
 #undef MGPT_ATTN_LDS
             // (head_parts -- the heads' partial sums of small launches -- is allocated by the first small launch: forward_chunk)
             if (m->mlp_fused && C == 160) {
@@ -412,8 +355,6 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
                     MGPT_LAUNCH_CHECK();
                 }
                 MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp160p_kernel<T, NP, 5>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             fastk::kM5Lds<NP>));
-                MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp160p_kernel<T, NP, 0>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                              fastk::kM5Lds<NP>));
                 MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp160p_kernel<T, NP, 5, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (fastk::kM5Lds<NP, 2>)));
@@ -501,7 +442,7 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
         // (MGPT_LN_FOLD=0 in the environment keeps the normalised planes: the raw planes round x itself to bf16, so a residual stream whose
         //  per-token mean is many times its standard deviation loses precision that LayerNorm-then-round keeps)
         const char *fold_env = getenv("MGPT_LN_FOLD");
-        m->ln_fold = kLnFold && NP == 1 && !m->mlp_fused && m->apk != nullptr && !(fold_env != nullptr && fold_env[0] == '0');
+        m->ln_fold = NP == 1 && !m->mlp_fused && m->apk != nullptr && !(fold_env != nullptr && fold_env[0] == '0');
         if (m->ln_fold) {
             m->attn_pk2g.assign(g->L, nullptr); m->fc_pk2g.assign(g->L, nullptr); m->attn_cs.assign(g->L, nullptr); m->fc_cs.assign(g->L, nullptr);
             auto packg = [&](std::vector<uint16_t *> &dst, std::vector<float *> &cs, size_t off, size_t goff, size_t R, size_t K, float scale, int l) -> int {
@@ -569,9 +510,8 @@ void free_mode(mgpt_gpt *g, ModeState *m)
     for (auto *p : m->mlp256q_pk) (void)hipFree(p);
     for (auto *p : m->mlp256_lut) (void)hipFree(p);
     for (auto *p : m->attn256_pk) (void)hipFree(p);
-    for (auto *p : m->attn256o_pk) (void)hipFree(p);
     for (auto *p : m->attn256q_pk) (void)hipFree(p);
-    (void)hipFree(m->attn256o_spill);
+    (void)hipFree(m->attn256q_spill);
     (void)hipFree(m->gelu_lut);
     for (auto *p : m->qkv_pk) (void)hipFree(p);
     for (auto *p : m->proj_pk) (void)hipFree(p);
@@ -619,27 +559,6 @@ int launch_gemm16(fastk::GemmArgs a, int C, hipStream_t s)
     return MGPT_OK;
 }
 
-#ifdef MGPT_AB_MLPF_32X32
-constexpr bool kMlpFused16 = false;     // A/B: the fused MLP block of the C = 64 / 160 shapes on the 32 x 32 x 16 MFMA in large calls too
-#else
-constexpr bool kMlpFused16 = true;
-#endif
-#ifdef MGPT_AB_ATTN_32X32
-constexpr bool kAttn256Q = false;       // A/B: the 6M attention block's projections and tail on the 32 x 32 x 16 MFMA (attn256o_kernel) as in rounds 4-5
-#else
-constexpr bool kAttn256Q = true;
-#endif
-#ifdef MGPT_AB_MLP_32X32
-constexpr bool kMlp256Q = false;        // A/B: the 6M MLP block of large calls on mlp256p_kernel (32 x 32 x 16 MFMA) as in rounds 3-4
-#else
-constexpr bool kMlp256Q = true;
-#endif
-#ifdef MGPT_AB_GEMM_32X32
-constexpr bool kGemmPk16 = false;       // A/B: the one-plane packed GEMM on the 32 x 32 x 16 MFMA as in rounds 1-4
-#else
-constexpr bool kGemmPk16 = true;
-#endif
-
 // compute units of the current device (grid of the persistent packed GEMM); asked once
 int gemm_pk_cus()
 {
@@ -669,7 +588,7 @@ int launch_gemm_pk(fastk::GemmArgs a, hipStream_t s, bool half_tiles = false, bo
     // half_tiles (small launches: one environment's rows are 32 tiles of 256 rows per column tile, which leaves most CUs idle): 128-row tiles, 4 waves,
     // two workgroups per CU -- same arithmetic per token (a wave's 64 x 128 sub-tile and its k order do not change)
     const size_t lut_b = lut ? (size_t)fastk::kGeluLutN * 8 : 0;
-    if constexpr (NP == 1 && kGemmPk16) {
+    if constexpr (NP == 1) {
         // one-plane mode: the same GEMM on v_mfma_f32_16x16x32 (gpt_kernels_fast.h: gemm_pk16_kernel), one workgroup per tile
         // -- in LARGE calls only: a 32-row forward is not at the power limit, and there the 12 % more cycles per flop of the small shape show (2.49 -> 2.71 ms);
         // the choice is a property of the call (as for the other small-launch kernels), so every chunk of a call runs the same arithmetic
@@ -756,24 +675,11 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
     // the first attention block forms x = wte[token] + wpe[position] itself (no embedding kernel, no first read of x)
     // ... unless the persistent block kernel of the 2M shape serves the layer (round 6, profiles/r06_ab.txt visit B): embed_tiled_kernel (0.6 ms per 16 384 rows)
     // + attn160o_kernel (4.5 ms) beat attn_block_kernel<EMBED> (5.8 ms), the round-1 kernel the first layer had stayed on because it gathers the embedding
-#if defined(MGPT_AB_EMBED_FUSED_160)
-    const bool persistent160 = false;
-#else
-    const bool persistent160 = attn_block && C == 160 && !head_par && m->attn160o_spill != nullptr && kAttn160o && m->x_tiled;
-#endif
+    const bool persistent160 = attn_block && C == 160 && !head_par && m->attn160o_spill != nullptr && m->x_tiled;
     const bool embed_fused = attn_block && g->L > 1 && !head_par && !persistent160;
     // ... and so does the 6M shape's persistent block kernel in a large call (attn256q_kernel<.., EMB>: from the (position, token) table, round 6)
-#if defined(MGPT_AB_EMBED_KERNEL_256)
-    const bool embed256 = false;
-#else
-    const bool embed256 = m->attn256 && kAttn256Fused && kAttn256Q && g->L > 1 && g->embed_table != nullptr && m->x_tiled &&
-                          !(call_rows <= kSmallRows && rows <= kSmallRows && kSmall256);
-#endif
-#if defined(MGPT_AB_EMBED_KERNEL_160)
-    const bool embed160 = false;
-#else
+    const bool embed256 = m->attn256 && g->L > 1 && g->embed_table != nullptr && m->x_tiled && !(call_rows <= kSmallRows && rows <= kSmallRows);
     const bool embed160 = persistent160 && g->L > 1 && g->embed_table != nullptr;      // ... and the 2M shape's (attn160o_kernel<.., EMB>)
-#endif
     if (embed256 || embed160) {
     } else if (m->x_tiled && !embed_fused) {
         ProfScope ps(P_EMBED, s);
@@ -819,11 +725,11 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
         // last layer: only token 255 is needed downstream (model.py:186) -> compact buffer, MLP and head on `rows` tokens
         const bool last_short = (attn_block || m->pk_gemm) && l == g->L - 1;
         const int rows_pad = ((rows + 255) / 256) * 256;
-        // 6M shape, every layer but the last: attn256o_kernel does the out-projection and the residual add itself
+        // 6M shape, every layer but the last: attn256q_kernel does the out-projection and the residual add itself
         // ... unless the CALL is small (one environment, rows <= kSmallRows): then a row's eight heads run on eight CUs at once
-        // (attn256_kernel<.., HP>, one workgroup per (row, head), y planes) and the packed GEMM projects them (round 5)
-        const bool small256 = m->attn256 && !last_short && call_rows <= kSmallRows && rows <= kSmallRows && kSmall256;
-        const bool proj_fused = m->attn256 && !last_short && kAttn256Fused && !small256;
+        // (attn256_kernel, one workgroup per (row, head), y planes) and the packed GEMM projects them (round 5)
+        const bool small256 = m->attn256 && !last_short && call_rows <= kSmallRows && rows <= kSmallRows;
+        const bool proj_fused = m->attn256 && !last_short && !small256;
         // the packed-GEMM chain (C = 768) in a small call: its residual GEMMs (N = 768: 3 column tiles) are 96 tiles of 256 rows for 32 rows -- 128-row
         // tiles put them on twice the CUs (same arithmetic per token: a wave's 64 x 128 sub-tile and its k order do not change).  One-plane mode: 32-row
         // forward 2.77 -> 2.49 ms (c_proj 70 -> 56 us, out-projection 30 -> 25, q|k + v^T 51 -> 47); in the split mode the 4-wave form has a 3-stage ring and
@@ -831,11 +737,12 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
         const bool small_pk = NP == 1 && m->pk_gemm && !m->attn256 && call_rows <= kSmallRows && rows <= kSmallRows;
         const bool big_call = call_rows > kSmallRows;                      // the one-plane packed GEMMs run on the 16 x 16 x 32 MFMA (launch_gemm_pk)
         // last layer of a launch that fills the chip: the attention block of token 255 alone, without K and V (attn_last1_kernel)
-        const bool last1 = last_short && m->last1_wt != nullptr && m->x_tiled && !head_par && kLast1;
+        const bool last1 = last_short && m->last1_wt != nullptr && m->x_tiled && !head_par;
         // small launch (one environment): the last layer's attention block, its MLP block, ln_f and the head are ONE launch, one
         // workgroup per row (attn_last1_kernel<.., 1, TAIL>), fp32 throughout; logits come straight out of it
-        const bool small_call = head_par || (m->attn256 && call_rows <= kSmallRows && rows <= kSmallRows && kSmall256);
-        const bool last_tail = last_short && small_call && m->last1_wt != nullptr && kLast1 && kLast1Tail;
+        // (every model with last1_wt takes one of these two launches in its last layer: the branches below serve the other layers)
+        const bool small_call = head_par || (m->attn256 && call_rows <= kSmallRows && rows <= kSmallRows);
+        const bool last_tail = last_short && small_call && m->last1_wt != nullptr;
         if (last_tail) {
             ProfScope ps(P_ATTN_LAST, s);
             const float *wk = P + lo.attn_w + (size_t)C * C;
@@ -861,7 +768,7 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
             else if (C == 256) MGPT_LAST1(256); else if (C == 160) MGPT_LAST1(160); else MGPT_LAST1(64);
 #undef MGPT_LAST1
             MGPT_LAUNCH_CHECK();
-        } else if (attn_block && C == 160 && !head_par && !last_short && !(embed_fused && l == 0) && m->attn160o_spill != nullptr && kAttn160o) {
+        } else if (persistent160 && !last_short) {
             // ---- the 2M shape's attention block as one persistent kernel (attn160o_kernel) ----
             ProfScope ps(P_ATTN, s);
             if (embed160 && l == 0)
@@ -873,55 +780,36 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
             MGPT_LAUNCH_CHECK();
         } else if (attn_block) {
             // ---- LN1 + QKV + attention + out-projection + residual in one kernel: q, k, v, y stay on chip ----
-            ProfScope ps(last_short ? P_ATTN_LAST : P_ATTN, s);
+            // (C = 160 comes here in small calls only: its large calls take attn160o_kernel above)
+            ProfScope ps(P_ATTN, s);
             const size_t lds = (size_t)NP * (kT * 80 + 32 * 528) + (size_t)(C / 16) * NP * 1024 * 4;   // K, V^T planes + 4 weight packet slots
-#define MGPT_ATTN_BLOCK(CT_, LAST_, EMB_, HP_)                                                                                              \
-    hipLaunchKernelGGL((fastk::attn_block_kernel<T, NP, CT_, true, LAST_, EMB_, HP_>), dim3((unsigned)(HP_ ? rows * g->nh : rows)), dim3(512), \
-                       lds, s, g->x, P + lo.ln1, m->qkv_pk[l], m->attn[l].inv_scale, m->y[0], m->y[1], g->nh, scale_log2e, m->proj_pk[l],     \
+#define MGPT_ATTN_BLOCK(CT_, EMB_, HP_)                                                                                                     \
+    hipLaunchKernelGGL((fastk::attn_block_kernel<T, NP, CT_, EMB_, HP_>), dim3((unsigned)(HP_ ? rows * g->nh : rows)), dim3(512), lds, s, g->x, \
+                       P + lo.ln1, m->qkv_pk[l], m->attn[l].inv_scale, m->y[0], m->y[1], g->nh, scale_log2e, m->proj_pk[l],                  \
                        m->proj[l].inv_scale, m->stats, m->x_last, d_tokens, P + g->off_wte, P + g->off_wpe, m->head_parts, part_stride)
-            const bool emb = embed_fused && l == 0;
-            if (head_par) {
-                if (C == 160) { if (last_short) MGPT_ATTN_BLOCK(5, true, false, true); else MGPT_ATTN_BLOCK(5, false, false, true); }
-                else { if (last_short) MGPT_ATTN_BLOCK(2, true, false, true); else MGPT_ATTN_BLOCK(2, false, false, true); }
-            } else if (C == 160) { if (last_short) MGPT_ATTN_BLOCK(5, true, false, false); else if (emb) MGPT_ATTN_BLOCK(5, false, true, false); else MGPT_ATTN_BLOCK(5, false, false, false); }
-            else { if (last_short) MGPT_ATTN_BLOCK(2, true, false, false); else if (emb) MGPT_ATTN_BLOCK(2, false, true, false); else MGPT_ATTN_BLOCK(2, false, false, false); }
+            if (head_par) { if (C == 160) MGPT_ATTN_BLOCK(5, false, true); else MGPT_ATTN_BLOCK(2, false, true); }
+            else if (embed_fused && l == 0) MGPT_ATTN_BLOCK(2, true, false);
+            else MGPT_ATTN_BLOCK(2, false, false);
 #undef MGPT_ATTN_BLOCK
             MGPT_LAUNCH_CHECK();
-            if (head_par && last_short) {
-                // new row of token 255 = its residual row + the heads' contributions (compact partial sums), padding rows zero
-                hipLaunchKernelGGL(fastk::gather_last_kernel, dim3((unsigned)cdiv64((int64_t)rows_pad * (C / 4), 256)), dim3(256), 0, s, g->x, m->x_last, rows,
-                                   rows_pad, C, 1, m->head_parts, g->nh, part_stride);
-                MGPT_LAUNCH_CHECK();
-            }
-        } else if (m->attn256 && proj_fused) {
+        } else if (proj_fused) {
             // ---- the whole attention block (LN1, QKV, attention, out-projection, residual) in one persistent kernel: q, k, v, y stay on chip ----
             ProfScope ps(P_ATTN, s);
-            // (gpt_kernels_c256b.h: the projection steps and the tail on v_mfma_f32_16x16x32, the attention phase as it was)
-            if (kAttn256Q && embed256 && l == 0)
+            // (gpt_kernels_c256b.h: the projection steps and the tail on v_mfma_f32_16x16x32)
+            if (embed256 && l == 0)
                 hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true>), dim3((unsigned)std::min(rows, m->n_cu)), dim3(512), (size_t)kA256Lds<NP>, s, g->x,
-                                   m->attn256q_pk[l], m->attn256_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn256o_spill, rows,
+                                   m->attn256q_pk[l], m->attn256_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn256q_spill, rows,
                                    (unsigned long long *)nullptr, d_tokens, g->embed_table);
-            else if (kAttn256Q)
-                hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP>), dim3((unsigned)std::min(rows, m->n_cu)), dim3(512), (size_t)kA256Lds<NP>, s, g->x,
-                                   m->attn256q_pk[l], m->attn256_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn256o_spill, rows,
-                                   (unsigned long long *)nullptr);
             else
-                hipLaunchKernelGGL((fastk::attn256o_kernel<T, NP>), dim3((unsigned)std::min(rows, m->n_cu)), dim3(512), (size_t)kA256Lds<NP>, s, g->x,
-                                   m->attn256o_pk[l], m->attn256_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn256o_spill, rows,
+                hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP>), dim3((unsigned)std::min(rows, m->n_cu)), dim3(512), (size_t)kA256Lds<NP>, s, g->x,
+                                   m->attn256q_pk[l], m->attn256_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn256q_spill, rows,
                                    (unsigned long long *)nullptr);
             MGPT_LAUNCH_CHECK();
-        } else if (m->attn256) {
-            // ---- LN1 + QKV + attention in one kernel (q, k, v stay on chip) -> y operand planes for the out-projection ----
-            ProfScope ps(last_short ? P_ATTN_LAST : P_ATTN, s);
-            if (last_short)
-                hipLaunchKernelGGL((fastk::attn256_kernel<T, NP, true>), dim3((unsigned)rows), dim3(512), (size_t)kA256Lds<NP>, s, g->x,
-                                   m->attn256_pk[l], m->attn256_inv[l], scale_log2e, m->y_last, (unsigned long long *)nullptr);
-            else if (small256)
-                hipLaunchKernelGGL((fastk::attn256_kernel<T, NP, false, 0, fastk::kA256Stagger, true>), dim3((unsigned)rows * 8), dim3(512), (size_t)kA256Lds<NP>, s,
-                                   g->x, m->attn256_pk[l], m->attn256_inv[l], scale_log2e, m->y[0], (unsigned long long *)nullptr);
-            else
-                hipLaunchKernelGGL((fastk::attn256_kernel<T, NP, false>), dim3((unsigned)rows), dim3(512), (size_t)kA256Lds<NP>, s, g->x,
-                                   m->attn256_pk[l], m->attn256_inv[l], scale_log2e, m->y[0], (unsigned long long *)nullptr);
+        } else if (small256) {
+            // ---- LN1 + QKV + attention, one workgroup per (row, head): q, k, v stay on chip -> y operand planes for the out-projection ----
+            ProfScope ps(P_ATTN, s);
+            hipLaunchKernelGGL((fastk::attn256_kernel<T, NP>), dim3((unsigned)rows * 8), dim3(512), (size_t)kA256Lds<NP>, s,
+                               g->x, m->attn256_pk[l], m->attn256_inv[l], scale_log2e, m->y[0], (unsigned long long *)nullptr);
             MGPT_LAUNCH_CHECK();
         } else if (m->pk_gemm) {
             // (folded LayerNorm: m->apk already holds the raw rows -- from the embedding or from the residual epilogue before -- and
@@ -993,9 +881,9 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
                     // small launch: 64-token blocks, four waves with a SIMD each (mlp256p_kernel<.., NPAIR = 2>): twice the workgroups
                     hipLaunchKernelGGL((fastk::mlp256p_kernel<T, NP, 0, 2>), dim3((unsigned)std::min(2 * n_blocks, m->n_cu)), dim3(256), (size_t)fastk::kMPLds<NP>, s,
                                        mlp_x, m->mlp256_pk[l], m->mlp256_inv1[l], m->proj2[l].inv_scale, m->mlp256_lut[l], 2 * n_blocks, (unsigned long long *)nullptr);
-                else if (small256 || !kMlp256Q)
-                hipLaunchKernelGGL((fastk::mlp256p_kernel<T, NP>), dim3((unsigned)std::min(n_blocks, m->n_cu)), dim3(512), (size_t)fastk::kMPLds<NP>, s,
-                                   mlp_x, m->mlp256_pk[l], m->mlp256_inv1[l], m->proj2[l].inv_scale, m->mlp256_lut[l], n_blocks, (unsigned long long *)nullptr);
+                else if (small256)
+                    hipLaunchKernelGGL((fastk::mlp256p_kernel<T, NP>), dim3((unsigned)std::min(n_blocks, m->n_cu)), dim3(512), (size_t)fastk::kMPLds<NP>, s,
+                                       mlp_x, m->mlp256_pk[l], m->mlp256_inv1[l], m->proj2[l].inv_scale, m->mlp256_lut[l], n_blocks, (unsigned long long *)nullptr);
                 else
                     // large calls: the same block on v_mfma_f32_16x16x32 (gpt_kernels_c256q.h: 13-15 % more f16 flops per second at the power limit; 2.66 -> 2.45 ms
                     // per 4096-row launch).  Small calls are not power-limited and keep the 32 x 32 x 16 kernel; the choice is a property of the call
@@ -1006,17 +894,13 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
                     if ((rc = launch_row_stats(g->x, m->stats, M, C, s)) != MGPT_OK) return rc;
                 }
             } else if (head_par && C == 160) {
-                // small launch: persistent producer / consumer blocks of 128 tokens (two waves per SIMD); the heads' partial sums are folded
-                // in (the last layer's compact rows were folded by gather_last_kernel)
+                // small launch: persistent producer / consumer blocks of 128 tokens (two waves per SIMD); the heads' partial sums are folded in
                 const int n_blocks = (int)(mlp_M / 128);
-                if (last_short)
-                    hipLaunchKernelGGL((fastk::mlp160p_kernel<T, NP, 0>), dim3((unsigned)std::min(n_blocks, m->n_cu)), dim3(512), (size_t)fastk::kM5Lds<NP>, s,
-                                       mlp_x, m->mlp160_pk[l], m->mlp160_inv1[l], m->proj2[l].inv_scale, m->gelu_lut, n_blocks, (const float *)nullptr, (int64_t)0);
-                else if (mlp_M <= (int64_t)32 * m->n_cu && kMlp160Half && kMlp160Quarter)
+                if (mlp_M <= (int64_t)32 * m->n_cu)
                     // ... or 32-token blocks, one producer and one consumer wave (cfg1's 8192 tokens: one block per CU)
                     hipLaunchKernelGGL((fastk::mlp160p_kernel<T, NP, 5, 1>), dim3((unsigned)std::min((int)(mlp_M / 32), m->n_cu)), dim3(128), (size_t)(fastk::kM5Lds<NP, 1>), s,
                                        mlp_x, m->mlp160_pk[l], m->mlp160_inv1[l], m->proj2[l].inv_scale, m->gelu_lut, (int)(mlp_M / 32), m->head_parts, part_stride);
-                else if (mlp_M <= (int64_t)64 * m->n_cu && kMlp160Half)
+                else if (mlp_M <= (int64_t)64 * m->n_cu)
                     // so few tokens that 128-token blocks would leave CUs idle (one environment): 64-token blocks, one wave per SIMD
                     hipLaunchKernelGGL((fastk::mlp160p_kernel<T, NP, 5, 2>), dim3((unsigned)std::min((int)(mlp_M / 64), m->n_cu)), dim3(256), (size_t)(fastk::kM5Lds<NP, 2>), s,
                                        mlp_x, m->mlp160_pk[l], m->mlp160_inv1[l], m->proj2[l].inv_scale, m->gelu_lut, (int)(mlp_M / 64), m->head_parts, part_stride);
@@ -1027,8 +911,8 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
                 const size_t lds = (size_t)(C / 16 + 2 * (C / 32)) * NP * 1024 * 3 + fastk::kGeluLutN * 8;
                 // 32 tokens per wave whatever the block size: small launches (cfg1: 32 rows = 32 blocks of 256 tokens) take
                 // fewer waves per block so that the tokens spread over more CUs; results do not depend on the choice
-#define MGPT_MLP_(CT_, NW_, NF_)                                                                                                     \
-    hipLaunchKernelGGL((fastk::mlp_fused_kernel<T, NP, CT_, NW_, NF_>), dim3((unsigned)(mlp_M / (32 * NW_))), dim3(64 * NW_), lds, s, mlp_x, \
+#define MGPT_MLP_(CT_, NW_)                                                                                                          \
+    hipLaunchKernelGGL((fastk::mlp_fused_kernel<T, NP, CT_, NW_>), dim3((unsigned)(mlp_M / (32 * NW_))), dim3(64 * NW_), lds, s, mlp_x, \
                        P + lo.ln2, m->mlp_pk[l], m->fc[l].inv_scale, m->proj2[l].inv_scale, last_short ? nullptr : m->stats, (int)mlp_M, m->gelu_lut, \
                        m->head_parts, part_stride)
     // large calls: the same block on v_mfma_f32_16x16x32 (gpt_kernels_fused16.h); small calls (head_par) are not power-limited and keep the 32 x 32 x 16 kernel
@@ -1036,13 +920,12 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
     hipLaunchKernelGGL((fastk::mlp_fused16_kernel<T, NP, CT_, NW_, 0>), dim3((unsigned)(mlp_M / (32 * NW_))), dim3(64 * NW_), lds, s, mlp_x, \
                        P + lo.ln2, m->mlp16_pk[l], m->fc[l].inv_scale, m->proj2[l].inv_scale, last_short ? nullptr : m->stats, (int)mlp_M, m->gelu_lut, \
                        (const float *)nullptr, (int64_t)0)
-#define MGPT_MLP(CT_, NW_) do { if (fold_parts) MGPT_MLP_(CT_, NW_, CT_); else if (!head_par && kMlpFused16) MGPT_MLP16_(CT_, NW_); else MGPT_MLP_(CT_, NW_, 0); } while (0)
+#define MGPT_MLP(CT_, NW_) do { if (head_par) MGPT_MLP_(CT_, NW_); else MGPT_MLP16_(CT_, NW_); } while (0)
                 // (one wave per workgroup -- 256 workgroups for cfg1's 8192 tokens -- is slower: 63 us per launch against 52, round 4)
                 const int nw = (mlp_M >= (int64_t)256 * m->n_cu) ? 8 : (mlp_M >= (int64_t)128 * m->n_cu ? 4 : 2);
-                // (the heads' partial sums = n_head buffers, and n_head == C / 32 for the shapes of this path;
-                //  the last layer's compact rows were folded by gather_last_kernel)
-                const bool fold_parts = head_par && !last_short;
-                if (C == 160) { if (nw == 8) MGPT_MLP(5, 8); else if (nw == 4) MGPT_MLP(5, 4); else MGPT_MLP(5, 2); }
+                // (head_par: mlp_fused_kernel folds in the heads' partial sums = n_head buffers, and n_head == C / 32 for the shapes of this path;
+                //  C = 160 comes here in large calls only)
+                if (C == 160) { if (nw == 8) MGPT_MLP16_(5, 8); else if (nw == 4) MGPT_MLP16_(5, 4); else MGPT_MLP16_(5, 2); }
                 else { if (nw == 8) MGPT_MLP(2, 8); else if (nw == 4) MGPT_MLP(2, 4); else MGPT_MLP(2, 2); }
 #undef MGPT_MLP
 #undef MGPT_MLP16_

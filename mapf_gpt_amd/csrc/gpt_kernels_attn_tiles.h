@@ -1,4 +1,4 @@
-// gpt_kernels_attn_tiles.h -- the attention phase of the persistent attention-block kernels (attn256o_kernel, attn160o_kernel), gfx950:
+// gpt_kernels_attn_tiles.h -- the attention phase of the persistent attention-block kernels (attn256q_kernel, attn160o_kernel), gfx950:
 // one wave, 32 queries (lane (r, h) = query r, half h of a key tile), the head's K planes [plane][key][KROW] and V^T planes
 // [plane][d][VROW] in LDS, q as the B operand of S^T = K Q^T in registers (qf), head size 32, 256 keys in eight tiles of 32.
 //     attention_tiles        the pipelined key-tile loop (round 5), q and k in EXPONENT units (a score is log2 of its softmax weight up
@@ -10,16 +10,10 @@
 #pragma once
 #include "gpt_kernels_c256p.h"
 
-// VALU instructions placed behind each MFMA of the pipelined loop's sub-blocks B1 / B2 (A/B knobs: tools/bench_probes/check_attn256o.hip)
-#ifndef MGPT_ATT_NVB1
-#define MGPT_ATT_NVB1 10
-#endif
-#ifndef MGPT_ATT_NVB2
-#define MGPT_ATT_NVB2 6
-#endif
-
 namespace mgpt {
 namespace fastk {
+
+constexpr int kAttNvb1 = 10, kAttNvb2 = 6;     // VALU instructions placed behind each MFMA of the pipelined loop's sub-blocks B1 / B2
 
 // waves that threw a head of the pipelined loop away and redid it with the exact loop; read by mgpt_gpt_debug_counter (tests: zero
 // on the synthetic N(0, 0.02) checkpoints, non-zero when the scores are made to spread)
@@ -46,7 +40,7 @@ __device__ __forceinline__ float other_half_sum(float v) { float a, b2; half_swa
 }  // namespace attn_tiles_detail
 
 // The EXACT loop (rounds 2-4): online softmax with a running maximum per query, one key tile after the other (6 S MFMAs, the softmax
-// arithmetic, 6 PV MFMAs).  Since round 5 the FALLBACK of attention_tiles (and the whole phase under -DMGPT_AB_ATTN_CLUMPED): a wave
+// arithmetic, 6 PV MFMAs).  Since round 5 the FALLBACK of attention_tiles: a wave
 // whose scores outgrow the fp16 range of the P planes redoes its head here.
 template <class T, int NP, int KROW, int VROW, int HS>
 __device__ __forceinline__ void attention_exact_tiles(unsigned kr_addr, unsigned vr_addr, const u32x4 (&qf)[2][2], float sc2, f32x16 &o, float &l_run)
@@ -166,14 +160,7 @@ __device__ __forceinline__ void attention_tiles(unsigned kr_addr, unsigned vr_ad
     u32x4 kf[2][2], vf[2][2], pf[2][2];
     f32x16 sA, sB;                             // score blocks of the even / odd key tiles
     constexpr int NM = NP == 2 ? 3 : 1;        // MFMAs per k-step
-#ifdef MGPT_ABL_ATT                                        // tools/bench_probes/check_attn256o.hip only (results are wrong): 1 = no MFMAs, 2 = no softmax arithmetic in the phase
-    auto amfma = [&](u32x4 a, u32x4 b2, f32x16 c) {
-        if constexpr ((MGPT_ABL_ATT & 1) != 0) { asm volatile("" : "+v"(c)); return c; }
-        else return T::mfma(a, b2, c);
-    };
-#else
     auto amfma = [&](u32x4 a, u32x4 b2, f32x16 c) { return T::mfma(a, b2, c); };
-#endif
     auto amma = [&](const u32x4 (&a)[2], const u32x4 (&b2)[2], f32x16 c) {     // = mma<T, NP>: small terms first
         if (NP == 2) { c = amfma(a[1], b2[0], c); c = amfma(a[0], b2[1], c); }
         return amfma(a[0], b2[0], c);
@@ -236,7 +223,6 @@ __device__ __forceinline__ void attention_tiles(unsigned kr_addr, unsigned vr_ad
         constexpr bool FIRSTT = kt == 0, LASTT = kt == kT / 32 - 1, HAS2 = kt + 2 < kT / 32;
         // ---- B1a: the second k-step of the previous tile's PV; the first exponentials ----
         // (read issued after V^T k-step 1 of tile kt - 1: K of tile kt + 1)
-#if !defined(MGPT_ABL_ATT) || (MGPT_ABL_ATT & 2) == 0
         if constexpr (!FIRSTT) {
             lgkm(std::integral_constant<int, LASTT ? 0 : LK::value>{});
             o = amma(vf[1], pf[1], o);
@@ -248,9 +234,6 @@ __device__ __forceinline__ void attention_tiles(unsigned kr_addr, unsigned vr_ad
             place(std::integral_constant<int, NM>{}, std::integral_constant<int, 4>{});
             asm volatile("" : "+v"(o));
         }
-#else
-        if constexpr (!FIRSTT) { lgkm(std::integral_constant<int, LASTT ? 0 : LK::value>{}); o = amma(vf[1], pf[1], o); __builtin_amdgcn_sched_barrier(0); }
-#endif
         // (V^T k-step 0 of THIS tile is requested only here, and K of tile kt + 2 only after B2: requested earlier their registers
         //  were live next to pf[1] / vf[1] above resp. next to the three P planes of B2, and xn paid for them with scratch)
         load_v(kt_c, I0{});
@@ -261,19 +244,13 @@ __device__ __forceinline__ void attention_tiles(unsigned kr_addr, unsigned vr_ad
             nxt = amma(kf[0], qf[0], nmb);
             nxt = amma(kf[1], qf[1], nxt);
         }
-#if !defined(MGPT_ABL_ATT) || (MGPT_ABL_ATT & 2) == 0
 #pragma unroll
         for (int g = FIRSTT ? 0 : 4; g < 16; g++) {
             cur[g] = __builtin_amdgcn_exp2f(cur[g]);
             l_part += cur[g];
         }
         pack_octet(cur, 0, pf[0]);
-#else
-        l_part += cur[3];
-#pragma unroll
-        for (int e = 0; e < 4; e++) { pf[0][0][e] = __builtin_bit_cast(unsigned, cur[e]); pf[0][1][e] = __builtin_bit_cast(unsigned, cur[4 + e]); }
-#endif
-        place(std::integral_constant<int, LASTT ? 0 : 2 * NM>{}, std::integral_constant<int, MGPT_ATT_NVB1>{});
+        place(std::integral_constant<int, LASTT ? 0 : 2 * NM>{}, std::integral_constant<int, kAttNvb1>{});
         if constexpr (!LASTT) asm volatile("" : "+v"(nxt));
         load_v(kt_c, I1{});
         // ---- B2: split of octet 1 under the first k-step of this tile's PV ----
@@ -284,13 +261,8 @@ __device__ __forceinline__ void attention_tiles(unsigned kr_addr, unsigned vr_ad
             for (int g = 0; g < 16; g++) o[g] = 0.f;
         }
         o = amma(vf[0], pf[0], o);
-#if !defined(MGPT_ABL_ATT) || (MGPT_ABL_ATT & 2) == 0
         pack_octet(cur, 1, pf[1]);
-#else
-#pragma unroll
-        for (int e = 0; e < 4; e++) { pf[1][0][e] = __builtin_bit_cast(unsigned, cur[8 + e]); pf[1][1][e] = __builtin_bit_cast(unsigned, cur[12 + e]); }
-#endif
-        place(std::integral_constant<int, NM>{}, std::integral_constant<int, MGPT_ATT_NVB2>{});
+        place(std::integral_constant<int, NM>{}, std::integral_constant<int, kAttNvb2>{});
         asm volatile("" : "+v"(o));
         if constexpr (HAS2) load_k(std::integral_constant<int, HAS2 ? kt + 2 : 0>{});
     };

@@ -1,6 +1,6 @@
 // gpt_kernels_c160a.h -- the whole attention block for n_embd = 160, 5 heads of 32 (MAPF-GPT-2M), gfx950:
 //     x <- x + c_proj(attention(LayerNorm(x)))                         (model.py:46-72, 102)
-// the structure of attn256o_kernel (gpt_kernels_c256a.h) at this shape: PERSISTENT (grid = number of CUs, a workgroup walks
+// the structure of attn256q_kernel (gpt_kernels_c256b.h) at this shape: PERSISTENT (grid = number of CUs, a workgroup walks
 // rows b = blockIdx.x, + gridDim.x, ...), a wave owns 32 tokens and keeps their normalised rows as MFMA operand planes
 // (10 k-steps: 80 registers), q, k, v, the scores and y never leave the chip, and the out-projection is a TAIL over the y
 // planes (heads 0-3 parked in a per-workgroup spill slab, head 4 kept in registers) so that the residual stream is read
@@ -22,7 +22,7 @@
 // heads' c_proj contributions are summed inside one accumulator chain per output tile (k = head-major d); results per token
 // do not depend on the grid.
 #pragma once
-#include "gpt_kernels_c256a.h"
+#include "gpt_kernels_c256b.h"
 
 namespace mgpt {
 namespace fastk {
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void pack_attn160o_kernel(const float *__restr
 #pragma unroll
     for (int e = 0; e < 8; e++) {
         const int g = 8 * (ks & 1) + e;
-        const int col = 32 * (ks >> 1) + (g & 3) + 8 * (g >> 2) + 4 * h;      // the operand planes' k-slot order (attn256o_kernel)
+        const int col = 32 * (ks >> 1) + (g & 3) + 8 * (g >> 2) + 4 * h;      // the operand planes' k-slot order (pack_attn256_kernel)
         v[e] = attn ? row[col] * gain[col] * scale_a : row[col] * scale_p;
     }
     u32x2 h0, l0, h1, l1;
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(512, 2) void attn160o_kernel(float *__restrict__ x,
     const unsigned lane16 = (unsigned)lane * 16u;
     const unsigned lds0 = (unsigned)(size_t)smem + lane16;
     const unsigned sK = (unsigned)(size_t)smem + NSLOT * STEP, sV = sK + NP * kT * KROW;
-    // global addresses: wave-uniform 64-bit base in SGPRs + a 32-bit lane offset + immediate (see attn256o_kernel)
+    // global addresses: wave-uniform 64-bit base in SGPRs + a 32-bit lane offset + immediate (see attn256q_kernel)
     const unsigned char *wbase = reinterpret_cast<const unsigned char *>(wstream);
     unsigned char *sp_wave = spill + ((size_t)blockIdx.x * NW + wave) * (size_t)(8 * NP * 1024);              // this wave's slab (uniform)
     const unsigned xoff = (unsigned)(r * 32 + h * 16);     // chunk-major x: lane (r, h) owns the 16 bytes at r * 32 + h * 16 of every 1-KiB chunk
@@ -172,12 +172,8 @@ __global__ __launch_bounds__(512, 2) void attn160o_kernel(float *__restrict__ x,
         }
         __builtin_amdgcn_sched_barrier(0);                 // the requests stay in front of this chunk's MFMAs
     };
-    // the same requests one at a time (default build: read n rides behind the chunk's MFMA n -- DESIGN 11.8; -DMGPT_AB_ATTN160_CLUMPED: all in front)
-#if defined(MGPT_AB_ATTN160_CLUMPED)
-    constexpr bool PLACED = false;
-#else
+    // the same requests one at a time (read n rides behind the chunk's MFMA n -- DESIGN 11.8)
     constexpr bool PLACED = true;
-#endif
     auto chunk_read = [&](auto c_c, auto next_c, auto n_c) {
         constexpr int c = decltype(c_c)::value, n = decltype(n_c)::value;
         if constexpr (n < 2 * NP) {
@@ -214,18 +210,13 @@ __global__ __launch_bounds__(512, 2) void attn160o_kernel(float *__restrict__ x,
     };
     auto other_half_max = [&](float v) { float a, b2; half_swap(v, a, b2); return fmaxf(a, b2); };
     auto other_half_sum = [&](float v) { float a, b2; half_swap(v, a, b2); return a + b2; };
-    // units of q and k: see attn256o_kernel (default build: exponent units, 32 multiplies per head before the split)
-#if defined(MGPT_AB_ATTN_CLUMPED)
-    constexpr bool QK_UNITS = false;
-    const float sc2 = scale_log2e * inv_scale * inv_scale; // softmax exponent scale for q.k in weight-scaled units
-#else
+    // units of q and k: see attn256q_kernel (exponent units, 32 multiplies per head before the split)
     constexpr bool QK_UNITS = true;
-#endif
     const float q_units = scale_log2e * inv_scale, k_units = inv_scale;
 
     u32x4 xn[KS][2];                                       // operand planes: LayerNorm(x) during the heads, y during the tail
 
-    // One step = five chunks on the two accumulator chains qa / ka (kernel scope, captured directly: see attn256o_kernel).
+    // One step = five chunks on the two accumulator chains qa / ka (kernel scope, captured directly: see attn256q_kernel).
     //   MODE 0 (q|k, tail tile pairs): chain 0 += W[2c] xn[5j+c], chain 1 += W[2c+1] xn[5j+c]   (swapped: lane = token)
     //   MODE 1 (tail, single tile):    chain 0 += W[2c] xn[2c],   chain 1 += W[2c+1] xn[2c+1]   (swapped)
     //   MODE 2 (v):                    chain 0 += xn[2c] W[2c],   chain 1 += xn[2c+1] W[2c+1]   (natural: lane = d)
@@ -418,14 +409,10 @@ __global__ __launch_bounds__(512, 2) void attn160o_kernel(float *__restrict__ x,
             __builtin_amdgcn_s_barrier();                  // k, v^T of the head complete
 
             // ---- attention of this wave's 32 queries against the 256 keys of the head (model.py:58-60: no mask): the pipelined
-            //      key-tile loop of attn256o_kernel (round 5, gpt_kernels_attn_tiles.h; exact running-maximum loop as its fallback) ----
+            //      key-tile loop of attn256q_kernel (round 5, gpt_kernels_attn_tiles.h; exact running-maximum loop as its fallback) ----
             f32x16 o;
             float l_run = 0.f;
-#if defined(MGPT_AB_ATTN_CLUMPED)
-            attention_exact_tiles<T, NP, KROW, VROW, HS>(kr_addr, vr_addr, qf, sc2, o, l_run);
-#else
             attention_tiles<T, NP, KROW, VROW, HS>(kr_addr, vr_addr, qf, lane, o, l_run);
-#endif
             // ---- y planes of the head: o[g] = O[query r][d = tau(g, h)] / l, times the v projection's weight scale: register
             //      octet kk = k-step 2 hd + kk of the out-projection's B operand ----
             {

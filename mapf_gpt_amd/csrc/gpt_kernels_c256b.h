@@ -1,7 +1,33 @@
-// gpt_kernels_c256b.h -- attn256o_kernel (gpt_kernels_c256a.h: the whole attention block of the 6M shape, persistent -- read its header first) with its q|k|v projection
-// steps and its out-projection tail on v_mfma_f32_16x16x32 instead of v_mfma_f32_32x32x16 (two thirds of the kernel's MFMAs; DESIGN section 10 fact 5: 13-15 % more f16
-// flops per second at the package power limit).  The ATTENTION PHASE (gpt_kernels_attn_tiles.h) is untouched: its inputs and outputs keep their 32 x 32 layouts, and the
-// two layouts meet through one v_permlane16_swap per register pair (lane l: t = l % 16, q = l / 16 = 2 b5 + b4; a wave's 32 tokens are the groups tg = 0, 1):
+// gpt_kernels_c256b.h -- the whole attention block for n_embd = 256, 8 heads of 32 (MAPF-GPT-6M), gfx950 (attn256q_kernel):
+//     x <- x + c_proj(attention(LayerNorm(x)))                         (model.py:46-72, 102)
+// one kernel, PERSISTENT (grid = number of CUs, a workgroup walks rows b = blockIdx.x, + gridDim.x, ...), and the attention
+// output never exists as a matrix in HBM: round 3's attn256_kernel wrote the y operand planes (1 KiB per token) and an
+// HBM-bound packed GEMM (6.2 TB/s, 1.78 ms per 12 288-row launch) read them back together with x.
+//
+// Why the out-projection is a TAIL and not part of the head loop: a wave owns 32 tokens; the q|k|v projections need the
+// normalised rows as operand planes for every head (xn: 128 registers), the out-projection needs a 32 x 256 fp32 accumulator
+// block (128 registers).  256 tokens x (xn + accumulators) = 512 KiB = the CU's whole register file: the two cannot be live
+// together.  So a head's output tile (32 tokens x 32 d, 16 registers as split planes -- exactly the B operand of its c_proj
+// slice) is parked in a per-workgroup spill slab (224 KiB, written once and read once by the SAME wave, L2-resident: the slab
+// is re-used row after row), and after the last head -- xn is dead -- the planes of heads 0-6 come back into xn's registers
+// (requested before the last head's attention phase, which hides the round trip) and head 7's go there directly.  The
+// out-projection then has the shape of the q|k projection steps: operand planes of K = 256 in registers, c_proj.weight
+// through the same LDS ring, two output tiles per 4 stream steps on two accumulator chains, residual rows of those tiles
+// requested 4 steps before they are needed, x + acc / scale stored tile pair by tile pair.
+//
+// Stream: c_attn.weight * ln_1.weight (48 steps, as attn256_kernel) followed by c_proj.weight (16 steps), CYCLIC with period 64
+// steps per row through the 5-slot ring: the next row's first steps land during the tail.  All vector-memory operations of
+// the row loop are inline asm with hand-counted s_waitcnt (they retire in issue order: "at most N outstanding" with N = the
+// operations issued after the one needed is exact; a smaller N is always safe).  Per wave and row, in issue order:
+//     32 x-row loads | per head: 6 x 2 ring pieces, 4 spill stores (heads 0-6) | 28 spill loads | tail pseudo-head t = 0..3:
+//     8 residual loads, 4 x 2 ring pieces, 8 stores
+// Numerics: the same products and the same fp16 split of y as attn256_kernel + gemm_pk_kernel<EPI_RESID> (y in true units,
+// c_proj pre-scaled by a power of two, fp32 accumulation over k = head-major d); results per token do not depend on the grid.
+//
+// The q|k|v projection steps and the out-projection tail run on v_mfma_f32_16x16x32 (two thirds of the kernel's MFMAs; DESIGN section 10
+// fact 5: 13-15 % more f16 flops per second at the package power limit than the v_mfma_f32_32x32x16 of rounds 4-5).  The ATTENTION PHASE
+// (gpt_kernels_attn_tiles.h) keeps the 32 x 32 layouts of its inputs and outputs, and the two layouts meet through one v_permlane16_swap
+// per register pair (lane l: t = l % 16, q = l / 16 = 2 b5 + b4; a wave's 32 tokens are the groups tg = 0, 1):
 //   q|k steps  fragment (kb, ug) = 16 dims x the 32 features of k-block kb; result quads D(ug, tg) = registers 4 (2 tg + ug) .. of qa / ka: token 16 tg + t, dims
 //              8 blk + 4 ug + i.  k: blk = q -- a lane's eight dims are one 16-byte piece of the key's row in LDS (layout unchanged).  q: blk = 2 b4 + b5 -- then the
 //              swap of the token-group index (a register index) with lane bit 4 turns the packed quads into the B operand of S^T = K Q^T as the attention phase
@@ -14,12 +40,16 @@
 //   x          as in gpt_kernels_c256q.h: lane (t, q) owns the 32 bytes of tokens t, 16 + t in chunk 4 kb + q (operand side) resp. the 16 bytes at half q % 2 of chunk
 //              2 fg + q / 2 (residual quads); LayerNorm folds over the four lanes of a token
 #pragma once
-#include "gpt_kernels_c256a.h"
+#include "gpt_kernels_c256p.h"
+#include "gpt_kernels_attn_tiles.h"
 
 namespace mgpt {
 namespace fastk {
 
-// weight stream: as pack_attn256o_kernel -- [period step G][fragment ms][plane][lane][8], same sizes -- with 16 x 32 fragments (lane = row rho + 16 qk, eight k values):
+constexpr int kA256oProjSteps = 16;
+constexpr int kA256oPeriod = 8 * kA256StepsPerHead + kA256oProjSteps;     // stream steps per row
+
+// weight stream: [period step G][fragment ms][plane][lane][8], 8 fragments of 1 KiB per plane and step, 16 x 32 fragments (lane = row rho + 16 qk, eight k values):
 //   q|k steps (st < 4)   chunk cc = 4 st + ms / 2: k-block cc / 2, q (cc even) or k (cc odd); fragment ms % 2 = unit group ug: dim 8 blk + 4 ug + rho % 4 with
 //                        blk = rho / 4 for k, its two bits swapped for q (header)
 //   v steps (st = 4, 5)  chunk cc = 4 (st - 4) + ms / 2 = k-block; fragment ms % 2 = dims 16 dg + rho
@@ -73,7 +103,7 @@ __global__ __launch_bounds__(256) void pack_attn256q_kernel(const float *__restr
     if (NP == 2) *reinterpret_cast<u32x4 *>(dst + 512) = lo;
 }
 
-// STAMPS (tools/bench_probes/check_attn256o.hip only): wave 0 of every workgroup leaves {entry cycles, entry 100-MHz ticks, cycles in
+// STAMPS (probes only): wave 0 of every workgroup leaves {entry cycles, entry 100-MHz ticks, cycles in
 // the prologues, in the q|k|v projection steps, in the attention phases (k / v barrier included), in the tail steps, in the
 // tail epilogues, exit ticks} summed over its rows.  STAMPS == 2: waves 0 and 4 leave the step-phase cycles (sphase below).
 // EMB (layer 0 of a forward, round 6): the rows do not exist yet -- the prologue takes them from the (position, token) embedding table
@@ -150,13 +180,9 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
         __builtin_amdgcn_s_barrier();
     };
     // part 2: the slot of step G - 1 is refilled with step G + 4; addresses of this step's and the next step's slots
-    int slot_refill = 0;                                   // (-DMGPT_AB_ATTNQ_DMA_PLACED: the refill is issued from inside the step's first chunk)
+    int slot_refill = 0;
     auto sync_issue = [&]() {
-#if defined(MGPT_AB_ATTNQ_DMA_PLACED) && !defined(MGPT_AB_ATTNQ_CLUMPED)
-        slot_refill = slot_prev;
-#else
         issue(slot_prev);
-#endif
         const int slot_next = slot_cur + 1 == NSLOT ? 0 : slot_cur + 1;
         cur_addr = lds0 + (unsigned)slot_cur * STEP;
         nxt_addr = lds0 + (unsigned)slot_next * STEP;
@@ -186,12 +212,8 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
         __builtin_amdgcn_sched_barrier(0);                 // the requests stay in front of this chunk's MFMAs
     };
     // The same requests, one at a time: read N of chunk c's list (fragment 2c+2 plane 0 [, plane 1], fragment 2c+3 ...).  Default build: each rides behind one of the
-    // chunk's first MFMAs (the matrix pipe is busy for 16 cycles per MFMA, the LDS request issues in its shadow; -DMGPT_AB_ATTNQ_CLUMPED: all in front, as attn256o_kernel)
-#if defined(MGPT_AB_ATTNQ_CLUMPED)
-    constexpr bool PLACED = false;
-#else
+    // chunk's first MFMAs (the matrix pipe is busy for 16 cycles per MFMA, the LDS request issues in its shadow; rounds 4-5 issued all in front)
     constexpr bool PLACED = true;
-#endif
     auto chunk_wait = [&]() {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
@@ -267,13 +289,9 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
     auto chunk_body = [&](auto c_c, auto next_c, auto &&mm) {
         if constexpr (PLACED) {
             chunk_wait();
-            // -DMGPT_AB_ATTNQ_DMA_PLACED: a step's first chunk also issues the ring refill (PW direct-to-LDS pieces) two MFMAs behind the last read instead of at the
+            // REFILL: a step's first chunk also issues the ring refill (PW direct-to-LDS pieces) two MFMAs behind the last read instead of at the
             // step's top.  Built and measured (profiles/r05_ab.txt, visit N): SLOWER, attention 48.0 -> 48.2 ms per cfg3 step -- the refill stays at the top
-#if defined(MGPT_AB_ATTNQ_DMA_PLACED)
-            constexpr bool REFILL = decltype(c_c)::value == 0;
-#else
             constexpr bool REFILL = false;
-#endif
             constexpr int N_REFILL = NP == 2 ? 5 : 2, N_LAST = REFILL ? N_REFILL : 2 * NP - 1, NMF = NP == 2 ? 12 : 4;
             mm([&](auto n_c) {
                 constexpr int n = decltype(n_c)::value;
@@ -306,17 +324,12 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
     };
     auto other_half_max = [&](float v) { float a, b2; half_swap(v, a, b2); return fmaxf(a, b2); };
     auto other_half_sum = [&](float v) { float a, b2; half_swap(v, a, b2); return a + b2; };
-    // Units of q and k.  Round 4 (and the -DMGPT_AB_ATTN_CLUMPED build): the planes carry the raw accumulators, i.e. q and k
-    // times the weight stream's power-of-two scale, and the softmax multiplies every score by sc2.  Default build: the accumulators are
+    // Units of q and k.  Round 4: the planes carried the raw accumulators, i.e. q and k
+    // times the weight stream's power-of-two scale, and the softmax multiplied every score by sc2.  Since round 5: the accumulators are
     // brought to q * log2(e) / sqrt(hs) and to k (true units) before they are split -- 32 multiplies per head -- so that a score IS
     // the exponent and the per-score multiply-add of the key-tile loop goes (see "one reference per query" below): sc2 = 1.
-#if defined(MGPT_AB_ATTN_CLUMPED)
-    constexpr bool QK_UNITS = false;
-    const float sc2 = scale_log2e * inv_scale * inv_scale; // softmax exponent scale for q.k in weight-scaled units
-#else
     constexpr bool QK_UNITS = true;
     const float sc2 = 1.0f;
-#endif
     const float q_units = scale_log2e * inv_scale, k_units = inv_scale;
     // (the four K / V^T lane addresses are recomputed at the top of every head from lane16 through an opaque copy: as row-loop
     //  invariants they cost four registers that this kernel does not have -- one variant of it kept one in scratch, and the
@@ -505,11 +518,7 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
                 sphase(5);
             };
             step_v(I0{}, std::true_type{});
-#ifdef MGPT_AB_ATTN_CLUMPED
-            step_v(I1{}, std::true_type{});
-#else
             step_v(I1{}, std::false_type{});               // (the next step's first pairs are requested at the end of the attention phase)
-#endif
             if constexpr (LASTH) {
                 // the normalised rows are dead: their registers take the y planes of heads 0-6 back (this wave's own stores,
                 // complete since the step waits above; L2-resident).  Needed at the first tail step, one attention phase away.
@@ -543,15 +552,11 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
             // ---- attention of this wave's 32 queries against the 256 keys of the head (gpt_kernels_attn_tiles.h) ----
             f32x16 o;
             float l_run = 0.f;
-#if defined(MGPT_AB_ATTN_CLUMPED)
-            attention_exact_tiles<T, NP, KROW, VROW, HS>(kr_addr, vr_addr, qf, sc2, o, l_run);
-#else
             attention_tiles<T, NP, KROW, VROW, HS>(kr_addr, vr_addr, qf, lane, o, l_run);
             // the first pairs of the next stream step (the step after this phase; its slot landed for every wave before the last
             // v step's barrier) -- round 4 requested them in that step's chunk 3 and held their 16 registers across the whole phase
             lds_pair(nxt_addr, I0{}, wb[0][0]);
             lds_pair(nxt_addr, I1{}, wb[0][1]);
-#endif
             // ---- y planes of the head: o[g] = O[query r][d = tau(g, h)] / l, times the v projection's weight scale; rows swapped between
             //      registers g and 8 + g: register octet tg = token group tg of k-block hd of the out-projection's B operand (header) ----
             {

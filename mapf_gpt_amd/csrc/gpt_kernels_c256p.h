@@ -1,6 +1,6 @@
 // gpt_kernels_c256p.h -- persistent, role-specialised MLP block for n_embd = 256 (MAPF-GPT-6M), gfx950.
 //
-// Why (round 3, profiles/r03_probe_mlp256_insitu_gap.txt): mlp256_kernel (gpt_kernels_c256.h: one 512-register wave per
+// Why (round 3, profiles/r03_probe_mlp256_insitu_gap.txt): round 2's MLP kernel (one 512-register wave per
 // SIMD, one workgroup per CU) spends 22 % of a block's cycles in its prologue (x rows in, LayerNorm, split) and epilogue
 // (residual read-modify-write) -- HBM bursts of all 256 CUs at once during which no MFMA runs on the CU -- and its ring loop
 // issues 1100 cycles per 768 cycles of matrix pipe because a lone wave cannot hide its LDS / DMA / VALU issue time.

@@ -200,12 +200,8 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256q_kernel(float *__restri
         __builtin_amdgcn_sched_barrier(0);
     };
     // the same requests one at a time (the consumer's placed chunks: each behind one of the chunk's first MFMAs, the matrix pipe being busy for 16 cycles per MFMA --
-    // measured on attn256q_kernel, gpt_kernels_c256b.h; -DMGPT_AB_MLPQ_CLUMPED: all in front as in the producer)
-#if defined(MGPT_AB_MLPQ_CLUMPED)
-    constexpr bool PLACED = false;
-#else
+    // measured on attn256q_kernel, gpt_kernels_c256b.h)
     constexpr bool PLACED = (kMQAbl == 0);
-#endif
     auto chunk_read = [&](auto mb_c, auto c_c, bool next_step_has_work, auto n_c) {
         constexpr int MB = decltype(mb_c)::value, c = decltype(c_c)::value, n = decltype(n_c)::value;
         if constexpr (n < 2 * NP) {

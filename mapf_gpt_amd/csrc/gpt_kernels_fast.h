@@ -952,21 +952,13 @@ __global__ __launch_bounds__(256) void ln_pack_kernel(const float *__restrict__ 
 // DBG (probe only): 1 = wave 0 leaves stamps[workgroup][8] = {cycles waiting at the tops of its tiles, in their k loops, in their epilogues, tiles, total cycles, total 100-MHz ticks}.
 // NWV = 8: one 256 x 256 block per CU.  NWV = 4: 128 x 256 blocks, two per CU, each with its own ring and barrier (small launches: more
 // tiles than the 256-row form; at full size it is no faster, profiles/r03_probe_gemm_pk.txt).
-#ifdef MGPT_AB_GEMM_CLUMPED
-constexpr bool kGemmPkPlace = false;
-#else
 constexpr bool kGemmPkPlace = true;
-#endif
 #ifdef MGPT_ABL_GEMM_16X16
 constexpr int kGemmPkMfmaPerTile = 2;       // (timing experiment: two 16 x 16 x 32 MFMAs in the place of every 32 x 32 x 16 one, see `round`)
 #else
 constexpr int kGemmPkMfmaPerTile = 1;
 #endif
-#ifdef MGPT_AB_GEMM_DMA_TOP
-constexpr bool kGemmPkDmaPlace = false;
-#else
 constexpr bool kGemmPkDmaPlace = true;
-#endif
 constexpr int gemm_pk_kps(int NP) { return 1; }
 // instances compiled WITH the tile loop (see gemm_pk_kernel): the one-plane GELU epilogue, where it measured faster; the split-mode and the
 // natural-orientation (v^T) instances would spill with the loop's state carried through their epilogues, and the residual epilogue at K = 3072
@@ -1138,11 +1130,9 @@ __global__ __launch_bounds__(NWV * 64, 2) void gemm_pk_kernel(GemmArgs p, unsign
 #pragma unroll
         for (int n = 0; n < NMF; n++) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-#ifndef MGPT_AB_GEMM_SALU_FRONT
             // slot / address arithmetic behind the first MFMA instead of between the barrier and it (one-plane mode: 731 -> 690 cycles per k-step; in the
             // split mode the group size does not fit the second stage of the unrolled pair and the placement falls apart -- left to hipcc there)
             if (n == 0 && NP == 1) __builtin_amdgcn_sched_group_barrier(0x004, 12, 0);
-#endif
             if (n < NRD) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             else if ((n - NRD) % GAP == 0 && (n - NRD) / GAP < PER_WAVE) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
         }
@@ -1599,7 +1589,7 @@ __global__ __launch_bounds__(NW * 64) void attn16_kernel(const uint16_t *__restr
     };
     // stage K [256][HS] and V^T [HS][256] planes (16-byte chunks).  ALL of a thread's loads are issued before the first LDS store (round 5; rounds 1-4: a
     // `for (idx = tid; idx < N; idx += threads)` loop, which hipcc cannot unroll -- it ran load, s_waitcnt vmcnt(0), ds_write eight times in sequence, eight
-    // memory round trips per workgroup before its first MFMA: the kernel sat at 0.51 of the HBM rate with 0.22 of the MFMA rate; -DMGPT_AB_ATTN16_SERIAL_STAGE)
+    // memory round trips per workgroup before its first MFMA: the kernel sat at 0.51 of the HBM rate with 0.22 of the MFMA rate)
     {
         constexpr int NCH = NP * kT * (HS / 8);             // 16-byte chunks of the K planes (= of the V^T planes)
         constexpr int NIT = NCH / (NW * 64);
@@ -1619,18 +1609,6 @@ __global__ __launch_bounds__(NW * 64) void attn16_kernel(const uint16_t *__restr
             else { row = rem / (kT / 8); c = rem - row * (kT / 8); src = (pl == 0 ? vt_hi : vt_lo) + base + (size_t)row * kT + c * 8; }
             dst = (unsigned)(pl * HS * VRS + row * VRS + c * 16);
         };
-#if defined(MGPT_AB_ATTN16_SERIAL_STAGE)
-        for (int idx = tid; idx < NCH; idx += NW * 64) {
-            const uint16_t *src; unsigned dst;
-            k_src(idx, src, dst);
-            *reinterpret_cast<u32x4 *>(sK + dst) = *reinterpret_cast<const u32x4 *>(src);
-        }
-        for (int idx = tid; idx < NCH; idx += NW * 64) {
-            const uint16_t *src; unsigned dst;
-            v_src(idx, src, dst);
-            *reinterpret_cast<u32x4 *>(sV + dst) = *reinterpret_cast<const u32x4 *>(src);
-        }
-#else
         u32x4 kreg[NIT], vreg[NIT];
         unsigned kdst[NIT], vdst[NIT];
 #pragma unroll
@@ -1642,7 +1620,6 @@ __global__ __launch_bounds__(NW * 64) void attn16_kernel(const uint16_t *__restr
         for (int it = 0; it < NIT; it++) *reinterpret_cast<u32x4 *>(sK + kdst[it]) = kreg[it];
 #pragma unroll
         for (int it = 0; it < NIT; it++) *reinterpret_cast<u32x4 *>(sV + vdst[it]) = vreg[it];
-#endif
     }
     __syncthreads();
 
@@ -1650,11 +1627,7 @@ __global__ __launch_bounds__(NW * 64) void attn16_kernel(const uint16_t *__restr
     const int kperm = (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1);
 
     for (int qt = qt_first; qt < kT / 32; qt += NW) {
-#if defined(MGPT_AB_ATTN16_SERIAL_STAGE)
-        load_q(qt, qf);
-#else
         if (qt != qt_first) load_q(qt, qf);
-#endif
         f32x16 o[DT];
 #pragma unroll
         for (int dt = 0; dt < DT; dt++)
@@ -1682,23 +1655,7 @@ __global__ __launch_bounds__(NW * 64) void attn16_kernel(const uint16_t *__restr
             mx = half_max32(mx);
             // The kernel runs at the SUM of its MFMA and VALU issue time, so the softmax arithmetic is kept short: the rescale of o and l
             // (16 DT + 3 instructions) only when some query's running maximum moved (wave-uniform branch; alpha = 1 exactly otherwise), and one fma per
-            // score in front of the exp2 (-DMGPT_AB_ATTN16_PLAIN: round 1's form, rescale every tile and (s - m) * scale)
-#if defined(MGPT_AB_ATTN16_PLAIN)
-            const float m_new = fmaxf(m_run, mx);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2e);
-            l_run *= alpha;
-#pragma unroll
-            for (int dt = 0; dt < DT; dt++)
-#pragma unroll
-                for (int g = 0; g < 16; g++) o[dt][g] *= alpha;
-            m_run = m_new;
-            float psum = 0.f;
-#pragma unroll
-            for (int g = 0; g < 16; g++) {
-                s[g] = __builtin_amdgcn_exp2f((s[g] - m_new) * scale_log2e);
-                psum += s[g];
-            }
-#else
+            // score in front of the exp2 (round 1 rescaled every tile and exponentiated (s - m) * scale)
             if (__builtin_amdgcn_ballot_w64(mx > m_run) != 0) {
                 const float m_new = fmaxf(m_run, mx);
                 const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2e);
@@ -1716,7 +1673,6 @@ __global__ __launch_bounds__(NW * 64) void attn16_kernel(const uint16_t *__restr
                 s[g] = __builtin_amdgcn_exp2f(fmaf(s[g], scale_log2e, nm));
                 psum += s[g];
             }
-#endif
             psum = half_sum32(psum);
             l_run += psum;
 #pragma unroll
@@ -1821,15 +1777,16 @@ __global__ __launch_bounds__(256) void pack_mlp_kernel(const float *__restrict__
 
 
 // (C = 64, 160: the 2M and tiny shapes; C = 256 has its own pipelined kernel in gpt_kernels_c256.h)
-template <class T, int NP, int CT, int NW = 8, int NFOLD = 0, int NBUF = 3, int NCH = 2>
+template <class T, int NP, int CT, int NW = 8, int NBUF = 3, int NCH = 2>
 __global__ __launch_bounds__(NW * 64, 2) void mlp_fused_kernel(float *__restrict__ x, const float *__restrict__ gain,
                                                             const uint16_t *__restrict__ wpk, float inv1, float inv2,
                                                             float2 *__restrict__ stats_out, int M,
                                                             const float2 *__restrict__ gelu_lut,
                                                             const float *__restrict__ fold = nullptr, int64_t fold_stride = 0)
 {
-    // NFOLD > 0 (small launches, after a head-parallel attn_block_kernel): NFOLD partial sums in x's layout, fold_stride floats
-    // apart, are added to the row in index order before anything else and the sum is written back (a token has ONE owner here).
+    // Small launches, after a head-parallel attn_block_kernel (the only launches of this kernel): CT partial sums (n_head = C / 32) in
+    // x's layout, fold_stride floats apart, are added to the row in index order before anything else and the sum is written back (a
+    // token has ONE owner here).
     // A compile-time count: every load of the fold is in flight at once (as a run-time loop hipcc serialised them, +23 us per launch)
     constexpr int C = CT * 32, KS = C / 16, NT = 4 * CT;
     constexpr int LUT_BYTES = kGeluLutN * 8;               // the Phi table sits behind the ring: [NBUF][PKT][LUT]
@@ -1881,10 +1838,10 @@ __global__ __launch_bounds__(NW * 64, 2) void mlp_fused_kernel(float *__restrict
             const f32x4 v = *reinterpret_cast<const f32x4 *>(xt + (4 * j + gq) * 256);
             acc[j][4 * gq] = v[0]; acc[j][4 * gq + 1] = v[1]; acc[j][4 * gq + 2] = v[2]; acc[j][4 * gq + 3] = v[3];
         }
-    if constexpr (NFOLD > 0) {
+    {
         const float *fp = fold + (xt - x);
 #pragma unroll
-        for (int p = 0; p < NFOLD; p++) {
+        for (int p = 0; p < CT; p++) {
             f32x4 t[4 * CT];
 #pragma unroll
             for (int c = 0; c < 4 * CT; c++) t[c] = *reinterpret_cast<const f32x4 *>(fp + (size_t)p * fold_stride + c * 256);
@@ -2163,19 +2120,17 @@ __global__ __launch_bounds__(256) void pack_cols_perm_kernel(const float *__rest
 // tile), so register octets [8m, 8m+8) are directly MFMA k-slot groups everywhere, and the LDS images are written
 // and read with the same (row, octet, half) address.
 // ---------------------------------------------------------------------------------------------
-// PROJ: also apply the output projection per head (c_proj fragments are the 4th packet of every head) and the
-// residual add: x <- x + c_proj(attention), LayerNorm statistics of the new row to stats_out; y planes unused.
-// LAST (needs PROJ): last layer -- only position 255 feeds ln_f and the head (model.py:186), so only K and V are
-// needed for all tokens; q, the attention, c_proj and the residual run for the wave that owns token 255 only, and
-// the new row of token 255 goes to the compact buffer x_last[row][C] (the MLP and the head then run on that).
+// The output projection is applied per head (c_proj fragments are the 4th packet of every head), then the residual add:
+// x <- x + c_proj(attention), LayerNorm statistics of the new row to stats_out.  (y_hi, y_lo and x_last are not used: the y-plane
+// and the last-layer forms of this kernel were retired for the persistent kernels and attn_last1_kernel.)
 // EMBED (first layer): the residual row is not read from x but formed here as wte[token] + wpe[position]
 // (model.py:171-175), which removes the embedding kernel's write and this kernel's first read of x.
-// HP (head-parallel, small launches: needs PROJ, excludes EMBED): one workgroup per (row, head) instead of per row -- with a few dozen
+// HP (head-parallel, small launches: excludes EMBED): one workgroup per (row, head) instead of per row -- with a few dozen
 // rows (one environment: BASELINE cfg1) a row's five heads run on five CUs at once instead of one after the other on one.  The
 // workgroup forms the row's LayerNorm itself, runs its head and writes that head's c_proj contribution (times the projection's
-// 1 / scale) to part_out + head * part_stride in x's own layout (LAST: the compact last-token layout); x is NOT touched -- the
-// next kernel (mlp_fused_kernel's / gather_last_kernel's fold arguments) adds the partial sums in head order.
-template <class T, int NP, int CT, bool PROJ, bool LAST = false, bool EMBED = false, bool HP = false>
+// 1 / scale) to part_out + head * part_stride in x's own layout; x is NOT touched -- the next kernel (mlp_fused_kernel's /
+// mlp160p_kernel's fold arguments) adds the partial sums in head order.
+template <class T, int NP, int CT, bool EMBED = false, bool HP = false>
 __global__ __launch_bounds__(512, 2) void attn_block_kernel(float *__restrict__ x, const float *__restrict__ gain,
                                                              const uint16_t *__restrict__ wpk, float inv_scale,
                                                              uint16_t *__restrict__ y_hi, uint16_t *__restrict__ y_lo,
@@ -2186,9 +2141,7 @@ __global__ __launch_bounds__(512, 2) void attn_block_kernel(float *__restrict__ 
                                                              const float *__restrict__ wpe, float *__restrict__ part_out = nullptr,
                                                              int64_t part_stride = 0)
 {
-    static_assert(!EMBED || (PROJ && !LAST), "EMBED is the first layer of a model with more than one layer");
-    static_assert(!LAST || PROJ, "LAST implies PROJ");
-    static_assert(!HP || (PROJ && !EMBED), "HP writes c_proj partial sums and reads x");
+    static_assert(!HP || !EMBED, "HP writes c_proj partial sums and reads x");
     constexpr int C = CT * 32, KS = C / 16, NW = 8, HS = 32;
     constexpr int F = KS * NP, PKT = F * 1024, PER_WAVE = (F + NW - 1) / NW;
     constexpr int KROW = 80, VROW = 528;                                  // padded LDS rows (bytes): conflict-free b128 reads
@@ -2207,7 +2160,6 @@ __global__ __launch_bounds__(512, 2) void attn_block_kernel(float *__restrict__ 
     const unsigned char *wsrc = reinterpret_cast<const unsigned char *>(wpk);
     const unsigned char *psrc = reinterpret_cast<const unsigned char *>(ppk);
     static_assert(2 * CT * NP == F, "c_proj slice packet has the same size as a c_attn tile packet");
-    const bool full = !LAST || wave == NW - 1;                            // wave-uniform: does this wave run q / attention / c_proj?
 
     // Two barriers per head:
     //   A(hd): q|k|v packets of head hd landed (issued right after B(hd-1)), K/V^T and the c_proj slot are free
@@ -2309,9 +2261,9 @@ __global__ __launch_bounds__(512, 2) void attn_block_kernel(float *__restrict__ 
         __builtin_amdgcn_s_barrier();
     };
 
-    f32x16 pacc[PROJ ? CT : 1];                                            // c_proj output accumulators (swapped layout)
+    f32x16 pacc[CT];                                                       // c_proj output accumulators (swapped layout)
 #pragma unroll
-    for (int j = 0; j < (PROJ ? CT : 1); j++)
+    for (int j = 0; j < CT; j++)
 #pragma unroll
         for (int g = 0; g < 16; g++) pacc[j][g] = 0.f;
     const float sc2 = scale_log2e * inv_scale * inv_scale;                // softmax exponent scale for q.k in weight-scaled units
@@ -2319,14 +2271,12 @@ __global__ __launch_bounds__(512, 2) void attn_block_kernel(float *__restrict__ 
     sync_all();                                                            // A(0)
 #pragma unroll 1
     for (int hd = hd_lo; hd < hd_hi; hd++) {
-        if (PROJ) dma(psrc + (size_t)hd * PKT, 3);                         // c_proj slice of this head (needed after the attention)
+        dma(psrc + (size_t)hd * PKT, 3);                                   // c_proj slice of this head (needed after the attention)
         f32x16 tile;
         u32x4 qf[2][2];                                                   // B operand of S^T = K Q^T: [k-step][plane]
-        if (full) {
-            project(0, true, tile);
+        project(0, true, tile);
 #pragma unroll
-            for (int ks = 0; ks < 2; ks++) pack_octet(tile, ks, qf[ks]);
-        }
+        for (int ks = 0; ks < 2; ks++) pack_octet(tile, ks, qf[ks]);
         // ---- k -> sK[pl][key = tok0 + r][octet ks][half h] ----
         project(1, true, tile);
 #pragma unroll
@@ -2356,7 +2306,7 @@ __global__ __launch_bounds__(512, 2) void attn_block_kernel(float *__restrict__ 
         for (int g = 0; g < 16; g++) o[g] = 0.f;
         float m_run = -INFINITY, l_run = 0.f;
 #pragma unroll 1
-        for (int kt = 0; kt < (full ? kT / 32 : 0); kt++) {
+        for (int kt = 0; kt < kT / 32; kt++) {
             f32x16 sc;
 #pragma unroll
             for (int g = 0; g < 16; g++) sc[g] = 0.f;
@@ -2400,21 +2350,11 @@ __global__ __launch_bounds__(512, 2) void attn_block_kernel(float *__restrict__ 
                 o = mma<T, NP>(vf, pf, o);
             }
         }
-        const float inv = full ? inv_scale / l_run : 0.f;                  // 1/l and the v projection's weight scale
+        const float inv = inv_scale / l_run;                               // 1/l and the v projection's weight scale
 #pragma unroll
         for (int g = 0; g < 16; g++) o[g] *= inv;
         // o[g] = O[query r][d = tau(g, h)]
-        if (!PROJ) {                                                      // -> y planes [b*256 + tok0 + r][hd*32 + d]
-            const size_t yrow = ((size_t)b * kT + tok0 + r) * C + hd * HS;
-#pragma unroll
-            for (int gq = 0; gq < 4; gq++) {
-                const float v[4] = {o[4 * gq], o[4 * gq + 1], o[4 * gq + 2], o[4 * gq + 3]};
-                u32x2 hi, lo;
-                split4<T, NP>(v, hi, lo);
-                *reinterpret_cast<u32x2 *>(y_hi + yrow + 8 * gq + 4 * h) = hi;
-                if (NP == 2) *reinterpret_cast<u32x2 *>(y_lo + yrow + 8 * gq + 4 * h) = lo;
-            }
-        } else if (full) {
+        {
             // the head's output is, as it stands, the B operand of its slice of c_proj: pacc += Wp[:, head] y_head
             u32x4 yf[2][2];
 #pragma unroll
@@ -2432,14 +2372,11 @@ __global__ __launch_bounds__(512, 2) void attn_block_kernel(float *__restrict__ 
         }
         sync_all();                                                        // A(hd+1)
     }
-    if (PROJ && full) {
+    {
         // ---- residual add, store, LayerNorm statistics of the new row (as the GEMM / MLP epilogues) ----
-        // LAST: only token 255 (lanes 31 and 63 of the last wave) is kept, in the compact buffer
-        const bool keep = !LAST || r == 31;
         if constexpr (HP) {
             // this head's c_proj contribution, in true units, where the residual row would go (in the head's own partial buffer)
-            float *prow = part_out + (size_t)hd_lo * part_stride +
-                          (LAST ? (b >> 5) * 32 * C + (b & 31) * 8 + 4 * h : (b * kT + tok0) * C + r * 8 + 4 * h);
+            float *prow = part_out + (size_t)hd_lo * part_stride + (b * kT + tok0) * C + r * 8 + 4 * h;
 #pragma unroll
             for (int j = 0; j < CT; j++)
 #pragma unroll
@@ -2447,12 +2384,10 @@ __global__ __launch_bounds__(512, 2) void attn_block_kernel(float *__restrict__ 
                     f32x4 v;
 #pragma unroll
                     for (int e = 0; e < 4; e++) v[e] = pacc[j][4 * gq + e] * inv_scale_p;
-                    if (keep) *reinterpret_cast<f32x4 *>(prow + (4 * j + gq) * 256) = v;
+                    *reinterpret_cast<f32x4 *>(prow + (4 * j + gq) * 256) = v;
                 }
             return;
         }
-        // (LAST: row b of the compact matrix, chunk-major as well: tile b / 32, token b % 32)
-        float *orow = LAST ? x_last + (b >> 5) * 32 * C + (b & 31) * 8 + 4 * h : xt;
         float s2 = 0.f;
 #pragma unroll
         for (int j = 0; j < CT; j++)
@@ -2463,10 +2398,10 @@ __global__ __launch_bounds__(512, 2) void attn_block_kernel(float *__restrict__ 
                                   : *reinterpret_cast<const f32x4 *>(xt + (4 * j + gq) * 256);
 #pragma unroll
                 for (int e = 0; e < 4; e++) { cur[e] += pacc[j][4 * gq + e] * inv_scale_p; pacc[j][4 * gq + e] = cur[e]; }
-                if (keep) *reinterpret_cast<f32x4 *>(orow + (4 * j + gq) * 256) = cur;
+                *reinterpret_cast<f32x4 *>(xt + (4 * j + gq) * 256) = cur;
                 s2 += (cur[0] + cur[1]) + (cur[2] + cur[3]);
             }
-        if (stats_out != nullptr && !LAST) {
+        if (stats_out != nullptr) {
             s2 += __shfl_xor(s2, 32);
             const float mean2 = s2 / (float)C;
             float q2 = 0.f;

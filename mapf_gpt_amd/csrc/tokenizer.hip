@@ -489,9 +489,7 @@ __global__ __launch_bounds__(256) void tokens_kernel(const AgentRec *__restrict_
             uint8_t *rw = row + u * kRowBytes;
             const uint32_t my0 = my0s[q0 + u];
             // "!" (cpp:375-376, 386-387) over bytes 4 .. 259: tokens 3 .. 258; tokens 0 .. 2 are window cells, written below
-#if !defined(MGPT_ABL_TOK) || (MGPT_ABL_TOK != 4)
             *reinterpret_cast<uint32_t __attribute__((may_alias)) *>(rw + 4 + 4 * lane) = padv;
-#endif
 
             // --- window tokens (cpp:288-311 + vocabulary cpp:321-357), both cells of the lane as one packed pair ---
             const uint32_t P = (w1[q0 + u] << 16) | w0[q0 + u];
@@ -507,12 +505,8 @@ __global__ __launch_bounds__(256) void tokens_kernel(const AgentRec *__restrict_
             t = t + e + e;
             const us2 isunr = (us2){0, 0} - __builtin_elementwise_sub_sat(as_us2(P), as_us2(unrm2));   // 0xffff iff v = UNR (cpp:308-309)
             const uint32_t tt = (as_u32(isunr) & unrtok2) | (~as_u32(isunr) & as_u32(t));               // -> one bit-select
-#if !defined(MGPT_ABL_TOK) || (MGPT_ABL_TOK != 1)      // LDS ablations (results wrong; tools/tok_lds_ablation.sh): 1 window-token stores, 2 bucket atomics,
-            tok0_at[u * kRowBytes] = (uint8_t)tt;           // 3 emission (record gather + stores), 4 pad fill, 5 rank read-back + list
+            tok0_at[u * kRowBytes] = (uint8_t)tt;
             tok1_at[u * kRowBytes] = (uint8_t)(tt >> 16);
-#else
-            asm volatile("" :: "v"(tt));
-#endif
 
             // --- neighbours: the (2A+1)^2 scan of cpp:492-495 on the LDS-resident positions ---
             const uint32_t myb = my0 ^ 0x80008000u;
@@ -565,12 +559,7 @@ __global__ __launch_bounds__(256) void tokens_kernel(const AgentRec *__restrict_
 #pragma unroll
         for (int u = 0; u < U; u++) {
             mine[u] = bkt + u * 16 + cmd[u];
-#if defined(MGPT_ABL_TOK) && (MGPT_ABL_TOK == 2)
-            asm volatile("" :: "v"(mine[u]));
-            if (false)
-#else
             if (have[u])                // divergent on purpose: same-address LDS atomics serialise, so only real neighbours issue one
-#endif
                 __hip_atomic_fetch_or(reinterpret_cast<unsigned long long *>(mine[u]), 1ull << lane,
                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);        // ds_or_b64, order-independent
         }
@@ -588,11 +577,7 @@ __global__ __launch_bounds__(256) void tokens_kernel(const AgentRec *__restrict_
         // --- the first S leave their id at list[row][rank] (cpp:506) ---
 #pragma unroll
         for (int u = 0; u < U; u++) {
-#if defined(MGPT_ABL_TOK) && (MGPT_ABL_TOK == 5)
-            if (false) {
-#else
             if (have[u]) {
-#endif
                 const uint4 e = *mine[u];
                 // lower buckets + the bucket's candidates in lanes below this one (v_mbcnt: the lane mask is implicit)
                 const uint32_t r = __builtin_amdgcn_mbcnt_hi(e.y, __builtin_amdgcn_mbcnt_lo(e.x, e.z));
@@ -629,11 +614,7 @@ __global__ __launch_bounds__(256) void tokens_kernel(const AgentRec *__restrict_
         //     +-A), rel goal clamped to +-L, the last Hn history tokens oldest first, greedy-direction bits ---
         {
             const uint32_t k16 = list[lane];
-#if defined(MGPT_ABL_TOK) && (MGPT_ABL_TOK == 3)
-            if (false) {
-#else
             if (k16 != kNoKey) {
-#endif
                 const uint4 o = srec[k16];
                 const uint32_t my0 = hdr[wave * RPW + q0 + eu];
                 const ss2 base = as_ss2(my0) - as_ss2(rep16(L));                               // pos - L
@@ -1016,11 +997,7 @@ extern "C" int mgpt_tokenizer_generate_observations(mgpt_tokenizer *t, uint8_t *
     const int kpp = kp <= 4 ? kp : kp <= 8 ? 8 : kp <= 16 ? 16 : 32;
     // rows per wavefront: 8 (more bytes in flight, records staged once per 32 rows) when the launch still fills the GPU
     const int64_t wg64 = (int64_t)t->n_inst * cdiv(t->n_agents, 64);               // workgroups at 64 rows each
-    int rpw = wg64 >= 4096 ? 8 : 4;
-    {
-        static const int forced = [] { const char *e = getenv("MGPT_TOK_RPW"); return e ? atoi(e) : 0; }();   // experiments only
-        if (forced == 4 || forced == 8 || forced == 16) rpw = forced;
-    }
+    const int rpw = wg64 >= 4096 ? 8 : 4;
     const int apb = 4 * rpw;
     const int chunks = cdiv(t->n_agents, apb);
     const int cw = kpp == 1 ? 0 : (kpp <= 4 ? 64 * kpp : 64);                      // CandWidth<KP>
@@ -1032,8 +1009,7 @@ extern "C" int mgpt_tokenizer_generate_observations(mgpt_tokenizer *t, uint8_t *
                        t->dist8, t->u8_ok, t->n_agents, t->H, t->W, chunks, d_tokens, t->step, t->cfg, t->hdrs)
 #define MGPT_TOKENS(KP_)                                                                                              \
     do {                                                                                                              \
-        if (rpw == 16) MGPT_TOKENS_R(KP_, 16);                                                                        \
-        else if (rpw == 8) MGPT_TOKENS_R(KP_, 8);                                                                     \
+        if (rpw == 8) MGPT_TOKENS_R(KP_, 8);                                                                          \
         else MGPT_TOKENS_R(KP_, 4);                                                                                   \
     } while (0)
     switch (kpp) {

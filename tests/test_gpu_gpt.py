@@ -396,7 +396,7 @@ def test_persistent_kernels_uneven_grid(name, precision):
 def test_spread_scores_take_the_exact_attention_loop():
     """Round 5: the 6M attention kernel's key-tile loop takes ONE softmax reference per query and head (the maximum of the first key
     tile) and falls back to the exact running-maximum loop when exp2(s - ref) leaves the fp16 range of the P planes
-    (gpt_kernels_c256a.h).  N(0, 0.02) weights never get there (counter 0, and the goldens above pin that path); here the q and k
+    (gpt_kernels_attn_tiles.h).  N(0, 0.02) weights never get there (counter 0, and the goldens above pin that path); here the q and k
     rows of c_attn are scaled until scores spread by tens of nats, so that a good share of the (wave, head) pairs must fall back.
     Both paths together must stay in the f16x3 class against our exact-fp32-MFMA path (whose attention is a different kernel)."""
     from mapf_gpt_amd.model import build_model

@@ -3,7 +3,7 @@
 register which an earlier ds_read has not yet been waited for (LDS returns in order: s_waitcnt lgkmcnt(n) retires all but
 the youngest n reads).  Inline-asm loads are invisible to hipcc, so under register pressure it may copy or consume their
 destinations before the hand-placed wait (cdna guide 5.7); a clean audit (0 violations) is part of the build check for
-mlp256_kernel.  Straight-line model: loop back-edges are not followed."""
+round 2's MLP kernel.  Straight-line model: loop back-edges are not followed."""
 import re
 import sys
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/build_ab.sh <name> [extra hipcc flags]  -- build a variant of the library into gpurun_tmp/lib_<name>.so (for tools/ab_lib.sh);
-# e.g.  tools/build_ab.sh unfused -DMGPT_AB_ATTN_UNFUSED ; tools/build_ab.sh new
+# e.g.  tools/build_ab.sh new ; tools/build_ab.sh probe -DMGPT_ABL_GEMM_16X16  (the library's remaining -D switches: tools/README.md)
 cd "$(dirname "$0")/.."
 N=$1; shift
 B=/tmp/ab_build_$N; mkdir -p $B gpurun_tmp
