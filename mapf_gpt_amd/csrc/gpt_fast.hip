@@ -62,6 +62,8 @@ struct ModeState {          // one precision mode
     // attn256q_kernel (whole attention block, persistent: gpt_kernels_c256b.h): c_attn + c_proj stream per layer, and the per-workgroup spill slab
     std::vector<uint16_t *> attn256q_pk;
     unsigned char *attn256q_spill = nullptr;
+    // layer 0's q | k | v per (position, token) pair (attn256q_kernel<.., TAB = 2>), built from attn256q_pk[0]; nullptr: MGPT_L0_TABLE=0 or L = 1
+    unsigned char *l0_table = nullptr;
     // register-resident LN+QKV (C = 64 / 160): per layer [tile][k-step][plane][lane][8] of c_attn.weight
     std::vector<uint16_t *> qkv_pk;
     bool qkv_fused = false;
@@ -244,6 +246,30 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
                     MGPT_LAUNCH_CHECK();
                 }
                 MGPT_HIP(hipMalloc(&m->attn256q_spill, (size_t)m->n_cu * 8 * 14 * NP * 1024));
+                // Layer 0 of large calls from a (position, token) table of q | k | v: its input row is etab[position][token], so the row's
+                // LayerNorm and q|k|v projection are a function of the pair.  The table is the output of the EMB kernel itself (TAB = 1) on kV
+                // synthetic rows, row j = token j at every position: every pair in the wave, lane and MFMA slot it has in a real row, so every
+                // entry is bit-identical to what layer 0 computes.  (MGPT_L0_TABLE=0 in the environment keeps the EMB kernel on layer 0.)
+                const char *tab_env = getenv("MGPT_L0_TABLE");
+                if (g->L > 1 && !(tab_env != nullptr && tab_env[0] == '0')) {
+                    ProfScope ps(P_PACK, nullptr);
+                    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP, 0, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, kA256Lds<NP>));
+                    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP, 0, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, kA256Lds<NP>));
+                    MGPT_HIP(hipMalloc(&m->l0_table, (size_t)kT * kV * fastk::kL0TabEntryBytes<NP>));
+                    float *xt = nullptr;
+                    unsigned char *tk = nullptr;
+                    MGPT_HIP(hipMalloc(&xt, (size_t)kV * kT * C * sizeof(float)));
+                    MGPT_HIP(hipMalloc(&tk, (size_t)kV * kT));
+                    for (int j = 0; j < kV; j++) MGPT_HIP(hipMemset(tk + (size_t)j * kT, j, kT));
+                    const float scale_log2e = (1.0f / sqrtf((float)g->hs)) * 1.44269504088896340736f;    // (as forward_chunk)
+                    hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true, 1>), dim3((unsigned)std::min(kV, m->n_cu)), dim3(512), (size_t)kA256Lds<NP>, nullptr, xt,
+                                       m->attn256q_pk[0], m->attn256_inv[0], scale_log2e, m->proj[0].inv_scale, m->attn256q_spill, kV,
+                                       (unsigned long long *)nullptr, tk, g->embed_table, m->l0_table);
+                    MGPT_LAUNCH_CHECK();
+                    MGPT_HIP(hipDeviceSynchronize());
+                    MGPT_HIP(hipFree(xt));
+                    MGPT_HIP(hipFree(tk));
+                }
             }
             MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256_kernel<T, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, kA256Lds<NP>));
         }
@@ -512,6 +538,7 @@ void free_mode(mgpt_gpt *g, ModeState *m)
     for (auto *p : m->attn256_pk) (void)hipFree(p);
     for (auto *p : m->attn256q_pk) (void)hipFree(p);
     (void)hipFree(m->attn256q_spill);
+    (void)hipFree(m->l0_table);
     (void)hipFree(m->gelu_lut);
     for (auto *p : m->qkv_pk) (void)hipFree(p);
     for (auto *p : m->proj_pk) (void)hipFree(p);
@@ -796,7 +823,11 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
             // ---- the whole attention block (LN1, QKV, attention, out-projection, residual) in one persistent kernel: q, k, v, y stay on chip ----
             ProfScope ps(P_ATTN, s);
             // (gpt_kernels_c256b.h: the projection steps and the tail on v_mfma_f32_16x16x32)
-            if (embed256 && l == 0)
+            if (embed256 && l == 0 && m->l0_table != nullptr)        // (q | k | v of layer 0 from the (position, token) table)
+                hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, false, 2>), dim3((unsigned)std::min(rows, m->n_cu)), dim3(512), (size_t)kA256Lds<NP>, s, g->x,
+                                   m->attn256q_pk[l], m->attn256_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn256q_spill, rows,
+                                   (unsigned long long *)nullptr, d_tokens, g->embed_table, m->l0_table);
+            else if (embed256 && l == 0)
                 hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true>), dim3((unsigned)std::min(rows, m->n_cu)), dim3(512), (size_t)kA256Lds<NP>, s, g->x,
                                    m->attn256q_pk[l], m->attn256_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn256q_spill, rows,
                                    (unsigned long long *)nullptr, d_tokens, g->embed_table);

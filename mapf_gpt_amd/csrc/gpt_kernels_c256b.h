@@ -111,12 +111,30 @@ __global__ __launch_bounds__(256) void pack_attn256q_kernel(const float *__restr
 // resident) through the SAME 32 loads per lane with other addresses, and writes them to x from there (the tail's residual read finds them:
 // the same wave's stores, one attention phase earlier).  embed_tiled_kernel (0.75 ms per 12 288 rows: a 3.2-GB write) and the prologue's
 // 3.2-GB read of what it wrote are gone.
-template <class T, int NP, int STAMPS = 0, bool EMB = false>
+// TAB: layer 0 from a per-checkpoint (position, token) table of q | k | v (kL0Tab* below).  In layer 0 a token's q, k and v depend on its
+// (position, token) pair alone -- LayerNorm and the projection act on each token by itself -- so 256 x 67 pairs cover every row.
+//     TAB == 1 (with EMB: the table's BUILD, once per checkpoint and mode): run on synthetic rows, row j = token j at every position, every head
+//              also stores its q planes, k planes and v values -- the very registers this kernel computes, each pair in the wave, lane and
+//              MFMA slot it has in a real row -- to `table`, then waits for them (vmcnt(0): the counted waits of the row stay valid)
+//     TAB == 2 (layer 0 of a large call): no LayerNorm, no projection steps, no spill slab.  Per head the lane loads its q quads (already the
+//              attention phase's B operand), its k quads and v values, writes k and v^T to LDS and runs the attention phase; the y planes of
+//              the eight heads stay in registers (xn).  Only c_proj is streamed (steps 48-63: a ring of period 16), the residual quads come
+//              from etab, and x is written once, by the tail.  x after the block is bit-identical to the EMB instance's.
+// Table entry of a (position, token) pair: [head][q | k | v], 64 NP bytes each:
+//     q  [lane bit 5 = k half][k-step][plane] quads of the attention phase's B operand (lane (query r, half b5) after row_swap)
+//     k  [q = 8-dim block][plane] quads, as written to sK
+//     v  [plane][dim] fp16 / bf16 values
+template <int NP> constexpr int kL0TabHeadBytes = 192 * NP;
+template <int NP> constexpr int kL0TabEntryBytes = 8 * kL0TabHeadBytes<NP>;
+template <class T, int NP, int STAMPS = 0, bool EMB = false, int TAB = 0>
 __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x, const uint16_t *__restrict__ wstream, float inv_scale,
                                                           float scale_log2e, float inv_proj, unsigned char *__restrict__ spill,
                                                           int n_rows, unsigned long long *stamps = nullptr,
-                                                          const unsigned char *__restrict__ tokens = nullptr, const float *__restrict__ etab = nullptr)
+                                                          const unsigned char *__restrict__ tokens = nullptr, const float *__restrict__ etab = nullptr,
+                                                          unsigned char *__restrict__ table = nullptr)
 {
+    static_assert(TAB == 0 || (TAB == 1 && EMB) || (TAB == 2 && !EMB && STAMPS == 0), "table modes");
+    constexpr int HB = kL0TabHeadBytes<NP>, ENT = kL0TabEntryBytes<NP>;
     constexpr int C = 256, KS = 16, NH = 8, HS = 32, NW = 8;
     static_assert(NP == 2 || NP == 1, "planes");
     constexpr int MS = 8;                                  // fragment pairs per step
@@ -138,7 +156,10 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
     // Global addresses are (wave-uniform 64-bit base in SGPRs) + (one of two 32-bit lane offsets) + immediate: 64-bit per-lane
     // pointers for the x rows, the spill slab and the stream cost ~40 registers that this kernel does not have (first build:
     // hipcc hoisted them out of the row loop and spilled 242 dwords per lane to scratch)
-    const unsigned char *wbase = reinterpret_cast<const unsigned char *>(wstream) + (size_t)(wave * PW) * 1024;   // wave-uniform
+    // (TAB == 2 streams c_proj only: the period's last 16 steps)
+    constexpr int PERIOD = TAB == 2 ? kA256oProjSteps : kA256oPeriod;
+    const unsigned char *wbase = reinterpret_cast<const unsigned char *>(wstream) + (size_t)(wave * PW) * 1024 +
+                                 (TAB == 2 ? (size_t)(kA256oPeriod - kA256oProjSteps) * STEP : 0);                         // wave-uniform
     unsigned char *sp_wave = spill + ((size_t)blockIdx.x * NW + wave) * (size_t)(14 * NP * 1024);              // this wave's slab (uniform)
     // chunk-major x ([32-token tile][C / 8 chunks][32 tokens][8 floats]).  Operand side: lane (t, q) owns the 32 bytes of tokens t, 16 + t in chunk 4 kb + q;
     // residual side: the 16 bytes at half q % 2 of chunk 2 fg + q / 2 (header)
@@ -167,7 +188,7 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
         unsigned char *dst = smem + (size_t)slot * STEP + (size_t)(wave * PW) * 1024;
 #pragma unroll
         for (int i = 0; i < PW; i++) dma_piece(src + lane16, dst, std::integral_constant<int, 0>{}, i);
-        r_issue = r_issue + 1 == kA256oPeriod ? 0 : r_issue + 1;
+        r_issue = r_issue + 1 == PERIOD ? 0 : r_issue + 1;
     };
 #pragma unroll
     for (int G = 0; G < NSLOT - 1; G++) issue(G);
@@ -376,8 +397,20 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
     for (int k = 0; k < n_mine; k++) {
         const int64_t b = (int64_t)blockIdx.x + (int64_t)k * gridDim.x;
         unsigned char *xw = reinterpret_cast<unsigned char *>(x + (b * kT + tok0) * C);   // this wave's 32-token tile (uniform), 32 KiB
+        unsigned ent0 = 0, ent1 = 0;                       // TAB == 2: (position, token) pairs of this lane's tokens tok0 + t, tok0 + 16 + t
         // ---- prologue: this lane's two tokens, LayerNorm (two-pass, model.py:19-20), operand planes ----
-        {
+        if constexpr (TAB == 2) {                          // (the table's prologue: the two token ids only)
+            unsigned l16p = lane16;
+            asm volatile("" : "+v"(l16p));
+            const unsigned char *tk = tokens + b * kT + tok0;                                          // uniform
+            const unsigned tt_p = (l16p >> 4) & 15u;
+            unsigned id0, id1;
+            asm volatile("global_load_ubyte %0, %1, %2" : "=v"(id0) : "v"(tt_p), "s"(tk) : "memory");
+            asm volatile("global_load_ubyte %0, %1, %2 offset:16" : "=v"(id1) : "v"(tt_p), "s"(tk) : "memory");
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(id0), "+v"(id1) : : "memory");
+            ent0 = ((unsigned)tok0 + tt_p) * 67u + id0;
+            ent1 = ((unsigned)tok0 + 16u + tt_p) * 67u + id1;
+        } else {
             unsigned l16p = lane16;
             asm volatile("" : "+v"(l16p));
             const unsigned xoff_p = (l16p >> 8) * 1024 + ((l16p >> 4) & 15u) * 32;
@@ -453,8 +486,10 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
             }
         }
         // the first pairs of the row's first step (its slot landed for every wave before the barrier of the step before)
-        lds_pair(nxt_addr, I0{}, wb[0][0]);
-        lds_pair(nxt_addr, I1{}, wb[0][1]);
+        if constexpr (TAB != 2) {
+            lds_pair(nxt_addr, I0{}, wb[0][0]);
+            lds_pair(nxt_addr, I1{}, wb[0][1]);
+        }
         phase(2);
 
         // ---- one head; LASTH (head 7): its output planes stay in registers (xn[14], xn[15]) and the planes of heads 0-6 are
@@ -489,6 +524,15 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
 #pragma unroll
                 for (int wd = 0; wd < 4; wd++) { unsigned a = qf[0][pl][wd], b2 = qf[1][pl][wd]; row_swap(a, b2); qf[0][pl][wd] = a; qf[1][pl][wd] = b2; }
             if (NP == 1) { qf[0][1] = qf[0][0]; qf[1][1] = qf[1][0]; }
+            // (TAB == 1: row b holds token b at every position; the lane's q is query r = lane % 32, half lane / 32)
+            if constexpr (TAB == 1) {
+                const unsigned voff = (((unsigned)tok0 + rr) * 67u * ENT) + (unsigned)b * ENT + (unsigned)hd * HB + hh * (32 * NP);
+#pragma unroll
+                for (int ks = 0; ks < 2; ks++)
+#pragma unroll
+                    for (int pl = 0; pl < NP; pl++)
+                        asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 1" ::"v"(voff), "v"(qf[ks][pl]), "s"(table), "n"((ks * NP + pl) * 16) : "memory");
+            }
             {   // k -> sK[pl][key = tok0 + 16 tg + t][dims 8 q ..]   (all waves passed this head's step syncs: the head before -- or the
                 // row before -- has finished its attention everywhere)
                 u32x4 kp[2][2];
@@ -499,6 +543,15 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
 #pragma unroll
                     for (int pl = 0; pl < NP; pl++)
                         asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(kw_addr), "v"(kp[tg][pl]), "n"(pl * kT * KROW + tg * 16 * KROW) : "memory");
+                if constexpr (TAB == 1) {                  // token tok0 + 16 tg + t, dims 8 q ..
+#pragma unroll
+                    for (int tg = 0; tg < 2; tg++) {
+                        const unsigned voff = (((unsigned)tok0 + 16u * tg + tt) * 67u * ENT) + (unsigned)b * ENT + (unsigned)hd * HB + 64 * NP + qq * (16 * NP);
+#pragma unroll
+                        for (int pl = 0; pl < NP; pl++)
+                            asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 1" ::"v"(voff), "v"(kp[tg][pl]), "s"(table), "n"(pl * 16) : "memory");
+                    }
+                }
             }
             // ---- steps 4-5: v quads (natural: lane = d = 16 dg + t, registers 4 (2 tg + dg) + i = token 16 tg + 4 q + i) ----
             f32x16 va;                                     // (started from zero by the first chunk)
@@ -543,8 +596,21 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
 #pragma unroll
                     for (int pl = 0; pl < NP; pl++)
                         asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(vw_addr), "v"(vp[pl]), "n"(pl * HS * VROW + (sl & 1) * 16 * VROW + (sl >> 1) * 32) : "memory");
+                    if constexpr (TAB == 1) {              // tokens tok0 + 16 tg + 4 q + i (i = 0..3: low / high halves of vp[pl][0], vp[pl][1]), dim 16 dg + t
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            const unsigned voff = (((unsigned)tok0 + 16u * (sl >> 1) + 4u * qq + i) * 67u * ENT) + (unsigned)b * ENT + (unsigned)hd * HB + 128 * NP +
+                                                  (16u * (sl & 1) + tt) * 2u;
+#pragma unroll
+                            for (int pl = 0; pl < NP; pl++) {
+                                if (i & 1) asm volatile("global_store_short_d16_hi %0, %1, %2 offset:%3" ::"v"(voff), "v"(vp[pl][i >> 1]), "s"(table), "n"(pl * 64) : "memory");
+                                else asm volatile("global_store_short %0, %1, %2 offset:%3" ::"v"(voff), "v"(vp[pl][i >> 1]), "s"(table), "n"(pl * 64) : "memory");
+                            }
+                        }
+                    }
                 }
             }
+            if constexpr (TAB == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the table stores retire here: a smaller count is always safe)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             phase(3);
             __builtin_amdgcn_s_barrier();                  // k, v^T of the head complete
@@ -582,9 +648,84 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
             }
             phase(4);
         };
+        // ---- TAB == 2: one head from the table.  The y planes go to xn[7], xn[15] after those of the heads before have moved down one place
+        //      (a rolled loop has fixed registers: 16 NP moves per head; after the eighth, xn[hd], xn[8 + hd] hold head hd as in the tail's order) ----
+        auto head_t = [&](int hd) {
+            unsigned l16 = lane16;
+            asm volatile("" : "+v"(l16));
+            const unsigned rr = (l16 >> 4) & 31u, hh = l16 >> 9;
+            const unsigned kr_addr = sK + rr * KROW + hh * 16;
+            const unsigned vr_addr = sV + rr * VROW + hh * 16;
+            const unsigned tt = (l16 >> 4) & 15u, qq = l16 >> 8;
+            const unsigned kw_addr = sK + ((unsigned)tok0 + tt) * KROW + qq * 16;
+            // v write side: key tok0 + 16 tg + t at its slot (bits 2 and 3 of t swapped: the phase's key order), dims 8 q + j
+            const unsigned vt_addr = sV + qq * 8 * VROW + (unsigned)wave * 64 + (((tt >> 2) & 1u) * 8 + ((tt >> 3) & 1u) * 4 + (tt & 3u)) * 2;
+            const unsigned hoff = (unsigned)hd * HB;
+            const unsigned e0 = ent0 * ENT + hoff, e1 = ent1 * ENT + hoff;
+            const unsigned qoff = ((qq & 1u) ? e1 : e0) + hh * (32 * NP);                       // query r = t + 16 (q % 2)
+            u32x4 qf[2][2], kp[2][2], vq[2][2];
+#pragma unroll
+            for (int ks = 0; ks < 2; ks++)
+#pragma unroll
+                for (int pl = 0; pl < NP; pl++)
+                    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(qf[ks][pl]) : "v"(qoff), "s"(table), "n"((ks * NP + pl) * 16) : "memory");
+#pragma unroll
+            for (int tg = 0; tg < 2; tg++) {
+                const unsigned ko = (tg ? e1 : e0) + qq * (16 * NP), vo = (tg ? e1 : e0) + qq * 16;
+#pragma unroll
+                for (int pl = 0; pl < NP; pl++) {
+                    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(kp[tg][pl]) : "v"(ko), "s"(table), "n"(64 * NP + pl * 16) : "memory");
+                    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(vq[tg][pl]) : "v"(vo), "s"(table), "n"(128 * NP + pl * 64) : "memory");
+                }
+            }
+            // every wave is done with the head before's K and V^T (its attention phase ended before this barrier); then the quads have landed
+            // (nothing else is in flight: the ring pieces of the tail's first steps were issued before the row's token ids, which waited for them)
+            __builtin_amdgcn_s_barrier();
+            if constexpr (NP == 2)
+                asm volatile("s_waitcnt vmcnt(0)" : "+v"(qf[0][0]), "+v"(qf[0][1]), "+v"(qf[1][0]), "+v"(qf[1][1]), "+v"(kp[0][0]), "+v"(kp[0][1]), "+v"(kp[1][0]), "+v"(kp[1][1]),
+                             "+v"(vq[0][0]), "+v"(vq[0][1]), "+v"(vq[1][0]), "+v"(vq[1][1]) : : "memory");
+            else
+                asm volatile("s_waitcnt vmcnt(0)" : "+v"(qf[0][0]), "+v"(qf[1][0]), "+v"(kp[0][0]), "+v"(kp[1][0]), "+v"(vq[0][0]), "+v"(vq[1][0]) : : "memory");
+            if (NP == 1) { qf[0][1] = qf[0][0]; qf[1][1] = qf[1][0]; }
+#pragma unroll
+            for (int tg = 0; tg < 2; tg++)
+#pragma unroll
+                for (int pl = 0; pl < NP; pl++) {
+                    asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(kw_addr), "v"(kp[tg][pl]), "n"(pl * kT * KROW + tg * 16 * KROW) : "memory");
+#pragma unroll
+                    for (int j = 0; j < 8; j++) {         // dim 8 q + j: low / high half of word j / 2
+                        if (j & 1) asm volatile("ds_write_b16_d16_hi %0, %1 offset:%2" ::"v"(vt_addr), "v"(vq[tg][pl][j >> 1]), "n"(pl * HS * VROW + j * VROW + tg * 32) : "memory");
+                        else asm volatile("ds_write_b16 %0, %1 offset:%2" ::"v"(vt_addr), "v"(vq[tg][pl][j >> 1]), "n"(pl * HS * VROW + j * VROW + tg * 32) : "memory");
+                    }
+                }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();                  // k, v^T of the head complete
+            f32x16 o;
+            float l_run = 0.f;
+            attention_tiles<T, NP, KROW, VROW, HS>(kr_addr, vr_addr, qf, lane, o, l_run);
+            const float inv = inv_scale / l_run;
+#pragma unroll
+            for (int g = 0; g < 16; g++) o[g] *= inv;
+#pragma unroll
+            for (int g = 0; g < 8; g++) { float a = o[g], b2 = o[8 + g]; asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b2)); o[g] = a; o[8 + g] = b2; }
+#pragma unroll
+            for (int k2 = 0; k2 < 7; k2++)
+#pragma unroll
+                for (int pl = 0; pl < NP; pl++) { xn[k2][pl] = xn[k2 + 1][pl]; xn[8 + k2][pl] = xn[9 + k2][pl]; }
+            pack_octet(o, 0, xn[7]);
+            pack_octet(o, 1, xn[15]);
+        };
+        if constexpr (TAB == 2) {
 #pragma unroll 1
-        for (int hd = 0; hd < NH - 1; hd++) head(hd, std::false_type{});
-        head(NH - 1, std::true_type{});
+            for (int hd = 0; hd < NH; hd++) head_t(hd);
+            // the first pairs of the tail's first step (its slot landed for every wave at the row before's last step)
+            lds_pair(nxt_addr, I0{}, wb[0][0]);
+            lds_pair(nxt_addr, I1{}, wb[0][1]);
+        } else {
+#pragma unroll 1
+            for (int hd = 0; hd < NH - 1; hd++) head(hd, std::false_type{});
+            head(NH - 1, std::true_type{});
+        }
 
         // ---- tail: x <- x + y c_proj^T.  Pseudo-head t = output features 64 t .. 64 t + 63 (four groups of 16) over K = 256 in
         //      four q|k-shaped steps; their residual quads are requested at its first step ----
@@ -599,18 +740,30 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
             unsigned l16t = lane16;
             asm volatile("" : "+v"(l16t));
             const unsigned xoff_t = (l16t >> 9) * 1024 + ((l16t >> 4) & 15u) * 32 + ((l16t >> 8) & 1u) * 16;
+            const unsigned qq_t = l16t >> 8;
             f32x4 xs[4][2];                                // residual quads: [feature group fgl][token group]
             unsigned char *xp = xw + (size_t)t * 8192;     // feature group 4 t + fgl: chunks 8 t + 2 fgl, + 1
             constexpr int OTHERS = 8;                      // vector-memory operations of this pseudo-head's first step besides ring pieces
             auto requests = [&]() {
+                if constexpr (TAB == 2) {                  // from etab: features 64 t + 16 fgl + 4 q .. of the (position, token) rows of tokens t, 16 + t
+                    const unsigned r0 = ent0 * (C * 4) + (unsigned)t * 256 + qq_t * 16, r1 = ent1 * (C * 4) + (unsigned)t * 256 + qq_t * 16;
+                    const unsigned char *eb = reinterpret_cast<const unsigned char *>(etab);
+#pragma unroll
+                    for (int fgl = 0; fgl < 4; fgl++) {
+                        asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(xs[fgl][0]) : "v"(r0), "s"(eb), "n"(fgl * 64) : "memory");
+                        asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(xs[fgl][1]) : "v"(r1), "s"(eb), "n"(fgl * 64) : "memory");
+                    }
+                    return;
+                }
 #pragma unroll
                 for (int fgl = 0; fgl < 4; fgl++)
 #pragma unroll
                     for (int tg = 0; tg < 2; tg++)
                         asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(xs[fgl][tg]) : "v"(xoff_t), "s"(xp + (fgl >> 1) * 4096), "n"((fgl & 1) * 2048 + tg * 512) : "memory");
             };
-            // step 0: pieces waited for are followed by 2 x PW pieces and [FIRST: the 28 spill loads | else: the 8 stores of the pseudo-head before]
-            step_pair(I0{}, std::integral_constant<int, 2 * PW + (FIRST ? NYLD : 8)>{}, requests, std::true_type{});
+            // step 0: pieces waited for are followed by 2 x PW pieces and [FIRST: the 28 spill loads (TAB == 2: nothing in flight, the heads waited
+            // for all) | else: the 8 stores of the pseudo-head before]
+            step_pair(I0{}, std::integral_constant<int, 2 * PW + (FIRST ? (TAB == 2 ? 0 : NYLD) : 8)>{}, requests, std::true_type{});
             step_pair(I1{}, std::integral_constant<int, 2 * PW + 8 + OTHERS>{}, nothing, std::true_type{});
             step_pair(I2{}, std::integral_constant<int, 2 * PW + 8 + OTHERS>{}, nothing, std::true_type{});
             step_pair(I3{}, P4{}, nothing, std::integral_constant<bool, !LASTT>{});
