@@ -210,6 +210,21 @@ int mgpt_gpt_forward(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, float *d_
  * kernels whatever the model's usual precision: the hot path (tokenizer rows, inference.py:145) is 256 tokens and never comes here. */
 int mgpt_gpt_forward_t(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int T, float *d_logits, void *stream);
 
+/* = GPT.forward(idx, targets) (model.py:167-184): logits of EVERY position + cross-entropy terms of the targeted ones.
+ * d_logits [rows][T][67] fp32 or NULL; d_targets int32 [rows][T] (-1 = ignored, model.py:183) or NULL;
+ * d_row_nll [rows] fp32 = sum over the row's targeted positions of -log softmax(logits)[target], d_row_count [rows] int32
+ * (both NULL iff d_targets is).  T == 256: the kernels of `precision` (resolved as by mgpt_gpt_forward); T < 256: exact fp32.
+ * Targets outside [-1, 67): NaN. */
+int mgpt_gpt_forward_seq(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int T, float *d_logits, const int32_t *d_targets,
+                         float *d_row_nll, int32_t *d_row_count, int precision, void *stream);
+
+/* Scoring against one action per row (dataset gt_actions: targets -1 except position 255, fast_data_loader.py:34,58):
+ * the forward of mgpt_gpt_forward (last-layer shortcut, same kernels, same logits), then d_row_nll[r] = -log softmax(logits[r])[target[r]]
+ * over all 67 logits and d_row_hit[r] = (greedy action of mgpt_gpt_act(do_sample = 0) == target[r]).  d_logits [rows][67] optional.
+ * Targets outside [0, 67): NaN, no hit. */
+int mgpt_gpt_score_last(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, const int32_t *d_targets, float *d_row_nll,
+                        int32_t *d_row_hit, float *d_logits, int precision, void *stream);
+
 /* = GPT.act (model.py:244-260): softmax over logits[:5]; do_sample != 0 draws from it with the
  * library's counter-based RNG keyed by (seed, step, row0 + row) -- torch.multinomial's stream is
  * device-specific and not reproduced -- else arg-max.  row0 = GLOBAL id of this call's first row, so

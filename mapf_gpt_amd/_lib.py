@@ -71,6 +71,8 @@ SYMBOLS = {
     "mgpt_gpt_finalize": (_i, [_vp]),
     "mgpt_gpt_forward": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
     "mgpt_gpt_forward_t": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "mgpt_gpt_forward_seq": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mgpt_gpt_score_last": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "mgpt_gpt_act": (_i, [_vp, _vp, _i, _vp, _vp, _i, _u64, _u64, _u64, _i, _vp]),
     "mgpt_gpt_act_dev": (_i, [_vp, _vp, _i, _vp, _vp, _i, _u64, _vp, _u64, _i, _vp]),
     "mgpt_step_create": (_i, [_pp, _vp, _vp, _vp, _i, _i, _i, _u64, _u64]),

@@ -52,6 +52,7 @@ enum ProfId {
     P_EMBED, P_LAYERNORM, P_GEMM_QKV, P_ATTN, P_GEMM_PROJ, P_GEMM_FC, P_GEMM_PROJ2, P_MLP_FUSED,
     P_HEAD, P_SAMPLE, P_PACK, P_LNQKV_FUSED,
     P_ATTN_LAST, P_GEMM_PROJ_LAST, P_MLP_FUSED_LAST,    // the last layer's launches (token 255 only, model.py:186): timed apart from the full ones
+    P_HEAD_SEQ, P_SCORE,                                // ln_f + head + cross-entropy of every position (mgpt_gpt_forward_seq), last-position scoring
     P_COUNT
 };
 

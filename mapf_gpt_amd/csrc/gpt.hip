@@ -5,6 +5,7 @@
 #include "common.h"
 #include "gpt_ctx.h"
 #include "gpt_kernels_f32.h"
+#include "gpt_kernels_seq.h"
 
 using namespace mgpt;
 
@@ -314,6 +315,27 @@ int gpt_launch_head(mgpt_gpt *g, int rows, float *d_logits, hipStream_t s)
     return gpt_launch_head_at(g, g->x, (int64_t)kT * g->C, (int64_t)(kT - 1) * g->C, rows, d_logits, s);
 }
 
+int gpt_launch_head_seq(mgpt_gpt *g, const float *x, bool tiled, int rows, int T, const SeqOut &o, hipStream_t s)
+{
+    ProfScope ps(P_HEAD_SEQ, s);
+    const size_t lds = seqk::seq_lds_bytes(g->C);
+    int dev = 0, n_cu = 256;
+    MGPT_HIP(hipGetDevice(&dev));
+    MGPT_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    const dim3 grid((unsigned)std::min(rows, std::max(1, n_cu)));      // one workgroup per CU walks the rows (results do not depend on the grid)
+    const float *lnf = g->params + g->off_lnf, *wte = g->params + g->off_wte;
+    const float *lnf_b = g->has_bias ? (const float *)(g->bias + g->off_lnf_b) : (const float *)nullptr;
+    if (tiled) {
+        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&seqk::head_seq_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(seqk::head_seq_kernel<1>, grid, dim3(512), lds, s, x, lnf, lnf_b, wte, g->C, rows, T, o.logits, o.targets, o.row_nll, o.row_count);
+    } else {
+        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&seqk::head_seq_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(seqk::head_seq_kernel<0>, grid, dim3(512), lds, s, x, lnf, lnf_b, wte, g->C, rows, T, o.logits, o.targets, o.row_nll, o.row_count);
+    }
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
 // ----- fp32 forward -----
 template <int EPI>
 static int launch_gemm(const float *A, const float *W, float *out, int64_t M, int N, int K, f32k::EpiArgs ep, int C,
@@ -353,7 +375,9 @@ static int launch_layernorm(const float *x, const float *w, const float *b, floa
 // T = tokens per row (kT on the hot path; mgpt_gpt_forward_t: any T <= block_size).  M = rows * T tokens; the GEMMs run on Mp = M rounded up to
 // their 128-token tile -- the padding rows of the workspaces hold whatever an earlier call left there, every token's arithmetic is its own, and
 // the one kernel that mixes tokens (attention) and the q|k|v scatter look at the first M only
-static int forward_f32_chunk(mgpt_gpt *g, const uint8_t *d_tokens, int rows, float *d_logits, hipStream_t s, int T = kT)
+// seq != NULL: ln_f + head + cross-entropy on every position instead of the last one's logits (mgpt_gpt_forward_seq; d_logits unused)
+static int forward_f32_chunk(mgpt_gpt *g, const uint8_t *d_tokens, int rows, float *d_logits, hipStream_t s, int T = kT,
+                             const SeqOut *seq = nullptr)
 {
     const int C = g->C;
     const int64_t M = (int64_t)rows * T, Mp = (M + 127) / 128 * 128;
@@ -404,6 +428,7 @@ static int forward_f32_chunk(mgpt_gpt *g, const uint8_t *d_tokens, int rows, flo
             if ((rc = launch_gemm<f32k::EPI_RESID>(g->hbuf, P + lo.proj2_w, g->x, Mp, C, 4 * C, ep, C, s)) != MGPT_OK) return rc;
         }
     }
+    if (seq != nullptr) return gpt_launch_head_seq(g, g->x, false, rows, T, *seq, s);
     if (T == kT) return gpt_launch_head(g, rows, d_logits, s);
     return gpt_launch_head_at(g, g->x, (int64_t)T * C, (int64_t)(T - 1) * C, rows, d_logits, s);      // the last position of a T-token row (model.py:186)
 }
@@ -485,14 +510,10 @@ static int envelope_decide(mgpt_gpt *g, hipStream_t s)
     return MGPT_OK;
 }
 
-// call_rows: rows of the C-ABI call these rows belong to (mgpt_gpt_act chunks its rows itself), see gpt_ctx.h
-static int gpt_forward_impl(mgpt_gpt *g, const uint8_t *d_tokens, int rows, float *d_logits, int precision, void *stream, int call_rows)
+// The kernels a request of `precision` runs on (mgpt_gpt_forward, mgpt_gpt_forward_seq): bias refusal, envelope policy, fallback to fp32
+static int resolve_precision(mgpt_gpt *g, int *precision_io, hipStream_t s)
 {
-    MGPT_REQUIRE(g && d_tokens && d_logits, MGPT_ERR_ARG, "NULL argument");
-    MGPT_REQUIRE(rows > 0, MGPT_ERR_ARG, "rows=%d", rows);
-    MGPT_REQUIRE(g->finalized, MGPT_ERR_STATE, "mgpt_gpt_finalize must precede forward");
-    MGPT_REQUIRE(g->block == kT, MGPT_ERR_UNSUPPORTED, "this entry point takes 256-token rows and the model's block_size is %d: mgpt_gpt_forward_t", g->block);
-    hipStream_t s = (hipStream_t)stream;
+    int precision = *precision_io;
     // bias = True checkpoints: only the exact-fp32 kernels carry the bias terms.  MGPT_PREC_F16X3 under the fallback policy is served by them
     // (the checkpoint counts as outside the envelope, mgpt_gpt_finalize); every other 16-bit request is refused -- it would be wrong, not imprecise
     MGPT_REQUIRE(!g->has_bias || precision == MGPT_PREC_F32 || (precision == MGPT_PREC_F16X3 && g->env_policy == MGPT_ENVELOPE_FALLBACK),
@@ -518,6 +539,22 @@ static int gpt_forward_impl(mgpt_gpt *g, const uint8_t *d_tokens, int rows, floa
             }
             precision = MGPT_PREC_F32;
         }
+    }
+    *precision_io = precision;
+    return MGPT_OK;
+}
+
+// call_rows: rows of the C-ABI call these rows belong to (mgpt_gpt_act chunks its rows itself), see gpt_ctx.h
+static int gpt_forward_impl(mgpt_gpt *g, const uint8_t *d_tokens, int rows, float *d_logits, int precision, void *stream, int call_rows)
+{
+    MGPT_REQUIRE(g && d_tokens && d_logits, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(rows > 0, MGPT_ERR_ARG, "rows=%d", rows);
+    MGPT_REQUIRE(g->finalized, MGPT_ERR_STATE, "mgpt_gpt_finalize must precede forward");
+    MGPT_REQUIRE(g->block == kT, MGPT_ERR_UNSUPPORTED, "this entry point takes 256-token rows and the model's block_size is %d: mgpt_gpt_forward_t", g->block);
+    hipStream_t s = (hipStream_t)stream;
+    {
+        const int rc = resolve_precision(g, &precision, s);
+        if (rc != MGPT_OK) return rc;
     }
     for (int r0 = 0; r0 < rows; r0 += g->max_rows) {
         const int n = std::min(g->max_rows, rows - r0);
@@ -596,4 +633,63 @@ extern "C" int mgpt_gpt_act_dev(mgpt_gpt *g, const uint8_t *d_tokens, int rows, 
 {
     MGPT_REQUIRE(d_step, MGPT_ERR_ARG, "NULL step counter");
     return gpt_act_impl(g, d_tokens, rows, d_actions, d_logits, do_sample, seed, 0, d_step, row0, precision, stream);
+}
+
+// = GPT.forward(idx, targets) (model.py:167-184): the last layer and the head at EVERY position, logits [rows][T][67] and the cross-entropy
+// terms of the targeted positions per row.  T == 256: the kernels of `precision` (resolved as mgpt_gpt_forward does; chunks of max_rows rows, the
+// call's row count picks the kernels as there); T < 256: the exact-fp32 kernels (as mgpt_gpt_forward_t)
+extern "C" int mgpt_gpt_forward_seq(mgpt_gpt *g, const uint8_t *d_tokens, int rows, int T, float *d_logits, const int32_t *d_targets,
+                                    float *d_row_nll, int32_t *d_row_count, int precision, void *stream)
+{
+    MGPT_REQUIRE(g && d_tokens, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(rows > 0, MGPT_ERR_ARG, "rows=%d", rows);
+    MGPT_REQUIRE((d_targets == nullptr) == (d_row_nll == nullptr) && (d_targets == nullptr) == (d_row_count == nullptr), MGPT_ERR_ARG,
+                 "d_targets, d_row_nll and d_row_count are given together or not at all");
+    MGPT_REQUIRE(d_logits || d_targets, MGPT_ERR_ARG, "neither logits nor targets: nothing to compute");
+    MGPT_REQUIRE(g->finalized, MGPT_ERR_STATE, "mgpt_gpt_finalize must precede forward");
+    MGPT_REQUIRE(T >= 1 && T <= g->block, MGPT_ERR_ARG, "cannot forward sequence of length %d, block size is only %d (model.py:170)", T, g->block);
+    hipStream_t s = (hipStream_t)stream;
+    const bool full = T == kT;                  // (then g->block == kT too)
+    if (full) {
+        const int rc = resolve_precision(g, &precision, s);
+        if (rc != MGPT_OK) return rc;
+    } else {
+        precision = MGPT_PREC_F32;
+    }
+    for (int r0 = 0; r0 < rows; r0 += g->max_rows) {
+        const int n = std::min(g->max_rows, rows - r0);
+        const size_t t0 = (size_t)r0 * T;
+        SeqOut o;
+        o.logits = d_logits ? d_logits + t0 * kV : nullptr;
+        o.targets = d_targets ? d_targets + t0 : nullptr;
+        o.row_nll = d_row_nll ? d_row_nll + r0 : nullptr;
+        o.row_count = d_row_count ? d_row_count + r0 : nullptr;
+        int rc;
+        if (precision == MGPT_PREC_F32) rc = forward_f32_chunk(g, d_tokens + t0, n, nullptr, s, T, &o);
+        else rc = gpt_fast_forward(g, d_tokens + t0, n, nullptr, precision, s, rows, &o);
+        if (rc != MGPT_OK) return rc;
+    }
+    return MGPT_OK;
+}
+
+// Scoring against one action per row (dataset gt_actions): the forward of mgpt_gpt_act (same chunks, same kernels, same logits), then
+// -log softmax(logits)[target] over all 67 logits and whether the greedy action of act(do_sample = 0) equals the target
+extern "C" int mgpt_gpt_score_last(mgpt_gpt *g, const uint8_t *d_tokens, int rows, const int32_t *d_targets, float *d_row_nll,
+                                   int32_t *d_row_hit, float *d_logits, int precision, void *stream)
+{
+    MGPT_REQUIRE(g && d_tokens && d_targets && d_row_nll && d_row_hit, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(rows > 0, MGPT_ERR_ARG, "rows=%d", rows);
+    MGPT_REQUIRE(g->finalized, MGPT_ERR_STATE, "mgpt_gpt_finalize must precede forward");
+    hipStream_t s = (hipStream_t)stream;
+    for (int r0 = 0; r0 < rows; r0 += g->max_rows) {          // (as gpt_act_impl)
+        const int n = std::min(g->max_rows, rows - r0);
+        float *lg = d_logits ? d_logits + (size_t)r0 * kV : g->logits_tmp;
+        int rc = gpt_forward_impl(g, d_tokens + (size_t)r0 * kT, n, lg, precision, stream, rows);
+        if (rc != MGPT_OK) return rc;
+        ProfScope ps(P_SCORE, s);
+        hipLaunchKernelGGL(seqk::score_last_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, lg, n, d_targets + r0, d_row_nll + r0, d_row_hit + r0,
+                           MGPT_NUM_ACTIONS);
+        MGPT_LAUNCH_CHECK();
+    }
+    return MGPT_OK;
 }

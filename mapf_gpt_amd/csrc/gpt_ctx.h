@@ -49,15 +49,28 @@ struct mgpt_gpt {
 // block, one-launch last layer): gpt_fast.hip, DESIGN.md section 3.2
 constexpr int kSmallRows = 128;
 
+// outputs of a sequence forward (mgpt_gpt_forward_seq) for one chunk of rows: logits of every position [rows][T][67] or NULL; targets [rows][T]
+// (-1 = ignored) with the per-row sum of the targeted positions' -log softmax and their count, or all three NULL
+struct SeqOut {
+    float *logits = nullptr;
+    const int32_t *targets = nullptr;
+    float *row_nll = nullptr;
+    int32_t *row_count = nullptr;
+};
+
 // gpt_fast.hip: 16-bit-MFMA path (packed operand planes, own workspace)
 int gpt_fast_finalize(mgpt_gpt *g);
 void gpt_fast_destroy(mgpt_gpt *g);
 // call_rows = rows of the whole C-ABI call this chunk belongs to: path choices that change the arithmetic (the head-parallel small-launch
-// kernels) are made from it, so that every chunk of one call -- a ragged remainder included -- runs the same kernels
-int gpt_fast_forward(mgpt_gpt *g, const uint8_t *d_tokens, int rows, float *d_logits, int precision, hipStream_t s, int call_rows);
+// kernels) are made from it, so that every chunk of one call -- a ragged remainder included -- runs the same kernels.
+// seq != NULL: the last layer runs at every position (the kernels of layers 0 .. L-2) and gpt_launch_head_seq replaces the head; d_logits unused
+int gpt_fast_forward(mgpt_gpt *g, const uint8_t *d_tokens, int rows, float *d_logits, int precision, hipStream_t s, int call_rows,
+                     const SeqOut *seq = nullptr);
 int gpt_fast_debug_copy(mgpt_gpt *g, int precision, int which, void *d_out, int64_t nbytes, hipStream_t s);
 
 // gpt.hip: final LayerNorm + tied lm_head on the last position of g->x (shared by both paths)
 int gpt_launch_head(mgpt_gpt *g, int rows, float *d_logits, hipStream_t s);
 int gpt_launch_head_at(mgpt_gpt *g, const float *xsrc, int64_t row_stride, int64_t row_offset, int rows, float *d_logits,
                        hipStream_t s);
+// gpt.hip: ln_f + head + cross-entropy on EVERY position of rows x T tokens of x (tiled: fastk::xt_off layout), seqk::head_seq_kernel
+int gpt_launch_head_seq(mgpt_gpt *g, const float *x, bool tiled, int rows, int T, const SeqOut &o, hipStream_t s);

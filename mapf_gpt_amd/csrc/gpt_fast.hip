@@ -680,7 +680,8 @@ int launch_row_stats(const float *x, float2 *stats, int64_t n_tok, int C, hipStr
 }
 
 template <class T, int NP>
-int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, float *d_logits, hipStream_t s, int call_rows)
+int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, float *d_logits, hipStream_t s, int call_rows,
+                  const SeqOut *seq = nullptr)
 {
     const int C = g->C;
     const int64_t M = (int64_t)rows * kT;
@@ -750,7 +751,9 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
         a.w_hi = m->attn[l].hi; a.w_lo = m->attn[l].lo; a.out_scale = m->attn[l].inv_scale;
         a.N = 2 * C; a.o_hi = m->qk[0]; a.o_lo = m->qk[1];
         // last layer: only token 255 is needed downstream (model.py:186) -> compact buffer, MLP and head on `rows` tokens
-        const bool last_short = (attn_block || m->pk_gemm) && l == g->L - 1;
+        // (a sequence forward, seq != NULL, needs every position: its last layer runs the kernels of the layers before)
+        const bool full_last = seq != nullptr;
+        const bool last_short = (attn_block || m->pk_gemm) && l == g->L - 1 && !full_last;
         const int rows_pad = ((rows + 255) / 256) * 256;
         // 6M shape, every layer but the last: attn256q_kernel does the out-projection and the residual add itself
         // ... unless the CALL is small (one environment, rows <= kSmallRows): then a row's eight heads run on eight CUs at once
@@ -1009,6 +1012,7 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
         }
         if (!fused_stats(C) && l + 1 < g->L && (rc = launch_row_stats(g->x, m->stats, M, C, s)) != MGPT_OK) return rc;
     }
+    if (seq != nullptr) return gpt_launch_head_seq(g, g->x, m->x_tiled, rows, kT, *seq, s);     // every position of the full residual stream
     if (m->x_tiled) {
         {
             ProfScope ps(P_HEAD, s);
@@ -1056,7 +1060,8 @@ void gpt_fast_destroy(mgpt_gpt *g)
     g->embed_table = nullptr;
 }
 
-int gpt_fast_forward(mgpt_gpt *g, const uint8_t *d_tokens, int rows, float *d_logits, int precision, hipStream_t s, int call_rows)
+int gpt_fast_forward(mgpt_gpt *g, const uint8_t *d_tokens, int rows, float *d_logits, int precision, hipStream_t s, int call_rows,
+                     const SeqOut *seq)
 {
     MGPT_REQUIRE(precision == MGPT_PREC_F16X3 || precision == MGPT_PREC_BF16, MGPT_ERR_ARG, "unknown precision %d", precision);
     FastState *f = static_cast<FastState *>(g->fast);
@@ -1074,8 +1079,8 @@ int gpt_fast_forward(mgpt_gpt *g, const uint8_t *d_tokens, int rows, float *d_lo
         }
         if (rc != MGPT_OK) { free_mode(g, m); return rc; }         // no half-built planes survive a failed build (e.g. out of memory)
     }
-    if (precision == MGPT_PREC_F16X3) return forward_chunk<fastk::F16T, 2>(g, m, d_tokens, rows, d_logits, s, call_rows);
-    return forward_chunk<fastk::BF16T, 1>(g, m, d_tokens, rows, d_logits, s, call_rows);
+    if (precision == MGPT_PREC_F16X3) return forward_chunk<fastk::F16T, 2>(g, m, d_tokens, rows, d_logits, s, call_rows, seq);
+    return forward_chunk<fastk::BF16T, 1>(g, m, d_tokens, rows, d_logits, s, call_rows, seq);
 }
 
 // test/debug: raw copy of a fast-path workspace buffer of the given precision

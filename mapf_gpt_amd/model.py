@@ -3,8 +3,10 @@
 `GPTConfig` / `GPT` keep the reference's names and call shapes for the inference surface:
     GPT(config); load_state_dict(sd, strict=False); to(device); eval();
     forward(idx) -> (logits [B,1,67], None)        (model.py:167-189, last position only)
+    forward(idx, targets) -> (logits [B,T,67], loss)  (model.py:180-184: every position, cross-entropy with ignore_index=-1)
     act(idx, do_sample=True, generator=None) -> LongTensor [B]   (model.py:244-260)
 plus the device-resident fast path `act_tokens(tokens_u8, ...)` used by the batched runner.
+`score_tokens` and mapf_gpt_amd/scoring.py score a checkpoint on expert data (train.py estimate_loss).
 Training helpers of the reference (configure_optimizers, estimate_mfu, crop_block_size) are out of
 scope.  Every compute call goes through the C ABI; there is no
 PyTorch forward here.
@@ -179,10 +181,52 @@ class GPT:
         return out
 
     def forward(self, idx, targets=None):
-        if targets is not None:
-            raise NotImplementedError("training loss is out of scope (inference path only)")
-        logits = self._logits(self._tokens_u8(idx))
-        return logits[:, None, :], None
+        tokens = self._tokens_u8(idx)
+        if targets is None:
+            logits = self._logits(tokens)
+            return logits[:, None, :], None
+        return self._forward_seq(tokens, targets)
+
+    def _forward_seq(self, tokens, targets):
+        # model.py:180-184: lm_head on every position, F.cross_entropy(logits.view(-1, 67), targets.view(-1), ignore_index=-1).  Evaluation only:
+        # no graph, no backward (train.py:244-257 estimate_loss runs it under no_grad)
+        assert self._loaded, "load_state_dict first"
+        B, T = tokens.shape
+        targets = torch.as_tensor(targets)
+        if targets.dtype.is_floating_point or targets.dtype == torch.bool or targets.numel() != B * T:
+            raise ValueError(f"targets must be an integer tensor of {B * T} elements (idx is {B} x {T}), got {targets.dtype} {tuple(targets.shape)}")
+        if targets.numel() and (int(targets.min()) < -1 or int(targets.max()) >= 67):
+            raise ValueError("targets must lie in [-1, 67): -1 is ignored (ignore_index=-1), 0 .. 66 are vocabulary ids")
+        tg = targets.reshape(B, T).to(device=self.device, dtype=torch.int32).contiguous()
+        logits = torch.empty((B, T, 67), dtype=torch.float32, device=self.device)
+        nll = torch.empty((B,), dtype=torch.float32, device=self.device)
+        cnt = torch.empty((B,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mgpt_gpt_forward_seq(self._h, _lib.ptr(tokens), B, T, _lib.ptr(logits), _lib.ptr(tg), _lib.ptr(nll), _lib.ptr(cnt),
+                                                       self._prec(None), _lib.stream_ptr()))
+        # mean over the targeted positions; 0 / 0 = NaN when every target is -1, as F.cross_entropy gives
+        loss = (nll.double().sum() / cnt.sum().double()).float()
+        return logits, loss
+
+    def score_tokens(self, tokens_u8, actions, precision=None, logits_out=None):
+        """Scoring of 256-token rows against one expert action each (dataset gt_actions): the forward of act_tokens (same kernels, same
+        logits) -> (nll float32 [N] = -log softmax(logits)[action] over all 67 logits, hit bool [N] = greedy action == action), on the device.
+        A hit agrees with act_tokens(do_sample=False) == action bit for bit."""
+        assert self._loaded, "load_state_dict first"
+        rows = tokens_u8.shape[0]
+        actions = torch.as_tensor(actions)
+        if actions.dtype.is_floating_point or actions.numel() != rows:
+            raise ValueError(f"actions must be {rows} integers, got {actions.dtype} {tuple(actions.shape)}")
+        if rows and (int(actions.min()) < 0 or int(actions.max()) >= 67):
+            raise ValueError("actions must lie in [0, 67)")
+        tg = actions.reshape(rows).to(device=self.device, dtype=torch.int32).contiguous()
+        nll = torch.empty((rows,), dtype=torch.float32, device=self.device)
+        hit = torch.empty((rows,), dtype=torch.int32, device=self.device)
+        lp = _lib.ptr(logits_out) if logits_out is not None else None
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mgpt_gpt_score_last(self._h, _lib.ptr(tokens_u8), rows, _lib.ptr(tg), _lib.ptr(nll), _lib.ptr(hit), lp,
+                                                      self._prec(precision), _lib.stream_ptr()))
+        return nll, hit.bool()
 
     __call__ = forward
 
