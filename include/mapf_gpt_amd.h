@@ -287,6 +287,48 @@ int mgpt_gpt_debug_counter(int which, uint64_t *value, int reset);
 int mgpt_gpt_act_dev(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int32_t *d_actions, float *d_logits,
                      int do_sample, uint64_t seed, const uint64_t *d_step, uint64_t row0, int precision, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training (train.py:324-331 with model.py:180-184 and configure_optimizers :202-226), exact fp32 throughout.  Released configs only:
+ * bias = False, dropout = 0 (dropout is a host-side flag: the caller refuses it), rows of T = 256 tokens.  Every product is an fp32 fmaf and
+ * every reduction runs in a fixed order without floating-point atomics: two identical calls give bit-identical gradients.
+ *   train_alloc: workspace for max_rows rows ((12 L + 16) C + 135 + 3 n_head floats per token: 30.1 MB per 6M row, 127.5 MB per 85M
+ *           row), one fp32 gradient buffer in the layout of the parameters and the AdamW moments (zeroed), step counters 0.  Needs a
+ *           finalized bias = False model (MGPT_ERR_UNSUPPORTED otherwise) with block_size 256 (MGPT_ERR_ARG).  A second call re-sizes the
+ *           activation part only (synchronises the device): gradients, moments and step counts are kept.  Nothing is allocated for a model
+ *           that never trains.
+ *   forward_backward: the exact-fp32 forward, then grads += loss_scale * d(mean cross-entropy, ignore_index = -1)/d(theta); d_targets
+ *           int32 [rows][T], -1 = ignored; *d_loss (device, may be NULL) = the unscaled mean loss.  Calls of more rows than the workspace
+ *           run in chunks; the mean is over the targeted positions of the whole call.  Synchronises `stream` once, before any other work of
+ *           the call is queued, to read the targeted-position count: none (MGPT_ERR_ARG, where torch gives NaN) or a target outside [-1, 67)
+ *           (MGPT_ERR_ARG) is refused.  T != 256: MGPT_ERR_ARG.
+ *   zero_grad: grads = 0.
+ *   clip_grad_norm: torch.nn.utils.clip_grad_norm_: total = || (||g_p||)_p ||, coef = min(max_norm / (total + 1e-6), 1), g *= coef; the
+ *           coefficient stays on the device, *d_total_norm (device, may be NULL) = total.  max_norm <= 0: the norm only.
+ *   adamw_step: torch.optim.AdamW with a step count per tensor: p *= 1 - lr * wd (the tensors of dim >= 2 only: wte = lm_head, wpe and the
+ *           four matrices of every block), m = lerp(m, g, 1 - beta1), v = beta2 v + (1 - beta2) g^2,
+ *           p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps).  Afterwards every precision serves the new weights: the
+ *           fp32 kernels at once, the 16-bit planes, layer-0 tables and the envelope decision are rebuilt before the next 16-bit call,
+ *           and captured step graphs re-capture.
+ *   train_get / train_set: one tensor by state_dict key (as mgpt_gpt_set_param; lm_head.weight = transformer.wte.weight) and `which`:
+ *           parameter, gradient, exp_avg, exp_avg_sq (the tensor's elements) or the step count (one float).  get copies device to device
+ *           on `stream`; set is synchronous (host or device source) and, for a parameter, acts as an optimizer step does on the 16-bit state.
+ *           Parameters need no training workspace; the other selectors do (MGPT_ERR_STATE).
+ * ------------------------------------------------------------------------------------------ */
+#define MGPT_TRAIN_PARAM 0
+#define MGPT_TRAIN_GRAD 1
+#define MGPT_TRAIN_EXP_AVG 2
+#define MGPT_TRAIN_EXP_AVG_SQ 3
+#define MGPT_TRAIN_STEP 4
+int mgpt_gpt_train_alloc(mgpt_gpt *gpt, int max_rows);
+int mgpt_gpt_train_free(mgpt_gpt *gpt);
+int mgpt_gpt_forward_backward(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int T, const int32_t *d_targets, float loss_scale,
+                              float *d_loss, void *stream);
+int mgpt_gpt_zero_grad(mgpt_gpt *gpt, void *stream);
+int mgpt_gpt_clip_grad_norm(mgpt_gpt *gpt, float max_norm, float *d_total_norm, void *stream);
+int mgpt_gpt_adamw_step(mgpt_gpt *gpt, float lr, float beta1, float beta2, float eps, float weight_decay, void *stream);
+int mgpt_gpt_train_get(mgpt_gpt *gpt, const char *name, int which, float *d_out, int64_t n_elem, void *stream);
+int mgpt_gpt_train_set(mgpt_gpt *gpt, const char *name, int which, const float *data, int64_t n_elem, int is_device);
+
 /* sampling alone (same RNG and key as mgpt_gpt_act), for callers that already hold logits */
 int mgpt_sample_actions(const float *d_logits, int rows, int32_t *d_actions, int do_sample,
                         uint64_t seed, uint64_t step, uint64_t row0, void *stream);

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmapf_gpt_amd.so")
 
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = 0, 1, 2, 3, 4
 PREC_F32, PREC_F16X3, PREC_BF16 = 0, 1, 2
+TRAIN_PARAM, TRAIN_GRAD, TRAIN_EXP_AVG, TRAIN_EXP_AVG_SQ, TRAIN_STEP = 0, 1, 2, 3, 4
 PRECISIONS = {"f32": PREC_F32, "fp32": PREC_F32, "f16x3": PREC_F16X3, "bf16": PREC_BF16}
 
 
@@ -86,6 +87,14 @@ SYMBOLS = {
     "mgpt_gpt_envelope": (_i, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_i)]),
     "mgpt_gpt_envelope_probe": (_i, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "mgpt_sample_actions": (_i, [_vp, _i, _vp, _i, _u64, _u64, _u64, _vp]),
+    "mgpt_gpt_train_alloc": (_i, [_vp, _i]),
+    "mgpt_gpt_train_free": (_i, [_vp]),
+    "mgpt_gpt_forward_backward": (_i, [_vp, _vp, _i, _i, _vp, ctypes.c_float, _vp, _vp]),
+    "mgpt_gpt_zero_grad": (_i, [_vp, _vp]),
+    "mgpt_gpt_clip_grad_norm": (_i, [_vp, ctypes.c_float, _vp, _vp]),
+    "mgpt_gpt_adamw_step": (_i, [_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp]),
+    "mgpt_gpt_train_get": (_i, [_vp, ctypes.c_char_p, _i, _vp, _i64, _vp]),
+    "mgpt_gpt_train_set": (_i, [_vp, ctypes.c_char_p, _i, _vp, _i64, _i]),
     "mgpt_prof_enable": (_i, [_i]),
     "mgpt_prof_reset": (_i, []),
     "mgpt_prof_read": (_i, [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float),

@@ -127,6 +127,7 @@ extern "C" int mgpt_gpt_create(mgpt_gpt **out, int n_layer, int n_head, int n_em
 extern "C" int mgpt_gpt_destroy(mgpt_gpt *g)
 {
     if (!g) return MGPT_OK;
+    gpt_train_destroy(g);
     gpt_fast_destroy(g);
     (void)hipFree(g->params); (void)hipFree(g->x); (void)hipFree(g->xn); (void)hipFree(g->qkv);
     (void)hipFree(g->hbuf); (void)hipFree(g->logits_tmp); (void)hipFree(g->bias);
@@ -188,6 +189,11 @@ static bool locate_param(const mgpt_gpt *g, const char *name_in, size_t *idx, si
     if (rest == "mlp.c_fc.weight") { *idx = base + 4; *off = lo.fc_w; *count = 4 * C * C; return true; }
     if (rest == "mlp.c_proj.weight") { *idx = base + 5; *off = lo.proj2_w; *count = 4 * C * C; return true; }
     return false;
+}
+
+bool gpt_locate_param(const mgpt_gpt *g, const char *name, size_t *idx, size_t *off, size_t *count)
+{
+    return locate_param(g, name, idx, off, count);
 }
 
 extern "C" int mgpt_gpt_set_param(mgpt_gpt *g, const char *name, const float *data, int64_t n_elem, int is_device)
@@ -273,7 +279,27 @@ extern "C" int mgpt_gpt_finalize(mgpt_gpt *g)
     // (bias vectors: outside by construction -- the 16-bit kernels have no bias terms, MGPT_PREC_F16X3 requests follow the envelope policy)
     g->env_state = g->has_bias ? 2 : 0; g->env_probe_err = g->env_probe_err_small = g->env_probe_err_large = -1.f; g->env_logged = false;
     g->env_probe_tol = 0.f; g->env_probe_max_logit = 0.f;
+    g->stale16 = false;
     g->finalized = true;
+    return MGPT_OK;
+}
+
+void gpt_params_changed(mgpt_gpt *g)
+{
+    g->stale16 = true;
+    g->generation++;
+}
+
+// the 16-bit state of weights changed in place (gpt_params_changed): what mgpt_gpt_finalize builds, rebuilt (planes lazily, at their first use)
+static int refresh_stale16(mgpt_gpt *g)
+{
+    if (!g->stale16) return MGPT_OK;
+    int rc = MGPT_OK;
+    if (g->block == kT && (rc = gpt_fast_finalize(g)) != MGPT_OK) return rc;
+    if ((rc = envelope_stats(g)) != MGPT_OK) return rc;
+    g->env_state = g->has_bias ? 2 : 0; g->env_probe_err = g->env_probe_err_small = g->env_probe_err_large = -1.f; g->env_logged = false;
+    g->env_probe_tol = 0.f; g->env_probe_max_logit = 0.f;
+    g->stale16 = false;
     return MGPT_OK;
 }
 
@@ -287,6 +313,8 @@ extern "C" int mgpt_gpt_set_envelope_policy(mgpt_gpt *g, int policy)
 extern "C" int mgpt_gpt_envelope(mgpt_gpt *g, float *out3, int *state)
 {
     MGPT_REQUIRE(g && out3 && state, MGPT_ERR_ARG, "NULL argument");
+    const int rc = refresh_stale16(g);
+    if (rc != MGPT_OK) return rc;
     out3[0] = g->env_max_w; out3[1] = g->env_max_rms; out3[2] = g->env_probe_err;
     *state = g->env_state;
     return MGPT_OK;
@@ -368,6 +396,44 @@ static int launch_layernorm(const float *x, const float *w, const float *b, floa
     else if (C <= 512) hipLaunchKernelGGL((f32k::layernorm_kernel<2>), grid, dim3(256), 0, s, x, w, y, n_tok, C, (int64_t)C, (int64_t)C, b);
     else if (C <= 768) hipLaunchKernelGGL((f32k::layernorm_kernel<3>), grid, dim3(256), 0, s, x, w, y, n_tok, C, (int64_t)C, (int64_t)C, b);
     else hipLaunchKernelGGL((f32k::layernorm_kernel<4>), grid, dim3(256), 0, s, x, w, y, n_tok, C, (int64_t)C, (int64_t)C, b);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
+// ----- the exact-fp32 forward as pieces, for the forward of mgpt_gpt_forward_backward (train.hip): the inference kernels, plus an EPI_STORE
+// instance for the c_fc pre-activation the backward keeps.  256-token rows, M = rows * 256 tokens -----
+int gpt_f32_embed(mgpt_gpt *g, const uint8_t *d_tokens, float *x, int64_t M, hipStream_t s)
+{
+    ProfScope ps(P_EMBED, s);
+    const int64_t total = M * (g->C / 4);
+    const int blocks = (int)std::min<int64_t>(cdiv64(total, 256), 256 * 64);
+    hipLaunchKernelGGL(f32k::embed_kernel, dim3(blocks), dim3(256), 0, s, d_tokens, g->params + g->off_wte, g->params + g->off_wpe, x, M, g->C, kT);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
+int gpt_f32_layernorm(mgpt_gpt *g, const float *x, const float *w, float *y, int64_t n_tok, hipStream_t s)
+{
+    return launch_layernorm(x, w, nullptr, y, n_tok, g->C, s);
+}
+
+// kind 0: out = A W^T;  1: out += A W^T;  2: q|k|v head-major planes of M * C floats each (the EPI_QKV scatter)
+int gpt_f32_linear(mgpt_gpt *g, int kind, const float *A, const float *W, float *out, int64_t M, int N, int K, hipStream_t s)
+{
+    f32k::EpiArgs ep;
+    ep.C = g->C; ep.n_head = g->nh; ep.hs = g->hs; ep.plane = M * g->C; ep.T = kT; ep.m_valid = M;
+    if (kind == 0) return launch_gemm<f32k::EPI_STORE>(A, W, out, M, N, K, ep, g->C, s);
+    if (kind == 1) return launch_gemm<f32k::EPI_RESID>(A, W, out, M, N, K, ep, g->C, s);
+    return launch_gemm<f32k::EPI_QKV>(A, W, out, M, N, K, ep, g->C, s);
+}
+
+int gpt_f32_attention(mgpt_gpt *g, const float *qkv, float *y, int rows, hipStream_t s)
+{
+    ProfScope ps(P_ATTN, s);
+    const int64_t plane = (int64_t)rows * kT * g->C;
+    const float scale = 1.0f / sqrtf((float)g->hs);
+    if (g->hs == 32) hipLaunchKernelGGL((f32k::attn_f32_kernel<32>), dim3(rows * g->nh), dim3(256), 0, s, qkv, qkv + plane, qkv + 2 * plane, y, g->nh, scale, kT);
+    else hipLaunchKernelGGL((f32k::attn_f32_kernel<64>), dim3(rows * g->nh), dim3(256), 0, s, qkv, qkv + plane, qkv + 2 * plane, y, g->nh, scale, kT);
     MGPT_LAUNCH_CHECK();
     return MGPT_OK;
 }
@@ -514,6 +580,10 @@ static int envelope_decide(mgpt_gpt *g, hipStream_t s)
 static int resolve_precision(mgpt_gpt *g, int *precision_io, hipStream_t s)
 {
     int precision = *precision_io;
+    if (precision != MGPT_PREC_F32) {                      // weights changed by an optimizer step since the planes were built
+        const int rc = refresh_stale16(g);
+        if (rc != MGPT_OK) return rc;
+    }
     // bias = True checkpoints: only the exact-fp32 kernels carry the bias terms.  MGPT_PREC_F16X3 under the fallback policy is served by them
     // (the checkpoint counts as outside the envelope, mgpt_gpt_finalize); every other 16-bit request is refused -- it would be wrong, not imprecise
     MGPT_REQUIRE(!g->has_bias || precision == MGPT_PREC_F32 || (precision == MGPT_PREC_F16X3 && g->env_policy == MGPT_ENVELOPE_FALLBACK),

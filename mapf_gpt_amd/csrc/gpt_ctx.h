@@ -42,6 +42,9 @@ struct mgpt_gpt {
     int env_policy = 0;                         // MGPT_ENVELOPE_FALLBACK / _REFUSE / _IGNORE
     int env_state = 0;                          // 0 not decided, 1 inside, 2 outside
     bool env_logged = false;
+    // training (train.hip): workspace of mgpt_gpt_train_alloc, NULL for a model that never trains
+    void *train = nullptr;
+    bool stale16 = false;                       // params changed in place (optimizer step): 16-bit planes and envelope rebuilt before the next 16-bit call
 };
 
 
@@ -67,6 +70,20 @@ void gpt_fast_destroy(mgpt_gpt *g);
 int gpt_fast_forward(mgpt_gpt *g, const uint8_t *d_tokens, int rows, float *d_logits, int precision, hipStream_t s, int call_rows,
                      const SeqOut *seq = nullptr);
 int gpt_fast_debug_copy(mgpt_gpt *g, int precision, int which, void *d_out, int64_t nbytes, hipStream_t s);
+
+// gpt.hip: reference state_dict key -> (tensor index, offset into params, element count); false for an unknown key
+bool gpt_locate_param(const mgpt_gpt *g, const char *name, size_t *idx, size_t *off, size_t *count);
+// gpt.hip: the parameters changed in place -- every precision serves the new weights: the fp32 kernels at once, the 16-bit planes, the layer-0
+// tables and the envelope decision are rebuilt before the next 16-bit call; `generation` is bumped so that captured step graphs re-capture
+void gpt_params_changed(mgpt_gpt *g);
+// gpt.hip: the exact-fp32 forward kernels one by one (256-token rows; the forward of mgpt_gpt_forward_backward).  linear kind: 0 store,
+// 1 add into out (the residual), 2 q|k|v scatter into head-major planes of M * C floats
+int gpt_f32_embed(mgpt_gpt *g, const uint8_t *d_tokens, float *x, int64_t M, hipStream_t s);
+int gpt_f32_layernorm(mgpt_gpt *g, const float *x, const float *w, float *y, int64_t n_tok, hipStream_t s);
+int gpt_f32_linear(mgpt_gpt *g, int kind, const float *A, const float *W, float *out, int64_t M, int N, int K, hipStream_t s);
+int gpt_f32_attention(mgpt_gpt *g, const float *qkv, float *y, int rows, hipStream_t s);
+// train.hip: frees the training workspace (mgpt_gpt_destroy)
+void gpt_train_destroy(mgpt_gpt *g);
 
 // gpt.hip: final LayerNorm + tied lm_head on the last position of g->x (shared by both paths)
 int gpt_launch_head(mgpt_gpt *g, int rows, float *d_logits, hipStream_t s);

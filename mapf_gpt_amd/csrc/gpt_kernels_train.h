@@ -1,0 +1,447 @@
+// gpt_kernels_train.h -- exact-fp32 backward, gradient clipping and AdamW kernels (mgpt_gpt_forward_backward & co., train.hip), gfx950.
+//
+// Training is what train.py:324-331 does with the released configs: bias = False, dropout = 0, rows of T = 256 tokens.  The forward that
+// saves activations runs the exact-fp32 forward kernels of gpt_kernels_f32.h (gemm_f32_kernel, attn_f32_kernel, layernorm_kernel); the
+// kernels here are the backward and the optimizer.  Every product is an fp32 fmaf on the VALU, every reduction runs in a fixed order and
+// no kernel uses a floating-point atomic: two identical calls give bit-identical gradients.
+//
+// Layouts (M = rows * 256 tokens of one workspace chunk):
+//   token-major [M][N] activations and gradients (x, ln outputs, y, c_fc pre-activation, dY, dq|dk|dv as [M][3C]);
+//   q, k, v head-major [rows][n_head][256][hs] planes, as the forward's EPI_QKV epilogue writes them;
+//   weight-gradient partials [S][N][K]: slab s sums the tokens [s * kps, (s + 1) * kps), slab_reduce_kernel adds the slabs in order.
+#pragma once
+#include "common.h"
+
+namespace mgpt {
+namespace trk {
+
+constexpr int kT = 256;
+
+// ----- strided GEMM: C(m, n) (op)= sum_{k in the split's range} A(m, k) * B(k, n), 64 x 64 tiles, 4 x 4 outputs per thread -----
+// A(m, k) = A[m * lda + k] (A_KC) or A[k * lda + m];  B(k, n) = B[k * ldb + n] (B_NC) or B[n * ldb + k].  Every index is bounds-checked,
+// so any M, N, K work.  k runs in increasing order: an fmaf chain over each 16-wide k tile, the tiles' sums added in order (a long chain
+// of K fmafs would grow the rounding error with K: the c_attn input gradient of 85M sums 2304 terms).
+enum { OUT_STORE = 0, OUT_ADD = 1, OUT_PART = 2, OUT_GELU_BWD = 3 };
+
+__device__ __forceinline__ float gelu_grad(float a)
+{
+    // d/da [0.5 a (1 + erf(a / sqrt 2))] = 0.5 (1 + erf(a / sqrt 2)) + a * exp(-a^2 / 2) / sqrt(2 pi)
+    return 0.5f * (1.0f + erff(a * 0.70710678118654752440f)) + a * expf(-0.5f * a * a) * 0.39894228040143267794f;
+}
+
+template <bool A_KC, bool B_NC, int OUT>
+__global__ __launch_bounds__(256) void gemm_tr_kernel(const float *__restrict__ A, int64_t lda, const float *__restrict__ B, int64_t ldb,
+                                                      float *__restrict__ Cout, int64_t ldc, int M, int N, int K, int kps,
+                                                      const float *__restrict__ aux)
+{
+    constexpr int BM = 64, BN = 64, BK = 16;
+    __shared__ __attribute__((aligned(16))) float sA[BK][BM];
+    __shared__ __attribute__((aligned(16))) float sB[BK][BN];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int n0 = blockIdx.x * BN, m0 = blockIdx.y * BM;
+    const int kb = blockIdx.z * kps, ke = min(K, kb + kps);
+    float acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) acc[i][j] = 0.f;
+    for (int k0 = kb; k0 < ke; k0 += BK) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int idx = tid + 256 * e;
+            int mm, kk;
+            if (A_KC) { mm = idx >> 4; kk = idx & 15; } else { mm = idx & 63; kk = idx >> 6; }
+            const int m = m0 + mm, k = k0 + kk;
+            sA[kk][mm] = (m < M && k < ke) ? (A_KC ? A[(int64_t)m * lda + k] : A[(int64_t)k * lda + m]) : 0.f;
+            int nn, kn;
+            if (B_NC) { nn = idx & 63; kn = idx >> 6; } else { nn = idx >> 4; kn = idx & 15; }
+            const int n = n0 + nn, k2 = k0 + kn;
+            sB[kn][nn] = (n < N && k2 < ke) ? (B_NC ? B[(int64_t)k2 * ldb + n] : B[(int64_t)n * ldb + k2]) : 0.f;
+        }
+        __syncthreads();
+        float tile[4][4];                                       // this k tile's 16 products per output, then added: two-level summation
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) tile[i][j] = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < BK; kk++) {
+            const float4 a = *reinterpret_cast<const float4 *>(&sA[kk][ty * 4]);
+            const float4 b = *reinterpret_cast<const float4 *>(&sB[kk][tx * 4]);
+            const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++) tile[i][j] = fmaf(av[i], bv[j], tile[i][j]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) acc[i][j] += tile[i][j];
+        __syncthreads();
+    }
+    float *dst = OUT == OUT_PART ? Cout + (int64_t)blockIdx.z * M * ldc : Cout;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int m = m0 + ty * 4 + i;
+        if (m >= M) continue;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int n = n0 + tx * 4 + j;
+            if (n >= N) continue;
+            const int64_t o = (int64_t)m * ldc + n;
+            if (OUT == OUT_ADD) dst[o] += acc[i][j];
+            else if (OUT == OUT_GELU_BWD) dst[o] = acc[i][j] * gelu_grad(aux[o]);
+            else dst[o] = acc[i][j];
+        }
+    }
+}
+
+// out[i] += sum_{s < S} part[s * n + i], s in increasing order
+__global__ __launch_bounds__(256) void slab_reduce_kernel(const float *__restrict__ part, int S, int64_t n, float *__restrict__ out)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        float s = 0.f;
+        for (int k = 0; k < S; k++) s += part[(int64_t)k * n + i];
+        out[i] += s;
+    }
+}
+
+// part[s][c] = sum over the tokens of slab s of v[m][c] (LayerNorm gain gradients), m in increasing order, accumulated in double
+__global__ __launch_bounds__(256) void colsum_part_kernel(const float *__restrict__ v, int64_t M, int C, int kps, float *__restrict__ part)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const int64_t mb = (int64_t)blockIdx.y * kps, me = min<int64_t>(M, mb + kps);
+    double s = 0.0;                                             // (a column sum of fp32 terms, kept in double)
+    for (int64_t m = mb; m < me; m++) s += (double)v[m * C + c];
+    part[(int64_t)blockIdx.y * C + c] = (float)s;
+}
+
+__global__ __launch_bounds__(256) void gelu_kernel(const float *__restrict__ a, float *__restrict__ h, int64_t n)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float v = a[i];
+        h[i] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));     // = f32k::gelu_erf
+    }
+}
+
+// ----- LayerNorm backward (eps 1e-5, gain only), one wavefront per token -----
+// dres[m] (+)= rstd * (g - mean(g) - xhat * mean(g * xhat)) with g = dxn * w;  gp[m] = dxn * xhat (the gain's per-token terms)
+template <bool ADD>
+__global__ __launch_bounds__(256) void ln_bwd_kernel(const float *__restrict__ x, const float *__restrict__ w, const float *__restrict__ dxn,
+                                                     float *__restrict__ dres, float *__restrict__ gp, int64_t n_tok, int C)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t tok = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tok >= n_tok) return;
+    const float *px = x + tok * C, *pd = dxn + tok * C;
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s += px[c];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float mean = s / (float)C;
+    float q = 0.f;
+    for (int c = lane; c < C; c += 64) { const float d = px[c] - mean; q = fmaf(d, d, q); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    const float rstd = rsqrtf(q / (float)C + 1e-5f);
+    float sg = 0.f, sgx = 0.f;
+    for (int c = lane; c < C; c += 64) {
+        const float xh = (px[c] - mean) * rstd, g = pd[c] * w[c];
+        sg += g;
+        sgx = fmaf(g, xh, sgx);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { sg += __shfl_xor(sg, o); sgx += __shfl_xor(sgx, o); }
+    const float mg = sg / (float)C, mgx = sgx / (float)C;
+    for (int c = lane; c < C; c += 64) {
+        const float xh = (px[c] - mean) * rstd, g = pd[c] * w[c];
+        const float dx = rstd * (g - mg - xh * mgx);
+        if (ADD) dres[tok * C + c] += dx; else dres[tok * C + c] = dx;
+        gp[tok * C + c] = pd[c] * xh;
+    }
+}
+
+// ----- cross-entropy (ignore_index = -1) on every token: dlogits = (softmax - onehot) * scale / count, nll per token -----
+__global__ __launch_bounds__(256) void ce_kernel(const float *__restrict__ logits, const int32_t *__restrict__ targets, int64_t M,
+                                                 const int32_t *__restrict__ d_count, float loss_scale, float *__restrict__ dlogits,
+                                                 float *__restrict__ tok_nll)
+{
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m >= M) return;
+    const int tg = targets[m];
+    const float *l = logits + m * MGPT_VOCAB;
+    float *dl = dlogits + m * MGPT_VOCAB;
+    if (tg < 0 || tg >= MGPT_VOCAB) {
+        for (int v = 0; v < MGPT_VOCAB; v++) dl[v] = 0.f;
+        tok_nll[m] = 0.f;
+        return;
+    }
+    float mx = l[0];
+    for (int v = 1; v < MGPT_VOCAB; v++) mx = fmaxf(mx, l[v]);
+    float sum = 0.f;
+    for (int v = 0; v < MGPT_VOCAB; v++) sum += expf(l[v] - mx);
+    const float lse = mx + logf(sum);
+    const float k = loss_scale / (float)(*d_count);
+    for (int v = 0; v < MGPT_VOCAB; v++) {
+        const float p = expf(l[v] - lse);
+        dl[v] = (p - (v == tg ? 1.f : 0.f)) * k;
+    }
+    tok_nll[m] = lse - l[tg];
+}
+
+// targeted positions of a whole call (0 <= t < 67) into cnt[0]; cnt[1] = 1 if any target is outside [-1, 67).  One workgroup.
+__global__ __launch_bounds__(1024) void count_targets_kernel(const int32_t *__restrict__ t, int64_t n, int32_t *__restrict__ cnt)
+{
+    __shared__ int sc[1024], sb[1024];
+    int c = 0, bad = 0;
+    for (int64_t i = threadIdx.x; i < n; i += 1024) {
+        const int v = t[i];
+        c += (v >= 0 && v < MGPT_VOCAB);
+        bad |= (v < -1 || v >= MGPT_VOCAB);
+    }
+    sc[threadIdx.x] = c; sb[threadIdx.x] = bad;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { sc[threadIdx.x] += sc[threadIdx.x + o]; sb[threadIdx.x] |= sb[threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { cnt[0] = sc[0]; cnt[1] = sb[0]; }
+}
+
+// acc[0] += sum of v[0 .. n) (double, fixed tree order); one workgroup, stream-ordered across chunks
+__global__ __launch_bounds__(256) void sum_acc_kernel(const float *__restrict__ v, int64_t n, double *__restrict__ acc)
+{
+    __shared__ double sd[256];
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) s += (double)v[i];
+    sd[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sd[threadIdx.x] += sd[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) acc[0] += sd[0];
+}
+
+__global__ void loss_final_kernel(const double *__restrict__ acc, const int32_t *__restrict__ cnt, float *__restrict__ loss)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) loss[0] = (float)(acc[0] / (double)cnt[0]);
+}
+
+// ----- attention backward (model.py:58-60, non-causal, T = 256), one workgroup per (row, head), thread = query / key -----
+// P is recomputed from q, k: s = (q . k) * scale, P = exp(s - m) / l with the query's (m, l) from attn_bwd_q_kernel; D = rowsum(dY o Y).
+// dQ = dS K * scale (this kernel, also stores (m, l, D) per query), dV = P^T dY and dK = dS^T Q * scale (attn_bwd_kv_kernel).
+template <int HS>
+__device__ __forceinline__ float dot_lds(const float *a, const float *__restrict__ b)
+{
+    float s = 0.f;
+#pragma unroll
+    for (int d = 0; d < HS; d += 4) {
+        const float4 v = *reinterpret_cast<const float4 *>(b + d);
+        s = fmaf(a[d], v.x, s); s = fmaf(a[d + 1], v.y, s); s = fmaf(a[d + 2], v.z, s); s = fmaf(a[d + 3], v.w, s);
+    }
+    return s;
+}
+
+template <int HS>
+__global__ __launch_bounds__(256) void attn_bwd_q_kernel(const float *__restrict__ qkv, int64_t plane, const float *__restrict__ Y,
+                                                         const float *__restrict__ dY, float *__restrict__ dqkv, float *__restrict__ stats,
+                                                         int n_head, float scale)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *sK = smem, *sV = smem + kT * HS;
+    const int bh = blockIdx.x, b = bh / n_head, head = bh - b * n_head, C = n_head * HS;
+    const float *Q = qkv + (int64_t)bh * kT * HS, *K = Q + plane, *V = Q + 2 * plane;
+    for (int i = threadIdx.x; i < kT * HS / 4; i += 256) {
+        reinterpret_cast<float4 *>(sK)[i] = reinterpret_cast<const float4 *>(K)[i];
+        reinterpret_cast<float4 *>(sV)[i] = reinterpret_cast<const float4 *>(V)[i];
+    }
+    __syncthreads();
+    const int i = threadIdx.x;
+    const int64_t tok = (int64_t)b * kT + i;
+    float q[HS], dy[HS], acc[HS];
+    float D = 0.f;
+#pragma unroll
+    for (int d = 0; d < HS; d++) {
+        q[d] = Q[i * HS + d];
+        dy[d] = dY[tok * C + head * HS + d];
+        D = fmaf(dy[d], Y[tok * C + head * HS + d], D);
+        acc[d] = 0.f;
+    }
+    float m = -INFINITY, l = 0.f;
+    for (int j = 0; j < kT; j++) {
+        const float s = dot_lds<HS>(q, sK + j * HS) * scale;
+        if (s > m) { l = l * expf(m - s) + 1.f; m = s; }
+        else l += expf(s - m);
+    }
+    const float inv_l = 1.f / l;
+    for (int j = 0; j < kT; j++) {
+        const float s = dot_lds<HS>(q, sK + j * HS) * scale;
+        const float p = expf(s - m) * inv_l;
+        const float ds = p * (dot_lds<HS>(dy, sV + j * HS) - D);
+        const float *kr = sK + j * HS;
+#pragma unroll
+        for (int d = 0; d < HS; d++) acc[d] = fmaf(ds, kr[d], acc[d]);
+    }
+    float *o = dqkv + tok * 3 * C + head * HS;
+#pragma unroll
+    for (int d = 0; d < HS; d++) o[d] = acc[d] * scale;
+    float *st = stats + ((int64_t)bh * kT + i) * 3;
+    st[0] = m; st[1] = inv_l; st[2] = D;
+}
+
+// MODE 0: dV (thread = key j: sum_i P_ij dY_i);  MODE 1: dK (sum_i dS_ij Q_i * scale)
+template <int HS, int MODE>
+__global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float *__restrict__ qkv, int64_t plane, const float *__restrict__ dY,
+                                                          float *__restrict__ dqkv, const float *__restrict__ stats, int n_head, float scale)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *sQ = smem, *sD = smem + kT * HS, *sS = smem + 2 * kT * HS;
+    const int bh = blockIdx.x, b = bh / n_head, head = bh - b * n_head, C = n_head * HS;
+    const float *Q = qkv + (int64_t)bh * kT * HS, *K = Q + plane, *V = Q + 2 * plane;
+    for (int i = threadIdx.x; i < kT * HS / 4; i += 256) {
+        reinterpret_cast<float4 *>(sQ)[i] = reinterpret_cast<const float4 *>(Q)[i];
+        const int t = (4 * i) / HS, d = 4 * i - t * HS;
+        reinterpret_cast<float4 *>(sD)[i] = *reinterpret_cast<const float4 *>(dY + ((int64_t)b * kT + t) * C + head * HS + d);
+    }
+    for (int i = threadIdx.x; i < kT * 3; i += 256) sS[i] = stats[(int64_t)bh * kT * 3 + i];
+    __syncthreads();
+    const int j = threadIdx.x;
+    float k[HS], v[MODE == 1 ? HS : 1], acc[HS];
+#pragma unroll
+    for (int d = 0; d < HS; d++) {
+        k[d] = K[j * HS + d];
+        if constexpr (MODE == 1) v[d] = V[j * HS + d];
+        acc[d] = 0.f;
+    }
+    for (int i = 0; i < kT; i++) {
+        // the same fmaf chain as attn_bwd_q_kernel's s (q . k over d in order): P is bit-identical in both kernels
+        const float *qr = sQ + i * HS;
+        float s = 0.f;
+#pragma unroll
+        for (int d = 0; d < HS; d += 4) {
+            const float4 a = *reinterpret_cast<const float4 *>(qr + d);
+            s = fmaf(a.x, k[d], s); s = fmaf(a.y, k[d + 1], s); s = fmaf(a.z, k[d + 2], s); s = fmaf(a.w, k[d + 3], s);
+        }
+        const float p = expf(s * scale - sS[3 * i]) * sS[3 * i + 1];
+        const float *dr = sD + i * HS;
+        if constexpr (MODE == 0) {
+#pragma unroll
+            for (int d = 0; d < HS; d++) acc[d] = fmaf(p, dr[d], acc[d]);
+        } else {
+            const float ds = p * (dot_lds<HS>(v, dr) - sS[3 * i + 2]);
+#pragma unroll
+            for (int d = 0; d < HS; d++) acc[d] = fmaf(ds, qr[d], acc[d]);
+        }
+    }
+    float *o = dqkv + ((int64_t)b * kT + j) * 3 * C + (MODE == 0 ? 2 : 1) * C + head * HS;
+#pragma unroll
+    for (int d = 0; d < HS; d++) o[d] = MODE == 0 ? acc[d] : acc[d] * scale;
+}
+
+// ----- embedding backward (model.py:171-175) -----
+// d wpe[t][c] += sum over rows of dx0[row][t][c], rows in order
+__global__ __launch_bounds__(256) void wpe_bwd_kernel(const float *__restrict__ dx, int rows, int C, float *__restrict__ gwpe)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)kT * C) return;
+    float s = 0.f;
+    for (int r = 0; r < rows; r++) s += dx[(int64_t)r * kT * C + i];
+    gwpe[i] += s;
+}
+
+// part[s][id][c] = sum over the tokens of slab s with token id `id` (blockIdx.x) of dx0[m][c], m in order, in double; no sort needed (67 ids)
+__global__ __launch_bounds__(256) void wte_bwd_part_kernel(const uint8_t *__restrict__ tokens, const float *__restrict__ dx, int64_t M, int C,
+                                                           int kps, float *__restrict__ part)
+{
+    const int id = blockIdx.x;
+    const int64_t mb = (int64_t)blockIdx.y * kps, me = min<int64_t>(M, mb + kps);
+    for (int c = threadIdx.x; c < C; c += 256) {
+        double s = 0.0;
+        for (int64_t m = mb; m < me; m++)
+            if (tokens[m] == id) s += (double)dx[m * C + c];
+        part[((int64_t)blockIdx.y * MGPT_VOCAB + id) * C + c] = (float)s;
+    }
+}
+
+// ----- gradient norm and AdamW over the parameter tensors; a block table splits every tensor into chunks of kChunk elements -----
+constexpr int kChunk = 16384;
+struct Blk {
+    int64_t begin, end;     // element range in params / grads
+    int tensor, decay;      // tensor index (its step counter), 1 = weight decay applies (configure_optimizers, model.py:209-214)
+};
+
+// part[b] = sum of g^2 over block b's range (double, fixed order)
+__global__ __launch_bounds__(256) void sumsq_part_kernel(const float *__restrict__ g, const Blk *__restrict__ blk, double *__restrict__ part)
+{
+    __shared__ double sd[256];
+    const Blk bk = blk[blockIdx.x];
+    double s = 0.0;
+    for (int64_t i = bk.begin + threadIdx.x; i < bk.end; i += 256) { const double v = g[i]; s += v * v; }
+    sd[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sd[threadIdx.x] += sd[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = sd[0];
+}
+
+// torch.nn.utils.clip_grad_norm_: total = || (||g_p||)_p ||, coef = min(max_norm / (total + 1e-6), 1); one thread, tensors and blocks in order
+__global__ void clip_coef_kernel(const double *__restrict__ part, const Blk *__restrict__ blk, int n_blk, float max_norm,
+                                 float *__restrict__ total_out, float *__restrict__ coef)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double tot = 0.0, cur = 0.0;
+    for (int b = 0; b < n_blk; b++) {
+        cur += part[b];
+        if (b + 1 == n_blk || blk[b + 1].tensor != blk[b].tensor) {
+            const double n = sqrt(cur);
+            tot += n * n;
+            cur = 0.0;
+        }
+    }
+    const float total = (float)sqrt(tot);
+    if (total_out) total_out[0] = total;
+    coef[0] = fminf(max_norm / (total + 1e-6f), 1.0f);
+}
+
+__global__ __launch_bounds__(256) void scale_kernel(float *__restrict__ g, int64_t n, const float *__restrict__ coef)
+{
+    const float c = coef[0];
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) g[i] *= c;
+}
+
+__global__ void step_inc_kernel(float *__restrict__ steps, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) steps[i] += 1.f;
+}
+
+// torch.optim.AdamW (single-tensor, non-capturable): step += 1 (step_inc_kernel, before this);  p *= 1 - lr * wd;  m = lerp(m, g, 1 - b1);
+// v = b2 v + (1 - b2) g^2;  p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+__global__ __launch_bounds__(256) void adamw_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+                                                    const Blk *__restrict__ blk, const float *__restrict__ steps, float lr, float b1, float b2,
+                                                    float eps, float wd)
+{
+    const Blk bk = blk[blockIdx.x];
+    const double t = (double)steps[bk.tensor];
+    const float step_size = (float)((double)lr / (1.0 - pow((double)b1, t)));
+    const float bc2s = (float)sqrt(1.0 - pow((double)b2, t));
+    const float decay = bk.decay ? 1.0f - lr * wd : 1.0f;
+    for (int64_t i = bk.begin + threadIdx.x; i < bk.end; i += 256) {
+        const float gi = g[i];
+        float pi = p[i] * decay;
+        const float mi = fmaf(1.0f - b1, gi - m[i], m[i]);          // torch.lerp(m, g, 1 - b1) (weight < 0.5 form)
+        const float vi = fmaf(v[i], b2, (1.0f - b2) * gi * gi);     // mul_(b2).addcmul_(g, g, value = 1 - b2)
+        m[i] = mi; v[i] = vi;
+        const float denom = sqrtf(vi) / bc2s + eps;
+        pi = fmaf(-step_size, mi / denom, pi);
+        p[i] = pi;
+    }
+}
+
+}  // namespace trk
+}  // namespace mgpt

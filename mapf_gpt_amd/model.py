@@ -7,9 +7,9 @@
     act(idx, do_sample=True, generator=None) -> LongTensor [B]   (model.py:244-260)
 plus the device-resident fast path `act_tokens(tokens_u8, ...)` used by the batched runner.
 `score_tokens` and mapf_gpt_amd/scoring.py score a checkpoint on expert data (train.py estimate_loss).
-Training helpers of the reference (configure_optimizers, estimate_mfu, crop_block_size) are out of
-scope.  Every compute call goes through the C ABI; there is no
-PyTorch forward here.
+Training (train.py:324-331) runs on the device in exact fp32: train(), forward_backward(idx, targets), zero_grad(),
+clip_grad_norm_(), grads(), state_dict() and configure_optimizers() -> AdamW (model.py:202-226).  estimate_mfu and
+crop_block_size are out of scope.  Every compute call goes through the C ABI; there is no PyTorch forward here.
 """
 import ctypes
 from dataclasses import dataclass
@@ -275,6 +275,158 @@ class GPT:
         else:
             self._act_seed = int(seed)
             self._act_pinned = True
+
+
+    # ---- training (include/mapf_gpt_amd.h: mgpt_gpt_train_alloc & co.; exact fp32) ------------------------------------
+    def named_parameters(self):
+        """(name, shape) of the parameters in model.py's named_parameters order (lm_head.weight is transformer.wte.weight, counted once)."""
+        c = self.config
+        C, L = c.n_embd, c.n_layer
+        out = [("transformer.wte.weight", (c.vocab_size, C)), ("transformer.wpe.weight", (c.block_size, C))]
+        for l in range(L):
+            p = f"transformer.h.{l}."
+            out += [(p + "ln_1.weight", (C,)), (p + "attn.c_attn.weight", (3 * C, C)), (p + "attn.c_proj.weight", (C, C)),
+                    (p + "ln_2.weight", (C,)), (p + "mlp.c_fc.weight", (4 * C, C)), (p + "mlp.c_proj.weight", (C, 4 * C))]
+        out.append(("transformer.ln_f.weight", (C,)))
+        return out
+
+    def train(self, mode=True, max_rows=None):
+        """mode=True: training mode.  The first call allocates the training workspace (max_rows rows per chunk, default: the model's max_rows)
+        with zeroed gradients and AdamW moments.  Later calls keep it: train() with no max_rows changes nothing (train.py calls model.train()
+        after every evaluation), a different max_rows re-sizes the activation part only -- gradients, moments and step counts survive.
+        train(False) = eval() and keeps the workspace.  Released configs only: bias=False, dropout=0, block_size 256."""
+        if not mode:
+            return self.eval()
+        assert self._loaded, "load_state_dict first"
+        if self.config.dropout > 0:
+            raise NotImplementedError("training with dropout > 0 is not supported (the released configs train with dropout = 0)")
+        have = getattr(self, "_train_rows", None)
+        rows = int(max_rows) if max_rows is not None else (have or self.max_rows)
+        if have != rows:
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().mgpt_gpt_train_alloc(self._h, rows))
+            self._train_rows = rows
+        self.training = True
+        return self
+
+    def _require_train(self):
+        if getattr(self, "_train_rows", None) is None:
+            raise RuntimeError("call train() first: it allocates the training workspace")
+
+    def forward_backward(self, idx, targets, loss_scale=1.0):
+        """= loss = model(idx, targets)[1]; (loss * loss_scale).backward() (model.py:180-184, train.py:324-331): gradients ACCUMULATE into the
+        device buffer; returns the unscaled mean cross-entropy (ignore_index=-1) as a 0-d float32 device tensor."""
+        self._require_train()
+        tokens = self._tokens_u8(idx)
+        B, T = tokens.shape
+        targets = torch.as_tensor(targets)
+        if targets.dtype.is_floating_point or targets.dtype == torch.bool or targets.numel() != B * T:
+            raise ValueError(f"targets must be an integer tensor of {B * T} elements (idx is {B} x {T}), got {targets.dtype} {tuple(targets.shape)}")
+        tg = targets.reshape(B, T).to(device=self.device, dtype=torch.int32).contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mgpt_gpt_forward_backward(self._h, _lib.ptr(tokens), B, T, _lib.ptr(tg), float(loss_scale), _lib.ptr(loss),
+                                                            _lib.stream_ptr()))
+        return loss
+
+    def zero_grad(self, set_to_none=True):
+        self._require_train()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mgpt_gpt_zero_grad(self._h, _lib.stream_ptr()))
+
+    def clip_grad_norm_(self, max_norm):
+        """= torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm); returns the total norm as a 0-d device tensor (max_norm <= 0: norm only)."""
+        self._require_train()
+        total = torch.empty((), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mgpt_gpt_clip_grad_norm(self._h, float(max_norm), _lib.ptr(total), _lib.stream_ptr()))
+        return total
+
+    def _train_tensor(self, name, which, shape):
+        out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mgpt_gpt_train_get(self._h, name.encode(), which, _lib.ptr(out), out.numel(), _lib.stream_ptr()))
+        return out
+
+    def _set_train_tensor(self, name, which, value):
+        a = torch.as_tensor(value).detach().to(device=self.device, dtype=torch.float32).contiguous()
+        torch.cuda.synchronize(self.device)
+        _lib.check(_lib.lib().mgpt_gpt_train_set(self._h, name.encode(), which, _lib.ptr(a), a.numel(), 1))
+
+    def grads(self):
+        """{named_parameters name: float32 device tensor} -- copies of the accumulated gradients."""
+        self._require_train()
+        return {n: self._train_tensor(n, _lib.TRAIN_GRAD, shp) for n, shp in self.named_parameters()}
+
+    def state_dict(self):
+        """The parameters read back from the device, in the reference's key layout; lm_head.weight aliases transformer.wte.weight."""
+        assert self._loaded, "load_state_dict first"
+        if self.config.bias:
+            raise NotImplementedError("state_dict() reads the weights of bias=False models (the bias vectors have no read-back)")
+        sd = {n: self._train_tensor(n, _lib.TRAIN_PARAM, shp) for n, shp in self.named_parameters()}     # (needs no training workspace)
+        sd["lm_head.weight"] = sd["transformer.wte.weight"]
+        return sd
+
+    def configure_optimizers(self, weight_decay, learning_rate, betas, device_type="cuda"):
+        """= GPT.configure_optimizers (model.py:202-226): AdamW with weight decay on the tensors of dim >= 2 only."""
+        self._require_train()
+        return AdamW(self, learning_rate, betas, weight_decay)
+
+
+class AdamW:
+    """torch.optim.AdamW over a GPT's device parameters (mgpt_gpt_adamw_step), with nanoGPT's two groups (model.py:209-214): group 0 the
+    tensors of dim >= 2 (weight_decay), group 1 the LayerNorm gains (0).  param_groups[i]["lr"] may be set between steps, as train.py:282-283
+    does; both groups take group 0's lr, betas and eps.  state_dict() / load_state_dict() use torch.optim.AdamW.state_dict()'s layout."""
+
+    def __init__(self, net, lr, betas, weight_decay, eps=1e-8):
+        self.net = net
+        names = [n for n, _ in net.named_parameters()]
+        shapes = dict(net.named_parameters())
+        self._names = [n for n in names if len(shapes[n]) >= 2] + [n for n in names if len(shapes[n]) < 2]
+        self._shapes = shapes
+        n_decay = sum(len(shapes[n]) >= 2 for n in names)
+        common = dict(lr=float(lr), betas=tuple(float(b) for b in betas), eps=float(eps), amsgrad=False, maximize=False, foreach=None,
+                      capturable=False, differentiable=False, fused=None)
+        self.param_groups = [dict(common, weight_decay=float(weight_decay), params=list(range(n_decay))),
+                             dict(common, weight_decay=0.0, params=list(range(n_decay, len(self._names))))]
+
+    def step(self):
+        g = self.param_groups[0]
+        if self.param_groups[1]["lr"] != g["lr"]:
+            raise ValueError("both parameter groups must share one learning rate (train.py:282-283 sets it on every group)")
+        with torch.cuda.device(self.net.device):
+            _lib.check(_lib.lib().mgpt_gpt_adamw_step(self.net._h, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
+                                                      _lib.stream_ptr()))
+
+    def zero_grad(self, set_to_none=True):
+        self.net.zero_grad()
+
+    def state_dict(self):
+        state = {}
+        for i, n in enumerate(self._names):
+            shp = self._shapes[n]
+            step = self.net._train_tensor(n, _lib.TRAIN_STEP, (1,))
+            if float(step.item()) == 0.0:
+                continue                      # torch keeps no state for a parameter that never stepped
+            state[i] = {"step": step.reshape(()).cpu(), "exp_avg": self.net._train_tensor(n, _lib.TRAIN_EXP_AVG, shp),
+                        "exp_avg_sq": self.net._train_tensor(n, _lib.TRAIN_EXP_AVG_SQ, shp)}
+        groups = [{k: (list(v) if k == "params" else v) for k, v in grp.items()} for grp in self.param_groups]
+        return {"state": state, "param_groups": groups}
+
+    def load_state_dict(self, sd):
+        groups = sd["param_groups"]
+        for mine, theirs in zip(self.param_groups, groups):
+            for k in ("lr", "betas", "eps", "weight_decay"):
+                mine[k] = tuple(theirs[k]) if k == "betas" else theirs[k]
+        order = [i for grp in groups for i in grp["params"]]
+        for pos, i in enumerate(order):
+            n = self._names[pos]
+            st = sd["state"].get(i)
+            if st is None:
+                st = {"step": 0.0, "exp_avg": torch.zeros(self._shapes[n]), "exp_avg_sq": torch.zeros(self._shapes[n])}
+            self.net._set_train_tensor(n, _lib.TRAIN_STEP, torch.as_tensor(float(st["step"])).reshape(1))
+            self.net._set_train_tensor(n, _lib.TRAIN_EXP_AVG, st["exp_avg"])
+            self.net._set_train_tensor(n, _lib.TRAIN_EXP_AVG_SQ, st["exp_avg_sq"])
 
 
 def build_model(name_or_args, seed=0, scale=1.0, max_rows=2048, precision="f32", device="cuda", state_dict=None, envelope="fallback"):
