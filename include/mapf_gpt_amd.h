@@ -288,19 +288,30 @@ int mgpt_gpt_act_dev(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int32_t *
                      int do_sample, uint64_t seed, const uint64_t *d_step, uint64_t row0, int precision, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * Training (train.py:324-331 with model.py:180-184 and configure_optimizers :202-226), exact fp32 throughout.  Released configs only:
- * bias = False, dropout = 0 (dropout is a host-side flag: the caller refuses it), rows of T = 256 tokens.  Every product is an fp32 fmaf and
- * every reduction runs in a fixed order without floating-point atomics: two identical calls give bit-identical gradients.
+ * Training (train.py:324-331 with model.py:180-184 and configure_optimizers :202-226), exact fp32 or bf16 mixed precision (train.py's
+ * autocast regime, forward_backward_prec).  Released configs only:
+ * bias = False, dropout = 0 (dropout is a host-side flag: the caller refuses it), rows of T = 256 tokens.  In the fp32 path every product is
+ * an fp32 fmaf or fp32 MFMA; the bf16 path runs its block linears and attention on bf16 MFMAs with fp32 accumulation.  In both, every reduction
+ * runs in a fixed order without floating-point atomics: two identical calls give bit-identical gradients.
  *   train_alloc: workspace for max_rows rows ((12 L + 16) C + 135 + 3 n_head floats per token: 30.1 MB per 6M row, 127.5 MB per 85M
- *           row), one fp32 gradient buffer in the layout of the parameters and the AdamW moments (zeroed), step counters 0.  Needs a
+ *           row; one workspace serves both precisions: the bf16 path keeps no weight copies or extra statistics), one fp32 gradient
+ *           buffer in the layout of the parameters and the AdamW moments (zeroed), step counters 0.  Needs a
  *           finalized bias = False model (MGPT_ERR_UNSUPPORTED otherwise) with block_size 256 (MGPT_ERR_ARG).  A second call re-sizes the
  *           activation part only (synchronises the device): gradients, moments and step counts are kept.  Nothing is allocated for a model
  *           that never trains.
- *   forward_backward: the exact-fp32 forward, then grads += loss_scale * d(mean cross-entropy, ignore_index = -1)/d(theta); d_targets
+ *   forward_backward: = forward_backward_prec with MGPT_PREC_F32.
+ *   forward_backward_prec: the forward in `precision`, then grads += loss_scale * d(mean cross-entropy, ignore_index = -1)/d(theta); d_targets
  *           int32 [rows][T], -1 = ignored; *d_loss (device, may be NULL) = the unscaled mean loss.  Calls of more rows than the workspace
  *           run in chunks; the mean is over the targeted positions of the whole call.  Synchronises `stream` once, before any other work of
  *           the call is queued, to read the targeted-position count: none (MGPT_ERR_ARG, where torch gives NaN) or a target outside [-1, 67)
- *           (MGPT_ERR_ARG) is refused.  T != 256: MGPT_ERR_ARG.
+ *           (MGPT_ERR_ARG) is refused.  T != 256: MGPT_ERR_ARG.  precision: MGPT_PREC_F32 = the exact-fp32 path above (bit-identical
+ *           gradients to forward_backward); MGPT_PREC_BF16 = train.py's torch.amp.autocast(bfloat16) regime: the operands and outputs of the
+ *           block linears, q, k, v, attention's output, P and dS and GELU's output are rounded to bf16 (round-to-nearest-even), and the
+ *           block linears and attention run on bf16 MFMAs with fp32 accumulation; the embedding, residual stream, LayerNorm, the softmax
+ *           statistics, the tied head, cross-entropy,
+ *           every accumulator, the gradients and the master weights stay fp32.  The weights are rounded as they are read, so the call
+ *           always uses the current parameters and needs no memory beyond the fp32 workspace.  Deterministic like the fp32 path.  Both
+ *           precisions accumulate into the same gradient buffer.  Any other precision: MGPT_ERR_UNSUPPORTED.
  *   zero_grad: grads = 0.
  *   clip_grad_norm: torch.nn.utils.clip_grad_norm_: total = || (||g_p||)_p ||, coef = min(max_norm / (total + 1e-6), 1), g *= coef; the
  *           coefficient stays on the device, *d_total_norm (device, may be NULL) = total.  max_norm <= 0: the norm only.
@@ -323,6 +334,8 @@ int mgpt_gpt_train_alloc(mgpt_gpt *gpt, int max_rows);
 int mgpt_gpt_train_free(mgpt_gpt *gpt);
 int mgpt_gpt_forward_backward(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int T, const int32_t *d_targets, float loss_scale,
                               float *d_loss, void *stream);
+int mgpt_gpt_forward_backward_prec(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int T, const int32_t *d_targets, float loss_scale,
+                                   float *d_loss, int precision, void *stream);
 int mgpt_gpt_zero_grad(mgpt_gpt *gpt, void *stream);
 int mgpt_gpt_clip_grad_norm(mgpt_gpt *gpt, float max_norm, float *d_total_norm, void *stream);
 int mgpt_gpt_adamw_step(mgpt_gpt *gpt, float lr, float beta1, float beta2, float eps, float weight_decay, void *stream);

@@ -1,11 +1,12 @@
-// train.hip -- training on the device (replaces train.py:324-331 with model.py:180-184 and :202-226): exact-fp32 forward with saved
-// activations, backward into one fp32 gradient buffer in the layout of mgpt_gpt::params, torch's clip_grad_norm_ and AdamW.
+// train.hip -- training on the device (replaces train.py:324-331 with model.py:180-184 and :202-226): exact-fp32 or bf16 mixed-precision
+// forward with saved activations, backward into one fp32 gradient buffer in the layout of mgpt_gpt::params, torch's clip_grad_norm_ and AdamW.
 #include <string>
 #include <vector>
 
 #include "common.h"
 #include "gpt_ctx.h"
 #include "gpt_kernels_train.h"
+#include "gpt_kernels_train_bf16.h"
 
 using namespace mgpt;
 
@@ -21,7 +22,8 @@ constexpr int kMaxSlabs = 64;
 // scratch: dx, d ln, dy, dq|dk|dv (3), dh (4), gelu(a) (4), gain terms -- 14 C, plus logits and their gradient (2 * 67), the token's loss
 // term (1) and the attention statistics (3 n_head).  In all (12 L + 16) C + 135 + 3 n_head floats per token, times 256 tokens of 4 bytes:
 // 6M 30.1 MB per row (25.7 MB of it saved activations), 2M 7.0 MB, 85M 127.5 MB (114.8 MB).  Independent of max_rows: the weight-gradient
-// slabs (at most 64 x 4 C^2 floats) and the gradients and AdamW moments (3 x the parameters).
+// slabs (at most 64 x 4 C^2 floats; beyond 128 C rows the bf16 path's LayerNorm-gain partials, 2 C floats per row, are larger) and the
+// gradients and AdamW moments (3 x the parameters).
 struct TrainState {
     int max_rows = 0;
     int64_t M = 0;
@@ -220,6 +222,175 @@ int chunk_fwd_bwd(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows, cons
     return MGPT_OK;
 }
 
+// ----- bf16 mixed precision (MGPT_PREC_BF16): the matrix products of the five linears on bf16 MFMAs (gpt_kernels_train_bf16.h) -----
+int gemm_bf16_check(int64_t M, int N, int K, int kps)
+{
+    MGPT_REQUIRE(M % 16 == 0 && N % 16 == 0 && K % 32 == 0 && kps % 32 == 0 && M <= INT32_MAX, MGPT_ERR_UNSUPPORTED,
+                 "bf16 gemm shape M=%lld N=%d K=%d (slab %d)", (long long)M, N, K, kps);
+    return MGPT_OK;
+}
+
+template <typename TA, bool A_KC, typename TB, bool B_KC, int EPI>
+int bf_gemm(const TA *A, int64_t lda, const TB *B, int64_t ldb, int64_t M, int N, int K, const tbk::Epi &ep, hipStream_t s, int slabs = 1,
+            int kps = 0)
+{
+    if (slabs == 1) kps = K;
+    const int rc = gemm_bf16_check(M, N, K, kps);
+    if (rc != MGPT_OK) return rc;
+    const dim3 grid((unsigned)cdiv(N, tbk::BN), (unsigned)cdiv64(M, tbk::BM), (unsigned)slabs);
+    hipLaunchKernelGGL((tbk::gemm_bf16_kernel<TA, A_KC, TB, B_KC, EPI>), grid, dim3(256), 0, s, A, lda, B, ldb, (int)M, N, K, kps, ep);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
+// dW[Nout][Kin] += dY^T @ X over Mtok tokens on bf16 MFMAs: fp32 partials per token slab (the slabs of weight_grad, 32-token aligned), summed in order
+template <typename TY, typename TX>
+int weight_grad_bf16(TrainState *t, const TY *dY, const TX *X, float *dW, int Nout, int Kin, int64_t Mtok, hipStream_t s)
+{
+    const int S = slabs_of(Mtok), kps = (int)((cdiv64(Mtok, S) + 31) / 32 * 32);
+    MGPT_REQUIRE((size_t)S * Nout * Kin <= t->part_elems, MGPT_ERR_ARG, "weight-gradient slabs exceed the workspace");
+    tbk::Epi ep;
+    ep.f32 = t->part;
+    ep.ldc = Kin;
+    int rc = bf_gemm<TY, false, TX, false, tbk::E_PART>(dY, Nout, X, Kin, Nout, Kin, (int)Mtok, ep, s, S, kps);
+    if (rc != MGPT_OK) return rc;
+    const int64_t n = (int64_t)Nout * Kin;
+    hipLaunchKernelGGL(trk::slab_reduce_kernel, dim3(grid_1d(n)), dim3(256), 0, s, (const float *)t->part, S, n, dW);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
+// LayerNorm backward with the gain's column sums fused: one partial per 128 tokens, summed in order
+template <bool ADD>
+int ln_backward_bf16(TrainState *t, const float *x, const float *w, const float *dxn, float *dres, float *gw, int64_t Mtok, int C, hipStream_t s)
+{
+    const int64_t P = cdiv64(Mtok, tbk::kLnTok);
+    MGPT_REQUIRE(C <= 64 * tbk::kLnMaxJ && (size_t)(P * C) <= t->part_elems, MGPT_ERR_UNSUPPORTED, "LayerNorm backward: C=%d, %lld tokens", C,
+                 (long long)Mtok);
+    hipLaunchKernelGGL((tbk::ln_bwd_gain_kernel<ADD>), dim3((unsigned)P), dim3(256), 0, s, x, w, dxn, dres, t->part, Mtok, C);
+    MGPT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tbk::colsum_reduce_kernel, dim3((unsigned)cdiv(C, 64)), dim3(1024), 0, s, (const float *)t->part, (int)P, C, gw);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
+// attention on bf16 MFMAs: forward (y bf16, statistics fp32) and backward (dq | dk | dv fp32 into t->DQKV)
+template <int HS>
+int attn_bf16(const uint16_t *qkv, int64_t plane, uint16_t *y, float *stats, int rows, int n_head, float scale, hipStream_t s)
+{
+    const size_t lds = tbk::attn_fwd_lds<HS>();
+    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tbk::attn_fwd_bf16_kernel<HS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(tbk::attn_fwd_bf16_kernel<HS>, dim3((unsigned)(rows * n_head)), dim3(256), lds, s, qkv, plane, y, stats, n_head, scale);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
+template <int HS>
+int attn_bwd_bf16(TrainState *t, const uint16_t *qkv, int64_t plane, const uint16_t *y, const uint16_t *dy, const float *stats, int rows,
+                  int n_head, float scale, hipStream_t s)
+{
+    const size_t lds = tbk::attn_bwd_lds<HS>();
+    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tbk::attn_bwd_bf16_kernel<HS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(tbk::attn_bwd_bf16_kernel<HS>, dim3((unsigned)(rows * n_head)), dim3(512), lds, s, qkv, plane, y, dy, stats, t->DQKV,
+                       n_head, scale);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
+// one chunk of rows in train.py's autocast regime.  Rounded to bf16 (as autocast holds them): the operands of the five linears -- the head's
+// excepted, which stays fp32 --, q, k, v, attention's output and its gradient, P and dS, the linears' outputs and GELU's, the gradients of the
+// MLP hidden tensors.  fp32: the embedding sum, the residual stream and its gradient, LayerNorm, softmax statistics, cross-entropy and every
+// accumulator.  The workspace is the fp32 path's: QKV[l] holds the bf16 q | k | v planes, Y[l] bf16 y and then the softmax statistics, A[l]
+// bf16(a) | bf16(gelu(a)), DY the bf16 gradient of y, DH the bf16 gradient of a.
+int chunk_fwd_bwd_bf16(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows, const int32_t *tg, float loss_scale, hipStream_t s)
+{
+    const int C = g->C, L = g->L;
+    const int64_t M = (int64_t)rows * kT;
+    const float *P = g->params;
+    float *G = t->grads;
+    int rc;
+    tbk::Epi ep;
+    if ((rc = gpt_f32_embed(g, tok, t->X[0], M, s)) != MGPT_OK) return rc;
+    const float scale = 1.0f / sqrtf((float)g->hs);
+    for (int l = 0; l < L; l++) {
+        const LayerOff &lo = g->layers[l];
+        float *x = t->X[l], *xm = t->XM[l], *xo = (l + 1 < L) ? t->X[l + 1] : t->XF;
+        uint16_t *a16 = reinterpret_cast<uint16_t *>(t->A[l]), *h16 = a16 + 4 * M * C;
+        uint16_t *qkv16 = reinterpret_cast<uint16_t *>(t->QKV[l]), *y16 = reinterpret_cast<uint16_t *>(t->Y[l]);
+        float *ast = reinterpret_cast<float *>(y16 + M * C);          // 2 n_head floats per token <= the C / 2 floats left in Y[l]
+        if ((rc = gpt_f32_layernorm(g, x, P + lo.ln1, t->XN1[l], M, s)) != MGPT_OK) return rc;
+        ep = tbk::Epi();
+        ep.b16 = qkv16; ep.C = C; ep.hs = g->hs; ep.n_head = g->nh; ep.plane = M * C;
+        if ((rc = bf_gemm<float, true, float, true, tbk::E_QKV>(t->XN1[l], C, P + lo.attn_w, C, M, 3 * C, C, ep, s)) != MGPT_OK) return rc;
+        rc = g->hs == 32 ? attn_bf16<32>(qkv16, M * C, y16, ast, rows, g->nh, scale, s)
+                         : attn_bf16<64>(qkv16, M * C, y16, ast, rows, g->nh, scale, s);
+        if (rc != MGPT_OK) return rc;
+        ep = tbk::Epi();
+        ep.f32 = xm; ep.res = x; ep.ldc = C;
+        if ((rc = bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(y16, C, P + lo.proj_w, C, M, C, C, ep, s)) != MGPT_OK) return rc;
+        if ((rc = gpt_f32_layernorm(g, xm, P + lo.ln2, t->XN2[l], M, s)) != MGPT_OK) return rc;
+        ep = tbk::Epi();
+        ep.b16 = a16; ep.b16b = h16; ep.ldc = 4 * C;
+        if ((rc = bf_gemm<float, true, float, true, tbk::E_FC>(t->XN2[l], C, P + lo.fc_w, C, M, 4 * C, C, ep, s)) != MGPT_OK) return rc;
+        ep = tbk::Epi();
+        ep.f32 = xo; ep.res = xm; ep.ldc = C;
+        if ((rc = bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(h16, 4 * C, P + lo.proj2_w, 4 * C, M, C, 4 * C, ep, s)) != MGPT_OK) return rc;
+    }
+    // head: the fp32 path's (ln_f, the tied head in fp32, cross-entropy), with this path's LayerNorm backward
+    if ((rc = gpt_f32_layernorm(g, t->XF, P + g->off_lnf, t->XNF, M, s)) != MGPT_OK) return rc;
+    if ((rc = tr_gemm<true, false, trk::OUT_STORE>(t->XNF, C, P + g->off_wte, C, t->LG, kV, M, kV, C, s)) != MGPT_OK) return rc;
+    hipLaunchKernelGGL(trk::ce_kernel, dim3((unsigned)cdiv64(M, 256)), dim3(256), 0, s, (const float *)t->LG, tg, M, (const int32_t *)t->cnt,
+                       loss_scale, t->DLG, t->NLL);
+    MGPT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(trk::sum_acc_kernel, dim3(1), dim3(256), 0, s, (const float *)t->NLL, M, t->loss_acc);
+    MGPT_LAUNCH_CHECK();
+    if ((rc = tr_gemm<true, true, trk::OUT_STORE>(t->DLG, kV, P + g->off_wte, C, t->DXN, C, M, C, kV, s)) != MGPT_OK) return rc;
+    if ((rc = weight_grad(t, t->DLG, t->XNF, G + g->off_wte, kV, C, M, s)) != MGPT_OK) return rc;
+    if ((rc = ln_backward_bf16<false>(t, t->XF, P + g->off_lnf, t->DXN, t->DX, G + g->off_lnf, M, C, s)) != MGPT_OK) return rc;
+    for (int l = L - 1; l >= 0; l--) {
+        const LayerOff &lo = g->layers[l];
+        const uint16_t *a16 = reinterpret_cast<const uint16_t *>(t->A[l]), *h16 = a16 + 4 * M * C;
+        uint16_t *da16 = reinterpret_cast<uint16_t *>(t->DH);
+        // MLP: DX = d x_out (its bf16 rounding is the gradient of the bf16 c_proj output)
+        ep = tbk::Epi();
+        ep.b16 = da16; ep.aux = a16; ep.ldc = 4 * C;
+        if ((rc = bf_gemm<float, true, float, false, tbk::E_GELU_BWD>(t->DX, C, P + lo.proj2_w, 4 * C, M, 4 * C, C, ep, s)) != MGPT_OK) return rc;
+        if ((rc = weight_grad_bf16(t, (const float *)t->DX, h16, G + lo.proj2_w, C, 4 * C, M, s)) != MGPT_OK) return rc;
+        ep = tbk::Epi();
+        ep.f32 = t->DXN; ep.ldc = C;
+        if ((rc = bf_gemm<uint16_t, true, float, false, tbk::E_F32>(da16, 4 * C, P + lo.fc_w, C, M, C, 4 * C, ep, s)) != MGPT_OK) return rc;
+        if ((rc = weight_grad_bf16(t, (const uint16_t *)da16, (const float *)t->XN2[l], G + lo.fc_w, 4 * C, C, M, s)) != MGPT_OK) return rc;
+        if ((rc = ln_backward_bf16<true>(t, t->XM[l], P + lo.ln2, t->DXN, t->DX, G + lo.ln2, M, C, s)) != MGPT_OK) return rc;
+        // attention: DX = d x_mid;  d y = bf16(DX W_proj), the gradient of the bf16 attention output
+        const uint16_t *qkv16 = reinterpret_cast<const uint16_t *>(t->QKV[l]), *y16 = reinterpret_cast<const uint16_t *>(t->Y[l]);
+        const float *ast = reinterpret_cast<const float *>(y16 + M * C);
+        uint16_t *dy16 = reinterpret_cast<uint16_t *>(t->DY);
+        ep = tbk::Epi();
+        ep.b16 = dy16; ep.ldc = C;
+        if ((rc = bf_gemm<float, true, float, false, tbk::E_B16>(t->DX, C, P + lo.proj_w, C, M, C, C, ep, s)) != MGPT_OK) return rc;
+        if ((rc = weight_grad_bf16(t, (const float *)t->DX, y16, G + lo.proj_w, C, C, M, s)) != MGPT_OK) return rc;
+        rc = g->hs == 32 ? attn_bwd_bf16<32>(t, qkv16, M * C, y16, dy16, ast, rows, g->nh, scale, s)
+                         : attn_bwd_bf16<64>(t, qkv16, M * C, y16, dy16, ast, rows, g->nh, scale, s);
+        if (rc != MGPT_OK) return rc;
+        ep = tbk::Epi();
+        ep.f32 = t->DXN; ep.ldc = C;
+        if ((rc = bf_gemm<float, true, float, false, tbk::E_F32>(t->DQKV, 3 * C, P + lo.attn_w, C, M, C, 3 * C, ep, s)) != MGPT_OK) return rc;
+        if ((rc = weight_grad_bf16(t, (const float *)t->DQKV, (const float *)t->XN1[l], G + lo.attn_w, 3 * C, C, M, s)) != MGPT_OK) return rc;
+        if ((rc = ln_backward_bf16<true>(t, t->X[l], P + lo.ln1, t->DXN, t->DX, G + lo.ln1, M, C, s)) != MGPT_OK) return rc;
+    }
+    // embedding: the fp32 path's kernels
+    hipLaunchKernelGGL(trk::wpe_bwd_kernel, dim3((unsigned)cdiv64((int64_t)kT * C, 256)), dim3(256), 0, s, (const float *)t->DX, rows, C, G + g->off_wpe);
+    MGPT_LAUNCH_CHECK();
+    {
+        const int S = slabs_of(M), kps = slab_tokens(M);
+        hipLaunchKernelGGL(trk::wte_bwd_part_kernel, dim3(kV, (unsigned)S), dim3(256), 0, s, tok, (const float *)t->DX, M, C, kps, t->part);
+        MGPT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(trk::slab_reduce_kernel, dim3(grid_1d((int64_t)kV * C)), dim3(256), 0, s, t->part, S, (int64_t)kV * C, G + g->off_wte);
+        MGPT_LAUNCH_CHECK();
+    }
+    return MGPT_OK;
+}
+
 int require_train(mgpt_gpt *g)
 {
     MGPT_REQUIRE(g, MGPT_ERR_ARG, "NULL argument");
@@ -295,7 +466,8 @@ extern "C" int mgpt_gpt_train_alloc(mgpt_gpt *g, int max_rows)
     t->XF = fa(M * C); t->XNF = fa(M * C); t->LG = fa(M * kV); t->DLG = fa(M * kV); t->NLL = fa(M);
     t->DX = fa(M * C); t->DXN = fa(M * C); t->DY = fa(M * C); t->DQKV = fa(3 * M * C); t->DH = fa(4 * M * C); t->HT = fa(4 * M * C);
     t->GP = fa(M * C); t->AST = fa(M * g->nh * 3);
-    const size_t part_elems = (size_t)slabs_of(M) * (size_t)std::max<int64_t>(4 * C * C, kV * C);
+    // weight-gradient, embedding and LayerNorm-gain partials (the bf16 path's: one row of C per 128 tokens)
+    const size_t part_elems = std::max((size_t)slabs_of(M) * (size_t)std::max<int64_t>(4 * C * C, kV * C), (size_t)(cdiv64(M, tbk::kLnTok) * C));
     t->part = fa((int64_t)part_elems);
     if (e != hipSuccess) {             // the optimizer state survives; forward_backward refuses until a re-size succeeds
         set_error("training workspace allocation failed (%d rows): %s", max_rows, hipGetErrorString(e));
@@ -318,12 +490,20 @@ extern "C" int mgpt_gpt_train_free(mgpt_gpt *g)
 extern "C" int mgpt_gpt_forward_backward(mgpt_gpt *g, const uint8_t *d_tokens, int rows, int T, const int32_t *d_targets, float loss_scale,
                                          float *d_loss, void *stream)
 {
+    return mgpt_gpt_forward_backward_prec(g, d_tokens, rows, T, d_targets, loss_scale, d_loss, MGPT_PREC_F32, stream);
+}
+
+extern "C" int mgpt_gpt_forward_backward_prec(mgpt_gpt *g, const uint8_t *d_tokens, int rows, int T, const int32_t *d_targets, float loss_scale,
+                                              float *d_loss, int precision, void *stream)
+{
     int rc = require_train(g);
     if (rc != MGPT_OK) return rc;
     MGPT_REQUIRE(d_tokens && d_targets, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(rows > 0, MGPT_ERR_ARG, "rows=%d", rows);
     MGPT_REQUIRE(T == kT, MGPT_ERR_ARG, "training takes rows of T = 256 tokens, got T = %d", T);
     MGPT_REQUIRE(!g->has_bias, MGPT_ERR_UNSUPPORTED, "training supports bias = False checkpoints only (the released configs)");
+    MGPT_REQUIRE(precision == MGPT_PREC_F32 || precision == MGPT_PREC_BF16, MGPT_ERR_UNSUPPORTED,
+                 "training precision %d: MGPT_PREC_F32 (exact fp32) or MGPT_PREC_BF16 (bf16 mixed precision)", precision);
     TrainState *t = ts(g);
     MGPT_REQUIRE(t->max_rows > 0, MGPT_ERR_STATE, "the training workspace holds no activation memory (a re-size failed): mgpt_gpt_train_alloc again");
     hipStream_t s = (hipStream_t)stream;
@@ -337,7 +517,10 @@ extern "C" int mgpt_gpt_forward_backward(mgpt_gpt *g, const uint8_t *d_tokens, i
     MGPT_HIP(hipMemsetAsync(t->loss_acc, 0, sizeof(double), s));
     for (int r0 = 0; r0 < rows; r0 += t->max_rows) {
         const int n = std::min(t->max_rows, rows - r0);
-        if ((rc = chunk_fwd_bwd(g, t, d_tokens + (size_t)r0 * kT, n, d_targets + (size_t)r0 * kT, loss_scale, s)) != MGPT_OK) return rc;
+        const uint8_t *tk = d_tokens + (size_t)r0 * kT;
+        const int32_t *tg = d_targets + (size_t)r0 * kT;
+        rc = precision == MGPT_PREC_BF16 ? chunk_fwd_bwd_bf16(g, t, tk, n, tg, loss_scale, s) : chunk_fwd_bwd(g, t, tk, n, tg, loss_scale, s);
+        if (rc != MGPT_OK) return rc;
     }
     if (d_loss) {
         hipLaunchKernelGGL(trk::loss_final_kernel, dim3(1), dim3(64), 0, s, (const double *)t->loss_acc, (const int32_t *)t->cnt, d_loss);

@@ -7,7 +7,8 @@
     act(idx, do_sample=True, generator=None) -> LongTensor [B]   (model.py:244-260)
 plus the device-resident fast path `act_tokens(tokens_u8, ...)` used by the batched runner.
 `score_tokens` and mapf_gpt_amd/scoring.py score a checkpoint on expert data (train.py estimate_loss).
-Training (train.py:324-331) runs on the device in exact fp32: train(), forward_backward(idx, targets), zero_grad(),
+Training (train.py:324-331) runs on the device in exact fp32 or in train.py's bf16 autocast regime (forward_backward(...,
+precision="bf16")): train(), forward_backward(idx, targets), zero_grad(),
 clip_grad_norm_(), grads(), state_dict() and configure_optimizers() -> AdamW (model.py:202-226).  estimate_mfu and
 crop_block_size are out of scope.  Every compute call goes through the C ABI; there is no PyTorch forward here.
 """
@@ -313,9 +314,13 @@ class GPT:
         if getattr(self, "_train_rows", None) is None:
             raise RuntimeError("call train() first: it allocates the training workspace")
 
-    def forward_backward(self, idx, targets, loss_scale=1.0):
+    def forward_backward(self, idx, targets, loss_scale=1.0, precision="f32"):
         """= loss = model(idx, targets)[1]; (loss * loss_scale).backward() (model.py:180-184, train.py:324-331): gradients ACCUMULATE into the
-        device buffer; returns the unscaled mean cross-entropy (ignore_index=-1) as a 0-d float32 device tensor."""
+        device buffer; returns the unscaled mean cross-entropy (ignore_index=-1) as a 0-d float32 device tensor.  precision "f32": exact fp32;
+        "bf16": train.py's torch.amp.autocast(bfloat16) regime (bf16 MFMA linears, fp32 gradients and master weights).  Micro-steps of
+        either precision accumulate into the same buffer."""
+        if precision not in _lib.PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}, got {precision!r}")
         self._require_train()
         tokens = self._tokens_u8(idx)
         B, T = tokens.shape
@@ -325,8 +330,8 @@ class GPT:
         tg = targets.reshape(B, T).to(device=self.device, dtype=torch.int32).contiguous()
         loss = torch.empty((), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().mgpt_gpt_forward_backward(self._h, _lib.ptr(tokens), B, T, _lib.ptr(tg), float(loss_scale), _lib.ptr(loss),
-                                                            _lib.stream_ptr()))
+            _lib.check(_lib.lib().mgpt_gpt_forward_backward_prec(self._h, _lib.ptr(tokens), B, T, _lib.ptr(tg), float(loss_scale), _lib.ptr(loss),
+                                                                 _lib.PRECISIONS[precision], _lib.stream_ptr()))
         return loss
 
     def zero_grad(self, set_to_none=True):

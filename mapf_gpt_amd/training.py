@@ -1,5 +1,5 @@
 """train.py's training loop (train.py:29-56 defaults, :162-165 batches, :263-276 cosine learning rate with warmup, :284-362 loop) on the
-device training path of GPT (forward_backward, clip_grad_norm_, configure_optimizers -> AdamW), exact fp32.
+device training path of GPT (forward_backward, clip_grad_norm_, configure_optimizers -> AdamW).
 
     python -m mapf_gpt_amd.training --init SHAPE_OR_CKPT --data FILE_OR_DIR --val FILE_OR_DIR [--out-dir DIR] [--max-iters N] ...
 
@@ -10,6 +10,10 @@ targets of -1 except the last position, which holds the expert action (fast_data
 loss of eval_iters batches of each split is measured with scoring.evaluate (= estimate_loss, train.py:244-259) and a ckpt.pt is written as
 train.py:298-310 writes it ({"model", "optimizer", "model_args", "iter_num", "best_val_loss", "config"}); weights.load_checkpoint and
 MAPFGPTInference load it unchanged.  One JSON line per evaluation and one at the end.  No DDP, GradScaler or torch.compile.
+
+--dtype takes train.py's knob (train.py:66-70): float32 (exact fp32, the default here) or bfloat16 (every micro-step and every estimate_loss in
+the bf16 autocast regime: forward_backward(precision="bf16"), scoring.evaluate(precision="bf16")).  train.py itself defaults to bfloat16 on a
+GPU that supports it; this command keeps float32 as its default.  float16 is refused: it needs a GradScaler, which this command does not have.
 """
 import argparse
 import glob
@@ -83,7 +87,10 @@ def _cpu(obj):
     return obj
 
 
-def main(argv=None):
+DTYPES = {"float32": "f32", "bfloat16": "bf16"}       # --dtype (train.py:66-70) -> precision of forward_backward and scoring.evaluate
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--init", required=True, help='shape name ("2M", "6M", "85M", "tiny") or a checkpoint path')
     ap.add_argument("--resume", action="store_true", help="restore optimizer state, iter_num and best_val_loss from the --init checkpoint")
@@ -96,8 +103,20 @@ def main(argv=None):
             ap.add_argument("--" + k.replace("_", "-"), type=lambda s: s.lower() in ("1", "true", "yes"), default=v)
         else:
             ap.add_argument("--" + k.replace("_", "-"), type=type(v), default=v)
+    ap.add_argument("--dtype", default="float32", choices=["float32", "bfloat16", "float16"],
+                    help="float32 (default here; train.py defaults to bfloat16) or bfloat16 (autocast regime); float16 is refused")
     a = ap.parse_args(argv)
+    if a.dtype == "float16":
+        ap.error("--dtype float16 is not supported: it needs torch's GradScaler, which this training path does not have "
+                 "(use bfloat16, which needs none, or float32)")
+    a.precision = DTYPES[a.dtype]
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     config = {k: getattr(a, k) for k in DEFAULTS}
+    config["dtype"] = a.dtype
     from . import scoring, weights
     from .model import GPT, GPTConfig
 
@@ -127,7 +146,7 @@ def main(argv=None):
         for split, it in (("train", train_it), ("val", val_it)):
             xs, ts = zip(*[next(it) for _ in range(a.eval_iters)])
             x, t = np.concatenate(xs), np.concatenate(ts)
-            out[split] = scoring.evaluate(net, x, t[:, -1], batch_size=a.batch_size, precision="f32")["loss"]
+            out[split] = scoring.evaluate(net, x, t[:, -1], batch_size=a.batch_size, precision=a.precision)["loss"]
         net.train()
         return out
 
@@ -149,7 +168,8 @@ def main(argv=None):
                     rec["saved"] = os.path.join(a.out_dir, "ckpt.pt")
             print(json.dumps(rec), flush=True)
         for _ in range(a.gradient_accumulation_steps):         # train.py:314-331
-            loss = net.forward_backward(torch.as_tensor(X), torch.as_tensor(Y), loss_scale=1.0 / a.gradient_accumulation_steps)
+            loss = net.forward_backward(torch.as_tensor(X), torch.as_tensor(Y), loss_scale=1.0 / a.gradient_accumulation_steps,
+                                       precision=a.precision)
             X, Y = next(train_it)
         if a.grad_clip != 0.0:
             net.clip_grad_norm_(a.grad_clip)

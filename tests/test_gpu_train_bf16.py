@@ -1,0 +1,261 @@
+"""bf16 mixed-precision training on the device (GPT.forward_backward(..., precision="bf16"), mgpt_gpt_forward_backward_prec).
+
+The truth g64 is fp64 autograd of the pinned restatement (tests/train_ref.py), the yardstick g_ac the same restatement on cuda leaves under
+torch.autocast("cuda", torch.bfloat16), train.py's own regime.  The bar, fixed before the first device run: for every tensor
+max|g - g64| <= 2 max|g_ac - g64| + 1e-3 max|g64|, and |l - l64| <= 2 |l_ac - l64| + 2e-3 |l64| for the loss."""
+
+import numpy as np
+import pytest
+import torch
+
+from mapf_gpt_amd import _lib, weights
+from mapf_gpt_amd.model import GPT, GPTConfig, build_model
+from tests.test_gpu_train import _dev_grads, _net, _rows, _targets
+from tests.test_loss_cpu import seq_oracle
+from tests.train_ref import targets_last
+
+pytestmark = pytest.mark.gpu
+
+
+def _ref(sd, args, micro, loss_scale=1.0, autocast=False):
+    """-> (losses, {name: grad float64 cpu}) of the micro-steps [(tokens, targets), ...]: fp64 (autocast=False) or fp32 leaves under bf16 autocast"""
+    dtype = torch.float32 if autocast else torch.float64
+    lv = {k: torch.tensor(np.asarray(v), dtype=dtype, device="cuda", requires_grad=True) for k, v in sd.items() if k != "lm_head.weight"}
+    view = dict(lv)
+    view["lm_head.weight"] = lv["transformer.wte.weight"]
+    losses = []
+    for tk, tg in micro:
+        tk, tg = torch.as_tensor(np.asarray(tk)).cuda(), torch.as_tensor(np.asarray(tg)).cuda()
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            _, loss = seq_oracle(view, args, tk, tg, dtype=dtype)
+        (loss.float() * loss_scale if autocast else loss * loss_scale).backward()
+        losses.append(float(loss.detach()))
+    return losses, {k: v.grad.detach().double().cpu() for k, v in lv.items()}
+
+
+def _check(name, got, g64, gac, loss=None, l64=None, lac=None):
+    assert set(got) == set(g64)
+    for k, ref in g64.items():
+        m = float(ref.abs().max())
+        err = float((got[k] - ref).abs().max())
+        eac = float((gac[k] - ref).abs().max())
+        bar = 2 * eac + 1e-3 * m
+        assert err <= bar, f"{name} {k}: max|g - g64| {err:.3e}, bar {bar:.3e} (autocast {eac:.3e}, max|g64| {m:.3e})"
+    if loss is not None:
+        bar = 2 * abs(lac - l64) + 2e-3 * abs(l64)
+        assert abs(loss - l64) <= bar, f"{name} loss {loss} vs {l64} (autocast {lac}), bar {bar:.3e}"
+
+
+def _bf16_case(net, micro, loss_scale=1.0):
+    net.zero_grad()
+    losses = [float(net.forward_backward(torch.as_tensor(tk), torch.as_tensor(tg), loss_scale=loss_scale, precision="bf16")) for tk, tg in micro]
+    got = _dev_grads(net)
+    sd = {k: v.cpu().numpy() for k, v in net.state_dict().items()}
+    l64, g64 = _ref(sd, net._args, micro, loss_scale)
+    lac, gac = _ref(sd, net._args, micro, loss_scale, autocast=True)
+    return losses, got, l64, g64, lac, gac
+
+
+@pytest.mark.parametrize("name", ["tiny", "2M", "6M", "85M"])
+@pytest.mark.parametrize("case", ["last", "all", "mixed"])
+def test_bf16_gradients_within_the_autocast_bar(case, name):
+    rows = 2 if name == "85M" else 3
+    tokens, actions = _rows(rows, seed=len(name))
+    targets = _targets(case, tokens, actions)
+    net = _net(name)
+    losses, got, l64, g64, lac, gac = _bf16_case(net, [(tokens, targets)])
+    _check(f"{name}/{case}", got, g64, gac, losses[0], l64[0], lac[0])
+
+
+def test_bf16_realistic_size():
+    """6M x 64 rows: 128-token GEMM tiles by the hundred, 64 weight-gradient slabs, 128 LayerNorm gain partials"""
+    tokens, actions = _rows(64, seed=11)
+    targets = _targets("mixed", tokens, actions)
+    net = _net("6M", max_rows=64)
+    losses, got, l64, g64, lac, gac = _bf16_case(net, [(tokens, targets)])
+    _check("6M x 64", got, g64, gac, losses[0], l64[0], lac[0])
+
+
+def test_bf16_deterministic():
+    tokens, actions = _rows(4, seed=3)
+    targets = _targets("mixed", tokens, actions)
+    net = _net("6M")
+    out = []
+    for _ in range(2):
+        net.zero_grad()
+        loss = net.forward_backward(torch.as_tensor(tokens), torch.as_tensor(targets), precision="bf16")
+        out.append((loss.cpu(), _dev_grads(net)))
+    assert torch.equal(out[0][0], out[1][0])
+    for k in out[0][1]:
+        assert torch.equal(out[0][1][k], out[1][1][k]), f"{k}: two identical bf16 calls differ"
+
+
+def test_bf16_accumulation_and_chunking():
+    tokens, actions = _rows(5, seed=4)
+    # two micro-steps with loss_scale 0.5 accumulate (train.py:324-331, gradient_accumulation_steps = 2)
+    net = _net("6M")
+    micro = [(tokens[:2], _targets("mixed", tokens[:2], actions[:2])), (tokens[2:4], targets_last(actions[2:4]))]
+    losses, got, l64, g64, lac, gac = _bf16_case(net, micro, loss_scale=0.5)
+    _check("accumulation", got, g64, gac)
+    for i in range(2):
+        assert abs(losses[i] - l64[i]) <= 2 * abs(lac[i] - l64[i]) + 2e-3 * abs(l64[i])
+    # 5 rows in chunks of 2, 2, 1: one normaliser for the whole call
+    small = _net("tiny", train_rows=2)
+    targets = _targets("mixed", tokens, actions)
+    losses, got, l64, g64, lac, gac = _bf16_case(small, [(tokens, targets)])
+    _check("chunked", got, g64, gac, losses[0], l64[0], lac[0])
+    # f32 + bf16 micro-steps share the gradient buffer: the sum of the parts, to fp32 rounding
+    tk, tg = torch.as_tensor(tokens), torch.as_tensor(targets)
+    parts = []
+    for p in ("f32", "bf16"):
+        small.zero_grad()
+        small.forward_backward(tk, tg, precision=p)
+        parts.append(_dev_grads(small))
+    small.zero_grad()
+    small.forward_backward(tk, tg, precision="f32")
+    small.forward_backward(tk, tg, precision="bf16")
+    both = _dev_grads(small)
+    for k in both:
+        a, b = parts[0][k], parts[1][k]
+        tol = 1e-6 * float((a.abs() + b.abs()).max())
+        assert float((both[k] - (a + b)).abs().max()) <= tol, k
+
+
+def test_f32_through_the_new_entry_point_is_bit_identical():
+    tokens, actions = _rows(3, seed=5)
+    targets = _targets("mixed", tokens, actions)
+    net = _net("2M")
+    tok = torch.as_tensor(tokens).to(torch.uint8).cuda().contiguous()
+    tg = torch.as_tensor(targets).to(torch.int32).cuda().contiguous()
+    res = []
+    for prec in (None, _lib.PREC_F32):
+        net.zero_grad()
+        loss = torch.empty((), dtype=torch.float32, device="cuda")
+        L = _lib.lib()
+        if prec is None:
+            rc = L.mgpt_gpt_forward_backward(net._h, _lib.ptr(tok), 3, 256, _lib.ptr(tg), 1.0, _lib.ptr(loss), _lib.stream_ptr())
+        else:
+            rc = L.mgpt_gpt_forward_backward_prec(net._h, _lib.ptr(tok), 3, 256, _lib.ptr(tg), 1.0, _lib.ptr(loss), prec, _lib.stream_ptr())
+        _lib.check(rc)
+        res.append((loss.cpu(), _dev_grads(net)))
+    assert torch.equal(res[0][0], res[1][0])
+    for k in res[0][1]:
+        assert torch.equal(res[0][1][k], res[1][1][k]), k
+
+
+def test_after_a_bf16_step():
+    tokens, actions = _rows(8, seed=6)
+    targets = targets_last(actions)
+    net = _net("6M", max_rows=16)
+    opt = net.configure_optimizers(0.1, 1e-3, (0.9, 0.95))
+    tok_dev = torch.as_tensor(tokens).to(torch.uint8).cuda()
+    net.zero_grad()
+    net.forward_backward(torch.as_tensor(tokens), torch.as_tensor(targets), precision="bf16")
+    net.clip_grad_norm_(1.0)
+    opt.step()
+    fresh = build_model("6M", state_dict={k: v.cpu() for k, v in net.state_dict().items()}, max_rows=16)
+    for p in ("f32", "f16x3", "bf16"):
+        assert torch.equal(net.logits_tokens(tok_dev, precision=p), fresh.logits_tokens(tok_dev, precision=p)), p
+    # the next bf16 gradient is taken at the new weights
+    mixed = _targets("mixed", tokens, actions)
+    losses, got, l64, g64, lac, gac = _bf16_case(net, [(tokens, mixed)])
+    _check("after step", got, g64, gac, losses[0], l64[0], lac[0])
+
+
+def _learn(precision):
+    tokens, actions = _rows(388, seed=7)
+    net = _net("tiny", max_rows=64)
+    opt = net.configure_optimizers(0.1, 1.5e-3, (0.9, 0.95))
+    out = []
+    for it in range(20):
+        sel = np.random.Generator(np.random.PCG64(it)).integers(0, len(tokens), 32)
+        net.zero_grad()
+        out.append(float(net.forward_backward(torch.as_tensor(tokens[sel]), torch.as_tensor(targets_last(actions[sel])), precision=precision)))
+        net.clip_grad_norm_(1.0)
+        opt.step()
+    return np.array(out)
+
+
+def test_tiny_learns_expert_rows_in_bf16():
+    """the schedule of test_gpu_train.py::test_tiny_learns_expert_rows"""
+    ours, f32 = _learn("bf16"), _learn("f32")
+    assert ours[-3:].mean() < 0.8 * ours[0], ours
+    assert abs(ours[-3:].mean() - f32[-3:].mean()) <= 0.05 * f32[-3:].mean(), (ours, f32)
+
+
+def test_training_cli_bfloat16(tmp_path):
+    import json
+    import subprocess
+    import sys
+    pa = pytest.importorskip("pyarrow")
+    from mapf_gpt_amd.inference import MAPFGPTInference, MAPFGPTInferenceConfig
+    from tests.helpers import ROOT
+    x, y = _rows(96, seed=9)
+    shard = tmp_path / "train.arrow"
+    table = pa.table({"input_tensors": pa.array(list(x.astype(np.int8))), "gt_actions": pa.array(y.astype(np.int8))})
+    with pa.OSFile(str(shard), "wb") as sink:
+        with pa.ipc.new_file(sink, table.schema) as w:
+            w.write_table(table)
+    out = tmp_path / "out"
+    common = ["--data", str(shard), "--val", str(shard), "--out-dir", str(out), "--eval-interval", "2", "--eval-iters", "2",
+              "--batch-size", "16", "--gradient-accumulation-steps", "2", "--warmup-iters", "2", "--lr-decay-iters", "6",
+              "--learning-rate", "1e-3", "--min-lr", "1e-4", "--dtype", "bfloat16"]
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, "-m", "mapf_gpt_amd.training", *extra, *common], cwd=ROOT, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+
+    lines = run("--init", "tiny", "--max-iters", "4")
+    evals = [l for l in lines if "val_loss" in l]
+    assert [e["iter"] for e in evals] == [0, 2, 4] and lines[-1]["iter"] == 5
+    assert all(np.isfinite(e["val_loss"]) and np.isfinite(e["train_loss"]) for e in evals)
+    ck = out / "ckpt.pt"
+    raw = torch.load(ck, map_location="cpu", weights_only=True)
+    assert raw["iter_num"] == 4 and raw["config"]["dtype"] == "bfloat16"
+    args, sd = weights.load_checkpoint(str(ck))
+    algo = MAPFGPTInference(MAPFGPTInferenceConfig(path_to_weights=str(ck), device="cuda"))
+    got = algo.net.state_dict()
+    for k in sd:
+        assert np.array_equal(got[k].cpu().numpy(), sd[k]), k
+    lines = run("--init", str(ck), "--resume", "--max-iters", "6")
+    evals = [l for l in lines if "val_loss" in l]
+    assert [e["iter"] for e in evals] == [4, 6] and lines[-1]["iter"] == 7
+    raw = torch.load(ck, map_location="cpu", weights_only=True)
+    assert raw["iter_num"] == 6 and all(float(s["step"]) == 6.0 for s in raw["optimizer"]["state"].values())
+
+
+def test_bf16_refusals():
+    net = _net("tiny")
+    tokens, _ = _rows(2)
+    with pytest.raises(_lib.MGPTError) as e:                 # split-fp16 is an inference precision only
+        net.forward_backward(torch.as_tensor(tokens), torch.zeros((2, 256), dtype=torch.int64), precision="f16x3")
+    assert e.value.code == _lib.ERR_UNSUPPORTED
+    with pytest.raises(ValueError):
+        net.forward_backward(torch.as_tensor(tokens), torch.zeros((2, 256), dtype=torch.int64), precision="fp16")
+    with pytest.raises(_lib.MGPTError) as e:                 # T != 256
+        net.forward_backward(torch.as_tensor(tokens[:, :128]), torch.zeros((2, 128), dtype=torch.int64), precision="bf16")
+    assert e.value.code == _lib.ERR_ARG
+    L = _lib.lib()
+    tok = torch.as_tensor(tokens).to(torch.uint8).cuda().contiguous()
+    tg = torch.zeros((2, 256), dtype=torch.int32, device="cuda")
+    for prec in (_lib.PREC_F16X3, 3, -1):
+        assert L.mgpt_gpt_forward_backward_prec(net._h, _lib.ptr(tok), 2, 256, _lib.ptr(tg), 1.0, None, prec, _lib.stream_ptr()) == _lib.ERR_UNSUPPORTED
+    a = weights.model_args("tiny")
+    a["bias"] = True
+    nb = GPT(GPTConfig(**a), max_rows=2)
+    nb.load_state_dict(weights.synthetic_state_dict(a, seed=0))
+    with pytest.raises(_lib.MGPTError) as e:                 # bias = True: no training workspace, so no bf16 call either
+        nb.train()
+    assert e.value.code == _lib.ERR_UNSUPPORTED
+    with pytest.raises(RuntimeError):
+        nb.forward_backward(torch.as_tensor(tokens), torch.zeros((2, 256), dtype=torch.int64), precision="bf16")
+    a = weights.model_args("tiny")
+    a["dropout"] = 0.1
+    nd = GPT(GPTConfig(**a), max_rows=2)
+    nd.load_state_dict(weights.synthetic_state_dict("tiny", seed=0))
+    with pytest.raises(NotImplementedError):
+        nd.train()
+    with pytest.raises(RuntimeError):
+        nd.forward_backward(torch.as_tensor(tokens), torch.zeros((2, 256), dtype=torch.int64), precision="bf16")

@@ -1,7 +1,13 @@
 """Device training step timings (mgpt_gpt_forward_backward, clip + AdamW) against the exact-fp32 forward(idx, targets) of the same rows, and,
 as a yardstick only, torch fp32 eager autograd of an in-repo restatement of model.py (oracle/gpt_oracle.py's formulas) on the same GPU.
 
-    python tools/bench_train.py [--shapes 6M:512,6M:2048,2M:4096,85M:512] [--torch-rows 512] [--iters 3] [--warmup 1]
+    python tools/bench_train.py [--shapes 6M:512,6M:2048,2M:4096,85M:512] [--precision f32,bf16] [--torch-rows 512] [--iters 3] [--warmup 1]
+
+--precision f32,bf16 times both training precisions in one call (one JSON line per shape and precision).  Every line carries the counted
+flops of the call (the products the model executes, 2 per multiply-add, backward = 2 x forward; the attention backward's recomputed S
+excluded) and, for bf16, the bytes its kernels move to and from memory (count_bytes below: every tensor read or written once per kernel,
+weights and L2 reuse not counted), with the achieved rate and the roofline bound against 2.5 PFLOP/s (bf16 MFMA) or 157 TFLOP/s (fp32) and
+8 TB/s.  The bf16 torch yardstick is the same restatement under torch.autocast("cuda", torch.bfloat16), train.py's regime.
 
 Targets follow the dataset's pattern (-1 except the last position, fast_data_loader.py:58).  Prints one JSON line per shape: median ms of
 each part over --iters timed calls after --warmup untimed ones, HIP events on the current stream.  The torch yardstick runs on
@@ -32,8 +38,29 @@ def timed(fn, iters, warmup):
     return float(np.median(out))
 
 
-def torch_step(name, tokens, targets):
-    """torch fp32 eager: loss = cross-entropy of ln_f(x) @ wte^T over every position (model.py:178-184), backward into .grad"""
+PEAK_FLOPS = {"f32": 157e12, "bf16": 2.5e15}
+PEAK_BYTES = 8e12
+
+
+def count_flops(args, rows, T=256, V=67):
+    """products of one forward_backward call: per token and layer 24 C^2 (the four linears) + 4 T C (QK^T and PV), the head 2 C V;
+    backward twice the forward"""
+    C, L = args["n_embd"], args["n_layer"]
+    return 3 * rows * T * (L * (24 * C * C + 4 * T * C) + 2 * C * V)
+
+
+def count_bytes(args, rows, T=256, V=67):
+    """bytes the bf16 path's kernels read and write per call (train.hip chunk_fwd_bwd_bf16), per token and layer in units of C:
+    forward 96 C (LayerNorms 2 x 8, q|k|v 16, attention 16, c_proj 12, c_fc 20 (bf16 a and gelu(a)), mlp c_proj 16);
+    backward 200 C (d h with gelu' 20, the four weight gradients 12 + 12 + 8 + 16, the input gradients 12 + 8 + 16, LayerNorms 2 x 16,
+    attention backward 64); the head and the embedding 16 V + 24 C per token"""
+    C, L = args["n_embd"], args["n_layer"]
+    return rows * T * (L * 296 * C + 16 * V + 24 * C)
+
+
+def torch_step(name, tokens, targets, autocast=False):
+    """torch fp32 eager (autocast: under torch.autocast("cuda", torch.bfloat16)): loss = cross-entropy of ln_f(x) @ wte^T over every
+    position (model.py:178-184), backward into .grad"""
     import torch.nn.functional as F
     from mapf_gpt_amd import weights
     from oracle import gpt_oracle
@@ -45,9 +72,10 @@ def torch_step(name, tokens, targets):
     idx, tg = tokens.long(), targets.long()
 
     def step():
-        x = gpt_oracle.forward_logits(view, args, idx, return_layers=True)[1][-1]
-        h = F.layer_norm(x, (x.shape[-1],), view["transformer.ln_f.weight"], None, 1e-5)
-        loss = F.cross_entropy((h @ view["lm_head.weight"].t()).reshape(-1, 67), tg.reshape(-1), ignore_index=-1)
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            x = gpt_oracle.forward_logits(view, args, idx, return_layers=True)[1][-1]
+            h = F.layer_norm(x, (x.shape[-1],), view["transformer.ln_f.weight"], None, 1e-5)
+            loss = F.cross_entropy((h @ view["lm_head.weight"].t()).reshape(-1, 67), tg.reshape(-1), ignore_index=-1)
         loss.backward()
     return step
 
@@ -55,6 +83,7 @@ def torch_step(name, tokens, targets):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="6M:512,6M:2048,2M:4096,85M:512")
+    ap.add_argument("--precision", default="f32,bf16", help="comma-separated training precisions: f32, bf16")
     ap.add_argument("--torch-rows", type=int, default=512)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
@@ -66,29 +95,39 @@ def main(argv=None):
         tokens = torch.as_tensor(rng.integers(0, 67, (rows, 256)), dtype=torch.uint8).cuda()
         targets = torch.full((rows, 256), -1, dtype=torch.int32, device="cuda")
         targets[:, -1] = torch.as_tensor(rng.integers(0, 5, rows), dtype=torch.int32).cuda()
-        net = build_model(name, seed=0, max_rows=rows).train()
-        opt = net.configure_optimizers(0.1, 6e-4, (0.9, 0.95))
-        fb = timed(lambda: net.forward_backward(tokens, targets), a.iters, a.warmup)
+        from mapf_gpt_amd import weights
+        args = weights.model_args(name)
+        for prec in a.precision.split(","):
+            net = build_model(name, seed=0, max_rows=rows).train()
+            opt = net.configure_optimizers(0.1, 6e-4, (0.9, 0.95))
+            fb = timed(lambda: net.forward_backward(tokens, targets, precision=prec), a.iters, a.warmup)
 
-        def clip_step():
-            net.clip_grad_norm_(1.0)
-            opt.step()
-        cs = timed(clip_step, a.iters, a.warmup)
-        fw = timed(lambda: net.forward(tokens, targets), a.iters, a.warmup)
-        rec = {"shape": name, "rows": rows, "forward_backward_ms": round(fb, 3), "clip_step_ms": round(cs, 3),
-               "forward_f32_ms": round(fw, 3), "fb_over_forward": round(fb / fw, 3)}
-        del net, opt
-        torch.cuda.empty_cache()
-        tr = min(rows, a.torch_rows)
-        if tr > 0:
-            rec["torch_rows"] = tr
-            try:
-                rec["torch_fwd_bwd_ms"] = round(timed(torch_step(name, tokens[:tr], targets[:tr]), a.iters, a.warmup), 3)
-                rec["ours_per_row_over_torch"] = round((fb / rows) / (rec["torch_fwd_bwd_ms"] / tr), 3)
-            except torch.cuda.OutOfMemoryError:
-                rec["torch_fwd_bwd_ms"] = "out of memory"
+            def clip_step():
+                net.clip_grad_norm_(1.0)
+                opt.step()
+            cs = timed(clip_step, a.iters, a.warmup)
+            fw = timed(lambda: net.forward(tokens, targets), a.iters, a.warmup)
+            flops = count_flops(args, rows)
+            rec = {"shape": name, "rows": rows, "precision": prec, "forward_backward_ms": round(fb, 3), "clip_step_ms": round(cs, 3),
+                   "forward_f32_ms": round(fw, 3), "fb_over_forward": round(fb / fw, 3), "gflop": round(flops / 1e9, 1),
+                   "tflops": round(flops / fb / 1e9, 1), "flop_bound_ms": round(flops / PEAK_FLOPS[prec] * 1e3, 3)}
+            if prec == "bf16":
+                nbytes = count_bytes(args, rows)
+                rec.update({"gbytes": round(nbytes / 1e9, 2), "tbytes_per_s": round(nbytes / fb / 1e9, 2),
+                            "byte_bound_ms": round(nbytes / PEAK_BYTES * 1e3, 3)})
+            del net, opt
             torch.cuda.empty_cache()
-        print(json.dumps(rec), flush=True)
+            tr = min(rows, a.torch_rows)
+            if tr > 0:
+                rec["torch_rows"] = tr
+                try:
+                    key = "torch_autocast_fwd_bwd_ms" if prec == "bf16" else "torch_fwd_bwd_ms"
+                    rec[key] = round(timed(torch_step(name, tokens[:tr], targets[:tr], autocast=prec == "bf16"), a.iters, a.warmup), 3)
+                    rec["ours_per_row_over_torch"] = round((fb / rows) / (rec[key] / tr), 3)
+                except torch.cuda.OutOfMemoryError:
+                    rec[key] = "out of memory"
+                torch.cuda.empty_cache()
+            print(json.dumps(rec), flush=True)
 
 
 if __name__ == "__main__":
