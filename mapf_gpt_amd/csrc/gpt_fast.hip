@@ -11,6 +11,7 @@
 #include "common.h"
 #include "gpt_ctx.h"
 #include "gpt_kernels_fast.h"
+#include "gpt_fast_launch.h"        // launch_gemm16, launch_gemm_pk, launch_ln_pack, launch_row_stats, launch_embed_stats
 #include "gpt_kernels_c256q.h"      // (includes gpt_kernels_c256p.h)
 #include "gpt_kernels_fused16.h"
 #include "gpt_kernels_c256b.h"      // attn256q_kernel (includes gpt_kernels_c256.h)
@@ -126,8 +127,26 @@ float pick_scale(const float *h_w, size_t n, bool f16)
     return ldexpf(1.0f, e);
 }
 
-template <int NP>
-constexpr int kA256Lds = 5 * 8 * NP * 1024 + NP * (256 * 80 + 32 * 528);    // attn256_kernel: 5-slot weight ring + K and V^T planes of a head
+// power-of-two scale of W * gain: the streams that carry a weight [n / C][C] (at w_off) with the LayerNorm gain (at g_off) folded into its
+// columns (c_attn.weight * ln_1.weight, c_fc.weight * ln_2.weight: model.py:19-20, 50, 86) have a scale of their own
+float folded_scale(const std::vector<float> &host, size_t w_off, size_t g_off, size_t n, size_t C, bool f16)
+{
+    std::vector<float> wg(n);
+    for (size_t i = 0; i < n; i++) wg[i] = host[w_off + i] * host[g_off + i % C];
+    return pick_scale(wg.data(), n, f16);
+}
+
+// (position, token) rows for layer 0 (attn256q_kernel<.., EMB>, attn160o_kernel<.., EMB>); one per checkpoint, shared by the modes
+int ensure_embed_table(mgpt_gpt *g)
+{
+    if (g->embed_table != nullptr) return MGPT_OK;
+    const size_t C = g->C;
+    MGPT_HIP(hipMalloc(&g->embed_table, (size_t)kT * kV * C * sizeof(float)));
+    hipLaunchKernelGGL(fastk::embed_table_kernel, dim3((unsigned)cdiv64((int64_t)kT * kV * (C / 4), 256)), dim3(256), 0, nullptr,
+                       g->params + g->off_wte, g->params + g->off_wpe, g->embed_table, C, kV);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
 
 template <class T, int NP>
 int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
@@ -179,10 +198,7 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
             MGPT_HIP(hipMalloc(&m->mlp256_pk[l], n16 * sizeof(uint16_t)));
             MGPT_HIP(hipMalloc(&m->mlp256q_pk[l], n16 * sizeof(uint16_t)));
             const LayerOff &lo = g->layers[l];
-            // the stream carries c_fc.weight * ln_2.weight (model.py:19-20, 86): its own power-of-two scale
-            std::vector<float> wg(4 * C * C);
-            for (size_t i = 0; i < wg.size(); i++) wg[i] = host[lo.fc_w + i] * host[lo.ln2 + i % C];
-            const float sc1 = pick_scale(wg.data(), wg.size(), f16);
+            const float sc1 = folded_scale(host, lo.fc_w, lo.ln2, 4 * C * C, C, f16);      // the stream carries c_fc.weight * ln_2.weight
             m->mlp256_inv1[l] = 1.0f / sc1;
             {   // Phi table pre-multiplied by the (power-of-two) 1 / scale: GELU = pre-activation in stream units x entry, the same bits
                 std::vector<float2> lt(fastk::kGeluLutN);
@@ -215,10 +231,7 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
             for (int l = 0; l < g->L; l++) {
                 MGPT_HIP(hipMalloc(&m->attn256_pk[l], n16 * sizeof(uint16_t)));
                 const LayerOff &lo = g->layers[l];
-                // the stream carries c_attn.weight * ln_1.weight (model.py:19-20, 50): its own power-of-two scale
-                std::vector<float> wg(3 * C * C);
-                for (size_t i = 0; i < wg.size(); i++) wg[i] = host[lo.attn_w + i] * host[lo.ln1 + i % C];
-                const float sc = pick_scale(wg.data(), wg.size(), f16);
+                const float sc = folded_scale(host, lo.attn_w, lo.ln1, 3 * C * C, C, f16);      // the stream carries c_attn.weight * ln_1.weight
                 m->attn256_inv[l] = 1.0f / sc;
                 ProfScope ps(P_PACK, nullptr);
                 hipLaunchKernelGGL((fastk::pack_attn256_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)8 * fastk::kA256StepsPerHead * 8 * 64, 256)), dim3(256), 0,
@@ -237,14 +250,9 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
                                        1.0f / m->attn256_inv[l], 1.0f / m->proj[l].inv_scale);
                     MGPT_LAUNCH_CHECK();
                 }
-                MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, kA256Lds<NP>));
-                MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kA256Lds<NP>));
-                if (g->embed_table == nullptr) {       // (position, token) rows for layer 0 (attn256q_kernel<.., EMB>); one per checkpoint, shared by the modes
-                    MGPT_HIP(hipMalloc(&g->embed_table, (size_t)kT * kV * C * sizeof(float)));
-                    hipLaunchKernelGGL(fastk::embed_table_kernel, dim3((unsigned)cdiv64((int64_t)kT * kV * (C / 4), 256)), dim3(256), 0, nullptr,
-                                       g->params + g->off_wte, g->params + g->off_wpe, g->embed_table, C, kV);
-                    MGPT_LAUNCH_CHECK();
-                }
+                MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, fastk::kA256Lds<NP>));
+                MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, fastk::kA256Lds<NP>));
+                if ((rc = ensure_embed_table(g)) != MGPT_OK) return rc;
                 MGPT_HIP(hipMalloc(&m->attn256q_spill, (size_t)m->n_cu * 8 * 14 * NP * 1024));
                 // Layer 0 of large calls from a (position, token) table of q | k | v: its input row is etab[position][token], so the row's
                 // LayerNorm and q|k|v projection are a function of the pair.  The table is the output of the EMB kernel itself (TAB = 1) on kV
@@ -253,8 +261,8 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
                 const char *tab_env = getenv("MGPT_L0_TABLE");
                 if (g->L > 1 && !(tab_env != nullptr && tab_env[0] == '0')) {
                     ProfScope ps(P_PACK, nullptr);
-                    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP, 0, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, kA256Lds<NP>));
-                    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP, 0, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, kA256Lds<NP>));
+                    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP, 0, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, fastk::kA256Lds<NP>));
+                    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP, 0, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, fastk::kA256Lds<NP>));
                     MGPT_HIP(hipMalloc(&m->l0_table, (size_t)kT * kV * fastk::kL0TabEntryBytes<NP>));
                     float *xt = nullptr;
                     unsigned char *tk = nullptr;
@@ -262,7 +270,7 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
                     MGPT_HIP(hipMalloc(&tk, (size_t)kV * kT));
                     for (int j = 0; j < kV; j++) MGPT_HIP(hipMemset(tk + (size_t)j * kT, j, kT));
                     const float scale_log2e = (1.0f / sqrtf((float)g->hs)) * 1.44269504088896340736f;    // (as forward_chunk)
-                    hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true, 1>), dim3((unsigned)std::min(kV, m->n_cu)), dim3(512), (size_t)kA256Lds<NP>, nullptr, xt,
+                    hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true, 1>), dim3((unsigned)std::min(kV, m->n_cu)), dim3(512), (size_t)fastk::kA256Lds<NP>, nullptr, xt,
                                        m->attn256q_pk[0], m->attn256_inv[0], scale_log2e, m->proj[0].inv_scale, m->attn256q_spill, kV,
                                        (unsigned long long *)nullptr, tk, g->embed_table, m->l0_table);
                     MGPT_LAUNCH_CHECK();
@@ -271,7 +279,7 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
                     MGPT_HIP(hipFree(tk));
                 }
             }
-            MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256_kernel<T, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, kA256Lds<NP>));
+            MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256_kernel<T, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, fastk::kA256Lds<NP>));
         }
     } else if (m->mlp_fused) {
         const size_t frags = C / 16 + 2 * (C / 32), nt = 4 * C / 32;
@@ -295,7 +303,7 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
                                1.0f / m->fc[l].inv_scale, 1.0f / m->proj2[l].inv_scale);
             MGPT_LAUNCH_CHECK();
         }
-        const int pkt = (int)(frags * NP * 1024 * 3) + fastk::kGeluLutN * 8;
+        const int pkt = fastk::mlp_fused_lds(NP, (int)C);
 #define MGPT_MLP16_ATTR(CT_, NW_) \
     MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp_fused16_kernel<T, NP, CT_, NW_, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, pkt))
 #define MGPT_MLP_ATTR(CT_, NW_) \
@@ -328,7 +336,7 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
                 MGPT_LAUNCH_CHECK();
             }
             // attn_block_kernel's dynamic LDS limit is a per-device function attribute: set it for this model's device
-            const int lds = (int)((size_t)NP * (kT * 80 + 32 * 528) + (size_t)(C / 16) * NP * 1024 * 4);
+            const int lds = fastk::attn_block_lds(NP, (int)C);
 #define MGPT_ATTN_LDS(CT_, EMB_, HP_)                                                                                            \
     MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn_block_kernel<T, NP, CT_, EMB_, HP_>), hipFuncAttributeMaxDynamicSharedMemorySize, lds))
             // (C = 160 runs it in small calls only: the persistent attn160o_kernel below serves the large ones)
@@ -343,9 +351,7 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
                 for (int l = 0; l < g->L; l++) {
                     MGPT_HIP(hipMalloc(&m->mlp160_pk[l], n16 * sizeof(uint16_t)));
                     const LayerOff &lo = g->layers[l];
-                    std::vector<float> wg(4 * C * C);                       // the stream carries c_fc.weight * ln_2.weight: its own power-of-two scale
-                    for (size_t i = 0; i < wg.size(); i++) wg[i] = host[lo.fc_w + i] * host[lo.ln2 + i % C];
-                    const float sc1 = pick_scale(wg.data(), wg.size(), f16);
+                    const float sc1 = folded_scale(host, lo.fc_w, lo.ln2, 4 * C * C, C, f16);      // the stream carries c_fc.weight * ln_2.weight
                     m->mlp160_inv1[l] = 1.0f / sc1;
                     ProfScope ps(P_PACK, nullptr);
                     hipLaunchKernelGGL((fastk::pack_mlp160p_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kM5Period * 20 * 64, 256)), dim3(256), 0,
@@ -359,9 +365,7 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
                 for (int l = 0; l < g->L; l++) {
                     MGPT_HIP(hipMalloc(&m->attn160o_pk[l], (size_t)fastk::kA160oPeriod * fastk::kA160oFrags * NP * 512 * sizeof(uint16_t)));
                     const LayerOff &lo = g->layers[l];
-                    std::vector<float> wg(3 * C * C);                       // c_attn.weight * ln_1.weight: its own power-of-two scale
-                    for (size_t i = 0; i < wg.size(); i++) wg[i] = host[lo.attn_w + i] * host[lo.ln1 + i % C];
-                    const float sca = pick_scale(wg.data(), wg.size(), f16);
+                    const float sca = folded_scale(host, lo.attn_w, lo.ln1, 3 * C * C, C, f16);      // c_attn.weight * ln_1.weight
                     m->attn160_inv[l] = 1.0f / sca;
                     ProfScope ps(P_PACK, nullptr);
                     hipLaunchKernelGGL((fastk::pack_attn160o_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kA160oPeriod * fastk::kA160oFrags * 64, 256)),
@@ -374,12 +378,7 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
                                              fastk::kA160oLds<NP>));
                 MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn160o_kernel<T, NP, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                              fastk::kA160oLds<NP>));
-                if (g->embed_table == nullptr) {       // (position, token) rows for layer 0 (attn160o_kernel<.., EMB>); one per checkpoint, shared by the modes
-                    MGPT_HIP(hipMalloc(&g->embed_table, (size_t)kT * kV * C * sizeof(float)));
-                    hipLaunchKernelGGL(fastk::embed_table_kernel, dim3((unsigned)cdiv64((int64_t)kT * kV * (C / 4), 256)), dim3(256), 0, nullptr,
-                                       g->params + g->off_wte, g->params + g->off_wpe, g->embed_table, C, kV);
-                    MGPT_LAUNCH_CHECK();
-                }
+                if ((rc = ensure_embed_table(g)) != MGPT_OK) return rc;
                 MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp160p_kernel<T, NP, 5>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                              fastk::kM5Lds<NP>));
                 MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp160p_kernel<T, NP, 5, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -439,28 +438,28 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
         MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_RESID, 4>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      fastk::gemm_pk_lds(NP, 4, fastk::EPI_RESID)));
         // the 128-row forms of the other epilogues (small calls of the C = 768 chain)
-#define MGPT_PK4(EPI_, LNF_, EXTRA_)                                                                                                                  \
+#define MGPT_PK4(EPI_, LNF_, LUT_)                                                                                                                    \
     MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_, 4, 0, LNF_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 fastk::gemm_pk_lds(NP, 4, fastk::EPI_) + (EXTRA_)))
-        MGPT_PK4(EPI_QK, false, 0); MGPT_PK4(EPI_VT, false, 0); MGPT_PK4(EPI_GELU, false, fastk::kGeluLutN * 8);
-        MGPT_PK4(EPI_QK, true, 3072); MGPT_PK4(EPI_VT, true, 3072); MGPT_PK4(EPI_GELU, true, fastk::kGeluLutN * 8 + 3072);
+                                 fastk::gemm_pk_lds(NP, 4, fastk::EPI_) + fastk::gemm_pk_lds_extra(LNF_, LUT_)))
+        MGPT_PK4(EPI_QK, false, false); MGPT_PK4(EPI_VT, false, false); MGPT_PK4(EPI_GELU, false, true);
+        MGPT_PK4(EPI_QK, true, false); MGPT_PK4(EPI_VT, true, false); MGPT_PK4(EPI_GELU, true, true);
 #undef MGPT_PK4
         if constexpr (NP == 1) {
-#define MGPT_PK16(EPI_, NWV_, LNF_, EXTRA_)                                                                                                            \
+#define MGPT_PK16(EPI_, NWV_, LNF_, LUT_)                                                                                                              \
     MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk16_kernel<T, fastk::EPI_, NWV_, LNF_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 fastk::gemm_pk_lds(NP, NWV_, fastk::EPI_) + (EXTRA_)))
-            MGPT_PK16(EPI_QK, 8, false, 0); MGPT_PK16(EPI_VT, 8, false, 0); MGPT_PK16(EPI_RESID, 8, false, 0); MGPT_PK16(EPI_GELU, 8, false, fastk::kGeluLutN * 8);
-            MGPT_PK16(EPI_QK, 4, false, 0); MGPT_PK16(EPI_VT, 4, false, 0); MGPT_PK16(EPI_RESID, 4, false, 0); MGPT_PK16(EPI_GELU, 4, false, fastk::kGeluLutN * 8);
-            MGPT_PK16(EPI_QK, 8, true, 3072); MGPT_PK16(EPI_VT, 8, true, 3072); MGPT_PK16(EPI_GELU, 8, true, fastk::kGeluLutN * 8 + 3072);
-            MGPT_PK16(EPI_QK, 4, true, 3072); MGPT_PK16(EPI_VT, 4, true, 3072); MGPT_PK16(EPI_GELU, 4, true, fastk::kGeluLutN * 8 + 3072);
+                                 fastk::gemm_pk_lds(NP, NWV_, fastk::EPI_) + fastk::gemm_pk_lds_extra(LNF_, LUT_)))
+            MGPT_PK16(EPI_QK, 8, false, false); MGPT_PK16(EPI_VT, 8, false, false); MGPT_PK16(EPI_RESID, 8, false, false); MGPT_PK16(EPI_GELU, 8, false, true);
+            MGPT_PK16(EPI_QK, 4, false, false); MGPT_PK16(EPI_VT, 4, false, false); MGPT_PK16(EPI_RESID, 4, false, false); MGPT_PK16(EPI_GELU, 4, false, true);
+            MGPT_PK16(EPI_QK, 8, true, false); MGPT_PK16(EPI_VT, 8, true, false); MGPT_PK16(EPI_GELU, 8, true, true);
+            MGPT_PK16(EPI_QK, 4, true, false); MGPT_PK16(EPI_VT, 4, true, false); MGPT_PK16(EPI_GELU, 4, true, true);
 #undef MGPT_PK16
         }
         MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_GELU, 8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     lds + fastk::kGeluLutN * 8));
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_QK, 8, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds + 3072));
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_VT, 8, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds + 3072));
+                                     lds + fastk::gemm_pk_lds_extra(false, true)));
+        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_QK, 8, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds + fastk::gemm_pk_lds_extra(true, false)));
+        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_VT, 8, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds + fastk::gemm_pk_lds_extra(true, false)));
         MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_GELU, 8, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     lds + fastk::kGeluLutN * 8 + 3072));
+                                     lds + fastk::gemm_pk_lds_extra(true, true)));
         if (!(C == 256 && m->mlp_fused && g->hs == 32 && g->nh == 8))      // LayerNorm planes of the GEMM chain (the 6M kernels normalise in registers)
             MGPT_HIP(hipMalloc(&m->apk, (size_t)g->max_rows * kT * C * NP * sizeof(uint16_t)));
         // one-plane mode of the full chain (no fused kernels): LayerNorm folded into the GEMMs (GemmArgs) -- ln_pack_kernel, which
@@ -563,446 +562,416 @@ void free_mode(mgpt_gpt *g, ModeState *m)
     *m = ModeState();
 }
 
-template <class T, int NP, int PRO, int EPI>
-int launch_gemm16(fastk::GemmArgs a, int C, hipStream_t s)
-{
-    MGPT_REQUIRE(a.M % 128 == 0 && a.K % 32 == 0, MGPT_ERR_UNSUPPORTED, "gemm16 shape M=%d K=%d", a.M, a.K);
-    const int mt = a.M / 128;
-    if (C == 160 && a.N % 160 == 0) {
-        a.n_tiles_n = a.N / 160;
-        hipLaunchKernelGGL((fastk::gemm16_kernel<T, NP, 160, 4, 1, PRO, EPI>), dim3(mt * a.n_tiles_n), dim3(256), 0, s, a);
-    } else if (C == 64 && a.N % 64 == 0) {
-        a.n_tiles_n = a.N / 64;
-        hipLaunchKernelGGL((fastk::gemm16_kernel<T, NP, 64, 4, 1, PRO, EPI>), dim3(mt * a.n_tiles_n), dim3(256), 0, s, a);
-    } else if (a.N % 128 == 0) {
-        a.n_tiles_n = a.N / 128;
-        if (EPI == fastk::EPI_RESID) a.stats_out = nullptr;          // rows span two waves: stats come from row_stats_kernel
-        hipLaunchKernelGGL((fastk::gemm16_kernel<T, NP, 128, 2, 2, PRO, EPI>), dim3(mt * a.n_tiles_n), dim3(256), 0, s, a);
-    } else {
-        set_error("gemm16: N=%d unsupported for C=%d", a.N, C);
-        return MGPT_ERR_UNSUPPORTED;
-    }
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
-}
+// ---------------------------------------------------------------------------------------------
+// The launch plan of a chunk: everything that decides which kernels it runs except "is this layer 0 / the last layer".  make_plan is the
+// one place where the shape, the precision mode and the row counts are looked at; where two conditions can hold at once, the order of
+// the ?: chains below is the precedence.  (DESIGN.md section 3.2 has the resulting table.)
+// ---------------------------------------------------------------------------------------------
+enum Family {               // fixed when the mode is built
+    FAM_REGISTER,           // C = 64 / 160, heads of 32: a layer is one attention-block kernel + one MLP-block kernel, q, k, v, y and the hidden stay on chip
+    FAM_6M,                 // C = 256, 8 heads of 32: the same, with kernels of its own
+    FAM_PACKED,             // any other C % 256 == 0 (85M): chain of packed-fragment GEMMs (gemm_pk) around attn16_kernel
+    FAM_GENERIC             // everything else: gemm16 chain on row-major planes (C = 64 / 160 with other heads: its MLP block is still the fused kernel)
+};
+enum EmbedKind {            // where x = wte[token] + wpe[position] comes from
+    EMBED_TABLE256,         // layer 0's attn256q_kernel reads the (position, token) table: x rows (EMB), or q | k | v themselves (TAB = 2, Plan::l0_qkv_table)
+    EMBED_TABLE160,         // layer 0's attn160o_kernel<EMB> reads the table
+    EMBED_ATTN_BLOCK,       // layer 0's attn_block_kernel<EMBED> gathers wte and wpe itself
+    EMBED_TILED,            // embed_tiled_kernel (chunk-major x)
+    EMBED_STATS             // embed_stats_kernel (row-major x + LayerNorm statistics)
+};
+enum AttnKind {             // the attention block of a full layer
+    ATTN_160O,              // attn160o_kernel: persistent, whole block
+    ATTN_BLOCK,             // attn_block_kernel: one workgroup per row, or per (row, head) in small calls (Plan::head_par)
+    ATTN_256Q,              // attn256q_kernel: persistent, whole block
+    ATTN_256_HEADS,         // attn256_kernel per (row, head) -> y planes -> packed out-projection
+    ATTN_PACKED,            // (ln_pack) q|k and v^T gemm_pk, attn16_kernel, out-projection gemm_pk
+    ATTN_GENERIC            // the same chain on gemm16
+};
+enum LastKind {             // the last layer, of which only token 255 of every row is needed (model.py:186)
+    LAST_NONE,              // runs as a full layer: sequence forward (every position is needed), or FAM_GENERIC
+    LAST_TAIL,              // small call: attention block, MLP block, ln_f and head in one attn_last1_kernel<.., 1, TAIL> launch; ends the chunk
+    LAST_1,                 // attn_last1_kernel -> x_last, then the MLP block on the compact rows
+    LAST_PACKED             // the packed chain with a compact tail: attn16 for query 255, gather_last, out-projection and MLP on rows_pad tokens
+};
+enum MlpKind { MLP_256P2, MLP_256P, MLP_256Q, MLP_160P, MLP_FUSED, MLP_FUSED16, MLP_PACKED, MLP_GENERIC };
 
-// compute units of the current device (grid of the persistent packed GEMM); asked once
-int gemm_pk_cus()
-{
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        n = v;
-    }
-    return n;
-}
+struct Plan {
+    int rows, rows_pad;     // of the chunk; rounded up to 256 (compact last-layer buffers)
+    int64_t M;              // tokens
+    // a small call (one environment): its kernels spread few rows over the CUs.  Decided by the CALL's row count, not the chunk's: the remainder
+    bool small;             // chunk of a large call stays on the large-call kernels
+    bool big_call;          // the one-plane packed GEMMs run on the 16 x 16 x 32 MFMA (launch_gemm_pk)
+    Family family;
+    EmbedKind embed;
+    bool l0_qkv_table;      // EMBED_TABLE256: layer 0's q | k | v from ModeState::l0_table
+    AttnKind attn;
+    bool head_par;          // ATTN_BLOCK per (row, head): the heads' c_proj contributions go to head_parts and the MLP kernel folds them in
+    int64_t part_stride;    // of head_parts
+    LastKind last;
+    bool last1_row_per_wg;  // LAST_1 with one row per workgroup instead of kLast1R (few rows on the 6M shape: so that they spread over the CUs)
+    MlpKind mlp;
+    int mlp160_tokens;      // MLP_160P: tokens per block (128: two waves per SIMD; 64, 32: so few tokens that larger blocks would leave CUs idle)
+    int mlp_nw, mlp_nw_last;   // MLP_FUSED / MLP_FUSED16: waves per workgroup (32 tokens each) of a full layer and of the compact last layer
+    bool half_qkv, half_proj, half_proj2;   // 128-row tiles in the packed GEMMs of small calls (q|k and v^T; out-projection and c_proj of full layers)
+};
 
-template <class T, int NP, int EPI>
-int launch_gemm_pk(fastk::GemmArgs a, hipStream_t s, bool half_tiles = false, bool big_call = true)
+Plan make_plan(const mgpt_gpt *g, const ModeState *m, int rows, int call_rows, bool seq)
 {
-    constexpr int NST = fastk::gemm_pk_nst(NP, 8, EPI), KPS = fastk::gemm_pk_kps(NP);
-    MGPT_REQUIRE(a.M % 256 == 0 && a.N % 256 == 0 && a.K % 32 == 0 && a.K >= 16 * KPS * NST, MGPT_ERR_UNSUPPORTED,
-                 "gemm_pk shape M=%d N=%d K=%d", a.M, a.N, a.K);
-    a.n_tiles_n = a.N / 256;
-    if (EPI == fastk::EPI_RESID) a.stats_out = nullptr;               // rows span two waves: stats come from row_stats_kernel
-    const bool lut = EPI == fastk::EPI_GELU && a.gelu_lut != nullptr;
-    const int n_cu = gemm_pk_cus();
-    const bool lnf = EPI != fastk::EPI_RESID && a.ln_stats != nullptr;
-    const bool persist = fastk::gemm_pk_persistent(NP, EPI, lnf);    // one workgroup per CU walking the tiles (gpt_kernels_fast.h: gemm_pk_kernel)
-    const unsigned grid8 = (unsigned)(persist ? std::min((a.M / 256) * a.n_tiles_n, n_cu) : (a.M / 256) * a.n_tiles_n);
-    const unsigned grid4 = (unsigned)(persist ? std::min((a.M / 128) * a.n_tiles_n, 2 * n_cu) : (a.M / 128) * a.n_tiles_n);
-    // half_tiles (small launches: one environment's rows are 32 tiles of 256 rows per column tile, which leaves most CUs idle): 128-row tiles, 4 waves,
-    // two workgroups per CU -- same arithmetic per token (a wave's 64 x 128 sub-tile and its k order do not change)
-    const size_t lut_b = lut ? (size_t)fastk::kGeluLutN * 8 : 0;
-    if constexpr (NP == 1) {
-        // one-plane mode: the same GEMM on v_mfma_f32_16x16x32 (gpt_kernels_fast.h: gemm_pk16_kernel), one workgroup per tile
-        // -- in LARGE calls only: a 32-row forward is not at the power limit, and there the 12 % more cycles per flop of the small shape show (2.49 -> 2.71 ms);
-        // the choice is a property of the call (as for the other small-launch kernels), so every chunk of a call runs the same arithmetic
-        if (big_call && a.K % 64 == 0 && a.K >= 128 && (EPI != fastk::EPI_GELU || lut)) {
-            const unsigned g8 = (unsigned)((a.M / 256) * a.n_tiles_n), g4 = (unsigned)((a.M / 128) * a.n_tiles_n);
-            if (lnf) {
-                if (half_tiles) hipLaunchKernelGGL((fastk::gemm_pk16_kernel<T, EPI, 4, true>), dim3(g4), dim3(256), (size_t)fastk::gemm_pk_lds(NP, 4, EPI) + lut_b + 3072, s, a);
-                else hipLaunchKernelGGL((fastk::gemm_pk16_kernel<T, EPI, 8, true>), dim3(g8), dim3(512), (size_t)fastk::gemm_pk_lds(NP) + lut_b + 3072, s, a);
-            } else {
-                if (half_tiles) hipLaunchKernelGGL((fastk::gemm_pk16_kernel<T, EPI, 4, false>), dim3(g4), dim3(256), (size_t)fastk::gemm_pk_lds(NP, 4, EPI) + lut_b, s, a);
-                else hipLaunchKernelGGL((fastk::gemm_pk16_kernel<T, EPI, 8, false>), dim3(g8), dim3(512), (size_t)fastk::gemm_pk_lds(NP) + lut_b, s, a);
-            }
-            MGPT_LAUNCH_CHECK();
-            return MGPT_OK;
-        }
-    }
-    if (lnf) {                                                       // folded LayerNorm (GemmArgs): the Phi table slot is always reserved
-        MGPT_REQUIRE(EPI != fastk::EPI_GELU || lut, MGPT_ERR_STATE, "%s", "folded LayerNorm: the GELU epilogue needs the Phi table");
-        if (half_tiles)
-            hipLaunchKernelGGL((fastk::gemm_pk_kernel<T, NP, EPI, 4, 0, true>), dim3(grid4), dim3(256),
-                               (size_t)fastk::gemm_pk_lds(NP, 4, EPI) + lut_b + 3072, s, a, (unsigned long long *)nullptr);
-        else
-            hipLaunchKernelGGL((fastk::gemm_pk_kernel<T, NP, EPI, 8, 0, true>), dim3(grid8), dim3(512),
-                               (size_t)fastk::gemm_pk_lds(NP) + lut_b + 3072, s, a, (unsigned long long *)nullptr);
-    } else if (half_tiles) {
-        hipLaunchKernelGGL((fastk::gemm_pk_kernel<T, NP, EPI, 4>), dim3(grid4), dim3(256),
-                           (size_t)fastk::gemm_pk_lds(NP, 4, EPI) + lut_b, s, a, (unsigned long long *)nullptr);
-    } else {
-        hipLaunchKernelGGL((fastk::gemm_pk_kernel<T, NP, EPI, 8>), dim3(grid8), dim3(512),
-                           (size_t)fastk::gemm_pk_lds(NP) + lut_b, s, a, (unsigned long long *)nullptr);
-    }
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
-}
-
-template <class T, int NP>
-int launch_ln_pack(const float *x, const float *gain, uint16_t *out, int64_t M, int C, int tiled, hipStream_t s)
-{
-    ProfScope ps(P_LAYERNORM, s);
-    const dim3 grid((unsigned)(M / 32));
-    if (C == 256) hipLaunchKernelGGL((fastk::ln_pack_kernel<T, NP, 4>), grid, dim3(256), 0, s, x, gain, out, C, tiled);
-    else if (C == 512) hipLaunchKernelGGL((fastk::ln_pack_kernel<T, NP, 8>), grid, dim3(256), 0, s, x, gain, out, C, tiled);
-    else if (C == 768) hipLaunchKernelGGL((fastk::ln_pack_kernel<T, NP, 12>), grid, dim3(256), 0, s, x, gain, out, C, tiled);
-    else if (C == 1024) hipLaunchKernelGGL((fastk::ln_pack_kernel<T, NP, 16>), grid, dim3(256), 0, s, x, gain, out, C, tiled);
-    else { set_error("ln_pack: C=%d unsupported", C); return MGPT_ERR_UNSUPPORTED; }
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
-}
-
-bool fused_stats(int C) { return C == 160 || C == 64; }
-
-int launch_row_stats(const float *x, float2 *stats, int64_t n_tok, int C, hipStream_t s)
-{
-    ProfScope ps(P_LAYERNORM, s);
-    const dim3 grid((unsigned)cdiv64(n_tok, 4));
-    if (C <= 256) hipLaunchKernelGGL((fastk::row_stats_kernel<1>), grid, dim3(256), 0, s, x, stats, n_tok, C);
-    else if (C <= 512) hipLaunchKernelGGL((fastk::row_stats_kernel<2>), grid, dim3(256), 0, s, x, stats, n_tok, C);
-    else if (C <= 768) hipLaunchKernelGGL((fastk::row_stats_kernel<3>), grid, dim3(256), 0, s, x, stats, n_tok, C);
-    else hipLaunchKernelGGL((fastk::row_stats_kernel<4>), grid, dim3(256), 0, s, x, stats, n_tok, C);
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
-}
-
-template <class T, int NP>
-int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, float *d_logits, hipStream_t s, int call_rows,
-                  const SeqOut *seq = nullptr)
-{
-    const int C = g->C;
-    const int64_t M = (int64_t)rows * kT;
-    const float *P = g->params;
-    int rc;
-    // register-resident path (C = 64, 160; head size 32): a layer is attn_block_kernel + mlp_fused_kernel
+    Plan p = {};
+    const int C = g->C, n_cu = m->n_cu;
+    p.rows = rows; p.rows_pad = ((rows + 255) / 256) * 256; p.M = (int64_t)rows * kT;
+    p.small = call_rows <= kSmallRows && rows <= kSmallRows;
+    p.big_call = call_rows > kSmallRows;
     const bool attn_block = m->qkv_fused && g->hs == 32 && m->mlp_fused;
-    // small launch: the heads of a row run on different CUs (attn_block_kernel<HP>), their partial sums are folded by the next kernel
-    // (decided by the CALL's row count, not the chunk's: the remainder chunk of a large call stays on the large-launch kernels)
-    const bool head_par = attn_block && call_rows <= kSmallRows && rows <= kSmallRows;
-    const int small_cap = std::min(g->max_rows, kSmallRows);                 // rows a small launch of this context can have
-    const int64_t part_stride = (int64_t)small_cap * kT * C;
-    if (head_par && m->head_parts == nullptr) {
-        // first small launch of this context (105 MB for the 2M shape were allocated per precision mode and per adapter whether
-        // or not the context ever served one environment).  New device memory: captured step graphs of this context are stale
-        MGPT_HIP(hipMalloc(&m->head_parts, (size_t)g->nh * (size_t)part_stride * sizeof(float)));
+    p.family = attn_block ? FAM_REGISTER : m->attn256 ? FAM_6M : m->pk_gemm ? FAM_PACKED : FAM_GENERIC;
+    p.head_par = attn_block && p.small;
+    p.part_stride = (int64_t)std::min(g->max_rows, kSmallRows) * kT * C;        // (rows a small launch of this context can have)
+    // the first attention block forms x = wte[token] + wpe[position] itself (no embedding kernel, no first read of x) ... unless the persistent block
+    // kernel of the 2M shape serves the layer (profiles/r06_ab.txt visit B): embed_tiled_kernel + attn160o_kernel (0.6 + 4.5 ms per 16 384 rows) beat attn_block_kernel<EMBED> (5.8 ms)
+    const bool persistent160 = attn_block && C == 160 && !p.head_par && m->attn160o_spill != nullptr && m->x_tiled;
+    const bool embed_fused = attn_block && g->L > 1 && !p.head_par && !persistent160;
+    // ... and so do the persistent block kernels in a large call, from the (position, token) table (round 6)
+    const bool embed256 = m->attn256 && g->L > 1 && g->embed_table != nullptr && m->x_tiled && !p.small;
+    const bool embed160 = persistent160 && g->L > 1 && g->embed_table != nullptr;
+    p.embed = embed256 ? EMBED_TABLE256 : embed160 ? EMBED_TABLE160 : embed_fused ? EMBED_ATTN_BLOCK : m->x_tiled ? EMBED_TILED : EMBED_STATS;
+    p.l0_qkv_table = m->l0_table != nullptr;
+    // 6M shape: attn256q_kernel does the out-projection and the residual add itself ... unless the call is small: then a row's eight heads
+    // run on eight CUs at once (attn256_kernel, one workgroup per (row, head), y planes) and the packed GEMM projects them (round 5)
+    const bool small256 = m->attn256 && p.small;
+    p.attn = persistent160 ? ATTN_160O : attn_block ? ATTN_BLOCK : m->attn256 ? (small256 ? ATTN_256_HEADS : ATTN_256Q) : m->pk_gemm ? ATTN_PACKED : ATTN_GENERIC;
+    // last layer: only token 255 is needed downstream -> compact buffer, MLP and head on `rows` tokens.  Every model with last1_wt (FAM_REGISTER,
+    // FAM_6M) takes LAST_TAIL in a small call and LAST_1 (without K and V: a launch that fills the chip) in a large one
+    const bool short_last = (attn_block || m->pk_gemm) && !seq;
+    const bool small_call = p.head_par || small256;
+    p.last = !short_last ? LAST_NONE : (small_call && m->last1_wt != nullptr) ? LAST_TAIL
+             : (m->last1_wt != nullptr && m->x_tiled && !p.head_par) ? LAST_1 : LAST_PACKED;
+    p.last1_row_per_wg = C == 256 && rows <= 2 * n_cu;
+    // MLP block.  Small calls are not power-limited and keep the 32 x 32 x 16 kernels; large calls run the same block on v_mfma_f32_16x16x32
+    // (mlp256q, mlp_fused16: 13-15 % more f16 flops per second at the power limit); the choice is a property of the call
+    auto nw = [&](int64_t mlp_M) { return mlp_M >= (int64_t)256 * n_cu ? 8 : (mlp_M >= (int64_t)128 * n_cu ? 4 : 2); };
+    p.mlp_nw = nw(p.M); p.mlp_nw_last = nw(p.rows_pad);
+    p.mlp160_tokens = p.M <= (int64_t)32 * n_cu ? 32 : (p.M <= (int64_t)64 * n_cu ? 64 : 128);
+    if (m->mlp_fused && C == 256) p.mlp = !small256 ? MLP_256Q : (2 * (int)(p.M / 128) <= n_cu ? MLP_256P2 : MLP_256P);
+    else if (m->mlp_fused) p.mlp = (p.head_par && C == 160) ? MLP_160P : (p.head_par && C != 160) ? MLP_FUSED : MLP_FUSED16;
+    else p.mlp = m->pk_gemm ? MLP_PACKED : MLP_GENERIC;
+    // the packed-GEMM chain (C = 768) in a small call: its residual GEMMs (N = 768: 3 column tiles) are 96 tiles of 256 rows for 32 rows -- 128-row
+    // tiles put them on twice the CUs (same arithmetic per token: a wave's 64 x 128 sub-tile and its k order do not change).  One-plane mode: 32-row forward
+    // 2.77 -> 2.49 ms (c_proj 70 -> 56 us, out-projection 30 -> 25, q|k + v^T 51 -> 47); in the split mode the 4-wave form has a 3-stage ring and loses (5.8 -> 6.4)
+    const bool small_pk = m->np == 1 && m->pk_gemm && !m->attn256 && p.small;
+    p.half_qkv = small_pk; p.half_proj = small256 || small_pk; p.half_proj2 = small_pk;
+    return p;
+}
+
+// One chunk of a call: what its launches share, and the launches, each named for what it launches (forward_chunk is the sequence).
+template <class T, int NP>
+struct Chunk {
+    mgpt_gpt *g;
+    ModeState *m;
+    const uint8_t *tokens;
+    float *logits;              // (a sequence forward writes through seq instead)
+    hipStream_t s;
+    const SeqOut *seq;
+    const Plan p;
+    const float *P = g->params;
+    const int C = g->C, rows = p.rows, rows_pad = p.rows_pad;
+    const int64_t M = p.M;
+    const float scale_log2e = (1.0f / sqrtf((float)g->hs)) * 1.44269504088896340736f;
+
+    // the GEMM chains hand one argument block per layer from launch to launch: each sets the fields it needs and clears what only it may see
+    fastk::GemmArgs layer_args(int l) const
+    {
+        fastk::GemmArgs a = {};
+        a.M = (int)M; a.C = C; a.n_head = g->nh; a.hs = g->hs; a.plane = M * C;
+        a.x = g->x; a.stats = m->stats; a.gain = P + g->layers[l].ln1; a.K = C;
+        a.w_hi = m->attn[l].hi; a.w_lo = m->attn[l].lo; a.out_scale = m->attn[l].inv_scale;
+        a.N = 2 * C; a.o_hi = m->qk[0]; a.o_lo = m->qk[1];
+        return a;
+    }
+
+    // head_parts is allocated by the first small launch of a context (105 MB for the 2M shape were allocated per precision mode and per
+    // adapter whether or not the context ever served one environment).  New device memory: captured step graphs of this context are stale
+    int ensure_head_parts()
+    {
+        if (!p.head_par || m->head_parts != nullptr) return MGPT_OK;
+        MGPT_HIP(hipMalloc(&m->head_parts, (size_t)g->nh * (size_t)p.part_stride * sizeof(float)));
         g->generation++;
+        return MGPT_OK;
     }
-    // the first attention block forms x = wte[token] + wpe[position] itself (no embedding kernel, no first read of x)
-    // ... unless the persistent block kernel of the 2M shape serves the layer (round 6, profiles/r06_ab.txt visit B): embed_tiled_kernel (0.6 ms per 16 384 rows)
-    // + attn160o_kernel (4.5 ms) beat attn_block_kernel<EMBED> (5.8 ms), the round-1 kernel the first layer had stayed on because it gathers the embedding
-    const bool persistent160 = attn_block && C == 160 && !head_par && m->attn160o_spill != nullptr && m->x_tiled;
-    const bool embed_fused = attn_block && g->L > 1 && !head_par && !persistent160;
-    // ... and so does the 6M shape's persistent block kernel in a large call (attn256q_kernel<.., EMB>: from the (position, token) table, round 6)
-    const bool embed256 = m->attn256 && g->L > 1 && g->embed_table != nullptr && m->x_tiled && !(call_rows <= kSmallRows && rows <= kSmallRows);
-    const bool embed160 = persistent160 && g->L > 1 && g->embed_table != nullptr;      // ... and the 2M shape's (attn160o_kernel<.., EMB>)
-    if (embed256 || embed160) {
-    } else if (m->x_tiled && !embed_fused) {
-        ProfScope ps(P_EMBED, s);
-        hipLaunchKernelGGL(fastk::embed_tiled_kernel, dim3((unsigned)(M / 32)), dim3(256), 0, s, d_tokens, P + g->off_wte, P + g->off_wpe, g->x, C);
-        MGPT_LAUNCH_CHECK();
-    } else if (!embed_fused) {
-        ProfScope ps(P_EMBED, s);
-        const dim3 grid((unsigned)cdiv64(M, 4));
-        if (C <= 256) hipLaunchKernelGGL((fastk::embed_stats_kernel<1>), grid, dim3(256), 0, s, d_tokens, P + g->off_wte, P + g->off_wpe, g->x, m->stats, M, C);
-        else if (C <= 512) hipLaunchKernelGGL((fastk::embed_stats_kernel<2>), grid, dim3(256), 0, s, d_tokens, P + g->off_wte, P + g->off_wpe, g->x, m->stats, M, C);
-        else if (C <= 768) hipLaunchKernelGGL((fastk::embed_stats_kernel<3>), grid, dim3(256), 0, s, d_tokens, P + g->off_wte, P + g->off_wpe, g->x, m->stats, M, C);
-        else hipLaunchKernelGGL((fastk::embed_stats_kernel<4>), grid, dim3(256), 0, s, d_tokens, P + g->off_wte, P + g->off_wpe, g->x, m->stats, M, C);
-        MGPT_LAUNCH_CHECK();
+
+    int embedding()
+    {
+        if (p.embed == EMBED_TILED) {
+            ProfScope ps(P_EMBED, s);
+            hipLaunchKernelGGL(fastk::embed_tiled_kernel, dim3((unsigned)(M / 32)), dim3(256), 0, s, tokens, P + g->off_wte, P + g->off_wpe, g->x, C);
+            MGPT_LAUNCH_CHECK();
+        } else if (p.embed == EMBED_STATS) {
+            const int rc = launch_embed_stats(tokens, P + g->off_wte, P + g->off_wpe, g->x, m->stats, M, C, s);
+            if (rc != MGPT_OK) return rc;
+        }                                                          // (the other kinds: layer 0's attention block forms x)
+        // folded LayerNorm: (mean, rstd) of the rows the next GEMM normalises live in m->stats, their raw operand planes in m->apk
+        if (m->ln_fold)                                            // the embedding rows: the one ln_pack_kernel launch of the forward (raw mode)
+            return launch_ln_pack<T, NP>(g->x, P + g->layers[0].ln1, m->apk, M, C, m->x_tiled ? 1 : 0, s, m->stats, m->ln_mean);
+        return MGPT_OK;
     }
-    // folded LayerNorm: (mean, rstd) of the rows the next GEMM normalises live in m->stats, their raw operand planes in m->apk
+
     // (compact = the last layer's rows: token 255 of every row; their means are not needed again)
-    auto ln_finalize = [&](int64_t Mrows, bool compact) -> int {
+    int ln_finalize(int64_t Mrows, bool compact)
+    {
         ProfScope ps(P_LAYERNORM, s);
         hipLaunchKernelGGL(fastk::ln_finalize_kernel, dim3((unsigned)cdiv64(Mrows, 256)), dim3(256), 0, s, m->ln_parts, C / 128, Mrows, C, m->stats,
                            m->ln_mean, compact ? kT : 1, compact ? kT - 1 : 0, compact ? 0 : 1);
         MGPT_LAUNCH_CHECK();
         return MGPT_OK;
-    };
-    if (m->ln_fold) {                                          // the embedding rows: the one ln_pack_kernel launch of the forward (raw mode)
-        ProfScope ps(P_LAYERNORM, s);
-        const dim3 grid((unsigned)(M / 32));
-        const float *g0 = P + g->layers[0].ln1;
-        if (C == 256) hipLaunchKernelGGL((fastk::ln_pack_kernel<T, NP, 4>), grid, dim3(256), 0, s, g->x, g0, m->apk, C, m->x_tiled ? 1 : 0, m->stats, m->ln_mean);
-        else if (C == 512) hipLaunchKernelGGL((fastk::ln_pack_kernel<T, NP, 8>), grid, dim3(256), 0, s, g->x, g0, m->apk, C, m->x_tiled ? 1 : 0, m->stats, m->ln_mean);
-        else if (C == 768) hipLaunchKernelGGL((fastk::ln_pack_kernel<T, NP, 12>), grid, dim3(256), 0, s, g->x, g0, m->apk, C, m->x_tiled ? 1 : 0, m->stats, m->ln_mean);
-        else hipLaunchKernelGGL((fastk::ln_pack_kernel<T, NP, 16>), grid, dim3(256), 0, s, g->x, g0, m->apk, C, m->x_tiled ? 1 : 0, m->stats, m->ln_mean);
-        MGPT_LAUNCH_CHECK();
     }
-    const float scale_log2e = (1.0f / sqrtf((float)g->hs)) * 1.44269504088896340736f;
-    const size_t attn_lds = (size_t)NP * (kT * (g->hs + 8) * 2 + g->hs * (kT + 8) * 2);
-    for (int l = 0; l < g->L; l++) {
+
+    // ---- last layer: the attention block of token 255 alone, without K and V (attn_last1_kernel), fp32 throughout ----
+    // LAST_1: -> x_last.  LAST_TAIL: one workgroup per row, and the MLP block, ln_f and the head in the same launch; logits come straight out of it
+    int attn_last(int l)
+    {
         const LayerOff &lo = g->layers[l];
-        fastk::GemmArgs a = {};
-        a.M = (int)M; a.C = C; a.n_head = g->nh; a.hs = g->hs; a.plane = M * C;
-        a.x = g->x; a.stats = m->stats; a.gain = P + lo.ln1; a.K = C;
-        a.w_hi = m->attn[l].hi; a.w_lo = m->attn[l].lo; a.out_scale = m->attn[l].inv_scale;
-        a.N = 2 * C; a.o_hi = m->qk[0]; a.o_lo = m->qk[1];
-        // last layer: only token 255 is needed downstream (model.py:186) -> compact buffer, MLP and head on `rows` tokens
-        // (a sequence forward, seq != NULL, needs every position: its last layer runs the kernels of the layers before)
-        const bool full_last = seq != nullptr;
-        const bool last_short = (attn_block || m->pk_gemm) && l == g->L - 1 && !full_last;
-        const int rows_pad = ((rows + 255) / 256) * 256;
-        // 6M shape, every layer but the last: attn256q_kernel does the out-projection and the residual add itself
-        // ... unless the CALL is small (one environment, rows <= kSmallRows): then a row's eight heads run on eight CUs at once
-        // (attn256_kernel, one workgroup per (row, head), y planes) and the packed GEMM projects them (round 5)
-        const bool small256 = m->attn256 && !last_short && call_rows <= kSmallRows && rows <= kSmallRows;
-        const bool proj_fused = m->attn256 && !last_short && !small256;
-        // the packed-GEMM chain (C = 768) in a small call: its residual GEMMs (N = 768: 3 column tiles) are 96 tiles of 256 rows for 32 rows -- 128-row
-        // tiles put them on twice the CUs (same arithmetic per token: a wave's 64 x 128 sub-tile and its k order do not change).  One-plane mode: 32-row
-        // forward 2.77 -> 2.49 ms (c_proj 70 -> 56 us, out-projection 30 -> 25, q|k + v^T 51 -> 47); in the split mode the 4-wave form has a 3-stage ring and
-        // loses (5.8 -> 6.4)
-        const bool small_pk = NP == 1 && m->pk_gemm && !m->attn256 && call_rows <= kSmallRows && rows <= kSmallRows;
-        const bool big_call = call_rows > kSmallRows;                      // the one-plane packed GEMMs run on the 16 x 16 x 32 MFMA (launch_gemm_pk)
-        // last layer of a launch that fills the chip: the attention block of token 255 alone, without K and V (attn_last1_kernel)
-        const bool last1 = last_short && m->last1_wt != nullptr && m->x_tiled && !head_par;
-        // small launch (one environment): the last layer's attention block, its MLP block, ln_f and the head are ONE launch, one
-        // workgroup per row (attn_last1_kernel<.., 1, TAIL>), fp32 throughout; logits come straight out of it
-        // (every model with last1_wt takes one of these two launches in its last layer: the branches below serve the other layers)
-        const bool small_call = head_par || (m->attn256 && call_rows <= kSmallRows && rows <= kSmallRows);
-        const bool last_tail = last_short && small_call && m->last1_wt != nullptr;
-        if (last_tail) {
-            ProfScope ps(P_ATTN_LAST, s);
-            const float *wk = P + lo.attn_w + (size_t)C * C;
+        ProfScope ps(P_ATTN_LAST, s);
+        const float *wk = P + lo.attn_w + (size_t)C * C;
 #define MGPT_LAST1T(C_)                                                                                                                     \
     hipLaunchKernelGGL((fastk::attn_last1_kernel<C_, 32, 1, true>), dim3((unsigned)rows), dim3(256 * fastk::last1_split(C_)),              \
                        (size_t)(fastk::kLast1Lds<C_, 1, true>), s, g->x, P + lo.ln1, wk, m->last1_wt, (float *)nullptr, rows, scale_log2e,    \
-                       P + lo.ln2, P + g->off_lnf, P + g->off_wte, d_logits, kV)
-            if (C == 256) MGPT_LAST1T(256); else if (C == 160) MGPT_LAST1T(160); else MGPT_LAST1T(64);
-#undef MGPT_LAST1T
-            MGPT_LAUNCH_CHECK();
-            return MGPT_OK;
-        }
-        if (last1) {
-            ProfScope ps(P_ATTN_LAST, s);
-            const float *wk = P + lo.attn_w + (size_t)C * C;
+                       P + lo.ln2, P + g->off_lnf, P + g->off_wte, logits, kV)
 #define MGPT_LAST1(C_)                                                                                                                      \
     hipLaunchKernelGGL((fastk::attn_last1_kernel<C_, 32>), dim3((unsigned)(rows_pad / fastk::kLast1R)), dim3(256 * fastk::last1_split(C_)), (size_t)fastk::kLast1Lds<C_>, s, g->x, P + lo.ln1, \
                        wk, m->last1_wt, m->x_last, rows, scale_log2e)
-            if (C == 256 && rows <= 2 * m->n_cu)
-                // few rows (one environment on the 6M shape): one row per workgroup, so that they spread over the CUs
-                hipLaunchKernelGGL((fastk::attn_last1_kernel<256, 32, 1, false>), dim3((unsigned)rows_pad), dim3(256 * fastk::last1_split(256)),
-                                   (size_t)(fastk::kLast1Lds<256, 1, false>), s, g->x, P + lo.ln1, wk, m->last1_wt, m->x_last, rows, scale_log2e);
-            else if (C == 256) MGPT_LAST1(256); else if (C == 160) MGPT_LAST1(160); else MGPT_LAST1(64);
+        if (p.last == LAST_TAIL) { if (C == 256) MGPT_LAST1T(256); else if (C == 160) MGPT_LAST1T(160); else MGPT_LAST1T(64); }
+        else if (p.last1_row_per_wg)
+            hipLaunchKernelGGL((fastk::attn_last1_kernel<256, 32, 1, false>), dim3((unsigned)rows_pad), dim3(256 * fastk::last1_split(256)),
+                               (size_t)(fastk::kLast1Lds<256, 1, false>), s, g->x, P + lo.ln1, wk, m->last1_wt, m->x_last, rows, scale_log2e);
+        else if (C == 256) MGPT_LAST1(256); else if (C == 160) MGPT_LAST1(160); else MGPT_LAST1(64);
 #undef MGPT_LAST1
-            MGPT_LAUNCH_CHECK();
-        } else if (persistent160 && !last_short) {
-            // ---- the 2M shape's attention block as one persistent kernel (attn160o_kernel) ----
-            ProfScope ps(P_ATTN, s);
-            if (embed160 && l == 0)
-                hipLaunchKernelGGL((fastk::attn160o_kernel<T, NP, true>), dim3((unsigned)std::min(rows, m->n_cu)), dim3(512), (size_t)fastk::kA160oLds<NP>, s, g->x,
-                                   m->attn160o_pk[l], m->attn160_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn160o_spill, rows, d_tokens, g->embed_table);
+#undef MGPT_LAST1T
+        MGPT_LAUNCH_CHECK();
+        return MGPT_OK;
+    }
+
+    // ---- the attention block of a full layer as ONE kernel (LN1, QKV, attention, out-projection, residual): q, k, v, y stay on chip ----
+    int attn_block(int l)
+    {
+        const LayerOff &lo = g->layers[l];
+        ProfScope ps(P_ATTN, s);
+        const dim3 grid((unsigned)std::min(rows, m->n_cu));       // of the persistent kernels
+        if (p.attn == ATTN_160O) {
+            if (p.embed == EMBED_TABLE160 && l == 0)
+                hipLaunchKernelGGL((fastk::attn160o_kernel<T, NP, true>), grid, dim3(512), (size_t)fastk::kA160oLds<NP>, s, g->x,
+                                   m->attn160o_pk[l], m->attn160_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn160o_spill, rows, tokens, g->embed_table);
             else
-                hipLaunchKernelGGL((fastk::attn160o_kernel<T, NP>), dim3((unsigned)std::min(rows, m->n_cu)), dim3(512), (size_t)fastk::kA160oLds<NP>, s, g->x,
+                hipLaunchKernelGGL((fastk::attn160o_kernel<T, NP>), grid, dim3(512), (size_t)fastk::kA160oLds<NP>, s, g->x,
                                    m->attn160o_pk[l], m->attn160_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn160o_spill, rows);
-            MGPT_LAUNCH_CHECK();
-        } else if (attn_block) {
-            // ---- LN1 + QKV + attention + out-projection + residual in one kernel: q, k, v, y stay on chip ----
-            // (C = 160 comes here in small calls only: its large calls take attn160o_kernel above)
-            ProfScope ps(P_ATTN, s);
-            const size_t lds = (size_t)NP * (kT * 80 + 32 * 528) + (size_t)(C / 16) * NP * 1024 * 4;   // K, V^T planes + 4 weight packet slots
+        } else if (p.attn == ATTN_BLOCK) {
+            // (C = 160 comes here in small calls only: its large calls take attn160o_kernel)
+            const size_t lds = (size_t)fastk::attn_block_lds(NP, C);
 #define MGPT_ATTN_BLOCK(CT_, EMB_, HP_)                                                                                                     \
     hipLaunchKernelGGL((fastk::attn_block_kernel<T, NP, CT_, EMB_, HP_>), dim3((unsigned)(HP_ ? rows * g->nh : rows)), dim3(512), lds, s, g->x, \
                        P + lo.ln1, m->qkv_pk[l], m->attn[l].inv_scale, m->y[0], m->y[1], g->nh, scale_log2e, m->proj_pk[l],                  \
-                       m->proj[l].inv_scale, m->stats, m->x_last, d_tokens, P + g->off_wte, P + g->off_wpe, m->head_parts, part_stride)
-            if (head_par) { if (C == 160) MGPT_ATTN_BLOCK(5, false, true); else MGPT_ATTN_BLOCK(2, false, true); }
-            else if (embed_fused && l == 0) MGPT_ATTN_BLOCK(2, true, false);
+                       m->proj[l].inv_scale, m->stats, m->x_last, tokens, P + g->off_wte, P + g->off_wpe, m->head_parts, p.part_stride)
+            if (p.head_par) { if (C == 160) MGPT_ATTN_BLOCK(5, false, true); else MGPT_ATTN_BLOCK(2, false, true); }
+            else if (p.embed == EMBED_ATTN_BLOCK && l == 0) MGPT_ATTN_BLOCK(2, true, false);
             else MGPT_ATTN_BLOCK(2, false, false);
 #undef MGPT_ATTN_BLOCK
-            MGPT_LAUNCH_CHECK();
-        } else if (proj_fused) {
-            // ---- the whole attention block (LN1, QKV, attention, out-projection, residual) in one persistent kernel: q, k, v, y stay on chip ----
-            ProfScope ps(P_ATTN, s);
-            // (gpt_kernels_c256b.h: the projection steps and the tail on v_mfma_f32_16x16x32)
-            if (embed256 && l == 0 && m->l0_table != nullptr)        // (q | k | v of layer 0 from the (position, token) table)
-                hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, false, 2>), dim3((unsigned)std::min(rows, m->n_cu)), dim3(512), (size_t)kA256Lds<NP>, s, g->x,
+        } else {
+            // ATTN_256Q (gpt_kernels_c256b.h: the projection steps and the tail on v_mfma_f32_16x16x32)
+            const bool emb = p.embed == EMBED_TABLE256 && l == 0;
+            if (emb && p.l0_qkv_table)                               // (q | k | v of layer 0 from the (position, token) table)
+                hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, false, 2>), grid, dim3(512), (size_t)fastk::kA256Lds<NP>, s, g->x,
                                    m->attn256q_pk[l], m->attn256_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn256q_spill, rows,
-                                   (unsigned long long *)nullptr, d_tokens, g->embed_table, m->l0_table);
-            else if (embed256 && l == 0)
-                hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true>), dim3((unsigned)std::min(rows, m->n_cu)), dim3(512), (size_t)kA256Lds<NP>, s, g->x,
+                                   (unsigned long long *)nullptr, tokens, g->embed_table, m->l0_table);
+            else if (emb)
+                hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true>), grid, dim3(512), (size_t)fastk::kA256Lds<NP>, s, g->x,
                                    m->attn256q_pk[l], m->attn256_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn256q_spill, rows,
-                                   (unsigned long long *)nullptr, d_tokens, g->embed_table);
+                                   (unsigned long long *)nullptr, tokens, g->embed_table);
             else
-                hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP>), dim3((unsigned)std::min(rows, m->n_cu)), dim3(512), (size_t)kA256Lds<NP>, s, g->x,
+                hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP>), grid, dim3(512), (size_t)fastk::kA256Lds<NP>, s, g->x,
                                    m->attn256q_pk[l], m->attn256_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn256q_spill, rows,
                                    (unsigned long long *)nullptr);
-            MGPT_LAUNCH_CHECK();
-        } else if (small256) {
-            // ---- LN1 + QKV + attention, one workgroup per (row, head): q, k, v stay on chip -> y operand planes for the out-projection ----
-            ProfScope ps(P_ATTN, s);
-            hipLaunchKernelGGL((fastk::attn256_kernel<T, NP>), dim3((unsigned)rows * 8), dim3(512), (size_t)kA256Lds<NP>, s,
-                               g->x, m->attn256_pk[l], m->attn256_inv[l], scale_log2e, m->y[0], (unsigned long long *)nullptr);
-            MGPT_LAUNCH_CHECK();
-        } else if (m->pk_gemm) {
-            // (folded LayerNorm: m->apk already holds the raw rows -- from the embedding or from the residual epilogue before -- and
-            //  m->stats their (mean, rstd); the W * ln_1.weight packing and its column sums do the rest in the epilogue)
-            if (!m->ln_fold && (rc = launch_ln_pack<T, NP>(g->x, P + lo.ln1, m->apk, M, C, m->x_tiled ? 1 : 0, s)) != MGPT_OK) return rc;
-            ProfScope ps(P_GEMM_QKV, s);
-            const size_t tile_halves = (size_t)(C / 16) * NP * 512;          // one 32-row tile of a PK matrix with K = C
-            const uint16_t *wq = m->ln_fold ? m->attn_pk2g[l] : m->attn_pk2[l];
-            a.a_hi = m->apk; a.w_hi = wq; a.chunk_major = 1;
-            if (m->ln_fold) { a.ln_stats = m->stats; a.colsum = m->attn_cs[l]; }
-            if ((rc = launch_gemm_pk<T, NP, fastk::EPI_QK>(a, s, small_pk, big_call)) != MGPT_OK) return rc;
-            a.w_hi = wq + (size_t)(2 * C / 32) * tile_halves;                // rows 2C.. of c_attn.weight: V
-            if (m->ln_fold) a.colsum = m->attn_cs[l] + 2 * C;
-            a.N = C; a.o_hi = m->vt[0]; a.o_lo = m->vt[1];
-            if ((rc = launch_gemm_pk<T, NP, fastk::EPI_VT>(a, s, small_pk, big_call)) != MGPT_OK) return rc;
-            a.ln_stats = nullptr; a.colsum = nullptr;
-        } else {
+        }
+        MGPT_LAUNCH_CHECK();
+        return MGPT_OK;
+    }
+
+    // ---- the attention block as a chain of launches (ATTN_256_HEADS, ATTN_PACKED, ATTN_GENERIC) ----
+    // LN1 + q|k and v^T projections -> planes
+    int qkv_gemms(int l, fastk::GemmArgs &a)
+    {
+        int rc;
+        if (p.attn == ATTN_GENERIC) {
             ProfScope ps(P_GEMM_QKV, s);
             if ((rc = launch_gemm16<T, NP, fastk::PRO_LN, fastk::EPI_QK>(a, C, s)) != MGPT_OK) return rc;
-            // ---- LN1 + V projection -> v^T planes ----
             a.w_hi = m->attn[l].hi + (size_t)2 * C * C; a.w_lo = (NP == 2) ? m->attn[l].lo + (size_t)2 * C * C : nullptr;
             a.N = C; a.o_hi = m->vt[0]; a.o_lo = m->vt[1];
-            if ((rc = launch_gemm16<T, NP, fastk::PRO_LN, fastk::EPI_VT>(a, C, s)) != MGPT_OK) return rc;
+            return launch_gemm16<T, NP, fastk::PRO_LN, fastk::EPI_VT>(a, C, s);
         }
-        if (!attn_block && !proj_fused && !last1) {
-            const bool ls = last_short && m->pk_gemm;       // only token 255 of every row from here on
-            if (!m->attn256) {
-                ProfScope ps(ls ? P_ATTN_LAST : P_ATTN, s);
-                const uint16_t *qh = m->qk[0], *ql = m->qk[1], *kh = m->qk[0] + M * C, *kl = (NP == 2) ? m->qk[1] + M * C : nullptr;
-                uint16_t *yh = ls ? m->y_last : m->y[0];
-                if (g->hs == 32)
-                    hipLaunchKernelGGL((fastk::attn16_kernel<T, NP, 32>), dim3(rows * g->nh), dim3(512), attn_lds, s, qh, ql, kh, kl, m->vt[0], m->vt[1], yh, m->y[1], g->nh, scale_log2e, m->pk_gemm ? 1 : 0, m->pk_gemm ? 1 : 0, ls ? 1 : 0);
-                else
-                    hipLaunchKernelGGL((fastk::attn16_kernel<T, NP, 64>), dim3(rows * g->nh), dim3(512), attn_lds, s, qh, ql, kh, kl, m->vt[0], m->vt[1], yh, m->y[1], g->nh, scale_log2e, m->pk_gemm ? 1 : 0, m->pk_gemm ? 1 : 0, ls ? 1 : 0);
-                MGPT_LAUNCH_CHECK();
-            }
-            if (ls) {
-                ProfScope ps(P_EMBED, s);
-                hipLaunchKernelGGL(fastk::gather_last_kernel, dim3((unsigned)cdiv64((int64_t)rows_pad * (C / 4), 256)), dim3(256), 0, s, g->x, m->x_last, rows,
-                                   rows_pad, C, m->x_tiled ? 1 : 0);
-                MGPT_LAUNCH_CHECK();
-            }
-            // ---- attention output projection + residual (+ stats of the new rows) ----
-            a.a_hi = ls ? m->y_last : m->y[0]; a.a_lo = m->y[1]; a.K = C; a.N = C;
-            a.w_hi = m->proj[l].hi; a.w_lo = m->proj[l].lo; a.out_scale = m->proj[l].inv_scale;
-            a.x_out = ls ? m->x_last : g->x; a.stats_out = m->stats; a.x_tiled = m->x_tiled ? 1 : 0;
-            if (ls) a.M = rows_pad;
-            ProfScope ps(ls ? P_GEMM_PROJ_LAST : P_GEMM_PROJ, s);
-            if (m->pk_gemm) {
+        // (folded LayerNorm: m->apk already holds the raw rows -- from the embedding or from the residual epilogue before -- and
+        //  m->stats their (mean, rstd); the W * ln_1.weight packing and its column sums do the rest in the epilogue)
+        if (!m->ln_fold && (rc = launch_ln_pack<T, NP>(g->x, P + g->layers[l].ln1, m->apk, M, C, m->x_tiled ? 1 : 0, s)) != MGPT_OK) return rc;
+        ProfScope ps(P_GEMM_QKV, s);
+        const size_t tile_halves = (size_t)(C / 16) * NP * 512;          // one 32-row tile of a PK matrix with K = C
+        const uint16_t *wq = m->ln_fold ? m->attn_pk2g[l] : m->attn_pk2[l];
+        a.a_hi = m->apk; a.w_hi = wq; a.chunk_major = 1;
+        if (m->ln_fold) { a.ln_stats = m->stats; a.colsum = m->attn_cs[l]; }
+        if ((rc = launch_gemm_pk<T, NP, fastk::EPI_QK>(a, m->n_cu, s, p.half_qkv, p.big_call)) != MGPT_OK) return rc;
+        a.w_hi = wq + (size_t)(2 * C / 32) * tile_halves;                // rows 2C.. of c_attn.weight: V
+        if (m->ln_fold) a.colsum = m->attn_cs[l] + 2 * C;
+        a.N = C; a.o_hi = m->vt[0]; a.o_lo = m->vt[1];
+        if ((rc = launch_gemm_pk<T, NP, fastk::EPI_VT>(a, m->n_cu, s, p.half_qkv, p.big_call)) != MGPT_OK) return rc;
+        a.ln_stats = nullptr; a.colsum = nullptr;
+        return MGPT_OK;
+    }
+
+    // ... attention -> y planes; output projection + residual (+ stats of the new rows).  last (LAST_PACKED): only token 255 of every row from here on
+    int attn_chain(int l, bool last, fastk::GemmArgs &a)
+    {
+        const bool packed = p.attn != ATTN_GENERIC;
+        int rc;
+        if (p.attn == ATTN_256_HEADS) {
+            // LN1 + QKV + attention, one workgroup per (row, head): q, k, v stay on chip -> y operand planes for the out-projection
+            ProfScope ps(P_ATTN, s);
+            hipLaunchKernelGGL((fastk::attn256_kernel<T, NP>), dim3((unsigned)rows * 8), dim3(512), (size_t)fastk::kA256Lds<NP>, s,
+                               g->x, m->attn256_pk[l], m->attn256_inv[l], scale_log2e, m->y[0], (unsigned long long *)nullptr);
+            MGPT_LAUNCH_CHECK();
+        } else {
+            if ((rc = qkv_gemms(l, a)) != MGPT_OK) return rc;
+            ProfScope ps(last ? P_ATTN_LAST : P_ATTN, s);
+            const uint16_t *qh = m->qk[0], *ql = m->qk[1], *kh = m->qk[0] + M * C, *kl = (NP == 2) ? m->qk[1] + M * C : nullptr;
+            uint16_t *yh = last ? m->y_last : m->y[0];
+#define MGPT_ATTN16(HS_)                                                                                                                    \
+    hipLaunchKernelGGL((fastk::attn16_kernel<T, NP, HS_>), dim3(rows * g->nh), dim3(512), (size_t)fastk::attn16_lds(NP, HS_), s, qh, ql, kh, kl, \
+                       m->vt[0], m->vt[1], yh, m->y[1], g->nh, scale_log2e, packed ? 1 : 0, packed ? 1 : 0, last ? 1 : 0)
+            if (g->hs == 32) MGPT_ATTN16(32); else MGPT_ATTN16(64);
+#undef MGPT_ATTN16
+            MGPT_LAUNCH_CHECK();
+        }
+        if (last) {
+            ProfScope ps(P_EMBED, s);
+            hipLaunchKernelGGL(fastk::gather_last_kernel, dim3((unsigned)cdiv64((int64_t)rows_pad * (C / 4), 256)), dim3(256), 0, s, g->x, m->x_last, rows,
+                               rows_pad, C, m->x_tiled ? 1 : 0);
+            MGPT_LAUNCH_CHECK();
+        }
+        a.a_hi = last ? m->y_last : m->y[0]; a.a_lo = m->y[1]; a.K = C; a.N = C;
+        a.w_hi = m->proj[l].hi; a.w_lo = m->proj[l].lo; a.out_scale = m->proj[l].inv_scale;
+        a.x_out = last ? m->x_last : g->x; a.stats_out = m->stats; a.x_tiled = m->x_tiled ? 1 : 0;
+        if (last) a.M = rows_pad;
+        {
+            ProfScope ps(last ? P_GEMM_PROJ_LAST : P_GEMM_PROJ, s);
+            if (packed) {
                 a.w_hi = m->proj_pk2[l];
                 if (m->ln_fold) {                                                      // the rows ln_2 normalises: planes + partial sums
                     a.raw_out = m->apk; a.rsum_out = m->ln_parts;
-                    a.shift = m->ln_mean; a.shift_stride = ls ? kT : 1; a.shift_offset = ls ? kT - 1 : 0;
+                    a.shift = m->ln_mean; a.shift_stride = last ? kT : 1; a.shift_offset = last ? kT - 1 : 0;
                 }
-                if ((rc = launch_gemm_pk<T, NP, fastk::EPI_RESID>(a, s, small256 || (small_pk && !ls), big_call)) != MGPT_OK) return rc;
+                if ((rc = launch_gemm_pk<T, NP, fastk::EPI_RESID>(a, m->n_cu, s, p.half_proj && !last, p.big_call)) != MGPT_OK) return rc;
                 a.raw_out = nullptr; a.rsum_out = nullptr; a.shift = nullptr;
             } else if ((rc = launch_gemm16<T, NP, fastk::PRO_PLANES, fastk::EPI_RESID>(a, C, s)) != MGPT_OK) return rc;
         }
-        if (!fused_stats(C) && !m->pk_gemm && (rc = launch_row_stats(g->x, m->stats, M, C, s)) != MGPT_OK) return rc;
-        float *mlp_x = last_short ? m->x_last : g->x;
-        const int64_t mlp_M = last_short ? (int64_t)rows_pad : M;
-        if (m->mlp_fused) {
-            // ---- whole MLP block in one kernel (hidden stays in registers) ----
-            ProfScope ps(last_short ? P_MLP_FUSED_LAST : P_MLP_FUSED, s);
-            if (C == 256) {
-                // persistent: one workgroup per CU walks the 128-token blocks round-robin (results do not depend on the grid)
-                const int n_blocks = (int)(mlp_M / 128);
-                if (small256 && 2 * n_blocks <= m->n_cu)
-                    // small launch: 64-token blocks, four waves with a SIMD each (mlp256p_kernel<.., NPAIR = 2>): twice the workgroups
-                    hipLaunchKernelGGL((fastk::mlp256p_kernel<T, NP, 0, 2>), dim3((unsigned)std::min(2 * n_blocks, m->n_cu)), dim3(256), (size_t)fastk::kMPLds<NP>, s,
-                                       mlp_x, m->mlp256_pk[l], m->mlp256_inv1[l], m->proj2[l].inv_scale, m->mlp256_lut[l], 2 * n_blocks, (unsigned long long *)nullptr);
-                else if (small256)
-                    hipLaunchKernelGGL((fastk::mlp256p_kernel<T, NP>), dim3((unsigned)std::min(n_blocks, m->n_cu)), dim3(512), (size_t)fastk::kMPLds<NP>, s,
-                                       mlp_x, m->mlp256_pk[l], m->mlp256_inv1[l], m->proj2[l].inv_scale, m->mlp256_lut[l], n_blocks, (unsigned long long *)nullptr);
-                else
-                    // large calls: the same block on v_mfma_f32_16x16x32 (gpt_kernels_c256q.h: 13-15 % more f16 flops per second at the power limit; 2.66 -> 2.45 ms
-                    // per 4096-row launch).  Small calls are not power-limited and keep the 32 x 32 x 16 kernel; the choice is a property of the call
-                    hipLaunchKernelGGL((fastk::mlp256q_kernel<T, NP>), dim3((unsigned)std::min(n_blocks, m->n_cu)), dim3(512), (size_t)fastk::kMPLds<NP>, s,
-                                       mlp_x, m->mlp256q_pk[l], m->mlp256_inv1[l], m->proj2[l].inv_scale, m->mlp256_lut[l], n_blocks, (unsigned long long *)nullptr);
-                if (!m->pk_gemm && l + 1 < g->L) {                       // this kernel leaves no LayerNorm statistics behind
-                    MGPT_LAUNCH_CHECK();
-                    if ((rc = launch_row_stats(g->x, m->stats, M, C, s)) != MGPT_OK) return rc;
-                }
-            } else if (head_par && C == 160) {
-                // small launch: persistent producer / consumer blocks of 128 tokens (two waves per SIMD); the heads' partial sums are folded in
-                const int n_blocks = (int)(mlp_M / 128);
-                if (mlp_M <= (int64_t)32 * m->n_cu)
-                    // ... or 32-token blocks, one producer and one consumer wave (cfg1's 8192 tokens: one block per CU)
-                    hipLaunchKernelGGL((fastk::mlp160p_kernel<T, NP, 5, 1>), dim3((unsigned)std::min((int)(mlp_M / 32), m->n_cu)), dim3(128), (size_t)(fastk::kM5Lds<NP, 1>), s,
-                                       mlp_x, m->mlp160_pk[l], m->mlp160_inv1[l], m->proj2[l].inv_scale, m->gelu_lut, (int)(mlp_M / 32), m->head_parts, part_stride);
-                else if (mlp_M <= (int64_t)64 * m->n_cu)
-                    // so few tokens that 128-token blocks would leave CUs idle (one environment): 64-token blocks, one wave per SIMD
-                    hipLaunchKernelGGL((fastk::mlp160p_kernel<T, NP, 5, 2>), dim3((unsigned)std::min((int)(mlp_M / 64), m->n_cu)), dim3(256), (size_t)(fastk::kM5Lds<NP, 2>), s,
-                                       mlp_x, m->mlp160_pk[l], m->mlp160_inv1[l], m->proj2[l].inv_scale, m->gelu_lut, (int)(mlp_M / 64), m->head_parts, part_stride);
-                else
-                    hipLaunchKernelGGL((fastk::mlp160p_kernel<T, NP, 5>), dim3((unsigned)std::min(n_blocks, m->n_cu)), dim3(512), (size_t)fastk::kM5Lds<NP>, s,
-                                       mlp_x, m->mlp160_pk[l], m->mlp160_inv1[l], m->proj2[l].inv_scale, m->gelu_lut, n_blocks, m->head_parts, part_stride);
-            } else {
-                const size_t lds = (size_t)(C / 16 + 2 * (C / 32)) * NP * 1024 * 3 + fastk::kGeluLutN * 8;
-                // 32 tokens per wave whatever the block size: small launches (cfg1: 32 rows = 32 blocks of 256 tokens) take
-                // fewer waves per block so that the tokens spread over more CUs; results do not depend on the choice
+        if (!fused_stats(C) && !packed) return launch_row_stats(g->x, m->stats, M, C, s);
+        return MGPT_OK;
+    }
+
+    // ---- the MLP block in one kernel (the hidden stays in registers); last: on the compact rows of the last layer ----
+    int mlp_fused(int l, bool last)
+    {
+        const LayerOff &lo = g->layers[l];
+        float *mlp_x = last ? m->x_last : g->x;
+        const int64_t mlp_M = last ? (int64_t)rows_pad : M;
+        ProfScope ps(last ? P_MLP_FUSED_LAST : P_MLP_FUSED, s);
+        if (p.mlp == MLP_256P2 || p.mlp == MLP_256P || p.mlp == MLP_256Q) {
+            // persistent: one workgroup per CU walks the 128-token blocks round-robin (results do not depend on the grid)
+            const int n_blocks = (int)(mlp_M / 128);
+            if (p.mlp == MLP_256P2)
+                // small launch: 64-token blocks, four waves with a SIMD each (mlp256p_kernel<.., NPAIR = 2>): twice the workgroups
+                hipLaunchKernelGGL((fastk::mlp256p_kernel<T, NP, 0, 2>), dim3((unsigned)std::min(2 * n_blocks, m->n_cu)), dim3(256), (size_t)fastk::kMPLds<NP>, s,
+                                   mlp_x, m->mlp256_pk[l], m->mlp256_inv1[l], m->proj2[l].inv_scale, m->mlp256_lut[l], 2 * n_blocks, (unsigned long long *)nullptr);
+            else if (p.mlp == MLP_256P)
+                hipLaunchKernelGGL((fastk::mlp256p_kernel<T, NP>), dim3((unsigned)std::min(n_blocks, m->n_cu)), dim3(512), (size_t)fastk::kMPLds<NP>, s,
+                                   mlp_x, m->mlp256_pk[l], m->mlp256_inv1[l], m->proj2[l].inv_scale, m->mlp256_lut[l], n_blocks, (unsigned long long *)nullptr);
+            else
+                hipLaunchKernelGGL((fastk::mlp256q_kernel<T, NP>), dim3((unsigned)std::min(n_blocks, m->n_cu)), dim3(512), (size_t)fastk::kMPLds<NP>, s,
+                                   mlp_x, m->mlp256q_pk[l], m->mlp256_inv1[l], m->proj2[l].inv_scale, m->mlp256_lut[l], n_blocks, (unsigned long long *)nullptr);
+            if (!m->pk_gemm && l + 1 < g->L) {                       // this kernel leaves no LayerNorm statistics behind
+                MGPT_LAUNCH_CHECK();
+                const int rc = launch_row_stats(g->x, m->stats, M, C, s);
+                if (rc != MGPT_OK) return rc;
+            }
+        } else if (p.mlp == MLP_160P) {
+            // small launch: persistent producer / consumer blocks of TOK_ tokens; the heads' partial sums are folded in
+#define MGPT_MLP160P(TOK_, ...)                                                                                                             \
+    hipLaunchKernelGGL((fastk::mlp160p_kernel<T, NP, __VA_ARGS__>), dim3((unsigned)std::min((int)(mlp_M / TOK_), m->n_cu)), dim3(4 * TOK_),   \
+                       (size_t)(fastk::kM5Lds<NP, TOK_ / 32>), s, mlp_x, m->mlp160_pk[l], m->mlp160_inv1[l], m->proj2[l].inv_scale, m->gelu_lut, \
+                       (int)(mlp_M / TOK_), m->head_parts, p.part_stride)
+            if (p.mlp160_tokens == 32) MGPT_MLP160P(32, 5, 1); else if (p.mlp160_tokens == 64) MGPT_MLP160P(64, 5, 2); else MGPT_MLP160P(128, 5);
+#undef MGPT_MLP160P
+        } else {
+            const size_t lds = (size_t)fastk::mlp_fused_lds(NP, C);
+            // 32 tokens per wave whatever the block size: small launches (cfg1: 32 rows = 32 blocks of 256 tokens) take fewer waves per block so that the tokens
+            // spread over more CUs; results do not depend on the choice (one wave per workgroup is slower: 63 us per launch against 52, round 4)
 #define MGPT_MLP_(CT_, NW_)                                                                                                          \
     hipLaunchKernelGGL((fastk::mlp_fused_kernel<T, NP, CT_, NW_>), dim3((unsigned)(mlp_M / (32 * NW_))), dim3(64 * NW_), lds, s, mlp_x, \
-                       P + lo.ln2, m->mlp_pk[l], m->fc[l].inv_scale, m->proj2[l].inv_scale, last_short ? nullptr : m->stats, (int)mlp_M, m->gelu_lut, \
-                       m->head_parts, part_stride)
-    // large calls: the same block on v_mfma_f32_16x16x32 (gpt_kernels_fused16.h); small calls (head_par) are not power-limited and keep the 32 x 32 x 16 kernel
+                       P + lo.ln2, m->mlp_pk[l], m->fc[l].inv_scale, m->proj2[l].inv_scale, last ? nullptr : m->stats, (int)mlp_M, m->gelu_lut, \
+                       m->head_parts, p.part_stride)
 #define MGPT_MLP16_(CT_, NW_)                                                                                                        \
     hipLaunchKernelGGL((fastk::mlp_fused16_kernel<T, NP, CT_, NW_, 0>), dim3((unsigned)(mlp_M / (32 * NW_))), dim3(64 * NW_), lds, s, mlp_x, \
-                       P + lo.ln2, m->mlp16_pk[l], m->fc[l].inv_scale, m->proj2[l].inv_scale, last_short ? nullptr : m->stats, (int)mlp_M, m->gelu_lut, \
+                       P + lo.ln2, m->mlp16_pk[l], m->fc[l].inv_scale, m->proj2[l].inv_scale, last ? nullptr : m->stats, (int)mlp_M, m->gelu_lut, \
                        (const float *)nullptr, (int64_t)0)
-#define MGPT_MLP(CT_, NW_) do { if (head_par) MGPT_MLP_(CT_, NW_); else MGPT_MLP16_(CT_, NW_); } while (0)
-                // (one wave per workgroup -- 256 workgroups for cfg1's 8192 tokens -- is slower: 63 us per launch against 52, round 4)
-                const int nw = (mlp_M >= (int64_t)256 * m->n_cu) ? 8 : (mlp_M >= (int64_t)128 * m->n_cu ? 4 : 2);
-                // (head_par: mlp_fused_kernel folds in the heads' partial sums = n_head buffers, and n_head == C / 32 for the shapes of this path;
-                //  C = 160 comes here in large calls only)
-                if (C == 160) { if (nw == 8) MGPT_MLP16_(5, 8); else if (nw == 4) MGPT_MLP16_(5, 4); else MGPT_MLP16_(5, 2); }
-                else { if (nw == 8) MGPT_MLP(2, 8); else if (nw == 4) MGPT_MLP(2, 4); else MGPT_MLP(2, 2); }
+#define MGPT_MLP(CT_, NW_) do { if (p.mlp == MLP_FUSED) MGPT_MLP_(CT_, NW_); else MGPT_MLP16_(CT_, NW_); } while (0)
+            // (MLP_FUSED: mlp_fused_kernel folds in the heads' partial sums = n_head buffers, and n_head == C / 32 for the shapes of this path;
+            //  C = 160 comes here in large calls only)
+            const int nw = last ? p.mlp_nw_last : p.mlp_nw;
+            if (C == 160) { if (nw == 8) MGPT_MLP16_(5, 8); else if (nw == 4) MGPT_MLP16_(5, 4); else MGPT_MLP16_(5, 2); }
+            else { if (nw == 8) MGPT_MLP(2, 8); else if (nw == 4) MGPT_MLP(2, 4); else MGPT_MLP(2, 2); }
 #undef MGPT_MLP
 #undef MGPT_MLP16_
 #undef MGPT_MLP_
-            }
-            MGPT_LAUNCH_CHECK();
-            continue;
         }
-        if (m->pk_gemm) {
-            // ---- LN2 -> PK planes; FC + GELU -> hidden PK planes; proj2 + residual ----
-            if (m->ln_fold) { if ((rc = ln_finalize(mlp_M, last_short)) != MGPT_OK) return rc; }
-            else if ((rc = launch_ln_pack<T, NP>(mlp_x, P + lo.ln2, m->apk, mlp_M, C, m->x_tiled ? 1 : 0, s)) != MGPT_OK) return rc;
-            a.M = (int)mlp_M;
-            a.a_hi = m->apk; a.K = C; a.N = 4 * C; a.w_hi = m->ln_fold ? m->fc_pk2g[l] : m->fc_pk2[l]; a.out_scale = m->fc[l].inv_scale;
-            a.o_hi = m->hbuf[0]; a.o_pk = 1; a.gelu_lut = m->gelu_lut;
-            if (m->ln_fold) { a.ln_stats = m->stats; a.colsum = m->fc_cs[l]; }
-            {
-                ProfScope ps(P_GEMM_FC, s);
-                // (c_fc keeps its 256-row tiles in small calls too: 384 of them already cover the CUs, and two 4-wave workgroups per CU move 1.5 x the ring
-                //  pieces per MFMA of one 8-wave workgroup -- 54.6 vs 56.5 us per launch at 32 rows)
-                if ((rc = launch_gemm_pk<T, NP, fastk::EPI_GELU>(a, s, false, big_call)) != MGPT_OK) return rc;
-            }
-            a.ln_stats = nullptr; a.colsum = nullptr;
-            a.a_hi = m->hbuf[0]; a.K = 4 * C; a.N = C; a.w_hi = m->proj2_pk2[l]; a.out_scale = m->proj2[l].inv_scale;
-            a.x_out = mlp_x; a.stats_out = nullptr;
-            const bool feeds_next = m->ln_fold && l + 1 < g->L;            // the rows the next layer's ln_1 normalises
-            if (feeds_next) { a.raw_out = m->apk; a.rsum_out = m->ln_parts; a.shift = m->ln_mean; a.shift_stride = 1; a.shift_offset = 0; }
-            {
-                ProfScope ps(P_GEMM_PROJ2, s);
-                if ((rc = launch_gemm_pk<T, NP, fastk::EPI_RESID>(a, s, small_pk && !last_short, big_call)) != MGPT_OK) return rc;
-            }
-            if (feeds_next && (rc = ln_finalize(mlp_M, false)) != MGPT_OK) return rc;
-            continue;
+        MGPT_LAUNCH_CHECK();
+        return MGPT_OK;
+    }
+
+    // ---- the MLP block of the packed chain: LN2 -> PK planes; FC + GELU -> hidden PK planes; proj2 + residual ----
+    int mlp_packed(int l, bool last, fastk::GemmArgs &a)
+    {
+        float *mlp_x = last ? m->x_last : g->x;
+        const int64_t mlp_M = last ? (int64_t)rows_pad : M;
+        int rc;
+        if (m->ln_fold) { if ((rc = ln_finalize(mlp_M, last)) != MGPT_OK) return rc; }
+        else if ((rc = launch_ln_pack<T, NP>(mlp_x, P + g->layers[l].ln2, m->apk, mlp_M, C, m->x_tiled ? 1 : 0, s)) != MGPT_OK) return rc;
+        a.M = (int)mlp_M;
+        a.a_hi = m->apk; a.K = C; a.N = 4 * C; a.w_hi = m->ln_fold ? m->fc_pk2g[l] : m->fc_pk2[l]; a.out_scale = m->fc[l].inv_scale;
+        a.o_hi = m->hbuf[0]; a.o_pk = 1; a.gelu_lut = m->gelu_lut;
+        if (m->ln_fold) { a.ln_stats = m->stats; a.colsum = m->fc_cs[l]; }
+        {
+            ProfScope ps(P_GEMM_FC, s);
+            // (c_fc keeps its 256-row tiles in small calls too: 384 of them already cover the CUs, and two 4-wave workgroups per CU move 1.5 x the ring
+            //  pieces per MFMA of one 8-wave workgroup -- 54.6 vs 56.5 us per launch at 32 rows)
+            if ((rc = launch_gemm_pk<T, NP, fastk::EPI_GELU>(a, m->n_cu, s, false, p.big_call)) != MGPT_OK) return rc;
         }
-        // ---- LN2 + FC + GELU -> hidden planes ----
-        a.x = g->x; a.stats = m->stats; a.gain = P + lo.ln2; a.K = C; a.N = 4 * C;
+        a.ln_stats = nullptr; a.colsum = nullptr;
+        a.a_hi = m->hbuf[0]; a.K = 4 * C; a.N = C; a.w_hi = m->proj2_pk2[l]; a.out_scale = m->proj2[l].inv_scale;
+        a.x_out = mlp_x; a.stats_out = nullptr;
+        const bool feeds_next = m->ln_fold && l + 1 < g->L;            // the rows the next layer's ln_1 normalises
+        if (feeds_next) { a.raw_out = m->apk; a.rsum_out = m->ln_parts; a.shift = m->ln_mean; a.shift_stride = 1; a.shift_offset = 0; }
+        {
+            ProfScope ps(P_GEMM_PROJ2, s);
+            if ((rc = launch_gemm_pk<T, NP, fastk::EPI_RESID>(a, m->n_cu, s, p.half_proj2 && !last, p.big_call)) != MGPT_OK) return rc;
+        }
+        return feeds_next ? ln_finalize(mlp_M, false) : MGPT_OK;
+    }
+
+    // ---- ... of the generic chain: LN2 + FC + GELU -> hidden planes; MLP output projection + residual (+ stats) ----
+    int mlp_generic(int l, fastk::GemmArgs &a)
+    {
+        int rc;
+        a.x = g->x; a.stats = m->stats; a.gain = P + g->layers[l].ln2; a.K = C; a.N = 4 * C;
         a.w_hi = m->fc[l].hi; a.w_lo = m->fc[l].lo; a.out_scale = m->fc[l].inv_scale;
         a.o_hi = m->hbuf[0]; a.o_lo = m->hbuf[1];
         {
             ProfScope ps(P_GEMM_FC, s);
             if ((rc = launch_gemm16<T, NP, fastk::PRO_LN, fastk::EPI_GELU>(a, C, s)) != MGPT_OK) return rc;
         }
-        // ---- MLP output projection + residual (+ stats) ----
         a.a_hi = m->hbuf[0]; a.a_lo = m->hbuf[1]; a.K = 4 * C; a.N = C;
         a.w_hi = m->proj2[l].hi; a.w_lo = m->proj2[l].lo; a.out_scale = m->proj2[l].inv_scale;
         a.x_out = g->x; a.stats_out = m->stats;
@@ -1010,26 +979,58 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
             ProfScope ps(P_GEMM_PROJ2, s);
             if ((rc = launch_gemm16<T, NP, fastk::PRO_PLANES, fastk::EPI_RESID>(a, C, s)) != MGPT_OK) return rc;
         }
-        if (!fused_stats(C) && l + 1 < g->L && (rc = launch_row_stats(g->x, m->stats, M, C, s)) != MGPT_OK) return rc;
+        if (!fused_stats(C) && l + 1 < g->L) return launch_row_stats(g->x, m->stats, M, C, s);
+        return MGPT_OK;
     }
-    if (seq != nullptr) return gpt_launch_head_seq(g, g->x, m->x_tiled, rows, kT, *seq, s);     // every position of the full residual stream
-    if (m->x_tiled) {
-        {
-            ProfScope ps(P_HEAD, s);
-            hipLaunchKernelGGL(fastk::untile_rows_kernel, dim3((unsigned)cdiv64((int64_t)rows * (C / 4), 256)), dim3(256), 0, s, m->x_last, m->x_head, rows, C);
-            MGPT_LAUNCH_CHECK();
+
+    // ---- ln_f + head on the last token of every row (a sequence forward: at every position of the full residual stream) ----
+    int head()
+    {
+        if (seq != nullptr) return gpt_launch_head_seq(g, g->x, m->x_tiled, rows, kT, *seq, s);
+        if (m->x_tiled) {
+            {
+                ProfScope ps(P_HEAD, s);
+                hipLaunchKernelGGL(fastk::untile_rows_kernel, dim3((unsigned)cdiv64((int64_t)rows * (C / 4), 256)), dim3(256), 0, s, m->x_last, m->x_head, rows, C);
+                MGPT_LAUNCH_CHECK();
+            }
+            return gpt_launch_head_at(g, m->x_head, (int64_t)C, 0, rows, logits, s);
         }
-        return gpt_launch_head_at(g, m->x_head, (int64_t)C, 0, rows, d_logits, s);
+        if (p.family != FAM_GENERIC) return gpt_launch_head_at(g, m->x_last, (int64_t)C, 0, rows, logits, s);
+        return gpt_launch_head(g, rows, logits, s);
     }
-    if (attn_block || m->pk_gemm) return gpt_launch_head_at(g, m->x_last, (int64_t)C, 0, rows, d_logits, s);
-    return gpt_launch_head(g, rows, d_logits, s);
+};
+
+// plan -> embedding -> for each layer { attention block; MLP block } -> head
+template <class T, int NP>
+int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, float *d_logits, hipStream_t s, int call_rows,
+                  const SeqOut *seq = nullptr)
+{
+    const Plan p = make_plan(g, m, rows, call_rows, seq != nullptr);
+    Chunk<T, NP> c = {g, m, d_tokens, d_logits, s, seq, p};
+    int rc;
+    if ((rc = c.ensure_head_parts()) != MGPT_OK) return rc;                      // (before any kernel of the chunk is enqueued)
+    if ((rc = c.embedding()) != MGPT_OK) return rc;
+    for (int l = 0; l < g->L; l++) {
+        const bool last = p.last != LAST_NONE && l == g->L - 1;
+        if (last && p.last == LAST_TAIL) return c.attn_last(l);                   // (logits and all: no head launch)
+        fastk::GemmArgs a = c.layer_args(l);
+        if (last && p.last == LAST_1) rc = c.attn_last(l);
+        else if (p.attn == ATTN_160O || p.attn == ATTN_BLOCK || p.attn == ATTN_256Q) rc = c.attn_block(l);
+        else rc = c.attn_chain(l, last, a);
+        if (rc != MGPT_OK) return rc;
+        if (p.mlp == MLP_PACKED) rc = c.mlp_packed(l, last, a);
+        else if (p.mlp == MLP_GENERIC) rc = c.mlp_generic(l, a);
+        else rc = c.mlp_fused(l, last);
+        if (rc != MGPT_OK) return rc;
+    }
+    return c.head();
 }
 
 template <class T, int NP, int HS>
-int raise_attn_lds(size_t bytes)
+int raise_attn_lds()
 {
     MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn16_kernel<T, NP, HS>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, fastk::attn16_lds(NP, HS)));
     return MGPT_OK;
 }
 
@@ -1067,15 +1068,14 @@ int gpt_fast_forward(mgpt_gpt *g, const uint8_t *d_tokens, int rows, float *d_lo
     FastState *f = static_cast<FastState *>(g->fast);
     MGPT_REQUIRE(f, MGPT_ERR_STATE, "mgpt_gpt_finalize must precede forward");
     ModeState *m = &f->mode[precision];
-    const size_t attn_lds = (size_t)(precision == MGPT_PREC_F16X3 ? 2 : 1) * (kT * (g->hs + 8) * 2 + g->hs * (kT + 8) * 2);
     if (!m->built) {                                     // first use of this precision: pack planes, size workspace
         int rc;
         if (precision == MGPT_PREC_F16X3) {
             rc = build_mode<fastk::F16T, 2>(g, m, true);
-            if (rc == MGPT_OK) rc = (g->hs == 32) ? raise_attn_lds<fastk::F16T, 2, 32>(attn_lds) : raise_attn_lds<fastk::F16T, 2, 64>(attn_lds);
+            if (rc == MGPT_OK) rc = (g->hs == 32) ? raise_attn_lds<fastk::F16T, 2, 32>() : raise_attn_lds<fastk::F16T, 2, 64>();
         } else {
             rc = build_mode<fastk::BF16T, 1>(g, m, false);
-            if (rc == MGPT_OK) rc = (g->hs == 32) ? raise_attn_lds<fastk::BF16T, 1, 32>(attn_lds) : raise_attn_lds<fastk::BF16T, 1, 64>(attn_lds);
+            if (rc == MGPT_OK) rc = (g->hs == 32) ? raise_attn_lds<fastk::BF16T, 1, 32>() : raise_attn_lds<fastk::BF16T, 1, 64>();
         }
         if (rc != MGPT_OK) { free_mode(g, m); return rc; }         // no half-built planes survive a failed build (e.g. out of memory)
     }

@@ -130,6 +130,8 @@ __global__ __launch_bounds__(256) void pack_attn256_kernel(const float *__restri
 // the y matrix, and the packed-GEMM out-projection that follows adds the residual.  A row's eight heads then run on eight CUs at
 // once instead of one after the other on one (117 -> ~30 us per attention block of a 32-row launch).  (Rounds 3-4 ran one row per
 // workgroup, all eight heads in turn; the arithmetic per token is the same, bit-identical y planes.)
+template <int NP>
+constexpr int kA256Lds = 5 * 8 * NP * 1024 + NP * (256 * 80 + 32 * 528);    // dynamic LDS (also attn256q_kernel's): 5-slot weight ring + K and V^T planes of a head
 template <class T, int NP, int ABL = 0>
 __global__ __launch_bounds__(512, 2) void attn256_kernel(const float *__restrict__ x,
                                                          const uint16_t *__restrict__ wstream, float inv_scale, float scale_log2e,

@@ -966,7 +966,9 @@ constexpr int gemm_pk_kps(int NP) { return 1; }
 // c_fc in front of it taking from the shared power budget, visit I)
 constexpr bool gemm_pk_persistent(int NP, int EPI, bool LNF) { return NP == 1 && EPI == EPI_GELU; }
 constexpr int gemm_pk_nst(int NP, int NWV = 8, int EPI = 0) { return NWV == 8 ? (NP == 2 ? 4 : 6) : (NP == 2 ? 3 : (EPI == EPI_GELU ? 4 : 6)); }
-constexpr int gemm_pk_lds(int NP, int NWV = 8, int EPI = 0) { return gemm_pk_nst(NP, NWV, EPI) * (NWV + 8) * gemm_pk_kps(NP) * NP * 1024; }   // + the Phi table when used
+constexpr int gemm_pk_lds(int NP, int NWV = 8, int EPI = 0) { return gemm_pk_nst(NP, NWV, EPI) * (NWV + 8) * gemm_pk_kps(NP) * NP * 1024; }   // + gemm_pk_lds_extra
+// ... behind the ring: the Phi table when the GELU epilogue uses it, and the three 1-KiB pieces of the folded LayerNorm (LNF, below)
+constexpr int gemm_pk_lds_extra(bool lnf, bool lut) { return (lut ? kGeluLutN * 8 : 0) + (lnf ? 3072 : 0); }
 
 // LNF (folded LayerNorm, GemmArgs): the block's 256 column sums and the (mean, rstd) of its 256 rows are three more 1-KiB pieces in LDS,
 // behind the ring and the Phi table.
@@ -1551,6 +1553,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void gemm_pk16_kernel(GemmArgs p)
 // ---------------------------------------------------------------------------------------------
 // NW waves per (row, head) workgroup: 8 (one query tile each) keeps two waves on every SIMD even when K and V^T of the
 // head fill most of LDS (hs = 64 in the split mode: 141 KiB, one workgroup per CU).
+constexpr int attn16_lds(int NP, int HS) { return NP * (256 * (HS + 8) * 2 + HS * (256 + 8) * 2); }    // dynamic LDS: K and V^T planes of a head
 template <class T, int NP, int HS, int NW = 8>
 __global__ __launch_bounds__(NW * 64) void attn16_kernel(const uint16_t *__restrict__ q_hi, const uint16_t *__restrict__ q_lo,
                                                      const uint16_t *__restrict__ k_hi, const uint16_t *__restrict__ k_lo,
@@ -1777,6 +1780,8 @@ __global__ __launch_bounds__(256) void pack_mlp_kernel(const float *__restrict__
 
 
 // (C = 64, 160: the 2M and tiny shapes; C = 256 has its own pipelined kernel in gpt_kernels_c256.h)
+// dynamic LDS of mlp_fused_kernel and mlp_fused16_kernel (gpt_kernels_fused16.h): three weight packets of a hidden tile + the Phi table
+constexpr int mlp_fused_lds(int NP, int C) { return (C / 16 + 2 * (C / 32)) * NP * 1024 * 3 + kGeluLutN * 8; }
 template <class T, int NP, int CT, int NW = 8, int NBUF = 3, int NCH = 2>
 __global__ __launch_bounds__(NW * 64, 2) void mlp_fused_kernel(float *__restrict__ x, const float *__restrict__ gain,
                                                             const uint16_t *__restrict__ wpk, float inv1, float inv2,
@@ -2130,6 +2135,7 @@ __global__ __launch_bounds__(256) void pack_cols_perm_kernel(const float *__rest
 // workgroup forms the row's LayerNorm itself, runs its head and writes that head's c_proj contribution (times the projection's
 // 1 / scale) to part_out + head * part_stride in x's own layout; x is NOT touched -- the next kernel (mlp_fused_kernel's /
 // mlp160p_kernel's fold arguments) adds the partial sums in head order.
+constexpr int attn_block_lds(int NP, int C) { return NP * (256 * 80 + 32 * 528) + (C / 16) * NP * 1024 * 4; }    // dynamic LDS: K, V^T planes + 4 weight packet slots
 template <class T, int NP, int CT, bool EMBED = false, bool HP = false>
 __global__ __launch_bounds__(512, 2) void attn_block_kernel(float *__restrict__ x, const float *__restrict__ gain,
                                                              const uint16_t *__restrict__ wpk, float inv_scale,

@@ -324,6 +324,36 @@ def test_other_shapes_take_the_generic_chain(n_head, n_embd, precision, tol):
     assert np.isfinite(logits).all() and err <= tol, f"C={n_embd} heads={n_head} {precision}: max |dlogit| = {err:.3e}"
 
 
+_ONE_LAYER_REF = {}
+
+
+def _one_layer_case(n_head, n_embd):
+    """(args, state dict, 129 token rows, their fp64 logits) of a one-layer model: computed once per shape, shared by the precisions."""
+    if (n_head, n_embd) not in _ONE_LAYER_REF:
+        args = weights.model_args(dict(n_layer=1, n_head=n_head, n_embd=n_embd))
+        sd = weights.synthetic_state_dict(args, seed=11, scale=2.0)
+        rows = np.ascontiguousarray(np.load(os.path.join(GOLDEN, "gptbig_2M_s1.npz"))["tokens"][:129])
+        _ONE_LAYER_REF[(n_head, n_embd)] = (args, sd, rows, gpt_oracle.forward_logits(sd, args, rows, dtype=torch.float64).numpy())
+    return _ONE_LAYER_REF[(n_head, n_embd)]
+
+
+@pytest.mark.parametrize("precision,tol", [("f16x3", TOL), ("bf16", 6e-2)])
+@pytest.mark.parametrize("n_head,n_embd", [(2, 64), (5, 160), (8, 256)])
+def test_one_layer_models_small_and_large_calls(n_head, n_embd, precision, tol):
+    """n_layer = 1 of the three fused shapes: layer 0 is also the last layer, so no attention block gathers the embedding or reads the
+    (position, token) table, and the whole model is the last-layer launch -- the one-launch tail in a small call (3 rows), attn_last1_kernel
+    + the MLP block on the compact rows in a large one (129 rows in one chunk).  Logits against the fp64 torch port of model.py."""
+    from mapf_gpt_amd.model import GPT, GPTConfig
+    args, sd, rows, ref = _one_layer_case(n_head, n_embd)
+    net = GPT(GPTConfig(**args), max_rows=129, precision=precision)
+    net.load_state_dict(sd)
+    for n in (3, 129):
+        logits = net.logits_tokens(torch.from_numpy(np.ascontiguousarray(rows[:n])).cuda()).cpu().numpy()
+        err = np.abs(logits - ref[:n]).max()
+        print(f"C={n_embd} heads={n_head} {precision} rows={n}: max |dlogit| = {err:.3e}")
+        assert np.isfinite(logits).all() and err <= tol, f"C={n_embd} heads={n_head} {precision} rows={n}: max |dlogit| = {err:.3e}"
+
+
 @pytest.mark.parametrize("name,precision", [("2M", "f16x3"), ("2M", "bf16"), ("tiny", "f16x3"), ("6M", "f16x3"), ("6M", "bf16")])
 def test_head_parallel_small_launch_vs_row_per_workgroup_path(name, precision):
     """Round 4: launches of <= 128 rows of the C = 64 / 160 shapes run the attention block head-parallel (one workgroup per

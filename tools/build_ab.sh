@@ -6,7 +6,8 @@ N=$1; shift
 B=/tmp/ab_build_$N; mkdir -p $B gpurun_tmp
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable -Wno-unused-but-set-variable $*"
 pids=()
-for s in prof tokenizer env gpt gpt_fast step; do
+SRCS=$(python -c "from mapf_gpt_amd.build import SOURCES; print(' '.join(s[:-4] for s in SOURCES))") || exit 1     # the translation units build.py compiles
+for s in $SRCS; do
   /opt/rocm/bin/hipcc $FLAGS -c mapf_gpt_amd/csrc/$s.hip -o $B/$s.o & pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p || exit 1; done

@@ -1,0 +1,102 @@
+"""tools/forward_digest.py <libA.so> <libB.so>  -- bit-for-bit comparison of the 16-bit forward of two builds of the library
+(the files tools/build_ab.sh writes): one SHA-256 of the output bytes per case, side by side, and a verdict.
+
+The case list is fixed here: seeded synthetic weights and tokens; every released shape, two shapes of the packed / generic chains and the
+one-layer variants; both precisions; small calls, large calls with and without a remainder chunk, an uneven persistent grid, the sequence
+forward and act_tokens.  Every (library, environment setting, model) runs in a fresh process under its own time limit; the first process that
+fails ends the run.  A refactor of the host side must leave the two columns identical.
+"""
+import hashlib
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MODELS = {  # name -> model_args
+    "tiny": "tiny", "2M": "2M", "6M": "6M", "85M": "85M",
+    "c256h4": dict(n_layer=2, n_head=4, n_embd=256), "c512h8": dict(n_layer=2, n_head=8, n_embd=512),
+    "tiny_L1": dict(n_layer=1, n_head=2, n_embd=64), "2M_L1": dict(n_layer=1, n_head=5, n_embd=160), "6M_L1": dict(n_layer=1, n_head=8, n_embd=256),
+}
+# (environment setting, models, precisions): one process each per model
+GROUPS = [({}, list(MODELS), ("f16x3", "bf16")),
+          ({"MGPT_L0_TABLE": "0"}, ["6M"], ("f16x3", "bf16")),
+          ({"MGPT_LN_FOLD": "0"}, ["85M"], ("bf16",))]
+TIME_LIMIT = 420    # seconds per process
+
+
+def child(lib_path, model, precisions):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    from mapf_gpt_amd import _lib
+    _lib.LIB_PATH = lib_path
+    from mapf_gpt_amd.model import build_model
+
+    tokens = np.random.default_rng(5).integers(0, 67, size=(600, 256), dtype=np.uint8)
+    targets = np.random.default_rng(6).integers(-1, 67, size=(130, 256), dtype=np.int64)
+    dev = torch.from_numpy(tokens).cuda()
+
+    def digest(t):
+        torch.cuda.synchronize()
+        return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+    for precision in precisions:
+        def net(max_rows):
+            return build_model(MODELS[model], seed=3, scale=2.0, max_rows=max_rows, precision=precision, envelope="ignore")
+        tag = f"{model} {precision}"
+        n = net(256)
+        for rows in (1, 40, 128, 129, 200):                       # small calls; large calls in one chunk
+            print(f"{tag} max_rows=256 rows={rows} logits {digest(n.logits_tokens(dev[:rows].contiguous()))}", flush=True)
+        for rows in (3, 130):
+            logits, _ = n.forward(dev[:rows].contiguous(), torch.from_numpy(targets[:rows]))
+            print(f"{tag} max_rows=256 rows={rows} forward_seq {digest(logits)}", flush=True)
+        for rows in (40, 200):
+            print(f"{tag} max_rows=256 rows={rows} act_tokens {digest(n.act_tokens(dev[:rows].contiguous(), do_sample=False))}", flush=True)
+        del n
+        n = net(128)
+        for rows in (129, 200):                                   # large calls in chunks of 128: remainders of 1 and 72 rows
+            print(f"{tag} max_rows=128 rows={rows} logits {digest(n.logits_tokens(dev[:rows].contiguous()))}", flush=True)
+        del n
+        if model in ("2M", "6M"):                                 # more rows than compute units, and no multiple of them
+            n = net(600)
+            print(f"{tag} max_rows=600 rows=600 logits {digest(n.logits_tokens(dev))}", flush=True)
+            del n
+
+
+def run(lib_path):
+    lib_path = os.path.abspath(lib_path)
+    name = os.path.basename(lib_path)
+    lines = []
+    for env, models, precisions in GROUPS:
+        for model in models:
+            cmd = ["timeout", "-k", "10", str(TIME_LIMIT), sys.executable, os.path.abspath(__file__), "--child", lib_path, model, ",".join(precisions)]
+            r = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True)
+            if r.returncode != 0:
+                sys.stderr.write(r.stdout + r.stderr)
+                sys.exit(f"forward_digest: {name} {env} {model}: exit status {r.returncode}; nothing more is started")
+            prefix = " ".join(f"{k}={v}" for k, v in env.items())
+            print(f"# {name} {prefix} {model}: done", file=sys.stderr, flush=True)
+            lines += [(prefix + " " + ln).strip() for ln in r.stdout.splitlines() if " " in ln and len(ln.rsplit(" ", 1)[1]) == 64]
+    return lines
+
+
+def main():
+    if len(sys.argv) >= 2 and sys.argv[1] == "--child":
+        return child(sys.argv[2], sys.argv[3], sys.argv[4].split(","))
+    if len(sys.argv) != 3:
+        sys.exit(__doc__)
+    a, b = run(sys.argv[1]), run(sys.argv[2])
+    differing = 0
+    print(f"{'case':<52} {sys.argv[1]:<64} {sys.argv[2]:<64}")
+    for la, lb in zip(a, b):
+        (ca, ha), (cb, hb) = la.rsplit(" ", 1), lb.rsplit(" ", 1)
+        same = ca == cb and ha == hb
+        differing += 0 if same else 1
+        print(f"{ca:<52} {ha} {hb}{'' if same else '  <-- DIFFERS'}")
+    differing += abs(len(a) - len(b))
+    print(f"{len(a)} / {len(b)} cases, differing {differing}")
+    sys.exit(1 if differing or not a else 0)
+
+
+if __name__ == "__main__":
+    main()
