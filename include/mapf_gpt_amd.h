@@ -390,6 +390,45 @@ int mgpt_dataset_tokenize_ex(mgpt_dataset *ds, int n_agents, int n_steps, const 
                              int only_obstacles, uint8_t *d_tokens, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Dataset builder: steps 2-3 of dataset/generate_dataset.py on rows that the bulk tokenizer above has left on the device --
+ * balance_and_filter_tensors (:65-103; sha256 of every row into a python set, then the "wait in goal" balancing loop) and the
+ * index arithmetic of its shuffles and picks.  Rows are uint8 [n][256] (16-byte aligned), labels int8 [n] in 0..5.
+ *   dedup_create:  a set for up to capacity_rows (<= 2^28) distinct rows: an open-addressing table (the power of two >= 2 x capacity
+ *           slots), the rows themselves and per-call workspace (about 300 bytes per row of capacity in all).  hash_bits 1 .. 64
+ *           masks the row hash: 64 in production, small values make tests collide.  Anything else: MGPT_ERR_ARG.
+ *   dedup_reset:   empties the set (stream-ordered).
+ *   dedup_count:   rows in the set (host value, no synchronisation).
+ *   dedup_filter:  d_first[i] = 1 iff no row of the set and no row j < i of the batch has the same 256 bytes; those rows join the
+ *           set.  The answer is exact whatever the hash does (rows that share a hash are compared byte by byte) and the same bits
+ *           on every run.  d_counts (device, may be NULL) int64 [4] = {first occurrences, duplicates, rows that shared a hash with a
+ *           different row, rows in the set afterwards}.  MGPT_ERR_ARG, before any state changes, when the set's rows + n exceed the
+ *           capacity.  MGPT_ERR_UNSUPPORTED when more rows collide than the exact pass takes (65536 per call, 4096 distinct ones
+ *           per set: not reachable with 64-bit hashes); the set is then unusable until reset (MGPT_ERR_STATE).  Synchronises
+ *           `stream` once to read the counts.
+ *   rows_workspace_bytes: size of the d_work buffer (16-byte aligned) that dataset_balance and rows_select want for n rows.
+ *   dataset_balance: the balancing loop of :80-95 in closed form over the rows with d_first != 0: with their count N, z = #(label 0) +
+ *           #(label 5) and n5 = #(label 5), k is the smallest value with k == n5 or z - k <= (N - k) / 5; the k label-5 rows of highest
+ *           index are dropped (d_keep = 0), every label 5 becomes 0 in d_labels_out (written for all n rows).  d_stats int64 [10] =
+ *           {discarded, duplicates (n - N), kept, actions_made[0..5] as the reference prints them (:96), labels outside 0..5}.
+ *   rows_select:  d_index = the positions of the non-zero bytes of d_keep in increasing order, *d_count = how many (both device; d_index
+ *           holds up to n entries).  Counting, a scan and a scatter: no atomics.
+ *   rows_gather:  d_rows_out[r] = d_rows[d_index[r]], d_labels_out[r] = d_labels[d_index[r]] (labels optional) for r < n_out; an index
+ *           outside [0, n_src) gives a zero row with label -1.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct mgpt_dedup mgpt_dedup;
+int mgpt_dedup_create(mgpt_dedup **out, int64_t capacity_rows, int hash_bits, void *stream);
+int mgpt_dedup_destroy(mgpt_dedup *set);
+int mgpt_dedup_reset(mgpt_dedup *set, void *stream);
+int mgpt_dedup_count(const mgpt_dedup *set, int64_t *rows);
+int mgpt_dedup_filter(mgpt_dedup *set, const uint8_t *d_rows, int64_t n, uint8_t *d_first, int64_t *d_counts, void *stream);
+int mgpt_rows_workspace_bytes(int64_t n, int64_t *bytes);
+int mgpt_dataset_balance(const uint8_t *d_first, const int8_t *d_labels, int64_t n, uint8_t *d_keep, int8_t *d_labels_out,
+                         int64_t *d_stats, void *d_work, void *stream);
+int mgpt_rows_select(const uint8_t *d_keep, int64_t n, int64_t *d_index, int64_t *d_count, void *d_work, void *stream);
+int mgpt_rows_gather(const uint8_t *d_rows, const int8_t *d_labels, int64_t n_src, const int64_t *d_index, int64_t n_out,
+                     uint8_t *d_rows_out, int8_t *d_labels_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Kernel timing hooks (bench.py's live roofline): when enabled, the library brackets every kernel
  * class with hipEvents on the launch stream.  mgpt_prof_read synchronises the device.
  * ------------------------------------------------------------------------------------------ */

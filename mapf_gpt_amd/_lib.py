@@ -66,6 +66,15 @@ SYMBOLS = {
     "mgpt_dataset_destroy": (_i, [_vp]),
     "mgpt_dataset_tokenize": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "mgpt_dataset_tokenize_ex": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "mgpt_dedup_create": (_i, [_pp, _i64, _i, _vp]),
+    "mgpt_dedup_destroy": (_i, [_vp]),
+    "mgpt_dedup_reset": (_i, [_vp, _vp]),
+    "mgpt_dedup_count": (_i, [_vp, ctypes.POINTER(_i64)]),
+    "mgpt_dedup_filter": (_i, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "mgpt_rows_workspace_bytes": (_i, [_i64, ctypes.POINTER(_i64)]),
+    "mgpt_dataset_balance": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "mgpt_rows_select": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "mgpt_rows_gather": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "mgpt_gpt_create": (_i, [_pp, _i, _i, _i, _i, _i]),
     "mgpt_gpt_destroy": (_i, [_vp]),
     "mgpt_gpt_set_param": (_i, [_vp, ctypes.c_char_p, _vp, _i64, _i]),

@@ -53,6 +53,7 @@ enum ProfId {
     P_HEAD, P_SAMPLE, P_PACK, P_LNQKV_FUSED,
     P_ATTN_LAST, P_GEMM_PROJ_LAST, P_MLP_FUSED_LAST,    // the last layer's launches (token 255 only, model.py:186): timed apart from the full ones
     P_HEAD_SEQ, P_SCORE,                                // ln_f + head + cross-entropy of every position (mgpt_gpt_forward_seq), last-position scoring
+    P_DS_HASH, P_DS_INSERT, P_DS_CLASSIFY, P_DS_RESOLVE, P_DS_BALANCE, P_DS_SELECT, P_DS_GATHER,   // dataset builder (dataset_build.hip)
     P_COUNT
 };
 

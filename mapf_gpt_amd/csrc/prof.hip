@@ -25,7 +25,8 @@ static const char *kProfNames[P_COUNT] = {
     "gpt_gemm_attn_proj", "gpt_gemm_mlp_fc", "gpt_gemm_mlp_proj", "gpt_mlp_fused", "gpt_head",
     "gpt_sample", "gpt_pack_weights", "gpt_ln_qkv_fused",
     "gpt_attention_last", "gpt_gemm_attn_proj_last", "gpt_mlp_fused_last",
-    "gpt_head_seq", "gpt_score"};
+    "gpt_head_seq", "gpt_score",
+    "ds_row_hash", "ds_insert", "ds_classify", "ds_resolve", "ds_balance", "ds_select", "ds_gather"};
 
 struct ProfState {
     std::mutex mu;
