@@ -21,7 +21,7 @@ constexpr int kT = 256;
 // A(m, k) = A[m * lda + k] (A_KC) or A[k * lda + m];  B(k, n) = B[k * ldb + n] (B_NC) or B[n * ldb + k].  Every index is bounds-checked,
 // so any M, N, K work.  k runs in increasing order: an fmaf chain over each 16-wide k tile, the tiles' sums added in order (a long chain
 // of K fmafs would grow the rounding error with K: the c_attn input gradient of 85M sums 2304 terms).
-enum { OUT_STORE = 0, OUT_ADD = 1, OUT_PART = 2, OUT_GELU_BWD = 3 };
+enum { OUT_STORE = 0, OUT_PART = 2, OUT_GELU_BWD = 3 };     // (the values are part of the instances' symbol names)
 
 __device__ __forceinline__ float gelu_grad(float a)
 {
@@ -90,8 +90,7 @@ __global__ __launch_bounds__(256) void gemm_tr_kernel(const float *__restrict__ 
             const int n = n0 + tx * 4 + j;
             if (n >= N) continue;
             const int64_t o = (int64_t)m * ldc + n;
-            if (OUT == OUT_ADD) dst[o] += acc[i][j];
-            else if (OUT == OUT_GELU_BWD) dst[o] = acc[i][j] * gelu_grad(aux[o]);
+            if (OUT == OUT_GELU_BWD) dst[o] = acc[i][j] * gelu_grad(aux[o]);
             else dst[o] = acc[i][j];
         }
     }
@@ -244,6 +243,12 @@ __device__ __forceinline__ float dot_lds(const float *a, const float *__restrict
     }
     return s;
 }
+
+// dynamic LDS of the two kernels below: K and V (q), or Q, dY and three statistics per query (kv), of one (row, head)
+template <int HS>
+constexpr size_t attn_bwd_q_lds() { return (size_t)2 * kT * HS * sizeof(float); }
+template <int HS>
+constexpr size_t attn_bwd_kv_lds() { return attn_bwd_q_lds<HS>() + (size_t)3 * kT * sizeof(float); }
 
 template <int HS>
 __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const float *__restrict__ qkv, int64_t plane, const float *__restrict__ Y,

@@ -1,5 +1,9 @@
 // train.hip -- training on the device (replaces train.py:324-331 with model.py:180-184 and :202-226): exact-fp32 or bf16 mixed-precision
 // forward with saved activations, backward into one fp32 gradient buffer in the layout of mgpt_gpt::params, torch's clip_grad_norm_ and AdamW.
+//
+// A call runs in chunks of the workspace's max_rows rows.  chunk_fwd_bwd is the one sequence of both precisions, its steps members of Chunk:
+// embed, layer_forward per layer, head forward and loss, head backward, layer_backward per layer in reverse, embedding backward.  The bf16
+// path reaches the shared, fp32-sized workspace through typed views (bf16_layer, bf16_grads).
 #include <string>
 #include <vector>
 
@@ -30,7 +34,10 @@ struct TrainState {
     float *grads = nullptr, *exp_avg = nullptr, *exp_avg_sq = nullptr, *steps = nullptr;    // [n_params] x 3, [n_tensors]
     std::vector<float *> X, XN1, QKV, Y, XM, XN2, A;
     float *XF = nullptr, *XNF = nullptr, *LG = nullptr, *DLG = nullptr, *NLL = nullptr;
-    float *DX = nullptr, *DXN = nullptr, *DY = nullptr, *DQKV = nullptr, *DH = nullptr, *HT = nullptr, *GP = nullptr, *AST = nullptr;
+    float *DX = nullptr, *DXN = nullptr, *DY = nullptr, *DQKV = nullptr, *DH = nullptr;
+    // fp32 path only: gelu(a), the LayerNorm gain terms, the attention statistics (bf16 keeps gelu(a) in A[l], fuses the gain sums and keeps
+    // its statistics in Y[l]: bf16_layer)
+    float *HT = nullptr, *GP = nullptr, *AST = nullptr;
     float *part = nullptr;                  // weight-gradient / gain / embedding slabs
     size_t part_elems = 0;
     int32_t *cnt = nullptr;                 // [0] targeted positions of the call, [1] invalid-target flag
@@ -89,306 +96,302 @@ std::vector<TensorInfo> tensor_table(const mgpt_gpt *g)
     return t;
 }
 
+// a failed step ends the sequence with its code
+#define MGPT_TRY(call) do { const int rc__ = (call); if (rc__ != MGPT_OK) return rc__; } while (0)
+// a launch and its MGPT_LAUNCH_CHECK
+#define MGPT_LAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); MGPT_LAUNCH_CHECK(); } while (0)
+
+// weight-gradient, gain and embedding partials: slabs of tokens, `align`-token aligned (16: the fp32 kernels' k tile, 32: one bf16 MFMA's k)
 int slabs_of(int64_t M) { return (int)std::min<int64_t>(kMaxSlabs, std::max<int64_t>(1, cdiv64(M, kSlabTokens))); }
-int slab_tokens(int64_t M) { const int S = slabs_of(M); return (int)((cdiv64(M, S) + 15) / 16 * 16); }
+int slab_tokens(int64_t M, int align) { return (int)((cdiv64(M, slabs_of(M)) + align - 1) / align * align); }
 
 unsigned grid_1d(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv64(n, 256), 8192)); }
 
-// ----- backward pieces -----
-// out[M][N] (op)= A'(M x K) @ B'(K x N) over all K
-template <bool A_KC, bool B_NC, int OUT>
-int tr_gemm(const float *A, int64_t lda, const float *B, int64_t ldb, float *out, int64_t ldc, int64_t M, int N, int K, hipStream_t s,
-            const float *aux = nullptr)
+// ----- the bf16 path's views of the workspace -----
+// Both precisions share one workspace, sized for fp32 (TrainState).  A bf16 chunk of M tokens (M <= t->M) keeps its 16-bit tensors at the
+// start of the fp32 buffers of the same role:
+//   QKV[l] (3 M C floats)  the bf16 q | k | v planes, M C elements each;
+//   Y[l]   (M C floats)    bf16 y, M C elements = M C / 2 floats, then the softmax statistics, 2 n_head floats per token.  They fit
+//                          because 2 n_head <= C / 2 (any head size >= 4);
+//   A[l]   (4 M C floats)  bf16 a, then bf16 gelu(a), 4 M C elements each: two bf16 per float, the whole buffer;
+//   DY, DH (M C, 4 M C)    the bf16 gradients of y and of a, the first half of each.
+// mgpt_gpt_train_alloc checks the two claims once; no layer body casts or offsets a buffer itself.
+struct Bf16Layer { uint16_t *qkv, *y; float *stats; uint16_t *a, *h; };
+struct Bf16Grads { uint16_t *dy, *da; };
+
+Bf16Layer bf16_layer(const TrainState *t, int l, int64_t M, int C)
 {
-    const dim3 grid((unsigned)cdiv(N, 64), (unsigned)cdiv64(M, 64), 1);
-    hipLaunchKernelGGL((trk::gemm_tr_kernel<A_KC, B_NC, OUT>), grid, dim3(256), 0, s, A, lda, B, ldb, out, ldc, (int)M, N, K, K, aux);
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
+    uint16_t *y = reinterpret_cast<uint16_t *>(t->Y[l]), *a = reinterpret_cast<uint16_t *>(t->A[l]);
+    return {reinterpret_cast<uint16_t *>(t->QKV[l]), y, reinterpret_cast<float *>(y + M * C), a, a + 4 * M * C};
 }
 
-// dW[Nout][Kin] += dY^T @ X over Mtok tokens: dY [Mtok][Nout], X [Mtok][Kin]; slabs of tokens, summed in order
-int weight_grad(TrainState *t, const float *dY, const float *X, float *dW, int Nout, int Kin, int64_t Mtok, hipStream_t s)
+Bf16Grads bf16_grads(const TrainState *t) { return {reinterpret_cast<uint16_t *>(t->DY), reinterpret_cast<uint16_t *>(t->DH)}; }
+
+// ----- epilogue arguments of gemm_bf16_kernel, one constructor per kind (the fields a kind does not read stay zero) -----
+tbk::Epi epi_f32(float *out, int64_t ldc) { tbk::Epi e; e.f32 = out; e.ldc = ldc; return e; }                              // E_F32, E_PART
+tbk::Epi epi_resid(float *out, const float *res, int64_t ldc) { tbk::Epi e = epi_f32(out, ldc); e.res = res; return e; }    // E_RESID
+tbk::Epi epi_b16(uint16_t *out, int64_t ldc) { tbk::Epi e; e.b16 = out; e.ldc = ldc; return e; }                            // E_B16
+tbk::Epi epi_fc(uint16_t *a, uint16_t *h, int64_t ldc) { tbk::Epi e = epi_b16(a, ldc); e.b16b = h; return e; }              // E_FC
+tbk::Epi epi_gelu_bwd(uint16_t *da, const uint16_t *a, int64_t ldc) { tbk::Epi e = epi_b16(da, ldc); e.aux = a; return e; }  // E_GELU_BWD
+tbk::Epi epi_qkv(uint16_t *planes, int C, int hs, int n_head, int64_t plane)                                                // E_QKV
 {
-    const int S = slabs_of(Mtok), kps = slab_tokens(Mtok);
-    MGPT_REQUIRE((size_t)S * Nout * Kin <= t->part_elems, MGPT_ERR_ARG, "weight-gradient slabs exceed the workspace");
-    const dim3 grid((unsigned)cdiv(Kin, 64), (unsigned)cdiv(Nout, 64), (unsigned)S);
-    hipLaunchKernelGGL((trk::gemm_tr_kernel<false, true, trk::OUT_PART>), grid, dim3(256), 0, s, dY, (int64_t)Nout, X, (int64_t)Kin, t->part,
-                       (int64_t)Kin, Nout, Kin, (int)Mtok, kps, (const float *)nullptr);
-    MGPT_LAUNCH_CHECK();
-    const int64_t n = (int64_t)Nout * Kin;
-    hipLaunchKernelGGL(trk::slab_reduce_kernel, dim3(grid_1d(n)), dim3(256), 0, s, t->part, S, n, dW);
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
+    tbk::Epi e;
+    e.b16 = planes; e.C = C; e.hs = hs; e.n_head = n_head; e.plane = plane;
+    return e;
 }
 
-// LayerNorm backward: dres (+)= d x, gain gradient += sum_m dxn * xhat
-template <bool ADD>
-int ln_backward(TrainState *t, const float *x, const float *w, const float *dxn, float *dres, float *gw, int64_t Mtok, int C, hipStream_t s)
-{
-    hipLaunchKernelGGL((trk::ln_bwd_kernel<ADD>), dim3((unsigned)cdiv64(Mtok, 4)), dim3(256), 0, s, x, w, dxn, dres, t->GP, Mtok, C);
-    MGPT_LAUNCH_CHECK();
-    const int S = slabs_of(Mtok), kps = slab_tokens(Mtok);
-    hipLaunchKernelGGL(trk::colsum_part_kernel, dim3((unsigned)cdiv(C, 256), (unsigned)S), dim3(256), 0, s, t->GP, Mtok, C, kps, t->part);
-    MGPT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(trk::slab_reduce_kernel, dim3(grid_1d(C)), dim3(256), 0, s, t->part, S, (int64_t)C, gw);
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
-}
-
+// the attention kernels' dynamic LDS exceeds the default limit: raised once per workspace (mgpt_gpt_train_alloc), for the model's head size
 template <int HS>
-int attn_backward(mgpt_gpt *g, TrainState *t, const float *qkv, int64_t plane, const float *Y, int rows, float scale, hipStream_t s)
+int raise_attn_lds()
 {
-    const size_t lds_q = (size_t)2 * kT * HS * sizeof(float), lds_kv = lds_q + (size_t)3 * kT * sizeof(float);
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&trk::attn_bwd_q_kernel<HS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&trk::attn_bwd_kv_kernel<HS, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv));
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&trk::attn_bwd_kv_kernel<HS, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv));
-    const dim3 grid((unsigned)(rows * g->nh));
-    hipLaunchKernelGGL(trk::attn_bwd_q_kernel<HS>, grid, dim3(256), lds_q, s, qkv, plane, Y, (const float *)t->DY, t->DQKV, t->AST, g->nh, scale);
-    MGPT_LAUNCH_CHECK();
-    hipLaunchKernelGGL((trk::attn_bwd_kv_kernel<HS, 0>), grid, dim3(256), lds_kv, s, qkv, plane, (const float *)t->DY, t->DQKV, (const float *)t->AST, g->nh, scale);
-    MGPT_LAUNCH_CHECK();
-    hipLaunchKernelGGL((trk::attn_bwd_kv_kernel<HS, 1>), grid, dim3(256), lds_kv, s, qkv, plane, (const float *)t->DY, t->DQKV, (const float *)t->AST, g->nh, scale);
-    MGPT_LAUNCH_CHECK();
+    const std::pair<const void *, size_t> kernels[] = {
+        {reinterpret_cast<const void *>(&trk::attn_bwd_q_kernel<HS>), trk::attn_bwd_q_lds<HS>()},
+        {reinterpret_cast<const void *>(&trk::attn_bwd_kv_kernel<HS, 0>), trk::attn_bwd_kv_lds<HS>()},
+        {reinterpret_cast<const void *>(&trk::attn_bwd_kv_kernel<HS, 1>), trk::attn_bwd_kv_lds<HS>()},
+        {reinterpret_cast<const void *>(&tbk::attn_fwd_bf16_kernel<HS>), tbk::attn_fwd_lds<HS>()},
+        {reinterpret_cast<const void *>(&tbk::attn_bwd_bf16_kernel<HS>), tbk::attn_bwd_lds<HS>()}};
+    for (const auto &k : kernels) MGPT_HIP(hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.second));
     return MGPT_OK;
 }
 
-// one chunk of rows: forward with saved activations, cross-entropy against the call's target count, backward into t->grads
-int chunk_fwd_bwd(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows, const int32_t *tg, float loss_scale, hipStream_t s)
-{
+// One chunk of rows of a call: what its launches share, and the launches (chunk_fwd_bwd is the sequence).  Only layer_forward,
+// layer_backward and ln_backward have a body per precision; the head and the embedding run the fp32 kernels in both.  bf16 (MGPT_PREC_BF16)
+// is train.py's autocast regime on bf16 MFMAs (gpt_kernels_train_bf16.h).  Rounded to bf16, as autocast holds them: the operands of the
+// block linears, q, k, v, attention's output and its gradient, P and dS, the linears' outputs and GELU's, the gradients of the MLP hidden
+// tensors.  fp32: the embedding sum, the residual stream and its gradient, LayerNorm, softmax statistics, the head, cross-entropy and every
+// accumulator.
+struct Chunk {
+    mgpt_gpt *g;
+    TrainState *t;
+    const uint8_t *tok;
+    const int32_t *tg;
+    int rows;
+    float loss_scale;
+    bool bf16;
+    hipStream_t s;
     const int C = g->C, L = g->L;
     const int64_t M = (int64_t)rows * kT;
     const float *P = g->params;
     float *G = t->grads;
-    int rc;
-    if ((rc = gpt_f32_embed(g, tok, t->X[0], M, s)) != MGPT_OK) return rc;
     const float scale = 1.0f / sqrtf((float)g->hs);
-    for (int l = 0; l < L; l++) {
-        const LayerOff &lo = g->layers[l];
-        float *x = t->X[l], *xm = t->XM[l], *xo = (l + 1 < L) ? t->X[l + 1] : t->XF;
-        if ((rc = gpt_f32_layernorm(g, x, P + lo.ln1, t->XN1[l], M, s)) != MGPT_OK) return rc;
-        if ((rc = gpt_f32_linear(g, 2, t->XN1[l], P + lo.attn_w, t->QKV[l], M, 3 * C, C, s)) != MGPT_OK) return rc;
-        if ((rc = gpt_f32_attention(g, t->QKV[l], t->Y[l], rows, s)) != MGPT_OK) return rc;
-        MGPT_HIP(hipMemcpyAsync(xm, x, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if ((rc = gpt_f32_linear(g, 1, t->Y[l], P + lo.proj_w, xm, M, C, C, s)) != MGPT_OK) return rc;
-        if ((rc = gpt_f32_layernorm(g, xm, P + lo.ln2, t->XN2[l], M, s)) != MGPT_OK) return rc;
-        if ((rc = gpt_f32_linear(g, 0, t->XN2[l], P + lo.fc_w, t->A[l], M, 4 * C, C, s)) != MGPT_OK) return rc;
-        hipLaunchKernelGGL(trk::gelu_kernel, dim3(grid_1d(4 * M * C)), dim3(256), 0, s, (const float *)t->A[l], t->HT, 4 * M * C);
-        MGPT_LAUNCH_CHECK();
-        MGPT_HIP(hipMemcpyAsync(xo, xm, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if ((rc = gpt_f32_linear(g, 1, t->HT, P + lo.proj2_w, xo, M, C, 4 * C, s)) != MGPT_OK) return rc;
+
+    float *x_out(int l) const { return l + 1 < L ? t->X[l + 1] : t->XF; }
+
+    // out[m][N] (op)= A'(m x K) @ B'(K x N), fp32 on the VALU; slabs > 1: one partial per kps of K
+    template <bool A_KC, bool B_NC, int OUT>
+    int tr_gemm(const float *A, int64_t lda, const float *B, int64_t ldb, float *out, int64_t ldc, int64_t m, int N, int K, const float *aux = nullptr,
+                int slabs = 1, int kps = 0)
+    {
+        const dim3 grid((unsigned)cdiv(N, 64), (unsigned)cdiv64(m, 64), (unsigned)slabs);
+        MGPT_LAUNCH((trk::gemm_tr_kernel<A_KC, B_NC, OUT>), grid, dim3(256), 0, s, A, lda, B, ldb, out, ldc, (int)m, N, K, slabs == 1 ? K : kps, aux);
+        return MGPT_OK;
     }
-    // head (model.py:178-184): ln_f, logits = ln_f(x) @ wte^T at every position, cross-entropy
-    if ((rc = gpt_f32_layernorm(g, t->XF, P + g->off_lnf, t->XNF, M, s)) != MGPT_OK) return rc;
-    if ((rc = tr_gemm<true, false, trk::OUT_STORE>(t->XNF, C, P + g->off_wte, C, t->LG, kV, M, kV, C, s)) != MGPT_OK) return rc;
-    hipLaunchKernelGGL(trk::ce_kernel, dim3((unsigned)cdiv64(M, 256)), dim3(256), 0, s, (const float *)t->LG, tg, M, (const int32_t *)t->cnt,
-                       loss_scale, t->DLG, t->NLL);
-    MGPT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(trk::sum_acc_kernel, dim3(1), dim3(256), 0, s, (const float *)t->NLL, M, t->loss_acc);
-    MGPT_LAUNCH_CHECK();
-    // d ln_f(x) = dlogits @ wte;  d wte += dlogits^T @ ln_f(x) (the tied lm_head);  ln_f backward starts the residual gradient
-    if ((rc = tr_gemm<true, true, trk::OUT_STORE>(t->DLG, kV, P + g->off_wte, C, t->DXN, C, M, C, kV, s)) != MGPT_OK) return rc;
-    if ((rc = weight_grad(t, t->DLG, t->XNF, G + g->off_wte, kV, C, M, s)) != MGPT_OK) return rc;
-    if ((rc = ln_backward<false>(t, t->XF, P + g->off_lnf, t->DXN, t->DX, G + g->off_lnf, M, C, s)) != MGPT_OK) return rc;
-    for (int l = L - 1; l >= 0; l--) {
+
+    // ... on bf16 MFMAs, the output named by the epilogue
+    template <typename TA, bool A_KC, typename TB, bool B_KC, int EPI>
+    int bf_gemm(const TA *A, int64_t lda, const TB *B, int64_t ldb, int64_t m, int N, int K, const tbk::Epi &ep, int slabs = 1, int kps = 0)
+    {
+        if (slabs == 1) kps = K;
+        MGPT_REQUIRE(m % 16 == 0 && N % 16 == 0 && K % 32 == 0 && kps % 32 == 0 && m <= INT32_MAX, MGPT_ERR_UNSUPPORTED,
+                     "bf16 gemm shape M=%lld N=%d K=%d (slab %d)", (long long)m, N, K, kps);
+        const dim3 grid((unsigned)cdiv(N, tbk::BN), (unsigned)cdiv64(m, tbk::BM), (unsigned)slabs);
+        MGPT_LAUNCH((tbk::gemm_bf16_kernel<TA, A_KC, TB, B_KC, EPI>), grid, dim3(256), 0, s, A, lda, B, ldb, (int)m, N, K, kps, ep);
+        return MGPT_OK;
+    }
+
+    // ----- sums over the chunk's tokens by slabs: partials(S, kps) launches S partial sums of kps tokens each into t->part [S][n], which are
+    // added to out[n] in order -----
+    template <class Launch>
+    int slab_sum(float *out, int64_t n, int align, Launch partials)
+    {
+        const int S = slabs_of(M), kps = slab_tokens(M, align);
+        MGPT_REQUIRE((size_t)S * n <= t->part_elems, MGPT_ERR_ARG, "weight-gradient slabs exceed the workspace");
+        MGPT_TRY(partials(S, kps));
+        MGPT_LAUNCH(trk::slab_reduce_kernel, dim3(grid_1d(n)), dim3(256), 0, s, t->part, S, n, out);
+        return MGPT_OK;
+    }
+
+    // weight gradients: dW[Nout][Kin] += dY^T @ X, dY [M][Nout], X [M][Kin]; fp32 on the VALU, or bf16 MFMAs (32-token aligned slabs)
+    int weight_grad(const float *dY, const float *X, float *dW, int Nout, int Kin)
+    {
+        return slab_sum(dW, (int64_t)Nout * Kin, 16, [&](int S, int kps) -> int {
+            return tr_gemm<false, true, trk::OUT_PART>(dY, Nout, X, Kin, t->part, Kin, Nout, Kin, (int)M, nullptr, S, kps);
+        });
+    }
+
+    template <typename TY, typename TX>
+    int weight_grad_bf16(const TY *dY, const TX *X, float *dW, int Nout, int Kin)
+    {
+        return slab_sum(dW, (int64_t)Nout * Kin, 32, [&](int S, int kps) -> int {
+            return bf_gemm<TY, false, TX, false, tbk::E_PART>(dY, Nout, X, Kin, Nout, Kin, (int)M, epi_f32(t->part, Kin), S, kps);
+        });
+    }
+
+    // ----- LayerNorm backward: DX (+)= d x from DXN, the gain's gradient gw += sum over the tokens of dxn * xhat -----
+    template <bool ADD>
+    int ln_backward_f32(const float *x, const float *w, float *gw)
+    {
+        MGPT_LAUNCH((trk::ln_bwd_kernel<ADD>), dim3((unsigned)cdiv64(M, 4)), dim3(256), 0, s, x, w, t->DXN, t->DX, t->GP, M, C);
+        return slab_sum(gw, C, 16, [&](int S, int kps) -> int {
+            MGPT_LAUNCH(trk::colsum_part_kernel, dim3((unsigned)cdiv(C, 256), (unsigned)S), dim3(256), 0, s, t->GP, M, C, kps, t->part);
+            return MGPT_OK;
+        });
+    }
+
+    // ... with the gain's column sums fused: one partial per 128 tokens, summed in order
+    template <bool ADD>
+    int ln_backward_bf16(const float *x, const float *w, float *gw)
+    {
+        const int64_t n_part = cdiv64(M, tbk::kLnTok);
+        MGPT_REQUIRE(C <= 64 * tbk::kLnMaxJ && (size_t)(n_part * C) <= t->part_elems, MGPT_ERR_UNSUPPORTED, "LayerNorm backward: C=%d, %lld tokens", C, (long long)M);
+        MGPT_LAUNCH((tbk::ln_bwd_gain_kernel<ADD>), dim3((unsigned)n_part), dim3(256), 0, s, x, w, t->DXN, t->DX, t->part, M, C);
+        MGPT_LAUNCH(tbk::colsum_reduce_kernel, dim3((unsigned)cdiv(C, 64)), dim3(1024), 0, s, t->part, (int)n_part, C, gw);
+        return MGPT_OK;
+    }
+
+    template <bool ADD>
+    int ln_backward(const float *x, size_t gain) { return bf16 ? ln_backward_bf16<ADD>(x, P + gain, G + gain) : ln_backward_f32<ADD>(x, P + gain, G + gain); }
+
+    // ----- attention, one workgroup per (row, head) -----
+    // fp32 backward: dq | dk | dv of DY into DQKV
+    template <int HS>
+    int attn_backward_f32(const float *qkv, const float *y)
+    {
+        const dim3 grid((unsigned)(rows * g->nh));
+        const int64_t plane = M * C;
+        MGPT_LAUNCH(trk::attn_bwd_q_kernel<HS>, grid, dim3(256), trk::attn_bwd_q_lds<HS>(), s, qkv, plane, y, t->DY, t->DQKV, t->AST, g->nh, scale);
+        MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 0>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale);
+        MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 1>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale);
+        return MGPT_OK;
+    }
+
+    // bf16 MFMAs: forward (y bf16, statistics fp32) and backward (dq | dk | dv fp32 into DQKV)
+    template <int HS>
+    int attn_forward_bf16(const Bf16Layer &v)
+    {
+        MGPT_LAUNCH(tbk::attn_fwd_bf16_kernel<HS>, dim3((unsigned)(rows * g->nh)), dim3(256), tbk::attn_fwd_lds<HS>(), s, v.qkv, M * C, v.y, v.stats, g->nh, scale);
+        return MGPT_OK;
+    }
+
+    template <int HS>
+    int attn_backward_bf16(const Bf16Layer &v, const uint16_t *dy)
+    {
+        MGPT_LAUNCH(tbk::attn_bwd_bf16_kernel<HS>, dim3((unsigned)(rows * g->nh)), dim3(512), tbk::attn_bwd_lds<HS>(), s, v.qkv, M * C, v.y, dy, v.stats, t->DQKV,
+                    g->nh, scale);
+        return MGPT_OK;
+    }
+
+    int layer_forward_f32(int l)
+    {
+        const LayerOff &lo = g->layers[l];
+        float *x = t->X[l], *xm = t->XM[l], *xo = x_out(l);
+        MGPT_TRY(gpt_f32_layernorm(g, x, P + lo.ln1, t->XN1[l], M, s));
+        MGPT_TRY(gpt_f32_linear(g, 2, t->XN1[l], P + lo.attn_w, t->QKV[l], M, 3 * C, C, s));
+        MGPT_TRY(gpt_f32_attention(g, t->QKV[l], t->Y[l], rows, s));
+        MGPT_HIP(hipMemcpyAsync(xm, x, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+        MGPT_TRY(gpt_f32_linear(g, 1, t->Y[l], P + lo.proj_w, xm, M, C, C, s));
+        MGPT_TRY(gpt_f32_layernorm(g, xm, P + lo.ln2, t->XN2[l], M, s));
+        MGPT_TRY(gpt_f32_linear(g, 0, t->XN2[l], P + lo.fc_w, t->A[l], M, 4 * C, C, s));
+        MGPT_LAUNCH(trk::gelu_kernel, dim3(grid_1d(4 * M * C)), dim3(256), 0, s, t->A[l], t->HT, 4 * M * C);
+        MGPT_HIP(hipMemcpyAsync(xo, xm, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return gpt_f32_linear(g, 1, t->HT, P + lo.proj2_w, xo, M, C, 4 * C, s);
+    }
+
+    int layer_forward_bf16(int l)
+    {
+        const LayerOff &lo = g->layers[l];
+        const Bf16Layer v = bf16_layer(t, l, M, C);
+        float *x = t->X[l], *xm = t->XM[l];
+        MGPT_TRY(gpt_f32_layernorm(g, x, P + lo.ln1, t->XN1[l], M, s));
+        MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_QKV>(t->XN1[l], C, P + lo.attn_w, C, M, 3 * C, C, epi_qkv(v.qkv, C, g->hs, g->nh, M * C))));
+        MGPT_TRY(g->hs == 32 ? attn_forward_bf16<32>(v) : attn_forward_bf16<64>(v));
+        MGPT_TRY((bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(v.y, C, P + lo.proj_w, C, M, C, C, epi_resid(xm, x, C))));
+        MGPT_TRY(gpt_f32_layernorm(g, xm, P + lo.ln2, t->XN2[l], M, s));
+        MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_FC>(t->XN2[l], C, P + lo.fc_w, C, M, 4 * C, C, epi_fc(v.a, v.h, 4 * C))));
+        return bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(v.h, 4 * C, P + lo.proj2_w, 4 * C, M, C, 4 * C, epi_resid(x_out(l), xm, C));
+    }
+
+    // head (model.py:178-184), fp32 in both precisions: ln_f, logits = ln_f(x) @ wte^T at every position, cross-entropy
+    int head_forward()
+    {
+        MGPT_TRY(gpt_f32_layernorm(g, t->XF, P + g->off_lnf, t->XNF, M, s));
+        MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(t->XNF, C, P + g->off_wte, C, t->LG, kV, M, kV, C)));
+        MGPT_LAUNCH(trk::ce_kernel, dim3((unsigned)cdiv64(M, 256)), dim3(256), 0, s, t->LG, tg, M, t->cnt, loss_scale, t->DLG, t->NLL);
+        MGPT_LAUNCH(trk::sum_acc_kernel, dim3(1), dim3(256), 0, s, t->NLL, M, t->loss_acc);
+        return MGPT_OK;
+    }
+
+    // d ln_f(x) = dlogits @ wte;  d wte += dlogits^T @ ln_f(x) (the tied lm_head);  ln_f backward starts the residual gradient DX
+    int head_backward()
+    {
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DLG, kV, P + g->off_wte, C, t->DXN, C, M, C, kV)));
+        MGPT_TRY(weight_grad(t->DLG, t->XNF, G + g->off_wte, kV, C));
+        return ln_backward<false>(t->XF, g->off_lnf);
+    }
+
+    int layer_backward_f32(int l)
+    {
         const LayerOff &lo = g->layers[l];
         // MLP (model.py:85-87,103): DX = d x_out
-        if ((rc = tr_gemm<true, true, trk::OUT_GELU_BWD>(t->DX, C, P + lo.proj2_w, 4 * C, t->DH, 4 * C, M, 4 * C, C, s, t->A[l])) != MGPT_OK) return rc;
-        hipLaunchKernelGGL(trk::gelu_kernel, dim3(grid_1d(4 * M * C)), dim3(256), 0, s, (const float *)t->A[l], t->HT, 4 * M * C);
-        MGPT_LAUNCH_CHECK();
-        if ((rc = weight_grad(t, t->DX, t->HT, G + lo.proj2_w, C, 4 * C, M, s)) != MGPT_OK) return rc;
-        if ((rc = tr_gemm<true, true, trk::OUT_STORE>(t->DH, 4 * C, P + lo.fc_w, C, t->DXN, C, M, C, 4 * C, s)) != MGPT_OK) return rc;
-        if ((rc = weight_grad(t, t->DH, t->XN2[l], G + lo.fc_w, 4 * C, C, M, s)) != MGPT_OK) return rc;
-        if ((rc = ln_backward<true>(t, t->XM[l], P + lo.ln2, t->DXN, t->DX, G + lo.ln2, M, C, s)) != MGPT_OK) return rc;
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_GELU_BWD>(t->DX, C, P + lo.proj2_w, 4 * C, t->DH, 4 * C, M, 4 * C, C, t->A[l])));
+        MGPT_LAUNCH(trk::gelu_kernel, dim3(grid_1d(4 * M * C)), dim3(256), 0, s, t->A[l], t->HT, 4 * M * C);
+        MGPT_TRY(weight_grad(t->DX, t->HT, G + lo.proj2_w, C, 4 * C));
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DH, 4 * C, P + lo.fc_w, C, t->DXN, C, M, C, 4 * C)));
+        MGPT_TRY(weight_grad(t->DH, t->XN2[l], G + lo.fc_w, 4 * C, C));
+        MGPT_TRY(ln_backward<true>(t->XM[l], lo.ln2));
         // attention (model.py:50-71,102): DX = d x_mid
-        if ((rc = tr_gemm<true, true, trk::OUT_STORE>(t->DX, C, P + lo.proj_w, C, t->DY, C, M, C, C, s)) != MGPT_OK) return rc;
-        if ((rc = weight_grad(t, t->DX, t->Y[l], G + lo.proj_w, C, C, M, s)) != MGPT_OK) return rc;
-        rc = g->hs == 32 ? attn_backward<32>(g, t, t->QKV[l], M * C, t->Y[l], rows, scale, s)
-                         : attn_backward<64>(g, t, t->QKV[l], M * C, t->Y[l], rows, scale, s);
-        if (rc != MGPT_OK) return rc;
-        if ((rc = tr_gemm<true, true, trk::OUT_STORE>(t->DQKV, 3 * C, P + lo.attn_w, C, t->DXN, C, M, C, 3 * C, s)) != MGPT_OK) return rc;
-        if ((rc = weight_grad(t, t->DQKV, t->XN1[l], G + lo.attn_w, 3 * C, C, M, s)) != MGPT_OK) return rc;
-        if ((rc = ln_backward<true>(t, t->X[l], P + lo.ln1, t->DXN, t->DX, G + lo.ln1, M, C, s)) != MGPT_OK) return rc;
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DX, C, P + lo.proj_w, C, t->DY, C, M, C, C)));
+        MGPT_TRY(weight_grad(t->DX, t->Y[l], G + lo.proj_w, C, C));
+        MGPT_TRY(g->hs == 32 ? attn_backward_f32<32>(t->QKV[l], t->Y[l]) : attn_backward_f32<64>(t->QKV[l], t->Y[l]));
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DQKV, 3 * C, P + lo.attn_w, C, t->DXN, C, M, C, 3 * C)));
+        MGPT_TRY(weight_grad(t->DQKV, t->XN1[l], G + lo.attn_w, 3 * C, C));
+        return ln_backward<true>(t->X[l], lo.ln1);
     }
-    // embedding (model.py:171-175): d wpe[t] += sum over rows, d wte[id] += sum over the tokens with that id
-    hipLaunchKernelGGL(trk::wpe_bwd_kernel, dim3((unsigned)cdiv64((int64_t)kT * C, 256)), dim3(256), 0, s, (const float *)t->DX, rows, C, G + g->off_wpe);
-    MGPT_LAUNCH_CHECK();
+
+    int layer_backward_bf16(int l)
     {
-        const int S = slabs_of(M), kps = slab_tokens(M);
-        hipLaunchKernelGGL(trk::wte_bwd_part_kernel, dim3(kV, (unsigned)S), dim3(256), 0, s, tok, (const float *)t->DX, M, C, kps, t->part);
-        MGPT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(trk::slab_reduce_kernel, dim3(grid_1d((int64_t)kV * C)), dim3(256), 0, s, t->part, S, (int64_t)kV * C, G + g->off_wte);
-        MGPT_LAUNCH_CHECK();
-    }
-    return MGPT_OK;
-}
-
-// ----- bf16 mixed precision (MGPT_PREC_BF16): the matrix products of the five linears on bf16 MFMAs (gpt_kernels_train_bf16.h) -----
-int gemm_bf16_check(int64_t M, int N, int K, int kps)
-{
-    MGPT_REQUIRE(M % 16 == 0 && N % 16 == 0 && K % 32 == 0 && kps % 32 == 0 && M <= INT32_MAX, MGPT_ERR_UNSUPPORTED,
-                 "bf16 gemm shape M=%lld N=%d K=%d (slab %d)", (long long)M, N, K, kps);
-    return MGPT_OK;
-}
-
-template <typename TA, bool A_KC, typename TB, bool B_KC, int EPI>
-int bf_gemm(const TA *A, int64_t lda, const TB *B, int64_t ldb, int64_t M, int N, int K, const tbk::Epi &ep, hipStream_t s, int slabs = 1,
-            int kps = 0)
-{
-    if (slabs == 1) kps = K;
-    const int rc = gemm_bf16_check(M, N, K, kps);
-    if (rc != MGPT_OK) return rc;
-    const dim3 grid((unsigned)cdiv(N, tbk::BN), (unsigned)cdiv64(M, tbk::BM), (unsigned)slabs);
-    hipLaunchKernelGGL((tbk::gemm_bf16_kernel<TA, A_KC, TB, B_KC, EPI>), grid, dim3(256), 0, s, A, lda, B, ldb, (int)M, N, K, kps, ep);
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
-}
-
-// dW[Nout][Kin] += dY^T @ X over Mtok tokens on bf16 MFMAs: fp32 partials per token slab (the slabs of weight_grad, 32-token aligned), summed in order
-template <typename TY, typename TX>
-int weight_grad_bf16(TrainState *t, const TY *dY, const TX *X, float *dW, int Nout, int Kin, int64_t Mtok, hipStream_t s)
-{
-    const int S = slabs_of(Mtok), kps = (int)((cdiv64(Mtok, S) + 31) / 32 * 32);
-    MGPT_REQUIRE((size_t)S * Nout * Kin <= t->part_elems, MGPT_ERR_ARG, "weight-gradient slabs exceed the workspace");
-    tbk::Epi ep;
-    ep.f32 = t->part;
-    ep.ldc = Kin;
-    int rc = bf_gemm<TY, false, TX, false, tbk::E_PART>(dY, Nout, X, Kin, Nout, Kin, (int)Mtok, ep, s, S, kps);
-    if (rc != MGPT_OK) return rc;
-    const int64_t n = (int64_t)Nout * Kin;
-    hipLaunchKernelGGL(trk::slab_reduce_kernel, dim3(grid_1d(n)), dim3(256), 0, s, (const float *)t->part, S, n, dW);
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
-}
-
-// LayerNorm backward with the gain's column sums fused: one partial per 128 tokens, summed in order
-template <bool ADD>
-int ln_backward_bf16(TrainState *t, const float *x, const float *w, const float *dxn, float *dres, float *gw, int64_t Mtok, int C, hipStream_t s)
-{
-    const int64_t P = cdiv64(Mtok, tbk::kLnTok);
-    MGPT_REQUIRE(C <= 64 * tbk::kLnMaxJ && (size_t)(P * C) <= t->part_elems, MGPT_ERR_UNSUPPORTED, "LayerNorm backward: C=%d, %lld tokens", C,
-                 (long long)Mtok);
-    hipLaunchKernelGGL((tbk::ln_bwd_gain_kernel<ADD>), dim3((unsigned)P), dim3(256), 0, s, x, w, dxn, dres, t->part, Mtok, C);
-    MGPT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tbk::colsum_reduce_kernel, dim3((unsigned)cdiv(C, 64)), dim3(1024), 0, s, (const float *)t->part, (int)P, C, gw);
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
-}
-
-// attention on bf16 MFMAs: forward (y bf16, statistics fp32) and backward (dq | dk | dv fp32 into t->DQKV)
-template <int HS>
-int attn_bf16(const uint16_t *qkv, int64_t plane, uint16_t *y, float *stats, int rows, int n_head, float scale, hipStream_t s)
-{
-    const size_t lds = tbk::attn_fwd_lds<HS>();
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tbk::attn_fwd_bf16_kernel<HS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(tbk::attn_fwd_bf16_kernel<HS>, dim3((unsigned)(rows * n_head)), dim3(256), lds, s, qkv, plane, y, stats, n_head, scale);
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
-}
-
-template <int HS>
-int attn_bwd_bf16(TrainState *t, const uint16_t *qkv, int64_t plane, const uint16_t *y, const uint16_t *dy, const float *stats, int rows,
-                  int n_head, float scale, hipStream_t s)
-{
-    const size_t lds = tbk::attn_bwd_lds<HS>();
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&tbk::attn_bwd_bf16_kernel<HS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(tbk::attn_bwd_bf16_kernel<HS>, dim3((unsigned)(rows * n_head)), dim3(512), lds, s, qkv, plane, y, dy, stats, t->DQKV,
-                       n_head, scale);
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
-}
-
-// one chunk of rows in train.py's autocast regime.  Rounded to bf16 (as autocast holds them): the operands of the five linears -- the head's
-// excepted, which stays fp32 --, q, k, v, attention's output and its gradient, P and dS, the linears' outputs and GELU's, the gradients of the
-// MLP hidden tensors.  fp32: the embedding sum, the residual stream and its gradient, LayerNorm, softmax statistics, cross-entropy and every
-// accumulator.  The workspace is the fp32 path's: QKV[l] holds the bf16 q | k | v planes, Y[l] bf16 y and then the softmax statistics, A[l]
-// bf16(a) | bf16(gelu(a)), DY the bf16 gradient of y, DH the bf16 gradient of a.
-int chunk_fwd_bwd_bf16(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows, const int32_t *tg, float loss_scale, hipStream_t s)
-{
-    const int C = g->C, L = g->L;
-    const int64_t M = (int64_t)rows * kT;
-    const float *P = g->params;
-    float *G = t->grads;
-    int rc;
-    tbk::Epi ep;
-    if ((rc = gpt_f32_embed(g, tok, t->X[0], M, s)) != MGPT_OK) return rc;
-    const float scale = 1.0f / sqrtf((float)g->hs);
-    for (int l = 0; l < L; l++) {
         const LayerOff &lo = g->layers[l];
-        float *x = t->X[l], *xm = t->XM[l], *xo = (l + 1 < L) ? t->X[l + 1] : t->XF;
-        uint16_t *a16 = reinterpret_cast<uint16_t *>(t->A[l]), *h16 = a16 + 4 * M * C;
-        uint16_t *qkv16 = reinterpret_cast<uint16_t *>(t->QKV[l]), *y16 = reinterpret_cast<uint16_t *>(t->Y[l]);
-        float *ast = reinterpret_cast<float *>(y16 + M * C);          // 2 n_head floats per token <= the C / 2 floats left in Y[l]
-        if ((rc = gpt_f32_layernorm(g, x, P + lo.ln1, t->XN1[l], M, s)) != MGPT_OK) return rc;
-        ep = tbk::Epi();
-        ep.b16 = qkv16; ep.C = C; ep.hs = g->hs; ep.n_head = g->nh; ep.plane = M * C;
-        if ((rc = bf_gemm<float, true, float, true, tbk::E_QKV>(t->XN1[l], C, P + lo.attn_w, C, M, 3 * C, C, ep, s)) != MGPT_OK) return rc;
-        rc = g->hs == 32 ? attn_bf16<32>(qkv16, M * C, y16, ast, rows, g->nh, scale, s)
-                         : attn_bf16<64>(qkv16, M * C, y16, ast, rows, g->nh, scale, s);
-        if (rc != MGPT_OK) return rc;
-        ep = tbk::Epi();
-        ep.f32 = xm; ep.res = x; ep.ldc = C;
-        if ((rc = bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(y16, C, P + lo.proj_w, C, M, C, C, ep, s)) != MGPT_OK) return rc;
-        if ((rc = gpt_f32_layernorm(g, xm, P + lo.ln2, t->XN2[l], M, s)) != MGPT_OK) return rc;
-        ep = tbk::Epi();
-        ep.b16 = a16; ep.b16b = h16; ep.ldc = 4 * C;
-        if ((rc = bf_gemm<float, true, float, true, tbk::E_FC>(t->XN2[l], C, P + lo.fc_w, C, M, 4 * C, C, ep, s)) != MGPT_OK) return rc;
-        ep = tbk::Epi();
-        ep.f32 = xo; ep.res = xm; ep.ldc = C;
-        if ((rc = bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(h16, 4 * C, P + lo.proj2_w, 4 * C, M, C, 4 * C, ep, s)) != MGPT_OK) return rc;
-    }
-    // head: the fp32 path's (ln_f, the tied head in fp32, cross-entropy), with this path's LayerNorm backward
-    if ((rc = gpt_f32_layernorm(g, t->XF, P + g->off_lnf, t->XNF, M, s)) != MGPT_OK) return rc;
-    if ((rc = tr_gemm<true, false, trk::OUT_STORE>(t->XNF, C, P + g->off_wte, C, t->LG, kV, M, kV, C, s)) != MGPT_OK) return rc;
-    hipLaunchKernelGGL(trk::ce_kernel, dim3((unsigned)cdiv64(M, 256)), dim3(256), 0, s, (const float *)t->LG, tg, M, (const int32_t *)t->cnt,
-                       loss_scale, t->DLG, t->NLL);
-    MGPT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(trk::sum_acc_kernel, dim3(1), dim3(256), 0, s, (const float *)t->NLL, M, t->loss_acc);
-    MGPT_LAUNCH_CHECK();
-    if ((rc = tr_gemm<true, true, trk::OUT_STORE>(t->DLG, kV, P + g->off_wte, C, t->DXN, C, M, C, kV, s)) != MGPT_OK) return rc;
-    if ((rc = weight_grad(t, t->DLG, t->XNF, G + g->off_wte, kV, C, M, s)) != MGPT_OK) return rc;
-    if ((rc = ln_backward_bf16<false>(t, t->XF, P + g->off_lnf, t->DXN, t->DX, G + g->off_lnf, M, C, s)) != MGPT_OK) return rc;
-    for (int l = L - 1; l >= 0; l--) {
-        const LayerOff &lo = g->layers[l];
-        const uint16_t *a16 = reinterpret_cast<const uint16_t *>(t->A[l]), *h16 = a16 + 4 * M * C;
-        uint16_t *da16 = reinterpret_cast<uint16_t *>(t->DH);
+        const Bf16Layer v = bf16_layer(t, l, M, C);
+        const Bf16Grads d = bf16_grads(t);
         // MLP: DX = d x_out (its bf16 rounding is the gradient of the bf16 c_proj output)
-        ep = tbk::Epi();
-        ep.b16 = da16; ep.aux = a16; ep.ldc = 4 * C;
-        if ((rc = bf_gemm<float, true, float, false, tbk::E_GELU_BWD>(t->DX, C, P + lo.proj2_w, 4 * C, M, 4 * C, C, ep, s)) != MGPT_OK) return rc;
-        if ((rc = weight_grad_bf16(t, (const float *)t->DX, h16, G + lo.proj2_w, C, 4 * C, M, s)) != MGPT_OK) return rc;
-        ep = tbk::Epi();
-        ep.f32 = t->DXN; ep.ldc = C;
-        if ((rc = bf_gemm<uint16_t, true, float, false, tbk::E_F32>(da16, 4 * C, P + lo.fc_w, C, M, C, 4 * C, ep, s)) != MGPT_OK) return rc;
-        if ((rc = weight_grad_bf16(t, (const uint16_t *)da16, (const float *)t->XN2[l], G + lo.fc_w, 4 * C, C, M, s)) != MGPT_OK) return rc;
-        if ((rc = ln_backward_bf16<true>(t, t->XM[l], P + lo.ln2, t->DXN, t->DX, G + lo.ln2, M, C, s)) != MGPT_OK) return rc;
+        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_GELU_BWD>(t->DX, C, P + lo.proj2_w, 4 * C, M, 4 * C, C, epi_gelu_bwd(d.da, v.a, 4 * C))));
+        MGPT_TRY(weight_grad_bf16(t->DX, v.h, G + lo.proj2_w, C, 4 * C));
+        MGPT_TRY((bf_gemm<uint16_t, true, float, false, tbk::E_F32>(d.da, 4 * C, P + lo.fc_w, C, M, C, 4 * C, epi_f32(t->DXN, C))));
+        MGPT_TRY(weight_grad_bf16(d.da, t->XN2[l], G + lo.fc_w, 4 * C, C));
+        MGPT_TRY(ln_backward<true>(t->XM[l], lo.ln2));
         // attention: DX = d x_mid;  d y = bf16(DX W_proj), the gradient of the bf16 attention output
-        const uint16_t *qkv16 = reinterpret_cast<const uint16_t *>(t->QKV[l]), *y16 = reinterpret_cast<const uint16_t *>(t->Y[l]);
-        const float *ast = reinterpret_cast<const float *>(y16 + M * C);
-        uint16_t *dy16 = reinterpret_cast<uint16_t *>(t->DY);
-        ep = tbk::Epi();
-        ep.b16 = dy16; ep.ldc = C;
-        if ((rc = bf_gemm<float, true, float, false, tbk::E_B16>(t->DX, C, P + lo.proj_w, C, M, C, C, ep, s)) != MGPT_OK) return rc;
-        if ((rc = weight_grad_bf16(t, (const float *)t->DX, y16, G + lo.proj_w, C, C, M, s)) != MGPT_OK) return rc;
-        rc = g->hs == 32 ? attn_bwd_bf16<32>(t, qkv16, M * C, y16, dy16, ast, rows, g->nh, scale, s)
-                         : attn_bwd_bf16<64>(t, qkv16, M * C, y16, dy16, ast, rows, g->nh, scale, s);
-        if (rc != MGPT_OK) return rc;
-        ep = tbk::Epi();
-        ep.f32 = t->DXN; ep.ldc = C;
-        if ((rc = bf_gemm<float, true, float, false, tbk::E_F32>(t->DQKV, 3 * C, P + lo.attn_w, C, M, C, 3 * C, ep, s)) != MGPT_OK) return rc;
-        if ((rc = weight_grad_bf16(t, (const float *)t->DQKV, (const float *)t->XN1[l], G + lo.attn_w, 3 * C, C, M, s)) != MGPT_OK) return rc;
-        if ((rc = ln_backward_bf16<true>(t, t->X[l], P + lo.ln1, t->DXN, t->DX, G + lo.ln1, M, C, s)) != MGPT_OK) return rc;
+        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_B16>(t->DX, C, P + lo.proj_w, C, M, C, C, epi_b16(d.dy, C))));
+        MGPT_TRY(weight_grad_bf16(t->DX, v.y, G + lo.proj_w, C, C));
+        MGPT_TRY(g->hs == 32 ? attn_backward_bf16<32>(v, d.dy) : attn_backward_bf16<64>(v, d.dy));
+        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_F32>(t->DQKV, 3 * C, P + lo.attn_w, C, M, C, 3 * C, epi_f32(t->DXN, C))));
+        MGPT_TRY(weight_grad_bf16(t->DQKV, t->XN1[l], G + lo.attn_w, 3 * C, C));
+        return ln_backward<true>(t->X[l], lo.ln1);
     }
-    // embedding: the fp32 path's kernels
-    hipLaunchKernelGGL(trk::wpe_bwd_kernel, dim3((unsigned)cdiv64((int64_t)kT * C, 256)), dim3(256), 0, s, (const float *)t->DX, rows, C, G + g->off_wpe);
-    MGPT_LAUNCH_CHECK();
+
+    int layer_forward(int l) { return bf16 ? layer_forward_bf16(l) : layer_forward_f32(l); }
+    int layer_backward(int l) { return bf16 ? layer_backward_bf16(l) : layer_backward_f32(l); }
+
+    // embedding (model.py:171-175), fp32 in both precisions: d wpe[t] += sum over rows, d wte[id] += sum over the tokens with that id
+    int embedding_backward()
     {
-        const int S = slabs_of(M), kps = slab_tokens(M);
-        hipLaunchKernelGGL(trk::wte_bwd_part_kernel, dim3(kV, (unsigned)S), dim3(256), 0, s, tok, (const float *)t->DX, M, C, kps, t->part);
-        MGPT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(trk::slab_reduce_kernel, dim3(grid_1d((int64_t)kV * C)), dim3(256), 0, s, t->part, S, (int64_t)kV * C, G + g->off_wte);
-        MGPT_LAUNCH_CHECK();
+        MGPT_LAUNCH(trk::wpe_bwd_kernel, dim3((unsigned)cdiv64((int64_t)kT * C, 256)), dim3(256), 0, s, t->DX, rows, C, G + g->off_wpe);
+        return slab_sum(G + g->off_wte, (int64_t)kV * C, 16, [&](int S, int kps) -> int {
+            MGPT_LAUNCH(trk::wte_bwd_part_kernel, dim3(kV, (unsigned)S), dim3(256), 0, s, tok, t->DX, M, C, kps, t->part);
+            return MGPT_OK;
+        });
     }
-    return MGPT_OK;
+};
+
+// one chunk of rows: forward with saved activations, cross-entropy against the call's target count, backward into t->grads
+int chunk_fwd_bwd(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows, const int32_t *tg, float loss_scale, int precision, hipStream_t s)
+{
+    Chunk c = {g, t, tok, tg, rows, loss_scale, precision == MGPT_PREC_BF16, s};
+    MGPT_TRY(gpt_f32_embed(g, tok, t->X[0], c.M, s));
+    for (int l = 0; l < g->L; l++) MGPT_TRY(c.layer_forward(l));
+    MGPT_TRY(c.head_forward());
+    MGPT_TRY(c.head_backward());
+    for (int l = g->L - 1; l >= 0; l--) MGPT_TRY(c.layer_backward(l));
+    return c.embedding_backward();
 }
 
 int require_train(mgpt_gpt *g)
@@ -413,6 +416,10 @@ extern "C" int mgpt_gpt_train_alloc(mgpt_gpt *g, int max_rows)
     MGPT_REQUIRE(g->finalized, MGPT_ERR_STATE, "mgpt_gpt_finalize must precede mgpt_gpt_train_alloc");
     MGPT_REQUIRE(!g->has_bias, MGPT_ERR_UNSUPPORTED, "training supports bias = False checkpoints only (the released configs)");
     MGPT_REQUIRE(g->block == kT, MGPT_ERR_ARG, "training takes rows of T = 256 tokens; the model's block_size is %d", g->block);
+    // the bf16 views of the workspace (bf16_layer): the statistics fit behind y, a and gelu(a) fit A[l]
+    MGPT_REQUIRE(2 * g->nh <= g->C / 2, MGPT_ERR_UNSUPPORTED, "bf16 training keeps 2 n_head = %d statistics per token in the C / 2 = %d floats behind y",
+                 2 * g->nh, g->C / 2);
+    static_assert(2 * sizeof(uint16_t) <= sizeof(float), "bf16 a and gelu(a), 4 M C elements each, fit the 4 M C floats of A[l]");
     hipError_t e = hipSuccess;
     TrainState *t = ts(g);
     const bool fresh = t == nullptr;
@@ -421,6 +428,7 @@ extern "C" int mgpt_gpt_train_alloc(mgpt_gpt *g, int max_rows)
         MGPT_HIP(hipDeviceSynchronize());              // (no queued call still uses the activations freed below)
         free_activations(t);
     } else {
+        MGPT_TRY(g->hs == 32 ? raise_attn_lds<32>() : raise_attn_lds<64>());
         t = new TrainState();
     }
     auto alloc_in = [&](std::vector<void *> &owner, size_t bytes) -> void * {
@@ -496,8 +504,7 @@ extern "C" int mgpt_gpt_forward_backward(mgpt_gpt *g, const uint8_t *d_tokens, i
 extern "C" int mgpt_gpt_forward_backward_prec(mgpt_gpt *g, const uint8_t *d_tokens, int rows, int T, const int32_t *d_targets, float loss_scale,
                                               float *d_loss, int precision, void *stream)
 {
-    int rc = require_train(g);
-    if (rc != MGPT_OK) return rc;
+    MGPT_TRY(require_train(g));
     MGPT_REQUIRE(d_tokens && d_targets, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(rows > 0, MGPT_ERR_ARG, "rows=%d", rows);
     MGPT_REQUIRE(T == kT, MGPT_ERR_ARG, "training takes rows of T = 256 tokens, got T = %d", T);
@@ -508,8 +515,7 @@ extern "C" int mgpt_gpt_forward_backward_prec(mgpt_gpt *g, const uint8_t *d_toke
     MGPT_REQUIRE(t->max_rows > 0, MGPT_ERR_STATE, "the training workspace holds no activation memory (a re-size failed): mgpt_gpt_train_alloc again");
     hipStream_t s = (hipStream_t)stream;
     // the cross-entropy normaliser is the targeted-position count of the WHOLE call (F.cross_entropy's mean over the call's tokens)
-    hipLaunchKernelGGL(trk::count_targets_kernel, dim3(1), dim3(1024), 0, s, d_targets, (int64_t)rows * kT, t->cnt);
-    MGPT_LAUNCH_CHECK();
+    MGPT_LAUNCH(trk::count_targets_kernel, dim3(1), dim3(1024), 0, s, d_targets, (int64_t)rows * kT, t->cnt);
     MGPT_HIP(hipMemcpyAsync(t->h_cnt, t->cnt, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     MGPT_HIP(hipStreamSynchronize(s));
     MGPT_REQUIRE(t->h_cnt[1] == 0, MGPT_ERR_ARG, "targets must lie in [-1, 67): -1 is ignored, 0 .. 66 are vocabulary ids");
@@ -519,56 +525,42 @@ extern "C" int mgpt_gpt_forward_backward_prec(mgpt_gpt *g, const uint8_t *d_toke
         const int n = std::min(t->max_rows, rows - r0);
         const uint8_t *tk = d_tokens + (size_t)r0 * kT;
         const int32_t *tg = d_targets + (size_t)r0 * kT;
-        rc = precision == MGPT_PREC_BF16 ? chunk_fwd_bwd_bf16(g, t, tk, n, tg, loss_scale, s) : chunk_fwd_bwd(g, t, tk, n, tg, loss_scale, s);
-        if (rc != MGPT_OK) return rc;
+        MGPT_TRY(chunk_fwd_bwd(g, t, tk, n, tg, loss_scale, precision, s));
     }
-    if (d_loss) {
-        hipLaunchKernelGGL(trk::loss_final_kernel, dim3(1), dim3(64), 0, s, (const double *)t->loss_acc, (const int32_t *)t->cnt, d_loss);
-        MGPT_LAUNCH_CHECK();
-    }
+    if (d_loss) MGPT_LAUNCH(trk::loss_final_kernel, dim3(1), dim3(64), 0, s, (const double *)t->loss_acc, t->cnt, d_loss);
     return MGPT_OK;
 }
 
 extern "C" int mgpt_gpt_zero_grad(mgpt_gpt *g, void *stream)
 {
-    const int rc = require_train(g);
-    if (rc != MGPT_OK) return rc;
+    MGPT_TRY(require_train(g));
     MGPT_HIP(hipMemsetAsync(ts(g)->grads, 0, g->n_params * sizeof(float), (hipStream_t)stream));
     return MGPT_OK;
 }
 
 extern "C" int mgpt_gpt_clip_grad_norm(mgpt_gpt *g, float max_norm, float *d_total_norm, void *stream)
 {
-    const int rc = require_train(g);
-    if (rc != MGPT_OK) return rc;
+    MGPT_TRY(require_train(g));
     TrainState *t = ts(g);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(trk::sumsq_part_kernel, dim3((unsigned)t->n_blk), dim3(256), 0, s, (const float *)t->grads, (const trk::Blk *)t->blk, t->norm_part);
-    MGPT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(trk::clip_coef_kernel, dim3(1), dim3(64), 0, s, (const double *)t->norm_part, (const trk::Blk *)t->blk, t->n_blk,
-                       max_norm > 0.f ? max_norm : 1.f, d_total_norm, t->coef);
-    MGPT_LAUNCH_CHECK();
-    if (max_norm > 0.f) {
-        hipLaunchKernelGGL(trk::scale_kernel, dim3(grid_1d((int64_t)g->n_params)), dim3(256), 0, s, t->grads, (int64_t)g->n_params, (const float *)t->coef);
-        MGPT_LAUNCH_CHECK();
-    }
+    MGPT_LAUNCH(trk::sumsq_part_kernel, dim3((unsigned)t->n_blk), dim3(256), 0, s, t->grads, (const trk::Blk *)t->blk, t->norm_part);
+    MGPT_LAUNCH(trk::clip_coef_kernel, dim3(1), dim3(64), 0, s, (const double *)t->norm_part, (const trk::Blk *)t->blk, t->n_blk, max_norm > 0.f ? max_norm : 1.f,
+                d_total_norm, t->coef);
+    if (max_norm > 0.f) MGPT_LAUNCH(trk::scale_kernel, dim3(grid_1d((int64_t)g->n_params)), dim3(256), 0, s, t->grads, (int64_t)g->n_params, t->coef);
     return MGPT_OK;
 }
 
 extern "C" int mgpt_gpt_adamw_step(mgpt_gpt *g, float lr, float beta1, float beta2, float eps, float weight_decay, void *stream)
 {
-    const int rc = require_train(g);
-    if (rc != MGPT_OK) return rc;
+    MGPT_TRY(require_train(g));
     MGPT_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f && lr >= 0.f, MGPT_ERR_ARG,
                  "AdamW hyper-parameters out of range (lr %g, betas %g %g, eps %g)", lr, beta1, beta2, eps);
     TrainState *t = ts(g);
     hipStream_t s = (hipStream_t)stream;
     const int nt = 3 + 6 * g->L;
-    hipLaunchKernelGGL(trk::step_inc_kernel, dim3((unsigned)cdiv(nt, 256)), dim3(256), 0, s, t->steps, nt);
-    MGPT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(trk::adamw_kernel, dim3((unsigned)t->n_blk), dim3(256), 0, s, g->params, (const float *)t->grads, t->exp_avg, t->exp_avg_sq,
-                       (const trk::Blk *)t->blk, (const float *)t->steps, lr, beta1, beta2, eps, weight_decay);
-    MGPT_LAUNCH_CHECK();
+    MGPT_LAUNCH(trk::step_inc_kernel, dim3((unsigned)cdiv(nt, 256)), dim3(256), 0, s, t->steps, nt);
+    MGPT_LAUNCH(trk::adamw_kernel, dim3((unsigned)t->n_blk), dim3(256), 0, s, g->params, t->grads, t->exp_avg, t->exp_avg_sq, (const trk::Blk *)t->blk, t->steps, lr,
+                beta1, beta2, eps, weight_decay);
     gpt_params_changed(g);
     return MGPT_OK;
 }
@@ -594,11 +586,10 @@ static int train_locate(mgpt_gpt *g, const char *name, int which, float **ptr, s
 
 extern "C" int mgpt_gpt_train_get(mgpt_gpt *g, const char *name, int which, float *d_out, int64_t n_elem, void *stream)
 {
-    int rc = MGPT_OK;
     MGPT_REQUIRE(g && d_out, MGPT_ERR_ARG, "NULL argument");
     float *src = nullptr;
     size_t count = 0;
-    if ((rc = train_locate(g, name, which, &src, &count)) != MGPT_OK) return rc;
+    MGPT_TRY(train_locate(g, name, which, &src, &count));
     MGPT_REQUIRE((size_t)n_elem == count, MGPT_ERR_ARG, "'%s' (which %d): got %lld elements, expected %zu", name, which, (long long)n_elem, count);
     MGPT_HIP(hipMemcpyAsync(d_out, src, count * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MGPT_OK;
@@ -606,11 +597,10 @@ extern "C" int mgpt_gpt_train_get(mgpt_gpt *g, const char *name, int which, floa
 
 extern "C" int mgpt_gpt_train_set(mgpt_gpt *g, const char *name, int which, const float *data, int64_t n_elem, int is_device)
 {
-    int rc = MGPT_OK;
     MGPT_REQUIRE(g && data, MGPT_ERR_ARG, "NULL argument");
     float *dst = nullptr;
     size_t count = 0;
-    if ((rc = train_locate(g, name, which, &dst, &count)) != MGPT_OK) return rc;
+    MGPT_TRY(train_locate(g, name, which, &dst, &count));
     MGPT_REQUIRE((size_t)n_elem == count, MGPT_ERR_ARG, "'%s' (which %d): got %lld elements, expected %zu", name, which, (long long)n_elem, count);
     MGPT_HIP(hipDeviceSynchronize());                  // (stream-ordered work on the tensor finishes first: this call is synchronous)
     MGPT_HIP(hipMemcpy(dst, data, count * sizeof(float), is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));

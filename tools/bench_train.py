@@ -2,7 +2,9 @@
 as a yardstick only, torch fp32 eager autograd of an in-repo restatement of model.py (oracle/gpt_oracle.py's formulas) on the same GPU.
 
     python tools/bench_train.py [--shapes 6M:512,6M:2048,2M:4096,85M:512] [--precision f32,bf16] [--torch-rows 512] [--iters 3] [--warmup 1]
+                                [--lib PATH]
 
+--lib PATH times another build of the library (a file tools/build_ab.sh writes) in place of the in-tree one.
 --precision f32,bf16 times both training precisions in one call (one JSON line per shape and precision).  Every line carries the counted
 flops of the call (the products the model executes, 2 per multiply-add, backward = 2 x forward; the attention backward's recomputed S
 excluded) and, for bf16, the bytes its kernels move to and from memory (count_bytes below: every tensor read or written once per kernel,
@@ -50,7 +52,7 @@ def count_flops(args, rows, T=256, V=67):
 
 
 def count_bytes(args, rows, T=256, V=67):
-    """bytes the bf16 path's kernels read and write per call (train.hip chunk_fwd_bwd_bf16), per token and layer in units of C:
+    """bytes the bf16 path's kernels read and write per call (train.hip, the bf16 bodies of Chunk), per token and layer in units of C:
     forward 96 C (LayerNorms 2 x 8, q|k|v 16, attention 16, c_proj 12, c_fc 20 (bf16 a and gelu(a)), mlp c_proj 16);
     backward 200 C (d h with gelu' 20, the four weight gradients 12 + 12 + 8 + 16, the input gradients 12 + 8 + 16, LayerNorms 2 x 16,
     attention backward 64); the head and the embedding 16 V + 24 C per token"""
@@ -87,7 +89,11 @@ def main(argv=None):
     ap.add_argument("--torch-rows", type=int, default=512)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--lib", default=None, help="path of the library to time (default: the in-tree build)")
     a = ap.parse_args(argv)
+    if a.lib:
+        from mapf_gpt_amd import _lib
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     for item in a.shapes.split(","):
         name, rows = item.split(":")
         rows = int(rows)

@@ -1,10 +1,13 @@
-"""tools/forward_digest.py <libA.so> <libB.so>  -- bit-for-bit comparison of the 16-bit forward of two builds of the library
-(the files tools/build_ab.sh writes): one SHA-256 of the output bytes per case, side by side, and a verdict.
+"""tools/forward_digest.py <libA.so> <libB.so>  -- bit-for-bit comparison of the 16-bit forward and of training of two builds of the
+library (the files tools/build_ab.sh writes): one SHA-256 of the output bytes per case, side by side, and a verdict.
 
-The case list is fixed here: seeded synthetic weights and tokens; every released shape, two shapes of the packed / generic chains and the
-one-layer variants; both precisions; small calls, large calls with and without a remainder chunk, an uneven persistent grid, the sequence
-forward and act_tokens.  Every (library, environment setting, model) runs in a fresh process under its own time limit; the first process that
-fails ends the run.  A refactor of the host side must leave the two columns identical.
+The case list is fixed here: seeded synthetic weights and tokens.  Forward: every released shape, two shapes of the packed / generic chains
+and the one-layer variants; both precisions; small calls, large calls with and without a remainder chunk, an uneven persistent grid, the
+sequence forward and act_tokens.  Training (TRAIN_MODELS, chunks of 2 rows, targets half -1 with one row all -1): per precision the loss and
+every gradient after a one-chunk call, a call of chunks 2, 2, 1 and an accumulating call, then after an f32 call followed by a bf16 call;
+each time the total norm of clip_grad_norm_(1.0) and the state_dict() after one AdamW step.  Every (library, environment setting, model)
+runs in a fresh process under its own time limit; the first process that fails ends the run.  A refactor of the host side must leave the
+two columns identical.
 """
 import hashlib
 import os
@@ -21,6 +24,7 @@ MODELS = {  # name -> model_args
 GROUPS = [({}, list(MODELS), ("f16x3", "bf16")),
           ({"MGPT_L0_TABLE": "0"}, ["6M"], ("f16x3", "bf16")),
           ({"MGPT_LN_FOLD": "0"}, ["85M"], ("bf16",))]
+TRAIN_MODELS = ("tiny", "2M", "6M", "85M")    # head size 32, and 64 (85M); one process each
 TIME_LIMIT = 420    # seconds per process
 
 
@@ -63,36 +67,84 @@ def child(lib_path, model, precisions):
             del n
 
 
+def child_train(lib_path, model):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    from mapf_gpt_amd import _lib
+    _lib.LIB_PATH = lib_path
+    from mapf_gpt_amd.model import build_model
+
+    rng = np.random.default_rng(7)
+    tokens = torch.from_numpy(rng.integers(0, 67, size=(10, 256), dtype=np.uint8)).cuda()
+    targets = rng.integers(0, 67, size=(10, 256)).astype(np.int64)
+    targets[rng.random((10, 256)) < 0.5] = -1
+    targets[[1, 6]] = -1                                          # rows with no targeted position
+    targets = torch.from_numpy(targets)
+    net = build_model(model, seed=3, max_rows=2).train(max_rows=2)
+    opt = net.configure_optimizers(0.1, 6e-4, (0.9, 0.95))
+
+    def digest(tag, *tensors):                                    # (named_parameters order for gradients and parameters)
+        torch.cuda.synchronize()
+        h = hashlib.sha256()
+        for t in tensors:
+            h.update(t.detach().cpu().contiguous().numpy().tobytes())
+        print(f"{model} train {tag} {h.hexdigest()}", flush=True)
+
+    def step(tag, calls):                                         # calls: (precision, first row, rows) into one gradient buffer
+        net.zero_grad()
+        for i, (precision, r0, n) in enumerate(calls):
+            loss = net.forward_backward(tokens[r0:r0 + n].contiguous(), targets[r0:r0 + n], precision=precision)
+            digest(f"{tag} call {i} {precision} rows={n} loss+grads", loss, *net.grads().values())
+        digest(f"{tag} total norm", net.clip_grad_norm_(1.0))
+        opt.step()
+        sd = net.state_dict()
+        digest(f"{tag} state_dict", *(sd[n] for n, _ in net.named_parameters()))
+
+    for precision in ("f32", "bf16"):
+        step(f"{precision} one chunk", [(precision, 0, 2)])
+        step(f"{precision} chunks 2,2,1 then accumulate", [(precision, 0, 5), (precision, 5, 5)])
+    step("f32 then bf16", [("f32", 0, 2), ("bf16", 2, 5)])
+
+
 def run(lib_path):
     lib_path = os.path.abspath(lib_path)
     name = os.path.basename(lib_path)
     lines = []
+
+    def one(env, model, *child_args):
+        cmd = ["timeout", "-k", "10", str(TIME_LIMIT), sys.executable, os.path.abspath(__file__), *child_args]
+        r = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True)
+        if r.returncode != 0:
+            sys.stderr.write(r.stdout + r.stderr)
+            sys.exit(f"forward_digest: {name} {env} {child_args[0]} {model}: exit status {r.returncode}; nothing more is started")
+        prefix = " ".join(f"{k}={v}" for k, v in env.items())
+        print(f"# {name} {prefix} {child_args[0]} {model}: done", file=sys.stderr, flush=True)
+        lines.extend((prefix + " " + ln).strip() for ln in r.stdout.splitlines() if " " in ln and len(ln.rsplit(" ", 1)[1]) == 64)
+
     for env, models, precisions in GROUPS:
         for model in models:
-            cmd = ["timeout", "-k", "10", str(TIME_LIMIT), sys.executable, os.path.abspath(__file__), "--child", lib_path, model, ",".join(precisions)]
-            r = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True)
-            if r.returncode != 0:
-                sys.stderr.write(r.stdout + r.stderr)
-                sys.exit(f"forward_digest: {name} {env} {model}: exit status {r.returncode}; nothing more is started")
-            prefix = " ".join(f"{k}={v}" for k, v in env.items())
-            print(f"# {name} {prefix} {model}: done", file=sys.stderr, flush=True)
-            lines += [(prefix + " " + ln).strip() for ln in r.stdout.splitlines() if " " in ln and len(ln.rsplit(" ", 1)[1]) == 64]
+            one(env, model, "--child", lib_path, model, ",".join(precisions))
+    for model in TRAIN_MODELS:
+        one({}, model, "--child-train", lib_path, model)
     return lines
 
 
 def main():
     if len(sys.argv) >= 2 and sys.argv[1] == "--child":
         return child(sys.argv[2], sys.argv[3], sys.argv[4].split(","))
+    if len(sys.argv) >= 2 and sys.argv[1] == "--child-train":
+        return child_train(sys.argv[2], sys.argv[3])
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     a, b = run(sys.argv[1]), run(sys.argv[2])
     differing = 0
-    print(f"{'case':<52} {sys.argv[1]:<64} {sys.argv[2]:<64}")
+    print(f"{'case':<80} {sys.argv[1]:<64} {sys.argv[2]:<64}")
     for la, lb in zip(a, b):
         (ca, ha), (cb, hb) = la.rsplit(" ", 1), lb.rsplit(" ", 1)
         same = ca == cb and ha == hb
         differing += 0 if same else 1
-        print(f"{ca:<52} {ha} {hb}{'' if same else '  <-- DIFFERS'}")
+        print(f"{ca:<80} {ha} {hb}{'' if same else '  <-- DIFFERS'}")
     differing += abs(len(a) - len(b))
     print(f"{len(a)} / {len(b)} cases, differing {differing}")
     sys.exit(1 if differing or not a else 0)
