@@ -324,6 +324,18 @@ int mgpt_gpt_act_dev(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int32_t *
  *           parameter, gradient, exp_avg, exp_avg_sq (the tensor's elements) or the step count (one float).  get copies device to device
  *           on `stream`; set is synchronous (host or device source) and, for a parameter, acts as an optimizer step does on the 16-bit state.
  *           Parameters need no training workspace; the other selectors do (MGPT_ERR_STATE).
+ * Data-parallel training (train.py:237-239, 314-322: one process per GPU, gradients averaged over the ranks at an iteration's last
+ * micro-step).  No collective runs inside the library: the caller gathers the ranks' buffers ([world][n_elem], rank-major) and the library
+ * adds them in rank order, so every rank computes the same bits whatever the collective library's ring or tree would have chosen.
+ *   grads_size: *n_elem = the length of the gradient buffer in the library's own layout (the layout of the parameters; padding, if a
+ *           layout ever has any, is included, is zero and stays zero).
+ *   grads_export: the whole gradient buffer to d_out (device, n_elem floats), an asynchronous device-to-device copy on `stream`.
+ *   grads_reduce: d_gathered device float [world][n_elem]; REPLACES the gradient buffer with
+ *           scale * (((g[0][i] + g[1][i]) + g[2][i]) + ...): plain fp32 additions in rank order, one multiplication at the end (scale =
+ *           1 / world gives DDP's mean).  d_gathered must not overlap the gradient buffer.  16-byte loads and stores when d_gathered is
+ *           16-byte aligned and n_elem % 4 == 0, element by element otherwise; no atomics.
+ *   All three: a NULL pointer or a wrong n_elem MGPT_ERR_ARG; world < 1 or a scale that is not finite and positive MGPT_ERR_ARG; no
+ *           training workspace MGPT_ERR_STATE.
  * ------------------------------------------------------------------------------------------ */
 #define MGPT_TRAIN_PARAM 0
 #define MGPT_TRAIN_GRAD 1
@@ -341,6 +353,9 @@ int mgpt_gpt_clip_grad_norm(mgpt_gpt *gpt, float max_norm, float *d_total_norm, 
 int mgpt_gpt_adamw_step(mgpt_gpt *gpt, float lr, float beta1, float beta2, float eps, float weight_decay, void *stream);
 int mgpt_gpt_train_get(mgpt_gpt *gpt, const char *name, int which, float *d_out, int64_t n_elem, void *stream);
 int mgpt_gpt_train_set(mgpt_gpt *gpt, const char *name, int which, const float *data, int64_t n_elem, int is_device);
+int mgpt_gpt_grads_size(mgpt_gpt *gpt, int64_t *n_elem);
+int mgpt_gpt_grads_export(mgpt_gpt *gpt, float *d_out, int64_t n_elem, void *stream);
+int mgpt_gpt_grads_reduce(mgpt_gpt *gpt, const float *d_gathered, int world, float scale, void *stream);
 
 /* sampling alone (same RNG and key as mgpt_gpt_act), for callers that already hold logits */
 int mgpt_sample_actions(const float *d_logits, int rows, int32_t *d_actions, int do_sample,

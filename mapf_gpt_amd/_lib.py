@@ -105,6 +105,9 @@ SYMBOLS = {
     "mgpt_gpt_adamw_step": (_i, [_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp]),
     "mgpt_gpt_train_get": (_i, [_vp, ctypes.c_char_p, _i, _vp, _i64, _vp]),
     "mgpt_gpt_train_set": (_i, [_vp, ctypes.c_char_p, _i, _vp, _i64, _i]),
+    "mgpt_gpt_grads_size": (_i, [_vp, ctypes.POINTER(_i64)]),
+    "mgpt_gpt_grads_export": (_i, [_vp, _vp, _i64, _vp]),
+    "mgpt_gpt_grads_reduce": (_i, [_vp, _vp, _i, ctypes.c_float, _vp]),
     "mgpt_prof_enable": (_i, [_i]),
     "mgpt_prof_reset": (_i, []),
     "mgpt_prof_read": (_i, [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float),

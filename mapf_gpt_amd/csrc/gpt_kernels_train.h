@@ -106,6 +106,34 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float *__restric
     }
 }
 
+// out[i] = scale * (((g[0][i] + g[1][i]) + g[2][i]) + ...), g = gathered [world][n]: the ranks' gradient buffers added in rank order with
+// plain fp32 additions, then one multiplication (train.py:237-239: DDP's mean over the ranks, here in an order the code fixes, so every
+// rank computes the same bits).  out is REPLACED.  Bandwidth-bound ((world + 1) * 4 n bytes): the first nv = n / 4 quads move as 16-byte
+// loads and stores -- the caller passes nv > 0 only when gathered, out and every row g[r] = gathered + r * n are 16-byte aligned
+// (n % 4 == 0) -- and the elements from 4 nv on one by one.
+__global__ __launch_bounds__(256) void rank_reduce_kernel(const float *__restrict__ gathered, int world, int64_t n, int64_t nv, float scale,
+                                                          float *__restrict__ out)
+{
+    const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    const float4 *g4 = reinterpret_cast<const float4 *>(gathered);
+    float4 *o4 = reinterpret_cast<float4 *>(out);
+    const int64_t row4 = n / 4;                                 // (quads per row; read only when nv > 0, i.e. n % 4 == 0)
+    for (int64_t i = t0; i < nv; i += stride) {
+        float4 s = g4[i];
+#pragma unroll 4
+        for (int r = 1; r < world; r++) {
+            const float4 v = g4[(int64_t)r * row4 + i];
+            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        }
+        o4[i] = make_float4(s.x * scale, s.y * scale, s.z * scale, s.w * scale);
+    }
+    for (int64_t i = 4 * nv + t0; i < n; i += stride) {
+        float s = gathered[i];
+        for (int r = 1; r < world; r++) s += gathered[(int64_t)r * n + i];
+        out[i] = s * scale;
+    }
+}
+
 // part[s][c] = sum over the tokens of slab s of v[m][c] (LayerNorm gain gradients), m in increasing order, accumulated in double
 __global__ __launch_bounds__(256) void colsum_part_kernel(const float *__restrict__ v, int64_t M, int C, int kps, float *__restrict__ part)
 {

@@ -4,6 +4,8 @@
 // A call runs in chunks of the workspace's max_rows rows.  chunk_fwd_bwd is the one sequence of both precisions, its steps members of Chunk:
 // embed, layer_forward per layer, head forward and loss, head backward, layer_backward per layer in reverse, embedding backward.  The bf16
 // path reaches the shared, fp32-sized workspace through typed views (bf16_layer, bf16_grads).
+#include <cmath>
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -535,6 +537,39 @@ extern "C" int mgpt_gpt_zero_grad(mgpt_gpt *g, void *stream)
 {
     MGPT_TRY(require_train(g));
     MGPT_HIP(hipMemsetAsync(ts(g)->grads, 0, g->n_params * sizeof(float), (hipStream_t)stream));
+    return MGPT_OK;
+}
+
+// ----- data-parallel gradient synchronisation (train.py:237-239, 314-322): the whole buffer out, the ranks' buffers summed in rank order -----
+extern "C" int mgpt_gpt_grads_size(mgpt_gpt *g, int64_t *n_elem)
+{
+    MGPT_REQUIRE(g && n_elem, MGPT_ERR_ARG, "NULL argument");
+    MGPT_TRY(require_train(g));
+    *n_elem = (int64_t)g->n_params;
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_gpt_grads_export(mgpt_gpt *g, float *d_out, int64_t n_elem, void *stream)
+{
+    MGPT_REQUIRE(g && d_out, MGPT_ERR_ARG, "NULL argument");
+    MGPT_TRY(require_train(g));
+    MGPT_REQUIRE(n_elem == (int64_t)g->n_params, MGPT_ERR_ARG, "the gradient buffer has %zu elements, got %lld", g->n_params, (long long)n_elem);
+    MGPT_HIP(hipMemcpyAsync(d_out, ts(g)->grads, g->n_params * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_gpt_grads_reduce(mgpt_gpt *g, const float *d_gathered, int world, float scale, void *stream)
+{
+    MGPT_REQUIRE(g && d_gathered, MGPT_ERR_ARG, "NULL argument");
+    MGPT_TRY(require_train(g));
+    MGPT_REQUIRE(world >= 1, MGPT_ERR_ARG, "world=%d", world);
+    MGPT_REQUIRE(std::isfinite(scale) && scale > 0.f, MGPT_ERR_ARG, "scale=%g: a finite positive factor (1 / world for the ranks' mean)", scale);
+    TrainState *t = ts(g);
+    const int64_t n = (int64_t)g->n_params;
+    // 16-byte accesses need every row of d_gathered and the gradient buffer on a 16-byte boundary; otherwise the scalar loop takes it all
+    const bool wide = n % 4 == 0 && reinterpret_cast<uintptr_t>(d_gathered) % 16 == 0 && reinterpret_cast<uintptr_t>(t->grads) % 16 == 0;
+    const int64_t nv = wide ? n / 4 : 0;
+    MGPT_LAUNCH(trk::rank_reduce_kernel, dim3(grid_1d(wide ? nv : n)), dim3(256), 0, (hipStream_t)stream, d_gathered, world, n, nv, scale, t->grads);
     return MGPT_OK;
 }
 

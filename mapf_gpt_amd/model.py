@@ -9,7 +9,8 @@ plus the device-resident fast path `act_tokens(tokens_u8, ...)` used by the batc
 `score_tokens` and mapf_gpt_amd/scoring.py score a checkpoint on expert data (train.py estimate_loss).
 Training (train.py:324-331) runs on the device in exact fp32 or in train.py's bf16 autocast regime (forward_backward(...,
 precision="bf16")): train(), forward_backward(idx, targets), zero_grad(),
-clip_grad_norm_(), grads(), state_dict() and configure_optimizers() -> AdamW (model.py:202-226).  estimate_mfu and
+clip_grad_norm_(), grads(), state_dict() and configure_optimizers() -> AdamW (model.py:202-226); data-parallel runs (train.py:237-239)
+synchronise through grads_size(), export_grads() and reduce_grads(): a gather and a rank-ordered sum, no DDP wrapper.  estimate_mfu and
 crop_block_size are out of scope.  Every compute call goes through the C ABI; there is no PyTorch forward here.
 """
 import ctypes
@@ -362,6 +363,37 @@ class GPT:
         """{named_parameters name: float32 device tensor} -- copies of the accumulated gradients."""
         self._require_train()
         return {n: self._train_tensor(n, _lib.TRAIN_GRAD, shp) for n, shp in self.named_parameters()}
+
+    # ---- data-parallel gradient synchronisation (train.py:237-239, 314-322; training.py runs it between all_gather and the clip) ----
+    def grads_size(self):
+        """Length of the flat gradient buffer (the library's layout: every parameter once, any padding included)."""
+        self._require_train()
+        n = ctypes.c_int64(0)
+        _lib.check(_lib.lib().mgpt_gpt_grads_size(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def export_grads(self, out=None):
+        """The whole gradient buffer as one flat float32 device tensor (a copy on the current stream), into `out` when given."""
+        n = self.grads_size()
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.numel() != n:
+            raise ValueError(f"out must be a contiguous float32 device tensor of {n} elements, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mgpt_gpt_grads_export(self._h, _lib.ptr(out), out.numel(), _lib.stream_ptr()))
+        return out
+
+    def reduce_grads(self, gathered, scale):
+        """gathered float32 device [world, grads_size()] = the ranks' export_grads() in rank order: REPLACES the gradients with
+        scale * (((g[0] + g[1]) + g[2]) + ...), fp32 additions in rank order (bit-identical on every rank); scale = 1 / world is DDP's mean."""
+        n = self.grads_size()
+        gathered = torch.as_tensor(gathered)
+        if gathered.dtype != torch.float32 or not gathered.is_cuda or gathered.numel() % n != 0:
+            raise ValueError(f"gathered must be a float32 device tensor of world x {n} elements, got {gathered.dtype} {tuple(gathered.shape)} "
+                             f"on {gathered.device}")
+        gathered = gathered.contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mgpt_gpt_grads_reduce(self._h, _lib.ptr(gathered), gathered.numel() // n, float(scale), _lib.stream_ptr()))
 
     def state_dict(self):
         """The parameters read back from the device, in the reference's key layout; lm_head.weight aliases transformer.wte.weight."""

@@ -9,7 +9,21 @@ directories of them) read through scoring.read_arrow; every file is shuffled whe
 targets of -1 except the last position, which holds the expert action (fast_data_loader.py:39-67).  Every eval_interval iterations the
 loss of eval_iters batches of each split is measured with scoring.evaluate (= estimate_loss, train.py:244-259) and a ckpt.pt is written as
 train.py:298-310 writes it ({"model", "optimizer", "model_args", "iter_num", "best_val_loss", "config"}); weights.load_checkpoint and
-MAPFGPTInference load it unchanged.  One JSON line per evaluation and one at the end.  No DDP, GradScaler or torch.compile.
+MAPFGPTInference load it unchanged.  One JSON line per evaluation and one at the end; --log-interval N adds {"iter", "loss", "ms"} every
+N iterations (train.py:346-355; 0, the default, prints none).  No GradScaler or torch.compile.
+
+Data-parallel runs (train.py:118-138, 237-239, 314-322, 364-365): one process per GPU under torchrun,
+
+    torchrun --standalone --nproc_per_node=N -m mapf_gpt_amd.training --init ... --data DIR --val DIR [--backend nccl|gloo]
+
+With RANK in the environment the process joins a process group (--backend nccl = RCCL, the default, or gloo), takes cuda:LOCAL_RANK
+(--share-gpu: every rank on cuda:0, for dry runs on a one-GPU box), divides gradient_accumulation_steps by the world size, reads its share of
+the training split's files (fast_data_loader.py:20-28) shuffled with seed + rank, and builds the same initial weights as every other rank.
+There is no DistributedDataParallel wrapper and no all_reduce: after the last micro-step of an iteration every rank exports its flat
+gradient buffer, the ranks all_gather them, and one kernel adds them in rank order and scales by 1 / world (GPT.reduce_grads), so every rank
+holds the same bits whatever the backend and the weights stay in lockstep without a broadcast.  param_checksum guards that: the ranks compare
+it at every eval_interval boundary and at the end, and a mismatch raises on every rank.  Rank 0 alone evaluates, writes ckpt.pt and prints.
+Without RANK nothing of this runs and the command behaves as a single process always did.
 
 --dtype takes train.py's knob (train.py:66-70): float32 (exact fp32, the default here) or bfloat16 (every micro-step and every estimate_loss in
 the bf16 autocast regime: forward_backward(precision="bf16"), scoring.evaluate(precision="bf16")).  train.py itself defaults to bfloat16 on a
@@ -20,6 +34,7 @@ import glob
 import json
 import math
 import os
+import time
 
 import numpy as np
 import torch
@@ -50,15 +65,44 @@ def shard_files(path):
     return files
 
 
+def rank_files(files, rank, world):
+    """The files of `rank` among `world` data-parallel ranks, as fast_data_loader.py:20-28 deals the training split: len(files) // world
+    consecutive files each, in name order; the remainder is unused.  (With more ranks than files the reference would fail on an empty list.)"""
+    if not 0 <= rank < world:
+        raise ValueError(f"rank {rank} outside a world of {world}")
+    if world > len(files):
+        raise ValueError(f"{world} ranks but only {len(files)} .arrow files: every rank needs at least one")
+    per = len(files) // world
+    return files[rank * per:(rank + 1) * per]
+
+
+def accumulation_per_rank(gradient_accumulation_steps, world):
+    """train.py:130-131: the micro-steps of an iteration are divided among the ranks."""
+    if gradient_accumulation_steps % world != 0:
+        raise ValueError(f"gradient_accumulation_steps = {gradient_accumulation_steps} is not a multiple of the world size {world}")
+    return gradient_accumulation_steps // world
+
+
+def param_checksum(net):
+    """Wrap-around int64 sum of the parameters' fp32 bit patterns, computed on the device: equal on ranks whose weights are bit-identical.
+    The data-parallel loop never broadcasts weights, so it compares this across the ranks instead."""
+    sd = net.state_dict()
+    total = torch.zeros((), dtype=torch.int64, device=net.device)
+    for name, _ in net.named_parameters():
+        total += sd[name].view(torch.int32).sum(dtype=torch.int64)
+    return int(total.item())
+
+
 class ArrowBatches:
     """= MapfArrowDataset.__iter__ (fast_data_loader.py:39-67): files in name order, forever; each file's rows shuffled when it is loaded
     (one numpy Generator seeded once), batches of batch_size consecutive rows (the last one of a file may be shorter).  Yields
-    (inputs int8 [b, 256], targets int64 [b, 256]) on the host: -1 everywhere except position 255 = the expert action."""
+    (inputs int8 [b, 256], targets int64 [b, 256]) on the host: -1 everywhere except position 255 = the expert action.  rank / world: the
+    files are dealt to the ranks of a data-parallel run (rank_files) and the generator is seeded with seed + rank; the defaults change nothing."""
 
-    def __init__(self, path, batch_size, seed=1337):
-        self.files = shard_files(path)
+    def __init__(self, path, batch_size, seed=1337, rank=0, world=1):
+        self.files = rank_files(shard_files(path), rank, world)
         self.batch_size = int(batch_size)
-        self.rng = np.random.Generator(np.random.PCG64(seed))
+        self.rng = np.random.Generator(np.random.PCG64(seed + rank))     # train.py:127,142: every rank its own shuffle
 
     def load(self, f):
         from .scoring import read_arrow
@@ -105,6 +149,12 @@ def parse_args(argv=None):
             ap.add_argument("--" + k.replace("_", "-"), type=type(v), default=v)
     ap.add_argument("--dtype", default="float32", choices=["float32", "bfloat16", "float16"],
                     help="float32 (default here; train.py defaults to bfloat16) or bfloat16 (autocast regime); float16 is refused")
+    ap.add_argument("--log-interval", type=int, default=0,
+                    help='print {"iter", "loss", "ms"} every N iterations (train.py:346-355); 0 = no such line')
+    ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
+                    help="process-group backend of a data-parallel run (RANK set): nccl = RCCL (train.py:58), gloo stages the gather through the host")
+    ap.add_argument("--share-gpu", action="store_true",
+                    help="data-parallel dry run on a one-GPU box: every rank uses cuda:0 instead of cuda:LOCAL_RANK")
     a = ap.parse_args(argv)
     if a.dtype == "float16":
         ap.error("--dtype float16 is not supported: it needs torch's GradScaler, which this training path does not have "
@@ -113,19 +163,86 @@ def parse_args(argv=None):
     return a
 
 
+class Ranks:
+    """The process group of a data-parallel run (train.py:118-138): RANK, LOCAL_RANK and WORLD_SIZE from the launcher's environment, the
+    device cuda:LOCAL_RANK (share_gpu: cuda:0), the gradient synchronisation and the lockstep guard."""
+
+    def __init__(self, backend, share_gpu=False):
+        import torch.distributed as dist
+        self.dist, self.backend = dist, backend
+        self.rank, self.local_rank, world = (int(os.environ[k]) for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"))
+        index = 0 if share_gpu else self.local_rank
+        if index >= torch.cuda.device_count():
+            raise RuntimeError(f"LOCAL_RANK {self.local_rank} but only {torch.cuda.device_count()} visible GPUs: one rank per GPU "
+                               "(--share-gpu puts every rank on cuda:0 for a dry run)")
+        self.device = torch.device("cuda", index)
+        torch.cuda.set_device(self.device)
+        if backend == "nccl":
+            dist.init_process_group("nccl", rank=self.rank, world_size=world, device_id=self.device)
+        else:
+            dist.init_process_group(backend, rank=self.rank, world_size=world)
+        self.world = dist.get_world_size()
+        self.master = self.rank == 0                   # train.py:126: evaluation, checkpoints and every stdout line
+        self.coll_device = self.device if backend == "nccl" else torch.device("cpu")
+        self.flat = self.gathered = None
+
+    def sync_grads(self, net):
+        """export_grads -> all_gather -> reduce_grads(gathered, 1 / world): the ranks' mean, added in rank order by one kernel, the same bits
+        on every rank.  gloo has no device collectives: the buffers go through the host (as runner.gather_metrics stages its records)."""
+        if self.gathered is None:
+            n = net.grads_size()
+            self.flat = torch.empty(n, dtype=torch.float32, device=self.device)
+            self.gathered = torch.empty((self.world, n), dtype=torch.float32, device=self.device)
+        net.export_grads(self.flat)
+        if self.backend == "nccl":
+            self.dist.all_gather_into_tensor(self.gathered, self.flat)
+        else:
+            host = self.flat.cpu()
+            parts = [torch.empty_like(host) for _ in range(self.world)]
+            self.dist.all_gather(parts, host)
+            for r, part in enumerate(parts):
+                self.gathered[r].copy_(part)
+        net.reduce_grads(self.gathered, 1.0 / self.world)
+
+    def check_lockstep(self, net, iter_num):
+        """Every rank's param_checksum, gathered (8 bytes each); a mismatch raises on every rank.  Weights are never broadcast, so a
+        divergence would otherwise be silent."""
+        mine = torch.tensor([param_checksum(net)], dtype=torch.int64, device=self.coll_device)
+        parts = [torch.empty_like(mine) for _ in range(self.world)]
+        self.dist.all_gather(parts, mine)
+        sums = [int(p.item()) for p in parts]
+        if len(set(sums)) != 1:
+            raise RuntimeError(f"the ranks' weights diverged at iteration {iter_num}: param_checksum per rank {sums}")
+        return sums
+
+    def close(self):
+        self.dist.destroy_process_group()
+
+
 def main(argv=None):
     a = parse_args(argv)
+    ranks = Ranks(a.backend, a.share_gpu) if "RANK" in os.environ else None      # train.py:118: is this a data-parallel run?
+    try:
+        return run(a, ranks)
+    finally:
+        if ranks is not None:
+            ranks.close()                          # train.py:364-365
+
+
+def run(a, ranks):
     config = {k: getattr(a, k) for k in DEFAULTS}
     config["dtype"] = a.dtype
     from . import scoring, weights
     from .model import GPT, GPTConfig
 
+    rank, world, master = (ranks.rank, ranks.world, ranks.master) if ranks else (0, 1, True)
+    accum = accumulation_per_rank(a.gradient_accumulation_steps, world)
     ckpt = None
     if os.path.exists(a.init):
         args, sd = weights.load_checkpoint(a.init)
         if a.resume:
             ckpt = torch.load(a.init, map_location="cpu", weights_only=True)
-    else:
+    else:                                          # --seed on every rank: all build the weights DDP would broadcast from rank 0
         args, sd = weights.model_args(a.init), weights.synthetic_state_dict(a.init, seed=a.seed)
     net = GPT(GPTConfig(**args), max_rows=a.batch_size, precision="f32")
     net.load_state_dict(sd)
@@ -135,9 +252,10 @@ def main(argv=None):
     if ckpt is not None:
         opt.load_state_dict(ckpt["optimizer"])
         iter_num, best_val_loss = int(ckpt["iter_num"]), float(ckpt["best_val_loss"])
-    train_it = iter(ArrowBatches(a.data, a.batch_size, a.seed))
-    val_it = iter(ArrowBatches(a.val, a.batch_size, a.seed + 1))
-    os.makedirs(a.out_dir, exist_ok=True)
+    train_it = iter(ArrowBatches(a.data, a.batch_size, a.seed, rank, world))
+    val_it = iter(ArrowBatches(a.val, a.batch_size, a.seed + 1))          # (the validation split is not divided)
+    if master:
+        os.makedirs(a.out_dir, exist_ok=True)
     model_args = {k: args[k] for k in ("n_layer", "n_head", "n_embd", "block_size", "bias", "vocab_size", "dropout")}
 
     def estimate_loss():                      # train.py:244-259, eval_iters batches of each split
@@ -152,11 +270,14 @@ def main(argv=None):
 
     X, Y = next(train_it)
     loss = None
+    t0 = time.monotonic()
     while True:
         lr = get_lr(iter_num, a.learning_rate, a.warmup_iters, a.lr_decay_iters, a.min_lr) if a.decay_lr else a.learning_rate
         for g in opt.param_groups:
             g["lr"] = lr
-        if iter_num % a.eval_interval == 0:
+        if iter_num % a.eval_interval == 0 and ranks is not None:
+            ranks.check_lockstep(net, iter_num)
+        if iter_num % a.eval_interval == 0 and master:          # train.py:292
             losses = estimate_loss()
             rec = {"iter": iter_num, "train_loss": losses["train"], "val_loss": losses["val"], "lr": lr}
             if losses["val"] < best_val_loss or a.always_save_checkpoint:
@@ -167,19 +288,28 @@ def main(argv=None):
                                os.path.join(a.out_dir, "ckpt.pt"))
                     rec["saved"] = os.path.join(a.out_dir, "ckpt.pt")
             print(json.dumps(rec), flush=True)
-        for _ in range(a.gradient_accumulation_steps):         # train.py:314-331
-            loss = net.forward_backward(torch.as_tensor(X), torch.as_tensor(Y), loss_scale=1.0 / a.gradient_accumulation_steps,
-                                       precision=a.precision)
+        for _ in range(accum):                                 # train.py:314-331
+            loss = net.forward_backward(torch.as_tensor(X), torch.as_tensor(Y), loss_scale=1.0 / accum, precision=a.precision)
             X, Y = next(train_it)
+        if ranks is not None:                                  # train.py:315-322: the ranks' gradients meet after the last micro-step
+            ranks.sync_grads(net)
         if a.grad_clip != 0.0:
             net.clip_grad_norm_(a.grad_clip)
         opt.step()
         opt.zero_grad(set_to_none=True)
+        if a.log_interval > 0 and iter_num % a.log_interval == 0 and master:      # train.py:346-355 (float(loss) waits for the device)
+            lossf, t1 = float(loss), time.monotonic()
+            print(json.dumps({"iter": iter_num, "loss": lossf, "ms": round((t1 - t0) * 1e3, 3)}), flush=True)
+        t0 = time.monotonic()
         iter_num += 1
         if iter_num > a.max_iters:
             break
     res = {"iter": iter_num, "loss": float(loss), "best_val_loss": float(best_val_loss)}
-    print(json.dumps(res), flush=True)
+    if ranks is not None:
+        res["world"] = world
+        res["param_checksums"] = ranks.check_lockstep(net, iter_num)
+    if master:
+        print(json.dumps(res), flush=True)
     return res
 
 

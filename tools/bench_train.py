@@ -3,6 +3,7 @@ as a yardstick only, torch fp32 eager autograd of an in-repo restatement of mode
 
     python tools/bench_train.py [--shapes 6M:512,6M:2048,2M:4096,85M:512] [--precision f32,bf16] [--torch-rows 512] [--iters 3] [--warmup 1]
                                 [--lib PATH]
+    python tools/bench_train.py --grad-sync WORLD [--grad-sync-shapes 6M,85M] [--iters 5] [--warmup 2]
 
 --lib PATH times another build of the library (a file tools/build_ab.sh writes) in place of the in-tree one.
 --precision f32,bf16 times both training precisions in one call (one JSON line per shape and precision).  Every line carries the counted
@@ -10,6 +11,12 @@ flops of the call (the products the model executes, 2 per multiply-add, backward
 excluded) and, for bf16, the bytes its kernels move to and from memory (count_bytes below: every tensor read or written once per kernel,
 weights and L2 reuse not counted), with the achieved rate and the roofline bound against 2.5 PFLOP/s (bf16 MFMA) or 157 TFLOP/s (fp32) and
 8 TB/s.  The bf16 torch yardstick is the same restatement under torch.autocast("cuda", torch.bfloat16), train.py's regime.
+
+--grad-sync WORLD times the device side of the data-parallel gradient synchronisation on one GPU (mapf_gpt_amd/training.py: export_grads,
+all_gather, reduce_grads): GPT.export_grads() and GPT.reduce_grads(gathered, 1 / WORLD) with a gathered array of WORLD rows of the size of the
+rank's own buffer, each as the median over --iters windows of 20 back-to-back calls between HIP events.  One JSON line per shape: microseconds
+per call and the fraction of 8 TB/s by counted bytes (export: read n and write n floats; reduce: read WORLD x n and write n, (WORLD + 1) 4 n
+bytes).  The all_gather itself is not in it: it needs the other ranks.  Nothing else runs in that mode.
 
 Targets follow the dataset's pattern (-1 except the last position, fast_data_loader.py:58).  Prints one JSON line per shape: median ms of
 each part over --iters timed calls after --warmup untimed ones, HIP events on the current stream.  The torch yardstick runs on
@@ -82,6 +89,32 @@ def torch_step(name, tokens, targets, autocast=False):
     return step
 
 
+def grad_sync(world, shapes, iters, warmup, reps=20):
+    """export_grads and reduce_grads of every shape: microseconds per call and the fraction of PEAK_BYTES by counted bytes"""
+    for name in shapes:
+        net = build_model(name, seed=0, max_rows=1).train()
+        n = net.grads_size()
+        flat = torch.empty(n, dtype=torch.float32, device="cuda")
+        gathered = torch.randn((world, n), dtype=torch.float32, device="cuda")
+
+        def export():
+            for _ in range(reps):
+                net.export_grads(flat)
+
+        def reduce():
+            for _ in range(reps):
+                net.reduce_grads(gathered, 1.0 / world)
+        ex, rd = timed(export, iters, warmup) / reps * 1e3, timed(reduce, iters, warmup) / reps * 1e3
+        ex_bytes, rd_bytes = 2 * 4 * n, (world + 1) * 4 * n
+        print(json.dumps({"shape": name, "grad_sync_world": world, "n_elem": n, "buffer_mb": round(4 * n / 1e6, 1),
+                          "export_us": round(ex, 1), "export_frac_of_8TBps": round(ex_bytes / (ex * 1e-6) / PEAK_BYTES, 3),
+                          "reduce_us": round(rd, 1), "reduce_mb": round(rd_bytes / 1e6, 1),
+                          "reduce_frac_of_8TBps": round(rd_bytes / (rd * 1e-6) / PEAK_BYTES, 3),
+                          "received_mb_per_rank": round((world - 1) * 4 * n / 1e6, 1)}), flush=True)
+        del net, flat, gathered
+        torch.cuda.empty_cache()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="6M:512,6M:2048,2M:4096,85M:512")
@@ -90,10 +123,15 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--lib", default=None, help="path of the library to time (default: the in-tree build)")
+    ap.add_argument("--grad-sync", type=int, default=0, metavar="WORLD",
+                    help="time export_grads and reduce_grads over WORLD gathered buffers instead of the training step")
+    ap.add_argument("--grad-sync-shapes", default="6M,85M")
     a = ap.parse_args(argv)
     if a.lib:
         from mapf_gpt_amd import _lib
         _lib.LIB_PATH = os.path.abspath(a.lib)
+    if a.grad_sync > 0:
+        return grad_sync(a.grad_sync, a.grad_sync_shapes.split(","), a.iters, a.warmup)
     for item in a.shapes.split(","):
         name, rows = item.split(":")
         rows = int(rows)
