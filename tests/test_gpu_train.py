@@ -1,7 +1,7 @@
 """Training on the device (GPT.forward_backward, clip_grad_norm_, configure_optimizers -> AdamW; include/mapf_gpt_amd.h mgpt_gpt_train_*):
 gradients against fp64 autograd of the pinned oracle's restatement of model.py, loss, determinism, accumulation, chunking, clip + AdamW
 against torch's, optimizer state round trip, inference after training in every precision, and a short training run on expert rows."""
-import os
+import functools
 
 import numpy as np
 import pytest
@@ -9,31 +9,22 @@ import torch
 
 from mapf_gpt_amd import _lib, weights
 from mapf_gpt_amd.model import GPT, GPTConfig, build_model
-from tests.helpers import GOLDEN
-from tests.train_ref import leaves, loss_and_grads, targets_last
+from tests.train_ref import LOCALISERS, expert_rows, leaves, loss_and_grads, targets_last, targets_mixed, trained_like_case
 
 pytestmark = pytest.mark.gpu
 
 
 def _rows(n, seed=0):
-    """expert rows of the committed dataset fixtures (inputs / gt_actions of the reference's tokenizer)"""
-    a, b = np.load(os.path.join(GOLDEN, "ds_random.npz")), np.load(os.path.join(GOLDEN, "ds_maze.npz"))
-    x = np.concatenate([a["inputs"], b["inputs"]]).astype(np.int64)
-    y = np.concatenate([a["gt_actions"], b["gt_actions"]]).astype(np.int64)
-    idx = np.random.Generator(np.random.PCG64(seed)).permutation(len(x))[:n]
-    return x[idx], y[idx]
+    return expert_rows(n, seed)
 
 
 def _targets(case, tokens, actions, seed=1):
     rows = len(tokens)
-    rng = np.random.Generator(np.random.PCG64(seed))
     if case == "last":
         return targets_last(actions)
-    t = rng.integers(0, 67, (rows, 256)).astype(np.int64)
     if case == "mixed":
-        t[rng.random((rows, 256)) < 0.5] = -1
-        t[1] = -1                                     # a row with no targeted position
-    return t
+        return targets_mixed(rows, seed)
+    return np.random.Generator(np.random.PCG64(seed)).integers(0, 67, (rows, 256)).astype(np.int64)
 
 
 def _net(name, max_rows=4, seed=0, train_rows=None):
@@ -47,13 +38,24 @@ def _dev_grads(net):
     return {k: v.double().cpu() for k, v in net.grads().items()}
 
 
-def _check_grads(name, got, g64, g32):
-    worst = 0.0
+def _grad_figures(got, g64, g32):
+    """per tensor: (name, max|g - g64|, the bar max(4 x fp32-autograd error, 1e-6 max|g64|), fp32-autograd error, max|g64|)"""
+    out = []
     for k, ref in g64.items():
         m = float(ref.abs().max())
         err = float((got[k] - ref).abs().max())
         e32 = float((g32[k].double() - ref).abs().max())
-        bar = max(4 * e32, 1e-6 * m)
+        out.append((k, err, max(4 * e32, 1e-6 * m), e32, m))
+    return out
+
+
+def _check_grads(name, got, g64, g32):
+    figures = _grad_figures(got, g64, g32)
+    k, err, bar, _, _ = max(figures, key=lambda f: f[1] / max(f[2], 1e-300))
+    print(f"{name}: worst error / bar {err / max(bar, 1e-300):.3f} ({k})")
+    worst = 0.0
+    for k, err, bar, e32, m in figures:
+        assert np.isfinite(err), f"{name} {k}: gradient not finite"
         assert err <= bar and err <= 1e-4 * m, f"{name} {k}: max|g - g64| {err:.3e}, bar {bar:.3e} (fp32 autograd {e32:.3e}, max|g64| {m:.3e})"
         worst = max(worst, err / max(m, 1e-30))
     return worst
@@ -113,6 +115,97 @@ def test_chunked_call_matches_one_chunk():
     _, g32 = loss_and_grads(small._sd, small._args, tokens, targets, torch.float32)
     _check_grads("chunked", _dev_grads(small), g64, g32)
     assert abs(ls - l64) <= 1e-5 * l64
+
+
+# ----- the trained-like regime (tests/train_ref.py: trained_like_state_dict; tests/test_train_cpu.py pins it): peaked attention, GELU tails,
+# LayerNorm gains of both signs.  At N(0, 0.02) attention is nearly uniform and a key or slot mix-up changes a ~10 % correction only.
+def _trained_net(args, sd, max_rows=4, train_rows=None):
+    net = build_model(args, state_dict=sd, max_rows=max_rows)
+    net._sd, net._args = sd, args
+    return net.train(max_rows=train_rows)
+
+
+@functools.lru_cache(maxsize=None)
+def _trained_ref(name, rows=None):
+    """one fp64 and one fp32 autograd run per case, shared by the tests that need it and left unchanged"""
+    tokens, targets, sd, args = trained_like_case(name, rows)
+    l64, g64 = loss_and_grads(sd, args, tokens, targets, torch.float64)
+    _, g32 = loss_and_grads(sd, args, tokens, targets, torch.float32)
+    return tokens, targets, sd, args, l64, g64, g32
+
+
+def _by_kernel(g, C):
+    """the block gradients of a one-layer model, c_attn.weight's by its q, k and v thirds: a failure names a kernel"""
+    p = "transformer.h.0."
+    out = {f"c_attn.{nm}": g[p + "attn.c_attn.weight"][i * C:(i + 1) * C] for i, nm in enumerate("qkv")}
+    out.update({nm: g[p + nm + ".weight"] for nm in ("attn.c_proj", "ln_1", "ln_2", "mlp.c_fc", "mlp.c_proj")})
+    return out
+
+
+def _kernel_report(name, got, g64, g32, C):
+    figures = _grad_figures(*(_by_kernel(g, C) for g in (got, g64, g32)))
+    return f"{name} by kernel: " + "; ".join(f"{k} {err:.3e} = {err / max(bar, 1e-300):.2f} x bar (max|g64| {m:.3e})" for k, err, bar, _, m in figures)
+
+
+@pytest.mark.parametrize("name", ["tiny", "2M", "6M", "85M", *LOCALISERS])
+def test_trained_like_gradients_match_fp64_autograd(name):
+    tokens, targets, sd, args, l64, g64, g32 = _trained_ref(name)
+    net = _trained_net(args, sd)
+    tk, tg = torch.as_tensor(tokens), torch.as_tensor(targets)
+    net.zero_grad()
+    loss = float(net.forward_backward(tk, tg))
+    got = _dev_grads(net)
+    assert set(got) == set(g64)
+    for k, v in got.items():
+        assert bool(torch.isfinite(v).all()), f"{name} {k}: gradient not finite"
+    try:
+        _check_grads(f"trained-like {name}", got, g64, g32)
+    except AssertionError as e:
+        if name in LOCALISERS:
+            raise AssertionError(f"{e}\n{_kernel_report(name, got, g64, g32, args['n_embd'])}") from None
+        raise
+    assert abs(loss - l64) <= 1e-5 * abs(l64), (loss, l64)
+    net.zero_grad()
+    again = float(net.forward_backward(tk, tg))
+    b = _dev_grads(net)
+    assert again == loss
+    for k in got:
+        assert torch.equal(got[k], b[k]), f"{name} {k}: two identical calls differ"
+
+
+# ----- ragged and empty weight-gradient slabs (train.hip: slabs_of, slab_tokens, kMaxSlabs = 64).  Up to 64 rows a slab is 256 tokens and
+# every slab is full.  65 rows: 16640 tokens in 64 slabs of 272 (fp32; slab 61 holds 48 tokens, 62 and 63 none) or of 288 (bf16; slab 57
+# holds 224, 58 - 63 none).  130 rows: slabs of 528 (fp32; slab 63 holds 16) or 544 (bf16; slab 61 holds 96, 62 and 63 none).
+@pytest.mark.parametrize("rows", [65, 130])
+def test_ragged_weight_gradient_slabs(rows):
+    tokens, targets, sd, args, l64, g64, g32 = _trained_ref("tiny", rows)
+    net = _trained_net(args, sd, train_rows=rows)
+    net.zero_grad()
+    loss = float(net.forward_backward(torch.as_tensor(tokens), torch.as_tensor(targets)))
+    _check_grads(f"{rows} rows, one chunk", _dev_grads(net), g64, g32)
+    assert abs(loss - l64) <= 1e-5 * abs(l64), (loss, l64)
+    if rows == 130:
+        # ... and as two full chunks of 65 rows: the same bars, the same loss
+        net.train(max_rows=65)
+        net.zero_grad()
+        two = float(net.forward_backward(torch.as_tensor(tokens), torch.as_tensor(targets)))
+        _check_grads("130 rows, chunks of 65", _dev_grads(net), g64, g32)
+        assert abs(two - l64) <= 1e-5 * abs(l64), (two, l64)
+        assert abs(two - loss) <= 1e-6 * abs(loss), (two, loss)
+
+
+def test_one_targeted_position():
+    """count = 1: the call's normaliser is 1, every other token's dlogits row is zero"""
+    tokens, _, sd, args = trained_like_case("tiny", 2)
+    targets = np.full((2, 256), -1, np.int64)
+    targets[1, 137] = 41
+    net = _trained_net(args, sd)
+    net.zero_grad()
+    loss = float(net.forward_backward(torch.as_tensor(tokens), torch.as_tensor(targets)))
+    l64, g64 = loss_and_grads(sd, args, tokens, targets, torch.float64)
+    _, g32 = loss_and_grads(sd, args, tokens, targets, torch.float32)
+    _check_grads("one target", _dev_grads(net), g64, g32)
+    assert abs(loss - l64) <= 1e-5 * abs(l64), (loss, l64)
 
 
 def test_refusals():
@@ -213,6 +306,49 @@ def test_clip_and_adamw_match_torch():
     s1, s2 = net.state_dict(), net2.state_dict()
     for k in s1:
         assert torch.equal(s1[k], s2[k]), k
+
+
+def test_clip_above_the_total_norm_changes_nothing():
+    tokens, targets, sd, args, *_ = _trained_ref("tiny")
+    net = _trained_net(args, sd)
+    net.zero_grad()
+    net.forward_backward(torch.as_tensor(tokens), torch.as_tensor(targets))
+    before = _dev_grads(net)
+    lv, _ = leaves(sd, torch.float64)
+    for n, v in lv.items():
+        v.grad = before[n].clone()
+    tn = float(torch.nn.utils.clip_grad_norm_(list(lv.values()), 1e30))
+    total = float(net.clip_grad_norm_(2.0 * tn))              # coefficient min(2 tn / (tn + 1e-6), 1) = 1
+    assert abs(total - tn) <= 1e-6 * tn, (total, tn)
+    after = _dev_grads(net)
+    for k in before:
+        assert torch.equal(before[k], after[k]), f"{k}: a clip above the total norm changed the gradient"
+
+
+def test_clip_and_adamw_on_the_trained_like_checkpoint():
+    """one clip + AdamW step where the total norm is far above max_norm (about 30 on this checkpoint: a coefficient near 0.03)"""
+    tokens, targets, sd, args, *_ = _trained_ref("2M")
+    net = _trained_net(args, sd)
+    opt = net.configure_optimizers(0.1, 6e-4, (0.9, 0.95), "cuda")
+    lv, topt = _torch_adamw(sd, net.named_parameters(), 0.1, 6e-4, (0.9, 0.95))
+    net.zero_grad()
+    net.forward_backward(torch.as_tensor(tokens), torch.as_tensor(targets))
+    g = _dev_grads(net)                                       # the library's own gradients into torch's clip + AdamW (fp64)
+    for n, v in lv.items():
+        v.grad = g[n].clone()
+    tn = float(torch.nn.utils.clip_grad_norm_(list(lv.values()), 1.0))
+    assert tn > 10.0, tn
+    total = float(net.clip_grad_norm_(1.0))
+    assert abs(total - tn) <= 1e-6 * tn + 1e-9, (total, tn)
+    gc = _dev_grads(net)
+    for n, v in lv.items():
+        assert float((gc[n] - v.grad).abs().max()) <= 1e-6 * float(v.grad.abs().max()) + 1e-12, n
+    opt.step()
+    topt.step()
+    new = net.state_dict()
+    for n, v in lv.items():
+        d = float((new[n].double().cpu() - v.detach()).abs().max())
+        assert d <= 1e-6 * float(v.detach().abs().max()) + 1e-9, (n, d)
 
 
 def test_inference_after_training_serves_new_weights():

@@ -1,11 +1,14 @@
 """CPU checks of the training CLI (mapf_gpt_amd/training.py): its learning-rate schedule against a restatement of train.py:263-276 and its
-batches against a restatement of fast_data_loader.py:39-67 with train.py:162-165 (targets -1 except the last position, a per-file shuffle)."""
+batches against a restatement of fast_data_loader.py:39-67 with train.py:162-165 (targets -1 except the last position, a per-file shuffle);
+and of the trained-like checkpoint recipe of the device gradient tests (tests/train_ref.py) against the fp64 oracle."""
 import math
 
 import numpy as np
 import pytest
+import torch
 
-from mapf_gpt_amd import training
+from mapf_gpt_amd import training, weights
+from tests import train_ref
 
 
 def ref_lr(it, learning_rate=6e-4, warmup_iters=2000, lr_decay_iters=30000, min_lr=6e-5):
@@ -62,3 +65,28 @@ def test_batches_match_fast_data_loader(tmp_path):
     one = iter(training.ArrowBatches(str(tmp_path / "part_1.arrow"), 8, seed=0))
     x1, t1 = next(one)
     assert x1.shape == (3, 256) and sorted(t1[:, -1].tolist()) == sorted(shards[1][1].tolist())
+
+
+@pytest.mark.parametrize("name", ["tiny", "2M", "6M", "85M", *train_ref.LOCALISERS])
+def test_trained_like_recipe_reaches_its_regime(name):
+    """Conditions on the INPUTS of tests/test_gpu_train.py's and test_gpu_train_bf16.py's trained-like cases, on the fp64 oracle alone:
+    peaked attention, GELU tails, gains of both signs and near zero, and a reference that meets _check_grads' hard clause itself."""
+    tokens, targets, sd, args = train_ref.trained_like_case(name)
+    for l, (spread, tail) in enumerate(train_ref.regime(sd, args, tokens)):
+        assert spread >= 8.0, f"{name} layer {l}: median per-query score spread {spread:.2f} nats"
+        assert tail >= 0.01, f"{name} layer {l}: share of |a| > 3 is {tail:.4f}"
+    gains = [k for k in sd if k.endswith(("ln_1.weight", "ln_2.weight", "ln_f.weight"))]
+    assert len(gains) == 2 * args["n_layer"] + 1
+    for k in gains:
+        assert sd[k].min() < 0 and np.abs(sd[k]).min() < 0.05, k
+    base = weights.synthetic_state_dict(args, seed=0)
+    assert set(sd) == set(base) and all(sd[k].shape == base[k].shape and sd[k].dtype == np.float32 for k in base)
+    assert sd["lm_head.weight"] is sd["transformer.wte.weight"]
+    l64, g64 = train_ref.loss_and_grads(sd, args, tokens, targets, torch.float64)
+    _, g32 = train_ref.loss_and_grads(sd, args, tokens, targets, torch.float32)
+    assert math.isfinite(l64)
+    for k, ref in g64.items():
+        assert bool(torch.isfinite(ref).all()), k
+        m = float(ref.abs().max())
+        e32 = float((g32[k].double() - ref).abs().max())
+        assert m > 0 and e32 <= 1e-4 * m, f"{name} {k}: fp32 autograd {e32:.3e}, max|g64| {m:.3e}"
