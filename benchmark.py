@@ -21,6 +21,8 @@ def main():
     ap.add_argument("--weights", nargs="*", default=[], help="ALGORITHM=path overrides of path_to_weights")
     ap.add_argument("--precision", default="f16x3", choices=["f32", "f16x3", "bf16"],
                     help="policy arithmetic of every algorithm entry (the adapter's own default is f32)")
+    ap.add_argument("--retire-done", action="store_true",
+                    help="stop forwarding finished episodes and end a batch when none is live (same records; off by default)")
     a = ap.parse_args()
 
     import torch
@@ -55,7 +57,8 @@ def main():
                 algo["device"] = f"cuda:{0 if os.environ.get('MGPT_BENCH_SHARE_GPU') else int(os.environ.get('LOCAL_RANK', '0'))}"
         if rank == 0:
             print(f"=== {folder}")
-        ev.evaluation(cfg, eval_dir=os.path.join(a.eval_root, folder), registry=reg, precision=a.precision, rank=rank, world=world)
+        ev.evaluation(cfg, eval_dir=os.path.join(a.eval_root, folder), registry=reg, precision=a.precision, rank=rank, world=world,
+                      retire_done=a.retire_done)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -360,6 +360,17 @@ int mgpt_gpt_grads_reduce(mgpt_gpt *gpt, const float *d_gathered, int world, flo
 /* sampling alone (same RNG and key as mgpt_gpt_act), for callers that already hold logits */
 int mgpt_sample_actions(const float *d_logits, int rows, int32_t *d_actions, int do_sample,
                         uint64_t seed, uint64_t step, uint64_t row0, void *stream);
+/* The same on the COMPACT logits of a subset of the instances (the sampler of the step object's retire mode, below): d_live int32 holds
+ * the ids of the chosen instances, *d_count (device int32) how many; compact row j of d_logits [*d_count * n_agents, 67] belongs to
+ * instance d_live[j / n_agents], agent j % n_agents.  Its action goes to d_actions[d_live[j / n_agents] * n_agents + j % n_agents] and its
+ * draw is keyed by row0 + that index: every chosen row gets what mgpt_sample_actions gives it on the full logits.  Other entries of
+ * d_actions are not written.  The count is read on the device: no synchronisation. */
+int mgpt_sample_actions_live(const float *d_logits, const int32_t *d_live, const int32_t *d_count, int n_agents, int32_t *d_actions,
+                             int do_sample, uint64_t seed, uint64_t step, uint64_t row0, void *stream);
+/* Ordered list of the instances that are not done: d_done uint8 [n_inst] (mgpt_env_state) -> d_live int32 [n_inst]: the indices i with
+ * d_done[i] == 0 in ascending order, then -1; *d_count (device int32) = how many.  A stable stream compaction in one workgroup (wave
+ * ballots, an LDS pass over the wave totals), no atomics: the same flags give the same bits.  n_inst >= 1. */
+int mgpt_live_list(const uint8_t *d_done, int n_inst, int32_t *d_live, int32_t *d_count, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * One whole environment step = the body of the reference's episode loop (example.py:63-65 around
@@ -373,6 +384,26 @@ int mgpt_sample_actions(const float *d_logits, int rows, int32_t *d_actions, int
  *           (identical results); eager is also used while the timing hooks are enabled.
  *   reset:  sets the RNG step counter (call with 0 when an episode starts; the k-th run after it draws with step k) and
  *           drops the captured graph -- call it after anything that re-allocates inside the contexts (mgpt_env_set_lifelong).
+ *           In retire mode it also makes every instance live again.
+ * Retire mode (opt-in): the reference's run_episode leaves an episode when all agents are terminated or truncated (create_env.py:15-18);
+ * a batch keeps stepping, but the policy -- about 99 % of a step -- need not see the finished instances.
+ *   set_retire: enable != 0 allocates an ordered list of live instance ids, its count (device int32 + a pinned host int32), a compact
+ *           token buffer [rows, 256] and compact logits [rows, 67]; every instance starts live.  enable == 0 frees them and restores the
+ *           plain step exactly.  Synchronous.
+ *   poll_live:  mgpt_live_list on the env's done flags, the count copied to the pinned int, `stream` synchronised, the count returned in
+ *           *n_live (may be NULL).  The only host synchronisation of the mode.  Between polls the list and the policy's row count are
+ *           FROZEN: an instance that finishes inside the window is forwarded until the next poll, which changes nothing, because the env
+ *           ignores the actions of a done instance.
+ *   run in retire mode: update_agents and generate_observations on ALL rows (d_tokens holds the full batch's rows, as ever), a gather of
+ *           the live instances' rows, the forward on those n_live * n_agents rows (the call regime follows that row count, as for any
+ *           call), mgpt_sample_actions_live into d_actions -- the entries of retired instances keep their last value --, env.step, the
+ *           step-counter bump.  With no live instance the gather, the forward and the sampler are skipped.  Draws are keyed by the global
+ *           row, so the MGPT_PREC_F32 kernels, which compute a row from that row alone, give every live row the bits of the plain step;
+ *           the 16-bit paths pick different kernels at <= 128 and above 128 rows, so a compacted call can differ from the plain one in the
+ *           last bits of a logit (within the envelope's bar).  use_graph != 0: MGPT_ERR_UNSUPPORTED (the row count changes).
+ *           d_tokens must be 16-byte aligned.
+ *   copy_live:  test/debug: the live list (int32 [n_inst]) and the compact logits of the last run (float32 [rows, 67], the first
+ *           n_live * n_agents rows valid) into caller-owned device buffers; either may be NULL.
  * ------------------------------------------------------------------------------------------ */
 typedef struct mgpt_step mgpt_step;
 int mgpt_step_create(mgpt_step **out, mgpt_tokenizer *tok, mgpt_gpt *gpt, mgpt_env *env, int rows, int precision,
@@ -380,6 +411,9 @@ int mgpt_step_create(mgpt_step **out, mgpt_tokenizer *tok, mgpt_gpt *gpt, mgpt_e
 int mgpt_step_destroy(mgpt_step *step);
 int mgpt_step_reset(mgpt_step *step, uint64_t step0, void *stream);
 int mgpt_step_run(mgpt_step *step, uint8_t *d_tokens, int32_t *d_actions, int goals_may_change, int use_graph, void *stream);
+int mgpt_step_set_retire(mgpt_step *step, int enable);
+int mgpt_step_poll_live(mgpt_step *step, int *n_live, void *stream);
+int mgpt_step_copy_live(mgpt_step *step, int32_t *d_live_out, float *d_logits_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Dataset-side bulk tokenizer: replaces dataset/tokenizer/generate_observations.py:8-92 with its two native modules

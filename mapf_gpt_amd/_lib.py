@@ -89,6 +89,9 @@ SYMBOLS = {
     "mgpt_step_destroy": (_i, [_vp]),
     "mgpt_step_reset": (_i, [_vp, _u64, _vp]),
     "mgpt_step_run": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "mgpt_step_set_retire": (_i, [_vp, _i]),
+    "mgpt_step_poll_live": (_i, [_vp, ctypes.POINTER(_i), _vp]),
+    "mgpt_step_copy_live": (_i, [_vp, _vp, _vp, _vp]),
     "mgpt_gpt_debug_copy": (_i, [_vp, _i, _vp, _i64, _vp]),
     "mgpt_gpt_debug_copy_raw": (_i, [_vp, _i, _i, _vp, _i64, _vp]),
     "mgpt_gpt_debug_counter": (_i, [_i, ctypes.POINTER(_u64), _i]),
@@ -96,6 +99,8 @@ SYMBOLS = {
     "mgpt_gpt_envelope": (_i, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_i)]),
     "mgpt_gpt_envelope_probe": (_i, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "mgpt_sample_actions": (_i, [_vp, _i, _vp, _i, _u64, _u64, _u64, _vp]),
+    "mgpt_sample_actions_live": (_i, [_vp, _vp, _vp, _i, _vp, _i, _u64, _u64, _u64, _vp]),
+    "mgpt_live_list": (_i, [_vp, _i, _vp, _vp, _vp]),
     "mgpt_gpt_train_alloc": (_i, [_vp, _i]),
     "mgpt_gpt_train_free": (_i, [_vp]),
     "mgpt_gpt_forward_backward": (_i, [_vp, _vp, _i, _i, _vp, ctypes.c_float, _vp, _vp]),

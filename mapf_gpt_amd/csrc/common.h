@@ -19,6 +19,11 @@ void set_error(const char *fmt, ...);
 // (The tokenizer context never re-allocates after create.)
 uint64_t gpt_generation(const mgpt_gpt *g);
 uint64_t env_generation(const mgpt_env *e);
+// instances and agents per instance of an env context (step.hip sizes its live list and compact buffers from them)
+void env_shape(const mgpt_env *e, int *n_inst, int *n_agents);
+// gpt.hip: the sampler on the compact logits of the live instances (sample_live_kernel), for step.hip's retire mode
+int sample_actions_live(const float *d_logits, const int32_t *d_live, const int32_t *d_count, int n_agents, int n_inst, int64_t grid_rows,
+                        int32_t *d_actions, int do_sample, uint64_t seed, uint64_t step, const uint64_t *d_step, uint64_t row0, hipStream_t s);
 
 #define MGPT_HIP(call)                                                                     \
     do {                                                                                   \

@@ -29,14 +29,10 @@ __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t step, uint64_
     return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
 
-__global__ __launch_bounds__(256) void sample_kernel(const float *__restrict__ logits, int rows, int32_t *__restrict__ actions,
-                                                     int do_sample, uint64_t seed, uint64_t step, uint64_t row0,
-                                                     const uint64_t *__restrict__ d_step)
+// one row of GPT.act: soft-max over the five action logits `l`, a draw keyed by the GLOBAL row id (or the first maximum).  The only
+// sampling arithmetic of the library: sample_kernel and sample_live_kernel both call it, so their draws cannot drift apart.
+__device__ __forceinline__ int sample_row(const float *__restrict__ l, int do_sample, uint64_t seed, uint64_t step, uint64_t global_row)
 {
-    const int row = blockIdx.x * 256 + threadIdx.x;
-    if (row >= rows) return;
-    if (d_step) step = *d_step;                  // step counter kept on the device (mgpt_step_run's graph)
-    const float *l = logits + (size_t)row * kV;
     float v[MGPT_NUM_ACTIONS];
     float mx = -INFINITY;
     int best = 0;
@@ -45,11 +41,11 @@ __global__ __launch_bounds__(256) void sample_kernel(const float *__restrict__ l
         v[i] = l[i];
         if (v[i] > mx) { mx = v[i]; best = i; }     // first maximum, as torch.topk(k=1) on ties
     }
-    if (!do_sample) { actions[row] = best; return; }
+    if (!do_sample) return best;
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < MGPT_NUM_ACTIONS; i++) { v[i] = expf(v[i] - mx); sum += v[i]; }
-    const float u = uniform01(seed, step, row0 + (uint64_t)row) * sum;
+    const float u = uniform01(seed, step, global_row) * sum;
     float c = 0.f;
     int a = MGPT_NUM_ACTIONS - 1;
 #pragma unroll
@@ -57,7 +53,36 @@ __global__ __launch_bounds__(256) void sample_kernel(const float *__restrict__ l
         c += v[i];
         if (u < c) { a = i; break; }
     }
-    actions[row] = a;
+    return a;
+}
+
+__global__ __launch_bounds__(256) void sample_kernel(const float *__restrict__ logits, int rows, int32_t *__restrict__ actions,
+                                                     int do_sample, uint64_t seed, uint64_t step, uint64_t row0,
+                                                     const uint64_t *__restrict__ d_step)
+{
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= rows) return;
+    if (d_step) step = *d_step;                  // step counter kept on the device (mgpt_step_run's graph)
+    actions[row] = sample_row(logits + (size_t)row * kV, do_sample, seed, step, row0 + (uint64_t)row);
+}
+
+// The same on the compact logits of the live instances (step.hip, retire mode): compact row j belongs to instance live[j / n_agents],
+// agent j % n_agents; the draw is keyed by that row's GLOBAL id and the action lands in that row of the full actions array, so a live
+// row gets exactly what sample_kernel gives it in a full-batch call.  *d_count = live instances (device); rows beyond it, and rows
+// whose instance id is not in [0, n_inst), write nothing.  Grid-stride: the launch need not know the count.
+__global__ __launch_bounds__(256) void sample_live_kernel(const float *__restrict__ logits, const int32_t *__restrict__ live,
+                                                          const int32_t *__restrict__ d_count, int n_agents, int n_inst,
+                                                          int32_t *__restrict__ actions, int do_sample, uint64_t seed, uint64_t step,
+                                                          uint64_t row0, const uint64_t *__restrict__ d_step)
+{
+    const int64_t n = (int64_t)min(max(*d_count, 0), n_inst) * n_agents;
+    if (d_step) step = *d_step;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
+        const int inst = live[j / n_agents];
+        if (inst < 0 || inst >= n_inst) continue;
+        const int64_t row = (int64_t)inst * n_agents + (int)(j % n_agents);
+        actions[row] = sample_row(logits + (size_t)j * kV, do_sample, seed, step, row0 + (uint64_t)row);
+    }
 }
 
 }  // namespace
@@ -667,6 +692,29 @@ extern "C" int mgpt_sample_actions(const float *d_logits, int rows, int32_t *d_a
     hipLaunchKernelGGL(sample_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, s, d_logits, rows, d_actions, do_sample, seed, step, row0, (const uint64_t *)nullptr);
     MGPT_LAUNCH_CHECK();
     return MGPT_OK;
+}
+
+// sample_live_kernel behind one launch.  grid_rows: an upper bound of the compact rows when the caller has one on the host (the step
+// object does: the count is frozen between polls), else <= 0 and a fixed grid strides over whatever *d_count says.
+int mgpt::sample_actions_live(const float *d_logits, const int32_t *d_live, const int32_t *d_count, int n_agents, int n_inst, int64_t grid_rows,
+                              int32_t *d_actions, int do_sample, uint64_t seed, uint64_t step, const uint64_t *d_step, uint64_t row0,
+                              hipStream_t s)
+{
+    const int blocks = grid_rows > 0 ? (int)std::min<int64_t>(cdiv64(grid_rows, 256), 4096) : 1024;
+    ProfScope ps(P_SAMPLE, s);
+    hipLaunchKernelGGL(sample_live_kernel, dim3(blocks), dim3(256), 0, s, d_logits, d_live, d_count, n_agents, n_inst, d_actions, do_sample,
+                       seed, step, row0, d_step);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_sample_actions_live(const float *d_logits, const int32_t *d_live, const int32_t *d_count, int n_agents, int32_t *d_actions,
+                                        int do_sample, uint64_t seed, uint64_t step, uint64_t row0, void *stream)
+{
+    MGPT_REQUIRE(d_logits && d_live && d_count && d_actions && n_agents > 0, MGPT_ERR_ARG, "bad argument");
+    // the caller's live list is trusted for the upper end (this entry is not told n_inst): ids must index d_actions
+    return sample_actions_live(d_logits, d_live, d_count, n_agents, INT32_MAX / n_agents, 0, d_actions, do_sample, seed, step, nullptr, row0,
+                               (hipStream_t)stream);
 }
 
 static int gpt_act_impl(mgpt_gpt *g, const uint8_t *d_tokens, int rows, int32_t *d_actions, float *d_logits, int do_sample,

@@ -8,6 +8,16 @@
 // builds the lazily packed weight planes) the sequence is captured once and replayed; the only per-step scalar, the RNG
 // step counter, lives in device memory and is bumped by the graph's last node.  For small workloads (one 32-agent env:
 // ~40 launches of a few microseconds each) this removes the per-launch host cost and the Python/ctypes round trips.
+//
+// Retire mode (mgpt_step_set_retire): the reference's run_episode leaves an episode once all agents are terminated or truncated
+// (create_env.py:15-18); a batch cannot leave, but it can stop forwarding the finished instances.  A poll compacts the ids of the
+// instances with done == 0 into an ordered live list (live_list_kernel) and reads the count back -- the only host synchronisation of the
+// mode.  Between polls the list is frozen: the tokenizer still runs over all rows, the token rows of the live instances are gathered
+// into a compact buffer, the policy forwards those rows alone, and sample_live_kernel (gpt.hip) writes each action to its global row
+// with the draw keyed by that global row.  An instance that finishes inside the window is forwarded until the next poll; the env
+// ignores it (env.hip: env_step_kernel returns on done != 0).  Eager launches only: the row count changes from poll to poll.
+#include <vector>
+
 #include "common.h"
 
 namespace mgpt {
@@ -37,18 +47,117 @@ struct mgpt_step {
     int cap_gmc = -1;
     bool capture_failed = false;
     uint64_t seen_gpt_gen = 0, seen_env_gen = 0; // generations of OUR contexts after our last step (0: never ran)
+    // retire mode (all NULL / 0 when off)
+    bool retire = false;
+    int n_inst = 0, n_agents = 0;
+    int n_live = 0;                             // live instances at the last poll (host copy: sizes the forward until the next poll)
+    int32_t *d_live = nullptr;                  // [n_inst] ids of the live instances, ascending; -1 beyond the count
+    int32_t *d_count = nullptr;                 // device copy of n_live
+    int32_t *h_count = nullptr;                 // pinned: the poll's read-back
+    uint8_t *d_ctokens = nullptr;               // [rows][256] token rows of the live instances, compact
+    float *d_clogits = nullptr;                 // [rows][67] their logits
 };
 
 namespace {
 __global__ void bump_kernel(uint64_t *ctr) { *ctr += 1; }
 __global__ void set_kernel(uint64_t *ctr, uint64_t v) { *ctr = v; }
 
+constexpr int kLiveThreads = 1024, kLiveWaves = kLiveThreads / 64;
+
+// Stable stream compaction of the instances with done == 0: live[0 .. count) = their ids in ascending order, live[count .. n_inst) = -1.
+// ONE workgroup walks n_inst in passes of kLiveThreads flags (a batch has at most 65536 instances: 64 passes).  Inside a wave the rank of
+// a live lane is the population count of the ballot below it; across the waves of a pass the wave totals go through LDS and every thread
+// sums the ones before its wave; across passes a running total that all threads carry.  Every slot is a function of the flags alone --
+// no atomics -- so the same flags give the same bits.
+__global__ __launch_bounds__(kLiveThreads) void live_list_kernel(const uint8_t *__restrict__ done, int n_inst, int32_t *__restrict__ live,
+                                                                 int32_t *__restrict__ count)
+{
+    __shared__ int wave_total[kLiveWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int running = 0;                                            // live instances of the passes so far (workgroup-uniform)
+    for (int base = 0; base < n_inst; base += kLiveThreads) {   // (uniform trip count: every thread reaches both barriers)
+        const int i = base + tid;
+        const bool is_live = i < n_inst && done[i] == 0;
+        const unsigned long long mask = __ballot(is_live);      // 64-bit on a wave64 target
+        const int rank = __popcll(mask & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_total[wave] = __popcll(mask);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < kLiveWaves; w++) {
+            const int t = wave_total[w];
+            total += t;
+            if (w < wave) before += t;
+        }
+        if (is_live) live[running + before + rank] = i;         // < running + total <= n_inst
+        running += total;
+        __syncthreads();                                        // wave_total is rewritten by the next pass
+    }
+    for (int i = running + tid; i < n_inst; i += kLiveThreads) live[i] = -1;
+    if (tid == 0) *count = running;
+}
+
+__global__ void live_all_kernel(int32_t *__restrict__ live, int32_t *__restrict__ count, int n_inst)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n_inst) live[i] = i;
+    if (i == 0) *count = n_inst;
+}
+
+// Token rows (256 B = 16 x uint4) of the live instances -> compact rows: compact row j = instance live[j / n_agents], agent j % n_agents.
+// 16 lanes per row, one 16-byte load and store each.  The row count comes from device memory (*d_count instances); threads beyond it,
+// and rows whose id is not an instance, do nothing.
+__global__ __launch_bounds__(256) void gather_live_rows_kernel(const uint4 *__restrict__ tokens, const int32_t *__restrict__ live,
+                                                               const int32_t *__restrict__ d_count, int n_agents, int n_inst,
+                                                               uint4 *__restrict__ out)
+{
+    const int64_t n = (int64_t)min(max(*d_count, 0), n_inst) * n_agents;
+    const int64_t j = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    if (j >= n) return;
+    const int inst = live[j / n_agents];
+    if (inst < 0 || inst >= n_inst) return;
+    const int64_t src = (int64_t)inst * n_agents + (int)(j % n_agents);
+    const int q = threadIdx.x & 15;
+    out[j * 16 + q] = tokens[src * 16 + q];
+}
+
+int launch_live_list(const uint8_t *d_done, int n_inst, int32_t *d_live, int32_t *d_count, hipStream_t s)
+{
+    hipLaunchKernelGGL(live_list_kernel, dim3(1), dim3(kLiveThreads), 0, s, d_done, n_inst, d_live, d_count);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
+// the policy part of a retire-mode step: gather -> forward on the compact rows -> sample into the global rows
+int act_live(mgpt_step *st, const uint8_t *d_tokens, int32_t *d_actions, hipStream_t s)
+{
+    if (st->n_live == 0) return MGPT_OK;
+    const int live_rows = st->n_live * st->n_agents;
+    hipLaunchKernelGGL(gather_live_rows_kernel, dim3(cdiv(live_rows, 16)), dim3(256), 0, s, (const uint4 *)d_tokens, st->d_live, st->d_count,
+                       st->n_agents, st->n_inst, (uint4 *)st->d_ctokens);
+    MGPT_LAUNCH_CHECK();
+    int rc = mgpt_gpt_forward(st->gpt, st->d_ctokens, live_rows, st->d_clogits, st->precision, s);
+    if (rc != MGPT_OK) return rc;
+    return sample_actions_live(st->d_clogits, st->d_live, st->d_count, st->n_agents, st->n_inst, live_rows, d_actions, st->do_sample, st->seed, 0,
+                               st->d_step, st->row0, s);
+}
+
+void free_retire(mgpt_step *st)
+{
+    (void)hipFree(st->d_live); (void)hipFree(st->d_count); (void)hipFree(st->d_ctokens); (void)hipFree(st->d_clogits);
+    if (st->h_count) (void)hipHostFree(st->h_count);
+    st->d_live = nullptr; st->d_count = nullptr; st->h_count = nullptr; st->d_ctokens = nullptr; st->d_clogits = nullptr;
+    st->retire = false; st->n_live = 0;
+}
+
 int step_body(mgpt_step *st, uint8_t *d_tokens, int32_t *d_actions, int gmc, hipStream_t s)
 {
     int rc;
     if ((rc = mgpt_tokenizer_update_agents(st->tok, st->d_pos, st->d_goal, d_actions, gmc, s)) != MGPT_OK) return rc;
     if ((rc = mgpt_tokenizer_generate_observations(st->tok, d_tokens, s)) != MGPT_OK) return rc;
-    if ((rc = mgpt_gpt_act_dev(st->gpt, d_tokens, st->rows, d_actions, nullptr, st->do_sample, st->seed, st->d_step, st->row0, st->precision,
+    if (st->retire) {
+        if ((rc = act_live(st, d_tokens, d_actions, s)) != MGPT_OK) return rc;
+    } else if ((rc = mgpt_gpt_act_dev(st->gpt, d_tokens, st->rows, d_actions, nullptr, st->do_sample, st->seed, st->d_step, st->row0, st->precision,
                                s)) != MGPT_OK)
         return rc;
     if ((rc = mgpt_env_step(st->env, d_actions, s)) != MGPT_OK) return rc;
@@ -99,6 +208,7 @@ extern "C" int mgpt_step_destroy(mgpt_step *st)
 {
     if (!st) return MGPT_OK;
     drop_graph(st);
+    free_retire(st);
     if (st->cap_stream) (void)hipStreamDestroy(st->cap_stream);
     (void)hipFree(st->d_step);
     delete st;
@@ -111,12 +221,87 @@ extern "C" int mgpt_step_reset(mgpt_step *st, uint64_t step0, void *stream)
     drop_graph(st);          // between episodes the contexts may re-allocate (lifelong goal queues): next run re-captures
     hipLaunchKernelGGL(set_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, st->d_step, step0);
     MGPT_LAUNCH_CHECK();
+    if (st->retire) {        // a new episode: every instance is live until the next poll says otherwise
+        hipLaunchKernelGGL(live_all_kernel, dim3(cdiv(st->n_inst, 256)), dim3(256), 0, (hipStream_t)stream, st->d_live, st->d_count, st->n_inst);
+        MGPT_LAUNCH_CHECK();
+        st->n_live = st->n_inst;
+    }
     return MGPT_OK;
+}
+
+extern "C" int mgpt_step_set_retire(mgpt_step *st, int enable)
+{
+    MGPT_REQUIRE(st, MGPT_ERR_ARG, "NULL argument");
+    if (!enable) {
+        if (st->retire) free_retire(st);          // (hipFree waits for the work that still reads the buffers)
+        return MGPT_OK;
+    }
+    if (st->retire) return MGPT_OK;
+    drop_graph(st);
+    env_shape(st->env, &st->n_inst, &st->n_agents);
+    MGPT_REQUIRE((int64_t)st->n_inst * st->n_agents == st->rows, MGPT_ERR_ARG, "the step has %d rows, its env %d x %d", st->rows, st->n_inst,
+                 st->n_agents);
+    hipError_t e = hipMalloc(&st->d_live, (size_t)st->n_inst * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&st->d_count, sizeof(int32_t));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&st->h_count, sizeof(int32_t), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc(&st->d_ctokens, (size_t)st->rows * MGPT_CONTEXT);
+    if (e == hipSuccess) e = hipMalloc(&st->d_clogits, (size_t)st->rows * MGPT_VOCAB * sizeof(float));
+    if (e == hipSuccess) {                        // all live, as after mgpt_step_reset
+        std::vector<int32_t> ids((size_t)st->n_inst);
+        for (int i = 0; i < st->n_inst; i++) ids[(size_t)i] = i;
+        e = hipMemcpy(st->d_live, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(st->d_count, &st->n_inst, sizeof(int32_t), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        set_error("allocation failed in mgpt_step_set_retire: %s", hipGetErrorString(e));
+        free_retire(st);
+        return MGPT_ERR_HIP;
+    }
+    st->retire = true;
+    st->n_live = st->n_inst;
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_step_poll_live(mgpt_step *st, int *n_live, void *stream)
+{
+    MGPT_REQUIRE(st, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(st->retire, MGPT_ERR_STATE, "mgpt_step_set_retire(step, 1) must precede mgpt_step_poll_live");
+    hipStream_t s = (hipStream_t)stream;
+    const uint8_t *d_done = nullptr;
+    int rc = mgpt_env_state(st->env, nullptr, nullptr, &d_done);
+    if (rc != MGPT_OK) return rc;
+    if ((rc = launch_live_list(d_done, st->n_inst, st->d_live, st->d_count, s)) != MGPT_OK) return rc;
+    MGPT_HIP(hipMemcpyAsync(st->h_count, st->d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    MGPT_HIP(hipStreamSynchronize(s));
+    st->n_live = *st->h_count;
+    MGPT_REQUIRE(st->n_live >= 0 && st->n_live <= st->n_inst, MGPT_ERR_STATE, "live count %d outside 0 .. %d", st->n_live, st->n_inst);
+    if (n_live) *n_live = st->n_live;
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_step_copy_live(mgpt_step *st, int32_t *d_live_out, float *d_logits_out, void *stream)
+{
+    MGPT_REQUIRE(st, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(st->retire, MGPT_ERR_STATE, "retire mode is off");
+    hipStream_t s = (hipStream_t)stream;
+    if (d_live_out) MGPT_HIP(hipMemcpyAsync(d_live_out, st->d_live, (size_t)st->n_inst * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (d_logits_out)
+        MGPT_HIP(hipMemcpyAsync(d_logits_out, st->d_clogits, (size_t)st->rows * MGPT_VOCAB * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_live_list(const uint8_t *d_done, int n_inst, int32_t *d_live, int32_t *d_count, void *stream)
+{
+    MGPT_REQUIRE(d_done && d_live && d_count && n_inst > 0, MGPT_ERR_ARG, "bad argument");
+    return launch_live_list(d_done, n_inst, d_live, d_count, (hipStream_t)stream);
 }
 
 extern "C" int mgpt_step_run(mgpt_step *st, uint8_t *d_tokens, int32_t *d_actions, int goals_may_change, int use_graph, void *stream)
 {
     MGPT_REQUIRE(st && d_tokens && d_actions, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(!(st->retire && use_graph), MGPT_ERR_UNSUPPORTED,
+                 "retire mode runs eager launches only (use_graph = 0): the policy's row count changes from poll to poll");
+    MGPT_REQUIRE(!st->retire || ((uintptr_t)d_tokens & 15) == 0, MGPT_ERR_ARG, "retire mode gathers 16-byte vectors: d_tokens must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const int gmc = goals_may_change ? 1 : 0;
     // one of OUR contexts re-allocated or freed device memory since our last step (weights reloaded -> planes freed and rebuilt lazily,

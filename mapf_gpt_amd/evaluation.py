@@ -188,12 +188,14 @@ def _build_algorithm(algo_cfg, max_rows):
 
 
 def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, max_rows_per_batch=65536, rank=0, world=1,
-               print_fn=print, trace=None):
+               print_fn=print, trace=None, retire_done=False):
     """Run `evaluation_config` (dict in the reference's YAML schema).  Returns the list of result records (on every
     rank); writes `<eval_dir>/<algorithm>.json` and prints the tabular views on rank 0.
     `trace(kind, payload)` (tests): called with ("reset", {algorithm, runs, grids, pos, goal, max_steps}) for every batch
     this rank runs and with ("step", int32 actions [instances, agents]) after every step -- the device's sampled actions,
-    from which an episode can be replayed on the host."""
+    from which an episode can be replayed on the host.
+    retire_done: BatchedRunner's retire mode -- finished episodes leave the policy's batch and a batch ends when none is live (the
+    reference's run_episode leaves at all(terminated) or all(truncated), create_env.py:15-18); same records, less work."""
     import torch
     from .runner import BatchedRunner, gather_metrics, shard_range
 
@@ -227,7 +229,7 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                         pos[k], goal[k] = _maps.place_agents(g, n_agents, int(runs[i][0].get("seed", 0)), s_ok, g_ok)
                     run = BatchedRunner(grids, len(mine), n_agents, algo.net, max_episode_steps=max_steps,
                                         seed=int(cfg.seed or 0), do_sample=True, precision=cfg.precision, device=cfg.device,
-                                        row_offset=lo * n_agents)
+                                        row_offset=lo * n_agents, retire_done=bool(retire_done))
                     queue = None
                     if on_target == "restart":          # lifelong: a seeded queue of further goals per agent (wraps)
                         queue = np.empty((len(mine), n_agents, LIFELONG_QUEUE, 2), np.int16)

@@ -11,6 +11,10 @@ One hot-path step (order as in the reference's run_episode loop, example.py:65 /
     tokens  = tokenizer.generate_observations()                # uint8 [rows, 256]
     actions = policy.act(tokens)                               # int32 [rows]
     env.step(actions); last_actions = actions
+
+retire_done=True (opt-in) stops forwarding finished instances: every poll_every-th step the library compacts the ids of the
+instances that are not done and reads their count back (the mode's only host synchronisation); until the next poll the policy
+runs on the token rows of those instances alone.  Draws and metrics are those of the plain run ("Retire mode").
 """
 import ctypes
 
@@ -62,7 +66,11 @@ def make_instances(grid, n_inst, n_agents, first_seed=0, start_ok=None, goal_ok=
 
 class BatchedRunner:
     def __init__(self, grids, n_inst, n_agents, net, max_episode_steps=128, seed=0, do_sample=True, precision=None,
-                 device="cuda", row_offset=0, use_graph=False):
+                 device="cuda", row_offset=0, use_graph=False, retire_done=False, poll_every=8):
+        if retire_done and use_graph:
+            raise ValueError("retire_done=True runs eager launches only: the policy's row count changes from poll to poll, use_graph=True cannot replay it")
+        if int(poll_every) < 1:
+            raise ValueError("poll_every must be >= 1")
         self.device = torch.device(device)
         self.env = BatchedEnv(grids, n_inst, n_agents, max_episode_steps, device=device)
         self.tok = BatchedTokenizer(grids, n_inst, n_agents, device=device)
@@ -85,6 +93,27 @@ class BatchedRunner:
             _lib.check(_lib.lib().mgpt_step_create(ctypes.byref(self._step), self.tok._h, self.net._h, self.env._h, self.rows,
                                                    _lib.PRECISIONS[precision or net.precision], 1 if do_sample else 0,
                                                    int(seed) & (2 ** 64 - 1), int(row_offset)))
+        # retire mode: live_instances = count at the last poll, rows_forwarded = rows sent through the policy since reset()
+        self.retire_done, self.poll_every = False, int(poll_every)
+        self._live, self._rows_forwarded, self._polled_t = n_inst, 0, -1
+        if retire_done:
+            self.set_retire_done(True)
+
+    def set_retire_done(self, on):
+        """Switch retire mode (mgpt_step_set_retire: allocates / frees its buffers); takes effect at the next reset()."""
+        if on and self.use_graph:
+            raise ValueError("retire_done=True runs eager launches only, this runner replays a hipGraph (use_graph=True)")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mgpt_step_set_retire(self._step, 1 if on else 0))
+        self.retire_done = bool(on)
+
+    @property
+    def live_instances(self):
+        return self._live
+
+    @property
+    def rows_forwarded(self):
+        return self._rows_forwarded
 
     def __del__(self):
         h = getattr(self, "_step", None)
@@ -106,16 +135,46 @@ class BatchedRunner:
         self.t = 0
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().mgpt_step_reset(self._step, 0, _lib.stream_ptr()))
+        self._live, self._rows_forwarded, self._polled_t = self.n_inst, 0, -1
+        if self.retire_done:
+            self._poll()
+
+    def _poll(self):
+        """Rebuild the live list from the env's done flags and read its count back (synchronises the stream)."""
+        n = ctypes.c_int(0)
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_step_poll_live(self._step, ctypes.byref(n), _lib.stream_ptr()))
+        self._live, self._polled_t = int(n.value), self.t
+
+    def _poll_if_due(self):
+        if self.retire_done and self.t % self.poll_every == 0 and self._polled_t != self.t:
+            self._poll()
+
+    def live_state(self):
+        """Retire mode, tests: (ids int32 [live_instances] of the live list, logits float32 [live_instances * n_agents, 67] of the
+        last step's compact policy call)."""
+        ids = torch.empty((self.n_inst,), dtype=torch.int32, device=self.device)
+        logits = torch.empty((self.rows, 67), dtype=torch.float32, device=self.device)
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_step_copy_live(self._step, _lib.ptr(ids), _lib.ptr(logits), _lib.stream_ptr()))
+        return ids[:self._live], logits[:self._live * self.n_agents]
 
     def step(self):
         """update_agents -> generate_observations -> act -> env.step in ONE library call (mgpt_step_run)."""
+        self._poll_if_due()
         with _lib.on_device(self.device):
             _lib.check(_lib.lib().mgpt_step_run(self._step, _lib.ptr(self.tokens), _lib.ptr(self.actions.view(-1)),
                                                 1 if self.env.lifelong else 0, 1 if self.use_graph else 0, _lib.stream_ptr()))
+        self._rows_forwarded += self._live * self.n_agents
         self.t += 1
 
     def run(self, steps):
+        """`steps` steps; with retire_done it returns early once a poll reports no live instance (self.t = steps actually run)."""
         for _ in range(steps):
+            if self.retire_done:
+                self._poll_if_due()
+                if self._live == 0:
+                    return
             self.step()
 
     def metrics(self):
