@@ -478,6 +478,33 @@ int mgpt_rows_gather(const uint8_t *d_rows, const int8_t *d_labels, int64_t n_sr
                      uint8_t *d_rows_out, int8_t *d_labels_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PIBT expert: the role of run_expert() (dataset/generate_dataset.py:214-230) and of the logging environment
+ * (experiment_setup/create_env.py:8-33: create_logging_env, LogActions :49-60) -- plans every agent's next cell by priority inheritance
+ * with backtracking (the spec is this project's own: DESIGN.md section 20; the reference's expert is LaCAM3, which is not rebuilt), steps
+ * the env with the plan and logs the actions made.  A weaker teacher than LaCAM: nothing guarantees that all agents reach their goals.
+ *   create:    borrows the distance fields and grids of `tok` (mgpt_tokenizer_create_agents must have run before the first reset) and
+ *              pos / goal / done of `env`; both must outlive the expert and agree in shape (MGPT_ERR_ARG otherwise).  seed and
+ *              inst_offset key the tie-breaking draws by the GLOBAL row (inst_offset + inst) * n_agents + agent, so a shard plans what the
+ *              unsharded job plans.  max_steps = the log's capacity per agent.  MGPT_ERR_UNSUPPORTED for a lifelong env, for a non-zero env
+ *              rule mask (also when either is set later: reset and step check again) and for n_agents > 65534 (generate_dataset.py:214-230).
+ *   reset:     since = 0, empty log, empty occupancy (every plan rebuilds it from the env's positions); call after mgpt_env_reset and
+ *              mgpt_tokenizer_create_agents (create_env.py:8-33).
+ *   step:      plan -> log -> mgpt_env_step -> since update, one call (generate_dataset.py:214-230).  d_actions int32 [n_inst, n_agents]
+ *              OUT: the planned actions, already executed by the env.  Instances that are done get action 0 and log nothing.
+ *   copy_plan: test read-back, int16 [n_inst, n_agents, 2]: the cell every agent planned to stand on after the last step
+ *              (create_env.py:8-33).
+ *   copy_log:  the made actions int8 [n_inst][n_agents][max_steps] and their count per instance int32 [n_inst] (= the instance's
+ *              ep_length); either may be NULL (create_env.py:8-33 LogActions; generate_dataset.py:214-230).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct mgpt_expert mgpt_expert;
+int mgpt_expert_create(mgpt_expert **out, mgpt_tokenizer *tok, mgpt_env *env, uint64_t seed, int64_t inst_offset, int max_steps);
+int mgpt_expert_destroy(mgpt_expert *ex);
+int mgpt_expert_reset(mgpt_expert *ex, void *stream);
+int mgpt_expert_step(mgpt_expert *ex, int32_t *d_actions, void *stream);
+int mgpt_expert_copy_plan(mgpt_expert *ex, int16_t *d_planned_out, void *stream);
+int mgpt_expert_copy_log(mgpt_expert *ex, int8_t *d_log_out, int32_t *d_len_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Kernel timing hooks (bench.py's live roofline): when enabled, the library brackets every kernel
  * class with hipEvents on the launch stream.  mgpt_prof_read synchronises the device.
  * ------------------------------------------------------------------------------------------ */

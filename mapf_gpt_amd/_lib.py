@@ -113,6 +113,12 @@ SYMBOLS = {
     "mgpt_gpt_grads_size": (_i, [_vp, ctypes.POINTER(_i64)]),
     "mgpt_gpt_grads_export": (_i, [_vp, _vp, _i64, _vp]),
     "mgpt_gpt_grads_reduce": (_i, [_vp, _vp, _i, ctypes.c_float, _vp]),
+    "mgpt_expert_create": (_i, [_pp, _vp, _vp, _u64, _i64, _i]),
+    "mgpt_expert_destroy": (_i, [_vp]),
+    "mgpt_expert_reset": (_i, [_vp, _vp]),
+    "mgpt_expert_step": (_i, [_vp, _vp, _vp]),
+    "mgpt_expert_copy_plan": (_i, [_vp, _vp, _vp]),
+    "mgpt_expert_copy_log": (_i, [_vp, _vp, _vp, _vp]),
     "mgpt_prof_enable": (_i, [_i]),
     "mgpt_prof_reset": (_i, []),
     "mgpt_prof_read": (_i, [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float),

@@ -21,6 +21,15 @@ uint64_t gpt_generation(const mgpt_gpt *g);
 uint64_t env_generation(const mgpt_env *e);
 // instances and agents per instance of an env context (step.hip sizes its live list and compact buffers from them)
 void env_shape(const mgpt_env *e, int *n_inst, int *n_agents);
+// rule mask, lifelong flag and frame of an env context; the device state a tokenizer context lends to the expert (expert.hip)
+void env_config(const mgpt_env *e, int *H, int *W, int *n_grids, int *rules, int *lifelong);
+struct TokView {
+    const uint16_t *dist;
+    const uint8_t *grids;
+    int n_inst, n_agents, H, W, n_grids;
+    bool have_agents;
+};
+void tok_view(const mgpt_tokenizer *t, TokView *out);
 // gpt.hip: the sampler on the compact logits of the live instances (sample_live_kernel), for step.hip's retire mode
 int sample_actions_live(const float *d_logits, const int32_t *d_live, const int32_t *d_count, int n_agents, int n_inst, int64_t grid_rows,
                         int32_t *d_actions, int do_sample, uint64_t seed, uint64_t step, const uint64_t *d_step, uint64_t row0, hipStream_t s);
@@ -59,6 +68,7 @@ enum ProfId {
     P_ATTN_LAST, P_GEMM_PROJ_LAST, P_MLP_FUSED_LAST,    // the last layer's launches (token 255 only, model.py:186): timed apart from the full ones
     P_HEAD_SEQ, P_SCORE,                                // ln_f + head + cross-entropy of every position (mgpt_gpt_forward_seq), last-position scoring
     P_DS_HASH, P_DS_INSERT, P_DS_CLASSIFY, P_DS_RESOLVE, P_DS_BALANCE, P_DS_SELECT, P_DS_GATHER,   // dataset builder (dataset_build.hip)
+    P_EXPERT_PLAN,                                      // the PIBT expert's plan kernel (expert.hip)
     P_COUNT
 };
 

@@ -834,6 +834,11 @@ struct mgpt_tokenizer {
     bool have_grids = false, have_agents = false;
 };
 
+void mgpt::tok_view(const mgpt_tokenizer *t, TokView *out)
+{
+    *out = TokView{t->dist, t->grids, t->n_inst, t->n_agents, t->H, t->W, t->n_grids, t->have_agents};
+}
+
 extern "C" int mgpt_tokenizer_create(mgpt_tokenizer **out, const mgpt_input_parameters *cfg, int n_inst,
                                      int n_agents, int H, int W, int n_grids)
 {

@@ -6,8 +6,9 @@ kept on the device from the tokenizer until the shard is written (DESIGN.md sect
         --out dataset/chunk --desired-size 1000000 [--maze-ratio 0.9 --files-per-chunk 10 --num-chunks 1 --seed 0]
 
 prints one JSON line per chunk (per-file counters, picks, shard sizes) and writes <out>_part_<i>.arrow (<out>_chunk_<c>_part_<i>.arrow with --num-chunks > 1), the files
-`python -m mapf_gpt_amd.training` and `mapf_gpt_amd.scoring` read.  Step 1 of that script (running the LaCAM expert under
-POGEMA) is not part of this repository; `split_by_map` is its step 2.
+`python -m mapf_gpt_amd.training` and `mapf_gpt_amd.scoring` read.  Step 1 of that script runs the LaCAM expert under
+POGEMA, which is not part of this repository; `python -m mapf_gpt_amd.expert` writes a log of the same shape with the PIBT expert
+(PIBT.json); `split_by_map` is its step 2.
 
 Shuffles draw from one np.random.Generator(PCG64(seed)) in a fixed order (per file in processing order, then the whole chunk);
 the reference draws from numpy's global stream, so orders differ from it seed for seed while the sets of rows do not.

@@ -187,17 +187,32 @@ def _build_algorithm(algo_cfg, max_rows):
     return algo, cfg
 
 
+class PIBTConfig:
+    """Config of the `name: PIBT` algorithm (the device-resident expert, mapf_gpt_amd/expert.py): name, seed, device; unknown keys
+    raise, as for the MAPF-GPT config."""
+
+    def __init__(self, name="PIBT", seed=0, device="cuda"):
+        self.name, self.seed, self.device = name, int(seed or 0), device
+
+
 def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, max_rows_per_batch=65536, rank=0, world=1,
-               print_fn=print, trace=None, retire_done=False):
+               print_fn=print, trace=None, retire_done=False, log_actions=False):
     """Run `evaluation_config` (dict in the reference's YAML schema).  Returns the list of result records (on every
     rank); writes `<eval_dir>/<algorithm>.json` and prints the tabular views on rank 0.
     `trace(kind, payload)` (tests): called with ("reset", {algorithm, runs, grids, pos, goal, max_steps}) for every batch
     this rank runs and with ("step", int32 actions [instances, agents]) after every step -- the device's sampled actions,
     from which an episode can be replayed on the host.
     retire_done: BatchedRunner's retire mode -- finished episodes leave the policy's batch and a batch ends when none is live (the
-    reference's run_episode leaves at all(terminated) or all(truncated), create_env.py:15-18); same records, less work."""
+    reference's run_episode leaves at all(terminated) or all(truncated), create_env.py:15-18); same records, less work.
+    An algorithm whose `name` is PIBT runs the device-resident expert (BatchedExpert) instead of a policy: same grouping, frames,
+    placement, sharding and metrics gather.  log_actions: the role of the reference's create_logging_env (create_env.py:8-33) -- the
+    PIBT records also carry `made_actions` (per agent, cut to the episode's length) and `init_positions` (padded coordinates), the
+    expert log that dataset_build / dataset_tokenizer consume; one rank only."""
     import torch
     from .runner import BatchedRunner, gather_metrics, shard_range
+
+    if log_actions and world != 1:
+        raise ValueError("log_actions=True needs world == 1: the action logs are not gathered across ranks")
 
     registry = registry or MapRegistry()
     runs = expand_grid_search(evaluation_config["environment"])
@@ -205,12 +220,18 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
     results = []
     for algo_name, algo_cfg in evaluation_config["algorithms"].items():
         algo_cfg = dict(algo_cfg)
-        if precision is not None:
-            algo_cfg["precision"] = precision
-        algo, cfg = _build_algorithm(algo_cfg, max_rows_per_batch)
+        is_pibt = algo_cfg.get("name") == "PIBT"
+        if is_pibt:
+            algo, cfg = None, PIBTConfig(**algo_cfg)
+        else:
+            if precision is not None:
+                algo_cfg["precision"] = precision
+            algo, cfg = _build_algorithm(algo_cfg, max_rows_per_batch)
         for (n_agents, max_steps, on_target), idxs in groups.items():
             if on_target not in ("nothing", "restart"):
                 raise NotImplementedError(f"on_target={on_target!r}: 'nothing' and 'restart' (lifelong) are built")
+            if is_pibt and on_target == "restart":
+                raise NotImplementedError("the PIBT expert does not plan lifelong (on_target='restart') episodes")
             parsed = [registry.get(runs[i][0]["map_name"]) for i in idxs]
             frames = dict(zip(idxs, common_frame(parsed)))
             per_batch = max(1, max_rows_per_batch // n_agents)
@@ -220,6 +241,7 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                 mine = chunk[lo:hi]
                 local = torch.zeros((0, len(METRIC_KEYS)), dtype=torch.float32, device=cfg.device)
                 t0 = time.perf_counter()
+                logged = {}
                 if mine:
                     grids = np.stack([frames[i][0] for i in mine])
                     pos = np.empty((len(mine), n_agents, 2), np.int16)
@@ -227,9 +249,13 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                     for k, i in enumerate(mine):
                         g, s_ok, g_ok = frames[i]
                         pos[k], goal[k] = _maps.place_agents(g, n_agents, int(runs[i][0].get("seed", 0)), s_ok, g_ok)
-                    run = BatchedRunner(grids, len(mine), n_agents, algo.net, max_episode_steps=max_steps,
-                                        seed=int(cfg.seed or 0), do_sample=True, precision=cfg.precision, device=cfg.device,
-                                        row_offset=lo * n_agents, retire_done=bool(retire_done))
+                    if is_pibt:
+                        from .expert import BatchedExpert
+                        run = BatchedExpert(grids, len(mine), n_agents, max_steps, seed=cfg.seed, device=cfg.device, inst_offset=lo)
+                    else:
+                        run = BatchedRunner(grids, len(mine), n_agents, algo.net, max_episode_steps=max_steps,
+                                            seed=int(cfg.seed or 0), do_sample=True, precision=cfg.precision, device=cfg.device,
+                                            row_offset=lo * n_agents, retire_done=bool(retire_done))
                     queue = None
                     if on_target == "restart":          # lifelong: a seeded queue of further goals per agent (wraps)
                         queue = np.empty((len(mine), n_agents, LIFELONG_QUEUE, 2), np.int16)
@@ -239,7 +265,10 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                             rng = np.random.Generator(np.random.PCG64([int(runs[i][0].get("seed", 0)), 0x4C4C]))
                             queue[k] = cells[rng.integers(0, len(cells), (n_agents, LIFELONG_QUEUE))]
                         queue = torch.from_numpy(queue)
-                    run.reset(torch.from_numpy(pos), torch.from_numpy(goal), goal_queue=queue)
+                    if is_pibt:
+                        run.reset(torch.from_numpy(pos), torch.from_numpy(goal))
+                    else:
+                        run.reset(torch.from_numpy(pos), torch.from_numpy(goal), goal_queue=queue)
                     if trace is None:
                         run.run(max_steps)
                     else:
@@ -251,6 +280,9 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                     local = run.metrics().to(torch.float32)
                     if queue is not None:               # ISR column carries the throughput (arrivals per step) in lifelong runs
                         local[:, 1] = run.env.goals_reached().sum(1).to(torch.float32) / float(max_steps)
+                    if is_pibt and log_actions:
+                        logged = dict(zip(mine, run.made_actions()))
+                        init = dict(zip(mine, pos.tolist()))
                     torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
                 allm = gather_metrics(local, len(chunk), rank, world).cpu().numpy()
@@ -259,6 +291,8 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                     if on_target == "restart":
                         m = {"avg_throughput": m["ISR"], "ep_length": m["ep_length"]}
                     m["runtime"] = dt / max(1, len(chunk))
+                    if i in logged:
+                        m["made_actions"], m["init_positions"] = logged[i], init[i]
                     results.append({"metrics": m, "env_grid_search": runs[i][1], "algorithm": algo_name})
         del algo
     if rank == 0:

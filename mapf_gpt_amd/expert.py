@@ -1,0 +1,138 @@
+"""Device-resident PIBT expert: the role of the reference's `run_expert()` (dataset/generate_dataset.py:214-230) with its logging
+environment (experiment_setup/create_env.py:8-33, 49-60) -- step 1 of the dataset pipeline, and a baseline for the evaluation tables.
+
+The reference's expert is LaCAM3 under POGEMA; neither is in its tree.  What runs here is PIBT (priority inheritance with
+backtracking), the configuration generator of such a search, by this project's own spec, one wave64 workgroup per
+instance on the BFS distance fields the tokenizer keeps in HBM.  It is a WEAKER teacher than LaCAM: nothing guarantees that all agents
+stand on their goals at once, and episodes that do not end with CSR = 1 are dropped by the dataset tokenizer as the reference drops them.
+
+    ex = BatchedExpert(grids, n_inst, n_agents, max_episode_steps, seed=0)
+    ex.reset(pos, goal); ex.run(max_episode_steps)
+    records = ex.records(run_keys, pos)            # toolbox records with made_actions / init_positions
+
+    python -m mapf_gpt_amd.expert --config CONFIG.yaml --maps MAPS.yaml --out DIR      # writes DIR/PIBT.json
+
+The config is an evaluation YAML (eval_configs/<folder>/<folder>.yaml): its `environment:` block is run; its `algorithms:` block is
+replaced by one PIBT entry (seed from --seed).  DIR/PIBT.json is what `dataset_build.split_by_map` and `dataset_build --logs` take
+where the reference has LaCAM.json.  Prints one JSON line: episodes, solved, rows, seconds.
+"""
+import argparse
+import ctypes
+import json
+import sys
+import time
+
+import numpy as np
+import torch
+
+from . import _lib
+from .env import METRIC_KEYS, BatchedEnv
+from .observation_generator import BatchedTokenizer
+
+
+class BatchedExpert:
+    """Same shape as BatchedRunner: owns a BatchedEnv and a BatchedTokenizer (used for its BFS distance fields only)."""
+
+    def __init__(self, grids, n_inst, n_agents, max_episode_steps, seed=0, device="cuda", inst_offset=0):
+        self.device = torch.device(device)
+        self.env = BatchedEnv(grids, n_inst, n_agents, max_episode_steps, device=device)
+        self.tok = BatchedTokenizer(grids, n_inst, n_agents, device=device)
+        self.n_inst, self.n_agents, self.max_episode_steps = int(n_inst), int(n_agents), int(max_episode_steps)
+        self.seed, self.inst_offset = int(seed), int(inst_offset)
+        self.actions = torch.zeros((n_inst, n_agents), dtype=torch.int32, device=self.device)
+        self.t = 0
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_create(ctypes.byref(self._h), self.tok._h, self.env._h, self.seed & (2 ** 64 - 1),
+                                                     self.inst_offset, self.max_episode_steps))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                _lib.lib().mgpt_expert_destroy(h)
+            except Exception:      # interpreter shutdown
+                pass
+            self._h = None
+
+    def reset(self, pos, goal):
+        self.env.reset(pos, goal)
+        self.tok.create_agents(self.env.pos, self.env.goal)       # the BFS distance-to-goal fields the planner reads
+        self.actions.zero_()
+        self.t = 0
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_reset(self._h, _lib.stream_ptr()))
+
+    def step(self):
+        """plan -> log -> env.step -> since update in ONE library call (mgpt_expert_step)."""
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_step(self._h, _lib.ptr(self.actions.view(-1)), _lib.stream_ptr()))
+        self.t += 1
+
+    def run(self, steps):
+        for _ in range(steps):
+            self.step()
+
+    def metrics(self):
+        return self.env.metrics()
+
+    def planned(self):
+        """int16 [n_inst, n_agents, 2]: the cell every agent planned to stand on after the last step (device tensor)."""
+        out = torch.empty((self.n_inst, self.n_agents, 2), dtype=torch.int16, device=self.device)
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_copy_plan(self._h, _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def log(self):
+        """-> (made_actions int8 [n_inst, n_agents, T], lengths int32 [n_inst]) device tensors; T = max_episode_steps, an instance's
+        entries beyond its length are 0."""
+        log = torch.empty((self.n_inst, self.n_agents, self.max_episode_steps), dtype=torch.int8, device=self.device)
+        lens = torch.empty((self.n_inst,), dtype=torch.int32, device=self.device)
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_copy_log(self._h, _lib.ptr(log), _lib.ptr(lens), _lib.stream_ptr()))
+        return log, lens
+
+    def made_actions(self):
+        """Per instance, per agent: the list of actions made, cut to the instance's episode length (host lists)."""
+        log, lens = self.log()
+        log, lens = log.cpu().numpy(), lens.cpu().numpy()
+        return [[log[i, a, :int(lens[i])].tolist() for a in range(self.n_agents)] for i in range(self.n_inst)]
+
+    def records(self, run_keys, init_pos, algorithm="PIBT"):
+        """Toolbox result records (evaluation.py): metrics = the six env metrics + made_actions + init_positions (padded coordinates,
+        as dataset_tokenizer.agent_paths expects), env_grid_search = run_keys[i], algorithm."""
+        m = self.metrics().cpu().numpy()
+        made = self.made_actions()
+        init = np.asarray(init_pos.cpu() if torch.is_tensor(init_pos) else init_pos).reshape(self.n_inst, self.n_agents, 2)
+        out = []
+        for i in range(self.n_inst):
+            rec = {k: float(m[i, j]) for j, k in enumerate(METRIC_KEYS)}
+            rec["made_actions"], rec["init_positions"] = made[i], init[i].astype(int).tolist()
+            out.append({"metrics": rec, "env_grid_search": dict(run_keys[i]), "algorithm": algorithm})
+        return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Run the PIBT expert over an evaluation config and write DIR/PIBT.json")
+    ap.add_argument("--config", required=True, help="evaluation YAML (its environment: block is run)")
+    ap.add_argument("--maps", default=None, help="maps.yaml ({name: map string}) registered on top of the built-in maps")
+    ap.add_argument("--out", required=True, help="output directory")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", default="cuda")
+    a = ap.parse_args(argv)
+    from . import evaluation as ev
+    cfg = ev.load_yaml(a.config)
+    reg = ev.MapRegistry()
+    if a.maps:
+        reg.register_maps(ev.load_yaml(a.maps))
+    cfg = {"environment": cfg["environment"], "algorithms": {"PIBT": {"name": "PIBT", "seed": a.seed, "device": a.device}}}
+    t0 = time.perf_counter()
+    res = ev.evaluation(cfg, eval_dir=a.out, registry=reg, print_fn=lambda *_: None, log_actions=True)
+    solved = [r for r in res if r["metrics"]["CSR"] >= 1]
+    rows = sum(len(r["metrics"]["made_actions"]) * (int(r["metrics"]["ep_length"]) + 1) for r in solved)     # dataset rows of the solved episodes
+    print(json.dumps({"episodes": len(res), "solved": len(solved), "rows": rows, "seconds": round(time.perf_counter() - t0, 3)}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

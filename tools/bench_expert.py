@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""Time and solve rates of the PIBT expert (mapf_gpt_amd/expert.py).
+
+    --what time    three shapes: `dataset` 4096 instances x 32 agents on a 21 x 21 maze (the dataset's shape), `cfg3` 64 instances x 192
+                   agents on wfi_warehouse (bench.py's cfg3 map), `one` 1 instance x 32 agents.  Per shape: one warm-up episode, then
+                   --repeats episodes with HIP events around reset() (the BFS of every agent's distance field) and around run(steps)
+                   (mgpt_expert_step: plan + env step + since update); then one more episode under the library's timing hooks for the
+                   split of a step between the plan kernel and the env step.  ms per step = run time / steps; episodes per second =
+                   instances / (reset + run).
+    --what solve   solved episodes of six small shapes on seeded random maps (seed 7): the table of DESIGN section 20.
+
+Prints one JSON line per shape; --out FILE appends them there too.  Needs the GPU: there is no CPU path.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from mapf_gpt_amd import _lib, maps  # noqa: E402
+from mapf_gpt_amd.expert import BatchedExpert  # noqa: E402
+from mapf_gpt_amd.runner import make_instances  # noqa: E402
+
+TIME_SHAPES = {"dataset": ("maze21", 4096, 32, 128), "cfg3": ("wfi_warehouse", 64, 192, 128), "one": ("maze21", 1, 32, 128)}
+# agents, (h, w, obstacle density), instances, step cap
+SOLVE_SHAPES = [(4, (8, 8, 0.0), 32, 64), (8, (12, 12, 0.2), 32, 64), (32, (21, 21, 0.25), 32, 128), (64, (32, 32, 0.3), 16, 256),
+                (70, (16, 16, 0.2), 16, 256), (3, (1, 12, 0.0), 16, 64)]
+
+
+def emit(rec, out):
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out:
+        with open(out, "a") as f:
+            f.write(line + "\n")
+
+
+def timed(fn):
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    fn()
+    t1.record()
+    t1.synchronize()
+    return t0.elapsed_time(t1)
+
+
+def time_shape(name, repeats, out):
+    map_name, n_inst, n, steps = TIME_SHAPES[name]
+    if map_name == "maze21":
+        grid, s_ok, g_ok = maps.pad(maps.maze_map(21, 21, 7)), None, None
+    else:
+        grid, s_ok, g_ok = maps.load_named(map_name)
+    pos, goal = make_instances(grid, n_inst, n, 0, s_ok, g_ok)
+    ex = BatchedExpert(grid, n_inst, n, steps, seed=7)
+    reset_ms, run_ms = [], []
+    for rep in range(repeats + 1):                   # episode 0 warms up (code objects, allocations)
+        r = timed(lambda: ex.reset(pos, goal))
+        s = timed(lambda: ex.run(steps))
+        if rep:
+            reset_ms.append(r)
+            run_ms.append(s)
+    m = ex.metrics().cpu().numpy()
+    _lib.prof_enable(True)                           # the split, in an episode of its own: the hooks add events to every launch
+    _lib.prof_reset()
+    ex.reset(pos, goal)
+    ex.run(steps)
+    prof = _lib.prof_read()
+    _lib.prof_enable(False)
+    plan, env, bfs = (prof.get(k, (0.0, 0))[0] for k in ("expert_pibt_plan", "env_step", "bfs_distance_field"))
+    r, s = float(np.median(reset_ms)), float(np.median(run_ms))
+    emit({"tool": "bench_expert", "what": "time", "shape": name, "map": map_name, "instances": n_inst, "agents": n, "steps": steps,
+          "ms_per_step": round(s / steps, 4), "ms_run": round(s, 3), "ms_runs": [round(x, 3) for x in run_ms], "ms_reset": round(r, 3),
+          "episodes_per_s": round(n_inst / ((r + s) * 1e-3), 1), "plan_ms_per_step": round(plan / steps, 4),
+          "env_ms_per_step": round(env / steps, 4), "plan_share_of_plan_plus_env": round(plan / max(plan + env, 1e-9), 3),
+          "bfs_ms_of_reset": round(bfs, 3), "solved": int(m[:, 0].sum()), "mean_isr": round(float(m[:, 1].mean()), 4)}, out)
+
+
+def solve_shape(n, hwd, n_inst, cap, out):
+    h, w, density = hwd
+    grids = np.stack([maps.pad(maps.random_map(h, w, density, 7000 + i)) for i in range(n_inst)])
+    pos = np.empty((n_inst, n, 2), np.int16)
+    goal = np.empty((n_inst, n, 2), np.int16)
+    for i in range(n_inst):
+        pos[i], goal[i] = maps.place_agents(grids[i], n, 7 + i)
+    ex = BatchedExpert(grids, n_inst, n, cap, seed=7)
+    ex.reset(torch.from_numpy(pos), torch.from_numpy(goal))
+    ex.run(cap)
+    m = ex.metrics().cpu().numpy()
+    ok = m[:, 0] >= 1
+    emit({"tool": "bench_expert", "what": "solve", "agents": n, "map": f"{h}x{w} at {density:.0%}", "instances": n_inst, "step_cap": cap,
+          "solved": int(ok.sum()), "mean_length_of_solved": round(float(m[ok, 4].mean()), 2) if ok.any() else None,
+          "mean_isr": round(float(m[:, 1].mean()), 4)}, out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--what", choices=["time", "solve"], required=True)
+    ap.add_argument("--shapes", nargs="*", default=None, help="time: a subset of " + " ".join(TIME_SHAPES))
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
+    a = ap.parse_args()
+    _lib.require_gpu()
+    if a.what == "time":
+        for name in a.shapes or list(TIME_SHAPES):
+            time_shape(name, a.repeats, a.out)
+    else:
+        for n, hwd, n_inst, cap in SOLVE_SHAPES:
+            solve_shape(n, hwd, n_inst, cap, a.out)
+
+
+if __name__ == "__main__":
+    main()
