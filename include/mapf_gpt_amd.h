@@ -504,6 +504,26 @@ int mgpt_expert_step(mgpt_expert *ex, int32_t *d_actions, void *stream);
 int mgpt_expert_copy_plan(mgpt_expert *ex, int16_t *d_planned_out, void *stream);
 int mgpt_expert_copy_log(mgpt_expert *ex, int8_t *d_log_out, int32_t *d_len_out, void *stream);
 
+/* LaCAM search over the PIBT generator (plain depth-first LaCAM, Okumura AAAI 2023, restated over section 20's
+ * step; nothing is taken from the reference's dataset/lacam).  Without set_search every call above behaves as it did.
+ *   set_search:    allocates the per-instance node store, open stack, constraint pool and hash table for at most max_iters iterations
+ *                  (1 .. 2^24).  iters_per_launch: iterations per instance and launch, 0 = the library's default.  hash_bits: 0 = the table's
+ *                  own size; 1 .. 63 cuts the hash to that many bits before the probe starts (tests: every lookup then goes through the
+ *                  equality check; the outcome does not change).  May be called again; MGPT_ERR_ARG for values out of range.
+ *   solve:         right after mgpt_expert_reset (MGPT_ERR_STATE otherwise, or without set_search): searches every instance from the env's
+ *                  positions; launches until no instance is unfinished, reading one device counter per launch (synchronises the stream).
+ *   copy_search:   int32 [n_inst] each, any may be NULL: status (1 solved within max_steps, 2 open ran empty: no solution exists,
+ *                  3 max_iters reached, 4 solved but longer than max_steps), iterations used, nodes created, solution length (0 unless
+ *                  status is 1 or 4).
+ *   copy_solution: int8 [n_inst][n_agents][max_steps]: the actions of the status-1 instances, 0 elsewhere.
+ *   step:          in search mode (after solve; MGPT_ERR_STATE before it) a status-1 instance replays its solution -- actions, planned
+ *                  cells and log come from it -- and every other instance is planned by PIBT as before.
+ */
+int mgpt_expert_set_search(mgpt_expert *ex, int max_iters, int iters_per_launch, int hash_bits);
+int mgpt_expert_solve(mgpt_expert *ex, void *stream);
+int mgpt_expert_copy_search(mgpt_expert *ex, int32_t *d_status, int32_t *d_iters, int32_t *d_nodes, int32_t *d_length, void *stream);
+int mgpt_expert_copy_solution(mgpt_expert *ex, int8_t *d_solution_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Kernel timing hooks (bench.py's live roofline): when enabled, the library brackets every kernel
  * class with hipEvents on the launch stream.  mgpt_prof_read synchronises the device.

@@ -119,6 +119,10 @@ SYMBOLS = {
     "mgpt_expert_step": (_i, [_vp, _vp, _vp]),
     "mgpt_expert_copy_plan": (_i, [_vp, _vp, _vp]),
     "mgpt_expert_copy_log": (_i, [_vp, _vp, _vp, _vp]),
+    "mgpt_expert_set_search": (_i, [_vp, _i, _i, _i]),
+    "mgpt_expert_solve": (_i, [_vp, _vp]),
+    "mgpt_expert_copy_search": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "mgpt_expert_copy_solution": (_i, [_vp, _vp, _vp]),
     "mgpt_prof_enable": (_i, [_i]),
     "mgpt_prof_reset": (_i, []),
     "mgpt_prof_read": (_i, [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float),

@@ -69,6 +69,7 @@ enum ProfId {
     P_HEAD_SEQ, P_SCORE,                                // ln_f + head + cross-entropy of every position (mgpt_gpt_forward_seq), last-position scoring
     P_DS_HASH, P_DS_INSERT, P_DS_CLASSIFY, P_DS_RESOLVE, P_DS_BALANCE, P_DS_SELECT, P_DS_GATHER,   // dataset builder (dataset_build.hip)
     P_EXPERT_PLAN,                                      // the PIBT expert's plan kernel (expert.hip)
+    P_EXPERT_SEARCH,                                    // the LaCAM search kernel, every launch of a solve (expert.hip)
     P_COUNT
 };
 

@@ -3,7 +3,8 @@
 //
 // The reference's expert is LaCAM3 under POGEMA, neither of which is in its tree.  What is built here is the configuration generator
 // of such a search, one step at a time, by this project's own spec -- a weaker teacher than LaCAM: nothing
-// guarantees that all agents stand on their goals at once.
+// guarantees that all agents stand on their goals at once.  A plain depth-first LaCAM search over this generator (DESIGN.md section 21,
+// lacam_search_kernel below) can run in front of the episode: an instance it solves within the step cap replays its solution.
 //
 // One step of one instance:
 //   order      agents by (since desc, id asc), since = steps since the agent last stood on its goal;
@@ -207,6 +208,361 @@ __global__ void pibt_since_kernel(const int16_t *__restrict__ pos, const int16_t
     since[i] = on ? 0u : since[i] + 1u;
 }
 
+// ---- LaCAM search over the PIBT generator ---------------------------------------------------------------
+// One wave64 workgroup per instance, as above: plain depth-first LaCAM whose configuration generator is the PIBT step with a chain of
+// (agent, action) constraints applied first.  The node on top of `open` lives in LDS (cells, since, order, decisions with a "fixed"
+// bit); the node store, `open`, the constraint pool (a node's FIFO is a linked list through it) and an open-addressing table of node
+// ids live in HBM per instance.  A launch runs at most iters_per_launch iterations per instance and leaves its state in HBM.  The
+// generator is a copy of pibt_plan_kernel's body with the two additions of the spec, so the plan kernel's code does not change.
+constexpr int kFixed = 1 << 28;                 // in nxt[]: the agent's move is set by a constraint
+enum { S_STATUS = 0, S_ITERS, S_NODES, S_CONS, S_OPEN, S_LENGTH, S_WORDS = 8 };
+
+struct SearchArgs {
+    const uint8_t *grids;
+    const uint16_t *dist;
+    const int16_t *pos, *goal;
+    uint16_t *occ;
+    int32_t *state;                             // [n_inst][S_WORDS]
+    int32_t *node_q;                            // [n_inst][node_cap][n_agents] cell ids
+    uint32_t *node_since;                       // [n_inst][node_cap][n_agents]
+    int4 *node_meta;                            // [n_inst][node_cap] depth, parent, FIFO head, FIFO tail
+    int32_t *open;                              // [n_inst][node_cap]
+    int4 *cons;                                 // [n_inst][cons_cap] parent, who | k << 16, depth, next in the FIFO
+    int32_t *table;                             // [n_inst][table_size] node id or -1
+    int8_t *sol;                                // [n_inst][n_agents][max_steps]
+    int32_t *unfinished;                        // set to 1 by every instance that needs another launch
+    int n_grids, n_agents, H, W, max_steps, max_iters, iters_per_launch, node_cap, cons_cap, table_size;
+    uint64_t hash_mask, seed;
+    int64_t inst_offset;
+};
+
+__global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int n_agents = A.n_agents, H = A.H, W = A.W;
+    uint2 *stack = reinterpret_cast<uint2 *>(smem);                       // [n_agents] PIBT frames
+    int *cell = reinterpret_cast<int *>(stack + n_agents);                // [n_agents] the node's cell ids
+    int *nxt = cell + n_agents;                                           // [n_agents] -1 undecided, else fixed | (action << 24) | next cell id
+    int *goalc = nxt + n_agents;                                          // [n_agents] goal cell ids
+    uint32_t *snc = reinterpret_cast<uint32_t *>(goalc + n_agents);       // [n_agents] the node's since
+    uint32_t *chain = snc + n_agents;                                     // [n_agents] the constraint chain, root end first
+    uint16_t *order = reinterpret_cast<uint16_t *>(chain + n_agents);     // [n_agents] agent ids by priority
+
+    const int inst = blockIdx.x, lane = threadIdx.x;
+    int32_t *st = A.state + (size_t)inst * S_WORDS;
+    if (st[S_STATUS] != 0) return;                                        // wave-uniform: this instance has its outcome
+    const int cells = H * W;
+    const size_t g0 = (size_t)inst * n_agents;
+    const uint8_t *grid = A.grids + (size_t)(inst % A.n_grids) * cells;
+    uint16_t *occ_now = A.occ + (size_t)inst * 2 * cells, *next_occ = occ_now + cells;
+    int32_t *nq = A.node_q + (size_t)inst * A.node_cap * n_agents;
+    uint32_t *ns = A.node_since + (size_t)inst * A.node_cap * n_agents;
+    int4 *nm = A.node_meta + (size_t)inst * A.node_cap;
+    int32_t *open = A.open + (size_t)inst * A.node_cap;
+    int4 *cons = A.cons + (size_t)inst * A.cons_cap;
+    int32_t *table = A.table + (size_t)inst * A.table_size;
+    const int tmask = A.table_size - 1;
+
+    int status = 0, iters = st[S_ITERS], nodes = st[S_NODES], ncons = st[S_CONS], open_n = st[S_OPEN], length = 0;
+
+    // wrap-around sum over the agents: the reduction order cannot matter
+    auto hash_of = [&](const int *arr) -> uint64_t {
+        uint64_t h = 0;
+        for (int a = lane; a < n_agents; a += 64) h += splitmix_z(0, (uint64_t)a, (uint64_t)(arr[a] & 0xFFFFFF));
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint32_t lo = __shfl_xor((uint32_t)h, off, 64), hi = __shfl_xor((uint32_t)(h >> 32), off, 64);
+            h += ((uint64_t)hi << 32) | lo;
+        }
+        return h;
+    };
+
+    for (int a = lane; a < n_agents; a += 64) {
+        const int gc = (int)A.goal[2 * (g0 + a)] * W + (int)A.goal[2 * (g0 + a) + 1];
+        goalc[a] = min(max(gc, 0), cells - 1);
+    }
+    if (nodes == 0) {                                                     // the first launch: the start node
+        for (int a = lane; a < n_agents; a += 64) {
+            int c = (int)A.pos[2 * (g0 + a)] * W + (int)A.pos[2 * (g0 + a) + 1];
+            c = min(max(c, 0), cells - 1);
+            nxt[a] = c;
+            nq[a] = c;
+            ns[a] = 0u;
+        }
+        __syncthreads();
+        const uint64_t h = hash_of(nxt);
+        cons[0] = make_int4(-1, 0, 0, -1);
+        nm[0] = make_int4(0, -1, 0, 0);
+        table[(int)(h & A.hash_mask & (uint64_t)tmask)] = 0;
+        open[0] = 0;
+        nodes = 1; ncons = 1; open_n = 1;
+    }
+    __syncthreads();
+
+    int cur = -1, depth = 0;
+    bool at_goal = false;
+    for (int it = 0; it < A.iters_per_launch; it++) {
+        if (open_n == 0) { status = 2; break; }
+        if (iters >= A.max_iters) { status = 3; break; }
+        iters++;
+        const int top = open[open_n - 1];
+        if (top != cur) {                                                 // bring the node into LDS, its occupancy into the workspace
+            if (cur >= 0)
+                for (int a = lane; a < n_agents; a += 64) occ_now[cell[a]] = (uint16_t)kNil;
+            __syncthreads();
+            bool off = false;
+            for (int a = lane; a < n_agents; a += 64) {
+                const int c = nq[(size_t)top * n_agents + a];
+                cell[a] = c;
+                snc[a] = ns[(size_t)top * n_agents + a];
+                occ_now[c] = (uint16_t)a;
+                off |= c != goalc[a];
+            }
+            at_goal = __ballot(off) == 0ull;
+            __syncthreads();
+            for (int a = lane; a < n_agents; a += 64) {                   // rank by counting: (since desc, id asc)
+                const uint32_t s = snc[a];
+                int rank = 0;
+                for (int b = 0; b < n_agents; b++) {
+                    const uint32_t sb = snc[b];
+                    rank += (sb > s || (sb == s && b < a)) ? 1 : 0;
+                }
+                order[rank] = (uint16_t)a;
+            }
+            __syncthreads();
+            cur = top;
+            depth = nm[top].x;
+        }
+        if (at_goal) {                                                    // 1. solved: the solution is the parent chain
+            status = depth <= A.max_steps ? 1 : 4;
+            length = depth;
+            if (status == 1) {
+                int node = top;
+                for (int t = depth - 1; t >= 0; t--) {
+                    const int par = nm[node].y;
+                    for (int a = lane; a < n_agents; a += 64) {
+                        const int d = nq[(size_t)node * n_agents + a] - nq[(size_t)par * n_agents + a];
+                        const int k = (d == 0) ? 0 : (d == -W) ? 1 : (d == W) ? 2 : (d == -1) ? 3 : 4;
+                        A.sol[(g0 + a) * (size_t)A.max_steps + t] = (int8_t)k;
+                    }
+                    node = par;
+                }
+            }
+            break;
+        }
+        const int4 meta = nm[top];
+        if (meta.z < 0) { open_n--; continue; }                           // 2. nothing left to try below this node
+        const int C = meta.z;                                             // 3. the front of the FIFO, and its successors behind the tail
+        const int4 ce = cons[C];
+        const int cd = ce.z;
+        int head = ce.w, tail = (ce.w < 0) ? -1 : meta.w;
+        if (cd < n_agents) {
+            const int i = order[cd], ci = cell[i];
+            const int r = ci / W, c = ci - r * W;
+            bool valid = false;
+            if (lane < 5) {
+                const int dr = (lane == 1) ? -1 : (lane == 2 ? 1 : 0), dc = (lane == 3) ? -1 : (lane == 4 ? 1 : 0);
+                const int rr = r + dr, cc = c + dc;
+                if (rr >= 0 && rr < H && cc >= 0 && cc < W) {
+                    const int u = rr * W + cc;
+                    valid = grid[u] == 0 && A.dist[(g0 + i) * (size_t)cells + u] != kUnreach;
+                }
+            }
+            const unsigned mask = (unsigned)(__ballot(valid) & 31ull);
+            for (int k = 0; k < 5; k++) {
+                if (!((mask >> k) & 1u) || ncons >= A.cons_cap) continue; // (the pool holds one root per node and five entries per iteration)
+                cons[ncons] = make_int4(C, i | (k << 16), cd + 1, -1);
+                if (tail >= 0) cons[tail].w = ncons; else head = ncons;
+                tail = ncons;
+                ncons++;
+            }
+        }
+        nm[top] = make_int4(meta.x, meta.y, head, tail);
+
+        // 4. the generator: constraints first, then PIBT for the undecided agents
+        for (int a = lane; a < n_agents; a += 64) nxt[a] = -1;
+        __syncthreads();
+        bool fail = false;
+        for (int j = cd - 1, c = C; j >= 0; j--) {
+            const int4 e = cons[c];
+            chain[j] = (uint32_t)e.y;
+            c = e.x;
+        }
+        for (int j = 0; j < cd; j++) {
+            const int who = (int)(chain[j] & 0xFFFFu), k = (int)(chain[j] >> 16);
+            const int ca = cell[who];
+            const int u = ca + ((k == 1) ? -W : (k == 2) ? W : (k == 3) ? -1 : (k == 4) ? 1 : 0);     // in the frame: checked when the constraint was made
+            if (next_occ[u] != kNil) { fail = true; break; }
+            unsigned c = occ_now[u];
+            if (c >= (unsigned)n_agents) c = kNil;
+            if (c != kNil && c != (unsigned)who) {
+                const int nc = nxt[c];
+                if (nc >= 0 && (nc & 0xFFFFFF) == ca) { fail = true; break; }
+            }
+            nxt[who] = kFixed | (k << 24) | u;
+            next_occ[u] = (uint16_t)who;
+        }
+        int sp = 0;
+        bool ret = false;
+        for (int oi = 0; oi < n_agents && !fail; oi++) {
+            const int first = order[oi];
+            if (nxt[first] >= 0) continue;
+            int push_a = first, push_par = (int)kNil;
+            for (;;) {
+                if (push_a >= 0) {                                        // enter PIBT(push_a, push_par): form and sort its candidates
+                    const int a = push_a, ca = cell[a];
+                    const int r = ca / W, c = ca - r * W;
+                    const uint64_t z = splitmix_z(A.seed, (uint64_t)depth, (uint64_t)((A.inst_offset + inst) * (int64_t)n_agents + a));
+                    unsigned key = 0xFFFFFFF8u | (unsigned)min(lane, 7);
+                    bool valid = false;
+                    if (lane < 5) {
+                        const int dr = (lane == 1) ? -1 : (lane == 2 ? 1 : 0), dc = (lane == 3) ? -1 : (lane == 4 ? 1 : 0);
+                        const int rr = r + dr, cc = c + dc;
+                        if (rr >= 0 && rr < H && cc >= 0 && cc < W) {
+                            const int u = rr * W + cc;
+                            const unsigned d = A.dist[(g0 + a) * (size_t)cells + u];
+                            if (grid[u] == 0 && d != kUnreach) {
+                                const unsigned who = occ_now[u];
+                                const unsigned o = (who != kNil && who != (unsigned)a) ? 1u : 0u;
+                                const unsigned rk = (unsigned)(z >> (5 * lane)) & 31u;
+                                key = (((d * 2u + o) * 32u + rk) * 8u) + (unsigned)lane;
+                                valid = true;
+                            }
+                        }
+                    }
+                    int rank = 0;
+#pragma unroll
+                    for (int j = 0; j < 5; j++) rank += (__shfl(key, j, 64) < key) ? 1 : 0;
+                    const unsigned contrib = valid ? ((unsigned)lane << (3 * rank)) : 0u;
+                    unsigned packed = 0;
+#pragma unroll
+                    for (int j = 0; j < 5; j++) packed |= __shfl(contrib, j, 64);
+                    const unsigned ncand = (unsigned)__popcll(__ballot(valid));
+                    if (sp >= n_agents) break;                            // (cannot happen: an agent enters at most once per step)
+                    stack[sp] = make_uint2((unsigned)a | ((unsigned)push_par << 16), packed | (ncand << 15));
+                    sp++;
+                    push_a = -1;
+                }
+                if (sp == 0) break;
+                const uint2 f = stack[sp - 1];
+                const int a = (int)(f.x & 0xFFFFu);
+                const unsigned par = f.x >> 16;
+                unsigned y = f.y;
+                if (y & kFrameWaiting) {                                  // back from PIBT(c, a)
+                    y &= ~kFrameWaiting;
+                    if (ret) { sp--; continue; }
+                }
+                const unsigned ncand = (y >> 15) & 7u;
+                unsigned idx = (y >> 18) & 7u;
+                const int ca = cell[a];
+                const int par_cell = (par != kNil) ? cell[par] : -1;
+                bool settled = false;
+                while (idx < ncand) {
+                    const int k = (int)((y >> (3 * idx)) & 7u);
+                    idx++;
+                    const int u = ca + ((k == 1) ? -W : (k == 2) ? W : (k == 3) ? -1 : (k == 4) ? 1 : 0);
+                    if (next_occ[u] != kNil) continue;                    // reserved for the next step (by a constraint too)
+                    if (u == par_cell) continue;
+                    unsigned c = occ_now[u];
+                    if (c >= (unsigned)n_agents) c = kNil;
+                    const int nc = (c != kNil) ? nxt[c] : -1;
+                    if (nc >= 0 && (nc & 0xFFFFFF) == ca) continue;       // a swap with a decided (or fixed) agent
+                    nxt[a] = (k << 24) | u;
+                    next_occ[u] = (uint16_t)a;
+                    settled = true;
+                    if (c != kNil && c != (unsigned)a && nc < 0) {
+                        stack[sp - 1].y = (y & ~(7u << 18)) | (idx << 18) | kFrameWaiting;
+                        push_a = (int)c;
+                        push_par = a;
+                    } else {
+                        ret = true;
+                        sp--;
+                    }
+                    break;
+                }
+                if (!settled) {                                           // no candidate left
+                    unsigned holder = next_occ[ca];
+                    if (holder >= (unsigned)n_agents) holder = kNil;
+                    if (holder != kNil && nxt[holder] >= 0 && (nxt[holder] & kFixed)) {   // a's cell belongs to a fixed agent: the generator fails
+                        fail = true;
+                        break;
+                    }
+                    nxt[a] = ca;
+                    next_occ[ca] = (uint16_t)a;
+                    ret = false;
+                    sp--;
+                }
+            }
+        }
+        __syncthreads();
+        for (int a = lane; a < n_agents; a += 64) {                       // the reservations of this call go back to NIL, whatever its outcome
+            const int v = nxt[a];
+            if (v >= 0) next_occ[v & 0xFFFFFF] = (uint16_t)kNil;
+        }
+        __syncthreads();
+        if (fail) continue;
+
+        // 5. explored?  Equality of the whole configuration decides; the hash only says where to start looking
+        const uint64_t h = hash_of(nxt);
+        int slot = (int)(h & A.hash_mask & (uint64_t)tmask);
+        bool found = false;
+        for (int probe = 0; probe < A.table_size; probe++) {
+            const int id = table[slot];
+            if (id < 0) break;
+            bool diff = false;
+            for (int a = lane; a < n_agents; a += 64) diff |= nq[(size_t)id * n_agents + a] != (nxt[a] & 0xFFFFFF);
+            if (__ballot(diff) == 0ull) { found = true; break; }
+            slot = (slot + 1) & tmask;
+        }
+        if (found || nodes >= A.node_cap || ncons >= A.cons_cap || table[slot] >= 0) continue;   // (the caps cannot be reached: see mgpt_expert_set_search)
+
+        // 6. the new node
+        const int id = nodes++;
+        for (int a = lane; a < n_agents; a += 64) {
+            const int u = nxt[a] & 0xFFFFFF;
+            nq[(size_t)id * n_agents + a] = u;
+            ns[(size_t)id * n_agents + a] = (u == goalc[a]) ? 0u : snc[a] + 1u;
+        }
+        cons[ncons] = make_int4(-1, 0, 0, -1);
+        nm[id] = make_int4(depth + 1, top, ncons, ncons);
+        ncons++;
+        table[slot] = id;
+        open[open_n++] = id;
+    }
+    __syncthreads();
+    if (cur >= 0)
+        for (int a = lane; a < n_agents; a += 64) occ_now[cell[a]] = (uint16_t)kNil;   // leave the workspace all-NIL
+    st[S_STATUS] = status; st[S_ITERS] = iters; st[S_NODES] = nodes; st[S_CONS] = ncons; st[S_OPEN] = open_n; st[S_LENGTH] = length;
+    if (status == 0 && lane == 0) *A.unfinished = 1;
+}
+
+// search mode: an instance whose solution is replayed is hidden from the plan kernel (as if done) ...
+__global__ void search_skip_kernel(const uint8_t *__restrict__ done, const int32_t *__restrict__ state, uint8_t *__restrict__ skip, int n_inst)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n_inst) skip[i] = (done[i] != 0 || state[(size_t)i * S_WORDS + S_STATUS] == 1) ? 1 : 0;
+}
+
+// ... and takes its actions, planned cells and log entry from the solution
+__global__ __launch_bounds__(64) void search_replay_kernel(const int32_t *__restrict__ state, const int8_t *__restrict__ sol,
+                                                           const int16_t *__restrict__ pos, const uint8_t *__restrict__ done, int n_agents,
+                                                           int32_t *__restrict__ actions, int16_t *__restrict__ planned, int8_t *__restrict__ log,
+                                                           int32_t *__restrict__ len, int max_steps)
+{
+    const int inst = blockIdx.x, lane = threadIdx.x;
+    if (done[inst] != 0 || state[(size_t)inst * S_WORDS + S_STATUS] != 1) return;
+    const int tl = len[inst], length = state[(size_t)inst * S_WORDS + S_LENGTH];
+    const size_t g0 = (size_t)inst * n_agents;
+    __syncthreads();
+    for (int a = lane; a < n_agents; a += 64) {
+        const int k = (tl < length && tl < max_steps) ? (int)sol[(g0 + a) * (size_t)max_steps + tl] : 0;
+        actions[g0 + a] = k;
+        planned[2 * (g0 + a)] = (int16_t)(pos[2 * (g0 + a)] + ((k == 1) ? -1 : (k == 2) ? 1 : 0));
+        planned[2 * (g0 + a) + 1] = (int16_t)(pos[2 * (g0 + a) + 1] + ((k == 3) ? -1 : (k == 4) ? 1 : 0));
+        if (tl < max_steps) log[(g0 + a) * (size_t)max_steps + tl] = (int8_t)k;
+    }
+    if (lane == 0 && tl < max_steps) len[inst] = tl + 1;
+}
+
 }  // namespace
 
 struct mgpt_expert {
@@ -225,9 +581,29 @@ struct mgpt_expert {
     int8_t *log = nullptr;                      // [n_inst][n_agents][max_steps]
     int32_t *len = nullptr;                     // [n_inst]
     bool have_reset = false;
+    // LaCAM search (mgpt_expert_set_search): all NULL / 0 without it
+    bool search = false, solved = false;
+    int max_iters = 0, iters_per_launch = 0, hash_bits = 0, node_cap = 0, cons_cap = 0, table_size = 0;
+    int32_t *s_state = nullptr, *s_node_q = nullptr, *s_open = nullptr, *s_table = nullptr, *s_unfinished = nullptr;
+    uint32_t *s_node_since = nullptr;
+    int4 *s_node_meta = nullptr, *s_cons = nullptr;
+    int8_t *s_sol = nullptr;
+    uint8_t *s_skip = nullptr;
 };
 
 static size_t expert_lds_bytes(int n_agents) { return (size_t)n_agents * (sizeof(uint2) + 2 * sizeof(int) + sizeof(uint16_t)); }
+static size_t search_lds_bytes(int n_agents) { return (size_t)n_agents * (sizeof(uint2) + 5 * sizeof(int) + sizeof(uint16_t)); }
+constexpr int kDefaultItersPerLaunch = 512;     // the slice after which the host looks at the unfinished counter
+
+static void search_free(mgpt_expert *ex)
+{
+    (void)hipFree(ex->s_state); (void)hipFree(ex->s_node_q); (void)hipFree(ex->s_open); (void)hipFree(ex->s_table);
+    (void)hipFree(ex->s_unfinished); (void)hipFree(ex->s_node_since); (void)hipFree(ex->s_node_meta); (void)hipFree(ex->s_cons);
+    (void)hipFree(ex->s_sol); (void)hipFree(ex->s_skip);
+    ex->s_state = ex->s_node_q = ex->s_open = ex->s_table = ex->s_unfinished = nullptr;
+    ex->s_node_since = nullptr; ex->s_node_meta = ex->s_cons = nullptr; ex->s_sol = nullptr; ex->s_skip = nullptr;
+    ex->search = ex->solved = false;
+}
 
 // what the planner does not model: lifelong goal queues and the non-default collision rules
 static int expert_check_env(const mgpt_expert *ex)
@@ -280,6 +656,7 @@ extern "C" int mgpt_expert_destroy(mgpt_expert *ex)
 {
     if (!ex) return MGPT_OK;
     (void)hipFree(ex->occ); (void)hipFree(ex->since); (void)hipFree(ex->planned); (void)hipFree(ex->log); (void)hipFree(ex->len);
+    search_free(ex);
     delete ex;
     return MGPT_OK;
 }
@@ -302,6 +679,106 @@ extern "C" int mgpt_expert_reset(mgpt_expert *ex, void *stream)
     MGPT_HIP(hipMemsetAsync(ex->len, 0, (size_t)ex->n_inst * sizeof(int32_t), s));
     ex->t = 0;
     ex->have_reset = true;
+    ex->solved = false;
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_expert_set_search(mgpt_expert *ex, int max_iters, int iters_per_launch, int hash_bits)
+{
+    MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(max_iters >= 1 && max_iters <= (1 << 24), MGPT_ERR_ARG, "max_iters=%d: 1 .. 2^24", max_iters);
+    MGPT_REQUIRE(iters_per_launch >= 0, MGPT_ERR_ARG, "iters_per_launch=%d: 0 (the default) or a positive count", iters_per_launch);
+    MGPT_REQUIRE(hash_bits >= 0 && hash_bits <= 63, MGPT_ERR_ARG, "hash_bits=%d: 0 (the table's own size) .. 63", hash_bits);
+    MGPT_REQUIRE(search_lds_bytes(ex->n_agents) <= 64 * 1024, MGPT_ERR_UNSUPPORTED, "n_agents=%d: the search's node does not fit 64 KB of LDS",
+                 ex->n_agents);
+    search_free(ex);
+    ex->max_iters = max_iters;
+    ex->iters_per_launch = iters_per_launch > 0 ? iters_per_launch : kDefaultItersPerLaunch;
+    ex->hash_bits = hash_bits;
+    ex->node_cap = max_iters + 1;                            // the start node and at most one node per iteration
+    ex->cons_cap = ex->node_cap + 5 * max_iters;             // one root per node and at most five successors per iteration
+    ex->table_size = 2;
+    while (ex->table_size < 2 * ex->node_cap) ex->table_size *= 2;      // load factor <= 1/2: a probe always ends on an empty slot
+    const size_t ni = (size_t)ex->n_inst, na = (size_t)ex->n_agents, nc = (size_t)ex->node_cap;
+    hipError_t e = hipMalloc(&ex->s_state, ni * S_WORDS * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&ex->s_node_q, ni * nc * na * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&ex->s_node_since, ni * nc * na * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&ex->s_node_meta, ni * nc * sizeof(int4));
+    if (e == hipSuccess) e = hipMalloc(&ex->s_open, ni * nc * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&ex->s_cons, ni * (size_t)ex->cons_cap * sizeof(int4));
+    if (e == hipSuccess) e = hipMalloc(&ex->s_table, ni * (size_t)ex->table_size * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&ex->s_sol, ni * na * (size_t)ex->max_steps);
+    if (e == hipSuccess) e = hipMalloc(&ex->s_skip, ni);
+    if (e == hipSuccess) e = hipMalloc(&ex->s_unfinished, sizeof(int32_t));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("hipMalloc failed in mgpt_expert_set_search (max_iters=%d, %d instances x %d agents): %s", max_iters, ex->n_inst, ex->n_agents,
+                  hipGetErrorString(e));
+        search_free(ex);
+        return MGPT_ERR_HIP;
+    }
+    ex->search = true;
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_expert_solve(mgpt_expert *ex, void *stream)
+{
+    MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(ex->search, MGPT_ERR_STATE, "mgpt_expert_set_search must precede mgpt_expert_solve");
+    MGPT_REQUIRE(ex->have_reset && ex->t == 0, MGPT_ERR_STATE, "mgpt_expert_solve runs right after mgpt_expert_reset (the search starts from the env's positions at reset)");
+    const int rc = expert_check_env(ex);
+    if (rc != MGPT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t ni = (size_t)ex->n_inst;
+    MGPT_HIP(hipMemsetAsync(ex->s_state, 0, ni * S_WORDS * sizeof(int32_t), s));
+    MGPT_HIP(hipMemsetAsync(ex->s_table, 0xFF, ni * (size_t)ex->table_size * sizeof(int32_t), s));
+    MGPT_HIP(hipMemsetAsync(ex->s_sol, 0, ni * (size_t)ex->n_agents * (size_t)ex->max_steps, s));
+    SearchArgs A;
+    A.grids = ex->grids; A.dist = ex->dist; A.pos = ex->pos; A.goal = ex->goal; A.occ = ex->occ;
+    A.state = ex->s_state; A.node_q = ex->s_node_q; A.node_since = ex->s_node_since; A.node_meta = ex->s_node_meta; A.open = ex->s_open;
+    A.cons = ex->s_cons; A.table = ex->s_table; A.sol = ex->s_sol; A.unfinished = ex->s_unfinished;
+    A.n_grids = ex->n_grids; A.n_agents = ex->n_agents; A.H = ex->H; A.W = ex->W; A.max_steps = ex->max_steps; A.max_iters = ex->max_iters;
+    A.iters_per_launch = ex->iters_per_launch; A.node_cap = ex->node_cap; A.cons_cap = ex->cons_cap; A.table_size = ex->table_size;
+    A.hash_mask = ex->hash_bits ? ((1ull << ex->hash_bits) - 1ull) : ~0ull;
+    A.seed = ex->seed; A.inst_offset = ex->inst_offset;
+    // every launch that leaves an instance unfinished has run iters_per_launch iterations of it: this many launches always suffice
+    const int64_t launches = cdiv64((int64_t)ex->max_iters + 1, ex->iters_per_launch) + 1;
+    int32_t unfinished = 1;
+    for (int64_t l = 0; l < launches && unfinished; l++) {
+        MGPT_HIP(hipMemsetAsync(ex->s_unfinished, 0, sizeof(int32_t), s));
+        {
+            ProfScope ps(P_EXPERT_SEARCH, s);
+            hipLaunchKernelGGL(lacam_search_kernel, dim3(ex->n_inst), dim3(64), search_lds_bytes(ex->n_agents), s, A);
+            MGPT_LAUNCH_CHECK();
+        }
+        MGPT_HIP(hipMemcpyAsync(&unfinished, ex->s_unfinished, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        MGPT_HIP(hipStreamSynchronize(s));
+    }
+    MGPT_REQUIRE(!unfinished, MGPT_ERR_STATE, "the search left instances unfinished after %lld launches", (long long)launches);
+    ex->solved = true;
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_expert_copy_search(mgpt_expert *ex, int32_t *d_status, int32_t *d_iters, int32_t *d_nodes, int32_t *d_length, void *stream)
+{
+    MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(ex->search && ex->solved, MGPT_ERR_STATE, "mgpt_expert_solve must precede mgpt_expert_copy_search");
+    hipStream_t s = (hipStream_t)stream;
+    int32_t *outs[4] = {d_status, d_iters, d_nodes, d_length};
+    const int words[4] = {S_STATUS, S_ITERS, S_NODES, S_LENGTH};
+    for (int j = 0; j < 4; j++)
+        if (outs[j])
+            MGPT_HIP(hipMemcpy2DAsync(outs[j], sizeof(int32_t), ex->s_state + words[j], S_WORDS * sizeof(int32_t), sizeof(int32_t), (size_t)ex->n_inst,
+                                      hipMemcpyDeviceToDevice, s));
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_expert_copy_solution(mgpt_expert *ex, int8_t *d_solution_out, void *stream)
+{
+    MGPT_REQUIRE(ex && d_solution_out, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(ex->search && ex->solved, MGPT_ERR_STATE, "mgpt_expert_solve must precede mgpt_expert_copy_solution");
+    MGPT_HIP(hipMemcpyAsync(d_solution_out, ex->s_sol, (size_t)ex->n_inst * ex->n_agents * (size_t)ex->max_steps, hipMemcpyDeviceToDevice,
+                            (hipStream_t)stream));
     return MGPT_OK;
 }
 
@@ -311,12 +788,24 @@ extern "C" int mgpt_expert_step(mgpt_expert *ex, int32_t *d_actions, void *strea
     MGPT_REQUIRE(ex->have_reset, MGPT_ERR_STATE, "mgpt_expert_reset must precede mgpt_expert_step");
     int rc = expert_check_env(ex);
     if (rc != MGPT_OK) return rc;
+    MGPT_REQUIRE(!ex->search || ex->solved, MGPT_ERR_STATE, "in search mode mgpt_expert_solve must precede mgpt_expert_step");
     hipStream_t s = (hipStream_t)stream;
+    const uint8_t *skip = ex->done;
+    if (ex->search) {                                        // solved instances replay their solution; the plan kernel sees them as done
+        hipLaunchKernelGGL(search_skip_kernel, dim3(cdiv(ex->n_inst, 256)), dim3(256), 0, s, ex->done, ex->s_state, ex->s_skip, ex->n_inst);
+        MGPT_LAUNCH_CHECK();
+        skip = ex->s_skip;
+    }
     {
         ProfScope ps(P_EXPERT_PLAN, s);
         hipLaunchKernelGGL(pibt_plan_kernel, dim3(ex->n_inst), dim3(64), expert_lds_bytes(ex->n_agents), s, ex->grids, ex->n_grids, ex->n_agents,
-                           ex->H, ex->W, ex->dist, ex->pos, ex->done, ex->since, ex->occ, d_actions, ex->planned, ex->log, ex->len, ex->max_steps,
+                           ex->H, ex->W, ex->dist, ex->pos, skip, ex->since, ex->occ, d_actions, ex->planned, ex->log, ex->len, ex->max_steps,
                            ex->seed, ex->t, ex->inst_offset);
+        MGPT_LAUNCH_CHECK();
+    }
+    if (ex->search) {
+        hipLaunchKernelGGL(search_replay_kernel, dim3(ex->n_inst), dim3(64), 0, s, ex->s_state, ex->s_sol, ex->pos, ex->done, ex->n_agents, d_actions,
+                           ex->planned, ex->log, ex->len, ex->max_steps);
         MGPT_LAUNCH_CHECK();
     }
     if ((rc = mgpt_env_step(ex->env, d_actions, s)) != MGPT_OK) return rc;

@@ -195,8 +195,17 @@ class PIBTConfig:
         self.name, self.seed, self.device = name, int(seed or 0), device
 
 
+class LaCAMConfig(PIBTConfig):
+    """Config of the `name: LaCAM` algorithm: the same expert with a LaCAM search in front of every episode (DESIGN.md section 21);
+    name, seed, device, max_iters."""
+
+    def __init__(self, name="LaCAM", seed=0, device="cuda", max_iters=4096):
+        super().__init__(name, seed, device)
+        self.max_iters = int(max_iters)
+
+
 def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, max_rows_per_batch=65536, rank=0, world=1,
-               print_fn=print, trace=None, retire_done=False, log_actions=False):
+               print_fn=print, trace=None, retire_done=False, log_actions=False, search_status=None):
     """Run `evaluation_config` (dict in the reference's YAML schema).  Returns the list of result records (on every
     rank); writes `<eval_dir>/<algorithm>.json` and prints the tabular views on rank 0.
     `trace(kind, payload)` (tests): called with ("reset", {algorithm, runs, grids, pos, goal, max_steps}) for every batch
@@ -207,7 +216,8 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
     An algorithm whose `name` is PIBT runs the device-resident expert (BatchedExpert) instead of a policy: same grouping, frames,
     placement, sharding and metrics gather.  log_actions: the role of the reference's create_logging_env (create_env.py:8-33) -- the
     PIBT records also carry `made_actions` (per agent, cut to the episode's length) and `init_positions` (padded coordinates), the
-    expert log that dataset_build / dataset_tokenizer consume; one rank only."""
+    expert log that dataset_build / dataset_tokenizer consume; one rank only.  An algorithm whose `name` is LaCAM is the same expert
+    with search="lacam"; search_status (a dict) then receives the count of this rank's instances per search status."""
     import torch
     from .runner import BatchedRunner, gather_metrics, shard_range
 
@@ -220,9 +230,9 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
     results = []
     for algo_name, algo_cfg in evaluation_config["algorithms"].items():
         algo_cfg = dict(algo_cfg)
-        is_pibt = algo_cfg.get("name") == "PIBT"
+        is_pibt = algo_cfg.get("name") in ("PIBT", "LaCAM")
         if is_pibt:
-            algo, cfg = None, PIBTConfig(**algo_cfg)
+            algo, cfg = None, (LaCAMConfig if algo_cfg.get("name") == "LaCAM" else PIBTConfig)(**algo_cfg)
         else:
             if precision is not None:
                 algo_cfg["precision"] = precision
@@ -251,7 +261,8 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                         pos[k], goal[k] = _maps.place_agents(g, n_agents, int(runs[i][0].get("seed", 0)), s_ok, g_ok)
                     if is_pibt:
                         from .expert import BatchedExpert
-                        run = BatchedExpert(grids, len(mine), n_agents, max_steps, seed=cfg.seed, device=cfg.device, inst_offset=lo)
+                        search = dict(search="lacam", max_iters=cfg.max_iters) if isinstance(cfg, LaCAMConfig) else {}
+                        run = BatchedExpert(grids, len(mine), n_agents, max_steps, seed=cfg.seed, device=cfg.device, inst_offset=lo, **search)
                     else:
                         run = BatchedRunner(grids, len(mine), n_agents, algo.net, max_episode_steps=max_steps,
                                             seed=int(cfg.seed or 0), do_sample=True, precision=cfg.precision, device=cfg.device,
@@ -267,6 +278,9 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                         queue = torch.from_numpy(queue)
                     if is_pibt:
                         run.reset(torch.from_numpy(pos), torch.from_numpy(goal))
+                        if run.search and search_status is not None:
+                            for v in run.search_stats()[0].cpu().tolist():
+                                search_status[v] = search_status.get(v, 0) + 1
                     else:
                         run.reset(torch.from_numpy(pos), torch.from_numpy(goal), goal_queue=queue)
                     if trace is None:

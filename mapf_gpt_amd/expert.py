@@ -11,10 +11,16 @@ stand on their goals at once, and episodes that do not end with CSR = 1 are drop
     records = ex.records(run_keys, pos)            # toolbox records with made_actions / init_positions
 
     python -m mapf_gpt_amd.expert --config CONFIG.yaml --maps MAPS.yaml --out DIR      # writes DIR/PIBT.json
+    python -m mapf_gpt_amd.expert --algo lacam [--max-iters N] ...                      # writes DIR/LaCAM.json
+
+`search="lacam"` puts a LaCAM search (plain depth-first LaCAM over this PIBT as its configuration generator) in
+front of the episode: reset() solves every instance on the device, an instance solved within the step cap replays its solution, every
+other instance is planned step by step by PIBT as before, so the expert is never worse than PIBT alone.
 
 The config is an evaluation YAML (eval_configs/<folder>/<folder>.yaml): its `environment:` block is run; its `algorithms:` block is
 replaced by one PIBT entry (seed from --seed).  DIR/PIBT.json is what `dataset_build.split_by_map` and `dataset_build --logs` take
-where the reference has LaCAM.json.  Prints one JSON line: episodes, solved, rows, seconds.
+where the reference has LaCAM.json.  Prints one JSON line: episodes, solved, rows, seconds (with --algo lacam also `status`: the
+count of instances per search status).
 """
 import argparse
 import ctypes
@@ -33,7 +39,10 @@ from .observation_generator import BatchedTokenizer
 class BatchedExpert:
     """Same shape as BatchedRunner: owns a BatchedEnv and a BatchedTokenizer (used for its BFS distance fields only)."""
 
-    def __init__(self, grids, n_inst, n_agents, max_episode_steps, seed=0, device="cuda", inst_offset=0):
+    def __init__(self, grids, n_inst, n_agents, max_episode_steps, seed=0, device="cuda", inst_offset=0, search=None, max_iters=4096,
+                 iters_per_launch=None, hash_bits=0):
+        if search not in (None, "lacam"):
+            raise ValueError(f"search={search!r}: None or 'lacam'")
         self.device = torch.device(device)
         self.env = BatchedEnv(grids, n_inst, n_agents, max_episode_steps, device=device)
         self.tok = BatchedTokenizer(grids, n_inst, n_agents, device=device)
@@ -45,6 +54,10 @@ class BatchedExpert:
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().mgpt_expert_create(ctypes.byref(self._h), self.tok._h, self.env._h, self.seed & (2 ** 64 - 1),
                                                      self.inst_offset, self.max_episode_steps))
+        self.search, self.max_iters = search, int(max_iters)
+        if search:           # iters_per_launch None = the library's default slice; hash_bits 0 = the table's own size (tests cut it short)
+            with _lib.on_device(self.device):
+                _lib.check(_lib.lib().mgpt_expert_set_search(self._h, self.max_iters, int(iters_per_launch or 0), int(hash_bits)))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -62,6 +75,23 @@ class BatchedExpert:
         self.t = 0
         with _lib.on_device(self.device):
             _lib.check(_lib.lib().mgpt_expert_reset(self._h, _lib.stream_ptr()))
+            if self.search:
+                _lib.check(_lib.lib().mgpt_expert_solve(self._h, _lib.stream_ptr()))
+
+    def search_stats(self):
+        """-> status, iterations, nodes, solution length: int32 [n_inst] device tensors.  status 1 solved within the step cap (the
+        instance replays its solution), 2 no solution exists, 3 max_iters reached, 4 solved but longer than the step cap."""
+        out = [torch.empty((self.n_inst,), dtype=torch.int32, device=self.device) for _ in range(4)]
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_copy_search(self._h, *[_lib.ptr(t) for t in out], _lib.stream_ptr()))
+        return tuple(out)
+
+    def solution(self):
+        """int8 [n_inst, n_agents, T]: the actions of the status-1 instances, 0 elsewhere (device tensor)."""
+        out = torch.empty((self.n_inst, self.n_agents, self.max_episode_steps), dtype=torch.int8, device=self.device)
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_copy_solution(self._h, _lib.ptr(out), _lib.stream_ptr()))
+        return out
 
     def step(self):
         """plan -> log -> env.step -> since update in ONE library call (mgpt_expert_step)."""
@@ -113,24 +143,33 @@ class BatchedExpert:
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="Run the PIBT expert over an evaluation config and write DIR/PIBT.json")
+    ap = argparse.ArgumentParser(description="Run the expert over an evaluation config and write DIR/PIBT.json (or DIR/LaCAM.json)")
     ap.add_argument("--config", required=True, help="evaluation YAML (its environment: block is run)")
     ap.add_argument("--maps", default=None, help="maps.yaml ({name: map string}) registered on top of the built-in maps")
     ap.add_argument("--out", required=True, help="output directory")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--algo", choices=["pibt", "lacam"], default="pibt", help="lacam: a LaCAM search in front of every episode")
+    ap.add_argument("--max-iters", type=int, default=4096, help="--algo lacam: iterations of the search per instance")
     a = ap.parse_args(argv)
     from . import evaluation as ev
     cfg = ev.load_yaml(a.config)
     reg = ev.MapRegistry()
     if a.maps:
         reg.register_maps(ev.load_yaml(a.maps))
-    cfg = {"environment": cfg["environment"], "algorithms": {"PIBT": {"name": "PIBT", "seed": a.seed, "device": a.device}}}
+    algo = {"name": "PIBT", "seed": a.seed, "device": a.device}
+    if a.algo == "lacam":
+        algo = {"name": "LaCAM", "seed": a.seed, "device": a.device, "max_iters": a.max_iters}
+    cfg = {"environment": cfg["environment"], "algorithms": {algo["name"]: algo}}
+    status = {}
     t0 = time.perf_counter()
-    res = ev.evaluation(cfg, eval_dir=a.out, registry=reg, print_fn=lambda *_: None, log_actions=True)
+    res = ev.evaluation(cfg, eval_dir=a.out, registry=reg, print_fn=lambda *_: None, log_actions=True, search_status=status)
     solved = [r for r in res if r["metrics"]["CSR"] >= 1]
     rows = sum(len(r["metrics"]["made_actions"]) * (int(r["metrics"]["ep_length"]) + 1) for r in solved)     # dataset rows of the solved episodes
-    print(json.dumps({"episodes": len(res), "solved": len(solved), "rows": rows, "seconds": round(time.perf_counter() - t0, 3)}))
+    line = {"episodes": len(res), "solved": len(solved), "rows": rows, "seconds": round(time.perf_counter() - t0, 3)}
+    if a.algo == "lacam":
+        line["status"] = {str(k): int(v) for k, v in sorted(status.items())}
+    print(json.dumps(line))
     return 0
 
 

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Time and solve rates of the PIBT expert (mapf_gpt_amd/expert.py).
+"""Time and solve rates of the PIBT expert (mapf_gpt_amd/expert.py) and of the LaCAM search in front of it
+(--algo lacam).
 
     --what time    three shapes: `dataset` 4096 instances x 32 agents on a 21 x 21 maze (the dataset's shape), `cfg3` 64 instances x 192
                    agents on wfi_warehouse (bench.py's cfg3 map), `one` 1 instance x 32 agents.  Per shape: one warm-up episode, then
@@ -7,7 +8,11 @@
                    (mgpt_expert_step: plan + env step + since update); then one more episode under the library's timing hooks for the
                    split of a step between the plan kernel and the env step.  ms per step = run time / steps; episodes per second =
                    instances / (reset + run).
-    --what solve   solved episodes of six small shapes on seeded random maps (seed 7): the table of DESIGN section 20.
+    --what solve   solved episodes of six small shapes on seeded random maps (seed 7): the table of DESIGN section 20; then 256 instances
+                   of 16, 24 and 32 agents on the dataset's 21 x 21 maze.
+    --algo lacam   the same shapes with search="lacam" (--max-iters, --iters-per-launch).  solve adds the count of instances per search
+                   status, the search's time per instance and its iterations; time adds the solve (HIP events around it, and the search
+                   kernel's own time from the timing hooks), iterations per second and microseconds per iteration.
 
 Prints one JSON line per shape; --out FILE appends them there too.  Needs the GPU: there is no CPU path.
 """
@@ -28,6 +33,8 @@ TIME_SHAPES = {"dataset": ("maze21", 4096, 32, 128), "cfg3": ("wfi_warehouse", 6
 # agents, (h, w, obstacle density), instances, step cap
 SOLVE_SHAPES = [(4, (8, 8, 0.0), 32, 64), (8, (12, 12, 0.2), 32, 64), (32, (21, 21, 0.25), 32, 128), (64, (32, 32, 0.3), 16, 256),
                 (70, (16, 16, 0.2), 16, 256), (3, (1, 12, 0.0), 16, 64)]
+# the dataset's maze at three agent counts
+MAZE_SHAPES = [(16, "maze21", 256, 128), (24, "maze21", 256, 128), (32, "maze21", 256, 128)]
 
 
 def emit(rec, out):
@@ -45,6 +52,58 @@ def timed(fn):
     t1.record()
     t1.synchronize()
     return t0.elapsed_time(t1)
+
+
+def search_kw(a):
+    return dict(search="lacam", max_iters=a.max_iters, iters_per_launch=a.iters_per_launch) if a.algo == "lacam" else {}
+
+
+def search_fields(ex, search_ms, kernel_ms=None):
+    """What a solve adds to a record: status counts, iterations, the search's time per instance and per iteration."""
+    st, it, nodes, length = (t.cpu().numpy() for t in ex.search_stats())
+    total = int(it.sum())
+    rec = {"max_iters": ex.max_iters, "status": {str(k): int((st == k).sum()) for k in (1, 2, 3, 4)}, "iterations": total,
+           "max_iterations_of_an_instance": int(it.max()), "nodes": int(nodes.sum()), "search_ms": round(search_ms, 3),
+           "search_ms_per_instance": round(search_ms / len(st), 4), "iterations_per_s": round(total / max(search_ms * 1e-3, 1e-9), 1),
+           "us_per_iteration_of_the_longest_instance": round(search_ms * 1e3 / max(int(it.max()), 1), 3),
+           "mean_length_of_status_1": round(float(length[st == 1].mean()), 2) if (st == 1).any() else None}
+    if kernel_ms is not None:
+        rec["search_kernel_ms"] = round(kernel_ms[0], 3)
+        rec["search_launches"] = int(kernel_ms[1])
+    return rec
+
+
+def time_search(name, a):
+    """The solve of one timing shape: reset() = BFS + search, the search alone from the stream's events around mgpt_expert_solve."""
+    map_name, n_inst, n, steps = TIME_SHAPES[name]
+    if map_name == "maze21":
+        grid, s_ok, g_ok = maps.pad(maps.maze_map(21, 21, 7)), None, None
+    else:
+        grid, s_ok, g_ok = maps.load_named(map_name)
+    pos, goal = make_instances(grid, n_inst, n, 0, s_ok, g_ok)
+    ex = BatchedExpert(grid, n_inst, n, steps, seed=7, **search_kw(a))
+    h = ex._h
+    solve_ms = []
+    for rep in range(a.repeats + 1):                 # episode 0 warms up
+        ex.search = None                             # reset without the solve, then the solve alone between two events
+        ex.reset(pos, goal)
+        ex.search = "lacam"
+        with _lib.on_device(ex.device):
+            ms = timed(lambda: _lib.check(_lib.lib().mgpt_expert_solve(h, _lib.stream_ptr())))
+        if rep:
+            solve_ms.append(ms)
+    _lib.prof_enable(True)
+    _lib.prof_reset()
+    ex.reset(pos, goal)
+    prof = _lib.prof_read()
+    _lib.prof_enable(False)
+    run_ms = timed(lambda: ex.run(steps))
+    m = ex.metrics().cpu().numpy()
+    rec = {"tool": "bench_expert", "what": "time", "algo": "lacam", "shape": name, "map": map_name, "instances": n_inst, "agents": n,
+           "steps": steps, "iters_per_launch": a.iters_per_launch, "solve_ms_runs": [round(x, 3) for x in solve_ms]}
+    rec.update(search_fields(ex, float(np.median(solve_ms)), prof.get("expert_lacam_search", (0.0, 0))))
+    rec.update({"ms_run_after_solve": round(run_ms, 3), "solved": int(m[:, 0].sum()), "mean_isr": round(float(m[:, 1].mean()), 4)})
+    emit(rec, a.out)
 
 
 def time_shape(name, repeats, out):
@@ -78,21 +137,31 @@ def time_shape(name, repeats, out):
           "bfs_ms_of_reset": round(bfs, 3), "solved": int(m[:, 0].sum()), "mean_isr": round(float(m[:, 1].mean()), 4)}, out)
 
 
-def solve_shape(n, hwd, n_inst, cap, out):
-    h, w, density = hwd
-    grids = np.stack([maps.pad(maps.random_map(h, w, density, 7000 + i)) for i in range(n_inst)])
-    pos = np.empty((n_inst, n, 2), np.int16)
-    goal = np.empty((n_inst, n, 2), np.int16)
-    for i in range(n_inst):
-        pos[i], goal[i] = maps.place_agents(grids[i], n, 7 + i)
-    ex = BatchedExpert(grids, n_inst, n, cap, seed=7)
-    ex.reset(torch.from_numpy(pos), torch.from_numpy(goal))
+def solve_shape(n, hwd, n_inst, cap, a):
+    if hwd == "maze21":
+        grids, label = maps.pad(maps.maze_map(21, 21, 7)), "21x21 maze"
+        pos, goal = make_instances(grids, n_inst, n, 0, None, None)
+    else:
+        h, w, density = hwd
+        label = f"{h}x{w} at {density:.0%}"
+        grids = np.stack([maps.pad(maps.random_map(h, w, density, 7000 + i)) for i in range(n_inst)])
+        pos = np.empty((n_inst, n, 2), np.int16)
+        goal = np.empty((n_inst, n, 2), np.int16)
+        for i in range(n_inst):
+            pos[i], goal[i] = maps.place_agents(grids[i], n, 7 + i)
+        pos, goal = torch.from_numpy(pos), torch.from_numpy(goal)
+    ex = BatchedExpert(grids, n_inst, n, cap, seed=7, **search_kw(a))
+    reset_ms = timed(lambda: ex.reset(pos, goal))
     ex.run(cap)
     m = ex.metrics().cpu().numpy()
     ok = m[:, 0] >= 1
-    emit({"tool": "bench_expert", "what": "solve", "agents": n, "map": f"{h}x{w} at {density:.0%}", "instances": n_inst, "step_cap": cap,
-          "solved": int(ok.sum()), "mean_length_of_solved": round(float(m[ok, 4].mean()), 2) if ok.any() else None,
-          "mean_isr": round(float(m[:, 1].mean()), 4)}, out)
+    rec = {"tool": "bench_expert", "what": "solve", "algo": a.algo, "agents": n, "map": label, "instances": n_inst, "step_cap": cap,
+           "solved": int(ok.sum()), "mean_length_of_solved": round(float(m[ok, 4].mean()), 2) if ok.any() else None,
+           "mean_isr": round(float(m[:, 1].mean()), 4)}
+    if a.algo == "lacam":                             # reset = BFS + search; the first shape's figure includes the code object's load
+        rec.update(search_fields(ex, reset_ms))
+        rec["search_ms_includes"] = "reset (BFS)"
+    emit(rec, a.out)
 
 
 def main():
@@ -101,14 +170,20 @@ def main():
     ap.add_argument("--shapes", nargs="*", default=None, help="time: a subset of " + " ".join(TIME_SHAPES))
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
+    ap.add_argument("--algo", choices=["pibt", "lacam"], default="pibt")
+    ap.add_argument("--max-iters", type=int, default=4096)
+    ap.add_argument("--iters-per-launch", type=int, default=None, help="default: the library's slice")
     a = ap.parse_args()
     _lib.require_gpu()
     if a.what == "time":
         for name in a.shapes or list(TIME_SHAPES):
-            time_shape(name, a.repeats, a.out)
+            if a.algo == "lacam":
+                time_search(name, a)
+            else:
+                time_shape(name, a.repeats, a.out)
     else:
-        for n, hwd, n_inst, cap in SOLVE_SHAPES:
-            solve_shape(n, hwd, n_inst, cap, a.out)
+        for n, hwd, n_inst, cap in SOLVE_SHAPES + MAZE_SHAPES:
+            solve_shape(n, hwd, n_inst, cap, a)
 
 
 if __name__ == "__main__":
