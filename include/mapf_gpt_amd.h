@@ -524,6 +524,17 @@ int mgpt_expert_solve(mgpt_expert *ex, void *stream);
 int mgpt_expert_copy_search(mgpt_expert *ex, int32_t *d_status, int32_t *d_iters, int32_t *d_nodes, int32_t *d_length, void *stream);
 int mgpt_expert_copy_solution(mgpt_expert *ex, int8_t *d_solution_out, void *stream);
 
+/* Corridor swap rule in the generator (the swap technique of Okumura, IJCAI 2023, restated over section 20's
+ * candidates; nothing is taken from the reference's dataset/lacam).  Off by default: without it every call above behaves as it did.
+ *   set_swap:  on = 1 turns the rule on in the plan kernel and in the search's generator (whichever of set_search and set_swap comes
+ *              first), on = 0 turns it off again; any other value is MGPT_ERR_ARG.  Allowed before mgpt_expert_reset, right after it
+ *              (before solve and the first step) and between episodes, i.e. once every instance is done (this call reads the done flags:
+ *              it synchronises the device); MGPT_ERR_STATE in the middle of an episode.  The first on = 1 builds a degree map of the
+ *              grids (timing-hook name expert_cell_degree) that the context keeps.  MGPT_ERR_UNSUPPORTED when the frames with their swap
+ *              agents (2 more bytes of LDS per agent) do not fit.
+ */
+int mgpt_expert_set_swap(mgpt_expert *ex, int on);
+
 /* ------------------------------------------------------------------------------------------
  * Kernel timing hooks (bench.py's live roofline): when enabled, the library brackets every kernel
  * class with hipEvents on the launch stream.  mgpt_prof_read synchronises the device.

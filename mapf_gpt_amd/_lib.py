@@ -120,6 +120,7 @@ SYMBOLS = {
     "mgpt_expert_copy_plan": (_i, [_vp, _vp, _vp]),
     "mgpt_expert_copy_log": (_i, [_vp, _vp, _vp, _vp]),
     "mgpt_expert_set_search": (_i, [_vp, _i, _i, _i]),
+    "mgpt_expert_set_swap": (_i, [_vp, _i]),
     "mgpt_expert_solve": (_i, [_vp, _vp]),
     "mgpt_expert_copy_search": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mgpt_expert_copy_solution": (_i, [_vp, _vp, _vp]),

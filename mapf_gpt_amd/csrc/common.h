@@ -70,6 +70,7 @@ enum ProfId {
     P_DS_HASH, P_DS_INSERT, P_DS_CLASSIFY, P_DS_RESOLVE, P_DS_BALANCE, P_DS_SELECT, P_DS_GATHER,   // dataset builder (dataset_build.hip)
     P_EXPERT_PLAN,                                      // the PIBT expert's plan kernel (expert.hip)
     P_EXPERT_SEARCH,                                    // the LaCAM search kernel, every launch of a solve (expert.hip)
+    P_EXPERT_CELL_DEGREE,                               // the swap rule's degree map, once per context (expert.hip)
     P_COUNT
 };
 

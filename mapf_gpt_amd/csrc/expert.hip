@@ -4,7 +4,8 @@
 // The reference's expert is LaCAM3 under POGEMA, neither of which is in its tree.  What is built here is the configuration generator
 // of such a search, one step at a time, by this project's own spec -- a weaker teacher than LaCAM: nothing
 // guarantees that all agents stand on their goals at once.  A plain depth-first LaCAM search over this generator (DESIGN.md section 21,
-// lacam_search_kernel below) can run in front of the episode: an instance it solves within the step cap replays its solution.
+// lacam_search_kernel below) can run in front of the episode: an instance it solves within the step cap replays its solution.  An
+// opt-in corridor swap rule is the SWAP = true instantiation of both kernels; SWAP = false is the code as it was.
 //
 // One step of one instance:
 //   order      agents by (since desc, id asc), since = steps since the agent last stood on its goal;
@@ -24,6 +25,8 @@
 // map size.  Every write is a plain vector store; no atomics.  The kernel is latency-bound pointer chasing (a chain of dependent
 // loads of a few bytes), not bandwidth- or ALU-bound.
 #include "common.h"
+
+#include <vector>
 
 using namespace mgpt;
 
@@ -46,12 +49,132 @@ __device__ __forceinline__ uint64_t splitmix_z(uint64_t seed, uint64_t step, uin
 // bit 21: a child call is outstanding
 constexpr unsigned kFrameWaiting = 1u << 21;
 
+// ---- the corridor swap rule: an opt-in addition to both generators, the SWAP = true instantiations ----------
+// cell_degree_kernel writes, once per context, the number of free 4-neighbours of every free cell (kDegBlocked on a blocked one), so
+// that a step of a walk needs no neighbour-of-neighbour grid loads.  The walks are wave-uniform serial loops, capped at H * W advances;
+// within a step lanes 1..4 take the four neighbours of v_puller (one deg, one occ_now and one dist load each) and a ballot gives
+// (n, other).  Everything they read was written before the last barrier (occ_now) or by every lane alike (nxt): no new barrier.
+constexpr unsigned kDegBlocked = 0xFFu;
+
+__global__ __launch_bounds__(256) void cell_degree_kernel(const uint8_t *__restrict__ grids, uint8_t *__restrict__ deg, int n_grids, int H, int W)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, cells = (int64_t)H * W;
+    if (i >= (int64_t)n_grids * cells) return;
+    const uint8_t *grid = grids + (i / cells) * cells;
+    const int v = (int)(i % cells), r = v / W, c = v - r * W;
+    unsigned d = kDegBlocked;
+    if (grid[v] == 0)
+        d = (r > 0 && grid[v - W] == 0) + (r + 1 < H && grid[v + W] == 0) + (c > 0 && grid[v - 1] == 0) + (c + 1 < W && grid[v + 1] == 0);
+    deg[i] = (uint8_t)d;
+}
+
+struct SwapView {
+    const uint8_t *deg;                         // [H*W] the degree map of this instance's grid
+    const uint16_t *occ_now;                    // [H*W]
+    const uint16_t *dist;                       // [n_agents][H*W] this instance's distance fields
+    int n_agents, H, W, cells, lane;
+};
+
+__device__ __forceinline__ int cell_step(int k, int W) { return (k == 1) ? -W : (k == 2) ? W : (k == 3) ? -1 : (k == 4) ? 1 : 0; }
+
+__device__ __forceinline__ unsigned swap_D(const SwapView &S, unsigned a, int v) { return S.dist[(size_t)a * S.cells + v]; }
+
+// count(v_pusher, v_puller): n = the free neighbours of v_puller that are neither v_pusher nor a dead end an agent rests in; other = the
+// last of them in action order
+__device__ __forceinline__ int swap_count(const SwapView &S, int vp, int vq, int &other)
+{
+    const int r = vq / S.W, c = vq - r * S.W, k = S.lane;
+    bool open = false;
+    if (k >= 1 && k <= 4) {
+        const int rr = r + ((k == 1) ? -1 : (k == 2 ? 1 : 0)), cc = c + ((k == 3) ? -1 : (k == 4 ? 1 : 0));
+        if (rr >= 0 && rr < S.H && cc >= 0 && cc < S.W) {
+            const int u = rr * S.W + cc;
+            const unsigned dg = S.deg[u];
+            if (dg != kDegBlocked && u != vp) {
+                open = true;
+                if (dg == 1u) {
+                    const unsigned b = S.occ_now[u];
+                    if (b < (unsigned)S.n_agents && swap_D(S, b, u) == 0u) open = false;
+                }
+            }
+        }
+    }
+    const unsigned m = (unsigned)(__ballot(open) & 0x1Eull);
+    other = m ? vq + cell_step(31 - __clz((int)m), S.W) : vq;
+    return __popc(m);
+}
+
+__device__ __forceinline__ bool swap_required(const SwapView &S, unsigned pusher, unsigned puller, int vp, int vq)
+{
+    unsigned dp = swap_D(S, pusher, vp), dq = swap_D(S, pusher, vq);
+    for (int s = 0; s < S.cells && dq < dp; s++) {
+        int other;
+        const int n = swap_count(S, vp, vq, other);
+        if (n >= 2) return false;
+        if (n <= 0) break;
+        vp = vq; vq = other;
+        dp = dq; dq = swap_D(S, pusher, vq);
+    }
+    return swap_D(S, puller, vp) < swap_D(S, puller, vq) && (dp == 0u || dq < dp);
+}
+
+__device__ __forceinline__ bool swap_possible(const SwapView &S, int vp, int vq)
+{
+    const int origin = vp;
+    for (int s = 0; s < S.cells && vq != origin; s++) {
+        int other;
+        const int n = swap_count(S, vp, vq, other);
+        if (n >= 2) return true;
+        if (n <= 0) return false;
+        vp = vq; vq = other;
+    }
+    return false;
+}
+
+// swap_agent(a, C) on the state at the entry of PIBT(a): ca = a's cell, c0 = its best candidate; kNil = none
+__device__ __forceinline__ unsigned swap_agent(const SwapView &S, const int *nxt, unsigned a, int ca, int c0)
+{
+    if (c0 == ca) return kNil;
+    const unsigned j = S.occ_now[c0];
+    if (j < (unsigned)S.n_agents && nxt[j] < 0 && swap_required(S, a, j, ca, c0) && swap_possible(S, c0, ca)) return j;
+    const int r = ca / S.W, c = ca - r * S.W;
+    for (int k = 1; k <= 4; k++) {
+        const int rr = r + ((k == 1) ? -1 : (k == 2 ? 1 : 0)), cc = c + ((k == 3) ? -1 : (k == 4 ? 1 : 0));
+        if (rr < 0 || rr >= S.H || cc < 0 || cc >= S.W) continue;
+        const int u = rr * S.W + cc;
+        if (u == c0 || S.deg[u] == kDegBlocked) continue;
+        const unsigned b = S.occ_now[u];
+        if (b >= (unsigned)S.n_agents) continue;
+        if (swap_required(S, b, a, ca, c0) && swap_possible(S, c0, ca)) return b;
+    }
+    return kNil;
+}
+
+// a frame with a swap agent keeps its candidates in reversed order
+__device__ __forceinline__ unsigned swap_reversed(unsigned packed, unsigned ncand)
+{
+    unsigned out = 0;
+    for (unsigned i = 0; i < ncand; i++) out |= ((packed >> (3u * (ncand - 1u - i))) & 7u) << (3u * i);
+    return out;
+}
+
+// the pull, on the success return of a frame that took its first candidate: the swap agent j, if still undecided, follows into a's cell
+__device__ __forceinline__ void swap_pull(int *nxt, const int *cell, uint16_t *next_occ, unsigned j, int ca, int W)
+{
+    if (j == kNil || nxt[j] >= 0 || next_occ[ca] != kNil) return;
+    const int d = ca - cell[j];
+    const int k = (d == -W) ? 1 : (d == W) ? 2 : (d == -1) ? 3 : 4;
+    nxt[j] = (k << 24) | ca;
+    next_occ[ca] = (uint16_t)j;
+}
+
+template <bool SWAP>
 __global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict__ grids, int n_grids, int n_agents, int H, int W,
                                                        const uint16_t *__restrict__ dist, const int16_t *__restrict__ pos,
                                                        const uint8_t *__restrict__ done, const uint32_t *__restrict__ since,
                                                        uint16_t *occ, int32_t *__restrict__ actions, int16_t *__restrict__ planned,
                                                        int8_t *__restrict__ log, int32_t *__restrict__ len, int max_steps, uint64_t seed,
-                                                       uint64_t t, int64_t inst_offset)
+                                                       uint64_t t, int64_t inst_offset, const uint8_t *__restrict__ degs)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint2 *stack = reinterpret_cast<uint2 *>(smem);                       // [n_agents] frames; the since values while ranking
@@ -59,6 +182,7 @@ __global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict
     int *cell = reinterpret_cast<int *>(stack + n_agents);                // [n_agents] current cell id
     int *nxt = cell + n_agents;                                           // [n_agents] -1 undecided, else (action << 24) | next cell id
     uint16_t *order = reinterpret_cast<uint16_t *>(nxt + n_agents);       // [n_agents] agent ids by priority
+    uint16_t *swp = order + n_agents;                                     // SWAP only: [n_agents] the swap agent of every frame, or NIL
 
     const int inst = blockIdx.x, lane = threadIdx.x;
     const int cells = H * W;
@@ -73,6 +197,8 @@ __global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict
     }
     const uint8_t *grid = grids + (size_t)(inst % n_grids) * cells;
     uint16_t *occ_now = occ + (size_t)inst * 2 * cells, *next_occ = occ_now + cells;
+    SwapView S;
+    if constexpr (SWAP) S = SwapView{degs + (size_t)(inst % n_grids) * cells, occ_now, dist + g0 * (size_t)cells, n_agents, H, W, cells, lane};
 
     for (int a = lane; a < n_agents; a += 64) {
         int c = (int)pos[2 * (g0 + a)] * W + (int)pos[2 * (g0 + a) + 1];
@@ -132,6 +258,11 @@ __global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict
                 for (int j = 0; j < 5; j++) packed |= __shfl(contrib, j, 64);
                 const unsigned ncand = (unsigned)__popcll(__ballot(valid));
                 if (sp >= n_agents) break;                                // (cannot happen: an agent enters at most once per step)
+                if constexpr (SWAP) {                                     // the swap decision, on the state at this moment
+                    const unsigned j = ncand ? swap_agent(S, nxt, (unsigned)a, ca, ca + cell_step((int)(packed & 7u), W)) : kNil;
+                    if (j != kNil) packed = swap_reversed(packed, ncand);
+                    swp[sp] = (uint16_t)j;
+                }
                 stack[sp] = make_uint2((unsigned)a | ((unsigned)push_par << 16), packed | (ncand << 15));
                 sp++;
                 push_a = -1;
@@ -143,7 +274,12 @@ __global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict
             unsigned y = f.y;
             if (y & kFrameWaiting) {                                      // back from PIBT(c, a)
                 y &= ~kFrameWaiting;
-                if (ret) { sp--; continue; }                              // the child found a cell: a keeps its reservation (ret stays true)
+                if (ret) {                                                // the child found a cell: a keeps its reservation (ret stays true)
+                    if constexpr (SWAP)
+                        if (((y >> 18) & 7u) == 1u) swap_pull(nxt, cell, next_occ, swp[sp - 1], cell[a], W);
+                    sp--;
+                    continue;
+                }
             }
             const unsigned ncand = (y >> 15) & 7u;
             unsigned idx = (y >> 18) & 7u;
@@ -169,6 +305,8 @@ __global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict
                     push_par = a;
                 } else {
                     ret = true;                                           // 6.
+                    if constexpr (SWAP)
+                        if (idx == 1u) swap_pull(nxt, cell, next_occ, swp[sp - 1], ca, W);
                     sp--;
                 }
                 break;
@@ -234,8 +372,10 @@ struct SearchArgs {
     int n_grids, n_agents, H, W, max_steps, max_iters, iters_per_launch, node_cap, cons_cap, table_size;
     uint64_t hash_mask, seed;
     int64_t inst_offset;
+    const uint8_t *deg;                         // [n_grids][H*W] the swap rule's degree map (NULL without it)
 };
 
+template <bool SWAP>
 __global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -247,6 +387,7 @@ __global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
     uint32_t *snc = reinterpret_cast<uint32_t *>(goalc + n_agents);       // [n_agents] the node's since
     uint32_t *chain = snc + n_agents;                                     // [n_agents] the constraint chain, root end first
     uint16_t *order = reinterpret_cast<uint16_t *>(chain + n_agents);     // [n_agents] agent ids by priority
+    uint16_t *swp = order + n_agents;                                     // SWAP only: [n_agents] the swap agent of every frame, or NIL
 
     const int inst = blockIdx.x, lane = threadIdx.x;
     int32_t *st = A.state + (size_t)inst * S_WORDS;
@@ -262,6 +403,8 @@ __global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
     int4 *cons = A.cons + (size_t)inst * A.cons_cap;
     int32_t *table = A.table + (size_t)inst * A.table_size;
     const int tmask = A.table_size - 1;
+    SwapView S;
+    if constexpr (SWAP) S = SwapView{A.deg + (size_t)(inst % A.n_grids) * cells, occ_now, A.dist + g0 * (size_t)cells, n_agents, H, W, cells, lane};
 
     int status = 0, iters = st[S_ITERS], nodes = st[S_NODES], ncons = st[S_CONS], open_n = st[S_OPEN], length = 0;
 
@@ -438,6 +581,11 @@ __global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
                     for (int j = 0; j < 5; j++) packed |= __shfl(contrib, j, 64);
                     const unsigned ncand = (unsigned)__popcll(__ballot(valid));
                     if (sp >= n_agents) break;                            // (cannot happen: an agent enters at most once per step)
+                    if constexpr (SWAP) {                                 // the swap decision, on the state at this moment
+                        const unsigned j = ncand ? swap_agent(S, nxt, (unsigned)a, ca, ca + cell_step((int)(packed & 7u), W)) : kNil;
+                        if (j != kNil) packed = swap_reversed(packed, ncand);
+                        swp[sp] = (uint16_t)j;
+                    }
                     stack[sp] = make_uint2((unsigned)a | ((unsigned)push_par << 16), packed | (ncand << 15));
                     sp++;
                     push_a = -1;
@@ -449,7 +597,12 @@ __global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
                 unsigned y = f.y;
                 if (y & kFrameWaiting) {                                  // back from PIBT(c, a)
                     y &= ~kFrameWaiting;
-                    if (ret) { sp--; continue; }
+                    if (ret) {
+                        if constexpr (SWAP)
+                            if (((y >> 18) & 7u) == 1u) swap_pull(nxt, cell, next_occ, swp[sp - 1], cell[a], W);
+                        sp--;
+                        continue;
+                    }
                 }
                 const unsigned ncand = (y >> 15) & 7u;
                 unsigned idx = (y >> 18) & 7u;
@@ -475,6 +628,8 @@ __global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
                         push_par = a;
                     } else {
                         ret = true;
+                        if constexpr (SWAP)
+                            if (idx == 1u) swap_pull(nxt, cell, next_occ, swp[sp - 1], ca, W);
                         sp--;
                     }
                     break;
@@ -589,10 +744,20 @@ struct mgpt_expert {
     int4 *s_node_meta = nullptr, *s_cons = nullptr;
     int8_t *s_sol = nullptr;
     uint8_t *s_skip = nullptr;
+    // the corridor swap rule (mgpt_expert_set_swap): off by default; the degree map is built when it is first turned on
+    bool swap = false;
+    uint8_t *deg = nullptr;                     // [n_grids][H*W]
 };
 
-static size_t expert_lds_bytes(int n_agents) { return (size_t)n_agents * (sizeof(uint2) + 2 * sizeof(int) + sizeof(uint16_t)); }
-static size_t search_lds_bytes(int n_agents) { return (size_t)n_agents * (sizeof(uint2) + 5 * sizeof(int) + sizeof(uint16_t)); }
+// with the swap rule a frame also keeps its swap agent: 2 more bytes per agent
+static size_t expert_lds_bytes(int n_agents, bool swap = false)
+{
+    return (size_t)n_agents * (sizeof(uint2) + 2 * sizeof(int) + sizeof(uint16_t) + (swap ? sizeof(uint16_t) : 0));
+}
+static size_t search_lds_bytes(int n_agents, bool swap = false)
+{
+    return (size_t)n_agents * (sizeof(uint2) + 5 * sizeof(int) + sizeof(uint16_t) + (swap ? sizeof(uint16_t) : 0));
+}
 constexpr int kDefaultItersPerLaunch = 512;     // the slice after which the host looks at the unfinished counter
 
 static void search_free(mgpt_expert *ex)
@@ -656,6 +821,7 @@ extern "C" int mgpt_expert_destroy(mgpt_expert *ex)
 {
     if (!ex) return MGPT_OK;
     (void)hipFree(ex->occ); (void)hipFree(ex->since); (void)hipFree(ex->planned); (void)hipFree(ex->log); (void)hipFree(ex->len);
+    (void)hipFree(ex->deg);
     search_free(ex);
     delete ex;
     return MGPT_OK;
@@ -689,8 +855,8 @@ extern "C" int mgpt_expert_set_search(mgpt_expert *ex, int max_iters, int iters_
     MGPT_REQUIRE(max_iters >= 1 && max_iters <= (1 << 24), MGPT_ERR_ARG, "max_iters=%d: 1 .. 2^24", max_iters);
     MGPT_REQUIRE(iters_per_launch >= 0, MGPT_ERR_ARG, "iters_per_launch=%d: 0 (the default) or a positive count", iters_per_launch);
     MGPT_REQUIRE(hash_bits >= 0 && hash_bits <= 63, MGPT_ERR_ARG, "hash_bits=%d: 0 (the table's own size) .. 63", hash_bits);
-    MGPT_REQUIRE(search_lds_bytes(ex->n_agents) <= 64 * 1024, MGPT_ERR_UNSUPPORTED, "n_agents=%d: the search's node does not fit 64 KB of LDS",
-                 ex->n_agents);
+    MGPT_REQUIRE(search_lds_bytes(ex->n_agents, ex->swap) <= 64 * 1024, MGPT_ERR_UNSUPPORTED,
+                 "n_agents=%d: the search's node does not fit 64 KB of LDS", ex->n_agents);
     search_free(ex);
     ex->max_iters = max_iters;
     ex->iters_per_launch = iters_per_launch > 0 ? iters_per_launch : kDefaultItersPerLaunch;
@@ -721,6 +887,37 @@ extern "C" int mgpt_expert_set_search(mgpt_expert *ex, int max_iters, int iters_
     return MGPT_OK;
 }
 
+extern "C" int mgpt_expert_set_swap(mgpt_expert *ex, int on)
+{
+    MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(on == 0 || on == 1, MGPT_ERR_ARG, "on=%d: 0 or 1", on);
+    if (ex->have_reset && (ex->t > 0 || ex->solved)) {       // an episode has begun: it is over when every instance is done
+        std::vector<uint8_t> done((size_t)ex->n_inst);
+        MGPT_HIP(hipDeviceSynchronize());
+        MGPT_HIP(hipMemcpy(done.data(), ex->done, done.size(), hipMemcpyDeviceToHost));
+        bool running = false;
+        for (uint8_t d : done) running |= d == 0;
+        MGPT_REQUIRE(!running, MGPT_ERR_STATE, "mgpt_expert_set_swap in the middle of an episode (before mgpt_expert_reset or between episodes only)");
+    }
+    if (on) {
+        MGPT_REQUIRE(expert_lds_bytes(ex->n_agents, true) <= 64 * 1024 && (!ex->search || search_lds_bytes(ex->n_agents, true) <= 64 * 1024),
+                     MGPT_ERR_UNSUPPORTED, "n_agents=%d: the frames with their swap agents do not fit 64 KB of LDS", ex->n_agents);
+        if (!ex->deg) {                                      // built once per context: the grids never change
+            const int64_t total = (int64_t)ex->n_grids * ex->H * ex->W;
+            MGPT_HIP(hipMalloc(&ex->deg, (size_t)total));
+            {
+                ProfScope ps(P_EXPERT_CELL_DEGREE, nullptr);
+                hipLaunchKernelGGL(cell_degree_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, nullptr, ex->grids, ex->deg, ex->n_grids,
+                                   ex->H, ex->W);
+                MGPT_LAUNCH_CHECK();
+            }
+            MGPT_HIP(hipStreamSynchronize(nullptr));         // whatever stream the next step runs on finds the map complete
+        }
+    }
+    ex->swap = on != 0;
+    return MGPT_OK;
+}
+
 extern "C" int mgpt_expert_solve(mgpt_expert *ex, void *stream)
 {
     MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
@@ -741,6 +938,7 @@ extern "C" int mgpt_expert_solve(mgpt_expert *ex, void *stream)
     A.iters_per_launch = ex->iters_per_launch; A.node_cap = ex->node_cap; A.cons_cap = ex->cons_cap; A.table_size = ex->table_size;
     A.hash_mask = ex->hash_bits ? ((1ull << ex->hash_bits) - 1ull) : ~0ull;
     A.seed = ex->seed; A.inst_offset = ex->inst_offset;
+    A.deg = ex->swap ? ex->deg : nullptr;
     // every launch that leaves an instance unfinished has run iters_per_launch iterations of it: this many launches always suffice
     const int64_t launches = cdiv64((int64_t)ex->max_iters + 1, ex->iters_per_launch) + 1;
     int32_t unfinished = 1;
@@ -748,7 +946,10 @@ extern "C" int mgpt_expert_solve(mgpt_expert *ex, void *stream)
         MGPT_HIP(hipMemsetAsync(ex->s_unfinished, 0, sizeof(int32_t), s));
         {
             ProfScope ps(P_EXPERT_SEARCH, s);
-            hipLaunchKernelGGL(lacam_search_kernel, dim3(ex->n_inst), dim3(64), search_lds_bytes(ex->n_agents), s, A);
+            if (ex->swap)
+                hipLaunchKernelGGL(lacam_search_kernel<true>, dim3(ex->n_inst), dim3(64), search_lds_bytes(ex->n_agents, true), s, A);
+            else
+                hipLaunchKernelGGL(lacam_search_kernel<false>, dim3(ex->n_inst), dim3(64), search_lds_bytes(ex->n_agents), s, A);
             MGPT_LAUNCH_CHECK();
         }
         MGPT_HIP(hipMemcpyAsync(&unfinished, ex->s_unfinished, sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -798,9 +999,14 @@ extern "C" int mgpt_expert_step(mgpt_expert *ex, int32_t *d_actions, void *strea
     }
     {
         ProfScope ps(P_EXPERT_PLAN, s);
-        hipLaunchKernelGGL(pibt_plan_kernel, dim3(ex->n_inst), dim3(64), expert_lds_bytes(ex->n_agents), s, ex->grids, ex->n_grids, ex->n_agents,
-                           ex->H, ex->W, ex->dist, ex->pos, skip, ex->since, ex->occ, d_actions, ex->planned, ex->log, ex->len, ex->max_steps,
-                           ex->seed, ex->t, ex->inst_offset);
+        if (ex->swap)
+            hipLaunchKernelGGL(pibt_plan_kernel<true>, dim3(ex->n_inst), dim3(64), expert_lds_bytes(ex->n_agents, true), s, ex->grids, ex->n_grids,
+                               ex->n_agents, ex->H, ex->W, ex->dist, ex->pos, skip, ex->since, ex->occ, d_actions, ex->planned, ex->log, ex->len,
+                               ex->max_steps, ex->seed, ex->t, ex->inst_offset, ex->deg);
+        else
+            hipLaunchKernelGGL(pibt_plan_kernel<false>, dim3(ex->n_inst), dim3(64), expert_lds_bytes(ex->n_agents), s, ex->grids, ex->n_grids,
+                               ex->n_agents, ex->H, ex->W, ex->dist, ex->pos, skip, ex->since, ex->occ, d_actions, ex->planned, ex->log, ex->len,
+                               ex->max_steps, ex->seed, ex->t, ex->inst_offset, nullptr);
         MGPT_LAUNCH_CHECK();
     }
     if (ex->search) {

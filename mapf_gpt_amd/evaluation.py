@@ -188,19 +188,19 @@ def _build_algorithm(algo_cfg, max_rows):
 
 
 class PIBTConfig:
-    """Config of the `name: PIBT` algorithm (the device-resident expert, mapf_gpt_amd/expert.py): name, seed, device; unknown keys
-    raise, as for the MAPF-GPT config."""
+    """Config of the `name: PIBT` algorithm (the device-resident expert, mapf_gpt_amd/expert.py): name, seed, device, swap (the
+    corridor swap rule of DESIGN.md section 22, off by default); unknown keys raise, as for the MAPF-GPT config."""
 
-    def __init__(self, name="PIBT", seed=0, device="cuda"):
-        self.name, self.seed, self.device = name, int(seed or 0), device
+    def __init__(self, name="PIBT", seed=0, device="cuda", swap=False):
+        self.name, self.seed, self.device, self.swap = name, int(seed or 0), device, bool(swap)
 
 
 class LaCAMConfig(PIBTConfig):
     """Config of the `name: LaCAM` algorithm: the same expert with a LaCAM search in front of every episode (DESIGN.md section 21);
-    name, seed, device, max_iters."""
+    name, seed, device, max_iters, swap."""
 
-    def __init__(self, name="LaCAM", seed=0, device="cuda", max_iters=4096):
-        super().__init__(name, seed, device)
+    def __init__(self, name="LaCAM", seed=0, device="cuda", max_iters=4096, swap=False):
+        super().__init__(name, seed, device, swap)
         self.max_iters = int(max_iters)
 
 
@@ -262,7 +262,8 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                     if is_pibt:
                         from .expert import BatchedExpert
                         search = dict(search="lacam", max_iters=cfg.max_iters) if isinstance(cfg, LaCAMConfig) else {}
-                        run = BatchedExpert(grids, len(mine), n_agents, max_steps, seed=cfg.seed, device=cfg.device, inst_offset=lo, **search)
+                        run = BatchedExpert(grids, len(mine), n_agents, max_steps, seed=cfg.seed, device=cfg.device, inst_offset=lo,
+                                            swap=cfg.swap, **search)
                     else:
                         run = BatchedRunner(grids, len(mine), n_agents, algo.net, max_episode_steps=max_steps,
                                             seed=int(cfg.seed or 0), do_sample=True, precision=cfg.precision, device=cfg.device,

@@ -12,15 +12,20 @@ stand on their goals at once, and episodes that do not end with CSR = 1 are drop
 
     python -m mapf_gpt_amd.expert --config CONFIG.yaml --maps MAPS.yaml --out DIR      # writes DIR/PIBT.json
     python -m mapf_gpt_amd.expert --algo lacam [--max-iters N] ...                      # writes DIR/LaCAM.json
+    python -m mapf_gpt_amd.expert [--algo lacam] --swap ...                             # the same files, with the corridor swap rule
 
 `search="lacam"` puts a LaCAM search (plain depth-first LaCAM over this PIBT as its configuration generator) in
 front of the episode: reset() solves every instance on the device, an instance solved within the step cap replays its solution, every
 other instance is planned step by step by PIBT as before, so the expert is never worse than PIBT alone.
 
+`swap=True` turns on the corridor swap rule in the generator, both in the episode's plan kernel and inside the
+search: two agents that meet head-on in a corridor walk together to the nearest junction and exchange there.  Off by default; with it
+off every result is bit for bit what it was.
+
 The config is an evaluation YAML (eval_configs/<folder>/<folder>.yaml): its `environment:` block is run; its `algorithms:` block is
 replaced by one PIBT entry (seed from --seed).  DIR/PIBT.json is what `dataset_build.split_by_map` and `dataset_build --logs` take
 where the reference has LaCAM.json.  Prints one JSON line: episodes, solved, rows, seconds (with --algo lacam also `status`: the
-count of instances per search status).
+count of instances per search status; with --swap also `"swap": true`).
 """
 import argparse
 import ctypes
@@ -40,7 +45,7 @@ class BatchedExpert:
     """Same shape as BatchedRunner: owns a BatchedEnv and a BatchedTokenizer (used for its BFS distance fields only)."""
 
     def __init__(self, grids, n_inst, n_agents, max_episode_steps, seed=0, device="cuda", inst_offset=0, search=None, max_iters=4096,
-                 iters_per_launch=None, hash_bits=0):
+                 iters_per_launch=None, hash_bits=0, swap=False):
         if search not in (None, "lacam"):
             raise ValueError(f"search={search!r}: None or 'lacam'")
         self.device = torch.device(device)
@@ -58,6 +63,15 @@ class BatchedExpert:
         if search:           # iters_per_launch None = the library's default slice; hash_bits 0 = the table's own size (tests cut it short)
             with _lib.on_device(self.device):
                 _lib.check(_lib.lib().mgpt_expert_set_search(self._h, self.max_iters, int(iters_per_launch or 0), int(hash_bits)))
+        self.swap = False
+        if swap:
+            self.set_swap(True)
+
+    def set_swap(self, on):
+        """Turn the corridor swap rule on or off: before reset() or between episodes (MGPTError with ERR_STATE in the middle of one)."""
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_set_swap(self._h, 1 if on else 0))
+        self.swap = bool(on)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -151,6 +165,7 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--algo", choices=["pibt", "lacam"], default="pibt", help="lacam: a LaCAM search in front of every episode")
     ap.add_argument("--max-iters", type=int, default=4096, help="--algo lacam: iterations of the search per instance")
+    ap.add_argument("--swap", action="store_true", help="the corridor swap rule in the generator (episode and search)")
     a = ap.parse_args(argv)
     from . import evaluation as ev
     cfg = ev.load_yaml(a.config)
@@ -160,6 +175,8 @@ def main(argv=None):
     algo = {"name": "PIBT", "seed": a.seed, "device": a.device}
     if a.algo == "lacam":
         algo = {"name": "LaCAM", "seed": a.seed, "device": a.device, "max_iters": a.max_iters}
+    if a.swap:
+        algo["swap"] = True
     cfg = {"environment": cfg["environment"], "algorithms": {algo["name"]: algo}}
     status = {}
     t0 = time.perf_counter()
@@ -169,6 +186,8 @@ def main(argv=None):
     line = {"episodes": len(res), "solved": len(solved), "rows": rows, "seconds": round(time.perf_counter() - t0, 3)}
     if a.algo == "lacam":
         line["status"] = {str(k): int(v) for k, v in sorted(status.items())}
+    if a.swap:
+        line["swap"] = True
     print(json.dumps(line))
     return 0
 

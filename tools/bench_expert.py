@@ -14,6 +14,9 @@
                    status, the search's time per instance and its iterations; time adds the solve (HIP events around it, and the search
                    kernel's own time from the timing hooks), iterations per second and microseconds per iteration.
 
+    --swap         the corridor swap rule in the generator, with either --algo; every record then carries
+                   "swap": true, and time (pibt) adds the degree map's own time from the timing hooks.
+
 Prints one JSON line per shape; --out FILE appends them there too.  Needs the GPU: there is no CPU path.
 """
 import argparse
@@ -37,7 +40,12 @@ SOLVE_SHAPES = [(4, (8, 8, 0.0), 32, 64), (8, (12, 12, 0.2), 32, 64), (32, (21, 
 MAZE_SHAPES = [(16, "maze21", 256, 128), (24, "maze21", 256, 128), (32, "maze21", 256, 128)]
 
 
+SWAP = False                                         # --swap: every expert is built with the rule, every record says so
+
+
 def emit(rec, out):
+    if SWAP:
+        rec = dict(rec, swap=True)
     line = json.dumps(rec)
     print(line, flush=True)
     if out:
@@ -81,7 +89,7 @@ def time_search(name, a):
     else:
         grid, s_ok, g_ok = maps.load_named(map_name)
     pos, goal = make_instances(grid, n_inst, n, 0, s_ok, g_ok)
-    ex = BatchedExpert(grid, n_inst, n, steps, seed=7, **search_kw(a))
+    ex = BatchedExpert(grid, n_inst, n, steps, seed=7, swap=SWAP, **search_kw(a))
     h = ex._h
     solve_ms = []
     for rep in range(a.repeats + 1):                 # episode 0 warms up
@@ -113,7 +121,14 @@ def time_shape(name, repeats, out):
     else:
         grid, s_ok, g_ok = maps.load_named(map_name)
     pos, goal = make_instances(grid, n_inst, n, 0, s_ok, g_ok)
-    ex = BatchedExpert(grid, n_inst, n, steps, seed=7)
+    if SWAP:                                         # the degree map is built by the constructor, once
+        _lib.prof_enable(True)
+        _lib.prof_reset()
+    ex = BatchedExpert(grid, n_inst, n, steps, seed=7, swap=SWAP)
+    extra = {}
+    if SWAP:
+        extra["cell_degree_ms"] = round(_lib.prof_read().get("expert_cell_degree", (0.0, 0))[0], 4)
+        _lib.prof_enable(False)
     reset_ms, run_ms = [], []
     for rep in range(repeats + 1):                   # episode 0 warms up (code objects, allocations)
         r = timed(lambda: ex.reset(pos, goal))
@@ -134,7 +149,7 @@ def time_shape(name, repeats, out):
           "ms_per_step": round(s / steps, 4), "ms_run": round(s, 3), "ms_runs": [round(x, 3) for x in run_ms], "ms_reset": round(r, 3),
           "episodes_per_s": round(n_inst / ((r + s) * 1e-3), 1), "plan_ms_per_step": round(plan / steps, 4),
           "env_ms_per_step": round(env / steps, 4), "plan_share_of_plan_plus_env": round(plan / max(plan + env, 1e-9), 3),
-          "bfs_ms_of_reset": round(bfs, 3), "solved": int(m[:, 0].sum()), "mean_isr": round(float(m[:, 1].mean()), 4)}, out)
+          "bfs_ms_of_reset": round(bfs, 3), "solved": int(m[:, 0].sum()), "mean_isr": round(float(m[:, 1].mean()), 4), **extra}, out)
 
 
 def solve_shape(n, hwd, n_inst, cap, a):
@@ -150,7 +165,7 @@ def solve_shape(n, hwd, n_inst, cap, a):
         for i in range(n_inst):
             pos[i], goal[i] = maps.place_agents(grids[i], n, 7 + i)
         pos, goal = torch.from_numpy(pos), torch.from_numpy(goal)
-    ex = BatchedExpert(grids, n_inst, n, cap, seed=7, **search_kw(a))
+    ex = BatchedExpert(grids, n_inst, n, cap, seed=7, swap=SWAP, **search_kw(a))
     reset_ms = timed(lambda: ex.reset(pos, goal))
     ex.run(cap)
     m = ex.metrics().cpu().numpy()
@@ -173,7 +188,10 @@ def main():
     ap.add_argument("--algo", choices=["pibt", "lacam"], default="pibt")
     ap.add_argument("--max-iters", type=int, default=4096)
     ap.add_argument("--iters-per-launch", type=int, default=None, help="default: the library's slice")
+    ap.add_argument("--swap", action="store_true", help="the corridor swap rule in the generator")
     a = ap.parse_args()
+    global SWAP
+    SWAP = a.swap
     _lib.require_gpu()
     if a.what == "time":
         for name in a.shapes or list(TIME_SHAPES):
