@@ -9,21 +9,43 @@ from oracle import oracle as orc
 pytestmark = pytest.mark.gpu
 
 
+# generated maps for the agent counts the kernel claims (one thread per agent, up to 1024, 16 wave partials in the density reduction):
+# name -> (h, w, obstacle density, distinct grids, steps).  A 64 x 64 map at density 0.1 has about 3 600 free cells.
+GENERATED = {"random-64x64": (64, 64, 0.1, 1, 12), "random-64x64-grid-per-instance": (64, 64, 0.1, 2, 12)}
+
+
+def _instances(name, n_agents, n_inst):
+    """-> (grids [n_grids, H, W], pos, goal int16 tensors, steps)."""
+    from mapf_gpt_amd.runner import make_instances
+    if name not in GENERATED:
+        grid, s_ok, g_ok = maps.load_named(name)
+        pos, goal = make_instances(grid, n_inst, n_agents, 0, s_ok, g_ok)
+        return grid[None], pos, goal, 40
+    h, w, density, n_grids, steps = GENERATED[name]
+    grids = np.stack([maps.pad(maps.random_map(h, w, density, 31 + k)) for k in range(n_grids)])
+    assert n_grids in (1, n_inst)
+    placed = [make_instances(grids[i % n_grids], 1, n_agents, i) for i in range(n_inst)]
+    return grids, torch.cat([p for p, _ in placed]), torch.cat([g for _, g in placed]), steps
+
+
 @pytest.mark.parametrize("name,n_agents,n_inst", [("validation-random-seed-000", 32, 6), ("validation-mazes-seed-000", 64, 4),
-                                                  ("puzzle-00", 4, 9), ("wfi_warehouse", 192, 2)])
+                                                  ("puzzle-00", 4, 9), ("wfi_warehouse", 192, 2),
+                                                  ("random-64x64", 1, 2), ("random-64x64", 255, 2), ("random-64x64-grid-per-instance", 256, 2),
+                                                  ("random-64x64", 257, 1), ("random-64x64-grid-per-instance", 1024, 2)])
 def test_env_step_matches_spec_and_invariants(name, n_agents, n_inst):
     from mapf_gpt_amd.env import BatchedEnv
-    from mapf_gpt_amd.runner import make_instances
-    grid, s_ok, g_ok = maps.load_named(name)
-    pos, goal = make_instances(grid, n_inst, n_agents, 0, s_ok, g_ok)
-    env = BatchedEnv(grid, n_inst, n_agents, max_episode_steps=40)
+    from tests.expert_checks import trajectory_metrics
+    grids, pos, goal, steps = _instances(name, n_agents, n_inst)
+    n_grids = len(grids)
+    env = BatchedEnv(grids, n_inst, n_agents, max_episode_steps=steps)
     env.reset(pos, goal)
     p = pos.numpy().astype(np.int32).copy()
     g = goal.numpy().astype(np.int32)
     rng = np.random.Generator(np.random.PCG64(11))
-    dens = [[orc.agents_density(grid, p[i])] for i in range(n_inst)]          # the reset observation's sample
+    dens = [[orc.agents_density(grids[i % n_grids], p[i])] for i in range(n_inst)]          # the reset observation's sample
+    traj = [[p[i].copy()] for i in range(n_inst)]
     was_done = np.zeros(n_inst, bool)
-    for t in range(40):
+    for t in range(steps):
         act = rng.integers(0, 5, (n_inst, n_agents)).astype(np.int32)
         if t % 3 == 0:       # provoke swaps and chains: everybody pushes the same way
             act[:] = rng.integers(1, 5)
@@ -31,6 +53,10 @@ def test_env_step_matches_spec_and_invariants(name, n_agents, n_inst):
         got, _, done = env.sync_state()
         got = got.cpu().numpy().astype(np.int32)
         for i in range(n_inst):
+            grid = grids[i % n_grids]
+            if was_done[i]:                                    # a finished instance ignores its actions
+                assert np.array_equal(got[i], p[i]), f"step {t} instance {i}"
+                continue
             exp, k = orc.env_step(grid, p[i], g[i], act[i])
             assert np.array_equal(got[i], exp), f"step {t} instance {i}"
             # invariants: no vertex conflict, never on an obstacle, no edge swap, moves of at most one cell
@@ -42,16 +68,19 @@ def test_env_step_matches_spec_and_invariants(name, n_agents, n_inst):
                 b = old.get(tuple(exp[a]))
                 if b is not None and b != a:
                     assert tuple(exp[b]) != tuple(p[i][a]), "edge swap"
-            if not was_done[i]:                                # the step that ends the episode still samples
-                dens[i].append(orc.agents_density(grid, exp))
+            dens[i].append(orc.agents_density(grid, exp))      # the step that ends the episode still samples
+            traj[i].append(exp.copy())
             p[i] = exp
         was_done = done.cpu().numpy() != 0
     m = env.metrics().cpu().numpy()
     assert np.allclose(m[:, 5], [np.mean(d) for d in dens], rtol=1e-6, atol=0), "avg_agents_density"
-    assert (m[:, 4] == 40).all() or (env.done.cpu().numpy() == 1).any()
+    assert (m[:, 4] == steps).all() or (env.done.cpu().numpy() == 1).any()
     on = (p == g).all(2)
     assert np.allclose(m[:, 1], on.mean(1))
-    assert (env.done.cpu().numpy() != 0).all()          # truncated (2) or terminated (1) after 40 steps
+    # CSR, ISR, SoC, makespan and ep_length from the whole trajectory (tests/expert_checks.py), not by the kernel's incremental rule
+    want = np.stack([trajectory_metrics(np.stack(traj[i]), g[i]) for i in range(n_inst)])
+    assert np.array_equal(m[:, :5], want.astype(np.float32)), (m[:, :5], want)
+    assert (env.done.cpu().numpy() != 0).all()          # truncated (2) or terminated (1) after the last step
     frozen = env.sync_state()[0].cpu().numpy().copy()   # done instances ignore further actions
     env.step(torch.from_numpy(rng.integers(0, 5, (n_inst, n_agents)).astype(np.int32)).cuda())
     assert np.array_equal(env.sync_state()[0].cpu().numpy(), frozen)

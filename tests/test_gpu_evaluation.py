@@ -85,17 +85,11 @@ def _replay_metrics(grid, pos0, goal, actions, max_steps):
         T = t + 1
         if np.all(pos == g):
             break
-    on = np.array([np.all(p == g, axis=1) for p in traj])              # [T + 1, agents]
-    n = g.shape[0]
-    arrive = np.full(n, T, np.int64)
-    for a in range(n):
-        if on[T, a]:
-            t = T
-            while t > 0 and on[t - 1, a]:
-                t -= 1
-            arrive[a] = t
-    return {"CSR": float(on[T].all()), "ISR": float(on[T].mean()), "SoC": float(arrive.sum()), "makespan": float(arrive.max()),
-            "ep_length": float(T), "avg_agents_density": float(np.mean(dens))}
+    from tests.expert_checks import trajectory_metrics               # the one trajectory computation the expert's tests use too
+    csr, isr, soc, makespan, ep_length = trajectory_metrics(np.stack(traj), g)
+    assert ep_length == T
+    return {"CSR": float(csr), "ISR": float(isr), "SoC": float(soc), "makespan": float(makespan), "ep_length": float(ep_length),
+            "avg_agents_density": float(np.mean(dens))}
 
 
 def _check_harness_against_replay(cfg, tmp_path):
