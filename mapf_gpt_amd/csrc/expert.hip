@@ -5,7 +5,8 @@
 // of such a search, one step at a time, by this project's own spec -- a weaker teacher than LaCAM: nothing
 // guarantees that all agents stand on their goals at once.  A plain depth-first LaCAM search over this generator (DESIGN.md section 21,
 // lacam_search_kernel below) can run in front of the episode: an instance it solves within the step cap replays its solution.  An
-// opt-in corridor swap rule is the SWAP = true instantiation of both kernels; SWAP = false is the code as it was.
+// opt-in corridor swap rule is the SWAP = true instantiation of both kernels.  The generator itself is one
+// device function, pibt_generate, that both kernels call.
 //
 // One step of one instance:
 //   order      agents by (since desc, id asc), since = steps since the agent last stood on its goal;
@@ -48,8 +49,50 @@ __device__ __forceinline__ uint64_t splitmix_z(uint64_t seed, uint64_t step, uin
 // frame word y: sorted candidate actions, 3 bits each, in bits [0, 15); their count in [15, 18); the next one to try in [18, 21);
 // bit 21: a child call is outstanding
 constexpr unsigned kFrameWaiting = 1u << 21;
+constexpr int kFixed = 1 << 28;                 // in nxt[]: the agent's move is set by a constraint of the search (the plan kernel never sets it)
 
-// ---- the corridor swap rule: an opt-in addition to both generators, the SWAP = true instantiations ----------
+// the arrays of one instance in dynamic LDS, [n_agents] each.  each() is the one description of the layout: lds_bytes() sums it
+// and lds_carve() walks it, so the launch's byte count and the kernel's pointers cannot drift apart.
+struct ExpertLds {
+    uint2 *stack = nullptr;                     // PIBT frames
+    int *cell = nullptr;                        // current cell id
+    int *nxt = nullptr;                         // -1 undecided, else fixed | (action << 24) | next cell id
+    int *goalc = nullptr;                       // search only: goal cell id
+    uint32_t *snc = nullptr;                    // the since values (the plan kernel ranks them in the stack's place, before the first frame)
+    uint32_t *chain = nullptr;                  // search only: the constraint chain, root end first
+    uint16_t *order = nullptr;                  // agent ids by priority
+    uint16_t *swp = nullptr;                    // SWAP only: the swap agent of every frame, or NIL
+
+    template <class F>
+    __host__ __device__ constexpr void each(bool swap, bool search, F f)
+    {
+        f(stack, true); f(cell, true); f(nxt, true); f(goalc, search); f(snc, search); f(chain, search); f(order, true); f(swp, swap);
+    }
+};
+
+// per agent: 18 bytes (20 with the swap rule) for the plan kernel, 30 (32) for the search
+constexpr size_t lds_bytes(int n_agents, bool swap, bool search)
+{
+    size_t bytes = 0;
+    ExpertLds().each(swap, search, [&](auto *&arr, bool present) { bytes += present ? (size_t)n_agents * sizeof(*arr) : 0; });
+    return bytes;
+}
+static_assert(lds_bytes(1, false, false) == 18 && lds_bytes(1, true, false) == 20 && lds_bytes(1, false, true) == 30 && lds_bytes(1, true, true) == 32);
+
+// An array the kernel does not have gets the address of the next one and is never used.  The plan kernel has no snc of its own: it
+// ranks the since values in the stack's place, which is dead until the first frame is pushed after the rank's barrier.
+__device__ __forceinline__ ExpertLds lds_carve(char *smem, int n_agents, bool swap, bool search)
+{
+    ExpertLds L;
+    L.each(swap, search, [&](auto *&arr, bool present) {
+        arr = reinterpret_cast<decltype(+arr)>(smem);
+        if (present) smem += (size_t)n_agents * sizeof(*arr);
+    });
+    if (!search) L.snc = reinterpret_cast<uint32_t *>(L.stack);
+    return L;
+}
+
+// ---- the corridor swap rule: an opt-in addition to the generator, the SWAP = true instantiations -------------
 // cell_degree_kernel writes, once per context, the number of free 4-neighbours of every free cell (kDegBlocked on a blocked one), so
 // that a step of a walk needs no neighbour-of-neighbour grid loads.  The walks are wave-uniform serial loops, capped at H * W advances;
 // within a step lanes 1..4 take the four neighbours of v_puller (one deg, one occ_now and one dist load each) and a ballot gives
@@ -68,62 +111,88 @@ __global__ __launch_bounds__(256) void cell_degree_kernel(const uint8_t *__restr
     deg[i] = (uint8_t)d;
 }
 
-struct SwapView {
-    const uint8_t *deg;                         // [H*W] the degree map of this instance's grid
-    const uint16_t *occ_now;                    // [H*W]
+// what the generator and the swap rule see of one instance: its maps, the occupancy workspace and its arrays in LDS
+struct GenView {
+    const uint8_t *grid;                        // [H*W]
+    const uint8_t *deg;                         // [H*W] SWAP only: the degree map of this instance's grid
     const uint16_t *dist;                       // [n_agents][H*W] this instance's distance fields
+    uint16_t *occ_now, *next_occ;               // [H*W] each
+    ExpertLds L;
     int n_agents, H, W, cells, lane;
 };
 
+// env.hip's action numbering: 0 wait, 1 up, 2 down, 3 left, 4 right
 __device__ __forceinline__ int cell_step(int k, int W) { return (k == 1) ? -W : (k == 2) ? W : (k == 3) ? -1 : (k == 4) ? 1 : 0; }
+__device__ __forceinline__ int step_action(int d, int W) { return (d == 0) ? 0 : (d == -W) ? 1 : (d == W) ? 2 : (d == -1) ? 3 : 4; }
 
-__device__ __forceinline__ unsigned swap_D(const SwapView &S, unsigned a, int v) { return S.dist[(size_t)a * S.cells + v]; }
+// u = neighbour k of cell v (k = 0: v itself); false outside the frame.  A flag and not a sentinel value of u: the callers branch on it as
+// they did on their own bounds tests, where a select cost pibt_plan_kernel<true> 1 % on 4096 instances
+__device__ __forceinline__ bool neighbour(int v, int k, int H, int W, int &u)
+{
+    const int r = v / W, c = v - r * W;
+    const int rr = r + ((k == 1) ? -1 : (k == 2 ? 1 : 0)), cc = c + ((k == 3) ? -1 : (k == 4 ? 1 : 0));
+    u = rr * W + cc;
+    return rr >= 0 && rr < H && cc >= 0 && cc < W;
+}
+
+// order[] = the agents by (since desc, id asc), by counting; the caller's barriers stand before and after
+__device__ __forceinline__ void rank_by_since(const uint32_t *snc, uint16_t *order, int n_agents, int lane)
+{
+    for (int a = lane; a < n_agents; a += 64) {
+        const uint32_t s = snc[a];
+        int rank = 0;
+        for (int b = 0; b < n_agents; b++) {
+            const uint32_t sb = snc[b];
+            rank += (sb > s || (sb == s && b < a)) ? 1 : 0;
+        }
+        order[rank] = (uint16_t)a;
+    }
+}
+
+__device__ __forceinline__ unsigned swap_D(const GenView &G, unsigned a, int v) { return G.dist[(size_t)a * G.cells + v]; }
 
 // count(v_pusher, v_puller): n = the free neighbours of v_puller that are neither v_pusher nor a dead end an agent rests in; other = the
 // last of them in action order
-__device__ __forceinline__ int swap_count(const SwapView &S, int vp, int vq, int &other)
+__device__ __forceinline__ int swap_count(const GenView &G, int vp, int vq, int &other)
 {
-    const int r = vq / S.W, c = vq - r * S.W, k = S.lane;
+    const int k = G.lane;
     bool open = false;
-    if (k >= 1 && k <= 4) {
-        const int rr = r + ((k == 1) ? -1 : (k == 2 ? 1 : 0)), cc = c + ((k == 3) ? -1 : (k == 4 ? 1 : 0));
-        if (rr >= 0 && rr < S.H && cc >= 0 && cc < S.W) {
-            const int u = rr * S.W + cc;
-            const unsigned dg = S.deg[u];
-            if (dg != kDegBlocked && u != vp) {
-                open = true;
-                if (dg == 1u) {
-                    const unsigned b = S.occ_now[u];
-                    if (b < (unsigned)S.n_agents && swap_D(S, b, u) == 0u) open = false;
-                }
+    int u;
+    if (k >= 1 && k <= 4 && neighbour(vq, k, G.H, G.W, u)) {
+        const unsigned dg = G.deg[u];
+        if (dg != kDegBlocked && u != vp) {
+            open = true;
+            if (dg == 1u) {
+                const unsigned b = G.occ_now[u];
+                if (b < (unsigned)G.n_agents && swap_D(G, b, u) == 0u) open = false;
             }
         }
     }
     const unsigned m = (unsigned)(__ballot(open) & 0x1Eull);
-    other = m ? vq + cell_step(31 - __clz((int)m), S.W) : vq;
+    other = m ? vq + cell_step(31 - __clz((int)m), G.W) : vq;
     return __popc(m);
 }
 
-__device__ __forceinline__ bool swap_required(const SwapView &S, unsigned pusher, unsigned puller, int vp, int vq)
+__device__ __forceinline__ bool swap_required(const GenView &G, unsigned pusher, unsigned puller, int vp, int vq)
 {
-    unsigned dp = swap_D(S, pusher, vp), dq = swap_D(S, pusher, vq);
-    for (int s = 0; s < S.cells && dq < dp; s++) {
+    unsigned dp = swap_D(G, pusher, vp), dq = swap_D(G, pusher, vq);
+    for (int s = 0; s < G.cells && dq < dp; s++) {
         int other;
-        const int n = swap_count(S, vp, vq, other);
+        const int n = swap_count(G, vp, vq, other);
         if (n >= 2) return false;
         if (n <= 0) break;
         vp = vq; vq = other;
-        dp = dq; dq = swap_D(S, pusher, vq);
+        dp = dq; dq = swap_D(G, pusher, vq);
     }
-    return swap_D(S, puller, vp) < swap_D(S, puller, vq) && (dp == 0u || dq < dp);
+    return swap_D(G, puller, vp) < swap_D(G, puller, vq) && (dp == 0u || dq < dp);
 }
 
-__device__ __forceinline__ bool swap_possible(const SwapView &S, int vp, int vq)
+__device__ __forceinline__ bool swap_possible(const GenView &G, int vp, int vq)
 {
     const int origin = vp;
-    for (int s = 0; s < S.cells && vq != origin; s++) {
+    for (int s = 0; s < G.cells && vq != origin; s++) {
         int other;
-        const int n = swap_count(S, vp, vq, other);
+        const int n = swap_count(G, vp, vq, other);
         if (n >= 2) return true;
         if (n <= 0) return false;
         vp = vq; vq = other;
@@ -132,20 +201,17 @@ __device__ __forceinline__ bool swap_possible(const SwapView &S, int vp, int vq)
 }
 
 // swap_agent(a, C) on the state at the entry of PIBT(a): ca = a's cell, c0 = its best candidate; kNil = none
-__device__ __forceinline__ unsigned swap_agent(const SwapView &S, const int *nxt, unsigned a, int ca, int c0)
+__device__ __forceinline__ unsigned swap_agent(const GenView &G, unsigned a, int ca, int c0)
 {
     if (c0 == ca) return kNil;
-    const unsigned j = S.occ_now[c0];
-    if (j < (unsigned)S.n_agents && nxt[j] < 0 && swap_required(S, a, j, ca, c0) && swap_possible(S, c0, ca)) return j;
-    const int r = ca / S.W, c = ca - r * S.W;
+    const unsigned j = G.occ_now[c0];
+    if (j < (unsigned)G.n_agents && G.L.nxt[j] < 0 && swap_required(G, a, j, ca, c0) && swap_possible(G, c0, ca)) return j;
     for (int k = 1; k <= 4; k++) {
-        const int rr = r + ((k == 1) ? -1 : (k == 2 ? 1 : 0)), cc = c + ((k == 3) ? -1 : (k == 4 ? 1 : 0));
-        if (rr < 0 || rr >= S.H || cc < 0 || cc >= S.W) continue;
-        const int u = rr * S.W + cc;
-        if (u == c0 || S.deg[u] == kDegBlocked) continue;
-        const unsigned b = S.occ_now[u];
-        if (b >= (unsigned)S.n_agents) continue;
-        if (swap_required(S, b, a, ca, c0) && swap_possible(S, c0, ca)) return b;
+        int u;
+        if (!neighbour(ca, k, G.H, G.W, u) || u == c0 || G.deg[u] == kDegBlocked) continue;
+        const unsigned b = G.occ_now[u];
+        if (b >= (unsigned)G.n_agents) continue;
+        if (swap_required(G, b, a, ca, c0) && swap_possible(G, c0, ca)) return b;
     }
     return kNil;
 }
@@ -159,94 +225,47 @@ __device__ __forceinline__ unsigned swap_reversed(unsigned packed, unsigned ncan
 }
 
 // the pull, on the success return of a frame that took its first candidate: the swap agent j, if still undecided, follows into a's cell
-__device__ __forceinline__ void swap_pull(int *nxt, const int *cell, uint16_t *next_occ, unsigned j, int ca, int W)
+__device__ __forceinline__ void swap_pull(const GenView &G, unsigned j, int ca)
 {
-    if (j == kNil || nxt[j] >= 0 || next_occ[ca] != kNil) return;
-    const int d = ca - cell[j];
-    const int k = (d == -W) ? 1 : (d == W) ? 2 : (d == -1) ? 3 : 4;
-    nxt[j] = (k << 24) | ca;
-    next_occ[ca] = (uint16_t)j;
+    if (j == kNil || G.L.nxt[j] >= 0 || G.next_occ[ca] != kNil) return;
+    G.L.nxt[j] = (step_action(ca - G.L.cell[j], G.W) << 24) | ca;
+    G.next_occ[ca] = (uint16_t)j;
 }
 
-template <bool SWAP>
-__global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict__ grids, int n_grids, int n_agents, int H, int W,
-                                                       const uint16_t *__restrict__ dist, const int16_t *__restrict__ pos,
-                                                       const uint8_t *__restrict__ done, const uint32_t *__restrict__ since,
-                                                       uint16_t *occ, int32_t *__restrict__ actions, int16_t *__restrict__ planned,
-                                                       int8_t *__restrict__ log, int32_t *__restrict__ len, int max_steps, uint64_t seed,
-                                                       uint64_t t, int64_t inst_offset, const uint8_t *__restrict__ degs)
+// ---- the generator: PIBT for every undecided agent in priority order, on the state in LDS and the occupancy workspace ----------------
+// The one copy that both kernels call.  It differs between them in the step index of the candidates' random bits (`step`: the
+// episode's step, or the node's depth), the global row of agent 0 (`row0`) and FIXED: the search, whose constraints have decided
+// some agents with kFixed set, fails (returns false) when an agent with no candidate left finds its own cell held by such an agent.
+// FIXED = false never fails.  Every lane runs this identically (uniform branches, identical addresses and values), so it needs no
+// barrier; sp < n_agents is checked where a frame is pushed.
+template <bool SWAP, bool FIXED>
+__device__ __forceinline__ bool pibt_generate(const GenView &G, uint64_t seed, uint64_t step, int64_t row0)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint2 *stack = reinterpret_cast<uint2 *>(smem);                       // [n_agents] frames; the since values while ranking
-    uint32_t *snc = reinterpret_cast<uint32_t *>(smem);
-    int *cell = reinterpret_cast<int *>(stack + n_agents);                // [n_agents] current cell id
-    int *nxt = cell + n_agents;                                           // [n_agents] -1 undecided, else (action << 24) | next cell id
-    uint16_t *order = reinterpret_cast<uint16_t *>(nxt + n_agents);       // [n_agents] agent ids by priority
-    uint16_t *swp = order + n_agents;                                     // SWAP only: [n_agents] the swap agent of every frame, or NIL
-
-    const int inst = blockIdx.x, lane = threadIdx.x;
-    const int cells = H * W;
-    const size_t g0 = (size_t)inst * n_agents;
-    if (done[inst] != 0) {                                                // wave-uniform: a finished instance is not planned
-        for (int a = lane; a < n_agents; a += 64) {
-            actions[g0 + a] = 0;
-            planned[2 * (g0 + a)] = pos[2 * (g0 + a)];
-            planned[2 * (g0 + a) + 1] = pos[2 * (g0 + a) + 1];
-        }
-        return;
-    }
-    const uint8_t *grid = grids + (size_t)(inst % n_grids) * cells;
-    uint16_t *occ_now = occ + (size_t)inst * 2 * cells, *next_occ = occ_now + cells;
-    SwapView S;
-    if constexpr (SWAP) S = SwapView{degs + (size_t)(inst % n_grids) * cells, occ_now, dist + g0 * (size_t)cells, n_agents, H, W, cells, lane};
-
-    for (int a = lane; a < n_agents; a += 64) {
-        int c = (int)pos[2 * (g0 + a)] * W + (int)pos[2 * (g0 + a) + 1];
-        c = min(max(c, 0), cells - 1);                                    // (env states are inside the frame)
-        cell[a] = c;
-        nxt[a] = -1;
-        snc[a] = since[g0 + a];
-        occ_now[c] = (uint16_t)a;
-    }
-    __syncthreads();
-    for (int a = lane; a < n_agents; a += 64) {                           // rank by counting: (since desc, id asc)
-        const uint32_t s = snc[a];
-        int rank = 0;
-        for (int b = 0; b < n_agents; b++) {
-            const uint32_t sb = snc[b];
-            rank += (sb > s || (sb == s && b < a)) ? 1 : 0;
-        }
-        order[rank] = (uint16_t)a;
-    }
-    __syncthreads();                                                      // order[] complete; snc[] is dead, the stack takes its place
-
-    // ---- the serial part: every lane runs it identically (uniform branches, identical addresses and values) ----
+    const int n_agents = G.n_agents, W = G.W, lane = G.lane;
+    uint2 *stack = G.L.stack;
+    int *cell = G.L.cell, *nxt = G.L.nxt;
+    uint16_t *occ_now = G.occ_now, *next_occ = G.next_occ;
     int sp = 0;
     bool ret = false;
     for (int oi = 0; oi < n_agents; oi++) {
-        const int top = order[oi];
+        const int top = G.L.order[oi];
         if (nxt[top] >= 0) continue;
         int push_a = top, push_par = (int)kNil;
         for (;;) {
             if (push_a >= 0) {                                            // enter PIBT(push_a, push_par): form and sort its candidates
                 const int a = push_a, ca = cell[a];
-                const int r = ca / W, c = ca - r * W;
-                const uint64_t z = splitmix_z(seed, t, (uint64_t)((inst_offset + inst) * (int64_t)n_agents + a));
+                const uint64_t z = splitmix_z(seed, step, (uint64_t)(row0 + a));
                 unsigned key = 0xFFFFFFF8u | (unsigned)min(lane, 7);      // dropped candidates sort last (and stay distinct)
                 bool valid = false;
-                if (lane < 5) {
-                    const int dr = (lane == 1) ? -1 : (lane == 2 ? 1 : 0), dc = (lane == 3) ? -1 : (lane == 4 ? 1 : 0);
-                    const int rr = r + dr, cc = c + dc;
-                    if (rr >= 0 && rr < H && cc >= 0 && cc < W) {
-                        const int u = rr * W + cc;
-                        const unsigned d = dist[(g0 + a) * (size_t)cells + u];
-                        if (grid[u] == 0 && d != kUnreach) {
-                            const unsigned who = occ_now[u];
-                            const unsigned o = (who != kNil && who != (unsigned)a) ? 1u : 0u;
-                            const unsigned rk = (unsigned)(z >> (5 * lane)) & 31u;
-                            key = (((d * 2u + o) * 32u + rk) * 8u) + (unsigned)lane;
-                            valid = true;
-                        }
+                int u;
+                if (lane < 5 && neighbour(ca, lane, G.H, W, u)) {
+                    const unsigned d = swap_D(G, (unsigned)a, u);
+                    if (G.grid[u] == 0 && d != kUnreach) {
+                        const unsigned who = occ_now[u];
+                        const unsigned o = (who != kNil && who != (unsigned)a) ? 1u : 0u;
+                        const unsigned rk = (unsigned)(z >> (5 * lane)) & 31u;
+                        key = (((d * 2u + o) * 32u + rk) * 8u) + (unsigned)lane;
+                        valid = true;
                     }
                 }
                 int rank = 0;
@@ -259,9 +278,9 @@ __global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict
                 const unsigned ncand = (unsigned)__popcll(__ballot(valid));
                 if (sp >= n_agents) break;                                // (cannot happen: an agent enters at most once per step)
                 if constexpr (SWAP) {                                     // the swap decision, on the state at this moment
-                    const unsigned j = ncand ? swap_agent(S, nxt, (unsigned)a, ca, ca + cell_step((int)(packed & 7u), W)) : kNil;
+                    const unsigned j = ncand ? swap_agent(G, (unsigned)a, ca, ca + cell_step((int)(packed & 7u), W)) : kNil;
                     if (j != kNil) packed = swap_reversed(packed, ncand);
-                    swp[sp] = (uint16_t)j;
+                    G.L.swp[sp] = (uint16_t)j;
                 }
                 stack[sp] = make_uint2((unsigned)a | ((unsigned)push_par << 16), packed | (ncand << 15));
                 sp++;
@@ -276,7 +295,7 @@ __global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict
                 y &= ~kFrameWaiting;
                 if (ret) {                                                // the child found a cell: a keeps its reservation (ret stays true)
                     if constexpr (SWAP)
-                        if (((y >> 18) & 7u) == 1u) swap_pull(nxt, cell, next_occ, swp[sp - 1], cell[a], W);
+                        if (((y >> 18) & 7u) == 1u) swap_pull(G, G.L.swp[sp - 1], cell[a]);
                     sp--;
                     continue;
                 }
@@ -289,13 +308,13 @@ __global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict
             while (idx < ncand) {
                 const int k = (int)((y >> (3 * idx)) & 7u);
                 idx++;
-                const int u = ca + ((k == 1) ? -W : (k == 2) ? W : (k == 3) ? -1 : (k == 4) ? 1 : 0);   // in the frame: checked at entry
-                if (next_occ[u] != kNil) continue;                        // 1. reserved for the next step
+                const int u = ca + cell_step(k, W);                       // in the frame: checked at entry
+                if (next_occ[u] != kNil) continue;                        // 1. reserved for the next step (by a constraint too)
                 if (u == par_cell) continue;                              // 2. the parent's cell
                 unsigned c = occ_now[u];
                 if (c >= (unsigned)n_agents) c = kNil;
                 const int nc = (c != kNil) ? nxt[c] : -1;
-                if (nc >= 0 && (nc & 0xFFFFFF) == ca) continue;           // 3. a swap with a decided agent
+                if (nc >= 0 && (nc & 0xFFFFFF) == ca) continue;           // 3. a swap with a decided (or fixed) agent
                 nxt[a] = (k << 24) | u;                                   // 4. reserve
                 next_occ[u] = (uint16_t)a;
                 settled = true;
@@ -306,12 +325,17 @@ __global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict
                 } else {
                     ret = true;                                           // 6.
                     if constexpr (SWAP)
-                        if (idx == 1u) swap_pull(nxt, cell, next_occ, swp[sp - 1], ca, W);
+                        if (idx == 1u) swap_pull(G, G.L.swp[sp - 1], ca);
                     sp--;
                 }
                 break;
             }
             if (!settled) {                                               // no candidate left: stay, taking the cell back from the parent
+                if constexpr (FIXED) {
+                    unsigned holder = next_occ[ca];
+                    if (holder >= (unsigned)n_agents) holder = kNil;
+                    if (holder != kNil && nxt[holder] >= 0 && (nxt[holder] & kFixed)) return false;   // a's cell belongs to a fixed agent
+                }
                 nxt[a] = ca;
                 next_occ[ca] = (uint16_t)a;
                 ret = false;
@@ -319,6 +343,48 @@ __global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict
             }
         }
     }
+    return true;
+}
+
+template <bool SWAP>
+__global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict__ grids, int n_grids, int n_agents, int H, int W,
+                                                       const uint16_t *__restrict__ dist, const int16_t *__restrict__ pos,
+                                                       const uint8_t *__restrict__ done, const uint32_t *__restrict__ since,
+                                                       uint16_t *occ, int32_t *__restrict__ actions, int16_t *__restrict__ planned,
+                                                       int8_t *__restrict__ log, int32_t *__restrict__ len, int max_steps, uint64_t seed,
+                                                       uint64_t t, int64_t inst_offset, const uint8_t *__restrict__ degs)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const ExpertLds L = lds_carve(smem, n_agents, SWAP, false);
+    const int inst = blockIdx.x, lane = threadIdx.x;
+    const int cells = H * W;
+    const size_t g0 = (size_t)inst * n_agents;
+    if (done[inst] != 0) {                                                // wave-uniform: a finished instance is not planned
+        for (int a = lane; a < n_agents; a += 64) {
+            actions[g0 + a] = 0;
+            planned[2 * (g0 + a)] = pos[2 * (g0 + a)];
+            planned[2 * (g0 + a) + 1] = pos[2 * (g0 + a) + 1];
+        }
+        return;
+    }
+    uint16_t *occ_now = occ + (size_t)inst * 2 * cells, *next_occ = occ_now + cells;
+    const size_t map0 = (size_t)(inst % n_grids) * cells;
+    const GenView G{grids + map0, SWAP ? degs + map0 : nullptr, dist + g0 * (size_t)cells, occ_now, next_occ, L, n_agents, H, W, cells, lane};
+    const int *cell = L.cell, *nxt = L.nxt;
+
+    for (int a = lane; a < n_agents; a += 64) {
+        int c = (int)pos[2 * (g0 + a)] * W + (int)pos[2 * (g0 + a) + 1];
+        c = min(max(c, 0), cells - 1);                                    // (env states are inside the frame)
+        L.cell[a] = c;
+        L.nxt[a] = -1;
+        L.snc[a] = since[g0 + a];
+        occ_now[c] = (uint16_t)a;
+    }
+    __syncthreads();
+    rank_by_since(L.snc, L.order, n_agents, lane);
+    __syncthreads();                                                      // order[] complete; snc[] is dead, the stack takes its place
+
+    pibt_generate<SWAP, false>(G, seed, t, (inst_offset + inst) * (int64_t)n_agents);
     __syncthreads();
 
     const int tl = len[inst];
@@ -351,8 +417,7 @@ __global__ void pibt_since_kernel(const int16_t *__restrict__ pos, const int16_t
 // (agent, action) constraints applied first.  The node on top of `open` lives in LDS (cells, since, order, decisions with a "fixed"
 // bit); the node store, `open`, the constraint pool (a node's FIFO is a linked list through it) and an open-addressing table of node
 // ids live in HBM per instance.  A launch runs at most iters_per_launch iterations per instance and leaves its state in HBM.  The
-// generator is a copy of pibt_plan_kernel's body with the two additions of the spec, so the plan kernel's code does not change.
-constexpr int kFixed = 1 << 28;                 // in nxt[]: the agent's move is set by a constraint
+// generator is pibt_generate, the function the plan kernel calls, with FIXED = true for the spec's failure exit.
 enum { S_STATUS = 0, S_ITERS, S_NODES, S_CONS, S_OPEN, S_LENGTH, S_WORDS = 8 };
 
 struct SearchArgs {
@@ -380,21 +445,16 @@ __global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int n_agents = A.n_agents, H = A.H, W = A.W;
-    uint2 *stack = reinterpret_cast<uint2 *>(smem);                       // [n_agents] PIBT frames
-    int *cell = reinterpret_cast<int *>(stack + n_agents);                // [n_agents] the node's cell ids
-    int *nxt = cell + n_agents;                                           // [n_agents] -1 undecided, else fixed | (action << 24) | next cell id
-    int *goalc = nxt + n_agents;                                          // [n_agents] goal cell ids
-    uint32_t *snc = reinterpret_cast<uint32_t *>(goalc + n_agents);       // [n_agents] the node's since
-    uint32_t *chain = snc + n_agents;                                     // [n_agents] the constraint chain, root end first
-    uint16_t *order = reinterpret_cast<uint16_t *>(chain + n_agents);     // [n_agents] agent ids by priority
-    uint16_t *swp = order + n_agents;                                     // SWAP only: [n_agents] the swap agent of every frame, or NIL
+    const ExpertLds L = lds_carve(smem, n_agents, SWAP, true);
+    int *cell = L.cell, *nxt = L.nxt, *goalc = L.goalc;
+    uint32_t *snc = L.snc, *chain = L.chain;
+    const uint16_t *order = L.order;
 
     const int inst = blockIdx.x, lane = threadIdx.x;
     int32_t *st = A.state + (size_t)inst * S_WORDS;
     if (st[S_STATUS] != 0) return;                                        // wave-uniform: this instance has its outcome
     const int cells = H * W;
     const size_t g0 = (size_t)inst * n_agents;
-    const uint8_t *grid = A.grids + (size_t)(inst % A.n_grids) * cells;
     uint16_t *occ_now = A.occ + (size_t)inst * 2 * cells, *next_occ = occ_now + cells;
     int32_t *nq = A.node_q + (size_t)inst * A.node_cap * n_agents;
     uint32_t *ns = A.node_since + (size_t)inst * A.node_cap * n_agents;
@@ -403,8 +463,8 @@ __global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
     int4 *cons = A.cons + (size_t)inst * A.cons_cap;
     int32_t *table = A.table + (size_t)inst * A.table_size;
     const int tmask = A.table_size - 1;
-    SwapView S;
-    if constexpr (SWAP) S = SwapView{A.deg + (size_t)(inst % A.n_grids) * cells, occ_now, A.dist + g0 * (size_t)cells, n_agents, H, W, cells, lane};
+    const size_t map0 = (size_t)(inst % A.n_grids) * cells;
+    const GenView G{A.grids + map0, SWAP ? A.deg + map0 : nullptr, A.dist + g0 * (size_t)cells, occ_now, next_occ, L, n_agents, H, W, cells, lane};
 
     int status = 0, iters = st[S_ITERS], nodes = st[S_NODES], ncons = st[S_CONS], open_n = st[S_OPEN], length = 0;
 
@@ -462,15 +522,7 @@ __global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
             }
             at_goal = __ballot(off) == 0ull;
             __syncthreads();
-            for (int a = lane; a < n_agents; a += 64) {                   // rank by counting: (since desc, id asc)
-                const uint32_t s = snc[a];
-                int rank = 0;
-                for (int b = 0; b < n_agents; b++) {
-                    const uint32_t sb = snc[b];
-                    rank += (sb > s || (sb == s && b < a)) ? 1 : 0;
-                }
-                order[rank] = (uint16_t)a;
-            }
+            rank_by_since(snc, L.order, n_agents, lane);
             __syncthreads();
             cur = top;
             depth = nm[top].x;
@@ -484,8 +536,7 @@ __global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
                     const int par = nm[node].y;
                     for (int a = lane; a < n_agents; a += 64) {
                         const int d = nq[(size_t)node * n_agents + a] - nq[(size_t)par * n_agents + a];
-                        const int k = (d == 0) ? 0 : (d == -W) ? 1 : (d == W) ? 2 : (d == -1) ? 3 : 4;
-                        A.sol[(g0 + a) * (size_t)A.max_steps + t] = (int8_t)k;
+                        A.sol[(g0 + a) * (size_t)A.max_steps + t] = (int8_t)step_action(d, W);
                     }
                     node = par;
                 }
@@ -499,17 +550,9 @@ __global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
         const int cd = ce.z;
         int head = ce.w, tail = (ce.w < 0) ? -1 : meta.w;
         if (cd < n_agents) {
-            const int i = order[cd], ci = cell[i];
-            const int r = ci / W, c = ci - r * W;
-            bool valid = false;
-            if (lane < 5) {
-                const int dr = (lane == 1) ? -1 : (lane == 2 ? 1 : 0), dc = (lane == 3) ? -1 : (lane == 4 ? 1 : 0);
-                const int rr = r + dr, cc = c + dc;
-                if (rr >= 0 && rr < H && cc >= 0 && cc < W) {
-                    const int u = rr * W + cc;
-                    valid = grid[u] == 0 && A.dist[(g0 + i) * (size_t)cells + u] != kUnreach;
-                }
-            }
+            const int i = order[cd];
+            int u;
+            const bool valid = lane < 5 && neighbour(cell[i], lane, H, W, u) && G.grid[u] == 0 && swap_D(G, (unsigned)i, u) != kUnreach;
             const unsigned mask = (unsigned)(__ballot(valid) & 31ull);
             for (int k = 0; k < 5; k++) {
                 if (!((mask >> k) & 1u) || ncons >= A.cons_cap) continue; // (the pool holds one root per node and five entries per iteration)
@@ -533,7 +576,7 @@ __global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
         for (int j = 0; j < cd; j++) {
             const int who = (int)(chain[j] & 0xFFFFu), k = (int)(chain[j] >> 16);
             const int ca = cell[who];
-            const int u = ca + ((k == 1) ? -W : (k == 2) ? W : (k == 3) ? -1 : (k == 4) ? 1 : 0);     // in the frame: checked when the constraint was made
+            const int u = ca + cell_step(k, W);                           // in the frame: checked when the constraint was made
             if (next_occ[u] != kNil) { fail = true; break; }
             unsigned c = occ_now[u];
             if (c >= (unsigned)n_agents) c = kNil;
@@ -544,110 +587,7 @@ __global__ __launch_bounds__(64) void lacam_search_kernel(const SearchArgs A)
             nxt[who] = kFixed | (k << 24) | u;
             next_occ[u] = (uint16_t)who;
         }
-        int sp = 0;
-        bool ret = false;
-        for (int oi = 0; oi < n_agents && !fail; oi++) {
-            const int first = order[oi];
-            if (nxt[first] >= 0) continue;
-            int push_a = first, push_par = (int)kNil;
-            for (;;) {
-                if (push_a >= 0) {                                        // enter PIBT(push_a, push_par): form and sort its candidates
-                    const int a = push_a, ca = cell[a];
-                    const int r = ca / W, c = ca - r * W;
-                    const uint64_t z = splitmix_z(A.seed, (uint64_t)depth, (uint64_t)((A.inst_offset + inst) * (int64_t)n_agents + a));
-                    unsigned key = 0xFFFFFFF8u | (unsigned)min(lane, 7);
-                    bool valid = false;
-                    if (lane < 5) {
-                        const int dr = (lane == 1) ? -1 : (lane == 2 ? 1 : 0), dc = (lane == 3) ? -1 : (lane == 4 ? 1 : 0);
-                        const int rr = r + dr, cc = c + dc;
-                        if (rr >= 0 && rr < H && cc >= 0 && cc < W) {
-                            const int u = rr * W + cc;
-                            const unsigned d = A.dist[(g0 + a) * (size_t)cells + u];
-                            if (grid[u] == 0 && d != kUnreach) {
-                                const unsigned who = occ_now[u];
-                                const unsigned o = (who != kNil && who != (unsigned)a) ? 1u : 0u;
-                                const unsigned rk = (unsigned)(z >> (5 * lane)) & 31u;
-                                key = (((d * 2u + o) * 32u + rk) * 8u) + (unsigned)lane;
-                                valid = true;
-                            }
-                        }
-                    }
-                    int rank = 0;
-#pragma unroll
-                    for (int j = 0; j < 5; j++) rank += (__shfl(key, j, 64) < key) ? 1 : 0;
-                    const unsigned contrib = valid ? ((unsigned)lane << (3 * rank)) : 0u;
-                    unsigned packed = 0;
-#pragma unroll
-                    for (int j = 0; j < 5; j++) packed |= __shfl(contrib, j, 64);
-                    const unsigned ncand = (unsigned)__popcll(__ballot(valid));
-                    if (sp >= n_agents) break;                            // (cannot happen: an agent enters at most once per step)
-                    if constexpr (SWAP) {                                 // the swap decision, on the state at this moment
-                        const unsigned j = ncand ? swap_agent(S, nxt, (unsigned)a, ca, ca + cell_step((int)(packed & 7u), W)) : kNil;
-                        if (j != kNil) packed = swap_reversed(packed, ncand);
-                        swp[sp] = (uint16_t)j;
-                    }
-                    stack[sp] = make_uint2((unsigned)a | ((unsigned)push_par << 16), packed | (ncand << 15));
-                    sp++;
-                    push_a = -1;
-                }
-                if (sp == 0) break;
-                const uint2 f = stack[sp - 1];
-                const int a = (int)(f.x & 0xFFFFu);
-                const unsigned par = f.x >> 16;
-                unsigned y = f.y;
-                if (y & kFrameWaiting) {                                  // back from PIBT(c, a)
-                    y &= ~kFrameWaiting;
-                    if (ret) {
-                        if constexpr (SWAP)
-                            if (((y >> 18) & 7u) == 1u) swap_pull(nxt, cell, next_occ, swp[sp - 1], cell[a], W);
-                        sp--;
-                        continue;
-                    }
-                }
-                const unsigned ncand = (y >> 15) & 7u;
-                unsigned idx = (y >> 18) & 7u;
-                const int ca = cell[a];
-                const int par_cell = (par != kNil) ? cell[par] : -1;
-                bool settled = false;
-                while (idx < ncand) {
-                    const int k = (int)((y >> (3 * idx)) & 7u);
-                    idx++;
-                    const int u = ca + ((k == 1) ? -W : (k == 2) ? W : (k == 3) ? -1 : (k == 4) ? 1 : 0);
-                    if (next_occ[u] != kNil) continue;                    // reserved for the next step (by a constraint too)
-                    if (u == par_cell) continue;
-                    unsigned c = occ_now[u];
-                    if (c >= (unsigned)n_agents) c = kNil;
-                    const int nc = (c != kNil) ? nxt[c] : -1;
-                    if (nc >= 0 && (nc & 0xFFFFFF) == ca) continue;       // a swap with a decided (or fixed) agent
-                    nxt[a] = (k << 24) | u;
-                    next_occ[u] = (uint16_t)a;
-                    settled = true;
-                    if (c != kNil && c != (unsigned)a && nc < 0) {
-                        stack[sp - 1].y = (y & ~(7u << 18)) | (idx << 18) | kFrameWaiting;
-                        push_a = (int)c;
-                        push_par = a;
-                    } else {
-                        ret = true;
-                        if constexpr (SWAP)
-                            if (idx == 1u) swap_pull(nxt, cell, next_occ, swp[sp - 1], ca, W);
-                        sp--;
-                    }
-                    break;
-                }
-                if (!settled) {                                           // no candidate left
-                    unsigned holder = next_occ[ca];
-                    if (holder >= (unsigned)n_agents) holder = kNil;
-                    if (holder != kNil && nxt[holder] >= 0 && (nxt[holder] & kFixed)) {   // a's cell belongs to a fixed agent: the generator fails
-                        fail = true;
-                        break;
-                    }
-                    nxt[a] = ca;
-                    next_occ[ca] = (uint16_t)a;
-                    ret = false;
-                    sp--;
-                }
-            }
-        }
+        if (!fail) fail = !pibt_generate<SWAP, true>(G, A.seed, (uint64_t)depth, (A.inst_offset + inst) * (int64_t)n_agents);
         __syncthreads();
         for (int a = lane; a < n_agents; a += 64) {                       // the reservations of this call go back to NIL, whatever its outcome
             const int v = nxt[a];
@@ -749,14 +689,11 @@ struct mgpt_expert {
     uint8_t *deg = nullptr;                     // [n_grids][H*W]
 };
 
-// with the swap rule a frame also keeps its swap agent: 2 more bytes per agent
-static size_t expert_lds_bytes(int n_agents, bool swap = false)
+// launches the SWAP instantiation of a kernel: one wave64 workgroup per instance, its arrays in dynamic LDS
+template <class... P, class... A>
+static void launch_swap(const mgpt_expert *ex, bool search, void (*with)(P...), void (*without)(P...), hipStream_t s, A... args)
 {
-    return (size_t)n_agents * (sizeof(uint2) + 2 * sizeof(int) + sizeof(uint16_t) + (swap ? sizeof(uint16_t) : 0));
-}
-static size_t search_lds_bytes(int n_agents, bool swap = false)
-{
-    return (size_t)n_agents * (sizeof(uint2) + 5 * sizeof(int) + sizeof(uint16_t) + (swap ? sizeof(uint16_t) : 0));
+    hipLaunchKernelGGL(ex->swap ? with : without, dim3(ex->n_inst), dim3(64), lds_bytes(ex->n_agents, ex->swap, search), s, static_cast<P>(args)...);
 }
 constexpr int kDefaultItersPerLaunch = 512;     // the slice after which the host looks at the unfinished counter
 
@@ -794,7 +731,7 @@ extern "C" int mgpt_expert_create(mgpt_expert **out, mgpt_tokenizer *tok, mgpt_e
                  "tokenizer (%d x %d agents, %d x %d, %d grids) and env (%d x %d agents, %d x %d, %d grids) differ in shape", tv.n_inst,
                  tv.n_agents, tv.H, tv.W, tv.n_grids, n_inst, n_agents, H, W, n_grids);
     MGPT_REQUIRE((int64_t)H * W < (1 << 24), MGPT_ERR_UNSUPPORTED, "H*W=%lld cells: a planned cell is kept in 24 bits", (long long)H * W);
-    MGPT_REQUIRE(expert_lds_bytes(n_agents) <= 64 * 1024, MGPT_ERR_UNSUPPORTED, "n_agents=%d: the stack does not fit 64 KB of LDS", n_agents);
+    MGPT_REQUIRE(lds_bytes(n_agents, false, false) <= 64 * 1024, MGPT_ERR_UNSUPPORTED, "n_agents=%d: the stack does not fit 64 KB of LDS", n_agents);
     mgpt_expert *ex = new mgpt_expert();
     ex->tok = tok; ex->env = env; ex->n_inst = n_inst; ex->n_agents = n_agents; ex->H = H; ex->W = W; ex->n_grids = n_grids;
     ex->max_steps = max_steps; ex->seed = seed; ex->inst_offset = inst_offset;
@@ -855,7 +792,7 @@ extern "C" int mgpt_expert_set_search(mgpt_expert *ex, int max_iters, int iters_
     MGPT_REQUIRE(max_iters >= 1 && max_iters <= (1 << 24), MGPT_ERR_ARG, "max_iters=%d: 1 .. 2^24", max_iters);
     MGPT_REQUIRE(iters_per_launch >= 0, MGPT_ERR_ARG, "iters_per_launch=%d: 0 (the default) or a positive count", iters_per_launch);
     MGPT_REQUIRE(hash_bits >= 0 && hash_bits <= 63, MGPT_ERR_ARG, "hash_bits=%d: 0 (the table's own size) .. 63", hash_bits);
-    MGPT_REQUIRE(search_lds_bytes(ex->n_agents, ex->swap) <= 64 * 1024, MGPT_ERR_UNSUPPORTED,
+    MGPT_REQUIRE(lds_bytes(ex->n_agents, ex->swap, true) <= 64 * 1024, MGPT_ERR_UNSUPPORTED,
                  "n_agents=%d: the search's node does not fit 64 KB of LDS", ex->n_agents);
     search_free(ex);
     ex->max_iters = max_iters;
@@ -900,7 +837,7 @@ extern "C" int mgpt_expert_set_swap(mgpt_expert *ex, int on)
         MGPT_REQUIRE(!running, MGPT_ERR_STATE, "mgpt_expert_set_swap in the middle of an episode (before mgpt_expert_reset or between episodes only)");
     }
     if (on) {
-        MGPT_REQUIRE(expert_lds_bytes(ex->n_agents, true) <= 64 * 1024 && (!ex->search || search_lds_bytes(ex->n_agents, true) <= 64 * 1024),
+        MGPT_REQUIRE(lds_bytes(ex->n_agents, true, false) <= 64 * 1024 && (!ex->search || lds_bytes(ex->n_agents, true, true) <= 64 * 1024),
                      MGPT_ERR_UNSUPPORTED, "n_agents=%d: the frames with their swap agents do not fit 64 KB of LDS", ex->n_agents);
         if (!ex->deg) {                                      // built once per context: the grids never change
             const int64_t total = (int64_t)ex->n_grids * ex->H * ex->W;
@@ -946,10 +883,7 @@ extern "C" int mgpt_expert_solve(mgpt_expert *ex, void *stream)
         MGPT_HIP(hipMemsetAsync(ex->s_unfinished, 0, sizeof(int32_t), s));
         {
             ProfScope ps(P_EXPERT_SEARCH, s);
-            if (ex->swap)
-                hipLaunchKernelGGL(lacam_search_kernel<true>, dim3(ex->n_inst), dim3(64), search_lds_bytes(ex->n_agents, true), s, A);
-            else
-                hipLaunchKernelGGL(lacam_search_kernel<false>, dim3(ex->n_inst), dim3(64), search_lds_bytes(ex->n_agents), s, A);
+            launch_swap(ex, true, lacam_search_kernel<true>, lacam_search_kernel<false>, s, A);
             MGPT_LAUNCH_CHECK();
         }
         MGPT_HIP(hipMemcpyAsync(&unfinished, ex->s_unfinished, sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -999,14 +933,9 @@ extern "C" int mgpt_expert_step(mgpt_expert *ex, int32_t *d_actions, void *strea
     }
     {
         ProfScope ps(P_EXPERT_PLAN, s);
-        if (ex->swap)
-            hipLaunchKernelGGL(pibt_plan_kernel<true>, dim3(ex->n_inst), dim3(64), expert_lds_bytes(ex->n_agents, true), s, ex->grids, ex->n_grids,
-                               ex->n_agents, ex->H, ex->W, ex->dist, ex->pos, skip, ex->since, ex->occ, d_actions, ex->planned, ex->log, ex->len,
-                               ex->max_steps, ex->seed, ex->t, ex->inst_offset, ex->deg);
-        else
-            hipLaunchKernelGGL(pibt_plan_kernel<false>, dim3(ex->n_inst), dim3(64), expert_lds_bytes(ex->n_agents), s, ex->grids, ex->n_grids,
-                               ex->n_agents, ex->H, ex->W, ex->dist, ex->pos, skip, ex->since, ex->occ, d_actions, ex->planned, ex->log, ex->len,
-                               ex->max_steps, ex->seed, ex->t, ex->inst_offset, nullptr);
+        launch_swap(ex, false, pibt_plan_kernel<true>, pibt_plan_kernel<false>, s, ex->grids, ex->n_grids, ex->n_agents, ex->H, ex->W, ex->dist, ex->pos,
+                    skip, ex->since, ex->occ, d_actions, ex->planned, ex->log, ex->len, ex->max_steps, ex->seed, ex->t, ex->inst_offset,
+                    ex->swap ? ex->deg : nullptr);
         MGPT_LAUNCH_CHECK();
     }
     if (ex->search) {

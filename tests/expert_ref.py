@@ -49,61 +49,96 @@ def priority_order(since):
     return sorted(range(len(since)), key=lambda a: (-int(since[a]), a))
 
 
-def plan(grid, pos, dist, since, seed, t, row0):
-    """One PIBT step of one instance.  pos [n][2], dist [n][H][W], since [n]; row0 = global row of agent 0.
-    -> (next cells [n] of (r, c), actions [n], deepest stack reached)."""
-    n = len(pos)
+def candidates(grid, pos, dist, occ_now, seed, t, row0, a):
+    """Agent a's candidates (key, action, cell) by ascending key."""
     H, W = grid.shape
-    pos = [(int(p[0]), int(p[1])) for p in pos]
-    occ_now = {p: a for a, p in enumerate(pos)}
+    z = splitmix_z(seed, t, row0 + a)
+    out = []
+    for k, (dr, dc) in enumerate(MOVES):
+        u = (pos[a][0] + dr, pos[a][1] + dc)
+        if not (0 <= u[0] < H and 0 <= u[1] < W) or grid[u] != 0:
+            continue
+        d = int(dist[a][u])
+        if d == UNREACHED:
+            continue
+        o = 1 if (u in occ_now and occ_now[u] != a) else 0
+        r = (z >> (5 * k)) & 31
+        out.append(((((d * 2 + o) * 32 + r) * 8 + k), k, u))
+    return sorted(out)
+
+
+class _Fail(Exception):
+    pass
+
+
+def gen(grid, Q, dist, since, order, chain, seed, t, row0, rule=None):
+    """The configuration generator: section 20's step on the cells Q, agents taken in `order`, with the (agent, action) constraints
+    of `chain` applied first (section 21).  `rule`, if given, is called with the state (grid, Q, dist, occ_now, nxt, act, next_occ)
+    and returns section 22's rule on it: an object with order(a, C) and pull(a, j, first) (tests/expert_swap_ref.py).
+    -> (next cells, actions, deepest stack reached), or None when the generator fails (with a chain only)."""
+    n = len(Q)
+    Q = [(int(p[0]), int(p[1])) for p in Q]
+    occ_now = {p: a for a, p in enumerate(Q)}
     next_occ = {}
-    nxt = [None] * n
-    act = [0] * n
+    nxt, act, fixed = [None] * n, [0] * n, [False] * n
+    rule = rule(grid, Q, dist, occ_now, nxt, act, next_occ) if rule is not None else None
     depth = [0, 0]
 
-    def candidates(a):
-        z = splitmix_z(seed, t, row0 + a)
-        out = []
-        for k, (dr, dc) in enumerate(MOVES):
-            u = (pos[a][0] + dr, pos[a][1] + dc)
-            if not (0 <= u[0] < H and 0 <= u[1] < W) or grid[u] != 0:
-                continue
-            d = int(dist[a][u])
-            if d == UNREACHED:
-                continue
-            o = 1 if (u in occ_now and occ_now[u] != a) else 0
-            r = (z >> (5 * k)) & 31
-            out.append(((((d * 2 + o) * 32 + r) * 8 + k), k, u))
-        return sorted(out)
+    for a, k in chain:
+        u = (Q[a][0] + MOVES[k][0], Q[a][1] + MOVES[k][1])
+        if u in next_occ:
+            return None
+        c = occ_now.get(u)
+        if c is not None and c != a and nxt[c] is not None and nxt[c] == Q[a]:
+            return None
+        nxt[a], act[a], fixed[a] = u, k, True
+        next_occ[u] = a
 
     def pibt(a, parent):
         depth[0] += 1
         depth[1] = max(depth[1], depth[0])
         try:
-            for _, k, u in candidates(a):
+            C, j = candidates(grid, Q, dist, occ_now, seed, t, row0, a), None
+            if rule is not None:
+                C, j = rule.order(a, C)
+            for i, (_, k, u) in enumerate(C):
                 if u in next_occ:
                     continue
-                if parent is not None and u == pos[parent]:
+                if parent is not None and u == Q[parent]:
                     continue
                 c = occ_now.get(u)
-                if c is not None and nxt[c] is not None and nxt[c] == pos[a]:
+                if c is not None and nxt[c] is not None and nxt[c] == Q[a]:
                     continue
                 nxt[a], act[a] = u, k
                 next_occ[u] = a
                 if c is not None and c != a and nxt[c] is None:
                     if not pibt(c, a):
                         continue
+                if rule is not None:
+                    rule.pull(a, j, i == 0)
                 return True
-            nxt[a], act[a] = pos[a], 0
-            next_occ[pos[a]] = a
+            holder = next_occ.get(Q[a])
+            if holder is not None and fixed[holder]:
+                raise _Fail()
+            nxt[a], act[a] = Q[a], 0
+            next_occ[Q[a]] = a
             return False
         finally:
             depth[0] -= 1
 
-    for a in priority_order(since):
-        if nxt[a] is None:
-            pibt(a, None)
+    try:
+        for a in order:
+            if nxt[a] is None:
+                pibt(a, None)
+    except _Fail:
+        return None
     return nxt, act, depth[1]
+
+
+def plan(grid, pos, dist, since, seed, t, row0):
+    """One PIBT step of one instance.  pos [n][2], dist [n][H][W], since [n]; row0 = global row of agent 0.
+    -> (next cells [n] of (r, c), actions [n], deepest stack reached)."""
+    return gen(grid, pos, dist, since, priority_order(since), (), seed, t, row0)
 
 
 def env_step(grid, pos, actions):
@@ -145,6 +180,8 @@ def density_sample(grid, pos, radius=DENSITY_RADIUS):
 
 
 class RefExpert:
+    rule = None                                                   # section 22's rule, as gen() takes it (tests/expert_swap_ref.py sets it)
+
     def __init__(self, grids, n_inst, n_agents, max_episode_steps, seed=0, inst_offset=0):
         grids = np.asarray(grids)
         if grids.ndim == 2:
@@ -170,6 +207,14 @@ class RefExpert:
         self.made = [[[] for _ in range(n)] for _ in range(n_inst)]
         self.max_depth = 0
 
+    def plan_instance(self, i):
+        """The step of instance i: -> (next cells, actions)."""
+        since = self.since[i]
+        nxt, act, depth = gen(self.grid(i), self.pos[i], self.dist[i], since, priority_order(since), (), self.seed, self.t,
+                              (self.inst_offset + i) * self.n_agents, self.rule)
+        self.max_depth = max(self.max_depth, depth)
+        return nxt, act
+
     def step(self):
         n_inst, n = self.n_inst, self.n_agents
         actions = np.zeros((n_inst, n), np.int32)
@@ -178,9 +223,7 @@ class RefExpert:
             if self.done[i]:
                 continue
             grid = self.grid(i)
-            nxt, act, depth = plan(grid, self.pos[i], self.dist[i], self.since[i], self.seed, self.t,
-                                   (self.inst_offset + i) * n)
-            self.max_depth = max(self.max_depth, depth)
+            nxt, act = self.plan_instance(i)
             actions[i], planned[i] = act, np.asarray(nxt, np.int16)
             for a in range(n):
                 self.made[i][a].append(int(act[a]))

@@ -41,75 +41,15 @@ class Node:
         self.fifo = deque([Constraint()])
 
 
-def gen(grid, Q, dist, since, order, chain, seed, t, row0):
+def gen(grid, Q, dist, since, order, chain, seed, t, row0, rule=None):
     """Section 20's step on (Q, since) with the constraints of `chain` applied first.  -> (next cells, actions) or None on failure."""
-    n = len(Q)
-    H, W = grid.shape
-    occ_now = {p: a for a, p in enumerate(Q)}
-    next_occ = {}
-    nxt, act, fixed = [None] * n, [0] * n, [False] * n
-
-    class Fail(Exception):
-        pass
-
-    for a, k in chain:
-        u = (Q[a][0] + er.MOVES[k][0], Q[a][1] + er.MOVES[k][1])
-        if u in next_occ:
-            return None
-        c = occ_now.get(u)
-        if c is not None and c != a and nxt[c] is not None and nxt[c] == Q[a]:
-            return None
-        nxt[a], act[a], fixed[a] = u, k, True
-        next_occ[u] = a
-
-    def candidates(a):
-        z = er.splitmix_z(seed, t, row0 + a)
-        out = []
-        for k, (dr, dc) in enumerate(er.MOVES):
-            u = (Q[a][0] + dr, Q[a][1] + dc)
-            if not (0 <= u[0] < H and 0 <= u[1] < W) or grid[u] != 0:
-                continue
-            d = int(dist[a][u])
-            if d == er.UNREACHED:
-                continue
-            o = 1 if (u in occ_now and occ_now[u] != a) else 0
-            out.append(((((d * 2 + o) * 32 + ((z >> (5 * k)) & 31)) * 8 + k), k, u))
-        return sorted(out)
-
-    def pibt(a, parent):
-        for _, k, u in candidates(a):
-            if u in next_occ:
-                continue
-            if parent is not None and u == Q[parent]:
-                continue
-            c = occ_now.get(u)
-            if c is not None and nxt[c] is not None and nxt[c] == Q[a]:
-                continue
-            nxt[a], act[a] = u, k
-            next_occ[u] = a
-            if c is not None and c != a and nxt[c] is None:
-                if not pibt(c, a):
-                    continue
-            return True
-        holder = next_occ.get(Q[a])
-        if holder is not None and fixed[holder]:
-            raise Fail()
-        nxt[a], act[a] = Q[a], 0
-        next_occ[Q[a]] = a
-        return False
-
-    try:
-        for a in order:
-            if nxt[a] is None:
-                pibt(a, None)
-    except Fail:
-        return None
-    return nxt, act
+    out = er.gen(grid, Q, dist, since, order, chain, seed, t, row0, rule)
+    return None if out is None else out[:2]
 
 
-def search(grid, pos, goal, dist, seed, row0, max_iters, max_steps):
-    """Depth-first LaCAM of one instance.  -> dict(status, iters, nodes, length, solution): solution int8 [n][length] for status 1
-    and 4, None otherwise; length 0 unless solved."""
+def search(grid, pos, goal, dist, seed, row0, max_iters, max_steps, rule=None):
+    """Depth-first LaCAM of one instance over gen(..., rule).  -> dict(status, iters, nodes, length, solution): solution int8
+    [n][length] for status 1 and 4, None otherwise; length 0 unless solved."""
     n = len(pos)
     H, W = grid.shape
     goal = [(int(g[0]), int(g[1])) for g in goal]
@@ -132,7 +72,7 @@ def search(grid, pos, goal, dist, seed, row0, max_iters, max_steps):
                 u = (N.Q[i][0] + dr, N.Q[i][1] + dc)
                 if 0 <= u[0] < H and 0 <= u[1] < W and grid[u] == 0 and int(dist[i][u]) != er.UNREACHED:
                     N.fifo.append(Constraint(C, i, k))
-        out = gen(grid, N.Q, dist, N.since, N.order, C.chain(), seed, N.depth, row0)
+        out = gen(grid, N.Q, dist, N.since, N.order, C.chain(), seed, N.depth, row0, rule)
         if out is None:
             continue
         Q2 = out[0]
@@ -169,7 +109,7 @@ class RefSearchExpert(er.RefExpert):
         super().reset(pos, goal)
         n = self.n_agents
         self.found = [search(self.grid(i), self.pos[i], self.goal[i], self.dist[i], self.seed, (self.inst_offset + i) * n,
-                             self.max_iters, self.max_steps) for i in range(self.n_inst)]
+                             self.max_iters, self.max_steps, self.rule) for i in range(self.n_inst)]
 
     def stats(self):
         """-> status, iterations, nodes, length: int32 [inst] each."""
@@ -183,36 +123,13 @@ class RefSearchExpert(er.RefExpert):
                 out[i, :, :f["length"]] = f["solution"]
         return out
 
-    def step(self):
-        n_inst, n = self.n_inst, self.n_agents
-        actions = np.zeros((n_inst, n), np.int32)
-        planned = self.pos.astype(np.int16).copy()
-        for i in range(n_inst):
-            if self.done[i]:
-                continue
-            grid, f = self.grid(i), self.found[i]
-            if f["status"] == SOLVED:
-                t = int(self.tcount[i])
-                act = [int(f["solution"][a, t]) if t < f["length"] else 0 for a in range(n)]
-                nxt = [(int(self.pos[i, a, 0]) + er.MOVES[act[a]][0], int(self.pos[i, a, 1]) + er.MOVES[act[a]][1]) for a in range(n)]
-            else:
-                nxt, act, _ = er.plan(grid, self.pos[i], self.dist[i], self.since[i], self.seed, self.t, (self.inst_offset + i) * n)
-            actions[i], planned[i] = act, np.asarray(nxt, np.int16)
-            for a in range(n):
-                self.made[i][a].append(int(act[a]))
-            was_on = (self.pos[i] == self.goal[i]).all(-1)
-            self.pos[i] = np.asarray(er.env_step(grid, self.pos[i], act), np.int64)
-            self.tcount[i] += 1
-            on = (self.pos[i] == self.goal[i]).all(-1)
-            self.arrive[i] = np.where(on, np.where(was_on, self.arrive[i], self.tcount[i]), -1)
-            self.dens[i].append(er.density_sample(grid, self.pos[i]))
-            self.since[i] = np.where(on, 0, self.since[i] + 1)
-            if on.all():
-                self.done[i] = 1
-            elif self.tcount[i] >= self.max_steps:
-                self.done[i] = 2
-        self.t += 1
-        return actions, planned
+    def plan_instance(self, i):
+        f = self.found[i]
+        if f["status"] != SOLVED:
+            return super().plan_instance(i)
+        t = int(self.tcount[i])
+        act = [int(f["solution"][a, t]) if t < f["length"] else 0 for a in range(self.n_agents)]
+        return [(int(p[0]) + er.MOVES[k][0], int(p[1]) + er.MOVES[k][1]) for p, k in zip(self.pos[i], act)], act
 
 
 # ---- the shapes both test files use -------------------------------------------------------------------------------------------

@@ -1,14 +1,17 @@
 """Plain Python restatement of the corridor swap rule on top of tests/expert_ref.py (section 20) and
-tests/expert_search_ref.py (section 21), both imported unchanged -- TEST INFRASTRUCTURE ONLY, written from the spec, not from the kernels.
+tests/expert_search_ref.py (section 21) -- TEST INFRASTRUCTURE ONLY, written from the spec, not from the kernels.
 
     nxt, act, depth = plan(grid, pos, dist, since, seed, t, row0, swap=True)
     out = gen(grid, Q, dist, since, order, chain, seed, t, row0, swap=True)
     out = search(grid, pos, goal, dist, seed, row0, max_iters, max_steps, swap=True)
     ref = RefSwapExpert(...); ref = RefSwapSearchExpert(...)          # RefExpert / RefSearchExpert with swap=True by default
 
-With swap=False every function calls the existing one.  `cap` (test-only) replaces the walk cap H * W.  `trace`, a dict, counts the
-branches a call went through, so that a test can tell that a hand case reaches the branch it was drawn for.
+Every function here is the one of those two files with Rule handed to the generator (swap=False: without it).  `cap` (test-only)
+replaces the walk cap H * W.  `trace`, a dict, counts the branches a call went through, so that a test can tell that a hand case
+reaches the branch it was drawn for.
 """
+import functools
+
 import numpy as np
 
 from tests import expert_ref as er
@@ -128,227 +131,44 @@ class Rule:
         self.note("pull")
 
 
-def _candidates(grid, pos, dist, occ_now, seed, t, row0, a):
-    H, W = grid.shape
-    z = er.splitmix_z(seed, t, row0 + a)
-    out = []
-    for k, (dr, dc) in enumerate(er.MOVES):
-        u = (pos[a][0] + dr, pos[a][1] + dc)
-        if not (0 <= u[0] < H and 0 <= u[1] < W) or grid[u] != 0:
-            continue
-        d = int(dist[a][u])
-        if d == er.UNREACHED:
-            continue
-        o = 1 if (u in occ_now and occ_now[u] != a) else 0
-        out.append(((((d * 2 + o) * 32 + ((z >> (5 * k)) & 31)) * 8 + k), k, u))
-    return sorted(out)
+def _rule(swap, cap, trace):
+    """The `rule` argument of expert_ref.gen: Rule on the generator's state, or None with the switch off."""
+    return functools.partial(Rule, cap=cap, trace=trace) if swap else None
 
 
 def plan(grid, pos, dist, since, seed, t, row0, swap=True, cap=None, trace=None):
     """expert_ref.plan with the rule: -> (next cells, actions, deepest stack reached)."""
-    if not swap:
-        return er.plan(grid, pos, dist, since, seed, t, row0)
-    n = len(pos)
-    pos = [(int(p[0]), int(p[1])) for p in pos]
-    occ_now = {p: a for a, p in enumerate(pos)}
-    next_occ = {}
-    nxt, act = [None] * n, [0] * n
-    rule = Rule(grid, pos, dist, occ_now, nxt, act, next_occ, cap, trace)
-    depth = [0, 0]
-
-    def pibt(a, parent):
-        depth[0] += 1
-        depth[1] = max(depth[1], depth[0])
-        try:
-            C, j = rule.order(a, _candidates(grid, pos, dist, occ_now, seed, t, row0, a))
-            for i, (_, k, u) in enumerate(C):
-                if u in next_occ:
-                    continue
-                if parent is not None and u == pos[parent]:
-                    continue
-                c = occ_now.get(u)
-                if c is not None and nxt[c] is not None and nxt[c] == pos[a]:
-                    continue
-                nxt[a], act[a] = u, k
-                next_occ[u] = a
-                if c is not None and c != a and nxt[c] is None:
-                    if not pibt(c, a):
-                        continue
-                rule.pull(a, j, i == 0)
-                return True
-            nxt[a], act[a] = pos[a], 0
-            next_occ[pos[a]] = a
-            return False
-        finally:
-            depth[0] -= 1
-
-    for a in er.priority_order(since):
-        if nxt[a] is None:
-            pibt(a, None)
-    return nxt, act, depth[1]
+    return er.gen(grid, pos, dist, since, er.priority_order(since), (), seed, t, row0, _rule(swap, cap, trace))
 
 
 def gen(grid, Q, dist, since, order, chain, seed, t, row0, swap=True, cap=None, trace=None):
     """expert_search_ref.gen with the rule: -> (next cells, actions) or None on failure."""
-    if not swap:
-        return sr.gen(grid, Q, dist, since, order, chain, seed, t, row0)
-    n = len(Q)
-    Q = [(int(p[0]), int(p[1])) for p in Q]
-    occ_now = {p: a for a, p in enumerate(Q)}
-    next_occ = {}
-    nxt, act, fixed = [None] * n, [0] * n, [False] * n
-    rule = Rule(grid, Q, dist, occ_now, nxt, act, next_occ, cap, trace)
-
-    class Fail(Exception):
-        pass
-
-    for a, k in chain:
-        u = (Q[a][0] + er.MOVES[k][0], Q[a][1] + er.MOVES[k][1])
-        if u in next_occ:
-            return None
-        c = occ_now.get(u)
-        if c is not None and c != a and nxt[c] is not None and nxt[c] == Q[a]:
-            return None
-        nxt[a], act[a], fixed[a] = u, k, True
-        next_occ[u] = a
-
-    def pibt(a, parent):
-        C, j = rule.order(a, _candidates(grid, Q, dist, occ_now, seed, t, row0, a))
-        for i, (_, k, u) in enumerate(C):
-            if u in next_occ:
-                continue
-            if parent is not None and u == Q[parent]:
-                continue
-            c = occ_now.get(u)
-            if c is not None and nxt[c] is not None and nxt[c] == Q[a]:
-                continue
-            nxt[a], act[a] = u, k
-            next_occ[u] = a
-            if c is not None and c != a and nxt[c] is None:
-                if not pibt(c, a):
-                    continue
-            rule.pull(a, j, i == 0)
-            return True
-        holder = next_occ.get(Q[a])
-        if holder is not None and fixed[holder]:
-            raise Fail()
-        nxt[a], act[a] = Q[a], 0
-        next_occ[Q[a]] = a
-        return False
-
-    try:
-        for a in order:
-            if nxt[a] is None:
-                pibt(a, None)
-    except Fail:
-        return None
-    return nxt, act
+    return sr.gen(grid, Q, dist, since, order, chain, seed, t, row0, _rule(swap, cap, trace))
 
 
 def search(grid, pos, goal, dist, seed, row0, max_iters, max_steps, swap=True, cap=None, trace=None):
     """expert_search_ref.search over the generator with the rule (the search itself is section 21's, unchanged)."""
-    if not swap:
-        return sr.search(grid, pos, goal, dist, seed, row0, max_iters, max_steps)
-    n = len(pos)
-    H, W = grid.shape
-    goal = [(int(g[0]), int(g[1])) for g in goal]
-    start = sr.Node([(int(p[0]), int(p[1])) for p in pos], [0] * n, 0, None)
-    open_, explored = [start], {tuple(start.Q): start}
-    iters, nodes, found = 0, 1, None
-    while open_ and iters < max_iters:
-        iters += 1
-        N = open_[-1]
-        if N.Q == goal:
-            found = N
-            break
-        if not N.fifo:
-            open_.pop()
-            continue
-        C = N.fifo.popleft()
-        if C.depth < n:
-            i = N.order[C.depth]
-            for k, (dr, dc) in enumerate(er.MOVES):
-                u = (N.Q[i][0] + dr, N.Q[i][1] + dc)
-                if 0 <= u[0] < H and 0 <= u[1] < W and grid[u] == 0 and int(dist[i][u]) != er.UNREACHED:
-                    N.fifo.append(sr.Constraint(C, i, k))
-        out = gen(grid, N.Q, dist, N.since, N.order, C.chain(), seed, N.depth, row0, True, cap, trace)
-        if out is None:
-            continue
-        Q2 = out[0]
-        if tuple(Q2) in explored:
-            continue
-        M = sr.Node(Q2, [0 if Q2[a] == goal[a] else N.since[a] + 1 for a in range(n)], N.depth + 1, N)
-        explored[tuple(Q2)] = M
-        open_.append(M)
-        nodes += 1
-    if found is None:
-        return dict(status=sr.EXHAUSTED if not open_ else sr.BUDGET, iters=iters, nodes=nodes, length=0, solution=None)
-    path = []
-    while found is not None:
-        path.append(found.Q)
-        found = found.parent
-    path = path[::-1]
-    L = len(path) - 1
-    sol = np.zeros((n, L), np.int8)
-    for t in range(L):
-        for a in range(n):
-            sol[a, t] = er.MOVES.index((path[t + 1][a][0] - path[t][a][0], path[t + 1][a][1] - path[t][a][1]))
-    return dict(status=sr.SOLVED if L <= max_steps else sr.TOO_LONG, iters=iters, nodes=nodes, length=L, solution=sol, path=path)
+    return sr.search(grid, pos, goal, dist, seed, row0, max_iters, max_steps, _rule(swap, cap, trace))
 
 
-class _SwapStep:
-    """step() of both experts: an instance that does not replay a solution is planned by plan(..., swap)."""
+class _Swap:
+    """Both experts with the switch: `rule` is what plan_instance() and the search hand to the generator."""
 
-    def step(self):
-        n_inst, n = self.n_inst, self.n_agents
-        actions = np.zeros((n_inst, n), np.int32)
-        planned = self.pos.astype(np.int16).copy()
-        for i in range(n_inst):
-            if self.done[i]:
-                continue
-            grid, f = self.grid(i), (self.found[i] if hasattr(self, "found") else None)
-            if f is not None and f["status"] == sr.SOLVED:
-                t = int(self.tcount[i])
-                act = [int(f["solution"][a, t]) if t < f["length"] else 0 for a in range(n)]
-                nxt = [(int(self.pos[i, a, 0]) + er.MOVES[act[a]][0], int(self.pos[i, a, 1]) + er.MOVES[act[a]][1]) for a in range(n)]
-            else:
-                nxt, act, depth = plan(grid, self.pos[i], self.dist[i], self.since[i], self.seed, self.t, (self.inst_offset + i) * n,
-                                       self.swap, self.cap, self.trace)
-                self.max_depth = max(self.max_depth, depth)
-            actions[i], planned[i] = act, np.asarray(nxt, np.int16)
-            for a in range(n):
-                self.made[i][a].append(int(act[a]))
-            was_on = (self.pos[i] == self.goal[i]).all(-1)
-            self.pos[i] = np.asarray(er.env_step(grid, self.pos[i], act), np.int64)
-            self.tcount[i] += 1
-            on = (self.pos[i] == self.goal[i]).all(-1)
-            self.arrive[i] = np.where(on, np.where(was_on, self.arrive[i], self.tcount[i]), -1)
-            self.dens[i].append(er.density_sample(grid, self.pos[i]))
-            self.since[i] = np.where(on, 0, self.since[i] + 1)
-            if on.all():
-                self.done[i] = 1
-            elif self.tcount[i] >= self.max_steps:
-                self.done[i] = 2
-        self.t += 1
-        return actions, planned
+    def set_swap(self, swap, cap):
+        self.swap, self.cap, self.trace = bool(swap), cap, {}
+        self.rule = _rule(self.swap, cap, self.trace)
 
 
-class RefSwapExpert(_SwapStep, er.RefExpert):
+class RefSwapExpert(_Swap, er.RefExpert):
     def __init__(self, grids, n_inst, n_agents, max_episode_steps, seed=0, inst_offset=0, swap=True, cap=None):
-        er.RefExpert.__init__(self, grids, n_inst, n_agents, max_episode_steps, seed, inst_offset)
-        self.swap, self.cap, self.trace = bool(swap), cap, {}
+        super().__init__(grids, n_inst, n_agents, max_episode_steps, seed, inst_offset)
+        self.set_swap(swap, cap)
 
 
-class RefSwapSearchExpert(_SwapStep, sr.RefSearchExpert):
+class RefSwapSearchExpert(_Swap, sr.RefSearchExpert):
     def __init__(self, grids, n_inst, n_agents, max_episode_steps, seed=0, inst_offset=0, max_iters=4096, swap=True, cap=None):
-        sr.RefSearchExpert.__init__(self, grids, n_inst, n_agents, max_episode_steps, seed, inst_offset, max_iters)
-        self.swap, self.cap, self.trace = bool(swap), cap, {}
-
-    def reset(self, pos, goal):
-        er.RefExpert.reset(self, pos, goal)
-        n = self.n_agents
-        self.found = [search(self.grid(i), self.pos[i], self.goal[i], self.dist[i], self.seed, (self.inst_offset + i) * n, self.max_iters,
-                             self.max_steps, self.swap, self.cap, self.trace) for i in range(self.n_inst)]
+        super().__init__(grids, n_inst, n_agents, max_episode_steps, seed, inst_offset, max_iters)
+        self.set_swap(swap, cap)
 
 
 def run_case(case, steps=None, swap=True, cap=None):

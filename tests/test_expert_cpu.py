@@ -1,5 +1,7 @@
 """The PIBT expert's spec on the host: invariants of every planned step of the restatement (tests/expert_ref.py), the hand cases, the
 record schema, and the restatement's solved counts on the shapes tests/test_gpu_expert.py compares the device against."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -150,6 +152,43 @@ def test_solved_counts_of_the_gpu_shapes():
         ref = er.run_case(case)
         got[name] = (int(ref.metrics()[:, 0].sum()), case["n_inst"])
     assert got == SOLVED
+
+
+def digest(ref):
+    """sha256 over a finished restatement's log, lengths, final positions, done flags and metrics, and,
+    where it searched, over status, iterations, nodes, length and every solution."""
+    log, lengths = ref.log()
+    parts = [(log, np.int8), (lengths, np.int32), (ref.pos, np.int64), (ref.done, np.uint8), (ref.metrics(), np.float64)]
+    if hasattr(ref, "found"):
+        parts += [(s, np.int32) for s in ref.stats()]
+        parts += [(f["solution"], np.int8) for f in ref.found if f["solution"] is not None]
+    h = hashlib.sha256()
+    for arr, dtype in parts:
+        h.update(np.ascontiguousarray(arr, dtype).tobytes())
+    return h.hexdigest()
+
+
+# The three restatements once held four copies of the generator, two of the search and three of the episode step.  These digests (and
+# those of tests/test_expert_search_cpu.py and tests/test_expert_swap_cpu.py) were computed with that code, on every case and mode,
+# before the copies were folded into expert_ref.gen, expert_search_ref.search and RefExpert.plan_instance: name -> digest(run_case(case))
+DIGESTS = {
+    "agents65": "13278d0db10a4909922173c599b6846bc1937be7af2d917d156f98747c8515e5",
+    "agents70": "f3f8fb4d77b1aa11c57fdf32dc5f5d779e4cc31f692c30693f8ac7ba8c458fee",
+    "dead_end": "e4ad371d0863106482f2143dae3b48cde24b77ecf7dc2603733460c285541c18",
+    "empty32": "a34b4d0cb2818e427999733db95dc61f26fad075903540fbb08710838ca3c20b",
+    "grids3": "bda730317c520112eb9a3b200fc2740b309d3c83a0b5bd962281363293fbeb68",
+    "offset7": "7ff9eb94b377d3862e0fd0dc93947015989b131f7534f9f856d3b472d0299479",
+    "one_agent": "8ea4d162561388b8d808b7ba214d0dd26f03ca388f1d03f047eb30c273cbdcf9",
+    "pocket": "74f400dd2d16e04fc3349ec6ad42f63404151396d68388ba1639d7315038c22f",
+    "rotation": "4d169063e2b52792a2e1bf65a51733510d2951d58bdae06e2612182b9d9159d5",
+    "shared5": "8f580042702ab7131c72494830c6c9c41a55ffae01678a51f3359957ebbf15b1",
+}
+
+
+def test_the_episodes_of_the_gpu_shapes_are_bit_for_bit_what_they_were():
+    cases = er.gpu_cases()
+    assert set(cases) == set(DIGESTS)
+    assert {name: digest(er.run_case(case)) for name, case in cases.items()} == DIGESTS
 
 
 def test_evaluation_refuses_what_the_pibt_branch_does_not_build():

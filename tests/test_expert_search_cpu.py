@@ -7,7 +7,7 @@ import pytest
 
 from tests import expert_ref as er
 from tests import expert_search_ref as sr
-from tests.test_expert_cpu import check_step
+from tests.test_expert_cpu import check_step, digest
 
 CASES = sr.gpu_cases()
 _REFS = {}
@@ -160,3 +160,37 @@ def test_status_iteration_and_node_counts_of_the_gpu_shapes():
         else:
             assert tuple(st) == PINNED[name], (name, st)
         assert int(ref.metrics()[:, 0].sum()) == SOLVED[name], name
+
+
+# digests (tests/test_expert_cpu.py: digest, and where they come from): name -> (PIBT alone, the search in front) on the case
+DIGESTS = {
+    "agents65": ("5d88e9b28816893259aab868c214e8cec1c33ef2a82f95656c00254229f4b118",
+        "e4902bd7954763bb222b83e15a6ce161a7c06faf71a3137be11d71e5756c18a1"),
+    "agents70": ("f3f8fb4d77b1aa11c57fdf32dc5f5d779e4cc31f692c30693f8ac7ba8c458fee",
+        "11dda0a66c69d29ac0512f273ded572adbdb2bc17fbc0fe04cbbab01e327ac89"),
+    "dead_end": ("e4ad371d0863106482f2143dae3b48cde24b77ecf7dc2603733460c285541c18",
+        "5756673cb3da9c279aa637a5f8d1c4fcc2c7f12ee921fb2d6296aa6c67a00881"),
+    "empty32": ("a34b4d0cb2818e427999733db95dc61f26fad075903540fbb08710838ca3c20b",
+        "9460ef711f098416f18bda7a7c2f70412eda5164408814498f279d3dbd4f21bf"),
+    "grids3": ("bda730317c520112eb9a3b200fc2740b309d3c83a0b5bd962281363293fbeb68",
+        "b3d9872a55af0beba99a921aa56b01c08d1aca9d9ec44b3cb6b3f5ecf0f8aa27"),
+    "offset7": ("7ff9eb94b377d3862e0fd0dc93947015989b131f7534f9f856d3b472d0299479",
+        "c19d06c0f685750593b5d4dff45a3b315aa57df67fb0a00dba937906ffab2f02"),
+    "one_agent": ("8ea4d162561388b8d808b7ba214d0dd26f03ca388f1d03f047eb30c273cbdcf9",
+        "88d1f05a50ef80492dc0e61bc8f8fc1983762bd3a920b20df77c276c7e03a4cb"),
+    "pocket": ("74f400dd2d16e04fc3349ec6ad42f63404151396d68388ba1639d7315038c22f",
+        "6edf3eb6adf4b5d4c45550738f0658b1421bc2eb20989f4b089efb713c289e37"),
+    "rotation": ("4d169063e2b52792a2e1bf65a51733510d2951d58bdae06e2612182b9d9159d5",
+        "1b5b8b9ce97303ce362817d284db3f2dbb3af037c70e311c66168b14339f28d4"),
+    "shared5": ("8f580042702ab7131c72494830c6c9c41a55ffae01678a51f3359957ebbf15b1",
+        "1c0012d6aaa967d898dd975356043ab8b9a2cd63fe635a15173d6c3845fad8a5"),
+    "swap2": ("2e17ab82e026b495a91a74709b86217d634165a5281f27bca3a2a2b210e37605",
+        "7c85ed72b36c30fd4ec982e7078746fcaefe518ca6c20711cb3b01ceba6a9ede"),
+    "swap3": ("8b0b2a2a2d497c27a0d38ddfaebe85a6adbe7b0b712759ecdc732daa1c8be9e0",
+        "303c459e2fdaad02d3b0a3624388d883e0a2eaa640c93b91c09c0d5c12e0c97b"),
+}
+
+
+def test_the_episodes_and_searches_of_the_gpu_shapes_are_bit_for_bit_what_they_were():
+    assert set(CASES) == set(DIGESTS)
+    assert {name: (digest(er.run_case(CASES[name])), digest(solved_ref(name))) for name in sorted(CASES)} == DIGESTS

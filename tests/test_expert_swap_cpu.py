@@ -7,7 +7,7 @@ import pytest
 from tests import expert_ref as er
 from tests import expert_search_ref as sr
 from tests import expert_swap_ref as sw
-from tests.test_expert_cpu import check_step
+from tests.test_expert_cpu import check_step, digest
 
 CASES = sw.gpu_cases()
 HAND = sorted(sw.hand_cases())
@@ -163,3 +163,47 @@ def test_with_the_walk_cap_at_one_the_invariants_hold(name):
 def test_the_cap_does_not_bind_on_the_test_shapes():
     for name in sorted(CASES):
         assert "cap" not in episode(name).trace and "cap" not in searched(name).trace, name
+
+
+# digests (tests/test_expert_cpu.py: digest, and where they come from): name -> (PIBT with the rule, the search with the rule in front)
+DIGESTS = {
+    "agents65": ("792e8eebc919acae88410c781831981468d8a13e29c540ebe1bdda2e4aebaca0",
+        "0a0baf20e847060d44e35a5e4a8d08d1479ce3ec8c95123bf5040cd8c12ace0b"),
+    "agents70": ("be1fce2b6b4810fa59c396ac19aa80a010b8654a3bd7be3a2afcd064565a6f64",
+        "ceb9981309a4b72ddeda722460f4099cd430f750f960b03c12490cca3369e5a7"),
+    "clear2": ("ba89fc421df34d420fcdc81d6bd5e0c9ddcd8a8d11a49cd4f1f957ac718c3292",
+        "b6ffdbea12a861fff8ff02f93d5d63b448f26f63a956cabe7a5625d1aa6ec4ef"),
+    "dead_end": ("e4ad371d0863106482f2143dae3b48cde24b77ecf7dc2603733460c285541c18",
+        "773880d9c66bb4dcc9c5d220ef71cc8b2d994ca57d0a2c0c45547041133f8a4a"),
+    "grids3": ("8f64937b328f17de5243f9c3d2a2ae67eb895e7d626f60374aed30768f2c5012",
+        "041241b1d0d09896505035209183766bafbbca667b1885f25ccf4e6903ef2237"),
+    "maze16": ("709adb895e7fdb8421d1d06c8b7d0d443fea7054219766ddae1bfe2c66bdc7e5",
+        "dee6eec1bea3d6513c8cf0c0d4f137743eb1eea250a42112ba0bbf152609af9a"),
+    "offset7": ("2629b015d99ef419fd4b70ad550a2ac8f264ec549bd5fde64a4a953ceee4e8ae",
+        "681a7c560904fd09ab6e9638e889886ae3c591d74ca3c6092a3879a10600ec1d"),
+    "one_agent": ("8ea4d162561388b8d808b7ba214d0dd26f03ca388f1d03f047eb30c273cbdcf9",
+        "88d1f05a50ef80492dc0e61bc8f8fc1983762bd3a920b20df77c276c7e03a4cb"),
+    "own3": ("c85aaf7cf0bdfdca1157b633d113da9e79d76f91be8d63613f3b752ee27662db",
+        "02614ce073c42b0cfdedff9c8b893ca5994adc9e40fc204fff5b9125c9db548c"),
+    "pocket": ("74f400dd2d16e04fc3349ec6ad42f63404151396d68388ba1639d7315038c22f",
+        "6edf3eb6adf4b5d4c45550738f0658b1421bc2eb20989f4b089efb713c289e37"),
+    "reserved4": ("fa8b0831bd96e9a5896ea2979fe94a1106ae87ff0896be69c6eb8a8ed161b11b",
+        "056445694760538efdae481703f22fdefa133b72321d2e19d74a060b1e21b2b1"),
+    "rests3": ("19f9fb4659300c36f8bce098eba71e2ff10fafafdb01e51c30d1f6352a0b4c93",
+        "ec10595cf544cd6143c4612d93b536cc237064c8ef835b177b1f51158cc38596"),
+    "ring2": ("d88cbaa5b86b2a1777a041380e785a170e70bc6cfccd155c48449a8e1adeaaf5",
+        "ef1ae677f109072571664aadec2a89e28e0d15f45a1a34d600180231442e26b3"),
+    "rotation": ("4d169063e2b52792a2e1bf65a51733510d2951d58bdae06e2612182b9d9159d5",
+        "1b5b8b9ce97303ce362817d284db3f2dbb3af037c70e311c66168b14339f28d4"),
+    "shared5": ("d8ddc0b589403aed654f9760417d5fb29cd9cda167955abac4f6a6ff0725ddee",
+        "d8ab34e3507730b3d99c5f282af871f49d7d4d402234a62ed0ef06172056f525"),
+    "swap2": ("407323cd545b7c4e6c983ffb2552bba9a1c8c771945dc4c7578da1611f1d7f1e",
+        "c18b185f0c84ae2eb4e050320457dffc6e738facdec3391f96d5a39747170409"),
+    "swap3": ("cce206207e1d2c8264ba62fa3e5921f5e5df967a9ac46806eda94bcc2edcbeac",
+        "51947f40e92014356ffa61f9915c1edf7252a03de7b033d49889aa532b69bcfc"),
+}
+
+
+def test_the_episodes_and_searches_are_bit_for_bit_what_they_were():
+    assert set(CASES) == set(DIGESTS)
+    assert {name: (digest(episode(name)), digest(searched(name))) for name in sorted(CASES)} == DIGESTS
