@@ -42,6 +42,9 @@ const char *mgpt_last_error(void);
 int mgpt_abi_version(void);
 /* number of visible HIP devices (0 and MGPT_OK when there is none) */
 int mgpt_device_count(int *count);
+/* test/debug: device and pinned-host allocations this library holds at the moment, process-wide, and their bytes (either may be NULL);
+ * every context's memory is counted from its allocation to its release, so a destroyed context leaves both where they were */
+int mgpt_mem_debug(int64_t *live_allocs, int64_t *live_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * Tokenizer: replaces the pybind module `observation_generator`

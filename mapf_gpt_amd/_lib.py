@@ -40,6 +40,7 @@ SYMBOLS = {
     "mgpt_last_error": (ctypes.c_char_p, []),
     "mgpt_abi_version": (_i, []),
     "mgpt_device_count": (_i, [ctypes.POINTER(_i)]),
+    "mgpt_mem_debug": (_i, [ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "mgpt_tokenizer_create": (_i, [_pp, ctypes.POINTER(InputParametersStruct), _i, _i, _i, _i, _i]),
     "mgpt_tokenizer_destroy": (_i, [_vp]),
     "mgpt_tokenizer_vocab_size": (_i, [_vp, _vp]),
@@ -213,6 +214,13 @@ def prof_read():
     n = ctypes.c_int(cap)
     check(lib().mgpt_prof_read(names, ms, cnt, ctypes.byref(n)))
     return {names[i].decode(): (float(ms[i]), int(cnt[i])) for i in range(n.value)}
+
+
+def mem_debug():
+    """(live allocations, live bytes) of device and pinned memory held by the library (include/mapf_gpt_amd.h: mgpt_mem_debug)."""
+    n, b = _i64(0), _i64(0)
+    check(lib().mgpt_mem_debug(ctypes.byref(n), ctypes.byref(b)))
+    return int(n.value), int(b.value)
 
 
 def debug_counter(which=0, reset=False):

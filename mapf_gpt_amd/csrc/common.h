@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "../../include/mapf_gpt_amd.h"
+#include "device_mem.h"
 
 namespace mgpt {
 
@@ -81,6 +82,13 @@ struct ProfScope {
     ProfScope(ProfId id, hipStream_t stream);
     ~ProfScope();
 };
+
+// raises a kernel's limit of dynamic LDS (a per-device function attribute) to `bytes`
+template <class K>
+inline hipError_t set_max_lds(K *kernel, int bytes)
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }

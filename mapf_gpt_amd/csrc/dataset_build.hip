@@ -442,15 +442,8 @@ struct mgpt_dedup {
     uint64_t *surv_hash = nullptr;
     int64_t *scal = nullptr;                          // device: [0] first count, [1] collision rows, [2] int surv_count, [3] int err
     void *work = nullptr;
+    DeviceArena mem;                                  // every device pointer above
 };
-
-static void dedup_free(mgpt_dedup *d)
-{
-    (void)hipFree(d->keys); (void)hipFree(d->vals); (void)hipFree(d->store); (void)hipFree(d->hashes); (void)hipFree(d->slot_of);
-    (void)hipFree(d->coll); (void)hipFree(d->cidx); (void)hipFree(d->idx); (void)hipFree(d->surv_idx); (void)hipFree(d->surv_hash);
-    (void)hipFree(d->scal); (void)hipFree(d->work);
-    delete d;
-}
 
 extern "C" int mgpt_dedup_reset(mgpt_dedup *d, void *stream)
 {
@@ -481,33 +474,33 @@ extern "C" int mgpt_dedup_create(mgpt_dedup **out, int64_t capacity_rows, int ha
     d->shift = 64 - lg;
     const size_t cap = (size_t)capacity_rows;
     hipError_t e = hipSuccess;
-    auto alloc = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-    alloc((void **)&d->keys, (size_t)d->slots * 8);
-    alloc((void **)&d->vals, (size_t)d->slots * 4);
-    alloc((void **)&d->store, cap * ROW);
-    alloc((void **)&d->hashes, cap * 8);
-    alloc((void **)&d->slot_of, cap * 4);
-    alloc((void **)&d->coll, cap);
-    alloc((void **)&d->cidx, cap * 8);
-    alloc((void **)&d->idx, cap * 8);
-    alloc((void **)&d->surv_idx, MAX_COLL_SURV * 4);
-    alloc((void **)&d->surv_hash, MAX_COLL_SURV * 8);
-    alloc((void **)&d->scal, 4 * 8);
+    auto alloc = [&](auto **p, size_t bytes) { if (e == hipSuccess) e = d->mem.alloc(p, bytes); };
+    alloc(&d->keys, (size_t)d->slots * 8);
+    alloc(&d->vals, (size_t)d->slots * 4);
+    alloc(&d->store, cap * ROW);
+    alloc(&d->hashes, cap * 8);
+    alloc(&d->slot_of, cap * 4);
+    alloc(&d->coll, cap);
+    alloc(&d->cidx, cap * 8);
+    alloc(&d->idx, cap * 8);
+    alloc(&d->surv_idx, MAX_COLL_SURV * 4);
+    alloc(&d->surv_hash, MAX_COLL_SURV * 8);
+    alloc(&d->scal, 4 * 8);
     alloc(&d->work, (size_t)work_bytes(capacity_rows));
     if (e != hipSuccess) {
-        set_error("hipMalloc failed for a set of %lld rows: %s", (long long)capacity_rows, hipGetErrorString(e));
-        dedup_free(d);
+        set_error("device allocation failed for a set of %lld rows: %s", (long long)capacity_rows, hipGetErrorString(e));
+        delete d;
         return MGPT_ERR_HIP;
     }
     const int rc = mgpt_dedup_reset(d, stream);
-    if (rc != MGPT_OK) { dedup_free(d); return rc; }
+    if (rc != MGPT_OK) { delete d; return rc; }
     *out = d;
     return MGPT_OK;
 }
 
 extern "C" int mgpt_dedup_destroy(mgpt_dedup *d)
 {
-    if (d) dedup_free(d);
+    delete d;                                         // (its arena frees what it holds)
     return MGPT_OK;
 }
 

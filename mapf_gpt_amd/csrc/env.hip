@@ -248,19 +248,22 @@ struct mgpt_env {
     uint8_t *done = nullptr;
     uint8_t *wfree = nullptr;           // [n_grids][H][W] traversable cells of the observation window around each cell
     double *dens = nullptr;             // [n_inst] running sum of the per-sample mean agent densities
-    int16_t *goal_queue = nullptr;      // lifelong: [n_inst][n_agents][queue_len][2], else NULL
-    int32_t *qnext = nullptr, *reached = nullptr;
-    int queue_len = 0;
+    struct Lifelong {                   // owned by lifelong_mem; replaced as a whole by mgpt_env_set_lifelong
+        int16_t *goal_queue = nullptr;  // [n_inst][n_agents][queue_len][2], else NULL
+        int32_t *qnext = nullptr, *reached = nullptr;
+        int queue_len = 0;
+    } ll;
     bool have_grids = false, have_reset = false;
     uint64_t generation = 1;            // bumped when the goal queues are replaced (common.h: env_generation)
     int rules = 0;                      // MGPT_ENV_RULE_* mask (mgpt_env_set_rules)
+    DeviceArena mem, lifelong_mem;      // everything above but ll (the pinned staging included); ll
 };
 
 uint64_t mgpt::env_generation(const mgpt_env *e) { return e->generation; }
 void mgpt::env_shape(const mgpt_env *e, int *n_inst, int *n_agents) { *n_inst = e->n_inst; *n_agents = e->n_agents; }
 void mgpt::env_config(const mgpt_env *e, int *H, int *W, int *n_grids, int *rules, int *lifelong)
 {
-    *H = e->H; *W = e->W; *n_grids = e->n_grids; *rules = e->rules; *lifelong = e->goal_queue != nullptr ? 1 : 0;
+    *H = e->H; *W = e->W; *n_grids = e->n_grids; *rules = e->rules; *lifelong = e->ll.goal_queue != nullptr ? 1 : 0;
 }
 
 extern "C" int mgpt_env_create(mgpt_env **out, int n_inst, int n_agents, int H, int W, int n_grids, int max_episode_steps)
@@ -272,21 +275,21 @@ extern "C" int mgpt_env_create(mgpt_env **out, int n_inst, int n_agents, int H, 
     mgpt_env *e = new mgpt_env();
     e->n_inst = n_inst; e->n_agents = n_agents; e->H = H; e->W = W; e->n_grids = n_grids; e->max_steps = max_episode_steps;
     const size_t total = (size_t)n_inst * n_agents;
-    hipError_t err = hipMalloc(&e->grids, (size_t)n_grids * H * W);
+    hipError_t err = e->mem.alloc(&e->grids, (size_t)n_grids * H * W);
     // pos | goal | done live in ONE allocation, in the order mgpt_env_step_host hands them to the host (one copy)
-    if (err == hipSuccess) err = hipMalloc(&e->state_blob, total * 8 + (size_t)n_inst);
+    if (err == hipSuccess) err = e->mem.alloc(&e->state_blob, total * 8 + (size_t)n_inst);
     if (err == hipSuccess) {
         e->pos = reinterpret_cast<int16_t *>(e->state_blob);
         e->goal = e->pos + total * 2;
         e->done = reinterpret_cast<uint8_t *>(e->goal + total * 2);
     }
-    if (err == hipSuccess) err = hipMalloc(&e->arrive, total * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMalloc(&e->tcount, (size_t)n_inst * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMalloc(&e->wfree, (size_t)n_grids * H * W);
-    if (err == hipSuccess) err = hipMalloc(&e->dens, (size_t)n_inst * sizeof(double));
+    if (err == hipSuccess) err = e->mem.alloc(&e->arrive, total * sizeof(int32_t));
+    if (err == hipSuccess) err = e->mem.alloc(&e->tcount, (size_t)n_inst * sizeof(int32_t));
+    if (err == hipSuccess) err = e->mem.alloc(&e->wfree, (size_t)n_grids * H * W);
+    if (err == hipSuccess) err = e->mem.alloc(&e->dens, (size_t)n_inst * sizeof(double));
     if (err != hipSuccess) {
-        set_error("hipMalloc failed in mgpt_env_create: %s", hipGetErrorString(err));
-        mgpt_env_destroy(e);
+        set_error("device allocation failed in mgpt_env_create: %s", hipGetErrorString(err));
+        delete e;
         return MGPT_ERR_HIP;
     }
     *out = e;
@@ -295,12 +298,7 @@ extern "C" int mgpt_env_create(mgpt_env **out, int n_inst, int n_agents, int H, 
 
 extern "C" int mgpt_env_destroy(mgpt_env *e)
 {
-    if (!e) return MGPT_OK;
-    (void)hipFree(e->grids); (void)hipFree(e->state_blob);
-    (void)hipFree(e->arrive); (void)hipFree(e->tcount);
-    (void)hipFree(e->wfree); (void)hipFree(e->dens); (void)hipHostFree(e->pin_act); (void)hipHostFree(e->pin_state);
-    (void)hipFree(e->goal_queue); (void)hipFree(e->qnext); (void)hipFree(e->reached);
-    delete e;
+    delete e;                                            // (its arenas free what it holds)
     return MGPT_OK;
 }
 
@@ -330,10 +328,10 @@ extern "C" int mgpt_env_reset(mgpt_env *e, const int16_t *d_pos, const int16_t *
     hipLaunchKernelGGL(env_density0_kernel, dim3(e->n_inst), dim3(threads), env_lds_bytes(e->n_agents), s, e->pos, e->n_agents,
                        e->n_grids, e->H, e->W, e->wfree, e->dens);
     MGPT_LAUNCH_CHECK();
-    if (e->goal_queue != nullptr) {
+    if (e->ll.goal_queue != nullptr) {
         const size_t total_b = (size_t)total * sizeof(int32_t);
-        MGPT_HIP(hipMemsetAsync(e->qnext, 0, total_b, s));
-        MGPT_HIP(hipMemsetAsync(e->reached, 0, total_b, s));
+        MGPT_HIP(hipMemsetAsync(e->ll.qnext, 0, total_b, s));
+        MGPT_HIP(hipMemsetAsync(e->ll.reached, 0, total_b, s));
     }
     e->have_reset = true;
     return MGPT_OK;
@@ -353,32 +351,33 @@ extern "C" int mgpt_env_set_lifelong(mgpt_env *e, const int16_t *d_goal_queue, i
     MGPT_REQUIRE(e, MGPT_ERR_ARG, "NULL argument");
     hipStream_t s = (hipStream_t)stream;
     e->generation++;                                     // a captured step graph holds the queue pointers (or their absence)
-    (void)hipFree(e->goal_queue); (void)hipFree(e->qnext); (void)hipFree(e->reached);
-    e->goal_queue = nullptr; e->qnext = nullptr; e->reached = nullptr; e->queue_len = 0;
+    e->lifelong_mem.release();
+    e->ll = mgpt_env::Lifelong();
     if (d_goal_queue == nullptr || queue_len <= 0) return MGPT_OK;          // back to on_target = "nothing"
     const size_t total = (size_t)e->n_inst * e->n_agents;
-    int16_t *q = nullptr;
-    int32_t *qn = nullptr, *rc = nullptr;
-    hipError_t err = hipMalloc(&q, total * queue_len * 2 * sizeof(int16_t));
-    if (err == hipSuccess) err = hipMalloc(&qn, total * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMalloc(&rc, total * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMemcpyAsync(q, d_goal_queue, total * queue_len * 2 * sizeof(int16_t), hipMemcpyDeviceToDevice, s);
-    if (err == hipSuccess) err = hipMemsetAsync(qn, 0, total * sizeof(int32_t), s);
-    if (err == hipSuccess) err = hipMemsetAsync(rc, 0, total * sizeof(int32_t), s);
+    DeviceArena mem;
+    mgpt_env::Lifelong ll;
+    hipError_t err = mem.alloc(&ll.goal_queue, total * queue_len * 2 * sizeof(int16_t));
+    if (err == hipSuccess) err = mem.alloc(&ll.qnext, total * sizeof(int32_t));
+    if (err == hipSuccess) err = mem.alloc(&ll.reached, total * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMemcpyAsync(ll.goal_queue, d_goal_queue, total * queue_len * 2 * sizeof(int16_t), hipMemcpyDeviceToDevice, s);
+    if (err == hipSuccess) err = hipMemsetAsync(ll.qnext, 0, total * sizeof(int32_t), s);
+    if (err == hipSuccess) err = hipMemsetAsync(ll.reached, 0, total * sizeof(int32_t), s);
     if (err != hipSuccess) {                                               // stay in on_target = "nothing" rather than half-configured
         set_error("mgpt_env_set_lifelong: %s", hipGetErrorString(err));
-        (void)hipFree(q); (void)hipFree(qn); (void)hipFree(rc);
         return MGPT_ERR_HIP;
     }
-    e->goal_queue = q; e->qnext = qn; e->reached = rc; e->queue_len = queue_len;
+    ll.queue_len = queue_len;
+    e->ll = ll;
+    e->lifelong_mem = std::move(mem);
     return MGPT_OK;
 }
 
 extern "C" int mgpt_env_lifelong_counts(mgpt_env *e, int32_t *d_reached_out, void *stream)
 {
     MGPT_REQUIRE(e && d_reached_out, MGPT_ERR_ARG, "NULL argument");
-    MGPT_REQUIRE(e->reached != nullptr, MGPT_ERR_STATE, "mgpt_env_set_lifelong must precede lifelong_counts");
-    MGPT_HIP(hipMemcpyAsync(d_reached_out, e->reached, (size_t)e->n_inst * e->n_agents * sizeof(int32_t), hipMemcpyDeviceToDevice,
+    MGPT_REQUIRE(e->ll.reached != nullptr, MGPT_ERR_STATE, "mgpt_env_set_lifelong must precede lifelong_counts");
+    MGPT_HIP(hipMemcpyAsync(d_reached_out, e->ll.reached, (size_t)e->n_inst * e->n_agents * sizeof(int32_t), hipMemcpyDeviceToDevice,
                             (hipStream_t)stream));
     return MGPT_OK;
 }
@@ -392,7 +391,7 @@ extern "C" int mgpt_env_step(mgpt_env *e, const int32_t *d_actions, void *stream
     ProfScope ps(P_ENV_STEP, s);
     hipLaunchKernelGGL(env_step_kernel, dim3(e->n_inst), dim3(threads), env_lds_bytes(e->n_agents), s, e->grids,
                        e->n_grids, e->n_agents, e->H, e->W, e->max_steps, e->pos, e->goal, d_actions, e->arrive,
-                       e->tcount, e->done, e->goal_queue, e->queue_len, e->qnext, e->reached, e->wfree, e->dens, e->rules);
+                       e->tcount, e->done, e->ll.goal_queue, e->ll.queue_len, e->ll.qnext, e->ll.reached, e->wfree, e->dens, e->rules);
     MGPT_LAUNCH_CHECK();
     return MGPT_OK;
 }
@@ -409,8 +408,13 @@ extern "C" int mgpt_env_step_host(mgpt_env *e, const int32_t *h_actions, uint8_t
     // comes back by one truly asynchronous copy -- two runtime calls and one synchronisation per step instead of a blocking
     // pageable copy each way (65 -> 4x us per GridEnv.step, tools/time_gridenv.py)
     if (!e->pin_state) {
-        MGPT_HIP(hipHostMalloc(reinterpret_cast<void **>(&e->pin_act), n * sizeof(int32_t), hipHostMallocDefault));
-        MGPT_HIP(hipHostMalloc(reinterpret_cast<void **>(&e->pin_state), nb, hipHostMallocDefault));
+        DeviceArena pin;
+        int32_t *act = nullptr;
+        uint8_t *state = nullptr;
+        MGPT_HIP(pin.alloc_host(&act, n * sizeof(int32_t)));
+        MGPT_HIP(pin.alloc_host(&state, nb));
+        e->pin_act = act; e->pin_state = state;
+        e->mem.adopt(std::move(pin));
     }
     if (h_actions) {
         memcpy(e->pin_act, h_actions, n * sizeof(int32_t));

@@ -678,15 +678,18 @@ struct mgpt_expert {
     bool have_reset = false;
     // LaCAM search (mgpt_expert_set_search): all NULL / 0 without it
     bool search = false, solved = false;
-    int max_iters = 0, iters_per_launch = 0, hash_bits = 0, node_cap = 0, cons_cap = 0, table_size = 0;
-    int32_t *s_state = nullptr, *s_node_q = nullptr, *s_open = nullptr, *s_table = nullptr, *s_unfinished = nullptr;
-    uint32_t *s_node_since = nullptr;
-    int4 *s_node_meta = nullptr, *s_cons = nullptr;
-    int8_t *s_sol = nullptr;
-    uint8_t *s_skip = nullptr;
+    struct Search {                             // sizes and buffers, owned by search_mem
+        int max_iters = 0, iters_per_launch = 0, hash_bits = 0, node_cap = 0, cons_cap = 0, table_size = 0;
+        int32_t *state = nullptr, *node_q = nullptr, *open = nullptr, *table = nullptr, *unfinished = nullptr;
+        uint32_t *node_since = nullptr;
+        int4 *node_meta = nullptr, *cons = nullptr;
+        int8_t *sol = nullptr;
+        uint8_t *skip = nullptr;
+    } ls;
     // the corridor swap rule (mgpt_expert_set_swap): off by default; the degree map is built when it is first turned on
     bool swap = false;
     uint8_t *deg = nullptr;                     // [n_grids][H*W]
+    DeviceArena mem, search_mem, deg_mem;       // occ .. len; ls; deg
 };
 
 // launches the SWAP instantiation of a kernel: one wave64 workgroup per instance, its arrays in dynamic LDS
@@ -699,11 +702,8 @@ constexpr int kDefaultItersPerLaunch = 512;     // the sli
 
 static void search_free(mgpt_expert *ex)
 {
-    (void)hipFree(ex->s_state); (void)hipFree(ex->s_node_q); (void)hipFree(ex->s_open); (void)hipFree(ex->s_table);
-    (void)hipFree(ex->s_unfinished); (void)hipFree(ex->s_node_since); (void)hipFree(ex->s_node_meta); (void)hipFree(ex->s_cons);
-    (void)hipFree(ex->s_sol); (void)hipFree(ex->s_skip);
-    ex->s_state = ex->s_node_q = ex->s_open = ex->s_table = ex->s_unfinished = nullptr;
-    ex->s_node_since = nullptr; ex->s_node_meta = ex->s_cons = nullptr; ex->s_sol = nullptr; ex->s_skip = nullptr;
+    ex->search_mem.release();
+    ex->ls = mgpt_expert::Search();
     ex->search = ex->solved = false;
 }
 
@@ -740,14 +740,14 @@ extern "C" int mgpt_expert_create(mgpt_expert **out, mgpt_tokenizer *tok, mgpt_e
     if (rc == MGPT_OK) rc = mgpt_env_state(env, &ex->pos, &ex->goal, &ex->done);
     if (rc != MGPT_OK) { delete ex; return rc; }
     const size_t total = (size_t)n_inst * n_agents;
-    hipError_t e = hipMalloc(&ex->occ, (size_t)n_inst * 2 * H * W * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMalloc(&ex->since, total * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&ex->planned, total * 2 * sizeof(int16_t));
-    if (e == hipSuccess) e = hipMalloc(&ex->log, total * (size_t)max_steps);
-    if (e == hipSuccess) e = hipMalloc(&ex->len, (size_t)n_inst * sizeof(int32_t));
+    hipError_t e = ex->mem.alloc(&ex->occ, (size_t)n_inst * 2 * H * W * sizeof(uint16_t));
+    if (e == hipSuccess) e = ex->mem.alloc(&ex->since, total * sizeof(uint32_t));
+    if (e == hipSuccess) e = ex->mem.alloc(&ex->planned, total * 2 * sizeof(int16_t));
+    if (e == hipSuccess) e = ex->mem.alloc(&ex->log, total * (size_t)max_steps);
+    if (e == hipSuccess) e = ex->mem.alloc(&ex->len, (size_t)n_inst * sizeof(int32_t));
     if (e != hipSuccess) {
-        set_error("hipMalloc failed in mgpt_expert_create: %s", hipGetErrorString(e));
-        mgpt_expert_destroy(ex);
+        set_error("device allocation failed in mgpt_expert_create: %s", hipGetErrorString(e));
+        delete ex;
         return MGPT_ERR_HIP;
     }
     *out = ex;
@@ -756,11 +756,7 @@ extern "C" int mgpt_expert_create(mgpt_expert **out, mgpt_tokenizer *tok, mgpt_e
 
 extern "C" int mgpt_expert_destroy(mgpt_expert *ex)
 {
-    if (!ex) return MGPT_OK;
-    (void)hipFree(ex->occ); (void)hipFree(ex->since); (void)hipFree(ex->planned); (void)hipFree(ex->log); (void)hipFree(ex->len);
-    (void)hipFree(ex->deg);
-    search_free(ex);
-    delete ex;
+    delete ex;                                           // (its arenas free what it holds)
     return MGPT_OK;
 }
 
@@ -795,27 +791,27 @@ extern "C" int mgpt_expert_set_search(mgpt_expert *ex, int max_iters, int iters_
     MGPT_REQUIRE(lds_bytes(ex->n_agents, ex->swap, true) <= 64 * 1024, MGPT_ERR_UNSUPPORTED,
                  "n_agents=%d: the search's node does not fit 64 KB of LDS", ex->n_agents);
     search_free(ex);
-    ex->max_iters = max_iters;
-    ex->iters_per_launch = iters_per_launch > 0 ? iters_per_launch : kDefaultItersPerLaunch;
-    ex->hash_bits = hash_bits;
-    ex->node_cap = max_iters + 1;                            // the start node and at most one node per iteration
-    ex->cons_cap = ex->node_cap + 5 * max_iters;             // one root per node and at most five successors per iteration
-    ex->table_size = 2;
-    while (ex->table_size < 2 * ex->node_cap) ex->table_size *= 2;      // load factor <= 1/2: a probe always ends on an empty slot
-    const size_t ni = (size_t)ex->n_inst, na = (size_t)ex->n_agents, nc = (size_t)ex->node_cap;
-    hipError_t e = hipMalloc(&ex->s_state, ni * S_WORDS * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&ex->s_node_q, ni * nc * na * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&ex->s_node_since, ni * nc * na * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&ex->s_node_meta, ni * nc * sizeof(int4));
-    if (e == hipSuccess) e = hipMalloc(&ex->s_open, ni * nc * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&ex->s_cons, ni * (size_t)ex->cons_cap * sizeof(int4));
-    if (e == hipSuccess) e = hipMalloc(&ex->s_table, ni * (size_t)ex->table_size * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&ex->s_sol, ni * na * (size_t)ex->max_steps);
-    if (e == hipSuccess) e = hipMalloc(&ex->s_skip, ni);
-    if (e == hipSuccess) e = hipMalloc(&ex->s_unfinished, sizeof(int32_t));
+    ex->ls.max_iters = max_iters;
+    ex->ls.iters_per_launch = iters_per_launch > 0 ? iters_per_launch : kDefaultItersPerLaunch;
+    ex->ls.hash_bits = hash_bits;
+    ex->ls.node_cap = max_iters + 1;                            // the start node and at most one node per iteration
+    ex->ls.cons_cap = ex->ls.node_cap + 5 * max_iters;             // one root per node and at most five successors per iteration
+    ex->ls.table_size = 2;
+    while (ex->ls.table_size < 2 * ex->ls.node_cap) ex->ls.table_size *= 2;      // load factor <= 1/2: a probe always ends on an empty slot
+    const size_t ni = (size_t)ex->n_inst, na = (size_t)ex->n_agents, nc = (size_t)ex->ls.node_cap;
+    hipError_t e = ex->search_mem.alloc(&ex->ls.state, ni * S_WORDS * sizeof(int32_t));
+    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.node_q, ni * nc * na * sizeof(int32_t));
+    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.node_since, ni * nc * na * sizeof(uint32_t));
+    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.node_meta, ni * nc * sizeof(int4));
+    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.open, ni * nc * sizeof(int32_t));
+    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.cons, ni * (size_t)ex->ls.cons_cap * sizeof(int4));
+    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.table, ni * (size_t)ex->ls.table_size * sizeof(int32_t));
+    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.sol, ni * na * (size_t)ex->max_steps);
+    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.skip, ni);
+    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.unfinished, sizeof(int32_t));
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        set_error("hipMalloc failed in mgpt_expert_set_search (max_iters=%d, %d instances x %d agents): %s", max_iters, ex->n_inst, ex->n_agents,
+        set_error("device allocation failed in mgpt_expert_set_search (max_iters=%d, %d instances x %d agents): %s", max_iters, ex->n_inst, ex->n_agents,
                   hipGetErrorString(e));
         search_free(ex);
         return MGPT_ERR_HIP;
@@ -841,14 +837,18 @@ extern "C" int mgpt_expert_set_swap(mgpt_expert *ex, int on)
                      MGPT_ERR_UNSUPPORTED, "n_agents=%d: the frames with their swap agents do not fit 64 KB of LDS", ex->n_agents);
         if (!ex->deg) {                                      // built once per context: the grids never change
             const int64_t total = (int64_t)ex->n_grids * ex->H * ex->W;
-            MGPT_HIP(hipMalloc(&ex->deg, (size_t)total));
+            DeviceArena mem;                                 // (ex->deg stays NULL unless the map is complete)
+            uint8_t *deg = nullptr;
+            MGPT_HIP(mem.alloc(&deg, (size_t)total));
             {
                 ProfScope ps(P_EXPERT_CELL_DEGREE, nullptr);
-                hipLaunchKernelGGL(cell_degree_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, nullptr, ex->grids, ex->deg, ex->n_grids,
+                hipLaunchKernelGGL(cell_degree_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, nullptr, ex->grids, deg, ex->n_grids,
                                    ex->H, ex->W);
                 MGPT_LAUNCH_CHECK();
             }
             MGPT_HIP(hipStreamSynchronize(nullptr));         // whatever stream the next step runs on finds the map complete
+            ex->deg = deg;
+            ex->deg_mem = std::move(mem);
         }
     }
     ex->swap = on != 0;
@@ -864,29 +864,29 @@ extern "C" int mgpt_expert_solve(mgpt_expert *ex, void *stream)
     if (rc != MGPT_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const size_t ni = (size_t)ex->n_inst;
-    MGPT_HIP(hipMemsetAsync(ex->s_state, 0, ni * S_WORDS * sizeof(int32_t), s));
-    MGPT_HIP(hipMemsetAsync(ex->s_table, 0xFF, ni * (size_t)ex->table_size * sizeof(int32_t), s));
-    MGPT_HIP(hipMemsetAsync(ex->s_sol, 0, ni * (size_t)ex->n_agents * (size_t)ex->max_steps, s));
+    MGPT_HIP(hipMemsetAsync(ex->ls.state, 0, ni * S_WORDS * sizeof(int32_t), s));
+    MGPT_HIP(hipMemsetAsync(ex->ls.table, 0xFF, ni * (size_t)ex->ls.table_size * sizeof(int32_t), s));
+    MGPT_HIP(hipMemsetAsync(ex->ls.sol, 0, ni * (size_t)ex->n_agents * (size_t)ex->max_steps, s));
     SearchArgs A;
     A.grids = ex->grids; A.dist = ex->dist; A.pos = ex->pos; A.goal = ex->goal; A.occ = ex->occ;
-    A.state = ex->s_state; A.node_q = ex->s_node_q; A.node_since = ex->s_node_since; A.node_meta = ex->s_node_meta; A.open = ex->s_open;
-    A.cons = ex->s_cons; A.table = ex->s_table; A.sol = ex->s_sol; A.unfinished = ex->s_unfinished;
-    A.n_grids = ex->n_grids; A.n_agents = ex->n_agents; A.H = ex->H; A.W = ex->W; A.max_steps = ex->max_steps; A.max_iters = ex->max_iters;
-    A.iters_per_launch = ex->iters_per_launch; A.node_cap = ex->node_cap; A.cons_cap = ex->cons_cap; A.table_size = ex->table_size;
-    A.hash_mask = ex->hash_bits ? ((1ull << ex->hash_bits) - 1ull) : ~0ull;
+    A.state = ex->ls.state; A.node_q = ex->ls.node_q; A.node_since = ex->ls.node_since; A.node_meta = ex->ls.node_meta; A.open = ex->ls.open;
+    A.cons = ex->ls.cons; A.table = ex->ls.table; A.sol = ex->ls.sol; A.unfinished = ex->ls.unfinished;
+    A.n_grids = ex->n_grids; A.n_agents = ex->n_agents; A.H = ex->H; A.W = ex->W; A.max_steps = ex->max_steps; A.max_iters = ex->ls.max_iters;
+    A.iters_per_launch = ex->ls.iters_per_launch; A.node_cap = ex->ls.node_cap; A.cons_cap = ex->ls.cons_cap; A.table_size = ex->ls.table_size;
+    A.hash_mask = ex->ls.hash_bits ? ((1ull << ex->ls.hash_bits) - 1ull) : ~0ull;
     A.seed = ex->seed; A.inst_offset = ex->inst_offset;
     A.deg = ex->swap ? ex->deg : nullptr;
     // every launch that leaves an instance unfinished has run iters_per_launch iterations of it: this many launches always suffice
-    const int64_t launches = cdiv64((int64_t)ex->max_iters + 1, ex->iters_per_launch) + 1;
+    const int64_t launches = cdiv64((int64_t)ex->ls.max_iters + 1, ex->ls.iters_per_launch) + 1;
     int32_t unfinished = 1;
     for (int64_t l = 0; l < launches && unfinished; l++) {
-        MGPT_HIP(hipMemsetAsync(ex->s_unfinished, 0, sizeof(int32_t), s));
+        MGPT_HIP(hipMemsetAsync(ex->ls.unfinished, 0, sizeof(int32_t), s));
         {
             ProfScope ps(P_EXPERT_SEARCH, s);
             launch_swap(ex, true, lacam_search_kernel<true>, lacam_search_kernel<false>, s, A);
             MGPT_LAUNCH_CHECK();
         }
-        MGPT_HIP(hipMemcpyAsync(&unfinished, ex->s_unfinished, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        MGPT_HIP(hipMemcpyAsync(&unfinished, ex->ls.unfinished, sizeof(int32_t), hipMemcpyDeviceToHost, s));
         MGPT_HIP(hipStreamSynchronize(s));
     }
     MGPT_REQUIRE(!unfinished, MGPT_ERR_STATE, "the search left instances unfinished after %lld launches", (long long)launches);
@@ -903,7 +903,7 @@ extern "C" int mgpt_expert_copy_search(mgpt_expert *ex, int32_t *d_status, int32
     const int words[4] = {S_STATUS, S_ITERS, S_NODES, S_LENGTH};
     for (int j = 0; j < 4; j++)
         if (outs[j])
-            MGPT_HIP(hipMemcpy2DAsync(outs[j], sizeof(int32_t), ex->s_state + words[j], S_WORDS * sizeof(int32_t), sizeof(int32_t), (size_t)ex->n_inst,
+            MGPT_HIP(hipMemcpy2DAsync(outs[j], sizeof(int32_t), ex->ls.state + words[j], S_WORDS * sizeof(int32_t), sizeof(int32_t), (size_t)ex->n_inst,
                                       hipMemcpyDeviceToDevice, s));
     return MGPT_OK;
 }
@@ -912,7 +912,7 @@ extern "C" int mgpt_expert_copy_solution(mgpt_expert *ex, int8_t *d_solution_out
 {
     MGPT_REQUIRE(ex && d_solution_out, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(ex->search && ex->solved, MGPT_ERR_STATE, "mgpt_expert_solve must precede mgpt_expert_copy_solution");
-    MGPT_HIP(hipMemcpyAsync(d_solution_out, ex->s_sol, (size_t)ex->n_inst * ex->n_agents * (size_t)ex->max_steps, hipMemcpyDeviceToDevice,
+    MGPT_HIP(hipMemcpyAsync(d_solution_out, ex->ls.sol, (size_t)ex->n_inst * ex->n_agents * (size_t)ex->max_steps, hipMemcpyDeviceToDevice,
                             (hipStream_t)stream));
     return MGPT_OK;
 }
@@ -927,9 +927,9 @@ extern "C" int mgpt_expert_step(mgpt_expert *ex, int32_t *d_actions, void *strea
     hipStream_t s = (hipStream_t)stream;
     const uint8_t *skip = ex->done;
     if (ex->search) {                                        // solved instances replay their solution; the plan kernel sees them as done
-        hipLaunchKernelGGL(search_skip_kernel, dim3(cdiv(ex->n_inst, 256)), dim3(256), 0, s, ex->done, ex->s_state, ex->s_skip, ex->n_inst);
+        hipLaunchKernelGGL(search_skip_kernel, dim3(cdiv(ex->n_inst, 256)), dim3(256), 0, s, ex->done, ex->ls.state, ex->ls.skip, ex->n_inst);
         MGPT_LAUNCH_CHECK();
-        skip = ex->s_skip;
+        skip = ex->ls.skip;
     }
     {
         ProfScope ps(P_EXPERT_PLAN, s);
@@ -939,7 +939,7 @@ extern "C" int mgpt_expert_step(mgpt_expert *ex, int32_t *d_actions, void *strea
         MGPT_LAUNCH_CHECK();
     }
     if (ex->search) {
-        hipLaunchKernelGGL(search_replay_kernel, dim3(ex->n_inst), dim3(64), 0, s, ex->s_state, ex->s_sol, ex->pos, ex->done, ex->n_agents, d_actions,
+        hipLaunchKernelGGL(search_replay_kernel, dim3(ex->n_inst), dim3(64), 0, s, ex->ls.state, ex->ls.sol, ex->pos, ex->done, ex->n_agents, d_actions,
                            ex->planned, ex->log, ex->len, ex->max_steps);
         MGPT_LAUNCH_CHECK();
     }

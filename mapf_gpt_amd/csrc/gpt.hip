@@ -134,15 +134,15 @@ extern "C" int mgpt_gpt_create(mgpt_gpt **out, int n_layer, int n_head, int n_em
         g->bias_set.assign(1 + (size_t)n_layer * 6, 0);
     }
     const size_t M = (size_t)max_rows * kT;
-    hipError_t e = hipMalloc(&g->params, off * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&g->x, M * C * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&g->xn, M * C * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&g->qkv, 3 * M * C * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&g->hbuf, 4 * M * C * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&g->logits_tmp, (size_t)max_rows * kV * sizeof(float));
+    hipError_t e = g->mem.alloc(&g->params, off * sizeof(float));
+    if (e == hipSuccess) e = g->mem.alloc(&g->x, M * C * sizeof(float));
+    if (e == hipSuccess) e = g->mem.alloc(&g->xn, M * C * sizeof(float));
+    if (e == hipSuccess) e = g->mem.alloc(&g->qkv, 3 * M * C * sizeof(float));
+    if (e == hipSuccess) e = g->mem.alloc(&g->hbuf, 4 * M * C * sizeof(float));
+    if (e == hipSuccess) e = g->mem.alloc(&g->logits_tmp, (size_t)max_rows * kV * sizeof(float));
     if (e != hipSuccess) {
-        set_error("hipMalloc failed in mgpt_gpt_create: %s", hipGetErrorString(e));
-        mgpt_gpt_destroy(g);
+        set_error("device allocation failed in mgpt_gpt_create: %s", hipGetErrorString(e));
+        delete g;
         return MGPT_ERR_HIP;
     }
     *out = g;
@@ -154,9 +154,7 @@ extern "C" int mgpt_gpt_destroy(mgpt_gpt *g)
     if (!g) return MGPT_OK;
     gpt_train_destroy(g);
     gpt_fast_destroy(g);
-    (void)hipFree(g->params); (void)hipFree(g->x); (void)hipFree(g->xn); (void)hipFree(g->qkv);
-    (void)hipFree(g->hbuf); (void)hipFree(g->logits_tmp); (void)hipFree(g->bias);
-    delete g;
+    delete g;                                            // (its arenas free the rest)
     return MGPT_OK;
 }
 
@@ -228,7 +226,7 @@ extern "C" int mgpt_gpt_set_param(mgpt_gpt *g, const char *name, const float *da
     if (locate_bias(g, name, &idx, &off, &count)) {        // a bias = True checkpoint (model.py:115): see mgpt_gpt_forward for which kernels carry it
         MGPT_REQUIRE((size_t)n_elem == count, MGPT_ERR_ARG, "parameter '%s': got %lld elements, expected %zu", name, (long long)n_elem, count);
         if (!g->bias) {
-            MGPT_HIP(hipMalloc(&g->bias, n_bias_elems(g) * sizeof(float)));
+            MGPT_HIP(g->mem.alloc(&g->bias, n_bias_elems(g) * sizeof(float)));
             MGPT_HIP(hipMemset(g->bias, 0, n_bias_elems(g) * sizeof(float)));
         }
         MGPT_HIP(hipMemcpy(g->bias + off, data, count * sizeof(float), is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
@@ -270,7 +268,8 @@ static int envelope_stats(mgpt_gpt *g)
 {
     const size_t C = g->C;
     float *d = nullptr;                                    // [0] max bits, [1] sum of squares
-    MGPT_HIP(hipMalloc(&d, 2 * sizeof(float)));
+    DeviceArena tmp;
+    MGPT_HIP(tmp.alloc(&d, 2 * sizeof(float)));
     g->env_max_w = 0.f; g->env_max_rms = 0.f;
     int rc = MGPT_OK;
     for (int l = 0; l < g->L && rc == MGPT_OK; l++) {
@@ -285,7 +284,6 @@ static int envelope_stats(mgpt_gpt *g)
             g->env_max_rms = std::max(g->env_max_rms, sqrtf(h[1] / (float)cnt[k]));
         }
     }
-    (void)hipFree(d);
     if (rc != MGPT_OK) set_error("envelope statistics failed: %s", hipGetErrorString(hipGetLastError()));
     return rc;
 }
@@ -379,10 +377,10 @@ int gpt_launch_head_seq(mgpt_gpt *g, const float *x, bool tiled, int rows, int T
     const float *lnf = g->params + g->off_lnf, *wte = g->params + g->off_wte;
     const float *lnf_b = g->has_bias ? (const float *)(g->bias + g->off_lnf_b) : (const float *)nullptr;
     if (tiled) {
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&seqk::head_seq_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        MGPT_HIP(set_max_lds(&seqk::head_seq_kernel<1>, (int)lds));
         hipLaunchKernelGGL(seqk::head_seq_kernel<1>, grid, dim3(512), lds, s, x, lnf, lnf_b, wte, g->C, rows, T, o.logits, o.targets, o.row_nll, o.row_count);
     } else {
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&seqk::head_seq_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        MGPT_HIP(set_max_lds(&seqk::head_seq_kernel<0>, (int)lds));
         hipLaunchKernelGGL(seqk::head_seq_kernel<0>, grid, dim3(512), lds, s, x, lnf, lnf_b, wte, g->C, rows, T, o.logits, o.targets, o.row_nll, o.row_count);
     }
     MGPT_LAUNCH_CHECK();
@@ -564,8 +562,9 @@ static int envelope_decide(mgpt_gpt *g, hipStream_t s)
         uint64_t st = 0x9e3779b97f4a7c15ull;
         for (auto &t : h_tok) { st = st * 6364136223846793005ull + 1442695040888963407ull; t = (uint8_t)((st >> 33) % (uint64_t)kV); }
         uint8_t *d_tok = nullptr; float *d_lg = nullptr;
-        MGPT_HIP(hipMalloc(&d_tok, h_tok.size()));
-        if (hipMalloc(&d_lg, (size_t)3 * n * kV * sizeof(float)) != hipSuccess) { (void)hipFree(d_tok); set_error("hipMalloc failed in the envelope probe"); return MGPT_ERR_HIP; }
+        DeviceArena tmp;
+        MGPT_HIP(tmp.alloc(&d_tok, h_tok.size()));
+        MGPT_HIP(tmp.alloc(&d_lg, (size_t)3 * n * kV * sizeof(float)));
         int rc = MGPT_OK;
         // BOTH call regimes: the same rows once as a call of n rows (the small-call kernels: head-parallel attention, 32 x 32 x 16 MLP
         // block, fp32 last layer) and once as a chunk of a call of more than kSmallRows rows (attn256q / attn160o, mlp256q /
@@ -577,7 +576,7 @@ static int envelope_decide(mgpt_gpt *g, hipStream_t s)
         if (rc == MGPT_OK) rc = gpt_fast_forward(g, d_tok, n, d_lg + (size_t)2 * n * kV, MGPT_PREC_F16X3, s, kSmallRows + 1);
         if (rc == MGPT_OK && hipMemcpyAsync(h_lg.data(), d_lg, h_lg.size() * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess) rc = MGPT_ERR_HIP;
         if (rc == MGPT_OK && hipStreamSynchronize(s) != hipSuccess) rc = MGPT_ERR_HIP;
-        (void)hipFree(d_tok); (void)hipFree(d_lg);
+        tmp.release();
         if (rc != MGPT_OK) { if (rc == MGPT_ERR_HIP) set_error("envelope probe failed: %s", hipGetErrorString(hipGetLastError())); return rc; }
         float err[2] = {0.f, 0.f}, max_logit = 0.f;
         for (size_t i = 0; i < (size_t)n * kV; i++) {

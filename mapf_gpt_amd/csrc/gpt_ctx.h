@@ -45,6 +45,9 @@ struct mgpt_gpt {
     // training (train.hip): workspace of mgpt_gpt_train_alloc, NULL for a model that never trains
     void *train = nullptr;
     bool stale16 = false;                       // params changed in place (optimizer step): 16-bit planes and envelope rebuilt before the next 16-bit call
+    // owners of the device memory above (device_mem.h); the precision modes and the training workspace own theirs (gpt_fast.hip, train.hip)
+    mgpt::DeviceArena mem;                      // params, the fp32-path workspace, bias
+    mgpt::DeviceArena embed_mem;                // embed_table
 };
 
 

@@ -96,25 +96,12 @@ struct ModeState {          // one precision mode
     std::vector<float *> attn_cs, fc_cs;
     float2 *ln_parts = nullptr;                // [C / 128][M]
     float *ln_mean = nullptr;                  // [M]: the mean of every row at its latest LayerNorm = the shift of its operand planes (GemmArgs::shift)
+    DeviceArena mem;                           // owns every device pointer of the mode (head_parts, allocated late, included): free_mode
 };
 
 struct FastState {
     ModeState mode[3];      // indexed by MGPT_PREC_* (slot 0 unused)
 };
-
-template <class T, int NP>
-int pack_matrix(const float *d_w, size_t n_elem, float scale, PlaneSet *out, hipStream_t s)
-{
-    MGPT_HIP(hipMalloc(&out->hi, n_elem * sizeof(uint16_t)));
-    if (NP == 2) MGPT_HIP(hipMalloc(&out->lo, n_elem * sizeof(uint16_t)));
-    out->inv_scale = 1.0f / scale;
-    const int64_t n4 = (int64_t)(n_elem / 4);
-    ProfScope ps(P_PACK, s);
-    hipLaunchKernelGGL((fastk::pack_planes_kernel<T, NP>), dim3((unsigned)cdiv64(n4, 256)), dim3(256), 0, s, d_w, out->hi,
-                       out->lo, n4, scale);
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
-}
 
 float pick_scale(const float *h_w, size_t n, bool f16)
 {
@@ -141,43 +128,90 @@ int ensure_embed_table(mgpt_gpt *g)
 {
     if (g->embed_table != nullptr) return MGPT_OK;
     const size_t C = g->C;
-    MGPT_HIP(hipMalloc(&g->embed_table, (size_t)kT * kV * C * sizeof(float)));
+    MGPT_HIP(g->embed_mem.alloc(&g->embed_table, (size_t)kT * kV * C * sizeof(float)));
     hipLaunchKernelGGL(fastk::embed_table_kernel, dim3((unsigned)cdiv64((int64_t)kT * kV * (C / 4), 256)), dim3(256), 0, nullptr,
                        g->params + g->off_wte, g->params + g->off_wpe, g->embed_table, C, kV);
     MGPT_LAUNCH_CHECK();
     return MGPT_OK;
 }
 
-template <class T, int NP>
-int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
+// the same limit of dynamic LDS for several kernels
+template <class... K>
+hipError_t set_max_lds_each(int bytes, K *...kernels)
 {
+    hipError_t e = hipSuccess;
+    ((e = (e == hipSuccess) ? set_max_lds(kernels, bytes) : e), ...);
+    return e;
+}
+
+// Builds one precision mode: packs the weights into the layouts of the family's kernels, raises those kernels' LDS limits and sizes the
+// workspace.  Everything is allocated from m->mem, in the order of build(); a failed build is undone by free_mode (gpt_fast_forward).
+template <class T, int NP>
+struct ModeBuilder {
+    mgpt_gpt *g;
+    ModeState *m;
+    const bool f16;
     const size_t C = g->C;
-    g->generation++;                                     // a step graph captured before this build must not be replayed as is
-    std::vector<float> host(g->n_params);
-    MGPT_HIP(hipMemcpy(host.data(), g->params, g->n_params * sizeof(float), hipMemcpyDeviceToHost));
-    m->np = NP;
+    const int L = g->L;
+    const float *P = g->params;
+    std::vector<float> host = std::vector<float>(g->n_params);      // the parameters, for the scales
+
+    int pack_matrix(const float *d_w, size_t n_elem, float scale, PlaneSet *out)
     {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        MGPT_HIP(hipGetDevice(&dev));
-        MGPT_HIP(hipGetDeviceProperties(&prop, dev));
-        m->n_cu = std::max(1, prop.multiProcessorCount);
+        MGPT_HIP(m->mem.alloc(&out->hi, n_elem * sizeof(uint16_t)));
+        if (NP == 2) MGPT_HIP(m->mem.alloc(&out->lo, n_elem * sizeof(uint16_t)));
+        out->inv_scale = 1.0f / scale;
+        const int64_t n4 = (int64_t)(n_elem / 4);
+        ProfScope ps(P_PACK, nullptr);
+        hipLaunchKernelGGL((fastk::pack_planes_kernel<T, NP>), dim3((unsigned)cdiv64(n4, 256)), dim3(256), 0, nullptr, d_w, out->hi,
+                           out->lo, n4, scale);
+        MGPT_LAUNCH_CHECK();
+        return MGPT_OK;
     }
-    m->attn.resize(g->L); m->proj.resize(g->L); m->fc.resize(g->L); m->proj2.resize(g->L);
-    int rc;
-    for (int l = 0; l < g->L; l++) {
-        const LayerOff &lo = g->layers[l];
-        struct { size_t off, n; PlaneSet *dst; } mats[4] = {{lo.attn_w, 3 * C * C, &m->attn[l]}, {lo.proj_w, C * C, &m->proj[l]},
-                                                           {lo.fc_w, 4 * C * C, &m->fc[l]}, {lo.proj2_w, 4 * C * C, &m->proj2[l]}};
-        for (auto &mt : mats) {
-            const float sc = pick_scale(host.data() + mt.off, mt.n, f16);
-            if ((rc = pack_matrix<T, NP>(g->params + mt.off, mt.n, sc, mt.dst, nullptr)) != MGPT_OK) return rc;
+
+    // One packed stream of n16 halves per layer that carries a weight with the LayerNorm gain folded in (of_attn: c_attn.weight * ln_1.weight,
+    // else c_fc.weight * ln_2.weight): allocates it, picks the folded scale, keeps 1 / scale and packs -- launch(layer offsets, layer, stream, scale)
+    template <class Launch>
+    int pack_folded(std::vector<uint16_t *> &pk, std::vector<float> &inv, size_t n16, bool of_attn, Launch launch)
+    {
+        pk.assign(L, nullptr);
+        inv.assign(L, 1.f);
+        for (int l = 0; l < L; l++) {
+            MGPT_HIP(m->mem.alloc(&pk[l], n16 * sizeof(uint16_t)));
+            const LayerOff &lo = g->layers[l];
+            const float sc = of_attn ? folded_scale(host, lo.attn_w, lo.ln1, 3 * C * C, C, f16) : folded_scale(host, lo.fc_w, lo.ln2, 4 * C * C, C, f16);
+            inv[l] = 1.0f / sc;
+            ProfScope ps(P_PACK, nullptr);
+            launch(lo, l, pk[l], sc);
+            MGPT_LAUNCH_CHECK();
         }
+        return MGPT_OK;
     }
-    // (C = 256: the fused kernels are the 6M shape's -- 8 heads of 32 -- and share the chunk-major residual stream; any other
-    //  C = 256 model takes the packed-fragment GEMM chain)
-    m->mlp_fused = (C == 160 || C == 64 || (C == 256 && g->hs == 32 && g->nh == 8));
-    {   // Phi(v) = (1 + erf(v / sqrt 2)) / 2 on [-6, 6) in steps of 1/256, as (value, forward difference) pairs
+
+    // ---- every family: the row-major planes of the four matrices of a layer, the Phi table of the GELU epilogues ----
+    int build_planes()
+    {
+        MGPT_HIP(hipMemcpy(host.data(), P, g->n_params * sizeof(float), hipMemcpyDeviceToHost));
+        m->np = NP;
+        {
+            int dev = 0;
+            hipDeviceProp_t prop;
+            MGPT_HIP(hipGetDevice(&dev));
+            MGPT_HIP(hipGetDeviceProperties(&prop, dev));
+            m->n_cu = std::max(1, prop.multiProcessorCount);
+        }
+        m->attn.resize(L); m->proj.resize(L); m->fc.resize(L); m->proj2.resize(L);
+        int rc;
+        for (int l = 0; l < L; l++) {
+            const LayerOff &lo = g->layers[l];
+            struct { size_t off, n; PlaneSet *dst; } mats[4] = {{lo.attn_w, 3 * C * C, &m->attn[l]}, {lo.proj_w, C * C, &m->proj[l]},
+                                                               {lo.fc_w, 4 * C * C, &m->fc[l]}, {lo.proj2_w, 4 * C * C, &m->proj2[l]}};
+            for (auto &mt : mats) {
+                const float sc = pick_scale(host.data() + mt.off, mt.n, f16);
+                if ((rc = pack_matrix(P + mt.off, mt.n, sc, mt.dst)) != MGPT_OK) return rc;
+            }
+        }
+        // Phi(v) = (1 + erf(v / sqrt 2)) / 2 on [-6, 6) in steps of 1/256, as (value, forward difference) pairs
         std::vector<float2> lut(fastk::kGeluLutN);
         auto phi = [](double v) { return 0.5 * (1.0 + erf(v * 0.70710678118654752440)); };
         for (int i = 0; i < fastk::kGeluLutN; i++) {
@@ -185,18 +219,23 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
             const float f0 = (float)phi(v0);
             lut[i] = make_float2(f0, (float)(phi(v1) - (double)f0));
         }
-        MGPT_HIP(hipMalloc(&m->gelu_lut, lut.size() * sizeof(float2)));
+        MGPT_HIP(m->mem.alloc(&m->gelu_lut, lut.size() * sizeof(float2)));
         MGPT_HIP(hipMemcpy(m->gelu_lut, lut.data(), lut.size() * sizeof(float2), hipMemcpyHostToDevice));
+        return MGPT_OK;
     }
-    if (C == 256 && m->mlp_fused) {
+
+    // ---- FAM_6M (C = 256, 8 heads of 32): MLP streams and their tables, attn256 / attn256q streams, spill slab, the layer-0 table ----
+    int build_6m()
+    {
+        int rc;
         const size_t n16 = (size_t)fastk::kMPPeriod * 16 * NP * 512;
-        m->mlp256_pk.assign(g->L, nullptr);
-        m->mlp256q_pk.assign(g->L, nullptr);
-        m->mlp256_inv1.assign(g->L, 1.f);
-        m->mlp256_lut.assign(g->L, nullptr);
-        for (int l = 0; l < g->L; l++) {
-            MGPT_HIP(hipMalloc(&m->mlp256_pk[l], n16 * sizeof(uint16_t)));
-            MGPT_HIP(hipMalloc(&m->mlp256q_pk[l], n16 * sizeof(uint16_t)));
+        m->mlp256_pk.assign(L, nullptr);
+        m->mlp256q_pk.assign(L, nullptr);
+        m->mlp256_inv1.assign(L, 1.f);
+        m->mlp256_lut.assign(L, nullptr);
+        for (int l = 0; l < L; l++) {
+            MGPT_HIP(m->mem.alloc(&m->mlp256_pk[l], n16 * sizeof(uint16_t)));
+            MGPT_HIP(m->mem.alloc(&m->mlp256q_pk[l], n16 * sizeof(uint16_t)));
             const LayerOff &lo = g->layers[l];
             const float sc1 = folded_scale(host, lo.fc_w, lo.ln2, 4 * C * C, C, f16);      // the stream carries c_fc.weight * ln_2.weight
             m->mlp256_inv1[l] = 1.0f / sc1;
@@ -204,361 +243,325 @@ int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
                 std::vector<float2> lt(fastk::kGeluLutN);
                 MGPT_HIP(hipMemcpy(lt.data(), m->gelu_lut, lt.size() * sizeof(float2), hipMemcpyDeviceToHost));
                 for (auto &e : lt) { e.x *= m->mlp256_inv1[l]; e.y *= m->mlp256_inv1[l]; }
-                MGPT_HIP(hipMalloc(&m->mlp256_lut[l], lt.size() * sizeof(float2)));
+                MGPT_HIP(m->mem.alloc(&m->mlp256_lut[l], lt.size() * sizeof(float2)));
                 MGPT_HIP(hipMemcpy(m->mlp256_lut[l], lt.data(), lt.size() * sizeof(float2), hipMemcpyHostToDevice));
             }
             ProfScope ps(P_PACK, nullptr);
             hipLaunchKernelGGL((fastk::pack_mlp256p_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kMPPeriod * 16 * 64, 256)), dim3(256), 0,
-                               nullptr, g->params + lo.fc_w, g->params + lo.proj2_w, g->params + lo.ln2, m->mlp256_pk[l], sc1,
-                               1.0f / m->proj2[l].inv_scale);
+                               nullptr, P + lo.fc_w, P + lo.proj2_w, P + lo.ln2, m->mlp256_pk[l], sc1, 1.0f / m->proj2[l].inv_scale);
             MGPT_LAUNCH_CHECK();
             hipLaunchKernelGGL((fastk::pack_mlp256q_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kMPPeriod * 16 * 64, 256)), dim3(256), 0,
-                               nullptr, g->params + lo.fc_w, g->params + lo.proj2_w, g->params + lo.ln2, m->mlp256q_pk[l], sc1,
-                               1.0f / m->proj2[l].inv_scale);
+                               nullptr, P + lo.fc_w, P + lo.proj2_w, P + lo.ln2, m->mlp256q_pk[l], sc1, 1.0f / m->proj2[l].inv_scale);
             MGPT_LAUNCH_CHECK();
         }
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp256p_kernel<T, NP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     fastk::kMPLds<NP>));
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp256p_kernel<T, NP, 0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     fastk::kMPLds<NP>));
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp256q_kernel<T, NP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     fastk::kMPLds<NP>));
+        MGPT_HIP(set_max_lds_each(fastk::kMPLds<NP>, &fastk::mlp256p_kernel<T, NP>, &fastk::mlp256p_kernel<T, NP, 0, 2>, &fastk::mlp256q_kernel<T, NP>));
         m->attn256 = (g->hs == 32 && g->nh == 8);
-        if (m->attn256) {
-            const size_t n16 = (size_t)8 * fastk::kA256StepsPerHead * 8 * NP * 512;
-            m->attn256_pk.assign(g->L, nullptr);
-            m->attn256_inv.assign(g->L, 1.f);
-            for (int l = 0; l < g->L; l++) {
-                MGPT_HIP(hipMalloc(&m->attn256_pk[l], n16 * sizeof(uint16_t)));
-                const LayerOff &lo = g->layers[l];
-                const float sc = folded_scale(host, lo.attn_w, lo.ln1, 3 * C * C, C, f16);      // the stream carries c_attn.weight * ln_1.weight
-                m->attn256_inv[l] = 1.0f / sc;
-                ProfScope ps(P_PACK, nullptr);
-                hipLaunchKernelGGL((fastk::pack_attn256_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)8 * fastk::kA256StepsPerHead * 8 * 64, 256)), dim3(256), 0,
-                                   nullptr, g->params + lo.attn_w, g->params + lo.ln1, m->attn256_pk[l], sc);
-                MGPT_LAUNCH_CHECK();
-            }
-            {   // the whole attention block in one persistent kernel: 48 steps of c_attn * ln_1 followed by 16 steps of c_proj
-                const size_t n16o = (size_t)fastk::kA256oPeriod * 8 * NP * 512;
-                m->attn256q_pk.assign(g->L, nullptr);
-                for (int l = 0; l < g->L; l++) {
-                    const LayerOff &lo = g->layers[l];
-                    ProfScope ps(P_PACK, nullptr);
-                    MGPT_HIP(hipMalloc(&m->attn256q_pk[l], n16o * sizeof(uint16_t)));
-                    hipLaunchKernelGGL((fastk::pack_attn256q_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kA256oPeriod * 8 * 64, 256)), dim3(256), 0,
-                                       nullptr, g->params + lo.attn_w, g->params + lo.ln1, g->params + lo.proj_w, m->attn256q_pk[l],
-                                       1.0f / m->attn256_inv[l], 1.0f / m->proj[l].inv_scale);
-                    MGPT_LAUNCH_CHECK();
-                }
-                MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, fastk::kA256Lds<NP>));
-                MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, fastk::kA256Lds<NP>));
-                if ((rc = ensure_embed_table(g)) != MGPT_OK) return rc;
-                MGPT_HIP(hipMalloc(&m->attn256q_spill, (size_t)m->n_cu * 8 * 14 * NP * 1024));
-                // Layer 0 of large calls from a (position, token) table of q | k | v: its input row is etab[position][token], so the row's
-                // LayerNorm and q|k|v projection are a function of the pair.  The table is the output of the EMB kernel itself (TAB = 1) on kV
-                // synthetic rows, row j = token j at every position: every pair in the wave, lane and MFMA slot it has in a real row, so every
-                // entry is bit-identical to what layer 0 computes.  (MGPT_L0_TABLE=0 in the environment keeps the EMB kernel on layer 0.)
-                const char *tab_env = getenv("MGPT_L0_TABLE");
-                if (g->L > 1 && !(tab_env != nullptr && tab_env[0] == '0')) {
-                    ProfScope ps(P_PACK, nullptr);
-                    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP, 0, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, fastk::kA256Lds<NP>));
-                    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256q_kernel<T, NP, 0, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, fastk::kA256Lds<NP>));
-                    MGPT_HIP(hipMalloc(&m->l0_table, (size_t)kT * kV * fastk::kL0TabEntryBytes<NP>));
-                    float *xt = nullptr;
-                    unsigned char *tk = nullptr;
-                    MGPT_HIP(hipMalloc(&xt, (size_t)kV * kT * C * sizeof(float)));
-                    MGPT_HIP(hipMalloc(&tk, (size_t)kV * kT));
-                    for (int j = 0; j < kV; j++) MGPT_HIP(hipMemset(tk + (size_t)j * kT, j, kT));
-                    const float scale_log2e = (1.0f / sqrtf((float)g->hs)) * 1.44269504088896340736f;    // (as forward_chunk)
-                    hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true, 1>), dim3((unsigned)std::min(kV, m->n_cu)), dim3(512), (size_t)fastk::kA256Lds<NP>, nullptr, xt,
-                                       m->attn256q_pk[0], m->attn256_inv[0], scale_log2e, m->proj[0].inv_scale, m->attn256q_spill, kV,
-                                       (unsigned long long *)nullptr, tk, g->embed_table, m->l0_table);
-                    MGPT_LAUNCH_CHECK();
-                    MGPT_HIP(hipDeviceSynchronize());
-                    MGPT_HIP(hipFree(xt));
-                    MGPT_HIP(hipFree(tk));
-                }
-            }
-            MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn256_kernel<T, NP>), hipFuncAttributeMaxDynamicSharedMemorySize, fastk::kA256Lds<NP>));
-        }
-    } else if (m->mlp_fused) {
-        const size_t frags = C / 16 + 2 * (C / 32), nt = 4 * C / 32;
-        const size_t n16 = nt * frags * NP * 512;
-        // (the small calls of C = 160 take mlp160p_kernel, below: mlp_fused_kernel's packets only for C = 64)
-        if (C == 64) m->mlp_pk.assign(g->L, nullptr);
-        m->mlp16_pk.assign(g->L, nullptr);
-        for (int l = 0; l < g->L; l++) {
+        if (!m->attn256) return MGPT_OK;
+        rc = pack_folded(m->attn256_pk, m->attn256_inv, (size_t)8 * fastk::kA256StepsPerHead * 8 * NP * 512, true,
+                         [&](const LayerOff &lo, int, uint16_t *pk, float sc) {
+                             hipLaunchKernelGGL((fastk::pack_attn256_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)8 * fastk::kA256StepsPerHead * 8 * 64, 256)),
+                                                dim3(256), 0, nullptr, P + lo.attn_w, P + lo.ln1, pk, sc);
+                         });
+        if (rc != MGPT_OK) return rc;
+        // the whole attention block in one persistent kernel: 48 steps of c_attn * ln_1 followed by 16 steps of c_proj
+        const size_t n16o = (size_t)fastk::kA256oPeriod * 8 * NP * 512;
+        m->attn256q_pk.assign(L, nullptr);
+        for (int l = 0; l < L; l++) {
             const LayerOff &lo = g->layers[l];
             ProfScope ps(P_PACK, nullptr);
-            if (C == 64) {
-                MGPT_HIP(hipMalloc(&m->mlp_pk[l], n16 * sizeof(uint16_t)));
-                hipLaunchKernelGGL((fastk::pack_mlp_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(nt * frags * 64), 256)), dim3(256), 0,
-                                   nullptr, g->params + lo.fc_w, g->params + lo.proj2_w, m->mlp_pk[l], (int)C,
-                                   1.0f / m->fc[l].inv_scale, 1.0f / m->proj2[l].inv_scale);
-                MGPT_LAUNCH_CHECK();
-            }
-            MGPT_HIP(hipMalloc(&m->mlp16_pk[l], n16 * sizeof(uint16_t)));
-            hipLaunchKernelGGL((fastk::pack_mlp16_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(nt * frags * 64), 256)), dim3(256), 0,
-                               nullptr, g->params + lo.fc_w, g->params + lo.proj2_w, m->mlp16_pk[l], (int)C,
-                               1.0f / m->fc[l].inv_scale, 1.0f / m->proj2[l].inv_scale);
+            MGPT_HIP(m->mem.alloc(&m->attn256q_pk[l], n16o * sizeof(uint16_t)));
+            hipLaunchKernelGGL((fastk::pack_attn256q_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kA256oPeriod * 8 * 64, 256)), dim3(256), 0,
+                               nullptr, P + lo.attn_w, P + lo.ln1, P + lo.proj_w, m->attn256q_pk[l], 1.0f / m->attn256_inv[l], 1.0f / m->proj[l].inv_scale);
             MGPT_LAUNCH_CHECK();
         }
-        const int pkt = fastk::mlp_fused_lds(NP, (int)C);
-#define MGPT_MLP16_ATTR(CT_, NW_) \
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp_fused16_kernel<T, NP, CT_, NW_, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, pkt))
-#define MGPT_MLP_ATTR(CT_, NW_) \
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp_fused_kernel<T, NP, CT_, NW_>), hipFuncAttributeMaxDynamicSharedMemorySize, pkt)); \
-    MGPT_MLP16_ATTR(CT_, NW_)
-        if (C == 160) { MGPT_MLP16_ATTR(5, 8); MGPT_MLP16_ATTR(5, 4); MGPT_MLP16_ATTR(5, 2); }
-        else { MGPT_MLP_ATTR(2, 8); MGPT_MLP_ATTR(2, 4); MGPT_MLP_ATTR(2, 2); }
-#undef MGPT_MLP_ATTR
-#undef MGPT_MLP16_ATTR
+        MGPT_HIP(set_max_lds_each(fastk::kA256Lds<NP>, &fastk::attn256q_kernel<T, NP>, &fastk::attn256q_kernel<T, NP, 0, true>));
+        if ((rc = ensure_embed_table(g)) != MGPT_OK) return rc;
+        MGPT_HIP(m->mem.alloc(&m->attn256q_spill, (size_t)m->n_cu * 8 * 14 * NP * 1024));
+        // Layer 0 of large calls from a (position, token) table of q | k | v: its input row is etab[position][token], so the row's
+        // LayerNorm and q|k|v projection are a function of the pair.  The table is the output of the EMB kernel itself (TAB = 1) on kV
+        // synthetic rows, row j = token j at every position: every pair in the wave, lane and MFMA slot it has in a real row, so every
+        // entry is bit-identical to what layer 0 computes.  (MGPT_L0_TABLE=0 in the environment keeps the EMB kernel on layer 0.)
+        const char *tab_env = getenv("MGPT_L0_TABLE");
+        if (L > 1 && !(tab_env != nullptr && tab_env[0] == '0')) {
+            ProfScope ps(P_PACK, nullptr);
+            MGPT_HIP(set_max_lds_each(fastk::kA256Lds<NP>, &fastk::attn256q_kernel<T, NP, 0, true, 1>, &fastk::attn256q_kernel<T, NP, 0, false, 2>));
+            MGPT_HIP(m->mem.alloc(&m->l0_table, (size_t)kT * kV * fastk::kL0TabEntryBytes<NP>));
+            DeviceArena tmp;                                 // the synthetic rows: freed on every way out, after the synchronise on the good one
+            float *xt = nullptr;
+            unsigned char *tk = nullptr;
+            MGPT_HIP(tmp.alloc(&xt, (size_t)kV * kT * C * sizeof(float)));
+            MGPT_HIP(tmp.alloc(&tk, (size_t)kV * kT));
+            for (int j = 0; j < kV; j++) MGPT_HIP(hipMemset(tk + (size_t)j * kT, j, kT));
+            const float scale_log2e = (1.0f / sqrtf((float)g->hs)) * 1.44269504088896340736f;    // (as forward_chunk)
+            hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true, 1>), dim3((unsigned)std::min(kV, m->n_cu)), dim3(512), (size_t)fastk::kA256Lds<NP>, nullptr, xt,
+                               m->attn256q_pk[0], m->attn256_inv[0], scale_log2e, m->proj[0].inv_scale, m->attn256q_spill, kV,
+                               (unsigned long long *)nullptr, tk, g->embed_table, m->l0_table);
+            MGPT_LAUNCH_CHECK();
+            MGPT_HIP(hipDeviceSynchronize());
+        }
+        MGPT_HIP(set_max_lds(&fastk::attn256_kernel<T, NP>, fastk::kA256Lds<NP>));
+        return MGPT_OK;
     }
-    m->qkv_fused = (C == 160 || C == 64);
-    if (m->qkv_fused) {
+
+    // ---- C = 64 / 160: the fused MLP's packets, and (FAM_REGISTER: heads of 32) qkv_pk / proj_pk and the 160-only persistent streams ----
+    template <int CT>
+    int build_register()
+    {
+        int rc;
+        {
+            const size_t frags = C / 16 + 2 * (C / 32), nt = 4 * C / 32;
+            const size_t n16 = nt * frags * NP * 512;
+            // (the small calls of C = 160 take mlp160p_kernel, below: mlp_fused_kernel's packets only for C = 64)
+            if (CT == 2) m->mlp_pk.assign(L, nullptr);
+            m->mlp16_pk.assign(L, nullptr);
+            for (int l = 0; l < L; l++) {
+                const LayerOff &lo = g->layers[l];
+                ProfScope ps(P_PACK, nullptr);
+                if (CT == 2) {
+                    MGPT_HIP(m->mem.alloc(&m->mlp_pk[l], n16 * sizeof(uint16_t)));
+                    hipLaunchKernelGGL((fastk::pack_mlp_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(nt * frags * 64), 256)), dim3(256), 0,
+                                       nullptr, P + lo.fc_w, P + lo.proj2_w, m->mlp_pk[l], (int)C, 1.0f / m->fc[l].inv_scale, 1.0f / m->proj2[l].inv_scale);
+                    MGPT_LAUNCH_CHECK();
+                }
+                MGPT_HIP(m->mem.alloc(&m->mlp16_pk[l], n16 * sizeof(uint16_t)));
+                hipLaunchKernelGGL((fastk::pack_mlp16_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(nt * frags * 64), 256)), dim3(256), 0,
+                                   nullptr, P + lo.fc_w, P + lo.proj2_w, m->mlp16_pk[l], (int)C, 1.0f / m->fc[l].inv_scale, 1.0f / m->proj2[l].inv_scale);
+                MGPT_LAUNCH_CHECK();
+            }
+            const int pkt = fastk::mlp_fused_lds(NP, (int)C);
+            if constexpr (CT == 2)
+                MGPT_HIP(set_max_lds_each(pkt, &fastk::mlp_fused_kernel<T, NP, 2, 8>, &fastk::mlp_fused_kernel<T, NP, 2, 4>, &fastk::mlp_fused_kernel<T, NP, 2, 2>));
+            MGPT_HIP(set_max_lds_each(pkt, &fastk::mlp_fused16_kernel<T, NP, CT, 8, 0>, &fastk::mlp_fused16_kernel<T, NP, CT, 4, 0>,
+                                      &fastk::mlp_fused16_kernel<T, NP, CT, 2, 0>));
+        }
+        m->qkv_fused = true;
         const size_t ks = C / 16, ntile = 3 * C / 32;
-        m->qkv_pk.assign(g->L, nullptr);
-        for (int l = 0; l < g->L; l++) {
-            MGPT_HIP(hipMalloc(&m->qkv_pk[l], ntile * ks * NP * 512 * sizeof(uint16_t)));
+        m->qkv_pk.assign(L, nullptr);
+        for (int l = 0; l < L; l++) {
+            MGPT_HIP(m->mem.alloc(&m->qkv_pk[l], ntile * ks * NP * 512 * sizeof(uint16_t)));
             ProfScope ps(P_PACK, nullptr);
             hipLaunchKernelGGL((fastk::pack_rows_perm_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(ntile * ks * 64), 256)), dim3(256), 0,
-                               nullptr, g->params + g->layers[l].attn_w, m->qkv_pk[l], (int)ntile, (int)C, 1.0f / m->attn[l].inv_scale);
+                               nullptr, P + g->layers[l].attn_w, m->qkv_pk[l], (int)ntile, (int)C, 1.0f / m->attn[l].inv_scale);
             MGPT_LAUNCH_CHECK();
         }
-        if (g->hs == 32) {
-            const size_t ct = C / 32;
-            m->proj_pk.assign(g->L, nullptr);
-            for (int l = 0; l < g->L; l++) {
-                MGPT_HIP(hipMalloc(&m->proj_pk[l], (size_t)g->nh * 2 * ct * NP * 512 * sizeof(uint16_t)));
-                ProfScope ps(P_PACK, nullptr);
-                hipLaunchKernelGGL((fastk::pack_cols_perm_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(g->nh * 2 * ct * 64), 256)), dim3(256), 0,
-                                   nullptr, g->params + g->layers[l].proj_w, m->proj_pk[l], g->nh, (int)C, (int)C, 1.0f / m->proj[l].inv_scale);
-                MGPT_LAUNCH_CHECK();
-            }
-            // attn_block_kernel's dynamic LDS limit is a per-device function attribute: set it for this model's device
-            const int lds = fastk::attn_block_lds(NP, (int)C);
-#define MGPT_ATTN_LDS(CT_, EMB_, HP_)                                                                                            \
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn_block_kernel<T, NP, CT_, EMB_, HP_>), hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-            // (C = 160 runs it in small calls only: the persistent attn160o_kernel below serves the large ones)
-            if (C == 160) MGPT_ATTN_LDS(5, false, true);
-            else { MGPT_ATTN_LDS(2, false, false); MGPT_ATTN_LDS(2, true, false); MGPT_ATTN_LDS(2, false, true); }
-#undef MGPT_ATTN_LDS
-            // (head_parts -- the heads' partial sums of small launches -- is allocated by the first small launch: forward_chunk)
-            if (m->mlp_fused && C == 160) {
-                const size_t n16 = (size_t)fastk::kM5Period * 20 * NP * 512;
-                m->mlp160_pk.assign(g->L, nullptr);
-                m->mlp160_inv1.assign(g->L, 1.f);
-                for (int l = 0; l < g->L; l++) {
-                    MGPT_HIP(hipMalloc(&m->mlp160_pk[l], n16 * sizeof(uint16_t)));
-                    const LayerOff &lo = g->layers[l];
-                    const float sc1 = folded_scale(host, lo.fc_w, lo.ln2, 4 * C * C, C, f16);      // the stream carries c_fc.weight * ln_2.weight
-                    m->mlp160_inv1[l] = 1.0f / sc1;
-                    ProfScope ps(P_PACK, nullptr);
-                    hipLaunchKernelGGL((fastk::pack_mlp160p_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kM5Period * 20 * 64, 256)), dim3(256), 0,
-                                       nullptr, g->params + lo.fc_w, g->params + lo.proj2_w, g->params + lo.ln2, m->mlp160_pk[l], sc1,
-                                       1.0f / m->proj2[l].inv_scale);
-                    MGPT_LAUNCH_CHECK();
-                }
-                // the attention block as one persistent kernel (layers that neither gather the embedding nor are the last)
-                m->attn160o_pk.assign(g->L, nullptr);
-                m->attn160_inv.assign(g->L, 1.f);
-                for (int l = 0; l < g->L; l++) {
-                    MGPT_HIP(hipMalloc(&m->attn160o_pk[l], (size_t)fastk::kA160oPeriod * fastk::kA160oFrags * NP * 512 * sizeof(uint16_t)));
-                    const LayerOff &lo = g->layers[l];
-                    const float sca = folded_scale(host, lo.attn_w, lo.ln1, 3 * C * C, C, f16);      // c_attn.weight * ln_1.weight
-                    m->attn160_inv[l] = 1.0f / sca;
-                    ProfScope ps(P_PACK, nullptr);
-                    hipLaunchKernelGGL((fastk::pack_attn160o_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kA160oPeriod * fastk::kA160oFrags * 64, 256)),
-                                       dim3(256), 0, nullptr, g->params + lo.attn_w, g->params + lo.ln1, g->params + lo.proj_w, m->attn160o_pk[l], sca,
-                                       1.0f / m->proj[l].inv_scale);
-                    MGPT_LAUNCH_CHECK();
-                }
-                MGPT_HIP(hipMalloc(&m->attn160o_spill, (size_t)m->n_cu * fastk::kA160oSpillPerWg<NP>));
-                MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn160o_kernel<T, NP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             fastk::kA160oLds<NP>));
-                MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn160o_kernel<T, NP, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             fastk::kA160oLds<NP>));
-                if ((rc = ensure_embed_table(g)) != MGPT_OK) return rc;
-                MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp160p_kernel<T, NP, 5>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             fastk::kM5Lds<NP>));
-                MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp160p_kernel<T, NP, 5, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (fastk::kM5Lds<NP, 2>)));
-                MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::mlp160p_kernel<T, NP, 5, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (fastk::kM5Lds<NP, 1>)));
-            }
+        if (g->hs != 32) return MGPT_OK;
+        const size_t ct = C / 32;
+        m->proj_pk.assign(L, nullptr);
+        for (int l = 0; l < L; l++) {
+            MGPT_HIP(m->mem.alloc(&m->proj_pk[l], (size_t)g->nh * 2 * ct * NP * 512 * sizeof(uint16_t)));
+            ProfScope ps(P_PACK, nullptr);
+            hipLaunchKernelGGL((fastk::pack_cols_perm_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(g->nh * 2 * ct * 64), 256)), dim3(256), 0,
+                               nullptr, P + g->layers[l].proj_w, m->proj_pk[l], g->nh, (int)C, (int)C, 1.0f / m->proj[l].inv_scale);
+            MGPT_LAUNCH_CHECK();
         }
+        // attn_block_kernel's dynamic LDS limit is a per-device function attribute: set it for this model's device
+        // (C = 160 runs it in small calls only: the persistent attn160o_kernel below serves the large ones)
+        const int lds = fastk::attn_block_lds(NP, (int)C);
+        if constexpr (CT == 5) MGPT_HIP(set_max_lds(&fastk::attn_block_kernel<T, NP, 5, false, true>, lds));
+        else MGPT_HIP(set_max_lds_each(lds, &fastk::attn_block_kernel<T, NP, 2, false, false>, &fastk::attn_block_kernel<T, NP, 2, true, false>,
+                                       &fastk::attn_block_kernel<T, NP, 2, false, true>));
+        // (head_parts -- the heads' partial sums of small launches -- is allocated by the first small launch: forward_chunk)
+        if (CT != 5) return MGPT_OK;
+        // ... and the MLP block of the small launches: mlp160p_kernel's cyclic stream per layer and the scale c_fc * ln_2 was packed with
+        rc = pack_folded(m->mlp160_pk, m->mlp160_inv1, (size_t)fastk::kM5Period * 20 * NP * 512, false,
+                         [&](const LayerOff &lo, int l, uint16_t *pk, float sc1) {
+                             hipLaunchKernelGGL((fastk::pack_mlp160p_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kM5Period * 20 * 64, 256)), dim3(256), 0,
+                                                nullptr, P + lo.fc_w, P + lo.proj2_w, P + lo.ln2, pk, sc1, 1.0f / m->proj2[l].inv_scale);
+                         });
+        if (rc != MGPT_OK) return rc;
+        // the attention block as one persistent kernel (layers that neither gather the embedding nor are the last)
+        rc = pack_folded(m->attn160o_pk, m->attn160_inv, (size_t)fastk::kA160oPeriod * fastk::kA160oFrags * NP * 512, true,
+                         [&](const LayerOff &lo, int l, uint16_t *pk, float sca) {
+                             hipLaunchKernelGGL((fastk::pack_attn160o_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kA160oPeriod * fastk::kA160oFrags * 64, 256)),
+                                                dim3(256), 0, nullptr, P + lo.attn_w, P + lo.ln1, P + lo.proj_w, pk, sca, 1.0f / m->proj[l].inv_scale);
+                         });
+        if (rc != MGPT_OK) return rc;
+        MGPT_HIP(m->mem.alloc(&m->attn160o_spill, (size_t)m->n_cu * fastk::kA160oSpillPerWg<NP>));
+        MGPT_HIP(set_max_lds_each(fastk::kA160oLds<NP>, &fastk::attn160o_kernel<T, NP>, &fastk::attn160o_kernel<T, NP, true>));
+        if ((rc = ensure_embed_table(g)) != MGPT_OK) return rc;
+        MGPT_HIP(set_max_lds(&fastk::mlp160p_kernel<T, NP, 5>, fastk::kM5Lds<NP>));
+        MGPT_HIP(set_max_lds(&fastk::mlp160p_kernel<T, NP, 5, 2>, fastk::kM5Lds<NP, 2>));
+        MGPT_HIP(set_max_lds(&fastk::mlp160p_kernel<T, NP, 5, 1>, fastk::kM5Lds<NP, 1>));
+        return MGPT_OK;
     }
-    if (g->hs == 32 && (C == 256 || C == 160 || C == 64) && m->mlp_fused) {
-        // the last layer's attention block for token 255 alone (attn_last1_kernel): fp32 transposes of W_q, W_v and c_proj.weight
-        const LayerOff &lo = g->layers[g->L - 1];
-        // (also c_fc.weight and mlp.c_proj.weight transposed, for the one-launch last layer + head of small launches; C = 256 since round 5)
-        const bool tail = true;
-        MGPT_HIP(hipMalloc(&m->last1_wt, (size_t)(tail ? 11 : 3) * C * C * sizeof(float)));
+
+    // ---- the last layer's attention block for token 255 alone (attn_last1_kernel): fp32 transposes of W_q, W_v and c_proj.weight, and of
+    // c_fc.weight and mlp.c_proj.weight for the one-launch last layer + head of small launches ----
+    template <int C_>
+    int build_last1()
+    {
+        const LayerOff &lo = g->layers[L - 1];
+        MGPT_HIP(m->mem.alloc(&m->last1_wt, (size_t)11 * C * C * sizeof(float)));
         struct { size_t off; int rows, cols; size_t dst; } mats[5] = {
             {lo.attn_w, (int)C, (int)C, 0}, {lo.attn_w + (size_t)2 * C * C, (int)C, (int)C, (size_t)C * C}, {lo.proj_w, (int)C, (int)C, (size_t)2 * C * C},
             {lo.fc_w, (int)(4 * C), (int)C, (size_t)3 * C * C}, {lo.proj2_w, (int)C, (int)(4 * C), (size_t)7 * C * C}};
         ProfScope ps(P_PACK, nullptr);
-        for (int i = 0; i < (tail ? 5 : 3); i++) {
-            hipLaunchKernelGGL(fastk::transpose_kernel, dim3((unsigned)cdiv64((int64_t)mats[i].rows * mats[i].cols, 256)), dim3(256), 0, nullptr,
-                               g->params + mats[i].off, m->last1_wt + mats[i].dst, mats[i].rows, mats[i].cols);
+        for (const auto &mt : mats) {
+            hipLaunchKernelGGL(fastk::transpose_kernel, dim3((unsigned)cdiv64((int64_t)mt.rows * mt.cols, 256)), dim3(256), 0, nullptr,
+                               P + mt.off, m->last1_wt + mt.dst, mt.rows, mt.cols);
             MGPT_LAUNCH_CHECK();
         }
-#define MGPT_LAST1_LDS(C_, R_, TAIL_)                                                                                                          \
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn_last1_kernel<C_, 32, R_, TAIL_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 fastk::kLast1Lds<C_, R_, TAIL_>))
-        if (C == 256) { MGPT_LAST1_LDS(256, fastk::kLast1R, false); MGPT_LAST1_LDS(256, 1, false); MGPT_LAST1_LDS(256, 1, true); }
-        else if (C == 160) { MGPT_LAST1_LDS(160, fastk::kLast1R, false); MGPT_LAST1_LDS(160, 1, true); }
-        else { MGPT_LAST1_LDS(64, fastk::kLast1R, false); MGPT_LAST1_LDS(64, 1, true); }
-#undef MGPT_LAST1_LDS
+        MGPT_HIP(set_max_lds(&fastk::attn_last1_kernel<C_, 32, fastk::kLast1R, false>, fastk::kLast1Lds<C_, fastk::kLast1R, false>));
+        if constexpr (C_ == 256) MGPT_HIP(set_max_lds(&fastk::attn_last1_kernel<C_, 32, 1, false>, fastk::kLast1Lds<C_, 1, false>));   // (Plan::last1_row_per_wg)
+        MGPT_HIP(set_max_lds(&fastk::attn_last1_kernel<C_, 32, 1, true>, fastk::kLast1Lds<C_, 1, true>));
+        return MGPT_OK;
     }
-    m->pk_gemm = (C == 256 || C == 512 || C == 768 || C == 1024);
-    if (m->pk_gemm) {
-        auto pack = [&](std::vector<uint16_t *> &dst, size_t off, size_t R, size_t K, float scale, int l) -> int {
-            MGPT_HIP(hipMalloc(&dst[l], R * K * NP * sizeof(uint16_t)));
-            ProfScope ps(P_PACK, nullptr);
-            hipLaunchKernelGGL((fastk::pack_pk_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(R / 32) * (K / 16) * 64, 256)), dim3(256), 0,
-                               nullptr, g->params + off, dst[l], (int)R, (int)K, scale);
-            MGPT_LAUNCH_CHECK();
-            return MGPT_OK;
-        };
-        m->attn_pk2.assign(g->L, nullptr); m->proj_pk2.assign(g->L, nullptr); m->fc_pk2.assign(g->L, nullptr); m->proj2_pk2.assign(g->L, nullptr);
-        for (int l = 0; l < g->L; l++) {
+
+    // ---- C % 256 == 0 (FAM_PACKED; FAM_6M for its out-projection): pack_pk streams, the PK4 / PK16 attributes, the LayerNorm-fold packings ----
+    template <int EPI, int NWV, bool LNF, bool LUT>
+    hipError_t gemm_pk_max_lds()                // gemm_pk_kernel<.., NWV, 0, LNF> (LUT: with the Phi table slot behind the ring)
+    {
+        return set_max_lds(&fastk::gemm_pk_kernel<T, NP, EPI, NWV, 0, LNF>, fastk::gemm_pk_lds(NP, NWV, EPI) + fastk::gemm_pk_lds_extra(LNF, LUT));
+    }
+    template <int EPI, int NWV, bool LNF, bool LUT>
+    hipError_t gemm_pk16_max_lds()              // gemm_pk16_kernel<.., NWV, LNF>, one-plane mode only
+    {
+        return set_max_lds(&fastk::gemm_pk16_kernel<T, EPI, NWV, LNF>, fastk::gemm_pk_lds(NP, NWV, EPI) + fastk::gemm_pk_lds_extra(LNF, LUT));
+    }
+    // every (epilogue, folded LayerNorm) form with NWV waves; the residual epilogue has no folded form, the GELU one carries the Phi table
+    template <int NWV>
+    int gemm_pk_max_lds_all()
+    {
+        using namespace fastk;
+        MGPT_HIP((gemm_pk_max_lds<EPI_QK, NWV, false, false>()));
+        MGPT_HIP((gemm_pk_max_lds<EPI_VT, NWV, false, false>()));
+        MGPT_HIP((gemm_pk_max_lds<EPI_RESID, NWV, false, false>()));
+        MGPT_HIP((gemm_pk_max_lds<EPI_GELU, NWV, false, true>()));
+        MGPT_HIP((gemm_pk_max_lds<EPI_QK, NWV, true, false>()));
+        MGPT_HIP((gemm_pk_max_lds<EPI_VT, NWV, true, false>()));
+        MGPT_HIP((gemm_pk_max_lds<EPI_GELU, NWV, true, true>()));
+        if constexpr (NP == 1) {
+            MGPT_HIP((gemm_pk16_max_lds<EPI_QK, NWV, false, false>()));
+            MGPT_HIP((gemm_pk16_max_lds<EPI_VT, NWV, false, false>()));
+            MGPT_HIP((gemm_pk16_max_lds<EPI_RESID, NWV, false, false>()));
+            MGPT_HIP((gemm_pk16_max_lds<EPI_GELU, NWV, false, true>()));
+            MGPT_HIP((gemm_pk16_max_lds<EPI_QK, NWV, true, false>()));
+            MGPT_HIP((gemm_pk16_max_lds<EPI_VT, NWV, true, false>()));
+            MGPT_HIP((gemm_pk16_max_lds<EPI_GELU, NWV, true, true>()));
+        }
+        return MGPT_OK;
+    }
+
+    // one matrix [R][K] at `off` as a packed-fragment stream; gain_off != 0: times the LayerNorm gain there, with its column sums in *cs
+    int pack_pk(uint16_t **dst, size_t off, size_t R, size_t K, float scale, size_t gain_off = 0, float **cs = nullptr)
+    {
+        const float *gain = cs != nullptr ? P + gain_off : nullptr;
+        MGPT_HIP(m->mem.alloc(dst, R * K * NP * sizeof(uint16_t)));
+        if (cs != nullptr) MGPT_HIP(m->mem.alloc(cs, R * sizeof(float)));
+        ProfScope ps(P_PACK, nullptr);
+        hipLaunchKernelGGL((fastk::pack_pk_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(R / 32) * (K / 16) * 64, 256)), dim3(256), 0,
+                           nullptr, P + off, *dst, (int)R, (int)K, scale, gain);
+        MGPT_LAUNCH_CHECK();
+        if (cs == nullptr) return MGPT_OK;
+        hipLaunchKernelGGL((fastk::colsum_pk_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)R, 256)), dim3(256), 0, nullptr, P + off,
+                           gain, *cs, (int)R, (int)K, scale);
+        MGPT_LAUNCH_CHECK();
+        return MGPT_OK;
+    }
+
+    int build_packed()
+    {
+        int rc;
+        m->attn_pk2.assign(L, nullptr); m->proj_pk2.assign(L, nullptr); m->fc_pk2.assign(L, nullptr); m->proj2_pk2.assign(L, nullptr);
+        for (int l = 0; l < L; l++) {
             const LayerOff &lo = g->layers[l];
-            if ((rc = pack(m->attn_pk2, lo.attn_w, 3 * C, C, 1.0f / m->attn[l].inv_scale, l)) != MGPT_OK) return rc;
-            if ((rc = pack(m->proj_pk2, lo.proj_w, C, C, 1.0f / m->proj[l].inv_scale, l)) != MGPT_OK) return rc;
+            if ((rc = pack_pk(&m->attn_pk2[l], lo.attn_w, 3 * C, C, 1.0f / m->attn[l].inv_scale)) != MGPT_OK) return rc;
+            if ((rc = pack_pk(&m->proj_pk2[l], lo.proj_w, C, C, 1.0f / m->proj[l].inv_scale)) != MGPT_OK) return rc;
             if (!m->mlp_fused) {
-                if ((rc = pack(m->fc_pk2, lo.fc_w, 4 * C, C, 1.0f / m->fc[l].inv_scale, l)) != MGPT_OK) return rc;
-                if ((rc = pack(m->proj2_pk2, lo.proj2_w, C, 4 * C, 1.0f / m->proj2[l].inv_scale, l)) != MGPT_OK) return rc;
+                if ((rc = pack_pk(&m->fc_pk2[l], lo.fc_w, 4 * C, C, 1.0f / m->fc[l].inv_scale)) != MGPT_OK) return rc;
+                if ((rc = pack_pk(&m->proj2_pk2[l], lo.proj2_w, C, 4 * C, 1.0f / m->proj2[l].inv_scale)) != MGPT_OK) return rc;
             }
         }
-        const int lds = fastk::gemm_pk_lds(NP);
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_QK, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_VT, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_RESID, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_RESID, 4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     fastk::gemm_pk_lds(NP, 4, fastk::EPI_RESID)));
-        // the 128-row forms of the other epilogues (small calls of the C = 768 chain)
-#define MGPT_PK4(EPI_, LNF_, LUT_)                                                                                                                    \
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_, 4, 0, LNF_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 fastk::gemm_pk_lds(NP, 4, fastk::EPI_) + fastk::gemm_pk_lds_extra(LNF_, LUT_)))
-        MGPT_PK4(EPI_QK, false, false); MGPT_PK4(EPI_VT, false, false); MGPT_PK4(EPI_GELU, false, true);
-        MGPT_PK4(EPI_QK, true, false); MGPT_PK4(EPI_VT, true, false); MGPT_PK4(EPI_GELU, true, true);
-#undef MGPT_PK4
-        if constexpr (NP == 1) {
-#define MGPT_PK16(EPI_, NWV_, LNF_, LUT_)                                                                                                              \
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk16_kernel<T, fastk::EPI_, NWV_, LNF_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 fastk::gemm_pk_lds(NP, NWV_, fastk::EPI_) + fastk::gemm_pk_lds_extra(LNF_, LUT_)))
-            MGPT_PK16(EPI_QK, 8, false, false); MGPT_PK16(EPI_VT, 8, false, false); MGPT_PK16(EPI_RESID, 8, false, false); MGPT_PK16(EPI_GELU, 8, false, true);
-            MGPT_PK16(EPI_QK, 4, false, false); MGPT_PK16(EPI_VT, 4, false, false); MGPT_PK16(EPI_RESID, 4, false, false); MGPT_PK16(EPI_GELU, 4, false, true);
-            MGPT_PK16(EPI_QK, 8, true, false); MGPT_PK16(EPI_VT, 8, true, false); MGPT_PK16(EPI_GELU, 8, true, true);
-            MGPT_PK16(EPI_QK, 4, true, false); MGPT_PK16(EPI_VT, 4, true, false); MGPT_PK16(EPI_GELU, 4, true, true);
-#undef MGPT_PK16
-        }
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_GELU, 8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     lds + fastk::gemm_pk_lds_extra(false, true)));
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_QK, 8, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds + fastk::gemm_pk_lds_extra(true, false)));
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_VT, 8, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds + fastk::gemm_pk_lds_extra(true, false)));
-        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::gemm_pk_kernel<T, NP, fastk::EPI_GELU, 8, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     lds + fastk::gemm_pk_lds_extra(true, true)));
+        // 256-row tiles (8 waves), and the 128-row forms (4 waves: small calls of the C = 768 chain, the 6M shape's out-projection)
+        if ((rc = gemm_pk_max_lds_all<8>()) != MGPT_OK) return rc;
+        if ((rc = gemm_pk_max_lds_all<4>()) != MGPT_OK) return rc;
         if (!(C == 256 && m->mlp_fused && g->hs == 32 && g->nh == 8))      // LayerNorm planes of the GEMM chain (the 6M kernels normalise in registers)
-            MGPT_HIP(hipMalloc(&m->apk, (size_t)g->max_rows * kT * C * NP * sizeof(uint16_t)));
+            MGPT_HIP(m->mem.alloc(&m->apk, (size_t)g->max_rows * kT * C * NP * sizeof(uint16_t)));
         // one-plane mode of the full chain (no fused kernels): LayerNorm folded into the GEMMs (GemmArgs) -- ln_pack_kernel, which
         // re-reads every residual row to normalise it (8 % of an 85M step), runs once per forward instead of twice per layer
         // (MGPT_LN_FOLD=0 in the environment keeps the normalised planes: the raw planes round x itself to bf16, so a residual stream whose
         //  per-token mean is many times its standard deviation loses precision that LayerNorm-then-round keeps)
         const char *fold_env = getenv("MGPT_LN_FOLD");
         m->ln_fold = NP == 1 && !m->mlp_fused && m->apk != nullptr && !(fold_env != nullptr && fold_env[0] == '0');
-        if (m->ln_fold) {
-            m->attn_pk2g.assign(g->L, nullptr); m->fc_pk2g.assign(g->L, nullptr); m->attn_cs.assign(g->L, nullptr); m->fc_cs.assign(g->L, nullptr);
-            auto packg = [&](std::vector<uint16_t *> &dst, std::vector<float *> &cs, size_t off, size_t goff, size_t R, size_t K, float scale, int l) -> int {
-                MGPT_HIP(hipMalloc(&dst[l], R * K * NP * sizeof(uint16_t)));
-                MGPT_HIP(hipMalloc(&cs[l], R * sizeof(float)));
-                ProfScope ps(P_PACK, nullptr);
-                hipLaunchKernelGGL((fastk::pack_pk_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(R / 32) * (K / 16) * 64, 256)), dim3(256), 0,
-                                   nullptr, g->params + off, dst[l], (int)R, (int)K, scale, g->params + goff);
-                MGPT_LAUNCH_CHECK();
-                hipLaunchKernelGGL((fastk::colsum_pk_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)R, 256)), dim3(256), 0, nullptr, g->params + off,
-                                   g->params + goff, cs[l], (int)R, (int)K, scale);
-                MGPT_LAUNCH_CHECK();
-                return MGPT_OK;
-            };
-            for (int l = 0; l < g->L; l++) {
-                const LayerOff &lo = g->layers[l];
-                if ((rc = packg(m->attn_pk2g, m->attn_cs, lo.attn_w, lo.ln1, 3 * C, C, 1.0f / m->attn[l].inv_scale, l)) != MGPT_OK) return rc;
-                if ((rc = packg(m->fc_pk2g, m->fc_cs, lo.fc_w, lo.ln2, 4 * C, C, 1.0f / m->fc[l].inv_scale, l)) != MGPT_OK) return rc;
-            }
-            MGPT_HIP(hipMalloc(&m->ln_parts, (size_t)(C / 128) * g->max_rows * kT * sizeof(float2)));
-            // (the last layer's compact launch is padded to 256 rows and addresses token 255 of each: room and finite values for all of them)
-            const size_t n_mean = (size_t)((g->max_rows + 255) / 256) * 256 * kT;
-            MGPT_HIP(hipMalloc(&m->ln_mean, n_mean * sizeof(float)));
-            MGPT_HIP(hipMemset(m->ln_mean, 0, n_mean * sizeof(float)));
+        if (!m->ln_fold) return MGPT_OK;
+        m->attn_pk2g.assign(L, nullptr); m->fc_pk2g.assign(L, nullptr); m->attn_cs.assign(L, nullptr); m->fc_cs.assign(L, nullptr);
+        for (int l = 0; l < L; l++) {
+            const LayerOff &lo = g->layers[l];
+            if ((rc = pack_pk(&m->attn_pk2g[l], lo.attn_w, 3 * C, C, 1.0f / m->attn[l].inv_scale, lo.ln1, &m->attn_cs[l])) != MGPT_OK) return rc;
+            if ((rc = pack_pk(&m->fc_pk2g[l], lo.fc_w, 4 * C, C, 1.0f / m->fc[l].inv_scale, lo.ln2, &m->fc_cs[l])) != MGPT_OK) return rc;
         }
+        MGPT_HIP(m->mem.alloc(&m->ln_parts, (size_t)(C / 128) * g->max_rows * kT * sizeof(float2)));
+        // (the last layer's compact launch is padded to 256 rows and addresses token 255 of each: room and finite values for all of them)
+        const size_t n_mean = (size_t)((g->max_rows + 255) / 256) * 256 * kT;
+        MGPT_HIP(m->mem.alloc(&m->ln_mean, n_mean * sizeof(float)));
+        MGPT_HIP(hipMemset(m->ln_mean, 0, n_mean * sizeof(float)));
+        return MGPT_OK;
     }
+
+    // ---- every family: the compact last-layer rows, LayerNorm statistics, and the activation planes that are not kept on chip ----
+    int build_workspace()
     {
         const size_t nl = (size_t)((g->max_rows + 255) / 256) * 256 * C;
-        MGPT_HIP(hipMalloc(&m->x_last, nl * sizeof(float)));
+        MGPT_HIP(m->mem.alloc(&m->x_last, nl * sizeof(float)));
         MGPT_HIP(hipMemset(m->x_last, 0, nl * sizeof(float)));           // padding rows stay finite
         // chunk-major residual stream: the fused kernels (6M shape; 2M / tiny shapes with heads of 32) and the packed-fragment GEMM chain
         m->x_tiled = m->pk_gemm || (m->qkv_fused && g->hs == 32 && m->mlp_fused);
-        if (m->x_tiled) MGPT_HIP(hipMalloc(&m->x_head, nl * sizeof(float)));
+        if (m->x_tiled) MGPT_HIP(m->mem.alloc(&m->x_head, nl * sizeof(float)));
         if (m->pk_gemm) {
-            MGPT_HIP(hipMalloc(&m->y_last, nl * NP * sizeof(uint16_t)));
+            MGPT_HIP(m->mem.alloc(&m->y_last, nl * NP * sizeof(uint16_t)));
             MGPT_HIP(hipMemset(m->y_last, 0, nl * NP * sizeof(uint16_t)));
         }
-    }
-    const size_t M = (size_t)g->max_rows * kT;
-    MGPT_HIP(hipMalloc(&m->stats, M * sizeof(float2)));
-    // q|k and v^T planes exist in HBM only where the projection is a GEMM of its own: the fused attention kernels keep them on chip
-    const bool qkv_on_chip = m->attn256 || (m->qkv_fused && g->hs == 32 && m->mlp_fused);
-    for (int p = 0; p < NP; p++) {
-        if (!qkv_on_chip) {
-            MGPT_HIP(hipMalloc(&m->qk[p], 2 * M * C * sizeof(uint16_t)));
-            MGPT_HIP(hipMalloc(&m->vt[p], M * C * sizeof(uint16_t)));
+        const size_t M = (size_t)g->max_rows * kT;
+        MGPT_HIP(m->mem.alloc(&m->stats, M * sizeof(float2)));
+        // q|k and v^T planes exist in HBM only where the projection is a GEMM of its own: the fused attention kernels keep them on chip
+        const bool qkv_on_chip = m->attn256 || (m->qkv_fused && g->hs == 32 && m->mlp_fused);
+        for (int p = 0; p < NP; p++) {
+            if (!qkv_on_chip) {
+                MGPT_HIP(m->mem.alloc(&m->qk[p], 2 * M * C * sizeof(uint16_t)));
+                MGPT_HIP(m->mem.alloc(&m->vt[p], M * C * sizeof(uint16_t)));
+            }
+            if (m->pk_gemm && p > 0) continue;                                   // PK buffers interleave the planes in [0]
+            MGPT_HIP(m->mem.alloc(&m->y[p], M * C * (m->pk_gemm ? NP : 1) * sizeof(uint16_t)));
+            if (!m->mlp_fused) MGPT_HIP(m->mem.alloc(&m->hbuf[p], 4 * M * C * (m->pk_gemm ? NP : 1) * sizeof(uint16_t)));
         }
-        if (m->pk_gemm && p > 0) continue;                                   // PK buffers interleave the planes in [0]
-        MGPT_HIP(hipMalloc(&m->y[p], M * C * (m->pk_gemm ? NP : 1) * sizeof(uint16_t)));
-        if (!m->mlp_fused) MGPT_HIP(hipMalloc(&m->hbuf[p], 4 * M * C * (m->pk_gemm ? NP : 1) * sizeof(uint16_t)));
+        return MGPT_OK;
     }
-    MGPT_HIP(hipDeviceSynchronize());
-    m->built = true;
-    return MGPT_OK;
+
+    // the sequence; the flags are what make_plan reads its family from
+    int build()
+    {
+        g->generation++;                                     // a step graph captured before this build must not be replayed as is
+        int rc;
+        if ((rc = build_planes()) != MGPT_OK) return rc;
+        // (C = 256: the fused kernels are the 6M shape's -- 8 heads of 32 -- and share the chunk-major residual stream; any other
+        //  C = 256 model takes the packed-fragment GEMM chain)
+        m->mlp_fused = (C == 160 || C == 64 || (C == 256 && g->hs == 32 && g->nh == 8));
+        if (C == 256 && m->mlp_fused) rc = build_6m();
+        else if (C == 160) rc = build_register<5>();
+        else if (C == 64) rc = build_register<2>();
+        if (rc != MGPT_OK) return rc;
+        if (g->hs == 32 && m->mlp_fused) rc = C == 256 ? build_last1<256>() : C == 160 ? build_last1<160>() : build_last1<64>();
+        if (rc != MGPT_OK) return rc;
+        m->pk_gemm = (C == 256 || C == 512 || C == 768 || C == 1024);
+        if (m->pk_gemm && (rc = build_packed()) != MGPT_OK) return rc;
+        if ((rc = build_workspace()) != MGPT_OK) return rc;
+        MGPT_HIP(hipDeviceSynchronize());
+        m->built = true;
+        return MGPT_OK;
+    }
+};
+
+template <class T, int NP>
+int build_mode(mgpt_gpt *g, ModeState *m, bool f16)
+{
+    ModeBuilder<T, NP> b = {g, m, f16};
+    return b.build();
 }
 
 void free_mode(mgpt_gpt *g, ModeState *m)
 {
     if (m->built) g->generation++;                       // captured step graphs hold these pointers
-    auto fr = [](std::vector<PlaneSet> &v) { for (auto &p : v) { (void)hipFree(p.hi); (void)hipFree(p.lo); } v.clear(); };
-    fr(m->attn); fr(m->proj); fr(m->fc); fr(m->proj2);
-    for (auto *p : m->mlp_pk) (void)hipFree(p);
-    for (auto *p : m->mlp16_pk) (void)hipFree(p);
-    for (auto *p : m->mlp256_pk) (void)hipFree(p);
-    for (auto *p : m->mlp256q_pk) (void)hipFree(p);
-    for (auto *p : m->mlp256_lut) (void)hipFree(p);
-    for (auto *p : m->attn256_pk) (void)hipFree(p);
-    for (auto *p : m->attn256q_pk) (void)hipFree(p);
-    (void)hipFree(m->attn256q_spill);
-    (void)hipFree(m->l0_table);
-    (void)hipFree(m->gelu_lut);
-    for (auto *p : m->qkv_pk) (void)hipFree(p);
-    for (auto *p : m->proj_pk) (void)hipFree(p);
-    for (auto *v : {&m->attn_pk2, &m->proj_pk2, &m->fc_pk2, &m->proj2_pk2}) for (auto *p : *v) (void)hipFree(p);
-    (void)hipFree(m->apk);
-    (void)hipFree(m->stats);
-    (void)hipFree(m->x_last);
-    (void)hipFree(m->x_head);
-    (void)hipFree(m->y_last);
-    (void)hipFree(m->head_parts);
-    (void)hipFree(m->last1_wt);
-    for (auto p : m->attn_pk2g) (void)hipFree(p);
-    for (auto p : m->fc_pk2g) (void)hipFree(p);
-    for (auto p : m->attn_cs) (void)hipFree(p);
-    for (auto p : m->fc_cs) (void)hipFree(p);
-    (void)hipFree(m->ln_parts);
-    (void)hipFree(m->ln_mean);
-    for (auto p : m->attn160o_pk) (void)hipFree(p);
-    (void)hipFree(m->attn160o_spill);
-    for (auto *p : m->mlp160_pk) (void)hipFree(p);
-    for (int p = 0; p < 2; p++) { (void)hipFree(m->qk[p]); (void)hipFree(m->vt[p]); (void)hipFree(m->y[p]); (void)hipFree(m->hbuf[p]); }
+    m->mem.release();
     *m = ModeState();
 }
 
@@ -694,7 +697,7 @@ struct Chunk {
     int ensure_head_parts()
     {
         if (!p.head_par || m->head_parts != nullptr) return MGPT_OK;
-        MGPT_HIP(hipMalloc(&m->head_parts, (size_t)g->nh * (size_t)p.part_stride * sizeof(float)));
+        MGPT_HIP(m->mem.alloc(&m->head_parts, (size_t)g->nh * (size_t)p.part_stride * sizeof(float)));
         g->generation++;
         return MGPT_OK;
     }
@@ -1029,8 +1032,7 @@ int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, 
 template <class T, int NP, int HS>
 int raise_attn_lds()
 {
-    MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&fastk::attn16_kernel<T, NP, HS>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, fastk::attn16_lds(NP, HS)));
+    MGPT_HIP(set_max_lds(&fastk::attn16_kernel<T, NP, HS>, fastk::attn16_lds(NP, HS)));
     return MGPT_OK;
 }
 
@@ -1042,7 +1044,7 @@ int gpt_fast_finalize(mgpt_gpt *g)
     FastState *f = static_cast<FastState *>(g->fast);
     if (f) {                                             // parameters changed: planes are rebuilt lazily
         for (auto &m : f->mode) free_mode(g, &m);
-        (void)hipFree(g->embed_table);                   // ... and so is the (position, token) table of layer 0
+        g->embed_mem.release();                          // ... and so is the (position, token) table of layer 0
         g->embed_table = nullptr;
     } else {
         g->fast = new FastState();
@@ -1057,7 +1059,7 @@ void gpt_fast_destroy(mgpt_gpt *g)
     for (auto &m : f->mode) free_mode(g, &m);
     delete f;
     g->fast = nullptr;
-    (void)hipFree(g->embed_table);
+    g->embed_mem.release();
     g->embed_table = nullptr;
 }
 

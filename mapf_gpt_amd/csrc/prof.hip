@@ -86,7 +86,14 @@ using namespace mgpt;
 
 extern "C" const char *mgpt_last_error(void) { return g_err; }
 
-extern "C" int mgpt_abi_version(void) { return 1002; }
+extern "C" int mgpt_abi_version(void) { return 1003; }
+
+extern "C" int mgpt_mem_debug(int64_t *live_allocs, int64_t *live_bytes)
+{
+    if (live_allocs) *live_allocs = MemCounters::allocs.load();
+    if (live_bytes) *live_bytes = MemCounters::bytes.load();
+    return MGPT_OK;
+}
 
 extern "C" int mgpt_device_count(int *count)
 {

@@ -51,11 +51,14 @@ struct mgpt_step {
     bool retire = false;
     int n_inst = 0, n_agents = 0;
     int n_live = 0;                             // live instances at the last poll (host copy: sizes the forward until the next poll)
-    int32_t *d_live = nullptr;                  // [n_inst] ids of the live instances, ascending; -1 beyond the count
-    int32_t *d_count = nullptr;                 // device copy of n_live
-    int32_t *h_count = nullptr;                 // pinned: the poll's read-back
-    uint8_t *d_ctokens = nullptr;               // [rows][256] token rows of the live instances, compact
-    float *d_clogits = nullptr;                 // [rows][67] their logits
+    struct Retire {                             // owned by retire_mem
+        int32_t *d_live = nullptr;              // [n_inst] ids of the live instances, ascending; -1 beyond the count
+        int32_t *d_count = nullptr;             // device copy of n_live
+        int32_t *h_count = nullptr;             // pinned: the poll's read-back
+        uint8_t *d_ctokens = nullptr;           // [rows][256] token rows of the live instances, compact
+        float *d_clogits = nullptr;             // [rows][67] their logits
+    } rt;
+    DeviceArena mem, retire_mem;                // d_step; rt
 };
 
 namespace {
@@ -133,20 +136,19 @@ int act_live(mgpt_step *st, const uint8_t *d_tokens, int32_t *d_actions, hipStre
 {
     if (st->n_live == 0) return MGPT_OK;
     const int live_rows = st->n_live * st->n_agents;
-    hipLaunchKernelGGL(gather_live_rows_kernel, dim3(cdiv(live_rows, 16)), dim3(256), 0, s, (const uint4 *)d_tokens, st->d_live, st->d_count,
-                       st->n_agents, st->n_inst, (uint4 *)st->d_ctokens);
+    hipLaunchKernelGGL(gather_live_rows_kernel, dim3(cdiv(live_rows, 16)), dim3(256), 0, s, (const uint4 *)d_tokens, st->rt.d_live, st->rt.d_count,
+                       st->n_agents, st->n_inst, (uint4 *)st->rt.d_ctokens);
     MGPT_LAUNCH_CHECK();
-    int rc = mgpt_gpt_forward(st->gpt, st->d_ctokens, live_rows, st->d_clogits, st->precision, s);
+    int rc = mgpt_gpt_forward(st->gpt, st->rt.d_ctokens, live_rows, st->rt.d_clogits, st->precision, s);
     if (rc != MGPT_OK) return rc;
-    return sample_actions_live(st->d_clogits, st->d_live, st->d_count, st->n_agents, st->n_inst, live_rows, d_actions, st->do_sample, st->seed, 0,
+    return sample_actions_live(st->rt.d_clogits, st->rt.d_live, st->rt.d_count, st->n_agents, st->n_inst, live_rows, d_actions, st->do_sample, st->seed, 0,
                                st->d_step, st->row0, s);
 }
 
 void free_retire(mgpt_step *st)
 {
-    (void)hipFree(st->d_live); (void)hipFree(st->d_count); (void)hipFree(st->d_ctokens); (void)hipFree(st->d_clogits);
-    if (st->h_count) (void)hipHostFree(st->h_count);
-    st->d_live = nullptr; st->d_count = nullptr; st->h_count = nullptr; st->d_ctokens = nullptr; st->d_clogits = nullptr;
+    st->retire_mem.release();
+    st->rt = mgpt_step::Retire();
     st->retire = false; st->n_live = 0;
 }
 
@@ -191,12 +193,11 @@ extern "C" int mgpt_step_create(mgpt_step **out, mgpt_tokenizer *tok, mgpt_gpt *
     st->seed = seed; st->row0 = row0;
     int rc = mgpt_env_state(env, &st->d_pos, &st->d_goal, nullptr);
     if (rc != MGPT_OK) { delete st; return rc; }
-    hipError_t e = hipMalloc(&st->d_step, sizeof(uint64_t));
+    hipError_t e = st->mem.alloc(&st->d_step, sizeof(uint64_t));
     if (e == hipSuccess) e = hipMemset(st->d_step, 0, sizeof(uint64_t));
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&st->cap_stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
-        set_error("hipMalloc / hipStreamCreate failed in mgpt_step_create: %s", hipGetErrorString(e));
-        (void)hipFree(st->d_step);
+        set_error("device allocation / hipStreamCreate failed in mgpt_step_create: %s", hipGetErrorString(e));
         delete st;
         return MGPT_ERR_HIP;
     }
@@ -210,7 +211,6 @@ extern "C" int mgpt_step_destroy(mgpt_step *st)
     drop_graph(st);
     free_retire(st);
     if (st->cap_stream) (void)hipStreamDestroy(st->cap_stream);
-    (void)hipFree(st->d_step);
     delete st;
     return MGPT_OK;
 }
@@ -222,7 +222,7 @@ extern "C" int mgpt_step_reset(mgpt_step *st, uint64_t step0, void *stream)
     hipLaunchKernelGGL(set_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, st->d_step, step0);
     MGPT_LAUNCH_CHECK();
     if (st->retire) {        // a new episode: every instance is live until the next poll says otherwise
-        hipLaunchKernelGGL(live_all_kernel, dim3(cdiv(st->n_inst, 256)), dim3(256), 0, (hipStream_t)stream, st->d_live, st->d_count, st->n_inst);
+        hipLaunchKernelGGL(live_all_kernel, dim3(cdiv(st->n_inst, 256)), dim3(256), 0, (hipStream_t)stream, st->rt.d_live, st->rt.d_count, st->n_inst);
         MGPT_LAUNCH_CHECK();
         st->n_live = st->n_inst;
     }
@@ -233,7 +233,7 @@ extern "C" int mgpt_step_set_retire(mgpt_step *st, int enable)
 {
     MGPT_REQUIRE(st, MGPT_ERR_ARG, "NULL argument");
     if (!enable) {
-        if (st->retire) free_retire(st);          // (hipFree waits for the work that still reads the buffers)
+        if (st->retire) free_retire(st);          // (freeing waits for the work that still reads the buffers)
         return MGPT_OK;
     }
     if (st->retire) return MGPT_OK;
@@ -241,16 +241,17 @@ extern "C" int mgpt_step_set_retire(mgpt_step *st, int enable)
     env_shape(st->env, &st->n_inst, &st->n_agents);
     MGPT_REQUIRE((int64_t)st->n_inst * st->n_agents == st->rows, MGPT_ERR_ARG, "the step has %d rows, its env %d x %d", st->rows, st->n_inst,
                  st->n_agents);
-    hipError_t e = hipMalloc(&st->d_live, (size_t)st->n_inst * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&st->d_count, sizeof(int32_t));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&st->h_count, sizeof(int32_t), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc(&st->d_ctokens, (size_t)st->rows * MGPT_CONTEXT);
-    if (e == hipSuccess) e = hipMalloc(&st->d_clogits, (size_t)st->rows * MGPT_VOCAB * sizeof(float));
+    DeviceArena &rm = st->retire_mem;
+    hipError_t e = rm.alloc(&st->rt.d_live, (size_t)st->n_inst * sizeof(int32_t));
+    if (e == hipSuccess) e = rm.alloc(&st->rt.d_count, sizeof(int32_t));
+    if (e == hipSuccess) e = rm.alloc_host(&st->rt.h_count, sizeof(int32_t));
+    if (e == hipSuccess) e = rm.alloc(&st->rt.d_ctokens, (size_t)st->rows * MGPT_CONTEXT);
+    if (e == hipSuccess) e = rm.alloc(&st->rt.d_clogits, (size_t)st->rows * MGPT_VOCAB * sizeof(float));
     if (e == hipSuccess) {                        // all live, as after mgpt_step_reset
         std::vector<int32_t> ids((size_t)st->n_inst);
         for (int i = 0; i < st->n_inst; i++) ids[(size_t)i] = i;
-        e = hipMemcpy(st->d_live, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(st->d_count, &st->n_inst, sizeof(int32_t), hipMemcpyHostToDevice);
+        e = hipMemcpy(st->rt.d_live, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(st->rt.d_count, &st->n_inst, sizeof(int32_t), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
         set_error("allocation failed in mgpt_step_set_retire: %s", hipGetErrorString(e));
@@ -270,10 +271,10 @@ extern "C" int mgpt_step_poll_live(mgpt_step *st, int *n_live, void *stream)
     const uint8_t *d_done = nullptr;
     int rc = mgpt_env_state(st->env, nullptr, nullptr, &d_done);
     if (rc != MGPT_OK) return rc;
-    if ((rc = launch_live_list(d_done, st->n_inst, st->d_live, st->d_count, s)) != MGPT_OK) return rc;
-    MGPT_HIP(hipMemcpyAsync(st->h_count, st->d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if ((rc = launch_live_list(d_done, st->n_inst, st->rt.d_live, st->rt.d_count, s)) != MGPT_OK) return rc;
+    MGPT_HIP(hipMemcpyAsync(st->rt.h_count, st->rt.d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     MGPT_HIP(hipStreamSynchronize(s));
-    st->n_live = *st->h_count;
+    st->n_live = *st->rt.h_count;
     MGPT_REQUIRE(st->n_live >= 0 && st->n_live <= st->n_inst, MGPT_ERR_STATE, "live count %d outside 0 .. %d", st->n_live, st->n_inst);
     if (n_live) *n_live = st->n_live;
     return MGPT_OK;
@@ -284,9 +285,9 @@ extern "C" int mgpt_step_copy_live(mgpt_step *st, int32_t *d_live_out, float *d_
     MGPT_REQUIRE(st, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(st->retire, MGPT_ERR_STATE, "retire mode is off");
     hipStream_t s = (hipStream_t)stream;
-    if (d_live_out) MGPT_HIP(hipMemcpyAsync(d_live_out, st->d_live, (size_t)st->n_inst * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (d_live_out) MGPT_HIP(hipMemcpyAsync(d_live_out, st->rt.d_live, (size_t)st->n_inst * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     if (d_logits_out)
-        MGPT_HIP(hipMemcpyAsync(d_logits_out, st->d_clogits, (size_t)st->rows * MGPT_VOCAB * sizeof(float), hipMemcpyDeviceToDevice, s));
+        MGPT_HIP(hipMemcpyAsync(d_logits_out, st->rt.d_clogits, (size_t)st->rows * MGPT_VOCAB * sizeof(float), hipMemcpyDeviceToDevice, s));
     return MGPT_OK;
 }
 
@@ -305,7 +306,7 @@ extern "C" int mgpt_step_run(mgpt_step *st, uint8_t *d_tokens, int32_t *d_action
     hipStream_t s = (hipStream_t)stream;
     const int gmc = goals_may_change ? 1 : 0;
     // one of OUR contexts re-allocated or freed device memory since our last step (weights reloaded -> planes freed and rebuilt lazily,
-    // goal queues replaced): the graph holds dead pointers, and the rebuild (hipMalloc, synchronous copies, null-stream pack
+    // goal queues replaced): the graph holds dead pointers, and the rebuild (allocations, synchronous copies, null-stream pack
     // kernels) must not happen inside a capture -> drop the graph and run one eager step first
     if (gpt_generation(st->gpt) != st->seen_gpt_gen || env_generation(st->env) != st->seen_env_gen) {
         drop_graph(st);

@@ -832,6 +832,7 @@ struct mgpt_tokenizer {
     uint8_t *dirty = nullptr;
     uint2 *hdrs = nullptr;              // per agent: row_header (position, window origin, flags), kept by create / update for tokens_kernel
     bool have_grids = false, have_agents = false;
+    DeviceArena mem;                    // every device pointer above
 };
 
 void mgpt::tok_view(const mgpt_tokenizer *t, TokView *out)
@@ -882,17 +883,17 @@ extern "C" int mgpt_tokenizer_create(mgpt_tokenizer **out, const mgpt_input_para
             return MGPT_ERR_UNSUPPORTED;
         }
     const size_t cells = (size_t)H * W, total = (size_t)n_inst * n_agents;
-    hipError_t e = hipMalloc(&t->grids, (size_t)n_grids * cells);
-    if (e == hipSuccess) e = hipMalloc(&t->dist, total * cells * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMalloc(&t->dist8, total * cells);
-    if (e == hipSuccess) e = hipMalloc(&t->u8_ok, sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&t->recs, total * sizeof(AgentRec));
-    if (e == hipSuccess) e = hipMalloc(&t->dirty, total);
-    if (e == hipSuccess) e = hipMalloc(&t->hdrs, (total + 64) * sizeof(uint2));     // (+ 64: a wave's scalar loads of its rows' headers may run past the last agent)
+    hipError_t e = t->mem.alloc(&t->grids, (size_t)n_grids * cells);
+    if (e == hipSuccess) e = t->mem.alloc(&t->dist, total * cells * sizeof(uint16_t));
+    if (e == hipSuccess) e = t->mem.alloc(&t->dist8, total * cells);
+    if (e == hipSuccess) e = t->mem.alloc(&t->u8_ok, sizeof(int));
+    if (e == hipSuccess) e = t->mem.alloc(&t->recs, total * sizeof(AgentRec));
+    if (e == hipSuccess) e = t->mem.alloc(&t->dirty, total);
+    if (e == hipSuccess) e = t->mem.alloc(&t->hdrs, (total + 64) * sizeof(uint2));     // (+ 64: a wave's scalar loads of its rows' headers may run past the last agent)
     if (e == hipSuccess) e = hipMemset(t->hdrs, 0, (total + 64) * sizeof(uint2));
     if (e != hipSuccess) {
-        set_error("hipMalloc failed in mgpt_tokenizer_create: %s", hipGetErrorString(e));
-        mgpt_tokenizer_destroy(t);
+        set_error("device allocation failed in mgpt_tokenizer_create: %s", hipGetErrorString(e));
+        delete t;
         return MGPT_ERR_HIP;
     }
     *out = t;
@@ -901,10 +902,7 @@ extern "C" int mgpt_tokenizer_create(mgpt_tokenizer **out, const mgpt_input_para
 
 extern "C" int mgpt_tokenizer_destroy(mgpt_tokenizer *t)
 {
-    if (!t) return MGPT_OK;
-    (void)hipFree(t->grids); (void)hipFree(t->dist); (void)hipFree(t->dist8); (void)hipFree(t->u8_ok);
-    (void)hipFree(t->recs); (void)hipFree(t->dirty); (void)hipFree(t->hdrs);
-    delete t;
+    delete t;                                            // (its arena frees what it holds)
     return MGPT_OK;
 }
 
@@ -1061,6 +1059,7 @@ struct mgpt_dataset {
     uint16_t *allpairs = nullptr;       // [H*W][H*W]
     AgentRec *recs = nullptr;           // scratch, grows
     size_t recs_cap = 0;
+    DeviceArena mem, recs_mem;          // allpairs; recs
 };
 
 extern "C" int mgpt_dataset_create(mgpt_dataset **out, const uint8_t *d_grid, int H, int W, void *stream)
@@ -1073,11 +1072,12 @@ extern "C" int mgpt_dataset_create(mgpt_dataset **out, const uint8_t *d_grid, in
     d->H = H; d->W = W;
     const int cells = H * W;
     AgentRec *src = nullptr;
-    hipError_t e = hipMalloc(&d->allpairs, (size_t)cells * cells * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMalloc(&src, (size_t)cells * sizeof(AgentRec));
+    DeviceArena tmp;                                      // src: freed when this call returns, after the stream synchronise below
+    hipError_t e = d->mem.alloc(&d->allpairs, (size_t)cells * cells * sizeof(uint16_t));
+    if (e == hipSuccess) e = tmp.alloc(&src, (size_t)cells * sizeof(AgentRec));
     if (e != hipSuccess) {
-        set_error("hipMalloc failed in mgpt_dataset_create: %s", hipGetErrorString(e));
-        (void)hipFree(src); (void)hipFree(d->allpairs); delete d;
+        set_error("device allocation failed in mgpt_dataset_create: %s", hipGetErrorString(e));
+        delete d;
         return MGPT_ERR_HIP;
     }
     hipLaunchKernelGGL(ds_sources_kernel, dim3(cdiv(cells, 256)), dim3(256), 0, s, src, cells, W);
@@ -1088,11 +1088,10 @@ extern "C" int mgpt_dataset_create(mgpt_dataset **out, const uint8_t *d_grid, in
                            d->allpairs, (uint8_t *)nullptr, (int *)nullptr);
     }
     hipError_t le = hipGetLastError();
-    hipError_t se = hipStreamSynchronize(s);              // `src` is freed below
-    (void)hipFree(src);
+    hipError_t se = hipStreamSynchronize(s);              // `src` is freed on return
     if (le != hipSuccess || se != hipSuccess) {
         set_error("mgpt_dataset_create: %s", hipGetErrorString(le != hipSuccess ? le : se));
-        (void)hipFree(d->allpairs); delete d;
+        delete d;
         return MGPT_ERR_HIP;
     }
     *out = d;
@@ -1101,9 +1100,7 @@ extern "C" int mgpt_dataset_create(mgpt_dataset **out, const uint8_t *d_grid, in
 
 extern "C" int mgpt_dataset_destroy(mgpt_dataset *d)
 {
-    if (!d) return MGPT_OK;
-    (void)hipFree(d->allpairs); (void)hipFree(d->recs);
-    delete d;
+    delete d;                                            // (its arenas free what it holds)
     return MGPT_OK;
 }
 
@@ -1121,9 +1118,9 @@ extern "C" int mgpt_dataset_tokenize_ex(mgpt_dataset *d, int n_agents, int n_ste
     const size_t total = (size_t)n_agents * n_steps;
     if (total > d->recs_cap) {
         MGPT_HIP(hipStreamSynchronize(s));
-        (void)hipFree(d->recs);
+        d->recs_mem.release();
         d->recs = nullptr; d->recs_cap = 0;
-        MGPT_HIP(hipMalloc(&d->recs, total * sizeof(AgentRec)));
+        MGPT_HIP(d->recs_mem.alloc(&d->recs, total * sizeof(AgentRec)));
         d->recs_cap = total;
     }
     {

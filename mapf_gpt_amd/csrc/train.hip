@@ -49,28 +49,19 @@ struct TrainState {
     trk::Blk *blk = nullptr;
     int n_blk = 0;
     double *norm_part = nullptr;
-    std::vector<void *> allocs;             // gradients, AdamW state and bookkeeping: live as long as the workspace
-    std::vector<void *> act_allocs;         // activations and backward scratch of max_rows rows: re-sized by mgpt_gpt_train_alloc
+    DeviceArena mem;                        // gradients, AdamW state and bookkeeping (h_cnt included): live as long as the workspace
+    DeviceArena act_mem;                    // activations and backward scratch of max_rows rows: re-sized by mgpt_gpt_train_alloc
 };
 
 TrainState *ts(mgpt_gpt *g) { return static_cast<TrainState *>(g->train); }
 
 void free_activations(TrainState *t)
 {
-    for (void *p : t->act_allocs) (void)hipFree(p);
-    t->act_allocs.clear();
+    t->act_mem.release();
     t->X.clear(); t->XN1.clear(); t->QKV.clear(); t->Y.clear(); t->XM.clear(); t->XN2.clear(); t->A.clear();
     t->max_rows = 0;
     t->M = 0;
     t->part_elems = 0;
-}
-
-void free_state(TrainState *t)
-{
-    free_activations(t);
-    for (void *p : t->allocs) (void)hipFree(p);
-    if (t->h_cnt) (void)hipHostFree(t->h_cnt);
-    delete t;
 }
 
 struct TensorInfo {
@@ -152,7 +143,7 @@ int raise_attn_lds()
         {reinterpret_cast<const void *>(&trk::attn_bwd_kv_kernel<HS, 1>), trk::attn_bwd_kv_lds<HS>()},
         {reinterpret_cast<const void *>(&tbk::attn_fwd_bf16_kernel<HS>), tbk::attn_fwd_lds<HS>()},
         {reinterpret_cast<const void *>(&tbk::attn_bwd_bf16_kernel<HS>), tbk::attn_bwd_lds<HS>()}};
-    for (const auto &k : kernels) MGPT_HIP(hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.second));
+    for (const auto &k : kernels) MGPT_HIP(set_max_lds(k.first, (int)k.second));
     return MGPT_OK;
 }
 
@@ -407,7 +398,7 @@ int require_train(mgpt_gpt *g)
 
 void gpt_train_destroy(mgpt_gpt *g)
 {
-    if (g->train) free_state(ts(g));
+    delete ts(g);                           // (its arenas free the workspace)
     g->train = nullptr;
 }
 
@@ -433,20 +424,19 @@ extern "C" int mgpt_gpt_train_alloc(mgpt_gpt *g, int max_rows)
         MGPT_TRY(g->hs == 32 ? raise_attn_lds<32>() : raise_attn_lds<64>());
         t = new TrainState();
     }
-    auto alloc_in = [&](std::vector<void *> &owner, size_t bytes) -> void * {
+    auto alloc_in = [&](DeviceArena &owner, size_t bytes) -> void * {
         void *p = nullptr;
-        if (e == hipSuccess) e = hipMalloc(&p, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess) owner.push_back(p);
-        return e == hipSuccess ? p : nullptr;
+        if (e == hipSuccess) e = owner.alloc(&p, std::max<size_t>(bytes, 16));
+        return p;
     };
     const int64_t M = (int64_t)max_rows * kT, C = g->C;
     const int L = g->L;
     const size_t nt = 3 + 6 * (size_t)L;
     if (fresh) {
-        auto fp = [&](int64_t n) { return static_cast<float *>(alloc_in(t->allocs, (size_t)n * sizeof(float))); };
+        auto fp = [&](int64_t n) { return static_cast<float *>(alloc_in(t->mem, (size_t)n * sizeof(float))); };
         t->grads = fp(g->n_params); t->exp_avg = fp(g->n_params); t->exp_avg_sq = fp(g->n_params); t->steps = fp(nt);
-        t->cnt = static_cast<int32_t *>(alloc_in(t->allocs, 2 * sizeof(int32_t)));
-        t->loss_acc = static_cast<double *>(alloc_in(t->allocs, sizeof(double)));
+        t->cnt = static_cast<int32_t *>(alloc_in(t->mem, 2 * sizeof(int32_t)));
+        t->loss_acc = static_cast<double *>(alloc_in(t->mem, sizeof(double)));
         t->coef = fp(1);
         std::vector<trk::Blk> blk;
         const std::vector<TensorInfo> tt = tensor_table(g);
@@ -454,21 +444,21 @@ extern "C" int mgpt_gpt_train_alloc(mgpt_gpt *g, int max_rows)
             for (size_t b = 0; b < tt[i].count; b += trk::kChunk)
                 blk.push_back({(int64_t)(tt[i].off + b), (int64_t)(tt[i].off + std::min(tt[i].count, b + trk::kChunk)), (int)i, tt[i].decay});
         t->n_blk = (int)blk.size();
-        t->blk = static_cast<trk::Blk *>(alloc_in(t->allocs, blk.size() * sizeof(trk::Blk)));
-        t->norm_part = static_cast<double *>(alloc_in(t->allocs, blk.size() * sizeof(double)));
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&t->h_cnt), 2 * sizeof(int32_t), hipHostMallocDefault);
+        t->blk = static_cast<trk::Blk *>(alloc_in(t->mem, blk.size() * sizeof(trk::Blk)));
+        t->norm_part = static_cast<double *>(alloc_in(t->mem, blk.size() * sizeof(double)));
+        if (e == hipSuccess) e = t->mem.alloc_host(&t->h_cnt, 2 * sizeof(int32_t));
         if (e == hipSuccess) e = hipMemcpy(t->blk, blk.data(), blk.size() * sizeof(trk::Blk), hipMemcpyHostToDevice);
         for (float *p : {t->grads, t->exp_avg, t->exp_avg_sq})
             if (e == hipSuccess) e = hipMemset(p, 0, g->n_params * sizeof(float));
         if (e == hipSuccess) e = hipMemset(t->steps, 0, nt * sizeof(float));
         if (e != hipSuccess) {
             set_error("training workspace allocation failed: %s", hipGetErrorString(e));
-            free_state(t);
+            delete t;
             return MGPT_ERR_HIP;
         }
         g->train = t;
     }
-    auto fa = [&](int64_t n) { return static_cast<float *>(alloc_in(t->act_allocs, (size_t)n * sizeof(float))); };
+    auto fa = [&](int64_t n) { return static_cast<float *>(alloc_in(t->act_mem, (size_t)n * sizeof(float))); };
     for (int l = 0; l < L; l++) {
         t->X.push_back(fa(M * C)); t->XN1.push_back(fa(M * C)); t->QKV.push_back(fa(3 * M * C)); t->Y.push_back(fa(M * C));
         t->XM.push_back(fa(M * C)); t->XN2.push_back(fa(M * C)); t->A.push_back(fa(4 * M * C));

@@ -35,7 +35,7 @@ def test_library_exports_every_declared_symbol(L):
 
 
 def test_version_and_error_string(L):
-    assert L.mgpt_abi_version() == 1002
+    assert L.mgpt_abi_version() == 1003
     rc = L.mgpt_gpt_create(None, 1, 1, 32, 256, 1)
     assert rc == _lib.ERR_ARG and b"NULL" in L.mgpt_last_error()
 
@@ -67,3 +67,42 @@ def test_no_cpu_fallback():
     from mapf_gpt_amd.inference import MAPFGPTInference, MAPFGPTInferenceConfig
     with pytest.raises(RuntimeError):
         MAPFGPTInference(MAPFGPTInferenceConfig(path_to_weights="synthetic:tiny"))
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="only meaningful on a box without a GPU")
+def test_failed_create_leaves_nothing_behind(L):
+    """Without a device every create with valid arguments fails at its first allocation: ERR_HIP, a NULL handle, and nothing
+    left in the arenas (mgpt_mem_debug)."""
+    assert _lib.mem_debug() == (0, 0)
+    cfg = _lib.InputParametersStruct(20, 13, 5, 256, 5, 5, 64, 0)
+    grid = np.zeros((20, 20), np.uint8)
+    creates = {
+        "env": lambda h: L.mgpt_env_create(ctypes.byref(h), 2, 4, 20, 20, 1, 16),
+        "tokenizer": lambda h: L.mgpt_tokenizer_create(ctypes.byref(h), ctypes.byref(cfg), 2, 4, 20, 20, 1),
+        "gpt": lambda h: L.mgpt_gpt_create(ctypes.byref(h), 2, 2, 64, 256, 2),
+        "dedup": lambda h: L.mgpt_dedup_create(ctypes.byref(h), 64, 64, None),
+        "dataset": lambda h: L.mgpt_dataset_create(ctypes.byref(h), ctypes.c_void_p(grid.ctypes.data), 20, 20, None),
+    }
+    for name, create in creates.items():
+        h = ctypes.c_void_p()
+        assert create(h) == _lib.ERR_HIP, (name, L.mgpt_last_error())
+        assert not h, name
+        assert _lib.mem_debug() == (0, 0), name
+
+
+def test_arena_bookkeeping_under_sanitizers(tmp_path):
+    """tests/host/arena_check.cpp: mgpt::Arena on malloc / free (alloc, release, move, adopt, reuse, a failure at every step of a
+    five-allocation sequence), built with AddressSanitizer + UBSan as a program of its own and run directly."""
+    import shutil
+    import subprocess
+    from mapf_gpt_amd import build
+    # the compiler behind hipcc first: clang links the sanitizer runtime statically, so the program does not care what else is loaded
+    rocm_clang = os.path.join(os.path.dirname(os.path.realpath(build.HIPCC)), "..", "lib", "llvm", "bin", "clang++")
+    cxx = next((c for c in (os.environ.get("CXX"), rocm_clang, "clang++", "c++", "g++") if c and shutil.which(c)), None)
+    assert cxx is not None, "no C++ compiler found"
+    exe = str(tmp_path / "arena_check")
+    subprocess.run([cxx, "-std=c++17", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "host", "arena_check.cpp"), "-o", exe], check=True, capture_output=True, text=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "arena_check: ok (0 allocations, 0 bytes live)" in r.stdout and "Sanitizer" not in r.stderr, r.stdout + r.stderr

@@ -109,7 +109,7 @@ def test_new_symbols_exported_and_bound(L):
     for s in ("mgpt_dedup_create", "mgpt_dedup_destroy", "mgpt_dedup_reset", "mgpt_dedup_count", "mgpt_dedup_filter",
               "mgpt_rows_workspace_bytes", "mgpt_dataset_balance", "mgpt_rows_select", "mgpt_rows_gather"):
         assert s in _lib.SYMBOLS and hasattr(L, s), s
-    assert L.mgpt_abi_version() == 1002
+    assert L.mgpt_abi_version() == 1003
 
 
 def test_argument_validation_without_gpu(L):
