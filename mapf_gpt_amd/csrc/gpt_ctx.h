@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gpt_plan.h"      // kSmallRows, and the launch plan of the 16-bit forward (host-only)
 
 struct LayerOff {
     size_t ln1, attn_w, proj_w, ln2, fc_w, proj2_w;
@@ -50,10 +51,6 @@ struct mgpt_gpt {
     mgpt::DeviceArena embed_mem;                // embed_table
 };
 
-
-// calls of up to kSmallRows rows (one environment) run other kernels than larger ones (head-parallel attention, 32 x 32 x 16 MLP
-// block, one-launch last layer): gpt_fast.hip, DESIGN.md section 3.2
-constexpr int kSmallRows = 128;
 
 // outputs of a sequence forward (mgpt_gpt_forward_seq) for one chunk of rows: logits of every position [rows][T][67] or NULL; targets [rows][T]
 // (-1 = ignored) with the per-row sum of the targeted positions' -log softmax and their count, or all three NULL

@@ -9,7 +9,7 @@
 #include <vector>
 
 #include "common.h"
-#include "gpt_ctx.h"
+#include "gpt_ctx.h"                // (includes gpt_plan.h: Family, ModeFacts, Plan; mode_facts at build, make_plan per chunk)
 #include "gpt_kernels_fast.h"
 #include "gpt_fast_launch.h"        // launch_gemm16, launch_gemm_pk, launch_ln_pack, launch_row_stats, launch_embed_stats
 #include "gpt_kernels_c256q.h"      // (includes gpt_kernels_c256p.h)
@@ -25,78 +25,67 @@ namespace {
 
 constexpr int kT = 256;
 constexpr int kV = MGPT_VOCAB;
-// kSmallRows (gpt_ctx.h): rows up to which the C = 64 / 160 attention block runs head-parallel: beyond ~164 rows of 5 heads the (row, head)
-// workgroups need more rounds on 256 CUs than one workgroup per row takes (25 us against 80 us per workgroup, profiles/r02_cfg1_step_trace.txt)
 
 struct PlaneSet {           // one weight matrix [N][K] as 16-bit planes
     uint16_t *hi = nullptr, *lo = nullptr;
     float inv_scale = 1.f;
 };
 
-struct ModeState {          // one precision mode
+struct ModeState {          // one precision mode: what dispatch depends on, and the buffers grouped by the ModeBuilder function that fills them
     bool built = false;
-    int np = 0;             // planes per operand
-    int n_cu = 256;         // compute units of the model's device (grid of the persistent kernels)
-    std::vector<PlaneSet> attn, proj, fc, proj2;
-    // workspace (sized for max_rows)
-    float2 *stats = nullptr;
-    uint16_t *qk[2] = {nullptr, nullptr};      // [2 (q,k)][M][C] per plane
-    uint16_t *vt[2] = {nullptr, nullptr};      // [M][C]
-    uint16_t *y[2] = {nullptr, nullptr};       // [M][C]
-    uint16_t *hbuf[2] = {nullptr, nullptr};    // [M][4C]
-    // fused MLP (C = 64 / 160): per layer one packed stream [hidden tile][fragment][plane][lane][8] in the fragment layout of
-    // mlp_fused16_kernel (16 x 16 x 32 MFMA: large calls), and (C = 64) in that of mlp_fused_kernel (32 x 32 x 16 MFMA: small calls)
-    std::vector<uint16_t *> mlp16_pk;
-    std::vector<uint16_t *> mlp_pk;
-    bool mlp_fused = false;
-    // C = 256 (6M): mlp256p_kernel's cyclic weight stream in consumption order (LayerNorm gain folded into c_fc), per layer
-    // [period step][pair][plane][lane][8], and the scale c_fc * gain was packed with
-    std::vector<uint16_t *> mlp256_pk;
-    std::vector<uint16_t *> mlp256q_pk;         // the same stream in the fragment layout of mlp256q_kernel (16 x 16 x 32 MFMA: large calls)
-    std::vector<float> mlp256_inv1;
-    std::vector<float> attn256_inv;            // 1 / scale of the attn256 weight stream (c_attn.weight * ln_1.weight)
-    float2 *gelu_lut = nullptr;                // the Phi table of the fused MLP kernels (kGeluLutN pairs)
-    std::vector<float2 *> mlp256_lut;          // per layer: the same table times 1 / scale of the layer's c_fc stream (mlp256p_kernel)
-    // C = 256, head size 32 (6M): attn256_kernel's c_attn stream in consumption order, per layer (small calls)
-    std::vector<uint16_t *> attn256_pk;
-    bool attn256 = false;
-    // attn256q_kernel (whole attention block, persistent: gpt_kernels_c256b.h): c_attn + c_proj stream per layer, and the per-workgroup spill slab
-    std::vector<uint16_t *> attn256q_pk;
-    unsigned char *attn256q_spill = nullptr;
-    // layer 0's q | k | v per (position, token) pair (attn256q_kernel<.., TAB = 2>), built from attn256q_pk[0]; nullptr: MGPT_L0_TABLE=0 or L = 1
-    unsigned char *l0_table = nullptr;
-    // register-resident LN+QKV (C = 64 / 160): per layer [tile][k-step][plane][lane][8] of c_attn.weight
-    std::vector<uint16_t *> qkv_pk;
-    bool qkv_fused = false;
-    // out-projection slices per head for attn_block_kernel: [head][out tile][kk][plane][lane][8]
-    std::vector<uint16_t *> proj_pk;
-    // last-layer shortcut: new residual rows of token 255 only, [round_up(max_rows, 256)][C] fp32
-    float *x_last = nullptr;
-    float *x_head = nullptr;                   // x_tiled: the last-token rows in plain row-major order for the head kernel
-    bool x_tiled = false;                      // residual stream chunk-major (fastk::xt_off): the C = 256 kernels
-    uint16_t *y_last = nullptr;                // packed-GEMM path: attention output of token 255 of every row, PK planes [rows_pad][C]
-    // small launches of the register-resident path (rows <= kSmallRows: one environment, BASELINE cfg1): attn_block_kernel<HP> runs one
-    // workgroup per (row, head) and leaves the heads' c_proj contributions here, [n_head][kSmallRows * 256 * C] fp32 in x's layout
-    float *head_parts = nullptr;
-    std::vector<uint16_t *> attn160o_pk;        // C = 160: attn160o_kernel's stream per layer (c_attn * ln_1 | c_proj), its 1 / scale, spill slab
-    std::vector<float> attn160_inv;
-    unsigned char *attn160o_spill = nullptr;
-    float *last1_wt = nullptr;                 // last layer, attn_last1_kernel: transposes of W_q, W_v, c_proj.weight (fp32)
-    // ... and the MLP block of those launches (C = 160): mlp160p_kernel's cyclic stream per layer and the scale c_fc * ln_2 was packed with
-    std::vector<uint16_t *> mlp160_pk;
-    std::vector<float> mlp160_inv1;
-    // PK GEMM path (C % 256 == 0: 6M, 85M): weights as MFMA-fragment streams, activations produced in the same layout
-    bool pk_gemm = false;
-    std::vector<uint16_t *> attn_pk2, proj_pk2, fc_pk2, proj2_pk2;   // [row tile][k-step][plane][lane][8]
-    uint16_t *apk = nullptr;                   // LayerNorm'ed rows in PK layout, [M/32][C/16][NP][512]
-    // folded LayerNorm (GemmArgs in gpt_kernels_fast.h; one-plane mode of the packed-GEMM chain): apk holds the RAW rows, written by the
-    // residual epilogues; W * ln.weight packings, their column sums, the epilogues' partial row sums
-    bool ln_fold = false;
-    std::vector<uint16_t *> attn_pk2g, fc_pk2g;
-    std::vector<float *> attn_cs, fc_cs;
-    float2 *ln_parts = nullptr;                // [C / 128][M]
-    float *ln_mean = nullptr;                  // [M]: the mean of every row at its latest LayerNorm = the shift of its operand planes (GemmArgs::shift)
-    DeviceArena mem;                           // owns every device pointer of the mode (head_parts, allocated late, included): free_mode
+    ModeFacts facts = {};
+    struct Planes {         // build_planes (every family): the four matrices of a layer as row-major planes, the Phi table of the fused MLP kernels (kGeluLutN pairs)
+        std::vector<PlaneSet> attn, proj, fc, proj2;
+        float2 *gelu_lut = nullptr;
+    } pl;
+    struct SixM {           // build_6m (FAM_6M)
+        // mlp256p_kernel's cyclic weight stream in consumption order (LayerNorm gain folded into c_fc), per layer [period step][pair][plane][lane][8];
+        // the same stream in the fragment layout of mlp256q_kernel (16 x 16 x 32 MFMA: large calls); 1 / the scale c_fc * gain was packed with
+        std::vector<uint16_t *> mlp256_pk, mlp256q_pk;
+        std::vector<float2 *> mlp256_lut;          // per layer: the Phi table times 1 / scale of the layer's c_fc stream (mlp256p_kernel)
+        std::vector<uint16_t *> attn256_pk;        // attn256_kernel's c_attn stream in consumption order, per layer (small calls)
+        std::vector<float> mlp256_inv1, attn256_inv;   // 1 / scale of the mlp256 streams and of the attn256 streams (c_attn.weight * ln_1.weight)
+        // attn256q_kernel (whole attention block, persistent: gpt_kernels_c256b.h): c_attn + c_proj stream per layer, and the per-workgroup spill slab
+        std::vector<uint16_t *> attn256q_pk;
+        unsigned char *attn256q_spill = nullptr;
+        // layer 0's q | k | v per (position, token) pair (attn256q_kernel<.., TAB = 2>), built from attn256q_pk[0]; facts.l0_qkv_table
+        unsigned char *l0_table = nullptr;
+    } m6;
+    struct Register {       // build_register (C = 64 / 160)
+        // the fused MLP's packed stream per layer, [hidden tile][fragment][plane][lane][8], in the fragment layout of mlp_fused16_kernel
+        // (16 x 16 x 32 MFMA: large calls), and (C = 64) in that of mlp_fused_kernel (32 x 32 x 16 MFMA: small calls)
+        std::vector<uint16_t *> mlp16_pk, mlp_pk;
+        std::vector<uint16_t *> qkv_pk;             // register-resident LN+QKV: per layer [tile][k-step][plane][lane][8] of c_attn.weight
+        std::vector<uint16_t *> proj_pk;            // FAM_REGISTER: out-projection slices per head for attn_block_kernel, [head][out tile][kk][plane][lane][8]
+        struct C160 {       // C = 160: attn160o_kernel's stream per layer (c_attn * ln_1 | c_proj), its 1 / scale and spill slab (large calls);
+            std::vector<uint16_t *> attn160o_pk, mlp160_pk;   // mlp160p_kernel's cyclic stream per layer and the scale c_fc * ln_2 was packed with (small calls)
+            std::vector<float> attn160_inv, mlp160_inv1;
+            unsigned char *attn160o_spill = nullptr;
+        } c160;
+        // small launches (rows <= kSmallRows: one environment, BASELINE cfg1): attn_block_kernel<HP> runs one workgroup per (row, head) and leaves the
+        // heads' c_proj contributions here, [n_head][kSmallRows * 256 * C] fp32 in x's layout.  Allocated by the first small launch (Chunk::ensure_head_parts)
+        float *head_parts = nullptr;
+    } rg;
+    struct Last1 { float *wt = nullptr; } last1;   // build_last1 (facts.last1()): attn_last1_kernel's fp32 transposes of W_q, W_v, c_proj.weight, c_fc.weight, mlp.c_proj.weight
+    struct Packed {         // build_packed (facts.pk_gemm()): weights as MFMA-fragment streams [row tile][k-step][plane][lane][8], activations produced in the same layout
+        std::vector<uint16_t *> attn_pk2, proj_pk2, fc_pk2, proj2_pk2;
+        uint16_t *apk = nullptr;                   // FAM_PACKED: LayerNorm'ed rows in PK layout, [M/32][C/16][NP][512]
+        struct Folded {     // facts.ln_fold: apk holds the RAW rows, written by the residual epilogues; W * ln.weight packings, their column sums, ...
+            std::vector<uint16_t *> attn_pk2g, fc_pk2g;
+            std::vector<float *> attn_cs, fc_cs;
+            float2 *ln_parts = nullptr;            // ... the epilogues' partial row sums, [C / 128][M]
+            float *ln_mean = nullptr;              // [M]: the mean of every row at its latest LayerNorm = the shift of its operand planes (GemmArgs::shift)
+        } fold;
+    } pk;
+    struct Workspace {      // build_workspace (every family; sized for max_rows)
+        float *x_last = nullptr;                   // last-layer shortcut: new residual rows of token 255 only, [round_up(max_rows, 256)][C] fp32
+        float *x_head = nullptr;                   // x_tiled: the last-token rows in plain row-major order for the head kernel
+        uint16_t *y_last = nullptr;                // pk_gemm: attention output of token 255 of every row, PK planes [rows_pad][C]
+        float2 *stats = nullptr;
+        uint16_t *qk[2] = {nullptr, nullptr}, *vt[2] = {nullptr, nullptr};      // per plane: [2 (q,k)][M][C]; [M][C]
+        uint16_t *y[2] = {nullptr, nullptr}, *hbuf[2] = {nullptr, nullptr};     // [M][C]; [M][4C]
+    } ws;
+    DeviceArena mem;                               // owns every device pointer of the mode (head_parts, allocated late, included): free_mode
 };
 
 struct FastState {
@@ -151,6 +140,7 @@ struct ModeBuilder {
     mgpt_gpt *g;
     ModeState *m;
     const bool f16;
+    const ModeFacts &f = m->facts;              // filled first by build(): the parts read it and derive nothing themselves
     const size_t C = g->C;
     const int L = g->L;
     const float *P = g->params;
@@ -192,20 +182,12 @@ struct ModeBuilder {
     int build_planes()
     {
         MGPT_HIP(hipMemcpy(host.data(), P, g->n_params * sizeof(float), hipMemcpyDeviceToHost));
-        m->np = NP;
-        {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            MGPT_HIP(hipGetDevice(&dev));
-            MGPT_HIP(hipGetDeviceProperties(&prop, dev));
-            m->n_cu = std::max(1, prop.multiProcessorCount);
-        }
-        m->attn.resize(L); m->proj.resize(L); m->fc.resize(L); m->proj2.resize(L);
+        m->pl.attn.resize(L); m->pl.proj.resize(L); m->pl.fc.resize(L); m->pl.proj2.resize(L);
         int rc;
         for (int l = 0; l < L; l++) {
             const LayerOff &lo = g->layers[l];
-            struct { size_t off, n; PlaneSet *dst; } mats[4] = {{lo.attn_w, 3 * C * C, &m->attn[l]}, {lo.proj_w, C * C, &m->proj[l]},
-                                                               {lo.fc_w, 4 * C * C, &m->fc[l]}, {lo.proj2_w, 4 * C * C, &m->proj2[l]}};
+            struct { size_t off, n; PlaneSet *dst; } mats[4] = {{lo.attn_w, 3 * C * C, &m->pl.attn[l]}, {lo.proj_w, C * C, &m->pl.proj[l]},
+                                                               {lo.fc_w, 4 * C * C, &m->pl.fc[l]}, {lo.proj2_w, 4 * C * C, &m->pl.proj2[l]}};
             for (auto &mt : mats) {
                 const float sc = pick_scale(host.data() + mt.off, mt.n, f16);
                 if ((rc = pack_matrix(P + mt.off, mt.n, sc, mt.dst)) != MGPT_OK) return rc;
@@ -219,8 +201,8 @@ struct ModeBuilder {
             const float f0 = (float)phi(v0);
             lut[i] = make_float2(f0, (float)(phi(v1) - (double)f0));
         }
-        MGPT_HIP(m->mem.alloc(&m->gelu_lut, lut.size() * sizeof(float2)));
-        MGPT_HIP(hipMemcpy(m->gelu_lut, lut.data(), lut.size() * sizeof(float2), hipMemcpyHostToDevice));
+        MGPT_HIP(m->mem.alloc(&m->pl.gelu_lut, lut.size() * sizeof(float2)));
+        MGPT_HIP(hipMemcpy(m->pl.gelu_lut, lut.data(), lut.size() * sizeof(float2), hipMemcpyHostToDevice));
         return MGPT_OK;
     }
 
@@ -229,35 +211,33 @@ struct ModeBuilder {
     {
         int rc;
         const size_t n16 = (size_t)fastk::kMPPeriod * 16 * NP * 512;
-        m->mlp256_pk.assign(L, nullptr);
-        m->mlp256q_pk.assign(L, nullptr);
-        m->mlp256_inv1.assign(L, 1.f);
-        m->mlp256_lut.assign(L, nullptr);
+        m->m6.mlp256_pk.assign(L, nullptr);
+        m->m6.mlp256q_pk.assign(L, nullptr);
+        m->m6.mlp256_inv1.assign(L, 1.f);
+        m->m6.mlp256_lut.assign(L, nullptr);
         for (int l = 0; l < L; l++) {
-            MGPT_HIP(m->mem.alloc(&m->mlp256_pk[l], n16 * sizeof(uint16_t)));
-            MGPT_HIP(m->mem.alloc(&m->mlp256q_pk[l], n16 * sizeof(uint16_t)));
+            MGPT_HIP(m->mem.alloc(&m->m6.mlp256_pk[l], n16 * sizeof(uint16_t)));
+            MGPT_HIP(m->mem.alloc(&m->m6.mlp256q_pk[l], n16 * sizeof(uint16_t)));
             const LayerOff &lo = g->layers[l];
             const float sc1 = folded_scale(host, lo.fc_w, lo.ln2, 4 * C * C, C, f16);      // the stream carries c_fc.weight * ln_2.weight
-            m->mlp256_inv1[l] = 1.0f / sc1;
+            m->m6.mlp256_inv1[l] = 1.0f / sc1;
             {   // Phi table pre-multiplied by the (power-of-two) 1 / scale: GELU = pre-activation in stream units x entry, the same bits
                 std::vector<float2> lt(fastk::kGeluLutN);
-                MGPT_HIP(hipMemcpy(lt.data(), m->gelu_lut, lt.size() * sizeof(float2), hipMemcpyDeviceToHost));
-                for (auto &e : lt) { e.x *= m->mlp256_inv1[l]; e.y *= m->mlp256_inv1[l]; }
-                MGPT_HIP(m->mem.alloc(&m->mlp256_lut[l], lt.size() * sizeof(float2)));
-                MGPT_HIP(hipMemcpy(m->mlp256_lut[l], lt.data(), lt.size() * sizeof(float2), hipMemcpyHostToDevice));
+                MGPT_HIP(hipMemcpy(lt.data(), m->pl.gelu_lut, lt.size() * sizeof(float2), hipMemcpyDeviceToHost));
+                for (auto &e : lt) { e.x *= m->m6.mlp256_inv1[l]; e.y *= m->m6.mlp256_inv1[l]; }
+                MGPT_HIP(m->mem.alloc(&m->m6.mlp256_lut[l], lt.size() * sizeof(float2)));
+                MGPT_HIP(hipMemcpy(m->m6.mlp256_lut[l], lt.data(), lt.size() * sizeof(float2), hipMemcpyHostToDevice));
             }
             ProfScope ps(P_PACK, nullptr);
             hipLaunchKernelGGL((fastk::pack_mlp256p_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kMPPeriod * 16 * 64, 256)), dim3(256), 0,
-                               nullptr, P + lo.fc_w, P + lo.proj2_w, P + lo.ln2, m->mlp256_pk[l], sc1, 1.0f / m->proj2[l].inv_scale);
+                               nullptr, P + lo.fc_w, P + lo.proj2_w, P + lo.ln2, m->m6.mlp256_pk[l], sc1, 1.0f / m->pl.proj2[l].inv_scale);
             MGPT_LAUNCH_CHECK();
             hipLaunchKernelGGL((fastk::pack_mlp256q_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kMPPeriod * 16 * 64, 256)), dim3(256), 0,
-                               nullptr, P + lo.fc_w, P + lo.proj2_w, P + lo.ln2, m->mlp256q_pk[l], sc1, 1.0f / m->proj2[l].inv_scale);
+                               nullptr, P + lo.fc_w, P + lo.proj2_w, P + lo.ln2, m->m6.mlp256q_pk[l], sc1, 1.0f / m->pl.proj2[l].inv_scale);
             MGPT_LAUNCH_CHECK();
         }
         MGPT_HIP(set_max_lds_each(fastk::kMPLds<NP>, &fastk::mlp256p_kernel<T, NP>, &fastk::mlp256p_kernel<T, NP, 0, 2>, &fastk::mlp256q_kernel<T, NP>));
-        m->attn256 = (g->hs == 32 && g->nh == 8);
-        if (!m->attn256) return MGPT_OK;
-        rc = pack_folded(m->attn256_pk, m->attn256_inv, (size_t)8 * fastk::kA256StepsPerHead * 8 * NP * 512, true,
+        rc = pack_folded(m->m6.attn256_pk, m->m6.attn256_inv, (size_t)8 * fastk::kA256StepsPerHead * 8 * NP * 512, true,
                          [&](const LayerOff &lo, int, uint16_t *pk, float sc) {
                              hipLaunchKernelGGL((fastk::pack_attn256_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)8 * fastk::kA256StepsPerHead * 8 * 64, 256)),
                                                 dim3(256), 0, nullptr, P + lo.attn_w, P + lo.ln1, pk, sc);
@@ -265,27 +245,26 @@ struct ModeBuilder {
         if (rc != MGPT_OK) return rc;
         // the whole attention block in one persistent kernel: 48 steps of c_attn * ln_1 followed by 16 steps of c_proj
         const size_t n16o = (size_t)fastk::kA256oPeriod * 8 * NP * 512;
-        m->attn256q_pk.assign(L, nullptr);
+        m->m6.attn256q_pk.assign(L, nullptr);
         for (int l = 0; l < L; l++) {
             const LayerOff &lo = g->layers[l];
             ProfScope ps(P_PACK, nullptr);
-            MGPT_HIP(m->mem.alloc(&m->attn256q_pk[l], n16o * sizeof(uint16_t)));
+            MGPT_HIP(m->mem.alloc(&m->m6.attn256q_pk[l], n16o * sizeof(uint16_t)));
             hipLaunchKernelGGL((fastk::pack_attn256q_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kA256oPeriod * 8 * 64, 256)), dim3(256), 0,
-                               nullptr, P + lo.attn_w, P + lo.ln1, P + lo.proj_w, m->attn256q_pk[l], 1.0f / m->attn256_inv[l], 1.0f / m->proj[l].inv_scale);
+                               nullptr, P + lo.attn_w, P + lo.ln1, P + lo.proj_w, m->m6.attn256q_pk[l], 1.0f / m->m6.attn256_inv[l], 1.0f / m->pl.proj[l].inv_scale);
             MGPT_LAUNCH_CHECK();
         }
         MGPT_HIP(set_max_lds_each(fastk::kA256Lds<NP>, &fastk::attn256q_kernel<T, NP>, &fastk::attn256q_kernel<T, NP, 0, true>));
         if ((rc = ensure_embed_table(g)) != MGPT_OK) return rc;
-        MGPT_HIP(m->mem.alloc(&m->attn256q_spill, (size_t)m->n_cu * 8 * 14 * NP * 1024));
+        MGPT_HIP(m->mem.alloc(&m->m6.attn256q_spill, (size_t)f.n_cu * 8 * 14 * NP * 1024));
         // Layer 0 of large calls from a (position, token) table of q | k | v: its input row is etab[position][token], so the row's
         // LayerNorm and q|k|v projection are a function of the pair.  The table is the output of the EMB kernel itself (TAB = 1) on kV
         // synthetic rows, row j = token j at every position: every pair in the wave, lane and MFMA slot it has in a real row, so every
         // entry is bit-identical to what layer 0 computes.  (MGPT_L0_TABLE=0 in the environment keeps the EMB kernel on layer 0.)
-        const char *tab_env = getenv("MGPT_L0_TABLE");
-        if (L > 1 && !(tab_env != nullptr && tab_env[0] == '0')) {
+        if (f.l0_qkv_table) {
             ProfScope ps(P_PACK, nullptr);
             MGPT_HIP(set_max_lds_each(fastk::kA256Lds<NP>, &fastk::attn256q_kernel<T, NP, 0, true, 1>, &fastk::attn256q_kernel<T, NP, 0, false, 2>));
-            MGPT_HIP(m->mem.alloc(&m->l0_table, (size_t)kT * kV * fastk::kL0TabEntryBytes<NP>));
+            MGPT_HIP(m->mem.alloc(&m->m6.l0_table, (size_t)kT * kV * fastk::kL0TabEntryBytes<NP>));
             DeviceArena tmp;                                 // the synthetic rows: freed on every way out, after the synchronise on the good one
             float *xt = nullptr;
             unsigned char *tk = nullptr;
@@ -293,9 +272,9 @@ struct ModeBuilder {
             MGPT_HIP(tmp.alloc(&tk, (size_t)kV * kT));
             for (int j = 0; j < kV; j++) MGPT_HIP(hipMemset(tk + (size_t)j * kT, j, kT));
             const float scale_log2e = (1.0f / sqrtf((float)g->hs)) * 1.44269504088896340736f;    // (as forward_chunk)
-            hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true, 1>), dim3((unsigned)std::min(kV, m->n_cu)), dim3(512), (size_t)fastk::kA256Lds<NP>, nullptr, xt,
-                               m->attn256q_pk[0], m->attn256_inv[0], scale_log2e, m->proj[0].inv_scale, m->attn256q_spill, kV,
-                               (unsigned long long *)nullptr, tk, g->embed_table, m->l0_table);
+            hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true, 1>), dim3((unsigned)std::min(kV, f.n_cu)), dim3(512), (size_t)fastk::kA256Lds<NP>, nullptr, xt,
+                               m->m6.attn256q_pk[0], m->m6.attn256_inv[0], scale_log2e, m->pl.proj[0].inv_scale, m->m6.attn256q_spill, kV,
+                               (unsigned long long *)nullptr, tk, g->embed_table, m->m6.l0_table);
             MGPT_LAUNCH_CHECK();
             MGPT_HIP(hipDeviceSynchronize());
         }
@@ -303,7 +282,7 @@ struct ModeBuilder {
         return MGPT_OK;
     }
 
-    // ---- C = 64 / 160: the fused MLP's packets, and (FAM_REGISTER: heads of 32) qkv_pk / proj_pk and the 160-only persistent streams ----
+    // ---- C = 64 / 160: the fused MLP's packets and qkv_pk, and (FAM_REGISTER: heads of 32) proj_pk and the 160-only persistent streams ----
     template <int CT>
     int build_register()
     {
@@ -312,20 +291,20 @@ struct ModeBuilder {
             const size_t frags = C / 16 + 2 * (C / 32), nt = 4 * C / 32;
             const size_t n16 = nt * frags * NP * 512;
             // (the small calls of C = 160 take mlp160p_kernel, below: mlp_fused_kernel's packets only for C = 64)
-            if (CT == 2) m->mlp_pk.assign(L, nullptr);
-            m->mlp16_pk.assign(L, nullptr);
+            if (CT == 2) m->rg.mlp_pk.assign(L, nullptr);
+            m->rg.mlp16_pk.assign(L, nullptr);
             for (int l = 0; l < L; l++) {
                 const LayerOff &lo = g->layers[l];
                 ProfScope ps(P_PACK, nullptr);
                 if (CT == 2) {
-                    MGPT_HIP(m->mem.alloc(&m->mlp_pk[l], n16 * sizeof(uint16_t)));
+                    MGPT_HIP(m->mem.alloc(&m->rg.mlp_pk[l], n16 * sizeof(uint16_t)));
                     hipLaunchKernelGGL((fastk::pack_mlp_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(nt * frags * 64), 256)), dim3(256), 0,
-                                       nullptr, P + lo.fc_w, P + lo.proj2_w, m->mlp_pk[l], (int)C, 1.0f / m->fc[l].inv_scale, 1.0f / m->proj2[l].inv_scale);
+                                       nullptr, P + lo.fc_w, P + lo.proj2_w, m->rg.mlp_pk[l], (int)C, 1.0f / m->pl.fc[l].inv_scale, 1.0f / m->pl.proj2[l].inv_scale);
                     MGPT_LAUNCH_CHECK();
                 }
-                MGPT_HIP(m->mem.alloc(&m->mlp16_pk[l], n16 * sizeof(uint16_t)));
+                MGPT_HIP(m->mem.alloc(&m->rg.mlp16_pk[l], n16 * sizeof(uint16_t)));
                 hipLaunchKernelGGL((fastk::pack_mlp16_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(nt * frags * 64), 256)), dim3(256), 0,
-                                   nullptr, P + lo.fc_w, P + lo.proj2_w, m->mlp16_pk[l], (int)C, 1.0f / m->fc[l].inv_scale, 1.0f / m->proj2[l].inv_scale);
+                                   nullptr, P + lo.fc_w, P + lo.proj2_w, m->rg.mlp16_pk[l], (int)C, 1.0f / m->pl.fc[l].inv_scale, 1.0f / m->pl.proj2[l].inv_scale);
                 MGPT_LAUNCH_CHECK();
             }
             const int pkt = fastk::mlp_fused_lds(NP, (int)C);
@@ -334,24 +313,23 @@ struct ModeBuilder {
             MGPT_HIP(set_max_lds_each(pkt, &fastk::mlp_fused16_kernel<T, NP, CT, 8, 0>, &fastk::mlp_fused16_kernel<T, NP, CT, 4, 0>,
                                       &fastk::mlp_fused16_kernel<T, NP, CT, 2, 0>));
         }
-        m->qkv_fused = true;
         const size_t ks = C / 16, ntile = 3 * C / 32;
-        m->qkv_pk.assign(L, nullptr);
+        m->rg.qkv_pk.assign(L, nullptr);
         for (int l = 0; l < L; l++) {
-            MGPT_HIP(m->mem.alloc(&m->qkv_pk[l], ntile * ks * NP * 512 * sizeof(uint16_t)));
+            MGPT_HIP(m->mem.alloc(&m->rg.qkv_pk[l], ntile * ks * NP * 512 * sizeof(uint16_t)));
             ProfScope ps(P_PACK, nullptr);
             hipLaunchKernelGGL((fastk::pack_rows_perm_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(ntile * ks * 64), 256)), dim3(256), 0,
-                               nullptr, P + g->layers[l].attn_w, m->qkv_pk[l], (int)ntile, (int)C, 1.0f / m->attn[l].inv_scale);
+                               nullptr, P + g->layers[l].attn_w, m->rg.qkv_pk[l], (int)ntile, (int)C, 1.0f / m->pl.attn[l].inv_scale);
             MGPT_LAUNCH_CHECK();
         }
-        if (g->hs != 32) return MGPT_OK;
+        if (f.family != FAM_REGISTER) return MGPT_OK;
         const size_t ct = C / 32;
-        m->proj_pk.assign(L, nullptr);
+        m->rg.proj_pk.assign(L, nullptr);
         for (int l = 0; l < L; l++) {
-            MGPT_HIP(m->mem.alloc(&m->proj_pk[l], (size_t)g->nh * 2 * ct * NP * 512 * sizeof(uint16_t)));
+            MGPT_HIP(m->mem.alloc(&m->rg.proj_pk[l], (size_t)g->nh * 2 * ct * NP * 512 * sizeof(uint16_t)));
             ProfScope ps(P_PACK, nullptr);
             hipLaunchKernelGGL((fastk::pack_cols_perm_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)(g->nh * 2 * ct * 64), 256)), dim3(256), 0,
-                               nullptr, P + g->layers[l].proj_w, m->proj_pk[l], g->nh, (int)C, (int)C, 1.0f / m->proj[l].inv_scale);
+                               nullptr, P + g->layers[l].proj_w, m->rg.proj_pk[l], g->nh, (int)C, (int)C, 1.0f / m->pl.proj[l].inv_scale);
             MGPT_LAUNCH_CHECK();
         }
         // attn_block_kernel's dynamic LDS limit is a per-device function attribute: set it for this model's device
@@ -363,20 +341,20 @@ struct ModeBuilder {
         // (head_parts -- the heads' partial sums of small launches -- is allocated by the first small launch: forward_chunk)
         if (CT != 5) return MGPT_OK;
         // ... and the MLP block of the small launches: mlp160p_kernel's cyclic stream per layer and the scale c_fc * ln_2 was packed with
-        rc = pack_folded(m->mlp160_pk, m->mlp160_inv1, (size_t)fastk::kM5Period * 20 * NP * 512, false,
+        rc = pack_folded(m->rg.c160.mlp160_pk, m->rg.c160.mlp160_inv1, (size_t)fastk::kM5Period * 20 * NP * 512, false,
                          [&](const LayerOff &lo, int l, uint16_t *pk, float sc1) {
                              hipLaunchKernelGGL((fastk::pack_mlp160p_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kM5Period * 20 * 64, 256)), dim3(256), 0,
-                                                nullptr, P + lo.fc_w, P + lo.proj2_w, P + lo.ln2, pk, sc1, 1.0f / m->proj2[l].inv_scale);
+                                                nullptr, P + lo.fc_w, P + lo.proj2_w, P + lo.ln2, pk, sc1, 1.0f / m->pl.proj2[l].inv_scale);
                          });
         if (rc != MGPT_OK) return rc;
         // the attention block as one persistent kernel (layers that neither gather the embedding nor are the last)
-        rc = pack_folded(m->attn160o_pk, m->attn160_inv, (size_t)fastk::kA160oPeriod * fastk::kA160oFrags * NP * 512, true,
+        rc = pack_folded(m->rg.c160.attn160o_pk, m->rg.c160.attn160_inv, (size_t)fastk::kA160oPeriod * fastk::kA160oFrags * NP * 512, true,
                          [&](const LayerOff &lo, int l, uint16_t *pk, float sca) {
                              hipLaunchKernelGGL((fastk::pack_attn160o_kernel<T, NP>), dim3((unsigned)cdiv64((int64_t)fastk::kA160oPeriod * fastk::kA160oFrags * 64, 256)),
-                                                dim3(256), 0, nullptr, P + lo.attn_w, P + lo.ln1, P + lo.proj_w, pk, sca, 1.0f / m->proj[l].inv_scale);
+                                                dim3(256), 0, nullptr, P + lo.attn_w, P + lo.ln1, P + lo.proj_w, pk, sca, 1.0f / m->pl.proj[l].inv_scale);
                          });
         if (rc != MGPT_OK) return rc;
-        MGPT_HIP(m->mem.alloc(&m->attn160o_spill, (size_t)m->n_cu * fastk::kA160oSpillPerWg<NP>));
+        MGPT_HIP(m->mem.alloc(&m->rg.c160.attn160o_spill, (size_t)f.n_cu * fastk::kA160oSpillPerWg<NP>));
         MGPT_HIP(set_max_lds_each(fastk::kA160oLds<NP>, &fastk::attn160o_kernel<T, NP>, &fastk::attn160o_kernel<T, NP, true>));
         if ((rc = ensure_embed_table(g)) != MGPT_OK) return rc;
         MGPT_HIP(set_max_lds(&fastk::mlp160p_kernel<T, NP, 5>, fastk::kM5Lds<NP>));
@@ -391,14 +369,14 @@ struct ModeBuilder {
     int build_last1()
     {
         const LayerOff &lo = g->layers[L - 1];
-        MGPT_HIP(m->mem.alloc(&m->last1_wt, (size_t)11 * C * C * sizeof(float)));
+        MGPT_HIP(m->mem.alloc(&m->last1.wt, (size_t)11 * C * C * sizeof(float)));
         struct { size_t off; int rows, cols; size_t dst; } mats[5] = {
             {lo.attn_w, (int)C, (int)C, 0}, {lo.attn_w + (size_t)2 * C * C, (int)C, (int)C, (size_t)C * C}, {lo.proj_w, (int)C, (int)C, (size_t)2 * C * C},
             {lo.fc_w, (int)(4 * C), (int)C, (size_t)3 * C * C}, {lo.proj2_w, (int)C, (int)(4 * C), (size_t)7 * C * C}};
         ProfScope ps(P_PACK, nullptr);
         for (const auto &mt : mats) {
             hipLaunchKernelGGL(fastk::transpose_kernel, dim3((unsigned)cdiv64((int64_t)mt.rows * mt.cols, 256)), dim3(256), 0, nullptr,
-                               P + mt.off, m->last1_wt + mt.dst, mt.rows, mt.cols);
+                               P + mt.off, m->last1.wt + mt.dst, mt.rows, mt.cols);
             MGPT_LAUNCH_CHECK();
         }
         MGPT_HIP(set_max_lds(&fastk::attn_last1_kernel<C_, 32, fastk::kLast1R, false>, fastk::kLast1Lds<C_, fastk::kLast1R, false>));
@@ -407,7 +385,7 @@ struct ModeBuilder {
         return MGPT_OK;
     }
 
-    // ---- C % 256 == 0 (FAM_PACKED; FAM_6M for its out-projection): pack_pk streams, the PK4 / PK16 attributes, the LayerNorm-fold packings ----
+    // ---- facts.pk_gemm() (FAM_PACKED; FAM_6M for its out-projection): pack_pk streams, the PK4 / PK16 attributes, the LayerNorm-fold packings ----
     template <int EPI, int NWV, bool LNF, bool LUT>
     hipError_t gemm_pk_max_lds()                // gemm_pk_kernel<.., NWV, 0, LNF> (LUT: with the Phi table slot behind the ring)
     {
@@ -462,39 +440,34 @@ struct ModeBuilder {
     int build_packed()
     {
         int rc;
-        m->attn_pk2.assign(L, nullptr); m->proj_pk2.assign(L, nullptr); m->fc_pk2.assign(L, nullptr); m->proj2_pk2.assign(L, nullptr);
+        m->pk.attn_pk2.assign(L, nullptr); m->pk.proj_pk2.assign(L, nullptr); m->pk.fc_pk2.assign(L, nullptr); m->pk.proj2_pk2.assign(L, nullptr);
         for (int l = 0; l < L; l++) {
             const LayerOff &lo = g->layers[l];
-            if ((rc = pack_pk(&m->attn_pk2[l], lo.attn_w, 3 * C, C, 1.0f / m->attn[l].inv_scale)) != MGPT_OK) return rc;
-            if ((rc = pack_pk(&m->proj_pk2[l], lo.proj_w, C, C, 1.0f / m->proj[l].inv_scale)) != MGPT_OK) return rc;
-            if (!m->mlp_fused) {
-                if ((rc = pack_pk(&m->fc_pk2[l], lo.fc_w, 4 * C, C, 1.0f / m->fc[l].inv_scale)) != MGPT_OK) return rc;
-                if ((rc = pack_pk(&m->proj2_pk2[l], lo.proj2_w, C, 4 * C, 1.0f / m->proj2[l].inv_scale)) != MGPT_OK) return rc;
+            if ((rc = pack_pk(&m->pk.attn_pk2[l], lo.attn_w, 3 * C, C, 1.0f / m->pl.attn[l].inv_scale)) != MGPT_OK) return rc;
+            if ((rc = pack_pk(&m->pk.proj_pk2[l], lo.proj_w, C, C, 1.0f / m->pl.proj[l].inv_scale)) != MGPT_OK) return rc;
+            if (f.family == FAM_PACKED) {
+                if ((rc = pack_pk(&m->pk.fc_pk2[l], lo.fc_w, 4 * C, C, 1.0f / m->pl.fc[l].inv_scale)) != MGPT_OK) return rc;
+                if ((rc = pack_pk(&m->pk.proj2_pk2[l], lo.proj2_w, C, 4 * C, 1.0f / m->pl.proj2[l].inv_scale)) != MGPT_OK) return rc;
             }
         }
         // 256-row tiles (8 waves), and the 128-row forms (4 waves: small calls of the C = 768 chain, the 6M shape's out-projection)
         if ((rc = gemm_pk_max_lds_all<8>()) != MGPT_OK) return rc;
         if ((rc = gemm_pk_max_lds_all<4>()) != MGPT_OK) return rc;
-        if (!(C == 256 && m->mlp_fused && g->hs == 32 && g->nh == 8))      // LayerNorm planes of the GEMM chain (the 6M kernels normalise in registers)
-            MGPT_HIP(m->mem.alloc(&m->apk, (size_t)g->max_rows * kT * C * NP * sizeof(uint16_t)));
-        // one-plane mode of the full chain (no fused kernels): LayerNorm folded into the GEMMs (GemmArgs) -- ln_pack_kernel, which
-        // re-reads every residual row to normalise it (8 % of an 85M step), runs once per forward instead of twice per layer
-        // (MGPT_LN_FOLD=0 in the environment keeps the normalised planes: the raw planes round x itself to bf16, so a residual stream whose
-        //  per-token mean is many times its standard deviation loses precision that LayerNorm-then-round keeps)
-        const char *fold_env = getenv("MGPT_LN_FOLD");
-        m->ln_fold = NP == 1 && !m->mlp_fused && m->apk != nullptr && !(fold_env != nullptr && fold_env[0] == '0');
-        if (!m->ln_fold) return MGPT_OK;
-        m->attn_pk2g.assign(L, nullptr); m->fc_pk2g.assign(L, nullptr); m->attn_cs.assign(L, nullptr); m->fc_cs.assign(L, nullptr);
+        if (f.family == FAM_PACKED)                          // LayerNorm planes of the GEMM chain (the 6M kernels normalise in registers)
+            MGPT_HIP(m->mem.alloc(&m->pk.apk, (size_t)g->max_rows * kT * C * NP * sizeof(uint16_t)));
+        // LayerNorm folded into the GEMMs (GemmArgs; mode_facts has the why): the W * ln.weight packings, their column sums, the row sums
+        if (!f.ln_fold) return MGPT_OK;
+        m->pk.fold.attn_pk2g.assign(L, nullptr); m->pk.fold.fc_pk2g.assign(L, nullptr); m->pk.fold.attn_cs.assign(L, nullptr); m->pk.fold.fc_cs.assign(L, nullptr);
         for (int l = 0; l < L; l++) {
             const LayerOff &lo = g->layers[l];
-            if ((rc = pack_pk(&m->attn_pk2g[l], lo.attn_w, 3 * C, C, 1.0f / m->attn[l].inv_scale, lo.ln1, &m->attn_cs[l])) != MGPT_OK) return rc;
-            if ((rc = pack_pk(&m->fc_pk2g[l], lo.fc_w, 4 * C, C, 1.0f / m->fc[l].inv_scale, lo.ln2, &m->fc_cs[l])) != MGPT_OK) return rc;
+            if ((rc = pack_pk(&m->pk.fold.attn_pk2g[l], lo.attn_w, 3 * C, C, 1.0f / m->pl.attn[l].inv_scale, lo.ln1, &m->pk.fold.attn_cs[l])) != MGPT_OK) return rc;
+            if ((rc = pack_pk(&m->pk.fold.fc_pk2g[l], lo.fc_w, 4 * C, C, 1.0f / m->pl.fc[l].inv_scale, lo.ln2, &m->pk.fold.fc_cs[l])) != MGPT_OK) return rc;
         }
-        MGPT_HIP(m->mem.alloc(&m->ln_parts, (size_t)(C / 128) * g->max_rows * kT * sizeof(float2)));
+        MGPT_HIP(m->mem.alloc(&m->pk.fold.ln_parts, (size_t)(C / 128) * g->max_rows * kT * sizeof(float2)));
         // (the last layer's compact launch is padded to 256 rows and addresses token 255 of each: room and finite values for all of them)
         const size_t n_mean = (size_t)((g->max_rows + 255) / 256) * 256 * kT;
-        MGPT_HIP(m->mem.alloc(&m->ln_mean, n_mean * sizeof(float)));
-        MGPT_HIP(hipMemset(m->ln_mean, 0, n_mean * sizeof(float)));
+        MGPT_HIP(m->mem.alloc(&m->pk.fold.ln_mean, n_mean * sizeof(float)));
+        MGPT_HIP(hipMemset(m->pk.fold.ln_mean, 0, n_mean * sizeof(float)));
         return MGPT_OK;
     }
 
@@ -502,48 +475,45 @@ struct ModeBuilder {
     int build_workspace()
     {
         const size_t nl = (size_t)((g->max_rows + 255) / 256) * 256 * C;
-        MGPT_HIP(m->mem.alloc(&m->x_last, nl * sizeof(float)));
-        MGPT_HIP(hipMemset(m->x_last, 0, nl * sizeof(float)));           // padding rows stay finite
-        // chunk-major residual stream: the fused kernels (6M shape; 2M / tiny shapes with heads of 32) and the packed-fragment GEMM chain
-        m->x_tiled = m->pk_gemm || (m->qkv_fused && g->hs == 32 && m->mlp_fused);
-        if (m->x_tiled) MGPT_HIP(m->mem.alloc(&m->x_head, nl * sizeof(float)));
-        if (m->pk_gemm) {
-            MGPT_HIP(m->mem.alloc(&m->y_last, nl * NP * sizeof(uint16_t)));
-            MGPT_HIP(hipMemset(m->y_last, 0, nl * NP * sizeof(uint16_t)));
+        MGPT_HIP(m->mem.alloc(&m->ws.x_last, nl * sizeof(float)));
+        MGPT_HIP(hipMemset(m->ws.x_last, 0, nl * sizeof(float)));           // padding rows stay finite
+        if (f.x_tiled()) MGPT_HIP(m->mem.alloc(&m->ws.x_head, nl * sizeof(float)));
+        if (f.pk_gemm()) {
+            MGPT_HIP(m->mem.alloc(&m->ws.y_last, nl * NP * sizeof(uint16_t)));
+            MGPT_HIP(hipMemset(m->ws.y_last, 0, nl * NP * sizeof(uint16_t)));
         }
         const size_t M = (size_t)g->max_rows * kT;
-        MGPT_HIP(m->mem.alloc(&m->stats, M * sizeof(float2)));
+        MGPT_HIP(m->mem.alloc(&m->ws.stats, M * sizeof(float2)));
         // q|k and v^T planes exist in HBM only where the projection is a GEMM of its own: the fused attention kernels keep them on chip
-        const bool qkv_on_chip = m->attn256 || (m->qkv_fused && g->hs == 32 && m->mlp_fused);
         for (int p = 0; p < NP; p++) {
-            if (!qkv_on_chip) {
-                MGPT_HIP(m->mem.alloc(&m->qk[p], 2 * M * C * sizeof(uint16_t)));
-                MGPT_HIP(m->mem.alloc(&m->vt[p], M * C * sizeof(uint16_t)));
+            if (!f.qkv_on_chip()) {
+                MGPT_HIP(m->mem.alloc(&m->ws.qk[p], 2 * M * C * sizeof(uint16_t)));
+                MGPT_HIP(m->mem.alloc(&m->ws.vt[p], M * C * sizeof(uint16_t)));
             }
-            if (m->pk_gemm && p > 0) continue;                                   // PK buffers interleave the planes in [0]
-            MGPT_HIP(m->mem.alloc(&m->y[p], M * C * (m->pk_gemm ? NP : 1) * sizeof(uint16_t)));
-            if (!m->mlp_fused) MGPT_HIP(m->mem.alloc(&m->hbuf[p], 4 * M * C * (m->pk_gemm ? NP : 1) * sizeof(uint16_t)));
+            if (f.pk_gemm() && p > 0) continue;                                   // PK buffers interleave the planes in [0]
+            MGPT_HIP(m->mem.alloc(&m->ws.y[p], M * C * (f.pk_gemm() ? NP : 1) * sizeof(uint16_t)));
+            if (!f.mlp_fused) MGPT_HIP(m->mem.alloc(&m->ws.hbuf[p], 4 * M * C * (f.pk_gemm() ? NP : 1) * sizeof(uint16_t)));
         }
         return MGPT_OK;
     }
 
-    // the sequence; the flags are what make_plan reads its family from
+    // the facts (the device's compute units and the two environment switches are read here, once), then the family's parts in allocation order
     int build()
     {
         g->generation++;                                     // a step graph captured before this build must not be replayed as is
-        int rc;
+        int dev = 0, rc;
+        hipDeviceProp_t prop;
+        MGPT_HIP(hipGetDevice(&dev));
+        MGPT_HIP(hipGetDeviceProperties(&prop, dev));
+        auto wanted = [](const char *name) { const char *v = getenv(name); return !(v != nullptr && v[0] == '0'); };
+        m->facts = mode_facts(g->C, L, g->nh, g->hs, g->max_rows, NP, std::max(1, prop.multiProcessorCount), wanted("MGPT_L0_TABLE"), wanted("MGPT_LN_FOLD"));
         if ((rc = build_planes()) != MGPT_OK) return rc;
-        // (C = 256: the fused kernels are the 6M shape's -- 8 heads of 32 -- and share the chunk-major residual stream; any other
-        //  C = 256 model takes the packed-fragment GEMM chain)
-        m->mlp_fused = (C == 160 || C == 64 || (C == 256 && g->hs == 32 && g->nh == 8));
-        if (C == 256 && m->mlp_fused) rc = build_6m();
-        else if (C == 160) rc = build_register<5>();
-        else if (C == 64) rc = build_register<2>();
+        if (f.family == FAM_6M) rc = build_6m();
+        else if (f.mlp_fused) rc = C == 160 ? build_register<5>() : build_register<2>();
         if (rc != MGPT_OK) return rc;
-        if (g->hs == 32 && m->mlp_fused) rc = C == 256 ? build_last1<256>() : C == 160 ? build_last1<160>() : build_last1<64>();
+        if (f.last1()) rc = C == 256 ? build_last1<256>() : C == 160 ? build_last1<160>() : build_last1<64>();
         if (rc != MGPT_OK) return rc;
-        m->pk_gemm = (C == 256 || C == 512 || C == 768 || C == 1024);
-        if (m->pk_gemm && (rc = build_packed()) != MGPT_OK) return rc;
+        if (f.pk_gemm() && (rc = build_packed()) != MGPT_OK) return rc;
         if ((rc = build_workspace()) != MGPT_OK) return rc;
         MGPT_HIP(hipDeviceSynchronize());
         m->built = true;
@@ -565,107 +535,6 @@ void free_mode(mgpt_gpt *g, ModeState *m)
     *m = ModeState();
 }
 
-// ---------------------------------------------------------------------------------------------
-// The launch plan of a chunk: everything that decides which kernels it runs except "is this layer 0 / the last layer".  make_plan is the
-// one place where the shape, the precision mode and the row counts are looked at; where two conditions can hold at once, the order of
-// the ?: chains below is the precedence.  (DESIGN.md section 3.2 has the resulting table.)
-// ---------------------------------------------------------------------------------------------
-enum Family {               // fixed when the mode is built
-    FAM_REGISTER,           // C = 64 / 160, heads of 32: a layer is one attention-block kernel + one MLP-block kernel, q, k, v, y and the hidden stay on chip
-    FAM_6M,                 // C = 256, 8 heads of 32: the same, with kernels of its own
-    FAM_PACKED,             // any other C % 256 == 0 (85M): chain of packed-fragment GEMMs (gemm_pk) around attn16_kernel
-    FAM_GENERIC             // everything else: gemm16 chain on row-major planes (C = 64 / 160 with other heads: its MLP block is still the fused kernel)
-};
-enum EmbedKind {            // where x = wte[token] + wpe[position] comes from
-    EMBED_TABLE256,         // layer 0's attn256q_kernel reads the (position, token) table: x rows (EMB), or q | k | v themselves (TAB = 2, Plan::l0_qkv_table)
-    EMBED_TABLE160,         // layer 0's attn160o_kernel<EMB> reads the table
-    EMBED_ATTN_BLOCK,       // layer 0's attn_block_kernel<EMBED> gathers wte and wpe itself
-    EMBED_TILED,            // embed_tiled_kernel (chunk-major x)
-    EMBED_STATS             // embed_stats_kernel (row-major x + LayerNorm statistics)
-};
-enum AttnKind {             // the attention block of a full layer
-    ATTN_160O,              // attn160o_kernel: persistent, whole block
-    ATTN_BLOCK,             // attn_block_kernel: one workgroup per row, or per (row, head) in small calls (Plan::head_par)
-    ATTN_256Q,              // attn256q_kernel: persistent, whole block
-    ATTN_256_HEADS,         // attn256_kernel per (row, head) -> y planes -> packed out-projection
-    ATTN_PACKED,            // (ln_pack) q|k and v^T gemm_pk, attn16_kernel, out-projection gemm_pk
-    ATTN_GENERIC            // the same chain on gemm16
-};
-enum LastKind {             // the last layer, of which only token 255 of every row is needed (model.py:186)
-    LAST_NONE,              // runs as a full layer: sequence forward (every position is needed), or FAM_GENERIC
-    LAST_TAIL,              // small call: attention block, MLP block, ln_f and head in one attn_last1_kernel<.., 1, TAIL> launch; ends the chunk
-    LAST_1,                 // attn_last1_kernel -> x_last, then the MLP block on the compact rows
-    LAST_PACKED             // the packed chain with a compact tail: attn16 for query 255, gather_last, out-projection and MLP on rows_pad tokens
-};
-enum MlpKind { MLP_256P2, MLP_256P, MLP_256Q, MLP_160P, MLP_FUSED, MLP_FUSED16, MLP_PACKED, MLP_GENERIC };
-
-struct Plan {
-    int rows, rows_pad;     // of the chunk; rounded up to 256 (compact last-layer buffers)
-    int64_t M;              // tokens
-    // a small call (one environment): its kernels spread few rows over the CUs.  Decided by the CALL's row count, not the chunk's: the remainder
-    bool small;             // chunk of a large call stays on the large-call kernels
-    bool big_call;          // the one-plane packed GEMMs run on the 16 x 16 x 32 MFMA (launch_gemm_pk)
-    Family family;
-    EmbedKind embed;
-    bool l0_qkv_table;      // EMBED_TABLE256: layer 0's q | k | v from ModeState::l0_table
-    AttnKind attn;
-    bool head_par;          // ATTN_BLOCK per (row, head): the heads' c_proj contributions go to head_parts and the MLP kernel folds them in
-    int64_t part_stride;    // of head_parts
-    LastKind last;
-    bool last1_row_per_wg;  // LAST_1 with one row per workgroup instead of kLast1R (few rows on the 6M shape: so that they spread over the CUs)
-    MlpKind mlp;
-    int mlp160_tokens;      // MLP_160P: tokens per block (128: two waves per SIMD; 64, 32: so few tokens that larger blocks would leave CUs idle)
-    int mlp_nw, mlp_nw_last;   // MLP_FUSED / MLP_FUSED16: waves per workgroup (32 tokens each) of a full layer and of the compact last layer
-    bool half_qkv, half_proj, half_proj2;   // 128-row tiles in the packed GEMMs of small calls (q|k and v^T; out-projection and c_proj of full layers)
-};
-
-Plan make_plan(const mgpt_gpt *g, const ModeState *m, int rows, int call_rows, bool seq)
-{
-    Plan p = {};
-    const int C = g->C, n_cu = m->n_cu;
-    p.rows = rows; p.rows_pad = ((rows + 255) / 256) * 256; p.M = (int64_t)rows * kT;
-    p.small = call_rows <= kSmallRows && rows <= kSmallRows;
-    p.big_call = call_rows > kSmallRows;
-    const bool attn_block = m->qkv_fused && g->hs == 32 && m->mlp_fused;
-    p.family = attn_block ? FAM_REGISTER : m->attn256 ? FAM_6M : m->pk_gemm ? FAM_PACKED : FAM_GENERIC;
-    p.head_par = attn_block && p.small;
-    p.part_stride = (int64_t)std::min(g->max_rows, kSmallRows) * kT * C;        // (rows a small launch of this context can have)
-    // the first attention block forms x = wte[token] + wpe[position] itself (no embedding kernel, no first read of x) ... unless the persistent block
-    // kernel of the 2M shape serves the layer (profiles/r06_ab.txt visit B): embed_tiled_kernel + attn160o_kernel (0.6 + 4.5 ms per 16 384 rows) beat attn_block_kernel<EMBED> (5.8 ms)
-    const bool persistent160 = attn_block && C == 160 && !p.head_par && m->attn160o_spill != nullptr && m->x_tiled;
-    const bool embed_fused = attn_block && g->L > 1 && !p.head_par && !persistent160;
-    // ... and so do the persistent block kernels in a large call, from the (position, token) table (round 6)
-    const bool embed256 = m->attn256 && g->L > 1 && g->embed_table != nullptr && m->x_tiled && !p.small;
-    const bool embed160 = persistent160 && g->L > 1 && g->embed_table != nullptr;
-    p.embed = embed256 ? EMBED_TABLE256 : embed160 ? EMBED_TABLE160 : embed_fused ? EMBED_ATTN_BLOCK : m->x_tiled ? EMBED_TILED : EMBED_STATS;
-    p.l0_qkv_table = m->l0_table != nullptr;
-    // 6M shape: attn256q_kernel does the out-projection and the residual add itself ... unless the call is small: then a row's eight heads
-    // run on eight CUs at once (attn256_kernel, one workgroup per (row, head), y planes) and the packed GEMM projects them (round 5)
-    const bool small256 = m->attn256 && p.small;
-    p.attn = persistent160 ? ATTN_160O : attn_block ? ATTN_BLOCK : m->attn256 ? (small256 ? ATTN_256_HEADS : ATTN_256Q) : m->pk_gemm ? ATTN_PACKED : ATTN_GENERIC;
-    // last layer: only token 255 is needed downstream -> compact buffer, MLP and head on `rows` tokens.  Every model with last1_wt (FAM_REGISTER,
-    // FAM_6M) takes LAST_TAIL in a small call and LAST_1 (without K and V: a launch that fills the chip) in a large one
-    const bool short_last = (attn_block || m->pk_gemm) && !seq;
-    const bool small_call = p.head_par || small256;
-    p.last = !short_last ? LAST_NONE : (small_call && m->last1_wt != nullptr) ? LAST_TAIL
-             : (m->last1_wt != nullptr && m->x_tiled && !p.head_par) ? LAST_1 : LAST_PACKED;
-    p.last1_row_per_wg = C == 256 && rows <= 2 * n_cu;
-    // MLP block.  Small calls are not power-limited and keep the 32 x 32 x 16 kernels; large calls run the same block on v_mfma_f32_16x16x32
-    // (mlp256q, mlp_fused16: 13-15 % more f16 flops per second at the power limit); the choice is a property of the call
-    auto nw = [&](int64_t mlp_M) { return mlp_M >= (int64_t)256 * n_cu ? 8 : (mlp_M >= (int64_t)128 * n_cu ? 4 : 2); };
-    p.mlp_nw = nw(p.M); p.mlp_nw_last = nw(p.rows_pad);
-    p.mlp160_tokens = p.M <= (int64_t)32 * n_cu ? 32 : (p.M <= (int64_t)64 * n_cu ? 64 : 128);
-    if (m->mlp_fused && C == 256) p.mlp = !small256 ? MLP_256Q : (2 * (int)(p.M / 128) <= n_cu ? MLP_256P2 : MLP_256P);
-    else if (m->mlp_fused) p.mlp = (p.head_par && C == 160) ? MLP_160P : (p.head_par && C != 160) ? MLP_FUSED : MLP_FUSED16;
-    else p.mlp = m->pk_gemm ? MLP_PACKED : MLP_GENERIC;
-    // the packed-GEMM chain (C = 768) in a small call: its residual GEMMs (N = 768: 3 column tiles) are 96 tiles of 256 rows for 32 rows -- 128-row
-    // tiles put them on twice the CUs (same arithmetic per token: a wave's 64 x 128 sub-tile and its k order do not change).  One-plane mode: 32-row forward
-    // 2.77 -> 2.49 ms (c_proj 70 -> 56 us, out-projection 30 -> 25, q|k + v^T 51 -> 47); in the split mode the 4-wave form has a 3-stage ring and loses (5.8 -> 6.4)
-    const bool small_pk = m->np == 1 && m->pk_gemm && !m->attn256 && p.small;
-    p.half_qkv = small_pk; p.half_proj = small256 || small_pk; p.half_proj2 = small_pk;
-    return p;
-}
-
 // One chunk of a call: what its launches share, and the launches, each named for what it launches (forward_chunk is the sequence).
 template <class T, int NP>
 struct Chunk {
@@ -676,6 +545,7 @@ struct Chunk {
     hipStream_t s;
     const SeqOut *seq;
     const Plan p;
+    const ModeFacts &f = m->facts;
     const float *P = g->params;
     const int C = g->C, rows = p.rows, rows_pad = p.rows_pad;
     const int64_t M = p.M;
@@ -686,9 +556,9 @@ struct Chunk {
     {
         fastk::GemmArgs a = {};
         a.M = (int)M; a.C = C; a.n_head = g->nh; a.hs = g->hs; a.plane = M * C;
-        a.x = g->x; a.stats = m->stats; a.gain = P + g->layers[l].ln1; a.K = C;
-        a.w_hi = m->attn[l].hi; a.w_lo = m->attn[l].lo; a.out_scale = m->attn[l].inv_scale;
-        a.N = 2 * C; a.o_hi = m->qk[0]; a.o_lo = m->qk[1];
+        a.x = g->x; a.stats = m->ws.stats; a.gain = P + g->layers[l].ln1; a.K = C;
+        a.w_hi = m->pl.attn[l].hi; a.w_lo = m->pl.attn[l].lo; a.out_scale = m->pl.attn[l].inv_scale;
+        a.N = 2 * C; a.o_hi = m->ws.qk[0]; a.o_lo = m->ws.qk[1];
         return a;
     }
 
@@ -696,8 +566,8 @@ struct Chunk {
     // adapter whether or not the context ever served one environment).  New device memory: captured step graphs of this context are stale
     int ensure_head_parts()
     {
-        if (!p.head_par || m->head_parts != nullptr) return MGPT_OK;
-        MGPT_HIP(m->mem.alloc(&m->head_parts, (size_t)g->nh * (size_t)p.part_stride * sizeof(float)));
+        if (!p.head_par || m->rg.head_parts != nullptr) return MGPT_OK;
+        MGPT_HIP(m->mem.alloc(&m->rg.head_parts, (size_t)g->nh * (size_t)p.part_stride * sizeof(float)));
         g->generation++;
         return MGPT_OK;
     }
@@ -709,12 +579,12 @@ struct Chunk {
             hipLaunchKernelGGL(fastk::embed_tiled_kernel, dim3((unsigned)(M / 32)), dim3(256), 0, s, tokens, P + g->off_wte, P + g->off_wpe, g->x, C);
             MGPT_LAUNCH_CHECK();
         } else if (p.embed == EMBED_STATS) {
-            const int rc = launch_embed_stats(tokens, P + g->off_wte, P + g->off_wpe, g->x, m->stats, M, C, s);
+            const int rc = launch_embed_stats(tokens, P + g->off_wte, P + g->off_wpe, g->x, m->ws.stats, M, C, s);
             if (rc != MGPT_OK) return rc;
         }                                                          // (the other kinds: layer 0's attention block forms x)
-        // folded LayerNorm: (mean, rstd) of the rows the next GEMM normalises live in m->stats, their raw operand planes in m->apk
-        if (m->ln_fold)                                            // the embedding rows: the one ln_pack_kernel launch of the forward (raw mode)
-            return launch_ln_pack<T, NP>(g->x, P + g->layers[0].ln1, m->apk, M, C, m->x_tiled ? 1 : 0, s, m->stats, m->ln_mean);
+        // folded LayerNorm: (mean, rstd) of the rows the next GEMM normalises live in m->ws.stats, their raw operand planes in m->pk.apk
+        if (f.ln_fold)                                            // the embedding rows: the one ln_pack_kernel launch of the forward (raw mode)
+            return launch_ln_pack<T, NP>(g->x, P + g->layers[0].ln1, m->pk.apk, M, C, f.x_tiled() ? 1 : 0, s, m->ws.stats, m->pk.fold.ln_mean);
         return MGPT_OK;
     }
 
@@ -722,8 +592,8 @@ struct Chunk {
     int ln_finalize(int64_t Mrows, bool compact)
     {
         ProfScope ps(P_LAYERNORM, s);
-        hipLaunchKernelGGL(fastk::ln_finalize_kernel, dim3((unsigned)cdiv64(Mrows, 256)), dim3(256), 0, s, m->ln_parts, C / 128, Mrows, C, m->stats,
-                           m->ln_mean, compact ? kT : 1, compact ? kT - 1 : 0, compact ? 0 : 1);
+        hipLaunchKernelGGL(fastk::ln_finalize_kernel, dim3((unsigned)cdiv64(Mrows, 256)), dim3(256), 0, s, m->pk.fold.ln_parts, C / 128, Mrows, C, m->ws.stats,
+                           m->pk.fold.ln_mean, compact ? kT : 1, compact ? kT - 1 : 0, compact ? 0 : 1);
         MGPT_LAUNCH_CHECK();
         return MGPT_OK;
     }
@@ -737,15 +607,15 @@ struct Chunk {
         const float *wk = P + lo.attn_w + (size_t)C * C;
 #define MGPT_LAST1T(C_)                                                                                                                     \
     hipLaunchKernelGGL((fastk::attn_last1_kernel<C_, 32, 1, true>), dim3((unsigned)rows), dim3(256 * fastk::last1_split(C_)),              \
-                       (size_t)(fastk::kLast1Lds<C_, 1, true>), s, g->x, P + lo.ln1, wk, m->last1_wt, (float *)nullptr, rows, scale_log2e,    \
+                       (size_t)(fastk::kLast1Lds<C_, 1, true>), s, g->x, P + lo.ln1, wk, m->last1.wt, (float *)nullptr, rows, scale_log2e,    \
                        P + lo.ln2, P + g->off_lnf, P + g->off_wte, logits, kV)
 #define MGPT_LAST1(C_)                                                                                                                      \
     hipLaunchKernelGGL((fastk::attn_last1_kernel<C_, 32>), dim3((unsigned)(rows_pad / fastk::kLast1R)), dim3(256 * fastk::last1_split(C_)), (size_t)fastk::kLast1Lds<C_>, s, g->x, P + lo.ln1, \
-                       wk, m->last1_wt, m->x_last, rows, scale_log2e)
+                       wk, m->last1.wt, m->ws.x_last, rows, scale_log2e)
         if (p.last == LAST_TAIL) { if (C == 256) MGPT_LAST1T(256); else if (C == 160) MGPT_LAST1T(160); else MGPT_LAST1T(64); }
         else if (p.last1_row_per_wg)
             hipLaunchKernelGGL((fastk::attn_last1_kernel<256, 32, 1, false>), dim3((unsigned)rows_pad), dim3(256 * fastk::last1_split(256)),
-                               (size_t)(fastk::kLast1Lds<256, 1, false>), s, g->x, P + lo.ln1, wk, m->last1_wt, m->x_last, rows, scale_log2e);
+                               (size_t)(fastk::kLast1Lds<256, 1, false>), s, g->x, P + lo.ln1, wk, m->last1.wt, m->ws.x_last, rows, scale_log2e);
         else if (C == 256) MGPT_LAST1(256); else if (C == 160) MGPT_LAST1(160); else MGPT_LAST1(64);
 #undef MGPT_LAST1
 #undef MGPT_LAST1T
@@ -758,21 +628,21 @@ struct Chunk {
     {
         const LayerOff &lo = g->layers[l];
         ProfScope ps(P_ATTN, s);
-        const dim3 grid((unsigned)std::min(rows, m->n_cu));       // of the persistent kernels
+        const dim3 grid((unsigned)std::min(rows, f.n_cu));       // of the persistent kernels
         if (p.attn == ATTN_160O) {
             if (p.embed == EMBED_TABLE160 && l == 0)
                 hipLaunchKernelGGL((fastk::attn160o_kernel<T, NP, true>), grid, dim3(512), (size_t)fastk::kA160oLds<NP>, s, g->x,
-                                   m->attn160o_pk[l], m->attn160_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn160o_spill, rows, tokens, g->embed_table);
+                                   m->rg.c160.attn160o_pk[l], m->rg.c160.attn160_inv[l], scale_log2e, m->pl.proj[l].inv_scale, m->rg.c160.attn160o_spill, rows, tokens, g->embed_table);
             else
                 hipLaunchKernelGGL((fastk::attn160o_kernel<T, NP>), grid, dim3(512), (size_t)fastk::kA160oLds<NP>, s, g->x,
-                                   m->attn160o_pk[l], m->attn160_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn160o_spill, rows);
+                                   m->rg.c160.attn160o_pk[l], m->rg.c160.attn160_inv[l], scale_log2e, m->pl.proj[l].inv_scale, m->rg.c160.attn160o_spill, rows);
         } else if (p.attn == ATTN_BLOCK) {
             // (C = 160 comes here in small calls only: its large calls take attn160o_kernel)
             const size_t lds = (size_t)fastk::attn_block_lds(NP, C);
 #define MGPT_ATTN_BLOCK(CT_, EMB_, HP_)                                                                                                     \
     hipLaunchKernelGGL((fastk::attn_block_kernel<T, NP, CT_, EMB_, HP_>), dim3((unsigned)(HP_ ? rows * g->nh : rows)), dim3(512), lds, s, g->x, \
-                       P + lo.ln1, m->qkv_pk[l], m->attn[l].inv_scale, m->y[0], m->y[1], g->nh, scale_log2e, m->proj_pk[l],                  \
-                       m->proj[l].inv_scale, m->stats, m->x_last, tokens, P + g->off_wte, P + g->off_wpe, m->head_parts, p.part_stride)
+                       P + lo.ln1, m->rg.qkv_pk[l], m->pl.attn[l].inv_scale, m->ws.y[0], m->ws.y[1], g->nh, scale_log2e, m->rg.proj_pk[l],                  \
+                       m->pl.proj[l].inv_scale, m->ws.stats, m->ws.x_last, tokens, P + g->off_wte, P + g->off_wpe, m->rg.head_parts, p.part_stride)
             if (p.head_par) { if (C == 160) MGPT_ATTN_BLOCK(5, false, true); else MGPT_ATTN_BLOCK(2, false, true); }
             else if (p.embed == EMBED_ATTN_BLOCK && l == 0) MGPT_ATTN_BLOCK(2, true, false);
             else MGPT_ATTN_BLOCK(2, false, false);
@@ -782,15 +652,15 @@ struct Chunk {
             const bool emb = p.embed == EMBED_TABLE256 && l == 0;
             if (emb && p.l0_qkv_table)                               // (q | k | v of layer 0 from the (position, token) table)
                 hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, false, 2>), grid, dim3(512), (size_t)fastk::kA256Lds<NP>, s, g->x,
-                                   m->attn256q_pk[l], m->attn256_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn256q_spill, rows,
-                                   (unsigned long long *)nullptr, tokens, g->embed_table, m->l0_table);
+                                   m->m6.attn256q_pk[l], m->m6.attn256_inv[l], scale_log2e, m->pl.proj[l].inv_scale, m->m6.attn256q_spill, rows,
+                                   (unsigned long long *)nullptr, tokens, g->embed_table, m->m6.l0_table);
             else if (emb)
                 hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true>), grid, dim3(512), (size_t)fastk::kA256Lds<NP>, s, g->x,
-                                   m->attn256q_pk[l], m->attn256_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn256q_spill, rows,
+                                   m->m6.attn256q_pk[l], m->m6.attn256_inv[l], scale_log2e, m->pl.proj[l].inv_scale, m->m6.attn256q_spill, rows,
                                    (unsigned long long *)nullptr, tokens, g->embed_table);
             else
                 hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP>), grid, dim3(512), (size_t)fastk::kA256Lds<NP>, s, g->x,
-                                   m->attn256q_pk[l], m->attn256_inv[l], scale_log2e, m->proj[l].inv_scale, m->attn256q_spill, rows,
+                                   m->m6.attn256q_pk[l], m->m6.attn256_inv[l], scale_log2e, m->pl.proj[l].inv_scale, m->m6.attn256q_spill, rows,
                                    (unsigned long long *)nullptr);
         }
         MGPT_LAUNCH_CHECK();
@@ -805,23 +675,23 @@ struct Chunk {
         if (p.attn == ATTN_GENERIC) {
             ProfScope ps(P_GEMM_QKV, s);
             if ((rc = launch_gemm16<T, NP, fastk::PRO_LN, fastk::EPI_QK>(a, C, s)) != MGPT_OK) return rc;
-            a.w_hi = m->attn[l].hi + (size_t)2 * C * C; a.w_lo = (NP == 2) ? m->attn[l].lo + (size_t)2 * C * C : nullptr;
-            a.N = C; a.o_hi = m->vt[0]; a.o_lo = m->vt[1];
+            a.w_hi = m->pl.attn[l].hi + (size_t)2 * C * C; a.w_lo = (NP == 2) ? m->pl.attn[l].lo + (size_t)2 * C * C : nullptr;
+            a.N = C; a.o_hi = m->ws.vt[0]; a.o_lo = m->ws.vt[1];
             return launch_gemm16<T, NP, fastk::PRO_LN, fastk::EPI_VT>(a, C, s);
         }
-        // (folded LayerNorm: m->apk already holds the raw rows -- from the embedding or from the residual epilogue before -- and
-        //  m->stats their (mean, rstd); the W * ln_1.weight packing and its column sums do the rest in the epilogue)
-        if (!m->ln_fold && (rc = launch_ln_pack<T, NP>(g->x, P + g->layers[l].ln1, m->apk, M, C, m->x_tiled ? 1 : 0, s)) != MGPT_OK) return rc;
+        // (folded LayerNorm: m->pk.apk already holds the raw rows -- from the embedding or from the residual epilogue before -- and
+        //  m->ws.stats their (mean, rstd); the W * ln_1.weight packing and its column sums do the rest in the epilogue)
+        if (!f.ln_fold && (rc = launch_ln_pack<T, NP>(g->x, P + g->layers[l].ln1, m->pk.apk, M, C, f.x_tiled() ? 1 : 0, s)) != MGPT_OK) return rc;
         ProfScope ps(P_GEMM_QKV, s);
         const size_t tile_halves = (size_t)(C / 16) * NP * 512;          // one 32-row tile of a PK matrix with K = C
-        const uint16_t *wq = m->ln_fold ? m->attn_pk2g[l] : m->attn_pk2[l];
-        a.a_hi = m->apk; a.w_hi = wq; a.chunk_major = 1;
-        if (m->ln_fold) { a.ln_stats = m->stats; a.colsum = m->attn_cs[l]; }
-        if ((rc = launch_gemm_pk<T, NP, fastk::EPI_QK>(a, m->n_cu, s, p.half_qkv, p.big_call)) != MGPT_OK) return rc;
+        const uint16_t *wq = f.ln_fold ? m->pk.fold.attn_pk2g[l] : m->pk.attn_pk2[l];
+        a.a_hi = m->pk.apk; a.w_hi = wq; a.chunk_major = 1;
+        if (f.ln_fold) { a.ln_stats = m->ws.stats; a.colsum = m->pk.fold.attn_cs[l]; }
+        if ((rc = launch_gemm_pk<T, NP, fastk::EPI_QK>(a, f.n_cu, s, p.half_qkv, p.big_call)) != MGPT_OK) return rc;
         a.w_hi = wq + (size_t)(2 * C / 32) * tile_halves;                // rows 2C.. of c_attn.weight: V
-        if (m->ln_fold) a.colsum = m->attn_cs[l] + 2 * C;
-        a.N = C; a.o_hi = m->vt[0]; a.o_lo = m->vt[1];
-        if ((rc = launch_gemm_pk<T, NP, fastk::EPI_VT>(a, m->n_cu, s, p.half_qkv, p.big_call)) != MGPT_OK) return rc;
+        if (f.ln_fold) a.colsum = m->pk.fold.attn_cs[l] + 2 * C;
+        a.N = C; a.o_hi = m->ws.vt[0]; a.o_lo = m->ws.vt[1];
+        if ((rc = launch_gemm_pk<T, NP, fastk::EPI_VT>(a, f.n_cu, s, p.half_qkv, p.big_call)) != MGPT_OK) return rc;
         a.ln_stats = nullptr; a.colsum = nullptr;
         return MGPT_OK;
     }
@@ -835,43 +705,43 @@ struct Chunk {
             // LN1 + QKV + attention, one workgroup per (row, head): q, k, v stay on chip -> y operand planes for the out-projection
             ProfScope ps(P_ATTN, s);
             hipLaunchKernelGGL((fastk::attn256_kernel<T, NP>), dim3((unsigned)rows * 8), dim3(512), (size_t)fastk::kA256Lds<NP>, s,
-                               g->x, m->attn256_pk[l], m->attn256_inv[l], scale_log2e, m->y[0], (unsigned long long *)nullptr);
+                               g->x, m->m6.attn256_pk[l], m->m6.attn256_inv[l], scale_log2e, m->ws.y[0], (unsigned long long *)nullptr);
             MGPT_LAUNCH_CHECK();
         } else {
             if ((rc = qkv_gemms(l, a)) != MGPT_OK) return rc;
             ProfScope ps(last ? P_ATTN_LAST : P_ATTN, s);
-            const uint16_t *qh = m->qk[0], *ql = m->qk[1], *kh = m->qk[0] + M * C, *kl = (NP == 2) ? m->qk[1] + M * C : nullptr;
-            uint16_t *yh = last ? m->y_last : m->y[0];
+            const uint16_t *qh = m->ws.qk[0], *ql = m->ws.qk[1], *kh = m->ws.qk[0] + M * C, *kl = (NP == 2) ? m->ws.qk[1] + M * C : nullptr;
+            uint16_t *yh = last ? m->ws.y_last : m->ws.y[0];
 #define MGPT_ATTN16(HS_)                                                                                                                    \
     hipLaunchKernelGGL((fastk::attn16_kernel<T, NP, HS_>), dim3(rows * g->nh), dim3(512), (size_t)fastk::attn16_lds(NP, HS_), s, qh, ql, kh, kl, \
-                       m->vt[0], m->vt[1], yh, m->y[1], g->nh, scale_log2e, packed ? 1 : 0, packed ? 1 : 0, last ? 1 : 0)
+                       m->ws.vt[0], m->ws.vt[1], yh, m->ws.y[1], g->nh, scale_log2e, packed ? 1 : 0, packed ? 1 : 0, last ? 1 : 0)
             if (g->hs == 32) MGPT_ATTN16(32); else MGPT_ATTN16(64);
 #undef MGPT_ATTN16
             MGPT_LAUNCH_CHECK();
         }
         if (last) {
             ProfScope ps(P_EMBED, s);
-            hipLaunchKernelGGL(fastk::gather_last_kernel, dim3((unsigned)cdiv64((int64_t)rows_pad * (C / 4), 256)), dim3(256), 0, s, g->x, m->x_last, rows,
-                               rows_pad, C, m->x_tiled ? 1 : 0);
+            hipLaunchKernelGGL(fastk::gather_last_kernel, dim3((unsigned)cdiv64((int64_t)rows_pad * (C / 4), 256)), dim3(256), 0, s, g->x, m->ws.x_last, rows,
+                               rows_pad, C, f.x_tiled() ? 1 : 0);
             MGPT_LAUNCH_CHECK();
         }
-        a.a_hi = last ? m->y_last : m->y[0]; a.a_lo = m->y[1]; a.K = C; a.N = C;
-        a.w_hi = m->proj[l].hi; a.w_lo = m->proj[l].lo; a.out_scale = m->proj[l].inv_scale;
-        a.x_out = last ? m->x_last : g->x; a.stats_out = m->stats; a.x_tiled = m->x_tiled ? 1 : 0;
+        a.a_hi = last ? m->ws.y_last : m->ws.y[0]; a.a_lo = m->ws.y[1]; a.K = C; a.N = C;
+        a.w_hi = m->pl.proj[l].hi; a.w_lo = m->pl.proj[l].lo; a.out_scale = m->pl.proj[l].inv_scale;
+        a.x_out = last ? m->ws.x_last : g->x; a.stats_out = m->ws.stats; a.x_tiled = f.x_tiled() ? 1 : 0;
         if (last) a.M = rows_pad;
         {
             ProfScope ps(last ? P_GEMM_PROJ_LAST : P_GEMM_PROJ, s);
             if (packed) {
-                a.w_hi = m->proj_pk2[l];
-                if (m->ln_fold) {                                                      // the rows ln_2 normalises: planes + partial sums
-                    a.raw_out = m->apk; a.rsum_out = m->ln_parts;
-                    a.shift = m->ln_mean; a.shift_stride = last ? kT : 1; a.shift_offset = last ? kT - 1 : 0;
+                a.w_hi = m->pk.proj_pk2[l];
+                if (f.ln_fold) {                                                      // the rows ln_2 normalises: planes + partial sums
+                    a.raw_out = m->pk.apk; a.rsum_out = m->pk.fold.ln_parts;
+                    a.shift = m->pk.fold.ln_mean; a.shift_stride = last ? kT : 1; a.shift_offset = last ? kT - 1 : 0;
                 }
-                if ((rc = launch_gemm_pk<T, NP, fastk::EPI_RESID>(a, m->n_cu, s, p.half_proj && !last, p.big_call)) != MGPT_OK) return rc;
+                if ((rc = launch_gemm_pk<T, NP, fastk::EPI_RESID>(a, f.n_cu, s, p.half_proj && !last, p.big_call)) != MGPT_OK) return rc;
                 a.raw_out = nullptr; a.rsum_out = nullptr; a.shift = nullptr;
             } else if ((rc = launch_gemm16<T, NP, fastk::PRO_PLANES, fastk::EPI_RESID>(a, C, s)) != MGPT_OK) return rc;
         }
-        if (!fused_stats(C) && !packed) return launch_row_stats(g->x, m->stats, M, C, s);
+        if (!fused_stats(C) && !packed) return launch_row_stats(g->x, m->ws.stats, M, C, s);
         return MGPT_OK;
     }
 
@@ -879,7 +749,7 @@ struct Chunk {
     int mlp_fused(int l, bool last)
     {
         const LayerOff &lo = g->layers[l];
-        float *mlp_x = last ? m->x_last : g->x;
+        float *mlp_x = last ? m->ws.x_last : g->x;
         const int64_t mlp_M = last ? (int64_t)rows_pad : M;
         ProfScope ps(last ? P_MLP_FUSED_LAST : P_MLP_FUSED, s);
         if (p.mlp == MLP_256P2 || p.mlp == MLP_256P || p.mlp == MLP_256Q) {
@@ -887,25 +757,20 @@ struct Chunk {
             const int n_blocks = (int)(mlp_M / 128);
             if (p.mlp == MLP_256P2)
                 // small launch: 64-token blocks, four waves with a SIMD each (mlp256p_kernel<.., NPAIR = 2>): twice the workgroups
-                hipLaunchKernelGGL((fastk::mlp256p_kernel<T, NP, 0, 2>), dim3((unsigned)std::min(2 * n_blocks, m->n_cu)), dim3(256), (size_t)fastk::kMPLds<NP>, s,
-                                   mlp_x, m->mlp256_pk[l], m->mlp256_inv1[l], m->proj2[l].inv_scale, m->mlp256_lut[l], 2 * n_blocks, (unsigned long long *)nullptr);
+                hipLaunchKernelGGL((fastk::mlp256p_kernel<T, NP, 0, 2>), dim3((unsigned)std::min(2 * n_blocks, f.n_cu)), dim3(256), (size_t)fastk::kMPLds<NP>, s,
+                                   mlp_x, m->m6.mlp256_pk[l], m->m6.mlp256_inv1[l], m->pl.proj2[l].inv_scale, m->m6.mlp256_lut[l], 2 * n_blocks, (unsigned long long *)nullptr);
             else if (p.mlp == MLP_256P)
-                hipLaunchKernelGGL((fastk::mlp256p_kernel<T, NP>), dim3((unsigned)std::min(n_blocks, m->n_cu)), dim3(512), (size_t)fastk::kMPLds<NP>, s,
-                                   mlp_x, m->mlp256_pk[l], m->mlp256_inv1[l], m->proj2[l].inv_scale, m->mlp256_lut[l], n_blocks, (unsigned long long *)nullptr);
+                hipLaunchKernelGGL((fastk::mlp256p_kernel<T, NP>), dim3((unsigned)std::min(n_blocks, f.n_cu)), dim3(512), (size_t)fastk::kMPLds<NP>, s,
+                                   mlp_x, m->m6.mlp256_pk[l], m->m6.mlp256_inv1[l], m->pl.proj2[l].inv_scale, m->m6.mlp256_lut[l], n_blocks, (unsigned long long *)nullptr);
             else
-                hipLaunchKernelGGL((fastk::mlp256q_kernel<T, NP>), dim3((unsigned)std::min(n_blocks, m->n_cu)), dim3(512), (size_t)fastk::kMPLds<NP>, s,
-                                   mlp_x, m->mlp256q_pk[l], m->mlp256_inv1[l], m->proj2[l].inv_scale, m->mlp256_lut[l], n_blocks, (unsigned long long *)nullptr);
-            if (!m->pk_gemm && l + 1 < g->L) {                       // this kernel leaves no LayerNorm statistics behind
-                MGPT_LAUNCH_CHECK();
-                const int rc = launch_row_stats(g->x, m->stats, M, C, s);
-                if (rc != MGPT_OK) return rc;
-            }
+                hipLaunchKernelGGL((fastk::mlp256q_kernel<T, NP>), dim3((unsigned)std::min(n_blocks, f.n_cu)), dim3(512), (size_t)fastk::kMPLds<NP>, s,
+                                   mlp_x, m->m6.mlp256q_pk[l], m->m6.mlp256_inv1[l], m->pl.proj2[l].inv_scale, m->m6.mlp256_lut[l], n_blocks, (unsigned long long *)nullptr);
         } else if (p.mlp == MLP_160P) {
             // small launch: persistent producer / consumer blocks of TOK_ tokens; the heads' partial sums are folded in
 #define MGPT_MLP160P(TOK_, ...)                                                                                                             \
-    hipLaunchKernelGGL((fastk::mlp160p_kernel<T, NP, __VA_ARGS__>), dim3((unsigned)std::min((int)(mlp_M / TOK_), m->n_cu)), dim3(4 * TOK_),   \
-                       (size_t)(fastk::kM5Lds<NP, TOK_ / 32>), s, mlp_x, m->mlp160_pk[l], m->mlp160_inv1[l], m->proj2[l].inv_scale, m->gelu_lut, \
-                       (int)(mlp_M / TOK_), m->head_parts, p.part_stride)
+    hipLaunchKernelGGL((fastk::mlp160p_kernel<T, NP, __VA_ARGS__>), dim3((unsigned)std::min((int)(mlp_M / TOK_), f.n_cu)), dim3(4 * TOK_),   \
+                       (size_t)(fastk::kM5Lds<NP, TOK_ / 32>), s, mlp_x, m->rg.c160.mlp160_pk[l], m->rg.c160.mlp160_inv1[l], m->pl.proj2[l].inv_scale, m->pl.gelu_lut, \
+                       (int)(mlp_M / TOK_), m->rg.head_parts, p.part_stride)
             if (p.mlp160_tokens == 32) MGPT_MLP160P(32, 5, 1); else if (p.mlp160_tokens == 64) MGPT_MLP160P(64, 5, 2); else MGPT_MLP160P(128, 5);
 #undef MGPT_MLP160P
         } else {
@@ -914,11 +779,11 @@ struct Chunk {
             // spread over more CUs; results do not depend on the choice (one wave per workgroup is slower: 63 us per launch against 52, round 4)
 #define MGPT_MLP_(CT_, NW_)                                                                                                          \
     hipLaunchKernelGGL((fastk::mlp_fused_kernel<T, NP, CT_, NW_>), dim3((unsigned)(mlp_M / (32 * NW_))), dim3(64 * NW_), lds, s, mlp_x, \
-                       P + lo.ln2, m->mlp_pk[l], m->fc[l].inv_scale, m->proj2[l].inv_scale, last ? nullptr : m->stats, (int)mlp_M, m->gelu_lut, \
-                       m->head_parts, p.part_stride)
+                       P + lo.ln2, m->rg.mlp_pk[l], m->pl.fc[l].inv_scale, m->pl.proj2[l].inv_scale, last ? nullptr : m->ws.stats, (int)mlp_M, m->pl.gelu_lut, \
+                       m->rg.head_parts, p.part_stride)
 #define MGPT_MLP16_(CT_, NW_)                                                                                                        \
     hipLaunchKernelGGL((fastk::mlp_fused16_kernel<T, NP, CT_, NW_, 0>), dim3((unsigned)(mlp_M / (32 * NW_))), dim3(64 * NW_), lds, s, mlp_x, \
-                       P + lo.ln2, m->mlp16_pk[l], m->fc[l].inv_scale, m->proj2[l].inv_scale, last ? nullptr : m->stats, (int)mlp_M, m->gelu_lut, \
+                       P + lo.ln2, m->rg.mlp16_pk[l], m->pl.fc[l].inv_scale, m->pl.proj2[l].inv_scale, last ? nullptr : m->ws.stats, (int)mlp_M, m->pl.gelu_lut, \
                        (const float *)nullptr, (int64_t)0)
 #define MGPT_MLP(CT_, NW_) do { if (p.mlp == MLP_FUSED) MGPT_MLP_(CT_, NW_); else MGPT_MLP16_(CT_, NW_); } while (0)
             // (MLP_FUSED: mlp_fused_kernel folds in the heads' partial sums = n_head buffers, and n_head == C / 32 for the shapes of this path;
@@ -937,29 +802,29 @@ struct Chunk {
     // ---- the MLP block of the packed chain: LN2 -> PK planes; FC + GELU -> hidden PK planes; proj2 + residual ----
     int mlp_packed(int l, bool last, fastk::GemmArgs &a)
     {
-        float *mlp_x = last ? m->x_last : g->x;
+        float *mlp_x = last ? m->ws.x_last : g->x;
         const int64_t mlp_M = last ? (int64_t)rows_pad : M;
         int rc;
-        if (m->ln_fold) { if ((rc = ln_finalize(mlp_M, last)) != MGPT_OK) return rc; }
-        else if ((rc = launch_ln_pack<T, NP>(mlp_x, P + g->layers[l].ln2, m->apk, mlp_M, C, m->x_tiled ? 1 : 0, s)) != MGPT_OK) return rc;
+        if (f.ln_fold) { if ((rc = ln_finalize(mlp_M, last)) != MGPT_OK) return rc; }
+        else if ((rc = launch_ln_pack<T, NP>(mlp_x, P + g->layers[l].ln2, m->pk.apk, mlp_M, C, f.x_tiled() ? 1 : 0, s)) != MGPT_OK) return rc;
         a.M = (int)mlp_M;
-        a.a_hi = m->apk; a.K = C; a.N = 4 * C; a.w_hi = m->ln_fold ? m->fc_pk2g[l] : m->fc_pk2[l]; a.out_scale = m->fc[l].inv_scale;
-        a.o_hi = m->hbuf[0]; a.o_pk = 1; a.gelu_lut = m->gelu_lut;
-        if (m->ln_fold) { a.ln_stats = m->stats; a.colsum = m->fc_cs[l]; }
+        a.a_hi = m->pk.apk; a.K = C; a.N = 4 * C; a.w_hi = f.ln_fold ? m->pk.fold.fc_pk2g[l] : m->pk.fc_pk2[l]; a.out_scale = m->pl.fc[l].inv_scale;
+        a.o_hi = m->ws.hbuf[0]; a.o_pk = 1; a.gelu_lut = m->pl.gelu_lut;
+        if (f.ln_fold) { a.ln_stats = m->ws.stats; a.colsum = m->pk.fold.fc_cs[l]; }
         {
             ProfScope ps(P_GEMM_FC, s);
             // (c_fc keeps its 256-row tiles in small calls too: 384 of them already cover the CUs, and two 4-wave workgroups per CU move 1.5 x the ring
             //  pieces per MFMA of one 8-wave workgroup -- 54.6 vs 56.5 us per launch at 32 rows)
-            if ((rc = launch_gemm_pk<T, NP, fastk::EPI_GELU>(a, m->n_cu, s, false, p.big_call)) != MGPT_OK) return rc;
+            if ((rc = launch_gemm_pk<T, NP, fastk::EPI_GELU>(a, f.n_cu, s, false, p.big_call)) != MGPT_OK) return rc;
         }
         a.ln_stats = nullptr; a.colsum = nullptr;
-        a.a_hi = m->hbuf[0]; a.K = 4 * C; a.N = C; a.w_hi = m->proj2_pk2[l]; a.out_scale = m->proj2[l].inv_scale;
+        a.a_hi = m->ws.hbuf[0]; a.K = 4 * C; a.N = C; a.w_hi = m->pk.proj2_pk2[l]; a.out_scale = m->pl.proj2[l].inv_scale;
         a.x_out = mlp_x; a.stats_out = nullptr;
-        const bool feeds_next = m->ln_fold && l + 1 < g->L;            // the rows the next layer's ln_1 normalises
-        if (feeds_next) { a.raw_out = m->apk; a.rsum_out = m->ln_parts; a.shift = m->ln_mean; a.shift_stride = 1; a.shift_offset = 0; }
+        const bool feeds_next = f.ln_fold && l + 1 < g->L;            // the rows the next layer's ln_1 normalises
+        if (feeds_next) { a.raw_out = m->pk.apk; a.rsum_out = m->pk.fold.ln_parts; a.shift = m->pk.fold.ln_mean; a.shift_stride = 1; a.shift_offset = 0; }
         {
             ProfScope ps(P_GEMM_PROJ2, s);
-            if ((rc = launch_gemm_pk<T, NP, fastk::EPI_RESID>(a, m->n_cu, s, p.half_proj2 && !last, p.big_call)) != MGPT_OK) return rc;
+            if ((rc = launch_gemm_pk<T, NP, fastk::EPI_RESID>(a, f.n_cu, s, p.half_proj2 && !last, p.big_call)) != MGPT_OK) return rc;
         }
         return feeds_next ? ln_finalize(mlp_M, false) : MGPT_OK;
     }
@@ -968,37 +833,36 @@ struct Chunk {
     int mlp_generic(int l, fastk::GemmArgs &a)
     {
         int rc;
-        a.x = g->x; a.stats = m->stats; a.gain = P + g->layers[l].ln2; a.K = C; a.N = 4 * C;
-        a.w_hi = m->fc[l].hi; a.w_lo = m->fc[l].lo; a.out_scale = m->fc[l].inv_scale;
-        a.o_hi = m->hbuf[0]; a.o_lo = m->hbuf[1];
+        a.x = g->x; a.stats = m->ws.stats; a.gain = P + g->layers[l].ln2; a.K = C; a.N = 4 * C;
+        a.w_hi = m->pl.fc[l].hi; a.w_lo = m->pl.fc[l].lo; a.out_scale = m->pl.fc[l].inv_scale;
+        a.o_hi = m->ws.hbuf[0]; a.o_lo = m->ws.hbuf[1];
         {
             ProfScope ps(P_GEMM_FC, s);
             if ((rc = launch_gemm16<T, NP, fastk::PRO_LN, fastk::EPI_GELU>(a, C, s)) != MGPT_OK) return rc;
         }
-        a.a_hi = m->hbuf[0]; a.a_lo = m->hbuf[1]; a.K = 4 * C; a.N = C;
-        a.w_hi = m->proj2[l].hi; a.w_lo = m->proj2[l].lo; a.out_scale = m->proj2[l].inv_scale;
-        a.x_out = g->x; a.stats_out = m->stats;
+        a.a_hi = m->ws.hbuf[0]; a.a_lo = m->ws.hbuf[1]; a.K = 4 * C; a.N = C;
+        a.w_hi = m->pl.proj2[l].hi; a.w_lo = m->pl.proj2[l].lo; a.out_scale = m->pl.proj2[l].inv_scale;
+        a.x_out = g->x; a.stats_out = m->ws.stats;
         {
             ProfScope ps(P_GEMM_PROJ2, s);
             if ((rc = launch_gemm16<T, NP, fastk::PRO_PLANES, fastk::EPI_RESID>(a, C, s)) != MGPT_OK) return rc;
         }
-        if (!fused_stats(C) && l + 1 < g->L) return launch_row_stats(g->x, m->stats, M, C, s);
+        if (!fused_stats(C) && l + 1 < g->L) return launch_row_stats(g->x, m->ws.stats, M, C, s);
         return MGPT_OK;
     }
 
     // ---- ln_f + head on the last token of every row (a sequence forward: at every position of the full residual stream) ----
     int head()
     {
-        if (seq != nullptr) return gpt_launch_head_seq(g, g->x, m->x_tiled, rows, kT, *seq, s);
-        if (m->x_tiled) {
+        if (seq != nullptr) return gpt_launch_head_seq(g, g->x, f.x_tiled(), rows, kT, *seq, s);
+        if (f.x_tiled()) {
             {
                 ProfScope ps(P_HEAD, s);
-                hipLaunchKernelGGL(fastk::untile_rows_kernel, dim3((unsigned)cdiv64((int64_t)rows * (C / 4), 256)), dim3(256), 0, s, m->x_last, m->x_head, rows, C);
+                hipLaunchKernelGGL(fastk::untile_rows_kernel, dim3((unsigned)cdiv64((int64_t)rows * (C / 4), 256)), dim3(256), 0, s, m->ws.x_last, m->ws.x_head, rows, C);
                 MGPT_LAUNCH_CHECK();
             }
-            return gpt_launch_head_at(g, m->x_head, (int64_t)C, 0, rows, logits, s);
+            return gpt_launch_head_at(g, m->ws.x_head, (int64_t)C, 0, rows, logits, s);
         }
-        if (p.family != FAM_GENERIC) return gpt_launch_head_at(g, m->x_last, (int64_t)C, 0, rows, logits, s);
         return gpt_launch_head(g, rows, logits, s);
     }
 };
@@ -1008,7 +872,7 @@ template <class T, int NP>
 int forward_chunk(mgpt_gpt *g, ModeState *m, const uint8_t *d_tokens, int rows, float *d_logits, hipStream_t s, int call_rows,
                   const SeqOut *seq = nullptr)
 {
-    const Plan p = make_plan(g, m, rows, call_rows, seq != nullptr);
+    const Plan p = make_plan(m->facts, rows, call_rows, seq != nullptr);
     Chunk<T, NP> c = {g, m, d_tokens, d_logits, s, seq, p};
     int rc;
     if ((rc = c.ensure_head_parts()) != MGPT_OK) return rc;                      // (before any kernel of the chunk is enqueued)
@@ -1094,15 +958,15 @@ int gpt_fast_debug_copy(mgpt_gpt *g, int precision, int which, void *d_out, int6
     ModeState *m = &f->mode[precision];
     const void *src = nullptr;
     switch (which) {
-        case 0: src = m->stats; break;
-        case 1: src = m->qk[0]; break;
-        case 2: src = m->qk[1]; break;
-        case 3: src = m->vt[0]; break;
-        case 4: src = m->vt[1]; break;
-        case 5: src = m->y[0]; break;
-        case 6: src = m->y[1]; break;
-        case 7: src = m->hbuf[0]; break;
-        case 8: src = m->hbuf[1]; break;
+        case 0: src = m->ws.stats; break;
+        case 1: src = m->ws.qk[0]; break;
+        case 2: src = m->ws.qk[1]; break;
+        case 3: src = m->ws.vt[0]; break;
+        case 4: src = m->ws.vt[1]; break;
+        case 5: src = m->ws.y[0]; break;
+        case 6: src = m->ws.y[1]; break;
+        case 7: src = m->ws.hbuf[0]; break;
+        case 8: src = m->ws.hbuf[1]; break;
         default: break;
     }
     MGPT_REQUIRE(src, MGPT_ERR_ARG, "which=%d has no buffer in this mode", which);

@@ -1,6 +1,6 @@
 // gpt_fast_launch.h -- host launchers of the 16-bit forward's GEMM, LayerNorm and embedding kernels (gpt_kernels_fast.h): each checks the
 // shape, picks the template instance and the dynamic LDS size, and launches on the given stream.  Which of them a call runs, and in which
-// order, is gpt_fast.hip's business (make_plan / forward_chunk).
+// order, is gpt_plan.h's and gpt_fast.hip's business (make_plan / forward_chunk).
 #pragma once
 #include <algorithm>
 
