@@ -538,11 +538,33 @@ int mgpt_expert_copy_solution(mgpt_expert *ex, int8_t *d_solution_out, void *str
  */
 int mgpt_expert_set_swap(mgpt_expert *ex, int on);
 
+/* Refinement of found solutions by single-agent space-time replanning (this project's own spec in the place of
+ * the anytime refinement of LaCAM3, the reference's expert, which is not in its tree: generate_dataset.py:214-230 only calls it;
+ * nothing is taken from the reference's dataset/lacam).  Off by default: without it every call above behaves as it did.
+ *   set_refine:    after mgpt_expert_set_search (MGPT_ERR_STATE without it; a later set_search turns the pass off again), before
+ *                  mgpt_expert_reset or between episodes (MGPT_ERR_STATE in the middle of one; reads the done flags as set_swap does).
+ *                  max_rounds 1 .. 65536 turns the pass on and sizes its memory, 0 turns it off and frees it.  horizon: solutions of
+ *                  up to this many steps are refined, 0 = twice max_steps, otherwise max_steps .. 2^20; MGPT_ERR_ARG outside these.
+ *                  MGPT_ERR_UNSUPPORTED when the horizon + 1 reach layers of the map do not fit the 160 KiB of LDS of a workgroup.
+ *   solve:         with the pass on, every instance the search left with status 1 or 4 and a length within the horizon is refined:
+ *                  rounds in which every agent is replanned once against the others' paths, until a round adopts nothing or max_rounds
+ *                  have run (one device counter read per round: synchronises the stream; timing-hook names expert_refine_path,
+ *                  expert_refine_round, expert_refine_final).
+ *   copy_search:   status and length are then the FINAL ones, which the episode replays (a status-4 instance may have become 1);
+ *                  iterations and nodes are the search's.  copy_solution returns the refined solution.
+ *   copy_refine:   int32 [n_inst] each, any may be NULL: the search's own status and length, the sum of costs before and after, rounds
+ *                  run, replans adopted (the last four are 0 for an instance that was left as it is).  MGPT_ERR_STATE before a solve or
+ *                  with the pass off.
+ */
+int mgpt_expert_set_refine(mgpt_expert *ex, int max_rounds, int horizon);
+int mgpt_expert_copy_refine(mgpt_expert *ex, int32_t *d_first_status, int32_t *d_first_length, int32_t *d_soc_before, int32_t *d_soc_after,
+                            int32_t *d_rounds, int32_t *d_replans, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Kernel timing hooks (bench.py's live roofline): when enabled, the library brackets every kernel
  * class with hipEvents on the launch stream.  mgpt_prof_read synchronises the device.
  * ------------------------------------------------------------------------------------------ */
-#define MGPT_PROF_MAX 32
+#define MGPT_PROF_MAX 64
 int mgpt_prof_enable(int on);
 int mgpt_prof_reset(void);
 /* names[i] (static strings), total_ms[i], launches[i] for i < *n (n in: capacity, out: used) */

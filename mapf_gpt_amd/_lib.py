@@ -125,6 +125,8 @@ SYMBOLS = {
     "mgpt_expert_solve": (_i, [_vp, _vp]),
     "mgpt_expert_copy_search": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mgpt_expert_copy_solution": (_i, [_vp, _vp, _vp]),
+    "mgpt_expert_set_refine": (_i, [_vp, _i, _i]),
+    "mgpt_expert_copy_refine": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mgpt_prof_enable": (_i, [_i]),
     "mgpt_prof_reset": (_i, []),
     "mgpt_prof_read": (_i, [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float),
@@ -207,7 +209,7 @@ def prof_reset():
 
 def prof_read():
     """-> {kernel_class: (total_ms, launches)}; synchronises the device."""
-    cap = 32
+    cap = 64
     names = (ctypes.c_char_p * cap)()
     ms = (ctypes.c_float * cap)()
     cnt = (ctypes.c_int64 * cap)()

@@ -6,7 +6,8 @@
 // guarantees that all agents stand on their goals at once.  A plain depth-first LaCAM search over this generator (DESIGN.md section 21,
 // lacam_search_kernel below) can run in front of the episode: an instance it solves within the step cap replays its solution.  An
 // opt-in corridor swap rule is the SWAP = true instantiation of both kernels.  The generator itself is one
-// device function, pibt_generate, that both kernels call.
+// device function, pibt_generate, that both kernels call.  An opt-in pass between the search and the episode
+// refines a found solution by replanning one agent at a time against the others' paths (refine_*_kernel below).
 //
 // One step of one instance:
 //   order      agents by (since desc, id asc), since = steps since the agent last stood on its goal;
@@ -658,6 +659,257 @@ __global__ __launch_bounds__(64) void search_replay_kernel(const int32_t *__rest
     if (lane == 0 && tl < max_steps) len[inst] = tl + 1;
 }
 
+// ---- refinement of a found solution: single-agent space-time replanning ---------------------------------------
+// Opt-in, between the search and the episode.  refine_path_kernel turns the parent chain of a status 1 / 4 instance whose length is
+// within the horizon into a path buffer [t][agent] of cell ids with every agent's arrival time; refine_round_kernel runs one round
+// (every agent with a non-zero arrival replanned once against the others' fixed paths) and is launched until no instance adopted
+// anything; refine_final_kernel writes what the episode's kernels read (status, length, sol) and the statistics.
+//
+// One wave64 workgroup per instance.  A replan is a layered reachability sweep over (time, cell): reach[t] is a bitmask over the cells
+// kept in 16-bit units in LDS, layers 0 .. horizon.  A lane owns whole units of the next layer: it forms the candidates of its unit
+// with shifts of the current layer (the four moves and the wait), then drops the cells another agent stands on at t + 1 and the
+// exchanges by looking into two LDS cell arrays (occ at t and at t + 1, scattered from the path buffer and cleared again by the same
+// scatter), and stores the unit: plain stores only, no atomics.  The hold scan is a strided loop over (t, agent) with a wave reduction;
+// the backtrack is serial in t, its five predecessor checks on five lanes and a ballot.  Per layer the wave goes through three
+// barriers and one dependent load from the path buffer: the sweep is latency-bound, not ALU- or bandwidth-bound.
+enum { R_ACTIVE = 0, R_LENGTH, R_FIRST_STATUS, R_FIRST_LENGTH, R_SOC_BEFORE, R_SOC_AFTER, R_ROUNDS, R_REPLANS, R_WORDS = 8 };
+
+struct RefineLds {
+    int *arr = nullptr, *goalc = nullptr;       // [n_agents] arrival times, goal cells
+    uint16_t *reach = nullptr;                  // [horizon + 1][units] the layers
+    uint16_t *occ = nullptr;                    // [2][cells] agent on a cell at t and at t + 1, NIL between replans
+    uint16_t *mask = nullptr;                   // [3][units] free cells; cells not in column 0; cells not in column W - 1
+};
+
+constexpr size_t kRefineMaxLds = 160 * 1024;  // what one workgroup may hold on gfx950; up to 64 KB of it several instances share a CU
+constexpr int refine_units(int64_t cells) { return (int)((cells + 15) / 16); }
+constexpr size_t refine_lds_bytes(int n_agents, int64_t cells, int horizon)
+{
+    return (size_t)n_agents * 8 + ((size_t)(horizon + 1) * refine_units(cells) + 2 * (size_t)cells + 3 * (size_t)refine_units(cells)) * 2;
+}
+
+__device__ __forceinline__ RefineLds refine_carve(char *smem, int n_agents, int cells, int horizon)
+{
+    const int units = refine_units(cells);
+    RefineLds L;
+    L.arr = reinterpret_cast<int *>(smem);
+    L.goalc = L.arr + n_agents;
+    L.reach = reinterpret_cast<uint16_t *>(L.goalc + n_agents);
+    L.occ = L.reach + (size_t)(horizon + 1) * units;
+    L.mask = L.occ + 2 * (size_t)cells;
+    return L;
+}
+
+// the 16 bits of layer R that start at bit p (any p: bits outside the layer are 0)
+__device__ __forceinline__ unsigned reach_window(const uint16_t *R, int units, int p)
+{
+    const int q = p >> 4, s = p & 15;
+    const unsigned lo = (q >= 0 && q < units) ? R[q] : 0u, hi = (q + 1 >= 0 && q + 1 < units) ? R[q + 1] : 0u;
+    return ((lo | (hi << 16)) >> s) & 0xFFFFu;
+}
+__device__ __forceinline__ bool reach_bit(const uint16_t *R, int v) { return (R[v >> 4] >> (v & 15)) & 1u; }
+
+struct RefineArgs {
+    const uint8_t *grids;
+    const int16_t *goal;
+    const int32_t *state;                       // the search's [n_inst][S_WORDS]
+    const int32_t *node_q, *open;
+    const int4 *node_meta;
+    int32_t *path;                              // [n_inst][horizon + 1][n_agents] cell ids
+    int32_t *arr;                               // [n_inst][n_agents]
+    int32_t *rstate;                            // [n_inst][R_WORDS]
+    int32_t *adopted;                           // set to 1 by every instance that adopted a replan in this launch
+    int n_grids, n_agents, H, W, max_steps, horizon, node_cap;
+};
+
+__global__ __launch_bounds__(64) void refine_path_kernel(const RefineArgs A)
+{
+    const int inst = blockIdx.x, lane = threadIdx.x, n_agents = A.n_agents;
+    const int32_t *st = A.state + (size_t)inst * S_WORDS;
+    int32_t *rs = A.rstate + (size_t)inst * R_WORDS;
+    const int status = st[S_STATUS], length = st[S_LENGTH];
+    const bool take = (status == 1 || status == 4) && length <= A.horizon;
+    int64_t soc = 0;
+    if (take) {                                                           // wave-uniform
+        const int32_t *nq = A.node_q + (size_t)inst * A.node_cap * n_agents;
+        const int4 *nm = A.node_meta + (size_t)inst * A.node_cap;
+        int32_t *P = A.path + (size_t)inst * (A.horizon + 1) * n_agents;
+        int node = A.open[(size_t)inst * A.node_cap + st[S_OPEN] - 1];
+        for (int t = length; t >= 0 && node >= 0 && node < A.node_cap; t--) {
+            for (int a = lane; a < n_agents; a += 64) P[(size_t)t * n_agents + a] = nq[(size_t)node * n_agents + a];
+            node = nm[node].y;
+        }
+        __syncthreads();
+        for (int a = lane; a < n_agents; a += 64) {                       // arrival: the start of the final stay on the goal
+            const int g = P[(size_t)length * n_agents + a];
+            int t = length;
+            while (t > 0 && P[(size_t)(t - 1) * n_agents + a] == g) t--;
+            A.arr[(size_t)inst * n_agents + a] = t;
+            soc += t;
+        }
+        for (int off = 32; off > 0; off >>= 1) soc += __shfl_xor((int)soc, off, 64);
+    }
+    if (lane == 0) {
+        rs[R_ACTIVE] = take ? 1 : 0; rs[R_LENGTH] = length; rs[R_FIRST_STATUS] = status; rs[R_FIRST_LENGTH] = length;
+        rs[R_SOC_BEFORE] = (int)soc; rs[R_SOC_AFTER] = (int)soc; rs[R_ROUNDS] = 0; rs[R_REPLANS] = 0;
+    }
+}
+
+__global__ __launch_bounds__(64) void refine_round_kernel(const RefineArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int inst = blockIdx.x, lane = threadIdx.x, n_agents = A.n_agents, H = A.H, W = A.W, cells = H * W;
+    int32_t *rs = A.rstate + (size_t)inst * R_WORDS;
+    if (rs[R_ACTIVE] == 0) return;                                        // wave-uniform: not refined, or a round of it adopted nothing
+    const int units = refine_units(cells);
+    const RefineLds L = refine_carve(smem, n_agents, cells, A.horizon);
+    uint16_t *occ_a = L.occ, *occ_b = L.occ + cells;                      // the agents at t and at t + 1
+    const uint16_t *free_m = L.mask, *notfirst_m = L.mask + units, *notlast_m = L.mask + 2 * units;
+    int32_t *P = A.path + (size_t)inst * (A.horizon + 1) * n_agents;
+    int32_t *garr = A.arr + (size_t)inst * n_agents;
+    const uint8_t *grid = A.grids + (size_t)(inst % A.n_grids) * cells;
+    const size_t g0 = (size_t)inst * n_agents;
+    int length = rs[R_LENGTH], adopted = 0;
+
+    for (int a = lane; a < n_agents; a += 64) {
+        const int gc = (int)A.goal[2 * (g0 + a)] * W + (int)A.goal[2 * (g0 + a) + 1];
+        L.goalc[a] = min(max(gc, 0), cells - 1);
+        L.arr[a] = garr[a];
+    }
+    for (int v = lane; v < 2 * cells; v += 64) L.occ[v] = (uint16_t)kNil;
+    for (int j = lane; j < units; j += 64) {
+        unsigned fr = 0, nf = 0, nl = 0;
+        for (int i = 0; i < 16; i++) {
+            const int v = j * 16 + i, c = v % W;
+            if (v < cells && grid[v] == 0) fr |= 1u << i;
+            if (c != 0) nf |= 1u << i;
+            if (c != W - 1) nl |= 1u << i;
+        }
+        L.mask[j] = (uint16_t)fr; L.mask[units + j] = (uint16_t)nf; L.mask[2 * units + j] = (uint16_t)nl;
+    }
+    __syncthreads();
+
+    // scatter (or clear) the agents other than a of layer t
+    auto scatter = [&](uint16_t *occ, int t, int a, bool set) {
+        for (int b = lane; b < n_agents; b += 64)
+            if (b != a) occ[P[(size_t)t * n_agents + b]] = set ? (uint16_t)b : (uint16_t)kNil;
+    };
+
+    for (int a = 0; a < n_agents; a++) {
+        const int arr_a = L.arr[a];
+        if (arr_a == 0) continue;
+        const int ga = L.goalc[a];
+        int hold = 0;                                                     // 1 + the last t at which another agent stands on a's goal
+        for (int idx = lane; idx < (length + 1) * n_agents; idx += 64) {
+            const int t = idx / n_agents, b = idx - t * n_agents;
+            if (b != a && P[idx] == ga) hold = max(hold, t + 1);
+        }
+        for (int off = 32; off > 0; off >>= 1) hold = max(hold, __shfl_xor(hold, off, 64));
+        if (hold >= arr_a) continue;                                      // T >= hold: nothing can be gained
+
+        const int start = P[a];
+        for (int j = lane; j < units; j += 64) L.reach[j] = (j == (start >> 4)) ? (uint16_t)(1u << (start & 15)) : (uint16_t)0;
+        scatter(occ_a, 0, a, true);
+        __syncthreads();
+        int T = -1, t = 0;
+        for (; t < arr_a; t++) {                                          // occ_a holds layer t
+            const uint16_t *R = L.reach + (size_t)t * units;
+            uint16_t *Rn = L.reach + (size_t)(t + 1) * units;
+            if (t >= hold && reach_bit(R, ga)) { T = t; break; }
+            scatter(occ_b, t + 1, a, true);
+            __syncthreads();
+            for (int j = lane; j < units; j += 64) {
+                const int base = j * 16;
+                unsigned m = (R[j] | (reach_window(R, units, base - 1) & notfirst_m[j]) | (reach_window(R, units, base + 1) & notlast_m[j]) |
+                              reach_window(R, units, base - W) | reach_window(R, units, base + W)) & free_m[j];
+                unsigned out = 0;
+                while (m) {
+                    const int i = __ffs((int)m) - 1, v = base + i;
+                    m &= m - 1u;
+                    if (occ_b[v] != kNil) continue;                       // another agent stands there at t + 1
+                    const unsigned b = occ_a[v];
+                    if (b != kNil) {                                      // b leaves v: a predecessor that b moves onto would be an exchange
+                        bool ok = false;
+                        for (int k = 0; k < 5; k++) {
+                            int u;
+                            ok |= neighbour(v, k, H, W, u) && reach_bit(R, u) && occ_b[u] != b;
+                        }
+                        if (!ok) continue;
+                    }
+                    out |= 1u << i;
+                }
+                Rn[j] = (uint16_t)out;
+            }
+            __syncthreads();
+            scatter(occ_a, t, a, false);
+            __syncthreads();
+            uint16_t *tmp = occ_a; occ_a = occ_b; occ_b = tmp;
+        }
+        scatter(occ_a, t, a, false);                                      // t = T, or arr_a: the layer occ_a still holds
+        __syncthreads();
+        if (T < 0) continue;
+
+        // adopt: backtrack from (T, ga), the first of wait, up, down, left, right whose predecessor is reached and is no exchange
+        int v = ga;
+        for (int tt = T; tt >= 1; tt--) {
+            const uint16_t *R = L.reach + (size_t)(tt - 1) * units;
+            int ex = -1;                                                  // where the agent that stands on v at tt - 1 goes
+            for (int b = lane; b < n_agents; b += 64)
+                if (b != a && P[(size_t)(tt - 1) * n_agents + b] == v) ex = P[(size_t)tt * n_agents + b];
+            for (int off = 32; off > 0; off >>= 1) ex = max(ex, __shfl_xor(ex, off, 64));
+            int u = v;
+            const int back = (lane == 1) ? 2 : (lane == 2) ? 1 : (lane == 3) ? 4 : (lane == 4) ? 3 : 0;      // u = v - move[lane]
+            const bool ok = lane < 5 && neighbour(v, back, H, W, u) && reach_bit(R, u) && u != ex;
+            const unsigned m = (unsigned)(__ballot(ok) & 31ull);
+            if (m == 0u) break;                                           // (cannot happen: v was reached from some cell of the layer before)
+            if (lane == 0) P[(size_t)tt * n_agents + a] = v;
+            v = __shfl(u, __ffs((int)m) - 1, 64);
+        }
+        for (int tt = T + 1 + lane; tt <= length; tt += 64) P[(size_t)tt * n_agents + a] = ga;
+        if (lane == 0) L.arr[a] = T;
+        adopted++;
+        __syncthreads();
+        int len = 0;
+        for (int b = lane; b < n_agents; b += 64) len = max(len, L.arr[b]);
+        for (int off = 32; off > 0; off >>= 1) len = max(len, __shfl_xor(len, off, 64));
+        length = len;
+    }
+
+    __syncthreads();
+    int soc = 0;
+    for (int b = lane; b < n_agents; b += 64) {
+        garr[b] = L.arr[b];
+        soc += L.arr[b];
+    }
+    for (int off = 32; off > 0; off >>= 1) soc += __shfl_xor(soc, off, 64);
+    if (lane == 0) {
+        rs[R_ACTIVE] = adopted ? 1 : 0; rs[R_LENGTH] = length; rs[R_SOC_AFTER] = soc; rs[R_ROUNDS] += 1; rs[R_REPLANS] += adopted;
+        if (adopted) *A.adopted = 1;
+    }
+}
+
+// the final status and length into the search's state, the refined solution into sol: what search_skip_kernel / search_replay_kernel read
+__global__ __launch_bounds__(64) void refine_final_kernel(const RefineArgs A, int32_t *__restrict__ state, int8_t *__restrict__ sol)
+{
+    const int inst = blockIdx.x, lane = threadIdx.x, n_agents = A.n_agents;
+    const int32_t *rs = A.rstate + (size_t)inst * R_WORDS;
+    const int first = rs[R_FIRST_STATUS];
+    if ((first != 1 && first != 4) || rs[R_FIRST_LENGTH] > A.horizon) return;          // left as it is
+    const int length = rs[R_LENGTH], status = length <= A.max_steps ? 1 : 4;
+    const int32_t *P = A.path + (size_t)inst * (A.horizon + 1) * n_agents;
+    const size_t g0 = (size_t)inst * n_agents;
+    for (int idx = lane; idx < n_agents * A.max_steps; idx += 64) {
+        const int a = idx / A.max_steps, t = idx - a * A.max_steps;
+        int k = 0;
+        if (status == 1 && t < length) k = step_action(P[(size_t)(t + 1) * n_agents + a] - P[(size_t)t * n_agents + a], A.W);
+        sol[(g0 + a) * (size_t)A.max_steps + t] = (int8_t)k;
+    }
+    if (lane == 0) {
+        state[(size_t)inst * S_WORDS + S_STATUS] = status;
+        state[(size_t)inst * S_WORDS + S_LENGTH] = length;
+    }
+}
+
 }  // namespace
 
 struct mgpt_expert {
@@ -689,7 +941,12 @@ struct mgpt_expert {
     // the corridor swap rule (mgpt_expert_set_swap): off by default; the degree map is built when it is first turned on
     bool swap = false;
     uint8_t *deg = nullptr;                     // [n_grids][H*W]
-    DeviceArena mem, search_mem, deg_mem;       // occ .. len; ls; deg
+    // refinement of found solutions (mgpt_expert_set_refine): off (max_rounds 0, all NULL) by default
+    struct Refine {                             // sizes and buffers, owned by refine_mem
+        int max_rounds = 0, horizon = 0;
+        int32_t *path = nullptr, *arr = nullptr, *rstate = nullptr, *adopted = nullptr;
+    } rf;
+    DeviceArena mem, search_mem, deg_mem, refine_mem;   // occ .. len; ls; deg; rf
 };
 
 // launches the SWAP instantiation of a kernel: one wave64 workgroup per instance, its arrays in dynamic LDS
@@ -700,11 +957,30 @@ static void launch_swap(const mgpt_expert *ex, bool search, void (*with)(P...), 
 }
 constexpr int kDefaultItersPerLaunch = 512;     // the slice after which the host looks at the unfinished counter
 
+static void refine_free(mgpt_expert *ex)
+{
+    ex->refine_mem.release();
+    ex->rf = mgpt_expert::Refine();
+}
+
 static void search_free(mgpt_expert *ex)
 {
+    refine_free(ex);                                         // the pass reads the search's node store: it goes with it
     ex->search_mem.release();
     ex->ls = mgpt_expert::Search();
     ex->search = ex->solved = false;
+}
+
+// *running: an episode has begun and some instance is not done yet (reads the done flags: synchronises the device)
+static int episode_running(const mgpt_expert *ex, bool *running)
+{
+    *running = false;
+    if (!ex->have_reset || (ex->t == 0 && !ex->solved)) return MGPT_OK;
+    std::vector<uint8_t> done((size_t)ex->n_inst);
+    MGPT_HIP(hipDeviceSynchronize());
+    MGPT_HIP(hipMemcpy(done.data(), ex->done, done.size(), hipMemcpyDeviceToHost));
+    for (uint8_t d : done) *running |= d == 0;
+    return MGPT_OK;
 }
 
 // what the planner does not model: lifelong goal queues and the non-default collision rules
@@ -824,14 +1100,10 @@ extern "C" int mgpt_expert_set_swap(mgpt_expert *ex, int on)
 {
     MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(on == 0 || on == 1, MGPT_ERR_ARG, "on=%d: 0 or 1", on);
-    if (ex->have_reset && (ex->t > 0 || ex->solved)) {       // an episode has begun: it is over when every instance is done
-        std::vector<uint8_t> done((size_t)ex->n_inst);
-        MGPT_HIP(hipDeviceSynchronize());
-        MGPT_HIP(hipMemcpy(done.data(), ex->done, done.size(), hipMemcpyDeviceToHost));
-        bool running = false;
-        for (uint8_t d : done) running |= d == 0;
-        MGPT_REQUIRE(!running, MGPT_ERR_STATE, "mgpt_expert_set_swap in the middle of an episode (before mgpt_expert_reset or between episodes only)");
-    }
+    bool running = false;                                    // an episode that has begun is over when every instance is done
+    const int rc = episode_running(ex, &running);
+    if (rc != MGPT_OK) return rc;
+    MGPT_REQUIRE(!running, MGPT_ERR_STATE, "mgpt_expert_set_swap in the middle of an episode (before mgpt_expert_reset or between episodes only)");
     if (on) {
         MGPT_REQUIRE(lds_bytes(ex->n_agents, true, false) <= 64 * 1024 && (!ex->search || lds_bytes(ex->n_agents, true, true) <= 64 * 1024),
                      MGPT_ERR_UNSUPPORTED, "n_agents=%d: the frames with their swap agents do not fit 64 KB of LDS", ex->n_agents);
@@ -852,6 +1124,39 @@ extern "C" int mgpt_expert_set_swap(mgpt_expert *ex, int on)
         }
     }
     ex->swap = on != 0;
+    return MGPT_OK;
+}
+
+// the refinement pass of a solve: path, rounds until none adopts anything (one device counter per launch, as the search's), final
+static int refine_run(mgpt_expert *ex, hipStream_t s)
+{
+    RefineArgs A;
+    A.grids = ex->grids; A.goal = ex->goal; A.state = ex->ls.state; A.node_q = ex->ls.node_q; A.open = ex->ls.open; A.node_meta = ex->ls.node_meta;
+    A.path = ex->rf.path; A.arr = ex->rf.arr; A.rstate = ex->rf.rstate; A.adopted = ex->rf.adopted;
+    A.n_grids = ex->n_grids; A.n_agents = ex->n_agents; A.H = ex->H; A.W = ex->W; A.max_steps = ex->max_steps; A.horizon = ex->rf.horizon;
+    A.node_cap = ex->ls.node_cap;
+    {
+        ProfScope ps(P_EXPERT_REFINE_PATH, s);
+        hipLaunchKernelGGL(refine_path_kernel, dim3(ex->n_inst), dim3(64), 0, s, A);
+        MGPT_LAUNCH_CHECK();
+    }
+    const size_t lds = refine_lds_bytes(ex->n_agents, (int64_t)ex->H * ex->W, ex->rf.horizon);
+    int32_t adopted = 1;
+    for (int r = 0; r < ex->rf.max_rounds && adopted; r++) {
+        MGPT_HIP(hipMemsetAsync(ex->rf.adopted, 0, sizeof(int32_t), s));
+        {
+            ProfScope ps(P_EXPERT_REFINE_ROUND, s);
+            hipLaunchKernelGGL(refine_round_kernel, dim3(ex->n_inst), dim3(64), lds, s, A);
+            MGPT_LAUNCH_CHECK();
+        }
+        MGPT_HIP(hipMemcpyAsync(&adopted, ex->rf.adopted, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        MGPT_HIP(hipStreamSynchronize(s));
+    }
+    {
+        ProfScope ps(P_EXPERT_REFINE_FINAL, s);
+        hipLaunchKernelGGL(refine_final_kernel, dim3(ex->n_inst), dim3(64), 0, s, A, ex->ls.state, ex->ls.sol);
+        MGPT_LAUNCH_CHECK();
+    }
     return MGPT_OK;
 }
 
@@ -890,7 +1195,69 @@ extern "C" int mgpt_expert_solve(mgpt_expert *ex, void *stream)
         MGPT_HIP(hipStreamSynchronize(s));
     }
     MGPT_REQUIRE(!unfinished, MGPT_ERR_STATE, "the search left instances unfinished after %lld launches", (long long)launches);
+    if (ex->rf.max_rounds > 0) {
+        const int rc2 = refine_run(ex, s);
+        if (rc2 != MGPT_OK) return rc2;
+    }
     ex->solved = true;
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_expert_set_refine(mgpt_expert *ex, int max_rounds, int horizon)
+{
+    MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(max_rounds >= 0 && max_rounds <= (1 << 16), MGPT_ERR_ARG, "max_rounds=%d: 0 (off) .. 65536", max_rounds);
+    MGPT_REQUIRE(horizon == 0 || (horizon >= ex->max_steps && horizon <= (1 << 20)), MGPT_ERR_ARG,
+                 "horizon=%d: 0 (twice max_steps) or max_steps=%d .. 2^20", horizon, ex->max_steps);
+    MGPT_REQUIRE(ex->search, MGPT_ERR_STATE, "mgpt_expert_set_search must precede mgpt_expert_set_refine (the pass refines what the search found)");
+    bool running = false;
+    const int rc = episode_running(ex, &running);
+    if (rc != MGPT_OK) return rc;
+    MGPT_REQUIRE(!running, MGPT_ERR_STATE, "mgpt_expert_set_refine in the middle of an episode (before mgpt_expert_reset or between episodes only)");
+    if (max_rounds == 0) {
+        refine_free(ex);
+        return MGPT_OK;
+    }
+    const int hz = horizon ? horizon : 2 * ex->max_steps;
+    const int64_t cells = (int64_t)ex->H * ex->W;
+    const size_t lds = refine_lds_bytes(ex->n_agents, cells, hz);
+    MGPT_REQUIRE(lds <= kRefineMaxLds, MGPT_ERR_UNSUPPORTED,
+                 "%d x %d cells, horizon %d, %d agents: the %d reach layers of %d bytes with two cell arrays (%zu bytes in all) do not fit the "
+                 "%zu bytes of LDS a workgroup may hold", ex->H, ex->W, hz, ex->n_agents, hz + 1, 2 * refine_units(cells), lds, kRefineMaxLds);
+    if (lds > 64 * 1024)                                     // above the default limit of a launch's dynamic LDS
+        MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(refine_round_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRefineMaxLds));
+    refine_free(ex);
+    const size_t ni = (size_t)ex->n_inst, na = (size_t)ex->n_agents;
+    hipError_t e = ex->refine_mem.alloc(&ex->rf.path, ni * (size_t)(hz + 1) * na * sizeof(int32_t));
+    if (e == hipSuccess) e = ex->refine_mem.alloc(&ex->rf.arr, ni * na * sizeof(int32_t));
+    if (e == hipSuccess) e = ex->refine_mem.alloc(&ex->rf.rstate, ni * R_WORDS * sizeof(int32_t));
+    if (e == hipSuccess) e = ex->refine_mem.alloc(&ex->rf.adopted, sizeof(int32_t));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("device allocation failed in mgpt_expert_set_refine (horizon=%d, %d instances x %d agents): %s", hz, ex->n_inst, ex->n_agents,
+                  hipGetErrorString(e));
+        refine_free(ex);
+        return MGPT_ERR_HIP;
+    }
+    ex->rf.max_rounds = max_rounds;
+    ex->rf.horizon = hz;
+    ex->solved = false;                                      // what a solve before this call left is not a refined result
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_expert_copy_refine(mgpt_expert *ex, int32_t *d_first_status, int32_t *d_first_length, int32_t *d_soc_before, int32_t *d_soc_after,
+                                       int32_t *d_rounds, int32_t *d_replans, void *stream)
+{
+    MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(ex->search && ex->solved && ex->rf.max_rounds > 0, MGPT_ERR_STATE,
+                 "mgpt_expert_set_refine (max_rounds > 0) and mgpt_expert_solve must precede mgpt_expert_copy_refine");
+    hipStream_t s = (hipStream_t)stream;
+    int32_t *outs[6] = {d_first_status, d_first_length, d_soc_before, d_soc_after, d_rounds, d_replans};
+    const int words[6] = {R_FIRST_STATUS, R_FIRST_LENGTH, R_SOC_BEFORE, R_SOC_AFTER, R_ROUNDS, R_REPLANS};
+    for (int j = 0; j < 6; j++)
+        if (outs[j])
+            MGPT_HIP(hipMemcpy2DAsync(outs[j], sizeof(int32_t), ex->rf.rstate + words[j], R_WORDS * sizeof(int32_t), sizeof(int32_t), (size_t)ex->n_inst,
+                                      hipMemcpyDeviceToDevice, s));
     return MGPT_OK;
 }
 

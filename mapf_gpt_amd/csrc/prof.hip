@@ -27,7 +27,8 @@ static const char *kProfNames[P_COUNT] = {
     "gpt_attention_last", "gpt_gemm_attn_proj_last", "gpt_mlp_fused_last",
     "gpt_head_seq", "gpt_score",
     "ds_row_hash", "ds_insert", "ds_classify", "ds_resolve", "ds_balance", "ds_select", "ds_gather",
-    "expert_pibt_plan", "expert_lacam_search", "expert_cell_degree"};
+    "expert_pibt_plan", "expert_lacam_search", "expert_cell_degree",
+    "expert_refine_path", "expert_refine_round", "expert_refine_final"};
 
 struct ProfState {
     std::mutex mu;

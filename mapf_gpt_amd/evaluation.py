@@ -197,15 +197,16 @@ class PIBTConfig:
 
 class LaCAMConfig(PIBTConfig):
     """Config of the `name: LaCAM` algorithm: the same expert with a LaCAM search in front of every episode (DESIGN.md section 21);
-    name, seed, device, max_iters, swap."""
+    name, seed, device, max_iters, swap, refine_rounds and refine_horizon (the refinement pass of section 26, off by default)."""
 
-    def __init__(self, name="LaCAM", seed=0, device="cuda", max_iters=4096, swap=False):
+    def __init__(self, name="LaCAM", seed=0, device="cuda", max_iters=4096, swap=False, refine_rounds=0, refine_horizon=None):
         super().__init__(name, seed, device, swap)
         self.max_iters = int(max_iters)
+        self.refine_rounds, self.refine_horizon = int(refine_rounds or 0), (int(refine_horizon) if refine_horizon else None)
 
 
 def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, max_rows_per_batch=65536, rank=0, world=1,
-               print_fn=print, trace=None, retire_done=False, log_actions=False, search_status=None):
+               print_fn=print, trace=None, retire_done=False, log_actions=False, search_status=None, refine_stats=None):
     """Run `evaluation_config` (dict in the reference's YAML schema).  Returns the list of result records (on every
     rank); writes `<eval_dir>/<algorithm>.json` and prints the tabular views on rank 0.
     `trace(kind, payload)` (tests): called with ("reset", {algorithm, runs, grids, pos, goal, max_steps}) for every batch
@@ -217,7 +218,9 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
     placement, sharding and metrics gather.  log_actions: the role of the reference's create_logging_env (create_env.py:8-33) -- the
     PIBT records also carry `made_actions` (per agent, cut to the episode's length) and `init_positions` (padded coordinates), the
     expert log that dataset_build / dataset_tokenizer consume; one rank only.  An algorithm whose `name` is LaCAM is the same expert
-    with search="lacam"; search_status (a dict) then receives the count of this rank's instances per search status."""
+    with search="lacam"; search_status (a dict) then receives the count of this rank's instances per (final) search status, and with
+    `refine_rounds` in the entry refine_stats (a dict) receives `refined` (instances whose length or sum of costs fell), `rescued` (first
+    status 4, final status 1) and `soc_before` / `soc_after` summed over the refined instances."""
     import torch
     from .runner import BatchedRunner, gather_metrics, shard_range
 
@@ -261,7 +264,10 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                         pos[k], goal[k] = _maps.place_agents(g, n_agents, int(runs[i][0].get("seed", 0)), s_ok, g_ok)
                     if is_pibt:
                         from .expert import BatchedExpert
-                        search = dict(search="lacam", max_iters=cfg.max_iters) if isinstance(cfg, LaCAMConfig) else {}
+                        search = {}
+                        if isinstance(cfg, LaCAMConfig):
+                            search = dict(search="lacam", max_iters=cfg.max_iters, refine_rounds=cfg.refine_rounds,
+                                          refine_horizon=cfg.refine_horizon)
                         run = BatchedExpert(grids, len(mine), n_agents, max_steps, seed=cfg.seed, device=cfg.device, inst_offset=lo,
                                             swap=cfg.swap, **search)
                     else:
@@ -282,6 +288,13 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                         if run.search and search_status is not None:
                             for v in run.search_stats()[0].cpu().tolist():
                                 search_status[v] = search_status.get(v, 0) + 1
+                        if run.search and run.refine_rounds and refine_stats is not None:
+                            final, _, _, length = (x.cpu().numpy() for x in run.search_stats())
+                            first, first_len, soc0, soc1, _, _ = (x.cpu().numpy() for x in run.refine_stats())
+                            better = (length < first_len) | (soc1 < soc0)
+                            for k, v in (("refined", better.sum()), ("rescued", ((first == 4) & (final == 1)).sum()),
+                                         ("soc_before", soc0[better].sum()), ("soc_after", soc1[better].sum())):
+                                refine_stats[k] = refine_stats.get(k, 0) + int(v)
                     else:
                         run.reset(torch.from_numpy(pos), torch.from_numpy(goal), goal_queue=queue)
                     if trace is None:

@@ -13,6 +13,7 @@ stand on their goals at once, and episodes that do not end with CSR = 1 are drop
     python -m mapf_gpt_amd.expert --config CONFIG.yaml --maps MAPS.yaml --out DIR      # writes DIR/PIBT.json
     python -m mapf_gpt_amd.expert --algo lacam [--max-iters N] ...                      # writes DIR/LaCAM.json
     python -m mapf_gpt_amd.expert [--algo lacam] --swap ...                             # the same files, with the corridor swap rule
+    python -m mapf_gpt_amd.expert --algo lacam --refine-rounds N [--refine-horizon H]   # ... with found solutions refined
 
 `search="lacam"` puts a LaCAM search (plain depth-first LaCAM over this PIBT as its configuration generator) in
 front of the episode: reset() solves every instance on the device, an instance solved within the step cap replays its solution, every
@@ -22,10 +23,16 @@ other instance is planned step by step by PIBT as before, so the expert is never
 search: two agents that meet head-on in a corridor walk together to the nearest junction and exchange there.  Off by default; with it
 off every result is bit for bit what it was.
 
+`refine_rounds=N` (search mode only) refines every found solution of up to `refine_horizon` steps before the episode (DESIGN.md section
+26): rounds in which every agent is replanned once, alone, against the others' fixed paths, until a round changes nothing or N rounds
+have run.  No agent's arrival ever grows, so a solution longer than the step cap may come under it and is then replayed.  Off by default.
+
 The config is an evaluation YAML (eval_configs/<folder>/<folder>.yaml): its `environment:` block is run; its `algorithms:` block is
 replaced by one PIBT entry (seed from --seed).  DIR/PIBT.json is what `dataset_build.split_by_map` and `dataset_build --logs` take
 where the reference has LaCAM.json.  Prints one JSON line: episodes, solved, rows, seconds (with --algo lacam also `status`: the
-count of instances per search status; with --swap also `"swap": true`).
+count of instances per search status; with --swap also `"swap": true`; with --refine-rounds also `refine_rounds`, `refined`: instances
+whose length or sum of costs fell, `rescued`: instances the search left over the step cap that are now replayed, and `soc_before` /
+`soc_after`: the sum of costs summed over the refined instances).
 """
 import argparse
 import ctypes
@@ -45,9 +52,11 @@ class BatchedExpert:
     """Same shape as BatchedRunner: owns a BatchedEnv and a BatchedTokenizer (used for its BFS distance fields only)."""
 
     def __init__(self, grids, n_inst, n_agents, max_episode_steps, seed=0, device="cuda", inst_offset=0, search=None, max_iters=4096,
-                 iters_per_launch=None, hash_bits=0, swap=False):
+                 iters_per_launch=None, hash_bits=0, swap=False, refine_rounds=0, refine_horizon=None):
         if search not in (None, "lacam"):
             raise ValueError(f"search={search!r}: None or 'lacam'")
+        if refine_rounds and not search:
+            raise ValueError("refine_rounds needs search='lacam': the pass refines what the search found")
         self.device = torch.device(device)
         self.env = BatchedEnv(grids, n_inst, n_agents, max_episode_steps, device=device)
         self.tok = BatchedTokenizer(grids, n_inst, n_agents, device=device)
@@ -66,12 +75,22 @@ class BatchedExpert:
         self.swap = False
         if swap:
             self.set_swap(True)
+        self.refine_rounds = 0
+        if refine_rounds:
+            self.set_refine(refine_rounds, refine_horizon)
 
     def set_swap(self, on):
         """Turn the corridor swap rule on or off: before reset() or between episodes (MGPTError with ERR_STATE in the middle of one)."""
         with _lib.on_device(self.device):
             _lib.check(_lib.lib().mgpt_expert_set_swap(self._h, 1 if on else 0))
         self.swap = bool(on)
+
+    def set_refine(self, max_rounds, horizon=None):
+        """Turn the refinement pass of reset() on (max_rounds >= 1; horizon None = twice max_episode_steps) or off (0): before reset()
+        or between episodes, in search mode only (MGPTError with ERR_STATE otherwise)."""
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_set_refine(self._h, int(max_rounds), int(horizon or 0)))
+        self.refine_rounds = int(max_rounds)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -98,6 +117,15 @@ class BatchedExpert:
         out = [torch.empty((self.n_inst,), dtype=torch.int32, device=self.device) for _ in range(4)]
         with _lib.on_device(self.device):
             _lib.check(_lib.lib().mgpt_expert_copy_search(self._h, *[_lib.ptr(t) for t in out], _lib.stream_ptr()))
+        return tuple(out)
+
+    def refine_stats(self):
+        """-> the search's own status and length, sum of costs before and after, rounds run, replans adopted: int32 [n_inst] device
+        tensors (the last four are 0 for an instance the pass left as it is).  With the pass on, search_stats() and solution() report
+        the final status, length and solution, which are what the episode replays."""
+        out = [torch.empty((self.n_inst,), dtype=torch.int32, device=self.device) for _ in range(6)]
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_copy_refine(self._h, *[_lib.ptr(t) for t in out], _lib.stream_ptr()))
         return tuple(out)
 
     def solution(self):
@@ -166,6 +194,8 @@ def main(argv=None):
     ap.add_argument("--algo", choices=["pibt", "lacam"], default="pibt", help="lacam: a LaCAM search in front of every episode")
     ap.add_argument("--max-iters", type=int, default=4096, help="--algo lacam: iterations of the search per instance")
     ap.add_argument("--swap", action="store_true", help="the corridor swap rule in the generator (episode and search)")
+    ap.add_argument("--refine-rounds", type=int, default=0, help="--algo lacam: rounds of the refinement pass over found solutions (0 = off)")
+    ap.add_argument("--refine-horizon", type=int, default=None, help="solutions of up to this many steps are refined (default: twice the step cap)")
     a = ap.parse_args(argv)
     from . import evaluation as ev
     cfg = ev.load_yaml(a.config)
@@ -177,10 +207,15 @@ def main(argv=None):
         algo = {"name": "LaCAM", "seed": a.seed, "device": a.device, "max_iters": a.max_iters}
     if a.swap:
         algo["swap"] = True
+    if a.refine_rounds:
+        if a.algo != "lacam":
+            ap.error("--refine-rounds needs --algo lacam")
+        algo.update(refine_rounds=a.refine_rounds, refine_horizon=a.refine_horizon)
     cfg = {"environment": cfg["environment"], "algorithms": {algo["name"]: algo}}
-    status = {}
+    status, refine = {}, {}
     t0 = time.perf_counter()
-    res = ev.evaluation(cfg, eval_dir=a.out, registry=reg, print_fn=lambda *_: None, log_actions=True, search_status=status)
+    res = ev.evaluation(cfg, eval_dir=a.out, registry=reg, print_fn=lambda *_: None, log_actions=True, search_status=status,
+                        refine_stats=refine)
     solved = [r for r in res if r["metrics"]["CSR"] >= 1]
     rows = sum(len(r["metrics"]["made_actions"]) * (int(r["metrics"]["ep_length"]) + 1) for r in solved)     # dataset rows of the solved episodes
     line = {"episodes": len(res), "solved": len(solved), "rows": rows, "seconds": round(time.perf_counter() - t0, 3)}
@@ -188,6 +223,8 @@ def main(argv=None):
         line["status"] = {str(k): int(v) for k, v in sorted(status.items())}
     if a.swap:
         line["swap"] = True
+    if a.refine_rounds:
+        line.update(refine_rounds=a.refine_rounds, **{k: int(refine.get(k, 0)) for k in ("refined", "rescued", "soc_before", "soc_after")})
     print(json.dumps(line))
     return 0
 

@@ -14,6 +14,11 @@
                    status, the search's time per instance and its iterations; time adds the solve (HIP events around it, and the search
                    kernel's own time from the timing hooks), iterations per second and microseconds per iteration.
 
+    --refine-rounds N   (--algo lacam) the refinement pass over found solutions, --refine-horizon H its horizon.
+                   Records then carry the search's own status counts next to the final ones, the instances refined and rescued, the
+                   sum of costs before and after and the rounds run; time adds the pass's kernels from the timing hooks and the solve
+                   with the pass off on the same context.  A shape whose reach layers do not fit is reported as refused.
+
     --swap         the corridor swap rule in the generator, with either --algo; every record then carries
                    "swap": true, and time (pibt) adds the degree map's own time from the timing hooks.
 
@@ -63,7 +68,23 @@ def timed(fn):
 
 
 def search_kw(a):
-    return dict(search="lacam", max_iters=a.max_iters, iters_per_launch=a.iters_per_launch) if a.algo == "lacam" else {}
+    if a.algo != "lacam":
+        return {}
+    return dict(search="lacam", max_iters=a.max_iters, iters_per_launch=a.iters_per_launch, refine_rounds=a.refine_rounds,
+                refine_horizon=a.refine_horizon)
+
+
+def refine_fields(ex, st, length):
+    """What the refinement pass adds to a record (st, length: the final status and length)."""
+    first, first_len, soc0, soc1, rounds, replans = (t.cpu().numpy() for t in ex.refine_stats())
+    better, took = (length < first_len) | (soc1 < soc0), rounds > 0
+    mean = lambda x, m: round(float(x[m].mean()), 2) if m.any() else None
+    return {"refine_rounds": ex.refine_rounds, "first_status": {str(k): int((first == k).sum()) for k in (1, 2, 3, 4)},
+            "refined": int(better.sum()), "rescued": int(((first == 4) & (st == 1)).sum()), "replans": int(replans.sum()),
+            "max_rounds_of_an_instance": int(rounds.max()), "mean_first_length_of_refined": mean(first_len, took),
+            "mean_length_of_refined": mean(length, took), "mean_soc_before_of_refined": mean(soc0, took),
+            "mean_soc_after_of_refined": mean(soc1, took), "mean_first_length_of_first_status_1": mean(first_len, first == 1),
+            "mean_soc_before_of_first_status_1": mean(soc0, first == 1), "mean_soc_after_of_status_1": mean(soc1, st == 1)}
 
 
 def search_fields(ex, search_ms, kernel_ms=None):
@@ -78,6 +99,8 @@ def search_fields(ex, search_ms, kernel_ms=None):
     if kernel_ms is not None:
         rec["search_kernel_ms"] = round(kernel_ms[0], 3)
         rec["search_launches"] = int(kernel_ms[1])
+    if ex.refine_rounds:
+        rec.update(refine_fields(ex, st, length))
     return rec
 
 
@@ -89,17 +112,35 @@ def time_search(name, a):
     else:
         grid, s_ok, g_ok = maps.load_named(map_name)
     pos, goal = make_instances(grid, n_inst, n, 0, s_ok, g_ok)
-    ex = BatchedExpert(grid, n_inst, n, steps, seed=7, swap=SWAP, **search_kw(a))
+    try:
+        ex = BatchedExpert(grid, n_inst, n, steps, seed=7, swap=SWAP, **search_kw(a))
+    except _lib.MGPTError as e:
+        if e.code != _lib.ERR_UNSUPPORTED:
+            raise
+        emit({"tool": "bench_expert", "what": "time", "algo": "lacam", "shape": name, "map": map_name, "instances": n_inst, "agents": n,
+              "refused": str(e)}, a.out)
+        return
     h = ex._h
-    solve_ms = []
-    for rep in range(a.repeats + 1):                 # episode 0 warms up
-        ex.search = None                             # reset without the solve, then the solve alone between two events
-        ex.reset(pos, goal)
-        ex.search = "lacam"
-        with _lib.on_device(ex.device):
-            ms = timed(lambda: _lib.check(_lib.lib().mgpt_expert_solve(h, _lib.stream_ptr())))
-        if rep:
-            solve_ms.append(ms)
+
+    def solves():
+        out = []
+        for rep in range(a.repeats + 1):             # episode 0 warms up
+            ex.search = None                         # reset without the solve, then the solve alone between two events
+            ex.reset(pos, goal)
+            ex.search = "lacam"
+            with _lib.on_device(ex.device):
+                ms = timed(lambda: _lib.check(_lib.lib().mgpt_expert_solve(h, _lib.stream_ptr())))
+            if rep:
+                out.append(ms)
+        return out
+
+    off_ms = None
+    if a.refine_rounds:                              # the same context with the pass off, then on again
+        ex.set_refine(0)
+        off_ms = solves()
+        ex.run(steps)                                # the switch is refused in the middle of an episode: run this one to its end
+        ex.set_refine(a.refine_rounds, a.refine_horizon)
+    solve_ms = solves()
     _lib.prof_enable(True)
     _lib.prof_reset()
     ex.reset(pos, goal)
@@ -110,6 +151,11 @@ def time_search(name, a):
     rec = {"tool": "bench_expert", "what": "time", "algo": "lacam", "shape": name, "map": map_name, "instances": n_inst, "agents": n,
            "steps": steps, "iters_per_launch": a.iters_per_launch, "solve_ms_runs": [round(x, 3) for x in solve_ms]}
     rec.update(search_fields(ex, float(np.median(solve_ms)), prof.get("expert_lacam_search", (0.0, 0))))
+    if a.refine_rounds:
+        rec["solve_ms_runs_with_the_pass_off"] = [round(x, 3) for x in off_ms]
+        for k in ("path", "round", "final"):
+            ms, launches = prof.get("expert_refine_" + k, (0.0, 0))
+            rec["refine_%s_ms" % k], rec["refine_%s_launches" % k] = round(ms, 3), int(launches)
     rec.update({"ms_run_after_solve": round(run_ms, 3), "solved": int(m[:, 0].sum()), "mean_isr": round(float(m[:, 1].mean()), 4)})
     emit(rec, a.out)
 
@@ -175,6 +221,8 @@ def solve_shape(n, hwd, n_inst, cap, a):
            "mean_isr": round(float(m[:, 1].mean()), 4)}
     if a.algo == "lacam":                             # reset = BFS + search; the first shape's figure includes the code object's load
         rec.update(search_fields(ex, reset_ms))
+        replayed = ex.search_stats()[0].cpu().numpy() == 1
+        rec["mean_soc_of_status_1"] = round(float(m[replayed, 2].mean()), 2) if replayed.any() else None
         rec["search_ms_includes"] = "reset (BFS)"
     emit(rec, a.out)
 
@@ -189,6 +237,9 @@ def main():
     ap.add_argument("--max-iters", type=int, default=4096)
     ap.add_argument("--iters-per-launch", type=int, default=None, help="default: the library's slice")
     ap.add_argument("--swap", action="store_true", help="the corridor swap rule in the generator")
+    ap.add_argument("--refine-rounds", type=int, default=0, help="--algo lacam: rounds of the refinement pass (0 = off)")
+    ap.add_argument("--refine-horizon", type=int, default=None, help="default: twice the step cap")
+    ap.add_argument("--maze-only", action="store_true", help="solve: the three maze shapes only")
     a = ap.parse_args()
     global SWAP
     SWAP = a.swap
@@ -200,7 +251,9 @@ def main():
             else:
                 time_shape(name, a.repeats, a.out)
     else:
-        for n, hwd, n_inst, cap in SOLVE_SHAPES + MAZE_SHAPES:
+        if a.refine_rounds and a.algo != "lacam":
+            ap.error("--refine-rounds needs --algo lacam")
+        for n, hwd, n_inst, cap in ([] if a.maze_only else SOLVE_SHAPES) + MAZE_SHAPES:
             solve_shape(n, hwd, n_inst, cap, a)
 
 
