@@ -254,7 +254,7 @@ struct ModeBuilder {
                                nullptr, P + lo.attn_w, P + lo.ln1, P + lo.proj_w, m->m6.attn256q_pk[l], 1.0f / m->m6.attn256_inv[l], 1.0f / m->pl.proj[l].inv_scale);
             MGPT_LAUNCH_CHECK();
         }
-        MGPT_HIP(set_max_lds_each(fastk::kA256Lds<NP>, &fastk::attn256q_kernel<T, NP>, &fastk::attn256q_kernel<T, NP, 0, true>));
+        MGPT_HIP(set_max_lds_each(fastk::kA256Lds<NP>, &fastk::attn256q_kernel<T, NP>, &fastk::attn256q_kernel<T, NP, true>));
         if ((rc = ensure_embed_table(g)) != MGPT_OK) return rc;
         MGPT_HIP(m->mem.alloc(&m->m6.attn256q_spill, (size_t)f.n_cu * 8 * 14 * NP * 1024));
         // Layer 0 of large calls from a (position, token) table of q | k | v: its input row is etab[position][token], so the row's
@@ -263,7 +263,7 @@ struct ModeBuilder {
         // entry is bit-identical to what layer 0 computes.  (MGPT_L0_TABLE=0 in the environment keeps the EMB kernel on layer 0.)
         if (f.l0_qkv_table) {
             ProfScope ps(P_PACK, nullptr);
-            MGPT_HIP(set_max_lds_each(fastk::kA256Lds<NP>, &fastk::attn256q_kernel<T, NP, 0, true, 1>, &fastk::attn256q_kernel<T, NP, 0, false, 2>));
+            MGPT_HIP(set_max_lds_each(fastk::kA256Lds<NP>, &fastk::attn256q_kernel<T, NP, true, 1>, &fastk::attn256q_kernel<T, NP, false, 2>));
             MGPT_HIP(m->mem.alloc(&m->m6.l0_table, (size_t)kT * kV * fastk::kL0TabEntryBytes<NP>));
             DeviceArena tmp;                                 // the synthetic rows: freed on every way out, after the synchronise on the good one
             float *xt = nullptr;
@@ -272,9 +272,9 @@ struct ModeBuilder {
             MGPT_HIP(tmp.alloc(&tk, (size_t)kV * kT));
             for (int j = 0; j < kV; j++) MGPT_HIP(hipMemset(tk + (size_t)j * kT, j, kT));
             const float scale_log2e = (1.0f / sqrtf((float)g->hs)) * 1.44269504088896340736f;    // (as forward_chunk)
-            hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true, 1>), dim3((unsigned)std::min(kV, f.n_cu)), dim3(512), (size_t)fastk::kA256Lds<NP>, nullptr, xt,
+            hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, true, 1>), dim3((unsigned)std::min(kV, f.n_cu)), dim3(512), (size_t)fastk::kA256Lds<NP>, nullptr, xt,
                                m->m6.attn256q_pk[0], m->m6.attn256_inv[0], scale_log2e, m->pl.proj[0].inv_scale, m->m6.attn256q_spill, kV,
-                               (unsigned long long *)nullptr, tk, g->embed_table, m->m6.l0_table);
+                               tk, g->embed_table, m->m6.l0_table);
             MGPT_LAUNCH_CHECK();
             MGPT_HIP(hipDeviceSynchronize());
         }
@@ -651,17 +651,16 @@ struct Chunk {
             // ATTN_256Q (gpt_kernels_c256b.h: the projection steps and the tail on v_mfma_f32_16x16x32)
             const bool emb = p.embed == EMBED_TABLE256 && l == 0;
             if (emb && p.l0_qkv_table)                               // (q | k | v of layer 0 from the (position, token) table)
-                hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, false, 2>), grid, dim3(512), (size_t)fastk::kA256Lds<NP>, s, g->x,
+                hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, false, 2>), grid, dim3(512), (size_t)fastk::kA256Lds<NP>, s, g->x,
                                    m->m6.attn256q_pk[l], m->m6.attn256_inv[l], scale_log2e, m->pl.proj[l].inv_scale, m->m6.attn256q_spill, rows,
-                                   (unsigned long long *)nullptr, tokens, g->embed_table, m->m6.l0_table);
+                                   tokens, g->embed_table, m->m6.l0_table);
             else if (emb)
-                hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, 0, true>), grid, dim3(512), (size_t)fastk::kA256Lds<NP>, s, g->x,
+                hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP, true>), grid, dim3(512), (size_t)fastk::kA256Lds<NP>, s, g->x,
                                    m->m6.attn256q_pk[l], m->m6.attn256_inv[l], scale_log2e, m->pl.proj[l].inv_scale, m->m6.attn256q_spill, rows,
-                                   (unsigned long long *)nullptr, tokens, g->embed_table);
+                                   tokens, g->embed_table);
             else
                 hipLaunchKernelGGL((fastk::attn256q_kernel<T, NP>), grid, dim3(512), (size_t)fastk::kA256Lds<NP>, s, g->x,
-                                   m->m6.attn256q_pk[l], m->m6.attn256_inv[l], scale_log2e, m->pl.proj[l].inv_scale, m->m6.attn256q_spill, rows,
-                                   (unsigned long long *)nullptr);
+                                   m->m6.attn256q_pk[l], m->m6.attn256_inv[l], scale_log2e, m->pl.proj[l].inv_scale, m->m6.attn256q_spill, rows);
         }
         MGPT_LAUNCH_CHECK();
         return MGPT_OK;
@@ -705,7 +704,7 @@ struct Chunk {
             // LN1 + QKV + attention, one workgroup per (row, head): q, k, v stay on chip -> y operand planes for the out-projection
             ProfScope ps(P_ATTN, s);
             hipLaunchKernelGGL((fastk::attn256_kernel<T, NP>), dim3((unsigned)rows * 8), dim3(512), (size_t)fastk::kA256Lds<NP>, s,
-                               g->x, m->m6.attn256_pk[l], m->m6.attn256_inv[l], scale_log2e, m->ws.y[0], (unsigned long long *)nullptr);
+                               g->x, m->m6.attn256_pk[l], m->m6.attn256_inv[l], scale_log2e, m->ws.y[0]);
             MGPT_LAUNCH_CHECK();
         } else {
             if ((rc = qkv_gemms(l, a)) != MGPT_OK) return rc;

@@ -19,34 +19,12 @@ constexpr int kAttNvb1 = 10, kAttNvb2 = 6;     // VALU instructions placed behin
 // on the synthetic N(0, 0.02) checkpoints, non-zero when the scores are made to spread)
 __device__ unsigned long long g_attn_fallbacks = 0;
 
-namespace attn_tiles_detail {
-template <class T, int NP>
-__device__ __forceinline__ void pack_octet(const f32x16 &v, int m, u32x4 (&dst)[2])
-{
-#pragma unroll
-    for (int wd = 0; wd < 4; wd++) {
-        unsigned a, b2;
-        split2p<T, NP>(v[8 * m + 2 * wd], v[8 * m + 2 * wd + 1], a, b2);
-        dst[0][wd] = a; dst[1][wd] = b2;
-    }
-}
-__device__ __forceinline__ void half_swap(float v, float &lower, float &upper)
-{
-    lower = v; upper = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lower), "+v"(upper));
-}
-__device__ __forceinline__ float other_half_max(float v) { float a, b2; half_swap(v, a, b2); return fmaxf(a, b2); }
-__device__ __forceinline__ float other_half_sum(float v) { float a, b2; half_swap(v, a, b2); return a + b2; }
-}  // namespace attn_tiles_detail
-
 // The EXACT loop (rounds 2-4): online softmax with a running maximum per query, one key tile after the other (6 S MFMAs, the softmax
 // arithmetic, 6 PV MFMAs).  Since round 5 the FALLBACK of attention_tiles: a wave
 // whose scores outgrow the fp16 range of the P planes redoes its head here.
 template <class T, int NP, int KROW, int VROW, int HS>
 __device__ __forceinline__ void attention_exact_tiles(unsigned kr_addr, unsigned vr_addr, const u32x4 (&qf)[2][2], float sc2, f32x16 &o, float &l_run)
 {
-    using namespace attn_tiles_detail;
-    auto pack_octet = [&](const f32x16 &v, int m, u32x4 (&dst)[2]) { attn_tiles_detail::pack_octet<T, NP>(v, m, dst); };
     // (the start values come out of an opaque asm: as plain constants hipcc hoisted a zero block and -inf out of the ROW loop
     //  -- this path being cold -- and paid for their 17 registers with spills in the LayerNorm prologue)
     float m_run, zero;
@@ -117,7 +95,7 @@ __device__ __forceinline__ void attention_exact_tiles(unsigned kr_addr, unsigned
         l_run += other_half_sum(psum);
         u32x4 pf[2][2];
 #pragma unroll
-        for (int mm = 0; mm < 2; mm++) pack_octet(sc, mm, pf[mm]);
+        for (int mm = 0; mm < 2; mm++) pack_octet<T, NP>(sc, mm, pf[mm]);
         if (kt + 1 < kT / 32) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * NP) : "memory");   // v^T fragments landed, K of the next tile may fly
         else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
@@ -130,8 +108,6 @@ __device__ __forceinline__ void attention_exact_tiles(unsigned kr_addr, unsigned
 template <class T, int NP, int KROW, int VROW, int HS>
 __device__ __forceinline__ void attention_tiles(unsigned kr_addr, unsigned vr_addr, const u32x4 (&qf)[2][2], int lane, f32x16 &o, float &l_run)
 {
-    using namespace attn_tiles_detail;
-    auto pack_octet = [&](const f32x16 &v, int m, u32x4 (&dst)[2]) { attn_tiles_detail::pack_octet<T, NP>(v, m, dst); };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
 
@@ -205,7 +181,7 @@ __device__ __forceinline__ void attention_tiles(unsigned kr_addr, unsigned vr_ad
     __builtin_amdgcn_sched_barrier(0);
     load_k(I1{});
     // the reference of the head: the maximum of the query's first key tile.  sA[g] = S[query r][key tau(g, h)], in exponent
-    // units (QK_UNITS).  The scores of tiles 1-7 START from -reference: the first S MFMA of a tile takes the block nmb (the
+    // units (the callers scale q and k before the split).  The scores of tiles 1-7 START from -reference: the first S MFMA of a tile takes the block nmb (the
     // value in all 16 registers) as its C operand, so that exp2 applies to the accumulator as it is -- 16 multiply-adds per
     // tile fewer; tile 0, whose scores exist before the reference does, pays 16 additions once per head.
     f32x16 nmb;
@@ -249,7 +225,7 @@ __device__ __forceinline__ void attention_tiles(unsigned kr_addr, unsigned vr_ad
             cur[g] = __builtin_amdgcn_exp2f(cur[g]);
             l_part += cur[g];
         }
-        pack_octet(cur, 0, pf[0]);
+        pack_octet<T, NP>(cur, 0, pf[0]);
         place(std::integral_constant<int, LASTT ? 0 : 2 * NM>{}, std::integral_constant<int, kAttNvb1>{});
         if constexpr (!LASTT) asm volatile("" : "+v"(nxt));
         load_v(kt_c, I1{});
@@ -261,7 +237,7 @@ __device__ __forceinline__ void attention_tiles(unsigned kr_addr, unsigned vr_ad
             for (int g = 0; g < 16; g++) o[g] = 0.f;
         }
         o = amma(vf[0], pf[0], o);
-        pack_octet(cur, 1, pf[1]);
+        pack_octet<T, NP>(cur, 1, pf[1]);
         place(std::integral_constant<int, NM>{}, std::integral_constant<int, kAttNvb2>{});
         asm volatile("" : "+v"(o));
         if constexpr (HAS2) load_k(std::integral_constant<int, HAS2 ? kt + 2 : 0>{});

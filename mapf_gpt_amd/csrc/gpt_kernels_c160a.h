@@ -145,35 +145,11 @@ __global__ __launch_bounds__(512, 2) void attn160o_kernel(float *__restrict__ x,
         slot_cur = slot_next;
     };
     u32x4 wb[3][2][2];                                     // weight fragments: [set][fragment 2c / 2c+1][plane]
-    auto lds_frag = [&](unsigned addr, auto off_c, u32x4 &dst) {
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(decltype(off_c)::value) : "memory");
-    };
-    auto lds_pair = [&](unsigned slot_addr, auto ms_c, u32x4 (&dst)[2]) {
-        constexpr int ms = decltype(ms_c)::value;
-        lds_frag(slot_addr, std::integral_constant<int, ms * NP * 1024>{}, dst[0]);
-        if (NP == 2) lds_frag(slot_addr, std::integral_constant<int, (ms * NP + 1) * 1024>{}, dst[1]);
-        else dst[1] = dst[0];
-    };
     // chunk c of a step uses fragments 2c, 2c+1 in register set {0, 1, 0, 1, 2}[c], requested one chunk earlier; it requests the
     // fragments of the next chunk (chunk 4: the first fragments of the NEXT step into set 0, whose slot has landed -- the stream
     // is cyclic, there always is one; NEXT = false only in a row's last step: the next row's first fragments are requested after
     // its prologue instead, so that their registers are not live across the LayerNorm)
-    auto chunk_begin = [&](auto c_c, auto next_c) {
-        constexpr int c = decltype(c_c)::value;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (c < 4) {
-            constexpr int sn = (c + 1 == 4) ? 2 : ((c + 1) & 1);
-            lds_pair(cur_addr, std::integral_constant<int, 2 * c + 2>{}, wb[sn][0]);
-            lds_pair(cur_addr, std::integral_constant<int, 2 * c + 3>{}, wb[sn][1]);
-        } else if constexpr (decltype(next_c)::value) {
-            lds_pair(nxt_addr, std::integral_constant<int, 0>{}, wb[0][0]);
-            lds_pair(nxt_addr, std::integral_constant<int, 1>{}, wb[0][1]);
-        }
-        __builtin_amdgcn_sched_barrier(0);                 // the requests stay in front of this chunk's MFMAs
-    };
-    // the same requests one at a time (read n rides behind the chunk's MFMA n -- DESIGN 11.8)
-    constexpr bool PLACED = true;
+    // the requests go one at a time: read n rides behind the chunk's MFMA n
     auto chunk_read = [&](auto c_c, auto next_c, auto n_c) {
         constexpr int c = decltype(c_c)::value, n = decltype(n_c)::value;
         if constexpr (n < 2 * NP) {
@@ -186,32 +162,12 @@ __global__ __launch_bounds__(512, 2) void attn160o_kernel(float *__restrict__ x,
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    auto pin6 = [&]() {
-#pragma unroll
-        for (int n = 0; n < (NP == 2 ? 6 : 2); n++) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto pack_octet = [&](const f32x16 &v, int m, u32x4 (&dst)[2]) {
-#pragma unroll
-        for (int wd = 0; wd < 4; wd++) {
-            unsigned a, b2;
-            split2p<T, NP>(v[8 * m + 2 * wd], v[8 * m + 2 * wd + 1], a, b2);
-            dst[0][wd] = a; dst[1][wd] = b2;
-        }
-    };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>;
     using I3 = std::integral_constant<int, 3>;
     using I4 = std::integral_constant<int, 4>;
-    auto half_swap = [&](float v, float &lower, float &upper) {
-        lower = v; upper = v;
-        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lower), "+v"(upper));
-    };
-    auto other_half_max = [&](float v) { float a, b2; half_swap(v, a, b2); return fmaxf(a, b2); };
-    auto other_half_sum = [&](float v) { float a, b2; half_swap(v, a, b2); return a + b2; };
     // units of q and k: see attn256q_kernel (exponent units, 32 multiplies per head before the split)
-    constexpr bool QK_UNITS = true;
     const float q_units = scale_log2e * inv_scale, k_units = inv_scale;
 
     u32x4 xn[KS][2];                                       // operand planes: LayerNorm(x) during the heads, y during the tail
@@ -230,11 +186,9 @@ __global__ __launch_bounds__(512, 2) void attn160o_kernel(float *__restrict__ x,
             constexpr int c = decltype(c_c)::value;
             constexpr int s = (c == 4) ? 2 : (c & 1);
             constexpr int k0 = MODE == 0 ? 5 * j + c : 2 * c, k1 = MODE == 0 ? 5 * j + c : 2 * c + 1;
-            if constexpr (PLACED) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-            } else chunk_begin(c_c, next_c);
-            auto behind = [&](auto n_c) { if constexpr (PLACED) chunk_read(c_c, next_c, n_c); };
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            auto behind = [&](auto n_c) { chunk_read(c_c, next_c, n_c); };
             using N0 = std::integral_constant<int, 0>; using N1 = std::integral_constant<int, 1>;
             using N2 = std::integral_constant<int, 2>; using N3 = std::integral_constant<int, 3>;
             if (MODE == 2) {
@@ -254,10 +208,8 @@ __global__ __launch_bounds__(512, 2) void attn160o_kernel(float *__restrict__ x,
                     qa = T::mfma(wb[s][0][0], xn[k0][0], qa); behind(N0{}); ka = T::mfma(wb[s][1][0], xn[k1][0], ka); behind(N1{});
                 }
             }
-            if constexpr (PLACED) {
-                if (NP == 2) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); }
-                __builtin_amdgcn_sched_barrier(0);
-            } else pin6();
+            if (NP == 2) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); }
+            __builtin_amdgcn_sched_barrier(0);
             asm volatile("" : "+v"(qa), "+v"(ka));         // both chains are pinned to this chunk
         };
         chunk(I0{}); chunk(I1{}); chunk(I2{}); chunk(I3{}); chunk(I4{});
@@ -341,8 +293,8 @@ __global__ __launch_bounds__(512, 2) void attn160o_kernel(float *__restrict__ x,
             }
         }
         // the first fragments of the row's first step (its slot landed for every wave before the barrier of the step before)
-        lds_pair(nxt_addr, I0{}, wb[0][0]);
-        lds_pair(nxt_addr, I1{}, wb[0][1]);
+        lds_pair<NP>(nxt_addr, I0{}, wb[0][0]);
+        lds_pair<NP>(nxt_addr, I1{}, wb[0][1]);
 
         // ---- one head; LASTH (head 4): its output planes stay in registers (xn[8], xn[9]) and the planes of heads 0-3 are
         //      requested from the spill slab before its attention phase (xn is dead after the v step) ----
@@ -362,17 +314,15 @@ __global__ __launch_bounds__(512, 2) void attn160o_kernel(float *__restrict__ x,
             step(I0{}, I0{}, P4S{}, nothing, std::true_type{});
             step(I0{}, I1{}, P4S{}, nothing, std::true_type{});
             u32x4 qf[2][2];                                // B operand of S^T = K Q^T: [k-step][plane]
-            if constexpr (QK_UNITS) {
 #pragma unroll
-                for (int g = 0; g < 16; g++) { qa[g] *= q_units; ka[g] *= k_units; }
-            }
+            for (int g = 0; g < 16; g++) { qa[g] *= q_units; ka[g] *= k_units; }
 #pragma unroll
-            for (int ks = 0; ks < 2; ks++) pack_octet(qa, ks, qf[ks]);
+            for (int ks = 0; ks < 2; ks++) pack_octet<T, NP>(qa, ks, qf[ks]);
             {   // k -> sK[pl][key = tok0 + r][octet ks][half h]   (all waves passed this head's step syncs: the head before -- or the
                 // row before -- has finished its attention everywhere)
                 u32x4 kp[2][2];
 #pragma unroll
-                for (int ks = 0; ks < 2; ks++) pack_octet(ka, ks, kp[ks]);
+                for (int ks = 0; ks < 2; ks++) pack_octet<T, NP>(ka, ks, kp[ks]);
 #pragma unroll
                 for (int ks = 0; ks < 2; ks++)
 #pragma unroll
@@ -398,7 +348,7 @@ __global__ __launch_bounds__(512, 2) void attn160o_kernel(float *__restrict__ x,
                 for (int g = 0; g < 16; g++) qa[g] += ka[g];
                 u32x4 vp[2][2];
 #pragma unroll
-                for (int mm = 0; mm < 2; mm++) pack_octet(qa, mm, vp[mm]);
+                for (int mm = 0; mm < 2; mm++) pack_octet<T, NP>(qa, mm, vp[mm]);
 #pragma unroll
                 for (int mm = 0; mm < 2; mm++)
 #pragma unroll
@@ -420,12 +370,12 @@ __global__ __launch_bounds__(512, 2) void attn160o_kernel(float *__restrict__ x,
 #pragma unroll
                 for (int g = 0; g < 16; g++) o[g] *= inv;
                 if constexpr (LASTH) {
-                    pack_octet(o, 0, xn[8]);
-                    pack_octet(o, 1, xn[9]);
+                    pack_octet<T, NP>(o, 0, xn[8]);
+                    pack_octet<T, NP>(o, 1, xn[9]);
                 } else {
                     u32x4 yp[2][2];
-                    pack_octet(o, 0, yp[0]);
-                    pack_octet(o, 1, yp[1]);
+                    pack_octet<T, NP>(o, 0, yp[0]);
+                    pack_octet<T, NP>(o, 1, yp[1]);
                     unsigned char *p = sp_wave + (size_t)hd * (size_t)(2 * NP * 1024);
 #pragma unroll
                     for (int kk = 0; kk < 2; kk++)

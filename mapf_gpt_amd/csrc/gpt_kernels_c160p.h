@@ -163,17 +163,11 @@ __global__ __launch_bounds__(128 * NPAIR, 2) void mlp160p_kernel(float *__restri
     using I4 = std::integral_constant<int, 4>;
 
     u32x4 wb[2][2][2];                                     // weight fragments [set = chunk & 1][pair of the chunk][plane]
-    auto lds_pair = [&](unsigned slot_addr, auto ms_c, u32x4 (&dst)[2]) {
-        constexpr int ms = decltype(ms_c)::value;
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[0]) : "v"(slot_addr), "n"(ms * NP * 1024) : "memory");
-        if (NP == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[1]) : "v"(slot_addr), "n"((ms * NP + 1) * 1024) : "memory");
-        else dst[1] = dst[0];
-    };
     // the first pairs of a step, right after its barrier
     auto step_first = [&](auto mb_c) {
         constexpr int MB = decltype(mb_c)::value;
-        lds_pair(cur_addr, std::integral_constant<int, MB>{}, wb[0][0]);
-        lds_pair(cur_addr, std::integral_constant<int, MB + 1>{}, wb[0][1]);
+        lds_pair<NP>(cur_addr, std::integral_constant<int, MB>{}, wb[0][0]);
+        lds_pair<NP>(cur_addr, std::integral_constant<int, MB + 1>{}, wb[0][1]);
     };
     // chunk c (0 .. 4) of a step works on pairs MB + 2c, MB + 2c + 1 (set c & 1), requested one chunk earlier; it requests the
     // pairs of the next chunk in front of its MFMAs
@@ -181,7 +175,7 @@ __global__ __launch_bounds__(128 * NPAIR, 2) void mlp160p_kernel(float *__restri
         constexpr int MB = decltype(mb_c)::value, c = decltype(c_c)::value;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        if (c < 4) { lds_pair(cur_addr, std::integral_constant<int, MB + 2 * c + 2>{}, wb[(c + 1) & 1][0]); lds_pair(cur_addr, std::integral_constant<int, MB + 2 * c + 3>{}, wb[(c + 1) & 1][1]); }
+        if (c < 4) { lds_pair<NP>(cur_addr, std::integral_constant<int, MB + 2 * c + 2>{}, wb[(c + 1) & 1][0]); lds_pair<NP>(cur_addr, std::integral_constant<int, MB + 2 * c + 3>{}, wb[(c + 1) & 1][1]); }
         __builtin_amdgcn_sched_barrier(0);
     };
     auto pin = [&](auto n_valu_c) {

@@ -54,6 +54,18 @@ __device__ __forceinline__ void split4p(const float v[4], u32x2 &hi, u32x2 &lo)
     }
 }
 
+// register octet m (registers 8m .. 8m+7) of a tile -> one 16-byte k-slot group per plane
+template <class T, int NP>
+__device__ __forceinline__ void pack_octet(const f32x16 &v, int m, u32x4 (&dst)[2])
+{
+#pragma unroll
+    for (int wd = 0; wd < 4; wd++) {
+        unsigned a, b2;
+        split2p<T, NP>(v[8 * m + 2 * wd], v[8 * m + 2 * wd + 1], a, b2);
+        dst[0][wd] = a; dst[1][wd] = b2;
+    }
+}
+
 // (GELU table: kGeluLut* in gpt_kernels_fast.h)
 
 // one 1-KiB direct global->LDS piece at byte offset 1024 * i from (src, dst): the instruction's immediate offset applies to
@@ -66,6 +78,23 @@ __device__ __forceinline__ void dma_piece(const unsigned char *src, unsigned cha
     case 2: __builtin_amdgcn_global_load_lds((gbl_void_t *)src, (lds_void_t *)dst, 16, 2048, 0); break;
     default: __builtin_amdgcn_global_load_lds((gbl_void_t *)src, (lds_void_t *)dst, 16, 3072, 0); break;
     }
+}
+
+// one 16-byte piece per lane of a weight fragment in LDS, at an immediate offset (inline asm: a compiler-visible LDS access makes
+// hipcc drain the direct-to-LDS rings with s_waitcnt vmcnt(0) in front of it) ...
+template <class OFF>
+__device__ __forceinline__ void lds_frag(unsigned addr, OFF, u32x4 &dst)
+{
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF::value) : "memory");
+}
+// ... and fragment MS of a ring slot: its NP planes of 1 KiB (one plane: both operands are that plane)
+template <int NP, class MS>
+__device__ __forceinline__ void lds_pair(unsigned slot_addr, MS, u32x4 (&dst)[2])
+{
+    constexpr int ms = MS::value;
+    lds_frag(slot_addr, std::integral_constant<int, ms * NP * 1024>{}, dst[0]);
+    if (NP == 2) lds_frag(slot_addr, std::integral_constant<int, (ms * NP + 1) * 1024>{}, dst[1]);
+    else dst[1] = dst[0];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -121,10 +150,6 @@ __global__ __launch_bounds__(256) void pack_attn256_kernel(const float *__restri
     if (NP == 2) *reinterpret_cast<u32x4 *>(dst + 512) = lo;
 }
 
-// ABL (probes only; the library instantiates ABL = 0): 1 no weight DMA in the loop, 2 no softmax arithmetic, 4 no attention phase,
-// 8 no projection MFMAs, 16 no ring barriers -- results are wrong unless ABL == 0.  32: wave 0 of every block leaves stamps[block][8]
-// = {entry cycles, entry 100-MHz ticks, cycles after LayerNorm, exit cycles, exit ticks, cycles in the q|k|v projection steps, cycles
-// waiting at the head's k / v barrier, cycles in the attention phase}.
 // Head-parallel (round 5: small launches -- one environment's rows on the 6M shape): one workgroup per (row, head), grid = rows * 8.
 // The workgroup forms the row's LayerNorm itself and runs ONE head (its six steps of the c_attn stream); the heads' y planes meet in
 // the y matrix, and the packed-GEMM out-projection that follows adds the residual.  A row's eight heads then run on eight CUs at
@@ -132,17 +157,12 @@ __global__ __launch_bounds__(256) void pack_attn256_kernel(const float *__restri
 // workgroup, all eight heads in turn; the arithmetic per token is the same, bit-identical y planes.)
 template <int NP>
 constexpr int kA256Lds = 5 * 8 * NP * 1024 + NP * (256 * 80 + 32 * 528);    // dynamic LDS (also attn256q_kernel's): 5-slot weight ring + K and V^T planes of a head
-template <class T, int NP, int ABL = 0>
+template <class T, int NP>
 __global__ __launch_bounds__(512, 2) void attn256_kernel(const float *__restrict__ x,
                                                          const uint16_t *__restrict__ wstream, float inv_scale, float scale_log2e,
-                                                         uint16_t *__restrict__ y, unsigned long long *stamps = nullptr)
+                                                         uint16_t *__restrict__ y)
 {
     constexpr int C = 256, CT = 8, KS = 16, NH = 8, HS = 32, NW = 8;
-    unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_mark = 0;
-    auto phase = [&](int i) {                              // ABL & 32: cycles since the previous call go to ts[i]
-        if constexpr ((ABL & 32) != 0) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long t = __builtin_readcyclecounter(); ts[i] += t - t_mark; t_mark = t; }
-    };
-    if constexpr ((ABL & 32) != 0) { ts[0] = __builtin_readcyclecounter(); ts[1] = wall_clock64(); }
     constexpr int MS = 8;                                  // fragment pairs per step
     constexpr int STEP = MS * NP * 1024;
     constexpr int NSLOT = 5;
@@ -244,23 +264,14 @@ __global__ __launch_bounds__(512, 2) void attn256_kernel(const float *__restrict
             if (stores_younger) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        if (!(ABL & 16)) __builtin_amdgcn_s_barrier();
-        if (!(ABL & 1) && gstep + NSLOT - 1 < nstep) issue(gstep + NSLOT - 1, slot_prev);   // (gstep + NSLOT - 1) % NSLOT
+        __builtin_amdgcn_s_barrier();
+        if (gstep + NSLOT - 1 < nstep) issue(gstep + NSLOT - 1, slot_prev);   // (gstep + NSLOT - 1) % NSLOT
         gstep++;
     };
     // (all asm destinations are arch VGPRs here: with no "a" constraint in the kernel hipcc gives the whole 256-register
     //  budget of a two-waves-per-SIMD kernel to the arch VGPRs, MFMA accumulators included; with one it splits 128 / 128
     //  and the 128 registers of operand planes no longer fit either half)
     u32x4 wb[2][2][2];                                     // weight fragments: [set][pair 2c / 2c+1][plane]
-    auto lds_frag = [&](unsigned addr, auto off_c, u32x4 &dst) {
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(decltype(off_c)::value) : "memory");
-    };
-    auto lds_pair = [&](unsigned slot_addr, auto ms_c, u32x4 (&dst)[2]) {
-        constexpr int ms = decltype(ms_c)::value;
-        lds_frag(slot_addr, std::integral_constant<int, ms * NP * 1024>{}, dst[0]);
-        if (NP == 2) lds_frag(slot_addr, std::integral_constant<int, (ms * NP + 1) * 1024>{}, dst[1]);
-        else dst[1] = dst[0];
-    };
     unsigned cur_addr = 0, nxt_addr = 0;
     auto step_begin = [&](bool stores_younger) {
         sync(stores_younger);                              // the step that runs now is gstep - 1, in slot_cur
@@ -275,8 +286,8 @@ __global__ __launch_bounds__(512, 2) void attn256_kernel(const float *__restrict
         constexpr int c = decltype(c_c)::value;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        if (c < 3) { lds_pair(cur_addr, std::integral_constant<int, 2 * c + 2>{}, wb[(c + 1) & 1][0]); lds_pair(cur_addr, std::integral_constant<int, 2 * c + 3>{}, wb[(c + 1) & 1][1]); }
-        else if (has_next) { lds_pair(nxt_addr, std::integral_constant<int, 0>{}, wb[0][0]); lds_pair(nxt_addr, std::integral_constant<int, 1>{}, wb[0][1]); }
+        if (c < 3) { lds_pair<NP>(cur_addr, std::integral_constant<int, 2 * c + 2>{}, wb[(c + 1) & 1][0]); lds_pair<NP>(cur_addr, std::integral_constant<int, 2 * c + 3>{}, wb[(c + 1) & 1][1]); }
+        else if (has_next) { lds_pair<NP>(nxt_addr, std::integral_constant<int, 0>{}, wb[0][0]); lds_pair<NP>(nxt_addr, std::integral_constant<int, 1>{}, wb[0][1]); }
         __builtin_amdgcn_sched_barrier(0);                 // the requests stay in front of this chunk's MFMAs
     };
     auto pin6 = [&]() {
@@ -284,32 +295,13 @@ __global__ __launch_bounds__(512, 2) void attn256_kernel(const float *__restrict
         for (int n = 0; n < (NP == 2 ? 6 : 2); n++) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_barrier(0);
     };
-    // register octet m (registers 8m .. 8m+7) of a tile -> one 16-byte k-slot group per plane
-    auto pack_octet = [&](const f32x16 &v, int m, u32x4 (&dst)[2]) {
-#pragma unroll
-        for (int wd = 0; wd < 4; wd++) {
-            unsigned a, b2;
-            split2p<T, NP>(v[8 * m + 2 * wd], v[8 * m + 2 * wd + 1], a, b2);
-            dst[0][wd] = a; dst[1][wd] = b2;
-        }
-    };
     auto lds_write = [&](unsigned addr, const u32x4 &v) { asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory"); };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>;
     using I3 = std::integral_constant<int, 3>;
 
-    // a query's 32 scores of a key tile sit in lanes r and r + 32: exchange by v_permlane32_swap (VALU; a ds_bpermute
-    // would join the fragment reads in lgkmcnt)
-    // (inline asm: the builtin's second result comes back as a copy of the first with this hipcc -- measured, tools/ history;
-    //  s_nop 1 = the two wait states between a VALU write and v_permlane*_swap reading it)
-    auto half_swap = [&](float v, float &lower, float &upper) {
-        lower = v; upper = v;
-        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lower), "+v"(upper));
-        // lower = value of lane r (lanes >= 32 received it), upper = value of lane r + 32 (lanes < 32 received it)
-    };
-    auto other_half_max = [&](float v) { float a, b2; half_swap(v, a, b2); return fmaxf(a, b2); };
-    auto other_half_sum = [&](float v) { float a, b2; half_swap(v, a, b2); return a + b2; };
+    // (a query's 32 scores of a key tile sit in lanes r and r + 32: other_half_max / other_half_sum, gpt_kernels_fast.h)
     const float sc2 = scale_log2e * inv_scale * inv_scale; // softmax exponent scale for q.k in weight-scaled units
     const unsigned kw_addr = sK + (unsigned)(tok0 + r) * KROW + h * 16;                   // this lane's key row (write side)
     const unsigned vw_addr = sV + (unsigned)r * VROW + (unsigned)wave * 64 + h * 16;      // this lane's d row, this wave's keys
@@ -318,9 +310,8 @@ __global__ __launch_bounds__(512, 2) void attn256_kernel(const float *__restrict
 
     // the first pairs of the very first step
     step_begin(false);
-    lds_pair(cur_addr, I0{}, wb[0][0]);
-    lds_pair(cur_addr, I1{}, wb[0][1]);
-    if constexpr ((ABL & 32) != 0) { ts[2] = __builtin_readcyclecounter(); t_mark = ts[2]; }
+    lds_pair<NP>(cur_addr, I0{}, wb[0][0]);
+    lds_pair<NP>(cur_addr, I1{}, wb[0][1]);
 
 #pragma unroll 1
     for (int hd = hd_lo; hd < hd_hi; hd++) {
@@ -337,12 +328,11 @@ __global__ __launch_bounds__(512, 2) void attn256_kernel(const float *__restrict
                 constexpr int c = decltype(c_c)::value;
                 chunk_begin(c_c, true);
                 constexpr int ks = 4 * j + c;
-                if (ABL & 8) asm volatile("" :: "v"(wb[c & 1][0][0]), "v"(wb[c & 1][0][1]), "v"(wb[c & 1][1][0]), "v"(wb[c & 1][1][1]));
-                else if (NP == 2) {
+                if (NP == 2) {
                     qa = T::mfma(wb[c & 1][0][1], xn[ks][0], qa); ka = T::mfma(wb[c & 1][1][1], xn[ks][0], ka);
                     qa = T::mfma(wb[c & 1][0][0], xn[ks][1], qa); ka = T::mfma(wb[c & 1][1][0], xn[ks][1], ka);
                 }
-                if (!(ABL & 8)) { qa = T::mfma(wb[c & 1][0][0], xn[ks][0], qa); ka = T::mfma(wb[c & 1][1][0], xn[ks][0], ka); }
+                qa = T::mfma(wb[c & 1][0][0], xn[ks][0], qa); ka = T::mfma(wb[c & 1][1][0], xn[ks][0], ka);
                 pin6();
             };
             chunk(I0{}); chunk(I1{}); chunk(I2{}); chunk(I3{});
@@ -353,12 +343,12 @@ __global__ __launch_bounds__(512, 2) void attn256_kernel(const float *__restrict
         step_qk(I3{});
         u32x4 qf[2][2];                                    // B operand of S^T = K Q^T: [k-step][plane]
 #pragma unroll
-        for (int ks = 0; ks < 2; ks++) pack_octet(qa, ks, qf[ks]);
+        for (int ks = 0; ks < 2; ks++) pack_octet<T, NP>(qa, ks, qf[ks]);
         {   // k -> sK[pl][key = tok0 + r][octet ks][half h]   (all waves passed this head's step syncs: the previous head's
             // attention is over everywhere)
             u32x4 kp[2][2];
 #pragma unroll
-            for (int ks = 0; ks < 2; ks++) pack_octet(ka, ks, kp[ks]);
+            for (int ks = 0; ks < 2; ks++) pack_octet<T, NP>(ka, ks, kp[ks]);
 #pragma unroll
             for (int ks = 0; ks < 2; ks++)
 #pragma unroll
@@ -375,12 +365,11 @@ __global__ __launch_bounds__(512, 2) void attn256_kernel(const float *__restrict
                 constexpr int c = decltype(c_c)::value;
                 chunk_begin(c_c, has_next);
                 constexpr int ks = 8 * j + 2 * c;
-                if (ABL & 8) asm volatile("" :: "v"(wb[c & 1][0][0]), "v"(wb[c & 1][0][1]), "v"(wb[c & 1][1][0]), "v"(wb[c & 1][1][1]));
-                else if (NP == 2) {
+                if (NP == 2) {
                     va = T::mfma(xn[ks][1], wb[c & 1][0][0], va); vb = T::mfma(xn[ks + 1][1], wb[c & 1][1][0], vb);
                     va = T::mfma(xn[ks][0], wb[c & 1][0][1], va); vb = T::mfma(xn[ks + 1][0], wb[c & 1][1][1], vb);
                 }
-                if (!(ABL & 8)) { va = T::mfma(xn[ks][0], wb[c & 1][0][0], va); vb = T::mfma(xn[ks + 1][0], wb[c & 1][1][0], vb); }
+                va = T::mfma(xn[ks][0], wb[c & 1][0][0], va); vb = T::mfma(xn[ks + 1][0], wb[c & 1][1][0], vb);
                 pin6();
             };
             chunk(I0{}); chunk(I1{}); chunk(I2{}); chunk(I3{});
@@ -392,23 +381,21 @@ __global__ __launch_bounds__(512, 2) void attn256_kernel(const float *__restrict
             for (int g = 0; g < 16; g++) va[g] += vb[g];
             u32x4 vp[2][2];
 #pragma unroll
-            for (int mm = 0; mm < 2; mm++) pack_octet(va, mm, vp[mm]);
+            for (int mm = 0; mm < 2; mm++) pack_octet<T, NP>(va, mm, vp[mm]);
 #pragma unroll
             for (int mm = 0; mm < 2; mm++)
 #pragma unroll
                 for (int pl = 0; pl < NP; pl++) lds_write(vw_addr + (unsigned)(pl * HS * VROW + mm * 32), vp[mm][pl]);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        phase(5);
         __builtin_amdgcn_s_barrier();                      // k, v^T of the head complete
-        phase(6);
 
         // ---- attention of this wave's 32 queries against the 256 keys of the head ----
         f32x16 o;
 #pragma unroll
         for (int g = 0; g < 16; g++) o[g] = 0.f;
         float m_run = -INFINITY, l_run = 0.f;
-        if (!(ABL & 4)) {
+        {
             u32x4 kf[2][2], vf[2][2];
             auto load_k = [&](int kt) {                    // K fragments of key tile kt: [k-step][plane]
                 const unsigned a = kr_addr + (unsigned)kt * (32 * KROW);
@@ -443,12 +430,10 @@ __global__ __launch_bounds__(512, 2) void attn256_kernel(const float *__restrict
                 if (kt + 1 < kT / 32) load_k(kt + 1);
                 // sc[g] = S[query r][key 32 kt + tau(g, h)]  (times 1/inv_scale^2)
                 float mx = sc[0];
-                if (!(ABL & 2)) {
 #pragma unroll
                 for (int g = 1; g < 16; g++) mx = fmaxf(mx, sc[g]);
                 mx = other_half_max(mx);
-                }
-                if (!(ABL & 2) && __builtin_amdgcn_ballot_w64(mx > m_run) != 0) {        // some query's running max moved: rescale (wave-uniform branch)
+                if (__builtin_amdgcn_ballot_w64(mx > m_run) != 0) {        // some query's running max moved: rescale (wave-uniform branch)
                     const float m_new = fmaxf(m_run, mx);
                     const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * sc2);
                     l_run *= alpha;
@@ -458,17 +443,15 @@ __global__ __launch_bounds__(512, 2) void attn256_kernel(const float *__restrict
                 }
                 const float nm = -m_run * sc2;
                 float psum = 0.f;
-                if (!(ABL & 2)) {
 #pragma unroll
                 for (int g = 0; g < 16; g++) {
                     sc[g] = __builtin_amdgcn_exp2f(fmaf(sc[g], sc2, nm));
                     psum += sc[g];
                 }
                 l_run += other_half_sum(psum);
-                } else l_run = 1.f;
                 u32x4 pf[2][2];
 #pragma unroll
-                for (int mm = 0; mm < 2; mm++) pack_octet(sc, mm, pf[mm]);
+                for (int mm = 0; mm < 2; mm++) pack_octet<T, NP>(sc, mm, pf[mm]);
                 if (kt + 1 < kT / 32) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * NP) : "memory");   // v^T fragments landed, K of the next tile may fly
                 else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
@@ -491,15 +474,8 @@ __global__ __launch_bounds__(512, 2) void attn256_kernel(const float *__restrict
                 if (NP == 2) *reinterpret_cast<u32x2 *>(y + pk_off(m, n, 1, C >> 4, NP)) = lo;
             }
         }
-        phase(7);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr ((ABL & 32) != 0) {
-        ts[3] = __builtin_readcyclecounter(); ts[4] = wall_clock64();
-        if (tid == 0)
-#pragma unroll
-            for (int i = 0; i < 8; i++) stamps[(size_t)blockIdx.x * 8 + i] = ts[i];
-    }
 }
 
 }  // namespace fastk

@@ -103,9 +103,6 @@ __global__ __launch_bounds__(256) void pack_attn256q_kernel(const float *__restr
     if (NP == 2) *reinterpret_cast<u32x4 *>(dst + 512) = lo;
 }
 
-// STAMPS (probes only): wave 0 of every workgroup leaves {entry cycles, entry 100-MHz ticks, cycles in
-// the prologues, in the q|k|v projection steps, in the attention phases (k / v barrier included), in the tail steps, in the
-// tail epilogues, exit ticks} summed over its rows.  STAMPS == 2: waves 0 and 4 leave the step-phase cycles (sphase below).
 // EMB (layer 0 of a forward, round 6): the rows do not exist yet -- the prologue takes them from the (position, token) embedding table
 // etab[256 positions][67 tokens][C] = wpe[position] + wte[token] (model.py:171-175; built once per checkpoint, 17.5 MB: L2 / memory-side cache
 // resident) through the SAME 32 loads per lane with other addresses, and writes them to x from there (the tail's residual read finds them:
@@ -126,14 +123,13 @@ __global__ __launch_bounds__(256) void pack_attn256q_kernel(const float *__restr
 //     v  [plane][dim] fp16 / bf16 values
 template <int NP> constexpr int kL0TabHeadBytes = 192 * NP;
 template <int NP> constexpr int kL0TabEntryBytes = 8 * kL0TabHeadBytes<NP>;
-template <class T, int NP, int STAMPS = 0, bool EMB = false, int TAB = 0>
+template <class T, int NP, bool EMB = false, int TAB = 0>
 __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x, const uint16_t *__restrict__ wstream, float inv_scale,
                                                           float scale_log2e, float inv_proj, unsigned char *__restrict__ spill,
-                                                          int n_rows, unsigned long long *stamps = nullptr,
-                                                          const unsigned char *__restrict__ tokens = nullptr, const float *__restrict__ etab = nullptr,
-                                                          unsigned char *__restrict__ table = nullptr)
+                                                          int n_rows, const unsigned char *__restrict__ tokens = nullptr,
+                                                          const float *__restrict__ etab = nullptr, unsigned char *__restrict__ table = nullptr)
 {
-    static_assert(TAB == 0 || (TAB == 1 && EMB) || (TAB == 2 && !EMB && STAMPS == 0), "table modes");
+    static_assert(TAB == 0 || (TAB == 1 && EMB) || (TAB == 2 && !EMB), "table modes");
     constexpr int HB = kL0TabHeadBytes<NP>, ENT = kL0TabEntryBytes<NP>;
     constexpr int C = 256, KS = 16, NH = 8, HS = 32, NW = 8;
     static_assert(NP == 2 || NP == 1, "planes");
@@ -166,17 +162,6 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
     // (both lane offsets are recomputed from lane16 through an opaque copy where they are used, as the K / V^T addresses below: as kernel-scope values they are two
     //  registers held across the attention phases)
     const int n_mine = n_rows > (int)blockIdx.x ? (n_rows - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
-    unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_mark = 0;
-    auto phase = [&](int i) {                              // STAMPS == 1: cycles since the previous call go to ts[i]
-        if constexpr (STAMPS == 1 || STAMPS == 3) { const unsigned long long t = __builtin_readcyclecounter(); ts[i] += t - t_mark; t_mark = t; }
-    };
-    // STAMPS == 3: as 1, left by wave 4 (the younger wave of SIMD 0) instead of wave 0.  STAMPS == 2, waves 0 AND 4: ts[2] / ts[4] = wait + barrier + piece issue / the four chunks of the q|k-shaped steps (projection
-    // steps 0-3 of every head and the 16 tail steps: 48 per row), ts[3] / ts[5] = the same of the v steps (16 per row)
-    auto smark = [&]() { if constexpr (STAMPS == 2) t_mark = __builtin_readcyclecounter(); };
-    auto sphase = [&](int i) {
-        if constexpr (STAMPS == 2) { const unsigned long long t = __builtin_readcyclecounter(); ts[i] += t - t_mark; t_mark = t; }
-    };
-    if constexpr (STAMPS != 0) { ts[0] = __builtin_readcyclecounter(); ts[1] = wall_clock64(); t_mark = ts[0]; }
     if (n_mine == 0) return;
 
     // ---- ring: slot of stream step G = G % 5, carried in two scalars; the source is cyclic with period 64 ----
@@ -211,30 +196,12 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
         slot_cur = slot_next;
     };
     u32x4 wb[2][2][2];                                     // weight fragments: [set][pair 2c / 2c+1][plane]
-    auto lds_frag = [&](unsigned addr, auto off_c, u32x4 &dst) {
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(decltype(off_c)::value) : "memory");
-    };
-    auto lds_pair = [&](unsigned slot_addr, auto ms_c, u32x4 (&dst)[2]) {
-        constexpr int ms = decltype(ms_c)::value;
-        lds_frag(slot_addr, std::integral_constant<int, ms * NP * 1024>{}, dst[0]);
-        if (NP == 2) lds_frag(slot_addr, std::integral_constant<int, (ms * NP + 1) * 1024>{}, dst[1]);
-        else dst[1] = dst[0];
-    };
     // chunk c of a step uses pairs 2c, 2c+1 (set c & 1), requested one chunk earlier; it requests the pairs of the next chunk
     // (chunk 3: the first pairs of the NEXT step, whose slot has landed -- the stream is cyclic, there always is one; NEXT = false
     //  only in a row's last step: the first pairs of the next row's first step are requested after its prologue instead, so that
     //  their 16 registers are not live across the 128-register LayerNorm)
-    auto chunk_begin = [&](auto c_c, auto next_c) {
-        constexpr int c = decltype(c_c)::value;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        if (c < 3) { lds_pair(cur_addr, std::integral_constant<int, 2 * c + 2>{}, wb[(c + 1) & 1][0]); lds_pair(cur_addr, std::integral_constant<int, 2 * c + 3>{}, wb[(c + 1) & 1][1]); }
-        else if (decltype(next_c)::value) { lds_pair(nxt_addr, std::integral_constant<int, 0>{}, wb[0][0]); lds_pair(nxt_addr, std::integral_constant<int, 1>{}, wb[0][1]); }
-        __builtin_amdgcn_sched_barrier(0);                 // the requests stay in front of this chunk's MFMAs
-    };
-    // The same requests, one at a time: read N of chunk c's list (fragment 2c+2 plane 0 [, plane 1], fragment 2c+3 ...).  Default build: each rides behind one of the
+    // The requests go one at a time: read N of chunk c's list (fragment 2c+2 plane 0 [, plane 1], fragment 2c+3 ...).  Each rides behind one of the
     // chunk's first MFMAs (the matrix pipe is busy for 16 cycles per MFMA, the LDS request issues in its shadow; rounds 4-5 issued all in front)
-    constexpr bool PLACED = true;
     auto chunk_wait = [&]() {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
@@ -248,33 +215,6 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
             if constexpr (NP == 1 && (c < 3 || decltype(next_c)::value)) wb[(c + 1) & 1][fr][1] = wb[(c + 1) & 1][fr][0];
             __builtin_amdgcn_sched_barrier(0);
         }
-    };
-    auto pin6 = [&]() {
-#pragma unroll
-        for (int n = 0; n < (NP == 2 ? 12 : 4); n++) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto pack_octet = [&](const f32x16 &v, int m, u32x4 (&dst)[2]) {
-#pragma unroll
-        for (int wd = 0; wd < 4; wd++) {
-            unsigned a, b2;
-            split2p<T, NP>(v[8 * m + 2 * wd], v[8 * m + 2 * wd + 1], a, b2);
-            dst[0][wd] = a; dst[1][wd] = b2;
-        }
-    };
-    // one product term on slice S (registers 4 S .. 4 S + 3) of a 16-register block
-    auto mm16 = [&](const u32x4 &a, const u32x4 &b2, f32x16 &blk, auto s_c) {
-        constexpr int S = decltype(s_c)::value;
-        f32x4 c = {blk[4 * S], blk[4 * S + 1], blk[4 * S + 2], blk[4 * S + 3]};
-        c = T::mfma16(a, b2, c);
-        blk[4 * S] = c[0]; blk[4 * S + 1] = c[1]; blk[4 * S + 2] = c[2]; blk[4 * S + 3] = c[3];
-    };
-    // the first term of a slice: C = 0 as the MFMA's inline constant (zeroing a slice by assignment costs four v_mov, see gpt_kernels_c256q.h)
-    auto mm16z = [&](const u32x4 &a, const u32x4 &b2, f32x16 &blk, auto s_c) {
-        constexpr int S = decltype(s_c)::value;
-        f32x4 c = {0.f, 0.f, 0.f, 0.f};
-        c = T::mfma16(a, b2, c);
-        blk[4 * S] = c[0]; blk[4 * S + 1] = c[1]; blk[4 * S + 2] = c[2]; blk[4 * S + 3] = c[3];
     };
     // (LDS writes and global accesses below are written out with immediate offsets: no per-offset address registers.
     //  Global accesses use the saddr form: vdata, voffset (32-bit lane offset), saddr (uniform base), immediate.
@@ -290,12 +230,12 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
     auto mma4 = [&](const u32x4 (&w0)[2], const u32x4 (&w1)[2], const u32x4 (&x0)[2], const u32x4 (&x1)[2], f32x16 &blk, auto swap_c, auto first_c, auto &&behind) {
         constexpr bool SW = decltype(swap_c)::value, FIRST = decltype(first_c)::value;
         auto one = [&](const u32x4 &w, const u32x4 &xx, auto s_c) {
-            if constexpr (SW) mm16(xx, w, blk, s_c); else mm16(w, xx, blk, s_c);
+            if constexpr (SW) mm16<T>(xx, w, blk, s_c); else mm16<T>(w, xx, blk, s_c);
         };
         auto onez = [&](const u32x4 &w, const u32x4 &xx, auto s_c) {
             if constexpr (!FIRST) one(w, xx, s_c);
-            else if constexpr (SW) mm16z(xx, w, blk, s_c);
-            else mm16z(w, xx, blk, s_c);
+            else if constexpr (SW) mm16z<T>(xx, w, blk, s_c);
+            else mm16z<T>(w, xx, blk, s_c);
         };
         if (NP == 2) {
             onez(w0[1], x0[0], I0{}); behind(I0{}); onez(w1[1], x0[0], I1{}); behind(I1{}); onez(w0[1], x1[0], I2{}); behind(I2{}); onez(w1[1], x1[0], I3{}); behind(I3{});
@@ -308,49 +248,26 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
     };
     // the MFMAs of a chunk with its requests: `mm` runs mma4 with the hook it is given
     auto chunk_body = [&](auto c_c, auto next_c, auto &&mm) {
-        if constexpr (PLACED) {
-            chunk_wait();
-            // REFILL: a step's first chunk also issues the ring refill (PW direct-to-LDS pieces) two MFMAs behind the last read instead of at the
-            // step's top.  Built and measured (profiles/r05_ab.txt, visit N): SLOWER, attention 48.0 -> 48.2 ms per cfg3 step -- the refill stays at the top
-            constexpr bool REFILL = false;
-            constexpr int N_REFILL = NP == 2 ? 5 : 2, N_LAST = REFILL ? N_REFILL : 2 * NP - 1, NMF = NP == 2 ? 12 : 4;
-            mm([&](auto n_c) {
-                constexpr int n = decltype(n_c)::value;
-                if constexpr (n < 2 * NP) { __builtin_amdgcn_sched_barrier(0); chunk_read(c_c, next_c, n_c); }
-                else if constexpr (REFILL && n == N_REFILL) { __builtin_amdgcn_sched_barrier(0); issue(slot_refill); __builtin_amdgcn_sched_barrier(0); }
-            });
+        chunk_wait();
+        // REFILL: a step's first chunk also issues the ring refill (PW direct-to-LDS pieces) two MFMAs behind the last read instead of at the
+        // step's top.  Built and measured (profiles/r05_ab.txt, visit N): SLOWER, attention 48.0 -> 48.2 ms per cfg3 step -- the refill stays at the top.
+        // (The arm never compiles, yet it stays: without it and slot_refill the layer-0 table instances <.., false, 2> come out with another register
+        //  assignment and 2 / 4 instructions more, and that change did not pass its speed check -- DESIGN section 27)
+        constexpr bool REFILL = false;
+        constexpr int N_REFILL = NP == 2 ? 5 : 2, N_LAST = REFILL ? N_REFILL : 2 * NP - 1, NMF = NP == 2 ? 12 : 4;
+        mm([&](auto n_c) {
+            constexpr int n = decltype(n_c)::value;
+            if constexpr (n < 2 * NP) { __builtin_amdgcn_sched_barrier(0); chunk_read(c_c, next_c, n_c); }
+            else if constexpr (REFILL && n == N_REFILL) { __builtin_amdgcn_sched_barrier(0); issue(slot_refill); __builtin_amdgcn_sched_barrier(0); }
+        });
 #pragma unroll
-            for (int n = 0; n < NMF - 1 - N_LAST; n++) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        } else {
-            chunk_begin(c_c, next_c);
-            mm([&](auto) {});
-            pin6();
-        }
+        for (int n = 0; n < NMF - 1 - N_LAST; n++) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_barrier(0);
     };
-    // a token's 256 features sit in the four lanes t + 16 q: v_permlane16_swap folds rows 0|1 and 2|3 of 16 lanes, v_permlane32_swap the halves
-    auto fold4 = [&](float v) {
-        float a = v, b2 = v;
-        asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b2));
-        float c = a + b2, d = c;
-        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(c), "+v"(d));
-        return c + d;
-    };
-    auto row_swap = [&](unsigned &a, unsigned &b2) {      // rows 1, 3 of a <-> rows 0, 2 of b2 (rows of 16 lanes)
-        asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b2));
-    };
-    auto half_swap = [&](float v, float &lower, float &upper) {
-        lower = v; upper = v;
-        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lower), "+v"(upper));
-    };
-    auto other_half_max = [&](float v) { float a, b2; half_swap(v, a, b2); return fmaxf(a, b2); };
-    auto other_half_sum = [&](float v) { float a, b2; half_swap(v, a, b2); return a + b2; };
     // Units of q and k.  Round 4: the planes carried the raw accumulators, i.e. q and k
     // times the weight stream's power-of-two scale, and the softmax multiplied every score by sc2.  Since round 5: the accumulators are
     // brought to q * log2(e) / sqrt(hs) and to k (true units) before they are split -- 32 multiplies per head -- so that a score IS
-    // the exponent and the per-score multiply-add of the key-tile loop goes (see "one reference per query" below): sc2 = 1.
-    constexpr bool QK_UNITS = true;
-    const float sc2 = 1.0f;
+    // the exponent and the per-score multiply-add of the key-tile loop goes (gpt_kernels_attn_tiles.h: one reference per query).
     const float q_units = scale_log2e * inv_scale, k_units = inv_scale;
     // (the four K / V^T lane addresses are recomputed at the top of every head from lane16 through an opaque copy: as row-loop
     //  invariants they cost four registers that this kernel does not have -- one variant of it kept one in scratch, and the
@@ -364,11 +281,9 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
     f32x16 qa, ka;
     auto step_pair = [&](auto j_c, auto pending_c, auto &&after_barrier, auto next_c) {
         constexpr int j = decltype(j_c)::value;
-        smark();
         sync_wait(pending_c);
         after_barrier();
         sync_issue();
-        sphase(2);
         auto chunk = [&](auto c_c) {
             constexpr int c = decltype(c_c)::value;
             constexpr int cc = 4 * j + c, kb = cc >> 1;    // even chunks -> qa, odd chunks -> ka
@@ -381,7 +296,6 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
                                                            // the weight fragments it needs -- to the chain's first use, see above)
         };
         chunk(I0{}); chunk(I1{}); chunk(I2{}); chunk(I3{});
-        sphase(4);
     };
     auto nothing = [&]() {};
     // every step but a row's first finds its first pairs requested by chunk 3 of the step before; a row's first step reads them after
@@ -461,13 +375,13 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
                 float sm = 0.f;
 #pragma unroll
                 for (int i = 0; i < 16; i++) sm += (xr[16 * tg + i][0] + xr[16 * tg + i][1]) + (xr[16 * tg + i][2] + xr[16 * tg + i][3]);
-                const float mean = fold4(sm) * (1.0f / (float)C);
+                const float mean = permlane_fold4(sm) * (1.0f / (float)C);
                 float qv = 0.f;
 #pragma unroll
                 for (int i = 0; i < 16; i++)
 #pragma unroll
                     for (int e = 0; e < 4; e++) { const float d = xr[16 * tg + i][e] - mean; xr[16 * tg + i][e] = d; qv = fmaf(d, d, qv); }   // (the centred row is kept)
-                rstd[tg] = rsqrtf(fold4(qv) * (1.0f / (float)C) + 1e-5f);
+                rstd[tg] = rsqrtf(permlane_fold4(qv) * (1.0f / (float)C) + 1e-5f);
             }
             // (x - mean) * rstd; ln_1.weight is part of the weight stream (pack_attn256q_kernel)
 #pragma unroll
@@ -487,10 +401,9 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
         }
         // the first pairs of the row's first step (its slot landed for every wave before the barrier of the step before)
         if constexpr (TAB != 2) {
-            lds_pair(nxt_addr, I0{}, wb[0][0]);
-            lds_pair(nxt_addr, I1{}, wb[0][1]);
+            lds_pair<NP>(nxt_addr, I0{}, wb[0][0]);
+            lds_pair<NP>(nxt_addr, I1{}, wb[0][1]);
         }
-        phase(2);
 
         // ---- one head; LASTH (head 7): its output planes stay in registers (xn[14], xn[15]) and the planes of heads 0-6 are
         //      requested from the spill slab before its attention phase (xn is dead after the v steps) ----
@@ -513,12 +426,10 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
             step_pair(I2{}, P4S{}, nothing, std::true_type{});
             step_pair(I3{}, P4{}, nothing, std::true_type{});
             u32x4 qf[2][2];                                // B operand of S^T = K Q^T: [k-step][plane]
-            if constexpr (QK_UNITS) {
 #pragma unroll
-                for (int g = 0; g < 16; g++) { qa[g] *= q_units; ka[g] *= k_units; }
-            }
+            for (int g = 0; g < 16; g++) { qa[g] *= q_units; ka[g] *= k_units; }
 #pragma unroll
-            for (int tg = 0; tg < 2; tg++) pack_octet(qa, tg, qf[tg]);         // token group tg, dims block blk(q) ...
+            for (int tg = 0; tg < 2; tg++) pack_octet<T, NP>(qa, tg, qf[tg]);         // token group tg, dims block blk(q) ...
 #pragma unroll
             for (int pl = 0; pl < NP; pl++)                                     // ... -> lane (query t + 16 b4, half b5), k-step (header)
 #pragma unroll
@@ -537,7 +448,7 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
                 // row before -- has finished its attention everywhere)
                 u32x4 kp[2][2];
 #pragma unroll
-                for (int tg = 0; tg < 2; tg++) pack_octet(ka, tg, kp[tg]);
+                for (int tg = 0; tg < 2; tg++) pack_octet<T, NP>(ka, tg, kp[tg]);
 #pragma unroll
                 for (int tg = 0; tg < 2; tg++)
 #pragma unroll
@@ -557,10 +468,8 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
             f32x16 va;                                     // (started from zero by the first chunk)
             auto step_v = [&](auto j_c, auto next_c) {
                 constexpr int j = decltype(j_c)::value;
-                smark();
                 sync_wait(P4{});
                 sync_issue();
-                sphase(3);
                 auto chunk = [&](auto c_c) {
                     constexpr int c = decltype(c_c)::value;
                     constexpr int kb = 4 * j + c;
@@ -568,7 +477,6 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
                     asm volatile("" : "+v"(va));
                 };
                 chunk(I0{}); chunk(I1{}); chunk(I2{}); chunk(I3{});
-                sphase(5);
             };
             step_v(I0{}, std::true_type{});
             step_v(I1{}, std::false_type{});               // (the next step's first pairs are requested at the end of the attention phase)
@@ -612,7 +520,6 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
             }
             if constexpr (TAB == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the table stores retire here: a smaller count is always safe)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            phase(3);
             __builtin_amdgcn_s_barrier();                  // k, v^T of the head complete
 
             // ---- attention of this wave's 32 queries against the 256 keys of the head (gpt_kernels_attn_tiles.h) ----
@@ -621,8 +528,8 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
             attention_tiles<T, NP, KROW, VROW, HS>(kr_addr, vr_addr, qf, lane, o, l_run);
             // the first pairs of the next stream step (the step after this phase; its slot landed for every wave before the last
             // v step's barrier) -- round 4 requested them in that step's chunk 3 and held their 16 registers across the whole phase
-            lds_pair(nxt_addr, I0{}, wb[0][0]);
-            lds_pair(nxt_addr, I1{}, wb[0][1]);
+            lds_pair<NP>(nxt_addr, I0{}, wb[0][0]);
+            lds_pair<NP>(nxt_addr, I1{}, wb[0][1]);
             // ---- y planes of the head: o[g] = O[query r][d = tau(g, h)] / l, times the v projection's weight scale; rows swapped between
             //      registers g and 8 + g: register octet tg = token group tg of k-block hd of the out-projection's B operand (header) ----
             {
@@ -632,12 +539,12 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
 #pragma unroll
                 for (int g = 0; g < 8; g++) { float a = o[g], b2 = o[8 + g]; asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b2)); o[g] = a; o[8 + g] = b2; }
                 if constexpr (LASTH) {
-                    pack_octet(o, 0, xn[7]);
-                    pack_octet(o, 1, xn[15]);
+                    pack_octet<T, NP>(o, 0, xn[7]);
+                    pack_octet<T, NP>(o, 1, xn[15]);
                 } else {
                     u32x4 yp[2][2];
-                    pack_octet(o, 0, yp[0]);
-                    pack_octet(o, 1, yp[1]);
+                    pack_octet<T, NP>(o, 0, yp[0]);
+                    pack_octet<T, NP>(o, 1, yp[1]);
                     unsigned char *p = sp_wave + (size_t)hd * (size_t)(2 * NP * 1024);
 #pragma unroll
                     for (int kk = 0; kk < 2; kk++)
@@ -646,7 +553,6 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
                             asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 1" ::"v"(lane16), "v"(yp[kk][pl]), "s"(p), "n"((kk * NP + pl) * 1024) : "memory");
                 }
             }
-            phase(4);
         };
         // ---- TAB == 2: one head from the table.  The y planes go to xn[7], xn[15] after those of the heads before have moved down one place
         //      (a rolled loop has fixed registers: 16 NP moves per head; after the eighth, xn[hd], xn[8 + hd] hold head hd as in the tail's order) ----
@@ -712,15 +618,15 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
             for (int k2 = 0; k2 < 7; k2++)
 #pragma unroll
                 for (int pl = 0; pl < NP; pl++) { xn[k2][pl] = xn[k2 + 1][pl]; xn[8 + k2][pl] = xn[9 + k2][pl]; }
-            pack_octet(o, 0, xn[7]);
-            pack_octet(o, 1, xn[15]);
+            pack_octet<T, NP>(o, 0, xn[7]);
+            pack_octet<T, NP>(o, 1, xn[15]);
         };
         if constexpr (TAB == 2) {
 #pragma unroll 1
             for (int hd = 0; hd < NH; hd++) head_t(hd);
             // the first pairs of the tail's first step (its slot landed for every wave at the row before's last step)
-            lds_pair(nxt_addr, I0{}, wb[0][0]);
-            lds_pair(nxt_addr, I1{}, wb[0][1]);
+            lds_pair<NP>(nxt_addr, I0{}, wb[0][0]);
+            lds_pair<NP>(nxt_addr, I1{}, wb[0][1]);
         } else {
 #pragma unroll 1
             for (int hd = 0; hd < NH - 1; hd++) head(hd, std::false_type{});
@@ -767,7 +673,6 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
             step_pair(I1{}, std::integral_constant<int, 2 * PW + 8 + OTHERS>{}, nothing, std::true_type{});
             step_pair(I2{}, std::integral_constant<int, 2 * PW + 8 + OTHERS>{}, nothing, std::true_type{});
             step_pair(I3{}, P4{}, nothing, std::integral_constant<bool, !LASTT>{});
-            phase(5);
             // ---- epilogue of the four feature groups: x + acc / scale (the residual loads are older than this pseudo-head's ring pieces) ----
             asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(xs[0][0]), "+v"(xs[0][1]), "+v"(xs[1][0]), "+v"(xs[1][1]), "+v"(xs[2][0]), "+v"(xs[2][1]), "+v"(xs[3][0]), "+v"(xs[3][1])
                          : [n] "n"(4 * PW) : "memory");
@@ -780,7 +685,6 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
                     for (int e = 0; e < 4; e++) v[e] = fmaf((fgl < 2 ? qa : ka)[4 * (2 * tg + (fgl & 1)) + e], inv_proj, xs[fgl][tg][e]);
                     asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 1" ::"v"(xoff_t), "v"(v), "s"(xp + (fgl >> 1) * 4096), "n"((fgl & 1) * 2048 + tg * 512) : "memory");
                 }
-            phase(6);
         };
         // the planes of heads 0-6 must have landed before the first tail MFMA reads them.  Everything in flight here -- three steps
         // of ring pieces and the 28 spill loads -- was issued at least one attention phase ago, so vmcnt(0) costs nothing and makes
@@ -800,13 +704,6 @@ __global__ __launch_bounds__(512, 2) void attn256q_kernel(float *__restrict__ x,
         tail(3, std::false_type{}, std::true_type{});
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // no direct-to-LDS load may outlive the workgroup
-    if constexpr (STAMPS != 0) {
-        if (lane == 0 && ((wave == 0 && STAMPS != 3) || (STAMPS == 2 && wave == 4) || (STAMPS == 3 && wave == 4))) {
-            ts[7] = wall_clock64();
-#pragma unroll
-            for (int i = 0; i < 8; i++) stamps[((size_t)blockIdx.x * (STAMPS == 2 ? 2 : 1) + (STAMPS == 2 ? (wave >> 2) : 0)) * 8 + i] = ts[i];
-        }
-    }
 }
 
 }  // namespace fastk

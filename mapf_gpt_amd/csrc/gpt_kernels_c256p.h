@@ -100,6 +100,22 @@ __device__ __forceinline__ void vm_wait()
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// Lane exchanges of the 16 x 16 x 32 kernels (lane = t + 16 q): v_permlane16_swap exchanges rows 1, 3 of a with rows 0, 2 of b (rows of 16 lanes);
+// s_nop 1 = the two wait states between a VALU write and v_permlane*_swap reading it (see half_swap, gpt_kernels_fast.h)
+__device__ __forceinline__ void row_swap(unsigned &a, unsigned &b)
+{
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+}
+// a token's 256 features sit in the four lanes t + 16 q: v_permlane16_swap folds rows 0|1 and 2|3 of 16 lanes, v_permlane32_swap the halves
+__device__ __forceinline__ float permlane_fold4(float v)
+{
+    float a = v, b = v;
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    float c = a + b, d = c;
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(c), "+v"(d));
+    return c + d;
+}
+
 // gelu_lut: the Phi table TIMES inv1 (GELU(v) = v_stream * (Phi(v) * inv1), the same bits as (v_stream * inv1) * Phi(v)).
 // STAMPS (tools/bench_probes/check_mlp256p.hip only): 1 = wave 0 and wave 4 of every workgroup leave s_memtime / s_memrealtime at entry and
 // exit; 2 = cycles spent in wait + barrier instead of the exit wall clock; 3 = cycles per phase of a step: {wait + barrier,
@@ -208,9 +224,7 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256p_kernel(float *__restri
     constexpr int kS1 = (kMPAbl & 1) ? 0 : 1;              // (ablation 1: the second pair of a chunk IS the first)
     auto lds_pair = [&](unsigned slot_addr, auto ms_c, u32x4 (&dst)[2]) {
         constexpr int ms = decltype(ms_c)::value;
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[0]) : "v"(slot_addr), "n"(ms * NP * 1024) : "memory");
-        if (NP == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[1]) : "v"(slot_addr), "n"((ms * NP + 1) * 1024) : "memory");
-        else dst[1] = dst[0];
+        fastk::lds_pair<NP>(slot_addr, ms_c, dst);
         if (kMPAbl & 4) {                                  // every fragment read issued twice (same bytes to the same registers)
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst[0]) : "v"(slot_addr), "n"(ms * NP * 1024) : "memory");
             if (NP == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst[1]) : "v"(slot_addr), "n"((ms * NP + 1) * 1024) : "memory");

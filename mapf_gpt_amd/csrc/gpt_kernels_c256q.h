@@ -181,9 +181,7 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256q_kernel(float *__restri
     constexpr int kS1 = (kMQAbl & 1) ? 0 : 1;              // (ablation 1: the second pair of a chunk IS the first)
     auto lds_pair = [&](unsigned slot_addr, auto ms_c, u32x4 (&dst)[2]) {
         constexpr int ms = decltype(ms_c)::value;
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[0]) : "v"(slot_addr), "n"(ms * NP * 1024) : "memory");
-        if (NP == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst[1]) : "v"(slot_addr), "n"((ms * NP + 1) * 1024) : "memory");
-        else dst[1] = dst[0];
+        fastk::lds_pair<NP>(slot_addr, ms_c, dst);
         if (kMQAbl & 4) {                                  // every fragment read issued twice (same bytes to the same registers)
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst[0]) : "v"(slot_addr), "n"(ms * NP * 1024) : "memory");
             if (NP == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst[1]) : "v"(slot_addr), "n"((ms * NP + 1) * 1024) : "memory");
@@ -227,22 +225,6 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256q_kernel(float *__restri
         __builtin_amdgcn_sched_barrier(0);
     };
 
-    // one product term on slice S (registers 4 S .. 4 S + 3) of a 16-register block
-    auto mm16 = [&](const u32x4 &a, const u32x4 &b, f32x16 &blk, auto s_c) {
-        constexpr int S = decltype(s_c)::value;
-        f32x4 c = {blk[4 * S], blk[4 * S + 1], blk[4 * S + 2], blk[4 * S + 3]};
-        c = T::mfma16(a, b, c);
-        blk[4 * S] = c[0]; blk[4 * S + 1] = c[1]; blk[4 * S + 2] = c[2]; blk[4 * S + 3] = c[3];
-    };
-    // the first term of a slice: C = 0 as the MFMA's inline constant (a slice zeroed by assignment costs four v_mov per slice: 16 x 16 x 32 has no 16-register
-    // destination to start from zero at once, and hipcc does not fold the assignments into the first MFMA of the slice)
-    auto mm16z = [&](const u32x4 &a, const u32x4 &b, f32x16 &blk, auto s_c) {
-        constexpr int S = decltype(s_c)::value;
-        f32x4 c = {0.f, 0.f, 0.f, 0.f};
-        c = T::mfma16(a, b, c);
-        blk[4 * S] = c[0]; blk[4 * S + 1] = c[1]; blk[4 * S + 2] = c[2]; blk[4 * S + 3] = c[3];
-    };
-
     if (producer) {
         // =============================================== producer ===============================================
         using MB = std::integral_constant<int, 0>;         // first pair of this role in a step
@@ -258,13 +240,13 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256q_kernel(float *__restri
         auto fc_mma = [&](const u32x4 (&w0)[2], const u32x4 (&w1)[2], const u32x4 (&x0)[2], const u32x4 (&x1)[2], f32x16 &hd, auto first_c) {
             constexpr bool FIRST = decltype(first_c)::value;
             auto head4 = [&](const u32x4 &a0, const u32x4 &a1, const u32x4 &b0, const u32x4 &b1) {
-                if constexpr (FIRST) { mm16z(a0, b0, hd, I0{}); mm16z(a1, b0, hd, I1{}); mm16z(a0, b1, hd, I2{}); mm16z(a1, b1, hd, I3{}); }
-                else { mm16(a0, b0, hd, I0{}); mm16(a1, b0, hd, I1{}); mm16(a0, b1, hd, I2{}); mm16(a1, b1, hd, I3{}); }
+                if constexpr (FIRST) { mm16z<T>(a0, b0, hd, I0{}); mm16z<T>(a1, b0, hd, I1{}); mm16z<T>(a0, b1, hd, I2{}); mm16z<T>(a1, b1, hd, I3{}); }
+                else { mm16<T>(a0, b0, hd, I0{}); mm16<T>(a1, b0, hd, I1{}); mm16<T>(a0, b1, hd, I2{}); mm16<T>(a1, b1, hd, I3{}); }
             };
             if (NP == 2) {
                 head4(w0[1], w1[1], x0[0], x1[0]);
-                mm16(w0[0], x0[1], hd, I0{}); mm16(w1[0], x0[1], hd, I1{}); mm16(w0[0], x1[1], hd, I2{}); mm16(w1[0], x1[1], hd, I3{});
-                mm16(w0[0], x0[0], hd, I0{}); mm16(w1[0], x0[0], hd, I1{}); mm16(w0[0], x1[0], hd, I2{}); mm16(w1[0], x1[0], hd, I3{});
+                mm16<T>(w0[0], x0[1], hd, I0{}); mm16<T>(w1[0], x0[1], hd, I1{}); mm16<T>(w0[0], x1[1], hd, I2{}); mm16<T>(w1[0], x1[1], hd, I3{});
+                mm16<T>(w0[0], x0[0], hd, I0{}); mm16<T>(w1[0], x0[0], hd, I1{}); mm16<T>(w0[0], x1[0], hd, I2{}); mm16<T>(w1[0], x1[0], hd, I3{});
             } else head4(w0[0], w1[0], x0[0], x1[0]);
         };
         // GELU of pre-activations 4q .. 4q+3 of hsrc (hidden units tau(4q + e, h)): part 0 forms the table addresses and issues
@@ -373,27 +355,19 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256q_kernel(float *__restri
             asm volatile("" : "+v"(xr[8]), "+v"(xr[9]), "+v"(xr[10]), "+v"(xr[11]), "+v"(xr[12]), "+v"(xr[13]), "+v"(xr[14]), "+v"(xr[15]));
             asm volatile("" : "+v"(xr[16]), "+v"(xr[17]), "+v"(xr[18]), "+v"(xr[19]), "+v"(xr[20]), "+v"(xr[21]), "+v"(xr[22]), "+v"(xr[23]));
             asm volatile("" : "+v"(xr[24]), "+v"(xr[25]), "+v"(xr[26]), "+v"(xr[27]), "+v"(xr[28]), "+v"(xr[29]), "+v"(xr[30]), "+v"(xr[31]));
-            // a token's 256 features sit in the four lanes t + 16 q: v_permlane16_swap folds rows 0|1 and 2|3 of 16 lanes, v_permlane32_swap the halves
-            auto fold4 = [&](float v) {
-                float a = v, b = v;
-                asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-                float c = a + b, d = c;
-                asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(c), "+v"(d));
-                return c + d;
-            };
             float mean[2], rstd[2];
 #pragma unroll
             for (int tg = 0; tg < 2; tg++) {
                 float sm = 0.f;
 #pragma unroll
                 for (int i = 0; i < 16; i++) sm += (xr[16 * tg + i][0] + xr[16 * tg + i][1]) + (xr[16 * tg + i][2] + xr[16 * tg + i][3]);
-                mean[tg] = fold4(sm) * (1.0f / (float)C);
+                mean[tg] = permlane_fold4(sm) * (1.0f / (float)C);
                 float qv = 0.f;
 #pragma unroll
                 for (int i = 0; i < 16; i++)
 #pragma unroll
                     for (int e = 0; e < 4; e++) { const float d = xr[16 * tg + i][e] - mean[tg]; qv = fmaf(d, d, qv); }
-                rstd[tg] = rsqrtf(fold4(qv) * (1.0f / (float)C) + 1e-5f);
+                rstd[tg] = rsqrtf(permlane_fold4(qv) * (1.0f / (float)C) + 1e-5f);
             }
             // ---- steps 2, 3: normalise and split the 16 k-steps ----
             auto norm = [&](auto ks_c) {
@@ -450,11 +424,11 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256q_kernel(float *__restri
             using S0 = std::integral_constant<int, tg>;
             using S1 = std::integral_constant<int, 2 + tg>;
             if (NP == 2) {
-                mm16(w0[1], hb[0], blk, S0{}); behind(I0{}); mm16(w1[1], hb[0], blk, S1{}); behind(I1{});
-                mm16(w0[0], hb[1], blk, S0{}); behind(I2{}); mm16(w1[0], hb[1], blk, S1{}); behind(I3{});
-                mm16(w0[0], hb[0], blk, S0{}); mm16(w1[0], hb[0], blk, S1{});
+                mm16<T>(w0[1], hb[0], blk, S0{}); behind(I0{}); mm16<T>(w1[1], hb[0], blk, S1{}); behind(I1{});
+                mm16<T>(w0[0], hb[1], blk, S0{}); behind(I2{}); mm16<T>(w1[0], hb[1], blk, S1{}); behind(I3{});
+                mm16<T>(w0[0], hb[0], blk, S0{}); mm16<T>(w1[0], hb[0], blk, S1{});
             } else {
-                mm16(w0[0], hb[0], blk, S0{}); behind(I0{}); mm16(w1[0], hb[0], blk, S1{}); behind(I1{});
+                mm16<T>(w0[0], hb[0], blk, S0{}); behind(I0{}); mm16<T>(w1[0], hb[0], blk, S1{}); behind(I1{});
             }
         };
         auto pj_half = [&](const u32x4 (&w0)[2], const u32x4 (&w1)[2], const u32x4 (&hb)[2], f32x16 &blk, auto tg_c) {

@@ -121,6 +121,26 @@ __device__ __forceinline__ f32x16 mma(const u32x4 (&a)[2], const u32x4 (&b)[2], 
     return T::mfma(a[0], b[0], c);
 }
 
+// one product term of the 16 x 16 x 32 MFMA on slice S (registers 4 S .. 4 S + 3) of a 16-register block
+template <class T, class SC>
+__device__ __forceinline__ void mm16(const u32x4 &a, const u32x4 &b, f32x16 &blk, SC)
+{
+    constexpr int S = SC::value;
+    f32x4 c = {blk[4 * S], blk[4 * S + 1], blk[4 * S + 2], blk[4 * S + 3]};
+    c = T::mfma16(a, b, c);
+    blk[4 * S] = c[0]; blk[4 * S + 1] = c[1]; blk[4 * S + 2] = c[2]; blk[4 * S + 3] = c[3];
+}
+// the first term of a slice: C = 0 as the MFMA's inline constant (a slice zeroed by assignment costs four v_mov per slice: 16 x 16 x 32 has no 16-register
+// destination to start from zero at once, and hipcc does not fold the assignments into the first MFMA of the slice)
+template <class T, class SC>
+__device__ __forceinline__ void mm16z(const u32x4 &a, const u32x4 &b, f32x16 &blk, SC)
+{
+    constexpr int S = SC::value;
+    f32x4 c = {0.f, 0.f, 0.f, 0.f};
+    c = T::mfma16(a, b, c);
+    blk[4 * S] = c[0]; blk[4 * S + 1] = c[1]; blk[4 * S + 2] = c[2]; blk[4 * S + 3] = c[3];
+}
+
 // ---------------------------------------------------------------------------------------------
 // weight packing: fp32 W[N][K] -> NP planes of 16-bit [N][K] (K contiguous), multiplied by `scale`
 // ---------------------------------------------------------------------------------------------
@@ -356,14 +376,15 @@ __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + e
 // value of the other half-wave's lane (r <-> r + 32) combined with this lane's: v_permlane32_swap is a VALU instruction; the
 // __shfl_xor(v, 32) it replaces compiles to ds_bpermute_b32, which joins the K / V fragment reads in lgkmcnt and waits for
 // them.  Inline asm: the builtin's second result comes back as a copy of the first with this hipcc; s_nop 1 = the two wait
-// states between a VALU write and v_permlane*_swap reading it.
-__device__ __forceinline__ void half_swap32(float v, float &lower, float &upper)
+// states between a VALU write and v_permlane*_swap reading it.  lower = the value of lane r (lanes >= 32 received it), upper = the
+// value of lane r + 32 (lanes < 32 received it).
+__device__ __forceinline__ void half_swap(float v, float &lower, float &upper)
 {
     lower = v; upper = v;
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lower), "+v"(upper));
 }
-__device__ __forceinline__ float half_max32(float v) { float a, b; half_swap32(v, a, b); return fmaxf(a, b); }
-__device__ __forceinline__ float half_sum32(float v) { float a, b; half_swap32(v, a, b); return a + b; }
+__device__ __forceinline__ float other_half_max(float v) { float a, b; half_swap(v, a, b); return fmaxf(a, b); }
+__device__ __forceinline__ float other_half_sum(float v) { float a, b; half_swap(v, a, b); return a + b; }
 
 // GELU with the 1/sqrt(2) and the powers of two folded into the rational's coefficients:
 // gelu(v) = hv + hv * erf(v / sqrt 2), hv = v / 2, erf(u / sqrt 2) ~= u N(u^2) / D(u^2) for |u| <= 4 sqrt 2 (1 beyond).
@@ -1655,7 +1676,7 @@ __global__ __launch_bounds__(NW * 64) void attn16_kernel(const uint16_t *__restr
             float mx = s[0];
 #pragma unroll
             for (int g = 1; g < 16; g++) mx = fmaxf(mx, s[g]);
-            mx = half_max32(mx);
+            mx = other_half_max(mx);
             // The kernel runs at the SUM of its MFMA and VALU issue time, so the softmax arithmetic is kept short: the rescale of o and l
             // (16 DT + 3 instructions) only when some query's running maximum moved (wave-uniform branch; alpha = 1 exactly otherwise), and one fma per
             // score in front of the exp2 (round 1 rescaled every tile and exponentiated (s - m) * scale)
@@ -1676,7 +1697,7 @@ __global__ __launch_bounds__(NW * 64) void attn16_kernel(const uint16_t *__restr
                 s[g] = __builtin_amdgcn_exp2f(fmaf(s[g], scale_log2e, nm));
                 psum += s[g];
             }
-            psum = half_sum32(psum);
+            psum = other_half_sum(psum);
             l_run += psum;
 #pragma unroll
             for (int mm = 0; mm < 2; mm++) {                      // two PV MFMAs of 16 keys each
@@ -2328,7 +2349,7 @@ __global__ __launch_bounds__(512, 2) void attn_block_kernel(float *__restrict__ 
             float mx = sc[0];
 #pragma unroll
             for (int g = 1; g < 16; g++) mx = fmaxf(mx, sc[g]);
-            mx = half_max32(mx);
+            mx = other_half_max(mx);
             if (__builtin_amdgcn_ballot_w64(mx > m_run) != 0) {            // some query's running max moved: rescale (wave-uniform branch)
                 const float m_new = fmaxf(m_run, mx);
                 const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * sc2);
@@ -2344,7 +2365,7 @@ __global__ __launch_bounds__(512, 2) void attn_block_kernel(float *__restrict__ 
                 sc[g] = __builtin_amdgcn_exp2f(fmaf(sc[g], sc2, nm));
                 psum += sc[g];
             }
-            psum = half_sum32(psum);
+            psum = other_half_sum(psum);
             l_run += psum;
 #pragma unroll
             for (int mm = 0; mm < 2; mm++) {

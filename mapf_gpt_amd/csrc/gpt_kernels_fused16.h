@@ -169,12 +169,6 @@ __global__ __launch_bounds__(NW * 64, 2) void mlp_fused16_kernel(float *__restri
     for (int j = 0; j < CT; j++)
 #pragma unroll
         for (int g = 0; g < 16; g++) acc[j][g] = 0.f;
-    auto mm16 = [&](const u32x4 &a, const u32x4 &b, f32x16 &blk, auto s_c) {     // one product term on registers 4 S .. 4 S + 3 of a 16-register block
-        constexpr int S = decltype(s_c)::value;
-        f32x4 c = {blk[4 * S], blk[4 * S + 1], blk[4 * S + 2], blk[4 * S + 3]};
-        c = T::mfma16(a, b, c);
-        blk[4 * S] = c[0]; blk[4 * S + 1] = c[1]; blk[4 * S + 2] = c[2]; blk[4 * S + 3] = c[3];
-    };
     using S0 = std::integral_constant<int, 0>; using S1 = std::integral_constant<int, 1>;
     using S2 = std::integral_constant<int, 2>; using S3 = std::integral_constant<int, 3>;
 
@@ -200,10 +194,10 @@ __global__ __launch_bounds__(NW * 64, 2) void mlp_fused16_kernel(float *__restri
 #pragma unroll
                     for (int pl = 0; pl < NP; pl++) w[ug][pl] = *reinterpret_cast<const u32x4 *>(pk + (size_t)((2 * kb + ug) * NP + pl) * 1024);
                 if (NP == 2) {
-                    mm16(w[0][1], xn[kb][0], hd, S0{}); mm16(w[1][1], xn[kb][0], hd, S1{}); mm16(w[0][1], xn[KB + kb][0], hd, S2{}); mm16(w[1][1], xn[KB + kb][0], hd, S3{});
-                    mm16(w[0][0], xn[kb][1], hd, S0{}); mm16(w[1][0], xn[kb][1], hd, S1{}); mm16(w[0][0], xn[KB + kb][1], hd, S2{}); mm16(w[1][0], xn[KB + kb][1], hd, S3{});
+                    mm16<T>(w[0][1], xn[kb][0], hd, S0{}); mm16<T>(w[1][1], xn[kb][0], hd, S1{}); mm16<T>(w[0][1], xn[KB + kb][0], hd, S2{}); mm16<T>(w[1][1], xn[KB + kb][0], hd, S3{});
+                    mm16<T>(w[0][0], xn[kb][1], hd, S0{}); mm16<T>(w[1][0], xn[kb][1], hd, S1{}); mm16<T>(w[0][0], xn[KB + kb][1], hd, S2{}); mm16<T>(w[1][0], xn[KB + kb][1], hd, S3{});
                 }
-                mm16(w[0][0], xn[kb][0], hd, S0{}); mm16(w[1][0], xn[kb][0], hd, S1{}); mm16(w[0][0], xn[KB + kb][0], hd, S2{}); mm16(w[1][0], xn[KB + kb][0], hd, S3{});
+                mm16<T>(w[0][0], xn[kb][0], hd, S0{}); mm16<T>(w[1][0], xn[kb][0], hd, S1{}); mm16<T>(w[0][0], xn[KB + kb][0], hd, S2{}); mm16<T>(w[1][0], xn[KB + kb][0], hd, S3{});
             }
             // fragment reads run one k-block ahead of the MFMAs that consume them, one behind each of the block's first MFMAs
             __builtin_amdgcn_sched_group_barrier(0x100, 2 * NP, 0);
@@ -259,10 +253,10 @@ __global__ __launch_bounds__(NW * 64, 2) void mlp_fused16_kernel(float *__restri
 #pragma unroll
                     for (int pl = 0; pl < NP; pl++) w[fo][pl] = *reinterpret_cast<const u32x4 *>(pk + (size_t)((2 * KB + 2 * j + fo) * NP + pl) * 1024);
                 if (NP == 2) {
-                    mm16(w[0][1], hf[0][0], acc[j], S0{}); mm16(w[0][1], hf[1][0], acc[j], S1{}); mm16(w[1][1], hf[0][0], acc[j], S2{}); mm16(w[1][1], hf[1][0], acc[j], S3{});
-                    mm16(w[0][0], hf[0][1], acc[j], S0{}); mm16(w[0][0], hf[1][1], acc[j], S1{}); mm16(w[1][0], hf[0][1], acc[j], S2{}); mm16(w[1][0], hf[1][1], acc[j], S3{});
+                    mm16<T>(w[0][1], hf[0][0], acc[j], S0{}); mm16<T>(w[0][1], hf[1][0], acc[j], S1{}); mm16<T>(w[1][1], hf[0][0], acc[j], S2{}); mm16<T>(w[1][1], hf[1][0], acc[j], S3{});
+                    mm16<T>(w[0][0], hf[0][1], acc[j], S0{}); mm16<T>(w[0][0], hf[1][1], acc[j], S1{}); mm16<T>(w[1][0], hf[0][1], acc[j], S2{}); mm16<T>(w[1][0], hf[1][1], acc[j], S3{});
                 }
-                mm16(w[0][0], hf[0][0], acc[j], S0{}); mm16(w[0][0], hf[1][0], acc[j], S1{}); mm16(w[1][0], hf[0][0], acc[j], S2{}); mm16(w[1][0], hf[1][0], acc[j], S3{});
+                mm16<T>(w[0][0], hf[0][0], acc[j], S0{}); mm16<T>(w[0][0], hf[1][0], acc[j], S1{}); mm16<T>(w[1][0], hf[0][0], acc[j], S2{}); mm16<T>(w[1][0], hf[1][0], acc[j], S3{});
             }
             __builtin_amdgcn_sched_group_barrier(0x100, 2 * NP, 1);
 #pragma unroll
