@@ -7,11 +7,16 @@ can be shared with torch tensors.
 """
 import ctypes
 import os
+import sys
 
 import torch  # noqa: F401  (must precede the CDLL below, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "csrc", "libmapf_gpt_amd.so")
+INSTALLED_PATH = os.path.join(_HERE, "csrc", "libmapf_gpt_amd.so")
+# MGPT_LIB_PATH (read once, here) names another build of the library, e.g. one that `python -m mapf_gpt_amd.build --out` wrote
+# for tools/ab.py; such a build is loaded from where it lies and never copied over the installed one
+_OVERRIDE = os.environ.get("MGPT_LIB_PATH", "")
+LIB_PATH = _OVERRIDE or INSTALLED_PATH
 
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = 0, 1, 2, 3, 4
 PREC_F32, PREC_F16X3, PREC_BF16 = 0, 1, 2
@@ -138,7 +143,11 @@ def lib():
     """The loaded library (raises if it was never built: run `python -m mapf_gpt_amd.build`)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
+        if _OVERRIDE:
+            if not os.path.exists(LIB_PATH):
+                raise ImportError(f"MGPT_LIB_PATH={LIB_PATH}: no such file (the installed library is not used in its place)")
+            print(f"mapf_gpt_amd: library from MGPT_LIB_PATH={LIB_PATH}", file=sys.stderr, flush=True)
+        elif not os.path.exists(LIB_PATH):
             raise ImportError(
                 f"{LIB_PATH} is missing. Build it with `python -m mapf_gpt_amd.build` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")

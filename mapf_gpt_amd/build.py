@@ -1,15 +1,18 @@
 """Build libmapf_gpt_amd.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
     python -m mapf_gpt_amd.build [--force] [--verbose]
+    python -m mapf_gpt_amd.build --out PATH [--csrc DIR] [-D...]
 
 One object per .hip translation unit (parallel), then one shared library next to the sources.
 The built .so is git-ignored but travels to the GPU box with the snapshot.
+--out builds a variant library somewhere else (another checkout's sources, a -D switch) for an A/B: tools/ab.py and
+tools/forward_digest.py load it by path (MGPT_LIB_PATH), it never replaces the installed one.
 """
+import argparse
 import concurrent.futures
 import hashlib
 import os
 import subprocess
-import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -21,8 +24,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
          "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 
 
-def _sources():
-    return [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
+def _sources(csrc=CSRC):
+    return [s for s in SOURCES if os.path.exists(os.path.join(csrc, s))]
 
 
 def _stamp():
@@ -40,9 +43,14 @@ def _stamp():
     return h.hexdigest()
 
 
-def _compile(src, verbose):
-    obj = os.path.join(BUILD, src.replace(".hip", ".o"))
-    cmd = [HIPCC] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
+def compile_command(src, csrc=CSRC, build_dir=BUILD, extra_flags=()):
+    """(command, object file) of one translation unit; the normal build and a variant differ in nothing else."""
+    obj = os.path.join(build_dir, src.replace(".hip", ".o"))
+    return [HIPCC] + FLAGS + list(extra_flags) + ["-c", os.path.join(csrc, src), "-o", obj], obj
+
+
+def _compile(src, verbose, csrc=CSRC, build_dir=BUILD, extra_flags=()):
+    cmd, obj = compile_command(src, csrc, build_dir, extra_flags)
     if verbose:
         print(" ".join(cmd), flush=True)
     r = subprocess.run(cmd, capture_output=True, text=True)
@@ -53,25 +61,52 @@ def _compile(src, verbose):
     return obj
 
 
-def build(force=False, verbose=False):
-    os.makedirs(BUILD, exist_ok=True)
-    stamp_file = os.path.join(BUILD, "stamp")
-    stamp = _stamp()
-    if not force and os.path.exists(LIB) and os.path.exists(stamp_file) and open(stamp_file).read() == stamp:
-        return LIB
-    srcs = _sources()
+def _compile_and_link(lib, verbose, csrc=CSRC, build_dir=BUILD, extra_flags=()):
+    os.makedirs(build_dir, exist_ok=True)
+    srcs = _sources(csrc)
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
-        objs = list(ex.map(lambda s: _compile(s, verbose), srcs))
-    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
+        objs = list(ex.map(lambda s: _compile(s, verbose, csrc, build_dir, extra_flags), srcs))
+    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs
     if verbose:
         print(" ".join(cmd), flush=True)
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    return lib
+
+
+def build(force=False, verbose=False, out=None, csrc=None, extra_flags=()):
+    """The installed library, rebuilt when its sources or flags changed.  With `out`: a variant library at that path -- the same
+    translation units, flags and job count, from `csrc` (default: this checkout's; another checkout's mapf_gpt_amd/csrc for its
+    build) with `extra_flags` added; its objects go to <out>.build/, and LIB, _build/ and the stamp are not touched."""
+    if out is not None:
+        out = os.path.abspath(out)
+        return _compile_and_link(out, verbose, os.path.abspath(csrc or CSRC), out + ".build", extra_flags)
+    if csrc is not None or extra_flags:
+        raise ValueError("csrc and extra_flags build a variant library: name its file with out")
+    os.makedirs(BUILD, exist_ok=True)
+    stamp_file = os.path.join(BUILD, "stamp")
+    stamp = _stamp()
+    if not force and os.path.exists(LIB) and os.path.exists(stamp_file) and open(stamp_file).read() == stamp:
+        return LIB
+    _compile_and_link(LIB, verbose)
     with open(stamp_file, "w") as f:
         f.write(stamp)
     return LIB
 
 
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--force", action="store_true")
+    ap.add_argument("--verbose", "-v", action="store_true")
+    ap.add_argument("--out", help="write a variant library to this path and leave the installed one alone")
+    ap.add_argument("--csrc", help="with --out: the directory of translation units to build (another checkout's mapf_gpt_amd/csrc)")
+    args, extra = ap.parse_known_args(argv)
+    bad = [f for f in extra if not f.startswith("-D")]
+    if bad:
+        ap.error(f"unknown arguments {bad} (only -D... flags are passed on to hipcc)")
+    print(build(args.force, args.verbose, args.out, args.csrc, tuple(extra)))
+
+
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose="--verbose" in sys.argv or "-v" in sys.argv))
+    main()

@@ -35,11 +35,6 @@ namespace fastk {
 constexpr int kMPPause = 4;                     // steps per block in which a role has no MFMAs (see the table above)
 constexpr int kMPPeriod = 64 + kMPPause;        // stream steps per block
 constexpr int kMPSlots = 3;                     // LDS ring depth (steps)
-#ifdef MGPT_ABL_MLPP                            // timing experiments (tools/bench_probes/check_mlp256p.hip; results are wrong): 1 = each chunk reads ONE
-constexpr int kMPAbl = MGPT_ABL_MLPP;           // fragment pair and uses it twice (the LDS traffic of a 64-token wave), 2 = no Phi-table gathers, 4 = every fragment read issued twice (results stay right)
-#else
-constexpr int kMPAbl = 0;
-#endif
 
 template <int NP>
 constexpr int kMPLds = kMPSlots * 16 * NP * 1024 + kGeluLutN * 8 + 4 * 2 * 2 * NP * 1024;   // ring | Phi table | hidden hand-off
@@ -221,23 +216,14 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256p_kernel(float *__restri
     using I3 = std::integral_constant<int, 3>;
 
     u32x4 wb[2][2][2];                                     // weight fragments [set = chunk & 1][pair of the chunk][plane]
-    constexpr int kS1 = (kMPAbl & 1) ? 0 : 1;              // (ablation 1: the second pair of a chunk IS the first)
-    auto lds_pair = [&](unsigned slot_addr, auto ms_c, u32x4 (&dst)[2]) {
-        constexpr int ms = decltype(ms_c)::value;
-        fastk::lds_pair<NP>(slot_addr, ms_c, dst);
-        if (kMPAbl & 4) {                                  // every fragment read issued twice (same bytes to the same registers)
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst[0]) : "v"(slot_addr), "n"(ms * NP * 1024) : "memory");
-            if (NP == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst[1]) : "v"(slot_addr), "n"((ms * NP + 1) * 1024) : "memory");
-        }
-    };
     // chunk c (0 .. 3) of a step works on pairs MB + 2c, MB + 2c + 1 (set c & 1), requested one chunk earlier; it requests the
     // pairs of the next chunk (chunk 3: the first pairs of the next step, whose slot has landed) in front of its MFMAs
     auto chunk_begin = [&](auto mb_c, auto c_c, bool next_step_has_work) {
         constexpr int MB = decltype(mb_c)::value, c = decltype(c_c)::value;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        if (c < 3) { lds_pair(cur_addr, std::integral_constant<int, MB + 2 * c + 2>{}, wb[(c + 1) & 1][0]); if (!(kMPAbl & 1)) lds_pair(cur_addr, std::integral_constant<int, MB + 2 * c + 3>{}, wb[(c + 1) & 1][1]); }
-        else if (next_step_has_work) { lds_pair(nxt_addr, std::integral_constant<int, MB>{}, wb[0][0]); if (!(kMPAbl & 1)) lds_pair(nxt_addr, std::integral_constant<int, MB + 1>{}, wb[0][1]); }
+        if (c < 3) { lds_pair<NP>(cur_addr, std::integral_constant<int, MB + 2 * c + 2>{}, wb[(c + 1) & 1][0]); lds_pair<NP>(cur_addr, std::integral_constant<int, MB + 2 * c + 3>{}, wb[(c + 1) & 1][1]); }
+        else if (next_step_has_work) { lds_pair<NP>(nxt_addr, std::integral_constant<int, MB>{}, wb[0][0]); lds_pair<NP>(nxt_addr, std::integral_constant<int, MB + 1>{}, wb[0][1]); }
         __builtin_amdgcn_sched_barrier(0);
     };
     auto pin = [&](auto n_valu_c) {
@@ -280,8 +266,7 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256p_kernel(float *__restri
                 const float t = __builtin_amdgcn_fmed3f(fmaf(hv, lut_scale, kGeluLutBias), 0.0f, (float)kGeluLutN - 0.002f);
                 gfr[e] = __builtin_amdgcn_fractf(t);
                 const unsigned idx = (unsigned)t;
-                if (kMPAbl & 2) { gt[e][0] = __builtin_bit_cast(float, idx); gt[e][1] = hv; (void)la; }
-                else asm volatile("ds_read_b64 %0, %1" : "=v"(gt[e]) : "v"(la + idx * 8u) : "memory");
+                asm volatile("ds_read_b64 %0, %1" : "=v"(gt[e]) : "v"(la + idx * 8u) : "memory");
             }
         };
         auto gelu1 = [&](auto q_c, int par) {
@@ -314,22 +299,22 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256p_kernel(float *__restri
             mark(1);
             chunk_begin(MB{}, I0{}, true);
             if (with_gelu) gelu0(std::integral_constant<int, 2 * half>{}, hsrc);
-            fc_mma(wb[0][0], xn[8 * half], wb[0][kS1], xn[8 * half + 1], hdst);
+            fc_mma(wb[0][0], xn[8 * half], wb[0][1], xn[8 * half + 1], hdst);
             pin(VN{});
             mark(2);
             chunk_begin(MB{}, I1{}, true);
             if (with_gelu) gelu1(std::integral_constant<int, 2 * half>{}, par);
-            fc_mma(wb[1][0], xn[8 * half + 2], wb[1][kS1], xn[8 * half + 3], hdst);
+            fc_mma(wb[1][0], xn[8 * half + 2], wb[1][1], xn[8 * half + 3], hdst);
             pin(VN{});
             mark(3);
             chunk_begin(MB{}, I2{}, true);
             if (with_gelu) gelu0(std::integral_constant<int, 2 * half + 1>{}, hsrc);
-            fc_mma(wb[0][0], xn[8 * half + 4], wb[0][kS1], xn[8 * half + 5], hdst);
+            fc_mma(wb[0][0], xn[8 * half + 4], wb[0][1], xn[8 * half + 5], hdst);
             pin(VN{});
             mark(4);
             chunk_begin(MB{}, I3{}, next_step_has_fc);
             if (with_gelu) gelu1(std::integral_constant<int, 2 * half + 1>{}, par);
-            fc_mma(wb[1][0], xn[8 * half + 6], wb[1][kS1], xn[8 * half + 7], hdst);
+            fc_mma(wb[1][0], xn[8 * half + 6], wb[1][1], xn[8 * half + 7], hdst);
             pin(VN{});
         };
         auto tile_fc = [&](f32x16 &hdst, const f32x16 &hsrc, int par, bool with_gelu, bool last_of_block) {
@@ -413,8 +398,8 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256p_kernel(float *__restri
             norm(std::integral_constant<int, 8>{}); norm(std::integral_constant<int, 9>{}); norm(std::integral_constant<int, 10>{}); norm(std::integral_constant<int, 11>{});
             norm(std::integral_constant<int, 12>{}); norm(std::integral_constant<int, 13>{}); norm(std::integral_constant<int, 14>{}); norm(std::integral_constant<int, 15>{});
             // the first fragments of step 4 (its slot has landed for every wave: step 3's barrier)
-            lds_pair(nxt_addr, std::integral_constant<int, 0>{}, wb[0][0]);
-            lds_pair(nxt_addr, std::integral_constant<int, 1>{}, wb[0][1]);
+            lds_pair<NP>(nxt_addr, std::integral_constant<int, 0>{}, wb[0][0]);
+            lds_pair<NP>(nxt_addr, std::integral_constant<int, 1>{}, wb[0][1]);
             // ---- steps 4 .. 67: c_fc of tiles 0 .. 31, GELU one tile behind ----
             tile_fc(hA, hB, 1, false, false);              // tile 0 (tile 31's GELU ran in steps 0, 1)
             tile_fc(hB, hA, 0, true, false);               // tile 1, GELU(tile 0) -> parity 0
@@ -469,19 +454,19 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256p_kernel(float *__restri
             chunk_begin(MB{}, I0{}, true);
             if (kk == 0) load_hidden(I1{}, par);
             if (kk == 1 && prefetch_next_tile) load_hidden(I0{}, par ^ 1);
-            pj_mma(wb[0][0], wb[0][kS1], hf[kk], acc[0], acc[1]);
+            pj_mma(wb[0][0], wb[0][1], hf[kk], acc[0], acc[1]);
             pin(E0{});
             mark(2);
             chunk_begin(MB{}, I1{}, true);
-            pj_mma(wb[1][0], wb[1][kS1], hf[kk], acc[2], acc[3]);
+            pj_mma(wb[1][0], wb[1][1], hf[kk], acc[2], acc[3]);
             pin(E0{});
             mark(3);
             chunk_begin(MB{}, I2{}, true);
-            pj_mma(wb[0][0], wb[0][kS1], hf[kk], acc[4], acc[5]);
+            pj_mma(wb[0][0], wb[0][1], hf[kk], acc[4], acc[5]);
             pin(E0{});
             mark(4);
             chunk_begin(MB{}, I3{}, next_step_has_pj);
-            pj_mma(wb[1][0], wb[1][kS1], hf[kk], acc[6], acc[7]);
+            pj_mma(wb[1][0], wb[1][1], hf[kk], acc[6], acc[7]);
             pin(E0{});
         };
 
@@ -544,8 +529,8 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256p_kernel(float *__restri
             // (x + 0 is written back unchanged), which keeps the loop free of branches and the step / wait counts uniform
             finish_block((int64_t)blockIdx.x + (int64_t)(k > 0 ? k - 1 : 0) * gridDim.x);
             // the first fragments of step 8 and the first k-step of tile 0's hidden planes (complete since step 6)
-            lds_pair(nxt_addr, std::integral_constant<int, 8>{}, wb[0][0]);
-            lds_pair(nxt_addr, std::integral_constant<int, 9>{}, wb[0][1]);
+            lds_pair<NP>(nxt_addr, std::integral_constant<int, 8>{}, wb[0][0]);
+            lds_pair<NP>(nxt_addr, std::integral_constant<int, 9>{}, wb[0][1]);
             load_hidden(I0{}, 0);
             // ---- steps 8 .. 67: c_proj of tiles 0 .. 29 ----
             step_pj(I0{}, 0, true, false, std::integral_constant<int, 8>{});             // step 8 (pending: S6 S7)

@@ -21,12 +21,6 @@
 namespace mgpt {
 namespace fastk {
 
-#ifdef MGPT_ABL_MLPQ
-constexpr int kMQAbl = MGPT_ABL_MLPQ;
-#else
-constexpr int kMQAbl = 0;
-#endif
-
 // weight stream: [period step R][pair ms][plane][lane][8]; pairs 0-7 = c_fc (gain folded in), 8-15 = c_proj
 template <class T, int NP>
 __global__ __launch_bounds__(256) void pack_mlp256q_kernel(const float *__restrict__ fc_w, const float *__restrict__ pj_w,
@@ -178,28 +172,18 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256q_kernel(float *__restri
     using I3 = std::integral_constant<int, 3>;
 
     u32x4 wb[2][2][2];                                     // weight fragments [set = chunk & 1][pair of the chunk][plane]
-    constexpr int kS1 = (kMQAbl & 1) ? 0 : 1;              // (ablation 1: the second pair of a chunk IS the first)
-    auto lds_pair = [&](unsigned slot_addr, auto ms_c, u32x4 (&dst)[2]) {
-        constexpr int ms = decltype(ms_c)::value;
-        fastk::lds_pair<NP>(slot_addr, ms_c, dst);
-        if (kMQAbl & 4) {                                  // every fragment read issued twice (same bytes to the same registers)
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst[0]) : "v"(slot_addr), "n"(ms * NP * 1024) : "memory");
-            if (NP == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(dst[1]) : "v"(slot_addr), "n"((ms * NP + 1) * 1024) : "memory");
-        }
-    };
     // chunk c (0 .. 3) of a step works on pairs MB + 2c, MB + 2c + 1 (set c & 1), requested one chunk earlier; it requests the
     // pairs of the next chunk (chunk 3: the first pairs of the next step, whose slot has landed) in front of its MFMAs
     auto chunk_begin = [&](auto mb_c, auto c_c, bool next_step_has_work) {
         constexpr int MB = decltype(mb_c)::value, c = decltype(c_c)::value;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        if (c < 3) { lds_pair(cur_addr, std::integral_constant<int, MB + 2 * c + 2>{}, wb[(c + 1) & 1][0]); if (!(kMQAbl & 1)) lds_pair(cur_addr, std::integral_constant<int, MB + 2 * c + 3>{}, wb[(c + 1) & 1][1]); }
-        else if (next_step_has_work) { lds_pair(nxt_addr, std::integral_constant<int, MB>{}, wb[0][0]); if (!(kMQAbl & 1)) lds_pair(nxt_addr, std::integral_constant<int, MB + 1>{}, wb[0][1]); }
+        if (c < 3) { lds_pair<NP>(cur_addr, std::integral_constant<int, MB + 2 * c + 2>{}, wb[(c + 1) & 1][0]); lds_pair<NP>(cur_addr, std::integral_constant<int, MB + 2 * c + 3>{}, wb[(c + 1) & 1][1]); }
+        else if (next_step_has_work) { lds_pair<NP>(nxt_addr, std::integral_constant<int, MB>{}, wb[0][0]); lds_pair<NP>(nxt_addr, std::integral_constant<int, MB + 1>{}, wb[0][1]); }
         __builtin_amdgcn_sched_barrier(0);
     };
     // the same requests one at a time (the consumer's placed chunks: each behind one of the chunk's first MFMAs, the matrix pipe being busy for 16 cycles per MFMA --
     // measured on attn256q_kernel, gpt_kernels_c256b.h)
-    constexpr bool PLACED = (kMQAbl == 0);
     auto chunk_read = [&](auto mb_c, auto c_c, bool next_step_has_work, auto n_c) {
         constexpr int MB = decltype(mb_c)::value, c = decltype(c_c)::value, n = decltype(n_c)::value;
         if constexpr (n < 2 * NP) {
@@ -263,8 +247,7 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256q_kernel(float *__restri
                 const float t = __builtin_amdgcn_fmed3f(fmaf(hv, lut_scale, kGeluLutBias), 0.0f, (float)kGeluLutN - 0.002f);
                 gfr[e] = __builtin_amdgcn_fractf(t);
                 const unsigned idx = (unsigned)t;
-                if (kMQAbl & 2) { gt[e][0] = __builtin_bit_cast(float, idx); gt[e][1] = hv; (void)la; }
-                else asm volatile("ds_read_b64 %0, %1" : "=v"(gt[e]) : "v"(la + idx * 8u) : "memory");
+                asm volatile("ds_read_b64 %0, %1" : "=v"(gt[e]) : "v"(la + idx * 8u) : "memory");
             }
         };
         auto gelu1 = [&](auto q_c, int par) {
@@ -297,22 +280,22 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256q_kernel(float *__restri
             mark(1);
             chunk_begin(MB{}, I0{}, true);
             if (with_gelu) gelu0(std::integral_constant<int, 2 * half>{}, hsrc);
-            fc_mma(wb[0][0], wb[0][kS1], xn[4 * half], xn[8 + 4 * half], hdst, std::integral_constant<bool, half == 0>{});
+            fc_mma(wb[0][0], wb[0][1], xn[4 * half], xn[8 + 4 * half], hdst, std::integral_constant<bool, half == 0>{});
             pin(VN{});
             mark(2);
             chunk_begin(MB{}, I1{}, true);
             if (with_gelu) gelu1(std::integral_constant<int, 2 * half>{}, par);
-            fc_mma(wb[1][0], wb[1][kS1], xn[4 * half + 1], xn[8 + 4 * half + 1], hdst, std::false_type{});
+            fc_mma(wb[1][0], wb[1][1], xn[4 * half + 1], xn[8 + 4 * half + 1], hdst, std::false_type{});
             pin(VN{});
             mark(3);
             chunk_begin(MB{}, I2{}, true);
             if (with_gelu) gelu0(std::integral_constant<int, 2 * half + 1>{}, hsrc);
-            fc_mma(wb[0][0], wb[0][kS1], xn[4 * half + 2], xn[8 + 4 * half + 2], hdst, std::false_type{});
+            fc_mma(wb[0][0], wb[0][1], xn[4 * half + 2], xn[8 + 4 * half + 2], hdst, std::false_type{});
             pin(VN{});
             mark(4);
             chunk_begin(MB{}, I3{}, next_step_has_fc);
             if (with_gelu) gelu1(std::integral_constant<int, 2 * half + 1>{}, par);
-            fc_mma(wb[1][0], wb[1][kS1], xn[4 * half + 3], xn[8 + 4 * half + 3], hdst, std::false_type{});
+            fc_mma(wb[1][0], wb[1][1], xn[4 * half + 3], xn[8 + 4 * half + 3], hdst, std::false_type{});
             pin(VN{});
         };
         auto tile_fc = [&](f32x16 &hdst, const f32x16 &hsrc, int par, bool with_gelu, bool last_of_block) {
@@ -388,8 +371,8 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256q_kernel(float *__restri
             norm(std::integral_constant<int, 8>{}); norm(std::integral_constant<int, 9>{}); norm(std::integral_constant<int, 10>{}); norm(std::integral_constant<int, 11>{});
             norm(std::integral_constant<int, 12>{}); norm(std::integral_constant<int, 13>{}); norm(std::integral_constant<int, 14>{}); norm(std::integral_constant<int, 15>{});
             // the first fragments of step 4 (its slot has landed for every wave: step 3's barrier)
-            lds_pair(nxt_addr, std::integral_constant<int, 0>{}, wb[0][0]);
-            lds_pair(nxt_addr, std::integral_constant<int, 1>{}, wb[0][1]);
+            lds_pair<NP>(nxt_addr, std::integral_constant<int, 0>{}, wb[0][0]);
+            lds_pair<NP>(nxt_addr, std::integral_constant<int, 1>{}, wb[0][1]);
             // ---- steps 4 .. 67: c_fc of tiles 0 .. 31, GELU one tile behind ----
             tile_fc(hA, hB, 1, false, false);              // tile 0 (tile 31's GELU ran in steps 0, 1)
             tile_fc(hB, hA, 0, true, false);               // tile 1, GELU(tile 0) -> parity 0
@@ -437,23 +420,14 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256q_kernel(float *__restri
         // a whole chunk (both token groups) with its requests placed behind the first MFMAs
         // (pre: requests in front of the chunk's MFMAs; between: between its two halves -- 2 NP fragment reads are younger than anything `pre` requested)
         auto pj_chunk = [&](auto c_c, bool next_has_work, const u32x4 (&w0)[2], const u32x4 (&w1)[2], f32x16 &blk, auto &&pre, auto &&between) {
-            if constexpr (PLACED) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                pre();
-                __builtin_amdgcn_sched_barrier(0);
-                pj_half_b(w0, w1, hf[0], blk, I0{}, [&](auto n_c) { __builtin_amdgcn_sched_barrier(0); chunk_read(MB{}, c_c, next_has_work, n_c); });
-                between();
-                pj_half(w0, w1, hf[1], blk, I1{});
-                pin_rest(std::integral_constant<int, (NP == 2 ? 8 : 2)>{});
-            } else {
-                chunk_begin(MB{}, c_c, next_has_work);
-                pre();
-                pj_half(w0, w1, hf[0], blk, I0{});
-                between();
-                pj_half(w0, w1, hf[1], blk, I1{});
-                pin(E0{});
-            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            pre();
+            __builtin_amdgcn_sched_barrier(0);
+            pj_half_b(w0, w1, hf[0], blk, I0{}, [&](auto n_c) { __builtin_amdgcn_sched_barrier(0); chunk_read(MB{}, c_c, next_has_work, n_c); });
+            between();
+            pj_half(w0, w1, hf[1], blk, I1{});
+            pin_rest(std::integral_constant<int, (NP == 2 ? 8 : 2)>{});
         };
         // hidden planes of token group kk (slot kk of the hand-off) of the tile with parity par
         auto load_hidden = [&](auto kk_c, int par) {
@@ -473,17 +447,17 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256q_kernel(float *__restri
             mark(1);
             auto none = [&]() {};
             // (LDS requests return in issue order: the second slot's planes are older than the chunk's placed fragment reads)
-            pj_chunk(I0{}, true, wb[0][0], wb[0][kS1], acc[4 * kk], [&]() { if (kk == 0) load_hidden(I1{}, par); },
+            pj_chunk(I0{}, true, wb[0][0], wb[0][1], acc[4 * kk], [&]() { if (kk == 0) load_hidden(I1{}, par); },
                      [&]() {
                          u32x4 (&h1)[2] = hf[1];           // (names used only inside asm operands of a generic lambda are not captured)
-                         if (kk == 0) asm volatile("s_waitcnt lgkmcnt(%[n])" : "+v"(h1[0]), "+v"(h1[1]) : [n] "n"(PLACED ? 2 * NP : 0) : "memory");
+                         if (kk == 0) asm volatile("s_waitcnt lgkmcnt(%[n])" : "+v"(h1[0]), "+v"(h1[1]) : [n] "n"(2 * NP) : "memory");
                      });
             mark(2);
-            pj_chunk(I1{}, true, wb[1][0], wb[1][kS1], acc[4 * kk + 1], none, none);
+            pj_chunk(I1{}, true, wb[1][0], wb[1][1], acc[4 * kk + 1], none, none);
             mark(3);
-            pj_chunk(I2{}, true, wb[0][0], wb[0][kS1], acc[4 * kk + 2], none, none);
+            pj_chunk(I2{}, true, wb[0][0], wb[0][1], acc[4 * kk + 2], none, none);
             mark(4);
-            pj_chunk(I3{}, next_step_has_pj, wb[1][0], wb[1][kS1], acc[4 * kk + 3], none, [&]() { if (kk == 1 && prefetch_next_tile) load_hidden(I0{}, par ^ 1); });
+            pj_chunk(I3{}, next_step_has_pj, wb[1][0], wb[1][1], acc[4 * kk + 3], none, [&]() { if (kk == 1 && prefetch_next_tile) load_hidden(I0{}, par ^ 1); });
         };
 
         // steps 0 .. 7 of a period for the consumer: the block blk_prev is finished (c_proj of its tiles 30, 31, then the
@@ -547,8 +521,8 @@ __global__ __launch_bounds__(NPAIR * 128, 2) void mlp256q_kernel(float *__restri
             // (x + 0 is written back unchanged), which keeps the loop free of branches and the step / wait counts uniform
             finish_block((int64_t)blockIdx.x + (int64_t)(k > 0 ? k - 1 : 0) * gridDim.x);
             // the first fragments of step 8 and the first k-step of tile 0's hidden planes (complete since step 6)
-            lds_pair(nxt_addr, std::integral_constant<int, 8>{}, wb[0][0]);
-            lds_pair(nxt_addr, std::integral_constant<int, 9>{}, wb[0][1]);
+            lds_pair<NP>(nxt_addr, std::integral_constant<int, 8>{}, wb[0][0]);
+            lds_pair<NP>(nxt_addr, std::integral_constant<int, 9>{}, wb[0][1]);
             load_hidden(I0{}, 0);
             // ---- steps 8 .. 67: c_proj of tiles 0 .. 29 ----
             step_pj(I0{}, 0, true, false, std::integral_constant<int, 8>{});             // step 8 (pending: S6 S7)

@@ -974,11 +974,6 @@ __global__ __launch_bounds__(256) void ln_pack_kernel(const float *__restrict__ 
 // NWV = 8: one 256 x 256 block per CU.  NWV = 4: 128 x 256 blocks, two per CU, each with its own ring and barrier (small launches: more
 // tiles than the 256-row form; at full size it is no faster, profiles/r03_probe_gemm_pk.txt).
 constexpr bool kGemmPkPlace = true;
-#ifdef MGPT_ABL_GEMM_16X16
-constexpr int kGemmPkMfmaPerTile = 2;       // (timing experiment: two 16 x 16 x 32 MFMAs in the place of every 32 x 32 x 16 one, see `round`)
-#else
-constexpr int kGemmPkMfmaPerTile = 1;
-#endif
 constexpr bool kGemmPkDmaPlace = true;
 constexpr int gemm_pk_kps(int NP) { return 1; }
 // instances compiled WITH the tile loop (see gemm_pk_kernel): the one-plane GELU epilogue, where it measured faster; the split-mode and the
@@ -1082,19 +1077,8 @@ __global__ __launch_bounds__(NWV * 64, 2) void gemm_pk_kernel(GemmArgs p, unsign
 #pragma unroll
         for (int i = 0; i < TM; i++)
 #pragma unroll
-            for (int j = 0; j < TN; j++) {
-#ifdef MGPT_ABL_GEMM_16X16
-                // timing experiment (tools/bench_probes/probe_gemm_pk.hip, results are WRONG): every 32 x 32 x 16 MFMA replaced by two 16 x 16 x 32 MFMAs on the
-                // same operand registers (the same flops, the same fragment reads), accumulating into two quads of the tile's registers
-                f32x4 c0 = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]}, c1 = {acc[i][j][4], acc[i][j][5], acc[i][j][6], acc[i][j][7]};
-                c0 = T::mfma16(fb[buf][j][pb], fa[buf][i][pa], c0);
-                c1 = T::mfma16(fa[buf][i][pa], fb[buf][j][pb], c1);
-#pragma unroll
-                for (int e = 0; e < 4; e++) { acc[i][j][e] = c0[e]; acc[i][j][4 + e] = c1[e]; }
-#else
+            for (int j = 0; j < TN; j++)
                 acc[i][j] = SWAP ? T::mfma(fb[buf][j][pb], fa[buf][i][pa], acc[i][j]) : T::mfma(fa[buf][i][pa], fb[buf][j][pb], acc[i][j]);
-#endif
-            }
         if (!kGemmPkPlace) __builtin_amdgcn_sched_barrier(0);
     };
     auto mfmas = [&](int buf) {
@@ -1149,7 +1133,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void gemm_pk_kernel(GemmArgs p, unsign
         mfmas(buf);
         // (the refill is a store to LDS as far as hipcc knows: the fragment reads, earlier in program order, stay in front of it -- so the reads go
         //  behind the first MFMAs and the refill pieces behind the ones that follow)
-        constexpr int NMF = kGemmPkMfmaPerTile * TM * TN * (NP == 2 ? 3 : 1), NRD = (TM + TN) * NP, GAP = (NMF - NRD) / PER_WAVE > 0 ? (NMF - NRD) / PER_WAVE : 1;
+        constexpr int NMF = TM * TN * (NP == 2 ? 3 : 1), NRD = (TM + TN) * NP, GAP = (NMF - NRD) / PER_WAVE > 0 ? (NMF - NRD) / PER_WAVE : 1;
 #pragma unroll
         for (int n = 0; n < NMF; n++) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -1393,10 +1377,7 @@ __device__ __forceinline__ void gemm16x16_epilogue(const GemmArgs &p, f32x4 (&c)
     }
 }
 
-#ifndef MGPT_PK16_SALU
-#define MGPT_PK16_SALU 12
-#endif
-constexpr int kPk16SaluBehind = MGPT_PK16_SALU;
+constexpr int kPk16SaluBehind = 12;
 template <class T, int EPI, int NWV, bool LNF = false>
 __global__ __launch_bounds__(NWV * 64, 2) void gemm_pk16_kernel(GemmArgs p)
 {

@@ -5,7 +5,8 @@ as a yardstick only, torch fp32 eager autograd of an in-repo restatement of mode
                                 [--lib PATH]
     python tools/bench_train.py --grad-sync WORLD [--grad-sync-shapes 6M,85M] [--iters 5] [--warmup 2]
 
---lib PATH times another build of the library (a file tools/build_ab.sh writes) in place of the in-tree one.
+--lib PATH times another build of the library (a file `python -m mapf_gpt_amd.build --out` writes) in place of the in-tree one: the same
+command runs in a fresh child process with MGPT_LIB_PATH set.
 --precision f32,bf16 times both training precisions in one call (one JSON line per shape and precision).  Every line carries the counted
 flops of the call (the products the model executes, 2 per multiply-add, backward = 2 x forward; the attention backward's recomputed S
 excluded) and, for bf16, the bytes its kernels move to and from memory (count_bytes below: every tensor read or written once per kernel,
@@ -24,6 +25,7 @@ min(rows, --torch-rows) rows (its activations are several times ours; 0 skips it
 import argparse
 import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -116,6 +118,12 @@ def grad_sync(world, shapes, iters, warmup, reps=20):
 
 
 def main(argv=None):
+    pre = argparse.ArgumentParser(add_help=False)
+    pre.add_argument("--lib", default=None)
+    lib, rest = pre.parse_known_args(argv)
+    if lib.lib:                 # mapf_gpt_amd/_lib.py reads the variable when it is imported, which has happened above
+        return subprocess.run([sys.executable, os.path.abspath(__file__), *rest],
+                              env=dict(os.environ, MGPT_LIB_PATH=os.path.abspath(lib.lib))).returncode
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="6M:512,6M:2048,2M:4096,85M:512")
     ap.add_argument("--precision", default="f32,bf16", help="comma-separated training precisions: f32, bf16")
@@ -127,9 +135,6 @@ def main(argv=None):
                     help="time export_grads and reduce_grads over WORLD gathered buffers instead of the training step")
     ap.add_argument("--grad-sync-shapes", default="6M,85M")
     a = ap.parse_args(argv)
-    if a.lib:
-        from mapf_gpt_amd import _lib
-        _lib.LIB_PATH = os.path.abspath(a.lib)
     if a.grad_sync > 0:
         return grad_sync(a.grad_sync, a.grad_sync_shapes.split(","), a.iters, a.warmup)
     for item in a.shapes.split(","):
@@ -175,4 +180,4 @@ def main(argv=None):
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

@@ -1,12 +1,12 @@
 """tools/forward_digest.py <libA.so> <libB.so>  -- bit-for-bit comparison of the 16-bit forward and of training of two builds of the
-library (the files tools/build_ab.sh writes): one SHA-256 of the output bytes per case, side by side, and a verdict.
+library (files that `python -m mapf_gpt_amd.build --out` writes): one SHA-256 of the output bytes per case, side by side, and a verdict.
 
 The case list is fixed here: seeded synthetic weights and tokens.  Forward: every released shape, two shapes of the packed / generic chains
 and the one-layer variants; both precisions; small calls, large calls with and without a remainder chunk, an uneven persistent grid, the
 sequence forward and act_tokens.  Training (TRAIN_MODELS, chunks of 2 rows, targets half -1 with one row all -1): per precision the loss and
 every gradient after a one-chunk call, a call of chunks 2, 2, 1 and an accumulating call, then after an f32 call followed by a bf16 call;
 each time the total norm of clip_grad_norm_(1.0) and the state_dict() after one AdamW step.  Every (library, environment setting, model)
-runs in a fresh process under its own time limit; the first process that fails ends the run.  A refactor of the host side must leave the
+runs in a fresh process, with MGPT_LIB_PATH naming the library, under its own time limit; the first process that fails ends the run.  A refactor of the host side must leave the
 two columns identical.
 """
 import hashlib
@@ -28,12 +28,10 @@ TRAIN_MODELS = ("tiny", "2M", "6M", "85M")    # head size 32, and 64 (85M); one 
 TIME_LIMIT = 420    # seconds per process
 
 
-def child(lib_path, model, precisions):
+def child(model, precisions):
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
-    from mapf_gpt_amd import _lib
-    _lib.LIB_PATH = lib_path
     from mapf_gpt_amd.model import build_model
 
     tokens = np.random.default_rng(5).integers(0, 67, size=(600, 256), dtype=np.uint8)
@@ -67,12 +65,10 @@ def child(lib_path, model, precisions):
             del n
 
 
-def child_train(lib_path, model):
+def child_train(model):
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
-    from mapf_gpt_amd import _lib
-    _lib.LIB_PATH = lib_path
     from mapf_gpt_amd.model import build_model
 
     rng = np.random.default_rng(7)
@@ -114,7 +110,7 @@ def run(lib_path):
 
     def one(env, model, *child_args):
         cmd = ["timeout", "-k", "10", str(TIME_LIMIT), sys.executable, os.path.abspath(__file__), *child_args]
-        r = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True)
+        r = subprocess.run(cmd, env=dict(os.environ, MGPT_LIB_PATH=lib_path, **env), capture_output=True, text=True)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
             sys.exit(f"forward_digest: {name} {env} {child_args[0]} {model}: exit status {r.returncode}; nothing more is started")
@@ -124,17 +120,17 @@ def run(lib_path):
 
     for env, models, precisions in GROUPS:
         for model in models:
-            one(env, model, "--child", lib_path, model, ",".join(precisions))
+            one(env, model, "--child", model, ",".join(precisions))
     for model in TRAIN_MODELS:
-        one({}, model, "--child-train", lib_path, model)
+        one({}, model, "--child-train", model)
     return lines
 
 
 def main():
     if len(sys.argv) >= 2 and sys.argv[1] == "--child":
-        return child(sys.argv[2], sys.argv[3], sys.argv[4].split(","))
+        return child(sys.argv[2], sys.argv[3].split(","))
     if len(sys.argv) >= 2 and sys.argv[1] == "--child-train":
-        return child_train(sys.argv[2], sys.argv[3])
+        return child_train(sys.argv[2])
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     a, b = run(sys.argv[1]), run(sys.argv[2])

@@ -1,6 +1,11 @@
 #!/bin/bash
 # tools/pmc.sh "<counters>" <tag> <command...>  -- one rocprofv3 PMC pass (counters only + kernel trace) over a command,
 # per-kernel per-dispatch averages printed and saved to gpurun_out/pmc_<tag>/summary.txt  (GPU box)
+# The pass runs under a time limit (PMC_LIMIT seconds, default 600): the function below puts `timeout` in front of the profiler
+# (timeout starts the program of that name, not the function).  A pass that fails or runs out of time ends the script there.
+set -euo pipefail
+rocprofv3() { timeout -k 10 "${PMC_LIMIT:-600}" rocprofv3 "$@"; }
+trap 'echo "pmc.sh: ended with status $? -- the log of the pass is log.txt in its output directory" >&2' ERR
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 CTRS="$1"; TAG="$2"; shift 2
