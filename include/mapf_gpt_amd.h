@@ -292,8 +292,8 @@ int mgpt_gpt_act_dev(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int32_t *
 
 /* ------------------------------------------------------------------------------------------
  * Training (train.py:324-331 with model.py:180-184 and configure_optimizers :202-226), exact fp32 or bf16 mixed precision (train.py's
- * autocast regime, forward_backward_prec).  Released configs only:
- * bias = False, dropout = 0 (dropout is a host-side flag: the caller refuses it), rows of T = 256 tokens.  In the fp32 path every product is
+ * autocast regime, forward_backward_prec), with dropout (model.py:33-34, 59, 66, 71, 82, 88, 129, 175; forward_backward_drop).  Released
+ * configs only: bias = False, rows of T = 256 tokens.  In the fp32 path every product is
  * an fp32 fmaf or fp32 MFMA; the bf16 path runs its block linears and attention on bf16 MFMAs with fp32 accumulation.  In both, every reduction
  * runs in a fixed order without floating-point atomics: two identical calls give bit-identical gradients.
  *   train_alloc: workspace for max_rows rows ((12 L + 16) C + 135 + 3 n_head floats per token: 30.1 MB per 6M row, 127.5 MB per 85M
@@ -315,6 +315,19 @@ int mgpt_gpt_act_dev(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int32_t *
  *           every accumulator, the gradients and the master weights stay fp32.  The weights are rounded as they are read, so the call
  *           always uses the current parameters and needs no memory beyond the fp32 workspace.  Deterministic like the fp32 path.  Both
  *           precisions accumulate into the same gradient buffer.  Any other precision: MGPT_ERR_UNSUPPORTED.
+ *   forward_backward_drop: forward_backward_prec in training mode with dropout probability p at model.py's four places (`sites`, a bit
+ *           mask: 1 the embedding sum, 2 the attention probabilities, 4 the output of attention's c_proj, 8 the output of the MLP's c_proj;
+ *           15 is the model's behaviour, the other values exist so that a test can name a site).  Stateless, as mgpt_gpt_act is: a mask is
+ *           a pure function keep(seed, step, site, layer, element) -- the splitmix64 finaliser over a key of (seed, step) and the stream
+ *           (site, layer), counted by the element's index ((row0 + row) * n_head + head) * 65536 + query * 256 + key for the attention
+ *           probabilities and ((row0 + row) * 256 + t) * C + c elsewhere, row = the row within the CALL; element e takes bits 16 (e & 3) of
+ *           hash(e >> 2), is kept iff they are >= thr = round(p * 65536) and kept values are scaled by 1 / (1 - thr / 65536) in fp32
+ *           (restated in mapf_gpt_amd/sampling.py: dropout_keep, dropout_scale).  So a mask does not depend on the workspace size, the
+ *           chunking of a call, the precision or the kernel that asks; forward and backward regenerate it, none is stored, and the
+ *           workspace is the one above.  The softmax sum runs over all keys, dropped ones included.  In the bf16 path the mask and scale
+ *           are applied in fp32 to P and to dP, a branch output is bf16(m s bf16(c_proj)).  p == 0 or sites == 0 runs exactly the launches of
+ *           forward_backward_prec; p outside [0, 1) or sites outside [0, 15]: MGPT_ERR_ARG; n_embd not a multiple of 4: MGPT_ERR_UNSUPPORTED.
+ *           Deterministic: two identical calls give bit-identical gradients.
  *   zero_grad: grads = 0.
  *   clip_grad_norm: torch.nn.utils.clip_grad_norm_: total = || (||g_p||)_p ||, coef = min(max_norm / (total + 1e-6), 1), g *= coef; the
  *           coefficient stays on the device, *d_total_norm (device, may be NULL) = total.  max_norm <= 0: the norm only.
@@ -349,6 +362,8 @@ int mgpt_gpt_train_alloc(mgpt_gpt *gpt, int max_rows);
 int mgpt_gpt_train_free(mgpt_gpt *gpt);
 int mgpt_gpt_forward_backward(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int T, const int32_t *d_targets, float loss_scale,
                               float *d_loss, void *stream);
+int mgpt_gpt_forward_backward_drop(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int T, const int32_t *d_targets, float loss_scale,
+                                   float *d_loss, int precision, float p, uint64_t seed, uint64_t step, uint64_t row0, int sites, void *stream);
 int mgpt_gpt_forward_backward_prec(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int T, const int32_t *d_targets, float loss_scale,
                                    float *d_loss, int precision, void *stream);
 int mgpt_gpt_zero_grad(mgpt_gpt *gpt, void *stream);

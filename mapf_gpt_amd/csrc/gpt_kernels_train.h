@@ -1,6 +1,6 @@
 // gpt_kernels_train.h -- exact-fp32 backward, gradient clipping and AdamW kernels (mgpt_gpt_forward_backward & co., train.hip), gfx950.
 //
-// Training is what train.py:324-331 does with the released configs: bias = False, dropout = 0, rows of T = 256 tokens.  The forward that
+// Training is what train.py:324-331 does: bias = False, rows of T = 256 tokens, dropout by counter-hash masks (Drop below).  The forward that
 // saves activations runs the exact-fp32 forward kernels of gpt_kernels_f32.h (gemm_f32_kernel, attn_f32_kernel, layernorm_kernel); the
 // kernels here are the backward and the optimizer.  Every product is an fp32 fmaf on the VALU, every reduction runs in a fixed order and
 // no kernel uses a floating-point atomic: two identical calls give bit-identical gradients.
@@ -93,6 +93,65 @@ __global__ __launch_bounds__(256) void gemm_tr_kernel(const float *__restrict__ 
             if (OUT == OUT_GELU_BWD) dst[o] = acc[i][j] * gelu_grad(aux[o]);
             else dst[o] = acc[i][j];
         }
+    }
+}
+
+// ----- dropout (model.py:33-34, 59, 66, 71, 82, 88, 129, 175; restated in mapf_gpt_amd/sampling.py: dropout_keep) -----
+// A mask is a pure function of (seed, step, site, layer, element index): forward and backward regenerate it and nothing is stored.  Sites:
+// 0 the embedding sum, 1 the attention probabilities, 2 attention's residual branch, 3 the MLP's.  Element index of site 1:
+// ((row0 + row) * n_head + head) * 65536 + query * 256 + key; of the others ((row0 + row) * 256 + t) * C + c; row counts from the start of
+// the CALL, so a mask does not depend on the workspace's chunking.  One splitmix64 value serves four consecutive elements: element e takes
+// bits 16 (e & 3) of hash(e >> 2), is kept iff they are >= thr = round(p * 65536), and kept values are scaled by 1 / (1 - thr / 65536).
+struct Drop {
+    uint64_t key = 0;       // drop_key(seed, step, site, layer), computed on the host
+    uint64_t base = 0;      // element index of the chunk's first element
+    uint32_t thr = 0;
+    float scale = 1.f;
+};
+
+__host__ __device__ __forceinline__ uint64_t drop_fmix(uint64_t z)
+{
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// the stream's key: the sampler's (seed, step) word (gpt.hip: uniform01) with the stream id folded in, finalised
+inline uint64_t drop_key(uint64_t seed, uint64_t step, int site, int layer)
+{
+    return drop_fmix((seed + 0x9E3779B97F4A7C15ull * (step + 1ull)) ^ ((uint64_t)(site * 256 + layer + 1) * 0xD1342543DE82EF95ull));
+}
+// the 64 mask bits of the elements 4 e4 .. 4 e4 + 3
+__device__ __forceinline__ uint64_t drop_hash(uint64_t key, uint64_t e4) { return drop_fmix(key + 0x9E3779B97F4A7C15ull * (e4 + 1ull)); }
+// ... as hash(b4 + l) with a wave-uniform b4: kb = drop_base(key, b4) on the scalar unit once, then a 64 x 32-bit product per hash
+__device__ __forceinline__ uint64_t drop_base(uint64_t key, uint64_t b4) { return key + 0x9E3779B97F4A7C15ull * (b4 + 1ull); }
+__device__ __forceinline__ uint64_t drop_hash_at(uint64_t kb, uint32_t l) { return drop_fmix(kb + 0x9E3779B97F4A7C15ull * (uint64_t)l); }
+__device__ __forceinline__ bool drop_keep(uint64_t h, int slot, uint32_t thr) { return ((uint32_t)(h >> (16 * slot)) & 0xffffu) >= thr; }
+// the factor of element `slot` of the hash: scale if kept, 0 if dropped
+__device__ __forceinline__ float drop_factor(uint64_t h, int slot, const Drop &d) { return drop_keep(h, slot, d.thr) ? d.scale : 0.f; }
+
+// out[i] = m s v(in[i]) over n4 quads of elements (the quad index is the hash's counter: base and n are multiples of 4);  v rounds to bf16
+// first when ROUND (the bf16 path's gradient of a bf16 branch output).  in == out is allowed.
+template <bool ROUND>
+__global__ __launch_bounds__(256) void drop_scale_kernel(const float *in, float *out, int64_t n4, Drop d)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const uint64_t h = drop_hash(d.key, (d.base >> 2) + (uint64_t)i);
+        float4 v = reinterpret_cast<const float4 *>(in)[i];
+        if (ROUND) { v.x = (float)(__bf16)v.x; v.y = (float)(__bf16)v.y; v.z = (float)(__bf16)v.z; v.w = (float)(__bf16)v.w; }    // (nearest-even)
+        reinterpret_cast<float4 *>(out)[i] =
+            make_float4(v.x * drop_factor(h, 0, d), v.y * drop_factor(h, 1, d), v.z * drop_factor(h, 2, d), v.w * drop_factor(h, 3, d));
+    }
+}
+
+// out[i] = x[i] + m s o[i]: a residual branch's output o joins the stream (fp32 path)
+__global__ __launch_bounds__(256) void drop_resid_kernel(const float *__restrict__ x, const float *__restrict__ o, float *__restrict__ out,
+                                                         int64_t n4, Drop d)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const uint64_t h = drop_hash(d.key, (d.base >> 2) + (uint64_t)i);
+        const float4 r = reinterpret_cast<const float4 *>(x)[i], v = reinterpret_cast<const float4 *>(o)[i];
+        reinterpret_cast<float4 *>(out)[i] = make_float4(r.x + v.x * drop_factor(h, 0, d), r.y + v.y * drop_factor(h, 1, d),
+                                                         r.z + v.z * drop_factor(h, 2, d), r.w + v.w * drop_factor(h, 3, d));
     }
 }
 
@@ -278,10 +337,12 @@ constexpr size_t attn_bwd_q_lds() { return (size_t)2 * kT * HS * sizeof(float); 
 template <int HS>
 constexpr size_t attn_bwd_kv_lds() { return attn_bwd_q_lds<HS>() + (size_t)3 * kT * sizeof(float); }
 
-template <int HS>
+// DROP (dropout on P, site 1): y = sum_j m s P v, so dP = m s (dy . v) and dV takes m s P; D = rowsum(dY o Y) holds for the dropped y, and
+// the statistics (m, l) run over all keys
+template <int HS, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const float *__restrict__ qkv, int64_t plane, const float *__restrict__ Y,
                                                          const float *__restrict__ dY, float *__restrict__ dqkv, float *__restrict__ stats,
-                                                         int n_head, float scale)
+                                                         int n_head, float scale, Drop dr)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *sK = smem, *sV = smem + kT * HS;
@@ -310,10 +371,18 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const float *__restrict
         else l += expf(s - m);
     }
     const float inv_l = 1.f / l;
+    [[maybe_unused]] uint64_t kb = 0, h = 0;                    // (DROP) the base of this (row, head)'s 65536 elements, four keys' hash
+    if constexpr (DROP) kb = drop_base(dr.key, (dr.base >> 2) + (uint64_t)bh * (kT * kT / 4));
     for (int j = 0; j < kT; j++) {
         const float s = dot_lds<HS>(q, sK + j * HS) * scale;
         const float p = expf(s - m) * inv_l;
-        const float ds = p * (dot_lds<HS>(dy, sV + j * HS) - D);
+        float ds;
+        if constexpr (DROP) {
+            if ((j & 3) == 0) h = drop_hash_at(kb, (uint32_t)(i * kT + j) >> 2);
+            ds = p * (dot_lds<HS>(dy, sV + j * HS) * drop_factor(h, j & 3, dr) - D);
+        } else {
+            ds = p * (dot_lds<HS>(dy, sV + j * HS) - D);
+        }
         const float *kr = sK + j * HS;
 #pragma unroll
         for (int d = 0; d < HS; d++) acc[d] = fmaf(ds, kr[d], acc[d]);
@@ -326,9 +395,10 @@ __global__ __launch_bounds__(256) void attn_bwd_q_kernel(const float *__restrict
 }
 
 // MODE 0: dV (thread = key j: sum_i P_ij dY_i);  MODE 1: dK (sum_i dS_ij Q_i * scale)
-template <int HS, int MODE>
+template <int HS, int MODE, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float *__restrict__ qkv, int64_t plane, const float *__restrict__ dY,
-                                                          float *__restrict__ dqkv, const float *__restrict__ stats, int n_head, float scale)
+                                                          float *__restrict__ dqkv, const float *__restrict__ stats, int n_head, float scale,
+                                                          Drop dp)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *sQ = smem, *sD = smem + kT * HS, *sS = smem + 2 * kT * HS;
@@ -360,9 +430,20 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float *__restric
         }
         const float p = expf(s * scale - sS[3 * i]) * sS[3 * i + 1];
         const float *dr = sD + i * HS;
-        if constexpr (MODE == 0) {
+        float f = 1.f;                                          // (DROP) m s of (query i, key j)
+        if constexpr (DROP)
+            f = drop_factor(drop_hash_at(drop_base(dp.key, (dp.base >> 2) + (uint64_t)bh * (kT * kT / 4)), (uint32_t)(i * kT + j) >> 2), j & 3, dp);
+        if constexpr (MODE == 0 && DROP) {
+            const float pm = p * f;
+#pragma unroll
+            for (int d = 0; d < HS; d++) acc[d] = fmaf(pm, dr[d], acc[d]);
+        } else if constexpr (MODE == 0) {
 #pragma unroll
             for (int d = 0; d < HS; d++) acc[d] = fmaf(p, dr[d], acc[d]);
+        } else if constexpr (DROP) {
+            const float ds = p * (dot_lds<HS>(v, dr) * f - sS[3 * i + 2]);
+#pragma unroll
+            for (int d = 0; d < HS; d++) acc[d] = fmaf(ds, qr[d], acc[d]);
         } else {
             const float ds = p * (dot_lds<HS>(v, dr) - sS[3 * i + 2]);
 #pragma unroll
@@ -372,6 +453,91 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float *__restric
     float *o = dqkv + ((int64_t)b * kT + j) * 3 * C + (MODE == 0 ? 2 : 1) * C + head * HS;
 #pragma unroll
     for (int d = 0; d < HS; d++) o[d] = MODE == 0 ? acc[d] : acc[d] * scale;
+}
+
+// ----- attention forward with dropout on P (fp32 path): f32k::attn_f32_kernel's walk for T = 256 (S^T = K Q^T per 32-query tile on
+// v_mfma_f32_32x32x2f32, keys in tiles of 32 with a running (max, sum)), the mask applied to exp(s - max) AFTER it joined the sum: the
+// softmax sum runs over all keys, y = s / l * sum_j m_j p_j v_j -----
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+template <int HS>
+__global__ __launch_bounds__(256) void attn_fwd_drop_kernel(const float *__restrict__ qkv, int64_t plane, float *__restrict__ y, int n_head,
+                                                            float scale, Drop dp)
+{
+    constexpr int HH = HS / 2, DT = HS / 32, KT = kT / 32;
+    const int bh = blockIdx.x, b = bh / n_head, head = bh - b * n_head, C = n_head * HS;
+    const float *Q = qkv + (int64_t)bh * kT * HS, *Kp = Q + plane, *V = Q + 2 * plane;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    for (int qt = wave; qt < KT; qt += 4) {
+        float4 qf[HH / 4];
+#pragma unroll
+        for (int i = 0; i < HH / 4; i++) qf[i] = *reinterpret_cast<const float4 *>(Q + (qt * 32 + r) * HS + h * HH + 4 * i);
+        f32x16 o[DT];
+#pragma unroll
+        for (int dt = 0; dt < DT; dt++)
+#pragma unroll
+            for (int g = 0; g < 16; g++) o[dt][g] = 0.f;
+        float m_run = -INFINITY, l_run = 0.f;
+        const uint64_t kb = drop_base(dp.key, (dp.base >> 2) + (uint64_t)bh * (kT * kT / 4));
+        const uint32_t e0 = (uint32_t)(qt * 32 + r) * kT;       // the query's first element within this (row, head)
+#pragma unroll 1
+        for (int kt = 0; kt < KT; kt++) {
+            f32x16 s;
+#pragma unroll
+            for (int g = 0; g < 16; g++) s[g] = 0.f;
+            const float *krow = Kp + (kt * 32 + r) * HS + h * HH;
+#pragma unroll
+            for (int i = 0; i < HH / 4; i++) {
+                const float4 kf = *reinterpret_cast<const float4 *>(krow + 4 * i);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[i].x, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[i].y, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[i].z, s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[i].w, s, 0, 0, 0);
+            }
+            // s[g] = S[query r][key = kt * 32 + (g & 3) + 8 * (g >> 2) + 4 * h]
+            float mx = s[0];
+#pragma unroll
+            for (int g = 1; g < 16; g++) mx = fmaxf(mx, s[g]);
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            const float m_new = fmaxf(m_run, mx);
+            const float alpha = expf((m_run - m_new) * scale);
+            float psum = 0.f;
+#pragma unroll
+            for (int g = 0; g < 16; g++) {
+                s[g] = expf((s[g] - m_new) * scale);
+                psum += s[g];
+            }
+            psum += __shfl_xor(psum, 32);
+            l_run = l_run * alpha + psum;
+            m_run = m_new;
+#pragma unroll
+            for (int gg = 0; gg < 4; gg++) {                    // four consecutive keys kt * 32 + 8 gg + 4 h ..: one hash
+                const uint64_t hh = drop_hash_at(kb, (e0 + kt * 32 + 8 * gg + 4 * h) >> 2);
+#pragma unroll
+                for (int i = 0; i < 4; i++) s[4 * gg + i] = drop_keep(hh, i, dp.thr) ? s[4 * gg + i] : 0.f;
+            }
+#pragma unroll
+            for (int dt = 0; dt < DT; dt++)
+#pragma unroll
+                for (int g = 0; g < 16; g++) o[dt][g] *= alpha;
+            const float *vbase = V + (kt * 32 + 4 * h) * HS + r;
+#pragma unroll
+            for (int g = 0; g < 16; g++) {
+                const int key = (g & 3) + 8 * (g >> 2);
+#pragma unroll
+                for (int dt = 0; dt < DT; dt++) o[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vbase[key * HS + dt * 32], s[g], o[dt], 0, 0, 0);
+            }
+        }
+        const float inv = dp.scale / l_run;
+        // o[dt][g] = O[query r][d = dt * 32 + (g & 3) + 8 * (g >> 2) + 4 * h]
+        float *yrow = y + ((int64_t)b * kT + qt * 32 + r) * C + head * HS;
+#pragma unroll
+        for (int dt = 0; dt < DT; dt++)
+#pragma unroll
+            for (int gg = 0; gg < 4; gg++)
+                *reinterpret_cast<float4 *>(yrow + dt * 32 + 8 * gg + 4 * h) =
+                    make_float4(o[dt][4 * gg] * inv, o[dt][4 * gg + 1] * inv, o[dt][4 * gg + 2] * inv, o[dt][4 * gg + 3] * inv);
+    }
 }
 
 // ----- embedding backward (model.py:171-175) -----

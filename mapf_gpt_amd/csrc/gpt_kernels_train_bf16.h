@@ -16,6 +16,7 @@
 // lane's four accumulators are four consecutive n of one m and every store is 8 or 16 bytes wide.
 #pragma once
 #include "common.h"
+#include "gpt_kernels_train.h"      // trk::Drop: the dropout masks
 
 namespace mgpt {
 namespace tbk {
@@ -100,7 +101,7 @@ __device__ __forceinline__ void stage(const T *__restrict__ src, int64_t ld, int
     }
 }
 
-enum { E_F32 = 0, E_PART = 1, E_RESID = 2, E_FC = 3, E_GELU_BWD = 4, E_QKV = 5, E_B16 = 6 };
+enum { E_F32 = 0, E_PART = 1, E_RESID = 2, E_FC = 3, E_GELU_BWD = 4, E_QKV = 5, E_B16 = 6, E_RESID_DROP = 7 };
 
 struct Epi {
     float *f32 = nullptr;           // E_F32 / E_PART / E_RESID output
@@ -111,6 +112,7 @@ struct Epi {
     int64_t ldc = 0;                // row pitch of the outputs (elements)
     int C = 0, hs = 0, n_head = 0;  // E_QKV: head-major bf16 planes of plane elements each
     int64_t plane = 0;
+    trk::Drop drop;                 // E_RESID_DROP: the branch's mask stream, base = the index of the chunk's first element
 };
 
 // four consecutive outputs (m, n .. n + 3)
@@ -127,6 +129,13 @@ __device__ __forceinline__ void epilogue(const Epi &ep, int64_t m, int n, f32x4 
         const float4 r = *reinterpret_cast<const float4 *>(ep.res + o);
         *reinterpret_cast<float4 *>(ep.f32 + o) =
             make_float4(r.x + bf_round(v[0]), r.y + bf_round(v[1]), r.z + bf_round(v[2]), r.w + bf_round(v[3]));
+    } else if constexpr (EPI == E_RESID_DROP) {
+        // x + dropout(bf16(linear output)): bf16(m s bf16(o)), as nn.Dropout on a bf16 tensor; n is a multiple of 4: one hash
+        const uint64_t h = trk::drop_hash(ep.drop.key, (ep.drop.base + (uint64_t)o) >> 2);
+        const float4 r = *reinterpret_cast<const float4 *>(ep.res + o);
+        *reinterpret_cast<float4 *>(ep.f32 + o) = make_float4(
+            r.x + bf_round(bf_round(v[0]) * trk::drop_factor(h, 0, ep.drop)), r.y + bf_round(bf_round(v[1]) * trk::drop_factor(h, 1, ep.drop)),
+            r.z + bf_round(bf_round(v[2]) * trk::drop_factor(h, 2, ep.drop)), r.w + bf_round(bf_round(v[3]) * trk::drop_factor(h, 3, ep.drop)));
     } else if constexpr (EPI == E_FC) {
         const u32x2 a = {pack2(v[0], v[1]), pack2(v[2], v[3])};
         const u32x2 h = {pack2(gelu_f(bf_lo(a[0])), gelu_f(bf_hi(a[0]))), pack2(gelu_f(bf_lo(a[1])), gelu_f(bf_hi(a[1])))};
@@ -233,9 +242,11 @@ constexpr size_t attn_bwd_lds() { return (size_t)3 * HS * kTP * 2 + (size_t)3 * 
 
 // forward: wave w takes the queries [64 w, 64 w + 64) in blocks of 16: S^T (16 key blocks in registers), fp32 max and sum of exp, then
 // O^T = V^T P^T over 8 chunks of 32 keys with bf16(P); y = bf16(O / sum)
-template <int HS>
+// DROP (dropout on P, site 1): the mask is applied to the fp32 exp(s - max) after it joined the sum (the softmax sum runs over all keys), the
+// masked value is rounded to bf16 as the PV operand, and the factor s joins 1 / sum in fp32
+template <int HS, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_fwd_bf16_kernel(const uint16_t *__restrict__ qkv, int64_t plane, uint16_t *__restrict__ y,
-                                                            float *__restrict__ stats, int n_head, float scale)
+                                                            float *__restrict__ stats, int n_head, float scale, trk::Drop dr)
 {
     constexpr int KP = HS + 8, NJ = HS / 32, ND = HS / 16;
     extern __shared__ __attribute__((aligned(16))) uint16_t lds16[];
@@ -277,6 +288,16 @@ __global__ __launch_bounds__(256) void attn_fwd_bf16_kernel(const uint16_t *__re
             for (int r = 0; r < 4; r++) { s[kb][r] = expf((s[kb][r] - mx) * scale); sum += s[kb][r]; }
         sum += __shfl_xor(sum, 16);
         sum += __shfl_xor(sum, 32);
+        if constexpr (DROP) {
+            const uint64_t hb = trk::drop_base(dr.key, (dr.base >> 2) + (uint64_t)bh * (kT * kT / 4));
+            const uint32_t e0 = (uint32_t)q * kT + 4 * g;   // the lane's keys 16 kb + 4 g + r: one hash per key block
+#pragma unroll
+            for (int kb = 0; kb < 16; kb++) {
+                const uint64_t h = trk::drop_hash_at(hb, (e0 + 16 * kb) >> 2);
+#pragma unroll
+                for (int r = 0; r < 4; r++) s[kb][r] = trk::drop_keep(h, r, dr.thr) ? s[kb][r] : 0.f;
+            }
+        }
         f32x4 o[ND];
 #pragma unroll
         for (int db = 0; db < ND; db++) o[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -289,10 +310,11 @@ __global__ __launch_bounds__(256) void attn_fwd_bf16_kernel(const uint16_t *__re
             for (int db = 0; db < ND; db++) o[db] = mfma16(tr_frag(sVt, db * 16 + fr, c, g), pf, o[db]);
         }
         const float inv = 1.f / sum;                         // o[db][r] = O[query q][d = 16 db + 4 g + r] * sum
+        const float oy = DROP ? inv * dr.scale : inv;
         uint16_t *yr = y + ((int64_t)b * kT + q) * C + head * HS;
 #pragma unroll
         for (int db = 0; db < ND; db++)
-            *reinterpret_cast<u32x2 *>(yr + db * 16 + 4 * g) = (u32x2){pack2(o[db][0] * inv, o[db][1] * inv), pack2(o[db][2] * inv, o[db][3] * inv)};
+            *reinterpret_cast<u32x2 *>(yr + db * 16 + 4 * g) = (u32x2){pack2(o[db][0] * oy, o[db][1] * oy), pack2(o[db][2] * oy, o[db][3] * oy)};
         if (g == 0) {
             stats[((int64_t)bh * kT + q) * 2] = mx;
             stats[((int64_t)bh * kT + q) * 2 + 1] = inv;
@@ -304,10 +326,12 @@ __global__ __launch_bounds__(256) void attn_fwd_bf16_kernel(const uint16_t *__re
 // Phase 1, wave w owns the keys [32 w, 32 w + 32): S and dP = dy V^T per 16 x 16 block, dV^T += dy^T P and dK^T += Q^T dS over the
 // queries in order.  Phase 2, wave w owns the queries [32 w, 32 w + 32): S^T and dP^T recomputed, dQ^T += K^T dS^T over the keys in order.
 // dq | dk | dv (fp32) into dqkv [tokens][3 C]
-template <int HS>
+// DROP: dV takes bf16(m s P), dP is masked and scaled in fp32 before dS = P (m s dP - D); D holds for the dropped y.  The mask of a 16 x 16
+// block is generated where the block is used (per tile, nothing is kept per row)
+template <int HS, bool DROP = false>
 __global__ __launch_bounds__(512) void attn_bwd_bf16_kernel(const uint16_t *__restrict__ qkv, int64_t plane, const uint16_t *__restrict__ y,
                                                             const uint16_t *__restrict__ dy, const float *__restrict__ stats,
-                                                            float *__restrict__ dqkv, int n_head, float scale)
+                                                            float *__restrict__ dqkv, int n_head, float scale, trk::Drop dr)
 {
     constexpr int NJ = HS / 32, ND = HS / 16;
     extern __shared__ __attribute__((aligned(16))) uint16_t lds16[];
@@ -339,6 +363,8 @@ __global__ __launch_bounds__(512) void attn_bwd_bf16_kernel(const uint16_t *__re
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, g = lane >> 4;
     float *out = dqkv + tok0 * 3 * C + head * HS;
+    [[maybe_unused]] uint64_t hb = 0;                         // (DROP) the base of this (row, head)'s 65536 elements
+    if constexpr (DROP) hb = trk::drop_base(dr.key, (dr.base >> 2) + (uint64_t)bh * (kT * kT / 4));
     {   // phase 1: dV, dK of the keys [32 wave, 32 wave + 32)
         u32x4 kf[2][NJ], vf[2][NJ];
 #pragma unroll
@@ -370,12 +396,26 @@ __global__ __launch_bounds__(512) void attn_bwd_bf16_kernel(const uint16_t *__re
                     f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = sv;     // [query (2 c + ql) * 16 + 4 g + r][key (2 wave + kl) * 16 + fr]
 #pragma unroll
                     for (int j = 0; j < NJ; j++) { sv = mfma16(qa[j], kf[kl][j], sv); dp = mfma16(da[j], vf[kl][j], dp); }
+                    // (DROP) the block's 16 x 16 mask takes 64 hashes, one per lane: lane L hashes query (2 c + ql) * 16 + (L >> 2), keys
+                    // (2 wave + kl) * 16 + 4 (L & 3) .. + 3 and keeps their four keep bits; a lane fetches the bits of its four queries
+                    [[maybe_unused]] unsigned kbits = 0;
+                    if constexpr (DROP) {
+                        const uint64_t h = trk::drop_hash_at(hb, (uint32_t)(((2 * c + ql) * 16 + (lane >> 2)) * kT + (2 * wave + kl) * 16 + 4 * (lane & 3)) >> 2);
+#pragma unroll
+                        for (int i = 0; i < 4; i++) kbits |= (unsigned)trk::drop_keep(h, i, dr.thr) << i;
+                    }
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
                         const int qi = (2 * c + ql) * 16 + 4 * g + r;
                         const float pr = expf((sv[r] - sM[qi]) * scale) * sIL[qi];
-                        p[ql][kl][r] = pr;
-                        ds[ql][kl][r] = pr * (dp[r] - sD[qi]);
+                        if constexpr (DROP) {
+                            const float f = ((unsigned)__shfl((int)kbits, ((4 * g + r) << 2) | (fr >> 2)) >> (fr & 3)) & 1u ? dr.scale : 0.f;
+                            p[ql][kl][r] = pr * f;
+                            ds[ql][kl][r] = pr * (dp[r] * f - sD[qi]);
+                        } else {
+                            p[ql][kl][r] = pr;
+                            ds[ql][kl][r] = pr * (dp[r] - sD[qi]);
+                        }
                     }
                 }
             }
@@ -432,10 +472,18 @@ __global__ __launch_bounds__(512) void attn_bwd_bf16_kernel(const uint16_t *__re
 #pragma unroll
                 for (int ql = 0; ql < 2; ql++) {
                     f32x4 st = {0.f, 0.f, 0.f, 0.f}, dpt = st;    // [key (2 c + kl) * 16 + 4 g + r][query (2 wave + ql) * 16 + fr]
+                    uint64_t hq = 0;                              // (DROP) the four keys' hash
 #pragma unroll
                     for (int j = 0; j < NJ; j++) { st = mfma16(ka[j], qf[ql][j], st); dpt = mfma16(va[j], df[ql][j], dpt); }
 #pragma unroll
-                    for (int r = 0; r < 4; r++) ds[ql][kl][r] = expf((st[r] - mq[ql]) * scale) * ilq[ql] * (dpt[r] - dq_[ql]);
+                    for (int r = 0; r < 4; r++) {
+                        if constexpr (DROP) {
+                            if (r == 0) hq = trk::drop_hash_at(hb, (uint32_t)(((2 * wave + ql) * 16 + fr) * kT + (2 * c + kl) * 16 + 4 * g) >> 2);
+                            ds[ql][kl][r] = expf((st[r] - mq[ql]) * scale) * ilq[ql] * (dpt[r] * trk::drop_factor(hq, r, dr) - dq_[ql]);
+                        } else {
+                            ds[ql][kl][r] = expf((st[r] - mq[ql]) * scale) * ilq[ql] * (dpt[r] - dq_[ql]);
+                        }
+                    }
                 }
             }
 #pragma unroll

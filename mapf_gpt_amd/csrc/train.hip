@@ -3,7 +3,8 @@
 //
 // A call runs in chunks of the workspace's max_rows rows.  chunk_fwd_bwd is the one sequence of both precisions, its steps members of Chunk:
 // embed, layer_forward per layer, head forward and loss, head backward, layer_backward per layer in reverse, embedding backward.  The bf16
-// path reaches the shared, fp32-sized workspace through typed views (bf16_layer, bf16_grads).
+// path reaches the shared, fp32-sized workspace through typed views (bf16_layer, bf16_grads).  Dropout (mgpt_gpt_forward_backward_drop) is a
+// DropCfg of the chunk: every site asks drops(site) and regenerates its mask from drop(site, layer); no mask is stored.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -142,10 +143,25 @@ int raise_attn_lds()
         {reinterpret_cast<const void *>(&trk::attn_bwd_kv_kernel<HS, 0>), trk::attn_bwd_kv_lds<HS>()},
         {reinterpret_cast<const void *>(&trk::attn_bwd_kv_kernel<HS, 1>), trk::attn_bwd_kv_lds<HS>()},
         {reinterpret_cast<const void *>(&tbk::attn_fwd_bf16_kernel<HS>), tbk::attn_fwd_lds<HS>()},
-        {reinterpret_cast<const void *>(&tbk::attn_bwd_bf16_kernel<HS>), tbk::attn_bwd_lds<HS>()}};
+        {reinterpret_cast<const void *>(&tbk::attn_bwd_bf16_kernel<HS>), tbk::attn_bwd_lds<HS>()},
+        {reinterpret_cast<const void *>(&trk::attn_bwd_q_kernel<HS, true>), trk::attn_bwd_q_lds<HS>()},
+        {reinterpret_cast<const void *>(&trk::attn_bwd_kv_kernel<HS, 0, true>), trk::attn_bwd_kv_lds<HS>()},
+        {reinterpret_cast<const void *>(&trk::attn_bwd_kv_kernel<HS, 1, true>), trk::attn_bwd_kv_lds<HS>()},
+        {reinterpret_cast<const void *>(&tbk::attn_fwd_bf16_kernel<HS, true>), tbk::attn_fwd_lds<HS>()},
+        {reinterpret_cast<const void *>(&tbk::attn_bwd_bf16_kernel<HS, true>), tbk::attn_bwd_lds<HS>()}};
     for (const auto &k : kernels) MGPT_HIP(set_max_lds(k.first, (int)k.second));
     return MGPT_OK;
 }
+
+// Dropout of one chunk (mgpt_gpt_forward_backward_drop): thr = 0 or sites = 0 is no dropout, and then every launch is the one of
+// mgpt_gpt_forward_backward_prec.  first_row = row0 + the chunk's first row within the call: the masks are keyed by the row of the call.
+enum { SITE_EMBED = 0, SITE_ATTN = 1, SITE_ATTN_PROJ = 2, SITE_MLP_PROJ = 3 };
+struct DropCfg {
+    uint32_t thr = 0;
+    float scale = 1.f;
+    uint64_t seed = 0, step = 0, first_row = 0;
+    int sites = 0;
+};
 
 // One chunk of rows of a call: what its launches share, and the launches (chunk_fwd_bwd is the sequence).  Only layer_forward,
 // layer_backward and ln_backward have a body per precision; the head and the embedding run the fp32 kernels in both.  bf16 (MGPT_PREC_BF16)
@@ -162,6 +178,7 @@ struct Chunk {
     float loss_scale;
     bool bf16;
     hipStream_t s;
+    DropCfg dc;
     const int C = g->C, L = g->L;
     const int64_t M = (int64_t)rows * kT;
     const float *P = g->params;
@@ -169,6 +186,55 @@ struct Chunk {
     const float scale = 1.0f / sqrtf((float)g->hs);
 
     float *x_out(int l) const { return l + 1 < L ? t->X[l + 1] : t->XF; }
+
+    // ----- dropout: is the site on, its mask stream for this chunk, and the two elementwise launches over the chunk's M x C elements -----
+    bool drops(int site) const { return dc.thr > 0 && ((dc.sites >> site) & 1); }
+    trk::Drop drop(int site, int layer) const
+    {
+        trk::Drop d;
+        d.key = trk::drop_key(dc.seed, dc.step, site, layer);
+        d.base = dc.first_row * (site == SITE_ATTN ? (uint64_t)g->nh * kT * kT : (uint64_t)kT * C);
+        d.thr = dc.thr;
+        d.scale = dc.scale;
+        return d;
+    }
+    // out = m s in (in rounded to bf16 first in the bf16 path's backward: the gradient of a bf16 branch output)
+    int drop_scale(int site, int layer, const float *in, float *out, bool round = false)
+    {
+        const int64_t n4 = M * C / 4;
+        if (round) MGPT_LAUNCH(trk::drop_scale_kernel<true>, dim3(grid_1d(n4)), dim3(256), 0, s, in, out, n4, drop(site, layer));
+        else MGPT_LAUNCH(trk::drop_scale_kernel<false>, dim3(grid_1d(n4)), dim3(256), 0, s, in, out, n4, drop(site, layer));
+        return MGPT_OK;
+    }
+    // the gradient that enters a residual branch's c_proj: DX, or m s DX in DXN (free at both points of layer_backward)
+    int branch_grad(int site, int layer, const float **dx)
+    {
+        *dx = t->DX;
+        if (!drops(site)) return MGPT_OK;
+        *dx = t->DXN;
+        return drop_scale(site, layer, t->DX, t->DXN, bf16);
+    }
+    // fp32 path: out = x + m s (A W^T), the branch output through DY (free during the forward)
+    int branch_forward_f32(int site, int layer, const float *A, const float *W, int K, const float *x, float *out)
+    {
+        if (!drops(site)) {
+            MGPT_HIP(hipMemcpyAsync(out, x, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+            return gpt_f32_linear(g, 1, A, W, out, M, C, K, s);
+        }
+        MGPT_TRY(gpt_f32_linear(g, 0, A, W, t->DY, M, C, K, s));
+        const int64_t n4 = M * C / 4;
+        MGPT_LAUNCH(trk::drop_resid_kernel, dim3(grid_1d(n4)), dim3(256), 0, s, x, (const float *)t->DY, out, n4, drop(site, layer));
+        return MGPT_OK;
+    }
+    // bf16 path: out = x + dropout(bf16(A W^T)) in the GEMM's epilogue
+    template <typename TA>
+    int branch_forward_bf16(int site, int layer, const TA *A, const float *W, int K, const float *x, float *out)
+    {
+        tbk::Epi e = epi_resid(out, x, C);
+        if (!drops(site)) return bf_gemm<TA, true, float, true, tbk::E_RESID>(A, K, W, K, M, C, K, e);
+        e.drop = drop(site, layer);
+        return bf_gemm<TA, true, float, true, tbk::E_RESID_DROP>(A, K, W, K, M, C, K, e);
+    }
 
     // out[m][N] (op)= A'(m x K) @ B'(K x N), fp32 on the VALU; slabs > 1: one partial per kps of K
     template <bool A_KC, bool B_NC, int OUT>
@@ -248,29 +314,56 @@ struct Chunk {
     // ----- attention, one workgroup per (row, head) -----
     // fp32 backward: dq | dk | dv of DY into DQKV
     template <int HS>
-    int attn_backward_f32(const float *qkv, const float *y)
+    int attn_backward_f32(int l, const float *qkv, const float *y)
     {
         const dim3 grid((unsigned)(rows * g->nh));
         const int64_t plane = M * C;
-        MGPT_LAUNCH(trk::attn_bwd_q_kernel<HS>, grid, dim3(256), trk::attn_bwd_q_lds<HS>(), s, qkv, plane, y, t->DY, t->DQKV, t->AST, g->nh, scale);
-        MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 0>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale);
-        MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 1>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale);
+        if (drops(SITE_ATTN)) {
+            const trk::Drop d = drop(SITE_ATTN, l);
+            MGPT_LAUNCH((trk::attn_bwd_q_kernel<HS, true>), grid, dim3(256), trk::attn_bwd_q_lds<HS>(), s, qkv, plane, y, t->DY, t->DQKV, t->AST, g->nh, scale, d);
+            MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 0, true>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale, d);
+            MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 1, true>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale, d);
+            return MGPT_OK;
+        }
+        MGPT_LAUNCH(trk::attn_bwd_q_kernel<HS>, grid, dim3(256), trk::attn_bwd_q_lds<HS>(), s, qkv, plane, y, t->DY, t->DQKV, t->AST, g->nh, scale, trk::Drop());
+        MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 0>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale, trk::Drop());
+        MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 1>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale, trk::Drop());
+        return MGPT_OK;
+    }
+
+    // fp32 forward: the inference kernel, or the training instance that masks P
+    template <int HS>
+    int attn_forward_f32(int l)
+    {
+        if (!drops(SITE_ATTN)) return gpt_f32_attention(g, t->QKV[l], t->Y[l], rows, s);
+        MGPT_LAUNCH(trk::attn_fwd_drop_kernel<HS>, dim3((unsigned)(rows * g->nh)), dim3(256), 0, s, (const float *)t->QKV[l], M * C, t->Y[l], g->nh, scale,
+                    drop(SITE_ATTN, l));
         return MGPT_OK;
     }
 
     // bf16 MFMAs: forward (y bf16, statistics fp32) and backward (dq | dk | dv fp32 into DQKV)
     template <int HS>
-    int attn_forward_bf16(const Bf16Layer &v)
+    int attn_forward_bf16(int l, const Bf16Layer &v)
     {
-        MGPT_LAUNCH(tbk::attn_fwd_bf16_kernel<HS>, dim3((unsigned)(rows * g->nh)), dim3(256), tbk::attn_fwd_lds<HS>(), s, v.qkv, M * C, v.y, v.stats, g->nh, scale);
+        if (drops(SITE_ATTN)) {
+            MGPT_LAUNCH((tbk::attn_fwd_bf16_kernel<HS, true>), dim3((unsigned)(rows * g->nh)), dim3(256), tbk::attn_fwd_lds<HS>(), s, v.qkv, M * C, v.y, v.stats, g->nh,
+                        scale, drop(SITE_ATTN, l));
+            return MGPT_OK;
+        }
+        MGPT_LAUNCH(tbk::attn_fwd_bf16_kernel<HS>, dim3((unsigned)(rows * g->nh)), dim3(256), tbk::attn_fwd_lds<HS>(), s, v.qkv, M * C, v.y, v.stats, g->nh, scale, trk::Drop());
         return MGPT_OK;
     }
 
     template <int HS>
-    int attn_backward_bf16(const Bf16Layer &v, const uint16_t *dy)
+    int attn_backward_bf16(int l, const Bf16Layer &v, const uint16_t *dy)
     {
+        if (drops(SITE_ATTN)) {
+            MGPT_LAUNCH((tbk::attn_bwd_bf16_kernel<HS, true>), dim3((unsigned)(rows * g->nh)), dim3(512), tbk::attn_bwd_lds<HS>(), s, v.qkv, M * C, v.y, dy, v.stats,
+                        t->DQKV, g->nh, scale, drop(SITE_ATTN, l));
+            return MGPT_OK;
+        }
         MGPT_LAUNCH(tbk::attn_bwd_bf16_kernel<HS>, dim3((unsigned)(rows * g->nh)), dim3(512), tbk::attn_bwd_lds<HS>(), s, v.qkv, M * C, v.y, dy, v.stats, t->DQKV,
-                    g->nh, scale);
+                    g->nh, scale, trk::Drop());
         return MGPT_OK;
     }
 
@@ -280,14 +373,12 @@ struct Chunk {
         float *x = t->X[l], *xm = t->XM[l], *xo = x_out(l);
         MGPT_TRY(gpt_f32_layernorm(g, x, P + lo.ln1, t->XN1[l], M, s));
         MGPT_TRY(gpt_f32_linear(g, 2, t->XN1[l], P + lo.attn_w, t->QKV[l], M, 3 * C, C, s));
-        MGPT_TRY(gpt_f32_attention(g, t->QKV[l], t->Y[l], rows, s));
-        MGPT_HIP(hipMemcpyAsync(xm, x, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, s));
-        MGPT_TRY(gpt_f32_linear(g, 1, t->Y[l], P + lo.proj_w, xm, M, C, C, s));
+        MGPT_TRY(g->hs == 32 ? attn_forward_f32<32>(l) : attn_forward_f32<64>(l));
+        MGPT_TRY(branch_forward_f32(SITE_ATTN_PROJ, l, t->Y[l], P + lo.proj_w, C, x, xm));
         MGPT_TRY(gpt_f32_layernorm(g, xm, P + lo.ln2, t->XN2[l], M, s));
         MGPT_TRY(gpt_f32_linear(g, 0, t->XN2[l], P + lo.fc_w, t->A[l], M, 4 * C, C, s));
         MGPT_LAUNCH(trk::gelu_kernel, dim3(grid_1d(4 * M * C)), dim3(256), 0, s, t->A[l], t->HT, 4 * M * C);
-        MGPT_HIP(hipMemcpyAsync(xo, xm, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, s));
-        return gpt_f32_linear(g, 1, t->HT, P + lo.proj2_w, xo, M, C, 4 * C, s);
+        return branch_forward_f32(SITE_MLP_PROJ, l, t->HT, P + lo.proj2_w, 4 * C, xm, xo);
     }
 
     int layer_forward_bf16(int l)
@@ -297,11 +388,11 @@ struct Chunk {
         float *x = t->X[l], *xm = t->XM[l];
         MGPT_TRY(gpt_f32_layernorm(g, x, P + lo.ln1, t->XN1[l], M, s));
         MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_QKV>(t->XN1[l], C, P + lo.attn_w, C, M, 3 * C, C, epi_qkv(v.qkv, C, g->hs, g->nh, M * C))));
-        MGPT_TRY(g->hs == 32 ? attn_forward_bf16<32>(v) : attn_forward_bf16<64>(v));
-        MGPT_TRY((bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(v.y, C, P + lo.proj_w, C, M, C, C, epi_resid(xm, x, C))));
+        MGPT_TRY(g->hs == 32 ? attn_forward_bf16<32>(l, v) : attn_forward_bf16<64>(l, v));
+        MGPT_TRY(branch_forward_bf16(SITE_ATTN_PROJ, l, v.y, P + lo.proj_w, C, x, xm));
         MGPT_TRY(gpt_f32_layernorm(g, xm, P + lo.ln2, t->XN2[l], M, s));
         MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_FC>(t->XN2[l], C, P + lo.fc_w, C, M, 4 * C, C, epi_fc(v.a, v.h, 4 * C))));
-        return bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(v.h, 4 * C, P + lo.proj2_w, 4 * C, M, C, 4 * C, epi_resid(x_out(l), xm, C));
+        return branch_forward_bf16(SITE_MLP_PROJ, l, v.h, P + lo.proj2_w, 4 * C, xm, x_out(l));
     }
 
     // head (model.py:178-184), fp32 in both precisions: ln_f, logits = ln_f(x) @ wte^T at every position, cross-entropy
@@ -325,17 +416,20 @@ struct Chunk {
     int layer_backward_f32(int l)
     {
         const LayerOff &lo = g->layers[l];
-        // MLP (model.py:85-87,103): DX = d x_out
-        MGPT_TRY((tr_gemm<true, true, trk::OUT_GELU_BWD>(t->DX, C, P + lo.proj2_w, 4 * C, t->DH, 4 * C, M, 4 * C, C, t->A[l])));
+        // MLP (model.py:85-88,103): DX = d x_out, db = the gradient of c_proj's output (m s DX under dropout)
+        const float *db;
+        MGPT_TRY(branch_grad(SITE_MLP_PROJ, l, &db));
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_GELU_BWD>(db, C, P + lo.proj2_w, 4 * C, t->DH, 4 * C, M, 4 * C, C, t->A[l])));
         MGPT_LAUNCH(trk::gelu_kernel, dim3(grid_1d(4 * M * C)), dim3(256), 0, s, t->A[l], t->HT, 4 * M * C);
-        MGPT_TRY(weight_grad(t->DX, t->HT, G + lo.proj2_w, C, 4 * C));
+        MGPT_TRY(weight_grad(db, t->HT, G + lo.proj2_w, C, 4 * C));
         MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DH, 4 * C, P + lo.fc_w, C, t->DXN, C, M, C, 4 * C)));
         MGPT_TRY(weight_grad(t->DH, t->XN2[l], G + lo.fc_w, 4 * C, C));
         MGPT_TRY(ln_backward<true>(t->XM[l], lo.ln2));
         // attention (model.py:50-71,102): DX = d x_mid
-        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DX, C, P + lo.proj_w, C, t->DY, C, M, C, C)));
-        MGPT_TRY(weight_grad(t->DX, t->Y[l], G + lo.proj_w, C, C));
-        MGPT_TRY(g->hs == 32 ? attn_backward_f32<32>(t->QKV[l], t->Y[l]) : attn_backward_f32<64>(t->QKV[l], t->Y[l]));
+        MGPT_TRY(branch_grad(SITE_ATTN_PROJ, l, &db));
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(db, C, P + lo.proj_w, C, t->DY, C, M, C, C)));
+        MGPT_TRY(weight_grad(db, t->Y[l], G + lo.proj_w, C, C));
+        MGPT_TRY(g->hs == 32 ? attn_backward_f32<32>(l, t->QKV[l], t->Y[l]) : attn_backward_f32<64>(l, t->QKV[l], t->Y[l]));
         MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DQKV, 3 * C, P + lo.attn_w, C, t->DXN, C, M, C, 3 * C)));
         MGPT_TRY(weight_grad(t->DQKV, t->XN1[l], G + lo.attn_w, 3 * C, C));
         return ln_backward<true>(t->X[l], lo.ln1);
@@ -346,16 +440,19 @@ struct Chunk {
         const LayerOff &lo = g->layers[l];
         const Bf16Layer v = bf16_layer(t, l, M, C);
         const Bf16Grads d = bf16_grads(t);
-        // MLP: DX = d x_out (its bf16 rounding is the gradient of the bf16 c_proj output)
-        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_GELU_BWD>(t->DX, C, P + lo.proj2_w, 4 * C, M, 4 * C, C, epi_gelu_bwd(d.da, v.a, 4 * C))));
-        MGPT_TRY(weight_grad_bf16(t->DX, v.h, G + lo.proj2_w, C, 4 * C));
+        // MLP: DX = d x_out (its bf16 rounding is the gradient of the bf16 c_proj output; under dropout db = m s bf16(DX), rounded as it is staged)
+        const float *db;
+        MGPT_TRY(branch_grad(SITE_MLP_PROJ, l, &db));
+        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_GELU_BWD>(db, C, P + lo.proj2_w, 4 * C, M, 4 * C, C, epi_gelu_bwd(d.da, v.a, 4 * C))));
+        MGPT_TRY(weight_grad_bf16(db, v.h, G + lo.proj2_w, C, 4 * C));
         MGPT_TRY((bf_gemm<uint16_t, true, float, false, tbk::E_F32>(d.da, 4 * C, P + lo.fc_w, C, M, C, 4 * C, epi_f32(t->DXN, C))));
         MGPT_TRY(weight_grad_bf16(d.da, t->XN2[l], G + lo.fc_w, 4 * C, C));
         MGPT_TRY(ln_backward<true>(t->XM[l], lo.ln2));
         // attention: DX = d x_mid;  d y = bf16(DX W_proj), the gradient of the bf16 attention output
-        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_B16>(t->DX, C, P + lo.proj_w, C, M, C, C, epi_b16(d.dy, C))));
-        MGPT_TRY(weight_grad_bf16(t->DX, v.y, G + lo.proj_w, C, C));
-        MGPT_TRY(g->hs == 32 ? attn_backward_bf16<32>(v, d.dy) : attn_backward_bf16<64>(v, d.dy));
+        MGPT_TRY(branch_grad(SITE_ATTN_PROJ, l, &db));
+        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_B16>(db, C, P + lo.proj_w, C, M, C, C, epi_b16(d.dy, C))));
+        MGPT_TRY(weight_grad_bf16(db, v.y, G + lo.proj_w, C, C));
+        MGPT_TRY(g->hs == 32 ? attn_backward_bf16<32>(l, v, d.dy) : attn_backward_bf16<64>(l, v, d.dy));
         MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_F32>(t->DQKV, 3 * C, P + lo.attn_w, C, M, C, 3 * C, epi_f32(t->DXN, C))));
         MGPT_TRY(weight_grad_bf16(t->DQKV, t->XN1[l], G + lo.attn_w, 3 * C, C));
         return ln_backward<true>(t->X[l], lo.ln1);
@@ -365,21 +462,34 @@ struct Chunk {
     int layer_backward(int l) { return bf16 ? layer_backward_bf16(l) : layer_backward_f32(l); }
 
     // embedding (model.py:171-175), fp32 in both precisions: d wpe[t] += sum over rows, d wte[id] += sum over the tokens with that id
+    // under dropout X[0] = m s (wte + wpe) (model.py:175) and the sums take m s DX (in DXN, free after the last LayerNorm backward)
+    int embed()
+    {
+        MGPT_TRY(gpt_f32_embed(g, tok, t->X[0], M, s));
+        return drops(SITE_EMBED) ? drop_scale(SITE_EMBED, 0, t->X[0], t->X[0]) : MGPT_OK;
+    }
+
     int embedding_backward()
     {
-        MGPT_LAUNCH(trk::wpe_bwd_kernel, dim3((unsigned)cdiv64((int64_t)kT * C, 256)), dim3(256), 0, s, t->DX, rows, C, G + g->off_wpe);
+        const float *dx = t->DX;
+        if (drops(SITE_EMBED)) {
+            MGPT_TRY(drop_scale(SITE_EMBED, 0, t->DX, t->DXN));
+            dx = t->DXN;
+        }
+        MGPT_LAUNCH(trk::wpe_bwd_kernel, dim3((unsigned)cdiv64((int64_t)kT * C, 256)), dim3(256), 0, s, dx, rows, C, G + g->off_wpe);
         return slab_sum(G + g->off_wte, (int64_t)kV * C, 16, [&](int S, int kps) -> int {
-            MGPT_LAUNCH(trk::wte_bwd_part_kernel, dim3(kV, (unsigned)S), dim3(256), 0, s, tok, t->DX, M, C, kps, t->part);
+            MGPT_LAUNCH(trk::wte_bwd_part_kernel, dim3(kV, (unsigned)S), dim3(256), 0, s, tok, dx, M, C, kps, t->part);
             return MGPT_OK;
         });
     }
 };
 
 // one chunk of rows: forward with saved activations, cross-entropy against the call's target count, backward into t->grads
-int chunk_fwd_bwd(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows, const int32_t *tg, float loss_scale, int precision, hipStream_t s)
+int chunk_fwd_bwd(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows, const int32_t *tg, float loss_scale, int precision, const DropCfg &dc,
+                  hipStream_t s)
 {
-    Chunk c = {g, t, tok, tg, rows, loss_scale, precision == MGPT_PREC_BF16, s};
-    MGPT_TRY(gpt_f32_embed(g, tok, t->X[0], c.M, s));
+    Chunk c = {g, t, tok, tg, rows, loss_scale, precision == MGPT_PREC_BF16, s, dc};
+    MGPT_TRY(c.embed());
     for (int l = 0; l < g->L; l++) MGPT_TRY(c.layer_forward(l));
     MGPT_TRY(c.head_forward());
     MGPT_TRY(c.head_backward());
@@ -496,6 +606,15 @@ extern "C" int mgpt_gpt_forward_backward(mgpt_gpt *g, const uint8_t *d_tokens, i
 extern "C" int mgpt_gpt_forward_backward_prec(mgpt_gpt *g, const uint8_t *d_tokens, int rows, int T, const int32_t *d_targets, float loss_scale,
                                               float *d_loss, int precision, void *stream)
 {
+    return mgpt_gpt_forward_backward_drop(g, d_tokens, rows, T, d_targets, loss_scale, d_loss, precision, 0.f, 0, 0, 0, 0, stream);
+}
+
+extern "C" int mgpt_gpt_forward_backward_drop(mgpt_gpt *g, const uint8_t *d_tokens, int rows, int T, const int32_t *d_targets, float loss_scale,
+                                              float *d_loss, int precision, float p, uint64_t seed, uint64_t step, uint64_t row0, int sites,
+                                              void *stream)
+{
+    MGPT_REQUIRE(p >= 0.f && p < 1.f, MGPT_ERR_ARG, "dropout p=%g: a probability in [0, 1)", (double)p);
+    MGPT_REQUIRE(sites >= 0 && sites <= 15, MGPT_ERR_ARG, "dropout sites=%d: a mask of the four sites (15 = all, model.py's behaviour)", sites);
     MGPT_TRY(require_train(g));
     MGPT_REQUIRE(d_tokens && d_targets, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(rows > 0, MGPT_ERR_ARG, "rows=%d", rows);
@@ -513,11 +632,18 @@ extern "C" int mgpt_gpt_forward_backward_prec(mgpt_gpt *g, const uint8_t *d_toke
     MGPT_REQUIRE(t->h_cnt[1] == 0, MGPT_ERR_ARG, "targets must lie in [-1, 67): -1 is ignored, 0 .. 66 are vocabulary ids");
     MGPT_REQUIRE(t->h_cnt[0] > 0, MGPT_ERR_ARG, "no targeted position in the call (every target is -1): the mean cross-entropy is undefined");
     MGPT_HIP(hipMemsetAsync(t->loss_acc, 0, sizeof(double), s));
+    // the 16-bit threshold of sampling.py: dropout_threshold, and the kept elements' factor 1 / (1 - thr / 65536)
+    DropCfg dc;
+    dc.thr = (uint32_t)std::min<long>(std::lround((double)p * 65536.0), 65535);
+    dc.scale = 1.0f / (1.0f - (float)dc.thr / 65536.0f);
+    dc.seed = seed; dc.step = step; dc.sites = sites;
+    MGPT_REQUIRE(dc.thr == 0 || sites == 0 || g->C % 4 == 0, MGPT_ERR_UNSUPPORTED, "dropout masks come four elements to a hash: n_embd = %d is no multiple of 4", g->C);
     for (int r0 = 0; r0 < rows; r0 += t->max_rows) {
         const int n = std::min(t->max_rows, rows - r0);
         const uint8_t *tk = d_tokens + (size_t)r0 * kT;
         const int32_t *tg = d_targets + (size_t)r0 * kT;
-        MGPT_TRY(chunk_fwd_bwd(g, t, tk, n, tg, loss_scale, precision, s));
+        dc.first_row = row0 + (uint64_t)r0;
+        MGPT_TRY(chunk_fwd_bwd(g, t, tk, n, tg, loss_scale, precision, dc, s));
     }
     if (d_loss) MGPT_LAUNCH(trk::loss_final_kernel, dim3(1), dim3(64), 0, s, (const double *)t->loss_acc, t->cnt, d_loss);
     return MGPT_OK;

@@ -43,8 +43,9 @@ class GPT:
         # exact-fp32 kernels -- precision="f16x3" then follows the envelope policy (fallback: fp32), "bf16" raises (include/mapf_gpt_amd.h)
         if not (0.0 <= config.dropout < 1.0):
             raise ValueError("dropout must be in [0, 1)")
-        # dropout: accepted and ignored -- this is the inference path, and the reference serves every model in eval mode
-        # (inference.py:85 net.eval(): nn.Dropout and scaled_dot_product_attention's dropout_p are the identity there, model.py:33-34,59,82,129)
+        # dropout: the identity on every inference and scoring path -- the reference serves every model in eval mode (inference.py:85
+        # net.eval(): nn.Dropout and scaled_dot_product_attention's dropout_p are the identity there, model.py:33-34,59,82,129); only
+        # forward_backward in training mode applies it
         self.config = config
         self.max_rows = int(max_rows)
         self.precision = precision
@@ -296,12 +297,16 @@ class GPT:
         """mode=True: training mode.  The first call allocates the training workspace (max_rows rows per chunk, default: the model's max_rows)
         with zeroed gradients and AdamW moments.  Later calls keep it: train() with no max_rows changes nothing (train.py calls model.train()
         after every evaluation), a different max_rows re-sizes the activation part only -- gradients, moments and step counts survive.
-        train(False) = eval() and keeps the workspace.  Released configs only: bias=False, dropout=0, block_size 256."""
+        train(False) = eval() and keeps the workspace.  bias=False and block_size 256 only.  config.dropout > 0: forward_backward drops as
+        model.py does in training mode, with masks of the stream set_dropout_rng(seed) pinned; after eval() it runs without dropout, as
+        torch does.  The masks are a counter hash with no generator behind it, so there is no default seed: train() of a dropout > 0 config
+        before set_dropout_rng raises NotImplementedError, as it did when dropout was not built."""
         if not mode:
             return self.eval()
         assert self._loaded, "load_state_dict first"
-        if self.config.dropout > 0:
-            raise NotImplementedError("training with dropout > 0 is not supported (the released configs train with dropout = 0)")
+        if self.config.dropout > 0 and getattr(self, "_drop_seed", None) is None:
+            raise NotImplementedError("training with dropout > 0 draws its masks from a counter hash keyed by a seed, and no default seed is "
+                                      "implemented: call set_dropout_rng(seed) before train()")
         have = getattr(self, "_train_rows", None)
         rows = int(max_rows) if max_rows is not None else (have or self.max_rows)
         if have != rows:
@@ -315,11 +320,20 @@ class GPT:
         if getattr(self, "_train_rows", None) is None:
             raise RuntimeError("call train() first: it allocates the training workspace")
 
-    def forward_backward(self, idx, targets, loss_scale=1.0, precision="f32"):
+    def set_dropout_rng(self, seed, step=0):
+        """Pin the dropout masks of forward_backward: mask = f(seed, step, site, layer, element) (sampling.dropout_keep), a counter hash as the
+        action sampler's.  forward_backward uses `step` and increments it per call.  A dropout > 0 config needs this call before train()."""
+        self._drop_seed, self._drop_step = int(seed), int(step)
+
+    def forward_backward(self, idx, targets, loss_scale=1.0, precision="f32", *, dropout_step=None, row0=0, dropout_sites=15):
         """= loss = model(idx, targets)[1]; (loss * loss_scale).backward() (model.py:180-184, train.py:324-331): gradients ACCUMULATE into the
         device buffer; returns the unscaled mean cross-entropy (ignore_index=-1) as a 0-d float32 device tensor.  precision "f32": exact fp32;
         "bf16": train.py's torch.amp.autocast(bfloat16) regime (bf16 MFMA linears, fp32 gradients and master weights).  Micro-steps of
-        either precision accumulate into the same buffer."""
+        either precision accumulate into the same buffer.
+        In training mode a config.dropout > 0 drops at model.py's four places (:129/:175, :59/:66, :71, :88) with masks keyed by
+        (set_dropout_rng's seed, step, row0 + row): dropout_step overrides the call counter and does not increment it, row0 is the global
+        index of the call's first row (so a batch split over calls draws the masks of the whole batch), dropout_sites a bit mask of the four
+        places (15 = all; tests name one).  After eval() / train(False) the call runs without dropout."""
         if precision not in _lib.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}, got {precision!r}")
         self._require_train()
@@ -330,9 +344,16 @@ class GPT:
             raise ValueError(f"targets must be an integer tensor of {B * T} elements (idx is {B} x {T}), got {targets.dtype} {tuple(targets.shape)}")
         tg = targets.reshape(B, T).to(device=self.device, dtype=torch.int32).contiguous()
         loss = torch.empty((), dtype=torch.float32, device=self.device)
+        p = float(self.config.dropout) if self.training else 0.0
+        step = dropout_step
+        if step is None:
+            step = getattr(self, "_drop_step", 0)
+            if p > 0:
+                self._drop_step = step + 1
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().mgpt_gpt_forward_backward_prec(self._h, _lib.ptr(tokens), B, T, _lib.ptr(tg), float(loss_scale), _lib.ptr(loss),
-                                                                 _lib.PRECISIONS[precision], _lib.stream_ptr()))
+            _lib.check(_lib.lib().mgpt_gpt_forward_backward_drop(self._h, _lib.ptr(tokens), B, T, _lib.ptr(tg), float(loss_scale), _lib.ptr(loss),
+                                                                 _lib.PRECISIONS[precision], p, (getattr(self, "_drop_seed", None) or 0) & 0xFFFFFFFFFFFFFFFF,
+                                                                 int(step) & 0xFFFFFFFFFFFFFFFF, int(row0), int(dropout_sites), _lib.stream_ptr()))
         return loss
 
     def zero_grad(self, set_to_none=True):

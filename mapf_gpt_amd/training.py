@@ -149,6 +149,9 @@ def parse_args(argv=None):
             ap.add_argument("--" + k.replace("_", "-"), type=type(v), default=v)
     ap.add_argument("--dtype", default="float32", choices=["float32", "bfloat16", "float16"],
                     help="float32 (default here; train.py defaults to bfloat16) or bfloat16 (autocast regime); float16 is refused")
+    ap.add_argument("--dropout", type=float, default=None,
+                    help="dropout probability of the training forward (train.py:43: 0 for pre-training, 0.1+ for fine-tuning); default: the "
+                         "--init checkpoint's model_args value, 0.0 for a shape name.  Stored in the checkpoint's model_args")
     ap.add_argument("--log-interval", type=int, default=0,
                     help='print {"iter", "loss", "ms"} every N iterations (train.py:346-355); 0 = no such line')
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -159,8 +162,17 @@ def parse_args(argv=None):
     if a.dtype == "float16":
         ap.error("--dtype float16 is not supported: it needs torch's GradScaler, which this training path does not have "
                  "(use bfloat16, which needs none, or float32)")
+    if a.dropout is not None and not (0.0 <= a.dropout < 1.0):
+        ap.error("--dropout must lie in [0, 1)")
     a.precision = DTYPES[a.dtype]
     return a
+
+
+def dropout_step(iter_num, total_accum, rank, world, micro):
+    """The mask step of micro-step `micro` of rank `rank` in iteration `iter_num`: i * A + r * (A / world) + j with A the accumulation
+    steps of the whole run.  A pure function of the loop's counters: a resumed run needs no new state, and one process that replays the
+    ranks' micro-steps in rank order draws the same masks."""
+    return iter_num * total_accum + rank * (total_accum // world) + micro
 
 
 class Ranks:
@@ -244,8 +256,11 @@ def run(a, ranks):
             ckpt = torch.load(a.init, map_location="cpu", weights_only=True)
     else:                                          # --seed on every rank: all build the weights DDP would broadcast from rank 0
         args, sd = weights.model_args(a.init), weights.synthetic_state_dict(a.init, seed=a.seed)
+    if a.dropout is not None:                      # the flag overrides the checkpoint's value
+        args = dict(args, dropout=float(a.dropout))
     net = GPT(GPTConfig(**args), max_rows=a.batch_size, precision="f32")
     net.load_state_dict(sd)
+    net.set_dropout_rng(a.seed)                    # dropout seed = --seed; the step is set per micro-step (dropout_step)
     net.train(max_rows=a.batch_size)
     opt = net.configure_optimizers(a.weight_decay, a.learning_rate, (a.beta1, a.beta2), "cuda")
     iter_num, best_val_loss = 0, 1e9
@@ -288,8 +303,9 @@ def run(a, ranks):
                                os.path.join(a.out_dir, "ckpt.pt"))
                     rec["saved"] = os.path.join(a.out_dir, "ckpt.pt")
             print(json.dumps(rec), flush=True)
-        for _ in range(accum):                                 # train.py:314-331
-            loss = net.forward_backward(torch.as_tensor(X), torch.as_tensor(Y), loss_scale=1.0 / accum, precision=a.precision)
+        for micro in range(accum):                             # train.py:314-331
+            loss = net.forward_backward(torch.as_tensor(X), torch.as_tensor(Y), loss_scale=1.0 / accum, precision=a.precision,
+                                        dropout_step=dropout_step(iter_num, a.gradient_accumulation_steps, rank, world, micro))
             X, Y = next(train_it)
         if ranks is not None:                                  # train.py:315-322: the ranks' gradients meet after the last micro-step
             ranks.sync_grads(net)

@@ -2,7 +2,7 @@
 as a yardstick only, torch fp32 eager autograd of an in-repo restatement of model.py (oracle/gpt_oracle.py's formulas) on the same GPU.
 
     python tools/bench_train.py [--shapes 6M:512,6M:2048,2M:4096,85M:512] [--precision f32,bf16] [--torch-rows 512] [--iters 3] [--warmup 1]
-                                [--lib PATH]
+                                [--dropout P] [--lib PATH]
     python tools/bench_train.py --grad-sync WORLD [--grad-sync-shapes 6M,85M] [--iters 5] [--warmup 2]
 
 --lib PATH times another build of the library (a file `python -m mapf_gpt_amd.build --out` writes) in place of the in-tree one: the same
@@ -12,6 +12,9 @@ flops of the call (the products the model executes, 2 per multiply-add, backward
 excluded) and, for bf16, the bytes its kernels move to and from memory (count_bytes below: every tensor read or written once per kernel,
 weights and L2 reuse not counted), with the achieved rate and the roofline bound against 2.5 PFLOP/s (bf16 MFMA) or 157 TFLOP/s (fp32) and
 8 TB/s.  The bf16 torch yardstick is the same restatement under torch.autocast("cuda", torch.bfloat16), train.py's regime.
+
+--dropout P times forward_backward of a dropout = P model in training mode (masks regenerated in the kernels, none stored) and gives the
+torch yardstick the same p: nn.Dropout at model.py's three places and scaled_dot_product_attention's dropout_p, torch's own streams.
 
 --grad-sync WORLD times the device side of the data-parallel gradient synchronisation on one GPU (mapf_gpt_amd/training.py: export_grads,
 all_gather, reduce_grads): GPT.export_grads() and GPT.reduce_grads(gathered, 1 / WORLD) with a gathered array of WORLD rows of the size of the
@@ -69,9 +72,26 @@ def count_bytes(args, rows, T=256, V=67):
     return rows * T * (L * 296 * C + 16 * V + 24 * C)
 
 
-def torch_step(name, tokens, targets, autocast=False):
+def dropout_forward(w, args, idx, p):
+    """model.py's training-mode forward up to the last block's output: oracle/gpt_oracle.py's formulas with dropout at :175, :59, :71, :88"""
+    import torch.nn.functional as F
+    B, T = idx.shape
+    nh, C = args["n_head"], args["n_embd"]
+    x = F.dropout(w["transformer.wte.weight"][idx] + w["transformer.wpe.weight"][:T], p)
+    for l in range(args["n_layer"]):
+        k_ = f"transformer.h.{l}."
+        qkv = F.linear(F.layer_norm(x, (C,), w[k_ + "ln_1.weight"], None, 1e-5), w[k_ + "attn.c_attn.weight"])
+        q, k, v = (t.view(B, T, nh, C // nh).transpose(1, 2) for t in qkv.split(C, dim=2))
+        y = F.scaled_dot_product_attention(q, k, v, attn_mask=None, dropout_p=p, is_causal=False).transpose(1, 2).contiguous().view(B, T, C)
+        x = x + F.dropout(F.linear(y, w[k_ + "attn.c_proj.weight"]), p)
+        h = F.gelu(F.linear(F.layer_norm(x, (C,), w[k_ + "ln_2.weight"], None, 1e-5), w[k_ + "mlp.c_fc.weight"]))
+        x = x + F.dropout(F.linear(h, w[k_ + "mlp.c_proj.weight"]), p)
+    return x
+
+
+def torch_step(name, tokens, targets, autocast=False, dropout=0.0):
     """torch fp32 eager (autocast: under torch.autocast("cuda", torch.bfloat16)): loss = cross-entropy of ln_f(x) @ wte^T over every
-    position (model.py:178-184), backward into .grad"""
+    position (model.py:178-184), backward into .grad; dropout > 0: the training-mode forward with torch's own masks"""
     import torch.nn.functional as F
     from mapf_gpt_amd import weights
     from oracle import gpt_oracle
@@ -84,7 +104,7 @@ def torch_step(name, tokens, targets, autocast=False):
 
     def step():
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
-            x = gpt_oracle.forward_logits(view, args, idx, return_layers=True)[1][-1]
+            x = dropout_forward(view, args, idx, dropout) if dropout > 0 else gpt_oracle.forward_logits(view, args, idx, return_layers=True)[1][-1]
             h = F.layer_norm(x, (x.shape[-1],), view["transformer.ln_f.weight"], None, 1e-5)
             loss = F.cross_entropy((h @ view["lm_head.weight"].t()).reshape(-1, 67), tg.reshape(-1), ignore_index=-1)
         loss.backward()
@@ -128,6 +148,7 @@ def main(argv=None):
     ap.add_argument("--shapes", default="6M:512,6M:2048,2M:4096,85M:512")
     ap.add_argument("--precision", default="f32,bf16", help="comma-separated training precisions: f32, bf16")
     ap.add_argument("--torch-rows", type=int, default=512)
+    ap.add_argument("--dropout", type=float, default=0.0, help="dropout probability of the timed call and of the torch yardstick")
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--lib", default=None, help="path of the library to time (default: the in-tree build)")
@@ -147,7 +168,9 @@ def main(argv=None):
         from mapf_gpt_amd import weights
         args = weights.model_args(name)
         for prec in a.precision.split(","):
-            net = build_model(name, seed=0, max_rows=rows).train()
+            net = build_model(dict(args, dropout=a.dropout), seed=0, max_rows=rows)
+            net.set_dropout_rng(0)
+            net.train()
             opt = net.configure_optimizers(0.1, 6e-4, (0.9, 0.95))
             fb = timed(lambda: net.forward_backward(tokens, targets, precision=prec), a.iters, a.warmup)
 
@@ -157,7 +180,7 @@ def main(argv=None):
             cs = timed(clip_step, a.iters, a.warmup)
             fw = timed(lambda: net.forward(tokens, targets), a.iters, a.warmup)
             flops = count_flops(args, rows)
-            rec = {"shape": name, "rows": rows, "precision": prec, "forward_backward_ms": round(fb, 3), "clip_step_ms": round(cs, 3),
+            rec = {"shape": name, "rows": rows, "precision": prec, "dropout": a.dropout, "forward_backward_ms": round(fb, 3), "clip_step_ms": round(cs, 3),
                    "forward_f32_ms": round(fw, 3), "fb_over_forward": round(fb / fw, 3), "gflop": round(flops / 1e9, 1),
                    "tflops": round(flops / fb / 1e9, 1), "flop_bound_ms": round(flops / PEAK_FLOPS[prec] * 1e3, 3)}
             if prec == "bf16":
@@ -171,7 +194,7 @@ def main(argv=None):
                 rec["torch_rows"] = tr
                 try:
                     key = "torch_autocast_fwd_bwd_ms" if prec == "bf16" else "torch_fwd_bwd_ms"
-                    rec[key] = round(timed(torch_step(name, tokens[:tr], targets[:tr], autocast=prec == "bf16"), a.iters, a.warmup), 3)
+                    rec[key] = round(timed(torch_step(name, tokens[:tr], targets[:tr], prec == "bf16", a.dropout), a.iters, a.warmup), 3)
                     rec["ours_per_row_over_torch"] = round((fb / rows) / (rec[key] / tr), 3)
                 except torch.cuda.OutOfMemoryError:
                     rec[key] = "out of memory"
