@@ -575,6 +575,24 @@ int mgpt_expert_set_refine(mgpt_expert *ex, int max_rounds, int horizon);
 int mgpt_expert_copy_refine(mgpt_expert *ex, int32_t *d_first_status, int32_t *d_first_length, int32_t *d_soc_before, int32_t *d_soc_after,
                             int32_t *d_rounds, int32_t *d_replans, void *stream);
 
+/* Lifelong episodes (on_target = restart; DESIGN.md section 30: section 20's plan on goals that move, the role of run_expert() on the
+ * reference's lifelong env, create_env.py:28-32).  Off by default: without it every call above behaves as it did, the refusal of a
+ * lifelong env included.
+ *   set_lifelong:  on = 1 / 0, any other value is MGPT_ERR_ARG.  Before mgpt_expert_reset or between episodes (MGPT_ERR_STATE in the middle
+ *                  of one; reads the done flags as set_swap does); a reset must follow before the next step.  MGPT_ERR_UNSUPPORTED together
+ *                  with the search in either order (set_search, and set_refine with it, look for a joint goal configuration).  The order of
+ *                  calls is create (on an env that is not lifelong yet), set_lifelong(1), mgpt_env_set_lifelong, the resets.
+ *   reset / step:  with it on the env must be lifelong: MGPT_ERR_STATE otherwise (mgpt_env_set_lifelong must come first).  A step is
+ *                  plan -> log -> mgpt_env_step -> mgpt_tokenizer_update_agents(goals_may_change = 1) on the borrowed tokenizer, fed the
+ *                  actions just made, which rebuilds the distance field of every agent whose goal changed -> the post-step kernel
+ *                  (timing-hook name expert_lifelong_post): since = 0 for an agent whose new cell is the goal it pursued during the step
+ *                  (the env's own arrival test), else since + 1, and the arrivals of the step.  Episodes end by truncation only.
+ *   copy_arrivals: int16 [n_inst][max_steps]: arrivals per instance and step (0 beyond the steps made); their sum over an episode is the
+ *                  sum over the agents of mgpt_env_lifelong_counts.  MGPT_ERR_STATE with lifelong planning off or before a reset.
+ */
+int mgpt_expert_set_lifelong(mgpt_expert *ex, int on);
+int mgpt_expert_copy_arrivals(mgpt_expert *ex, int16_t *d_arrivals_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Kernel timing hooks (bench.py's live roofline): when enabled, the library brackets every kernel
  * class with hipEvents on the launch stream.  mgpt_prof_read synchronises the device.

@@ -134,6 +134,8 @@ SYMBOLS = {
     "mgpt_expert_copy_solution": (_i, [_vp, _vp, _vp]),
     "mgpt_expert_set_refine": (_i, [_vp, _i, _i]),
     "mgpt_expert_copy_refine": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mgpt_expert_set_lifelong": (_i, [_vp, _i]),
+    "mgpt_expert_copy_arrivals": (_i, [_vp, _vp, _vp]),
     "mgpt_prof_enable": (_i, [_i]),
     "mgpt_prof_reset": (_i, []),
     "mgpt_prof_read": (_i, [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float),
@@ -155,6 +157,8 @@ def lib():
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SYMBOLS.items():
+            if _OVERRIDE and not hasattr(L, name):      # a variant built from an older checkout (tools/ab.py): calling what it lacks raises
+                continue
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args

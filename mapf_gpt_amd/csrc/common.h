@@ -73,6 +73,7 @@ enum ProfId {
     P_EXPERT_SEARCH,                                    // the LaCAM search kernel, every launch of a solve (expert.hip)
     P_EXPERT_CELL_DEGREE,                               // the swap rule's degree map, once per context (expert.hip)
     P_EXPERT_REFINE_PATH, P_EXPERT_REFINE_ROUND, P_EXPERT_REFINE_FINAL,   // the refinement pass of a solve: path, every round, final (expert.hip)
+    P_EXPERT_LIFELONG_POST,                             // lifelong episodes: arrivals, since and the arrivals log after the env step (expert.hip)
     P_COUNT
 };
 

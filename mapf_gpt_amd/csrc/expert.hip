@@ -8,6 +8,8 @@
 // opt-in corridor swap rule is the SWAP = true instantiation of both kernels.  The generator itself is one
 // device function, pibt_generate, that both kernels call.  An opt-in pass between the search and the episode
 // refines a found solution by replanning one agent at a time against the others' paths (refine_*_kernel below).
+// Opt-in lifelong episodes keep the plan kernel and change what follows the env step: the borrowed tokenizer
+// rebuilds the fields of the agents whose goal changed and pibt_lifelong_post_kernel stands in pibt_since_kernel's place.
 //
 // One step of one instance:
 //   order      agents by (since desc, id asc), since = steps since the agent last stood on its goal;
@@ -411,6 +413,35 @@ __global__ void pibt_since_kernel(const int16_t *__restrict__ pos, const int16_t
     if (done[i / n_agents] != 0) return;
     const bool on = pos[2 * i] == goal[2 * i] && pos[2 * i + 1] == goal[2 * i + 1];
     since[i] = on ? 0u : since[i] + 1u;
+}
+
+// ---- lifelong episodes: the post-step kernel, in pibt_since_kernel's place when mgpt_expert_set_lifelong is on ----
+// After the env has stepped an agent that arrived already holds the next goal of its queue, so "on the goal" is decided against `held`,
+// the expert's own copy of the goals the agents pursued during the step: arrived = the new cell equals the held goal, which is the env's
+// own test on the same values, so the count equals the env's `reached` exactly.  Then held takes the env's goals for the next step.
+// One wave64 workgroup per instance, the agents in a strided loop (a cell is one 32-bit word: row | column << 16), the arrivals of the
+// step summed by shuffles and written by lane 0 to arrivals[inst][t].  `live` says the instance was not done when the step began: the
+// env's done flag cannot, it is already set after the episode's last step, whose arrivals still count.  Plain vector stores only.
+__global__ __launch_bounds__(64) void pibt_lifelong_post_kernel(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ goal,
+                                                                const uint8_t *__restrict__ done, uint32_t *__restrict__ since,
+                                                                uint32_t *__restrict__ held, uint8_t *__restrict__ live,
+                                                                int16_t *__restrict__ arrivals, int n_agents, int max_steps, int64_t t)
+{
+    const int inst = blockIdx.x, lane = threadIdx.x;
+    if (live[inst] == 0) return;                                          // wave-uniform: done before this step, nothing moved
+    const size_t g0 = (size_t)inst * n_agents;
+    int n = 0;
+    for (int a = lane; a < n_agents; a += 64) {
+        const bool on = pos[g0 + a] == held[g0 + a];
+        since[g0 + a] = on ? 0u : since[g0 + a] + 1u;
+        held[g0 + a] = goal[g0 + a];
+        n += on ? 1 : 0;
+    }
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+    if (lane == 0) {
+        if (t < (int64_t)max_steps) arrivals[(size_t)inst * max_steps + t] = (int16_t)n;
+        live[inst] = done[inst] == 0 ? 1 : 0;
+    }
 }
 
 // ---- LaCAM search over the PIBT generator ---------------------------------------------------------------
@@ -946,7 +977,14 @@ struct mgpt_expert {
         int max_rounds = 0, horizon = 0;
         int32_t *path = nullptr, *arr = nullptr, *rstate = nullptr, *adopted = nullptr;
     } rf;
-    DeviceArena mem, search_mem, deg_mem, refine_mem;   // occ .. len; ls; deg; rf
+    // lifelong episodes (mgpt_expert_set_lifelong): off (all NULL) by default
+    bool lifelong = false;
+    struct Lifelong {                           // buffers, owned by lifelong_mem
+        uint32_t *held = nullptr;               // [n_inst][n_agents] the goal every agent pursued during the step (row | column << 16)
+        uint8_t *live = nullptr;                // [n_inst] the instance was not done when the last step began
+        int16_t *arrivals = nullptr;            // [n_inst][max_steps] arrivals per step
+    } lf;
+    DeviceArena mem, search_mem, deg_mem, refine_mem, lifelong_mem;   // occ .. len; ls; deg; rf; lf
 };
 
 // launches the SWAP instantiation of a kernel: one wave64 workgroup per instance, its arrays in dynamic LDS
@@ -983,12 +1021,16 @@ static int episode_running(const mgpt_expert *ex, bool *running)
     return MGPT_OK;
 }
 
-// what the planner does not model: lifelong goal queues and the non-default collision rules
+// what the planner does not model: lifelong goal queues (unless mgpt_expert_set_lifelong is on, and then the env must have them) and
+// the non-default collision rules
 static int expert_check_env(const mgpt_expert *ex)
 {
     int H = 0, W = 0, n_grids = 0, rules = 0, lifelong = 0;
     env_config(ex->env, &H, &W, &n_grids, &rules, &lifelong);
-    MGPT_REQUIRE(!lifelong, MGPT_ERR_UNSUPPORTED, "the PIBT expert does not plan lifelong (on_target = restart) episodes");
+    if (ex->lifelong)
+        MGPT_REQUIRE(lifelong, MGPT_ERR_STATE, "lifelong planning is on (mgpt_expert_set_lifelong): mgpt_env_set_lifelong must come first, the env has no goal queues");
+    else
+        MGPT_REQUIRE(!lifelong, MGPT_ERR_UNSUPPORTED, "the PIBT expert does not plan lifelong (on_target = restart) episodes");
     MGPT_REQUIRE(rules == 0, MGPT_ERR_UNSUPPORTED, "the PIBT expert plans for the default collision rules only (env rule mask %d)", rules);
     return MGPT_OK;
 }
@@ -1052,6 +1094,11 @@ extern "C" int mgpt_expert_reset(mgpt_expert *ex, void *stream)
     MGPT_HIP(hipMemsetAsync(ex->planned, 0, total * 2 * sizeof(int16_t), s));
     MGPT_HIP(hipMemsetAsync(ex->log, 0, total * (size_t)ex->max_steps, s));
     MGPT_HIP(hipMemsetAsync(ex->len, 0, (size_t)ex->n_inst * sizeof(int32_t), s));
+    if (ex->lifelong) {                                      // held = the goals at reset; every instance is live; no arrivals yet
+        MGPT_HIP(hipMemcpyAsync(ex->lf.held, ex->goal, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        MGPT_HIP(hipMemsetAsync(ex->lf.live, 1, (size_t)ex->n_inst, s));
+        MGPT_HIP(hipMemsetAsync(ex->lf.arrivals, 0, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t), s));
+    }
     ex->t = 0;
     ex->have_reset = true;
     ex->solved = false;
@@ -1064,6 +1111,9 @@ extern "C" int mgpt_expert_set_search(mgpt_expert *ex, int max_iters, int iters_
     MGPT_REQUIRE(max_iters >= 1 && max_iters <= (1 << 24), MGPT_ERR_ARG, "max_iters=%d: 1 .. 2^24", max_iters);
     MGPT_REQUIRE(iters_per_launch >= 0, MGPT_ERR_ARG, "iters_per_launch=%d: 0 (the default) or a positive count", iters_per_launch);
     MGPT_REQUIRE(hash_bits >= 0 && hash_bits <= 63, MGPT_ERR_ARG, "hash_bits=%d: 0 (the table's own size) .. 63", hash_bits);
+    MGPT_REQUIRE(!ex->lifelong, MGPT_ERR_UNSUPPORTED,
+                 "mgpt_expert_set_search with lifelong planning on (mgpt_expert_set_lifelong): the search looks for a joint goal configuration, "
+                 "which a lifelong episode does not have");
     MGPT_REQUIRE(lds_bytes(ex->n_agents, ex->swap, true) <= 64 * 1024, MGPT_ERR_UNSUPPORTED,
                  "n_agents=%d: the search's node does not fit 64 KB of LDS", ex->n_agents);
     search_free(ex);
@@ -1124,6 +1174,51 @@ extern "C" int mgpt_expert_set_swap(mgpt_expert *ex, int on)
         }
     }
     ex->swap = on != 0;
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_expert_set_lifelong(mgpt_expert *ex, int on)
+{
+    MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(on == 0 || on == 1, MGPT_ERR_ARG, "on=%d: 0 or 1", on);
+    bool running = false;
+    const int rc = episode_running(ex, &running);
+    if (rc != MGPT_OK) return rc;
+    MGPT_REQUIRE(!running, MGPT_ERR_STATE, "mgpt_expert_set_lifelong in the middle of an episode (before mgpt_expert_reset or between episodes only)");
+    if (on == (ex->lifelong ? 1 : 0)) return MGPT_OK;
+    if (!on) {
+        ex->lifelong_mem.release();
+        ex->lf = mgpt_expert::Lifelong();
+        ex->lifelong = false;
+        ex->have_reset = false;                              // what the last reset prepared was a lifelong episode's state
+        return MGPT_OK;
+    }
+    MGPT_REQUIRE(!ex->search, MGPT_ERR_UNSUPPORTED,
+                 "mgpt_expert_set_lifelong with the search on (mgpt_expert_set_search, and mgpt_expert_set_refine with it): they look for a joint "
+                 "goal configuration, which a lifelong episode does not have");
+    DeviceArena mem;
+    mgpt_expert::Lifelong lf;
+    hipError_t e = mem.alloc(&lf.held, (size_t)ex->n_inst * ex->n_agents * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(&lf.live, (size_t)ex->n_inst);
+    if (e == hipSuccess) e = mem.alloc(&lf.arrivals, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("device allocation failed in mgpt_expert_set_lifelong (%d instances x %d agents): %s", ex->n_inst, ex->n_agents, hipGetErrorString(e));
+        return MGPT_ERR_HIP;
+    }
+    ex->lf = lf;
+    ex->lifelong_mem = std::move(mem);
+    ex->lifelong = true;
+    ex->have_reset = false;                                  // held / live / arrivals are prepared by the next reset
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_expert_copy_arrivals(mgpt_expert *ex, int16_t *d_arrivals_out, void *stream)
+{
+    MGPT_REQUIRE(ex && d_arrivals_out, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(ex->lifelong && ex->have_reset, MGPT_ERR_STATE, "mgpt_expert_set_lifelong and mgpt_expert_reset must precede mgpt_expert_copy_arrivals");
+    MGPT_HIP(hipMemcpyAsync(d_arrivals_out, ex->lf.arrivals, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t), hipMemcpyDeviceToDevice,
+                            (hipStream_t)stream));
     return MGPT_OK;
 }
 
@@ -1311,6 +1406,16 @@ extern "C" int mgpt_expert_step(mgpt_expert *ex, int32_t *d_actions, void *strea
         MGPT_LAUNCH_CHECK();
     }
     if ((rc = mgpt_env_step(ex->env, d_actions, s)) != MGPT_OK) return rc;
+    if (ex->lifelong) {                                      // the fields of the agents whose goal changed, then since and the arrivals
+        if ((rc = mgpt_tokenizer_update_agents(ex->tok, ex->pos, ex->goal, d_actions, 1, s)) != MGPT_OK) return rc;
+        ProfScope ps(P_EXPERT_LIFELONG_POST, s);
+        hipLaunchKernelGGL(pibt_lifelong_post_kernel, dim3(ex->n_inst), dim3(64), 0, s, reinterpret_cast<const uint32_t *>(ex->pos),
+                           reinterpret_cast<const uint32_t *>(ex->goal), ex->done, ex->since, ex->lf.held, ex->lf.live, ex->lf.arrivals,
+                           ex->n_agents, ex->max_steps, (int64_t)ex->t);
+        MGPT_LAUNCH_CHECK();
+        ex->t++;
+        return MGPT_OK;
+    }
     const int total = ex->n_inst * ex->n_agents;
     hipLaunchKernelGGL(pibt_since_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, ex->pos, ex->goal, ex->done, ex->since, ex->n_inst, ex->n_agents);
     MGPT_LAUNCH_CHECK();

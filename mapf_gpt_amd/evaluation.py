@@ -87,6 +87,20 @@ def common_frame(parsed, r=_maps.OBS_RADIUS):
     return out
 
 
+def lifelong_cells(frame):
+    """The cells a lifelong queue draws from: those of the largest free component of frame = (grid, start_ok, goal_ok) that may be goals."""
+    g, _, g_ok = frame
+    return np.argwhere(_maps.largest_component(g == 0) & g_ok)
+
+
+def lifelong_queue(frame, seed, n_agents, length=LIFELONG_QUEUE, cells=None):
+    """The seeded queue of further goals of one on_target="restart" run: int16 [n_agents, length, 2] of lifelong_cells(frame) (`cells`:
+    that array, where the caller seeds many runs on one frame)."""
+    cells = lifelong_cells(frame) if cells is None else cells
+    rng = np.random.Generator(np.random.PCG64([int(seed), 0x4C4C]))
+    return cells[rng.integers(0, len(cells), (n_agents, length))].astype(np.int16)
+
+
 def group_runs(runs):
     """Runs that can share one batch: same num_agents, max_episode_steps and on_target."""
     groups = OrderedDict()
@@ -189,18 +203,20 @@ def _build_algorithm(algo_cfg, max_rows):
 
 class PIBTConfig:
     """Config of the `name: PIBT` algorithm (the device-resident expert, mapf_gpt_amd/expert.py): name, seed, device, swap (the
-    corridor swap rule of DESIGN.md section 22, off by default); unknown keys raise, as for the MAPF-GPT config."""
+    corridor swap rule of DESIGN.md section 22, off by default), lifelong (plan the on_target: restart groups, DESIGN.md section 30, off
+    by default); unknown keys raise, as for the MAPF-GPT config."""
 
-    def __init__(self, name="PIBT", seed=0, device="cuda", swap=False):
-        self.name, self.seed, self.device, self.swap = name, int(seed or 0), device, bool(swap)
+    def __init__(self, name="PIBT", seed=0, device="cuda", swap=False, lifelong=False):
+        self.name, self.seed, self.device, self.swap, self.lifelong = name, int(seed or 0), device, bool(swap), bool(lifelong)
 
 
 class LaCAMConfig(PIBTConfig):
     """Config of the `name: LaCAM` algorithm: the same expert with a LaCAM search in front of every episode (DESIGN.md section 21);
-    name, seed, device, max_iters, swap, refine_rounds and refine_horizon (the refinement pass of section 26, off by default)."""
+    name, seed, device, max_iters, swap, refine_rounds and refine_horizon (the refinement pass of section 26, off by default).
+    `lifelong` is read and changes nothing: the search does not run on_target: restart groups."""
 
-    def __init__(self, name="LaCAM", seed=0, device="cuda", max_iters=4096, swap=False, refine_rounds=0, refine_horizon=None):
-        super().__init__(name, seed, device, swap)
+    def __init__(self, name="LaCAM", seed=0, device="cuda", max_iters=4096, swap=False, refine_rounds=0, refine_horizon=None, lifelong=False):
+        super().__init__(name, seed, device, swap, lifelong)
         self.max_iters = int(max_iters)
         self.refine_rounds, self.refine_horizon = int(refine_rounds or 0), (int(refine_horizon) if refine_horizon else None)
 
@@ -210,15 +226,17 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
     """Run `evaluation_config` (dict in the reference's YAML schema).  Returns the list of result records (on every
     rank); writes `<eval_dir>/<algorithm>.json` and prints the tabular views on rank 0.
     `trace(kind, payload)` (tests): called with ("reset", {algorithm, runs, grids, pos, goal, max_steps}) for every batch
-    this rank runs and with ("step", int32 actions [instances, agents]) after every step -- the device's sampled actions,
-    from which an episode can be replayed on the host.
+    this rank runs (plus on_target and goal_queue: the lifelong queues, else None) and with ("step", int32 actions [instances, agents])
+    after every step -- the device's sampled actions, from which an episode can be replayed on the host.
     retire_done: BatchedRunner's retire mode -- finished episodes leave the policy's batch and a batch ends when none is live (the
     reference's run_episode leaves at all(terminated) or all(truncated), create_env.py:15-18); same records, less work.
     An algorithm whose `name` is PIBT runs the device-resident expert (BatchedExpert) instead of a policy: same grouping, frames,
     placement, sharding and metrics gather.  log_actions: the role of the reference's create_logging_env (create_env.py:8-33) -- the
     PIBT records also carry `made_actions` (per agent, cut to the episode's length) and `init_positions` (padded coordinates), the
-    expert log that dataset_build / dataset_tokenizer consume; one rank only.  An algorithm whose `name` is LaCAM is the same expert
-    with search="lacam"; search_status (a dict) then receives the count of this rank's instances per (final) search status, and with
+    expert log that dataset_build / dataset_tokenizer consume; one rank only.  A PIBT entry with `lifelong: true` also runs the
+    on_target="restart" groups (BatchedExpert(lifelong=True) on the seeded queue the policy branch gets; throughput in the ISR column as
+    for a policy; with log_actions the records also carry `global_lifelong_targets_xy`); without it, and for LaCAM, such a group raises.
+    An algorithm whose `name` is LaCAM is the same expert with search="lacam"; search_status (a dict) then receives the count of this rank's instances per (final) search status, and with
     `refine_rounds` in the entry refine_stats (a dict) receives `refined` (instances whose length or sum of costs fell), `rescued` (first
     status 4, final status 1) and `soc_before` / `soc_after` summed over the refined instances."""
     import torch
@@ -243,8 +261,12 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
         for (n_agents, max_steps, on_target), idxs in groups.items():
             if on_target not in ("nothing", "restart"):
                 raise NotImplementedError(f"on_target={on_target!r}: 'nothing' and 'restart' (lifelong) are built")
-            if is_pibt and on_target == "restart":
-                raise NotImplementedError("the PIBT expert does not plan lifelong (on_target='restart') episodes")
+            if is_pibt and on_target == "restart" and isinstance(cfg, LaCAMConfig):
+                raise NotImplementedError("the LaCAM search does not plan lifelong (on_target='restart') episodes: it looks for a joint "
+                                          "goal configuration (a PIBT entry with lifelong: true does)")
+            if is_pibt and on_target == "restart" and not cfg.lifelong:
+                raise NotImplementedError("the PIBT expert does not plan lifelong (on_target='restart') episodes unless its entry says "
+                                          "lifelong: true")
             parsed = [registry.get(runs[i][0]["map_name"]) for i in idxs]
             frames = dict(zip(idxs, common_frame(parsed)))
             per_batch = max(1, max_rows_per_batch // n_agents)
@@ -269,7 +291,7 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                             search = dict(search="lacam", max_iters=cfg.max_iters, refine_rounds=cfg.refine_rounds,
                                           refine_horizon=cfg.refine_horizon)
                         run = BatchedExpert(grids, len(mine), n_agents, max_steps, seed=cfg.seed, device=cfg.device, inst_offset=lo,
-                                            swap=cfg.swap, **search)
+                                            swap=cfg.swap, lifelong=on_target == "restart", **search)
                     else:
                         run = BatchedRunner(grids, len(mine), n_agents, algo.net, max_episode_steps=max_steps,
                                             seed=int(cfg.seed or 0), do_sample=True, precision=cfg.precision, device=cfg.device,
@@ -278,13 +300,10 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                     if on_target == "restart":          # lifelong: a seeded queue of further goals per agent (wraps)
                         queue = np.empty((len(mine), n_agents, LIFELONG_QUEUE, 2), np.int16)
                         for k, i in enumerate(mine):
-                            g, s_ok, g_ok = frames[i]
-                            cells = np.argwhere(_maps.largest_component(g == 0) & g_ok)
-                            rng = np.random.Generator(np.random.PCG64([int(runs[i][0].get("seed", 0)), 0x4C4C]))
-                            queue[k] = cells[rng.integers(0, len(cells), (n_agents, LIFELONG_QUEUE))]
+                            queue[k] = lifelong_queue(frames[i], runs[i][0].get("seed", 0), n_agents)
                         queue = torch.from_numpy(queue)
                     if is_pibt:
-                        run.reset(torch.from_numpy(pos), torch.from_numpy(goal))
+                        run.reset(torch.from_numpy(pos), torch.from_numpy(goal), goal_queue=queue)
                         if run.search and search_status is not None:
                             for v in run.search_stats()[0].cpu().tolist():
                                 search_status[v] = search_status.get(v, 0) + 1
@@ -301,16 +320,19 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                         run.run(max_steps)
                     else:
                         trace("reset", {"algorithm": algo_name, "runs": list(mine), "grids": grids.copy(), "pos": pos.copy(),
-                                        "goal": goal.copy(), "max_steps": max_steps, "on_target": on_target})
+                                        "goal": goal.copy(), "max_steps": max_steps, "on_target": on_target,
+                                        "goal_queue": None if queue is None else queue.numpy().copy()})
                         for _ in range(max_steps):
                             run.step()
                             trace("step", run.actions.cpu().numpy().copy())
                     local = run.metrics().to(torch.float32)
                     if queue is not None:               # ISR column carries the throughput (arrivals per step) in lifelong runs
-                        local[:, 1] = run.env.goals_reached().sum(1).to(torch.float32) / float(max_steps)
+                        local[:, 1] = run.throughput() if is_pibt else run.env.goals_reached().sum(1).to(torch.float32) / float(max_steps)
                     if is_pibt and log_actions:
                         logged = dict(zip(mine, run.made_actions()))
                         init = dict(zip(mine, pos.tolist()))
+                        if queue is not None:
+                            targets = dict(zip(mine, run.targets()))
                     torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
                 allm = gather_metrics(local, len(chunk), rank, world).cpu().numpy()
@@ -321,6 +343,8 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                     m["runtime"] = dt / max(1, len(chunk))
                     if i in logged:
                         m["made_actions"], m["init_positions"] = logged[i], init[i]
+                        if on_target == "restart":
+                            m["global_lifelong_targets_xy"] = targets[i]
                     results.append({"metrics": m, "env_grid_search": runs[i][1], "algorithm": algo_name})
         del algo
     if rank == 0:

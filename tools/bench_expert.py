@@ -22,6 +22,11 @@
     --swap         the corridor swap rule in the generator, with either --algo; every record then carries
                    "swap": true, and time (pibt) adds the degree map's own time from the timing hooks.
 
+    --lifelong     (--what time, pibt) lifelong episodes: every instance gets the queue evaluation.py seeds for run i,
+                   reset() takes it, and a step is plan + env step + the tokenizer's update (goal check, the BFS of the agents whose
+                   goal changed, next-action bits) + the post-step kernel; the split comes from the timing hooks over run(steps) alone.
+                   Records carry "lifelong": true and throughput (arrivals per step and instance) in the place of solved counts.
+
 Prints one JSON line per shape; --out FILE appends them there too.  Needs the GPU: there is no CPU path.
 """
 import argparse
@@ -160,6 +165,52 @@ def time_search(name, a):
     emit(rec, a.out)
 
 
+def lifelong_queues(grid, g_ok, n_inst, n):
+    from mapf_gpt_amd import evaluation as ev
+    frame = (grid, None, np.ones(grid.shape, bool) if g_ok is None else g_ok)
+    cells = ev.lifelong_cells(frame)
+    return torch.from_numpy(np.stack([ev.lifelong_queue(frame, i, n, cells=cells) for i in range(n_inst)]))
+
+
+def time_lifelong(name, repeats, out):
+    map_name, n_inst, n, steps = TIME_SHAPES[name]
+    if map_name == "maze21":
+        grid, s_ok, g_ok = maps.pad(maps.maze_map(21, 21, 7)), None, None
+    else:
+        grid, s_ok, g_ok = maps.load_named(map_name)
+    pos, goal = make_instances(grid, n_inst, n, 0, s_ok, g_ok)
+    queue = lifelong_queues(grid, g_ok, n_inst, n)
+    ex = BatchedExpert(grid, n_inst, n, steps, seed=7, swap=SWAP, lifelong=True)
+    reset_ms, run_ms = [], []
+    for rep in range(repeats + 1):                   # episode 0 warms up (code objects, allocations)
+        r = timed(lambda: ex.reset(pos, goal, queue))
+        s = timed(lambda: ex.run(steps))
+        if rep:
+            reset_ms.append(r)
+            run_ms.append(s)
+    arrivals = ex.arrivals().sum(1).cpu().numpy()
+    dirty = float(ex.env.goals_reached().sum().item()) / (steps * n_inst * n)
+    ex.reset(pos, goal, queue)                       # the split, over the steps of an episode of its own (the hooks add events to every launch)
+    _lib.prof_enable(True)
+    _lib.prof_reset()
+    ex.run(steps)
+    prof = _lib.prof_read()
+    _lib.prof_enable(False)
+    names = {"plan": ("expert_pibt_plan",), "env": ("env_step",), "tok_update": ("tok_update_agents",), "tok_bfs": ("bfs_distance_field",),
+             "tok_next": ("tok_next_action",), "post": ("expert_lifelong_post",)}
+    k = {key: round(sum(prof.get(x, (0.0, 0))[0] for x in xs) / steps, 4) for key, xs in names.items()}
+    total = max(sum(k.values()), 1e-9)
+    r, s = float(np.median(reset_ms)), float(np.median(run_ms))
+    emit({"tool": "bench_expert", "what": "time", "lifelong": True, "shape": name, "map": map_name, "instances": n_inst, "agents": n,
+          "steps": steps, "queue": int(queue.shape[2]), "ms_per_step": round(s / steps, 4), "ms_run": round(s, 3),
+          "ms_runs": [round(x, 3) for x in run_ms], "ms_reset": round(r, 3), "episodes_per_s": round(n_inst / ((r + s) * 1e-3), 1),
+          "kernel_ms_per_step": k, "tokenizer_update_ms_per_step": round(k["tok_update"] + k["tok_bfs"] + k["tok_next"], 4),
+          "field_rebuild_share_of_kernel_time": round(k["tok_bfs"] / total, 3),
+          "tokenizer_update_share_of_kernel_time": round((k["tok_update"] + k["tok_bfs"] + k["tok_next"]) / total, 3),
+          "dirty_agents_per_step_share": round(dirty, 5), "arrivals_per_step_per_instance": round(float(arrivals.mean()) / steps, 4),
+          "min_arrivals_of_an_instance": int(arrivals.min())}, out)
+
+
 def time_shape(name, repeats, out):
     map_name, n_inst, n, steps = TIME_SHAPES[name]
     if map_name == "maze21":
@@ -240,13 +291,18 @@ def main():
     ap.add_argument("--refine-rounds", type=int, default=0, help="--algo lacam: rounds of the refinement pass (0 = off)")
     ap.add_argument("--refine-horizon", type=int, default=None, help="default: twice the step cap")
     ap.add_argument("--maze-only", action="store_true", help="solve: the three maze shapes only")
+    ap.add_argument("--lifelong", action="store_true", help="time (pibt): lifelong episodes on evaluation.py's seeded queues")
     a = ap.parse_args()
     global SWAP
     SWAP = a.swap
     _lib.require_gpu()
+    if a.lifelong and (a.what != "time" or a.algo != "pibt"):
+        ap.error("--lifelong goes with --what time and --algo pibt")
     if a.what == "time":
         for name in a.shapes or list(TIME_SHAPES):
-            if a.algo == "lacam":
+            if a.lifelong:
+                time_lifelong(name, a.repeats, a.out)
+            elif a.algo == "lacam":
                 time_search(name, a)
             else:
                 time_shape(name, a.repeats, a.out)
