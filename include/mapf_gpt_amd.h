@@ -593,6 +593,42 @@ int mgpt_expert_copy_refine(mgpt_expert *ex, int32_t *d_first_status, int32_t *d
 int mgpt_expert_set_lifelong(mgpt_expert *ex, int on);
 int mgpt_expert_copy_arrivals(mgpt_expert *ex, int16_t *d_arrivals_out, void *stream);
 
+/* Collision shield (section 20's PIBT with the policy's action preferences as every agent's candidate order, "CS-PIBT"
+ * of Veerapaneni et al., ICAPS 2024, restated over this project's own spec).  Off by default: without it every call above behaves as it did.
+ *   set_shield:    on = 1 / 0, any other value is MGPT_ERR_ARG.  on = 1 allocates `first` [n_inst][n_agents] and `overrides` [n_inst]; a reset
+ *                  must follow.  MGPT_ERR_UNSUPPORTED together with set_search, set_swap, set_refine or set_lifelong (in either order), for a
+ *                  lifelong env and for a non-zero env rule mask.  MGPT_ERR_STATE in the middle of an episode (reads the done flags as
+ *                  set_swap does, and a device flag that every shield launch sets and reset clears: steps replayed from a captured
+ *                  graph count).  On a shield-mode context mgpt_expert_step and mgpt_expert_solve return MGPT_ERR_STATE.
+ *   shield:        plans only (timing-hook name expert_shield).  d_actions int32 [n_inst, n_agents] IN: the sampler's action of every row
+ *                  (`first`, kept as a copy), OUT: the planned actions.  d_logits: float32 rows of ld >= 5 values, the first five are read.
+ *                  An agent's candidates are tried with `first` first, the others by descending logit (compared as bit patterns: the fp32
+ *                  pattern mapped monotonically to u32, so -0 < +0 and NaNs have a fixed place), ties by ascending action.  d_live = NULL
+ *                  (d_count NULL too): every instance, the logits of instance i at rows i * n_agents ...  Otherwise block b < *d_count
+ *                  handles instance d_live[b] with its logits at rows b * n_agents ..; d_actions is indexed by the global row in both
+ *                  modes.  Instances that are done, or not in the live list, are left untouched.  overrides[i] grows by the agents of
+ *                  instance i whose planned action is not `first`.
+ *   shield_commit: the since update of section 20; call after mgpt_env_step has executed the planned actions.
+ *   copy_shield:   int32 [n_inst, n_agents] `first` of the last shield call and int32 [n_inst] overrides since reset; either may be NULL.
+ *                  mgpt_expert_copy_plan gives the planned cells.
+ * In the step (mgpt_step above):
+ *   step_set_shield: attaches a shield-mode expert made from the step's own tokenizer and env contexts (MGPT_ERR_ARG otherwise;
+ *                  MGPT_ERR_STATE for an expert that is not in shield mode); NULL detaches.  Allocates a logits buffer [rows][67] for the
+ *                  plain path and drops a captured graph.  A run is then update_agents -> generate_observations -> act (logits kept) ->
+ *                  shield -> env.step -> shield_commit -> the counter bump; d_actions holds the planned actions, which are the made ones,
+ *                  and the next run's update_agents sees them.  The launch sequence stays static: use_graph works as before.  The caller
+ *                  resets the expert (mgpt_expert_reset) whenever it resets the step.
+ *   step_copy_shield_logits: test read-back of the plain path's logits of the last run, float32 [rows][67] (retire mode:
+ *                  mgpt_step_copy_live).  MGPT_ERR_STATE without an attached shield.
+ */
+int mgpt_expert_set_shield(mgpt_expert *ex, int on);
+int mgpt_expert_shield(mgpt_expert *ex, const float *d_logits, int64_t ld, const int32_t *d_live, const int32_t *d_count, int32_t *d_actions,
+                       void *stream);
+int mgpt_expert_shield_commit(mgpt_expert *ex, void *stream);
+int mgpt_expert_copy_shield(mgpt_expert *ex, int32_t *d_first_out, int32_t *d_overrides_out, void *stream);
+int mgpt_step_set_shield(mgpt_step *step, mgpt_expert *ex);
+int mgpt_step_copy_shield_logits(mgpt_step *step, float *d_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Kernel timing hooks (bench.py's live roofline): when enabled, the library brackets every kernel
  * class with hipEvents on the launch stream.  mgpt_prof_read synchronises the device.

@@ -31,6 +31,8 @@ struct TokView {
     bool have_agents;
 };
 void tok_view(const mgpt_tokenizer *t, TokView *out);
+// expert.hip: the contexts an expert was made from and whether it is in shield mode (step.hip: mgpt_step_set_shield)
+void expert_contexts(const mgpt_expert *ex, const mgpt_tokenizer **tok, const mgpt_env **env, bool *shield);
 // gpt.hip: the sampler on the compact logits of the live instances (sample_live_kernel), for step.hip's retire mode
 int sample_actions_live(const float *d_logits, const int32_t *d_live, const int32_t *d_count, int n_agents, int n_inst, int64_t grid_rows,
                         int32_t *d_actions, int do_sample, uint64_t seed, uint64_t step, const uint64_t *d_step, uint64_t row0, hipStream_t s);
@@ -74,6 +76,7 @@ enum ProfId {
     P_EXPERT_CELL_DEGREE,                               // the swap rule's degree map, once per context (expert.hip)
     P_EXPERT_REFINE_PATH, P_EXPERT_REFINE_ROUND, P_EXPERT_REFINE_FINAL,   // the refinement pass of a solve: path, every round, final (expert.hip)
     P_EXPERT_LIFELONG_POST,                             // lifelong episodes: arrivals, since and the arrivals log after the env step (expert.hip)
+    P_EXPERT_SHIELD,                                    // the collision shield's plan kernel (expert.hip)
     P_COUNT
 };
 

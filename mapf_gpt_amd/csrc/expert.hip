@@ -10,6 +10,8 @@
 // refines a found solution by replanning one agent at a time against the others' paths (refine_*_kernel below).
 // Opt-in lifelong episodes keep the plan kernel and change what follows the env step: the borrowed tokenizer
 // rebuilds the fields of the agents whose goal changed and pibt_lifelong_post_kernel stands in pibt_since_kernel's place.
+// An opt-in collision shield for a policy (pibt_shield_kernel) runs the same generator on the policy's action
+// preferences in the place of section 20's keys: the PREF = true instantiation.
 //
 // One step of one instance:
 //   order      agents by (since desc, id asc), since = steps since the agent last stood on its goal;
@@ -65,29 +67,32 @@ struct ExpertLds {
     uint32_t *chain = nullptr;                  // search only: the constraint chain, root end first
     uint16_t *order = nullptr;                  // agent ids by priority
     uint16_t *swp = nullptr;                    // SWAP only: the swap agent of every frame, or NIL
+    uint16_t *pref = nullptr;                   // shield only: every agent's candidates in preference order (pref_word below)
 
     template <class F>
-    __host__ __device__ constexpr void each(bool swap, bool search, F f)
+    __host__ __device__ constexpr void each(bool swap, bool search, bool shield, F f)
     {
         f(stack, true); f(cell, true); f(nxt, true); f(goalc, search); f(snc, search); f(chain, search); f(order, true); f(swp, swap);
+        f(pref, shield);
     }
 };
 
-// per agent: 18 bytes (20 with the swap rule) for the plan kernel, 30 (32) for the search
-constexpr size_t lds_bytes(int n_agents, bool swap, bool search)
+// per agent: 18 bytes (20 with the swap rule) for the plan kernel, 30 (32) for the search, 20 for the shield
+constexpr size_t lds_bytes(int n_agents, bool swap, bool search, bool shield = false)
 {
     size_t bytes = 0;
-    ExpertLds().each(swap, search, [&](auto *&arr, bool present) { bytes += present ? (size_t)n_agents * sizeof(*arr) : 0; });
+    ExpertLds().each(swap, search, shield, [&](auto *&arr, bool present) { bytes += present ? (size_t)n_agents * sizeof(*arr) : 0; });
     return bytes;
 }
 static_assert(lds_bytes(1, false, false) == 18 && lds_bytes(1, true, false) == 20 && lds_bytes(1, false, true) == 30 && lds_bytes(1, true, true) == 32);
+static_assert(lds_bytes(1, false, false, true) == 20 && lds_bytes(3, false, false, true) == 60);
 
 // An array the kernel does not have gets the address of the next one and is never used.  The plan kernel has no snc of its own: it
 // ranks the since values in the stack's place, which is dead until the first frame is pushed after the rank's barrier.
-__device__ __forceinline__ ExpertLds lds_carve(char *smem, int n_agents, bool swap, bool search)
+__device__ __forceinline__ ExpertLds lds_carve(char *smem, int n_agents, bool swap, bool search, bool shield = false)
 {
     ExpertLds L;
-    L.each(swap, search, [&](auto *&arr, bool present) {
+    L.each(swap, search, shield, [&](auto *&arr, bool present) {
         arr = reinterpret_cast<decltype(+arr)>(smem);
         if (present) smem += (size_t)n_agents * sizeof(*arr);
     });
@@ -235,13 +240,45 @@ __device__ __forceinline__ void swap_pull(const GenView &G, unsigned j, int ca)
     G.next_occ[ca] = (uint16_t)j;
 }
 
+// ---- the shield's preference word: an agent's candidates in preference order, 3 bits each from bit 0; a slot
+// beyond the last candidate holds 7, so 16 bits carry the count too (bit 15 is 0, which leaves the frame word's count field clear)
+__device__ __forceinline__ unsigned pref_count(unsigned w)
+{
+    const unsigned used = ~w & 0x7FFFu;                                   // an action is 0..4: its slot has a clear bit, an empty slot has none
+    return used ? (unsigned)(31 - __clz((int)used)) / 3u + 1u : 0u;
+}
+
+// the monotone map of an fp32 bit pattern to u32: a total order on bit patterns, no floating-point arithmetic
+__device__ __forceinline__ unsigned pref_key(unsigned bits) { return (bits & 0x80000000u) ? ~bits : bits ^ 0x80000000u; }
+
+// valid: bit k set = action k is a candidate; first: the sampler's action, tried first if it is one; the others by descending key, ties by
+// ascending k
+__device__ __forceinline__ unsigned pref_word(unsigned valid, int first, const unsigned (&key)[5])
+{
+    unsigned w = 0x7FFFu;
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+        if (!((valid >> k) & 1u)) continue;
+        int rank = 0;
+#pragma unroll
+        for (int j = 0; j < 5; j++) {
+            if (j == k || !((valid >> j) & 1u)) continue;
+            const bool before = j == first || (k != first && (key[j] > key[k] || (key[j] == key[k] && j < k)));
+            rank += before ? 1 : 0;
+        }
+        w = (w & ~(7u << (3 * rank))) | ((unsigned)k << (3 * rank));
+    }
+    return w;
+}
+
 // ---- the generator: PIBT for every undecided agent in priority order, on the state in LDS and the occupancy workspace ----------------
 // The one copy that both kernels call.  It differs between them in the step index of the candidates' random bits (`step`: the
 // episode's step, or the node's depth), the global row of agent 0 (`row0`) and FIXED: the search, whose constraints have decided
 // some agents with kFixed set, fails (returns false) when an agent with no candidate left finds its own cell held by such an agent.
 // FIXED = false never fails.  Every lane runs this identically (uniform branches, identical addresses and values), so it needs no
-// barrier; sp < n_agents is checked where a frame is pushed.
-template <bool SWAP, bool FIXED>
+// barrier; sp < n_agents is checked where a frame is pushed.  PREF = true (the collision shield): the candidate
+// order of an agent does not depend on the running step, the caller has left it in L.pref[] and a frame entry is one LDS load.
+template <bool SWAP, bool FIXED, bool PREF = false>
 __device__ __forceinline__ bool pibt_generate(const GenView &G, uint64_t seed, uint64_t step, int64_t row0)
 {
     const int n_agents = G.n_agents, W = G.W, lane = G.lane;
@@ -257,28 +294,33 @@ __device__ __forceinline__ bool pibt_generate(const GenView &G, uint64_t seed, u
         for (;;) {
             if (push_a >= 0) {                                            // enter PIBT(push_a, push_par): form and sort its candidates
                 const int a = push_a, ca = cell[a];
-                const uint64_t z = splitmix_z(seed, step, (uint64_t)(row0 + a));
-                unsigned key = 0xFFFFFFF8u | (unsigned)min(lane, 7);      // dropped candidates sort last (and stay distinct)
-                bool valid = false;
-                int u;
-                if (lane < 5 && neighbour(ca, lane, G.H, W, u)) {
-                    const unsigned d = swap_D(G, (unsigned)a, u);
-                    if (G.grid[u] == 0 && d != kUnreach) {
-                        const unsigned who = occ_now[u];
-                        const unsigned o = (who != kNil && who != (unsigned)a) ? 1u : 0u;
-                        const unsigned rk = (unsigned)(z >> (5 * lane)) & 31u;
-                        key = (((d * 2u + o) * 32u + rk) * 8u) + (unsigned)lane;
-                        valid = true;
+                unsigned packed = 0, ncand;
+                if constexpr (PREF) {                                     // formed by the caller before the serial part
+                    packed = G.L.pref[a];
+                    ncand = pref_count(packed);
+                } else {
+                    const uint64_t z = splitmix_z(seed, step, (uint64_t)(row0 + a));
+                    unsigned key = 0xFFFFFFF8u | (unsigned)min(lane, 7);  // dropped candidates sort last (and stay distinct)
+                    bool valid = false;
+                    int u;
+                    if (lane < 5 && neighbour(ca, lane, G.H, W, u)) {
+                        const unsigned d = swap_D(G, (unsigned)a, u);
+                        if (G.grid[u] == 0 && d != kUnreach) {
+                            const unsigned who = occ_now[u];
+                            const unsigned o = (who != kNil && who != (unsigned)a) ? 1u : 0u;
+                            const unsigned rk = (unsigned)(z >> (5 * lane)) & 31u;
+                            key = (((d * 2u + o) * 32u + rk) * 8u) + (unsigned)lane;
+                            valid = true;
+                        }
                     }
+                    int rank = 0;
+#pragma unroll
+                    for (int j = 0; j < 5; j++) rank += (__shfl(key, j, 64) < key) ? 1 : 0;
+                    const unsigned contrib = valid ? ((unsigned)lane << (3 * rank)) : 0u;
+#pragma unroll
+                    for (int j = 0; j < 5; j++) packed |= __shfl(contrib, j, 64);
+                    ncand = (unsigned)__popcll(__ballot(valid));
                 }
-                int rank = 0;
-#pragma unroll
-                for (int j = 0; j < 5; j++) rank += (__shfl(key, j, 64) < key) ? 1 : 0;
-                const unsigned contrib = valid ? ((unsigned)lane << (3 * rank)) : 0u;
-                unsigned packed = 0;
-#pragma unroll
-                for (int j = 0; j < 5; j++) packed |= __shfl(contrib, j, 64);
-                const unsigned ncand = (unsigned)__popcll(__ballot(valid));
                 if (sp >= n_agents) break;                                // (cannot happen: an agent enters at most once per step)
                 if constexpr (SWAP) {                                     // the swap decision, on the state at this moment
                     const unsigned j = ncand ? swap_agent(G, (unsigned)a, ca, ca + cell_step((int)(packed & 7u), W)) : kNil;
@@ -413,6 +455,81 @@ __global__ void pibt_since_kernel(const int16_t *__restrict__ pos, const int16_t
     if (done[i / n_agents] != 0) return;
     const bool on = pos[2 * i] == goal[2 * i] && pos[2 * i + 1] == goal[2 * i + 1];
     since[i] = on ? 0u : since[i] + 1u;
+}
+
+// ---- the collision shield: section 20's PIBT on the policy's preferences --------------------------------------
+// One wave64 workgroup per instance, as the plan kernel.  An agent's candidate order is a function of its five logits, the sampler's
+// action and the maps, none of which the running step changes, so all preference words are formed before the serial part, one agent
+// per lane in the strided loop that also fills cell / nxt / snc / occ_now: the generator (PREF = true) then loads nothing from HBM for
+// keys and shuffles nothing at a frame entry.  `actions` holds the sampler's actions on entry (copied to `first`) and the planned ones
+// on return; overrides[inst] grows by the agents whose planned action is not the sampler's, summed by shuffles and stored by lane 0.
+// *started = 1 (lane 0 of block 0) tells the host that an episode has begun, also where the launch is replayed from a graph.
+// live != NULL (retire mode): block b handles instance live[b] for b < *count, with its logits at the compact rows b * n_agents ..;
+// actions, pos and every other array are indexed by the global row in both modes.  An instance that is done is left untouched.
+__global__ __launch_bounds__(64) void pibt_shield_kernel(const uint8_t *__restrict__ grids, int n_grids, int n_inst, int n_agents, int H, int W,
+                                                         const uint16_t *__restrict__ dist, const int16_t *__restrict__ pos,
+                                                         const uint8_t *__restrict__ done, const uint32_t *__restrict__ since, uint16_t *occ,
+                                                         const float *__restrict__ logits, int64_t ld, const int32_t *__restrict__ live,
+                                                         const int32_t *__restrict__ count, int32_t *actions, int32_t *__restrict__ first,
+                                                         int16_t *__restrict__ planned, int32_t *__restrict__ overrides,
+                                                         int32_t *__restrict__ started)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const ExpertLds L = lds_carve(smem, n_agents, false, false, true);
+    const int lane = threadIdx.x;
+    int inst = blockIdx.x;
+    if (inst == 0 && lane == 0) *started = 1;                             // the episode has begun: on the device, so that a graph replay says so too
+    if (live != nullptr) {                                                // wave-uniform: beyond the live list, or not an instance
+        if (inst >= *count) return;
+        inst = live[inst];
+    }
+    if (inst < 0 || inst >= n_inst || done[inst] != 0) return;            // wave-uniform: a finished instance is left untouched
+    const int cells = H * W;
+    const size_t g0 = (size_t)inst * n_agents;
+    const float *lrow = logits + (size_t)blockIdx.x * n_agents * (size_t)ld;    // (blockIdx.x == inst without a live list)
+    uint16_t *occ_now = occ + (size_t)inst * 2 * cells, *next_occ = occ_now + cells;
+    const size_t map0 = (size_t)(inst % n_grids) * cells;
+    const GenView G{grids + map0, nullptr, dist + g0 * (size_t)cells, occ_now, next_occ, L, n_agents, H, W, cells, lane};
+    const int *cell = L.cell, *nxt = L.nxt;
+
+    for (int a = lane; a < n_agents; a += 64) {
+        int c = (int)pos[2 * (g0 + a)] * W + (int)pos[2 * (g0 + a) + 1];
+        c = min(max(c, 0), cells - 1);                                    // (env states are inside the frame)
+        L.cell[a] = c;
+        L.nxt[a] = -1;
+        L.snc[a] = since[g0 + a];
+        occ_now[c] = (uint16_t)a;
+        const int f = actions[g0 + a];
+        first[g0 + a] = f;
+        unsigned key[5], valid = 0;
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            key[k] = pref_key(__float_as_uint(lrow[(size_t)a * ld + k]));
+            int u;
+            if (neighbour(c, k, H, W, u) && G.grid[u] == 0 && swap_D(G, (unsigned)a, u) != kUnreach) valid |= 1u << k;
+        }
+        L.pref[a] = (uint16_t)pref_word(valid, f, key);
+    }
+    __syncthreads();
+    rank_by_since(L.snc, L.order, n_agents, lane);
+    __syncthreads();                                                      // order[] complete; snc[] is dead, the stack takes its place
+
+    pibt_generate<false, false, true>(G, 0, 0, 0);
+    __syncthreads();
+
+    int n_over = 0;
+    for (int a = lane; a < n_agents; a += 64) {
+        const int v = nxt[a], u = v & 0xFFFFFF, k = (v >> 24) & 7;
+        const int ur = u / W;
+        n_over += (k != actions[g0 + a]) ? 1 : 0;                         // still the sampler's action
+        actions[g0 + a] = k;
+        planned[2 * (g0 + a)] = (int16_t)ur;
+        planned[2 * (g0 + a) + 1] = (int16_t)(u - ur * W);
+        occ_now[cell[a]] = (uint16_t)kNil;                                // leave the workspace all-NIL for the next step
+        next_occ[u] = (uint16_t)kNil;
+    }
+    for (int off = 32; off > 0; off >>= 1) n_over += __shfl_xor(n_over, off, 64);
+    if (lane == 0) overrides[inst] += n_over;
 }
 
 // ---- lifelong episodes: the post-step kernel, in pibt_since_kernel's place when mgpt_expert_set_lifelong is on ----
@@ -984,7 +1101,14 @@ struct mgpt_expert {
         uint8_t *live = nullptr;                // [n_inst] the instance was not done when the last step began
         int16_t *arrivals = nullptr;            // [n_inst][max_steps] arrivals per step
     } lf;
-    DeviceArena mem, search_mem, deg_mem, refine_mem, lifelong_mem;   // occ .. len; ls; deg; rf; lf
+    // the collision shield (mgpt_expert_set_shield): off (all NULL) by default
+    bool shield = false;
+    struct Shield {                             // buffers, owned by shield_mem
+        int32_t *first = nullptr;               // [n_inst][n_agents] the sampler's actions of the last step
+        int32_t *overrides = nullptr;           // [n_inst] agents whose planned action was not the sampler's, since reset
+        int32_t *started = nullptr;             // [1] 0 at reset, 1 once a shield launch has run (a replayed graph never passes the host)
+    } sh;
+    DeviceArena mem, search_mem, deg_mem, refine_mem, lifelong_mem, shield_mem;   // occ .. len; ls; deg; rf; lf; sh
 };
 
 // launches the SWAP instantiation of a kernel: one wave64 workgroup per instance, its arrays in dynamic LDS
@@ -1013,7 +1137,14 @@ static void search_free(mgpt_expert *ex)
 static int episode_running(const mgpt_expert *ex, bool *running)
 {
     *running = false;
-    if (!ex->have_reset || (ex->t == 0 && !ex->solved)) return MGPT_OK;
+    if (!ex->have_reset) return MGPT_OK;
+    if (ex->shield) {                                        // the host's t does not see the steps of a replayed graph: ask the device
+        int32_t started = 0;
+        MGPT_HIP(hipDeviceSynchronize());
+        MGPT_HIP(hipMemcpy(&started, ex->sh.started, sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (!started) return MGPT_OK;
+    } else if (ex->t == 0 && !ex->solved)
+        return MGPT_OK;
     std::vector<uint8_t> done((size_t)ex->n_inst);
     MGPT_HIP(hipDeviceSynchronize());
     MGPT_HIP(hipMemcpy(done.data(), ex->done, done.size(), hipMemcpyDeviceToHost));
@@ -1094,6 +1225,11 @@ extern "C" int mgpt_expert_reset(mgpt_expert *ex, void *stream)
     MGPT_HIP(hipMemsetAsync(ex->planned, 0, total * 2 * sizeof(int16_t), s));
     MGPT_HIP(hipMemsetAsync(ex->log, 0, total * (size_t)ex->max_steps, s));
     MGPT_HIP(hipMemsetAsync(ex->len, 0, (size_t)ex->n_inst * sizeof(int32_t), s));
+    if (ex->shield) {
+        MGPT_HIP(hipMemsetAsync(ex->sh.first, 0, total * sizeof(int32_t), s));
+        MGPT_HIP(hipMemsetAsync(ex->sh.overrides, 0, (size_t)ex->n_inst * sizeof(int32_t), s));
+        MGPT_HIP(hipMemsetAsync(ex->sh.started, 0, sizeof(int32_t), s));
+    }
     if (ex->lifelong) {                                      // held = the goals at reset; every instance is live; no arrivals yet
         MGPT_HIP(hipMemcpyAsync(ex->lf.held, ex->goal, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
         MGPT_HIP(hipMemsetAsync(ex->lf.live, 1, (size_t)ex->n_inst, s));
@@ -1114,6 +1250,7 @@ extern "C" int mgpt_expert_set_search(mgpt_expert *ex, int max_iters, int iters_
     MGPT_REQUIRE(!ex->lifelong, MGPT_ERR_UNSUPPORTED,
                  "mgpt_expert_set_search with lifelong planning on (mgpt_expert_set_lifelong): the search looks for a joint goal configuration, "
                  "which a lifelong episode does not have");
+    MGPT_REQUIRE(!ex->shield, MGPT_ERR_UNSUPPORTED, "mgpt_expert_set_search in shield mode (mgpt_expert_set_shield): the shield plans single steps only");
     MGPT_REQUIRE(lds_bytes(ex->n_agents, ex->swap, true) <= 64 * 1024, MGPT_ERR_UNSUPPORTED,
                  "n_agents=%d: the search's node does not fit 64 KB of LDS", ex->n_agents);
     search_free(ex);
@@ -1155,6 +1292,7 @@ extern "C" int mgpt_expert_set_swap(mgpt_expert *ex, int on)
     if (rc != MGPT_OK) return rc;
     MGPT_REQUIRE(!running, MGPT_ERR_STATE, "mgpt_expert_set_swap in the middle of an episode (before mgpt_expert_reset or between episodes only)");
     if (on) {
+        MGPT_REQUIRE(!ex->shield, MGPT_ERR_UNSUPPORTED, "mgpt_expert_set_swap in shield mode (mgpt_expert_set_shield): the shield keeps the policy's candidate order");
         MGPT_REQUIRE(lds_bytes(ex->n_agents, true, false) <= 64 * 1024 && (!ex->search || lds_bytes(ex->n_agents, true, true) <= 64 * 1024),
                      MGPT_ERR_UNSUPPORTED, "n_agents=%d: the frames with their swap agents do not fit 64 KB of LDS", ex->n_agents);
         if (!ex->deg) {                                      // built once per context: the grids never change
@@ -1193,6 +1331,7 @@ extern "C" int mgpt_expert_set_lifelong(mgpt_expert *ex, int on)
         ex->have_reset = false;                              // what the last reset prepared was a lifelong episode's state
         return MGPT_OK;
     }
+    MGPT_REQUIRE(!ex->shield, MGPT_ERR_UNSUPPORTED, "mgpt_expert_set_lifelong in shield mode (mgpt_expert_set_shield): the shield does not plan lifelong episodes");
     MGPT_REQUIRE(!ex->search, MGPT_ERR_UNSUPPORTED,
                  "mgpt_expert_set_lifelong with the search on (mgpt_expert_set_search, and mgpt_expert_set_refine with it): they look for a joint "
                  "goal configuration, which a lifelong episode does not have");
@@ -1258,6 +1397,7 @@ static int refine_run(mgpt_expert *ex, hipStream_t s)
 extern "C" int mgpt_expert_solve(mgpt_expert *ex, void *stream)
 {
     MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(!ex->shield, MGPT_ERR_STATE, "mgpt_expert_solve on a shield-mode context (mgpt_expert_set_shield): it plans through mgpt_expert_shield only");
     MGPT_REQUIRE(ex->search, MGPT_ERR_STATE, "mgpt_expert_set_search must precede mgpt_expert_solve");
     MGPT_REQUIRE(ex->have_reset && ex->t == 0, MGPT_ERR_STATE, "mgpt_expert_solve runs right after mgpt_expert_reset (the search starts from the env's positions at reset)");
     const int rc = expert_check_env(ex);
@@ -1382,6 +1522,7 @@ extern "C" int mgpt_expert_copy_solution(mgpt_expert *ex, int8_t *d_solution_out
 extern "C" int mgpt_expert_step(mgpt_expert *ex, int32_t *d_actions, void *stream)
 {
     MGPT_REQUIRE(ex && d_actions, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(!ex->shield, MGPT_ERR_STATE, "mgpt_expert_step on a shield-mode context (mgpt_expert_set_shield): it plans through mgpt_expert_shield only");
     MGPT_REQUIRE(ex->have_reset, MGPT_ERR_STATE, "mgpt_expert_reset must precede mgpt_expert_step");
     int rc = expert_check_env(ex);
     if (rc != MGPT_OK) return rc;
@@ -1439,4 +1580,92 @@ extern "C" int mgpt_expert_copy_log(mgpt_expert *ex, int8_t *d_log_out, int32_t 
         MGPT_HIP(hipMemcpyAsync(d_log_out, ex->log, (size_t)ex->n_inst * ex->n_agents * (size_t)ex->max_steps, hipMemcpyDeviceToDevice, s));
     if (d_len_out) MGPT_HIP(hipMemcpyAsync(d_len_out, ex->len, (size_t)ex->n_inst * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     return MGPT_OK;
+}
+
+// ---- the collision shield --------------------------------------------------------------------------------------
+extern "C" int mgpt_expert_set_shield(mgpt_expert *ex, int on)
+{
+    MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(on == 0 || on == 1, MGPT_ERR_ARG, "on=%d: 0 or 1", on);
+    bool running = false;
+    int rc = episode_running(ex, &running);
+    if (rc != MGPT_OK) return rc;
+    MGPT_REQUIRE(!running, MGPT_ERR_STATE, "mgpt_expert_set_shield in the middle of an episode (before mgpt_expert_reset or between episodes only)");
+    if (on == (ex->shield ? 1 : 0)) return MGPT_OK;
+    if (!on) {
+        ex->shield_mem.release();
+        ex->sh = mgpt_expert::Shield();
+        ex->shield = false;
+        ex->have_reset = false;
+        return MGPT_OK;
+    }
+    MGPT_REQUIRE(!ex->search && !ex->swap && ex->rf.max_rounds == 0 && !ex->lifelong, MGPT_ERR_UNSUPPORTED,
+                 "mgpt_expert_set_shield together with the search, the swap rule, the refinement pass or lifelong planning: the shield runs "
+                 "section 20's PIBT on the policy's candidate order, one step at a time");
+    if ((rc = expert_check_env(ex)) != MGPT_OK) return rc;   // a lifelong env, a non-zero rule mask
+    MGPT_REQUIRE(lds_bytes(ex->n_agents, false, false, true) <= 64 * 1024, MGPT_ERR_UNSUPPORTED,
+                 "n_agents=%d: the frames with the preference words do not fit 64 KB of LDS", ex->n_agents);
+    DeviceArena mem;
+    mgpt_expert::Shield sh;
+    hipError_t e = mem.alloc(&sh.first, (size_t)ex->n_inst * ex->n_agents * sizeof(int32_t));
+    if (e == hipSuccess) e = mem.alloc(&sh.overrides, (size_t)ex->n_inst * sizeof(int32_t));
+    if (e == hipSuccess) e = mem.alloc(&sh.started, sizeof(int32_t));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("device allocation failed in mgpt_expert_set_shield (%d instances x %d agents): %s", ex->n_inst, ex->n_agents, hipGetErrorString(e));
+        return MGPT_ERR_HIP;
+    }
+    ex->sh = sh;
+    ex->shield_mem = std::move(mem);
+    ex->shield = true;
+    ex->have_reset = false;                                  // first / overrides are prepared by the next reset
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_expert_shield(mgpt_expert *ex, const float *d_logits, int64_t ld, const int32_t *d_live, const int32_t *d_count,
+                                  int32_t *d_actions, void *stream)
+{
+    MGPT_REQUIRE(ex && d_logits && d_actions, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(ld >= MGPT_NUM_ACTIONS, MGPT_ERR_ARG, "ld=%lld: a logits row holds at least %d values", (long long)ld, MGPT_NUM_ACTIONS);
+    MGPT_REQUIRE((d_live == nullptr) == (d_count == nullptr), MGPT_ERR_ARG, "d_live and d_count come together (both NULL: all instances)");
+    MGPT_REQUIRE(ex->shield, MGPT_ERR_STATE, "mgpt_expert_set_shield(ex, 1) must precede mgpt_expert_shield");
+    MGPT_REQUIRE(ex->have_reset, MGPT_ERR_STATE, "mgpt_expert_reset must precede mgpt_expert_shield");
+    const int rc = expert_check_env(ex);
+    if (rc != MGPT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(P_EXPERT_SHIELD, s);
+    hipLaunchKernelGGL(pibt_shield_kernel, dim3(ex->n_inst), dim3(64), lds_bytes(ex->n_agents, false, false, true), s, ex->grids, ex->n_grids,
+                       ex->n_inst, ex->n_agents, ex->H, ex->W, ex->dist, ex->pos, ex->done, ex->since, ex->occ, d_logits, ld, d_live, d_count,
+                       d_actions, ex->sh.first, ex->planned, ex->sh.overrides, ex->sh.started);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_expert_shield_commit(mgpt_expert *ex, void *stream)
+{
+    MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(ex->shield && ex->have_reset, MGPT_ERR_STATE, "mgpt_expert_set_shield and mgpt_expert_reset must precede mgpt_expert_shield_commit");
+    const int total = ex->n_inst * ex->n_agents;
+    hipLaunchKernelGGL(pibt_since_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, ex->pos, ex->goal, ex->done, ex->since, ex->n_inst,
+                       ex->n_agents);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;                                          // (no host step counter: a captured step is replayed without this call)
+}
+
+extern "C" int mgpt_expert_copy_shield(mgpt_expert *ex, int32_t *d_first_out, int32_t *d_overrides_out, void *stream)
+{
+    MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(ex->shield && ex->have_reset, MGPT_ERR_STATE, "mgpt_expert_set_shield and mgpt_expert_reset must precede mgpt_expert_copy_shield");
+    hipStream_t s = (hipStream_t)stream;
+    if (d_first_out)
+        MGPT_HIP(hipMemcpyAsync(d_first_out, ex->sh.first, (size_t)ex->n_inst * ex->n_agents * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (d_overrides_out)
+        MGPT_HIP(hipMemcpyAsync(d_overrides_out, ex->sh.overrides, (size_t)ex->n_inst * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return MGPT_OK;
+}
+
+// what step.hip asks of the expert it is handed (mgpt_step_set_shield)
+void mgpt::expert_contexts(const mgpt_expert *ex, const mgpt_tokenizer **tok, const mgpt_env **env, bool *shield)
+{
+    *tok = ex->tok; *env = ex->env; *shield = ex->shield;
 }

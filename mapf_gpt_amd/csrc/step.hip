@@ -58,7 +58,10 @@ struct mgpt_step {
         uint8_t *d_ctokens = nullptr;           // [rows][256] token rows of the live instances, compact
         float *d_clogits = nullptr;             // [rows][67] their logits
     } rt;
-    DeviceArena mem, retire_mem;                // d_step; rt
+    // collision shield (mgpt_step_set_shield): NULL when off
+    mgpt_expert *shield = nullptr;              // a shield-mode expert over tok and env, owned by the caller
+    float *d_logits = nullptr;                  // [rows][67] the plain path's logits of the last step (retire mode has rt.d_clogits)
+    DeviceArena mem, retire_mem, shield_mem;    // d_step; rt; d_logits
 };
 
 namespace {
@@ -159,10 +162,18 @@ int step_body(mgpt_step *st, uint8_t *d_tokens, int32_t *d_actions, int gmc, hip
     if ((rc = mgpt_tokenizer_generate_observations(st->tok, d_tokens, s)) != MGPT_OK) return rc;
     if (st->retire) {
         if ((rc = act_live(st, d_tokens, d_actions, s)) != MGPT_OK) return rc;
-    } else if ((rc = mgpt_gpt_act_dev(st->gpt, d_tokens, st->rows, d_actions, nullptr, st->do_sample, st->seed, st->d_step, st->row0, st->precision,
+    } else if ((rc = mgpt_gpt_act_dev(st->gpt, d_tokens, st->rows, d_actions, st->d_logits, st->do_sample, st->seed, st->d_step, st->row0, st->precision,
                                s)) != MGPT_OK)
         return rc;
+    if (st->shield) {                                           // the sampled actions become every agent's first candidate of a PIBT step
+        if (st->retire) {
+            if (st->n_live > 0 && (rc = mgpt_expert_shield(st->shield, st->rt.d_clogits, MGPT_VOCAB, st->rt.d_live, st->rt.d_count, d_actions, s)) != MGPT_OK)
+                return rc;
+        } else if ((rc = mgpt_expert_shield(st->shield, st->d_logits, MGPT_VOCAB, nullptr, nullptr, d_actions, s)) != MGPT_OK)
+            return rc;
+    }
     if ((rc = mgpt_env_step(st->env, d_actions, s)) != MGPT_OK) return rc;
+    if (st->shield && (rc = mgpt_expert_shield_commit(st->shield, s)) != MGPT_OK) return rc;
     hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, s, st->d_step);
     MGPT_LAUNCH_CHECK();
     return MGPT_OK;
@@ -260,6 +271,43 @@ extern "C" int mgpt_step_set_retire(mgpt_step *st, int enable)
     }
     st->retire = true;
     st->n_live = st->n_inst;
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_step_set_shield(mgpt_step *st, mgpt_expert *ex)
+{
+    MGPT_REQUIRE(st, MGPT_ERR_ARG, "NULL argument");
+    drop_graph(st);
+    if (!ex) {
+        st->shield = nullptr;
+        st->shield_mem.release();                 // (freeing waits for the work that still reads the buffer)
+        st->d_logits = nullptr;
+        return MGPT_OK;
+    }
+    const mgpt_tokenizer *tok = nullptr;
+    const mgpt_env *env = nullptr;
+    bool on = false;
+    expert_contexts(ex, &tok, &env, &on);
+    MGPT_REQUIRE(tok == st->tok && env == st->env, MGPT_ERR_ARG, "the expert was made from another tokenizer or env context than this step");
+    MGPT_REQUIRE(on, MGPT_ERR_STATE, "mgpt_expert_set_shield(ex, 1) must precede mgpt_step_set_shield");
+    if (!st->d_logits) {
+        const hipError_t e = st->shield_mem.alloc(&st->d_logits, (size_t)st->rows * MGPT_VOCAB * sizeof(float));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("allocation failed in mgpt_step_set_shield: %s", hipGetErrorString(e));
+            st->d_logits = nullptr;
+            return MGPT_ERR_HIP;
+        }
+    }
+    st->shield = ex;
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_step_copy_shield_logits(mgpt_step *st, float *d_out, void *stream)
+{
+    MGPT_REQUIRE(st && d_out, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(st->shield && st->d_logits, MGPT_ERR_STATE, "no shield is attached (mgpt_step_set_shield)");
+    MGPT_HIP(hipMemcpyAsync(d_out, st->d_logits, (size_t)st->rows * MGPT_VOCAB * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MGPT_OK;
 }
 

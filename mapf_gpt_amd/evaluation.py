@@ -238,7 +238,10 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
     for a policy; with log_actions the records also carry `global_lifelong_targets_xy`); without it, and for LaCAM, such a group raises.
     An algorithm whose `name` is LaCAM is the same expert with search="lacam"; search_status (a dict) then receives the count of this rank's instances per (final) search status, and with
     `refine_rounds` in the entry refine_stats (a dict) receives `refined` (instances whose length or sum of costs fell), `rescued` (first
-    status 4, final status 1) and `soc_before` / `soc_after` summed over the refined instances."""
+    status 4, final status 1) and `soc_before` / `soc_after` summed over the refined instances.
+    A MAPF-GPT entry with `shield: pibt` runs its policy behind the collision shield (BatchedRunner(shield="pibt"), DESIGN.md section 31);
+    its records also carry `shield_overrides`: the agents whose planned action was not the sampled one, summed over the episode and
+    divided by ep_length x num_agents.  Such an entry raises on an on_target="restart" group, as log_actions does."""
     import torch
     from .runner import BatchedRunner, gather_metrics, shard_range
 
@@ -267,6 +270,9 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
             if is_pibt and on_target == "restart" and not cfg.lifelong:
                 raise NotImplementedError("the PIBT expert does not plan lifelong (on_target='restart') episodes unless its entry says "
                                           "lifelong: true")
+            shield = None if is_pibt else getattr(cfg, "shield", None)
+            if shield and on_target == "restart":
+                raise NotImplementedError("shield: pibt does not plan lifelong (on_target='restart') episodes")
             parsed = [registry.get(runs[i][0]["map_name"]) for i in idxs]
             frames = dict(zip(idxs, common_frame(parsed)))
             per_batch = max(1, max_rows_per_batch // n_agents)
@@ -274,7 +280,7 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                 chunk = idxs[b0:b0 + per_batch]
                 lo, hi = shard_range(len(chunk), rank, world)
                 mine = chunk[lo:hi]
-                local = torch.zeros((0, len(METRIC_KEYS)), dtype=torch.float32, device=cfg.device)
+                local = torch.zeros((0, len(METRIC_KEYS) + (1 if shield else 0)), dtype=torch.float32, device=cfg.device)
                 t0 = time.perf_counter()
                 logged = {}
                 if mine:
@@ -295,7 +301,7 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                     else:
                         run = BatchedRunner(grids, len(mine), n_agents, algo.net, max_episode_steps=max_steps,
                                             seed=int(cfg.seed or 0), do_sample=True, precision=cfg.precision, device=cfg.device,
-                                            row_offset=lo * n_agents, retire_done=bool(retire_done))
+                                            row_offset=lo * n_agents, retire_done=bool(retire_done), **({"shield": shield} if shield else {}))
                     queue = None
                     if on_target == "restart":          # lifelong: a seeded queue of further goals per agent (wraps)
                         queue = np.empty((len(mine), n_agents, LIFELONG_QUEUE, 2), np.int16)
@@ -328,6 +334,8 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                     local = run.metrics().to(torch.float32)
                     if queue is not None:               # ISR column carries the throughput (arrivals per step) in lifelong runs
                         local[:, 1] = run.throughput() if is_pibt else run.env.goals_reached().sum(1).to(torch.float32) / float(max_steps)
+                    if shield:                          # one more column for the gather: the episode's override count
+                        local = torch.cat([local, run.shield_overrides().to(torch.float32)[:, None]], dim=1)
                     if is_pibt and log_actions:
                         logged = dict(zip(mine, run.made_actions()))
                         init = dict(zip(mine, pos.tolist()))
@@ -340,6 +348,8 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                     m = {key: float(allm[k, j]) for j, key in enumerate(METRIC_KEYS)}
                     if on_target == "restart":
                         m = {"avg_throughput": m["ISR"], "ep_length": m["ep_length"]}
+                    if shield:
+                        m["shield_overrides"] = float(allm[k, len(METRIC_KEYS)]) / max(1.0, m["ep_length"] * n_agents)
                     m["runtime"] = dt / max(1, len(chunk))
                     if i in logged:
                         m["made_actions"], m["init_positions"] = logged[i], init[i]

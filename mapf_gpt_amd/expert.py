@@ -34,6 +34,12 @@ of its queue (the queue wraps) and its distance field is rebuilt inside the same
 count of arrivals per instance and step, targets() every agent's list of goals as the dataset tokenizer walks it, and records() carries
 it as `global_lifelong_targets_xy` with `avg_throughput` in the place of CSR .. makespan.  Not together with search=.  Off by default.
 
+`shield=True` makes the context a collision shield for a policy instead of an expert of its own: PIBT with the
+policy's action preferences as every agent's candidate order.  `env=` / `tok=` then name the BatchedEnv / BatchedTokenizer it plans on
+(BatchedRunner(shield="pibt") passes its own); shield_step(logits, first) is plan -> env step -> since update, shield_overrides() the
+count of agents per instance whose planned action was not the policy's.  step() and run() are refused.  Not together with search=,
+swap=, refine_rounds= or lifelong=.  Off by default.
+
 The config is an evaluation YAML (eval_configs/<folder>/<folder>.yaml): its `environment:` block is run; its `algorithms:` block is
 replaced by one PIBT entry (seed from --seed).  DIR/PIBT.json is what `dataset_build.split_by_map` and `dataset_build --logs` take
 where the reference has LaCAM.json.  Prints one JSON line: episodes, solved, rows, seconds (with --algo lacam also `status`: the
@@ -61,16 +67,21 @@ class BatchedExpert:
     """Same shape as BatchedRunner: owns a BatchedEnv and a BatchedTokenizer (used for its BFS distance fields only)."""
 
     def __init__(self, grids, n_inst, n_agents, max_episode_steps, seed=0, device="cuda", inst_offset=0, search=None, max_iters=4096,
-                 iters_per_launch=None, hash_bits=0, swap=False, refine_rounds=0, refine_horizon=None, lifelong=False):
+                 iters_per_launch=None, hash_bits=0, swap=False, refine_rounds=0, refine_horizon=None, lifelong=False, shield=False, env=None,
+                 tok=None):
         if search not in (None, "lacam"):
             raise ValueError(f"search={search!r}: None or 'lacam'")
         if lifelong and search:
             raise ValueError("lifelong=True with search=: the search looks for a joint goal configuration, which a lifelong episode does not have")
         if refine_rounds and not search:
             raise ValueError("refine_rounds needs search='lacam': the pass refines what the search found")
+        if shield and (search or swap or refine_rounds or lifelong):
+            raise ValueError("shield=True with search=, swap=, refine_rounds= or lifelong=: the shield runs plain PIBT on the policy's candidate order")
+        if (env is not None or tok is not None) and not shield:
+            raise ValueError("env= / tok= need shield=True: an expert of its own makes its env and tokenizer")
         self.device = torch.device(device)
-        self.env = BatchedEnv(grids, n_inst, n_agents, max_episode_steps, device=device)
-        self.tok = BatchedTokenizer(grids, n_inst, n_agents, device=device)
+        self.env = env if env is not None else BatchedEnv(grids, n_inst, n_agents, max_episode_steps, device=device)
+        self.tok = tok if tok is not None else BatchedTokenizer(grids, n_inst, n_agents, device=device)
         self.n_inst, self.n_agents, self.max_episode_steps = int(n_inst), int(n_agents), int(max_episode_steps)
         self.seed, self.inst_offset = int(seed), int(inst_offset)
         self.actions = torch.zeros((n_inst, n_agents), dtype=torch.int32, device=self.device)
@@ -93,6 +104,50 @@ class BatchedExpert:
         self._goal0 = self._queue = None
         if lifelong:
             self.set_lifelong(True)
+        self.shield = False
+        if shield:
+            self.set_shield(True)
+
+    def set_shield(self, on):
+        """Turn shield mode on or off: before reset() or between episodes (MGPTError with ERR_STATE in the middle of one, with
+        ERR_UNSUPPORTED together with the search, the swap rule or lifelong planning); reset() must follow."""
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_set_shield(self._h, 1 if on else 0))
+        self.shield = bool(on)
+
+    def reset_shield(self):
+        """Shield mode over a borrowed env and tokenizer (BatchedRunner): the expert's own part of reset(), after theirs."""
+        self.actions.zero_()
+        self.t = 0
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_reset(self._h, _lib.stream_ptr()))
+
+    def shield_step(self, logits, first):
+        """logits float32 [n_inst * n_agents, >= 5] (or [n_inst, n_agents, >= 5]), first int32 [n_inst, n_agents]: the policy's logits and
+        sampled actions -> the planned actions int32 [n_inst, n_agents] (self.actions), already executed by the env."""
+        logits = logits.to(self.device, torch.float32).reshape(self.n_inst * self.n_agents, -1).contiguous()
+        self.actions.copy_(first.to(self.device, torch.int32).reshape(self.n_inst, self.n_agents))
+        with _lib.on_device(self.device):
+            L, s = _lib.lib(), _lib.stream_ptr()
+            _lib.check(L.mgpt_expert_shield(self._h, _lib.ptr(logits), int(logits.shape[1]), None, None, _lib.ptr(self.actions.view(-1)), s))
+            _lib.check(L.mgpt_env_step(self.env._h, _lib.ptr(self.actions.view(-1)), s))
+            _lib.check(L.mgpt_expert_shield_commit(self._h, s))
+        self.t += 1
+        return self.actions
+
+    def shield_first(self):
+        """int32 [n_inst, n_agents]: the policy's actions of the last shield step, as the planner read them (device tensor)."""
+        out = torch.empty((self.n_inst, self.n_agents), dtype=torch.int32, device=self.device)
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_copy_shield(self._h, _lib.ptr(out), None, _lib.stream_ptr()))
+        return out
+
+    def shield_overrides(self):
+        """int32 [n_inst]: agents whose planned action was not the policy's, summed over the steps since reset() (device tensor)."""
+        out = torch.empty((self.n_inst,), dtype=torch.int32, device=self.device)
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_copy_shield(self._h, None, _lib.ptr(out), _lib.stream_ptr()))
+        return out
 
     def set_lifelong(self, on):
         """Turn lifelong planning on or off: before reset() or between episodes (MGPTError with ERR_STATE in the middle of one, with

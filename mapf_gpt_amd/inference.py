@@ -59,6 +59,9 @@ class MAPFGPTInferenceConfig(BaseModel):
     # unconditionally; "bf16" = the reference's autocast class.
     precision: Literal["f32", "f16x3", "bf16"] = "f16x3"
     envelope: Literal["fallback", "refuse", "ignore"] = "fallback"
+    # extension: "pibt" puts the collision shield between the policy and the env.  Read by evaluation.py only, which
+    # hands it to BatchedRunner; the list API below (act / act_batch) steps an env it does not own and ignores the field with one warning.
+    shield: Optional[str] = None
 
 
 def strip_prefix_from_state_dict(state_dict, prefix="_orig_mod."):
@@ -230,6 +233,11 @@ class MAPFGPTInference:
 
     def act_batch(self, observations_list, positions=None):
         """= inference.py:151-172: rows of many envs -> one forward -> split back per env."""
+        if self.cfg.shield and not getattr(self, "_shield_warned", False):
+            import warnings
+            warnings.warn("MAPFGPTInferenceConfig.shield is read by the batched evaluation only: act() / act_batch() return the policy's own "
+                          "sampled actions", stacklevel=2)
+            self._shield_warned = True
         if positions is None:
             positions = list(range(len(observations_list)))
         counts = [len(o) for o in observations_list]

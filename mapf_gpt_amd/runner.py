@@ -15,6 +15,10 @@ One hot-path step (order as in the reference's run_episode loop, example.py:65 /
 retire_done=True (opt-in) stops forwarding finished instances: every poll_every-th step the library compacts the ids of the
 instances that are not done and reads their count back (the mode's only host synchronisation); until the next poll the policy
 runs on the token rows of those instances alone.  Draws and metrics are those of the plain run ("Retire mode").
+
+shield="pibt" (opt-in) puts a collision shield between the policy and the env: every step the sampled actions
+and the logits go through one PIBT step per instance, with each agent's candidates in the policy's order of preference, and the env
+executes the planned actions -- nobody steps into a conflict, so the env's rules never make an agent wait.
 """
 import ctypes
 
@@ -66,7 +70,9 @@ def make_instances(grid, n_inst, n_agents, first_seed=0, start_ok=None, goal_ok=
 
 class BatchedRunner:
     def __init__(self, grids, n_inst, n_agents, net, max_episode_steps=128, seed=0, do_sample=True, precision=None,
-                 device="cuda", row_offset=0, use_graph=False, retire_done=False, poll_every=8):
+                 device="cuda", row_offset=0, use_graph=False, retire_done=False, poll_every=8, shield=None):
+        if shield not in (None, "pibt"):
+            raise ValueError(f"shield={shield!r}: None or 'pibt'")
         if retire_done and use_graph:
             raise ValueError("retire_done=True runs eager launches only: the policy's row count changes from poll to poll, use_graph=True cannot replay it")
         if int(poll_every) < 1:
@@ -98,6 +104,31 @@ class BatchedRunner:
         self._live, self._rows_forwarded, self._polled_t = n_inst, 0, -1
         if retire_done:
             self.set_retire_done(True)
+        self.shield, self._shield = shield, None
+        if shield:
+            from .expert import BatchedExpert
+            self._shield = BatchedExpert(grids, n_inst, n_agents, max_episode_steps, device=device, shield=True, env=self.env, tok=self.tok)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().mgpt_step_set_shield(self._step, self._shield._h))
+
+    def shield_overrides(self):
+        """int32 [n_inst]: agents whose planned action was not the sampled one, summed over the steps since reset() (device tensor)."""
+        if self._shield is None:
+            raise RuntimeError("shield_overrides() needs shield='pibt'")
+        return self._shield.shield_overrides()
+
+    def shield_state(self):
+        """Tests: (logits float32 [rows, 67], first int32 [n_inst, n_agents], actions int32 [n_inst, n_agents], planned int16 [n_inst,
+        n_agents, 2]) of the last step.  In retire mode the logits are the compact rows of live_state()."""
+        if self._shield is None:
+            raise RuntimeError("shield_state() needs shield='pibt'")
+        if self.retire_done:
+            logits = self.live_state()[1]
+        else:
+            logits = torch.empty((self.rows, 67), dtype=torch.float32, device=self.device)
+            with _lib.on_device(self.device):
+                _lib.check(_lib.lib().mgpt_step_copy_shield_logits(self._step, _lib.ptr(logits), _lib.stream_ptr()))
+        return logits, self._shield.shield_first(), self.actions.clone(), self._shield.planned()
 
     def set_retire_done(self, on):
         """Switch retire mode (mgpt_step_set_retire: allocates / frees its buffers); takes effect at the next reset()."""
@@ -118,7 +149,7 @@ class BatchedRunner:
     def __del__(self):
         h = getattr(self, "_step", None)
         if h:
-            try:
+            try:                   # (the step goes before the shield expert it points to)
                 _lib.lib().mgpt_step_destroy(h)
             except Exception:      # interpreter shutdown
                 pass
@@ -127,6 +158,8 @@ class BatchedRunner:
     def reset(self, pos, goal, goal_queue=None):
         """goal_queue int16 [n_inst, n_agents, Q, 2]: lifelong mode (on_target="restart"), the tokenizer then re-checks
         goals every step (observation_generator.cpp:464-477)."""
+        if goal_queue is not None and self._shield is not None:
+            raise NotImplementedError("shield='pibt' does not plan lifelong (goal_queue) episodes")
         if goal_queue is not None or self.env.lifelong:
             self.env.set_lifelong(goal_queue)
         self.env.reset(pos, goal)
@@ -136,6 +169,8 @@ class BatchedRunner:
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().mgpt_step_reset(self._step, 0, _lib.stream_ptr()))
         self._live, self._rows_forwarded, self._polled_t = self.n_inst, 0, -1
+        if self._shield is not None:
+            self._shield.reset_shield()
         if self.retire_done:
             self._poll()
 
