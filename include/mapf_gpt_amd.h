@@ -422,6 +422,19 @@ int mgpt_live_list(const uint8_t *d_done, int n_inst, int32_t *d_live, int32_t *
  *           d_tokens must be 16-byte aligned.
  *   copy_live:  test/debug: the live list (int32 [n_inst]) and the compact logits of the last run (float32 [rows, 67], the first
  *           n_live * n_agents rows valid) into caller-owned device buffers; either may be NULL.
+ * Episode recorder (opt-in): the trajectory of the policy's own episode stays on the device.
+ *   set_record: enable != 0 allocates, for T = the env's max_episode_steps, traj_pos int16 [T + 1][rows][2], traj_act int8 [T][rows] and
+ *           a one-word device t0 (zero-filled; t0 = the current step counter), and drops a captured graph.  enable == 0 frees them and
+ *           restores the plain step exactly.  Synchronous.
+ *   reset with recording on: t0 = step0, both buffers zero-filled, the env's current positions copied into slot 0 -- so the env must
+ *           have been reset BEFORE mgpt_step_reset (mgpt_env_reset, then mgpt_step_reset: the order BatchedRunner.reset calls in).
+ *   run with recording on: one more launch (timing-hook name step_record) after the env step (and the shield's commit), before the
+ *           counter bump: with t = step counter - t0 read on the device, traj_pos[t + 1][row] = the row's position after the step and
+ *           traj_act[t][row] = (int8) the action handed to the env (with a shield: the planned one), for every row, done or retired
+ *           instances included (they do not move; their action entries beyond the episode's length -- the env's ep_length metric --
+ *           mean nothing).  A step with t >= T writes nothing.  Eager, graph, retire, shield and lifelong steps all record.
+ *   copy_record: traj_pos and traj_act into caller-owned device buffers of those shapes; either may be NULL.  MGPT_ERR_STATE with
+ *           recording off.
  * ------------------------------------------------------------------------------------------ */
 typedef struct mgpt_step mgpt_step;
 int mgpt_step_create(mgpt_step **out, mgpt_tokenizer *tok, mgpt_gpt *gpt, mgpt_env *env, int rows, int precision,
@@ -432,6 +445,8 @@ int mgpt_step_run(mgpt_step *step, uint8_t *d_tokens, int32_t *d_actions, int go
 int mgpt_step_set_retire(mgpt_step *step, int enable);
 int mgpt_step_poll_live(mgpt_step *step, int *n_live, void *stream);
 int mgpt_step_copy_live(mgpt_step *step, int32_t *d_live_out, float *d_logits_out, void *stream);
+int mgpt_step_set_record(mgpt_step *step, int enable);
+int mgpt_step_copy_record(mgpt_step *step, int16_t *d_pos_out, int8_t *d_act_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Dataset-side bulk tokenizer: replaces dataset/tokenizer/generate_observations.py:8-92 with its two native modules

@@ -98,6 +98,8 @@ SYMBOLS = {
     "mgpt_step_set_retire": (_i, [_vp, _i]),
     "mgpt_step_poll_live": (_i, [_vp, ctypes.POINTER(_i), _vp]),
     "mgpt_step_copy_live": (_i, [_vp, _vp, _vp, _vp]),
+    "mgpt_step_set_record": (_i, [_vp, _i]),
+    "mgpt_step_copy_record": (_i, [_vp, _vp, _vp, _vp]),
     "mgpt_gpt_debug_copy": (_i, [_vp, _i, _vp, _i64, _vp]),
     "mgpt_gpt_debug_copy_raw": (_i, [_vp, _i, _i, _vp, _i64, _vp]),
     "mgpt_gpt_debug_counter": (_i, [_i, ctypes.POINTER(_u64), _i]),

@@ -22,6 +22,8 @@ uint64_t gpt_generation(const mgpt_gpt *g);
 uint64_t env_generation(const mgpt_env *e);
 // instances and agents per instance of an env context (step.hip sizes its live list and compact buffers from them)
 void env_shape(const mgpt_env *e, int *n_inst, int *n_agents);
+// max_episode_steps of an env context (step.hip sizes the episode recorder's buffers from it)
+int env_max_steps(const mgpt_env *e);
 // rule mask, lifelong flag and frame of an env context; the device state a tokenizer context lends to the expert (expert.hip)
 void env_config(const mgpt_env *e, int *H, int *W, int *n_grids, int *rules, int *lifelong);
 struct TokView {
@@ -77,6 +79,7 @@ enum ProfId {
     P_EXPERT_REFINE_PATH, P_EXPERT_REFINE_ROUND, P_EXPERT_REFINE_FINAL,   // the refinement pass of a solve: path, every round, final (expert.hip)
     P_EXPERT_LIFELONG_POST,                             // lifelong episodes: arrivals, since and the arrivals log after the env step (expert.hip)
     P_EXPERT_SHIELD,                                    // the collision shield's plan kernel (expert.hip)
+    P_STEP_RECORD,                                      // the episode recorder's store of a step (step.hip)
     P_COUNT
 };
 

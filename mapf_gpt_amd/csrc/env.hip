@@ -261,6 +261,7 @@ struct mgpt_env {
 
 uint64_t mgpt::env_generation(const mgpt_env *e) { return e->generation; }
 void mgpt::env_shape(const mgpt_env *e, int *n_inst, int *n_agents) { *n_inst = e->n_inst; *n_agents = e->n_agents; }
+int mgpt::env_max_steps(const mgpt_env *e) { return e->max_steps; }
 void mgpt::env_config(const mgpt_env *e, int *H, int *W, int *n_grids, int *rules, int *lifelong)
 {
     *H = e->H; *W = e->W; *n_grids = e->n_grids; *rules = e->rules; *lifelong = e->ll.goal_queue != nullptr ? 1 : 0;

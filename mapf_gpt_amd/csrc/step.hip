@@ -16,6 +16,10 @@
 // into a compact buffer, the policy forwards those rows alone, and sample_live_kernel (gpt.hip) writes each action to its global row
 // with the draw keyed by that global row.  An instance that finishes inside the window is forwarded until the next poll; the env
 // ignores it (env.hip: env_step_kernel returns on done != 0).  Eager launches only: the row count changes from poll to poll.
+//
+// Recording (mgpt_step_set_record): one more launch per step, record_kernel, after the env step and before the
+// counter bump, stores every row's new position and the action the env was handed into per-step slots of two trajectory buffers.  The
+// slot index is read on the device (step counter minus the counter at reset), so the launch is static and a captured graph replays it.
 #include <vector>
 
 #include "common.h"
@@ -61,12 +65,35 @@ struct mgpt_step {
     // collision shield (mgpt_step_set_shield): NULL when off
     mgpt_expert *shield = nullptr;              // a shield-mode expert over tok and env, owned by the caller
     float *d_logits = nullptr;                  // [rows][67] the plain path's logits of the last step (retire mode has rt.d_clogits)
-    DeviceArena mem, retire_mem, shield_mem;    // d_step; rt; d_logits
+    // episode recorder (mgpt_step_set_record): all NULL / 0 when off
+    struct Record {                             // owned by record_mem
+        uint32_t *d_pos = nullptr;              // [T + 1][rows] one (row, col) int16 pair per word: slot 0 = the reset positions, slot t + 1 after step t
+        int8_t *d_act = nullptr;                // [T][rows] the action handed to the env at step t
+        uint64_t *d_t0 = nullptr;               // the step counter at the last reset: slot index = *d_step - *d_t0
+        int T = 0;                              // the env's max_episode_steps
+    } rec;
+    DeviceArena mem, retire_mem, shield_mem, record_mem;    // d_step; rt; d_logits; rec
 };
 
 namespace {
 __global__ void bump_kernel(uint64_t *ctr) { *ctr += 1; }
 __global__ void set_kernel(uint64_t *ctr, uint64_t v) { *ctr = v; }
+
+// One step of the episode recorder: row's cell after the env step -> traj_pos[t + 1][row] (one 4-byte store), the action the env was
+// handed -> traj_act[t][row], with t = *d_step - *t0 read here, so the launch has no per-step argument.  Steps beyond the buffers'
+// T slots (and a counter behind t0: the unsigned difference is then huge) write nothing.  Every row is handled, done instances too:
+// they do not move, and their entries beyond the episode's length mean nothing.
+__global__ __launch_bounds__(256) void record_kernel(const uint32_t *__restrict__ pos, const int32_t *__restrict__ actions,
+                                                     const uint64_t *__restrict__ d_step, const uint64_t *__restrict__ t0, int T, int rows,
+                                                     uint32_t *__restrict__ traj_pos, int8_t *__restrict__ traj_act)
+{
+    const uint64_t t = *d_step - *t0;
+    if (t >= (uint64_t)T) return;
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= rows) return;
+    traj_pos[(t + 1) * (uint64_t)rows + row] = pos[row];
+    traj_act[t * (uint64_t)rows + row] = (int8_t)actions[row];
+}
 
 constexpr int kLiveThreads = 1024, kLiveWaves = kLiveThreads / 64;
 
@@ -148,6 +175,12 @@ int act_live(mgpt_step *st, const uint8_t *d_tokens, int32_t *d_actions, hipStre
                                st->d_step, st->row0, s);
 }
 
+void free_record(mgpt_step *st)
+{
+    st->record_mem.release();
+    st->rec = mgpt_step::Record();
+}
+
 void free_retire(mgpt_step *st)
 {
     st->retire_mem.release();
@@ -174,6 +207,12 @@ int step_body(mgpt_step *st, uint8_t *d_tokens, int32_t *d_actions, int gmc, hip
     }
     if ((rc = mgpt_env_step(st->env, d_actions, s)) != MGPT_OK) return rc;
     if (st->shield && (rc = mgpt_expert_shield_commit(st->shield, s)) != MGPT_OK) return rc;
+    if (st->rec.d_pos) {
+        ProfScope prof(P_STEP_RECORD, s);
+        hipLaunchKernelGGL(record_kernel, dim3(cdiv(st->rows, 256)), dim3(256), 0, s, (const uint32_t *)st->d_pos, d_actions, st->d_step, st->rec.d_t0,
+                           st->rec.T, st->rows, st->rec.d_pos, st->rec.d_act);
+        MGPT_LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, s, st->d_step);
     MGPT_LAUNCH_CHECK();
     return MGPT_OK;
@@ -221,6 +260,7 @@ extern "C" int mgpt_step_destroy(mgpt_step *st)
     if (!st) return MGPT_OK;
     drop_graph(st);
     free_retire(st);
+    free_record(st);
     if (st->cap_stream) (void)hipStreamDestroy(st->cap_stream);
     delete st;
     return MGPT_OK;
@@ -237,6 +277,54 @@ extern "C" int mgpt_step_reset(mgpt_step *st, uint64_t step0, void *stream)
         MGPT_LAUNCH_CHECK();
         st->n_live = st->n_inst;
     }
+    if (st->rec.d_pos) {     // a new recording: slot index 0 at step0, empty buffers, the env's (already reset) positions in slot 0
+        hipStream_t s = (hipStream_t)stream;
+        const size_t rows = (size_t)st->rows;
+        hipLaunchKernelGGL(set_kernel, dim3(1), dim3(1), 0, s, st->rec.d_t0, step0);
+        MGPT_LAUNCH_CHECK();
+        MGPT_HIP(hipMemsetAsync(st->rec.d_pos, 0, ((size_t)st->rec.T + 1) * rows * sizeof(uint32_t), s));
+        MGPT_HIP(hipMemsetAsync(st->rec.d_act, 0, (size_t)st->rec.T * rows, s));
+        MGPT_HIP(hipMemcpyAsync(st->rec.d_pos, st->d_pos, rows * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    }
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_step_set_record(mgpt_step *st, int enable)
+{
+    MGPT_REQUIRE(st, MGPT_ERR_ARG, "NULL argument");
+    drop_graph(st);                               // the launch sequence changes either way
+    if (!enable) {
+        free_record(st);                          // (freeing waits for the work that still writes the buffers)
+        return MGPT_OK;
+    }
+    if (st->rec.d_pos) return MGPT_OK;
+    const int T = env_max_steps(st->env);
+    const size_t rows = (size_t)st->rows;
+    DeviceArena &rm = st->record_mem;
+    hipError_t e = rm.alloc(&st->rec.d_pos, ((size_t)T + 1) * rows * sizeof(uint32_t));
+    if (e == hipSuccess) e = rm.alloc(&st->rec.d_act, (size_t)T * rows);
+    if (e == hipSuccess) e = rm.alloc(&st->rec.d_t0, sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMemset(st->rec.d_pos, 0, ((size_t)T + 1) * rows * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(st->rec.d_act, 0, (size_t)T * rows);
+    if (e == hipSuccess) e = hipMemcpy(st->rec.d_t0, st->d_step, sizeof(uint64_t), hipMemcpyDeviceToDevice);   // recording starts at slot 0 from here
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("allocation failed in mgpt_step_set_record: %s", hipGetErrorString(e));
+        free_record(st);
+        return MGPT_ERR_HIP;
+    }
+    st->rec.T = T;
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_step_copy_record(mgpt_step *st, int16_t *d_pos_out, int8_t *d_act_out, void *stream)
+{
+    MGPT_REQUIRE(st, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(st->rec.d_pos, MGPT_ERR_STATE, "recording is off (mgpt_step_set_record)");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t rows = (size_t)st->rows;
+    if (d_pos_out) MGPT_HIP(hipMemcpyAsync(d_pos_out, st->rec.d_pos, ((size_t)st->rec.T + 1) * rows * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    if (d_act_out) MGPT_HIP(hipMemcpyAsync(d_act_out, st->rec.d_act, (size_t)st->rec.T * rows, hipMemcpyDeviceToDevice, s));
     return MGPT_OK;
 }
 

@@ -222,7 +222,8 @@ class LaCAMConfig(PIBTConfig):
 
 
 def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, max_rows_per_batch=65536, rank=0, world=1,
-               print_fn=print, trace=None, retire_done=False, log_actions=False, search_status=None, refine_stats=None):
+               print_fn=print, trace=None, retire_done=False, log_actions=False, search_status=None, refine_stats=None, record=False,
+               on_batch=None):
     """Run `evaluation_config` (dict in the reference's YAML schema).  Returns the list of result records (on every
     rank); writes `<eval_dir>/<algorithm>.json` and prints the tabular views on rank 0.
     `trace(kind, payload)` (tests): called with ("reset", {algorithm, runs, grids, pos, goal, max_steps}) for every batch
@@ -241,12 +242,19 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
     status 4, final status 1) and `soc_before` / `soc_after` summed over the refined instances.
     A MAPF-GPT entry with `shield: pibt` runs its policy behind the collision shield (BatchedRunner(shield="pibt"), DESIGN.md section 31);
     its records also carry `shield_overrides`: the agents whose planned action was not the sampled one, summed over the episode and
-    divided by ep_length x num_agents.  Such an entry raises on an on_target="restart" group, as log_actions does."""
+    divided by ep_length x num_agents.  Such an entry raises on an on_target="restart" group, as log_actions does.
+    record: MAPF-GPT entries run a recording runner (BatchedRunner(record=True)) and their records also carry
+    `made_actions` (the actions the env was handed, cut to the episode's length), `init_positions` and `moves` (the actions the env
+    executed); one rank only, as log_actions, which keeps its meaning (the expert's logs).  on_batch(info): called after each policy
+    batch has run, info = {runner, algorithm, mine (the run indices of the batch, in instance order), grids, pos, goal, run_keys,
+    n_agents, max_steps, on_target} -- how mapf_gpt_amd.ddg reads the recorded trajectories while they are on the device."""
     import torch
     from .runner import BatchedRunner, gather_metrics, shard_range
 
     if log_actions and world != 1:
         raise ValueError("log_actions=True needs world == 1: the action logs are not gathered across ranks")
+    if record and world != 1:
+        raise ValueError("record=True needs world == 1: the recorded episodes are not gathered across ranks")
 
     registry = registry or MapRegistry()
     runs = expand_grid_search(evaluation_config["environment"])
@@ -282,7 +290,7 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                 mine = chunk[lo:hi]
                 local = torch.zeros((0, len(METRIC_KEYS) + (1 if shield else 0)), dtype=torch.float32, device=cfg.device)
                 t0 = time.perf_counter()
-                logged = {}
+                logged, recorded = {}, {}
                 if mine:
                     grids = np.stack([frames[i][0] for i in mine])
                     pos = np.empty((len(mine), n_agents, 2), np.int16)
@@ -301,7 +309,8 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                     else:
                         run = BatchedRunner(grids, len(mine), n_agents, algo.net, max_episode_steps=max_steps,
                                             seed=int(cfg.seed or 0), do_sample=True, precision=cfg.precision, device=cfg.device,
-                                            row_offset=lo * n_agents, retire_done=bool(retire_done), **({"shield": shield} if shield else {}))
+                                            row_offset=lo * n_agents, retire_done=bool(retire_done), **({"shield": shield} if shield else {}),
+                                            **({"record": True} if record else {}))
                     queue = None
                     if on_target == "restart":          # lifelong: a seeded queue of further goals per agent (wraps)
                         queue = np.empty((len(mine), n_agents, LIFELONG_QUEUE, 2), np.int16)
@@ -341,6 +350,12 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                         init = dict(zip(mine, pos.tolist()))
                         if queue is not None:
                             targets = dict(zip(mine, run.targets()))
+                    if not is_pibt and record:
+                        recorded = dict(zip(mine, (r["metrics"] for r in run.records([runs[i][1] for i in mine], algo_name))))
+                    if not is_pibt and on_batch is not None:
+                        on_batch({"runner": run, "algorithm": algo_name, "mine": list(mine), "grids": grids, "pos": pos, "goal": goal,
+                                  "run_keys": [runs[i][1] for i in mine], "n_agents": n_agents, "max_steps": max_steps,
+                                  "on_target": on_target})
                     torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
                 allm = gather_metrics(local, len(chunk), rank, world).cpu().numpy()
@@ -355,6 +370,8 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                         m["made_actions"], m["init_positions"] = logged[i], init[i]
                         if on_target == "restart":
                             m["global_lifelong_targets_xy"] = targets[i]
+                    if i in recorded:
+                        m.update({key: recorded[i][key] for key in ("made_actions", "init_positions", "moves")})
                     results.append({"metrics": m, "env_grid_search": runs[i][1], "algorithm": algo_name})
         del algo
     if rank == 0:

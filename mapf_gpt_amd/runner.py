@@ -19,6 +19,10 @@ runs on the token rows of those instances alone.  Draws and metrics are those of
 shield="pibt" (opt-in) puts a collision shield between the policy and the env: every step the sampled actions
 and the logits go through one PIBT step per instance, with each agent's candidates in the policy's order of preference, and the env
 executes the planned actions -- nobody steps into a conflict, so the env's rules never make an agent wait.
+
+record=True (opt-in) keeps the episode on the device: one more launch per step stores every agent's position after
+the step and the action the env was handed; trajectory() hands the buffers out as tensors, records() as toolbox records with
+`made_actions`, `init_positions` and `moves` (the action the env executed), which is what mapf_gpt_amd.ddg relabels.
 """
 import ctypes
 
@@ -68,9 +72,20 @@ def make_instances(grid, n_inst, n_agents, first_seed=0, start_ok=None, goal_ok=
     return torch.from_numpy(pos), torch.from_numpy(goal)
 
 
+def moves_from_positions(pos):
+    """pos integer tensor [T + 1, ..., 2] -> int8 [T, ...]: the action the env executed between consecutive slots, the unique k with
+    pos[t] + move[k] == pos[t + 1] (0 wait, 1 up, 2 down, 3 left, 4 right; 0 where the env made the agent wait)."""
+    d = pos[1:].to(torch.int32) - pos[:-1].to(torch.int32)
+    dr, dc = d[..., 0], d[..., 1]
+    k = torch.zeros_like(dr)
+    for code, (r, c) in ((1, (-1, 0)), (2, (1, 0)), (3, (0, -1)), (4, (0, 1))):
+        k = torch.where((dr == r) & (dc == c), torch.full_like(k, code), k)
+    return k.to(torch.int8)
+
+
 class BatchedRunner:
     def __init__(self, grids, n_inst, n_agents, net, max_episode_steps=128, seed=0, do_sample=True, precision=None,
-                 device="cuda", row_offset=0, use_graph=False, retire_done=False, poll_every=8, shield=None):
+                 device="cuda", row_offset=0, use_graph=False, retire_done=False, poll_every=8, shield=None, record=False):
         if shield not in (None, "pibt"):
             raise ValueError(f"shield={shield!r}: None or 'pibt'")
         if retire_done and use_graph:
@@ -110,6 +125,47 @@ class BatchedRunner:
             self._shield = BatchedExpert(grids, n_inst, n_agents, max_episode_steps, device=device, shield=True, env=self.env, tok=self.tok)
             with torch.cuda.device(self.device):
                 _lib.check(_lib.lib().mgpt_step_set_shield(self._step, self._shield._h))
+        self.record = False
+        if record:
+            self.set_record(True)
+
+    def set_record(self, on):
+        """Switch the episode recorder (mgpt_step_set_record: allocates / frees its buffers); a recording starts at the next reset()."""
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mgpt_step_set_record(self._step, 1 if on else 0))
+        self.record = bool(on)
+
+    def trajectory(self):
+        """record=True: (pos int16 [T + 1, n_inst, n_agents, 2], actions int8 [T, n_inst, n_agents], lengths int32 [n_inst]) device
+        tensors, T = max_episode_steps.  Slot 0 of pos is the reset positions, slot t + 1 the positions after step t; actions[t] is
+        what the env was handed at step t (with a shield: the planned action).  Instance i is valid up to lengths[i], the env's
+        ep_length: pos[lengths[i]] is where it ended (and every later slot that was stepped repeats it), actions beyond are meaningless."""
+        T = self.env.max_episode_steps
+        pos = torch.empty((T + 1, self.n_inst, self.n_agents, 2), dtype=torch.int16, device=self.device)
+        act = torch.empty((T, self.n_inst, self.n_agents), dtype=torch.int8, device=self.device)
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_step_copy_record(self._step, _lib.ptr(pos), _lib.ptr(act), _lib.stream_ptr()))
+        return pos, act, self.metrics()[:, 4].to(torch.int32)
+
+    def records(self, run_keys, algorithm="MAPF-GPT"):
+        """record=True: toolbox result records in BatchedExpert.records' shape -- the six env metrics, `init_positions` (slot 0, padded
+        coordinates), `made_actions` (per agent, the actions the env was handed, cut to the episode's length) and `moves`: the action
+        the env executed, from the recorded positions.  dataset_tokenizer.agent_paths(init_positions, moves) is the recorded path;
+        with made_actions it is not wherever the env turned a move into a wait."""
+        pos, act, lens = self.trajectory()
+        moves = moves_from_positions(pos).permute(1, 2, 0).cpu().numpy()
+        made = act.permute(1, 2, 0).cpu().numpy()
+        init, lens, m = pos[0].cpu().numpy(), lens.cpu().numpy(), self.metrics().cpu().numpy()
+        from .env import METRIC_KEYS
+        out = []
+        for i in range(self.n_inst):
+            rec = {k: float(m[i, j]) for j, k in enumerate(METRIC_KEYS)}
+            n = int(lens[i])
+            rec["made_actions"] = [made[i, a, :n].tolist() for a in range(self.n_agents)]
+            rec["moves"] = [moves[i, a, :n].tolist() for a in range(self.n_agents)]
+            rec["init_positions"] = init[i].astype(int).tolist()
+            out.append({"metrics": rec, "env_grid_search": dict(run_keys[i]), "algorithm": algorithm})
+        return out
 
     def shield_overrides(self):
         """int32 [n_inst]: agents whose planned action was not the sampled one, summed over the steps since reset() (device tensor)."""
