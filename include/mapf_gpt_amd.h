@@ -470,6 +470,29 @@ int mgpt_dataset_tokenize(mgpt_dataset *ds, int n_agents, int n_steps, const int
  *   only_obstacles != 0: the mask_cost2go ablation (cost2go.cpp:52-62) -- window cells become the integers 0 / 1 (blocked). */
 int mgpt_dataset_tokenize_ex(mgpt_dataset *ds, int n_agents, int n_steps, const int16_t *d_paths, const int16_t *d_goals,
                              int only_obstacles, uint8_t *d_tokens, void *stream);
+/* A batch of episodes of one map, straight from the expert's device log: no per-episode host work.
+ *   d_init     int16 [n_batch][n_agents][2]: the agents' first cells, padded coords (the table's frame);
+ *   d_actions  int8 [n_batch][n_agents][max_steps]: the made actions, the layout of mgpt_expert_copy_log.  A byte outside 0..4 counts as
+ *              a wait; cells are clamped into the frame, so no byte value moves a read out of bounds (a logged path never leaves it);
+ *   d_len      int32 [n_batch]: actions made per episode, clamped to [0, max_steps] on the device;
+ *   d_keep     uint8 [n_batch] or NULL: 0 = the episode gives no rows (generate_observations.py:44-45, CSR < 1);
+ *   d_episodes int32 [n_sel] or NULL: the selected episodes (indices below n_batch, any order, repeats allowed); NULL = 0 .. n_sel - 1.
+ *   episode_offsets:   d_row0 int64 [n_sel + 1] = the exclusive scan of rows(k) = keep ? n_agents * (len + 1) : 0 in selection order.  One
+ *              workgroup, no atomics: the same bits on every run.
+ *   tokenize_episodes: d_row0 as episode_offsets wrote it for the same arguments, or a window of n_sel + 1 entries of a longer scan together
+ *              with the same window of d_episodes (not NULL then): a large selection is tokenized in several calls into one output.
+ *              Rows [row0[k], row0[k + 1]) of d_tokens uint8 [N][256] and d_labels int8 [N] (N = the scan's last entry) are what
+ *              mgpt_dataset_tokenize makes of the episode's paths (init + the running sum of the moves; the goal is the path's last
+ *              cell), agent-major then timestep 0 .. len, and the labels of generate_observations.py:67-90: with a = actions[:len] +
+ *              [0] and g the index of a's last non-zero entry (len + 1 if none), 5 where t > g, else a[t].  Lifelong logs (per-step
+ *              goals) are not supported: use mgpt_dataset_tokenize_ex per episode.  Stream-ordered; no host synchronisation except
+ *              when the context's workspace (16 bytes per row of n_sel * n_agents * (max_steps + 1)) grows.  MGPT_ERR_UNSUPPORTED
+ *              when that product reaches 2^31: split the selection.  n_sel = 0 launches nothing. */
+int mgpt_dataset_episode_offsets(int n_sel, int n_agents, int max_steps, const int32_t *d_len, const uint8_t *d_keep,
+                                 const int32_t *d_episodes, int64_t *d_row0, void *stream);
+int mgpt_dataset_tokenize_episodes(mgpt_dataset *ds, int n_sel, int n_agents, int max_steps, const int16_t *d_init, const int8_t *d_actions,
+                                   const int32_t *d_len, const uint8_t *d_keep, const int32_t *d_episodes, const int64_t *d_row0,
+                                   int only_obstacles, uint8_t *d_tokens, int8_t *d_labels, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Dataset builder: steps 2-3 of dataset/generate_dataset.py on rows that the bulk tokenizer above has left on the device --

@@ -80,6 +80,7 @@ enum ProfId {
     P_EXPERT_LIFELONG_POST,                             // lifelong episodes: arrivals, since and the arrivals log after the env step (expert.hip)
     P_EXPERT_SHIELD,                                    // the collision shield's plan kernel (expert.hip)
     P_STEP_RECORD,                                      // the episode recorder's store of a step (step.hip)
+    P_DS_PATHS, P_DS_EPISODE_TOKENS,                    // batched episode tokenizer: paths + labels + records, rows (tokenizer.hip)
     P_COUNT
 };
 

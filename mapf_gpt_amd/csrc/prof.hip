@@ -29,7 +29,8 @@ static const char *kProfNames[P_COUNT] = {
     "ds_row_hash", "ds_insert", "ds_classify", "ds_resolve", "ds_balance", "ds_select", "ds_gather",
     "expert_pibt_plan", "expert_lacam_search", "expert_cell_degree",
     "expert_refine_path", "expert_refine_round", "expert_refine_final",
-    "expert_lifelong_post", "expert_shield", "step_record"};
+    "expert_lifelong_post", "expert_shield", "step_record",
+    "ds_paths", "ds_episode_tokens"};
 
 struct ProfState {
     std::mutex mu;

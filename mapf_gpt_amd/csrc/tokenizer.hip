@@ -15,6 +15,7 @@
 //                                                                                        (cpp:288-311, 487-528, 352-389)
 //   ds_* kernels      dataset-side bulk tokenizer (dataset/tokenizer/*): all-pairs BFS table per map, one row per
 //                     (agent, timestep) of a logged episode
+//   ds_offsets / ds_paths / ds_episode_tokens   the same rows for a batch of episodes of one map, straight from the expert's device log
 #include "common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -815,6 +816,189 @@ __global__ __launch_bounds__(256) void ds_tokens_kernel(const AgentRec *__restri
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Batched episodes: the expert's device log -> rows, one call per map.  Selected episode k = d_episodes[k] of the
+// batch (NULL: k) owns rows [row0[k], row0[k + 1]), agent-major then timestep 0 .. len like the per-episode path above; an episode that is
+// not kept owns none.  The kernels read an episode's length back from the offsets ((row0[k + 1] - row0[k]) / n_agents = len + 1), so the
+// clamp of ds_offsets_kernel is the only place that looks at d_len.
+//   ds_offsets_kernel         one workgroup: exclusive scan of the episodes' row counts (per-thread runs, then the 256 partial sums
+//                             summed in thread order: no atomics, the same bits on every run)
+//   ds_paths_kernel           one thread per (episode, agent) walks its actions twice: once for the path's last cell (the goal) and the
+//                             last move, once more leaving the record and the label of every timestep.  The running sum of the moves
+//                             lives in registers and each cell goes straight into its record, so there is no path array in between;
+//                             the history is a five-token shift register (what ds_records_kernel reads off the path per timestep)
+//   ds_episode_tokens_kernel  grid (episode x chunk of 16 agents, timestep <= max_steps), early exit past the episode's length
+// Records are kept timestep-major inside an episode (row0[k] - row0[0] + t * n_agents + a), as the neighbour search stages them; rows and
+// labels go to their absolute offsets, so a call may be handed a window of a longer scan (dataset_tokenizer.tokenize_episodes splits so).
+// ds_records_kernel / ds_tokens_kernel are not touched: a row body shared with them as one inlined function compiled them to other
+// instruction streams (section 33), so ds_episode_tokens_kernel restates the row of ds_tokens_kernel over next_action_token,
+// window_token and emit_record, with the goal read from the agent's own record.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int ds_episode_of(const int32_t *__restrict__ episodes, int k) { return episodes != nullptr ? episodes[k] : k; }
+
+__global__ __launch_bounds__(256) void ds_offsets_kernel(int n_sel, int n_agents, int max_steps, const int32_t *__restrict__ len,
+                                                         const uint8_t *__restrict__ keep, const int32_t *__restrict__ episodes,
+                                                         int64_t *__restrict__ row0)
+{
+    __shared__ int64_t part[256];
+    const int tid = threadIdx.x;
+    const int per = (n_sel + 255) / 256;
+    const int b = min(tid * per, n_sel), e = min(b + per, n_sel);
+    auto rows_of = [&](int k) -> int64_t {
+        const int ep = ds_episode_of(episodes, k);
+        if (keep != nullptr && keep[ep] == 0) return 0;
+        return (int64_t)n_agents * (min(max(len[ep], 0), max_steps) + 1);
+    };
+    int64_t sum = 0;
+    for (int k = b; k < e; k++) sum += rows_of(k);
+    part[tid] = sum;
+    __syncthreads();
+    int64_t at = 0;
+    for (int j = 0; j < tid; j++) at += part[j];
+    for (int k = b; k < e; k++) { row0[k] = at; at += rows_of(k); }
+    if (tid == 255) row0[n_sel] = at;                                                 // (thread 255's run ends at n_sel, or is empty behind it)
+}
+
+__global__ __launch_bounds__(256) void ds_paths_kernel(int n_sel, int n_agents, int max_steps, int H, int W, const int16_t *__restrict__ init,
+                                                       const int8_t *__restrict__ actions, const int32_t *__restrict__ episodes,
+                                                       const int64_t *__restrict__ row0, const uint16_t *__restrict__ allpairs,
+                                                       AgentRec *__restrict__ recs, int8_t *__restrict__ labels)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_sel * n_agents) return;
+    const int k = i / n_agents, a = i - k * n_agents;
+    const int64_t r0 = row0[k];
+    const int len1 = (int)((row0[k + 1] - r0) / n_agents);                           // len + 1, 0 = not kept
+    if (len1 == 0) return;
+    const int len = len1 - 1;
+    const size_t ea = (size_t)ds_episode_of(episodes, k) * n_agents + a;
+    const uint8_t *act = reinterpret_cast<const uint8_t *>(actions) + ea * max_steps;
+    auto action = [&](int t) -> int { return t < len && act[t] <= 4 ? act[t] : 0; }; // a byte outside 0..4 counts as a wait; one wait appended
+    // MOVES: 1 up, 2 down, 3 left, 4 right.  A logged path never leaves the frame; cells are clamped into it all the same, so that no
+    // init or action byte can move a table read out of bounds.
+    auto move = [&](int &r, int &c, int v) {
+        r = min(max(r + (v == 2) - (v == 1), 0), H - 1);
+        c = min(max(c + (v == 4) - (v == 3), 0), W - 1);
+    };
+    const int ir = min(max((int)init[2 * ea], 0), H - 1), ic = min(max((int)init[2 * ea + 1], 0), W - 1);
+    int gr = ir, gc = ic;                                                             // -> the path's last cell (:199)
+    int g = len + 1;                                                                  // -> index of the last move (gt_actions: len(a) if none)
+    for (int t = 0; t < len; t++) {
+        const int v = action(t);
+        if (v != 0) g = t;
+        move(gr, gc, v);
+    }
+    const uint16_t *dg = allpairs + (size_t)(gr * W + gc) * (H * W);                  // distance-to-goal field = a table row
+    int8_t *lab = labels + r0 + (int64_t)a * len1;
+    AgentRec r;
+    r.pr = (int16_t)ir; r.pc = (int16_t)ic; r.gr = (int16_t)gr; r.gc = (int16_t)gc;
+    r.org[0] = r.org[1] = 0;
+    AgentRec *rec_at = recs + (r0 - row0[0]) + a;                                     // (the workspace starts at this call's first row)
+    unsigned long long hist = (unsigned long long)TOK_N * 0x0101010101ull;            // before the episode: 'n' (:207)
+    for (int t = 0; t <= len; t++) {
+        if (t >= 1) {                                                                 // the move that led here; 'w' at the last step (:225-228)
+            int nr = r.pr, nc = r.pc;
+            move(nr, nc, action(t - 1));
+            const int dr = nr - r.pr, dc = nc - r.pc;
+            const int tok = t == len ? TOK_N + 1 : dr < 0 ? TOK_N + 2 : dr > 0 ? TOK_N + 3 : dc < 0 ? TOK_N + 4 : dc > 0 ? TOK_N + 5 : TOK_N + 1;
+            hist = (hist >> 8) | ((unsigned long long)tok << 32);
+            r.pr = (int16_t)nr; r.pc = (int16_t)nc;
+        }
+#pragma unroll
+        for (int s = 0; s < 5; s++) r.hist[s] = (uint8_t)(hist >> (8 * s));           // oldest first
+        r.next = (uint8_t)next_action_token(dg, H, W, r.pr, r.pc);                    // :230-243
+        rec_at[(int64_t)t * n_agents] = r;
+        lab[t] = (int8_t)(t > g ? 5 : action(t));
+    }
+}
+
+__global__ __launch_bounds__(256) void ds_episode_tokens_kernel(const AgentRec *__restrict__ recs, const uint16_t *__restrict__ allpairs,
+                                                                const int64_t *__restrict__ row0, int only_obstacles, int n_agents, int H,
+                                                                int W, int chunks_per_step, uint8_t *__restrict__ tokens)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint4 *srec = reinterpret_cast<uint4 *>(smem);                                        // [n_agents]
+    uint32_t *scand = reinterpret_cast<uint32_t *>(smem + (size_t)n_agents * 16);         // [4][kDsMaxCand]
+    uint8_t *srow = reinterpret_cast<uint8_t *>(scand + 4 * kDsMaxCand);                  // [4][272], token t at byte t + 1
+    const int k = blockIdx.x / chunks_per_step, chunk = blockIdx.x - k * chunks_per_step, t = blockIdx.y;
+    const int64_t r0 = row0[k];
+    const int len1 = (int)((row0[k + 1] - r0) / n_agents);
+    if (t >= len1) return;                                                                // block-uniform: not kept, or past the episode's end
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint4 *grec = reinterpret_cast<const uint4 *>(recs) + (r0 - row0[0]) + (int64_t)t * n_agents;
+    for (int i = tid; i < n_agents; i += 256) srec[i] = grec[i];
+    __syncthreads();
+    uint32_t *cand = scand + wave * kDsMaxCand;
+    uint8_t *row = srow + wave * 272;
+    const int cells = H * W;
+    for (int q = 0; q < kDsAgentsPerBlock / 4; q++) {
+        const int a = chunk * kDsAgentsPerBlock + wave + 4 * q;
+        if (a >= n_agents) break;                                                         // wave-uniform
+        const uint4 me = srec[a];
+        const int pr = (int16_t)(me.x & 0xffffu), pc = (int16_t)(me.x >> 16);
+        const int gr = (int16_t)(me.y & 0xffffu), gc = (int16_t)(me.y >> 16);               // the path's last cell (ds_paths_kernel)
+        const bool gok = gr >= 0 && gr < H && gc >= 0 && gc < W;
+        const uint16_t *dg = allpairs + (size_t)(gok ? gr * W + gc : 0) * cells;          // distance-to-goal field = a table row
+        const uint16_t *dm = allpairs + (size_t)(pr * W + pc) * cells;                    // distances from my own cell
+        if (lane < 34) reinterpret_cast<uint2 *>(row)[lane] = make_uint2(0x42424242u, 0x42424242u);
+        // --- window (cost2go.cpp:44-88) ---
+        int v[2];
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const int cell = lane + 64 * u, i = cell / kWin, j = cell - i * kWin;
+            const int rr = pr - kR + i, cc = pc - kR + j;
+            v[u] = (gok && cell < kWin * kWin && rr >= 0 && rr < H && cc >= 0 && cc < W) ? (int)dg[rr * W + cc] : kUnreach;
+        }
+        const int mid = __shfl(v[0], kR * kWin + kR);
+        // --- neighbours in the window, reachable from my cell, keyed (BFS distance, id) (:121-141) ---
+        int cnt = 0;
+        for (int b0 = 0; b0 < n_agents; b0 += 64) {
+            const int b = b0 + lane;
+            bool in = false;
+            uint32_t key = 0;
+            if (b < n_agents) {
+                const uint32_t bp = srec[b].x;
+                const int br = (int16_t)(bp & 0xffffu), bc = (int16_t)(bp >> 16);
+                if (abs(br - pr) <= kR && abs(bc - pc) <= kR && br >= 0 && br < H && bc >= 0 && bc < W) {
+                    const int d = dm[br * W + bc];
+                    in = d != kUnreach;
+                    key = ((uint32_t)d << 11) | (uint32_t)b;
+                }
+            }
+            const unsigned long long bm = __ballot(in);
+            if (in) {
+                const int at = cnt + __popcll(bm & ((1ull << lane) - 1ull));
+                if (at < kDsMaxCand) cand[at] = key;
+            }
+            cnt += __popcll(bm);
+        }
+        cnt = min(cnt, kDsMaxCand);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (only_obstacles) {                                                             // tokens of the integers 1 / 0
+            row[1 + lane] = (uint8_t)(kLimit + (v[0] == kUnreach ? 1 : 0));
+            if (lane + 64 < kWin * kWin) row[65 + lane] = (uint8_t)(kLimit + (v[1] == kUnreach ? 1 : 0));
+        } else {
+            row[1 + lane] = (uint8_t)window_token(v[0], mid);
+            if (lane + 64 < kWin * kWin) row[65 + lane] = (uint8_t)window_token(v[1], mid);
+        }
+        for (int c = lane; c < cnt; c += 64) {
+            const uint32_t key = cand[c];
+            int rank = 0;
+            for (int j = 0; j < cnt; j++) rank += (cand[j] < key) ? 1 : 0;
+            if (rank < kSlots) emit_record(row, rank, srec[key & 0x7ffu], me.x);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint32_t *row32 = reinterpret_cast<const uint32_t *>(row);
+        const uint32_t packed = __builtin_amdgcn_alignbyte(row32[lane + 1], row32[lane], 1);
+        reinterpret_cast<uint32_t *>(tokens + (r0 + (int64_t)a * len1 + t) * 256)[lane] = packed;   // episode: [agent][timestep][256]
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -1062,6 +1246,18 @@ struct mgpt_dataset {
     DeviceArena mem, recs_mem;          // allpairs; recs
 };
 
+// recs for at least `rows` records (both tokenize calls): grows only, and a growth waits for the stream's work on the old buffer
+static int ds_reserve_recs(mgpt_dataset *d, size_t rows, hipStream_t s)
+{
+    if (rows <= d->recs_cap) return MGPT_OK;
+    MGPT_HIP(hipStreamSynchronize(s));
+    d->recs_mem.release();
+    d->recs = nullptr; d->recs_cap = 0;
+    MGPT_HIP(d->recs_mem.alloc(&d->recs, rows * sizeof(AgentRec)));
+    d->recs_cap = rows;
+    return MGPT_OK;
+}
+
 extern "C" int mgpt_dataset_create(mgpt_dataset **out, const uint8_t *d_grid, int H, int W, void *stream)
 {
     MGPT_REQUIRE(out && d_grid, MGPT_ERR_ARG, "NULL argument");
@@ -1116,13 +1312,8 @@ extern "C" int mgpt_dataset_tokenize_ex(mgpt_dataset *d, int n_agents, int n_ste
     MGPT_REQUIRE(n_agents > 0 && n_agents <= 2048 && n_steps > 0, MGPT_ERR_ARG, "n_agents=%d n_steps=%d", n_agents, n_steps);
     hipStream_t s = (hipStream_t)stream;
     const size_t total = (size_t)n_agents * n_steps;
-    if (total > d->recs_cap) {
-        MGPT_HIP(hipStreamSynchronize(s));
-        d->recs_mem.release();
-        d->recs = nullptr; d->recs_cap = 0;
-        MGPT_HIP(d->recs_mem.alloc(&d->recs, total * sizeof(AgentRec)));
-        d->recs_cap = total;
-    }
+    const int rc = ds_reserve_recs(d, total, s);
+    if (rc != MGPT_OK) return rc;
     {
         ProfScope ps(P_TOK_UPDATE, s);
         hipLaunchKernelGGL(ds_records_kernel, dim3(cdiv((int)total, 256)), dim3(256), 0, s, d_paths, d_goals, n_agents, n_steps, d->H, d->W,
@@ -1138,3 +1329,47 @@ extern "C" int mgpt_dataset_tokenize_ex(mgpt_dataset *d, int n_agents, int n_ste
     return MGPT_OK;
 }
 
+
+extern "C" int mgpt_dataset_episode_offsets(int n_sel, int n_agents, int max_steps, const int32_t *d_len, const uint8_t *d_keep,
+                                            const int32_t *d_episodes, int64_t *d_row0, void *stream)
+{
+    MGPT_REQUIRE(d_len && d_row0, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(n_sel >= 0 && n_agents > 0 && n_agents <= 2048 && max_steps >= 0 && max_steps < 65535, MGPT_ERR_ARG,
+                 "n_sel=%d n_agents=%d max_steps=%d", n_sel, n_agents, max_steps);
+    hipLaunchKernelGGL(ds_offsets_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n_sel, n_agents, max_steps, d_len, d_keep, d_episodes,
+                       d_row0);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_dataset_tokenize_episodes(mgpt_dataset *d, int n_sel, int n_agents, int max_steps, const int16_t *d_init,
+                                              const int8_t *d_actions, const int32_t *d_len, const uint8_t *d_keep,
+                                              const int32_t *d_episodes, const int64_t *d_row0, int only_obstacles, uint8_t *d_tokens,
+                                              int8_t *d_labels, void *stream)
+{
+    MGPT_REQUIRE(d && d_init && d_len && d_row0 && (d_actions || max_steps == 0), MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(n_sel >= 0 && n_agents > 0 && n_agents <= 2048 && max_steps >= 0 && max_steps < 65535, MGPT_ERR_ARG,
+                 "n_sel=%d n_agents=%d max_steps=%d", n_sel, n_agents, max_steps);
+    if (n_sel == 0) return MGPT_OK;
+    MGPT_REQUIRE(d_tokens && d_labels, MGPT_ERR_ARG, "NULL argument");
+    // (d_len and d_keep were read by mgpt_dataset_episode_offsets: the kernels here take every length from d_row0)
+    const int chunks = cdiv(n_agents, kDsAgentsPerBlock);
+    const int64_t rows_max = (int64_t)n_sel * n_agents * (max_steps + 1);          // the workspace is sized for no skipped and no short episode
+    MGPT_REQUIRE(rows_max < ((int64_t)1 << 31) && (int64_t)n_sel * chunks < ((int64_t)1 << 31), MGPT_ERR_UNSUPPORTED,
+                 "n_sel=%d episodes of up to %d x %d rows in one call: split the selection", n_sel, n_agents, max_steps + 1);
+    hipStream_t s = (hipStream_t)stream;
+    int rc = ds_reserve_recs(d, (size_t)rows_max, s);
+    if (rc != MGPT_OK) return rc;
+    {
+        ProfScope ps(P_DS_PATHS, s);
+        hipLaunchKernelGGL(ds_paths_kernel, dim3(cdiv(n_sel * n_agents, 256)), dim3(256), 0, s, n_sel, n_agents, max_steps, d->H, d->W, d_init,
+                           d_actions, d_episodes, d_row0, d->allpairs, d->recs, d_labels);
+        MGPT_LAUNCH_CHECK();
+    }
+    const size_t smem = (size_t)n_agents * 16 + 4 * kDsMaxCand * 4 + 4 * 272;
+    ProfScope ps(P_DS_EPISODE_TOKENS, s);
+    hipLaunchKernelGGL(ds_episode_tokens_kernel, dim3(n_sel * chunks, max_steps + 1), dim3(256), smem, s, d->recs, d->allpairs, d_row0,
+                       only_obstacles ? 1 : 0, n_agents, d->H, d->W, chunks, d_tokens);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}

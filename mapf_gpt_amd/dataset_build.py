@@ -10,6 +10,11 @@ prints one JSON line per chunk (per-file counters, picks, shard sizes) and write
 POGEMA, which is not part of this repository; `python -m mapf_gpt_amd.expert` writes a log of the same shape with the PIBT expert
 (PIBT.json); `split_by_map` is its step 2.
 
+`EpisodeStore` + `build_shards_from_store` are the same steps 2-3 with no log file: the store keeps the expert's
+device logs as the batches are planned (evaluation(on_expert_batch=store.append)), every map's episodes become rows in one
+dataset_tokenizer.tokenize_episodes call per (map, batch), and from there on the code is the one below.  `python -m mapf_gpt_amd.expert
+--shards` and `python -m mapf_gpt_amd.ddg --shards` write shards this way.
+
 Shuffles draw from one np.random.Generator(PCG64(seed)) in a fixed order (per file in processing order, then the whole chunk);
 the reference draws from numpy's global stream, so orders differ from it seed for seed while the sets of rows do not.
 """
@@ -25,6 +30,7 @@ import torch
 from . import _lib
 
 STAT_NAMES = ("discarded", "duplicates", "kept")          # generate_dataset.py:96 prints these three, then actions_made
+METRIC_CSR = 0                                             # env.METRIC_KEYS: the column of CSR in BatchedExpert.metrics()
 
 
 def _i64_dev(n, device):
@@ -225,6 +231,20 @@ def split_by_map(result_json, out_dir=None):
 # ---------------------------------------------------------------------------------------------------------------------
 # the pipeline
 # ---------------------------------------------------------------------------------------------------------------------
+def _balance_and_shuffle(rows, labels, file_name, rng, device):
+    """What follows the tokenizer for one file's rows: drop duplicates, balance, shuffle (one rng.permutation).
+    -> (rows uint8 [kept, 256], labels int8 [kept]) on the device; stats."""
+    n = int(rows.shape[0])
+    stats = {"file": file_name, "samples": n, "discarded": 0, "duplicates": 0, "kept": 0, "actions_made": [0] * 6}
+    if n == 0:
+        return rows, labels, stats
+    index, labels_out, st = DedupSet(n, device=device).filter_and_balance_index(rows, labels)
+    stats.update(st)
+    perm = torch.as_tensor(rng.permutation(st["kept"])).to(rows.device)       # step 3: the index list, not the rows, is shuffled
+    x, y = gather_rows(rows, labels_out, index[perm])                        # compaction and shuffle in one gather
+    return x, y, stats
+
+
 def _process_file(path, maps, rng, device, tokenize):
     """One log file -> (rows uint8 [kept, 256], labels int8 [kept]) on the device, balanced and in shuffled order; stats."""
     from .dataset_tokenizer import InputParameters, ObservationGenerator
@@ -237,27 +257,18 @@ def _process_file(path, maps, rng, device, tokenize):
         inputs, gts = gen.generate_observations(0, len(data))
         x = np.stack(inputs).view(np.uint8) if inputs else np.zeros((0, 256), np.uint8)
         rows, labels = torch.as_tensor(x).to(device), torch.as_tensor(np.asarray(gts, dtype=np.int8)).to(device)
-    n = int(rows.shape[0])
-    stats = {"file": os.path.basename(path), "samples": n, "discarded": 0, "duplicates": 0, "kept": 0, "actions_made": [0] * 6}
-    if n == 0:
-        return rows, labels, stats
-    index, labels_out, st = DedupSet(n, device=device).filter_and_balance_index(rows, labels)
-    stats.update(st)
-    perm = torch.as_tensor(rng.permutation(st["kept"])).to(rows.device)       # step 3: the index list, not the rows, is shuffled
-    x, y = gather_rows(rows, labels_out, index[perm])                        # compaction and shuffle in one gather
-    return x, y, stats
+    return _balance_and_shuffle(rows, labels, os.path.basename(path), rng, device)
 
 
-def build_chunk(maps_mazes, maps_random, maze_files, random_files, out_prefix, desired_size, maze_ratio=0.9, files_per_chunk=10,
-                rng=None, device="cuda", tokenize="device"):
-    """= process_files (:143-212) for one chunk.  -> the chunk's report (what the CLI prints)."""
-    rng = rng if rng is not None else np.random.Generator(np.random.PCG64(0))
+def _assemble_chunk(sources, out_prefix, desired_size, maze_ratio, files_per_chunk, rng):
+    """= process_files (:143-212) for one chunk over sources = ((files, process, kind) for mazes, then random): process(file) ->
+    (rows, labels, stats) balanced and shuffled, drawing from rng.  -> the chunk's report."""
     maze_desired = int(desired_size * maze_ratio)
     random_desired = desired_size - maze_desired
     report = {"out": out_prefix, "files": [], "shards": []}
     parts = []
-    for maps, files, want, kind in ((maps_mazes, maze_files, maze_desired, "mazes"), (maps_random, random_files, random_desired, "random")):
-        done = [_process_file(f, maps, rng, device, tokenize) for f in files]
+    for (files, process, kind), want in zip(sources, (maze_desired, random_desired)):
+        done = [process(f) for f in files]
         picks, _ = elements_to_pick([int(x.shape[0]) for x, _, _ in done], want)
         for (x, y, st), p in zip(done, picks):
             st.update(kind=kind, picked=p)
@@ -280,20 +291,124 @@ def build_chunk(maps_mazes, maps_random, maze_files, random_files, out_prefix, d
     return report
 
 
+def build_chunk(maps_mazes, maps_random, maze_files, random_files, out_prefix, desired_size, maze_ratio=0.9, files_per_chunk=10,
+                rng=None, device="cuda", tokenize="device"):
+    """= process_files (:143-212) for one chunk.  -> the chunk's report (what the CLI prints)."""
+    rng = rng if rng is not None else np.random.Generator(np.random.PCG64(0))
+    sources = ((maze_files, lambda f: _process_file(f, maps_mazes, rng, device, tokenize), "mazes"),
+               (random_files, lambda f: _process_file(f, maps_random, rng, device, tokenize), "random"))
+    return _assemble_chunk(sources, out_prefix, desired_size, maze_ratio, files_per_chunk, rng)
+
+
+def _chunk_plan(files, out_prefix, num_chunks):
+    """generate_chunks (:246-256): [(maze files, random files, output prefix)] of every chunk."""
+    maze_files, random_files = files_by_type(list(files))
+    if num_chunks == 1:
+        return [(maze_files, random_files, out_prefix)]
+    mz, rd = chunk_groups(maze_files, num_chunks), chunk_groups(random_files, num_chunks)
+    return [(mz[c], rd[c], f"{out_prefix}_chunk_{c}") for c in range(num_chunks)]
+
+
 def build_shards(maps_mazes, maps_random, log_files, out_prefix, desired_size, maze_ratio=0.9, files_per_chunk=10, num_chunks=1, seed=0,
                  device="cuda", tokenize="device"):
     """Steps 3 of generate_dataset.py (generate_chunks :246-256) over per-map log files.  desired_size is per chunk, as in the
     reference.  One chunk writes <out_prefix>_part_<i>.arrow; with num_chunks > 1, chunk c writes <out_prefix>_chunk_<c>_part_<i>.arrow
     (the reference's chunk_<c>).  -> list of chunk reports."""
-    maze_files, random_files = files_by_type(list(log_files))
     rng = np.random.Generator(np.random.PCG64(seed))
-    if num_chunks == 1:
-        groups = [(maze_files, random_files, out_prefix)]
-    else:
-        mz, rd = chunk_groups(maze_files, num_chunks), chunk_groups(random_files, num_chunks)
-        groups = [(mz[c], rd[c], f"{out_prefix}_chunk_{c}") for c in range(num_chunks)]
     return [build_chunk(maps_mazes, maps_random, m, r, out, desired_size, maze_ratio, files_per_chunk, rng, device, tokenize)
-            for m, r, out in groups]
+            for m, r, out in _chunk_plan(log_files, out_prefix, num_chunks)]
+
+
+class EpisodeStore:
+    """The expert's episodes, kept where they were planned, until the shards are built: append(info) takes one batch of
+    evaluation(on_expert_batch=...) and keeps its device log once -- first cells, made actions, lengths, CSR and the frame grids, about one
+    byte per agent-step -- plus, per map name, the batch's episode indices in log order.  No row exists until rows_of(map) is asked.
+    The episodes of a map name in order (batch, then index) are the records of split_by_map's <map_name>.json in order."""
+
+    def __init__(self, device="cuda", tables=None, mask_cost2go=False):
+        from .dataset_tokenizer import TableCache
+        self.device = torch.device(device)
+        self.tables = tables if tables is not None else TableCache(device=self.device)
+        self.mask_cost2go = bool(mask_cost2go)
+        self.batches = []                                    # {init, actions, lengths, solved, grids (host), n_agents, max_steps}
+        self.per_map = {}                                    # map name -> [(batch index, [episode indices])], in log order
+
+    @staticmethod
+    def group_by_map(run_keys):
+        """{map_name: [indices into run_keys]} in order of first appearance, indices increasing: split_by_map on one batch."""
+        out = {}
+        for k, key in enumerate(run_keys):
+            out.setdefault(key["map_name"], []).append(k)
+        return out
+
+    def append(self, info):
+        if info.get("on_target", "nothing") != "nothing":
+            raise NotImplementedError("EpisodeStore keeps no per-step goals: lifelong (on_target='restart') episodes go through the JSON log")
+        ex = info["expert"]
+        log, lens = ex.log()
+        self.add_batch(info["run_keys"], info["pos"], log, lens, ex.metrics()[:, METRIC_CSR] >= 1, info["grids"])
+
+    def add_batch(self, run_keys, init, actions, lengths, solved, grids):
+        """One batch given as tensors (append() reads them off a BatchedExpert; mapf_gpt_amd.ddg hands in the teacher's): run_keys
+        [n] dicts with `map_name`; init [n, n_agents, 2]; actions int8 [n, n_agents, max_steps]; lengths [n]; solved bool [n] (CSR >= 1);
+        grids [n or 1, H, W], the frame every episode ran in."""
+        actions = torch.as_tensor(actions).to(self.device, torch.int8).contiguous()
+        n = int(actions.shape[0])
+        assert len(run_keys) == n, "one run key per episode"
+        grids = np.asarray(grids.cpu() if torch.is_tensor(grids) else grids)
+        self.batches.append({"init": torch.as_tensor(init).to(self.device, torch.int16).reshape(n, -1, 2).contiguous(),
+                             "actions": actions, "lengths": torch.as_tensor(lengths).to(self.device, torch.int32).contiguous(),
+                             "solved": (torch.as_tensor(solved).to(self.device) != 0).to(torch.uint8).contiguous(),
+                             "grids": grids[None] if grids.ndim == 2 else grids})
+        for name, idx in self.group_by_map(run_keys).items():
+            self.per_map.setdefault(name, []).append((len(self.batches) - 1, idx))
+
+    def map_names(self):
+        return list(self.per_map)
+
+    def episodes(self):
+        return sum(int(b["actions"].shape[0]) for b in self.batches)
+
+    def solved_rows(self):
+        """(solved episodes, their rows) over the whole store: one reduction per batch on the device."""
+        ep = rows = 0
+        for b in self.batches:
+            k = b["solved"] != 0
+            per = (b["lengths"].clamp(0, b["actions"].shape[2]).to(torch.int64) + 1) * int(b["actions"].shape[1])
+            e, r = torch.stack([k.sum(), (per * k).sum()]).cpu().tolist()
+            ep, rows = ep + e, rows + r
+        return ep, rows
+
+    def rows_of(self, map_name):
+        """-> (rows uint8 [N, 256], labels int8 [N]) on the device: the solved episodes of the map in log order, one
+        tokenize_episodes call per batch that has some -- what generate_observations_device makes of <map_name>.json."""
+        from .dataset_tokenizer import tokenize_episodes
+        xs, ys = [], []
+        for bi, idx in self.per_map.get(map_name, []):
+            b = self.batches[bi]
+            table = self.tables.get(b["grids"][idx[0] % len(b["grids"])])
+            x, y, _ = tokenize_episodes(table, b["init"], b["actions"], b["lengths"], b["solved"], idx, self.mask_cost2go)
+            xs.append(x)
+            ys.append(y)
+        if not xs:
+            return torch.empty((0, 256), dtype=torch.uint8, device=self.device), torch.empty((0,), dtype=torch.int8, device=self.device)
+        return (xs[0], ys[0]) if len(xs) == 1 else (torch.cat(xs), torch.cat(ys))
+
+
+def build_shards_from_store(store, out_prefix, desired_size, maze_ratio=0.9, files_per_chunk=10, num_chunks=1, seed=0):
+    """build_shards over an EpisodeStore: every map name stands for the file <map_name>.json that split_by_map would have written
+    (`mazes` / `random` in the name decides the kind, the names are sorted as files_by_type sorts, chunks are cut as chunk_groups cuts),
+    its rows come from store.rows_of, and everything after the tokenizer is build_shards' own code drawing from the one rng in the same
+    order -- the same .arrow bytes for the same seed.  -> list of chunk reports."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    files = {f"{name}.json": name for name in store.map_names()}
+
+    def process(f):
+        rows, labels = store.rows_of(files[f])
+        return _balance_and_shuffle(rows, labels, f, rng, store.device)
+
+    return [_assemble_chunk(((m, process, "mazes"), (r, process, "random")), out, desired_size, maze_ratio, files_per_chunk, rng)
+            for m, r, out in _chunk_plan(list(files), out_prefix, num_chunks)]
 
 
 def main(argv=None):

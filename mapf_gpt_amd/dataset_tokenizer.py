@@ -12,7 +12,13 @@ Lifelong logs ("global_lifelong_targets_xy", :55-60, 143-153) and the `mask_cost
 device like the rest; the other three mask_* fields are carried by `InputParameters` but, as in the reference's dataset
 pipeline (whose C++ encoder ignores them), only the python `Encoder.mask` applies them (tokenizer.py:104-138; restated for the tests in oracle/dataset_encoder.py).
 Not supported: cost2go_radius != 5.
+
+Batched route: `tokenize_episodes(table, init, actions, lengths, ...)` turns a whole batch of episodes of one map --
+the expert's device log as BatchedExpert.log() returns it -- into (rows, labels, row0) on the device in one call, with no per-episode
+host work; `TableCache` keeps the maps' all-pairs tables by grid bytes.  BatchedExpert.dataset_rows and dataset_build.EpisodeStore sit on
+top of the two.  `episode_row_offsets` / `episode_labels` restate the offsets and the label rule in numpy (tests, tools).
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -105,6 +111,126 @@ def gt_actions(made_actions):
         goal_t = nz[-1] if nz else len(a)
         out.append([5 if t > goal_t else a[t] for t in range(len(a))])
     return out
+
+
+def episode_row_offsets(lengths, n_agents, max_steps, keep=None, episodes=None):
+    """numpy restatement of mgpt_dataset_episode_offsets: int64 [n_sel + 1], the exclusive scan of
+    rows(e) = keep[e] ? n_agents * (clamp(len[e], 0, max_steps) + 1) : 0 over `episodes` (None: all, in order)."""
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    sel = np.arange(len(lengths)) if episodes is None else np.asarray(episodes, dtype=np.int64).reshape(-1)
+    rows = int(n_agents) * (np.clip(lengths[sel], 0, int(max_steps)) + 1)
+    if keep is not None:
+        rows = np.where(np.asarray(keep).reshape(-1)[sel] != 0, rows, 0)
+    return np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+
+
+def episode_labels(actions, length):
+    """numpy restatement of the device's label rule = gt_actions on one episode's log: actions int8 [n_agents, >= length] (bytes outside
+    0..4 count as 0) -> int8 [n_agents, length + 1]: with a = actions[:length] + [0] and g the index of a's last non-zero entry
+    (length + 1 if none), 5 where t > g, else a[t]."""
+    a = np.asarray(actions).astype(np.int64)[:, :int(length)]
+    a = np.where((a >= 0) & (a <= 4), a, 0)
+    a = np.concatenate([a, np.zeros((a.shape[0], 1), np.int64)], axis=1)
+    t = np.arange(a.shape[1])
+    g = np.where((a != 0).any(1), ((a != 0) * t).max(1), a.shape[1])
+    return np.where(t[None, :] > g[:, None], 5, a).astype(np.int8)
+
+
+def tokenize_episodes(table, init, actions, lengths, keep=None, episodes=None, mask_cost2go=False, max_rows_per_call=1 << 22):
+    """A batch of logged episodes of one map -> (rows uint8 [N, 256], labels int8 [N], row0 int64 [n_sel + 1]), device tensors.
+    table: the map's MapTable (the episodes' frame); init int16 [n_batch, n_agents, 2] first cells in its coordinates; actions int8
+    [n_batch, n_agents, max_steps] and lengths int32 [n_batch] as BatchedExpert.log() returns them; keep: uint8 / bool [n_batch] or
+    None, 0 = the episode gives no rows; episodes: the selected episodes in output order (list, array or tensor of indices below
+    n_batch) or None for all.  Selected episode k owns rows [row0[k], row0[k + 1]): what MapTable.tokenize makes of its paths, agent-major
+    then timestep 0 .. len, with the labels of gt_actions.  The one value read back is row0[-1], to size the output (with `episodes` on
+    the device, a flag that every index is in range travels with it).  The selection is tokenized in pieces of at most max_rows_per_call //
+    (n_agents * (max_steps + 1)) episodes (at least one), which bounds the library's workspace; the result does not depend on the pieces."""
+    dev = table.device
+    init = torch.as_tensor(init).to(dev, torch.int16).contiguous()
+    actions = torch.as_tensor(actions).to(dev, torch.int8).contiguous()
+    lengths = torch.as_tensor(lengths).to(dev, torch.int32).contiguous()
+    assert actions.dim() == 3 and tuple(init.shape) == tuple(actions.shape[:2]) + (2,) and tuple(lengths.shape) == (actions.shape[0],), \
+        "init [n_batch, n_agents, 2], actions [n_batch, n_agents, max_steps], lengths [n_batch]"
+    n_batch, n_agents, max_steps = (int(v) for v in actions.shape)
+    if keep is not None:
+        keep = (torch.as_tensor(keep).to(dev) != 0).to(torch.uint8).contiguous()
+        assert tuple(keep.shape) == (n_batch,), "keep [n_batch]"
+    flag = None
+    if episodes is None:
+        n_sel = n_batch
+    elif torch.is_tensor(episodes) and episodes.is_cuda:
+        raw = episodes.to(dev, torch.int64).reshape(-1)
+        n_sel = int(raw.shape[0])
+        episodes = raw.clamp(0, max(n_batch - 1, 0)).to(torch.int32).contiguous()
+        flag = (episodes != raw).any().to(torch.int64).reshape(1)
+    else:
+        host = np.asarray(episodes.cpu() if torch.is_tensor(episodes) else episodes, dtype=np.int64).reshape(-1)
+        if len(host) and (host.min() < 0 or host.max() >= n_batch):
+            raise IndexError(f"episodes outside 0 .. {n_batch - 1}")
+        n_sel = len(host)
+        episodes = torch.as_tensor(host.astype(np.int32)).to(dev)
+    row0 = torch.empty((n_sel + 1,), dtype=torch.int64, device=dev)
+    L = _lib.lib()
+    with _lib.on_device(dev):
+        s = _lib.stream_ptr()
+        _lib.check(L.mgpt_dataset_episode_offsets(n_sel, n_agents, max_steps, _lib.ptr(lengths), _lib.ptr(keep) if keep is not None else None,
+                                                  _lib.ptr(episodes) if episodes is not None else None, _lib.ptr(row0), s))
+        back = (row0[-1:] if flag is None else torch.cat([row0[-1:], flag])).cpu().tolist()
+        if flag is not None and back[1]:
+            raise IndexError(f"episodes outside 0 .. {n_batch - 1}")
+        n_rows = int(back[0])
+        rows = torch.empty((n_rows, 256), dtype=torch.uint8, device=dev)
+        labels = torch.empty((n_rows,), dtype=torch.int8, device=dev)
+        if n_rows == 0:
+            return rows, labels, row0
+        per = max(1, int(max_rows_per_call) // (n_agents * (max_steps + 1)))
+        if per < n_sel and episodes is None:                 # a piece names its episodes: k of a window is not the episode's index
+            episodes = torch.arange(n_sel, dtype=torch.int32, device=dev)
+        for k0 in range(0, n_sel, per):
+            k1 = min(k0 + per, n_sel)
+            _lib.check(L.mgpt_dataset_tokenize_episodes(table._h, k1 - k0, n_agents, max_steps, _lib.ptr(init), _lib.ptr(actions),
+                                                        _lib.ptr(lengths), _lib.ptr(keep) if keep is not None else None,
+                                                        ctypes.c_void_p(episodes.data_ptr() + 4 * k0) if episodes is not None else None,
+                                                        ctypes.c_void_p(row0.data_ptr() + 8 * k0), 1 if mask_cost2go else 0,
+                                                        _lib.ptr(rows), _lib.ptr(labels), s))
+    return rows, labels, row0
+
+
+class TableCache:
+    """grid bytes -> MapTable, within a byte budget (a table is 2 * (H * W) ** 2 bytes), oldest first out.  The key is the frame grid
+    itself, as the expert holds it -- not a map name or string: a frame larger than the map's own padded grid only adds blocked cells,
+    which the table and the window both treat as unreachable, so the rows are those of the map's own grid.
+    The newest table stays even when it alone exceeds the budget.  make(grid, device) builds a table (tests count the builds)."""
+
+    def __init__(self, budget_bytes=8 << 30, device="cuda", make=None):
+        self.budget, self.device = int(budget_bytes), device
+        self._make = make if make is not None else MapTable
+        self._tables = collections.OrderedDict()             # key -> (table, bytes), in order of creation
+        self.bytes = self.builds = 0
+
+    @staticmethod
+    def key(grid):
+        g = np.ascontiguousarray(np.asarray(grid.cpu() if torch.is_tensor(grid) else grid) != 0, dtype=np.uint8)
+        assert g.ndim == 2, "grid [H, W]"
+        return g.shape + (g.tobytes(),), g
+
+    def __len__(self):
+        return len(self._tables)
+
+    def get(self, grid):
+        key, g = self.key(grid)
+        hit = self._tables.get(key)
+        if hit is not None:
+            return hit[0]
+        size = 2 * (g.shape[0] * g.shape[1]) ** 2
+        while self._tables and self.bytes + size > self.budget:
+            _, (_, freed) = self._tables.popitem(last=False)
+            self.bytes -= freed
+        table = self._make(g, self.device)
+        self._tables[key] = (table, size)
+        self.bytes += size
+        self.builds += 1
+        return table
 
 
 class ObservationGenerator:

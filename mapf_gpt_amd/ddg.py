@@ -7,6 +7,7 @@ fine-tuned on.  The generator is not in the reference; what runs here is this pr
 
     python -m mapf_gpt_amd.ddg --weights CKPT --config CONFIG.yaml [--maps MAPS.yaml] --out DIR
         [--every 16 --max-iters 1024 --refine-rounds 8 --shield pibt --precision P --seed 0]       # writes DIR/DDG.json
+    python -m mapf_gpt_amd.ddg ... --shards PREFIX --desired-size N [--maze-ratio --files-per-chunk --num-chunks --shard-seed]
 
 Per policy batch (on_target "nothing" only: a lifelong episode has no joint goal, hence no cost-to-go), with K = `every`, T the recorded
 steps and J = T // K + 1:
@@ -25,6 +26,10 @@ steps and J = T // K + 1:
 DIR/DDG.json is what dataset_build.split_by_map and `dataset_build --logs` take where the reference has LaCAM.json; the loop is
 ddg -> split_by_map -> dataset_build -> `training --init CKPT --dropout 0.1`.  The CLI prints one JSON line: episodes, snapshots probed,
 picked, teacher_solved, rows (dataset rows of the solved teacher episodes), delta_mean / delta_max of the picks, seconds per stage.
+
+With --shards the teacher's episodes go from its device log straight to .arrow shards (dataset_build.EpisodeStore /
+build_shards_from_store): no DDG.json between the teacher and training unless --out asks for it too; the line
+gains `chunks`, the chunk reports.  collect_from_trajectory(rows=True) hands the same rows back as device tensors.
 """
 import argparse
 import json
@@ -91,9 +96,10 @@ def segments(ids, max_instances):
 
 
 # ---- the device stages -------------------------------------------------------------------------------------------------------------
-def _run_expert(grids, grid_of, ids, pos, goal, steps, kw, seed, max_instances, device, keys=None, algorithm=None):
+def _run_expert(grids, grid_of, ids, pos, goal, steps, kw, seed, max_instances, device, keys=None, algorithm=None, rows=None, store=None):
     """One expert episode per entry: entry e plans on grids[grid_of[e]] under global id ids[e] from (pos[e], goal[e]).
-    -> (metrics float32 [n, 6] device tensor, records or None)."""
+    -> (metrics float32 [n, 6] device tensor, records or None).  rows: a list that receives every entry's (rows, labels) device
+    tensors (empty ones for an unsolved episode), from the expert's device log; store: an EpisodeStore that takes every context's log."""
     from .expert import BatchedExpert
     grids = np.asarray(grids)
     if grids.ndim == 2:
@@ -107,6 +113,16 @@ def _run_expert(grids, grid_of, ids, pos, goal, steps, kw, seed, max_instances, 
         metrics.append(ex.metrics())
         if keys is not None:
             records.extend(ex.records(keys[a:b], pos[a:b], algorithm=algorithm))
+        if rows is not None:
+            per = [None] * (b - a)
+            for inst, x, y, row0 in ex.dataset_rows(pos[a:b], tables=store.tables if store is not None else None, offsets=True):
+                r0 = row0.cpu().tolist()
+                for k, i in enumerate(inst):
+                    per[int(i)] = (x[r0[k]:r0[k + 1]], y[r0[k]:r0[k + 1]])
+            rows.extend(per)
+        if store is not None:
+            log, lens = ex.log()
+            store.add_batch(keys[a:b], pos[a:b], log, lens, metrics[-1][:, 0] >= 1, g)
     n = len(ids)
     m = torch.cat(metrics) if metrics else torch.zeros((0, 6), dtype=torch.float32, device=device)
     assert m.shape[0] == n
@@ -115,13 +131,16 @@ def _run_expert(grids, grid_of, ids, pos, goal, steps, kw, seed, max_instances, 
 
 def collect_from_trajectory(grids, pos_traj, lengths, goal, run_keys, every=16, probe=None, teacher=None, probe_steps=None,
                             teacher_steps=None, min_delta=None, seed=0, max_teacher_instances=4096, global_ids=None,
-                            max_episode_steps=None, on_target="nothing", device="cuda"):
+                            max_episode_steps=None, on_target="nothing", device="cuda", rows=False, store=None):
     """Probe, pick and teacher on a recorded batch.  grids [n_grids, H, W] (instance i lives on grid i % n_grids, as in BatchedRunner),
     pos_traj integer [T + 1, n_inst, n_agents, 2] and lengths [n_inst] as BatchedRunner.trajectory() gives them (tensors or arrays),
     goal [n_inst, n_agents, 2], run_keys: the env_grid_search dict of every instance; global_ids: every instance's g (default 0, 1, ..).
     probe_steps / teacher_steps default to max_episode_steps, and that to T.
     -> dict: records (the teacher's, in instance order), valid / solved / cost [n_inst, J], delta / cand [n_inst, J - 1], picked, j, dmax
-    [n_inst] (numpy), teacher_metrics float32 [picked, 6], probed (snapshots run), seconds {probe, pick, teacher}."""
+    [n_inst] (numpy), teacher_metrics float32 [picked, 6], probed (snapshots run), seconds {probe, pick, teacher}.
+    rows=True: the dict also has `rows` uint8 [N, 256] and `labels` int8 [N], device tensors: the rows of the solved teacher episodes in
+    record order, from the teacher's device log (what the dataset tokenizer makes of `records`).  store: a dataset_build.EpisodeStore
+    that takes the teacher's logs, one batch per expert context, in global-id order (= record order when global_ids ascend)."""
     if on_target != "nothing":
         raise NotImplementedError(f"on_target={on_target!r}: delta data needs a cost-to-go, and a lifelong episode has no joint goal to "
                                   "measure one against")
@@ -183,11 +202,17 @@ def collect_from_trajectory(grids, pos_traj, lengths, goal, run_keys, every=16, 
         key["ddg_step"], key["ddg_delta"] = int(j_h[i]) * K, int(d_h[i])
         keys.append(key)
     sel = torch.as_tensor(p_h, device=dev)
+    ep_rows = [] if rows else None
     tm, records = _run_expert(grids, p_h % n_grids, gids[p_h], snaps[sel, jstar[sel]], goal[sel], teacher_steps, teacher, seed,
-                              max_teacher_instances, dev, keys=keys, algorithm="DDG")
+                              max_teacher_instances, dev, keys=keys, algorithm="DDG", rows=ep_rows, store=store)
     back = np.argsort(p_h, kind="stable")                               # from global-id order back to instance order
+    extra = {}
+    if rows:
+        xs = [ep_rows[k][0] for k in back] + [torch.empty((0, 256), dtype=torch.uint8, device=dev)]
+        ys = [ep_rows[k][1] for k in back] + [torch.empty((0,), dtype=torch.int8, device=dev)]
+        extra = {"rows": torch.cat(xs), "labels": torch.cat(ys)}
     t3 = sync()
-    return {"records": [records[k] for k in back], "valid": valid.cpu().numpy(), "solved": solved.cpu().numpy(), "cost": cost.cpu().numpy(),
+    return {**extra, "records": [records[k] for k in back], "valid": valid.cpu().numpy(), "solved": solved.cpu().numpy(), "cost": cost.cpu().numpy(),
             "delta": delta.cpu().numpy(), "cand": cand.cpu().numpy(), "picked": picked.cpu().numpy(), "j": j_h, "dmax": d_h,
             "teacher_metrics": tm.cpu().numpy()[back], "probed": int(len(ids)), "every": K, "J": J,
             "seconds": {"probe": t1 - t0, "pick": t2 - t1, "teacher": t3 - t2}}
@@ -214,7 +239,13 @@ def main(argv=None):
     ap.add_argument("--weights", required=True, help="the policy's checkpoint (or synthetic:<shape>[:seed])")
     ap.add_argument("--config", required=True, help="evaluation YAML (its environment: block is run)")
     ap.add_argument("--maps", default=None, help="maps.yaml ({name: map string}) registered on top of the built-in maps")
-    ap.add_argument("--out", required=True, help="output directory")
+    ap.add_argument("--out", default=None, help="output directory (optional with --shards)")
+    ap.add_argument("--shards", default=None, metavar="PREFIX", help="write .arrow shards from the teacher's device log")
+    ap.add_argument("--desired-size", type=int, default=None, help="--shards: rows per chunk")
+    ap.add_argument("--maze-ratio", type=float, default=0.9)
+    ap.add_argument("--files-per-chunk", type=int, default=10)
+    ap.add_argument("--num-chunks", type=int, default=1)
+    ap.add_argument("--shard-seed", type=int, default=0, help="--shards: seed of the shuffles (dataset_build --seed)")
     ap.add_argument("--every", type=int, default=16, help="steps between two snapshots")
     ap.add_argument("--max-iters", type=int, default=TEACHER["max_iters"], help="iterations of the teacher's search per instance")
     ap.add_argument("--refine-rounds", type=int, default=TEACHER["refine_rounds"], help="rounds of the teacher's refinement pass (0 = off)")
@@ -224,11 +255,19 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda")
     a = ap.parse_args(argv)
+    if a.shards is None and a.out is None:
+        ap.error("one of --out and --shards is required")
+    if a.shards is not None and a.desired_size is None:
+        ap.error("--shards needs --desired-size")
     from . import evaluation as ev
     cfg = ev.load_yaml(a.config)
     reg = ev.MapRegistry()
     if a.maps:
         reg.register_maps(ev.load_yaml(a.maps))
+    store = None
+    if a.shards is not None:
+        from .dataset_build import EpisodeStore, build_shards_from_store
+        store = EpisodeStore(device=a.device)
     algo = {"name": "MAPF-GPT", "path_to_weights": a.weights, "seed": a.seed, "device": a.device}
     if a.shield:
         algo["shield"] = a.shield
@@ -242,7 +281,7 @@ def main(argv=None):
 
     def on_batch(info):
         out = collect(info["runner"], info["grids"], info["goal"], info["run_keys"], every=a.every, teacher=teacher, seed=a.seed,
-                      global_ids=info["mine"], max_episode_steps=info["max_steps"], on_target=info["on_target"])
+                      global_ids=info["mine"], max_episode_steps=info["max_steps"], on_target=info["on_target"], store=store)
         records.extend(out["records"])
         deltas.extend(int(d) for d, p in zip(out["dmax"], out["picked"]) if p)
         line["snapshots"] += out["probed"]
@@ -252,12 +291,19 @@ def main(argv=None):
     t0 = time.perf_counter()
     res = ev.evaluation(cfg, registry=reg, precision=a.precision, print_fn=lambda *_: None, record=True, on_batch=on_batch)
     secs["rollout"] = time.perf_counter() - t0 - secs["probe"] - secs["pick"] - secs["teacher"]
-    os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, "DDG.json"), "w") as f:
-        json.dump(records, f, indent=1)
+    if a.out is not None:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "DDG.json"), "w") as f:
+            json.dump(records, f, indent=1)
     line.update(episodes=len(res), picked=len(records), teacher_solved=sum(1 for r in records if r["metrics"]["CSR"] >= 1),
                 rows=dataset_rows(records), delta_mean=round(float(np.mean(deltas)), 3) if deltas else 0.0,
                 delta_max=max(deltas) if deltas else 0, seconds={k: round(v, 3) for k, v in secs.items()})
+    if store is not None:
+        t1 = time.perf_counter()
+        if os.path.dirname(a.shards):
+            os.makedirs(os.path.dirname(a.shards), exist_ok=True)
+        line["chunks"] = build_shards_from_store(store, a.shards, a.desired_size, a.maze_ratio, a.files_per_chunk, a.num_chunks, a.shard_seed)
+        line["seconds"]["shards"] = round(time.perf_counter() - t1, 3)
     print(json.dumps(line))
     return 0
 

@@ -223,7 +223,7 @@ class LaCAMConfig(PIBTConfig):
 
 def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, max_rows_per_batch=65536, rank=0, world=1,
                print_fn=print, trace=None, retire_done=False, log_actions=False, search_status=None, refine_stats=None, record=False,
-               on_batch=None):
+               on_batch=None, on_expert_batch=None):
     """Run `evaluation_config` (dict in the reference's YAML schema).  Returns the list of result records (on every
     rank); writes `<eval_dir>/<algorithm>.json` and prints the tabular views on rank 0.
     `trace(kind, payload)` (tests): called with ("reset", {algorithm, runs, grids, pos, goal, max_steps}) for every batch
@@ -247,7 +247,10 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
     `made_actions` (the actions the env was handed, cut to the episode's length), `init_positions` and `moves` (the actions the env
     executed); one rank only, as log_actions, which keeps its meaning (the expert's logs).  on_batch(info): called after each policy
     batch has run, info = {runner, algorithm, mine (the run indices of the batch, in instance order), grids, pos, goal, run_keys,
-    n_agents, max_steps, on_target} -- how mapf_gpt_amd.ddg reads the recorded trajectories while they are on the device."""
+    n_agents, max_steps, on_target} -- how mapf_gpt_amd.ddg reads the recorded trajectories while they are on the device.
+    on_expert_batch(info): the same for the PIBT / LaCAM batches, called after each has run, with `expert` (the BatchedExpert, its log
+    and metrics still on the device) in the place of `runner` -- how dataset_build.EpisodeStore takes the episodes without a JSON log
+    (DESIGN.md section 33).  on_batch keeps its meaning: policy batches only."""
     import torch
     from .runner import BatchedRunner, gather_metrics, shard_range
 
@@ -352,6 +355,10 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                             targets = dict(zip(mine, run.targets()))
                     if not is_pibt and record:
                         recorded = dict(zip(mine, (r["metrics"] for r in run.records([runs[i][1] for i in mine], algo_name))))
+                    if is_pibt and on_expert_batch is not None:
+                        on_expert_batch({"expert": run, "algorithm": algo_name, "mine": list(mine), "grids": grids, "pos": pos, "goal": goal,
+                                         "run_keys": [runs[i][1] for i in mine], "n_agents": n_agents, "max_steps": max_steps,
+                                         "on_target": on_target})
                     if not is_pibt and on_batch is not None:
                         on_batch({"runner": run, "algorithm": algo_name, "mine": list(mine), "grids": grids, "pos": pos, "goal": goal,
                                   "run_keys": [runs[i][1] for i in mine], "n_agents": n_agents, "max_steps": max_steps,

@@ -9,12 +9,14 @@ stand on their goals at once, and episodes that do not end with CSR = 1 are drop
     ex = BatchedExpert(grids, n_inst, n_agents, max_episode_steps, seed=0)
     ex.reset(pos, goal); ex.run(max_episode_steps)
     records = ex.records(run_keys, pos)            # toolbox records with made_actions / init_positions
+    for ids, rows, labels in ex.dataset_rows(pos): # or straight to training rows on the device, grouped by grid
 
     python -m mapf_gpt_amd.expert --config CONFIG.yaml --maps MAPS.yaml --out DIR      # writes DIR/PIBT.json
     python -m mapf_gpt_amd.expert --algo lacam [--max-iters N] ...                      # writes DIR/LaCAM.json
     python -m mapf_gpt_amd.expert [--algo lacam] --swap ...                             # the same files, with the corridor swap rule
     python -m mapf_gpt_amd.expert --algo lacam --refine-rounds N [--refine-horizon H]   # ... with found solutions refined
     python -m mapf_gpt_amd.expert --lifelong [--swap] ...                               # on_target: restart configs, DIR/PIBT.json
+    python -m mapf_gpt_amd.expert ... --shards PREFIX --desired-size N                  # .arrow shards straight from the device log
 
 `search="lacam"` puts a LaCAM search (plain depth-first LaCAM over this PIBT as its configuration generator) in
 front of the episode: reset() solves every instance on the device, an instance solved within the step cap replays its solution, every
@@ -48,6 +50,11 @@ whose length or sum of costs fell, `rescued`: instances the search left over the
 `soc_after`: the sum of costs summed over the refined instances).  With --lifelong (the config's environment must say `on_target:
 restart`; not with --algo lacam) the line has `"lifelong": true`, `arrivals` (of all episodes) and `throughput` (arrivals per step, summed
 over the agents, averaged over the episodes) in the place of `solved` -- a lifelong episode has no CSR -- and `rows` counts every episode.
+
+`--shards PREFIX --desired-size N [--maze-ratio --files-per-chunk --num-chunks --shard-seed]` builds the training shards from the device
+log as the episodes are planned (dataset_build.EpisodeStore / build_shards_from_store): the files that --out +
+split_by_map + `dataset_build --logs` write, with no JSON in between.  --out is optional then (with both, the JSON is written too); the
+line gains `chunks`, the chunk reports.  Not with --lifelong: per-step goals go through records().
 """
 import argparse
 import ctypes
@@ -286,6 +293,38 @@ class BatchedExpert:
         log, lens = log.cpu().numpy(), lens.cpu().numpy()
         return [[log[i, a, :int(lens[i])].tolist() for a in range(self.n_agents)] for i in range(self.n_inst)]
 
+    def dataset_rows(self, init_pos, keep="solved", tables=None, mask_cost2go=False, offsets=False):
+        """The episodes since reset() as training rows, from the expert's own device log with no host loop over episodes:
+        -> [(instance_ids, rows uint8 [N, 256], labels int8 [N])], one entry per distinct grid in order of first appearance
+        (instance_ids: int64 array, every instance on that grid; rows and labels: device tensors, the kept instances' rows in id order --
+        what records() -> ObservationGenerator.generate_observations_device gives for them).  init_pos: the positions handed to
+        reset().  keep: "solved" = CSR >= 1 from the env's metrics, taken on the device (the reference's filter); None = all; or a
+        bool / uint8 tensor [n_inst].  tables: a dataset_tokenizer.TableCache to share the maps' tables between calls.  offsets=True
+        adds a fourth entry, row0 int64 [len(instance_ids) + 1] (device): instance_ids[k] owns rows [row0[k], row0[k + 1])."""
+        if self.lifelong:
+            raise NotImplementedError("dataset_rows() has no per-step goals: a lifelong expert's episodes go through records() and "
+                                      "dataset_tokenizer.ObservationGenerator")
+        from .dataset_tokenizer import TableCache, tokenize_episodes
+        tables = tables if tables is not None else TableCache(device=self.device)
+        if isinstance(keep, str):
+            if keep != "solved":
+                raise ValueError(f"keep={keep!r}: 'solved', None or a tensor [n_inst]")
+            keep = self.metrics()[:, METRIC_KEYS.index("CSR")] >= 1
+        init = torch.as_tensor(init_pos).to(self.device, torch.int16).reshape(self.n_inst, self.n_agents, 2)
+        log, lens = self.log()
+        grids = self.env.grids.cpu().numpy()
+        flat = grids.reshape(len(grids), -1)
+        _, first, inverse = np.unique(flat, axis=0, return_index=True, return_inverse=True)
+        of_inst = inverse.reshape(-1)[np.arange(self.n_inst) % len(grids)]                  # instance i uses grid i % n_grids
+        out = []
+        for u in np.argsort(first):                                                        # distinct grids, first appearance first
+            ids = np.flatnonzero(of_inst == u).astype(np.int64)
+            if len(ids) == 0:                                                              # (a grid no instance uses: n_grids > n_inst)
+                continue
+            rows, labels, row0 = tokenize_episodes(tables.get(grids[first[u]]), init, log, lens, keep, ids, mask_cost2go)
+            out.append((ids, rows, labels, row0) if offsets else (ids, rows, labels))
+        return out
+
     def records(self, run_keys, init_pos, algorithm="PIBT"):
         """Toolbox result records (evaluation.py): metrics = the six env metrics + made_actions + init_positions (padded coordinates,
         as dataset_tokenizer.agent_paths expects), env_grid_search = run_keys[i], algorithm.  In lifelong mode the metrics are
@@ -310,7 +349,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="Run the expert over an evaluation config and write DIR/PIBT.json (or DIR/LaCAM.json)")
     ap.add_argument("--config", required=True, help="evaluation YAML (its environment: block is run)")
     ap.add_argument("--maps", default=None, help="maps.yaml ({name: map string}) registered on top of the built-in maps")
-    ap.add_argument("--out", required=True, help="output directory")
+    ap.add_argument("--out", default=None, help="output directory (optional with --shards)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--algo", choices=["pibt", "lacam"], default="pibt", help="lacam: a LaCAM search in front of every episode")
@@ -319,7 +358,19 @@ def main(argv=None):
     ap.add_argument("--refine-rounds", type=int, default=0, help="--algo lacam: rounds of the refinement pass over found solutions (0 = off)")
     ap.add_argument("--refine-horizon", type=int, default=None, help="solutions of up to this many steps are refined (default: twice the step cap)")
     ap.add_argument("--lifelong", action="store_true", help="plan lifelong episodes: the config's environment must say on_target: restart")
+    ap.add_argument("--shards", default=None, metavar="PREFIX", help="write .arrow shards from the device log (dataset_build.build_shards_from_store)")
+    ap.add_argument("--desired-size", type=int, default=None, help="--shards: rows per chunk")
+    ap.add_argument("--maze-ratio", type=float, default=0.9)
+    ap.add_argument("--files-per-chunk", type=int, default=10)
+    ap.add_argument("--num-chunks", type=int, default=1)
+    ap.add_argument("--shard-seed", type=int, default=0, help="--shards: seed of the shuffles (dataset_build --seed)")
     a = ap.parse_args(argv)
+    if a.shards is None and a.out is None:
+        ap.error("one of --out and --shards is required")
+    if a.shards is not None and a.desired_size is None:
+        ap.error("--shards needs --desired-size")
+    if a.shards is not None and a.lifelong:
+        ap.error("--shards does not take --lifelong: per-step goals go through the JSON log (--out) and dataset_build --logs")
     from . import evaluation as ev
     cfg = ev.load_yaml(a.config)
     reg = ev.MapRegistry()
@@ -342,11 +393,18 @@ def main(argv=None):
         algo["lifelong"] = True
     cfg = {"environment": cfg["environment"], "algorithms": {algo["name"]: algo}}
     status, refine = {}, {}
+    store = None
+    if a.shards is not None:
+        from .dataset_build import EpisodeStore
+        store = EpisodeStore(device=a.device)
     t0 = time.perf_counter()
-    res = ev.evaluation(cfg, eval_dir=a.out, registry=reg, print_fn=lambda *_: None, log_actions=True, search_status=status,
-                        refine_stats=refine)
+    res = ev.evaluation(cfg, eval_dir=a.out, registry=reg, print_fn=lambda *_: None, log_actions=a.out is not None, search_status=status,
+                        refine_stats=refine, on_expert_batch=store.append if store is not None else None)
     solved = res if a.lifelong else [r for r in res if r["metrics"]["CSR"] >= 1]
-    rows = sum(len(r["metrics"]["made_actions"]) * (int(r["metrics"]["ep_length"]) + 1) for r in solved)     # dataset rows of the solved episodes
+    if a.out is not None:
+        rows = sum(len(r["metrics"]["made_actions"]) * (int(r["metrics"]["ep_length"]) + 1) for r in solved)     # dataset rows of the solved episodes
+    else:                                            # --shards alone: no action list ever reaches the host
+        rows = store.solved_rows()[1]
     line = {"episodes": len(res), "solved": len(solved), "rows": rows, "seconds": round(time.perf_counter() - t0, 3)}
     if a.lifelong:                                   # no CSR in a lifelong record: every episode gives rows
         del line["solved"]
@@ -359,6 +417,13 @@ def main(argv=None):
         line["swap"] = True
     if a.refine_rounds:
         line.update(refine_rounds=a.refine_rounds, **{k: int(refine.get(k, 0)) for k in ("refined", "rescued", "soc_before", "soc_after")})
+    if store is not None:
+        import os
+        from .dataset_build import build_shards_from_store
+        if os.path.dirname(a.shards):
+            os.makedirs(os.path.dirname(a.shards), exist_ok=True)
+        line["chunks"] = build_shards_from_store(store, a.shards, a.desired_size, a.maze_ratio, a.files_per_chunk, a.num_chunks, a.shard_seed)
+        line["seconds"] = round(time.perf_counter() - t0, 3)
     print(json.dumps(line))
     return 0
 
