@@ -485,7 +485,7 @@ int mgpt_dataset_tokenize_ex(mgpt_dataset *ds, int n_agents, int n_steps, const 
  *              mgpt_dataset_tokenize makes of the episode's paths (init + the running sum of the moves; the goal is the path's last
  *              cell), agent-major then timestep 0 .. len, and the labels of generate_observations.py:67-90: with a = actions[:len] +
  *              [0] and g the index of a's last non-zero entry (len + 1 if none), 5 where t > g, else a[t].  Lifelong logs (per-step
- *              goals) are not supported: use mgpt_dataset_tokenize_ex per episode.  Stream-ordered; no host synchronisation except
+ *              goals) go through mgpt_dataset_tokenize_episodes_lifelong below.  Stream-ordered; no host synchronisation except
  *              when the context's workspace (16 bytes per row of n_sel * n_agents * (max_steps + 1)) grows.  MGPT_ERR_UNSUPPORTED
  *              when that product reaches 2^31: split the selection.  n_sel = 0 launches nothing. */
 int mgpt_dataset_episode_offsets(int n_sel, int n_agents, int max_steps, const int32_t *d_len, const uint8_t *d_keep,
@@ -493,6 +493,25 @@ int mgpt_dataset_episode_offsets(int n_sel, int n_agents, int max_steps, const i
 int mgpt_dataset_tokenize_episodes(mgpt_dataset *ds, int n_sel, int n_agents, int max_steps, const int16_t *d_init, const int8_t *d_actions,
                                    const int32_t *d_len, const uint8_t *d_keep, const int32_t *d_episodes, const int64_t *d_row0,
                                    int only_obstacles, uint8_t *d_tokens, int8_t *d_labels, void *stream);
+/* The same for LIFELONG logs (generate_observations.py:55-60, 72-79, 156-166, 188-202): the arguments of
+ * tokenize_episodes plus the agents' target lists.  An agent's list is target(0), target(1), ...; walking its path t = 0 .. len with
+ * cur = 0, a cell equal to target(cur) advances cur by one (an `if`, not a loop; also at t = 0, before that cell's goal is read) and the
+ * goal at t is target(cur).  The record of every agent (own and neighbours) carries that per-step goal -- the relative goal and the
+ * greedy-direction bits of the goal's field; the cost-to-go window is still cut from the field of the path's LAST CELL, as in the
+ * reference (:75-78).  Labels, history, row order and offsets are those of tokenize_episodes.
+ *   d_targets   int16 [n_batch][n_agents][L][2], L >= 1: target(0) = entry 0 and, for j >= 1, target(j) = entry 1 + (j - 1) % (L - 1) --
+ *               the expert's (goal at reset, cyclic queue of Q = L - 1) as it lies; a plain list is the case without a wrap;
+ *   d_n_targets int32 [n_batch][n_agents] or NULL (= L each): the length of every list, j < n_targets;
+ *   d_status    int32 [1], zeroed by the caller: set to 1 (a plain store, stream-ordered) when a kept agent's walk reaches n_targets
+ *               or n_targets < 1 -- the reference's IndexError.  The walk goes on with the last valid index: the rows of such a call are
+ *               unspecified, every access stays in bounds.
+ * A target outside the frame gives no table read and the direction bits "0000", as an out-of-frame goal of tokenize_ex; init cells and
+ * moves are clamped as in tokenize_episodes: no byte of d_init, d_actions, d_targets or d_n_targets moves a read out of bounds.  Same
+ * stream ordering, workspace (plus 4 bytes per n_sel * n_agents), windows of a longer scan and n_sel = 0 rule as tokenize_episodes. */
+int mgpt_dataset_tokenize_episodes_lifelong(mgpt_dataset *ds, int n_sel, int n_agents, int max_steps, const int16_t *d_init,
+                                            const int8_t *d_actions, const int32_t *d_len, const uint8_t *d_keep, const int32_t *d_episodes,
+                                            const int64_t *d_row0, const int16_t *d_targets, int L, const int32_t *d_n_targets,
+                                            int32_t *d_status, int only_obstacles, uint8_t *d_tokens, int8_t *d_labels, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Dataset builder: steps 2-3 of dataset/generate_dataset.py on rows that the bulk tokenizer above has left on the device --

@@ -74,6 +74,7 @@ SYMBOLS = {
     "mgpt_dataset_tokenize_ex": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "mgpt_dataset_episode_offsets": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mgpt_dataset_tokenize_episodes": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "mgpt_dataset_tokenize_episodes_lifelong": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "mgpt_dedup_create": (_i, [_pp, _i64, _i, _vp]),
     "mgpt_dedup_destroy": (_i, [_vp]),
     "mgpt_dedup_reset": (_i, [_vp, _vp]),

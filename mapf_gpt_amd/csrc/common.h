@@ -81,6 +81,7 @@ enum ProfId {
     P_EXPERT_SHIELD,                                    // the collision shield's plan kernel (expert.hip)
     P_STEP_RECORD,                                      // the episode recorder's store of a step (step.hip)
     P_DS_PATHS, P_DS_EPISODE_TOKENS,                    // batched episode tokenizer: paths + labels + records, rows (tokenizer.hip)
+    P_DS_PATHS_LIFELONG, P_DS_EPISODE_TOKENS_LIFELONG,  // the same for lifelong logs: a goal per timestep (tokenizer.hip)
     P_COUNT
 };
 

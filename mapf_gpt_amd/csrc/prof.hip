@@ -30,7 +30,8 @@ static const char *kProfNames[P_COUNT] = {
     "expert_pibt_plan", "expert_lacam_search", "expert_cell_degree",
     "expert_refine_path", "expert_refine_round", "expert_refine_final",
     "expert_lifelong_post", "expert_shield", "step_record",
-    "ds_paths", "ds_episode_tokens"};
+    "ds_paths", "ds_episode_tokens",
+    "ds_paths_lifelong", "ds_episode_tokens_lifelong"};
 
 struct ProfState {
     std::mutex mu;

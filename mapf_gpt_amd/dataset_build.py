@@ -13,7 +13,8 @@ POGEMA, which is not part of this repository; `python -m mapf_gpt_amd.expert` wr
 `EpisodeStore` + `build_shards_from_store` are the same steps 2-3 with no log file: the store keeps the expert's
 device logs as the batches are planned (evaluation(on_expert_batch=store.append)), every map's episodes become rows in one
 dataset_tokenizer.tokenize_episodes call per (map, batch), and from there on the code is the one below.  `python -m mapf_gpt_amd.expert
---shards` and `python -m mapf_gpt_amd.ddg --shards` write shards this way.
+--shards` and `python -m mapf_gpt_amd.ddg --shards` write shards this way; `EpisodeStore(lifelong=True)` and `python -m mapf_gpt_amd.expert
+--lifelong-shards` do the same for lifelong (on_target: restart) episodes, whose goal changes along the path.
 
 Shuffles draw from one np.random.Generator(PCG64(seed)) in a fixed order (per file in processing order, then the whole chunk);
 the reference draws from numpy's global stream, so orders differ from it seed for seed while the sets of rows do not.
@@ -323,14 +324,17 @@ class EpisodeStore:
     """The expert's episodes, kept where they were planned, until the shards are built: append(info) takes one batch of
     evaluation(on_expert_batch=...) and keeps its device log once -- first cells, made actions, lengths, CSR and the frame grids, about one
     byte per agent-step -- plus, per map name, the batch's episode indices in log order.  No row exists until rows_of(map) is asked.
-    The episodes of a map name in order (batch, then index) are the records of split_by_map's <map_name>.json in order."""
+    The episodes of a map name in order (batch, then index) are the records of split_by_map's <map_name>.json in order.
+    lifelong=True makes it a store of on_target='restart' batches: append() also keeps the expert's
+    lifelong_targets(), every episode counts as kept, and rows_of carries the goal pursued at every timestep.  A store is one or the other."""
 
-    def __init__(self, device="cuda", tables=None, mask_cost2go=False):
+    def __init__(self, device="cuda", tables=None, mask_cost2go=False, lifelong=False):
         from .dataset_tokenizer import TableCache
         self.device = torch.device(device)
         self.tables = tables if tables is not None else TableCache(device=self.device)
         self.mask_cost2go = bool(mask_cost2go)
-        self.batches = []                                    # {init, actions, lengths, solved, grids (host), n_agents, max_steps}
+        self.lifelong = bool(lifelong)
+        self.batches = []                                    # {init, actions, lengths, solved, grids (host)} + lifelong: {targets, n_targets}
         self.per_map = {}                                    # map name -> [(batch index, [episode indices])], in log order
 
     @staticmethod
@@ -342,24 +346,42 @@ class EpisodeStore:
         return out
 
     def append(self, info):
-        if info.get("on_target", "nothing") != "nothing":
-            raise NotImplementedError("EpisodeStore keeps no per-step goals: lifelong (on_target='restart') episodes go through the JSON log")
+        on_target = info.get("on_target", "nothing")
+        if self.lifelong:
+            if on_target != "restart":
+                raise NotImplementedError(f"EpisodeStore(lifelong=True) keeps lifelong (on_target='restart') episodes only, not on_target={on_target!r}")
+            ex = info["expert"]
+            log, lens = ex.log()
+            targets, n_targets = ex.lifelong_targets()
+            self.add_batch(info["run_keys"], info["pos"], log, lens, torch.ones_like(lens, dtype=torch.bool), info["grids"], targets, n_targets)
+            return
+        if on_target != "nothing":
+            raise NotImplementedError("EpisodeStore keeps no per-step goals: lifelong (on_target='restart') episodes go through the JSON log "
+                                      "(or a store made with lifelong=True)")
         ex = info["expert"]
         log, lens = ex.log()
         self.add_batch(info["run_keys"], info["pos"], log, lens, ex.metrics()[:, METRIC_CSR] >= 1, info["grids"])
 
-    def add_batch(self, run_keys, init, actions, lengths, solved, grids):
+    def add_batch(self, run_keys, init, actions, lengths, solved, grids, targets=None, n_targets=None):
         """One batch given as tensors (append() reads them off a BatchedExpert; mapf_gpt_amd.ddg hands in the teacher's): run_keys
         [n] dicts with `map_name`; init [n, n_agents, 2]; actions int8 [n, n_agents, max_steps]; lengths [n]; solved bool [n] (CSR >= 1);
-        grids [n or 1, H, W], the frame every episode ran in."""
+        grids [n or 1, H, W], the frame every episode ran in.  A lifelong store also takes the batch's target lists (targets int16 [n,
+        n_agents, L, 2], n_targets int32 [n, n_agents] or None, as dataset_tokenizer.tokenize_episodes reads them) and keeps every
+        episode whatever `solved` says: a lifelong record has no CSR."""
         actions = torch.as_tensor(actions).to(self.device, torch.int8).contiguous()
         n = int(actions.shape[0])
         assert len(run_keys) == n, "one run key per episode"
+        if self.lifelong != (targets is not None):
+            raise ValueError("a lifelong store takes batches with targets, a default store batches without")
         grids = np.asarray(grids.cpu() if torch.is_tensor(grids) else grids)
         self.batches.append({"init": torch.as_tensor(init).to(self.device, torch.int16).reshape(n, -1, 2).contiguous(),
                              "actions": actions, "lengths": torch.as_tensor(lengths).to(self.device, torch.int32).contiguous(),
                              "solved": (torch.as_tensor(solved).to(self.device) != 0).to(torch.uint8).contiguous(),
                              "grids": grids[None] if grids.ndim == 2 else grids})
+        if self.lifelong:
+            self.batches[-1]["solved"].fill_(1)
+            self.batches[-1]["targets"] = torch.as_tensor(targets).to(self.device, torch.int16).contiguous()
+            self.batches[-1]["n_targets"] = None if n_targets is None else torch.as_tensor(n_targets).to(self.device, torch.int32).contiguous()
         for name, idx in self.group_by_map(run_keys).items():
             self.per_map.setdefault(name, []).append((len(self.batches) - 1, idx))
 
@@ -387,7 +409,8 @@ class EpisodeStore:
         for bi, idx in self.per_map.get(map_name, []):
             b = self.batches[bi]
             table = self.tables.get(b["grids"][idx[0] % len(b["grids"])])
-            x, y, _ = tokenize_episodes(table, b["init"], b["actions"], b["lengths"], b["solved"], idx, self.mask_cost2go)
+            x, y, _ = tokenize_episodes(table, b["init"], b["actions"], b["lengths"], b["solved"], idx, self.mask_cost2go,
+                                        targets=b.get("targets"), n_targets=b.get("n_targets"))
             xs.append(x)
             ys.append(y)
         if not xs:

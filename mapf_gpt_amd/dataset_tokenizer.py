@@ -17,6 +17,10 @@ Batched route: `tokenize_episodes(table, init, actions, l
 the expert's device log as BatchedExpert.log() returns it -- into (rows, labels, row0) on the device in one call, with no per-episode
 host work; `TableCache` keeps the maps' all-pairs tables by grid bytes.  BatchedExpert.dataset_rows and dataset_build.EpisodeStore sit on
 top of the two.  `episode_row_offsets` / `episode_labels` restate the offsets and the label rule in numpy (tests, tools).
+Lifelong logs take the same route: `tokenize_episodes(..., targets=, n_targets=)` hands the agents' target lists
+(goal at reset + cyclic queue, as BatchedExpert.lifelong_targets() returns them) to mgpt_dataset_tokenize_episodes_lifelong, which
+derives the goal of every timestep on the device; `episode_goals` restates that rule in numpy.  BatchedExpert.lifelong_rows and
+dataset_build.EpisodeStore(lifelong=True) sit on top of it.
 """
 import collections
 import ctypes
@@ -136,7 +140,43 @@ def episode_labels(actions, length):
     return np.where(t[None, :] > g[:, None], 5, a).astype(np.int8)
 
 
-def tokenize_episodes(table, init, actions, lengths, keep=None, episodes=None, mask_cost2go=False, max_rows_per_call=1 << 22):
+def target_at(targets, j):
+    """target(j) of one agent's list as the lifelong batched call addresses it: targets [L, 2]; entry 0, then the L - 1 entries behind it
+    cyclically -- the expert's (goal at reset, cyclic queue) as it lies."""
+    L = len(targets)
+    return targets[0] if j == 0 else targets[1 + (j - 1) % (L - 1)]
+
+
+def episode_goals(init, actions, length, targets, n_targets=None):
+    """numpy restatement of the device's per-step goal rule (= goal_positions, with the cyclic addressing of
+    mgpt_dataset_tokenize_episodes_lifelong) on one episode's log: init [n_agents, 2], actions int8 [n_agents, >= length] (bytes outside 0..4
+    count as 0), targets int16 [n_agents, L, 2], n_targets [n_agents] or None (L each) -> int32 [n_agents, length + 1, 2].  Walking an agent's
+    path t = 0 .. length with cur = 0: a cell equal to target(cur) advances cur (an `if`; also at t = 0), the goal at t is target(cur).
+    A walk that reaches n_targets raises IndexError, as the reference does."""
+    a = np.asarray(actions).astype(np.int64)[:, :int(length)]
+    a = np.where((a >= 0) & (a <= 4), a, 0)
+    paths = agent_paths(np.asarray(init).reshape(-1, 2), a)
+    targets = np.asarray(targets).astype(np.int32)
+    n, L = int(targets.shape[0]), int(targets.shape[1])
+    assert targets.shape == (paths.shape[0], L, 2) and L >= 1, "targets [n_agents, L >= 1, 2]"
+    nt = np.full((n,), L, np.int64) if n_targets is None else np.asarray(n_targets, dtype=np.int64).reshape(n)
+    out = np.empty_like(paths)
+    for ag in range(n):
+        limit = min(int(nt[ag]), 1) if L == 1 else int(nt[ag])
+        cur = 0
+        if limit < 1:
+            raise IndexError(f"agent {ag}: an empty target list")
+        for t in range(paths.shape[1]):
+            if (paths[ag, t] == target_at(targets[ag], cur)).all():
+                cur += 1
+                if cur >= limit:
+                    raise IndexError(f"agent {ag} exhausts its {limit} targets at t = {t}")
+            out[ag, t] = target_at(targets[ag], cur)
+    return out
+
+
+def tokenize_episodes(table, init, actions, lengths, keep=None, episodes=None, mask_cost2go=False, max_rows_per_call=1 << 22,
+                      targets=None, n_targets=None):
     """A batch of logged episodes of one map -> (rows uint8 [N, 256], labels int8 [N], row0 int64 [n_sel + 1]), device tensors.
     table: the map's MapTable (the episodes' frame); init int16 [n_batch, n_agents, 2] first cells in its coordinates; actions int8
     [n_batch, n_agents, max_steps] and lengths int32 [n_batch] as BatchedExpert.log() returns them; keep: uint8 / bool [n_batch] or
@@ -144,7 +184,12 @@ def tokenize_episodes(table, init, actions, lengths, keep=None, episodes=None, m
     n_batch) or None for all.  Selected episode k owns rows [row0[k], row0[k + 1]): what MapTable.tokenize makes of its paths, agent-major
     then timestep 0 .. len, with the labels of gt_actions.  The one value read back is row0[-1], to size the output (with `episodes` on
     the device, a flag that every index is in range travels with it).  The selection is tokenized in pieces of at most max_rows_per_call //
-    (n_agents * (max_steps + 1)) episodes (at least one), which bounds the library's workspace; the result does not depend on the pieces."""
+    (n_agents * (max_steps + 1)) episodes (at least one), which bounds the library's workspace; the result does not depend on the pieces.
+    targets (lifelong logs): int16 [n_batch, n_agents, L, 2], every agent's target list -- entry 0, then the L - 1
+    entries behind it cyclically (BatchedExpert.lifelong_targets(); a plain list is the case without a wrap); n_targets int32 [n_batch,
+    n_agents] or None (L each), the lists' lengths.  The records then carry the goal pursued at every timestep (episode_goals) and the rows
+    are what MapTable.tokenize(paths, goals) makes of the episode.  One more value is read back then, after the last piece: a flag that a
+    kept agent's walk exhausted its list, which raises IndexError as the reference does."""
     dev = table.device
     init = torch.as_tensor(init).to(dev, torch.int16).contiguous()
     actions = torch.as_tensor(actions).to(dev, torch.int8).contiguous()
@@ -155,6 +200,15 @@ def tokenize_episodes(table, init, actions, lengths, keep=None, episodes=None, m
     if keep is not None:
         keep = (torch.as_tensor(keep).to(dev) != 0).to(torch.uint8).contiguous()
         assert tuple(keep.shape) == (n_batch,), "keep [n_batch]"
+    if targets is None:
+        assert n_targets is None, "n_targets needs targets"
+    else:
+        targets = torch.as_tensor(targets).to(dev, torch.int16).contiguous()
+        assert targets.dim() == 4 and tuple(targets.shape[:2]) == (n_batch, n_agents) and targets.shape[2] >= 1 and targets.shape[3] == 2, \
+            "targets [n_batch, n_agents, L >= 1, 2]"
+        if n_targets is not None:
+            n_targets = torch.as_tensor(n_targets).to(dev, torch.int32).contiguous()
+            assert tuple(n_targets.shape) == (n_batch, n_agents), "n_targets [n_batch, n_agents]"
     flag = None
     if episodes is None:
         n_sel = n_batch
@@ -186,13 +240,21 @@ def tokenize_episodes(table, init, actions, lengths, keep=None, episodes=None, m
         per = max(1, int(max_rows_per_call) // (n_agents * (max_steps + 1)))
         if per < n_sel and episodes is None:                 # a piece names its episodes: k of a window is not the episode's index
             episodes = torch.arange(n_sel, dtype=torch.int32, device=dev)
+        status = torch.zeros((1,), dtype=torch.int32, device=dev) if targets is not None else None
         for k0 in range(0, n_sel, per):
             k1 = min(k0 + per, n_sel)
-            _lib.check(L.mgpt_dataset_tokenize_episodes(table._h, k1 - k0, n_agents, max_steps, _lib.ptr(init), _lib.ptr(actions),
-                                                        _lib.ptr(lengths), _lib.ptr(keep) if keep is not None else None,
-                                                        ctypes.c_void_p(episodes.data_ptr() + 4 * k0) if episodes is not None else None,
-                                                        ctypes.c_void_p(row0.data_ptr() + 8 * k0), 1 if mask_cost2go else 0,
-                                                        _lib.ptr(rows), _lib.ptr(labels), s))
+            piece = (table._h, k1 - k0, n_agents, max_steps, _lib.ptr(init), _lib.ptr(actions), _lib.ptr(lengths),
+                     _lib.ptr(keep) if keep is not None else None,
+                     ctypes.c_void_p(episodes.data_ptr() + 4 * k0) if episodes is not None else None, ctypes.c_void_p(row0.data_ptr() + 8 * k0))
+            out = (1 if mask_cost2go else 0, _lib.ptr(rows), _lib.ptr(labels), s)
+            if targets is None:
+                _lib.check(L.mgpt_dataset_tokenize_episodes(*piece, *out))
+            else:
+                _lib.check(L.mgpt_dataset_tokenize_episodes_lifelong(*piece, _lib.ptr(targets), int(targets.shape[2]),
+                                                                     _lib.ptr(n_targets) if n_targets is not None else None,
+                                                                     _lib.ptr(status), *out))
+        if status is not None and status.cpu().item():
+            raise IndexError("a kept episode's agent stood on more targets than its list holds (generate_observations.py:146-149)")
     return rows, labels, row0
 
 

@@ -17,6 +17,7 @@ stand on their goals at once, and episodes that do not end with CSR = 1 are drop
     python -m mapf_gpt_amd.expert --algo lacam --refine-rounds N [--refine-horizon H]   # ... with found solutions refined
     python -m mapf_gpt_amd.expert --lifelong [--swap] ...                               # on_target: restart configs, DIR/PIBT.json
     python -m mapf_gpt_amd.expert ... --shards PREFIX --desired-size N                  # .arrow shards straight from the device log
+    python -m mapf_gpt_amd.expert ... --lifelong-shards PREFIX --desired-size N         # the same for on_target: restart configs
 
 `search="lacam"` puts a LaCAM search (plain depth-first LaCAM over this PIBT as its configuration generator) in
 front of the episode: reset() solves every instance on the device, an instance solved within the step cap replays its solution, every
@@ -54,7 +55,11 @@ over the agents, averaged over the episodes) in the place of `solved` -- a lifel
 `--shards PREFIX --desired-size N [--maze-ratio --files-per-chunk --num-chunks --shard-seed]` builds the training shards from the device
 log as the episodes are planned (dataset_build.EpisodeStore / build_shards_from_store): the files that --out +
 split_by_map + `dataset_build --logs` write, with no JSON in between.  --out is optional then (with both, the JSON is written too); the
-line gains `chunks`, the chunk reports.  Not with --lifelong: per-step goals go through records().
+line gains `chunks`, the chunk reports.  Not with --lifelong: that is `--lifelong-shards PREFIX --desired-size N [the same options]`
+(DESIGN.md section 34), which implies --lifelong (same checks: on_target: restart, not with --algo lacam; not together with --shards)
+and builds the shards of the lifelong episodes the same way -- every episode kept, the goal pursued at every timestep derived on the
+device from the goal at reset, the queue and the arrival counts (BatchedExpert.lifelong_targets() -> EpisodeStore(lifelong=True)); `rows`
+and `arrivals` are then counted on the device.  BatchedExpert.lifelong_rows(pos) is dataset_rows() for a lifelong expert.
 """
 import argparse
 import ctypes
@@ -108,7 +113,7 @@ class BatchedExpert:
         if refine_rounds:
             self.set_refine(refine_rounds, refine_horizon)
         self.lifelong = False
-        self._goal0 = self._queue = None
+        self._goal0 = self._queue = self._targets = None
         if lifelong:
             self.set_lifelong(True)
         self.shield = False
@@ -196,6 +201,9 @@ class BatchedExpert:
             self.env.set_lifelong(q)
             self._queue = q.cpu().numpy().astype(np.int64)
             self._goal0 = torch.as_tensor(goal).cpu().numpy().astype(np.int64).reshape(self.n_inst, self.n_agents, 2)
+            # the same two on the device, goal first: every agent's target list as lifelong_targets() hands it on
+            self._targets = torch.cat([torch.as_tensor(goal).to(self.device, torch.int16).reshape(self.n_inst, self.n_agents, 1, 2),
+                                       q.to(self.device, torch.int16)], dim=2).contiguous()
         else:
             if goal_queue is not None:
                 raise ValueError("goal_queue needs lifelong=True")
@@ -280,6 +288,49 @@ class BatchedExpert:
         return [[[self._goal0[i, a].tolist()] + [self._queue[i, a, k % Q].tolist() for k in range(int(reached[i, a]))]
                  for a in range(self.n_agents)] for i in range(self.n_inst)]
 
+    def lifelong_targets(self):
+        """Lifelong mode: targets() as the batched tokenizer takes it, with no host loop -> (targets int16 [n_inst, n_agents, 1 + Q, 2]: the
+        goal at reset, then the queue as it lies (entry 1 + (j - 1) % Q is target j >= 1); n_targets int32 [n_inst, n_agents] = 1 + the
+        agent's arrivals), device tensors."""
+        if not self.lifelong or self._targets is None:
+            raise RuntimeError("lifelong_targets() needs lifelong=True and a reset()")
+        return self._targets, (self.env.goals_reached() + 1).to(torch.int32)
+
+    def lifelong_rows(self, init_pos, tables=None, mask_cost2go=False, offsets=False):
+        """dataset_rows() for a lifelong expert: the episodes since reset() as training rows with the goal pursued
+        at every timestep, from the device log and lifelong_targets() in one tokenize_episodes call per distinct grid -> [(instance_ids,
+        rows uint8 [N, 256], labels int8 [N])] (offsets=True: + row0) as dataset_rows returns them, every episode kept (a lifelong record has
+        no CSR and the reference keeps it) -- what records() -> ObservationGenerator.generate_observations_device gives.  Raises IndexError
+        where that route does: an agent that stood on more targets than its list holds (one that starts on its own goal)."""
+        if not self.lifelong:
+            raise RuntimeError("lifelong_rows() needs lifelong=True: the episodes of a one-shot expert go through dataset_rows()")
+        if self._targets is None:
+            raise RuntimeError("lifelong_rows() needs a reset(): there is no episode and no goal queue yet")
+        from .dataset_tokenizer import TableCache, tokenize_episodes
+        tables = tables if tables is not None else TableCache(device=self.device)
+        init = torch.as_tensor(init_pos).to(self.device, torch.int16).reshape(self.n_inst, self.n_agents, 2)
+        log, lens = self.log()
+        targets, n_targets = self.lifelong_targets()
+        out = []
+        for ids, grid in self._instances_by_grid():
+            rows, labels, row0 = tokenize_episodes(tables.get(grid), init, log, lens, None, ids, mask_cost2go, targets=targets,
+                                                   n_targets=n_targets)
+            out.append((ids, rows, labels, row0) if offsets else (ids, rows, labels))
+        return out
+
+    def _instances_by_grid(self):
+        """[(instance ids int64, grid)] per distinct grid in order of first appearance (instance i uses grid i % n_grids)."""
+        grids = self.env.grids.cpu().numpy()
+        flat = grids.reshape(len(grids), -1)
+        _, first, inverse = np.unique(flat, axis=0, return_index=True, return_inverse=True)
+        of_inst = inverse.reshape(-1)[np.arange(self.n_inst) % len(grids)]
+        out = []
+        for u in np.argsort(first):
+            ids = np.flatnonzero(of_inst == u).astype(np.int64)
+            if len(ids):                                                                   # (a grid no instance uses: n_grids > n_inst)
+                out.append((ids, grids[first[u]]))
+        return out
+
     def throughput(self):
         """float32 [n_inst]: arrivals per step, summed over the agents, over max_episode_steps (lifelong mode; device tensor).  The
         counts are divided on the host, one correctly rounded float32 division each: torch's division of a device tensor by a scalar
@@ -302,8 +353,8 @@ class BatchedExpert:
         bool / uint8 tensor [n_inst].  tables: a dataset_tokenizer.TableCache to share the maps' tables between calls.  offsets=True
         adds a fourth entry, row0 int64 [len(instance_ids) + 1] (device): instance_ids[k] owns rows [row0[k], row0[k + 1])."""
         if self.lifelong:
-            raise NotImplementedError("dataset_rows() has no per-step goals: a lifelong expert's episodes go through records() and "
-                                      "dataset_tokenizer.ObservationGenerator")
+            raise NotImplementedError("dataset_rows() has no per-step goals: a lifelong expert's episodes go through lifelong_rows(), or "
+                                      "records() and dataset_tokenizer.ObservationGenerator")
         from .dataset_tokenizer import TableCache, tokenize_episodes
         tables = tables if tables is not None else TableCache(device=self.device)
         if isinstance(keep, str):
@@ -364,13 +415,24 @@ def main(argv=None):
     ap.add_argument("--files-per-chunk", type=int, default=10)
     ap.add_argument("--num-chunks", type=int, default=1)
     ap.add_argument("--shard-seed", type=int, default=0, help="--shards: seed of the shuffles (dataset_build --seed)")
+    ap.add_argument("--lifelong-shards", default=None, metavar="PREFIX",
+                    help="--shards for lifelong episodes (implies --lifelong): the goal pursued at every timestep is derived on the device")
     a = ap.parse_args(argv)
-    if a.shards is None and a.out is None:
-        ap.error("one of --out and --shards is required")
+    if a.lifelong_shards is not None:
+        if a.shards is not None:
+            ap.error("--lifelong-shards and --shards are two kinds of episodes: one store keeps one of them")
+        if a.desired_size is None:
+            ap.error("--lifelong-shards needs --desired-size")
+        if a.algo == "lacam":
+            ap.error("--lifelong-shards plans with PIBT only: the search of --algo lacam looks for a joint goal configuration")
+        a.lifelong = True
+    if a.shards is None and a.lifelong_shards is None and a.out is None:
+        ap.error("one of --out, --shards and --lifelong-shards is required")
     if a.shards is not None and a.desired_size is None:
         ap.error("--shards needs --desired-size")
     if a.shards is not None and a.lifelong:
-        ap.error("--shards does not take --lifelong: per-step goals go through the JSON log (--out) and dataset_build --logs")
+        ap.error("--shards does not take --lifelong: per-step goals go through --lifelong-shards, or the JSON log (--out) and "
+                 "dataset_build --logs")
     from . import evaluation as ev
     cfg = ev.load_yaml(a.config)
     reg = ev.MapRegistry()
@@ -394,22 +456,26 @@ def main(argv=None):
     cfg = {"environment": cfg["environment"], "algorithms": {algo["name"]: algo}}
     status, refine = {}, {}
     store = None
-    if a.shards is not None:
+    shards = a.shards if a.shards is not None else a.lifelong_shards
+    if shards is not None:
         from .dataset_build import EpisodeStore
-        store = EpisodeStore(device=a.device)
+        store = EpisodeStore(device=a.device, lifelong=a.lifelong_shards is not None)
     t0 = time.perf_counter()
     res = ev.evaluation(cfg, eval_dir=a.out, registry=reg, print_fn=lambda *_: None, log_actions=a.out is not None, search_status=status,
                         refine_stats=refine, on_expert_batch=store.append if store is not None else None)
     solved = res if a.lifelong else [r for r in res if r["metrics"]["CSR"] >= 1]
-    if a.out is not None:
+    if a.out is not None and a.lifelong_shards is None:
         rows = sum(len(r["metrics"]["made_actions"]) * (int(r["metrics"]["ep_length"]) + 1) for r in solved)     # dataset rows of the solved episodes
-    else:                                            # --shards alone: no action list ever reaches the host
+    else:                                            # --shards alone: no action list ever reaches the host; --lifelong-shards: counted on the device
         rows = store.solved_rows()[1]
     line = {"episodes": len(res), "solved": len(solved), "rows": rows, "seconds": round(time.perf_counter() - t0, 3)}
     if a.lifelong:                                   # no CSR in a lifelong record: every episode gives rows
         del line["solved"]
         line["lifelong"] = True
-        line["arrivals"] = sum(len(tg) - 1 for r in res for tg in r["metrics"]["global_lifelong_targets_xy"])
+        if a.lifelong_shards is not None:            # the store's lists: no target list reaches the host without --out
+            line["arrivals"] = sum(int((b["n_targets"] - 1).sum()) for b in store.batches)
+        else:
+            line["arrivals"] = sum(len(tg) - 1 for r in res for tg in r["metrics"]["global_lifelong_targets_xy"])
         line["throughput"] = round(float(np.mean([r["metrics"]["avg_throughput"] for r in res])), 4) if res else 0.0
     if a.algo == "lacam":
         line["status"] = {str(k): int(v) for k, v in sorted(status.items())}
@@ -420,9 +486,9 @@ def main(argv=None):
     if store is not None:
         import os
         from .dataset_build import build_shards_from_store
-        if os.path.dirname(a.shards):
-            os.makedirs(os.path.dirname(a.shards), exist_ok=True)
-        line["chunks"] = build_shards_from_store(store, a.shards, a.desired_size, a.maze_ratio, a.files_per_chunk, a.num_chunks, a.shard_seed)
+        if os.path.dirname(shards):
+            os.makedirs(os.path.dirname(shards), exist_ok=True)
+        line["chunks"] = build_shards_from_store(store, shards, a.desired_size, a.maze_ratio, a.files_per_chunk, a.num_chunks, a.shard_seed)
         line["seconds"] = round(time.perf_counter() - t0, 3)
     print(json.dumps(line))
     return 0

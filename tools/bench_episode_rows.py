@@ -15,7 +15,11 @@ it stands next to (records() -> ObservationGenerator.generate_observations_devic
                   each once after a warm-up run of the shards route, as functions of this process; the two sets of .arrow files are
                   compared byte for byte.
 
-Prints ONE JSON line and appends it to profiles/bench_episode_rows.jsonl (or --out).
+    --mode rows --lifelong   the same schedule on BatchedExpert(lifelong=True, swap=True) with the evaluation's seeded goal queues (DESIGN.md
+                  section 34): BatchedExpert.lifelong_rows against records() -> generate_observations_device; every episode runs the
+                  whole cap and is kept.  Kernel ms under ds_paths_lifelong and ds_episode_tokens_lifelong.
+
+Prints ONE JSON line and appends it to profiles/bench_episode_rows.jsonl (bench_episode_rows_lifelong.jsonl with --lifelong; or --out).
 """
 import argparse
 import contextlib
@@ -53,18 +57,29 @@ def bench_rows(a):
     grid = maps.pad(obst)
     named = {"maze21": map_string(obst)}
     runs = []
+    frame = (grid, grid == 0, grid == 0)
     for n in AGENTS:
         pos = np.empty((a.seeds, n, 2), np.int16)
         goal = np.empty_like(pos)
         for s in range(a.seeds):
             pos[s], goal[s] = maps.place_agents(grid, n, s)
-        ex = BatchedExpert(grid, a.seeds, n, CAP, seed=0, swap=True)
-        ex.reset(torch.from_numpy(pos), torch.from_numpy(goal))
+            while a.lifelong and (pos[s] == goal[s]).all(-1).any():      # an agent that starts on its goal advances its list with no arrival:
+                goal[s] = np.roll(goal[s], 1, axis=0)                   # both routes raise the reference's IndexError on such a log
+        ex = BatchedExpert(grid, a.seeds, n, CAP, seed=0, swap=True, lifelong=a.lifelong)
+        if a.lifelong:
+            from mapf_gpt_amd import evaluation as ev
+            cells = ev.lifelong_cells(frame)
+            queue = np.stack([ev.lifelong_queue(frame, s, n, cells=cells) for s in range(a.seeds)])
+            ex.reset(torch.from_numpy(pos), torch.from_numpy(goal), torch.from_numpy(queue))
+        else:
+            ex.reset(torch.from_numpy(pos), torch.from_numpy(goal))
         ex.run(CAP)
         runs.append((ex, pos, [{"map_name": "maze21", "seed": s, "num_agents": n} for s in range(a.seeds)]))
     cache = TableCache()
 
     def batched():
+        if a.lifelong:
+            return [ex.lifelong_rows(pos, tables=cache)[0][1:] for ex, pos, _ in runs]
         return [ex.dataset_rows(pos, tables=cache)[0][1:] for ex, pos, _ in runs]
 
     def loop():
@@ -83,6 +98,7 @@ def bench_rows(a):
     same = all(torch.equal(x, wx) and torch.equal(y, wy) for (x, y), (wx, wy) in zip(got, want))
     rows = sum(int(x.shape[0]) for x, _ in got)
     solved = sum(int((ex.metrics()[:, 0] >= 1).sum()) for ex, _, _ in runs)
+    arrivals = sum(int(ex.env.goals_reached().sum()) for ex, _, _ in runs) if a.lifelong else None
     del got, want
     tb, tl = [], []
     for rep in range(a.repeats):
@@ -93,13 +109,14 @@ def bench_rows(a):
     t_hook = timed(batched)
     hooks = _lib.prof_read()
     _lib.prof_enable(False)
-    kern = {k: round(hooks[k][0], 4) for k in ("ds_paths", "ds_episode_tokens") if k in hooks}
+    kern = {k: round(hooks[k][0], 4) for k in ("ds_paths", "ds_episode_tokens", "ds_paths_lifelong", "ds_episode_tokens_lifelong") if k in hooks}
 
     def stats(t):
         return {"median_s": round(float(np.median(t)), 5), "min_s": round(min(t), 5), "max_s": round(max(t), 5),
                 "us_per_row": round(1e6 * float(np.median(t)) / max(rows, 1), 4)}
 
-    return {"tool": "bench_episode_rows", "mode": "rows", "map": f"maze {SIDE}x{SIDE}", "episodes": a.seeds * len(AGENTS), "solved": solved,
+    kind = {"mode": "rows", "lifelong": True, "arrivals": arrivals} if a.lifelong else {"mode": "rows", "solved": solved}
+    return {"tool": "bench_episode_rows", **kind, "map": f"maze {SIDE}x{SIDE}", "episodes": a.seeds * len(AGENTS),
             "rows": rows, "rows_equal": bool(same), "repeats": a.repeats, "batched": stats(tb), "loop": stats(tl),
             "speedup": round(float(np.median(tl)) / float(np.median(tb)), 2), "kernel_ms": kern,
             "kernel_share_of_pass": round(sum(kern.values()) / (1e3 * t_hook), 4), "hooked_pass_s": round(t_hook, 5)}
@@ -161,8 +178,12 @@ def main():
     ap.add_argument("--mode", choices=["rows", "e2e"], required=True)
     ap.add_argument("--seeds", type=int, default=0, help="seeds per agent count (rows: 100; e2e: 8)")
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_episode_rows.jsonl"))
+    ap.add_argument("--lifelong", action="store_true", help="--mode rows on a lifelong expert: lifelong_rows against records() -> the generator")
+    ap.add_argument("--out", default=None, help="default: profiles/bench_episode_rows.jsonl (bench_episode_rows_lifelong.jsonl with --lifelong)")
     a = ap.parse_args()
+    if a.lifelong and a.mode != "rows":
+        ap.error("--lifelong is a --mode rows run")
+    a.out = a.out or os.path.join(ROOT, "profiles", "bench_episode_rows_lifelong.jsonl" if a.lifelong else "bench_episode_rows.jsonl")
     a.seeds = a.seeds or (100 if a.mode == "rows" else 8)
     rec = bench_rows(a) if a.mode == "rows" else bench_e2e(a)
     line = json.dumps(rec)
