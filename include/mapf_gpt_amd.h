@@ -686,6 +686,28 @@ int mgpt_expert_copy_shield(mgpt_expert *ex, int32_t *d_first_out, int32_t *d_ov
 int mgpt_step_set_shield(mgpt_step *step, mgpt_expert *ex);
 int mgpt_step_copy_shield_logits(mgpt_step *step, float *d_out, void *stream);
 
+/* The collision shield on lifelong episodes (on_target = restart; DESIGN.md section 35: section 31's plan on the fields of the goals the
+ * agents hold now, section 30's rules after the env step).  Off by default: without it every call above behaves as it did, the shield's
+ * refusal of a lifelong env and of set_lifelong included.
+ *   set_shield_lifelong: on = 1 / 0, any other value is MGPT_ERR_ARG.  On a shield-mode context only (MGPT_ERR_STATE otherwise), before
+ *                  mgpt_expert_reset or between episodes (MGPT_ERR_STATE in the middle of one, read from the device as set_shield does).
+ *                  on = 1 allocates `held` u32 [n_inst][n_agents], `live` u8 [n_inst], `arrivals` int16 [n_inst][max_steps] and `steps`
+ *                  int32 [n_inst]; 0 frees them and restores the plain shield; mgpt_expert_set_shield(ex, 0) releases them too.  A reset
+ *                  must follow.  The order of calls is create (on an env that is not lifelong yet), set_shield(1), set_shield_lifelong(1),
+ *                  mgpt_env_set_lifelong, the resets.
+ *   reset / shield: with it on the env must be lifelong: MGPT_ERR_STATE otherwise (mgpt_env_set_lifelong must come first).  reset copies
+ *                  the env's goals into `held`, sets `live` and clears `arrivals` and `steps`.
+ *   shield_commit: launches the post-step kernel (timing-hook name expert_shield_lifelong_post) in the since update's place: since = 0 for
+ *                  an agent whose new cell is the goal it held during the step, else since + 1; held = the env's goals; the arrivals of the
+ *                  step go to arrivals[inst][steps[inst]] while that index is below max_steps, and steps[inst] grows by one -- no argument
+ *                  changes from step to step, so a captured step replays it.  It never calls the tokenizer: the distance fields of the
+ *                  agents whose goal changed are rebuilt by the caller, once per step and before the next plan, with
+ *                  mgpt_tokenizer_update_agents(goals_may_change = 1) -- in mgpt_step_run that is the update at the head of the next run;
+ *                  a caller that drives shield / env_step / shield_commit itself issues it between the env step and the commit.
+ *   copy_arrivals: mgpt_expert_copy_arrivals serves this mode as well.
+ */
+int mgpt_expert_set_shield_lifelong(mgpt_expert *ex, int on);
+
 /* ------------------------------------------------------------------------------------------
  * Kernel timing hooks (bench.py's live roofline): when enabled, the library brackets every kernel
  * class with hipEvents on the launch stream.  mgpt_prof_read synchronises the device.

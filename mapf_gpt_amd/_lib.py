@@ -145,6 +145,7 @@ SYMBOLS = {
     "mgpt_expert_shield": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "mgpt_expert_shield_commit": (_i, [_vp, _vp]),
     "mgpt_expert_copy_shield": (_i, [_vp, _vp, _vp, _vp]),
+    "mgpt_expert_set_shield_lifelong": (_i, [_vp, _i]),
     "mgpt_step_set_shield": (_i, [_vp, _vp]),
     "mgpt_step_copy_shield_logits": (_i, [_vp, _vp, _vp]),
     "mgpt_prof_enable": (_i, [_i]),

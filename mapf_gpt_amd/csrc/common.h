@@ -82,6 +82,7 @@ enum ProfId {
     P_STEP_RECORD,                                      // the episode recorder's store of a step (step.hip)
     P_DS_PATHS, P_DS_EPISODE_TOKENS,                    // batched episode tokenizer: paths + labels + records, rows (tokenizer.hip)
     P_DS_PATHS_LIFELONG, P_DS_EPISODE_TOKENS_LIFELONG,  // the same for lifelong logs: a goal per timestep (tokenizer.hip)
+    P_EXPERT_SHIELD_LIFELONG_POST,                      // the shield on lifelong episodes: since and the arrivals log after the env step (expert.hip)
     P_COUNT
 };
 

@@ -11,7 +11,9 @@
 // Opt-in lifelong episodes keep the plan kernel and change what follows the env step: the borrowed tokenizer
 // rebuilds the fields of the agents whose goal changed and pibt_lifelong_post_kernel stands in pibt_since_kernel's place.
 // An opt-in collision shield for a policy (pibt_shield_kernel) runs the same generator on the policy's action
-// preferences in the place of section 20's keys: the PREF = true instantiation.
+// preferences in the place of section 20's keys: the PREF = true instantiation.  Opt-in again, the shield runs on lifelong episodes
+// (DESIGN.md section 35): the plan is unchanged, pibt_shield_lifelong_post_kernel follows the env step with section 30's rules and a
+// step index that lives on the device, since a captured step is replayed without the host.
 //
 // One step of one instance:
 //   order      agents by (since desc, id asc), since = steps since the agent last stood on its goal;
@@ -557,6 +559,37 @@ __global__ __launch_bounds__(64) void pibt_lifelong_post_kernel(const uint32_t *
     for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
     if (lane == 0) {
         if (t < (int64_t)max_steps) arrivals[(size_t)inst * max_steps + t] = (int16_t)n;
+        live[inst] = done[inst] == 0 ? 1 : 0;
+    }
+}
+
+// ---- the shield on lifelong episodes: the post-step kernel, in pibt_since_kernel's place when
+// mgpt_expert_set_shield_lifelong is on -- pibt_lifelong_post_kernel's rules with the step index on the device ----------------------
+// The shield's launches are replayed from a captured graph and never pass the host, so the slot of the arrivals log is steps[inst], the
+// number of steps this instance has made since reset: lane 0 of the instance's own wave reads it, stores the step's arrivals only while
+// 0 <= k < max_steps (a graph replayed beyond the step cap writes nothing out of range) and stores k + 1.  No other wave touches the
+// counter: no race, no atomics.  The launch covers every instance, guarded by `live`; it does not read retire mode's live list.
+__global__ __launch_bounds__(64) void pibt_shield_lifelong_post_kernel(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ goal,
+                                                                       const uint8_t *__restrict__ done, uint32_t *__restrict__ since,
+                                                                       uint32_t *__restrict__ held, uint8_t *__restrict__ live,
+                                                                       int16_t *__restrict__ arrivals, int32_t *__restrict__ steps,
+                                                                       int n_inst, int n_agents, int max_steps)
+{
+    const int inst = blockIdx.x, lane = threadIdx.x;
+    if (inst >= n_inst || live[inst] == 0) return;                        // wave-uniform: done before this step, nothing moved
+    const size_t g0 = (size_t)inst * n_agents;
+    int n = 0;
+    for (int a = lane; a < n_agents; a += 64) {
+        const bool on = pos[g0 + a] == held[g0 + a];
+        since[g0 + a] = on ? 0u : since[g0 + a] + 1u;
+        held[g0 + a] = goal[g0 + a];
+        n += on ? 1 : 0;
+    }
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+    if (lane == 0) {
+        const int k = steps[inst];
+        if (k >= 0 && k < max_steps) arrivals[(size_t)inst * max_steps + k] = (int16_t)n;
+        steps[inst] = k + 1;
         live[inst] = done[inst] == 0 ? 1 : 0;
     }
 }
@@ -1108,7 +1141,15 @@ struct mgpt_expert {
         int32_t *overrides = nullptr;           // [n_inst] agents whose planned action was not the sampler's, since reset
         int32_t *started = nullptr;             // [1] 0 at reset, 1 once a shield launch has run (a replayed graph never passes the host)
     } sh;
-    DeviceArena mem, search_mem, deg_mem, refine_mem, lifelong_mem, shield_mem;   // occ .. len; ls; deg; rf; lf; sh
+    // the shield on lifelong episodes (mgpt_expert_set_shield_lifelong, shield mode only): off (all NULL) by default
+    bool shield_lifelong = false;
+    struct ShieldLifelong {                     // buffers, owned by shield_lifelong_mem
+        uint32_t *held = nullptr;               // [n_inst][n_agents] as Lifelong::held
+        uint8_t *live = nullptr;                // [n_inst] as Lifelong::live
+        int16_t *arrivals = nullptr;            // [n_inst][max_steps] arrivals per step
+        int32_t *steps = nullptr;               // [n_inst] steps made since reset: the slot of the next arrivals entry
+    } sl;
+    DeviceArena mem, search_mem, deg_mem, refine_mem, lifelong_mem, shield_mem, shield_lifelong_mem;   // occ .. len; ls; deg; rf; lf; sh; sl
 };
 
 // launches the SWAP instantiation of a kernel: one wave64 workgroup per instance, its arrays in dynamic LDS
@@ -1160,6 +1201,8 @@ static int expert_check_env(const mgpt_expert *ex)
     env_config(ex->env, &H, &W, &n_grids, &rules, &lifelong);
     if (ex->lifelong)
         MGPT_REQUIRE(lifelong, MGPT_ERR_STATE, "lifelong planning is on (mgpt_expert_set_lifelong): mgpt_env_set_lifelong must come first, the env has no goal queues");
+    else if (ex->shield_lifelong)
+        MGPT_REQUIRE(lifelong, MGPT_ERR_STATE, "the lifelong shield is on (mgpt_expert_set_shield_lifelong): mgpt_env_set_lifelong must come first, the env has no goal queues");
     else
         MGPT_REQUIRE(!lifelong, MGPT_ERR_UNSUPPORTED, "the PIBT expert does not plan lifelong (on_target = restart) episodes");
     MGPT_REQUIRE(rules == 0, MGPT_ERR_UNSUPPORTED, "the PIBT expert plans for the default collision rules only (env rule mask %d)", rules);
@@ -1234,6 +1277,12 @@ extern "C" int mgpt_expert_reset(mgpt_expert *ex, void *stream)
         MGPT_HIP(hipMemcpyAsync(ex->lf.held, ex->goal, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
         MGPT_HIP(hipMemsetAsync(ex->lf.live, 1, (size_t)ex->n_inst, s));
         MGPT_HIP(hipMemsetAsync(ex->lf.arrivals, 0, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t), s));
+    }
+    if (ex->shield_lifelong) {                               // the same, and no step made yet
+        MGPT_HIP(hipMemcpyAsync(ex->sl.held, ex->goal, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        MGPT_HIP(hipMemsetAsync(ex->sl.live, 1, (size_t)ex->n_inst, s));
+        MGPT_HIP(hipMemsetAsync(ex->sl.arrivals, 0, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t), s));
+        MGPT_HIP(hipMemsetAsync(ex->sl.steps, 0, (size_t)ex->n_inst * sizeof(int32_t), s));
     }
     ex->t = 0;
     ex->have_reset = true;
@@ -1355,8 +1404,10 @@ extern "C" int mgpt_expert_set_lifelong(mgpt_expert *ex, int on)
 extern "C" int mgpt_expert_copy_arrivals(mgpt_expert *ex, int16_t *d_arrivals_out, void *stream)
 {
     MGPT_REQUIRE(ex && d_arrivals_out, MGPT_ERR_ARG, "NULL argument");
-    MGPT_REQUIRE(ex->lifelong && ex->have_reset, MGPT_ERR_STATE, "mgpt_expert_set_lifelong and mgpt_expert_reset must precede mgpt_expert_copy_arrivals");
-    MGPT_HIP(hipMemcpyAsync(d_arrivals_out, ex->lf.arrivals, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t), hipMemcpyDeviceToDevice,
+    MGPT_REQUIRE((ex->lifelong || ex->shield_lifelong) && ex->have_reset, MGPT_ERR_STATE,
+                 "mgpt_expert_set_lifelong and mgpt_expert_reset must precede mgpt_expert_copy_arrivals");
+    const int16_t *arrivals = ex->lifelong ? ex->lf.arrivals : ex->sl.arrivals;         // (a shield-mode context: section 35's log)
+    MGPT_HIP(hipMemcpyAsync(d_arrivals_out, arrivals, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t), hipMemcpyDeviceToDevice,
                             (hipStream_t)stream));
     return MGPT_OK;
 }
@@ -1593,6 +1644,9 @@ extern "C" int mgpt_expert_set_shield(mgpt_expert *ex, int on)
     MGPT_REQUIRE(!running, MGPT_ERR_STATE, "mgpt_expert_set_shield in the middle of an episode (before mgpt_expert_reset or between episodes only)");
     if (on == (ex->shield ? 1 : 0)) return MGPT_OK;
     if (!on) {
+        ex->shield_lifelong_mem.release();                   // (section 35's buffers go with the shield)
+        ex->sl = mgpt_expert::ShieldLifelong();
+        ex->shield_lifelong = false;
         ex->shield_mem.release();
         ex->sh = mgpt_expert::Shield();
         ex->shield = false;
@@ -1645,11 +1699,58 @@ extern "C" int mgpt_expert_shield_commit(mgpt_expert *ex, void *stream)
 {
     MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(ex->shield && ex->have_reset, MGPT_ERR_STATE, "mgpt_expert_set_shield and mgpt_expert_reset must precede mgpt_expert_shield_commit");
+    if (ex->shield_lifelong) {                               // section 35: since against the goals held during the step, and the arrivals
+        hipStream_t s = (hipStream_t)stream;
+        ProfScope ps(P_EXPERT_SHIELD_LIFELONG_POST, s);
+        hipLaunchKernelGGL(pibt_shield_lifelong_post_kernel, dim3(ex->n_inst), dim3(64), 0, s, reinterpret_cast<const uint32_t *>(ex->pos),
+                           reinterpret_cast<const uint32_t *>(ex->goal), ex->done, ex->since, ex->sl.held, ex->sl.live, ex->sl.arrivals,
+                           ex->sl.steps, ex->n_inst, ex->n_agents, ex->max_steps);
+        MGPT_LAUNCH_CHECK();
+        return MGPT_OK;                                      // (the tokenizer is not called here: the caller rebuilds the fields once per step)
+    }
     const int total = ex->n_inst * ex->n_agents;
     hipLaunchKernelGGL(pibt_since_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, ex->pos, ex->goal, ex->done, ex->since, ex->n_inst,
                        ex->n_agents);
     MGPT_LAUNCH_CHECK();
     return MGPT_OK;                                          // (no host step counter: a captured step is replayed without this call)
+}
+
+// ---- the shield on lifelong episodes ---------------------------------------------------------------------------
+extern "C" int mgpt_expert_set_shield_lifelong(mgpt_expert *ex, int on)
+{
+    MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(on == 0 || on == 1, MGPT_ERR_ARG, "on=%d: 0 or 1", on);
+    MGPT_REQUIRE(ex->shield, MGPT_ERR_STATE, "mgpt_expert_set_shield(ex, 1) must precede mgpt_expert_set_shield_lifelong: it switches a shield-mode context");
+    bool running = false;
+    const int rc = episode_running(ex, &running);
+    if (rc != MGPT_OK) return rc;
+    MGPT_REQUIRE(!running, MGPT_ERR_STATE,
+                 "mgpt_expert_set_shield_lifelong in the middle of an episode (before mgpt_expert_reset or between episodes only)");
+    if (on == (ex->shield_lifelong ? 1 : 0)) return MGPT_OK;
+    if (!on) {
+        ex->shield_lifelong_mem.release();
+        ex->sl = mgpt_expert::ShieldLifelong();
+        ex->shield_lifelong = false;
+        ex->have_reset = false;                              // what the last reset prepared was a lifelong episode's state
+        return MGPT_OK;
+    }
+    DeviceArena mem;
+    mgpt_expert::ShieldLifelong sl;
+    hipError_t e = mem.alloc(&sl.held, (size_t)ex->n_inst * ex->n_agents * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(&sl.live, (size_t)ex->n_inst);
+    if (e == hipSuccess) e = mem.alloc(&sl.arrivals, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t));
+    if (e == hipSuccess) e = mem.alloc(&sl.steps, (size_t)ex->n_inst * sizeof(int32_t));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("device allocation failed in mgpt_expert_set_shield_lifelong (%d instances x %d agents): %s", ex->n_inst, ex->n_agents,
+                  hipGetErrorString(e));
+        return MGPT_ERR_HIP;
+    }
+    ex->sl = sl;
+    ex->shield_lifelong_mem = std::move(mem);
+    ex->shield_lifelong = true;
+    ex->have_reset = false;                                  // held / live / arrivals / steps are prepared by the next reset
+    return MGPT_OK;
 }
 
 extern "C" int mgpt_expert_copy_shield(mgpt_expert *ex, int32_t *d_first_out, int32_t *d_overrides_out, void *stream)

@@ -31,7 +31,8 @@ static const char *kProfNames[P_COUNT] = {
     "expert_refine_path", "expert_refine_round", "expert_refine_final",
     "expert_lifelong_post", "expert_shield", "step_record",
     "ds_paths", "ds_episode_tokens",
-    "ds_paths_lifelong", "ds_episode_tokens_lifelong"};
+    "ds_paths_lifelong", "ds_episode_tokens_lifelong",
+    "expert_shield_lifelong_post"};
 
 struct ProfState {
     std::mutex mu;

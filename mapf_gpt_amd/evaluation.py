@@ -242,7 +242,10 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
     status 4, final status 1) and `soc_before` / `soc_after` summed over the refined instances.
     A MAPF-GPT entry with `shield: pibt` runs its policy behind the collision shield (BatchedRunner(shield="pibt"), DESIGN.md section 31);
     its records also carry `shield_overrides`: the agents whose planned action was not the sampled one, summed over the episode and
-    divided by ep_length x num_agents.  Such an entry raises on an on_target="restart" group, as log_actions does.
+    divided by ep_length x num_agents.  Such an entry raises on an on_target="restart" group, as log_actions does, unless it also says
+    `shield_lifelong: true`: its restart groups then run behind BatchedRunner(shield="pibt", shield_lifelong=True)
+    on the seeded queue every policy entry gets, and their records carry `avg_throughput` and `shield_overrides`; its on_target="nothing"
+    groups run the plain shield as before.
     record: MAPF-GPT entries run a recording runner (BatchedRunner(record=True)) and their records also carry
     `made_actions` (the actions the env was handed, cut to the episode's length), `init_positions` and `moves` (the actions the env
     executed); one rank only, as log_actions, which keeps its meaning (the expert's logs).  on_batch(info): called after each policy
@@ -282,7 +285,8 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                 raise NotImplementedError("the PIBT expert does not plan lifelong (on_target='restart') episodes unless its entry says "
                                           "lifelong: true")
             shield = None if is_pibt else getattr(cfg, "shield", None)
-            if shield and on_target == "restart":
+            shield_lifelong = bool(shield) and on_target == "restart" and bool(getattr(cfg, "shield_lifelong", False))
+            if shield and on_target == "restart" and not shield_lifelong:
                 raise NotImplementedError("shield: pibt does not plan lifelong (on_target='restart') episodes")
             parsed = [registry.get(runs[i][0]["map_name"]) for i in idxs]
             frames = dict(zip(idxs, common_frame(parsed)))
@@ -313,7 +317,7 @@ def evaluation(evaluation_config, eval_dir=None, registry=None, precision=None, 
                         run = BatchedRunner(grids, len(mine), n_agents, algo.net, max_episode_steps=max_steps,
                                             seed=int(cfg.seed or 0), do_sample=True, precision=cfg.precision, device=cfg.device,
                                             row_offset=lo * n_agents, retire_done=bool(retire_done), **({"shield": shield} if shield else {}),
-                                            **({"record": True} if record else {}))
+                                            **({"shield_lifelong": True} if shield_lifelong else {}), **({"record": True} if record else {}))
                     queue = None
                     if on_target == "restart":          # lifelong: a seeded queue of further goals per agent (wraps)
                         queue = np.empty((len(mine), n_agents, LIFELONG_QUEUE, 2), np.int16)

@@ -43,6 +43,11 @@ policy's action preferences as every agent's candidate order.  `env=` / `tok=` t
 count of agents per instance whose planned action was not the policy's.  step() and run() are refused.  Not together with search=,
 swap=, refine_rounds= or lifelong=.  Off by default.
 
+`shield_lifelong=True` (with shield=True) runs the shield on lifelong episodes: reset() takes the env's goal queues
+as with lifelong=True, the plan is section 31's on the fields of the goals the agents hold now, and what follows the env step is section
+30's: since against the goal held during the step, the arrivals of every step (arrivals(), throughput()).  shield_step() is then plan ->
+env step -> tokenizer update (goals_may_change=1: the fields of the agents whose goal changed) -> commit.  Off by default.
+
 The config is an evaluation YAML (eval_configs/<folder>/<folder>.yaml): its `environment:` block is run; its `algorithms:` block is
 replaced by one PIBT entry (seed from --seed).  DIR/PIBT.json is what `dataset_build.split_by_map` and `dataset_build --logs` take
 where the reference has LaCAM.json.  Prints one JSON line: episodes, solved, rows, seconds (with --algo lacam also `status`: the
@@ -77,10 +82,11 @@ from .observation_generator import BatchedTokenizer
 
 class BatchedExpert:
     """Same shape as BatchedRunner: owns a BatchedEnv and a BatchedTokenizer (used for its BFS distance fields only)."""
+    shield = shield_lifelong = False                              # (what reset()'s own checks read on an object that was never initialised)
 
     def __init__(self, grids, n_inst, n_agents, max_episode_steps, seed=0, device="cuda", inst_offset=0, search=None, max_iters=4096,
                  iters_per_launch=None, hash_bits=0, swap=False, refine_rounds=0, refine_horizon=None, lifelong=False, shield=False, env=None,
-                 tok=None):
+                 tok=None, shield_lifelong=False):
         if search not in (None, "lacam"):
             raise ValueError(f"search={search!r}: None or 'lacam'")
         if lifelong and search:
@@ -89,6 +95,8 @@ class BatchedExpert:
             raise ValueError("refine_rounds needs search='lacam': the pass refines what the search found")
         if shield and (search or swap or refine_rounds or lifelong):
             raise ValueError("shield=True with search=, swap=, refine_rounds= or lifelong=: the shield runs plain PIBT on the policy's candidate order")
+        if shield_lifelong and not shield:
+            raise ValueError("shield_lifelong=True needs shield=True: it switches what follows the env step of a shield-mode context")
         if (env is not None or tok is not None) and not shield:
             raise ValueError("env= / tok= need shield=True: an expert of its own makes its env and tokenizer")
         self.device = torch.device(device)
@@ -117,8 +125,18 @@ class BatchedExpert:
         if lifelong:
             self.set_lifelong(True)
         self.shield = False
+        self.shield_lifelong = False
         if shield:
             self.set_shield(True)
+        if shield_lifelong:
+            self.set_shield_lifelong(True)
+
+    def set_shield_lifelong(self, on):
+        """Turn the shield's lifelong mode on or off (shield mode only): before reset() or between episodes (MGPTError with ERR_STATE on a
+        context that is not in shield mode, or in the middle of an episode); reset() must follow."""
+        with _lib.on_device(self.device):
+            _lib.check(_lib.lib().mgpt_expert_set_shield_lifelong(self._h, 1 if on else 0))
+        self.shield_lifelong = bool(on)
 
     def set_shield(self, on):
         """Turn shield mode on or off: before reset() or between episodes (MGPTError with ERR_STATE in the middle of one, with
@@ -126,6 +144,8 @@ class BatchedExpert:
         with _lib.on_device(self.device):
             _lib.check(_lib.lib().mgpt_expert_set_shield(self._h, 1 if on else 0))
         self.shield = bool(on)
+        if not on:
+            self.shield_lifelong = False                          # (the library releases section 35's buffers with the shield)
 
     def reset_shield(self):
         """Shield mode over a borrowed env and tokenizer (BatchedRunner): the expert's own part of reset(), after theirs."""
@@ -136,13 +156,17 @@ class BatchedExpert:
 
     def shield_step(self, logits, first):
         """logits float32 [n_inst * n_agents, >= 5] (or [n_inst, n_agents, >= 5]), first int32 [n_inst, n_agents]: the policy's logits and
-        sampled actions -> the planned actions int32 [n_inst, n_agents] (self.actions), already executed by the env."""
+        sampled actions -> the planned actions int32 [n_inst, n_agents] (self.actions), already executed by the env.  With
+        shield_lifelong=True the tokenizer rebuilds the fields of the agents whose goal changed between the env step and the commit."""
         logits = logits.to(self.device, torch.float32).reshape(self.n_inst * self.n_agents, -1).contiguous()
         self.actions.copy_(first.to(self.device, torch.int32).reshape(self.n_inst, self.n_agents))
         with _lib.on_device(self.device):
             L, s = _lib.lib(), _lib.stream_ptr()
             _lib.check(L.mgpt_expert_shield(self._h, _lib.ptr(logits), int(logits.shape[1]), None, None, _lib.ptr(self.actions.view(-1)), s))
             _lib.check(L.mgpt_env_step(self.env._h, _lib.ptr(self.actions.view(-1)), s))
+            if self.shield_lifelong:
+                pos, goal, _ = self.env.state_ptrs()
+                _lib.check(L.mgpt_tokenizer_update_agents(self.tok._h, pos, goal, _lib.ptr(self.actions.view(-1)), 1, s))
             _lib.check(L.mgpt_expert_shield_commit(self._h, s))
         self.t += 1
         return self.actions
@@ -191,10 +215,11 @@ class BatchedExpert:
             self._h = None
 
     def reset(self, pos, goal, goal_queue=None):
-        """goal_queue int16 [n_inst, n_agents, Q, 2]: required with lifelong=True (the env's goal queues), refused without it."""
-        if self.lifelong:
+        """goal_queue int16 [n_inst, n_agents, Q, 2]: required with lifelong=True or shield_lifelong=True (the env's goal queues), refused
+        without them."""
+        if self.lifelong or self.shield_lifelong:
             if goal_queue is None:
-                raise ValueError("lifelong=True: reset() needs goal_queue, int16 [n_inst, n_agents, Q, 2]")
+                raise ValueError(f"{'lifelong' if self.lifelong else 'shield_lifelong'}=True: reset() needs goal_queue, int16 [n_inst, n_agents, Q, 2]")
             q = torch.as_tensor(goal_queue)
             if q.dim() != 4 or tuple(q.shape[:2]) != (self.n_inst, self.n_agents) or q.shape[2] < 1 or q.shape[3] != 2:
                 raise ValueError(f"goal_queue {tuple(q.shape)}: [n_inst={self.n_inst}, n_agents={self.n_agents}, Q >= 1, 2]")
@@ -206,7 +231,7 @@ class BatchedExpert:
                                        q.to(self.device, torch.int16)], dim=2).contiguous()
         else:
             if goal_queue is not None:
-                raise ValueError("goal_queue needs lifelong=True")
+                raise ValueError("goal_queue needs lifelong=True" + (" (a shield: shield_lifelong=True)" if self.shield else ""))
             if self.env.lifelong:                                 # an earlier lifelong episode on this context
                 self.env.set_lifelong(None)
         self.env.reset(pos, goal)
@@ -272,7 +297,8 @@ class BatchedExpert:
         return log, lens
 
     def arrivals(self):
-        """int16 [n_inst, T]: arrivals per instance and step (lifelong mode; device tensor; T = max_episode_steps)."""
+        """int16 [n_inst, T]: arrivals per instance and step (lifelong mode, or a shield with shield_lifelong=True; device tensor; T =
+        max_episode_steps)."""
         out = torch.empty((self.n_inst, self.max_episode_steps), dtype=torch.int16, device=self.device)
         with _lib.on_device(self.device):
             _lib.check(_lib.lib().mgpt_expert_copy_arrivals(self._h, _lib.ptr(out), _lib.stream_ptr()))

@@ -62,6 +62,9 @@ class MAPFGPTInferenceConfig(BaseModel):
     # extension: "pibt" puts the collision shield between the policy and the env.  Read by evaluation.py only, which
     # hands it to BatchedRunner; the list API below (act / act_batch) steps an env it does not own and ignores the field with one warning.
     shield: Optional[str] = None
+    # extension: with shield "pibt", true also runs the entry's on_target: restart groups behind the shield; without
+    # it such a group raises as before.  Read by evaluation.py only, like `shield`.
+    shield_lifelong: bool = False
 
 
 def strip_prefix_from_state_dict(state_dict, prefix="_orig_mod."):

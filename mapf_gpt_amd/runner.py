@@ -20,6 +20,10 @@ shield="pibt" (opt-in) puts a collision shield between the policy and the env (D
 and the logits go through one PIBT step per instance, with each agent's candidates in the policy's order of preference, and the env
 executes the planned actions -- nobody steps into a conflict, so the env's rules never make an agent wait.
 
+shield_lifelong=True (opt-in, with shield="pibt") runs that shield on lifelong episodes: the runner is then
+lifelong-only, reset() needs a goal_queue, the plan reads the fields of the goals the agents hold now (the step's own update_agents
+rebuilds them) and arrivals() is the count of arrivals per instance and step.  Without it a shield refuses a goal_queue as before.
+
 record=True (opt-in) keeps the episode on the device: one more launch per step stores every agent's position after
 the step and the action the env was handed; trajectory() hands the buffers out as tensors, records() as toolbox records with
 `made_actions`, `init_positions` and `moves` (the action the env executed), which is what mapf_gpt_amd.ddg relabels.
@@ -84,10 +88,15 @@ def moves_from_positions(pos):
 
 
 class BatchedRunner:
+    shield_lifelong = False
+
     def __init__(self, grids, n_inst, n_agents, net, max_episode_steps=128, seed=0, do_sample=True, precision=None,
-                 device="cuda", row_offset=0, use_graph=False, retire_done=False, poll_every=8, shield=None, record=False):
+                 device="cuda", row_offset=0, use_graph=False, retire_done=False, poll_every=8, shield=None, record=False,
+                 shield_lifelong=False):
         if shield not in (None, "pibt"):
             raise ValueError(f"shield={shield!r}: None or 'pibt'")
+        if shield_lifelong and shield != "pibt":
+            raise ValueError("shield_lifelong=True needs shield='pibt': it is the shield that runs on lifelong episodes")
         if retire_done and use_graph:
             raise ValueError("retire_done=True runs eager launches only: the policy's row count changes from poll to poll, use_graph=True cannot replay it")
         if int(poll_every) < 1:
@@ -119,10 +128,12 @@ class BatchedRunner:
         self._live, self._rows_forwarded, self._polled_t = n_inst, 0, -1
         if retire_done:
             self.set_retire_done(True)
-        self.shield, self._shield = shield, None
+        self.shield, self._shield, self.shield_lifelong = shield, None, bool(shield_lifelong)
         if shield:
             from .expert import BatchedExpert
-            self._shield = BatchedExpert(grids, n_inst, n_agents, max_episode_steps, device=device, shield=True, env=self.env, tok=self.tok)
+            # (shield_lifelong: switched here, once, before the env gets its queues in reset())
+            self._shield = BatchedExpert(grids, n_inst, n_agents, max_episode_steps, device=device, shield=True, env=self.env, tok=self.tok,
+                                         **({"shield_lifelong": True} if shield_lifelong else {}))
             with torch.cuda.device(self.device):
                 _lib.check(_lib.lib().mgpt_step_set_shield(self._step, self._shield._h))
         self.record = False
@@ -173,6 +184,13 @@ class BatchedRunner:
             raise RuntimeError("shield_overrides() needs shield='pibt'")
         return self._shield.shield_overrides()
 
+    def arrivals(self):
+        """shield_lifelong=True: int16 [n_inst, T] arrivals per instance and step since reset() (device tensor; T = max_episode_steps);
+        an instance's sum is the env's own arrival count, the figure behind avg_throughput."""
+        if not self.shield_lifelong:
+            raise RuntimeError("arrivals() needs shield='pibt' with shield_lifelong=True")
+        return self._shield.arrivals()
+
     def shield_state(self):
         """Tests: (logits float32 [rows, 67], first int32 [n_inst, n_agents], actions int32 [n_inst, n_agents], planned int16 [n_inst,
         n_agents, 2]) of the last step.  In retire mode the logits are the compact rows of live_state()."""
@@ -214,7 +232,10 @@ class BatchedRunner:
     def reset(self, pos, goal, goal_queue=None):
         """goal_queue int16 [n_inst, n_agents, Q, 2]: lifelong mode (on_target="restart"), the tokenizer then re-checks
         goals every step (observation_generator.cpp:464-477)."""
-        if goal_queue is not None and self._shield is not None:
+        if self.shield_lifelong:
+            if goal_queue is None:
+                raise ValueError("shield_lifelong=True: reset() needs goal_queue, int16 [n_inst, n_agents, Q, 2] (the runner is lifelong-only)")
+        elif goal_queue is not None and self._shield is not None:
             raise NotImplementedError("shield='pibt' does not plan lifelong (goal_queue) episodes")
         if goal_queue is not None or self.env.lifelong:
             self.env.set_lifelong(goal_queue)
