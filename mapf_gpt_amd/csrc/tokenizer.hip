@@ -14,9 +14,10 @@
 //                     neighbours ranked through a distance-bucket table in LDS, row assembled in LDS
 //                                                                                        (cpp:288-311, 487-528, 352-389)
 //   ds_* kernels      dataset-side bulk tokenizer (dataset/tokenizer/*): all-pairs BFS table per map, one row per
-//                     (agent, timestep) of a logged episode
-//   ds_offsets / ds_paths / ds_episode_tokens   the same rows for a batch of episodes of one map, straight from the expert's device log
-//   ds_paths_lifelong / ds_episode_tokens_lifelong   ... of lifelong episodes: the goal of every timestep derived from the agents' target lists
+//                     (agent, timestep) of a logged episode.  Every row is made by ds_row:
+//     ds_records / ds_tokens                      one episode, from its paths
+//     ds_offsets / ds_paths<> / ds_episode_tokens<>   a batch of episodes of one map, straight from the expert's device log; <true>: lifelong
+//                                                 episodes, the goal of every timestep derived from the agents' target lists
 #include "common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -720,6 +721,9 @@ __global__ __launch_bounds__(256) void ds_records_kernel(const int16_t *__restri
 
 constexpr int kDsAgentsPerBlock = 16;
 constexpr int kDsMaxCand = 128;
+constexpr int kDsRowBytes = 272;                 // a wave's row image in LDS: token t at byte t + 1, so 257 bytes rounded up to 16
+constexpr uint32_t kDsPadWord = 0x42424242u;     // four TOK_PAD
+static_assert(kDsPadWord == TOK_PAD * 0x01010101u, "the row image is preset to the pad token");
 
 // window value -> token (cost2go.cpp:72-85 + encoder.cpp:52-73): unreachable -> -80, else clamp(v - mid) to +-20 / +-40
 __device__ __forceinline__ int window_token(int v, int mid)
@@ -729,91 +733,111 @@ __device__ __forceinline__ int window_token(int v, int mid)
     return w > kLimit ? TOK_POS : (w < -kLimit ? TOK_NEG : w + kLimit);
 }
 
-// The window is cut from the field of the PATH'S LAST CELL (generate_observations.py:75-78) -- in lifelong logs that is not
-// the goal the record carries; only_obstacles = the mask_cost2go ablation (cost2go.cpp:52-62: cell -> 0 / 1 = blocked).
+// The dynamic LDS of every kernel that makes dataset rows: the timestep's records, then per wave a candidate list and a row image.
+constexpr size_t ds_row_lds_bytes(int n_agents) { return (size_t)n_agents * 16 + 4 * kDsMaxCand * 4 + 4 * kDsRowBytes; }
+
+// Stage the n_agents records of one timestep (`grec`) in LDS and hand out this wave's areas.  Every thread of the block calls it.
+__device__ __forceinline__ void ds_stage_records(char *smem, const uint4 *__restrict__ grec, int n_agents, const uint4 *&srec,
+                                                 uint32_t *&cand, uint8_t *&row)
+{
+    uint4 *rec = reinterpret_cast<uint4 *>(smem);                                         // [n_agents]
+    uint32_t *scand = reinterpret_cast<uint32_t *>(smem + (size_t)n_agents * 16);         // [4][kDsMaxCand]
+    uint8_t *srow = reinterpret_cast<uint8_t *>(scand + 4 * kDsMaxCand);                  // [4][kDsRowBytes]
+    const int tid = threadIdx.x, wave = tid >> 6;
+    for (int i = tid; i < n_agents; i += 256) rec[i] = grec[i];
+    __syncthreads();
+    srec = rec;
+    cand = scand + wave * kDsMaxCand;
+    row = srow + wave * kDsRowBytes;
+}
+
+// One dataset row, made by one wave: the agent of the staged timestep whose record is `me` -> the 256 tokens at `dst`.  The one row body of
+// the per-episode, batched and lifelong routes.  The window is cut from table row `field_cell`, the field of the PATH'S LAST CELL
+// (generate_observations.py:75-78; in lifelong logs that is not the goal the record carries), all unreachable when !field_ok;
+// only_obstacles = the mask_cost2go ablation (cost2go.cpp:52-62: cell -> 0 / 1 = blocked).  A window keeps its first kDsMaxCand
+// reachable neighbours in id order; keys hold the id in 11 bits (n_agents <= 2048).
+__device__ __forceinline__ void ds_row(const uint4 *srec, uint32_t *cand, uint8_t *row, int lane, uint4 me, int n_agents, int H, int W,
+                                       const uint16_t *__restrict__ allpairs, int field_cell, bool field_ok, int only_obstacles,
+                                       uint8_t *__restrict__ dst)
+{
+    const int cells = H * W;
+    const int pr = (int16_t)(me.x & 0xffffu), pc = (int16_t)(me.x >> 16);
+    const uint16_t *dg = allpairs + (size_t)(field_ok ? field_cell : 0) * cells;          // the window's field = a table row
+    const uint16_t *dm = allpairs + (size_t)(pr * W + pc) * cells;                        // distances from my own cell
+    if (lane < kDsRowBytes / 8) reinterpret_cast<uint2 *>(row)[lane] = make_uint2(kDsPadWord, kDsPadWord);
+    // --- window (cost2go.cpp:44-88) ---
+    int v[2];
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        const int cell = lane + 64 * u, i = cell / kWin, j = cell - i * kWin;
+        const int rr = pr - kR + i, cc = pc - kR + j;
+        v[u] = (field_ok && cell < kWin * kWin && rr >= 0 && rr < H && cc >= 0 && cc < W) ? (int)dg[rr * W + cc] : kUnreach;
+    }
+    const int mid = __shfl(v[0], kR * kWin + kR);
+    // --- neighbours in the window, reachable from my cell, keyed (BFS distance, id) (:121-141) ---
+    int cnt = 0;
+    for (int b0 = 0; b0 < n_agents; b0 += 64) {
+        const int b = b0 + lane;
+        bool in = false;
+        uint32_t key = 0;
+        if (b < n_agents) {
+            const uint32_t bp = srec[b].x;
+            const int br = (int16_t)(bp & 0xffffu), bc = (int16_t)(bp >> 16);
+            if (abs(br - pr) <= kR && abs(bc - pc) <= kR && br >= 0 && br < H && bc >= 0 && bc < W) {
+                const int d = dm[br * W + bc];
+                in = d != kUnreach;
+                key = ((uint32_t)d << 11) | (uint32_t)b;
+            }
+        }
+        const unsigned long long bm = __ballot(in);
+        if (in) {
+            const int at = cnt + __popcll(bm & ((1ull << lane) - 1ull));
+            if (at < kDsMaxCand) cand[at] = key;
+        }
+        cnt += __popcll(bm);
+    }
+    cnt = min(cnt, kDsMaxCand);
+    wave_lds_sync();
+    if (only_obstacles) {                                                                 // tokens of the integers 1 / 0
+        row[1 + lane] = (uint8_t)(kLimit + (v[0] == kUnreach ? 1 : 0));
+        if (lane + 64 < kWin * kWin) row[65 + lane] = (uint8_t)(kLimit + (v[1] == kUnreach ? 1 : 0));
+    } else {
+        row[1 + lane] = (uint8_t)window_token(v[0], mid);
+        if (lane + 64 < kWin * kWin) row[65 + lane] = (uint8_t)window_token(v[1], mid);
+    }
+    for (int c = lane; c < cnt; c += 64) {
+        const uint32_t key = cand[c];
+        int rank = 0;
+        for (int j = 0; j < cnt; j++) rank += (cand[j] < key) ? 1 : 0;
+        if (rank < kSlots) emit_record(row, rank, srec[key & 0x7ffu], me.x);              // (the record's goal: the one pursued at t)
+    }
+    wave_lds_sync();
+    const uint32_t *row32 = reinterpret_cast<const uint32_t *>(row);
+    const uint32_t packed = __builtin_amdgcn_alignbyte(row32[lane + 1], row32[lane], 1);  // tokens 4 * lane .. 4 * lane + 3
+    reinterpret_cast<uint32_t *>(dst)[lane] = packed;
+    __builtin_amdgcn_wave_barrier();                                                      // (the next row presets `row` after these reads)
+}
+
+// The per-episode route: records [timestep][agent] (ds_records_kernel), the window's cell = the last cell of `paths`, rows [agent][timestep].
 __global__ __launch_bounds__(256) void ds_tokens_kernel(const AgentRec *__restrict__ recs, const uint16_t *__restrict__ allpairs,
                                                         const int16_t *__restrict__ paths, int only_obstacles,
                                                         int n_agents, int n_steps, int H, int W, int chunks_per_step,
                                                         uint8_t *__restrict__ tokens)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint4 *srec = reinterpret_cast<uint4 *>(smem);                                        // [n_agents]
-    uint32_t *scand = reinterpret_cast<uint32_t *>(smem + (size_t)n_agents * 16);         // [4][kDsMaxCand]
-    uint8_t *srow = reinterpret_cast<uint8_t *>(scand + 4 * kDsMaxCand);                  // [4][272], token t at byte t + 1
     const int t = blockIdx.x / chunks_per_step, chunk = blockIdx.x - t * chunks_per_step;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint4 *grec = reinterpret_cast<const uint4 *>(recs) + (size_t)t * n_agents;
-    for (int i = tid; i < n_agents; i += 256) srec[i] = grec[i];
-    __syncthreads();
-    uint32_t *cand = scand + wave * kDsMaxCand;
-    uint8_t *row = srow + wave * 272;
-    const int cells = H * W;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint4 *srec;
+    uint32_t *cand;
+    uint8_t *row;
+    ds_stage_records(smem, reinterpret_cast<const uint4 *>(recs) + (size_t)t * n_agents, n_agents, srec, cand, row);
     for (int q = 0; q < kDsAgentsPerBlock / 4; q++) {
         const int a = chunk * kDsAgentsPerBlock + wave + 4 * q;
         if (a >= n_agents) break;                                                         // wave-uniform
-        const uint4 me = srec[a];
-        const int pr = (int16_t)(me.x & 0xffffu), pc = (int16_t)(me.x >> 16);
         const int16_t *pend = paths + ((size_t)a * n_steps + (n_steps - 1)) * 2;
         const int gr = pend[0], gc = pend[1];
-        const bool gok = gr >= 0 && gr < H && gc >= 0 && gc < W;
-        const uint16_t *dg = allpairs + (size_t)(gok ? gr * W + gc : 0) * cells;          // distance-to-goal field = a table row
-        const uint16_t *dm = allpairs + (size_t)(pr * W + pc) * cells;                    // distances from my own cell
-        if (lane < 34) reinterpret_cast<uint2 *>(row)[lane] = make_uint2(0x42424242u, 0x42424242u);
-        // --- window (cost2go.cpp:44-88) ---
-        int v[2];
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            const int cell = lane + 64 * u, i = cell / kWin, j = cell - i * kWin;
-            const int rr = pr - kR + i, cc = pc - kR + j;
-            v[u] = (gok && cell < kWin * kWin && rr >= 0 && rr < H && cc >= 0 && cc < W) ? (int)dg[rr * W + cc] : kUnreach;
-        }
-        const int mid = __shfl(v[0], kR * kWin + kR);
-        // --- neighbours in the window, reachable from my cell, keyed (BFS distance, id) (:121-141) ---
-        int cnt = 0;
-        for (int b0 = 0; b0 < n_agents; b0 += 64) {
-            const int b = b0 + lane;
-            bool in = false;
-            uint32_t key = 0;
-            if (b < n_agents) {
-                const uint32_t bp = srec[b].x;
-                const int br = (int16_t)(bp & 0xffffu), bc = (int16_t)(bp >> 16);
-                if (abs(br - pr) <= kR && abs(bc - pc) <= kR && br >= 0 && br < H && bc >= 0 && bc < W) {
-                    const int d = dm[br * W + bc];
-                    in = d != kUnreach;
-                    key = ((uint32_t)d << 11) | (uint32_t)b;
-                }
-            }
-            const unsigned long long bm = __ballot(in);
-            if (in) {
-                const int at = cnt + __popcll(bm & ((1ull << lane) - 1ull));
-                if (at < kDsMaxCand) cand[at] = key;
-            }
-            cnt += __popcll(bm);
-        }
-        cnt = min(cnt, kDsMaxCand);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (only_obstacles) {                                                             // tokens of the integers 1 / 0
-            row[1 + lane] = (uint8_t)(kLimit + (v[0] == kUnreach ? 1 : 0));
-            if (lane + 64 < kWin * kWin) row[65 + lane] = (uint8_t)(kLimit + (v[1] == kUnreach ? 1 : 0));
-        } else {
-            row[1 + lane] = (uint8_t)window_token(v[0], mid);
-            if (lane + 64 < kWin * kWin) row[65 + lane] = (uint8_t)window_token(v[1], mid);
-        }
-        for (int c = lane; c < cnt; c += 64) {
-            const uint32_t key = cand[c];
-            int rank = 0;
-            for (int j = 0; j < cnt; j++) rank += (cand[j] < key) ? 1 : 0;
-            if (rank < kSlots) emit_record(row, rank, srec[key & 0x7ffu], me.x);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint32_t *row32 = reinterpret_cast<const uint32_t *>(row);
-        const uint32_t packed = __builtin_amdgcn_alignbyte(row32[lane + 1], row32[lane], 1);
-        reinterpret_cast<uint32_t *>(tokens + ((size_t)a * n_steps + t) * 256)[lane] = packed;      // [agent][timestep][256]
-        __builtin_amdgcn_wave_barrier();
+        ds_row(srec, cand, row, lane, srec[a], n_agents, H, W, allpairs, gr * W + gc, gr >= 0 && gr < H && gc >= 0 && gc < W, only_obstacles,
+               tokens + ((size_t)a * n_steps + t) * 256);
     }
 }
 
@@ -831,9 +855,18 @@ __global__ __launch_bounds__(256) void ds_tokens_kernel(const AgentRec *__restri
 //   ds_episode_tokens_kernel  grid (episode x chunk of 16 agents, timestep <= max_steps), early exit past the episode's length
 // Records are kept timestep-major inside an episode (row0[k] - row0[0] + t * n_agents + a), as the neighbour search stages them; rows and
 // labels go to their absolute offsets, so a call may be handed a window of a longer scan (dataset_tokenizer.tokenize_episodes splits so).
-// ds_records_kernel / ds_tokens_kernel are not touched: a row body shared with them as one inlined function compiled them to other
-// instruction streams (section 33), so ds_episode_tokens_kernel restates the row of ds_tokens_kernel over next_action_token,
-// window_token and emit_record, with the goal read from the agent's own record.
+// ds_episode_tokens_kernel makes its rows with ds_row, the row body of ds_tokens_kernel, with the window's cell read from the agent's own
+// record (section 36).
+//
+// Batched LIFELONG episodes = the kLifelong instantiations of the two kernels: a goal per timestep
+// (generate_observations.py:55-60, 143-153).  An agent's target list is target(0), target(1), ...; walking its path t = 0 .. len with
+// cur = 0: a cell equal to target(cur) advances cur by one (an `if`, also at t = 0, before the cell's goal is read) and the goal at t is
+// target(cur).  Every record carries that goal (relative goal + greedy bits from the goal's table row); the WINDOW stays that of the path's
+// last cell (:75-78), which therefore travels apart from the records: `last` [selected episode of this call][agent] = (row | col << 16).
+// targets int16 [n_batch][n_agents][L][2]: target(0) = entry 0, target(j >= 1) = entry 1 + (j - 1) % (L - 1) -- the expert's (goal at
+// reset, cyclic queue) as it lies; n_targets int32 [n_batch][n_agents] or NULL (L each) bounds j.  A walk that reaches n_targets (the
+// reference's IndexError) stores 1 to *status and goes on with the last valid index: its rows are unspecified, its accesses in bounds.
+// A target outside the frame is what ds_records_kernel makes of such a goal: no table read, TOK_BITS0.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ int ds_episode_of(const int32_t *__restrict__ episodes, int k) { return episodes != nullptr ? episodes[k] : k; }
 
@@ -860,10 +893,14 @@ __global__ __launch_bounds__(256) void ds_offsets_kernel(int n_sel, int n_agents
     if (tid == 255) row0[n_sel] = at;                                                 // (thread 255's run ends at n_sel, or is empty behind it)
 }
 
+// targets, L, n_targets, status and last are read and written by the kLifelong instantiation only.
+template <bool kLifelong>
 __global__ __launch_bounds__(256) void ds_paths_kernel(int n_sel, int n_agents, int max_steps, int H, int W, const int16_t *__restrict__ init,
                                                        const int8_t *__restrict__ actions, const int32_t *__restrict__ episodes,
                                                        const int64_t *__restrict__ row0, const uint16_t *__restrict__ allpairs,
-                                                       AgentRec *__restrict__ recs, int8_t *__restrict__ labels)
+                                                       const int16_t *__restrict__ targets, int L, const int32_t *__restrict__ n_targets,
+                                                       int32_t *__restrict__ status, AgentRec *__restrict__ recs, uint32_t *__restrict__ last,
+                                                       int8_t *__restrict__ labels)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_sel * n_agents) return;
@@ -882,17 +919,31 @@ __global__ __launch_bounds__(256) void ds_paths_kernel(int n_sel, int n_agents, 
         c = min(max(c + (v == 4) - (v == 3), 0), W - 1);
     };
     const int ir = min(max((int)init[2 * ea], 0), H - 1), ic = min(max((int)init[2 * ea + 1], 0), W - 1);
-    int gr = ir, gc = ic;                                                             // -> the path's last cell (:199)
+    int tr = ir, tc = ic;                                                             // -> the path's last cell: the goal (:199), the window's field (:75-78)
     int g = len + 1;                                                                  // -> index of the last move (gt_actions: len(a) if none)
     for (int t = 0; t < len; t++) {
         const int v = action(t);
         if (v != 0) g = t;
-        move(gr, gc, v);
+        move(tr, tc, v);
     }
-    const uint16_t *dg = allpairs + (size_t)(gr * W + gc) * (H * W);                  // distance-to-goal field = a table row
+    bool gok = true;                                                                  // (tr, tc): the goal of the record being made, and whether it is in the frame
+    const int16_t *tg = nullptr;
+    int nt = 0, cur = 0, slot = 0;                                                    // slot = the entry of target(cur)
+    if constexpr (kLifelong) {
+        last[i] = (uint32_t)tr | ((uint32_t)tc << 16);
+        // the target list: entry 0, then the L - 1 entries behind it cyclically; j < nt.  L == 1 has no entry behind the first.
+        tg = targets + ea * (size_t)L * 2;
+        nt = n_targets != nullptr ? n_targets[ea] : L;
+        if (L == 1) nt = min(nt, 1);
+        if (nt < 1) { *status = 1; nt = 1; }                                          // (plain store; every writer stores 1)
+        tr = tg[0]; tc = tg[1];
+        gok = tr >= 0 && tr < H && tc >= 0 && tc < W;
+    }
+    const int cells = H * W;
+    const uint16_t *dg = allpairs + (size_t)(gok ? tr * W + tc : 0) * cells;          // distance-to-goal field = a table row
     int8_t *lab = labels + r0 + (int64_t)a * len1;
     AgentRec r;
-    r.pr = (int16_t)ir; r.pc = (int16_t)ic; r.gr = (int16_t)gr; r.gc = (int16_t)gc;
+    r.pr = (int16_t)ir; r.pc = (int16_t)ic;
     r.org[0] = r.org[1] = 0;
     AgentRec *rec_at = recs + (r0 - row0[0]) + a;                                     // (the workspace starts at this call's first row)
     unsigned long long hist = (unsigned long long)TOK_N * 0x0101010101ull;            // before the episode: 'n' (:207)
@@ -905,275 +956,54 @@ __global__ __launch_bounds__(256) void ds_paths_kernel(int n_sel, int n_agents, 
             hist = (hist >> 8) | ((unsigned long long)tok << 32);
             r.pr = (int16_t)nr; r.pc = (int16_t)nc;
         }
-#pragma unroll
-        for (int s = 0; s < 5; s++) r.hist[s] = (uint8_t)(hist >> (8 * s));           // oldest first
-        r.next = (uint8_t)next_action_token(dg, H, W, r.pr, r.pc);                    // :230-243
-        rec_at[(int64_t)t * n_agents] = r;
-        lab[t] = (int8_t)(t > g ? 5 : action(t));
-    }
-}
-
-__global__ __launch_bounds__(256) void ds_episode_tokens_kernel(const AgentRec *__restrict__ recs, const uint16_t *__restrict__ allpairs,
-                                                                const int64_t *__restrict__ row0, int only_obstacles, int n_agents, int H,
-                                                                int W, int chunks_per_step, uint8_t *__restrict__ tokens)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint4 *srec = reinterpret_cast<uint4 *>(smem);                                        // [n_agents]
-    uint32_t *scand = reinterpret_cast<uint32_t *>(smem + (size_t)n_agents * 16);         // [4][kDsMaxCand]
-    uint8_t *srow = reinterpret_cast<uint8_t *>(scand + 4 * kDsMaxCand);                  // [4][272], token t at byte t + 1
-    const int k = blockIdx.x / chunks_per_step, chunk = blockIdx.x - k * chunks_per_step, t = blockIdx.y;
-    const int64_t r0 = row0[k];
-    const int len1 = (int)((row0[k + 1] - r0) / n_agents);
-    if (t >= len1) return;                                                                // block-uniform: not kept, or past the episode's end
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint4 *grec = reinterpret_cast<const uint4 *>(recs) + (r0 - row0[0]) + (int64_t)t * n_agents;
-    for (int i = tid; i < n_agents; i += 256) srec[i] = grec[i];
-    __syncthreads();
-    uint32_t *cand = scand + wave * kDsMaxCand;
-    uint8_t *row = srow + wave * 272;
-    const int cells = H * W;
-    for (int q = 0; q < kDsAgentsPerBlock / 4; q++) {
-        const int a = chunk * kDsAgentsPerBlock + wave + 4 * q;
-        if (a >= n_agents) break;                                                         // wave-uniform
-        const uint4 me = srec[a];
-        const int pr = (int16_t)(me.x & 0xffffu), pc = (int16_t)(me.x >> 16);
-        const int gr = (int16_t)(me.y & 0xffffu), gc = (int16_t)(me.y >> 16);               // the path's last cell (ds_paths_kernel)
-        const bool gok = gr >= 0 && gr < H && gc >= 0 && gc < W;
-        const uint16_t *dg = allpairs + (size_t)(gok ? gr * W + gc : 0) * cells;          // distance-to-goal field = a table row
-        const uint16_t *dm = allpairs + (size_t)(pr * W + pc) * cells;                    // distances from my own cell
-        if (lane < 34) reinterpret_cast<uint2 *>(row)[lane] = make_uint2(0x42424242u, 0x42424242u);
-        // --- window (cost2go.cpp:44-88) ---
-        int v[2];
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            const int cell = lane + 64 * u, i = cell / kWin, j = cell - i * kWin;
-            const int rr = pr - kR + i, cc = pc - kR + j;
-            v[u] = (gok && cell < kWin * kWin && rr >= 0 && rr < H && cc >= 0 && cc < W) ? (int)dg[rr * W + cc] : kUnreach;
-        }
-        const int mid = __shfl(v[0], kR * kWin + kR);
-        // --- neighbours in the window, reachable from my cell, keyed (BFS distance, id) (:121-141) ---
-        int cnt = 0;
-        for (int b0 = 0; b0 < n_agents; b0 += 64) {
-            const int b = b0 + lane;
-            bool in = false;
-            uint32_t key = 0;
-            if (b < n_agents) {
-                const uint32_t bp = srec[b].x;
-                const int br = (int16_t)(bp & 0xffffu), bc = (int16_t)(bp >> 16);
-                if (abs(br - pr) <= kR && abs(bc - pc) <= kR && br >= 0 && br < H && bc >= 0 && bc < W) {
-                    const int d = dm[br * W + bc];
-                    in = d != kUnreach;
-                    key = ((uint32_t)d << 11) | (uint32_t)b;
+        if constexpr (kLifelong) {
+            if (r.pr == tr && r.pc == tc) {                                           // :146-149: standing on the pursued target advances the list
+                if (cur + 1 < nt) {
+                    cur++;
+                    slot = slot + 1 < L ? slot + 1 : 1;                               // 1 + (cur - 1) % (L - 1); cur + 1 < nt implies L >= 2
+                    tr = tg[2 * slot]; tc = tg[2 * slot + 1];
+                    gok = tr >= 0 && tr < H && tc >= 0 && tc < W;
+                    dg = allpairs + (size_t)(gok ? tr * W + tc : 0) * cells;
+                } else {
+                    *status = 1;                                                      // the list is exhausted (the reference's IndexError)
                 }
-            }
-            const unsigned long long bm = __ballot(in);
-            if (in) {
-                const int at = cnt + __popcll(bm & ((1ull << lane) - 1ull));
-                if (at < kDsMaxCand) cand[at] = key;
-            }
-            cnt += __popcll(bm);
-        }
-        cnt = min(cnt, kDsMaxCand);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (only_obstacles) {                                                             // tokens of the integers 1 / 0
-            row[1 + lane] = (uint8_t)(kLimit + (v[0] == kUnreach ? 1 : 0));
-            if (lane + 64 < kWin * kWin) row[65 + lane] = (uint8_t)(kLimit + (v[1] == kUnreach ? 1 : 0));
-        } else {
-            row[1 + lane] = (uint8_t)window_token(v[0], mid);
-            if (lane + 64 < kWin * kWin) row[65 + lane] = (uint8_t)window_token(v[1], mid);
-        }
-        for (int c = lane; c < cnt; c += 64) {
-            const uint32_t key = cand[c];
-            int rank = 0;
-            for (int j = 0; j < cnt; j++) rank += (cand[j] < key) ? 1 : 0;
-            if (rank < kSlots) emit_record(row, rank, srec[key & 0x7ffu], me.x);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint32_t *row32 = reinterpret_cast<const uint32_t *>(row);
-        const uint32_t packed = __builtin_amdgcn_alignbyte(row32[lane + 1], row32[lane], 1);
-        reinterpret_cast<uint32_t *>(tokens + (r0 + (int64_t)a * len1 + t) * 256)[lane] = packed;   // episode: [agent][timestep][256]
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Batched LIFELONG episodes: the two kernels above with a goal per timestep (generate_observations.py:55-60,
-// 143-153).  An agent's target list is target(0), target(1), ...; walking its path t = 0 .. len with cur = 0: a cell equal to target(cur)
-// advances cur by one (an `if`, also at t = 0, before the cell's goal is read) and the goal at t is target(cur).  Every record carries that
-// goal (relative goal + greedy bits from the goal's table row); the WINDOW stays that of the path's last cell (:75-78), which therefore
-// travels apart from the records: `last` [selected episode of this call][agent] = (row | col << 16).
-// targets int16 [n_batch][n_agents][L][2]: target(0) = entry 0, target(j >= 1) = entry 1 + (j - 1) % (L - 1) -- the expert's (goal at
-// reset, cyclic queue) as it lies; n_targets int32 [n_batch][n_agents] or NULL (L each) bounds j.  A walk that reaches n_targets (the
-// reference's IndexError) stores 1 to *status and goes on with the last valid index: its rows are unspecified, its accesses in bounds.
-// A target outside the frame is what ds_records_kernel makes of such a goal: no table read, TOK_BITS0.
-// Restated, not shared: the six kernels above keep their instruction streams (tools/kernel_digest.py, section 34).
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ds_paths_lifelong_kernel(int n_sel, int n_agents, int max_steps, int H, int W,
-                                                                const int16_t *__restrict__ init, const int8_t *__restrict__ actions,
-                                                                const int32_t *__restrict__ episodes, const int64_t *__restrict__ row0,
-                                                                const uint16_t *__restrict__ allpairs, const int16_t *__restrict__ targets,
-                                                                int L, const int32_t *__restrict__ n_targets, int32_t *__restrict__ status,
-                                                                AgentRec *__restrict__ recs, uint32_t *__restrict__ last,
-                                                                int8_t *__restrict__ labels)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_sel * n_agents) return;
-    const int k = i / n_agents, a = i - k * n_agents;
-    const int64_t r0 = row0[k];
-    const int len1 = (int)((row0[k + 1] - r0) / n_agents);                           // len + 1, 0 = not kept
-    if (len1 == 0) return;
-    const int len = len1 - 1;
-    const size_t ea = (size_t)ds_episode_of(episodes, k) * n_agents + a;
-    const uint8_t *act = reinterpret_cast<const uint8_t *>(actions) + ea * max_steps;
-    auto action = [&](int t) -> int { return t < len && act[t] <= 4 ? act[t] : 0; };
-    auto move = [&](int &r, int &c, int v) {                                          // clamped into the frame, as in ds_paths_kernel
-        r = min(max(r + (v == 2) - (v == 1), 0), H - 1);
-        c = min(max(c + (v == 4) - (v == 3), 0), W - 1);
-    };
-    const int ir = min(max((int)init[2 * ea], 0), H - 1), ic = min(max((int)init[2 * ea + 1], 0), W - 1);
-    int er = ir, ec = ic;                                                             // -> the path's last cell: the window's field (:75-78)
-    int g = len + 1;                                                                  // -> index of the last move
-    for (int t = 0; t < len; t++) {
-        const int v = action(t);
-        if (v != 0) g = t;
-        move(er, ec, v);
-    }
-    last[i] = (uint32_t)er | ((uint32_t)ec << 16);
-    // the target list: entry 0, then the L - 1 entries behind it cyclically; j < nt.  L == 1 has no entry behind the first.
-    const int16_t *tg = targets + ea * (size_t)L * 2;
-    int nt = n_targets != nullptr ? n_targets[ea] : L;
-    if (L == 1) nt = min(nt, 1);
-    if (nt < 1) { *status = 1; nt = 1; }                                              // (plain store; every writer stores 1)
-    const int cells = H * W;
-    int cur = 0, slot = 0;                                                            // slot = the entry of target(cur)
-    int tr = tg[0], tc = tg[1];
-    bool gok = tr >= 0 && tr < H && tc >= 0 && tc < W;
-    const uint16_t *dg = allpairs + (size_t)(gok ? tr * W + tc : 0) * cells;          // distance-to-goal field = a table row
-    int8_t *lab = labels + r0 + (int64_t)a * len1;
-    AgentRec r;
-    r.pr = (int16_t)ir; r.pc = (int16_t)ic;
-    r.org[0] = r.org[1] = 0;
-    AgentRec *rec_at = recs + (r0 - row0[0]) + a;
-    unsigned long long hist = (unsigned long long)TOK_N * 0x0101010101ull;            // before the episode: 'n' (:207)
-    for (int t = 0; t <= len; t++) {
-        if (t >= 1) {                                                                 // the move that led here; 'w' at the last step (:225-228)
-            int nr = r.pr, nc = r.pc;
-            move(nr, nc, action(t - 1));
-            const int dr = nr - r.pr, dc = nc - r.pc;
-            const int tok = t == len ? TOK_N + 1 : dr < 0 ? TOK_N + 2 : dr > 0 ? TOK_N + 3 : dc < 0 ? TOK_N + 4 : dc > 0 ? TOK_N + 5 : TOK_N + 1;
-            hist = (hist >> 8) | ((unsigned long long)tok << 32);
-            r.pr = (int16_t)nr; r.pc = (int16_t)nc;
-        }
-        if (r.pr == tr && r.pc == tc) {                                               // :146-149: standing on the pursued target advances the list
-            if (cur + 1 < nt) {
-                cur++;
-                slot = slot + 1 < L ? slot + 1 : 1;                                   // 1 + (cur - 1) % (L - 1); cur + 1 < nt implies L >= 2
-                tr = tg[2 * slot]; tc = tg[2 * slot + 1];
-                gok = tr >= 0 && tr < H && tc >= 0 && tc < W;
-                dg = allpairs + (size_t)(gok ? tr * W + tc : 0) * cells;
-            } else {
-                *status = 1;                                                          // the list is exhausted (the reference's IndexError)
             }
         }
         r.gr = (int16_t)tr; r.gc = (int16_t)tc;
 #pragma unroll
         for (int s = 0; s < 5; s++) r.hist[s] = (uint8_t)(hist >> (8 * s));           // oldest first
-        r.next = (uint8_t)(gok ? next_action_token(dg, H, W, r.pr, r.pc) : TOK_BITS0); // :230-243
+        r.next = (uint8_t)(gok ? next_action_token(dg, H, W, r.pr, r.pc) : TOK_BITS0); // :230-243; a target outside the frame: no table read
         rec_at[(int64_t)t * n_agents] = r;
         lab[t] = (int8_t)(t > g ? 5 : action(t));
     }
 }
 
-__global__ __launch_bounds__(256) void ds_episode_tokens_lifelong_kernel(const AgentRec *__restrict__ recs, const uint32_t *__restrict__ last,
-                                                                         const uint16_t *__restrict__ allpairs,
-                                                                         const int64_t *__restrict__ row0, int only_obstacles, int n_agents,
-                                                                         int H, int W, int chunks_per_step, uint8_t *__restrict__ tokens)
+// The window's cell: last[] (ds_paths_kernel<true>) where kLifelong, else the goal of the agent's own record = the path's last cell.
+template <bool kLifelong>
+__global__ __launch_bounds__(256) void ds_episode_tokens_kernel(const AgentRec *__restrict__ recs, const uint32_t *__restrict__ last,
+                                                                const uint16_t *__restrict__ allpairs, const int64_t *__restrict__ row0,
+                                                                int only_obstacles, int n_agents, int H, int W, int chunks_per_step,
+                                                                uint8_t *__restrict__ tokens)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint4 *srec = reinterpret_cast<uint4 *>(smem);                                        // [n_agents]
-    uint32_t *scand = reinterpret_cast<uint32_t *>(smem + (size_t)n_agents * 16);         // [4][kDsMaxCand]
-    uint8_t *srow = reinterpret_cast<uint8_t *>(scand + 4 * kDsMaxCand);                  // [4][272], token t at byte t + 1
     const int k = blockIdx.x / chunks_per_step, chunk = blockIdx.x - k * chunks_per_step, t = blockIdx.y;
     const int64_t r0 = row0[k];
     const int len1 = (int)((row0[k + 1] - r0) / n_agents);
     if (t >= len1) return;                                                                // block-uniform: not kept, or past the episode's end
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint4 *grec = reinterpret_cast<const uint4 *>(recs) + (r0 - row0[0]) + (int64_t)t * n_agents;
-    for (int i = tid; i < n_agents; i += 256) srec[i] = grec[i];
-    __syncthreads();
-    uint32_t *cand = scand + wave * kDsMaxCand;
-    uint8_t *row = srow + wave * 272;
-    const int cells = H * W;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint4 *srec;
+    uint32_t *cand;
+    uint8_t *row;
+    ds_stage_records(smem, reinterpret_cast<const uint4 *>(recs) + (r0 - row0[0]) + (int64_t)t * n_agents, n_agents, srec, cand, row);
     for (int q = 0; q < kDsAgentsPerBlock / 4; q++) {
         const int a = chunk * kDsAgentsPerBlock + wave + 4 * q;
         if (a >= n_agents) break;                                                         // wave-uniform
         const uint4 me = srec[a];
-        const int pr = (int16_t)(me.x & 0xffffu), pc = (int16_t)(me.x >> 16);
-        const uint32_t le = last[(size_t)k * n_agents + a];                               // the path's last cell (ds_paths_lifelong_kernel)
-        const int gr = (int)(le & 0xffffu), gc = (int)(le >> 16);
-        const bool gok = gr < H && gc < W;
-        const uint16_t *dg = allpairs + (size_t)(gok ? gr * W + gc : 0) * cells;          // the window's field = a table row
-        const uint16_t *dm = allpairs + (size_t)(pr * W + pc) * cells;                    // distances from my own cell
-        if (lane < 34) reinterpret_cast<uint2 *>(row)[lane] = make_uint2(0x42424242u, 0x42424242u);
-        // --- window (cost2go.cpp:44-88) ---
-        int v[2];
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            const int cell = lane + 64 * u, i = cell / kWin, j = cell - i * kWin;
-            const int rr = pr - kR + i, cc = pc - kR + j;
-            v[u] = (gok && cell < kWin * kWin && rr >= 0 && rr < H && cc >= 0 && cc < W) ? (int)dg[rr * W + cc] : kUnreach;
-        }
-        const int mid = __shfl(v[0], kR * kWin + kR);
-        // --- neighbours in the window, reachable from my cell, keyed (BFS distance, id) (:121-141) ---
-        int cnt = 0;
-        for (int b0 = 0; b0 < n_agents; b0 += 64) {
-            const int b = b0 + lane;
-            bool in = false;
-            uint32_t key = 0;
-            if (b < n_agents) {
-                const uint32_t bp = srec[b].x;
-                const int br = (int16_t)(bp & 0xffffu), bc = (int16_t)(bp >> 16);
-                if (abs(br - pr) <= kR && abs(bc - pc) <= kR && br >= 0 && br < H && bc >= 0 && bc < W) {
-                    const int d = dm[br * W + bc];
-                    in = d != kUnreach;
-                    key = ((uint32_t)d << 11) | (uint32_t)b;
-                }
-            }
-            const unsigned long long bm = __ballot(in);
-            if (in) {
-                const int at = cnt + __popcll(bm & ((1ull << lane) - 1ull));
-                if (at < kDsMaxCand) cand[at] = key;
-            }
-            cnt += __popcll(bm);
-        }
-        cnt = min(cnt, kDsMaxCand);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (only_obstacles) {                                                             // tokens of the integers 1 / 0
-            row[1 + lane] = (uint8_t)(kLimit + (v[0] == kUnreach ? 1 : 0));
-            if (lane + 64 < kWin * kWin) row[65 + lane] = (uint8_t)(kLimit + (v[1] == kUnreach ? 1 : 0));
-        } else {
-            row[1 + lane] = (uint8_t)window_token(v[0], mid);
-            if (lane + 64 < kWin * kWin) row[65 + lane] = (uint8_t)window_token(v[1], mid);
-        }
-        for (int c = lane; c < cnt; c += 64) {
-            const uint32_t key = cand[c];
-            int rank = 0;
-            for (int j = 0; j < cnt; j++) rank += (cand[j] < key) ? 1 : 0;
-            if (rank < kSlots) emit_record(row, rank, srec[key & 0x7ffu], me.x);          // (the record's goal: the one pursued at t)
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint32_t *row32 = reinterpret_cast<const uint32_t *>(row);
-        const uint32_t packed = __builtin_amdgcn_alignbyte(row32[lane + 1], row32[lane], 1);
-        reinterpret_cast<uint32_t *>(tokens + (r0 + (int64_t)a * len1 + t) * 256)[lane] = packed;   // episode: [agent][timestep][256]
-        __builtin_amdgcn_wave_barrier();
+        uint32_t cell = me.y;                                                             // (row | col << 16), as int16 each
+        if constexpr (kLifelong) cell = last[(size_t)k * n_agents + a];
+        const int gr = (int16_t)(cell & 0xffffu), gc = (int16_t)(cell >> 16);
+        ds_row(srec, cand, row, lane, me, n_agents, H, W, allpairs, gr * W + gc, gr >= 0 && gr < H && gc >= 0 && gc < W, only_obstacles,
+               tokens + (r0 + (int64_t)a * len1 + t) * 256);                              // episode: [agent][timestep][256]
     }
 }
 
@@ -1426,27 +1256,17 @@ struct mgpt_dataset {
     DeviceArena mem, recs_mem, last_mem;   // allpairs; recs; last
 };
 
-// recs for at least `rows` records (both tokenize calls): grows only, and a growth waits for the stream's work on the old buffer
-static int ds_reserve_recs(mgpt_dataset *d, size_t rows, hipStream_t s)
+// a scratch buffer (recs of the tokenize calls, last) for at least `n` elements: grows only, and a growth waits for the stream's work on
+// the old buffer
+template <class T>
+static int ds_reserve(DeviceArena &mem, T *&buf, size_t &cap, size_t n, hipStream_t s)
 {
-    if (rows <= d->recs_cap) return MGPT_OK;
+    if (n <= cap) return MGPT_OK;
     MGPT_HIP(hipStreamSynchronize(s));
-    d->recs_mem.release();
-    d->recs = nullptr; d->recs_cap = 0;
-    MGPT_HIP(d->recs_mem.alloc(&d->recs, rows * sizeof(AgentRec)));
-    d->recs_cap = rows;
-    return MGPT_OK;
-}
-
-// the same for `last` (the lifelong batched call): one word per (selected episode, agent)
-static int ds_reserve_last(mgpt_dataset *d, size_t words, hipStream_t s)
-{
-    if (words <= d->last_cap) return MGPT_OK;
-    MGPT_HIP(hipStreamSynchronize(s));
-    d->last_mem.release();
-    d->last = nullptr; d->last_cap = 0;
-    MGPT_HIP(d->last_mem.alloc(&d->last, words * sizeof(uint32_t)));
-    d->last_cap = words;
+    mem.release();
+    buf = nullptr; cap = 0;
+    MGPT_HIP(mem.alloc(&buf, n * sizeof(T)));
+    cap = n;
     return MGPT_OK;
 }
 
@@ -1504,7 +1324,7 @@ extern "C" int mgpt_dataset_tokenize_ex(mgpt_dataset *d, int n_agents, int n_ste
     MGPT_REQUIRE(n_agents > 0 && n_agents <= 2048 && n_steps > 0, MGPT_ERR_ARG, "n_agents=%d n_steps=%d", n_agents, n_steps);
     hipStream_t s = (hipStream_t)stream;
     const size_t total = (size_t)n_agents * n_steps;
-    const int rc = ds_reserve_recs(d, total, s);
+    const int rc = ds_reserve(d->recs_mem, d->recs, d->recs_cap, total, s);
     if (rc != MGPT_OK) return rc;
     {
         ProfScope ps(P_TOK_UPDATE, s);
@@ -1513,9 +1333,8 @@ extern "C" int mgpt_dataset_tokenize_ex(mgpt_dataset *d, int n_agents, int n_ste
         MGPT_LAUNCH_CHECK();
     }
     const int chunks = cdiv(n_agents, kDsAgentsPerBlock);
-    const size_t smem = (size_t)n_agents * 16 + 4 * kDsMaxCand * 4 + 4 * 272;
     ProfScope ps(P_TOKENS, s);
-    hipLaunchKernelGGL(ds_tokens_kernel, dim3(n_steps * chunks), dim3(256), smem, s, d->recs, d->allpairs, d_paths, only_obstacles ? 1 : 0,
+    hipLaunchKernelGGL(ds_tokens_kernel, dim3(n_steps * chunks), dim3(256), ds_row_lds_bytes(n_agents), s, d->recs, d->allpairs, d_paths, only_obstacles ? 1 : 0,
                        n_agents, n_steps, d->H, d->W, chunks, d_tokens);
     MGPT_LAUNCH_CHECK();
     return MGPT_OK;
@@ -1534,36 +1353,56 @@ extern "C" int mgpt_dataset_episode_offsets(int n_sel, int n_agents, int max_ste
     return MGPT_OK;
 }
 
+struct DsLifelong {                     // what mgpt_dataset_tokenize_episodes_lifelong takes beyond mgpt_dataset_tokenize_episodes
+    const int16_t *targets;
+    int L;
+    const int32_t *n_targets;
+    int32_t *status;
+};
+
+// both batched calls; ll = NULL: plain episodes.  (d_len and d_keep were read by mgpt_dataset_episode_offsets: the kernels here take
+// every length from d_row0)
+static int ds_tokenize_episodes(mgpt_dataset *d, int n_sel, int n_agents, int max_steps, const int16_t *d_init, const int8_t *d_actions,
+                                const int32_t *d_len, const int32_t *d_episodes, const int64_t *d_row0, const DsLifelong *ll,
+                                int only_obstacles, uint8_t *d_tokens, int8_t *d_labels, hipStream_t s)
+{
+    MGPT_REQUIRE(d && d_init && d_len && d_row0 && (!ll || (ll->targets && ll->status)) && (d_actions || max_steps == 0), MGPT_ERR_ARG,
+                 "NULL argument");
+    const bool sizes_ok = n_sel >= 0 && n_agents > 0 && n_agents <= 2048 && max_steps >= 0 && max_steps < 65535;
+    if (ll) MGPT_REQUIRE(sizes_ok && ll->L >= 1, MGPT_ERR_ARG, "n_sel=%d n_agents=%d max_steps=%d L=%d", n_sel, n_agents, max_steps, ll->L);
+    else MGPT_REQUIRE(sizes_ok, MGPT_ERR_ARG, "n_sel=%d n_agents=%d max_steps=%d", n_sel, n_agents, max_steps);
+    if (n_sel == 0) return MGPT_OK;
+    MGPT_REQUIRE(d_tokens && d_labels, MGPT_ERR_ARG, "NULL argument");
+    const int chunks = cdiv(n_agents, kDsAgentsPerBlock);
+    const int64_t rows_max = (int64_t)n_sel * n_agents * (max_steps + 1);          // the workspace is sized for no skipped and no short episode
+    MGPT_REQUIRE(rows_max < ((int64_t)1 << 31) && (int64_t)n_sel * chunks < ((int64_t)1 << 31), MGPT_ERR_UNSUPPORTED,
+                 "n_sel=%d episodes of up to %d x %d rows in one call: split the selection", n_sel, n_agents, max_steps + 1);
+    int rc = ds_reserve(d->recs_mem, d->recs, d->recs_cap, (size_t)rows_max, s);
+    if (rc == MGPT_OK && ll) rc = ds_reserve(d->last_mem, d->last, d->last_cap, (size_t)n_sel * n_agents, s);
+    if (rc != MGPT_OK) return rc;
+    const DsLifelong x = ll ? *ll : DsLifelong{};
+    {
+        ProfScope ps(ll ? P_DS_PATHS_LIFELONG : P_DS_PATHS, s);
+        hipLaunchKernelGGL(ll ? ds_paths_kernel<true> : ds_paths_kernel<false>, dim3(cdiv(n_sel * n_agents, 256)), dim3(256), 0, s, n_sel, n_agents,
+                           max_steps, d->H, d->W, d_init, d_actions, d_episodes, d_row0, d->allpairs, x.targets, x.L, x.n_targets, x.status,
+                           d->recs, d->last, d_labels);
+        MGPT_LAUNCH_CHECK();
+    }
+    ProfScope ps(ll ? P_DS_EPISODE_TOKENS_LIFELONG : P_DS_EPISODE_TOKENS, s);
+    hipLaunchKernelGGL(ll ? ds_episode_tokens_kernel<true> : ds_episode_tokens_kernel<false>, dim3(n_sel * chunks, max_steps + 1), dim3(256),
+                       ds_row_lds_bytes(n_agents), s, d->recs, d->last, d->allpairs, d_row0, only_obstacles ? 1 : 0, n_agents, d->H, d->W, chunks,
+                       d_tokens);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
 extern "C" int mgpt_dataset_tokenize_episodes(mgpt_dataset *d, int n_sel, int n_agents, int max_steps, const int16_t *d_init,
                                               const int8_t *d_actions, const int32_t *d_len, const uint8_t *d_keep,
                                               const int32_t *d_episodes, const int64_t *d_row0, int only_obstacles, uint8_t *d_tokens,
                                               int8_t *d_labels, void *stream)
 {
-    MGPT_REQUIRE(d && d_init && d_len && d_row0 && (d_actions || max_steps == 0), MGPT_ERR_ARG, "NULL argument");
-    MGPT_REQUIRE(n_sel >= 0 && n_agents > 0 && n_agents <= 2048 && max_steps >= 0 && max_steps < 65535, MGPT_ERR_ARG,
-                 "n_sel=%d n_agents=%d max_steps=%d", n_sel, n_agents, max_steps);
-    if (n_sel == 0) return MGPT_OK;
-    MGPT_REQUIRE(d_tokens && d_labels, MGPT_ERR_ARG, "NULL argument");
-    // (d_len and d_keep were read by mgpt_dataset_episode_offsets: the kernels here take every length from d_row0)
-    const int chunks = cdiv(n_agents, kDsAgentsPerBlock);
-    const int64_t rows_max = (int64_t)n_sel * n_agents * (max_steps + 1);          // the workspace is sized for no skipped and no short episode
-    MGPT_REQUIRE(rows_max < ((int64_t)1 << 31) && (int64_t)n_sel * chunks < ((int64_t)1 << 31), MGPT_ERR_UNSUPPORTED,
-                 "n_sel=%d episodes of up to %d x %d rows in one call: split the selection", n_sel, n_agents, max_steps + 1);
-    hipStream_t s = (hipStream_t)stream;
-    int rc = ds_reserve_recs(d, (size_t)rows_max, s);
-    if (rc != MGPT_OK) return rc;
-    {
-        ProfScope ps(P_DS_PATHS, s);
-        hipLaunchKernelGGL(ds_paths_kernel, dim3(cdiv(n_sel * n_agents, 256)), dim3(256), 0, s, n_sel, n_agents, max_steps, d->H, d->W, d_init,
-                           d_actions, d_episodes, d_row0, d->allpairs, d->recs, d_labels);
-        MGPT_LAUNCH_CHECK();
-    }
-    const size_t smem = (size_t)n_agents * 16 + 4 * kDsMaxCand * 4 + 4 * 272;
-    ProfScope ps(P_DS_EPISODE_TOKENS, s);
-    hipLaunchKernelGGL(ds_episode_tokens_kernel, dim3(n_sel * chunks, max_steps + 1), dim3(256), smem, s, d->recs, d->allpairs, d_row0,
-                       only_obstacles ? 1 : 0, n_agents, d->H, d->W, chunks, d_tokens);
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
+    return ds_tokenize_episodes(d, n_sel, n_agents, max_steps, d_init, d_actions, d_len, d_episodes, d_row0, nullptr, only_obstacles, d_tokens,
+                                d_labels, (hipStream_t)stream);
 }
 
 extern "C" int mgpt_dataset_tokenize_episodes_lifelong(mgpt_dataset *d, int n_sel, int n_agents, int max_steps, const int16_t *d_init,
@@ -1572,30 +1411,7 @@ extern "C" int mgpt_dataset_tokenize_episodes_lifelong(mgpt_dataset *d, int n_se
                                                        const int32_t *d_n_targets, int32_t *d_status, int only_obstacles,
                                                        uint8_t *d_tokens, int8_t *d_labels, void *stream)
 {
-    MGPT_REQUIRE(d && d_init && d_len && d_row0 && d_targets && d_status && (d_actions || max_steps == 0), MGPT_ERR_ARG, "NULL argument");
-    MGPT_REQUIRE(n_sel >= 0 && n_agents > 0 && n_agents <= 2048 && max_steps >= 0 && max_steps < 65535 && L >= 1, MGPT_ERR_ARG,
-                 "n_sel=%d n_agents=%d max_steps=%d L=%d", n_sel, n_agents, max_steps, L);
-    if (n_sel == 0) return MGPT_OK;
-    MGPT_REQUIRE(d_tokens && d_labels, MGPT_ERR_ARG, "NULL argument");
-    const int chunks = cdiv(n_agents, kDsAgentsPerBlock);
-    const int64_t rows_max = (int64_t)n_sel * n_agents * (max_steps + 1);          // the workspace is sized for no skipped and no short episode
-    MGPT_REQUIRE(rows_max < ((int64_t)1 << 31) && (int64_t)n_sel * chunks < ((int64_t)1 << 31), MGPT_ERR_UNSUPPORTED,
-                 "n_sel=%d episodes of up to %d x %d rows in one call: split the selection", n_sel, n_agents, max_steps + 1);
-    hipStream_t s = (hipStream_t)stream;
-    int rc = ds_reserve_recs(d, (size_t)rows_max, s);
-    if (rc != MGPT_OK) return rc;
-    rc = ds_reserve_last(d, (size_t)n_sel * n_agents, s);
-    if (rc != MGPT_OK) return rc;
-    {
-        ProfScope ps(P_DS_PATHS_LIFELONG, s);
-        hipLaunchKernelGGL(ds_paths_lifelong_kernel, dim3(cdiv(n_sel * n_agents, 256)), dim3(256), 0, s, n_sel, n_agents, max_steps, d->H, d->W,
-                           d_init, d_actions, d_episodes, d_row0, d->allpairs, d_targets, L, d_n_targets, d_status, d->recs, d->last, d_labels);
-        MGPT_LAUNCH_CHECK();
-    }
-    const size_t smem = (size_t)n_agents * 16 + 4 * kDsMaxCand * 4 + 4 * 272;
-    ProfScope ps(P_DS_EPISODE_TOKENS_LIFELONG, s);
-    hipLaunchKernelGGL(ds_episode_tokens_lifelong_kernel, dim3(n_sel * chunks, max_steps + 1), dim3(256), smem, s, d->recs, d->last, d->allpairs,
-                       d_row0, only_obstacles ? 1 : 0, n_agents, d->H, d->W, chunks, d_tokens);
-    MGPT_LAUNCH_CHECK();
-    return MGPT_OK;
+    const DsLifelong ll = {d_targets, L, d_n_targets, d_status};
+    return ds_tokenize_episodes(d, n_sel, n_agents, max_steps, d_init, d_actions, d_len, d_episodes, d_row0, &ll, only_obstacles, d_tokens,
+                                d_labels, (hipStream_t)stream);
 }

@@ -312,11 +312,8 @@ class ObservationGenerator:
         obst = np.array([[1 if ch == "#" else 0 for ch in r] for r in rows], dtype=np.uint8)
         return _maps.pad(obst, self.cfg.cost2go_radius, 1)
 
-    def generate_observations_device(self, start_range, end_range):
-        """The rows of `generate_observations` (same instances, order, CSR filter and labels) left where the kernel wrote them:
-        -> (uint8 device tensor [N, 256], int8 device tensor [N]).  Only the labels (one byte per row, built from the logged
-        actions on the host) travel to the device; no row travels back.  Does not touch self.inputs / self.gt_actions."""
-        rows, labels = [], []
+    def _instances(self, start_range, end_range):
+        """Per kept instance of data[start_range:end_range], in order: (uint8 device tensor [rows, 256], its labels as a list)."""
         for instance_id in range(start_range, end_range):
             rec = self.data[instance_id]
             if rec["metrics"].get("CSR", 1) < 1:                        # :44-45
@@ -328,9 +325,17 @@ class ObservationGenerator:
             goals = None
             if "global_lifelong_targets_xy" in rec["metrics"]:          # :55-60
                 goals = goal_positions(paths, rec["metrics"]["global_lifelong_targets_xy"])
-            rows.append(self._table.tokenize(paths, goals, self.cfg.mask_cost2go).reshape(-1, 256))
-            for g in gt_actions(rec["metrics"]["made_actions"]):
-                labels.extend(g)
+            rows = self._table.tokenize(paths, goals, self.cfg.mask_cost2go).reshape(-1, 256)
+            yield rows, [v for g in gt_actions(rec["metrics"]["made_actions"]) for v in g]
+
+    def generate_observations_device(self, start_range, end_range):
+        """The rows of `generate_observations` (same instances, order, CSR filter and labels) left where the kernel wrote them:
+        -> (uint8 device tensor [N, 256], int8 device tensor [N]).  Only the labels (one byte per row, built from the logged
+        actions on the host) travel to the device; no row travels back.  Does not touch self.inputs / self.gt_actions."""
+        rows, labels = [], []
+        for x, y in self._instances(start_range, end_range):
+            rows.append(x)
+            labels.extend(y)
         dev = torch.device(self.device)
         if not rows:
             return torch.empty((0, 256), dtype=torch.uint8, device=dev), torch.empty((0,), dtype=torch.int8, device=dev)
@@ -341,19 +346,8 @@ class ObservationGenerator:
 
     def generate_observations(self, start_range, end_range):
         self.inputs, self.gt_actions = [], []
-        for instance_id in range(start_range, end_range):
-            rec = self.data[instance_id]
-            if rec["metrics"].get("CSR", 1) < 1:                        # :44-45
-                continue
-            name = rec["env_grid_search"]["map_name"]
-            if name != self._table_name:                                # :46-54
-                self._table, self._table_name = MapTable(self.get_grid_map(name), self.device), name
-            paths = agent_paths(rec["metrics"]["init_positions"], rec["metrics"]["made_actions"])
-            goals = None
-            if "global_lifelong_targets_xy" in rec["metrics"]:          # :55-60
-                goals = goal_positions(paths, rec["metrics"]["global_lifelong_targets_xy"])
-            toks = self._table.tokenize(paths, goals, self.cfg.mask_cost2go).cpu().numpy().astype(np.int8).reshape(-1, 256)
-            self.inputs.extend(list(toks))
-            for g in gt_actions(rec["metrics"]["made_actions"]):
-                self.gt_actions.extend(g)
+        for x, y in self._instances(start_range, end_range):
+            self.inputs.extend(list(x.cpu().numpy().astype(np.int8)))
+            self.gt_actions.extend(y)
         return self.inputs, self.gt_actions
+

@@ -14,11 +14,14 @@ def paths_of(init_e, actions_e, length):
     return np.asarray(dso.agent_paths(np.asarray(init_e).astype(int).tolist(), [row[:length].tolist() for row in np.asarray(actions_e)]), np.int64)
 
 
-def random_targets(grid, init, actions, lengths, seed):
+def random_targets(grid, init, actions, lengths, seed, within=None):
     """-> int16 [n_batch, n_agents, L = cap + 2, 2].  One np.random.Generator(PCG64(seed)), episodes then agents; per agent: k =
     integers(0, 4); min(k, len + 1) distinct timesteps of 0 .. len by choice(replace=False), sorted: the path's cells at those times are
     the first targets (an agent that follows its path stands on them in this order, unless a fill cell or a repeat comes between);
-    uniformly drawn free cells fill the list.  A walk advances at most once per path cell, len + 1 <= cap + 1 times: never exhausted."""
+    uniformly drawn free cells fill the list.  A walk advances at most once per path cell, len + 1 <= cap + 1 times: never exhausted.
+    within: the fill cells of an agent lie at most this far, per coordinate, from its first cell.  The reference's encoder has no token
+    for a relative goal beyond +-20 (encoder.cpp:93 throws, and so does the restatement), so on a map wider than 21 cells a test keeps
+    every goal that far from every observer: within + cap + 5 <= 20."""
     n_batch, n_agents, cap = np.asarray(actions).shape
     rng = np.random.Generator(np.random.PCG64(seed))
     free = np.argwhere(np.asarray(grid) == 0)
@@ -31,7 +34,8 @@ def random_targets(grid, init, actions, lengths, seed):
             k = min(int(rng.integers(0, 4)), ln + 1)
             ts = np.sort(rng.choice(ln + 1, size=k, replace=False))
             out[e, a, :k] = paths[a, ts]
-            out[e, a, k:] = free[rng.integers(0, len(free), L - k)]
+            pool = free if within is None else free[(np.abs(free - paths[a, 0]) <= within).all(1)]
+            out[e, a, k:] = pool[rng.integers(0, len(pool), L - k)]
     return out
 
 

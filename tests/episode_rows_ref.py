@@ -69,6 +69,36 @@ def expected(grid, init, actions, lengths, keep=None, episodes=None, mask_cost2g
     return np.concatenate(xs), np.concatenate(ys), np.asarray(row0, np.int64)
 
 
+def most_agents_in_a_window(init, actions, lengths):
+    """The largest number of agents, the observer included, inside any observer's 11 x 11 window over every episode and timestep of the
+    (clamped) log.  The kernels keep 128 candidates per window: a case at or below that is one the restatement and the kernels agree on."""
+    most = 0
+    for e, length in enumerate(lengths):
+        made = [row[:int(length)].tolist() for row in np.asarray(actions[e])]
+        paths = np.asarray(dso.agent_paths(np.asarray(init[e]).astype(int).tolist(), made), np.int64)      # [n_agents, length + 1, 2]
+        near = (np.abs(paths[:, None] - paths[None, :]) <= 5).all(-1)                                      # [observer, agent, timestep]
+        most = max(most, int(near.sum(1).max()))
+    return most
+
+
+# Crowded windows at three 64-lane candidate passes, the last one partial: the shared neighbour loop against the restatement.
+CROWDED = dict(h=30, w=34, density=0.15, lengths=[3, 2], n_agents=(129, 150))
+
+
+def crowded_case(n_agents):
+    """-> (grid, init, actions, lengths, most agents in a window) of a CROWDED case; the windows hold more agents than a row has slots."""
+    from mapf_gpt_amd import maps
+    key = ("crowded", n_agents)
+    if key not in _cache:
+        c = CROWDED
+        grid = maps.pad(maps.random_map(c["h"], c["w"], c["density"], 300 + n_agents))
+        init, actions = random_walks(grid, 2, n_agents, 3, c["lengths"], seed=n_agents)
+        most = most_agents_in_a_window(init, actions, c["lengths"])
+        assert most > 13, most
+        _cache[key] = (grid, init, actions, list(c["lengths"]), most)
+    return _cache[key]
+
+
 # ---- BatchedExpert.dataset_rows: two maps of different size in one common frame ----------------------------------------------------
 # Chosen with tests/expert_ref.py on the CPU (RefExpert, plain PIBT, seed 4) over map seeds {21, 31, 41} x placement seeds {200, 300} x
 # caps {8, 10, 12, 16}: (21, 200, 12) is the first with a solved and an unsolved episode and a solved one on either map -- CSR

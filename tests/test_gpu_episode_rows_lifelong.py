@@ -110,6 +110,19 @@ def test_agent_count_edges(n_agents):
     assert_equal(run(grid, init, actions, lengths, targets), lr.expected(grid, init, actions, lengths, targets))
 
 
+@pytest.mark.parametrize("mask", [False, True], ids=["cost2go", "mask_cost2go"])
+@pytest.mark.parametrize("n_agents", rr.CROWDED["n_agents"])
+def test_crowded_windows_against_the_restatement(n_agents, mask):
+    """The crowded case of tests/test_gpu_episode_rows.py with target lists: three 64-lane candidate passes, the last one partial, through
+    the lifelong instantiation of the shared row body; no window holds more agents than the 128 candidates the kernels keep."""
+    grid, init, actions, lengths, most = rr.crowded_case(n_agents)
+    assert most <= 128
+    targets = lr.random_targets(grid, init, actions, lengths, seed=100 + n_agents, within=12)     # 12 + cap 3 + radius 5 = 20
+    assert lr.goal_stats(grid, init, actions, lengths, targets)[0] >= n_agents // 5
+    assert_equal(run(grid, init, actions, lengths, targets, mask_cost2go=mask),
+                 lr.expected(grid, init, actions, lengths, targets, mask_cost2go=mask))
+
+
 def _oscillation():
     """Open 8 x 8, two agents: agent 0 walks x0 x1 x0 x1 x0 x1 with target(0) = x1 and the queue [x0, x1] (L = 3): it stands on the target
     it pursues at every t >= 1, so its list advances every step and wraps at t = 3.  Agent 1 stands next to it with a far goal."""

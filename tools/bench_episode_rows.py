@@ -7,7 +7,10 @@ it stands next to (records() -> ObservationGenerator.generate_observations_devic
                   time is a host clock from its first call to a device synchronise after its last.  One warm-up of each route (tables,
                   lazy allocations), then --repeats pairs, batched first in odd pairs and the loop first in even ones -> median and range
                   per route.  Then one more batched pass with the library's timing hooks on -> kernel ms under ds_paths and
-                  ds_episode_tokens and their share of that pass's host time.  The two routes' rows are compared before anything is timed.
+                  ds_episode_tokens and their share of that pass's host time, and one hooked pass of the loop -> kernel ms under
+                  tok_generate_observations (ds_tokens_kernel) and tok_update_agents (ds_records_kernel).  For tools/ab.py the line also
+                  carries ms_per_step (the batched median) and kernel_ms_per_step (all those hooks).  The two routes' rows are compared
+                  before anything is timed.
     --mode e2e    a 4-map config (two 21 x 21 mazes, two 21 x 21 random maps at 15 %), --seeds seeds x 16 / 24 / 32 agents, 128-step cap,
                   PIBT with the swap rule, from a YAML written to a temporary folder:
                       log     python -m mapf_gpt_amd.expert --out  +  split_by_map  +  build_shards (dataset_build --logs)
@@ -108,8 +111,12 @@ def bench_rows(a):
     _lib.prof_enable(True)
     t_hook = timed(batched)
     hooks = _lib.prof_read()
-    _lib.prof_enable(False)
     kern = {k: round(hooks[k][0], 4) for k in ("ds_paths", "ds_episode_tokens", "ds_paths_lifelong", "ds_episode_tokens_lifelong") if k in hooks}
+    _lib.prof_reset()
+    timed(loop)                                                    # one hooked pass of the per-episode route: ds_records / ds_tokens
+    hooks = _lib.prof_read()
+    _lib.prof_enable(False)
+    per_episode = {k: round(hooks[k][0], 4) for k in ("tok_generate_observations", "tok_update_agents") if k in hooks}
 
     def stats(t):
         return {"median_s": round(float(np.median(t)), 5), "min_s": round(min(t), 5), "max_s": round(max(t), 5),
@@ -119,7 +126,9 @@ def bench_rows(a):
     return {"tool": "bench_episode_rows", **kind, "map": f"maze {SIDE}x{SIDE}", "episodes": a.seeds * len(AGENTS),
             "rows": rows, "rows_equal": bool(same), "repeats": a.repeats, "batched": stats(tb), "loop": stats(tl),
             "speedup": round(float(np.median(tl)) / float(np.median(tb)), 2), "kernel_ms": kern,
-            "kernel_share_of_pass": round(sum(kern.values()) / (1e3 * t_hook), 4), "hooked_pass_s": round(t_hook, 5)}
+            "kernel_share_of_pass": round(sum(kern.values()) / (1e3 * t_hook), 4), "hooked_pass_s": round(t_hook, 5),
+            # the two keys tools/ab.py records: a "step" is one batched pass
+            "ms_per_step": round(1e3 * float(np.median(tb)), 3), "kernel_ms_per_step": {**kern, **per_episode}}
 
 
 def bench_e2e(a):
