@@ -312,6 +312,9 @@ struct ModeBuilder {
                 MGPT_HIP(set_max_lds_each(pkt, &fastk::mlp_fused_kernel<T, NP, 2, 8>, &fastk::mlp_fused_kernel<T, NP, 2, 4>, &fastk::mlp_fused_kernel<T, NP, 2, 2>));
             MGPT_HIP(set_max_lds_each(pkt, &fastk::mlp_fused16_kernel<T, NP, CT, 8, 0>, &fastk::mlp_fused16_kernel<T, NP, CT, 4, 0>,
                                       &fastk::mlp_fused16_kernel<T, NP, CT, 2, 0>));
+            if constexpr (CT == 2)                           // (C = 64 with one head of 64, FAM_GENERIC: the same kernel on plain rows)
+                MGPT_HIP(set_max_lds_each(pkt, &fastk::mlp_fused16_kernel<T, NP, 2, 8, 0, 3, true>, &fastk::mlp_fused16_kernel<T, NP, 2, 4, 0, 3, true>,
+                                          &fastk::mlp_fused16_kernel<T, NP, 2, 2, 0, 3, true>));
         }
         const size_t ks = C / 16, ntile = 3 * C / 32;
         m->rg.qkv_pk.assign(L, nullptr);
@@ -784,13 +787,19 @@ struct Chunk {
     hipLaunchKernelGGL((fastk::mlp_fused16_kernel<T, NP, CT_, NW_, 0>), dim3((unsigned)(mlp_M / (32 * NW_))), dim3(64 * NW_), lds, s, mlp_x, \
                        P + lo.ln2, m->rg.mlp16_pk[l], m->pl.fc[l].inv_scale, m->pl.proj2[l].inv_scale, last ? nullptr : m->ws.stats, (int)mlp_M, m->pl.gelu_lut, \
                        (const float *)nullptr, (int64_t)0)
-#define MGPT_MLP(CT_, NW_) do { if (p.mlp == MLP_FUSED) MGPT_MLP_(CT_, NW_); else MGPT_MLP16_(CT_, NW_); } while (0)
+    // (FAM_GENERIC keeps plain rows: C = 64 with one head of 64 runs the XROW form of the kernel)
+#define MGPT_MLP16R_(NW_)                                                                                                             \
+    hipLaunchKernelGGL((fastk::mlp_fused16_kernel<T, NP, 2, NW_, 0, 3, true>), dim3((unsigned)(mlp_M / (32 * NW_))), dim3(64 * NW_), lds, s, mlp_x, \
+                       P + lo.ln2, m->rg.mlp16_pk[l], m->pl.fc[l].inv_scale, m->pl.proj2[l].inv_scale, last ? nullptr : m->ws.stats, (int)mlp_M, m->pl.gelu_lut, \
+                       (const float *)nullptr, (int64_t)0)
+#define MGPT_MLP(CT_, NW_) do { if (p.mlp == MLP_FUSED) MGPT_MLP_(CT_, NW_); else if (!f.x_tiled()) MGPT_MLP16R_(NW_); else MGPT_MLP16_(CT_, NW_); } while (0)
             // (MLP_FUSED: mlp_fused_kernel folds in the heads' partial sums = n_head buffers, and n_head == C / 32 for the shapes of this path;
             //  C = 160 comes here in large calls only)
             const int nw = last ? p.mlp_nw_last : p.mlp_nw;
             if (C == 160) { if (nw == 8) MGPT_MLP16_(5, 8); else if (nw == 4) MGPT_MLP16_(5, 4); else MGPT_MLP16_(5, 2); }
             else { if (nw == 8) MGPT_MLP(2, 8); else if (nw == 4) MGPT_MLP(2, 4); else MGPT_MLP(2, 2); }
 #undef MGPT_MLP
+#undef MGPT_MLP16R_
 #undef MGPT_MLP16_
 #undef MGPT_MLP_
         }

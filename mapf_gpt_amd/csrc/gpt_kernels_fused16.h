@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void pack_mlp16_kernel(const float *__restrict
 
 constexpr bool kMlpF16Placed = true;
 
-template <class T, int NP, int CT, int NW = 8, int NFOLD = 0, int NBUF = 3>
+template <class T, int NP, int CT, int NW = 8, int NFOLD = 0, int NBUF = 3, bool XROW = false>
 __global__ __launch_bounds__(NW * 64, 2) void mlp_fused16_kernel(float *__restrict__ x, const float *__restrict__ gain,
                                                               const uint16_t *__restrict__ wpk, float inv1, float inv2,
                                                               float2 *__restrict__ stats_out, int M,
@@ -69,8 +69,11 @@ __global__ __launch_bounds__(NW * 64, 2) void mlp_fused16_kernel(float *__restri
     const int t16 = lane & 15, q4 = lane >> 4;
     const int64_t m0 = (int64_t)blockIdx.x * (NW * 32) + wave * 32;        // this wave's first token
     // x is chunk-major (xt_off): chunk c (8 features) of the wave's 32-token tile sits c * 256 floats up, token T at T * 8
-    float *xt = x + m0 * C + q4 * 256 + t16 * 8;                           // operand side: chunk 4 kb + q, tokens t (+ 16): 32 bytes each
-    float *xq = x + m0 * C + (q4 >> 1) * 256 + t16 * 8 + 4 * (q4 & 1);     // result side: chunk 2 fg + q / 2, half q % 2: 16 bytes
+    // (XROW: plain rows -- the residual stream of FAM_GENERIC, whose C = 64 shape with one head of 64 runs this kernel: feature n of token T at T * C + n)
+    constexpr int XKB = XROW ? 32 : 1024, XTG = XROW ? 16 * C : 128;      // floats from k-block to k-block (32 features), from token group to token group (16 tokens)
+    constexpr int XFG = XROW ? 16 : 512;                                   // ... from feature group to feature group (16 features) on the result side
+    float *xt = XROW ? x + m0 * C + t16 * C + q4 * 8 : x + m0 * C + q4 * 256 + t16 * 8;                           // operand side: chunk 4 kb + q, tokens t (+ 16): 32 bytes each
+    float *xq = XROW ? x + m0 * C + t16 * C + q4 * 4 : x + m0 * C + (q4 >> 1) * 256 + t16 * 8 + 4 * (q4 & 1);     // result side: chunk 2 fg + q / 2, half q % 2: 16 bytes
 
     auto issue = [&](int t) {
         const unsigned char *src = reinterpret_cast<const unsigned char *>(wpk) + (size_t)t * PKT;
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(NW * 64, 2) void mlp_fused16_kernel(float *__restri
 #pragma unroll
         for (int kb = 0; kb < KB; kb++)
 #pragma unroll
-            for (int hf = 0; hf < 2; hf++) xr[tg][kb][hf] = *reinterpret_cast<const f32x4 *>(xt + kb * 1024 + tg * 128 + hf * 4);
+            for (int hf = 0; hf < 2; hf++) xr[tg][kb][hf] = *reinterpret_cast<const f32x4 *>(xt + kb * XKB + tg * XTG + hf * 4);
     if constexpr (NFOLD > 0) {                             // small launches: the heads' partial sums, in x's layout, are added in index order and the sum written back
         const float *fp = fold + (xt - x);
 #pragma unroll
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(NW * 64, 2) void mlp_fused16_kernel(float *__restri
 #pragma unroll
                 for (int kb = 0; kb < KB; kb++)
 #pragma unroll
-                    for (int hf = 0; hf < 2; hf++) tt[tg][kb][hf] = *reinterpret_cast<const f32x4 *>(fp + (size_t)p * fold_stride + kb * 1024 + tg * 128 + hf * 4);
+                    for (int hf = 0; hf < 2; hf++) tt[tg][kb][hf] = *reinterpret_cast<const f32x4 *>(fp + (size_t)p * fold_stride + kb * XKB + tg * XTG + hf * 4);
 #pragma unroll
             for (int tg = 0; tg < 2; tg++)
 #pragma unroll
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(NW * 64, 2) void mlp_fused16_kernel(float *__restri
 #pragma unroll
             for (int kb = 0; kb < KB; kb++)
 #pragma unroll
-                for (int hf = 0; hf < 2; hf++) *reinterpret_cast<f32x4 *>(xt + kb * 1024 + tg * 128 + hf * 4) = xr[tg][kb][hf];
+                for (int hf = 0; hf < 2; hf++) *reinterpret_cast<f32x4 *>(xt + kb * XKB + tg * XTG + hf * 4) = xr[tg][kb][hf];
     }
     auto fold4 = [&](float v) { v += __shfl_xor(v, 16); v += __shfl_xor(v, 32); return v; };      // a token's features sit in the four lanes t + 16 q
     u32x4 xn[2 * KB][2];                                   // B operand of c_fc: [tg * KB + kb][plane]
@@ -287,7 +290,7 @@ __global__ __launch_bounds__(NW * 64, 2) void mlp_fused16_kernel(float *__restri
 #pragma unroll
     for (int j = 0; j < CT; j++)
 #pragma unroll
-        for (int gq = 0; gq < 4; gq++) cur[j][gq] = *reinterpret_cast<const f32x4 *>(xq2 + (2 * (2 * j + (gq >> 1))) * 256 + (gq & 1) * 128);
+        for (int gq = 0; gq < 4; gq++) cur[j][gq] = *reinterpret_cast<const f32x4 *>(xq2 + (2 * (2 * j + (gq >> 1))) * (XFG / 2) + (gq & 1) * XTG);
 #pragma unroll
     for (int j = 0; j < CT; j++)
 #pragma unroll
@@ -295,7 +298,7 @@ __global__ __launch_bounds__(NW * 64, 2) void mlp_fused16_kernel(float *__restri
             f32x4 c = cur[j][gq];
 #pragma unroll
             for (int e = 0; e < 4; e++) { c[e] += acc[j][4 * gq + e] * inv2; acc[j][4 * gq + e] = c[e]; }
-            *reinterpret_cast<f32x4 *>(xq2 + (2 * (2 * j + (gq >> 1))) * 256 + (gq & 1) * 128) = c;
+            *reinterpret_cast<f32x4 *>(xq2 + (2 * (2 * j + (gq >> 1))) * (XFG / 2) + (gq & 1) * XTG) = c;
             s2[gq & 1] += (c[0] + c[1]) + (c[2] + c[3]);
         }
     if (stats_out != nullptr) {
