@@ -328,6 +328,20 @@ int mgpt_gpt_act_dev(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int32_t *
  *           are applied in fp32 to P and to dP, a branch output is bf16(m s bf16(c_proj)).  p == 0 or sites == 0 runs exactly the launches of
  *           forward_backward_prec; p outside [0, 1) or sites outside [0, 15]: MGPT_ERR_ARG; n_embd not a multiple of 4: MGPT_ERR_UNSUPPORTED.
  *           Deterministic: two identical calls give bit-identical gradients.
+ *   forward_backward_rows: the micro-step of rows with ONE targeted position, token 255 (every row the dataset path makes): mathematically
+ *           forward_backward_prec(d_tokens, rows, 256, targets) with targets[r][255] = d_labels[r] and -1 elsewhere; d_labels int32 [rows].
+ *           The loss is the mean over the `rows` rows of the whole call (chunked like the general call), the gradients accumulate into the
+ *           same buffer, and micro-steps of either kind and precision may be mixed within an iteration.  The layers below the last run the
+ *           general call's launches; the last layer runs ln_1 and the K | V projection on all tokens and everything else -- the query,
+ *           attention's output (attn_last_fwd_kernel), c_proj, the MLP, ln_f, the head, the cross-entropy and their backward
+ *           (attn_last_bwd_kernel) -- on the compact matrix of the rows' last tokens, which lives in the activation slots the last layer no
+ *           longer fills: the workspace is the one above.  MGPT_PREC_BF16 applies the roundings of the general call at query 255.  NO HOST
+ *           WAIT: the normaliser is `rows`, a host-side number, and the call holds no stream synchronise, no blocking copy and no host read
+ *           of device memory.  Labels must lie in [0, 67): the cross-entropy kernel compares a label with that range before it indexes
+ *           anything with it, and an out-of-range label makes the row's loss term and logit gradients NaN -- *d_loss and the next gradient
+ *           norm are NaN, loudly; callers validate on the host where they hold the labels.  No dropout (the general call serves it).
+ *           Deterministic.  A NULL pointer, rows < 1 or a non-finite loss_scale: MGPT_ERR_ARG; no training workspace: MGPT_ERR_STATE; a
+ *           precision other than MGPT_PREC_F32 / MGPT_PREC_BF16: MGPT_ERR_UNSUPPORTED.
  *   zero_grad: grads = 0.
  *   clip_grad_norm: torch.nn.utils.clip_grad_norm_: total = || (||g_p||)_p ||, coef = min(max_norm / (total + 1e-6), 1), g *= coef; the
  *           coefficient stays on the device, *d_total_norm (device, may be NULL) = total.  max_norm <= 0: the norm only.
@@ -366,6 +380,8 @@ int mgpt_gpt_forward_backward_drop(mgpt_gpt *gpt, const uint8_t *d_tokens, int r
                                    float *d_loss, int precision, float p, uint64_t seed, uint64_t step, uint64_t row0, int sites, void *stream);
 int mgpt_gpt_forward_backward_prec(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int T, const int32_t *d_targets, float loss_scale,
                                    float *d_loss, int precision, void *stream);
+int mgpt_gpt_forward_backward_rows(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, const int32_t *d_labels, float loss_scale, float *d_loss,
+                                   int precision, void *stream);
 int mgpt_gpt_zero_grad(mgpt_gpt *gpt, void *stream);
 int mgpt_gpt_clip_grad_norm(mgpt_gpt *gpt, float max_norm, float *d_total_norm, void *stream);
 int mgpt_gpt_adamw_step(mgpt_gpt *gpt, float lr, float beta1, float beta2, float eps, float weight_decay, void *stream);

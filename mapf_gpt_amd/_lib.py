@@ -116,6 +116,7 @@ SYMBOLS = {
     "mgpt_gpt_train_free": (_i, [_vp]),
     "mgpt_gpt_forward_backward": (_i, [_vp, _vp, _i, _i, _vp, ctypes.c_float, _vp, _vp]),
     "mgpt_gpt_forward_backward_prec": (_i, [_vp, _vp, _i, _i, _vp, ctypes.c_float, _vp, _i, _vp]),
+    "mgpt_gpt_forward_backward_rows": (_i, [_vp, _vp, _i, _vp, ctypes.c_float, _vp, _i, _vp]),
     "mgpt_gpt_forward_backward_drop": (_i, [_vp, _vp, _i, _i, _vp, ctypes.c_float, _vp, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64,
                                             ctypes.c_uint64, _i, _vp]),
     "mgpt_gpt_zero_grad": (_i, [_vp, _vp]),

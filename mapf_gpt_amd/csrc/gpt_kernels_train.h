@@ -21,7 +21,7 @@ constexpr int kT = 256;
 // A(m, k) = A[m * lda + k] (A_KC) or A[k * lda + m];  B(k, n) = B[k * ldb + n] (B_NC) or B[n * ldb + k].  Every index is bounds-checked,
 // so any M, N, K work.  k runs in increasing order: an fmaf chain over each 16-wide k tile, the tiles' sums added in order (a long chain
 // of K fmafs would grow the rounding error with K: the c_attn input gradient of 85M sums 2304 terms).
-enum { OUT_STORE = 0, OUT_PART = 2, OUT_GELU_BWD = 3 };     // (the values are part of the instances' symbol names)
+enum { OUT_STORE = 0, OUT_RESID = 1, OUT_PART = 2, OUT_GELU_BWD = 3 };     // (the values are part of the instances' symbol names)
 
 __device__ __forceinline__ float gelu_grad(float a)
 {
@@ -91,6 +91,7 @@ __global__ __launch_bounds__(256) void gemm_tr_kernel(const float *__restrict__ 
             if (n >= N) continue;
             const int64_t o = (int64_t)m * ldc + n;
             if (OUT == OUT_GELU_BWD) dst[o] = acc[i][j] * gelu_grad(aux[o]);
+            else if (OUT == OUT_RESID) dst[o] = aux[o] + acc[i][j];     // a residual branch joins the stream aux (the compact last layer)
             else dst[o] = acc[i][j];
         }
     }
@@ -537,6 +538,228 @@ __global__ __launch_bounds__(256) void attn_fwd_drop_kernel(const float *__restr
             for (int gg = 0; gg < 4; gg++)
                 *reinterpret_cast<float4 *>(yrow + dt * 32 + 8 * gg + 4 * h) =
                     make_float4(o[dt][4 * gg] * inv, o[dt][4 * gg + 1] * inv, o[dt][4 * gg + 2] * inv, o[dt][4 * gg + 3] * inv);
+    }
+}
+
+// ===== the last-position micro-step (mgpt_gpt_forward_backward_rows): one targeted position per row, token 255 =====
+// The last layer runs its attention output, out-projection, MLP, ln_f, head and cross-entropy on a compact matrix [mc][C] of the rows'
+// last tokens (row r of the chunk = token r * 256 + 255); rows >= n_rows of the compact matrix are zero padding (the bf16 GEMMs take
+// token counts in multiples of 32), and zero rows stay zero through every step.
+
+// dst[r][c] = src[(r * 256 + 255)][c] for r < n_rows, 0 for the padding rows up to mc
+__global__ __launch_bounds__(256) void gather_last_kernel(const float *__restrict__ src, float *__restrict__ dst, int n_rows, int mc, int C)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (int64_t)mc * C; i += (int64_t)gridDim.x * 256) {
+        const int r = (int)(i / C), c = (int)(i - (int64_t)r * C);
+        dst[i] = r < n_rows ? src[((int64_t)r * kT + kT - 1) * C + c] : 0.f;
+    }
+}
+
+// dst[(r * 256 + 255)][c] += src[r][c], r < n_rows: a compact gradient joins the dense one (every element has one writer)
+__global__ __launch_bounds__(256) void scatter_last_add_kernel(const float *__restrict__ src, float *__restrict__ dst, int n_rows, int C)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (int64_t)n_rows * C; i += (int64_t)gridDim.x * 256) {
+        const int r = (int)(i / C), c = (int)(i - (int64_t)r * C);
+        dst[((int64_t)r * kT + kT - 1) * C + c] += src[i];
+    }
+}
+
+// cross-entropy of the compact logits [mc][67] against one label per row; k = loss_scale / rows of the WHOLE call, a host-side number (no
+// count is read from the device).  The label is compared with [0, 67) before anything is indexed with it: an out-of-range label makes the
+// row's loss term and its dlogits NaN -- the call's loss and the next gradient norm are NaN, loudly, and no host wait is spent on it.
+__global__ __launch_bounds__(256) void ce_rows_kernel(const float *__restrict__ logits, const int32_t *__restrict__ labels, int n_rows, int mc,
+                                                      float k, float *__restrict__ dlogits, float *__restrict__ row_nll)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= mc) return;
+    float *dl = dlogits + (int64_t)r * MGPT_VOCAB;
+    if (r >= n_rows) {
+        for (int v = 0; v < MGPT_VOCAB; v++) dl[v] = 0.f;
+        row_nll[r] = 0.f;
+        return;
+    }
+    const int tg = labels[r];
+    if (tg < 0 || tg >= MGPT_VOCAB) {
+        const float nan = __builtin_nanf("");
+        for (int v = 0; v < MGPT_VOCAB; v++) dl[v] = nan;
+        row_nll[r] = nan;
+        return;
+    }
+    const float *l = logits + (int64_t)r * MGPT_VOCAB;
+    float mx = l[0];
+    for (int v = 1; v < MGPT_VOCAB; v++) mx = fmaxf(mx, l[v]);
+    float sum = 0.f;
+    for (int v = 0; v < MGPT_VOCAB; v++) sum += expf(l[v] - mx);
+    const float lse = mx + logf(sum);
+    for (int v = 0; v < MGPT_VOCAB; v++) {
+        const float p = expf(l[v] - lse);
+        dl[v] = (p - (v == tg ? 1.f : 0.f)) * k;
+    }
+    row_nll[r] = lse - l[tg];
+}
+
+__global__ void loss_final_rows_kernel(const double *__restrict__ acc, double n_rows, float *__restrict__ loss)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) loss[0] = (float)(acc[0] / n_rows);
+}
+
+// ----- attention of query 255 only (model.py:58-60), one workgroup per (row, head), thread j = key j -----
+// TQ = float: the exact-fp32 path (s = (q . k) * scale, p = exp(s - m), statistics (m, 1 / l) as attn_bwd_q_kernel keeps them);
+// TQ = uint16_t: the bf16 regime with the roundings attn_fwd_bf16_kernel / attn_bwd_bf16_kernel apply at query 255 -- q, k, v, y, dy are
+// bf16, the statistics (max of q . k, 1 / sum of exp((q . k - max) * scale)) and every accumulator fp32; the forward's PV product takes
+// bf16(exp(..)) and y = bf16(O / sum); the backward's dV takes bf16(P), dK and dq take bf16(dS), P = exp(..) / sum.
+// q, y, dy, dq: compact [rows][C]; k, v: the head-major planes [rows][n_head][256][HS] of the general path; dk | dv: dense [tokens][3 C]
+// columns [C, 3 C); stats [rows * n_head][2].  Matrix-vector work bound by one read of K and V.  Sums over the keys: each wave its 64
+// keys by a fixed butterfly, the four waves in order; sums over keys per output d: 256 / HS groups of keys in order, the groups in order.
+__device__ __forceinline__ float lastk_val(const float *p, int i) { return p[i]; }
+__device__ __forceinline__ float lastk_val(const uint16_t *p, int i) { return __builtin_bit_cast(float, (unsigned)p[i] << 16); }
+__device__ __forceinline__ float lastk_round(float v, const float *) { return v; }
+__device__ __forceinline__ float lastk_round(float v, const uint16_t *) { return (float)(__bf16)v; }      // (nearest-even)
+__device__ __forceinline__ void lastk_store(float *p, float v) { *p = v; }
+__device__ __forceinline__ void lastk_store(uint16_t *p, float v) { *p = __builtin_bit_cast(uint16_t, (__bf16)v); }
+
+// the key's row of HS elements into registers as fp32
+template <int HS>
+__device__ __forceinline__ void lastk_row(const float *p, float out[HS])
+{
+#pragma unroll
+    for (int d = 0; d < HS; d += 4) {
+        const float4 v = *reinterpret_cast<const float4 *>(p + d);
+        out[d] = v.x; out[d + 1] = v.y; out[d + 2] = v.z; out[d + 3] = v.w;
+    }
+}
+template <int HS>
+__device__ __forceinline__ void lastk_row(const uint16_t *p, float out[HS])
+{
+#pragma unroll
+    for (int d = 0; d < HS; d += 8) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(p + d);
+        const unsigned u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            out[d + 2 * e] = __builtin_bit_cast(float, u[e] << 16);
+            out[d + 2 * e + 1] = __builtin_bit_cast(float, u[e] & 0xffff0000u);
+        }
+    }
+}
+
+// s = q . k over d in order: the forward and the backward walk the same fmaf chain, so P is bit-identical in both
+template <int HS>
+__device__ __forceinline__ float lastk_dot(const float *__restrict__ a_lds, const float b[HS])
+{
+    float s = 0.f;
+#pragma unroll
+    for (int d = 0; d < HS; d++) s = fmaf(a_lds[d], b[d], s);
+    return s;
+}
+
+// the sum of v over the workgroup's 256 threads in a fixed order; red: 4 floats of LDS; every thread gets the sum
+__device__ __forceinline__ float lastk_sum256(float v, float *red)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();                                            // (red is free again)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+__device__ __forceinline__ float lastk_max256(float v, float *red)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// out[d] = sum_j w[j] * X[j][d] (w in LDS, X the (row, head)'s plane in memory, coalesced over d): thread (g, d) sums the keys of group g in
+// order into part[g][d]; after a barrier the caller adds the groups in order
+template <int HS, typename TQ>
+__device__ __forceinline__ void lastk_weighted_rows(const float *w, const TQ *__restrict__ X, float *part)
+{
+    constexpr int NG = kT / HS, KPG = kT / NG;
+    const int d = threadIdx.x % HS, g = threadIdx.x / HS;
+    float acc = 0.f;
+#pragma unroll 8
+    for (int j = g * KPG; j < (g + 1) * KPG; j++) acc = fmaf(w[j], lastk_val(X, j * HS + d), acc);
+    part[g * HS + d] = acc;
+}
+
+template <int HS, typename TQ>
+__global__ __launch_bounds__(256) void attn_last_fwd_kernel(const TQ *__restrict__ q, const TQ *__restrict__ kplane, const TQ *__restrict__ vplane,
+                                                            TQ *__restrict__ y, float *__restrict__ stats, int n_head, float scale)
+{
+    constexpr bool BF = sizeof(TQ) == 2;
+    constexpr int NG = kT / HS;
+    __shared__ __attribute__((aligned(16))) float sq[HS], sp[kT], part[kT], red[4];
+    const int bh = blockIdx.x, b = bh / n_head, head = bh - b * n_head, C = n_head * HS, j = threadIdx.x;
+    const TQ *K = kplane + (int64_t)bh * kT * HS, *V = vplane + (int64_t)bh * kT * HS;
+    if (j < HS) sq[j] = lastk_val(q, (int64_t)b * C + head * HS + j);
+    float kr[HS];
+    lastk_row<HS>(K + j * HS, kr);
+    __syncthreads();
+    float s = lastk_dot<HS>(sq, kr);
+    if (!BF) s *= scale;
+    const float m = lastk_max256(s, red);
+    const float p = BF ? expf((s - m) * scale) : expf(s - m);
+    const float l = lastk_sum256(p, red);
+    sp[j] = lastk_round(p, q);
+    __syncthreads();
+    lastk_weighted_rows<HS, TQ>(sp, V, part);
+    __syncthreads();
+    const float inv_l = 1.f / l;
+    if (j < HS) {
+        float o = 0.f;
+#pragma unroll
+        for (int g = 0; g < NG; g++) o += part[g * HS + j];
+        lastk_store(y + (int64_t)b * C + head * HS + j, o * inv_l);
+    }
+    if (j == 0) { stats[(int64_t)bh * 2] = m; stats[(int64_t)bh * 2 + 1] = inv_l; }
+}
+
+template <int HS, typename TQ>
+__global__ __launch_bounds__(256) void attn_last_bwd_kernel(const TQ *__restrict__ q, const TQ *__restrict__ kplane, const TQ *__restrict__ vplane,
+                                                            const TQ *__restrict__ y, const TQ *__restrict__ dy, const float *__restrict__ stats,
+                                                            float *__restrict__ dqkv, float *__restrict__ dq, int n_head, float scale)
+{
+    constexpr bool BF = sizeof(TQ) == 2;
+    constexpr int NG = kT / HS;
+    __shared__ __attribute__((aligned(16))) float sq[HS], sdy[HS], sy[HS], sds[kT], part[kT];
+    const int bh = blockIdx.x, b = bh / n_head, head = bh - b * n_head, C = n_head * HS, j = threadIdx.x;
+    const TQ *K = kplane + (int64_t)bh * kT * HS, *V = vplane + (int64_t)bh * kT * HS;
+    if (j < HS) {
+        const int64_t o = (int64_t)b * C + head * HS + j;
+        sq[j] = lastk_val(q, o); sdy[j] = lastk_val(dy, o); sy[j] = lastk_val(y, o);
+    }
+    float kr[HS], vr[HS];
+    lastk_row<HS>(K + j * HS, kr);
+    lastk_row<HS>(V + j * HS, vr);
+    const float m = stats[(int64_t)bh * 2], inv_l = stats[(int64_t)bh * 2 + 1];
+    __syncthreads();
+    float D = 0.f;                                              // rowsum(dy o y), every thread the same chain
+#pragma unroll
+    for (int d = 0; d < HS; d++) D = fmaf(sdy[d], sy[d], D);
+    const float s = lastk_dot<HS>(sq, kr);
+    const float p = (BF ? expf((s - m) * scale) : expf(s * scale - m)) * inv_l;
+    const float ds = p * (lastk_dot<HS>(sdy, vr) - D);
+    const float pw = lastk_round(p, q), dsw = lastk_round(ds, q);       // the operands of dV, and of dK and dq
+    sds[j] = dsw;
+    float *o = dqkv + ((int64_t)b * kT + j) * 3 * C + C + head * HS;       // dK_j, and dV_j at + C
+#pragma unroll
+    for (int d = 0; d < HS; d += 4) {
+        *reinterpret_cast<float4 *>(o + d) =
+            make_float4(dsw * sq[d] * scale, dsw * sq[d + 1] * scale, dsw * sq[d + 2] * scale, dsw * sq[d + 3] * scale);
+        *reinterpret_cast<float4 *>(o + C + d) = make_float4(pw * sdy[d], pw * sdy[d + 1], pw * sdy[d + 2], pw * sdy[d + 3]);
+    }
+    __syncthreads();
+    lastk_weighted_rows<HS, TQ>(sds, K, part);
+    __syncthreads();
+    if (j < HS) {
+        float a = 0.f;
+#pragma unroll
+        for (int g = 0; g < NG; g++) a += part[g * HS + j];
+        dq[(int64_t)b * C + head * HS + j] = a * scale;
     }
 }
 

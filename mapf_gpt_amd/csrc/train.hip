@@ -5,6 +5,11 @@
 // embed, layer_forward per layer, head forward and loss, head backward, layer_backward per layer in reverse, embedding backward.  The bf16
 // path reaches the shared, fp32-sized workspace through typed views (bf16_layer, bf16_grads).  Dropout (mgpt_gpt_forward_backward_drop) is a
 // DropCfg of the chunk: every site asks drops(site) and regenerates its mask from drop(site, layer); no mask is stored.
+//
+// mgpt_gpt_forward_backward_rows is the micro-step of rows with one targeted position, token 255 (every row the dataset path makes):
+// chunk_fwd_bwd_rows runs the layers below the last as chunk_fwd_bwd does, and the last layer, ln_f, the head and the cross-entropy on the
+// compact matrix of the rows' last tokens (layer_forward_last, layer_backward_last, Span, Compact).  Its normaliser is the call's row count,
+// a host-side number: that path holds no stream synchronise, no blocking copy and no host read of device memory.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -121,6 +126,33 @@ Bf16Layer bf16_layer(const TrainState *t, int l, int64_t M, int C)
 
 Bf16Grads bf16_grads(const TrainState *t) { return {reinterpret_cast<uint16_t *>(t->DY), reinterpret_cast<uint16_t *>(t->DH)}; }
 
+// ----- the compact matrix of the last-position micro-step -----
+// The tokens a token-wise launch runs over, with their gradient scratch: all M tokens of the chunk (Chunk::all), or the mc compact tokens.
+struct Span { int64_t m; float *dx, *dxn, *gp; };
+
+// A chunk of n rows keeps mc compact tokens, one per row (token 255), in the slots its last layer l = L - 1 does not fill.  mc = n in fp32
+// (gemm_tr_kernel checks every index); in bf16 n rounded up to 32, the MFMA GEMMs' k step, the padding rows zero (gather_last_kernel,
+// ce_rows_kernel), and zero rows stay zero through LayerNorm, the linears, GELU and their backward.  A slot of M C = 256 n C floats holds
+// eight compact matrices of mc C floats (mc <= 32 n): sub(slot, i).
+//   QKV[l] plane 0  q (the k and v planes are the general path's, filled for all tokens)
+//   Y[l]            y | ln_1(x) of token 255 | x of token 255
+//   XM[l], XN2[l], A[l], XF, XNF, LG, DLG, NLL, HT, DH   their roles, mc tokens (bf16: bf16_layer(t, l, mc, C)'s a and h, bf16_grads' da)
+//   AST             the softmax statistics (m, 1 / l) per (row, head), in both precisions
+//   DY              d y | d x | d ln | gain terms | d q | d ln_1 of token 255
+struct Compact {
+    int n, mc;
+    float *q, *y, *xn1, *x, *dy, *dq, *dxn1;
+    Span span;
+};
+
+Compact compact_of(const TrainState *t, int l, int n, bool bf16, int C)
+{
+    const int mc = bf16 ? (n + 31) / 32 * 32 : n;
+    auto sub = [&](float *slot, int i) { return slot + (size_t)i * mc * C; };
+    return {n, mc, t->QKV[l], t->Y[l], sub(t->Y[l], 1), sub(t->Y[l], 2), t->DY, sub(t->DY, 4), sub(t->DY, 5),
+            {(int64_t)mc, sub(t->DY, 1), sub(t->DY, 2), sub(t->DY, 3)}};
+}
+
 // ----- epilogue arguments of gemm_bf16_kernel, one constructor per kind (the fields a kind does not read stay zero) -----
 tbk::Epi epi_f32(float *out, int64_t ldc) { tbk::Epi e; e.f32 = out; e.ldc = ldc; return e; }                              // E_F32, E_PART
 tbk::Epi epi_resid(float *out, const float *res, int64_t ldc) { tbk::Epi e = epi_f32(out, ldc); e.res = res; return e; }    // E_RESID
@@ -164,8 +196,8 @@ struct DropCfg {
 };
 
 // One chunk of rows of a call: what its launches share, and the launches (chunk_fwd_bwd is the sequence).  Only layer_forward,
-// layer_backward and ln_backward have a body per precision; the head and the embedding run the fp32 kernels in both.  bf16 (MGPT_PREC_BF16)
-// is train.py's autocast regime on bf16 MFMAs (gpt_kernels_train_bf16.h).  Rounded to bf16, as autocast holds them: the operands of the
+// layer_backward, their _last forms and ln_backward have a body per precision; the head and the embedding run the fp32 kernels in both.
+// bf16 (MGPT_PREC_BF16) is train.py's autocast regime on bf16 MFMAs (gpt_kernels_train_bf16.h).  Rounded to bf16, as autocast holds them: the operands of the
 // block linears, q, k, v, attention's output and its gradient, P and dS, the linears' outputs and GELU's, the gradients of the MLP hidden
 // tensors.  fp32: the embedding sum, the residual stream and its gradient, LayerNorm, softmax statistics, the head, cross-entropy and every
 // accumulator.
@@ -261,9 +293,12 @@ struct Chunk {
     // ----- sums over the chunk's tokens by slabs: partials(S, kps) launches S partial sums of kps tokens each into t->part [S][n], which are
     // added to out[n] in order -----
     template <class Launch>
-    int slab_sum(float *out, int64_t n, int align, Launch partials)
+    int slab_sum(float *out, int64_t n, int align, Launch partials) { return slab_sum(out, n, align, M, partials); }
+    // ... over m tokens
+    template <class Launch>
+    int slab_sum(float *out, int64_t n, int align, int64_t m, Launch partials)
     {
-        const int S = slabs_of(M), kps = slab_tokens(M, align);
+        const int S = slabs_of(m), kps = slab_tokens(m, align);
         MGPT_REQUIRE((size_t)S * n <= t->part_elems, MGPT_ERR_ARG, "weight-gradient slabs exceed the workspace");
         MGPT_TRY(partials(S, kps));
         MGPT_LAUNCH(trk::slab_reduce_kernel, dim3(grid_1d(n)), dim3(256), 0, s, t->part, S, n, out);
@@ -271,45 +306,56 @@ struct Chunk {
     }
 
     // weight gradients: dW[Nout][Kin] += dY^T @ X, dY [M][Nout], X [M][Kin]; fp32 on the VALU, or bf16 MFMAs (32-token aligned slabs)
-    int weight_grad(const float *dY, const float *X, float *dW, int Nout, int Kin)
+    int weight_grad(const float *dY, const float *X, float *dW, int Nout, int Kin) { return weight_grad(dY, Nout, X, dW, Nout, Kin, M); }
+    // ... dY with row pitch ldy, over m tokens
+    int weight_grad(const float *dY, int64_t ldy, const float *X, float *dW, int Nout, int Kin, int64_t m)
     {
-        return slab_sum(dW, (int64_t)Nout * Kin, 16, [&](int S, int kps) -> int {
-            return tr_gemm<false, true, trk::OUT_PART>(dY, Nout, X, Kin, t->part, Kin, Nout, Kin, (int)M, nullptr, S, kps);
+        return slab_sum(dW, (int64_t)Nout * Kin, 16, m, [&](int S, int kps) -> int {
+            return tr_gemm<false, true, trk::OUT_PART>(dY, ldy, X, Kin, t->part, Kin, Nout, Kin, (int)m, nullptr, S, kps);
         });
     }
 
     template <typename TY, typename TX>
-    int weight_grad_bf16(const TY *dY, const TX *X, float *dW, int Nout, int Kin)
+    int weight_grad_bf16(const TY *dY, const TX *X, float *dW, int Nout, int Kin) { return weight_grad_bf16(dY, Nout, X, dW, Nout, Kin, M); }
+    template <typename TY, typename TX>
+    int weight_grad_bf16(const TY *dY, int64_t ldy, const TX *X, float *dW, int Nout, int Kin, int64_t m)
     {
-        return slab_sum(dW, (int64_t)Nout * Kin, 32, [&](int S, int kps) -> int {
-            return bf_gemm<TY, false, TX, false, tbk::E_PART>(dY, Nout, X, Kin, Nout, Kin, (int)M, epi_f32(t->part, Kin), S, kps);
+        return slab_sum(dW, (int64_t)Nout * Kin, 32, m, [&](int S, int kps) -> int {
+            return bf_gemm<TY, false, TX, false, tbk::E_PART>(dY, ldy, X, Kin, Nout, Kin, (int)m, epi_f32(t->part, Kin), S, kps);
         });
     }
 
     // ----- LayerNorm backward: DX (+)= d x from DXN, the gain's gradient gw += sum over the tokens of dxn * xhat -----
+    Span all() const { return {M, t->DX, t->DXN, t->GP}; }
+
     template <bool ADD>
-    int ln_backward_f32(const float *x, const float *w, float *gw)
+    int ln_backward_f32(const float *x, const float *w, float *gw, const Span &sp)
     {
-        MGPT_LAUNCH((trk::ln_bwd_kernel<ADD>), dim3((unsigned)cdiv64(M, 4)), dim3(256), 0, s, x, w, t->DXN, t->DX, t->GP, M, C);
-        return slab_sum(gw, C, 16, [&](int S, int kps) -> int {
-            MGPT_LAUNCH(trk::colsum_part_kernel, dim3((unsigned)cdiv(C, 256), (unsigned)S), dim3(256), 0, s, t->GP, M, C, kps, t->part);
+        MGPT_LAUNCH((trk::ln_bwd_kernel<ADD>), dim3((unsigned)cdiv64(sp.m, 4)), dim3(256), 0, s, x, w, (const float *)sp.dxn, sp.dx, sp.gp, sp.m, C);
+        return slab_sum(gw, C, 16, sp.m, [&](int S, int kps) -> int {
+            MGPT_LAUNCH(trk::colsum_part_kernel, dim3((unsigned)cdiv(C, 256), (unsigned)S), dim3(256), 0, s, (const float *)sp.gp, sp.m, C, kps, t->part);
             return MGPT_OK;
         });
     }
 
     // ... with the gain's column sums fused: one partial per 128 tokens, summed in order
     template <bool ADD>
-    int ln_backward_bf16(const float *x, const float *w, float *gw)
+    int ln_backward_bf16(const float *x, const float *w, float *gw, const Span &sp)
     {
-        const int64_t n_part = cdiv64(M, tbk::kLnTok);
-        MGPT_REQUIRE(C <= 64 * tbk::kLnMaxJ && (size_t)(n_part * C) <= t->part_elems, MGPT_ERR_UNSUPPORTED, "LayerNorm backward: C=%d, %lld tokens", C, (long long)M);
-        MGPT_LAUNCH((tbk::ln_bwd_gain_kernel<ADD>), dim3((unsigned)n_part), dim3(256), 0, s, x, w, t->DXN, t->DX, t->part, M, C);
+        const int64_t n_part = cdiv64(sp.m, tbk::kLnTok);
+        MGPT_REQUIRE(C <= 64 * tbk::kLnMaxJ && (size_t)(n_part * C) <= t->part_elems, MGPT_ERR_UNSUPPORTED, "LayerNorm backward: C=%d, %lld tokens", C, (long long)sp.m);
+        MGPT_LAUNCH((tbk::ln_bwd_gain_kernel<ADD>), dim3((unsigned)n_part), dim3(256), 0, s, x, w, (const float *)sp.dxn, sp.dx, t->part, sp.m, C);
         MGPT_LAUNCH(tbk::colsum_reduce_kernel, dim3((unsigned)cdiv(C, 64)), dim3(1024), 0, s, t->part, (int)n_part, C, gw);
         return MGPT_OK;
     }
 
     template <bool ADD>
-    int ln_backward(const float *x, size_t gain) { return bf16 ? ln_backward_bf16<ADD>(x, P + gain, G + gain) : ln_backward_f32<ADD>(x, P + gain, G + gain); }
+    int ln_backward(const float *x, size_t gain) { return ln_backward<ADD>(x, gain, all()); }
+    template <bool ADD>
+    int ln_backward(const float *x, size_t gain, const Span &sp)
+    {
+        return bf16 ? ln_backward_bf16<ADD>(x, P + gain, G + gain, sp) : ln_backward_f32<ADD>(x, P + gain, G + gain, sp);
+    }
 
     // ----- attention, one workgroup per (row, head) -----
     // fp32 backward: dq | dk | dv of DY into DQKV
@@ -461,6 +507,172 @@ struct Chunk {
     int layer_forward(int l) { return bf16 ? layer_forward_bf16(l) : layer_forward_f32(l); }
     int layer_backward(int l) { return bf16 ? layer_backward_bf16(l) : layer_backward_f32(l); }
 
+    // ----- the last layer and the head on the compact matrix of the rows' last tokens (mgpt_gpt_forward_backward_rows; no dropout) -----
+    // Of the last layer only ln_1 and the K | V projection run on all tokens; the query, attention's output, c_proj, the MLP, ln_f, the head
+    // and the cross-entropy run on token 255 of each row.  Backward: the residual gradient is non-zero at token 255 only, d K and d V are
+    // dense, so c_attn's K | V columns and ln_1 run over all tokens and everything else on the compact matrix.
+    Compact compact() const { return compact_of(t, L - 1, rows, bf16, C); }
+
+    int gather_last(const float *src, float *dst, const Compact &k)
+    {
+        MGPT_LAUNCH(trk::gather_last_kernel, dim3(grid_1d((int64_t)k.mc * C)), dim3(256), 0, s, src, dst, k.n, k.mc, C);
+        return MGPT_OK;
+    }
+    int scatter_last_add(const float *src, float *dst, const Compact &k)
+    {
+        MGPT_LAUNCH(trk::scatter_last_add_kernel, dim3(grid_1d((int64_t)k.n * C)), dim3(256), 0, s, src, dst, k.n, C);
+        return MGPT_OK;
+    }
+    // the attention kernels write the rows' tokens only: the padding rows of their compact outputs are zeroed (stream-ordered)
+    int zero_pad(void *buf, size_t elem, const Compact &k)
+    {
+        if (k.mc > k.n) MGPT_HIP(hipMemsetAsync(static_cast<char *>(buf) + (size_t)k.n * C * elem, 0, (size_t)(k.mc - k.n) * C * elem, s));
+        return MGPT_OK;
+    }
+
+    template <typename TQ>
+    int attn_last_forward(const Compact &k, const TQ *q, const TQ *kp, const TQ *vp, TQ *y)
+    {
+        const dim3 grid((unsigned)(k.n * g->nh));
+        if (g->hs == 32) MGPT_LAUNCH((trk::attn_last_fwd_kernel<32, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, t->AST, g->nh, scale);
+        else MGPT_LAUNCH((trk::attn_last_fwd_kernel<64, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, t->AST, g->nh, scale);
+        return zero_pad(y, sizeof(TQ), k);
+    }
+    template <typename TQ>
+    int attn_last_backward(const Compact &k, const TQ *q, const TQ *kp, const TQ *vp, const TQ *y, const TQ *dy)
+    {
+        const dim3 grid((unsigned)(k.n * g->nh));
+        if (g->hs == 32)
+            MGPT_LAUNCH((trk::attn_last_bwd_kernel<32, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, dy, (const float *)t->AST, t->DQKV, k.dq, g->nh, scale);
+        else
+            MGPT_LAUNCH((trk::attn_last_bwd_kernel<64, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, dy, (const float *)t->AST, t->DQKV, k.dq, g->nh, scale);
+        return zero_pad(k.dq, sizeof(float), k);
+    }
+
+    int layer_forward_last_f32()
+    {
+        const int l = L - 1;
+        const LayerOff &lo = g->layers[l];
+        const Compact k = compact();
+        const int64_t mc = k.mc;
+        float *kp = t->QKV[l] + M * C, *vp = kp + M * C;
+        MGPT_TRY(gpt_f32_layernorm(g, t->X[l], P + lo.ln1, t->XN1[l], M, s));
+        MGPT_TRY(gpt_f32_linear(g, 2, t->XN1[l], P + lo.attn_w + (size_t)C * C, kp, M, 2 * C, C, s));           // k | v planes of every token
+        MGPT_TRY(gather_last(t->XN1[l], k.xn1, k));
+        MGPT_TRY(gather_last(t->X[l], k.x, k));
+        MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(k.xn1, C, P + lo.attn_w, C, k.q, C, mc, C, C)));
+        MGPT_TRY(attn_last_forward<float>(k, k.q, kp, vp, k.y));
+        MGPT_TRY((tr_gemm<true, false, trk::OUT_RESID>(k.y, C, P + lo.proj_w, C, t->XM[l], C, mc, C, C, k.x)));
+        MGPT_TRY(gpt_f32_layernorm(g, t->XM[l], P + lo.ln2, t->XN2[l], mc, s));
+        MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(t->XN2[l], C, P + lo.fc_w, C, t->A[l], 4 * C, mc, 4 * C, C)));
+        MGPT_LAUNCH(trk::gelu_kernel, dim3(grid_1d(4 * mc * C)), dim3(256), 0, s, t->A[l], t->HT, 4 * mc * C);
+        return tr_gemm<true, false, trk::OUT_RESID>(t->HT, 4 * C, P + lo.proj2_w, 4 * C, t->XF, C, mc, C, 4 * C, t->XM[l]);
+    }
+
+    int layer_forward_last_bf16()
+    {
+        const int l = L - 1;
+        const LayerOff &lo = g->layers[l];
+        const Compact k = compact();
+        const int64_t mc = k.mc;
+        const Bf16Layer v = bf16_layer(t, l, mc, C);                // y, a, gelu(a) of the compact tokens; v.qkv: the compact q
+        uint16_t *kp = v.qkv + M * C, *vp = kp + M * C;             // the general path's k and v planes
+        MGPT_TRY(gpt_f32_layernorm(g, t->X[l], P + lo.ln1, t->XN1[l], M, s));
+        MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_QKV>(t->XN1[l], C, P + lo.attn_w + (size_t)C * C, C, M, 2 * C, C, epi_qkv(kp, C, g->hs, g->nh, M * C))));
+        MGPT_TRY(gather_last(t->XN1[l], k.xn1, k));
+        MGPT_TRY(gather_last(t->X[l], k.x, k));
+        MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_B16>(k.xn1, C, P + lo.attn_w, C, mc, C, C, epi_b16(v.qkv, C))));
+        MGPT_TRY(attn_last_forward<uint16_t>(k, v.qkv, kp, vp, v.y));
+        MGPT_TRY((bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(v.y, C, P + lo.proj_w, C, mc, C, C, epi_resid(t->XM[l], k.x, C))));
+        MGPT_TRY(gpt_f32_layernorm(g, t->XM[l], P + lo.ln2, t->XN2[l], mc, s));
+        MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_FC>(t->XN2[l], C, P + lo.fc_w, C, mc, 4 * C, C, epi_fc(v.a, v.h, 4 * C))));
+        return bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(v.h, 4 * C, P + lo.proj2_w, 4 * C, mc, C, 4 * C, epi_resid(t->XF, t->XM[l], C));
+    }
+
+    // ln_f, logits and cross-entropy of the compact tokens; the normaliser call_rows is the row count of the WHOLE call
+    int head_forward_rows(const int32_t *labels, int call_rows)
+    {
+        const Compact k = compact();
+        MGPT_TRY(gpt_f32_layernorm(g, t->XF, P + g->off_lnf, t->XNF, k.mc, s));
+        MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(t->XNF, C, P + g->off_wte, C, t->LG, kV, k.mc, kV, C)));
+        MGPT_LAUNCH(trk::ce_rows_kernel, dim3((unsigned)cdiv(k.mc, 256)), dim3(256), 0, s, (const float *)t->LG, labels, k.n, k.mc, loss_scale / (float)call_rows,
+                    t->DLG, t->NLL);
+        MGPT_LAUNCH(trk::sum_acc_kernel, dim3(1), dim3(256), 0, s, t->NLL, (int64_t)k.mc, t->loss_acc);
+        return MGPT_OK;
+    }
+
+    // ... and their backward: the compact residual gradient starts in the span's dx
+    int head_backward_rows()
+    {
+        const Compact k = compact();
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DLG, kV, P + g->off_wte, C, k.span.dxn, C, k.mc, C, kV)));
+        MGPT_TRY(weight_grad(t->DLG, kV, t->XNF, G + g->off_wte, kV, C, k.mc));
+        return ln_backward<false>(t->XF, g->off_lnf, k.span);
+    }
+
+    // the tail both precisions share: d ln_1(x) of token 255 joins DXN, ln_1 backward over all tokens, d x_mid of token 255 joins DX
+    int layer_backward_last_tail(const Compact &k)
+    {
+        MGPT_TRY(scatter_last_add(k.dxn1, t->DXN, k));
+        MGPT_TRY(ln_backward<false>(t->X[L - 1], g->layers[L - 1].ln1));
+        return scatter_last_add(k.span.dx, t->DX, k);
+    }
+
+    int layer_backward_last_f32()
+    {
+        const int l = L - 1;
+        const LayerOff &lo = g->layers[l];
+        const Compact k = compact();
+        const int64_t mc = k.mc;
+        const float *db = k.span.dx, *kp = t->QKV[l] + M * C, *vp = kp + M * C;
+        const size_t kv = (size_t)C * C;                            // c_attn's K | V rows start here
+        // MLP; HT still holds gelu(a) of the compact tokens (no layer ran after this one's forward)
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_GELU_BWD>(db, C, P + lo.proj2_w, 4 * C, t->DH, 4 * C, mc, 4 * C, C, t->A[l])));
+        MGPT_TRY(weight_grad(db, C, t->HT, G + lo.proj2_w, C, 4 * C, mc));
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DH, 4 * C, P + lo.fc_w, C, k.span.dxn, C, mc, C, 4 * C)));
+        MGPT_TRY(weight_grad(t->DH, 4 * C, t->XN2[l], G + lo.fc_w, 4 * C, C, mc));
+        MGPT_TRY(ln_backward<true>(t->XM[l], lo.ln2, k.span));
+        // attention of query 255: d y, then d q (compact) and d k | d v (dense)
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(db, C, P + lo.proj_w, C, k.dy, C, mc, C, C)));
+        MGPT_TRY(weight_grad(db, C, k.y, G + lo.proj_w, C, C, mc));
+        MGPT_TRY(attn_last_backward<float>(k, k.q, kp, vp, k.y, k.dy));
+        // c_attn: the K | V columns over all tokens, the Q rows from the compact tokens
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DQKV + C, 3 * C, P + lo.attn_w + kv, C, t->DXN, C, M, C, 2 * C)));
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(k.dq, C, P + lo.attn_w, C, k.dxn1, C, mc, C, C)));
+        MGPT_TRY(weight_grad(t->DQKV + C, 3 * C, t->XN1[l], G + lo.attn_w + kv, 2 * C, C, M));
+        MGPT_TRY(weight_grad(k.dq, C, k.xn1, G + lo.attn_w, C, C, mc));
+        return layer_backward_last_tail(k);
+    }
+
+    int layer_backward_last_bf16()
+    {
+        const int l = L - 1;
+        const LayerOff &lo = g->layers[l];
+        const Compact k = compact();
+        const int64_t mc = k.mc;
+        const Bf16Layer v = bf16_layer(t, l, mc, C);
+        const Bf16Grads d = bf16_grads(t);                          // d.dy = k.dy's slot, d.da = DH
+        const uint16_t *kp = v.qkv + M * C, *vp = kp + M * C;
+        const float *db = k.span.dx;
+        const size_t kv = (size_t)C * C;
+        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_GELU_BWD>(db, C, P + lo.proj2_w, 4 * C, mc, 4 * C, C, epi_gelu_bwd(d.da, v.a, 4 * C))));
+        MGPT_TRY(weight_grad_bf16(db, C, v.h, G + lo.proj2_w, C, 4 * C, mc));
+        MGPT_TRY((bf_gemm<uint16_t, true, float, false, tbk::E_F32>(d.da, 4 * C, P + lo.fc_w, C, mc, C, 4 * C, epi_f32(k.span.dxn, C))));
+        MGPT_TRY(weight_grad_bf16(d.da, 4 * C, t->XN2[l], G + lo.fc_w, 4 * C, C, mc));
+        MGPT_TRY(ln_backward<true>(t->XM[l], lo.ln2, k.span));
+        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_B16>(db, C, P + lo.proj_w, C, mc, C, C, epi_b16(d.dy, C))));
+        MGPT_TRY(weight_grad_bf16(db, C, v.y, G + lo.proj_w, C, C, mc));
+        MGPT_TRY(attn_last_backward<uint16_t>(k, v.qkv, kp, vp, v.y, d.dy));
+        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_F32>(t->DQKV + C, 3 * C, P + lo.attn_w + kv, C, M, C, 2 * C, epi_f32(t->DXN, C))));
+        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_F32>(k.dq, C, P + lo.attn_w, C, mc, C, C, epi_f32(k.dxn1, C))));
+        MGPT_TRY(weight_grad_bf16(t->DQKV + C, 3 * C, t->XN1[l], G + lo.attn_w + kv, 2 * C, C, M));
+        MGPT_TRY(weight_grad_bf16(k.dq, C, k.xn1, G + lo.attn_w, C, C, mc));
+        return layer_backward_last_tail(k);
+    }
+
+    int layer_forward_last() { return bf16 ? layer_forward_last_bf16() : layer_forward_last_f32(); }
+    int layer_backward_last() { return bf16 ? layer_backward_last_bf16() : layer_backward_last_f32(); }
+
     // embedding (model.py:171-175), fp32 in both precisions: d wpe[t] += sum over rows, d wte[id] += sum over the tokens with that id
     // under dropout X[0] = m s (wte + wpe) (model.py:175) and the sums take m s DX (in DXN, free after the last LayerNorm backward)
     int embed()
@@ -494,6 +706,22 @@ int chunk_fwd_bwd(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows, cons
     MGPT_TRY(c.head_forward());
     MGPT_TRY(c.head_backward());
     for (int l = g->L - 1; l >= 0; l--) MGPT_TRY(c.layer_backward(l));
+    return c.embedding_backward();
+}
+
+// one chunk of rows of mgpt_gpt_forward_backward_rows: the layers below the last run chunk_fwd_bwd's launches, the last layer and the head
+// the compact ones; call_rows normalises the cross-entropy
+int chunk_fwd_bwd_rows(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows, const int32_t *labels, int call_rows, float loss_scale, int precision,
+                       hipStream_t s)
+{
+    Chunk c = {g, t, tok, nullptr, rows, loss_scale, precision == MGPT_PREC_BF16, s, DropCfg()};
+    MGPT_TRY(c.embed());
+    for (int l = 0; l + 1 < g->L; l++) MGPT_TRY(c.layer_forward(l));
+    MGPT_TRY(c.layer_forward_last());
+    MGPT_TRY(c.head_forward_rows(labels, call_rows));
+    MGPT_TRY(c.head_backward_rows());
+    MGPT_TRY(c.layer_backward_last());
+    for (int l = g->L - 2; l >= 0; l--) MGPT_TRY(c.layer_backward(l));
     return c.embedding_backward();
 }
 
@@ -646,6 +874,29 @@ extern "C" int mgpt_gpt_forward_backward_drop(mgpt_gpt *g, const uint8_t *d_toke
         MGPT_TRY(chunk_fwd_bwd(g, t, tk, n, tg, loss_scale, precision, dc, s));
     }
     if (d_loss) MGPT_LAUNCH(trk::loss_final_kernel, dim3(1), dim3(64), 0, s, (const double *)t->loss_acc, t->cnt, d_loss);
+    return MGPT_OK;
+}
+
+extern "C" int mgpt_gpt_forward_backward_rows(mgpt_gpt *g, const uint8_t *d_tokens, int rows, const int32_t *d_labels, float loss_scale,
+                                              float *d_loss, int precision, void *stream)
+{
+    MGPT_TRY(require_train(g));
+    MGPT_REQUIRE(d_tokens && d_labels, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(rows > 0, MGPT_ERR_ARG, "rows=%d", rows);
+    MGPT_REQUIRE(std::isfinite(loss_scale), MGPT_ERR_ARG, "loss_scale=%g: a finite factor", (double)loss_scale);
+    MGPT_REQUIRE(!g->has_bias, MGPT_ERR_UNSUPPORTED, "training supports bias = False checkpoints only (the released configs)");
+    MGPT_REQUIRE(precision == MGPT_PREC_F32 || precision == MGPT_PREC_BF16, MGPT_ERR_UNSUPPORTED,
+                 "training precision %d: MGPT_PREC_F32 (exact fp32) or MGPT_PREC_BF16 (bf16 mixed precision)", precision);
+    TrainState *t = ts(g);
+    MGPT_REQUIRE(t->max_rows > 0, MGPT_ERR_STATE, "the training workspace holds no activation memory (a re-size failed): mgpt_gpt_train_alloc again");
+    hipStream_t s = (hipStream_t)stream;
+    // every launch below is stream-ordered and the normaliser is `rows`: the host waits for nothing
+    MGPT_HIP(hipMemsetAsync(t->loss_acc, 0, sizeof(double), s));
+    for (int r0 = 0; r0 < rows; r0 += t->max_rows) {
+        const int n = std::min(t->max_rows, rows - r0);
+        MGPT_TRY(chunk_fwd_bwd_rows(g, t, d_tokens + (size_t)r0 * kT, n, d_labels + r0, rows, loss_scale, precision, s));
+    }
+    if (d_loss) MGPT_LAUNCH(trk::loss_final_rows_kernel, dim3(1), dim3(64), 0, s, (const double *)t->loss_acc, (double)rows, d_loss);
     return MGPT_OK;
 }
 

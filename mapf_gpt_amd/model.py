@@ -356,6 +356,38 @@ class GPT:
                                                                  int(step) & 0xFFFFFFFFFFFFFFFF, int(row0), int(dropout_sites), _lib.stream_ptr()))
         return loss
 
+    def forward_backward_rows(self, rows_u8, labels, loss_scale=1.0, precision="f32", check=True):
+        """forward_backward for rows with ONE targeted position, token 255 (what dataset_rows, EpisodeStore, the .arrow shards and
+        ArrowBatches(labels=True) carry): = forward_backward(rows_u8, targets) with targets[r, 255] = labels[r] and -1 elsewhere, the loss
+        the mean over the call's rows.  rows_u8 int8 / uint8 [B, 256] and labels (any integer dtype, [B]) may live on the host or the
+        device; casts happen on the device and no [B, 256] target matrix is built.  The last layer, ln_f, the head and the cross-entropy run
+        on token 255 only, and the call never waits for the device (the general call waits once per call for its targeted-position count).
+        check=True validates the labels against [0, 67) with one min / max (a wait when they live on the device); with check=False an
+        out-of-range label makes the loss and the next gradient norm NaN.  Gradients accumulate into the same buffer as forward_backward's,
+        in either precision.  Dropout is not built here: a config.dropout > 0 in training mode raises NotImplementedError (forward_backward
+        serves it); after eval() the call runs, as the general one does."""
+        if precision not in _lib.PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}, got {precision!r}")
+        self._require_train()
+        if self.training and self.config.dropout > 0:
+            raise NotImplementedError(f"forward_backward_rows has no dropout (config.dropout = {self.config.dropout}): use "
+                                      "forward_backward(idx, targets), the general call, which serves it")
+        tokens = self._tokens_u8(rows_u8)
+        B, T = tokens.shape
+        if T != 256:
+            raise ValueError(f"rows_u8 must be [B, 256], got {tuple(tokens.shape)}")
+        labels = torch.as_tensor(labels)
+        if labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.dim() != 1 or labels.numel() != B:
+            raise ValueError(f"labels must be an integer tensor [{B}] (one per row), got {labels.dtype} {tuple(labels.shape)}")
+        if check and B and (int(labels.min()) < 0 or int(labels.max()) >= 67):
+            raise ValueError("labels must lie in [0, 67)")
+        lb = labels.to(device=self.device, dtype=torch.int32).contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().mgpt_gpt_forward_backward_rows(self._h, _lib.ptr(tokens), B, _lib.ptr(lb), float(loss_scale), _lib.ptr(loss),
+                                                                 _lib.PRECISIONS[precision], _lib.stream_ptr()))
+        return loss
+
     def zero_grad(self, set_to_none=True):
         self._require_train()
         with torch.cuda.device(self.device):

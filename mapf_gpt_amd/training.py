@@ -97,11 +97,15 @@ class ArrowBatches:
     """= MapfArrowDataset.__iter__ (fast_data_loader.py:39-67): files in name order, forever; each file's rows shuffled when it is loaded
     (one numpy Generator seeded once), batches of batch_size consecutive rows (the last one of a file may be shorter).  Yields
     (inputs int8 [b, 256], targets int64 [b, 256]) on the host: -1 everywhere except position 255 = the expert action.  rank / world: the
-    files are dealt to the ranks of a data-parallel run (rank_files) and the generator is seeded with seed + rank; the defaults change nothing."""
+    files are dealt to the ranks of a data-parallel run (rank_files) and the generator is seeded with seed + rank; the defaults change nothing.
+    labels=True yields (inputs int8 [b, 256], labels int64 [b]) instead, the input of GPT.forward_backward_rows: the same generator draws
+    in the same order, so labels equals the default mode's targets[:, -1] batch for batch, and no [b, 256] target matrix is built.  That
+    mode validates a file's labels against [0, 67) on the host when it loads the file (ValueError), so the micro-steps need no check."""
 
-    def __init__(self, path, batch_size, seed=1337, rank=0, world=1):
+    def __init__(self, path, batch_size, seed=1337, rank=0, world=1, labels=False):
         self.files = rank_files(shard_files(path), rank, world)
         self.batch_size = int(batch_size)
+        self.labels = bool(labels)
         self.rng = np.random.Generator(np.random.PCG64(seed + rank))     # train.py:127,142: every rank its own shuffle
 
     def load(self, f):
@@ -109,6 +113,11 @@ class ArrowBatches:
         x, y = read_arrow(f)
         idx = self.rng.permutation(len(x))
         x, y = x[idx], np.asarray(y)[idx]
+        if self.labels:
+            y = y.astype(np.int64)
+            if len(y) and (y.min() < 0 or y.max() >= 67):
+                raise ValueError(f"{f}: labels must lie in [0, 67), got [{y.min()}, {y.max()}]")
+            return x, y
         t = np.full(x.shape, -1, np.int64)
         t[:, -1] = y
         return x, t
@@ -134,6 +143,10 @@ def _cpu(obj):
 DTYPES = {"float32": "f32", "bfloat16": "bf16"}       # --dtype (train.py:66-70) -> precision of forward_backward and scoring.evaluate
 
 
+ROWS_CALL_DROPOUT = ("--rows-call with dropout {} > 0: forward_backward_rows has no dropout (its masks are not built for the compact last "
+                     "layer); drop --rows-call, or pass --dropout 0")
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--init", required=True, help='shape name ("2M", "6M", "85M", "tiny") or a checkpoint path')
@@ -152,6 +165,9 @@ def parse_args(argv=None):
     ap.add_argument("--dropout", type=float, default=None,
                     help="dropout probability of the training forward (train.py:43: 0 for pre-training, 0.1+ for fine-tuning); default: the "
                          "--init checkpoint's model_args value, 0.0 for a shape name.  Stored in the checkpoint's model_args")
+    ap.add_argument("--rows-call", action="store_true",
+                    help="run the micro-steps through GPT.forward_backward_rows: the last layer, head and loss on token 255 only and no "
+                         "host wait per micro-step; the same gradients up to summation order.  Needs an effective dropout of 0")
     ap.add_argument("--log-interval", type=int, default=0,
                     help='print {"iter", "loss", "ms"} every N iterations (train.py:346-355); 0 = no such line')
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -164,6 +180,8 @@ def parse_args(argv=None):
                  "(use bfloat16, which needs none, or float32)")
     if a.dropout is not None and not (0.0 <= a.dropout < 1.0):
         ap.error("--dropout must lie in [0, 1)")
+    if a.rows_call and a.dropout:
+        ap.error(ROWS_CALL_DROPOUT.format(a.dropout))
     a.precision = DTYPES[a.dtype]
     return a
 
@@ -258,6 +276,8 @@ def run(a, ranks):
         args, sd = weights.model_args(a.init), weights.synthetic_state_dict(a.init, seed=a.seed)
     if a.dropout is not None:                      # the flag overrides the checkpoint's value
         args = dict(args, dropout=float(a.dropout))
+    if a.rows_call and args.get("dropout", 0.0) > 0:         # (the checkpoint's value, when no flag overrides it)
+        raise SystemExit("training: " + ROWS_CALL_DROPOUT.format(args["dropout"]))
     net = GPT(GPTConfig(**args), max_rows=a.batch_size, precision="f32")
     net.load_state_dict(sd)
     net.set_dropout_rng(a.seed)                    # dropout seed = --seed; the step is set per micro-step (dropout_step)
@@ -267,7 +287,7 @@ def run(a, ranks):
     if ckpt is not None:
         opt.load_state_dict(ckpt["optimizer"])
         iter_num, best_val_loss = int(ckpt["iter_num"]), float(ckpt["best_val_loss"])
-    train_it = iter(ArrowBatches(a.data, a.batch_size, a.seed, rank, world))
+    train_it = iter(ArrowBatches(a.data, a.batch_size, a.seed, rank, world, labels=a.rows_call))     # (labels validated per file at load)
     val_it = iter(ArrowBatches(a.val, a.batch_size, a.seed + 1))          # (the validation split is not divided)
     if master:
         os.makedirs(a.out_dir, exist_ok=True)
@@ -279,7 +299,7 @@ def run(a, ranks):
         for split, it in (("train", train_it), ("val", val_it)):
             xs, ts = zip(*[next(it) for _ in range(a.eval_iters)])
             x, t = np.concatenate(xs), np.concatenate(ts)
-            out[split] = scoring.evaluate(net, x, t[:, -1], batch_size=a.batch_size, precision=a.precision)["loss"]
+            out[split] = scoring.evaluate(net, x, t if t.ndim == 1 else t[:, -1], batch_size=a.batch_size, precision=a.precision)["loss"]
         net.train()
         return out
 
@@ -304,8 +324,11 @@ def run(a, ranks):
                     rec["saved"] = os.path.join(a.out_dir, "ckpt.pt")
             print(json.dumps(rec), flush=True)
         for micro in range(accum):                             # train.py:314-331
-            loss = net.forward_backward(torch.as_tensor(X), torch.as_tensor(Y), loss_scale=1.0 / accum, precision=a.precision,
-                                        dropout_step=dropout_step(iter_num, a.gradient_accumulation_steps, rank, world, micro))
+            if a.rows_call:
+                loss = net.forward_backward_rows(torch.as_tensor(X), torch.as_tensor(Y), loss_scale=1.0 / accum, precision=a.precision, check=False)
+            else:
+                loss = net.forward_backward(torch.as_tensor(X), torch.as_tensor(Y), loss_scale=1.0 / accum, precision=a.precision,
+                                            dropout_step=dropout_step(iter_num, a.gradient_accumulation_steps, rank, world, micro))
             X, Y = next(train_it)
         if ranks is not None:                                  # train.py:315-322: the ranks' gradients meet after the last micro-step
             ranks.sync_grads(net)

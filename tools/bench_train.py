@@ -2,7 +2,7 @@
 as a yardstick only, torch fp32 eager autograd of an in-repo restatement of model.py (oracle/gpt_oracle.py's formulas) on the same GPU.
 
     python tools/bench_train.py [--shapes 6M:512,6M:2048,2M:4096,85M:512] [--precision f32,bf16] [--torch-rows 512] [--iters 3] [--warmup 1]
-                                [--dropout P] [--lib PATH]
+                                [--dropout P] [--lib PATH] [--call general|rows|ab] [--accum N]
     python tools/bench_train.py --grad-sync WORLD [--grad-sync-shapes 6M,85M] [--iters 5] [--warmup 2]
 
 --lib PATH times another build of the library (a file `python -m mapf_gpt_amd.build --out` writes) in place of the in-tree one: the same
@@ -22,6 +22,12 @@ rank's own buffer, each as the median over --iters windows of 20 back-to-back ca
 per call and the fraction of 8 TB/s by counted bytes (export: read n and write n floats; reduce: read WORLD x n and write n, (WORLD + 1) 4 n
 bytes).  The all_gather itself is not in it: it needs the other ranks.  Nothing else runs in that mode.
 
+--call rows times GPT.forward_backward_rows (the last-position micro-step: the last layer, head and loss on token 255 only, no host wait) on
+the same rows and labels in place of forward_backward; --call ab times both in one process, alternating general, rows, general, rows ...
+call by call, and prints for each the median and the range of its --iters timed regions.  --accum N puts N back-to-back micro-steps in a
+timed region (gradient accumulation: the general call waits for the stream once per micro-step, the rows call never).  In these modes a
+line carries the micro-step timings only (no clip + AdamW, forward or torch yardstick).  The default, --call general, is unchanged.
+
 Targets follow the dataset's pattern (-1 except the last position, fast_data_loader.py:58).  Prints one JSON line per shape: median ms of
 each part over --iters timed calls after --warmup untimed ones, HIP events on the current stream.  The torch yardstick runs on
 min(rows, --torch-rows) rows (its activations are several times ours; 0 skips it) and reports the rows it ran."""
@@ -36,6 +42,56 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mapf_gpt_amd.model import build_model  # noqa: E402
+
+
+def timed_ab(fns, iters, warmup):
+    """{name: [ms per timed region]} of the calls fns = {name: fn}, alternating between them region by region"""
+    out = {k: [] for k in fns}
+    for i in range(warmup + iters):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if i >= warmup:
+                out[k].append(a.elapsed_time(b))
+    return out
+
+
+def count_flops_rows(args, rows, T=256, V=67):
+    """... of one forward_backward_rows call: the last layer keeps its K | V projection on all tokens (4 C^2 per token) and runs the rest,
+    the head included, on one token per row"""
+    C, L = args["n_embd"], args["n_layer"]
+    return 3 * rows * (T * ((L - 1) * (24 * C * C + 4 * T * C) + 4 * C * C) + 20 * C * C + 4 * T * C + 2 * C * V)
+
+
+def micro_steps(a, name, rows, args, tokens, targets):
+    """--call rows / ab: the micro-step alone, a.accum of them per timed region"""
+    labels = targets[:, -1].contiguous()
+    for prec in a.precision.split(","):
+        net = build_model(args, seed=0, max_rows=rows).train()
+
+        def general():
+            for _ in range(a.accum):
+                net.forward_backward(tokens, targets, loss_scale=1.0 / a.accum, precision=prec)
+
+        def rows_call():
+            for _ in range(a.accum):
+                net.forward_backward_rows(tokens, labels, loss_scale=1.0 / a.accum, precision=prec, check=False)
+        fns = {"general": general, "rows": rows_call} if a.call == "ab" else {"rows": rows_call}
+        ms = timed_ab(fns, a.iters, a.warmup)
+        rec = {"shape": name, "rows": rows, "precision": prec, "call": a.call, "accum": a.accum}
+        for k, v in ms.items():
+            rec[k + "_ms"] = round(float(np.median(v)), 3)
+            rec[k + "_range_ms"] = [round(min(v), 3), round(max(v), 3)]
+        if a.call == "ab":
+            rec["rows_over_general"] = round(rec["rows_ms"] / rec["general_ms"], 4)
+            rec["ranges_overlap"] = not (max(ms["rows"]) < min(ms["general"]) or max(ms["general"]) < min(ms["rows"]))
+            rec["flops_rows_over_general"] = round(count_flops_rows(args, rows) / count_flops(args, rows), 4)
+        print(json.dumps(rec), flush=True)
+        del net
+        torch.cuda.empty_cache()
 
 
 def timed(fn, iters, warmup):
@@ -152,6 +208,9 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--lib", default=None, help="path of the library to time (default: the in-tree build)")
+    ap.add_argument("--call", default="general", choices=["general", "rows", "ab"],
+                    help="general: forward_backward (default); rows: forward_backward_rows; ab: both, alternating in one process")
+    ap.add_argument("--accum", type=int, default=1, help="--call rows / ab: back-to-back micro-steps per timed region")
     ap.add_argument("--grad-sync", type=int, default=0, metavar="WORLD",
                     help="time export_grads and reduce_grads over WORLD gathered buffers instead of the training step")
     ap.add_argument("--grad-sync-shapes", default="6M,85M")
@@ -167,6 +226,11 @@ def main(argv=None):
         targets[:, -1] = torch.as_tensor(rng.integers(0, 5, rows), dtype=torch.int32).cuda()
         from mapf_gpt_amd import weights
         args = weights.model_args(name)
+        if a.call != "general":
+            if a.dropout > 0:
+                ap.error("--call rows / ab: forward_backward_rows has no dropout")
+            micro_steps(a, name, rows, args, tokens, targets)
+            continue
         for prec in a.precision.split(","):
             net = build_model(dict(args, dropout=a.dropout), seed=0, max_rows=rows)
             net.set_dropout_rng(0)
