@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <initializer_list>
 #include <utility>
 #include <vector>
 
@@ -59,6 +60,25 @@ public:
     // ... pinned host memory
     template <class T>
     Error alloc_host(T **p, size_t bytes) { return record(reinterpret_cast<void **>(p), bytes, true); }
+
+    // one request of alloc_all: where the pointer goes and how many bytes of device memory it gets
+    struct Request {
+        void **p;
+        size_t bytes;
+        template <class T>
+        Request(T **p_, size_t bytes_) : p(reinterpret_cast<void **>(p_)), bytes(bytes_) {}
+    };
+    // the requests in order, up to the first failure, whose error it returns: the failed pointer and every later one are nullptr, what
+    // was allocated before it is owned by this arena (a caller that gives up releases the arena, or lets a local one go out of scope)
+    Error alloc_all(std::initializer_list<Request> requests)
+    {
+        for (const Request &r : requests) *r.p = nullptr;
+        for (const Request &r : requests) {
+            const Error e = record(r.p, r.bytes, false);
+            if (e != Mem::ok) return e;
+        }
+        return Mem::ok;
+    }
 
     // frees everything, latest first; the arena is empty and usable afterwards.  (The owner's pointers dangle: it resets itself as a whole.)
     void release()

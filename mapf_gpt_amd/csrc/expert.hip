@@ -12,8 +12,9 @@
 // rebuilds the fields of the agents whose goal changed and pibt_lifelong_post_kernel stands in pibt_since_kernel's place.
 // An opt-in collision shield for a policy (pibt_shield_kernel) runs the same generator on the policy's action
 // preferences in the place of section 20's keys: the PREF = true instantiation.  Opt-in again, the shield runs on lifelong episodes
-// (DESIGN.md section 35): the plan is unchanged, pibt_shield_lifelong_post_kernel follows the env step with section 30's rules and a
-// step index that lives on the device, since a captured step is replayed without the host.
+// (DESIGN.md section 35): the plan is unchanged and the same pibt_lifelong_post_kernel follows the env step, on the same state
+// (mgpt_expert::Lifelong: a context is a planner or a shield, never both).  Its step index lives on the device, since a captured
+// step is replayed without the host.
 //
 // One step of one instance:
 //   order      agents by (since desc, id asc), since = steps since the agent last stood on its goal;
@@ -160,6 +161,44 @@ __device__ __forceinline__ void rank_by_since(const uint32_t *snc, uint16_t *ord
 }
 
 __device__ __forceinline__ unsigned swap_D(const GenView &G, unsigned a, int v) { return G.dist[(size_t)a * G.cells + v]; }
+
+// The frame of one step of the plan and shield kernels, from the env's state (g0 = the instance's first global row): cell / nxt / snc
+// in LDS, the agents scattered into occ_now, order[] ranked.  per_agent(a, c) runs once per agent in the fill loop, with its cell.
+// Returns behind the second barrier: order[] is complete, snc[] is dead and the stack takes its place.
+template <class F>
+__device__ __forceinline__ void frame_fill(const GenView &G, const int16_t *pos, const uint32_t *since, size_t g0, F per_agent)
+{
+    for (int a = G.lane; a < G.n_agents; a += 64) {
+        int c = (int)pos[2 * (g0 + a)] * G.W + (int)pos[2 * (g0 + a) + 1];
+        c = min(max(c, 0), G.cells - 1);                                  // (env states are inside the frame)
+        G.L.cell[a] = c;
+        G.L.nxt[a] = -1;
+        G.L.snc[a] = since[g0 + a];
+        G.occ_now[c] = (uint16_t)a;
+        per_agent(a, c);
+    }
+    __syncthreads();
+    rank_by_since(G.L.snc, G.L.order, G.n_agents, G.lane);
+    __syncthreads();
+}
+
+// The plan of a step back to the env's layout, behind the generator's barrier: nxt unpacked into actions and planned, the workspace
+// left all-NIL for the next step.  per_agent(a, k, was) runs once per agent with its planned action and the one actions[] held on entry.
+template <class F>
+__device__ __forceinline__ void plan_write_back(const GenView &G, int32_t *actions, int16_t *planned, size_t g0, F per_agent)
+{
+    for (int a = G.lane; a < G.n_agents; a += 64) {
+        const int v = G.L.nxt[a], u = v & 0xFFFFFF, k = (v >> 24) & 7;
+        const int ur = u / G.W;
+        const int was = actions[g0 + a];
+        actions[g0 + a] = k;
+        planned[2 * (g0 + a)] = (int16_t)ur;
+        planned[2 * (g0 + a) + 1] = (int16_t)(u - ur * G.W);
+        per_agent(a, k, was);
+        G.occ_now[G.L.cell[a]] = (uint16_t)kNil;                          // leave the workspace all-NIL for the next step
+        G.next_occ[u] = (uint16_t)kNil;
+    }
+}
 
 // count(v_pusher, v_puller): n = the free neighbours of v_puller that are neither v_pusher nor a dead end an agent rests in; other = the
 // last of them in action order
@@ -417,34 +456,15 @@ __global__ __launch_bounds__(64) void pibt_plan_kernel(const uint8_t *__restrict
     uint16_t *occ_now = occ + (size_t)inst * 2 * cells, *next_occ = occ_now + cells;
     const size_t map0 = (size_t)(inst % n_grids) * cells;
     const GenView G{grids + map0, SWAP ? degs + map0 : nullptr, dist + g0 * (size_t)cells, occ_now, next_occ, L, n_agents, H, W, cells, lane};
-    const int *cell = L.cell, *nxt = L.nxt;
 
-    for (int a = lane; a < n_agents; a += 64) {
-        int c = (int)pos[2 * (g0 + a)] * W + (int)pos[2 * (g0 + a) + 1];
-        c = min(max(c, 0), cells - 1);                                    // (env states are inside the frame)
-        L.cell[a] = c;
-        L.nxt[a] = -1;
-        L.snc[a] = since[g0 + a];
-        occ_now[c] = (uint16_t)a;
-    }
-    __syncthreads();
-    rank_by_since(L.snc, L.order, n_agents, lane);
-    __syncthreads();                                                      // order[] complete; snc[] is dead, the stack takes its place
-
+    frame_fill(G, pos, since, g0, [](int, int) {});
     pibt_generate<SWAP, false>(G, seed, t, (inst_offset + inst) * (int64_t)n_agents);
     __syncthreads();
 
     const int tl = len[inst];
-    for (int a = lane; a < n_agents; a += 64) {
-        const int v = nxt[a], u = v & 0xFFFFFF, k = (v >> 24) & 7;
-        const int ur = u / W;
-        actions[g0 + a] = k;
-        planned[2 * (g0 + a)] = (int16_t)ur;
-        planned[2 * (g0 + a) + 1] = (int16_t)(u - ur * W);
+    plan_write_back(G, actions, planned, g0, [=](int a, int k, int) {     // (by value: a capture by reference costs the kernel 3 VGPRs)
         if (tl < max_steps) log[(g0 + a) * (size_t)max_steps + tl] = (int8_t)k;
-        occ_now[cell[a]] = (uint16_t)kNil;                                // leave the workspace all-NIL for the next step
-        next_occ[u] = (uint16_t)kNil;
-    }
+    });
     if (lane == 0 && tl < max_steps) len[inst] = tl + 1;
 }
 
@@ -492,15 +512,8 @@ __global__ __launch_bounds__(64) void pibt_shield_kernel(const uint8_t *__restri
     uint16_t *occ_now = occ + (size_t)inst * 2 * cells, *next_occ = occ_now + cells;
     const size_t map0 = (size_t)(inst % n_grids) * cells;
     const GenView G{grids + map0, nullptr, dist + g0 * (size_t)cells, occ_now, next_occ, L, n_agents, H, W, cells, lane};
-    const int *cell = L.cell, *nxt = L.nxt;
 
-    for (int a = lane; a < n_agents; a += 64) {
-        int c = (int)pos[2 * (g0 + a)] * W + (int)pos[2 * (g0 + a) + 1];
-        c = min(max(c, 0), cells - 1);                                    // (env states are inside the frame)
-        L.cell[a] = c;
-        L.nxt[a] = -1;
-        L.snc[a] = since[g0 + a];
-        occ_now[c] = (uint16_t)a;
+    frame_fill(G, pos, since, g0, [=](int a, int c) {                     // and the preference word of every agent
         const int f = actions[g0 + a];
         first[g0 + a] = f;
         unsigned key[5], valid = 0;
@@ -511,69 +524,37 @@ __global__ __launch_bounds__(64) void pibt_shield_kernel(const uint8_t *__restri
             if (neighbour(c, k, H, W, u) && G.grid[u] == 0 && swap_D(G, (unsigned)a, u) != kUnreach) valid |= 1u << k;
         }
         L.pref[a] = (uint16_t)pref_word(valid, f, key);
-    }
-    __syncthreads();
-    rank_by_since(L.snc, L.order, n_agents, lane);
-    __syncthreads();                                                      // order[] complete; snc[] is dead, the stack takes its place
-
+    });
     pibt_generate<false, false, true>(G, 0, 0, 0);
     __syncthreads();
 
     int n_over = 0;
-    for (int a = lane; a < n_agents; a += 64) {
-        const int v = nxt[a], u = v & 0xFFFFFF, k = (v >> 24) & 7;
-        const int ur = u / W;
-        n_over += (k != actions[g0 + a]) ? 1 : 0;                         // still the sampler's action
-        actions[g0 + a] = k;
-        planned[2 * (g0 + a)] = (int16_t)ur;
-        planned[2 * (g0 + a) + 1] = (int16_t)(u - ur * W);
-        occ_now[cell[a]] = (uint16_t)kNil;                                // leave the workspace all-NIL for the next step
-        next_occ[u] = (uint16_t)kNil;
-    }
+    plan_write_back(G, actions, planned, g0, [&](int, int k, int sampled) { n_over += (k != sampled) ? 1 : 0; });
     for (int off = 32; off > 0; off >>= 1) n_over += __shfl_xor(n_over, off, 64);
     if (lane == 0) overrides[inst] += n_over;
 }
 
-// ---- lifelong episodes: the post-step kernel, in pibt_since_kernel's place when mgpt_expert_set_lifelong is on ----
+// ---- lifelong episodes (DESIGN.md sections 30 and 35): the post-step kernel, in pibt_since_kernel's place when ex->lifelong is on ----
 // After the env has stepped an agent that arrived already holds the next goal of its queue, so "on the goal" is decided against `held`,
 // the expert's own copy of the goals the agents pursued during the step: arrived = the new cell equals the held goal, which is the env's
 // own test on the same values, so the count equals the env's `reached` exactly.  Then held takes the env's goals for the next step.
 // One wave64 workgroup per instance, the agents in a strided loop (a cell is one 32-bit word: row | column << 16), the arrivals of the
-// step summed by shuffles and written by lane 0 to arrivals[inst][t].  `live` says the instance was not done when the step began: the
+// step summed by shuffles and written by lane 0 to arrivals[inst][k].  `live` says the instance was not done when the step began: the
 // env's done flag cannot, it is already set after the episode's last step, whose arrivals still count.  Plain vector stores only.
+//
+// The one kernel of the planner (mgpt_expert_step) and of the shield on lifelong episodes (mgpt_expert_shield_commit, DESIGN.md
+// section 35).  The shield's launches are replayed from a captured graph and never pass the host, so the slot k of the arrivals log is
+// steps[inst], the number of steps this instance has made since reset: lane 0 of the instance's own wave reads it, stores the step's
+// arrivals only while 0 <= k < max_steps (a graph replayed beyond the step cap writes nothing out of range) and stores k + 1.  No
+// other wave touches the counter: no race, no atomics.  The launch covers every instance, guarded by `live`; it does not read retire
+// mode's live list.  For the planner k is the host's step index t, as it was when the host passed t in: live[inst] is 1 at reset and
+// the kernel returns early once it is 0, for good, so an instance that reaches the slot store has run this kernel in every one of the
+// host's t steps since reset, and steps[inst], 0 at reset and one more per run, equals t.
 __global__ __launch_bounds__(64) void pibt_lifelong_post_kernel(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ goal,
                                                                 const uint8_t *__restrict__ done, uint32_t *__restrict__ since,
                                                                 uint32_t *__restrict__ held, uint8_t *__restrict__ live,
-                                                                int16_t *__restrict__ arrivals, int n_agents, int max_steps, int64_t t)
-{
-    const int inst = blockIdx.x, lane = threadIdx.x;
-    if (live[inst] == 0) return;                                          // wave-uniform: done before this step, nothing moved
-    const size_t g0 = (size_t)inst * n_agents;
-    int n = 0;
-    for (int a = lane; a < n_agents; a += 64) {
-        const bool on = pos[g0 + a] == held[g0 + a];
-        since[g0 + a] = on ? 0u : since[g0 + a] + 1u;
-        held[g0 + a] = goal[g0 + a];
-        n += on ? 1 : 0;
-    }
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
-    if (lane == 0) {
-        if (t < (int64_t)max_steps) arrivals[(size_t)inst * max_steps + t] = (int16_t)n;
-        live[inst] = done[inst] == 0 ? 1 : 0;
-    }
-}
-
-// ---- the shield on lifelong episodes: the post-step kernel, in pibt_since_kernel's place when
-// mgpt_expert_set_shield_lifelong is on -- pibt_lifelong_post_kernel's rules with the step index on the device ----------------------
-// The shield's launches are replayed from a captured graph and never pass the host, so the slot of the arrivals log is steps[inst], the
-// number of steps this instance has made since reset: lane 0 of the instance's own wave reads it, stores the step's arrivals only while
-// 0 <= k < max_steps (a graph replayed beyond the step cap writes nothing out of range) and stores k + 1.  No other wave touches the
-// counter: no race, no atomics.  The launch covers every instance, guarded by `live`; it does not read retire mode's live list.
-__global__ __launch_bounds__(64) void pibt_shield_lifelong_post_kernel(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ goal,
-                                                                       const uint8_t *__restrict__ done, uint32_t *__restrict__ since,
-                                                                       uint32_t *__restrict__ held, uint8_t *__restrict__ live,
-                                                                       int16_t *__restrict__ arrivals, int32_t *__restrict__ steps,
-                                                                       int n_inst, int n_agents, int max_steps)
+                                                                int16_t *__restrict__ arrivals, int32_t *__restrict__ steps, int n_inst,
+                                                                int n_agents, int max_steps)
 {
     const int inst = blockIdx.x, lane = threadIdx.x;
     if (inst >= n_inst || live[inst] == 0) return;                        // wave-uniform: done before this step, nothing moved
@@ -1127,12 +1108,14 @@ struct mgpt_expert {
         int max_rounds = 0, horizon = 0;
         int32_t *path = nullptr, *arr = nullptr, *rstate = nullptr, *adopted = nullptr;
     } rf;
-    // lifelong episodes (mgpt_expert_set_lifelong): off (all NULL) by default
+    // lifelong episodes: off (all NULL) by default.  One flag and one state for the planner (mgpt_expert_set_lifelong) and the shield
+    // (mgpt_expert_set_shield_lifelong): which of the two it is follows from `shield`, a context is never both
     bool lifelong = false;
     struct Lifelong {                           // buffers, owned by lifelong_mem
         uint32_t *held = nullptr;               // [n_inst][n_agents] the goal every agent pursued during the step (row | column << 16)
         uint8_t *live = nullptr;                // [n_inst] the instance was not done when the last step began
         int16_t *arrivals = nullptr;            // [n_inst][max_steps] arrivals per step
+        int32_t *steps = nullptr;               // [n_inst] steps made since reset: the slot of the next arrivals entry
     } lf;
     // the collision shield (mgpt_expert_set_shield): off (all NULL) by default
     bool shield = false;
@@ -1141,15 +1124,7 @@ struct mgpt_expert {
         int32_t *overrides = nullptr;           // [n_inst] agents whose planned action was not the sampler's, since reset
         int32_t *started = nullptr;             // [1] 0 at reset, 1 once a shield launch has run (a replayed graph never passes the host)
     } sh;
-    // the shield on lifelong episodes (mgpt_expert_set_shield_lifelong, shield mode only): off (all NULL) by default
-    bool shield_lifelong = false;
-    struct ShieldLifelong {                     // buffers, owned by shield_lifelong_mem
-        uint32_t *held = nullptr;               // [n_inst][n_agents] as Lifelong::held
-        uint8_t *live = nullptr;                // [n_inst] as Lifelong::live
-        int16_t *arrivals = nullptr;            // [n_inst][max_steps] arrivals per step
-        int32_t *steps = nullptr;               // [n_inst] steps made since reset: the slot of the next arrivals entry
-    } sl;
-    DeviceArena mem, search_mem, deg_mem, refine_mem, lifelong_mem, shield_mem, shield_lifelong_mem;   // occ .. len; ls; deg; rf; lf; sh; sl
+    DeviceArena mem, search_mem, deg_mem, refine_mem, lifelong_mem, shield_mem;   // occ .. len; ls; deg; rf; lf; sh
 };
 
 // launches the SWAP instantiation of a kernel: one wave64 workgroup per instance, its arrays in dynamic LDS
@@ -1193,15 +1168,68 @@ static int episode_running(const mgpt_expert *ex, bool *running)
     return MGPT_OK;
 }
 
-// what the planner does not model: lifelong goal queues (unless mgpt_expert_set_lifelong is on, and then the env must have them) and
+// a switch of modes (`who`: the setter's name) is refused while an episode that has begun is not over, i.e. some instance is not done
+static int between_episodes(const mgpt_expert *ex, const char *who)
+{
+    bool running = false;
+    const int rc = episode_running(ex, &running);
+    if (rc != MGPT_OK) return rc;
+    MGPT_REQUIRE(!running, MGPT_ERR_STATE, "%s in the middle of an episode (before mgpt_expert_reset or between episodes only)", who);
+    return MGPT_OK;
+}
+
+// the lifelong state on or off, for mgpt_expert_set_lifelong and mgpt_expert_set_shield_lifelong (`who`) once their own checks have passed
+static int lifelong_switch(mgpt_expert *ex, bool on, const char *who)
+{
+    DeviceArena mem;                                         // (off: stays empty, and the state is released by the move below)
+    mgpt_expert::Lifelong lf;
+    if (on) {
+        const size_t ni = (size_t)ex->n_inst;
+        const hipError_t e = mem.alloc_all({{&lf.held, ni * ex->n_agents * sizeof(uint32_t)}, {&lf.live, ni},
+                                            {&lf.arrivals, ni * ex->max_steps * sizeof(int16_t)}, {&lf.steps, ni * sizeof(int32_t)}});
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("device allocation failed in %s (%d instances x %d agents): %s", who, ex->n_inst, ex->n_agents, hipGetErrorString(e));
+            return MGPT_ERR_HIP;
+        }
+    }
+    ex->lf = lf;
+    ex->lifelong_mem = std::move(mem);
+    ex->lifelong = on;
+    ex->have_reset = false;                                  // on: held / live / arrivals / steps are prepared by the next reset; off: what
+    return MGPT_OK;                                          // the last reset prepared was a lifelong episode's state
+}
+
+// the launch behind the env step of a lifelong episode, under the hook of the mode that asks for it
+static int lifelong_post(mgpt_expert *ex, ProfId hook, hipStream_t s)
+{
+    ProfScope ps(hook, s);
+    hipLaunchKernelGGL(pibt_lifelong_post_kernel, dim3(ex->n_inst), dim3(64), 0, s, reinterpret_cast<const uint32_t *>(ex->pos),
+                       reinterpret_cast<const uint32_t *>(ex->goal), ex->done, ex->since, ex->lf.held, ex->lf.live, ex->lf.arrivals, ex->lf.steps,
+                       ex->n_inst, ex->n_agents, ex->max_steps);
+    MGPT_LAUNCH_CHECK();
+    return MGPT_OK;
+}
+
+// copies word `words[j]` of every instance's state block ([n_inst][stride] on the device) to outs[j], [n_inst]; a NULL out is skipped
+static int copy_state_words(const mgpt_expert *ex, const int32_t *state, int stride, int n, int32_t *const *outs, const int *words, hipStream_t s)
+{
+    for (int j = 0; j < n; j++)
+        if (outs[j])
+            MGPT_HIP(hipMemcpy2DAsync(outs[j], sizeof(int32_t), state + words[j], (size_t)stride * sizeof(int32_t), sizeof(int32_t), (size_t)ex->n_inst,
+                                      hipMemcpyDeviceToDevice, s));
+    return MGPT_OK;
+}
+
+// what the planner does not model: lifelong goal queues (unless the context's lifelong mode is on, and then the env must have them) and
 // the non-default collision rules
 static int expert_check_env(const mgpt_expert *ex)
 {
     int H = 0, W = 0, n_grids = 0, rules = 0, lifelong = 0;
     env_config(ex->env, &H, &W, &n_grids, &rules, &lifelong);
-    if (ex->lifelong)
+    if (ex->lifelong && !ex->shield)
         MGPT_REQUIRE(lifelong, MGPT_ERR_STATE, "lifelong planning is on (mgpt_expert_set_lifelong): mgpt_env_set_lifelong must come first, the env has no goal queues");
-    else if (ex->shield_lifelong)
+    else if (ex->lifelong)
         MGPT_REQUIRE(lifelong, MGPT_ERR_STATE, "the lifelong shield is on (mgpt_expert_set_shield_lifelong): mgpt_env_set_lifelong must come first, the env has no goal queues");
     else
         MGPT_REQUIRE(!lifelong, MGPT_ERR_UNSUPPORTED, "the PIBT expert does not plan lifelong (on_target = restart) episodes");
@@ -1232,11 +1260,9 @@ extern "C" int mgpt_expert_create(mgpt_expert **out, mgpt_tokenizer *tok, mgpt_e
     if (rc == MGPT_OK) rc = mgpt_env_state(env, &ex->pos, &ex->goal, &ex->done);
     if (rc != MGPT_OK) { delete ex; return rc; }
     const size_t total = (size_t)n_inst * n_agents;
-    hipError_t e = ex->mem.alloc(&ex->occ, (size_t)n_inst * 2 * H * W * sizeof(uint16_t));
-    if (e == hipSuccess) e = ex->mem.alloc(&ex->since, total * sizeof(uint32_t));
-    if (e == hipSuccess) e = ex->mem.alloc(&ex->planned, total * 2 * sizeof(int16_t));
-    if (e == hipSuccess) e = ex->mem.alloc(&ex->log, total * (size_t)max_steps);
-    if (e == hipSuccess) e = ex->mem.alloc(&ex->len, (size_t)n_inst * sizeof(int32_t));
+    const hipError_t e = ex->mem.alloc_all({{&ex->occ, (size_t)n_inst * 2 * H * W * sizeof(uint16_t)}, {&ex->since, total * sizeof(uint32_t)},
+                                            {&ex->planned, total * 2 * sizeof(int16_t)}, {&ex->log, total * (size_t)max_steps},
+                                            {&ex->len, (size_t)n_inst * sizeof(int32_t)}});
     if (e != hipSuccess) {
         set_error("device allocation failed in mgpt_expert_create: %s", hipGetErrorString(e));
         delete ex;
@@ -1273,16 +1299,11 @@ extern "C" int mgpt_expert_reset(mgpt_expert *ex, void *stream)
         MGPT_HIP(hipMemsetAsync(ex->sh.overrides, 0, (size_t)ex->n_inst * sizeof(int32_t), s));
         MGPT_HIP(hipMemsetAsync(ex->sh.started, 0, sizeof(int32_t), s));
     }
-    if (ex->lifelong) {                                      // held = the goals at reset; every instance is live; no arrivals yet
+    if (ex->lifelong) {                                      // held = the goals at reset; every instance is live; no arrivals and no step yet
         MGPT_HIP(hipMemcpyAsync(ex->lf.held, ex->goal, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
         MGPT_HIP(hipMemsetAsync(ex->lf.live, 1, (size_t)ex->n_inst, s));
         MGPT_HIP(hipMemsetAsync(ex->lf.arrivals, 0, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t), s));
-    }
-    if (ex->shield_lifelong) {                               // the same, and no step made yet
-        MGPT_HIP(hipMemcpyAsync(ex->sl.held, ex->goal, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        MGPT_HIP(hipMemsetAsync(ex->sl.live, 1, (size_t)ex->n_inst, s));
-        MGPT_HIP(hipMemsetAsync(ex->sl.arrivals, 0, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t), s));
-        MGPT_HIP(hipMemsetAsync(ex->sl.steps, 0, (size_t)ex->n_inst * sizeof(int32_t), s));
+        MGPT_HIP(hipMemsetAsync(ex->lf.steps, 0, (size_t)ex->n_inst * sizeof(int32_t), s));
     }
     ex->t = 0;
     ex->have_reset = true;
@@ -1296,7 +1317,7 @@ extern "C" int mgpt_expert_set_search(mgpt_expert *ex, int max_iters, int iters_
     MGPT_REQUIRE(max_iters >= 1 && max_iters <= (1 << 24), MGPT_ERR_ARG, "max_iters=%d: 1 .. 2^24", max_iters);
     MGPT_REQUIRE(iters_per_launch >= 0, MGPT_ERR_ARG, "iters_per_launch=%d: 0 (the default) or a positive count", iters_per_launch);
     MGPT_REQUIRE(hash_bits >= 0 && hash_bits <= 63, MGPT_ERR_ARG, "hash_bits=%d: 0 (the table's own size) .. 63", hash_bits);
-    MGPT_REQUIRE(!ex->lifelong, MGPT_ERR_UNSUPPORTED,
+    MGPT_REQUIRE(!ex->lifelong || ex->shield, MGPT_ERR_UNSUPPORTED,     // (a shield's lifelong mode: the shield's own refusal below)
                  "mgpt_expert_set_search with lifelong planning on (mgpt_expert_set_lifelong): the search looks for a joint goal configuration, "
                  "which a lifelong episode does not have");
     MGPT_REQUIRE(!ex->shield, MGPT_ERR_UNSUPPORTED, "mgpt_expert_set_search in shield mode (mgpt_expert_set_shield): the shield plans single steps only");
@@ -1311,16 +1332,11 @@ extern "C" int mgpt_expert_set_search(mgpt_expert *ex, int max_iters, int iters_
     ex->ls.table_size = 2;
     while (ex->ls.table_size < 2 * ex->ls.node_cap) ex->ls.table_size *= 2;      // load factor <= 1/2: a probe always ends on an empty slot
     const size_t ni = (size_t)ex->n_inst, na = (size_t)ex->n_agents, nc = (size_t)ex->ls.node_cap;
-    hipError_t e = ex->search_mem.alloc(&ex->ls.state, ni * S_WORDS * sizeof(int32_t));
-    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.node_q, ni * nc * na * sizeof(int32_t));
-    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.node_since, ni * nc * na * sizeof(uint32_t));
-    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.node_meta, ni * nc * sizeof(int4));
-    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.open, ni * nc * sizeof(int32_t));
-    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.cons, ni * (size_t)ex->ls.cons_cap * sizeof(int4));
-    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.table, ni * (size_t)ex->ls.table_size * sizeof(int32_t));
-    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.sol, ni * na * (size_t)ex->max_steps);
-    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.skip, ni);
-    if (e == hipSuccess) e = ex->search_mem.alloc(&ex->ls.unfinished, sizeof(int32_t));
+    const hipError_t e = ex->search_mem.alloc_all(
+        {{&ex->ls.state, ni * S_WORDS * sizeof(int32_t)}, {&ex->ls.node_q, ni * nc * na * sizeof(int32_t)},
+         {&ex->ls.node_since, ni * nc * na * sizeof(uint32_t)}, {&ex->ls.node_meta, ni * nc * sizeof(int4)}, {&ex->ls.open, ni * nc * sizeof(int32_t)},
+         {&ex->ls.cons, ni * (size_t)ex->ls.cons_cap * sizeof(int4)}, {&ex->ls.table, ni * (size_t)ex->ls.table_size * sizeof(int32_t)},
+         {&ex->ls.sol, ni * na * (size_t)ex->max_steps}, {&ex->ls.skip, ni}, {&ex->ls.unfinished, sizeof(int32_t)}});
     if (e != hipSuccess) {
         (void)hipGetLastError();
         set_error("device allocation failed in mgpt_expert_set_search (max_iters=%d, %d instances x %d agents): %s", max_iters, ex->n_inst, ex->n_agents,
@@ -1336,10 +1352,8 @@ extern "C" int mgpt_expert_set_swap(mgpt_expert *ex, int on)
 {
     MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(on == 0 || on == 1, MGPT_ERR_ARG, "on=%d: 0 or 1", on);
-    bool running = false;                                    // an episode that has begun is over when every instance is done
-    const int rc = episode_running(ex, &running);
+    const int rc = between_episodes(ex, "mgpt_expert_set_swap");
     if (rc != MGPT_OK) return rc;
-    MGPT_REQUIRE(!running, MGPT_ERR_STATE, "mgpt_expert_set_swap in the middle of an episode (before mgpt_expert_reset or between episodes only)");
     if (on) {
         MGPT_REQUIRE(!ex->shield, MGPT_ERR_UNSUPPORTED, "mgpt_expert_set_swap in shield mode (mgpt_expert_set_shield): the shield keeps the policy's candidate order");
         MGPT_REQUIRE(lds_bytes(ex->n_agents, true, false) <= 64 * 1024 && (!ex->search || lds_bytes(ex->n_agents, true, true) <= 64 * 1024),
@@ -1368,46 +1382,24 @@ extern "C" int mgpt_expert_set_lifelong(mgpt_expert *ex, int on)
 {
     MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(on == 0 || on == 1, MGPT_ERR_ARG, "on=%d: 0 or 1", on);
-    bool running = false;
-    const int rc = episode_running(ex, &running);
+    const int rc = between_episodes(ex, "mgpt_expert_set_lifelong");
     if (rc != MGPT_OK) return rc;
-    MGPT_REQUIRE(!running, MGPT_ERR_STATE, "mgpt_expert_set_lifelong in the middle of an episode (before mgpt_expert_reset or between episodes only)");
-    if (on == (ex->lifelong ? 1 : 0)) return MGPT_OK;
-    if (!on) {
-        ex->lifelong_mem.release();
-        ex->lf = mgpt_expert::Lifelong();
-        ex->lifelong = false;
-        ex->have_reset = false;                              // what the last reset prepared was a lifelong episode's state
-        return MGPT_OK;
+    // the planner's switch: a shield's lifelong mode is not this function's to read or change, to it a shield-mode context is always off
+    if (on == (ex->lifelong && !ex->shield ? 1 : 0)) return MGPT_OK;
+    if (on) {
+        MGPT_REQUIRE(!ex->shield, MGPT_ERR_UNSUPPORTED, "mgpt_expert_set_lifelong in shield mode (mgpt_expert_set_shield): the shield does not plan lifelong episodes");
+        MGPT_REQUIRE(!ex->search, MGPT_ERR_UNSUPPORTED,
+                     "mgpt_expert_set_lifelong with the search on (mgpt_expert_set_search, and mgpt_expert_set_refine with it): they look for a joint "
+                     "goal configuration, which a lifelong episode does not have");
     }
-    MGPT_REQUIRE(!ex->shield, MGPT_ERR_UNSUPPORTED, "mgpt_expert_set_lifelong in shield mode (mgpt_expert_set_shield): the shield does not plan lifelong episodes");
-    MGPT_REQUIRE(!ex->search, MGPT_ERR_UNSUPPORTED,
-                 "mgpt_expert_set_lifelong with the search on (mgpt_expert_set_search, and mgpt_expert_set_refine with it): they look for a joint "
-                 "goal configuration, which a lifelong episode does not have");
-    DeviceArena mem;
-    mgpt_expert::Lifelong lf;
-    hipError_t e = mem.alloc(&lf.held, (size_t)ex->n_inst * ex->n_agents * sizeof(uint32_t));
-    if (e == hipSuccess) e = mem.alloc(&lf.live, (size_t)ex->n_inst);
-    if (e == hipSuccess) e = mem.alloc(&lf.arrivals, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("device allocation failed in mgpt_expert_set_lifelong (%d instances x %d agents): %s", ex->n_inst, ex->n_agents, hipGetErrorString(e));
-        return MGPT_ERR_HIP;
-    }
-    ex->lf = lf;
-    ex->lifelong_mem = std::move(mem);
-    ex->lifelong = true;
-    ex->have_reset = false;                                  // held / live / arrivals are prepared by the next reset
-    return MGPT_OK;
+    return lifelong_switch(ex, on != 0, "mgpt_expert_set_lifelong");
 }
 
 extern "C" int mgpt_expert_copy_arrivals(mgpt_expert *ex, int16_t *d_arrivals_out, void *stream)
 {
     MGPT_REQUIRE(ex && d_arrivals_out, MGPT_ERR_ARG, "NULL argument");
-    MGPT_REQUIRE((ex->lifelong || ex->shield_lifelong) && ex->have_reset, MGPT_ERR_STATE,
-                 "mgpt_expert_set_lifelong and mgpt_expert_reset must precede mgpt_expert_copy_arrivals");
-    const int16_t *arrivals = ex->lifelong ? ex->lf.arrivals : ex->sl.arrivals;         // (a shield-mode context: section 35's log)
-    MGPT_HIP(hipMemcpyAsync(d_arrivals_out, arrivals, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t), hipMemcpyDeviceToDevice,
+    MGPT_REQUIRE(ex->lifelong && ex->have_reset, MGPT_ERR_STATE, "mgpt_expert_set_lifelong and mgpt_expert_reset must precede mgpt_expert_copy_arrivals");
+    MGPT_HIP(hipMemcpyAsync(d_arrivals_out, ex->lf.arrivals, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t), hipMemcpyDeviceToDevice,
                             (hipStream_t)stream));
     return MGPT_OK;
 }
@@ -1496,10 +1488,8 @@ extern "C" int mgpt_expert_set_refine(mgpt_expert *ex, int max_rounds, int horiz
     MGPT_REQUIRE(horizon == 0 || (horizon >= ex->max_steps && horizon <= (1 << 20)), MGPT_ERR_ARG,
                  "horizon=%d: 0 (twice max_steps) or max_steps=%d .. 2^20", horizon, ex->max_steps);
     MGPT_REQUIRE(ex->search, MGPT_ERR_STATE, "mgpt_expert_set_search must precede mgpt_expert_set_refine (the pass refines what the search found)");
-    bool running = false;
-    const int rc = episode_running(ex, &running);
+    const int rc = between_episodes(ex, "mgpt_expert_set_refine");
     if (rc != MGPT_OK) return rc;
-    MGPT_REQUIRE(!running, MGPT_ERR_STATE, "mgpt_expert_set_refine in the middle of an episode (before mgpt_expert_reset or between episodes only)");
     if (max_rounds == 0) {
         refine_free(ex);
         return MGPT_OK;
@@ -1514,10 +1504,8 @@ extern "C" int mgpt_expert_set_refine(mgpt_expert *ex, int max_rounds, int horiz
         MGPT_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(refine_round_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRefineMaxLds));
     refine_free(ex);
     const size_t ni = (size_t)ex->n_inst, na = (size_t)ex->n_agents;
-    hipError_t e = ex->refine_mem.alloc(&ex->rf.path, ni * (size_t)(hz + 1) * na * sizeof(int32_t));
-    if (e == hipSuccess) e = ex->refine_mem.alloc(&ex->rf.arr, ni * na * sizeof(int32_t));
-    if (e == hipSuccess) e = ex->refine_mem.alloc(&ex->rf.rstate, ni * R_WORDS * sizeof(int32_t));
-    if (e == hipSuccess) e = ex->refine_mem.alloc(&ex->rf.adopted, sizeof(int32_t));
+    const hipError_t e = ex->refine_mem.alloc_all({{&ex->rf.path, ni * (size_t)(hz + 1) * na * sizeof(int32_t)}, {&ex->rf.arr, ni * na * sizeof(int32_t)},
+                                                   {&ex->rf.rstate, ni * R_WORDS * sizeof(int32_t)}, {&ex->rf.adopted, sizeof(int32_t)}});
     if (e != hipSuccess) {
         (void)hipGetLastError();
         set_error("device allocation failed in mgpt_expert_set_refine (horizon=%d, %d instances x %d agents): %s", hz, ex->n_inst, ex->n_agents,
@@ -1537,28 +1525,18 @@ extern "C" int mgpt_expert_copy_refine(mgpt_expert *ex, int32_t *d_first_status,
     MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(ex->search && ex->solved && ex->rf.max_rounds > 0, MGPT_ERR_STATE,
                  "mgpt_expert_set_refine (max_rounds > 0) and mgpt_expert_solve must precede mgpt_expert_copy_refine");
-    hipStream_t s = (hipStream_t)stream;
     int32_t *outs[6] = {d_first_status, d_first_length, d_soc_before, d_soc_after, d_rounds, d_replans};
     const int words[6] = {R_FIRST_STATUS, R_FIRST_LENGTH, R_SOC_BEFORE, R_SOC_AFTER, R_ROUNDS, R_REPLANS};
-    for (int j = 0; j < 6; j++)
-        if (outs[j])
-            MGPT_HIP(hipMemcpy2DAsync(outs[j], sizeof(int32_t), ex->rf.rstate + words[j], R_WORDS * sizeof(int32_t), sizeof(int32_t), (size_t)ex->n_inst,
-                                      hipMemcpyDeviceToDevice, s));
-    return MGPT_OK;
+    return copy_state_words(ex, ex->rf.rstate, R_WORDS, 6, outs, words, (hipStream_t)stream);
 }
 
 extern "C" int mgpt_expert_copy_search(mgpt_expert *ex, int32_t *d_status, int32_t *d_iters, int32_t *d_nodes, int32_t *d_length, void *stream)
 {
     MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(ex->search && ex->solved, MGPT_ERR_STATE, "mgpt_expert_solve must precede mgpt_expert_copy_search");
-    hipStream_t s = (hipStream_t)stream;
     int32_t *outs[4] = {d_status, d_iters, d_nodes, d_length};
     const int words[4] = {S_STATUS, S_ITERS, S_NODES, S_LENGTH};
-    for (int j = 0; j < 4; j++)
-        if (outs[j])
-            MGPT_HIP(hipMemcpy2DAsync(outs[j], sizeof(int32_t), ex->ls.state + words[j], S_WORDS * sizeof(int32_t), sizeof(int32_t), (size_t)ex->n_inst,
-                                      hipMemcpyDeviceToDevice, s));
-    return MGPT_OK;
+    return copy_state_words(ex, ex->ls.state, S_WORDS, 4, outs, words, (hipStream_t)stream);
 }
 
 extern "C" int mgpt_expert_copy_solution(mgpt_expert *ex, int8_t *d_solution_out, void *stream)
@@ -1600,11 +1578,7 @@ extern "C" int mgpt_expert_step(mgpt_expert *ex, int32_t *d_actions, void *strea
     if ((rc = mgpt_env_step(ex->env, d_actions, s)) != MGPT_OK) return rc;
     if (ex->lifelong) {                                      // the fields of the agents whose goal changed, then since and the arrivals
         if ((rc = mgpt_tokenizer_update_agents(ex->tok, ex->pos, ex->goal, d_actions, 1, s)) != MGPT_OK) return rc;
-        ProfScope ps(P_EXPERT_LIFELONG_POST, s);
-        hipLaunchKernelGGL(pibt_lifelong_post_kernel, dim3(ex->n_inst), dim3(64), 0, s, reinterpret_cast<const uint32_t *>(ex->pos),
-                           reinterpret_cast<const uint32_t *>(ex->goal), ex->done, ex->since, ex->lf.held, ex->lf.live, ex->lf.arrivals,
-                           ex->n_agents, ex->max_steps, (int64_t)ex->t);
-        MGPT_LAUNCH_CHECK();
+        if ((rc = lifelong_post(ex, P_EXPERT_LIFELONG_POST, s)) != MGPT_OK) return rc;
         ex->t++;
         return MGPT_OK;
     }
@@ -1638,15 +1612,11 @@ extern "C" int mgpt_expert_set_shield(mgpt_expert *ex, int on)
 {
     MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(on == 0 || on == 1, MGPT_ERR_ARG, "on=%d: 0 or 1", on);
-    bool running = false;
-    int rc = episode_running(ex, &running);
+    int rc = between_episodes(ex, "mgpt_expert_set_shield");
     if (rc != MGPT_OK) return rc;
-    MGPT_REQUIRE(!running, MGPT_ERR_STATE, "mgpt_expert_set_shield in the middle of an episode (before mgpt_expert_reset or between episodes only)");
     if (on == (ex->shield ? 1 : 0)) return MGPT_OK;
     if (!on) {
-        ex->shield_lifelong_mem.release();                   // (section 35's buffers go with the shield)
-        ex->sl = mgpt_expert::ShieldLifelong();
-        ex->shield_lifelong = false;
+        (void)lifelong_switch(ex, false, "mgpt_expert_set_shield");   // (section 35's state goes with the shield; off cannot fail)
         ex->shield_mem.release();
         ex->sh = mgpt_expert::Shield();
         ex->shield = false;
@@ -1661,9 +1631,8 @@ extern "C" int mgpt_expert_set_shield(mgpt_expert *ex, int on)
                  "n_agents=%d: the frames with the preference words do not fit 64 KB of LDS", ex->n_agents);
     DeviceArena mem;
     mgpt_expert::Shield sh;
-    hipError_t e = mem.alloc(&sh.first, (size_t)ex->n_inst * ex->n_agents * sizeof(int32_t));
-    if (e == hipSuccess) e = mem.alloc(&sh.overrides, (size_t)ex->n_inst * sizeof(int32_t));
-    if (e == hipSuccess) e = mem.alloc(&sh.started, sizeof(int32_t));
+    const hipError_t e = mem.alloc_all({{&sh.first, (size_t)ex->n_inst * ex->n_agents * sizeof(int32_t)},
+                                        {&sh.overrides, (size_t)ex->n_inst * sizeof(int32_t)}, {&sh.started, sizeof(int32_t)}});
     if (e != hipSuccess) {
         (void)hipGetLastError();
         set_error("device allocation failed in mgpt_expert_set_shield (%d instances x %d agents): %s", ex->n_inst, ex->n_agents, hipGetErrorString(e));
@@ -1699,15 +1668,8 @@ extern "C" int mgpt_expert_shield_commit(mgpt_expert *ex, void *stream)
 {
     MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(ex->shield && ex->have_reset, MGPT_ERR_STATE, "mgpt_expert_set_shield and mgpt_expert_reset must precede mgpt_expert_shield_commit");
-    if (ex->shield_lifelong) {                               // section 35: since against the goals held during the step, and the arrivals
-        hipStream_t s = (hipStream_t)stream;
-        ProfScope ps(P_EXPERT_SHIELD_LIFELONG_POST, s);
-        hipLaunchKernelGGL(pibt_shield_lifelong_post_kernel, dim3(ex->n_inst), dim3(64), 0, s, reinterpret_cast<const uint32_t *>(ex->pos),
-                           reinterpret_cast<const uint32_t *>(ex->goal), ex->done, ex->since, ex->sl.held, ex->sl.live, ex->sl.arrivals,
-                           ex->sl.steps, ex->n_inst, ex->n_agents, ex->max_steps);
-        MGPT_LAUNCH_CHECK();
-        return MGPT_OK;                                      // (the tokenizer is not called here: the caller rebuilds the fields once per step)
-    }
+    if (ex->lifelong)                                        // section 35: since against the goals held during the step, and the arrivals
+        return lifelong_post(ex, P_EXPERT_SHIELD_LIFELONG_POST, (hipStream_t)stream);   // (the tokenizer is not called here: the caller rebuilds the fields once per step)
     const int total = ex->n_inst * ex->n_agents;
     hipLaunchKernelGGL(pibt_since_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, ex->pos, ex->goal, ex->done, ex->since, ex->n_inst,
                        ex->n_agents);
@@ -1721,36 +1683,10 @@ extern "C" int mgpt_expert_set_shield_lifelong(mgpt_expert *ex, int on)
     MGPT_REQUIRE(ex, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(on == 0 || on == 1, MGPT_ERR_ARG, "on=%d: 0 or 1", on);
     MGPT_REQUIRE(ex->shield, MGPT_ERR_STATE, "mgpt_expert_set_shield(ex, 1) must precede mgpt_expert_set_shield_lifelong: it switches a shield-mode context");
-    bool running = false;
-    const int rc = episode_running(ex, &running);
+    const int rc = between_episodes(ex, "mgpt_expert_set_shield_lifelong");
     if (rc != MGPT_OK) return rc;
-    MGPT_REQUIRE(!running, MGPT_ERR_STATE,
-                 "mgpt_expert_set_shield_lifelong in the middle of an episode (before mgpt_expert_reset or between episodes only)");
-    if (on == (ex->shield_lifelong ? 1 : 0)) return MGPT_OK;
-    if (!on) {
-        ex->shield_lifelong_mem.release();
-        ex->sl = mgpt_expert::ShieldLifelong();
-        ex->shield_lifelong = false;
-        ex->have_reset = false;                              // what the last reset prepared was a lifelong episode's state
-        return MGPT_OK;
-    }
-    DeviceArena mem;
-    mgpt_expert::ShieldLifelong sl;
-    hipError_t e = mem.alloc(&sl.held, (size_t)ex->n_inst * ex->n_agents * sizeof(uint32_t));
-    if (e == hipSuccess) e = mem.alloc(&sl.live, (size_t)ex->n_inst);
-    if (e == hipSuccess) e = mem.alloc(&sl.arrivals, (size_t)ex->n_inst * ex->max_steps * sizeof(int16_t));
-    if (e == hipSuccess) e = mem.alloc(&sl.steps, (size_t)ex->n_inst * sizeof(int32_t));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("device allocation failed in mgpt_expert_set_shield_lifelong (%d instances x %d agents): %s", ex->n_inst, ex->n_agents,
-                  hipGetErrorString(e));
-        return MGPT_ERR_HIP;
-    }
-    ex->sl = sl;
-    ex->shield_lifelong_mem = std::move(mem);
-    ex->shield_lifelong = true;
-    ex->have_reset = false;                                  // held / live / arrivals / steps are prepared by the next reset
-    return MGPT_OK;
+    if (on == (ex->lifelong ? 1 : 0)) return MGPT_OK;        // (on a shield-mode context the one flag is this mode's)
+    return lifelong_switch(ex, on != 0, "mgpt_expert_set_shield_lifelong");
 }
 
 extern "C" int mgpt_expert_copy_shield(mgpt_expert *ex, int32_t *d_first_out, int32_t *d_overrides_out, void *stream)

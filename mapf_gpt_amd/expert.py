@@ -389,16 +389,9 @@ class BatchedExpert:
             keep = self.metrics()[:, METRIC_KEYS.index("CSR")] >= 1
         init = torch.as_tensor(init_pos).to(self.device, torch.int16).reshape(self.n_inst, self.n_agents, 2)
         log, lens = self.log()
-        grids = self.env.grids.cpu().numpy()
-        flat = grids.reshape(len(grids), -1)
-        _, first, inverse = np.unique(flat, axis=0, return_index=True, return_inverse=True)
-        of_inst = inverse.reshape(-1)[np.arange(self.n_inst) % len(grids)]                  # instance i uses grid i % n_grids
         out = []
-        for u in np.argsort(first):                                                        # distinct grids, first appearance first
-            ids = np.flatnonzero(of_inst == u).astype(np.int64)
-            if len(ids) == 0:                                                              # (a grid no instance uses: n_grids > n_inst)
-                continue
-            rows, labels, row0 = tokenize_episodes(tables.get(grids[first[u]]), init, log, lens, keep, ids, mask_cost2go)
+        for ids, grid in self._instances_by_grid():
+            rows, labels, row0 = tokenize_episodes(tables.get(grid), init, log, lens, keep, ids, mask_cost2go)
             out.append((ids, rows, labels, row0) if offsets else (ids, rows, labels))
         return out
 

@@ -131,6 +131,50 @@ int main()
         TestMem::arm(0);
     }
     CHECK(all_free());
+    {   // alloc_all: every request served, in order, and owned by the arena; nothing is live after release()
+        A a;
+        float *x = nullptr;
+        int *y = nullptr;
+        char *z = nullptr;
+        CHECK(a.alloc_all({{&x, 64}, {&y, 12}, {&z, 3}}) == TestMem::ok && x && y && z);
+        x[15] = 1.f; y[2] = 1; z[2] = 1;
+        CHECK(a.count() == 3 && live_allocs() == 3 && live_bytes() == 79 && TestMem::live == 3 && TestMem::live_host == 0);
+        a.release();
+        CHECK(a.empty() && all_free());
+    }
+    // alloc_all with a failure at request k, for every k: the first error comes back, the pointers from k on are nullptr, the earlier
+    // allocations are the arena's and go with it
+    for (int k = 1; k <= 3; k++) {
+        A a;
+        void *const stale = reinterpret_cast<void *>(0x10);
+        float *x = static_cast<float *>(stale);
+        int *y = static_cast<int *>(stale);
+        char *z = static_cast<char *>(stale);
+        TestMem::arm(k);
+        CHECK(a.alloc_all({{&x, 64}, {&y, 12}, {&z, 3}}) == 2);
+        CHECK(TestMem::calls == k);                                 // it stopped at the failure
+        TestMem::arm(0);
+        CHECK((x != nullptr) == (k > 1) && (y != nullptr) == (k > 2) && z == nullptr);
+        CHECK(x != stale && y != stale);
+        CHECK(a.count() == (size_t)(k - 1) && live_allocs() == k - 1 && TestMem::live == k - 1);
+        CHECK(live_bytes() == (k == 1 ? 0 : k == 2 ? 64 : 76));
+        if (k > 1) x[15] = 1.f;
+        if (k > 2) y[2] = 1;
+        a.release();
+        CHECK(a.empty() && all_free());
+    }
+    {   // a zero-byte request is no failure and stops nothing: the requests around it are served, the counters return to 0 / 0
+        A a;
+        float *x = nullptr;
+        int *none = reinterpret_cast<int *>(0x10);
+        char *z = nullptr;
+        CHECK(a.alloc_all({{&x, 8}, {&none, 0}, {&z, 5}}) == TestMem::ok && x && z);
+        CHECK(live_bytes() == 13 && a.count() == (none ? 3u : 2u));
+        CHECK(a.alloc_all({}) == TestMem::ok);                      // (an empty list too)
+        a.release();
+        CHECK(a.empty() && all_free());
+    }
+    CHECK(all_free());
     if (g_failures == 0) printf("arena_check: ok (%lld allocations, %lld bytes live)\n", (long long)live_allocs(), (long long)live_bytes());
     return g_failures == 0 ? 0 : 1;
 }

@@ -128,6 +128,27 @@ def test_a_second_episode_with_another_queue_and_then_one_shot_planning_again():
     assert np.array_equal(ex.metrics().cpu().numpy()[:, :5], want.metrics()[:, :5].astype(np.float32))
 
 
+def test_steps_beyond_the_cap_write_nothing():
+    """The planner-mode twin of the lifelong shield's test of the same name: max_steps + 2 steps; after step max_steps every instance is
+    done, `live` keeps the post-step kernel's device step counter at max_steps and the two further steps change none of the arrivals
+    log, the action log and the lengths (nor the env's positions and counts)."""
+    case = lr.random_case(12, 12, 0.2, 2, 3, 6, seed=21, Q=4)
+    ex = make_expert(case)
+    ref = lr.new_ref(case)
+    assert_steps_equal(ex, ref, case["steps"])
+    assert_final_state(ex, ref)
+
+    def state():
+        log, lens = ex.log()
+        return [x.cpu().numpy().copy() for x in (ex.arrivals(), log, lens, ex.env.sync_state()[0], ex.env.goals_reached())]
+
+    at_cap = state()
+    assert (at_cap[2] == case["steps"]).all() and at_cap[0].sum() > 0
+    for extra in range(2):
+        ex.step()
+        assert all(np.array_equal(x, y) for x, y in zip(state(), at_cap)), f"step max_steps + {extra + 1} changed the state"
+
+
 def test_refusals_and_their_messages():
     import torch
     from mapf_gpt_amd import _lib

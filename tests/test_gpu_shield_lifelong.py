@@ -110,6 +110,67 @@ def test_a_second_episode_then_the_plain_shield_again():
         assert np.array_equal(pos, plain.pos) and np.array_equal(done, plain.done) and np.array_equal(over, plain.overrides), t
 
 
+def test_one_context_walked_through_the_modes_equals_a_fresh_context_in_each():
+    """The planner's and the shield's lifelong modes share one state (held / live / arrivals / steps).  One context goes planner
+    lifelong -> one-shot planner -> shield -> lifelong shield -> shield -> one-shot planner -> planner lifelong, with a reset and a whole
+    6-step episode after every switch (every instance is then done by truncation, so the next switch is allowed); after every episode
+    its log, lengths, planned cells, env positions and, where the mode has them, arrivals and overrides are those of a context created
+    directly in that mode and given the same inputs."""
+    import torch
+    from mapf_gpt_amd import _lib
+    from mapf_gpt_amd.expert import BatchedExpert
+    case = lr.random_case(12, 12, 0.2, 2, 3, 6, seed=21, Q=4)
+    pos, goal, queue = (torch.from_numpy(case[k]) for k in ("pos", "goal", "queue"))
+    mk = lambda **kw: BatchedExpert(case["grids"], 2, 3, 6, seed=case["seed"], inst_offset=case["inst_offset"], **kw)
+    modes = {"lifelong": dict(lifelong=True), "plain": {}, "shield": dict(shield=True), "shield_lifelong": dict(shield=True, shield_lifelong=True)}
+
+    def shield_inputs(mode):                                              # the logits of the episode, from the mode's restatement
+        if mode == "shield_lifelong":
+            ref = slr.new_ref(case)
+        else:
+            ref = sr.RefShield(case["grids"], 2, 3, 6)
+            ref.reset(case["pos"], case["goal"])
+        rng, out = np.random.default_rng(slr.SEED), []
+        for t in range(6):
+            out.append(slr.step_inputs(ref, rng, t))
+            ref.step(*out[-1])
+        return out
+
+    inputs = {mode: shield_inputs(mode) for mode in ("shield", "shield_lifelong")}
+
+    def episode(ex, mode):
+        ex.reset(pos, goal, queue if "lifelong" in mode else None)
+        if "shield" in mode:
+            for bits, first in inputs[mode]:
+                device_step(ex, bits, first)
+        else:
+            ex.run(6)
+        log, lens = ex.log()
+        out = {"log": log, "lens": lens, "planned": ex.planned(), "pos": ex.env.sync_state()[0], "done": ex.env.sync_state()[2]}
+        if "lifelong" in mode:
+            out["arrivals"] = ex.arrivals()
+        else:
+            with pytest.raises(_lib.MGPTError):                           # no arrivals log in a one-shot mode, whatever came before
+                ex.arrivals()
+        if "shield" in mode:
+            out["overrides"] = ex.shield_overrides()
+        return {k: v.cpu().numpy().copy() for k, v in out.items()}
+
+    fresh = {mode: episode(mk(**kw), mode) for mode, kw in modes.items()}
+    assert fresh["lifelong"]["arrivals"].sum() > 0 and fresh["shield_lifelong"]["arrivals"].sum() > 0 and fresh["shield_lifelong"]["overrides"].sum() > 0
+    ex = mk()
+    walk = [("lifelong", lambda: ex.set_lifelong(True)), ("plain", lambda: ex.set_lifelong(False)), ("shield", lambda: ex.set_shield(True)),
+            ("shield_lifelong", lambda: ex.set_shield_lifelong(True)), ("shield", lambda: ex.set_shield_lifelong(False)),
+            ("plain", lambda: ex.set_shield(False)), ("lifelong", lambda: ex.set_lifelong(True))]
+    for leg, (mode, switch) in enumerate(walk):
+        switch()
+        got = episode(ex, mode)
+        assert (got["done"] != 0).all(), (leg, mode)
+        assert got.keys() == fresh[mode].keys()
+        for k, want in fresh[mode].items():
+            assert np.array_equal(got[k], want), f"{k} differs from a fresh {mode} context's on leg {leg} of the walk"
+
+
 # ---- through the policy ---------------------------------------------------------------------------------------------------------------
 N_INST, N_AGENTS, POLICY_STEPS, Q = 2, 8, 16, 4
 _cache = {}

@@ -246,6 +246,7 @@ def time_shape(name, repeats, out):
           "ms_per_step": round(s / steps, 4), "ms_run": round(s, 3), "ms_runs": [round(x, 3) for x in run_ms], "ms_reset": round(r, 3),
           "episodes_per_s": round(n_inst / ((r + s) * 1e-3), 1), "plan_ms_per_step": round(plan / steps, 4),
           "env_ms_per_step": round(env / steps, 4), "plan_share_of_plan_plus_env": round(plan / max(plan + env, 1e-9), 3),
+          "kernel_ms_per_step": {"plan": round(plan / steps, 4), "env": round(env / steps, 4)},      # (the keys tools/ab.py records)
           "bfs_ms_of_reset": round(bfs, 3), "solved": int(m[:, 0].sum()), "mean_isr": round(float(m[:, 1].mean()), 4), **extra}, out)
 
 
