@@ -339,9 +339,20 @@ int mgpt_gpt_act_dev(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, int32_t *
  *           WAIT: the normaliser is `rows`, a host-side number, and the call holds no stream synchronise, no blocking copy and no host read
  *           of device memory.  Labels must lie in [0, 67): the cross-entropy kernel compares a label with that range before it indexes
  *           anything with it, and an out-of-range label makes the row's loss term and logit gradients NaN -- *d_loss and the next gradient
- *           norm are NaN, loudly; callers validate on the host where they hold the labels.  No dropout (the general call serves it).
+ *           norm are NaN, loudly; callers validate on the host where they hold the labels.  No dropout: it is forward_backward_rows_drop
+ *           with p = 0 and launches what it launched before that call existed.
  *           Deterministic.  A NULL pointer, rows < 1 or a non-finite loss_scale: MGPT_ERR_ARG; no training workspace: MGPT_ERR_STATE; a
  *           precision other than MGPT_PREC_F32 / MGPT_PREC_BF16: MGPT_ERR_UNSUPPORTED.
+ *   forward_backward_rows_drop: forward_backward_rows in training mode with dropout = forward_backward_drop(d_tokens, rows, 256, targets, ...,
+ *           p, seed, step, row0, sites) with targets[r][255] = d_labels[r] and -1 elsewhere: the same masks keep(seed, step, site, layer,
+ *           element).  The embedding and the layers below the last draw them through the general call's launches; the compact last layer
+ *           draws the general call's masks at token / query 255 -- site 1 element ((row0 + row) n_head + head) 65536 + 255 * 256 + key
+ *           (attn_last_fwd_kernel / attn_last_bwd_kernel<.., true>), sites 2 and 3 element ((row0 + row) 256 + 255) C + c (the mask's rows
+ *           lie 256 C apart, the compact matrix's C).  p, seed, step, row0 and sites as forward_backward_drop takes them, with its refusals
+ *           (p outside [0, 1) or sites outside [0, 15]: MGPT_ERR_ARG; n_embd % 4 != 0 with dropout on: MGPT_ERR_UNSUPPORTED); p = 0 or
+ *           sites = 0 launches exactly forward_backward_rows.  Everything else is forward_backward_rows' contract: no host wait, the
+ *           normaliser `rows`, NaN for an out-of-range label, no floating-point atomics (two identical calls give identical bits), the
+ *           same workspace.
  *   zero_grad: grads = 0.
  *   clip_grad_norm: torch.nn.utils.clip_grad_norm_: total = || (||g_p||)_p ||, coef = min(max_norm / (total + 1e-6), 1), g *= coef; the
  *           coefficient stays on the device, *d_total_norm (device, may be NULL) = total.  max_norm <= 0: the norm only.
@@ -382,6 +393,8 @@ int mgpt_gpt_forward_backward_prec(mgpt_gpt *gpt, const uint8_t *d_tokens, int r
                                    float *d_loss, int precision, void *stream);
 int mgpt_gpt_forward_backward_rows(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, const int32_t *d_labels, float loss_scale, float *d_loss,
                                    int precision, void *stream);
+int mgpt_gpt_forward_backward_rows_drop(mgpt_gpt *gpt, const uint8_t *d_tokens, int rows, const int32_t *d_labels, float loss_scale, float *d_loss,
+                                        int precision, float p, uint64_t seed, uint64_t step, uint64_t row0, int sites, void *stream);
 int mgpt_gpt_zero_grad(mgpt_gpt *gpt, void *stream);
 int mgpt_gpt_clip_grad_norm(mgpt_gpt *gpt, float max_norm, float *d_total_norm, void *stream);
 int mgpt_gpt_adamw_step(mgpt_gpt *gpt, float lr, float beta1, float beta2, float eps, float weight_decay, void *stream);

@@ -119,6 +119,8 @@ SYMBOLS = {
     "mgpt_gpt_forward_backward_rows": (_i, [_vp, _vp, _i, _vp, ctypes.c_float, _vp, _i, _vp]),
     "mgpt_gpt_forward_backward_drop": (_i, [_vp, _vp, _i, _i, _vp, ctypes.c_float, _vp, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64,
                                             ctypes.c_uint64, _i, _vp]),
+    "mgpt_gpt_forward_backward_rows_drop": (_i, [_vp, _vp, _i, _vp, ctypes.c_float, _vp, _i, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64,
+                                                 ctypes.c_uint64, _i, _vp]),
     "mgpt_gpt_zero_grad": (_i, [_vp, _vp]),
     "mgpt_gpt_clip_grad_norm": (_i, [_vp, ctypes.c_float, _vp, _vp]),
     "mgpt_gpt_adamw_step": (_i, [_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp]),

@@ -564,6 +564,42 @@ __global__ __launch_bounds__(256) void scatter_last_add_kernel(const float *__re
     }
 }
 
+// The two residual joins of the compact matrix under dropout (sites 2 and 3): compact row r is token 255 of row r, so its mask elements are
+// ((row0 + r) * 256 + 255) * C + c -- the mask's row pitch is 256 C while the data's is C.  d.base = the element of compact row 0, column 0;
+// a quad index is the hash's counter (C a multiple of 4).
+__device__ __forceinline__ uint64_t drop_last_hash(const Drop &d, int64_t i, int C4)
+{
+    const int64_t r = i / C4;
+    return drop_hash(d.key, (d.base >> 2) + (uint64_t)r * (uint64_t)(kT * C4) + (uint64_t)(i - r * C4));
+}
+
+// out[r][c] = x[r][c] + m s o[r][c] over n_rows compact rows (fp32 path)
+__global__ __launch_bounds__(256) void drop_resid_last_kernel(const float *__restrict__ x, const float *__restrict__ o, float *__restrict__ out,
+                                                              int n_rows, int C, Drop d)
+{
+    const int C4 = C / 4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (int64_t)n_rows * C4; i += (int64_t)gridDim.x * 256) {
+        const uint64_t h = drop_last_hash(d, i, C4);
+        const float4 r = reinterpret_cast<const float4 *>(x)[i], v = reinterpret_cast<const float4 *>(o)[i];
+        reinterpret_cast<float4 *>(out)[i] = make_float4(r.x + v.x * drop_factor(h, 0, d), r.y + v.y * drop_factor(h, 1, d),
+                                                         r.z + v.z * drop_factor(h, 2, d), r.w + v.w * drop_factor(h, 3, d));
+    }
+}
+
+// out[r][c] = m s v(in[r][c]): the gradient that enters a compact residual branch's c_proj;  v rounds to bf16 first when ROUND
+template <bool ROUND>
+__global__ __launch_bounds__(256) void drop_scale_last_kernel(const float *__restrict__ in, float *__restrict__ out, int n_rows, int C, Drop d)
+{
+    const int C4 = C / 4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (int64_t)n_rows * C4; i += (int64_t)gridDim.x * 256) {
+        const uint64_t h = drop_last_hash(d, i, C4);
+        float4 v = reinterpret_cast<const float4 *>(in)[i];
+        if (ROUND) { v.x = (float)(__bf16)v.x; v.y = (float)(__bf16)v.y; v.z = (float)(__bf16)v.z; v.w = (float)(__bf16)v.w; }    // (nearest-even)
+        reinterpret_cast<float4 *>(out)[i] =
+            make_float4(v.x * drop_factor(h, 0, d), v.y * drop_factor(h, 1, d), v.z * drop_factor(h, 2, d), v.w * drop_factor(h, 3, d));
+    }
+}
+
 // cross-entropy of the compact logits [mc][67] against one label per row; k = loss_scale / rows of the WHOLE call, a host-side number (no
 // count is read from the device).  The label is compared with [0, 67) before anything is indexed with it: an out-of-range label makes the
 // row's loss term and its dlogits NaN -- the call's loss and the next gradient norm are NaN, loudly, and no host wait is spent on it.
@@ -686,9 +722,22 @@ __device__ __forceinline__ void lastk_weighted_rows(const float *w, const TQ *__
     part[g * HS + d] = acc;
 }
 
-template <int HS, typename TQ>
+// DROP (dropout on P, site 1; mgpt_gpt_forward_backward_rows_drop): the masks of the general call at query 255 -- element
+// ((row0 + row) * n_head + head) * 65536 + 255 * 256 + key, thread j = key j, one hash per four consecutive keys (the four threads of a
+// quad compute the same one).  As attn_fwd_drop_kernel / attn_fwd_bf16_kernel<HS, true>: l sums over all keys, the mask zeroes exp(..)
+// after it joined the sum (bf16: the masked value is rounded for the PV product), and y = s / l * sum_j m_j p_j v_j with s / l in fp32.
+// Backward: dp_j = m_j s (dy . v_j), D = dy . y (it holds for the dropped y), ds_j = p_j (dp_j - D), dV_j = m_j s p_j dy (bf16: mask and
+// scale in fp32 before P is rounded as the dV operand).
+template <bool DROP>
+__device__ __forceinline__ uint64_t lastk_hash(const Drop &dr, int bh, int j)
+{
+    if constexpr (DROP) return drop_hash_at(drop_base(dr.key, (dr.base >> 2) + (uint64_t)bh * (kT * kT / 4)), (uint32_t)((kT - 1) * kT + j) >> 2);
+    else return 0;
+}
+
+template <int HS, typename TQ, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_last_fwd_kernel(const TQ *__restrict__ q, const TQ *__restrict__ kplane, const TQ *__restrict__ vplane,
-                                                            TQ *__restrict__ y, float *__restrict__ stats, int n_head, float scale)
+                                                            TQ *__restrict__ y, float *__restrict__ stats, int n_head, float scale, Drop dr)
 {
     constexpr bool BF = sizeof(TQ) == 2;
     constexpr int NG = kT / HS;
@@ -704,7 +753,8 @@ __global__ __launch_bounds__(256) void attn_last_fwd_kernel(const TQ *__restrict
     const float m = lastk_max256(s, red);
     const float p = BF ? expf((s - m) * scale) : expf(s - m);
     const float l = lastk_sum256(p, red);
-    sp[j] = lastk_round(p, q);
+    if constexpr (DROP) sp[j] = drop_keep(lastk_hash<DROP>(dr, bh, j), j & 3, dr.thr) ? lastk_round(p, q) : 0.f;
+    else sp[j] = lastk_round(p, q);
     __syncthreads();
     lastk_weighted_rows<HS, TQ>(sp, V, part);
     __syncthreads();
@@ -713,15 +763,16 @@ __global__ __launch_bounds__(256) void attn_last_fwd_kernel(const TQ *__restrict
         float o = 0.f;
 #pragma unroll
         for (int g = 0; g < NG; g++) o += part[g * HS + j];
-        lastk_store(y + (int64_t)b * C + head * HS + j, o * inv_l);
+        if constexpr (DROP) lastk_store(y + (int64_t)b * C + head * HS + j, o * (dr.scale / l));
+        else lastk_store(y + (int64_t)b * C + head * HS + j, o * inv_l);
     }
     if (j == 0) { stats[(int64_t)bh * 2] = m; stats[(int64_t)bh * 2 + 1] = inv_l; }
 }
 
-template <int HS, typename TQ>
+template <int HS, typename TQ, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_last_bwd_kernel(const TQ *__restrict__ q, const TQ *__restrict__ kplane, const TQ *__restrict__ vplane,
                                                             const TQ *__restrict__ y, const TQ *__restrict__ dy, const float *__restrict__ stats,
-                                                            float *__restrict__ dqkv, float *__restrict__ dq, int n_head, float scale)
+                                                            float *__restrict__ dqkv, float *__restrict__ dq, int n_head, float scale, Drop dr)
 {
     constexpr bool BF = sizeof(TQ) == 2;
     constexpr int NG = kT / HS;
@@ -742,8 +793,16 @@ __global__ __launch_bounds__(256) void attn_last_bwd_kernel(const TQ *__restrict
     for (int d = 0; d < HS; d++) D = fmaf(sdy[d], sy[d], D);
     const float s = lastk_dot<HS>(sq, kr);
     const float p = (BF ? expf((s - m) * scale) : expf(s * scale - m)) * inv_l;
-    const float ds = p * (lastk_dot<HS>(sdy, vr) - D);
-    const float pw = lastk_round(p, q), dsw = lastk_round(ds, q);       // the operands of dV, and of dK and dq
+    float ds, pw;                                               // pw, dsw: the operands of dV, and of dK and dq
+    if constexpr (DROP) {
+        const float f = drop_factor(lastk_hash<DROP>(dr, bh, j), j & 3, dr);        // m s of (query 255, key j)
+        ds = p * (lastk_dot<HS>(sdy, vr) * f - D);
+        pw = lastk_round(p * f, q);
+    } else {
+        ds = p * (lastk_dot<HS>(sdy, vr) - D);
+        pw = lastk_round(p, q);
+    }
+    const float dsw = lastk_round(ds, q);
     sds[j] = dsw;
     float *o = dqkv + ((int64_t)b * kT + j) * 3 * C + C + head * HS;       // dK_j, and dV_j at + C
 #pragma unroll

@@ -101,7 +101,7 @@ __device__ __forceinline__ void stage(const T *__restrict__ src, int64_t ld, int
     }
 }
 
-enum { E_F32 = 0, E_PART = 1, E_RESID = 2, E_FC = 3, E_GELU_BWD = 4, E_QKV = 5, E_B16 = 6, E_RESID_DROP = 7 };
+enum { E_F32 = 0, E_PART = 1, E_RESID = 2, E_FC = 3, E_GELU_BWD = 4, E_QKV = 5, E_B16 = 6, E_RESID_DROP = 7, E_RESID_DROP_LAST = 8 };
 
 struct Epi {
     float *f32 = nullptr;           // E_F32 / E_PART / E_RESID output
@@ -111,7 +111,7 @@ struct Epi {
     const uint16_t *aux = nullptr;  // E_GELU_BWD: bf16(a)
     int64_t ldc = 0;                // row pitch of the outputs (elements)
     int C = 0, hs = 0, n_head = 0;  // E_QKV: head-major bf16 planes of plane elements each
-    int64_t plane = 0;
+    int64_t plane = 0;              // (E_RESID_DROP_LAST: the row pitch of the mask, 256 C, the output being the compact matrix)
     trk::Drop drop;                 // E_RESID_DROP: the branch's mask stream, base = the index of the chunk's first element
 };
 
@@ -132,6 +132,14 @@ __device__ __forceinline__ void epilogue(const Epi &ep, int64_t m, int n, f32x4 
     } else if constexpr (EPI == E_RESID_DROP) {
         // x + dropout(bf16(linear output)): bf16(m s bf16(o)), as nn.Dropout on a bf16 tensor; n is a multiple of 4: one hash
         const uint64_t h = trk::drop_hash(ep.drop.key, (ep.drop.base + (uint64_t)o) >> 2);
+        const float4 r = *reinterpret_cast<const float4 *>(ep.res + o);
+        *reinterpret_cast<float4 *>(ep.f32 + o) = make_float4(
+            r.x + bf_round(bf_round(v[0]) * trk::drop_factor(h, 0, ep.drop)), r.y + bf_round(bf_round(v[1]) * trk::drop_factor(h, 1, ep.drop)),
+            r.z + bf_round(bf_round(v[2]) * trk::drop_factor(h, 2, ep.drop)), r.w + bf_round(bf_round(v[3]) * trk::drop_factor(h, 3, ep.drop)));
+    } else if constexpr (EPI == E_RESID_DROP_LAST) {
+        // ... of the compact last layer: row m is token 255 of row m, whose mask elements lie ep.plane = 256 C apart; drop.base = the
+        // element of compact row 0, column 0
+        const uint64_t h = trk::drop_hash(ep.drop.key, (ep.drop.base + (uint64_t)m * (uint64_t)ep.plane + (uint64_t)n) >> 2);
         const float4 r = *reinterpret_cast<const float4 *>(ep.res + o);
         *reinterpret_cast<float4 *>(ep.f32 + o) = make_float4(
             r.x + bf_round(bf_round(v[0]) * trk::drop_factor(h, 0, ep.drop)), r.y + bf_round(bf_round(v[1]) * trk::drop_factor(h, 1, ep.drop)),

@@ -10,6 +10,8 @@
 // chunk_fwd_bwd_rows runs the layers below the last as chunk_fwd_bwd does, and the last layer, ln_f, the head and the cross-entropy on the
 // compact matrix of the rows' last tokens (layer_forward_last, layer_backward_last, Span, Compact).  Its normaliser is the call's row count,
 // a host-side number: that path holds no stream synchronise, no blocking copy and no host read of device memory.
+// mgpt_gpt_forward_backward_rows_drop is that call with a DropCfg: the compact last layer draws the general call's masks at token / query 255
+// (drop_last, attn_last_*_kernel<.., true>, branch_forward_last_*, branch_grad_last).
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -138,11 +140,13 @@ struct Span { int64_t m; float *dx, *dxn, *gp; };
 //   Y[l]            y | ln_1(x) of token 255 | x of token 255
 //   XM[l], XN2[l], A[l], XF, XNF, LG, DLG, NLL, HT, DH   their roles, mc tokens (bf16: bf16_layer(t, l, mc, C)'s a and h, bf16_grads' da)
 //   AST             the softmax statistics (m, 1 / l) per (row, head), in both precisions
-//   DY              d y | d x | d ln | gain terms | d q | d ln_1 of token 255
+//   DY              d y | d x | d ln | gain terms | d q | d ln_1 of token 255 | under dropout: a branch's output before its mask joins
+//                   (forward, fp32), then m s d x, the gradient that enters a branch's c_proj (backward)
 struct Compact {
     int n, mc;
     float *q, *y, *xn1, *x, *dy, *dq, *dxn1;
     Span span;
+    float *db;
 };
 
 Compact compact_of(const TrainState *t, int l, int n, bool bf16, int C)
@@ -150,7 +154,7 @@ Compact compact_of(const TrainState *t, int l, int n, bool bf16, int C)
     const int mc = bf16 ? (n + 31) / 32 * 32 : n;
     auto sub = [&](float *slot, int i) { return slot + (size_t)i * mc * C; };
     return {n, mc, t->QKV[l], t->Y[l], sub(t->Y[l], 1), sub(t->Y[l], 2), t->DY, sub(t->DY, 4), sub(t->DY, 5),
-            {(int64_t)mc, sub(t->DY, 1), sub(t->DY, 2), sub(t->DY, 3)}};
+            {(int64_t)mc, sub(t->DY, 1), sub(t->DY, 2), sub(t->DY, 3)}, sub(t->DY, 6)};
 }
 
 // ----- epilogue arguments of gemm_bf16_kernel, one constructor per kind (the fields a kind does not read stay zero) -----
@@ -507,11 +511,50 @@ struct Chunk {
     int layer_forward(int l) { return bf16 ? layer_forward_bf16(l) : layer_forward_f32(l); }
     int layer_backward(int l) { return bf16 ? layer_backward_bf16(l) : layer_backward_f32(l); }
 
-    // ----- the last layer and the head on the compact matrix of the rows' last tokens (mgpt_gpt_forward_backward_rows; no dropout) -----
+    // ----- the last layer and the head on the compact matrix of the rows' last tokens (mgpt_gpt_forward_backward_rows, _rows_drop) -----
     // Of the last layer only ln_1 and the K | V projection run on all tokens; the query, attention's output, c_proj, the MLP, ln_f, the head
     // and the cross-entropy run on token 255 of each row.  Backward: the residual gradient is non-zero at token 255 only, d K and d V are
     // dense, so c_attn's K | V columns and ln_1 run over all tokens and everything else on the compact matrix.
+    // Under dropout the compact tokens draw the general call's masks at token / query 255: site 1 through drop(SITE_ATTN, l) (the kernels
+    // add query 255's offset), sites 2 and 3 through drop_last, whose base is token 255 of the chunk's first row (the mask's rows lie
+    // 256 C elements apart, the compact matrix's C).
     Compact compact() const { return compact_of(t, L - 1, rows, bf16, C); }
+
+    trk::Drop drop_last(int site) const
+    {
+        trk::Drop d = drop(site, L - 1);
+        d.base += (uint64_t)(kT - 1) * C;
+        return d;
+    }
+    // fp32: out = x + m s (A W^T) on the compact matrix, the branch output through k.db
+    int branch_forward_last_f32(int site, const Compact &k, const float *A, const float *W, int K, const float *x, float *out)
+    {
+        if (!drops(site)) return tr_gemm<true, false, trk::OUT_RESID>(A, K, W, K, out, C, k.mc, C, K, x);
+        MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(A, K, W, K, k.db, C, k.mc, C, K)));
+        MGPT_LAUNCH(trk::drop_resid_last_kernel, dim3(grid_1d((int64_t)k.mc * C / 4)), dim3(256), 0, s, x, (const float *)k.db, out, k.mc, C, drop_last(site));
+        return MGPT_OK;
+    }
+    // bf16: out = x + bf16(m s bf16(A W^T)) in the GEMM's epilogue (the padding rows stay zero: x and A are zero there)
+    int branch_forward_last_bf16(int site, const Compact &k, const uint16_t *A, const float *W, int K, const float *x, float *out)
+    {
+        tbk::Epi e = epi_resid(out, x, C);
+        if (!drops(site)) return bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(A, K, W, K, k.mc, C, K, e);
+        e.drop = drop_last(site);
+        e.plane = (int64_t)kT * C;
+        return bf_gemm<uint16_t, true, float, true, tbk::E_RESID_DROP_LAST>(A, K, W, K, k.mc, C, K, e);
+    }
+    // the gradient that enters a compact branch's c_proj: the span's dx, or m s dx in k.db (bf16: the input rounded first, as branch_grad;
+    // zero padding rows stay zero)
+    int branch_grad_last(int site, const Compact &k, const float **dx)
+    {
+        *dx = k.span.dx;
+        if (!drops(site)) return MGPT_OK;
+        *dx = k.db;
+        const dim3 grid(grid_1d((int64_t)k.mc * C / 4));
+        if (bf16) MGPT_LAUNCH(trk::drop_scale_last_kernel<true>, grid, dim3(256), 0, s, (const float *)k.span.dx, k.db, k.mc, C, drop_last(site));
+        else MGPT_LAUNCH(trk::drop_scale_last_kernel<false>, grid, dim3(256), 0, s, (const float *)k.span.dx, k.db, k.mc, C, drop_last(site));
+        return MGPT_OK;
+    }
 
     int gather_last(const float *src, float *dst, const Compact &k)
     {
@@ -534,18 +577,27 @@ struct Chunk {
     int attn_last_forward(const Compact &k, const TQ *q, const TQ *kp, const TQ *vp, TQ *y)
     {
         const dim3 grid((unsigned)(k.n * g->nh));
-        if (g->hs == 32) MGPT_LAUNCH((trk::attn_last_fwd_kernel<32, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, t->AST, g->nh, scale);
-        else MGPT_LAUNCH((trk::attn_last_fwd_kernel<64, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, t->AST, g->nh, scale);
+        if (drops(SITE_ATTN)) {
+            const trk::Drop d = drop(SITE_ATTN, L - 1);
+            if (g->hs == 32) MGPT_LAUNCH((trk::attn_last_fwd_kernel<32, TQ, true>), grid, dim3(256), 0, s, q, kp, vp, y, t->AST, g->nh, scale, d);
+            else MGPT_LAUNCH((trk::attn_last_fwd_kernel<64, TQ, true>), grid, dim3(256), 0, s, q, kp, vp, y, t->AST, g->nh, scale, d);
+        } else if (g->hs == 32) MGPT_LAUNCH((trk::attn_last_fwd_kernel<32, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, t->AST, g->nh, scale, trk::Drop());
+        else MGPT_LAUNCH((trk::attn_last_fwd_kernel<64, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, t->AST, g->nh, scale, trk::Drop());
         return zero_pad(y, sizeof(TQ), k);
     }
     template <typename TQ>
     int attn_last_backward(const Compact &k, const TQ *q, const TQ *kp, const TQ *vp, const TQ *y, const TQ *dy)
     {
         const dim3 grid((unsigned)(k.n * g->nh));
-        if (g->hs == 32)
-            MGPT_LAUNCH((trk::attn_last_bwd_kernel<32, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, dy, (const float *)t->AST, t->DQKV, k.dq, g->nh, scale);
+        const float *st = t->AST;
+        if (drops(SITE_ATTN)) {
+            const trk::Drop d = drop(SITE_ATTN, L - 1);
+            if (g->hs == 32) MGPT_LAUNCH((trk::attn_last_bwd_kernel<32, TQ, true>), grid, dim3(256), 0, s, q, kp, vp, y, dy, st, t->DQKV, k.dq, g->nh, scale, d);
+            else MGPT_LAUNCH((trk::attn_last_bwd_kernel<64, TQ, true>), grid, dim3(256), 0, s, q, kp, vp, y, dy, st, t->DQKV, k.dq, g->nh, scale, d);
+        } else if (g->hs == 32)
+            MGPT_LAUNCH((trk::attn_last_bwd_kernel<32, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, dy, st, t->DQKV, k.dq, g->nh, scale, trk::Drop());
         else
-            MGPT_LAUNCH((trk::attn_last_bwd_kernel<64, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, dy, (const float *)t->AST, t->DQKV, k.dq, g->nh, scale);
+            MGPT_LAUNCH((trk::attn_last_bwd_kernel<64, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, dy, st, t->DQKV, k.dq, g->nh, scale, trk::Drop());
         return zero_pad(k.dq, sizeof(float), k);
     }
 
@@ -562,11 +614,11 @@ struct Chunk {
         MGPT_TRY(gather_last(t->X[l], k.x, k));
         MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(k.xn1, C, P + lo.attn_w, C, k.q, C, mc, C, C)));
         MGPT_TRY(attn_last_forward<float>(k, k.q, kp, vp, k.y));
-        MGPT_TRY((tr_gemm<true, false, trk::OUT_RESID>(k.y, C, P + lo.proj_w, C, t->XM[l], C, mc, C, C, k.x)));
+        MGPT_TRY(branch_forward_last_f32(SITE_ATTN_PROJ, k, k.y, P + lo.proj_w, C, k.x, t->XM[l]));
         MGPT_TRY(gpt_f32_layernorm(g, t->XM[l], P + lo.ln2, t->XN2[l], mc, s));
         MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(t->XN2[l], C, P + lo.fc_w, C, t->A[l], 4 * C, mc, 4 * C, C)));
         MGPT_LAUNCH(trk::gelu_kernel, dim3(grid_1d(4 * mc * C)), dim3(256), 0, s, t->A[l], t->HT, 4 * mc * C);
-        return tr_gemm<true, false, trk::OUT_RESID>(t->HT, 4 * C, P + lo.proj2_w, 4 * C, t->XF, C, mc, C, 4 * C, t->XM[l]);
+        return branch_forward_last_f32(SITE_MLP_PROJ, k, t->HT, P + lo.proj2_w, 4 * C, t->XM[l], t->XF);
     }
 
     int layer_forward_last_bf16()
@@ -583,10 +635,10 @@ struct Chunk {
         MGPT_TRY(gather_last(t->X[l], k.x, k));
         MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_B16>(k.xn1, C, P + lo.attn_w, C, mc, C, C, epi_b16(v.qkv, C))));
         MGPT_TRY(attn_last_forward<uint16_t>(k, v.qkv, kp, vp, v.y));
-        MGPT_TRY((bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(v.y, C, P + lo.proj_w, C, mc, C, C, epi_resid(t->XM[l], k.x, C))));
+        MGPT_TRY(branch_forward_last_bf16(SITE_ATTN_PROJ, k, v.y, P + lo.proj_w, C, k.x, t->XM[l]));
         MGPT_TRY(gpt_f32_layernorm(g, t->XM[l], P + lo.ln2, t->XN2[l], mc, s));
         MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_FC>(t->XN2[l], C, P + lo.fc_w, C, mc, 4 * C, C, epi_fc(v.a, v.h, 4 * C))));
-        return bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(v.h, 4 * C, P + lo.proj2_w, 4 * C, mc, C, 4 * C, epi_resid(t->XF, t->XM[l], C));
+        return branch_forward_last_bf16(SITE_MLP_PROJ, k, v.h, P + lo.proj2_w, 4 * C, t->XM[l], t->XF);
     }
 
     // ln_f, logits and cross-entropy of the compact tokens; the normaliser call_rows is the row count of the WHOLE call
@@ -624,15 +676,17 @@ struct Chunk {
         const LayerOff &lo = g->layers[l];
         const Compact k = compact();
         const int64_t mc = k.mc;
-        const float *db = k.span.dx, *kp = t->QKV[l] + M * C, *vp = kp + M * C;
+        const float *db, *kp = t->QKV[l] + M * C, *vp = kp + M * C;
         const size_t kv = (size_t)C * C;                            // c_attn's K | V rows start here
-        // MLP; HT still holds gelu(a) of the compact tokens (no layer ran after this one's forward)
+        // MLP; HT still holds gelu(a) of the compact tokens (no layer ran after this one's forward); db = d x_out, or m s d x_out
+        MGPT_TRY(branch_grad_last(SITE_MLP_PROJ, k, &db));
         MGPT_TRY((tr_gemm<true, true, trk::OUT_GELU_BWD>(db, C, P + lo.proj2_w, 4 * C, t->DH, 4 * C, mc, 4 * C, C, t->A[l])));
         MGPT_TRY(weight_grad(db, C, t->HT, G + lo.proj2_w, C, 4 * C, mc));
         MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DH, 4 * C, P + lo.fc_w, C, k.span.dxn, C, mc, C, 4 * C)));
         MGPT_TRY(weight_grad(t->DH, 4 * C, t->XN2[l], G + lo.fc_w, 4 * C, C, mc));
         MGPT_TRY(ln_backward<true>(t->XM[l], lo.ln2, k.span));
         // attention of query 255: d y, then d q (compact) and d k | d v (dense)
+        MGPT_TRY(branch_grad_last(SITE_ATTN_PROJ, k, &db));
         MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(db, C, P + lo.proj_w, C, k.dy, C, mc, C, C)));
         MGPT_TRY(weight_grad(db, C, k.y, G + lo.proj_w, C, C, mc));
         MGPT_TRY(attn_last_backward<float>(k, k.q, kp, vp, k.y, k.dy));
@@ -653,13 +707,15 @@ struct Chunk {
         const Bf16Layer v = bf16_layer(t, l, mc, C);
         const Bf16Grads d = bf16_grads(t);                          // d.dy = k.dy's slot, d.da = DH
         const uint16_t *kp = v.qkv + M * C, *vp = kp + M * C;
-        const float *db = k.span.dx;
+        const float *db;
         const size_t kv = (size_t)C * C;
+        MGPT_TRY(branch_grad_last(SITE_MLP_PROJ, k, &db));
         MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_GELU_BWD>(db, C, P + lo.proj2_w, 4 * C, mc, 4 * C, C, epi_gelu_bwd(d.da, v.a, 4 * C))));
         MGPT_TRY(weight_grad_bf16(db, C, v.h, G + lo.proj2_w, C, 4 * C, mc));
         MGPT_TRY((bf_gemm<uint16_t, true, float, false, tbk::E_F32>(d.da, 4 * C, P + lo.fc_w, C, mc, C, 4 * C, epi_f32(k.span.dxn, C))));
         MGPT_TRY(weight_grad_bf16(d.da, 4 * C, t->XN2[l], G + lo.fc_w, 4 * C, C, mc));
         MGPT_TRY(ln_backward<true>(t->XM[l], lo.ln2, k.span));
+        MGPT_TRY(branch_grad_last(SITE_ATTN_PROJ, k, &db));
         MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_B16>(db, C, P + lo.proj_w, C, mc, C, C, epi_b16(d.dy, C))));
         MGPT_TRY(weight_grad_bf16(db, C, v.y, G + lo.proj_w, C, C, mc));
         MGPT_TRY(attn_last_backward<uint16_t>(k, v.qkv, kp, vp, v.y, d.dy));
@@ -710,11 +766,13 @@ int chunk_fwd_bwd(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows, cons
 }
 
 // one chunk of rows of mgpt_gpt_forward_backward_rows: the layers below the last run chunk_fwd_bwd's launches, the last layer and the head
-// the compact ones; call_rows normalises the cross-entropy
+// the compact ones; call_rows normalises the cross-entropy.  Under dropout (dc) the dense launches draw their masks as chunk_fwd_bwd's do.
+// Slot lifetimes: the dense fp32 forward's branch outputs pass through DY before the compact gradients live there, and branch_grad and
+// embedding_backward fill DXN after layer_backward_last_tail has consumed it.
 int chunk_fwd_bwd_rows(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows, const int32_t *labels, int call_rows, float loss_scale, int precision,
-                       hipStream_t s)
+                       const DropCfg &dc, hipStream_t s)
 {
-    Chunk c = {g, t, tok, nullptr, rows, loss_scale, precision == MGPT_PREC_BF16, s, DropCfg()};
+    Chunk c = {g, t, tok, nullptr, rows, loss_scale, precision == MGPT_PREC_BF16, s, dc};
     MGPT_TRY(c.embed());
     for (int l = 0; l + 1 < g->L; l++) MGPT_TRY(c.layer_forward(l));
     MGPT_TRY(c.layer_forward_last());
@@ -723,6 +781,16 @@ int chunk_fwd_bwd_rows(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows,
     MGPT_TRY(c.layer_backward_last());
     for (int l = g->L - 2; l >= 0; l--) MGPT_TRY(c.layer_backward(l));
     return c.embedding_backward();
+}
+
+// the 16-bit threshold of sampling.py: dropout_threshold, and the kept elements' factor 1 / (1 - thr / 65536)
+DropCfg drop_cfg(float p, uint64_t seed, uint64_t step, int sites)
+{
+    DropCfg dc;
+    dc.thr = (uint32_t)std::min<long>(std::lround((double)p * 65536.0), 65535);
+    dc.scale = 1.0f / (1.0f - (float)dc.thr / 65536.0f);
+    dc.seed = seed; dc.step = step; dc.sites = sites;
+    return dc;
 }
 
 int require_train(mgpt_gpt *g)
@@ -860,11 +928,7 @@ extern "C" int mgpt_gpt_forward_backward_drop(mgpt_gpt *g, const uint8_t *d_toke
     MGPT_REQUIRE(t->h_cnt[1] == 0, MGPT_ERR_ARG, "targets must lie in [-1, 67): -1 is ignored, 0 .. 66 are vocabulary ids");
     MGPT_REQUIRE(t->h_cnt[0] > 0, MGPT_ERR_ARG, "no targeted position in the call (every target is -1): the mean cross-entropy is undefined");
     MGPT_HIP(hipMemsetAsync(t->loss_acc, 0, sizeof(double), s));
-    // the 16-bit threshold of sampling.py: dropout_threshold, and the kept elements' factor 1 / (1 - thr / 65536)
-    DropCfg dc;
-    dc.thr = (uint32_t)std::min<long>(std::lround((double)p * 65536.0), 65535);
-    dc.scale = 1.0f / (1.0f - (float)dc.thr / 65536.0f);
-    dc.seed = seed; dc.step = step; dc.sites = sites;
+    DropCfg dc = drop_cfg(p, seed, step, sites);
     MGPT_REQUIRE(dc.thr == 0 || sites == 0 || g->C % 4 == 0, MGPT_ERR_UNSUPPORTED, "dropout masks come four elements to a hash: n_embd = %d is no multiple of 4", g->C);
     for (int r0 = 0; r0 < rows; r0 += t->max_rows) {
         const int n = std::min(t->max_rows, rows - r0);
@@ -880,6 +944,15 @@ extern "C" int mgpt_gpt_forward_backward_drop(mgpt_gpt *g, const uint8_t *d_toke
 extern "C" int mgpt_gpt_forward_backward_rows(mgpt_gpt *g, const uint8_t *d_tokens, int rows, const int32_t *d_labels, float loss_scale,
                                               float *d_loss, int precision, void *stream)
 {
+    return mgpt_gpt_forward_backward_rows_drop(g, d_tokens, rows, d_labels, loss_scale, d_loss, precision, 0.f, 0, 0, 0, 0, stream);
+}
+
+extern "C" int mgpt_gpt_forward_backward_rows_drop(mgpt_gpt *g, const uint8_t *d_tokens, int rows, const int32_t *d_labels, float loss_scale,
+                                                   float *d_loss, int precision, float p, uint64_t seed, uint64_t step, uint64_t row0, int sites,
+                                                   void *stream)
+{
+    MGPT_REQUIRE(p >= 0.f && p < 1.f, MGPT_ERR_ARG, "dropout p=%g: a probability in [0, 1)", (double)p);
+    MGPT_REQUIRE(sites >= 0 && sites <= 15, MGPT_ERR_ARG, "dropout sites=%d: a mask of the four sites (15 = all, model.py's behaviour)", sites);
     MGPT_TRY(require_train(g));
     MGPT_REQUIRE(d_tokens && d_labels, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(rows > 0, MGPT_ERR_ARG, "rows=%d", rows);
@@ -892,9 +965,13 @@ extern "C" int mgpt_gpt_forward_backward_rows(mgpt_gpt *g, const uint8_t *d_toke
     hipStream_t s = (hipStream_t)stream;
     // every launch below is stream-ordered and the normaliser is `rows`: the host waits for nothing
     MGPT_HIP(hipMemsetAsync(t->loss_acc, 0, sizeof(double), s));
+    const DropCfg base = drop_cfg(p, seed, step, sites);
+    MGPT_REQUIRE(base.thr == 0 || sites == 0 || g->C % 4 == 0, MGPT_ERR_UNSUPPORTED, "dropout masks come four elements to a hash: n_embd = %d is no multiple of 4", g->C);
     for (int r0 = 0; r0 < rows; r0 += t->max_rows) {
         const int n = std::min(t->max_rows, rows - r0);
-        MGPT_TRY(chunk_fwd_bwd_rows(g, t, d_tokens + (size_t)r0 * kT, n, d_labels + r0, rows, loss_scale, precision, s));
+        DropCfg dc = base;
+        dc.first_row = row0 + (uint64_t)r0;
+        MGPT_TRY(chunk_fwd_bwd_rows(g, t, d_tokens + (size_t)r0 * kT, n, d_labels + r0, rows, loss_scale, precision, dc, s));
     }
     if (d_loss) MGPT_LAUNCH(trk::loss_final_rows_kernel, dim3(1), dim3(64), 0, s, (const double *)t->loss_acc, (double)rows, d_loss);
     return MGPT_OK;

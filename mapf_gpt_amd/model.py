@@ -364,14 +364,30 @@ class GPT:
         on token 255 only, and the call never waits for the device (the general call waits once per call for its targeted-position count).
         check=True validates the labels against [0, 67) with one min / max (a wait when they live on the device); with check=False an
         out-of-range label makes the loss and the next gradient norm NaN.  Gradients accumulate into the same buffer as forward_backward's,
-        in either precision.  Dropout is not built here: a config.dropout > 0 in training mode raises NotImplementedError (forward_backward
-        serves it); after eval() the call runs, as the general one does."""
+        in either precision.  This call has no dropout: a config.dropout > 0 in training mode raises NotImplementedError
+        (forward_backward_rows_drop and forward_backward serve it); after eval() the call runs, as the general one does."""
         if precision not in _lib.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}, got {precision!r}")
         self._require_train()
         if self.training and self.config.dropout > 0:
             raise NotImplementedError(f"forward_backward_rows has no dropout (config.dropout = {self.config.dropout}): use "
                                       "forward_backward(idx, targets), the general call, which serves it")
+        return self._rows_call(rows_u8, labels, loss_scale, precision, check, 0.0, 0, 0, 0)
+
+    def forward_backward_rows_drop(self, rows_u8, labels, loss_scale=1.0, precision="f32", check=True, *, dropout_step=None, row0=0,
+                                   dropout_sites=15):
+        """forward_backward_rows with forward_backward's dropout: = forward_backward(rows_u8, targets, ..., dropout_step=, row0=,
+        dropout_sites=) with targets[r, 255] = labels[r] and -1 elsewhere -- the same masks (the compact last layer draws the general
+        call's at token / query 255), the same step counter (set_dropout_rng; incremented per call when p > 0; dropout_step overrides it
+        without incrementing it), p = config.dropout in training mode and 0 after eval(), where the call is forward_backward_rows.
+        rows_u8, labels and check as forward_backward_rows takes them; no host wait."""
+        if precision not in _lib.PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}, got {precision!r}")
+        self._require_train()
+        p = float(self.config.dropout) if self.training else 0.0
+        return self._rows_call(rows_u8, labels, loss_scale, precision, check, p, dropout_step, row0, dropout_sites)
+
+    def _rows_call(self, rows_u8, labels, loss_scale, precision, check, p, step, row0, sites):
         tokens = self._tokens_u8(rows_u8)
         B, T = tokens.shape
         if T != 256:
@@ -383,9 +399,14 @@ class GPT:
             raise ValueError("labels must lie in [0, 67)")
         lb = labels.to(device=self.device, dtype=torch.int32).contiguous()
         loss = torch.empty((), dtype=torch.float32, device=self.device)
+        if step is None:
+            step = getattr(self, "_drop_step", 0)
+            if p > 0:
+                self._drop_step = step + 1
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().mgpt_gpt_forward_backward_rows(self._h, _lib.ptr(tokens), B, _lib.ptr(lb), float(loss_scale), _lib.ptr(loss),
-                                                                 _lib.PRECISIONS[precision], _lib.stream_ptr()))
+            _lib.check(_lib.lib().mgpt_gpt_forward_backward_rows_drop(self._h, _lib.ptr(tokens), B, _lib.ptr(lb), float(loss_scale), _lib.ptr(loss),
+                                                                      _lib.PRECISIONS[precision], p, (getattr(self, "_drop_seed", None) or 0) & 0xFFFFFFFFFFFFFFFF,
+                                                                      int(step) & 0xFFFFFFFFFFFFFFFF, int(row0), int(sites), _lib.stream_ptr()))
         return loss
 
     def zero_grad(self, set_to_none=True):

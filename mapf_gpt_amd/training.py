@@ -25,6 +25,10 @@ holds the same bits whatever the backend and the weights stay in lockstep withou
 it at every eval_interval boundary and at the end, and a mismatch raises on every rank.  Rank 0 alone evaluates, writes ckpt.pt and prints.
 Without RANK nothing of this runs and the command behaves as a single process always did.
 
+--rows-call runs the micro-steps through GPT.forward_backward_rows (the last layer, the head and the loss on token 255 only, no host wait;
+effective dropout 0 only); --rows-call-drop runs them through GPT.forward_backward_rows_drop, the same micro-step with the general call's
+dropout masks, for any --dropout or checkpoint dropout in [0, 1): the fine-tuning command is --init CKPT --dropout 0.1 --rows-call-drop.
+
 --dtype takes train.py's knob (train.py:66-70): float32 (exact fp32, the default here) or bfloat16 (every micro-step and every estimate_loss in
 the bf16 autocast regime: forward_backward(precision="bf16"), scoring.evaluate(precision="bf16")).  train.py itself defaults to bfloat16 on a
 GPU that supports it; this command keeps float32 as its default.  float16 is refused: it needs a GradScaler, which this command does not have.
@@ -168,6 +172,9 @@ def parse_args(argv=None):
     ap.add_argument("--rows-call", action="store_true",
                     help="run the micro-steps through GPT.forward_backward_rows: the last layer, head and loss on token 255 only and no "
                          "host wait per micro-step; the same gradients up to summation order.  Needs an effective dropout of 0")
+    ap.add_argument("--rows-call-drop", action="store_true",
+                    help="--rows-call through GPT.forward_backward_rows_drop: the same micro-step with the general call's dropout masks "
+                         "(the compact last layer draws them at token 255); any effective dropout in [0, 1), 0 included")
     ap.add_argument("--log-interval", type=int, default=0,
                     help='print {"iter", "loss", "ms"} every N iterations (train.py:346-355); 0 = no such line')
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -182,6 +189,8 @@ def parse_args(argv=None):
         ap.error("--dropout must lie in [0, 1)")
     if a.rows_call and a.dropout:
         ap.error(ROWS_CALL_DROPOUT.format(a.dropout))
+    if a.rows_call and a.rows_call_drop:
+        ap.error("--rows-call and --rows-call-drop name two forms of one micro-step: pass one of them")
     a.precision = DTYPES[a.dtype]
     return a
 
@@ -287,7 +296,7 @@ def run(a, ranks):
     if ckpt is not None:
         opt.load_state_dict(ckpt["optimizer"])
         iter_num, best_val_loss = int(ckpt["iter_num"]), float(ckpt["best_val_loss"])
-    train_it = iter(ArrowBatches(a.data, a.batch_size, a.seed, rank, world, labels=a.rows_call))     # (labels validated per file at load)
+    train_it = iter(ArrowBatches(a.data, a.batch_size, a.seed, rank, world, labels=a.rows_call or a.rows_call_drop))     # (validated per file at load)
     val_it = iter(ArrowBatches(a.val, a.batch_size, a.seed + 1))          # (the validation split is not divided)
     if master:
         os.makedirs(a.out_dir, exist_ok=True)
@@ -326,6 +335,9 @@ def run(a, ranks):
         for micro in range(accum):                             # train.py:314-331
             if a.rows_call:
                 loss = net.forward_backward_rows(torch.as_tensor(X), torch.as_tensor(Y), loss_scale=1.0 / accum, precision=a.precision, check=False)
+            elif a.rows_call_drop:
+                loss = net.forward_backward_rows_drop(torch.as_tensor(X), torch.as_tensor(Y), loss_scale=1.0 / accum, precision=a.precision, check=False,
+                                                      dropout_step=dropout_step(iter_num, a.gradient_accumulation_steps, rank, world, micro))
             else:
                 loss = net.forward_backward(torch.as_tensor(X), torch.as_tensor(Y), loss_scale=1.0 / accum, precision=a.precision,
                                             dropout_step=dropout_step(iter_num, a.gradient_accumulation_steps, rank, world, micro))

@@ -27,6 +27,8 @@ the same rows and labels in place of forward_backward; --call ab times both in o
 call by call, and prints for each the median and the range of its --iters timed regions.  --accum N puts N back-to-back micro-steps in a
 timed region (gradient accumulation: the general call waits for the stream once per micro-step, the rows call never).  In these modes a
 line carries the micro-step timings only (no clip + AdamW, forward or torch yardstick).  The default, --call general, is unchanged.
+With --dropout P the rows call is GPT.forward_backward_rows_drop and the general call runs with the same p: --call ab --dropout 0.1 times
+the two dropout micro-steps against each other on the same rows.
 
 Targets follow the dataset's pattern (-1 except the last position, fast_data_loader.py:58).  Prints one JSON line per shape: median ms of
 each part over --iters timed calls after --warmup untimed ones, HIP events on the current stream.  The torch yardstick runs on
@@ -70,18 +72,23 @@ def micro_steps(a, name, rows, args, tokens, targets):
     """--call rows / ab: the micro-step alone, a.accum of them per timed region"""
     labels = targets[:, -1].contiguous()
     for prec in a.precision.split(","):
-        net = build_model(args, seed=0, max_rows=rows).train()
+        net = build_model(dict(args, dropout=a.dropout), seed=0, max_rows=rows)
+        net.set_dropout_rng(0)
+        net.train()
 
         def general():
             for _ in range(a.accum):
                 net.forward_backward(tokens, targets, loss_scale=1.0 / a.accum, precision=prec)
 
-        def rows_call():
+        def rows_call():                        # (--dropout P: the call with the general call's masks, forward_backward_rows_drop)
             for _ in range(a.accum):
-                net.forward_backward_rows(tokens, labels, loss_scale=1.0 / a.accum, precision=prec, check=False)
+                if a.dropout > 0:
+                    net.forward_backward_rows_drop(tokens, labels, loss_scale=1.0 / a.accum, precision=prec, check=False)
+                else:
+                    net.forward_backward_rows(tokens, labels, loss_scale=1.0 / a.accum, precision=prec, check=False)
         fns = {"general": general, "rows": rows_call} if a.call == "ab" else {"rows": rows_call}
         ms = timed_ab(fns, a.iters, a.warmup)
-        rec = {"shape": name, "rows": rows, "precision": prec, "call": a.call, "accum": a.accum}
+        rec = {"shape": name, "rows": rows, "precision": prec, "call": a.call, "accum": a.accum, "dropout": a.dropout}
         for k, v in ms.items():
             rec[k + "_ms"] = round(float(np.median(v)), 3)
             rec[k + "_range_ms"] = [round(min(v), 3), round(max(v), 3)]
@@ -227,8 +234,6 @@ def main(argv=None):
         from mapf_gpt_amd import weights
         args = weights.model_args(name)
         if a.call != "general":
-            if a.dropout > 0:
-                ap.error("--call rows / ab: forward_backward_rows has no dropout")
             micro_steps(a, name, rows, args, tokens, targets)
             continue
         for prec in a.precision.split(","):
