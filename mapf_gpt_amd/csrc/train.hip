@@ -1,20 +1,25 @@
 // train.hip -- training on the device (replaces train.py:324-331 with model.py:180-184 and :202-226): exact-fp32 or bf16 mixed-precision
 // forward with saved activations, backward into one fp32 gradient buffer in the layout of mgpt_gpt::params, torch's clip_grad_norm_ and AdamW.
 //
-// A call runs in chunks of the workspace's max_rows rows.  chunk_fwd_bwd is the one sequence of both precisions, its steps members of Chunk:
-// embed, layer_forward per layer, head forward and loss, head backward, layer_backward per layer in reverse, embedding backward.  The bf16
-// path reaches the shared, fp32-sized workspace through typed views (bf16_layer, bf16_grads).  Dropout (mgpt_gpt_forward_backward_drop) is a
-// DropCfg of the chunk: every site asks drops(site) and regenerates its mask from drop(site, layer); no mask is stored.
+// A call (train_call: the checks and the chunk loop of both entry points) runs in chunks of the workspace's max_rows rows.  chunk_fwd_bwd is
+// the one sequence of both precisions and both calls, its steps members of Chunk: embed, layer_forward per layer, head forward and loss, head
+// backward, layer_backward per layer in reverse, embedding backward.  The bf16 path reaches the shared, fp32-sized workspace through typed
+// views (bf16_layer, bf16_grads).  Dropout is a DropCfg of the chunk: every site asks drops(site) and regenerates its mask from drop(site,
+// layer, tokens); no mask is stored.  with_attn_kernel turns the head size and attention dropout into the attention kernels' HS and DROP.
 //
-// mgpt_gpt_forward_backward_rows is the micro-step of rows with one targeted position, token 255 (every row the dataset path makes):
-// chunk_fwd_bwd_rows runs the layers below the last as chunk_fwd_bwd does, and the last layer, ln_f, the head and the cross-entropy on the
-// compact matrix of the rows' last tokens (layer_forward_last, layer_backward_last, Span, Compact).  Its normaliser is the call's row count,
-// a host-side number: that path holds no stream synchronise, no blocking copy and no host read of device memory.
-// mgpt_gpt_forward_backward_rows_drop is that call with a DropCfg: the compact last layer draws the general call's masks at token / query 255
-// (drop_last, attn_last_*_kernel<.., true>, branch_forward_last_*, branch_grad_last).
+// mgpt_gpt_forward_backward_rows(_drop) is the micro-step of rows with one targeted position, token 255 (every row the dataset path makes):
+// chunk_fwd_bwd runs the last layer, ln_f, the head and the cross-entropy on the compact matrix of the rows' last tokens (Compact).  Its
+// normaliser is the call's row count, a host-side number: that path holds no stream synchronise, no blocking copy and no host read of device
+// memory.
+//
+// The token-wise steps -- a residual branch's join and gradient, the MLP and out-projection backward, the bf16 MLP forward, LayerNorm
+// backward, the head -- are written once per precision on a Tokens: all tokens of the chunk (Chunk::all) or the compact ones (Compact::tok),
+// which draw the general call's dropout masks at token 255.  A layer's dense and compact bodies hold what differs: attention, c_attn, ln_1
+// and, in fp32, the forward's linears.
 #include <cmath>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -129,8 +134,12 @@ Bf16Layer bf16_layer(const TrainState *t, int l, int64_t M, int C)
 Bf16Grads bf16_grads(const TrainState *t) { return {reinterpret_cast<uint16_t *>(t->DY), reinterpret_cast<uint16_t *>(t->DH)}; }
 
 // ----- the compact matrix of the last-position micro-step -----
-// The tokens a token-wise launch runs over, with their gradient scratch: all M tokens of the chunk (Chunk::all), or the mc compact tokens.
-struct Span { int64_t m; float *dx, *dxn, *gp; };
+// The tokens a token-wise step runs over: all M tokens of the chunk (Chunk::all), or the mc compact tokens (Compact::tok).  With them their
+// gradient scratch (d x, d ln, the gain terms), the slot m s d x is written to before a masked branch's c_proj (drop_dx), and the slot a
+// masked fp32 branch's output passes through before it joins the residual (drop_out).  last: the tokens are token 255 of each row, so
+// their dropout masks lie 256 C elements apart from token 255 of the chunk's first row on (Chunk::drop), and the elementwise kernels and
+// the epilogue that draw them are the _last ones.
+struct Tokens { int64_t m; float *dx, *dxn, *gp, *drop_dx, *drop_out; bool last; };
 
 // A chunk of n rows keeps mc compact tokens, one per row (token 255), in the slots its last layer l = L - 1 does not fill.  mc = n in fp32
 // (gemm_tr_kernel checks every index); in bf16 n rounded up to 32, the MFMA GEMMs' k step, the padding rows zero (gather_last_kernel,
@@ -145,8 +154,7 @@ struct Span { int64_t m; float *dx, *dxn, *gp; };
 struct Compact {
     int n, mc;
     float *q, *y, *xn1, *x, *dy, *dq, *dxn1;
-    Span span;
-    float *db;
+    Tokens tok;
 };
 
 Compact compact_of(const TrainState *t, int l, int n, bool bf16, int C)
@@ -154,7 +162,7 @@ Compact compact_of(const TrainState *t, int l, int n, bool bf16, int C)
     const int mc = bf16 ? (n + 31) / 32 * 32 : n;
     auto sub = [&](float *slot, int i) { return slot + (size_t)i * mc * C; };
     return {n, mc, t->QKV[l], t->Y[l], sub(t->Y[l], 1), sub(t->Y[l], 2), t->DY, sub(t->DY, 4), sub(t->DY, 5),
-            {(int64_t)mc, sub(t->DY, 1), sub(t->DY, 2), sub(t->DY, 3)}, sub(t->DY, 6)};
+            {(int64_t)mc, sub(t->DY, 1), sub(t->DY, 2), sub(t->DY, 3), sub(t->DY, 6), sub(t->DY, 6), true}};
 }
 
 // ----- epilogue arguments of gemm_bf16_kernel, one constructor per kind (the fields a kind does not read stay zero) -----
@@ -199,8 +207,9 @@ struct DropCfg {
     int sites = 0;
 };
 
-// One chunk of rows of a call: what its launches share, and the launches (chunk_fwd_bwd is the sequence).  Only layer_forward,
-// layer_backward, their _last forms and ln_backward have a body per precision; the head and the embedding run the fp32 kernels in both.
+// One chunk of rows of a call: what its launches share, and the launches (chunk_fwd_bwd is the sequence).  The layer's steps and
+// ln_backward have a body per precision; the head and the embedding run the fp32 kernels in both.  call_rows > 0: the rows call, tg its
+// labels, one per row, and call_rows the row count of the whole call.
 // bf16 (MGPT_PREC_BF16) is train.py's autocast regime on bf16 MFMAs (gpt_kernels_train_bf16.h).  Rounded to bf16, as autocast holds them: the operands of the
 // block linears, q, k, v, attention's output and its gradient, P and dS, the linears' outputs and GELU's, the gradients of the MLP hidden
 // tensors.  fp32: the embedding sum, the residual stream and its gradient, LayerNorm, softmax statistics, the head, cross-entropy and every
@@ -210,7 +219,7 @@ struct Chunk {
     TrainState *t;
     const uint8_t *tok;
     const int32_t *tg;
-    int rows;
+    int rows, call_rows;
     float loss_scale;
     bool bf16;
     hipStream_t s;
@@ -223,7 +232,13 @@ struct Chunk {
 
     float *x_out(int l) const { return l + 1 < L ? t->X[l + 1] : t->XF; }
 
-    // ----- dropout: is the site on, its mask stream for this chunk, and the two elementwise launches over the chunk's M x C elements -----
+    // all tokens of the chunk: the masked branch gradient goes to DXN (free at both points of layer_backward), a masked fp32 branch output
+    // through DY (free during the forward)
+    Tokens all() const { return {M, t->DX, t->DXN, t->GP, t->DXN, t->DY, false}; }
+    // the last layer's compact tokens (the rows call)
+    Compact compact() const { return compact_of(t, L - 1, rows, bf16, C); }
+
+    // ----- dropout: is the site on, its mask stream for this chunk, and the elementwise launches over the tokens' m x C elements -----
     bool drops(int site) const { return dc.thr > 0 && ((dc.sites >> site) & 1); }
     trk::Drop drop(int site, int layer) const
     {
@@ -234,42 +249,63 @@ struct Chunk {
         d.scale = dc.scale;
         return d;
     }
+    // ... of sites 0, 2 and 3 over `tk`: the compact tokens' base is token 255 of the chunk's first row
+    trk::Drop drop(int site, int layer, const Tokens &tk) const
+    {
+        trk::Drop d = drop(site, layer);
+        if (tk.last) d.base += (uint64_t)(kT - 1) * C;
+        return d;
+    }
     // out = m s in (in rounded to bf16 first in the bf16 path's backward: the gradient of a bf16 branch output)
-    int drop_scale(int site, int layer, const float *in, float *out, bool round = false)
+    int drop_scale(int site, int layer, const Tokens &tk, const float *in, float *out, bool round = false)
     {
-        const int64_t n4 = M * C / 4;
-        if (round) MGPT_LAUNCH(trk::drop_scale_kernel<true>, dim3(grid_1d(n4)), dim3(256), 0, s, in, out, n4, drop(site, layer));
-        else MGPT_LAUNCH(trk::drop_scale_kernel<false>, dim3(grid_1d(n4)), dim3(256), 0, s, in, out, n4, drop(site, layer));
+        const int64_t n4 = tk.m * C / 4;
+        const dim3 grid(grid_1d(n4));
+        const trk::Drop d = drop(site, layer, tk);
+        if (tk.last) {
+            if (round) MGPT_LAUNCH(trk::drop_scale_last_kernel<true>, grid, dim3(256), 0, s, in, out, (int)tk.m, C, d);
+            else MGPT_LAUNCH(trk::drop_scale_last_kernel<false>, grid, dim3(256), 0, s, in, out, (int)tk.m, C, d);
+        } else if (round) MGPT_LAUNCH(trk::drop_scale_kernel<true>, grid, dim3(256), 0, s, in, out, n4, d);
+        else MGPT_LAUNCH(trk::drop_scale_kernel<false>, grid, dim3(256), 0, s, in, out, n4, d);
         return MGPT_OK;
     }
-    // the gradient that enters a residual branch's c_proj: DX, or m s DX in DXN (free at both points of layer_backward)
-    int branch_grad(int site, int layer, const float **dx)
+    // the gradient that enters a residual branch's c_proj: the tokens' dx, or m s dx in their drop_dx (zero padding rows stay zero)
+    int branch_grad(int site, int layer, const Tokens &tk, const float **db)
     {
-        *dx = t->DX;
+        *db = tk.dx;
         if (!drops(site)) return MGPT_OK;
-        *dx = t->DXN;
-        return drop_scale(site, layer, t->DX, t->DXN, bf16);
+        *db = tk.drop_dx;
+        return drop_scale(site, layer, tk, tk.dx, tk.drop_dx, bf16);
     }
-    // fp32 path: out = x + m s (A W^T), the branch output through DY (free during the forward)
-    int branch_forward_f32(int site, int layer, const float *A, const float *W, int K, const float *x, float *out)
+    // fp32 path: out = x + m s (A W^T), the masked branch's output through the tokens' drop_out.  All tokens: the inference linear, which
+    // accumulates onto a copy of x; the compact ones: gemm_tr_kernel, which checks every index
+    int branch_forward_f32(int site, int layer, const Tokens &tk, const float *A, const float *W, int K, const float *x, float *out)
     {
-        if (!drops(site)) {
-            MGPT_HIP(hipMemcpyAsync(out, x, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, s));
-            return gpt_f32_linear(g, 1, A, W, out, M, C, K, s);
+        const int64_t n4 = tk.m * C / 4;
+        if (tk.last) {
+            if (!drops(site)) return tr_gemm<true, false, trk::OUT_RESID>(A, K, W, K, out, C, tk.m, C, K, x);
+            MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(A, K, W, K, tk.drop_out, C, tk.m, C, K)));
+            MGPT_LAUNCH(trk::drop_resid_last_kernel, dim3(grid_1d(n4)), dim3(256), 0, s, x, (const float *)tk.drop_out, out, (int)tk.m, C, drop(site, layer, tk));
+            return MGPT_OK;
         }
-        MGPT_TRY(gpt_f32_linear(g, 0, A, W, t->DY, M, C, K, s));
-        const int64_t n4 = M * C / 4;
-        MGPT_LAUNCH(trk::drop_resid_kernel, dim3(grid_1d(n4)), dim3(256), 0, s, x, (const float *)t->DY, out, n4, drop(site, layer));
+        if (!drops(site)) {
+            MGPT_HIP(hipMemcpyAsync(out, x, (size_t)tk.m * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+            return gpt_f32_linear(g, 1, A, W, out, tk.m, C, K, s);
+        }
+        MGPT_TRY(gpt_f32_linear(g, 0, A, W, tk.drop_out, tk.m, C, K, s));
+        MGPT_LAUNCH(trk::drop_resid_kernel, dim3(grid_1d(n4)), dim3(256), 0, s, x, (const float *)tk.drop_out, out, n4, drop(site, layer, tk));
         return MGPT_OK;
     }
-    // bf16 path: out = x + dropout(bf16(A W^T)) in the GEMM's epilogue
+    // bf16 path: out = x + bf16(m s bf16(A W^T)) in the GEMM's epilogue (the compact tokens' padding rows stay zero: x and A are zero there)
     template <typename TA>
-    int branch_forward_bf16(int site, int layer, const TA *A, const float *W, int K, const float *x, float *out)
+    int branch_forward_bf16(int site, int layer, const Tokens &tk, const TA *A, const float *W, int K, const float *x, float *out)
     {
         tbk::Epi e = epi_resid(out, x, C);
-        if (!drops(site)) return bf_gemm<TA, true, float, true, tbk::E_RESID>(A, K, W, K, M, C, K, e);
-        e.drop = drop(site, layer);
-        return bf_gemm<TA, true, float, true, tbk::E_RESID_DROP>(A, K, W, K, M, C, K, e);
+        if (!drops(site)) return bf_gemm<TA, true, float, true, tbk::E_RESID>(A, K, W, K, tk.m, C, K, e);
+        e.drop = drop(site, layer, tk);
+        if (!tk.last) return bf_gemm<TA, true, float, true, tbk::E_RESID_DROP>(A, K, W, K, tk.m, C, K, e);
+        e.plane = (int64_t)kT * C;
+        return bf_gemm<TA, true, float, true, tbk::E_RESID_DROP_LAST>(A, K, W, K, tk.m, C, K, e);
     }
 
     // out[m][N] (op)= A'(m x K) @ B'(K x N), fp32 on the VALU; slabs > 1: one partial per kps of K
@@ -294,11 +330,8 @@ struct Chunk {
         return MGPT_OK;
     }
 
-    // ----- sums over the chunk's tokens by slabs: partials(S, kps) launches S partial sums of kps tokens each into t->part [S][n], which are
-    // added to out[n] in order -----
-    template <class Launch>
-    int slab_sum(float *out, int64_t n, int align, Launch partials) { return slab_sum(out, n, align, M, partials); }
-    // ... over m tokens
+    // ----- sums over m tokens by slabs: partials(S, kps) launches S partial sums of kps tokens each into t->part [S][n], which are added to
+    // out[n] in order -----
     template <class Launch>
     int slab_sum(float *out, int64_t n, int align, int64_t m, Launch partials)
     {
@@ -309,9 +342,8 @@ struct Chunk {
         return MGPT_OK;
     }
 
-    // weight gradients: dW[Nout][Kin] += dY^T @ X, dY [M][Nout], X [M][Kin]; fp32 on the VALU, or bf16 MFMAs (32-token aligned slabs)
-    int weight_grad(const float *dY, const float *X, float *dW, int Nout, int Kin) { return weight_grad(dY, Nout, X, dW, Nout, Kin, M); }
-    // ... dY with row pitch ldy, over m tokens
+    // weight gradients: dW[Nout][Kin] += dY^T @ X over m tokens, dY [m][Nout] with row pitch ldy, X [m][Kin]; fp32 on the VALU, or bf16
+    // MFMAs (32-token aligned slabs)
     int weight_grad(const float *dY, int64_t ldy, const float *X, float *dW, int Nout, int Kin, int64_t m)
     {
         return slab_sum(dW, (int64_t)Nout * Kin, 16, m, [&](int S, int kps) -> int {
@@ -320,8 +352,6 @@ struct Chunk {
     }
 
     template <typename TY, typename TX>
-    int weight_grad_bf16(const TY *dY, const TX *X, float *dW, int Nout, int Kin) { return weight_grad_bf16(dY, Nout, X, dW, Nout, Kin, M); }
-    template <typename TY, typename TX>
     int weight_grad_bf16(const TY *dY, int64_t ldy, const TX *X, float *dW, int Nout, int Kin, int64_t m)
     {
         return slab_sum(dW, (int64_t)Nout * Kin, 32, m, [&](int S, int kps) -> int {
@@ -329,11 +359,9 @@ struct Chunk {
         });
     }
 
-    // ----- LayerNorm backward: DX (+)= d x from DXN, the gain's gradient gw += sum over the tokens of dxn * xhat -----
-    Span all() const { return {M, t->DX, t->DXN, t->GP}; }
-
+    // ----- LayerNorm backward over `sp`: dx (+)= d x from dxn, the gain's gradient gw += sum over the tokens of dxn * xhat -----
     template <bool ADD>
-    int ln_backward_f32(const float *x, const float *w, float *gw, const Span &sp)
+    int ln_backward_f32(const float *x, const float *w, float *gw, const Tokens &sp)
     {
         MGPT_LAUNCH((trk::ln_bwd_kernel<ADD>), dim3((unsigned)cdiv64(sp.m, 4)), dim3(256), 0, s, x, w, (const float *)sp.dxn, sp.dx, sp.gp, sp.m, C);
         return slab_sum(gw, C, 16, sp.m, [&](int S, int kps) -> int {
@@ -344,7 +372,7 @@ struct Chunk {
 
     // ... with the gain's column sums fused: one partial per 128 tokens, summed in order
     template <bool ADD>
-    int ln_backward_bf16(const float *x, const float *w, float *gw, const Span &sp)
+    int ln_backward_bf16(const float *x, const float *w, float *gw, const Tokens &sp)
     {
         const int64_t n_part = cdiv64(sp.m, tbk::kLnTok);
         MGPT_REQUIRE(C <= 64 * tbk::kLnMaxJ && (size_t)(n_part * C) <= t->part_elems, MGPT_ERR_UNSUPPORTED, "LayerNorm backward: C=%d, %lld tokens", C, (long long)sp.m);
@@ -354,81 +382,180 @@ struct Chunk {
     }
 
     template <bool ADD>
-    int ln_backward(const float *x, size_t gain) { return ln_backward<ADD>(x, gain, all()); }
-    template <bool ADD>
-    int ln_backward(const float *x, size_t gain, const Span &sp)
+    int ln_backward(const float *x, size_t gain, const Tokens &sp)
     {
         return bf16 ? ln_backward_bf16<ADD>(x, P + gain, G + gain, sp) : ln_backward_f32<ADD>(x, P + gain, G + gain, sp);
     }
 
     // ----- attention, one workgroup per (row, head) -----
-    // fp32 backward: dq | dk | dv of DY into DQKV
-    template <int HS>
-    int attn_backward_f32(int l, const float *qkv, const float *y)
+    // The model's head size and whether site 1 drops, as the kernels' template arguments: launch(hs, dropped, d), hs and dropped
+    // std::integral_constants of HS and DROP, d layer l's mask stream -- trk::Drop() for a DROP = false instance
+    template <class Launch>
+    int with_attn_kernel(int l, Launch launch)
     {
-        const dim3 grid((unsigned)(rows * g->nh));
-        const int64_t plane = M * C;
-        if (drops(SITE_ATTN)) {
-            const trk::Drop d = drop(SITE_ATTN, l);
-            MGPT_LAUNCH((trk::attn_bwd_q_kernel<HS, true>), grid, dim3(256), trk::attn_bwd_q_lds<HS>(), s, qkv, plane, y, t->DY, t->DQKV, t->AST, g->nh, scale, d);
-            MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 0, true>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale, d);
-            MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 1, true>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale, d);
-            return MGPT_OK;
-        }
-        MGPT_LAUNCH(trk::attn_bwd_q_kernel<HS>, grid, dim3(256), trk::attn_bwd_q_lds<HS>(), s, qkv, plane, y, t->DY, t->DQKV, t->AST, g->nh, scale, trk::Drop());
-        MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 0>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale, trk::Drop());
-        MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 1>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale, trk::Drop());
-        return MGPT_OK;
+        using H32 = std::integral_constant<int, 32>;
+        using H64 = std::integral_constant<int, 64>;
+        if (!drops(SITE_ATTN)) return g->hs == 32 ? launch(H32(), std::false_type(), trk::Drop()) : launch(H64(), std::false_type(), trk::Drop());
+        const trk::Drop d = drop(SITE_ATTN, l);
+        return g->hs == 32 ? launch(H32(), std::true_type(), d) : launch(H64(), std::true_type(), d);
     }
 
     // fp32 forward: the inference kernel, or the training instance that masks P
-    template <int HS>
     int attn_forward_f32(int l)
     {
         if (!drops(SITE_ATTN)) return gpt_f32_attention(g, t->QKV[l], t->Y[l], rows, s);
-        MGPT_LAUNCH(trk::attn_fwd_drop_kernel<HS>, dim3((unsigned)(rows * g->nh)), dim3(256), 0, s, (const float *)t->QKV[l], M * C, t->Y[l], g->nh, scale,
-                    drop(SITE_ATTN, l));
-        return MGPT_OK;
+        return with_attn_kernel(l, [&](auto hs, auto, const trk::Drop &d) -> int {
+            MGPT_LAUNCH(trk::attn_fwd_drop_kernel<decltype(hs)::value>, dim3((unsigned)(rows * g->nh)), dim3(256), 0, s, (const float *)t->QKV[l], M * C, t->Y[l],
+                        g->nh, scale, d);
+            return MGPT_OK;
+        });
+    }
+
+    // fp32 backward: dq | dk | dv of DY into DQKV
+    int attn_backward_f32(int l, const float *qkv, const float *y)
+    {
+        return with_attn_kernel(l, [&](auto hs, auto dropped, const trk::Drop &d) -> int {
+            constexpr int HS = decltype(hs)::value;
+            constexpr bool DROP = decltype(dropped)::value;
+            const dim3 grid((unsigned)(rows * g->nh));
+            const int64_t plane = M * C;
+            MGPT_LAUNCH((trk::attn_bwd_q_kernel<HS, DROP>), grid, dim3(256), trk::attn_bwd_q_lds<HS>(), s, qkv, plane, y, t->DY, t->DQKV, t->AST, g->nh, scale, d);
+            MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 0, DROP>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale, d);
+            MGPT_LAUNCH((trk::attn_bwd_kv_kernel<HS, 1, DROP>), grid, dim3(256), trk::attn_bwd_kv_lds<HS>(), s, qkv, plane, t->DY, t->DQKV, t->AST, g->nh, scale, d);
+            return MGPT_OK;
+        });
     }
 
     // bf16 MFMAs: forward (y bf16, statistics fp32) and backward (dq | dk | dv fp32 into DQKV)
-    template <int HS>
     int attn_forward_bf16(int l, const Bf16Layer &v)
     {
-        if (drops(SITE_ATTN)) {
-            MGPT_LAUNCH((tbk::attn_fwd_bf16_kernel<HS, true>), dim3((unsigned)(rows * g->nh)), dim3(256), tbk::attn_fwd_lds<HS>(), s, v.qkv, M * C, v.y, v.stats, g->nh,
-                        scale, drop(SITE_ATTN, l));
+        return with_attn_kernel(l, [&](auto hs, auto dropped, const trk::Drop &d) -> int {
+            constexpr int HS = decltype(hs)::value;
+            MGPT_LAUNCH((tbk::attn_fwd_bf16_kernel<HS, decltype(dropped)::value>), dim3((unsigned)(rows * g->nh)), dim3(256), tbk::attn_fwd_lds<HS>(), s, v.qkv, M * C,
+                        v.y, v.stats, g->nh, scale, d);
             return MGPT_OK;
-        }
-        MGPT_LAUNCH(tbk::attn_fwd_bf16_kernel<HS>, dim3((unsigned)(rows * g->nh)), dim3(256), tbk::attn_fwd_lds<HS>(), s, v.qkv, M * C, v.y, v.stats, g->nh, scale, trk::Drop());
-        return MGPT_OK;
+        });
     }
 
-    template <int HS>
     int attn_backward_bf16(int l, const Bf16Layer &v, const uint16_t *dy)
     {
-        if (drops(SITE_ATTN)) {
-            MGPT_LAUNCH((tbk::attn_bwd_bf16_kernel<HS, true>), dim3((unsigned)(rows * g->nh)), dim3(512), tbk::attn_bwd_lds<HS>(), s, v.qkv, M * C, v.y, dy, v.stats,
-                        t->DQKV, g->nh, scale, drop(SITE_ATTN, l));
+        return with_attn_kernel(l, [&](auto hs, auto dropped, const trk::Drop &d) -> int {
+            constexpr int HS = decltype(hs)::value;
+            MGPT_LAUNCH((tbk::attn_bwd_bf16_kernel<HS, decltype(dropped)::value>), dim3((unsigned)(rows * g->nh)), dim3(512), tbk::attn_bwd_lds<HS>(), s, v.qkv, M * C,
+                        v.y, dy, v.stats, t->DQKV, g->nh, scale, d);
             return MGPT_OK;
-        }
-        MGPT_LAUNCH(tbk::attn_bwd_bf16_kernel<HS>, dim3((unsigned)(rows * g->nh)), dim3(512), tbk::attn_bwd_lds<HS>(), s, v.qkv, M * C, v.y, dy, v.stats, t->DQKV,
-                    g->nh, scale, trk::Drop());
+        });
+    }
+
+    // query 255 of each row against the row's k and v planes, TQ float or bf16 bits: y and dq compact, dk | dv dense into DQKV.  The
+    // kernels write the rows' tokens only: the padding rows of their compact outputs are zeroed (stream-ordered)
+    int zero_pad(void *buf, size_t elem, const Compact &k)
+    {
+        if (k.mc > k.n) MGPT_HIP(hipMemsetAsync(static_cast<char *>(buf) + (size_t)k.n * C * elem, 0, (size_t)(k.mc - k.n) * C * elem, s));
+        return MGPT_OK;
+    }
+    template <typename TQ>
+    int attn_last_forward(const Compact &k, const TQ *q, const TQ *kp, const TQ *vp, TQ *y)
+    {
+        MGPT_TRY((with_attn_kernel(L - 1, [&](auto hs, auto dropped, const trk::Drop &d) -> int {
+            MGPT_LAUNCH((trk::attn_last_fwd_kernel<decltype(hs)::value, TQ, decltype(dropped)::value>), dim3((unsigned)(k.n * g->nh)), dim3(256), 0, s, q, kp, vp, y,
+                        t->AST, g->nh, scale, d);
+            return MGPT_OK;
+        })));
+        return zero_pad(y, sizeof(TQ), k);
+    }
+    template <typename TQ>
+    int attn_last_backward(const Compact &k, const TQ *q, const TQ *kp, const TQ *vp, const TQ *y, const TQ *dy)
+    {
+        MGPT_TRY((with_attn_kernel(L - 1, [&](auto hs, auto dropped, const trk::Drop &d) -> int {
+            MGPT_LAUNCH((trk::attn_last_bwd_kernel<decltype(hs)::value, TQ, decltype(dropped)::value>), dim3((unsigned)(k.n * g->nh)), dim3(256), 0, s, q, kp, vp, y,
+                        dy, (const float *)t->AST, t->DQKV, k.dq, g->nh, scale, d);
+            return MGPT_OK;
+        })));
+        return zero_pad(k.dq, sizeof(float), k);
+    }
+
+    // ----- the steps of a layer that are the same launches over all tokens and over the compact ones -----
+    // fp32: HT = gelu(a)
+    int gelu(int l, const Tokens &tk)
+    {
+        MGPT_LAUNCH(trk::gelu_kernel, dim3(grid_1d(4 * tk.m * C)), dim3(256), 0, s, t->A[l], t->HT, 4 * tk.m * C);
         return MGPT_OK;
     }
 
+    // bf16 MLP half (model.py:85-88,103): xo = xm + dropout(c_proj(gelu(c_fc(ln_2(xm))))), a and gelu(a) kept
+    int mlp_forward_bf16(int l, const Tokens &tk, const float *xm, float *xo)
+    {
+        const LayerOff &lo = g->layers[l];
+        const Bf16Layer v = bf16_layer(t, l, tk.m, C);
+        MGPT_TRY(gpt_f32_layernorm(g, xm, P + lo.ln2, t->XN2[l], tk.m, s));
+        MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_FC>(t->XN2[l], C, P + lo.fc_w, C, tk.m, 4 * C, C, epi_fc(v.a, v.h, 4 * C))));
+        return branch_forward_bf16(SITE_MLP_PROJ, l, tk, v.h, P + lo.proj2_w, 4 * C, xm, xo);
+    }
+
+    // MLP backward (model.py:85-88,103): the tokens' dx = d x_out becomes d x_mid; db = the gradient of c_proj's output (m s dx under dropout).
+    // fp32: HT = gelu(a) of these tokens, recomputed first where `regelu`
+    int mlp_backward_f32(int l, const Tokens &tk, bool regelu)
+    {
+        const LayerOff &lo = g->layers[l];
+        const float *db;
+        MGPT_TRY(branch_grad(SITE_MLP_PROJ, l, tk, &db));
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_GELU_BWD>(db, C, P + lo.proj2_w, 4 * C, t->DH, 4 * C, tk.m, 4 * C, C, t->A[l])));
+        if (regelu) MGPT_TRY(gelu(l, tk));
+        MGPT_TRY(weight_grad(db, C, t->HT, G + lo.proj2_w, C, 4 * C, tk.m));
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DH, 4 * C, P + lo.fc_w, C, tk.dxn, C, tk.m, C, 4 * C)));
+        MGPT_TRY(weight_grad(t->DH, 4 * C, t->XN2[l], G + lo.fc_w, 4 * C, C, tk.m));
+        return ln_backward<true>(t->XM[l], lo.ln2, tk);
+    }
+    // bf16: dx's bf16 rounding is the gradient of the bf16 c_proj output (under dropout db = m s bf16(dx), rounded as it is staged)
+    int mlp_backward_bf16(int l, const Tokens &tk)
+    {
+        const LayerOff &lo = g->layers[l];
+        const Bf16Layer v = bf16_layer(t, l, tk.m, C);
+        const Bf16Grads d = bf16_grads(t);
+        const float *db;
+        MGPT_TRY(branch_grad(SITE_MLP_PROJ, l, tk, &db));
+        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_GELU_BWD>(db, C, P + lo.proj2_w, 4 * C, tk.m, 4 * C, C, epi_gelu_bwd(d.da, v.a, 4 * C))));
+        MGPT_TRY(weight_grad_bf16(db, C, v.h, G + lo.proj2_w, C, 4 * C, tk.m));
+        MGPT_TRY((bf_gemm<uint16_t, true, float, false, tbk::E_F32>(d.da, 4 * C, P + lo.fc_w, C, tk.m, C, 4 * C, epi_f32(tk.dxn, C))));
+        MGPT_TRY(weight_grad_bf16(d.da, 4 * C, t->XN2[l], G + lo.fc_w, 4 * C, C, tk.m));
+        return ln_backward<true>(t->XM[l], lo.ln2, tk);
+    }
+
+    // attention's out-projection backward (model.py:71,102): the tokens' dx = d x_mid; dy = d y, c_proj's weight gradient from y
+    int proj_backward_f32(int l, const Tokens &tk, const float *y, float *dy)
+    {
+        const LayerOff &lo = g->layers[l];
+        const float *db;
+        MGPT_TRY(branch_grad(SITE_ATTN_PROJ, l, tk, &db));
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(db, C, P + lo.proj_w, C, dy, C, tk.m, C, C)));
+        return weight_grad(db, C, y, G + lo.proj_w, C, C, tk.m);
+    }
+    // bf16: d y = bf16(db W_proj), the gradient of the bf16 attention output
+    int proj_backward_bf16(int l, const Tokens &tk, const uint16_t *y, uint16_t *dy)
+    {
+        const LayerOff &lo = g->layers[l];
+        const float *db;
+        MGPT_TRY(branch_grad(SITE_ATTN_PROJ, l, tk, &db));
+        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_B16>(db, C, P + lo.proj_w, C, tk.m, C, C, epi_b16(dy, C))));
+        return weight_grad_bf16(db, C, y, G + lo.proj_w, C, C, tk.m);
+    }
+
+    // ----- a layer on all tokens -----
+    // fp32 forward: the inference kernels
     int layer_forward_f32(int l)
     {
         const LayerOff &lo = g->layers[l];
+        const Tokens tk = all();
         float *x = t->X[l], *xm = t->XM[l], *xo = x_out(l);
         MGPT_TRY(gpt_f32_layernorm(g, x, P + lo.ln1, t->XN1[l], M, s));
         MGPT_TRY(gpt_f32_linear(g, 2, t->XN1[l], P + lo.attn_w, t->QKV[l], M, 3 * C, C, s));
-        MGPT_TRY(g->hs == 32 ? attn_forward_f32<32>(l) : attn_forward_f32<64>(l));
-        MGPT_TRY(branch_forward_f32(SITE_ATTN_PROJ, l, t->Y[l], P + lo.proj_w, C, x, xm));
+        MGPT_TRY(attn_forward_f32(l));
+        MGPT_TRY(branch_forward_f32(SITE_ATTN_PROJ, l, tk, t->Y[l], P + lo.proj_w, C, x, xm));
         MGPT_TRY(gpt_f32_layernorm(g, xm, P + lo.ln2, t->XN2[l], M, s));
         MGPT_TRY(gpt_f32_linear(g, 0, t->XN2[l], P + lo.fc_w, t->A[l], M, 4 * C, C, s));
-        MGPT_LAUNCH(trk::gelu_kernel, dim3(grid_1d(4 * M * C)), dim3(256), 0, s, t->A[l], t->HT, 4 * M * C);
-        return branch_forward_f32(SITE_MLP_PROJ, l, t->HT, P + lo.proj2_w, 4 * C, xm, xo);
+        MGPT_TRY(gelu(l, tk));
+        return branch_forward_f32(SITE_MLP_PROJ, l, tk, t->HT, P + lo.proj2_w, 4 * C, xm, xo);
     }
 
     int layer_forward_bf16(int l)
@@ -438,124 +565,46 @@ struct Chunk {
         float *x = t->X[l], *xm = t->XM[l];
         MGPT_TRY(gpt_f32_layernorm(g, x, P + lo.ln1, t->XN1[l], M, s));
         MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_QKV>(t->XN1[l], C, P + lo.attn_w, C, M, 3 * C, C, epi_qkv(v.qkv, C, g->hs, g->nh, M * C))));
-        MGPT_TRY(g->hs == 32 ? attn_forward_bf16<32>(l, v) : attn_forward_bf16<64>(l, v));
-        MGPT_TRY(branch_forward_bf16(SITE_ATTN_PROJ, l, v.y, P + lo.proj_w, C, x, xm));
-        MGPT_TRY(gpt_f32_layernorm(g, xm, P + lo.ln2, t->XN2[l], M, s));
-        MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_FC>(t->XN2[l], C, P + lo.fc_w, C, M, 4 * C, C, epi_fc(v.a, v.h, 4 * C))));
-        return branch_forward_bf16(SITE_MLP_PROJ, l, v.h, P + lo.proj2_w, 4 * C, xm, x_out(l));
+        MGPT_TRY(attn_forward_bf16(l, v));
+        MGPT_TRY(branch_forward_bf16(SITE_ATTN_PROJ, l, all(), v.y, P + lo.proj_w, C, x, xm));
+        return mlp_forward_bf16(l, all(), xm, x_out(l));
     }
 
-    // head (model.py:178-184), fp32 in both precisions: ln_f, logits = ln_f(x) @ wte^T at every position, cross-entropy
-    int head_forward()
-    {
-        MGPT_TRY(gpt_f32_layernorm(g, t->XF, P + g->off_lnf, t->XNF, M, s));
-        MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(t->XNF, C, P + g->off_wte, C, t->LG, kV, M, kV, C)));
-        MGPT_LAUNCH(trk::ce_kernel, dim3((unsigned)cdiv64(M, 256)), dim3(256), 0, s, t->LG, tg, M, t->cnt, loss_scale, t->DLG, t->NLL);
-        MGPT_LAUNCH(trk::sum_acc_kernel, dim3(1), dim3(256), 0, s, t->NLL, M, t->loss_acc);
-        return MGPT_OK;
-    }
-
-    // d ln_f(x) = dlogits @ wte;  d wte += dlogits^T @ ln_f(x) (the tied lm_head);  ln_f backward starts the residual gradient DX
-    int head_backward()
-    {
-        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DLG, kV, P + g->off_wte, C, t->DXN, C, M, C, kV)));
-        MGPT_TRY(weight_grad(t->DLG, t->XNF, G + g->off_wte, kV, C));
-        return ln_backward<false>(t->XF, g->off_lnf);
-    }
-
+    // backward: the MLP, then attention (model.py:50-71,102), c_attn and ln_1
     int layer_backward_f32(int l)
     {
         const LayerOff &lo = g->layers[l];
-        // MLP (model.py:85-88,103): DX = d x_out, db = the gradient of c_proj's output (m s DX under dropout)
-        const float *db;
-        MGPT_TRY(branch_grad(SITE_MLP_PROJ, l, &db));
-        MGPT_TRY((tr_gemm<true, true, trk::OUT_GELU_BWD>(db, C, P + lo.proj2_w, 4 * C, t->DH, 4 * C, M, 4 * C, C, t->A[l])));
-        MGPT_LAUNCH(trk::gelu_kernel, dim3(grid_1d(4 * M * C)), dim3(256), 0, s, t->A[l], t->HT, 4 * M * C);
-        MGPT_TRY(weight_grad(db, t->HT, G + lo.proj2_w, C, 4 * C));
-        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DH, 4 * C, P + lo.fc_w, C, t->DXN, C, M, C, 4 * C)));
-        MGPT_TRY(weight_grad(t->DH, t->XN2[l], G + lo.fc_w, 4 * C, C));
-        MGPT_TRY(ln_backward<true>(t->XM[l], lo.ln2));
-        // attention (model.py:50-71,102): DX = d x_mid
-        MGPT_TRY(branch_grad(SITE_ATTN_PROJ, l, &db));
-        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(db, C, P + lo.proj_w, C, t->DY, C, M, C, C)));
-        MGPT_TRY(weight_grad(db, t->Y[l], G + lo.proj_w, C, C));
-        MGPT_TRY(g->hs == 32 ? attn_backward_f32<32>(l, t->QKV[l], t->Y[l]) : attn_backward_f32<64>(l, t->QKV[l], t->Y[l]));
+        const Tokens tk = all();
+        MGPT_TRY(mlp_backward_f32(l, tk, true));                    // HT has held every later layer's gelu(a) since: recomputed
+        MGPT_TRY(proj_backward_f32(l, tk, t->Y[l], t->DY));
+        MGPT_TRY(attn_backward_f32(l, t->QKV[l], t->Y[l]));
         MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DQKV, 3 * C, P + lo.attn_w, C, t->DXN, C, M, C, 3 * C)));
-        MGPT_TRY(weight_grad(t->DQKV, t->XN1[l], G + lo.attn_w, 3 * C, C));
-        return ln_backward<true>(t->X[l], lo.ln1);
+        MGPT_TRY(weight_grad(t->DQKV, 3 * C, t->XN1[l], G + lo.attn_w, 3 * C, C, M));
+        return ln_backward<true>(t->X[l], lo.ln1, tk);
     }
 
     int layer_backward_bf16(int l)
     {
         const LayerOff &lo = g->layers[l];
+        const Tokens tk = all();
         const Bf16Layer v = bf16_layer(t, l, M, C);
         const Bf16Grads d = bf16_grads(t);
-        // MLP: DX = d x_out (its bf16 rounding is the gradient of the bf16 c_proj output; under dropout db = m s bf16(DX), rounded as it is staged)
-        const float *db;
-        MGPT_TRY(branch_grad(SITE_MLP_PROJ, l, &db));
-        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_GELU_BWD>(db, C, P + lo.proj2_w, 4 * C, M, 4 * C, C, epi_gelu_bwd(d.da, v.a, 4 * C))));
-        MGPT_TRY(weight_grad_bf16(db, v.h, G + lo.proj2_w, C, 4 * C));
-        MGPT_TRY((bf_gemm<uint16_t, true, float, false, tbk::E_F32>(d.da, 4 * C, P + lo.fc_w, C, M, C, 4 * C, epi_f32(t->DXN, C))));
-        MGPT_TRY(weight_grad_bf16(d.da, t->XN2[l], G + lo.fc_w, 4 * C, C));
-        MGPT_TRY(ln_backward<true>(t->XM[l], lo.ln2));
-        // attention: DX = d x_mid;  d y = bf16(DX W_proj), the gradient of the bf16 attention output
-        MGPT_TRY(branch_grad(SITE_ATTN_PROJ, l, &db));
-        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_B16>(db, C, P + lo.proj_w, C, M, C, C, epi_b16(d.dy, C))));
-        MGPT_TRY(weight_grad_bf16(db, v.y, G + lo.proj_w, C, C));
-        MGPT_TRY(g->hs == 32 ? attn_backward_bf16<32>(l, v, d.dy) : attn_backward_bf16<64>(l, v, d.dy));
+        MGPT_TRY(mlp_backward_bf16(l, tk));
+        MGPT_TRY(proj_backward_bf16(l, tk, v.y, d.dy));
+        MGPT_TRY(attn_backward_bf16(l, v, d.dy));
         MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_F32>(t->DQKV, 3 * C, P + lo.attn_w, C, M, C, 3 * C, epi_f32(t->DXN, C))));
-        MGPT_TRY(weight_grad_bf16(t->DQKV, t->XN1[l], G + lo.attn_w, 3 * C, C));
-        return ln_backward<true>(t->X[l], lo.ln1);
+        MGPT_TRY(weight_grad_bf16(t->DQKV, 3 * C, t->XN1[l], G + lo.attn_w, 3 * C, C, M));
+        return ln_backward<true>(t->X[l], lo.ln1, tk);
     }
 
     int layer_forward(int l) { return bf16 ? layer_forward_bf16(l) : layer_forward_f32(l); }
     int layer_backward(int l) { return bf16 ? layer_backward_bf16(l) : layer_backward_f32(l); }
 
-    // ----- the last layer and the head on the compact matrix of the rows' last tokens (mgpt_gpt_forward_backward_rows, _rows_drop) -----
-    // Of the last layer only ln_1 and the K | V projection run on all tokens; the query, attention's output, c_proj, the MLP, ln_f, the head
-    // and the cross-entropy run on token 255 of each row.  Backward: the residual gradient is non-zero at token 255 only, d K and d V are
-    // dense, so c_attn's K | V columns and ln_1 run over all tokens and everything else on the compact matrix.
+    // ----- the last layer with its query, attention output, c_proj and MLP on the compact tokens (the rows call) -----
+    // Of the last layer only ln_1 and the K | V projection run on all tokens.  Backward: the residual gradient is non-zero at token 255 only,
+    // d K and d V are dense, so c_attn's K | V columns and ln_1 run over all tokens and everything else on the compact matrix.
     // Under dropout the compact tokens draw the general call's masks at token / query 255: site 1 through drop(SITE_ATTN, l) (the kernels
-    // add query 255's offset), sites 2 and 3 through drop_last, whose base is token 255 of the chunk's first row (the mask's rows lie
-    // 256 C elements apart, the compact matrix's C).
-    Compact compact() const { return compact_of(t, L - 1, rows, bf16, C); }
-
-    trk::Drop drop_last(int site) const
-    {
-        trk::Drop d = drop(site, L - 1);
-        d.base += (uint64_t)(kT - 1) * C;
-        return d;
-    }
-    // fp32: out = x + m s (A W^T) on the compact matrix, the branch output through k.db
-    int branch_forward_last_f32(int site, const Compact &k, const float *A, const float *W, int K, const float *x, float *out)
-    {
-        if (!drops(site)) return tr_gemm<true, false, trk::OUT_RESID>(A, K, W, K, out, C, k.mc, C, K, x);
-        MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(A, K, W, K, k.db, C, k.mc, C, K)));
-        MGPT_LAUNCH(trk::drop_resid_last_kernel, dim3(grid_1d((int64_t)k.mc * C / 4)), dim3(256), 0, s, x, (const float *)k.db, out, k.mc, C, drop_last(site));
-        return MGPT_OK;
-    }
-    // bf16: out = x + bf16(m s bf16(A W^T)) in the GEMM's epilogue (the padding rows stay zero: x and A are zero there)
-    int branch_forward_last_bf16(int site, const Compact &k, const uint16_t *A, const float *W, int K, const float *x, float *out)
-    {
-        tbk::Epi e = epi_resid(out, x, C);
-        if (!drops(site)) return bf_gemm<uint16_t, true, float, true, tbk::E_RESID>(A, K, W, K, k.mc, C, K, e);
-        e.drop = drop_last(site);
-        e.plane = (int64_t)kT * C;
-        return bf_gemm<uint16_t, true, float, true, tbk::E_RESID_DROP_LAST>(A, K, W, K, k.mc, C, K, e);
-    }
-    // the gradient that enters a compact branch's c_proj: the span's dx, or m s dx in k.db (bf16: the input rounded first, as branch_grad;
-    // zero padding rows stay zero)
-    int branch_grad_last(int site, const Compact &k, const float **dx)
-    {
-        *dx = k.span.dx;
-        if (!drops(site)) return MGPT_OK;
-        *dx = k.db;
-        const dim3 grid(grid_1d((int64_t)k.mc * C / 4));
-        if (bf16) MGPT_LAUNCH(trk::drop_scale_last_kernel<true>, grid, dim3(256), 0, s, (const float *)k.span.dx, k.db, k.mc, C, drop_last(site));
-        else MGPT_LAUNCH(trk::drop_scale_last_kernel<false>, grid, dim3(256), 0, s, (const float *)k.span.dx, k.db, k.mc, C, drop_last(site));
-        return MGPT_OK;
-    }
-
+    // add query 255's offset), sites 2 and 3 through drop(site, l, k.tok).
     int gather_last(const float *src, float *dst, const Compact &k)
     {
         MGPT_LAUNCH(trk::gather_last_kernel, dim3(grid_1d((int64_t)k.mc * C)), dim3(256), 0, s, src, dst, k.n, k.mc, C);
@@ -566,41 +615,8 @@ struct Chunk {
         MGPT_LAUNCH(trk::scatter_last_add_kernel, dim3(grid_1d((int64_t)k.n * C)), dim3(256), 0, s, src, dst, k.n, C);
         return MGPT_OK;
     }
-    // the attention kernels write the rows' tokens only: the padding rows of their compact outputs are zeroed (stream-ordered)
-    int zero_pad(void *buf, size_t elem, const Compact &k)
-    {
-        if (k.mc > k.n) MGPT_HIP(hipMemsetAsync(static_cast<char *>(buf) + (size_t)k.n * C * elem, 0, (size_t)(k.mc - k.n) * C * elem, s));
-        return MGPT_OK;
-    }
 
-    template <typename TQ>
-    int attn_last_forward(const Compact &k, const TQ *q, const TQ *kp, const TQ *vp, TQ *y)
-    {
-        const dim3 grid((unsigned)(k.n * g->nh));
-        if (drops(SITE_ATTN)) {
-            const trk::Drop d = drop(SITE_ATTN, L - 1);
-            if (g->hs == 32) MGPT_LAUNCH((trk::attn_last_fwd_kernel<32, TQ, true>), grid, dim3(256), 0, s, q, kp, vp, y, t->AST, g->nh, scale, d);
-            else MGPT_LAUNCH((trk::attn_last_fwd_kernel<64, TQ, true>), grid, dim3(256), 0, s, q, kp, vp, y, t->AST, g->nh, scale, d);
-        } else if (g->hs == 32) MGPT_LAUNCH((trk::attn_last_fwd_kernel<32, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, t->AST, g->nh, scale, trk::Drop());
-        else MGPT_LAUNCH((trk::attn_last_fwd_kernel<64, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, t->AST, g->nh, scale, trk::Drop());
-        return zero_pad(y, sizeof(TQ), k);
-    }
-    template <typename TQ>
-    int attn_last_backward(const Compact &k, const TQ *q, const TQ *kp, const TQ *vp, const TQ *y, const TQ *dy)
-    {
-        const dim3 grid((unsigned)(k.n * g->nh));
-        const float *st = t->AST;
-        if (drops(SITE_ATTN)) {
-            const trk::Drop d = drop(SITE_ATTN, L - 1);
-            if (g->hs == 32) MGPT_LAUNCH((trk::attn_last_bwd_kernel<32, TQ, true>), grid, dim3(256), 0, s, q, kp, vp, y, dy, st, t->DQKV, k.dq, g->nh, scale, d);
-            else MGPT_LAUNCH((trk::attn_last_bwd_kernel<64, TQ, true>), grid, dim3(256), 0, s, q, kp, vp, y, dy, st, t->DQKV, k.dq, g->nh, scale, d);
-        } else if (g->hs == 32)
-            MGPT_LAUNCH((trk::attn_last_bwd_kernel<32, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, dy, st, t->DQKV, k.dq, g->nh, scale, trk::Drop());
-        else
-            MGPT_LAUNCH((trk::attn_last_bwd_kernel<64, TQ>), grid, dim3(256), 0, s, q, kp, vp, y, dy, st, t->DQKV, k.dq, g->nh, scale, trk::Drop());
-        return zero_pad(k.dq, sizeof(float), k);
-    }
-
+    // fp32 forward: gemm_tr_kernel on the compact tokens
     int layer_forward_last_f32()
     {
         const int l = L - 1;
@@ -614,11 +630,11 @@ struct Chunk {
         MGPT_TRY(gather_last(t->X[l], k.x, k));
         MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(k.xn1, C, P + lo.attn_w, C, k.q, C, mc, C, C)));
         MGPT_TRY(attn_last_forward<float>(k, k.q, kp, vp, k.y));
-        MGPT_TRY(branch_forward_last_f32(SITE_ATTN_PROJ, k, k.y, P + lo.proj_w, C, k.x, t->XM[l]));
+        MGPT_TRY(branch_forward_f32(SITE_ATTN_PROJ, l, k.tok, k.y, P + lo.proj_w, C, k.x, t->XM[l]));
         MGPT_TRY(gpt_f32_layernorm(g, t->XM[l], P + lo.ln2, t->XN2[l], mc, s));
         MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(t->XN2[l], C, P + lo.fc_w, C, t->A[l], 4 * C, mc, 4 * C, C)));
-        MGPT_LAUNCH(trk::gelu_kernel, dim3(grid_1d(4 * mc * C)), dim3(256), 0, s, t->A[l], t->HT, 4 * mc * C);
-        return branch_forward_last_f32(SITE_MLP_PROJ, k, t->HT, P + lo.proj2_w, 4 * C, t->XM[l], t->XF);
+        MGPT_TRY(gelu(l, k.tok));
+        return branch_forward_f32(SITE_MLP_PROJ, l, k.tok, t->HT, P + lo.proj2_w, 4 * C, t->XM[l], t->XF);
     }
 
     int layer_forward_last_bf16()
@@ -626,71 +642,39 @@ struct Chunk {
         const int l = L - 1;
         const LayerOff &lo = g->layers[l];
         const Compact k = compact();
-        const int64_t mc = k.mc;
-        const Bf16Layer v = bf16_layer(t, l, mc, C);                // y, a, gelu(a) of the compact tokens; v.qkv: the compact q
+        const Bf16Layer v = bf16_layer(t, l, k.mc, C);              // y, a, gelu(a) of the compact tokens; v.qkv: the compact q
         uint16_t *kp = v.qkv + M * C, *vp = kp + M * C;             // the general path's k and v planes
         MGPT_TRY(gpt_f32_layernorm(g, t->X[l], P + lo.ln1, t->XN1[l], M, s));
         MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_QKV>(t->XN1[l], C, P + lo.attn_w + (size_t)C * C, C, M, 2 * C, C, epi_qkv(kp, C, g->hs, g->nh, M * C))));
         MGPT_TRY(gather_last(t->XN1[l], k.xn1, k));
         MGPT_TRY(gather_last(t->X[l], k.x, k));
-        MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_B16>(k.xn1, C, P + lo.attn_w, C, mc, C, C, epi_b16(v.qkv, C))));
+        MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_B16>(k.xn1, C, P + lo.attn_w, C, k.mc, C, C, epi_b16(v.qkv, C))));
         MGPT_TRY(attn_last_forward<uint16_t>(k, v.qkv, kp, vp, v.y));
-        MGPT_TRY(branch_forward_last_bf16(SITE_ATTN_PROJ, k, v.y, P + lo.proj_w, C, k.x, t->XM[l]));
-        MGPT_TRY(gpt_f32_layernorm(g, t->XM[l], P + lo.ln2, t->XN2[l], mc, s));
-        MGPT_TRY((bf_gemm<float, true, float, true, tbk::E_FC>(t->XN2[l], C, P + lo.fc_w, C, mc, 4 * C, C, epi_fc(v.a, v.h, 4 * C))));
-        return branch_forward_last_bf16(SITE_MLP_PROJ, k, v.h, P + lo.proj2_w, 4 * C, t->XM[l], t->XF);
-    }
-
-    // ln_f, logits and cross-entropy of the compact tokens; the normaliser call_rows is the row count of the WHOLE call
-    int head_forward_rows(const int32_t *labels, int call_rows)
-    {
-        const Compact k = compact();
-        MGPT_TRY(gpt_f32_layernorm(g, t->XF, P + g->off_lnf, t->XNF, k.mc, s));
-        MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(t->XNF, C, P + g->off_wte, C, t->LG, kV, k.mc, kV, C)));
-        MGPT_LAUNCH(trk::ce_rows_kernel, dim3((unsigned)cdiv(k.mc, 256)), dim3(256), 0, s, (const float *)t->LG, labels, k.n, k.mc, loss_scale / (float)call_rows,
-                    t->DLG, t->NLL);
-        MGPT_LAUNCH(trk::sum_acc_kernel, dim3(1), dim3(256), 0, s, t->NLL, (int64_t)k.mc, t->loss_acc);
-        return MGPT_OK;
-    }
-
-    // ... and their backward: the compact residual gradient starts in the span's dx
-    int head_backward_rows()
-    {
-        const Compact k = compact();
-        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DLG, kV, P + g->off_wte, C, k.span.dxn, C, k.mc, C, kV)));
-        MGPT_TRY(weight_grad(t->DLG, kV, t->XNF, G + g->off_wte, kV, C, k.mc));
-        return ln_backward<false>(t->XF, g->off_lnf, k.span);
+        MGPT_TRY(branch_forward_bf16(SITE_ATTN_PROJ, l, k.tok, v.y, P + lo.proj_w, C, k.x, t->XM[l]));
+        return mlp_forward_bf16(l, k.tok, t->XM[l], t->XF);
     }
 
     // the tail both precisions share: d ln_1(x) of token 255 joins DXN, ln_1 backward over all tokens, d x_mid of token 255 joins DX
     int layer_backward_last_tail(const Compact &k)
     {
         MGPT_TRY(scatter_last_add(k.dxn1, t->DXN, k));
-        MGPT_TRY(ln_backward<false>(t->X[L - 1], g->layers[L - 1].ln1));
-        return scatter_last_add(k.span.dx, t->DX, k);
+        MGPT_TRY(ln_backward<false>(t->X[L - 1], g->layers[L - 1].ln1, all()));
+        return scatter_last_add(k.tok.dx, t->DX, k);
     }
 
+    // backward: the MLP and attention of query 255 -- d y, then d q (compact) and d k | d v (dense); c_attn: the K | V columns (from row kv
+    // of its weight on) over all tokens, the Q rows from the compact tokens
     int layer_backward_last_f32()
     {
         const int l = L - 1;
         const LayerOff &lo = g->layers[l];
         const Compact k = compact();
         const int64_t mc = k.mc;
-        const float *db, *kp = t->QKV[l] + M * C, *vp = kp + M * C;
-        const size_t kv = (size_t)C * C;                            // c_attn's K | V rows start here
-        // MLP; HT still holds gelu(a) of the compact tokens (no layer ran after this one's forward); db = d x_out, or m s d x_out
-        MGPT_TRY(branch_grad_last(SITE_MLP_PROJ, k, &db));
-        MGPT_TRY((tr_gemm<true, true, trk::OUT_GELU_BWD>(db, C, P + lo.proj2_w, 4 * C, t->DH, 4 * C, mc, 4 * C, C, t->A[l])));
-        MGPT_TRY(weight_grad(db, C, t->HT, G + lo.proj2_w, C, 4 * C, mc));
-        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DH, 4 * C, P + lo.fc_w, C, k.span.dxn, C, mc, C, 4 * C)));
-        MGPT_TRY(weight_grad(t->DH, 4 * C, t->XN2[l], G + lo.fc_w, 4 * C, C, mc));
-        MGPT_TRY(ln_backward<true>(t->XM[l], lo.ln2, k.span));
-        // attention of query 255: d y, then d q (compact) and d k | d v (dense)
-        MGPT_TRY(branch_grad_last(SITE_ATTN_PROJ, k, &db));
-        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(db, C, P + lo.proj_w, C, k.dy, C, mc, C, C)));
-        MGPT_TRY(weight_grad(db, C, k.y, G + lo.proj_w, C, C, mc));
+        const float *kp = t->QKV[l] + M * C, *vp = kp + M * C;
+        const size_t kv = (size_t)C * C;
+        MGPT_TRY(mlp_backward_f32(l, k.tok, false));                // HT still holds gelu(a) of the compact tokens: no layer ran after this one's forward
+        MGPT_TRY(proj_backward_f32(l, k.tok, k.y, k.dy));
         MGPT_TRY(attn_last_backward<float>(k, k.q, kp, vp, k.y, k.dy));
-        // c_attn: the K | V columns over all tokens, the Q rows from the compact tokens
         MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DQKV + C, 3 * C, P + lo.attn_w + kv, C, t->DXN, C, M, C, 2 * C)));
         MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(k.dq, C, P + lo.attn_w, C, k.dxn1, C, mc, C, C)));
         MGPT_TRY(weight_grad(t->DQKV + C, 3 * C, t->XN1[l], G + lo.attn_w + kv, 2 * C, C, M));
@@ -705,19 +689,11 @@ struct Chunk {
         const Compact k = compact();
         const int64_t mc = k.mc;
         const Bf16Layer v = bf16_layer(t, l, mc, C);
-        const Bf16Grads d = bf16_grads(t);                          // d.dy = k.dy's slot, d.da = DH
+        const Bf16Grads d = bf16_grads(t);                          // d.dy = k.dy's slot
         const uint16_t *kp = v.qkv + M * C, *vp = kp + M * C;
-        const float *db;
         const size_t kv = (size_t)C * C;
-        MGPT_TRY(branch_grad_last(SITE_MLP_PROJ, k, &db));
-        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_GELU_BWD>(db, C, P + lo.proj2_w, 4 * C, mc, 4 * C, C, epi_gelu_bwd(d.da, v.a, 4 * C))));
-        MGPT_TRY(weight_grad_bf16(db, C, v.h, G + lo.proj2_w, C, 4 * C, mc));
-        MGPT_TRY((bf_gemm<uint16_t, true, float, false, tbk::E_F32>(d.da, 4 * C, P + lo.fc_w, C, mc, C, 4 * C, epi_f32(k.span.dxn, C))));
-        MGPT_TRY(weight_grad_bf16(d.da, 4 * C, t->XN2[l], G + lo.fc_w, 4 * C, C, mc));
-        MGPT_TRY(ln_backward<true>(t->XM[l], lo.ln2, k.span));
-        MGPT_TRY(branch_grad_last(SITE_ATTN_PROJ, k, &db));
-        MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_B16>(db, C, P + lo.proj_w, C, mc, C, C, epi_b16(d.dy, C))));
-        MGPT_TRY(weight_grad_bf16(db, C, v.y, G + lo.proj_w, C, C, mc));
+        MGPT_TRY(mlp_backward_bf16(l, k.tok));
+        MGPT_TRY(proj_backward_bf16(l, k.tok, v.y, d.dy));
         MGPT_TRY(attn_last_backward<uint16_t>(k, v.qkv, kp, vp, v.y, d.dy));
         MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_F32>(t->DQKV + C, 3 * C, P + lo.attn_w + kv, C, M, C, 2 * C, epi_f32(t->DXN, C))));
         MGPT_TRY((bf_gemm<float, true, float, false, tbk::E_F32>(k.dq, C, P + lo.attn_w, C, mc, C, C, epi_f32(k.dxn1, C))));
@@ -729,57 +705,77 @@ struct Chunk {
     int layer_forward_last() { return bf16 ? layer_forward_last_bf16() : layer_forward_last_f32(); }
     int layer_backward_last() { return bf16 ? layer_backward_last_bf16() : layer_backward_last_f32(); }
 
+    // ----- head (model.py:178-184), fp32 in both precisions: ln_f, logits = ln_f(x) @ wte^T, the caller's cross-entropy launch, the loss sum -----
+    template <class CrossEntropy>
+    int head_forward(const Tokens &tk, CrossEntropy cross_entropy)
+    {
+        MGPT_TRY(gpt_f32_layernorm(g, t->XF, P + g->off_lnf, t->XNF, tk.m, s));
+        MGPT_TRY((tr_gemm<true, false, trk::OUT_STORE>(t->XNF, C, P + g->off_wte, C, t->LG, kV, tk.m, kV, C)));
+        MGPT_TRY(cross_entropy());
+        MGPT_LAUNCH(trk::sum_acc_kernel, dim3(1), dim3(256), 0, s, t->NLL, tk.m, t->loss_acc);
+        return MGPT_OK;
+    }
+    // at every position against the call's target count (t->cnt), and of the compact tokens against call_rows, the row count of the WHOLE call
+    int ce_targets()
+    {
+        MGPT_LAUNCH(trk::ce_kernel, dim3((unsigned)cdiv64(M, 256)), dim3(256), 0, s, t->LG, tg, M, t->cnt, loss_scale, t->DLG, t->NLL);
+        return MGPT_OK;
+    }
+    int ce_rows(const Compact &k)
+    {
+        MGPT_LAUNCH(trk::ce_rows_kernel, dim3((unsigned)cdiv(k.mc, 256)), dim3(256), 0, s, (const float *)t->LG, tg, k.n, k.mc, loss_scale / (float)call_rows,
+                    t->DLG, t->NLL);
+        return MGPT_OK;
+    }
+
+    // d ln_f(x) = dlogits @ wte;  d wte += dlogits^T @ ln_f(x) (the tied lm_head);  ln_f backward starts the tokens' residual gradient dx
+    int head_backward(const Tokens &tk)
+    {
+        MGPT_TRY((tr_gemm<true, true, trk::OUT_STORE>(t->DLG, kV, P + g->off_wte, C, tk.dxn, C, tk.m, C, kV)));
+        MGPT_TRY(weight_grad(t->DLG, kV, t->XNF, G + g->off_wte, kV, C, tk.m));
+        return ln_backward<false>(t->XF, g->off_lnf, tk);
+    }
+
     // embedding (model.py:171-175), fp32 in both precisions: d wpe[t] += sum over rows, d wte[id] += sum over the tokens with that id
     // under dropout X[0] = m s (wte + wpe) (model.py:175) and the sums take m s DX (in DXN, free after the last LayerNorm backward)
     int embed()
     {
         MGPT_TRY(gpt_f32_embed(g, tok, t->X[0], M, s));
-        return drops(SITE_EMBED) ? drop_scale(SITE_EMBED, 0, t->X[0], t->X[0]) : MGPT_OK;
+        return drops(SITE_EMBED) ? drop_scale(SITE_EMBED, 0, all(), t->X[0], t->X[0]) : MGPT_OK;
     }
 
     int embedding_backward()
     {
         const float *dx = t->DX;
         if (drops(SITE_EMBED)) {
-            MGPT_TRY(drop_scale(SITE_EMBED, 0, t->DX, t->DXN));
+            MGPT_TRY(drop_scale(SITE_EMBED, 0, all(), t->DX, t->DXN));
             dx = t->DXN;
         }
         MGPT_LAUNCH(trk::wpe_bwd_kernel, dim3((unsigned)cdiv64((int64_t)kT * C, 256)), dim3(256), 0, s, dx, rows, C, G + g->off_wpe);
-        return slab_sum(G + g->off_wte, (int64_t)kV * C, 16, [&](int S, int kps) -> int {
+        return slab_sum(G + g->off_wte, (int64_t)kV * C, 16, M, [&](int S, int kps) -> int {
             MGPT_LAUNCH(trk::wte_bwd_part_kernel, dim3(kV, (unsigned)S), dim3(256), 0, s, tok, dx, M, C, kps, t->part);
             return MGPT_OK;
         });
     }
 };
 
-// one chunk of rows: forward with saved activations, cross-entropy against the call's target count, backward into t->grads
-int chunk_fwd_bwd(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows, const int32_t *tg, float loss_scale, int precision, const DropCfg &dc,
-                  hipStream_t s)
+// One chunk of rows: forward with saved activations, cross-entropy against the call's normaliser, backward into t->grads.  The rows call
+// (c.call_rows > 0) runs the last layer and the head on the compact tokens; the layers below it are the general call's launches, masks
+// included.  Slot lifetimes there: the dense fp32 forward's branch outputs pass through DY before the compact gradients live there, and
+// branch_grad and embedding_backward fill DXN after layer_backward_last_tail has consumed it.
+int chunk_fwd_bwd(Chunk &c)
 {
-    Chunk c = {g, t, tok, tg, rows, loss_scale, precision == MGPT_PREC_BF16, s, dc};
+    const bool last = c.call_rows > 0;
+    const int dense = last ? c.L - 1 : c.L;
+    const Compact k = c.compact();
+    const Tokens head = last ? k.tok : c.all();
     MGPT_TRY(c.embed());
-    for (int l = 0; l < g->L; l++) MGPT_TRY(c.layer_forward(l));
-    MGPT_TRY(c.head_forward());
-    MGPT_TRY(c.head_backward());
-    for (int l = g->L - 1; l >= 0; l--) MGPT_TRY(c.layer_backward(l));
-    return c.embedding_backward();
-}
-
-// one chunk of rows of mgpt_gpt_forward_backward_rows: the layers below the last run chunk_fwd_bwd's launches, the last layer and the head
-// the compact ones; call_rows normalises the cross-entropy.  Under dropout (dc) the dense launches draw their masks as chunk_fwd_bwd's do.
-// Slot lifetimes: the dense fp32 forward's branch outputs pass through DY before the compact gradients live there, and branch_grad and
-// embedding_backward fill DXN after layer_backward_last_tail has consumed it.
-int chunk_fwd_bwd_rows(mgpt_gpt *g, TrainState *t, const uint8_t *tok, int rows, const int32_t *labels, int call_rows, float loss_scale, int precision,
-                       const DropCfg &dc, hipStream_t s)
-{
-    Chunk c = {g, t, tok, nullptr, rows, loss_scale, precision == MGPT_PREC_BF16, s, dc};
-    MGPT_TRY(c.embed());
-    for (int l = 0; l + 1 < g->L; l++) MGPT_TRY(c.layer_forward(l));
-    MGPT_TRY(c.layer_forward_last());
-    MGPT_TRY(c.head_forward_rows(labels, call_rows));
-    MGPT_TRY(c.head_backward_rows());
-    MGPT_TRY(c.layer_backward_last());
-    for (int l = g->L - 2; l >= 0; l--) MGPT_TRY(c.layer_backward(l));
+    for (int l = 0; l < dense; l++) MGPT_TRY(c.layer_forward(l));
+    if (last) MGPT_TRY(c.layer_forward_last());
+    MGPT_TRY(c.head_forward(head, [&]() -> int { return last ? c.ce_rows(k) : c.ce_targets(); }));
+    MGPT_TRY(c.head_backward(head));
+    if (last) MGPT_TRY(c.layer_backward_last());
+    for (int l = dense - 1; l >= 0; l--) MGPT_TRY(c.layer_backward(l));
     return c.embedding_backward();
 }
 
@@ -797,6 +793,40 @@ int require_train(mgpt_gpt *g)
 {
     MGPT_REQUIRE(g, MGPT_ERR_ARG, "NULL argument");
     MGPT_REQUIRE(g->train, MGPT_ERR_STATE, "no training workspace: mgpt_gpt_train_alloc first");
+    return MGPT_OK;
+}
+
+// A micro-step call, general (call_rows = 0: d_aim the targets, 256 per row) or on rows (call_rows = rows: d_aim the labels, one per row).
+// The checks both calls make, and the call's dropout; a call's own checks follow
+int train_call_check(mgpt_gpt *g, const uint8_t *d_tokens, const int32_t *d_aim, int rows, int precision, float p, uint64_t seed, uint64_t step, int sites,
+                     DropCfg *dc)
+{
+    MGPT_REQUIRE(p >= 0.f && p < 1.f, MGPT_ERR_ARG, "dropout p=%g: a probability in [0, 1)", (double)p);
+    MGPT_REQUIRE(sites >= 0 && sites <= 15, MGPT_ERR_ARG, "dropout sites=%d: a mask of the four sites (15 = all, model.py's behaviour)", sites);
+    MGPT_TRY(require_train(g));
+    MGPT_REQUIRE(d_tokens && d_aim, MGPT_ERR_ARG, "NULL argument");
+    MGPT_REQUIRE(rows > 0, MGPT_ERR_ARG, "rows=%d", rows);
+    MGPT_REQUIRE(!g->has_bias, MGPT_ERR_UNSUPPORTED, "training supports bias = False checkpoints only (the released configs)");
+    MGPT_REQUIRE(precision == MGPT_PREC_F32 || precision == MGPT_PREC_BF16, MGPT_ERR_UNSUPPORTED,
+                 "training precision %d: MGPT_PREC_F32 (exact fp32) or MGPT_PREC_BF16 (bf16 mixed precision)", precision);
+    MGPT_REQUIRE(ts(g)->max_rows > 0, MGPT_ERR_STATE, "the training workspace holds no activation memory (a re-size failed): mgpt_gpt_train_alloc again");
+    *dc = drop_cfg(p, seed, step, sites);
+    MGPT_REQUIRE(dc->thr == 0 || sites == 0 || g->C % 4 == 0, MGPT_ERR_UNSUPPORTED, "dropout masks come four elements to a hash: n_embd = %d is no multiple of 4", g->C);
+    return MGPT_OK;
+}
+
+// ... and its chunks of at most max_rows rows into a zeroed loss sum: the masks are keyed by the row of the call, row0 + the chunk's first
+int train_call_chunks(mgpt_gpt *g, const uint8_t *d_tokens, const int32_t *d_aim, int rows, int call_rows, float loss_scale, int precision, DropCfg dc,
+                      uint64_t row0, hipStream_t s)
+{
+    TrainState *t = ts(g);
+    MGPT_HIP(hipMemsetAsync(t->loss_acc, 0, sizeof(double), s));
+    for (int r0 = 0; r0 < rows; r0 += t->max_rows) {
+        dc.first_row = row0 + (uint64_t)r0;
+        Chunk c = {g, t, d_tokens + (size_t)r0 * kT, d_aim + (size_t)r0 * (call_rows > 0 ? 1 : kT), std::min(t->max_rows, rows - r0), call_rows, loss_scale,
+                   precision == MGPT_PREC_BF16, s, dc};
+        MGPT_TRY(chunk_fwd_bwd(c));
+    }
     return MGPT_OK;
 }
 
@@ -909,17 +939,10 @@ extern "C" int mgpt_gpt_forward_backward_drop(mgpt_gpt *g, const uint8_t *d_toke
                                               float *d_loss, int precision, float p, uint64_t seed, uint64_t step, uint64_t row0, int sites,
                                               void *stream)
 {
-    MGPT_REQUIRE(p >= 0.f && p < 1.f, MGPT_ERR_ARG, "dropout p=%g: a probability in [0, 1)", (double)p);
-    MGPT_REQUIRE(sites >= 0 && sites <= 15, MGPT_ERR_ARG, "dropout sites=%d: a mask of the four sites (15 = all, model.py's behaviour)", sites);
-    MGPT_TRY(require_train(g));
-    MGPT_REQUIRE(d_tokens && d_targets, MGPT_ERR_ARG, "NULL argument");
-    MGPT_REQUIRE(rows > 0, MGPT_ERR_ARG, "rows=%d", rows);
+    DropCfg dc;
+    MGPT_TRY(train_call_check(g, d_tokens, d_targets, rows, precision, p, seed, step, sites, &dc));
     MGPT_REQUIRE(T == kT, MGPT_ERR_ARG, "training takes rows of T = 256 tokens, got T = %d", T);
-    MGPT_REQUIRE(!g->has_bias, MGPT_ERR_UNSUPPORTED, "training supports bias = False checkpoints only (the released configs)");
-    MGPT_REQUIRE(precision == MGPT_PREC_F32 || precision == MGPT_PREC_BF16, MGPT_ERR_UNSUPPORTED,
-                 "training precision %d: MGPT_PREC_F32 (exact fp32) or MGPT_PREC_BF16 (bf16 mixed precision)", precision);
     TrainState *t = ts(g);
-    MGPT_REQUIRE(t->max_rows > 0, MGPT_ERR_STATE, "the training workspace holds no activation memory (a re-size failed): mgpt_gpt_train_alloc again");
     hipStream_t s = (hipStream_t)stream;
     // the cross-entropy normaliser is the targeted-position count of the WHOLE call (F.cross_entropy's mean over the call's tokens)
     MGPT_LAUNCH(trk::count_targets_kernel, dim3(1), dim3(1024), 0, s, d_targets, (int64_t)rows * kT, t->cnt);
@@ -927,16 +950,7 @@ extern "C" int mgpt_gpt_forward_backward_drop(mgpt_gpt *g, const uint8_t *d_toke
     MGPT_HIP(hipStreamSynchronize(s));
     MGPT_REQUIRE(t->h_cnt[1] == 0, MGPT_ERR_ARG, "targets must lie in [-1, 67): -1 is ignored, 0 .. 66 are vocabulary ids");
     MGPT_REQUIRE(t->h_cnt[0] > 0, MGPT_ERR_ARG, "no targeted position in the call (every target is -1): the mean cross-entropy is undefined");
-    MGPT_HIP(hipMemsetAsync(t->loss_acc, 0, sizeof(double), s));
-    DropCfg dc = drop_cfg(p, seed, step, sites);
-    MGPT_REQUIRE(dc.thr == 0 || sites == 0 || g->C % 4 == 0, MGPT_ERR_UNSUPPORTED, "dropout masks come four elements to a hash: n_embd = %d is no multiple of 4", g->C);
-    for (int r0 = 0; r0 < rows; r0 += t->max_rows) {
-        const int n = std::min(t->max_rows, rows - r0);
-        const uint8_t *tk = d_tokens + (size_t)r0 * kT;
-        const int32_t *tg = d_targets + (size_t)r0 * kT;
-        dc.first_row = row0 + (uint64_t)r0;
-        MGPT_TRY(chunk_fwd_bwd(g, t, tk, n, tg, loss_scale, precision, dc, s));
-    }
+    MGPT_TRY(train_call_chunks(g, d_tokens, d_targets, rows, 0, loss_scale, precision, dc, row0, s));
     if (d_loss) MGPT_LAUNCH(trk::loss_final_kernel, dim3(1), dim3(64), 0, s, (const double *)t->loss_acc, t->cnt, d_loss);
     return MGPT_OK;
 }
@@ -951,29 +965,13 @@ extern "C" int mgpt_gpt_forward_backward_rows_drop(mgpt_gpt *g, const uint8_t *d
                                                    float *d_loss, int precision, float p, uint64_t seed, uint64_t step, uint64_t row0, int sites,
                                                    void *stream)
 {
-    MGPT_REQUIRE(p >= 0.f && p < 1.f, MGPT_ERR_ARG, "dropout p=%g: a probability in [0, 1)", (double)p);
-    MGPT_REQUIRE(sites >= 0 && sites <= 15, MGPT_ERR_ARG, "dropout sites=%d: a mask of the four sites (15 = all, model.py's behaviour)", sites);
-    MGPT_TRY(require_train(g));
-    MGPT_REQUIRE(d_tokens && d_labels, MGPT_ERR_ARG, "NULL argument");
-    MGPT_REQUIRE(rows > 0, MGPT_ERR_ARG, "rows=%d", rows);
+    DropCfg dc;
+    MGPT_TRY(train_call_check(g, d_tokens, d_labels, rows, precision, p, seed, step, sites, &dc));
     MGPT_REQUIRE(std::isfinite(loss_scale), MGPT_ERR_ARG, "loss_scale=%g: a finite factor", (double)loss_scale);
-    MGPT_REQUIRE(!g->has_bias, MGPT_ERR_UNSUPPORTED, "training supports bias = False checkpoints only (the released configs)");
-    MGPT_REQUIRE(precision == MGPT_PREC_F32 || precision == MGPT_PREC_BF16, MGPT_ERR_UNSUPPORTED,
-                 "training precision %d: MGPT_PREC_F32 (exact fp32) or MGPT_PREC_BF16 (bf16 mixed precision)", precision);
-    TrainState *t = ts(g);
-    MGPT_REQUIRE(t->max_rows > 0, MGPT_ERR_STATE, "the training workspace holds no activation memory (a re-size failed): mgpt_gpt_train_alloc again");
     hipStream_t s = (hipStream_t)stream;
-    // every launch below is stream-ordered and the normaliser is `rows`: the host waits for nothing
-    MGPT_HIP(hipMemsetAsync(t->loss_acc, 0, sizeof(double), s));
-    const DropCfg base = drop_cfg(p, seed, step, sites);
-    MGPT_REQUIRE(base.thr == 0 || sites == 0 || g->C % 4 == 0, MGPT_ERR_UNSUPPORTED, "dropout masks come four elements to a hash: n_embd = %d is no multiple of 4", g->C);
-    for (int r0 = 0; r0 < rows; r0 += t->max_rows) {
-        const int n = std::min(t->max_rows, rows - r0);
-        DropCfg dc = base;
-        dc.first_row = row0 + (uint64_t)r0;
-        MGPT_TRY(chunk_fwd_bwd_rows(g, t, d_tokens + (size_t)r0 * kT, n, d_labels + r0, rows, loss_scale, precision, dc, s));
-    }
-    if (d_loss) MGPT_LAUNCH(trk::loss_final_rows_kernel, dim3(1), dim3(64), 0, s, (const double *)t->loss_acc, (double)rows, d_loss);
+    // every launch is stream-ordered and the normaliser is `rows`: the host waits for nothing
+    MGPT_TRY(train_call_chunks(g, d_tokens, d_labels, rows, rows, loss_scale, precision, dc, row0, s));
+    if (d_loss) MGPT_LAUNCH(trk::loss_final_rows_kernel, dim3(1), dim3(64), 0, s, (const double *)ts(g)->loss_acc, (double)rows, d_loss);
     return MGPT_OK;
 }
 

@@ -5,9 +5,11 @@ The case list is fixed here: seeded synthetic weights and tokens.  Forward: ever
 and the one-layer variants; both precisions; small calls, large calls with and without a remainder chunk, an uneven persistent grid, the
 sequence forward and act_tokens.  Training (TRAIN_MODELS, chunks of 2 rows, targets half -1 with one row all -1): per precision the loss and
 every gradient after a one-chunk call, a call of chunks 2, 2, 1 and an accumulating call, then after an f32 call followed by a bf16 call;
-each time the total norm of clip_grad_norm_(1.0) and the state_dict() after one AdamW step.  Every (library, environment setting, model)
-runs in a fresh process, with MGPT_LIB_PATH naming the library, under its own time limit; the first process that fails ends the run.  A refactor of the host side must leave the
-two columns identical.
+each time the total norm of clip_grad_norm_(1.0) and the state_dict() after one AdamW step; then the loss and every gradient of
+forward_backward_rows, of forward_backward under config.dropout = 0.1 (all four sites, set_dropout_rng pinned, row0 = 3) and of
+forward_backward_rows_drop with the same masks, each per precision as a one-chunk call of 2 rows and a 5-row call in chunks 2, 2, 1.
+Every (library, environment setting, model) runs in a fresh process, with MGPT_LIB_PATH naming the library, under its own time limit; the
+first process that fails ends the run.  A refactor of the host side must leave the two columns identical.
 """
 import hashlib
 import os
@@ -69,6 +71,7 @@ def child_train(model):
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
+    from mapf_gpt_amd import weights
     from mapf_gpt_amd.model import build_model
 
     rng = np.random.default_rng(7)
@@ -101,6 +104,26 @@ def child_train(model):
         step(f"{precision} one chunk", [(precision, 0, 2)])
         step(f"{precision} chunks 2,2,1 then accumulate", [(precision, 0, 5), (precision, 5, 5)])
     step("f32 then bf16", [("f32", 0, 2), ("bf16", 2, 5)])
+
+    # the last-position micro-step and dropout: per call and precision a one-chunk call of 2 rows and a 5-row call in chunks 2, 2, 1 (a
+    # remainder chunk, the call's row advancing across chunks, the bf16 compact matrix padded to 32 > rows), into zeroed gradients
+    labels = torch.from_numpy(rng.integers(0, 67, size=10).astype(np.int64))     # (drawn last: the cases above keep their data)
+
+    def micro_steps(n, tag, call):
+        for precision in ("f32", "bf16"):
+            for r0, rows in ((0, 2), (2, 5)):
+                n.zero_grad()
+                loss = call(slice(r0, r0 + rows), precision)
+                digest(f"{tag} {precision} rows={rows} loss+grads", loss, *n.grads().values())
+
+    micro_steps(net, "rows", lambda r, precision: net.forward_backward_rows(tokens[r].contiguous(), labels[r], precision=precision))
+    del net, opt
+    nd = build_model(dict(weights.model_args(model), dropout=0.1), seed=3, max_rows=2)
+    nd.set_dropout_rng(11)
+    nd.train(max_rows=2)
+    drop = dict(dropout_step=4, row0=3, dropout_sites=15)         # all four sites; the masks pinned, the call's first row not row 0
+    micro_steps(nd, "dropout 0.1", lambda r, precision: nd.forward_backward(tokens[r].contiguous(), targets[r], precision=precision, **drop))
+    micro_steps(nd, "rows dropout 0.1", lambda r, precision: nd.forward_backward_rows_drop(tokens[r].contiguous(), labels[r], precision=precision, **drop))
 
 
 def run(lib_path):
