@@ -181,6 +181,7 @@ def density_sample(grid, pos, radius=DENSITY_RADIUS):
 
 class RefExpert:
     rule = None                                                   # section 22's rule, as gen() takes it (tests/expert_swap_ref.py sets it)
+    fields = None                                                 # optional: the distance fields [inst][agent] of reset()'s goals (tests/expert_shapes.py)
 
     def __init__(self, grids, n_inst, n_agents, max_episode_steps, seed=0, inst_offset=0):
         grids = np.asarray(grids)
@@ -197,7 +198,10 @@ class RefExpert:
         n_inst, n = self.n_inst, self.n_agents
         self.pos = np.asarray(pos, np.int64).reshape(n_inst, n, 2).copy()
         self.goal = np.asarray(goal, np.int64).reshape(n_inst, n, 2).copy()
-        self.dist = [[bfs(self.grid(i), self.goal[i, a]) for a in range(n)] for i in range(n_inst)]
+        if self.fields is not None:                               # precomputed for these goals and shared: the lists are copied, not the fields
+            self.dist = [list(row) for row in self.fields]
+        else:
+            self.dist = [[bfs(self.grid(i), self.goal[i, a]) for a in range(n)] for i in range(n_inst)]
         self.since = np.zeros((n_inst, n), np.int64)
         self.done = np.zeros(n_inst, np.uint8)
         self.t = 0

@@ -8,7 +8,8 @@ ONLY, written from the spec, not from the kernels.
     ref.reset(pos, goal)                   # searches, then refines
     actions, planned = ref.step()          # replays the refined solution of a final-status-1 instance, plans the others by section 20
 
-Everything here works on sets of cells; nothing is packed into words.
+Everything here works on sets of cells; nothing is packed into words -- but for refine_many(), refine() again for cases of hundreds of
+agents, which keeps a set of cells as one Python integer and is held equal to refine() on the small cases.
 """
 import numpy as np
 
@@ -102,6 +103,97 @@ def refine(grid, path, goal, max_rounds):
     return dict(path=P, length=len(P) - 1, arr=arr, soc_before=soc_before, soc_after=sum(arr), rounds=rounds, replans=replans)
 
 
+_BACK = (0, 2, 1, 4, 3)                                          # the move that undoes move k
+
+
+def refine_many(grid, path, goal, max_rounds):
+    """refine() for a case whose sets would take minutes (hundreds of agents on an open map: tests/expert_shapes.py's refine257): the
+    same rules and the same result, with a set of cells kept as one Python integer (bit r * W + c) and the others' paths kept per time
+    step and updated when a replan is adopted, where replan() forms them again for every agent.  tests/test_expert_many_cpu.py holds
+    it equal to refine() on every case of gpu_cases()."""
+    H, W = grid.shape
+    n = len(goal)
+    goal = [(int(g[0]), int(g[1])) for g in goal]
+    P = [[(int(c[0]), int(c[1])) for c in q] for q in path]
+    bit = lambda c: 1 << (c[0] * W + c[1])
+    move = lambda u, v: er.MOVES.index((v[0] - u[0], v[1] - u[1]))
+    frame = (1 << (H * W)) - 1
+    free = sum(bit((int(r), int(c))) for r, c in np.argwhere(grid == 0))
+    first_col, last_col = sum(bit((r, 0)) for r in range(H)), sum(bit((r, W - 1)) for r in range(H))
+
+    def moved(m, k):
+        """The cells u + MOVES[k] inside the frame, for the cells u of m."""
+        return (m, m >> W, (m << W) & frame, (m & ~first_col) >> 1, (m & ~last_col) << 1)[k]
+
+    # occ[t]: the cells on which an agent stands at t; went[t][k]: the cells at t of the agents that make move k between t and t + 1
+    occ = [sum(bit(c) for c in q) for q in P]
+    went = [[0] * 5 for _ in range(len(P) - 1)]
+
+    def toggle(a):                                              # takes agent a's path out of occ and went, or puts it in
+        for t in range(len(P)):
+            occ[t] ^= bit(P[t][a])
+            if t + 1 < len(P):
+                went[t][move(P[t][a], P[t + 1][a])] ^= bit(P[t][a])
+
+    for t in range(len(P) - 1):
+        for a in range(n):
+            went[t][move(P[t][a], P[t + 1][a])] |= bit(P[t][a])
+
+    def replan_a(a, arr_a):                                     # with agent a taken out: occ and went are the others'
+        g, gb = goal[a], bit(goal[a])
+        hold = max([t + 1 for t in range(len(P)) if occ[t] & gb], default=0)
+        reach, T = [bit(P[0][a])], None
+        for t in range(arr_a):
+            if t >= hold and reach[t] & gb:
+                T = t
+                break
+            nxt = 0
+            for k in range(5):                                  # u -> v = u + MOVES[k] is an exchange when the agent on v goes to u
+                nxt |= moved(reach[t], k) & ~went[t][_BACK[k]]
+            reach.append(nxt & free & ~occ[t + 1])
+        if T is None:
+            return None
+        cells, v = [g], g
+        for t in range(T, 0, -1):
+            for k, (dr, dc) in enumerate(er.MOVES):             # wait first
+                u = (v[0] - dr, v[1] - dc)
+                if 0 <= u[0] < H and 0 <= u[1] < W and reach[t - 1] & bit(u) and not went[t - 1][_BACK[k]] & bit(v):
+                    break
+            else:
+                raise AssertionError("a reached cell has no predecessor")
+            cells.append(u)
+            v = u
+        assert v == P[0][a]
+        return cells[::-1]
+
+    arr = arrivals(P, goal)
+    assert max(arr) == len(P) - 1
+    soc_before, rounds, replans = sum(arr), 0, 0
+    while rounds < max_rounds:
+        rounds += 1
+        adopted = 0
+        for a in range(n):
+            if arr[a] == 0:
+                continue
+            toggle(a)
+            new = replan_a(a, arr[a])
+            if new is not None:
+                for t in range(len(P)):
+                    P[t][a] = new[t] if t < len(new) else goal[a]
+            toggle(a)
+            if new is None:
+                continue
+            arr = arrivals(P, goal)
+            assert arr[a] == len(new) - 1
+            P = P[:max(arr) + 1]
+            del occ[len(P):], went[len(P) - 1:]
+            adopted += 1
+        replans += adopted
+        if adopted == 0:
+            break
+    return dict(path=P, length=len(P) - 1, arr=arr, soc_before=soc_before, soc_after=sum(arr), rounds=rounds, replans=replans)
+
+
 def path_actions(P):
     n, L = len(P[0]), len(P) - 1
     sol = np.zeros((n, L), np.int8)
@@ -111,14 +203,14 @@ def path_actions(P):
     return sol
 
 
-def refine_found(grid, found, goal, max_rounds, horizon, max_steps):
+def refine_found(grid, found, goal, max_rounds, horizon, max_steps, refine_fn=None):
     """Refine search()'s result `found`.  -> a dict of the same shape with the final status, length, solution and path, plus
     first_status, first_length, soc_before, soc_after, rounds, replans (all 0 but the first two for an instance that is left as it is:
     status 2 or 3, or a solution longer than the horizon)."""
     out = dict(found, first_status=found["status"], first_length=found["length"], soc_before=0, soc_after=0, rounds=0, replans=0)
     if found["status"] not in (sr.SOLVED, sr.TOO_LONG) or found["length"] > horizon:
         return out
-    r = refine(grid, found["path"], goal, max_rounds)
+    r = (refine_fn or refine)(grid, found["path"], goal, max_rounds)
     out.update(status=sr.SOLVED if r["length"] <= max_steps else sr.TOO_LONG, length=r["length"], path=r["path"],
                solution=path_actions(r["path"]), soc_before=r["soc_before"], soc_after=r["soc_after"], rounds=r["rounds"],
                replans=r["replans"])
@@ -130,6 +222,7 @@ REFINE_KEYS = ("first_status", "first_length", "soc_before", "soc_after", "round
 
 class RefRefineExpert(sw.RefSwapSearchExpert):
     """RefSwapSearchExpert whose reset() refines what the search found; step() replays by the final status."""
+    refine_fn = None                                            # refine, or refine_many where a test sets it
 
     def __init__(self, grids, n_inst, n_agents, max_episode_steps, seed=0, inst_offset=0, max_iters=4096, swap=False, max_rounds=16,
                  horizon=None):
@@ -140,7 +233,7 @@ class RefRefineExpert(sw.RefSwapSearchExpert):
         super().reset(pos, goal)
         self.first = self.found
         if self.max_rounds > 0:
-            self.found = [refine_found(self.grid(i), f, self.goal[i], self.max_rounds, self.horizon, self.max_steps)
+            self.found = [refine_found(self.grid(i), f, self.goal[i], self.max_rounds, self.horizon, self.max_steps, self.refine_fn)
                           for i, f in enumerate(self.first)]
 
     def refine_stats(self):

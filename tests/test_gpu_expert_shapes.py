@@ -21,13 +21,6 @@ pytestmark = pytest.mark.gpu
 CASES = es.shape_cases()
 
 
-def assert_not_idle(ref):
-    log, lens = ref.log()
-    moves = log != 0                                            # [inst, agent, T]; zero beyond an instance's length
-    assert (lens > 0).all() and moves.any(axis=(1, 2)).all(), "an instance never moves"
-    assert moves.any(axis=(0, 1))[:int(lens.max())].all(), "a step at which every live agent waits"
-
-
 @pytest.mark.parametrize("mode", sorted(es.MODES))
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_every_step_equals_the_restatement(name, mode):
@@ -40,7 +33,7 @@ def test_every_step_equals_the_restatement(name, mode):
         assert_search_equals(ex, ref)
     assert_every_step_equals(ex, ref, case["steps"])
     # the case is not vacuous (asserted on the restatement, which the device has just been found equal to)
-    assert_not_idle(ref)
+    es.assert_not_idle(ref)
     if name == "maze32" and m["swap"]:
         assert {"swap", "pull", "clear", "pull_decided"} <= set(ref.trace)
     if name == "frame":
